@@ -14,11 +14,21 @@ essential trees by an RCCL all-gather (nbody/sharded.py "let"; NBMI_SHARD_MODE=r
 replicated-tree exchange that is bit-identical to one GPU).  `python bench.py --gpus N` typed plainly
 starts its own N ranks.
 
-Rank 0 prints ONE JSON line.  At N = 1 it also carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, `config`).  With --full, at N = 1 the
+line also carries
+  phase_ms     - per-phase HIP-event times of a second pass of the same K steps;
   roofline     - dominant kernel (k_walk): algorithmic bytes per launch / its mean duration,
                  measured with HIP events on the library's own stream (nbmi timers);
+  frame_pcie   - the reference's per-frame call pattern timed with its device-to-host copies;
   cpu_baseline - the CPU oracle ("port" of the reference's CPU path, OpenMP, -O3 -ffast-math like
-                 Numba fastmath) timed on this host for a bounded sample of the same workload.
+                 Numba fastmath) timed on this host for a bounded sample of the same workload;
+  north_star_10m - the same measurement for BASELINE config 4's 10 M-body input (default workload);
+and the boids workload its sweep roofline, a steady_state object and its own CPU baseline.
+
+--dump-outputs DIR writes the state the timed steps leave behind (what a caller of the stepped
+simulation receives: positions, velocities, and the boids' colours) as DIR/<name>.npy in float64,
+before anything else runs; the inputs are seeded, so two builds can be compared array for array.
 """
 import argparse
 import contextlib
@@ -81,6 +91,21 @@ WORKLOADS = {
 
 
 PROFILE_ROUND = "r04"
+DUMP_BYTES = 60_000_000  # --dump-outputs: under 64 MB in all, .npy headers included
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """Write `arrays` (name -> rows x k) as out_dir/<name>.npy in float64.  Above DUMP_BYTES the same fixed, seeded
+    sample of rows is kept of every array, and its row indices go along as sample_rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(8 * (a.size // max(1, len(a))) for a in arrays.values())
+    if n * row_bytes > DUMP_BYTES:
+        rows = np.sort(np.random.default_rng(seed).choice(n, DUMP_BYTES // (row_bytes + 8), replace=False))
+        arrays = {name: a[rows] for name, a in arrays.items()}
+        arrays["sample_rows"] = rows
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def csrc_sha():
@@ -256,7 +281,8 @@ def bench_boids(args, n, dt):
     from oracle import pyref
     with contextlib.redirect_stdout(sys.stderr):
         fl = Flock(n, seed=42)
-    p0, v0, c0 = fl.positions.copy(), fl.velocities.copy(), fl.colors.copy()
+    if args.full:  # the CPU baseline starts from the same state
+        p0, v0, c0 = fl.positions.copy(), fl.velocities.copy(), fl.colors.copy()
 
     def fence():
         fl.sync()
@@ -270,6 +296,18 @@ def bench_boids(args, n, dt):
     fl.update(dt, args.steps)
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"positions": fl.positions, "velocities": fl.velocities, "colors": fl.colors})
+    info = fl.grid_info()
+    out = {"metric": "boid-steps/sec (boids sep/align/cohesion sweep)", "value": n * args.steps / elapsed,
+           "unit": "boid-steps/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+           "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
+           "vs_baseline": None, "dtype": "f64", "data": "synthetic (reference Flock ICs, seed 42)",
+           "config": {"workload": "boids_2m", "boids": n, "bounds": 500.0, "perception_radius": 5.0, "dt": dt,
+                      "grid_dim": info["grid_dim"], "num_cells": info["num_cells"]}}
+    if not args.full:
+        print(json.dumps(out), flush=True)
+        return
     fl.enable_timers(True)
     fl.timers(reset=True)
     fl.update(dt, args.steps)
@@ -293,20 +331,15 @@ def bench_boids(args, n, dt):
     compulsory = n * (96 + 76) + info["num_cells"] // 32 * 8 + info["occupied"] * 4
     ach = compulsory / (sweep_ms * 1e-3) / 1e9
     tr = pmc_traffic("boids_2m", "k_flock<true") if n == 2_000_000 else None
-    out = {"metric": "boid-steps/sec (boids sep/align/cohesion sweep)", "value": n * args.steps / elapsed,
-           "unit": "boid-steps/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-           "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
-           "vs_baseline": None, "dtype": "f64", "data": "synthetic (reference Flock ICs, seed 42)",
-           "config": {"workload": "boids_2m", "boids": n, "bounds": 500.0, "perception_radius": 5.0, "dt": dt,
-                      "grid_dim": info["grid_dim"], "num_cells": info["num_cells"]},
-           "phase_ms": {key: tm[key] / k for key in ("sort_ms", "table_ms", "sweep_ms")},
-           "roofline": {"bound": "hbm", "kernel": "k_flock", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                        "frac": ach / HBM_PEAK_GBS,
-                        "traffic": tr["bytes"] if tr else None, "traffic_from_profile": tr,
-                        "traffic_gbs": (tr["bytes"] / (sweep_ms * 1e-3) / 1e9) if tr else None,
-                        "alg_bytes_per_launch": compulsory, "model_bytes_with_candidates": alg,
-                        "model_gbs_with_candidates": model_gbs,
-                        "kernel_ms": sweep_ms, "occupied_cells": info["occupied"]}}
+    out["phase_ms"] = {key: tm[key] / k for key in ("sort_ms", "table_ms", "sweep_ms")}
+    out["roofline"] = {"bound": "hbm", "kernel": "k_flock", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                       "frac": ach / HBM_PEAK_GBS,
+                       "traffic": tr["bytes"] if tr else None, "traffic_from_profile": tr,
+                       "traffic_gbs": (tr["bytes"] / (sweep_ms * 1e-3) / 1e9) if tr else None,
+                       "alg_bytes_per_launch": compulsory, "model_bytes_with_candidates": alg,
+                       "model_gbs_with_candidates": model_gbs,
+                       "kernel_ms": sweep_ms, "occupied_cells": info["occupied"]}
+
     def candidates_per_boid():
         """mean number of candidates a boid tests: boids of the 27 cells around its own (itself included)"""
         cells = np.bincount(fl.cell_indices(), minlength=info["num_cells"]).astype(np.float64)
@@ -415,6 +448,10 @@ def bench_boids_slabs(args, n, dt, world, rank, dev):
     tmax = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
     dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     elapsed = float(tmax.item())
+    if args.dump_outputs:
+        pos, vel, col = fl.gather_state(n)  # every rank takes part
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"positions": pos, "velocities": vel, "colors": col})
     return {"metric": "boid-steps/sec (boids sep/align/cohesion sweep)", "value": n * args.steps / elapsed,
             "unit": "boid-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "strong",
@@ -520,6 +557,13 @@ def measure_nbody(args, workload, world, rank, dev, use_dist, steps, warmup, cpu
         tmax = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    if args.dump_outputs and workload == args.workload:
+        if use_dist and method == "barnes_hut" and shard_mode == "let":
+            pos, vel = sharded.gather_state()  # every rank takes part
+        else:  # one handle, or a replicated state
+            pos, vel = sim.get_positions_f64(), sim.get_velocities()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"positions": pos, "velocities": vel})
 
     par = "single GPU"
     if world > 1 or use_dist:
@@ -557,7 +601,7 @@ def measure_nbody(args, workload, world, rank, dev, use_dist, steps, warmup, cpu
                            "received_tree_rows_rank0": [int(c) for c in e.let_counts], "owned_bodies_rank0": int(sim.n),
                            # rank 0's own waves that asked for float64 forces; whether the SYSTEM-WIDE vote made every wave float64
                            "float64_wave_share_rank0": round(float(share), 4), "all_waves_float64": bool(all64)}
-    if world == 1 and rank == 0 and not use_dist:
+    if world == 1 and rank == 0 and not use_dist and args.full:
         # second pass with per-phase HIP events on the library stream (same K steps)
         sim.enable_timers(True)
         sim.timers(reset=True)
@@ -629,13 +673,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="galaxy_1m_bh", choices=sorted(WORKLOADS))
     ap.add_argument("--bodies-per-gpu", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-phase times, roofline, frame rates, CPU "
+                         "baselines, the default workload's 10 M-body object and the boids steady state")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state the timed steps leave behind as DIR/<name>.npy (float64, under 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--presteps", type=int, default=0,
                     help="boids: untimed steps before the warm-up (profiles of the state flocks reach)")
     ap.add_argument("--steady-steps", type=int, default=1000,
-                    help="boids: the line's steady_state object is measured after this many steps (0: skip)")
+                    help="boids, --full: the line's steady_state object is measured after this many steps (0: skip)")
     ap.add_argument("--skip-10m", action="store_true",
-                    help="default run only: leave out the second object (north_star's N = 10 M on this one GPU)")
+                    help="--full default run only: leave out the second object (north_star's N = 10 M on this one GPU)")
     ap.add_argument("--dt", type=float, default=None,
                     help="override the workload's step (the `4k_galaxy_1m` preset steps galaxy_1m_bh at 0.05 / 5 = 0.01)")
     ap.add_argument("--force-precision", default=None, choices=["auto", "f32", "f64"],
@@ -685,7 +734,7 @@ def main():
     # The default line times BASELINE config 2 (1 M bodies: the configuration the metric is quoted on that
     # fits the "few minutes" budget with its CPU baseline).  north_star's target is quoted at N = 10 M, which
     # also fits one GPU: the same measurement for the config-4 input rides along as a second object.
-    plain_default = (world == 1 and not use_dist and args.workload == "galaxy_1m_bh" and not args.bodies_per_gpu
+    plain_default = (args.full and world == 1 and not use_dist and args.workload == "galaxy_1m_bh" and not args.bodies_per_gpu
                      and args.theta is None and args.dt is None and not args.skip_10m and not args.force_precision)
     if plain_default:
         out["north_star_10m"] = measure_nbody(args, "collision_10m_bh", 1, 0, dev, False, min(args.steps, 10),

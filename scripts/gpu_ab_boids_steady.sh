@@ -3,13 +3,15 @@
 # alternating rounds; parity suite first
 set -u
 mkdir -p gpurun_out
+O=${OUT:-$PWD/bench_out}  # where the bench lines and their error output go
+mkdir -p "$O"
 export TMPDIR=/tmp
 timeout -k 10 600 python -m pytest tests/test_gpu_boids.py tests/test_gpu_visibility.py -m gpu -q -x -p no:cacheprovider 2>&1 | tail -n 3 || exit 1
 for rep in 1 2; do
 for lib in default ${PREV:-}; do
-  if [ "$lib" = default ]; then unset NBMI_LIB; else export NBMI_LIB=$GRAFT_REPO_ROOT/3d-spatial-sim-for-boid-and-nbody_amd/$lib; fi
-  timeout -k 10 600 python bench.py --workload boids_2m --no-cpu-baseline > gpurun_out/r4h_boids_$(basename $lib).json 2> gpurun_out/r4h_err.txt || { tail -n 20 gpurun_out/r4h_err.txt; exit 1; }
-  python3 - gpurun_out/r4h_boids_$(basename $lib).json $(basename $lib) <<'PY'
+  if [ "$lib" = default ]; then unset NBMI_LIB; else export NBMI_LIB=$PWD/3d-spatial-sim-for-boid-and-nbody_amd/$lib; fi
+  timeout -k 10 600 python bench.py --full --workload boids_2m --no-cpu-baseline > $O/boids_$(basename $lib).json 2> $O/boids_err.txt || { tail -n 20 $O/boids_err.txt; exit 1; }
+  python3 - $O/boids_$(basename $lib).json $(basename $lib) <<'PY'
 import json, sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 s=d['steady_state']

@@ -9,7 +9,7 @@ cd $R
 for rep in 1 2; do
   for lib in default "$@"; do
     if [ "$lib" = default ]; then unset NBMI_LIB; else export NBMI_LIB=$R/$lib; fi
-    timeout -k 10 300 python bench.py --no-cpu-baseline --steps 20 --warmup 3 > $O/bench_${rep}_$(basename $lib).json 2> $O/err.txt || { echo "bench failed"; tail -5 $O/err.txt; exit 1; }
+    timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps 20 --warmup 3 > $O/bench_${rep}_$(basename $lib).json 2> $O/err.txt || { echo "bench failed"; tail -5 $O/err.txt; exit 1; }
     python3 - "$O/bench_${rep}_$(basename $lib).json" "$(basename $lib)" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

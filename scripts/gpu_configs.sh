@@ -1,6 +1,7 @@
 #!/bin/bash
 # Bench lines for the other BASELINE configs (3: direct 1M, 4: collision 10M on one GPU, 5: boids 2M).
 set -u
+EXTRA="--full ${EXTRA:-}"  # the lines with their rooflines and CPU baselines
 mkdir -p gpurun_out
 for w in ${WORKLOADS:-boids_2m cluster_1m_direct collision_10m_bh}; do
   steps=10; [ "$w" = cluster_1m_direct ] && steps=3

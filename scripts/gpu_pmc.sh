@@ -1,6 +1,7 @@
 #!/bin/bash
 # rocprofv3 PMC passes over a short bench run (separate passes, kernel-trace only).
 set -u
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # the dispatches of the whole line: HIP-event pass, frame leg, 10 M object
 out=$GRAFT_REPO_ROOT/gpurun_out/pmc_${TAG:-x}
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp

@@ -6,10 +6,10 @@ ROUND=${ROUND:-rXX}
 O=$R/gpurun_out/profiles_$ROUND
 mkdir -p $O
 cd $R
-timeout -k 10 600 python bench.py > $O/${ROUND}_default_bench.json 2> gpurun_out/bench_err.txt || { tail -n 5 gpurun_out/bench_err.txt; exit 1; }
+timeout -k 10 600 python bench.py --full > $O/${ROUND}_default_bench.json 2> $O/bench_err.txt || { tail -n 5 $O/bench_err.txt; exit 1; }
 cut -c1-600 $O/${ROUND}_default_bench.json
 : > $O/${ROUND}_other_configs_bench.jsonl
-run() { timeout -k 10 600 python bench.py "$@" 2>> gpurun_out/bench_err.txt | tee -a $O/${ROUND}_other_configs_bench.jsonl | cut -c1-330; }
+run() { timeout -k 10 600 python bench.py --full "$@" 2>> $O/bench_err.txt | tee -a $O/${ROUND}_other_configs_bench.jsonl | cut -c1-330; }
 run --workload cluster_1m_direct --steps 3 --warmup 1
 run --workload boids_2m
 run --workload galaxy_10k_bh --steps 100 --warmup 10 --no-cpu-baseline

@@ -9,7 +9,7 @@ O=$R/gpurun_out/profiles_$ROUND
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 for w in galaxy_1m_bh collision_10m_bh boids_2m; do
-  X=""; [ "$w" = galaxy_1m_bh ] && X="--skip-10m"   # (the default line's nested 10 M object would mix into the 1 M averages)
+  X="--full"; [ "$w" = galaxy_1m_bh ] && X="--full --skip-10m"   # (the default line's nested 10 M object would mix into the 1 M averages)
   rm -rf $R/gpurun_out/stats_$w
   timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/stats_$w -- python3 $R/bench.py --workload $w --steps 10 --warmup 2 --no-cpu-baseline --steady-steps 0 $X > $R/gpurun_out/stats_$w.log 2>&1
   rc=$?; echo "stats $w rc=$rc"

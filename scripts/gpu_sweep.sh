@@ -7,7 +7,7 @@ mkdir -p gpurun_out
 IFS=';' read -ra SETS <<< "${SETTINGS:-NBMI_XCD_CHUNK=0}"
 for setting in "${SETS[@]}"; do
   echo "=== $setting" | tee -a gpurun_out/sweep.log
-  env $setting timeout -k 10 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline ${BENCH_ARGS:-} 2>/dev/null | python -c "
+  env $setting timeout -k 10 300 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline ${BENCH_ARGS:-} 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -9,7 +9,7 @@ NBMI_WALK_PAIR=2 timeout -k 10 900 python -m pytest tests/test_gpu_nbody.py -x -
 [ $rc -ne 0 ] && exit $rc
 for rep in 1 2; do
   for mode in 1 2; do
-    NBMI_WALK_PAIR=$mode timeout -k 10 300 python bench.py --no-cpu-baseline --steps 20 --warmup 3 > $O/bench_${rep}_$mode.json 2> $O/err.txt || { echo "bench failed"; tail -5 $O/err.txt; exit 1; }
+    NBMI_WALK_PAIR=$mode timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps 20 --warmup 3 > $O/bench_${rep}_$mode.json 2> $O/err.txt || { echo "bench failed"; tail -5 $O/err.txt; exit 1; }
     python3 - "$O/bench_${rep}_$mode.json" "$mode" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

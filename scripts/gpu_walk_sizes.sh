@@ -8,7 +8,7 @@ cd $R
 for wl in galaxy_1m_bh collision_10m_bh; do
   for nb in 1000000 2000000 4000000 10000000; do
     for mode in 1 2 3; do
-      NBMI_WALK_PAIR=$mode timeout -k 10 300 python bench.py --workload $wl --bodies-per-gpu $nb --skip-10m --no-cpu-baseline --steps 10 --warmup 2 > $O/b.json 2> $O/err.txt || { echo "bench failed"; tail -5 $O/err.txt; exit 1; }
+      NBMI_WALK_PAIR=$mode timeout -k 10 300 python bench.py --full --workload $wl --bodies-per-gpu $nb --skip-10m --no-cpu-baseline --steps 10 --warmup 2 > $O/b.json 2> $O/err.txt || { echo "bench failed"; tail -5 $O/err.txt; exit 1; }
       python3 - "$O/b.json" "$wl" "$nb" "$mode" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
