@@ -49,6 +49,13 @@ hipError_t radix_sort_pairs_u32(void *temp, size_t temp_bytes, const uint32_t *k
 hipError_t radix_init_temp(void *temp, hipStream_t s);
 hipError_t radix_error_word(const void *temp, unsigned *out, hipStream_t s);
 
+// ---- point renderer (render.hip) reads a simulation handle through these (nbmi.hip) ---------------
+}  // namespace nbmi
+struct nbmi_sim;
+namespace nbmi {
+int render_source(::nbmi_sim *s, int64_t *n, int *device);
+int render_fetch(::nbmi_sim *s, float *d_pos, float *d_col, hipEvent_t done);
+
 // One body of a key-sorted run as it travels between GPUs (multi-GPU run exchange): the two
 // octant-path key words and the fp32 {x, y, z, G*m} the octree is built from.  32 bytes.
 struct RunRec {

@@ -4715,3 +4715,34 @@ int nbmi_set_exchange_sync(nbmi_sim *s, int sync) {
 void *nbmi_stream(nbmi_sim *s) { return s ? (void *)s->stream : nullptr; }
 
 }  // extern "C"
+
+// ---- point renderer source (render.hip) ----------------------------------------------------------
+namespace nbmi {
+// Body count and device of a handle the renderer may draw (not an owner-mode handle).
+int render_source(nbmi_sim *s, int64_t *n, int *device) {
+    if (int rc = check_handle(s)) return rc;
+    if (s->owner) { nbmi::set_error("nbmi_render_sim: not available on an owner-mode handle"); return NBMI_ERR_ARG; }
+    *n = s->n;
+    *device = s->device;
+    return 0;
+}
+// The handle's current float32 positions (as nbmi_get_positions_f32) and the colours of its last
+// nbmi_compute_colors, copied in the caller's row order into the device buffers d_pos / d_col (N x 3 each) on the
+// handle's own stream; `done` is recorded behind the copies for the renderer's stream to wait on.
+int render_fetch(nbmi_sim *s, float *d_pos, float *d_col, hipEvent_t done) {
+    if (int rc = check_handle(s)) return rc;
+    const int64_t n = s->n;
+    if (n > 0) {
+        Bodies cur = s->buf[s->curbuf];
+        k_unperm3_f32<<<nblocks(n), kBlock, 0, s->stream>>>(cur.x, cur.y, cur.z, cur.id, n, d_pos);
+        NBMI_HIP_CHECK(hipGetLastError());
+        NBMI_HIP_CHECK(hipMemcpyAsync(d_col, s->colors, (size_t)n * 12, hipMemcpyDeviceToDevice, s->stream));
+    }
+    NBMI_HIP_CHECK(hipEventRecord(done, s->stream));
+    if (s->method == NBMI_METHOD_BARNES_HUT) {
+        NBMI_HIP_CHECK(hipEventSynchronize(done));
+        return check_device_error(s);
+    }
+    return 0;
+}
+}  // namespace nbmi

@@ -71,6 +71,12 @@ PROTOTYPES = {
     "nbmi_frame_delta_i16": (C.c_int, [_vp, _vp, _vp]),
     "nbmi_frame_set_previous": (C.c_int, [_vp, _vp, _vp]),
     "nbmi_debug_sort_pairs": (C.c_int, [C.c_int, _i64, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
+    "nbmi_render_create": (_vp, [C.c_int, C.c_int, C.c_int]),
+    "nbmi_render_destroy": (None, [_vp]),
+    "nbmi_render_points": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp]),
+    "nbmi_render_sim": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "nbmi_render_stats": (C.c_int, [_vp, _vp]),
+    "nbmi_render_timers": (C.c_int, [_vp, _vp]),
     "bdmi_create": (_vp, [_i64, _vp, _vp, _vp, _vp, C.c_int]),
     "bdmi_create_slab": (_vp, [_i64, _vp, _vp, _vp, _vp, _i64, _vp, _dbl, _dbl, C.c_int, C.c_int, C.c_int]),
     "bdmi_slab_count": (_i64, [_vp]),

@@ -200,6 +200,11 @@ class _HIPSimulation:
         k = int(cnt.value)
         return p[:k], c[:k]
 
+    def render(self, renderer, params=None, out=None, **camera):
+        """This handle's bodies drawn by a nbody.render.HIPPointRenderer on the device (current positions, colours of
+        the last compute_colors): uint8 (H, W, 3)."""
+        return renderer.render_sim(self, params=params, out=out, **camera)
+
     # frame codec on the device (tools/record.py: format-1 / format-2 payloads of a .zstd frame)
     def frame_keyframe(self):
         """(positions f32 (N,3), colours f32 (N,3)); they become the device's previous decoded frame."""

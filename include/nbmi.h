@@ -297,6 +297,56 @@ int nbmi_frame_set_previous(nbmi_sim *sim, const float *positions_xyz, const flo
 int nbmi_debug_sort_pairs(int key_bytes, int64_t n, const void *keys, const uint32_t *values, void *keys_out,
                           uint32_t *values_out, int bits, int impl, int repeats, double *ms_per_sort);
 
+/* ---- headless point renderer (csrc/render.hip; tools/export.py) ------------------------------------------------
+ * The image fixed-function GL draws for the exporter's frame: GL_POINTS with GL_POINT_SMOOTH, glBlendFunc(GL_SRC_ALPHA,
+ * GL_ONE), GL_DEPTH_TEST (GL_LESS, depth writes on), GL_EXP2 fog, gluLookAt + gluPerspective.  Where GL leaves the
+ * result to the implementation, one deterministic answer is fixed here; the kernels and the tests' NumPy restatement
+ * (tests/render_ref.py) both follow this text.  Arithmetic is float64 in the order written, without FMA.
+ *
+ * params (17 doubles): eye[3], target[3], up[3], fovy (degrees, reference 75), near (0.1), far (10000),
+ * point_size (in (0, 4]; reference 1.5), fog_density (>= 0; reference 0.0003, 0 = no fog), bg[3] (in [0, 1];
+ * reference (0, 0, 0.02)).  Computed once per frame on the host (C library sqrt / tan):
+ *   f = normalize(target - eye), s = normalize(f x up), u = s x f        normalize(a) = a / sqrt(a.a), each component
+ *   cot = 1 / tan(fovy * pi / 360), aspect = W / H
+ *   za = (far + near) / (near - far), zb = 2 * far * near / (near - far)  (left to right)
+ * Per point, p = the float32 position converted exactly, e = p - eye (per component), a.b = (a0 b0 + a1 b1) + a2 b2:
+ *   x_e = s.e, y_e = u.e, z_e = -(f.e)
+ *   x_c = (cot / aspect) x_e, y_c = cot y_e, z_c = za z_e + zb, w_c = -z_e
+ *   clip: the point is drawn only if |x_c| <= w_c and |y_c| <= w_c and |z_c| <= w_c (else discarded whole)
+ *   x_w = (x_c / w_c)(W / 2) + W / 2, y_w = (y_c / w_c)(H / 2) + H / 2
+ *   depth d = floor(((z_c / w_c) 0.5 + 0.5)(2^24 - 1) + 0.5)
+ *   coverage, R = point_size / 2: pixel (i, j) with floor(x_w - R) <= i <= floor(x_w + R) (same for j), inside
+ *     [0, W) x [0, H), gets c = the number of its 16 samples (i + (a + 1/2)/4, j + (b + 1/2)/4), a, b in 0..3, with
+ *     dx dx + dy dy <= R R (dx = sample x - x_w, dy likewise); a fragment exists where c >= 1
+ *   fog = exp(-(t t)), t = fog_density (-z_e);  C = clamp(colour, 0, 1) (NaN -> 0);
+ *     C' = fog C + (1 - fog) bg;  v = floor(C' 4080 + 0.5) per channel
+ * Fragments are taken in the caller's row order.  One passes iff d < 2^24 - 1 and d < the d of every earlier fragment
+ * of the same pixel (GL_LESS against a depth buffer cleared to 2^24 - 1 that every fragment leaves at its minimum).
+ * Per pixel and channel A = sum over passing fragments of c v (an exact integer), and the output is
+ *   min(255, bg8 + ((A + 128) >> 8)),  bg8 = floor(bg 255 + 0.5)
+ * as uint8 (H, W, 3) RGB with row 0 at the TOP (glReadPixels, then flipud).  Window pixel (i, j) is image row H-1-j.
+ * The image depends on draw order only through the exact depth rule: it is the same bytes on every run.  Device exp
+ * may differ from the C library's by an ulp, which can move a fogged v by one.
+ *
+ * A renderer owns one stream, its device buffers and a pinned image buffer, and is used from one host thread at a
+ * time.  Sizes up to 16384 x 16384; at most 2^27 - 1 points; a frame of more than 2^30 - 1 fragments is refused
+ * with NBMI_ERR_CAPACITY.  n == 0, or every point clipped, gives the background image. */
+typedef struct nbmi_render nbmi_render;
+/* NULL (message in nbmi_last_error) on bad size or device. */
+nbmi_render *nbmi_render_create(int width, int height, int device);
+void nbmi_render_destroy(nbmi_render *r);
+/* Host arrays (N,3) float32, caller's row order; out_rgb = W*H*3 bytes.  Uploads go through pinned staging. */
+int nbmi_render_points(nbmi_render *r, const float *positions_xyz, const float *colors_rgb, int64_t n,
+                       const double *params, uint8_t *out_rgb);
+/* The handle's current positions (as nbmi_get_positions_f32) and the colours of its last nbmi_compute_colors, read on
+ * the device.  The handle and the renderer must be on the same device; owner-mode handles are refused. */
+int nbmi_render_sim(nbmi_render *r, nbmi_sim *sim, const double *params, uint8_t *out_rgb);
+/* Of the last frame: {points drawn (centre inside the clip volume), fragments, passing fragments, pixels with at
+ * least one fragment}. */
+int nbmi_render_stats(nbmi_render *r, int64_t *out4);
+/* Device time of the last frame in ms: {project + emit, sort, resolve, pack + copy to the host}. */
+int nbmi_render_timers(nbmi_render *r, double *out_ms4);
+
 #ifdef __cplusplus
 }
 #endif
