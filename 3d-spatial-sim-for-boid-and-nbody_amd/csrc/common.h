@@ -67,6 +67,8 @@ struct RunRec {
 #define NBMI_IC_GALAXY 0
 #define NBMI_IC_COLLISION 1
 #define NBMI_IC_CLUSTER 2
+#define NBMI_IC_SPIRAL 3
+#define NBMI_IC_FILAMENT 4
 struct IcArrays {
     double *x, *y, *z, *vx, *vy, *vz, *m;
     int32_t *id;

@@ -1,10 +1,11 @@
-// Device-side initial conditions: the three distributions BASELINE.json names,
-// drawn on the GPU so that a 10 M-body start does not wait for seconds of host NumPy and a 640 MB
-// upload.  Same formulas as the reference's generate_distribution (tools/presets.py:104-232 galaxy /
-// collision via the disk helper and compute_rotation_curve :52-88, :350-397 cluster); the random
-// stream is a counter-based Philox4x32-10 (key = seed, counter = body index, draw block), so the
-// result depends only on (seed, n, R, G) - STATISTICAL parity with the NumPy generator, not bit
-// parity (tests/test_gpu_icgen.py compares the distributions).
+// Device-side initial conditions: the five distributions of tools/presets.py,
+// drawn on the GPU so that a 10-50 M-body start does not wait for seconds to minutes of host NumPy
+// and a 2.8 GB upload.  Same formulas as the reference's generate_distribution (tools/presets.py:
+// 104-232 galaxy / collision via the disk helper and compute_rotation_curve :52-88, :234-295 spiral,
+// :350-397 cluster, :609-684 filament); the random stream is a counter-based Philox4x32-10 (key =
+// seed, counter = body index, draw block, stream tag), so the result depends only on (seed, n, R, G)
+// - STATISTICAL parity with the NumPy generator, not bit parity (tests/test_gpu_icgen.py and
+// tests/test_gpu_icgen_more.py compare the distributions).
 #include <cstring>
 #include <math.h>
 
@@ -17,12 +18,17 @@ namespace {
 constexpr int kBlock = 256;
 constexpr double kTwoPi = 6.283185307179586476925286766559;
 
+// Philox stream tags (last counter word): per-body draws, and the filament node table (counter = node index)
+constexpr uint32_t kTagBodies = 0x49436e62u;  // "ICnb"
+constexpr uint32_t kTagNodes = 0x49436e6eu;   // "ICnn"
+
 struct Draws {
     uint2 key;
     uint32_t body_lo, body_hi;
+    uint32_t tag;
     // uniform double in (0,1) number `k` of this body (two 32-bit words of Philox block k/2)
     __device__ double uniform(uint32_t k) const {
-        uint32_t ctr[4] = {body_lo, body_hi, k >> 1, 0x49436e62u};  // last word: stream tag
+        uint32_t ctr[4] = {body_lo, body_hi, k >> 1, tag};
         uint32_t out[4];
         const uint32_t key2[2] = {key.x, key.y};
         philox4x32_10(ctr, key2, out);
@@ -41,20 +47,27 @@ struct Draws {
     }
 };
 
-__device__ inline Draws draws_for(uint64_t seed, int64_t body) {
+__device__ inline Draws draws_for(uint64_t seed, int64_t body, uint32_t tag = kTagBodies) {
     Draws d;
     d.key = make_uint2((uint32_t)seed, (uint32_t)(seed >> 32));
     d.body_lo = (uint32_t)body;
     d.body_hi = (uint32_t)((uint64_t)body >> 32);
+    d.tag = tag;
     return d;
 }
 
 struct DiskP {
     double R, G, scale_length, softening, max_r, height, disp, spin, x0, y0, vx_add;
     int64_t first, count;  // bodies [first, first + count) form this disk
+    // "spiral" only (0 for galaxy / collision): number of trailing log-spiral arms, and the rotation speed's floor
+    // as a fraction of sqrt(G n 0.001 / (r + softening))
+    int arms;
+    double min_speed_frac;
 };
 
-// positions of one exponential disk + the radius sort key (presets.py:110-127 / :161-178)
+// positions of one exponential disk + the radius sort key (presets.py:110-127 / :161-178).  With P.arms > 0 the
+// position angle follows the spiral's arms instead (presets.py:247-265): base -ln(r/(0.02R)+1)/0.35, a uniform arm
+// in [0, arms), N(0, 0.12 + 0.15 sqrt(r/R)) scatter; the same uniforms are used, in the same roles.
 __global__ __launch_bounds__(kBlock) void k_disk_positions(DiskP P, uint64_t seed, double *__restrict__ x,
                                                            double *__restrict__ y, double *__restrict__ z,
                                                            double *__restrict__ radius, double *__restrict__ angle,
@@ -66,9 +79,16 @@ __global__ __launch_bounds__(kBlock) void k_disk_positions(DiskP P, uint64_t see
     double r = -P.scale_length * log(d.uniform(0));          // exponential(scale_length)
     r = r * (1.0 - exp(-P.max_r / (r + 0.01)));                // soft truncation
     r = fmax(r, P.R * 0.001);
-    const double th = kTwoPi * d.uniform(1);
+    double th;
     double n0, n1;
     d.normal2(1, n0, n1);                                      // uniforms 2,3
+    if (P.arms > 0) {
+        const int arm = min((int)(d.uniform(1) * P.arms), P.arms - 1);
+        const double scatter = 0.12 + 0.15 * sqrt(r / P.R);
+        th = -log(r / (P.R * 0.02) + 1.0) / 0.35 + arm * (kTwoPi / P.arms) + n1 * scatter;
+    } else {
+        th = kTwoPi * d.uniform(1);
+    }
     const double disk_height = P.R * P.height * (1.0 + sqrt(r / P.R) * 0.3);
     double s, c;
     sincos(th, &s, &c);
@@ -97,6 +117,8 @@ __global__ __launch_bounds__(kBlock) void k_disk_velocities(DiskP P, uint64_t se
     const double eps = P.softening * 2.0, eps_sq = eps * eps, r_sq = r * r;
     double speed = sqrt(P.G * enclosed * r_sq / pow(r_sq + eps_sq, 1.5));
     speed *= fmax(r_sq / (r_sq + eps_sq), 0.3);                // inner_scale = softening*2 = eps
+    if (P.min_speed_frac > 0.0)                                // spiral: floor (presets.py:274-281)
+        speed = fmax(speed, sqrt(P.G * (double)P.count * 0.001 / (r + P.softening)) * P.min_speed_frac);
     double s, c;
     sincos(th, &s, &c);
     double ux = -speed * s * P.spin, uz = speed * c * P.spin;
@@ -146,10 +168,117 @@ __global__ __launch_bounds__(kBlock) void k_cluster(int64_t n, double R, double 
     vz[i] = v_mag * v_sin * s;
 }
 
-__global__ __launch_bounds__(kBlock) void k_fill_mass_id(int64_t n, double *__restrict__ m, int32_t *__restrict__ id) {
+// ---- filament ("cosmic web", presets.py:609-684) ----
+// Two levels: a node table drawn by one block (512 candidate nodes on an 8^3 grid over [-1.25R, 1.25R]^3, each active
+// with probability 0.35, weight power(2) = sqrt(u), an elongation axis and two perpendicular unit vectors), then one
+// thread per body picking a node through the weights' CDF and placing itself in the node's elongated Gaussian cloud.
+constexpr int kWebGrid = 8;
+constexpr int kWebNodes = kWebGrid * kWebGrid * kWebGrid;
+
+struct WebNodes {
+    int count;                     // active nodes; entries [0, count) below are valid, in grid order
+    double cdf[kWebNodes];         // normalised inclusive prefix sum of the weights, cdf[count-1] == 1
+    double c[kWebNodes][3];        // centre
+    double e[kWebNodes][3];        // elongation axis
+    double p1[kWebNodes][3], p2[kWebNodes][3];  // perpendicular unit vectors
+};
+
+__device__ inline void unit3(double v[3]) {
+    const double inv = 1.0 / (sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]) + 1e-10);
+    v[0] *= inv; v[1] *= inv; v[2] *= inv;
+}
+
+// one block of kWebNodes threads; thread j owns grid node j = (ix*8 + iy)*8 + iz, draws from stream kTagNodes
+__global__ __launch_bounds__(kWebNodes) void k_web_nodes(double R, uint64_t seed, WebNodes *__restrict__ T) {
+    __shared__ double w[kWebNodes];
+    __shared__ int slot[kWebNodes];
+    const int j = threadIdx.x;
+    const Draws d = draws_for(seed, j, kTagNodes);
+    const bool active = d.uniform(0) < 0.35;
+    w[j] = active ? sqrt(d.uniform(1)) : 0.0;                  // numpy power(2): pdf 2x on [0,1]
+    slot[j] = active;
+    __syncthreads();
+    if (j == 0) {  // 512 sequential adds: the CDF in grid order, like cumsum over the active nodes
+        int k = 0;
+        double acc = 0.0;
+        for (int i = 0; i < kWebNodes; i++) {
+            if (slot[i]) {
+                acc += w[i];
+                w[i] = acc;
+                slot[i] = k++;
+            } else {
+                slot[i] = -1;
+            }
+        }
+        T->count = k;
+        for (int i = 0; i < kWebNodes; i++)
+            if (slot[i] >= 0) T->cdf[slot[i]] = slot[i] == k - 1 ? 1.0 : w[i] / acc;
+    }
+    __syncthreads();
+    const int k = slot[j];
+    if (k < 0) return;
+    const double step = R * 2.5 / (kWebGrid - 1);
+    T->c[k][0] = -R * 1.25 + step * (j / (kWebGrid * kWebGrid));
+    T->c[k][1] = -R * 1.25 + step * ((j / kWebGrid) % kWebGrid);
+    T->c[k][2] = -R * 1.25 + step * (j % kWebGrid);
+    double e[3], p[3], t;
+    d.normal2(1, e[0], e[1]);                                  // uniforms 2..5
+    d.normal2(2, e[2], t);
+    unit3(e);
+    d.normal2(3, p[0], p[1]);                                  // uniforms 6..9
+    d.normal2(4, p[2], t);
+    const double dot = p[0] * e[0] + p[1] * e[1] + p[2] * e[2];
+    for (int a = 0; a < 3; a++) p[a] -= dot * e[a];
+    unit3(p);
+    double q[3] = {e[1] * p[2] - e[2] * p[1], e[2] * p[0] - e[0] * p[2], e[0] * p[1] - e[1] * p[0]};
+    unit3(q);
+    for (int a = 0; a < 3; a++) {
+        T->e[k][a] = e[a];
+        T->p1[k][a] = p[a];
+        T->p2[k][a] = q[a];
+    }
+}
+
+// one thread per body: node = upper bound of a uniform in the CDF (searchsorted 'right'), position = centre +
+// N(0, 0.8 s) e + N(0, 0.12 s) p1 + N(0, 0.12 s) p2 with s = 2.5R/8, velocity = 0.05 x + N(0, 0.3)
+__global__ __launch_bounds__(kBlock) void k_web_bodies(int64_t n, double R, uint64_t seed,
+                                                       const WebNodes *__restrict__ T, double *__restrict__ x,
+                                                       double *__restrict__ y, double *__restrict__ z,
+                                                       double *__restrict__ vx, double *__restrict__ vy,
+                                                       double *__restrict__ vz) {
+    __shared__ double cdf[kWebNodes];
+    const int count = T->count;
+    for (int k = threadIdx.x; k < count; k += kBlock) cdf[k] = T->cdf[k];
+    __syncthreads();
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
-    m[i] = 1.0;
+    const Draws d = draws_for(seed, i);
+    const double u = d.uniform(0);
+    int lo = 0, hi = count;                                    // first k with cdf[k] > u
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (cdf[mid] <= u) lo = mid + 1; else hi = mid;
+    }
+    const int k = min(lo, count - 1);
+    const double s = R * 2.5 / kWebGrid;
+    double a, b, c, g0, g1, g2;
+    d.normal2(1, a, b);                                        // uniforms 2..7
+    d.normal2(2, c, g0);
+    d.normal2(3, g1, g2);
+    a *= 0.8 * s; b *= 0.12 * s; c *= 0.12 * s;
+    double p[3];
+    for (int m = 0; m < 3; m++) p[m] = T->c[k][m] + a * T->e[k][m] + b * T->p1[k][m] + c * T->p2[k][m];
+    x[i] = p[0]; y[i] = p[1]; z[i] = p[2];
+    vx[i] = p[0] * 0.05 + g0 * 0.3;
+    vy[i] = p[1] * 0.05 + g1 * 0.3;
+    vz[i] = p[2] * 0.05 + g2 * 0.3;
+}
+
+__global__ __launch_bounds__(kBlock) void k_fill_mass_id(int64_t n, double mass, double *__restrict__ m,
+                                                         int32_t *__restrict__ id) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    m[i] = mass;
     id[i] = (int32_t)i;
 }
 
@@ -192,9 +321,10 @@ struct Scratch {
     uint64_t *rkey = nullptr, *rkey_s = nullptr;
     uint32_t *ridx = nullptr, *ridx_s = nullptr;
     void *tmp = nullptr;
+    WebNodes *web = nullptr;
     ~Scratch() {
         for (void *p : {(void *)radius, (void *)angle, (void *)part, (void *)rkey, (void *)rkey_s, (void *)ridx,
-                        (void *)ridx_s, tmp})
+                        (void *)ridx_s, tmp, (void *)web})
             if (p) (void)hipFree(p);
     }
 };
@@ -223,7 +353,7 @@ int ic_generate(int distribution, int64_t n, double R, double G, uint64_t seed, 
     NBMI_HIP_CHECK(hipMalloc((void **)&S.ridx_s, n * 4));
     NBMI_HIP_CHECK(hipMalloc(&S.tmp, tmp_bytes + 256));
     NBMI_HIP_CHECK(sort_init_temp(S.tmp, st));
-    k_fill_mass_id<<<nblocks(n), kBlock, 0, st>>>(n, A.m, A.id);
+    k_fill_mass_id<<<nblocks(n), kBlock, 0, st>>>(n, distribution == NBMI_IC_FILAMENT ? 0.1 : 1.0, A.m, A.id);
     bool remove_com = false;
     if (distribution == NBMI_IC_GALAXY) {  // presets.py:104-146
         DiskP P{R, G, R * 0.3, R * 0.03, R * 1.0, 0.012, 0.12, +1.0, 0.0, 0.0, 0.0, 0, n};
@@ -242,6 +372,21 @@ int ic_generate(int distribution, int64_t n, double R, double G, uint64_t seed, 
     } else if (distribution == NBMI_IC_CLUSTER) {  // presets.py:350-397
         k_cluster<<<nblocks(n), kBlock, 0, st>>>(n, R, G, seed, A.x, A.y, A.z, A.vx, A.vy, A.vz);
         remove_com = true;
+    } else if (distribution == NBMI_IC_SPIRAL) {  // presets.py:234-295: the galaxy disk on 4 arms, speed floor 0.7
+        DiskP P{R, G, R * 0.3, R * 0.03, R * 1.0, 0.012, 0.10, +1.0, 0.0, 0.0, 0.0, 0, n, 4, 0.7};
+        if (int rc = disk(P, seed, A, S, tmp_bytes, st)) return rc;
+        remove_com = true;
+    } else if (distribution == NBMI_IC_FILAMENT) {  // presets.py:609-684; no centre-of-mass correction
+        NBMI_HIP_CHECK(hipMalloc((void **)&S.web, sizeof(WebNodes)));
+        k_web_nodes<<<1, kWebNodes, 0, st>>>(R, seed, S.web);
+        int active = 0;
+        NBMI_HIP_CHECK(hipMemcpyAsync(&active, &S.web->count, sizeof(int), hipMemcpyDeviceToHost, st));
+        NBMI_HIP_CHECK(hipStreamSynchronize(st));
+        if (active == 0) {  // probability 0.65^512 ~ 1e-96; numpy's choice() raises here too
+            set_error("filament: no active grid node for seed %llu", (unsigned long long)seed);
+            return -1;
+        }
+        k_web_bodies<<<nblocks(n), kBlock, 0, st>>>(n, R, seed, S.web, A.x, A.y, A.z, A.vx, A.vy, A.vz);
     } else {
         set_error("unknown distribution %d", distribution);
         return -1;

@@ -3751,7 +3751,7 @@ nbmi_sim *nbmi_create(int64_t n, const double *pos, const double *vel, const dou
 nbmi_sim *nbmi_create_generated(int distribution, int64_t n, double spawn_radius, uint64_t seed, double G,
                                 double softening, double damping, double theta, int method, int device) {
     nbmi::clear_error();
-    if (n < 0 || n > kMaxBodies || distribution < NBMI_IC_GALAXY || distribution > NBMI_IC_CLUSTER ||
+    if (n < 0 || n > kMaxBodies || distribution < NBMI_IC_GALAXY || distribution > NBMI_IC_FILAMENT ||
         (method != NBMI_METHOD_BARNES_HUT && method != NBMI_METHOD_DIRECT) || !(softening >= 0.0) || !(theta >= 0.0) ||
         !(spawn_radius > 0.0)) {
         nbmi::set_error("nbmi_create_generated: bad arguments (n=%lld, distribution=%d)", (long long)n, distribution);

@@ -24,6 +24,9 @@ import nbmi_native as _nat
 METHOD_BARNES_HUT = 0
 METHOD_DIRECT = 1
 
+# distributions nbmi_create_generated draws on the device (NBMI_IC_* of include/nbmi.h)
+GENERATED_DISTRIBUTIONS = {"galaxy": 0, "collision": 1, "cluster": 2, "spiral": 3, "filament": 4}
+
 
 class Backend(Enum):
     HIP = "hip"                    # MI355X: Barnes-Hut (default) or direct N^2 in hand-written HIP
@@ -105,10 +108,10 @@ class _HIPSimulation:
     @classmethod
     def generated(cls, distribution, n, spawn_radius, G, softening, damping, theta=0.5, seed=42, device=None):
         """Same backend object, but the bodies are drawn ON THE DEVICE from the reference's
-        generate_distribution formulas (tools/presets.py:104-232, :350-397; `distribution` in
-        "galaxy" / "collision" / "cluster") with a Philox stream keyed by `seed`: statistical,
-        not bit, parity with the NumPy generator; no host arrays, no upload."""
-        kinds = {"galaxy": 0, "collision": 1, "cluster": 2}
+        generate_distribution formulas (tools/presets.py:104-295, :350-397, :609-684; `distribution`
+        one of GENERATED_DISTRIBUTIONS) with a Philox stream keyed by `seed`: statistical, not bit,
+        parity with the NumPy generator; no host arrays, no upload."""
+        kinds = GENERATED_DISTRIBUTIONS
         if distribution not in kinds:
             raise ValueError(f"device-side generator has {sorted(kinds)}, not {distribution!r}")
         self = cls.__new__(cls)

@@ -13,7 +13,9 @@ reproduced; ``compress_recording`` converts finished .npz frames to .zstd with t
 chaining, and ``record(config with "zstd": True)`` writes .zstd frames directly: the int16 delta
 payload is quantised ON THE DEVICE against the previous decoded frame kept in HBM (12 instead of
 24 bytes per body over PCIe), zstd runs on the host.  ``extend_recording`` is the reference's
-``--extend`` (:1156-1199); Ctrl-C leaves a state checkpoint like the reference (:916-935).  zstd comes from the system libzstd through ctypes (python-zstandard is
+``--extend`` (:1156-1199); Ctrl-C leaves a state checkpoint like the reference (:916-935).  ``main`` is the
+reference's command line (``python -m tools.record``, :1128-1283) without the interactive menu; its --help lists
+the differences.  zstd comes from the system libzstd through ctypes (python-zstandard is
 not installed in this image); without it the .zstd functions raise and raw .npz still works.
 """
 import ctypes as C
@@ -329,6 +331,8 @@ def record(config: dict, resume: bool = False, root: Path = None, quiet: bool = 
                                         config["damping"], theta=config.get("theta", 0.5), force_gpu=True)
     if gpu_sim is None:
         raise RuntimeError("[Record] create_gpu_simulation returned None")
+    if device_ic:  # the state checkpoints carry the generated masses (0.1 for "filament"), not the unit default
+        masses = gpu_sim.get_masses()
     say(f"[Record] GPU acceleration: {backend.value} - {info}")
     direct_zstd = bool(config.get("zstd"))  # extra config key: write .zstd frames, delta payload quantised on the device
     if direct_zstd and start_frame > 0:
@@ -403,3 +407,189 @@ def extend_recording(session_name: str, extra_frames: int, root: Path = None, qu
         json.dump(config, f, indent=2)
     config["session_name"] = session_name
     return record(config, resume=True, root=root, quiet=quiet)
+
+
+# ---- command line (reference :938-992, :1116-1283) ---------------------------------------------
+def _session_dir(session_name: str, root: Path = None) -> Path:
+    """get_recording_dir without creating it (a status query leaves no empty directory behind)."""
+    return Path(root or PROJECT_ROOT) / "recordings" / session_name
+
+
+def parse_number(value: str) -> int:
+    """100000, 100k, 1.5m (case-insensitive) -> int (reference :1116-1125)."""
+    value = value.strip().lower()
+    for suffix, mult in (("k", 1_000), ("m", 1_000_000)):
+        if value.endswith(suffix):
+            return int(float(value[:-1]) * mult)
+    return int(value)
+
+
+def show_status(session_name: str, root: Path = None) -> bool:
+    """Progress of one session (reference :938-961); False when it has no metadata.json."""
+    rec_dir = _session_dir(session_name, root)
+    if not (rec_dir / "metadata.json").exists():
+        print(f"[Status] No recording found: {session_name}")
+        return False
+    meta = load_metadata(rec_dir)
+    completed, total = get_completed_frames(rec_dir), meta["total_frames"]
+    print(f"\n[Status] Recording: {session_name}")
+    print(f"  Bodies: {meta['num_bodies']:,}")
+    print(f"  Theta: {meta['theta']}")
+    print(f"  Distribution: {meta.get('distribution', 'unknown')}")
+    print(f"  Progress: {completed}/{total} frames ({completed / total * 100:.1f}%)")
+    print(f"  Started: {meta.get('start_datetime', 'unknown')}")
+    if completed < total:
+        print(f"\n  To resume: python -m tools.record --resume {session_name}")
+    else:
+        print(f"\n  Complete! Export: python -m tools.export {session_name}")
+    return True
+
+
+def _sessions(root: Path = None):
+    base = Path(root or PROJECT_ROOT) / "recordings"
+    if not base.is_dir():
+        return []
+    return [d for d in base.iterdir() if d.is_dir() and (d / "metadata.json").exists()]
+
+
+def list_recordings(root: Path = None):
+    """One line per session with a metadata.json (reference :964-990)."""
+    sessions = sorted(_sessions(root), key=lambda d: d.name)
+    if not sessions:
+        print("[List] No recordings found")
+        return
+    print(f"\n[List] Found {len(sessions)} recording(s):\n")
+    for rec_dir in sessions:
+        meta = load_metadata(rec_dir)
+        completed, total = get_completed_frames(rec_dir), meta["total_frames"]
+        status = "done" if completed >= total else f"{completed / total * 100:.0f}%"
+        print(f"  {rec_dir.name:30s} | {meta['num_bodies']:>10,} bodies | {completed:>4}/{total:<4} frames | {status}")
+    print()
+
+
+def build_parser():
+    import argparse
+    ap = argparse.ArgumentParser(
+        prog="python -m tools.record",
+        description="Record an N-body preset to recordings/<session>/ on the GPU.",
+        epilog="Differences from the reference's recorder: there is no interactive menu (give --preset or "
+               "--preset-id); --preset-id indexes this build's preset list (python -m tools.record --presets shows "
+               "it); --dt sets dt_per_frame (the reference writes an unused 'dt' key); --presets, --seed, "
+               "--device-ic and --root are additions.")
+    ap.add_argument("session", nargs="?", help="session name (for --resume, --status or --extend)")
+    ap.add_argument("--resume", action="store_true", help="resume an interrupted recording (default: the most recent)")
+    ap.add_argument("--extend", type=int, metavar="FRAMES", help="extend an existing recording by N frames")
+    ap.add_argument("--status", action="store_true", help="show a session's progress (all sessions without one)")
+    ap.add_argument("--list", action="store_true", help="list all recordings")
+    ap.add_argument("--presets", action="store_true", help="list the presets with their --preset-id")
+    ap.add_argument("--preset", type=str, help="preset by name (e.g. quick_galaxy)")
+    ap.add_argument("--preset-id", type=int, help="preset by index in this build's preset list")
+    ap.add_argument("--bodies", "-n", type=str, help="override the number of bodies (100000, 100k, 1.5m)")
+    ap.add_argument("--frames", "-f", type=int, help="override the number of frames")
+    ap.add_argument("--theta", "-t", type=float, help="override the Barnes-Hut opening angle (0.3-1.5)")
+    ap.add_argument("--dt", type=float, help="override dt_per_frame (the time advanced per recorded frame)")
+    ap.add_argument("--seed", type=int, help="seed of the initial conditions (stored in metadata.json)")
+    ap.add_argument("--device-ic", action="store_true",
+                    help="draw the bodies on the GPU (statistically, not bitwise, like the host generator; "
+                         "galaxy, collision, cluster, spiral and filament)")
+    ap.add_argument("--root", type=Path, default=None, help="directory holding recordings/ (default: the package's)")
+    return ap
+
+
+def build_config(args) -> dict:
+    """Preset + overrides -> the config record() takes; no I/O, no GPU.  ValueError with a printable message."""
+    from nbody.gpu_backend import GENERATED_DISTRIBUTIONS
+    from tools.presets import get_preset_by_index, get_preset_config
+    if args.preset_id is not None:
+        key, _ = get_preset_by_index(args.preset_id)
+        if key is None:
+            raise ValueError(f"Invalid preset index: {args.preset_id}")
+        config = get_preset_config(key)
+    elif args.preset:
+        config = get_preset_config(args.preset)
+        if config is None:
+            raise ValueError(f"Unknown preset: {args.preset} (python -m tools.record --presets lists them)")
+    else:
+        raise ValueError("give --preset NAME or --preset-id N (this build has no interactive menu)")
+    if args.session:
+        config["session_name"] = args.session
+    if args.bodies:
+        try:
+            config["num_bodies"] = parse_number(args.bodies)
+        except ValueError:
+            raise ValueError(f"Invalid bodies value: {args.bodies}") from None
+        if config["num_bodies"] <= 0:
+            raise ValueError(f"Invalid bodies value: {args.bodies}")
+    if args.frames:
+        config["total_frames"] = args.frames
+    if args.theta:
+        config["theta"] = args.theta
+    if args.dt:
+        config["dt_per_frame"] = args.dt
+    if args.device_ic:
+        if config["distribution"] not in GENERATED_DISTRIBUTIONS:
+            raise ValueError(f"--device-ic: no device generator for {config['distribution']!r} "
+                             f"(have {', '.join(GENERATED_DISTRIBUTIONS)})")
+        config["device_ic"] = True
+    return config
+
+
+def main(argv=None) -> int:
+    args = build_parser().parse_args(argv)
+    root = args.root
+    if args.list:
+        list_recordings(root)
+        return 0
+    if args.presets:
+        from tools.presets import get_preset_list
+        for idx, (key, p) in enumerate(get_preset_list()):
+            print(f"  [{idx:2d}] {key:<24} {p['category']:<13} {p['distribution']:<10} {p['num_bodies']:>11,} bodies "
+                  f"| {p['total_frames']:>5} frames")
+        return 0
+    if args.status:
+        if args.session:
+            return 0 if show_status(args.session, root) else 1
+        list_recordings(root)
+        return 0
+    if args.extend:
+        if not args.session:
+            print("[Record] Error: --extend requires a session name")
+            return 2
+        if not (_session_dir(args.session, root) / "metadata.json").exists():
+            print(f"[Record] No recording found: {args.session}")
+            return 1
+        print(f"[Record] Extending '{args.session}' by {args.extend} frames")
+        extend_recording(args.session, args.extend, root=root, quiet=False)
+        return 0
+    if args.resume:
+        session = args.session
+        if session is None:
+            sessions = sorted(_sessions(root), key=lambda d: d.stat().st_mtime, reverse=True)
+            if not sessions:
+                print("[Record] No recordings found to resume")
+                return 1
+            session = sessions[0].name
+            print(f"[Record] Resuming most recent: {session}")
+        rec_dir = _session_dir(session, root)
+        if not (rec_dir / "metadata.json").exists():
+            print(f"[Record] No metadata found for session: {session}")
+            return 1
+        config = load_metadata(rec_dir)
+        config["session_name"] = session
+        record(config, resume=True, root=root)
+        return 0
+    try:
+        config = build_config(args)
+    except ValueError as e:
+        print(f"[Record] {e}")
+        return 2
+    print(f"[Record] Preset {config['name']!r}: {config['num_bodies']:,} bodies ({config['distribution']}), "
+          f"{config['total_frames']} frames, theta {config['theta']}, dt_per_frame {config['dt_per_frame']}"
+          + (", generated on the device" if config.get("device_ic") else ""))
+    record(config, resume=False, root=root, seed=args.seed)
+    return 0
+
+
+if __name__ == "__main__":
+    import sys
+    sys.exit(main())

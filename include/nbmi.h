@@ -51,14 +51,18 @@ nbmi_sim *nbmi_create(int64_t n, const double *positions_xyz, const double *velo
 
 /* Constructor with DEVICE-SIDE initial conditions: the bodies are drawn on the
  * GPU from generate_distribution's formulas (tools/presets.py:104-232 "galaxy" / "collision",
- * :350-397 "cluster"; unit masses) with a counter-based Philox4x32-10 stream keyed by `seed`, so a
- * 10 M-body start needs no host generator and no 640 MB upload.  Statistical, not bit, parity with
- * the NumPy generator; the same (seed, n, radius, G) always gives the same bodies.  G is used both
- * for the rotation curve / dispersions and for the simulation, as record() does
- * (tools/record.py:747-758).  Body i of the getters is the i-th generated body. */
+ * :234-295 "spiral", :350-397 "cluster": unit masses; :609-684 "filament", the cosmic web: masses
+ * 0.1) with a counter-based Philox4x32-10 stream keyed by `seed`, so a 10-50 M-body start needs no
+ * host generator and no multi-GB upload.  Statistical, not bit, parity with the NumPy generator;
+ * the same (seed, n, radius, G) always gives the same bodies.  G is used both for the rotation
+ * curve / dispersions and for the simulation, as record() does (tools/record.py:747-758).  Body i
+ * of the getters is the i-th generated body.  "filament" fails (NULL) in the ~1e-96 case that none
+ * of its 512 grid nodes is active, as the reference does. */
 #define NBMI_IC_GALAXY 0
 #define NBMI_IC_COLLISION 1
 #define NBMI_IC_CLUSTER 2
+#define NBMI_IC_SPIRAL 3
+#define NBMI_IC_FILAMENT 4
 nbmi_sim *nbmi_create_generated(int distribution, int64_t n, double spawn_radius, uint64_t seed, double G,
                                 double softening, double damping, double theta, int method, int device);
 /* The generator's random function, computed on the host (known-answer tests). */
