@@ -91,3 +91,19 @@ def test_radix_sort_at_bench_sizes_and_timing(gpu, n):
     kr, vr, ms_lib = _sort(nat, cells, vals, 24, 1, repeats=10)
     assert np.array_equal(ko, kr) and np.array_equal(vo, vr)
     print(f"n={n}: 24-bit cell indices, own radix sort {ms_own:.3f} ms, rocPRIM {ms_lib:.3f} ms")
+
+
+@pytest.mark.parametrize("n", [65_536, 65_537, 524_288, 524_289])
+def test_radix_sort_at_tile_size_switches(gpu, n):
+    """Pairs per thread change at n = 65 536 (4 -> 8) and 524 288 (8 -> 16): both sides of each switch."""
+    import nbmi_native as nat
+    rng = np.random.default_rng(n)
+    for dtype, bits in ((np.uint64, 63), (np.uint32, 24), (np.uint32, 31)):
+        for name, keys in _cases(rng, n, dtype, bits):
+            vals = rng.permutation(n).astype(np.uint32)
+            ko, vo, _ = _sort(nat, keys, vals, bits, 0)
+            order = np.argsort(keys, kind="stable")
+            assert np.array_equal(ko, keys[order]), (name, dtype, bits)
+            assert np.array_equal(vo, vals[order]), (name, dtype, bits)
+            kr, vr, _ = _sort(nat, keys, vals, bits, 1)
+            assert np.array_equal(ko, kr) and np.array_equal(vo, vr), (name, dtype, bits)
