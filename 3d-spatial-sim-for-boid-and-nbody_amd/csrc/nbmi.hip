@@ -764,7 +764,14 @@ __global__ __launch_bounds__(kBlock) void k_emit_tile(const int32_t *__restrict_
                 lf.s2t = 0.0f;
                 lf.next_off = (unsigned)(idx + 1 + link_base) * kNodeBytes;
                 nodes[idx] = lf;
-                if (diag64) diag64[idx] = p64_s ? p64_s[r] : make_double4((double)p.x, (double)p.y, (double)p.z, (double)p.w);
+                if (diag64) {  // the body as the float64 state has it (p64_s holds the same values where it exists)
+                    if (p64_s) {
+                        diag64[idx] = p64_s[r];
+                    } else {
+                        const uint32_t j = perm[r];
+                        diag64[idx] = make_double4(cur.x[j], cur.y[j], cur.z[j], G * cur.m[j]);
+                    }
+                }
                 if (nodesd) {  // the body as the float64 state has it (nearly sequential: the state is in last step's key order)
                     const uint32_t j = perm[r];
                     nodesd[idx] = NodeD{cur.x[j], cur.y[j], cur.z[j], G * cur.m[j], 0.0f, (unsigned)(idx + 1 + link_base) * kNodeDBytes};
@@ -3117,6 +3124,188 @@ __global__ void k_copy_ids(const int32_t *__restrict__ ids, int32_t *__restrict_
     if (i < n) dst[i] = ids[i];
 }
 
+// ---------------------------------------------------------------------------------------
+// K14: conservation diagnostics (nbmi_diagnostics / nbmi_get_potentials_f64; include/nbmi.h).
+// Float64 throughout; every sum has a fixed order (no floating-point atomics), so two calls on one state agree bit
+// for bit.
+// ---------------------------------------------------------------------------------------
+// Tree potential.  The walk of K9 in its C++ form, one wave per 64 key-adjacent bodies, one wave-uniform cursor over
+// the same pre-order array and skip links, and per lane the same opening decision as visit(): the fp32 test on the
+// Node record, re-decided in float64 through Node64 (exact_take) where d^2 falls inside the uncertainty band.  A lane's
+// accepted set does not depend on the other lanes of its wave (it takes part in every node none of its own accepted
+// ancestors covers), so it is the force walk's set.  What differs is the term: the node's float64 row pot[idx] =
+// {cx, cy, cz, G M} (written by k_emit_tile into the diag64 slot for this build only: a cell's double-double moments,
+// a leaf's body as the float64 state has it), and the reference's guard (simulation.py:260) on the float64 dist_sq.
+// The own leaf has d = 0 exactly, so the guard skips it as the reference's explicit test does.  phi and the number of
+// applied terms land at the body's state row j = perm[rank].
+__global__ __launch_bounds__(kBlock) void k_potential_tree(const Node *__restrict__ nodes, const double4 *__restrict__ pot,
+                                                           const WalkTable *tab, const TreeInfo *info,
+                                                           const float4 *__restrict__ posm_s, const uint32_t *__restrict__ perm,
+                                                           int curbuf, float eps2f, int64_t n, double *__restrict__ phi,
+                                                           int32_t *__restrict__ cnt) {
+    if (info->error != 0 || info->sticky_error != 0) return;  // the tree did not fit: the caller reports it
+    const int64_t rank = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const bool valid = rank < n;
+    const unsigned nn = __builtin_amdgcn_readfirstlane((unsigned)info->num_nodes * kNodeBytes);
+    const unsigned band2 = __builtin_amdgcn_readfirstlane(info->band2);
+    const double eps2 = tab->eps2;
+    float px = 0.f, py = 0.f, pz = 0.f;
+    double qx = 0.0, qy = 0.0, qz = 0.0;
+    uint32_t j = 0;
+    if (valid) {
+        const float4 p = posm_s[rank];
+        px = p.x; py = p.y; pz = p.z;
+        j = perm[rank];
+        const Bodies &cur = tab->buf[curbuf];
+        qx = cur.x[j]; qy = cur.y[j]; qz = cur.z[j];
+    }
+    const Body64 b64{tab, curbuf, j};
+    unsigned resume = valid ? 0u : 0xffffffffu;
+    double acc = 0.0;
+    int32_t terms = 0;
+    unsigned off = 0u;
+    while (off < nn) {
+        off = __builtin_amdgcn_readfirstlane(off);
+        const unsigned idx = off / kNodeBytes;
+        const Node nd = nodes[idx];
+        // visit(): the same fp32 operations in the same order
+        const float dx = nd.cx - px, dy = nd.cy - py, dz = nd.cz - pz;
+        const float dist_sq = fmaf(dz, dz, fmaf(dy, dy, fmaf(dx, dx, eps2f)));
+        const bool active = resume <= off;
+        const int d2b = __float_as_int(dist_sq), hi = __float_as_int(nd.s2t), lo = hi - (int)band2;
+        bool geom = hi < d2b;
+        const bool band = active && !geom && lo < d2b;
+        if (band) geom = (hi == 0) || exact_take_idx(idx, b64);
+        const bool take = active && geom;
+        if (take) {
+            const double4 q = pot[idx];
+            const double ex = q.x - qx, ey = q.y - qy, ez = q.z - qz;
+            const double d2 = ex * ex + ey * ey + ez * ez + eps2;  // (-ffp-contract=off: the reference's roundings)
+            if (q.w > 0.0 && d2 > eps2) {
+                acc -= q.w / sqrt(d2);
+                terms++;
+            }
+            resume = nd.next_off;
+        }
+        const unsigned long long any_open = __builtin_amdgcn_ballot_w64(active && !geom);
+        off = any_open ? off + kNodeBytes : nd.next_off;
+    }
+    if (valid) {
+        phi[j] = acc;
+        cnt[j] = terms;
+    }
+}
+
+// Direct potential: phi_i = -sum_{j != i} G m_j / sqrt(|x_j - x_i|^2 + eps^2), float64 bodies staged through LDS
+// tiles of kBlock, every thread one body, j in index order.  eps == 0: pairs at zero distance are skipped (k_direct's
+// guard).
+__global__ __launch_bounds__(kBlock) void k_potential_direct(Bodies cur, int64_t n, double G, double eps2,
+                                                             double *__restrict__ phi, int32_t *__restrict__ cnt) {
+    __shared__ double4 tile[kBlock];
+    const int t = threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * kBlock + t;
+    const bool valid = i < n;
+    double x = 0.0, y = 0.0, z = 0.0;
+    if (valid) { x = cur.x[i]; y = cur.y[i]; z = cur.z[i]; }
+    double acc = 0.0;
+    int32_t terms = 0;
+    for (int64_t base = 0; base < n; base += kBlock) {
+        const int64_t jj = base + t;
+        tile[t] = jj < n ? make_double4(cur.x[jj], cur.y[jj], cur.z[jj], G * cur.m[jj]) : make_double4(0.0, 0.0, 0.0, 0.0);
+        __syncthreads();
+        const int lim = n - base < kBlock ? (int)(n - base) : kBlock;
+        const int self = (int)(i - base);  // this body's slot in the tile (outside [0, lim) when it is not in it)
+        for (int k = 0; k < lim; k++) {
+            const double4 q = tile[k];
+            const double ex = q.x - x, ey = q.y - y, ez = q.z - z;
+            const double d2 = ex * ex + ey * ey + ez * ez + eps2;
+            if (k != self && d2 > 0.0) {
+                acc -= q.w / sqrt(d2);
+                terms++;
+            }
+        }
+        __syncthreads();
+    }
+    if (valid) {
+        phi[i] = acc;
+        cnt[i] = terms;
+    }
+}
+
+// Body sums, in the order of the state rows: per block a contiguous range of rows, per thread a strided part of it,
+// then a fixed tree over the block's threads.  Sums: m, m x (3), m v (3), m x X v (3), m |v|^2, m phi; and the
+// applied terms as an integer.
+constexpr int kDiagSums = 12;
+constexpr int kDiagBlocksMax = 1024;
+__device__ __forceinline__ void diag_block_sum(double (*sh)[kBlock], long long *shc, double *v, long long c,
+                                               double *__restrict__ out, long long *__restrict__ outc) {
+    const int t = threadIdx.x;
+    for (int k = 0; k < kDiagSums; k++) sh[k][t] = v[k];
+    shc[t] = c;
+    __syncthreads();
+    for (int w = kBlock / 2; w > 0; w >>= 1) {
+        if (t < w) {
+            for (int k = 0; k < kDiagSums; k++) sh[k][t] += sh[k][t + w];
+            shc[t] += shc[t + w];
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        for (int k = 0; k < kDiagSums; k++) out[k] = sh[k][0];
+        *outc = shc[0];
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_diag_partial(Bodies cur, const double *__restrict__ phi,
+                                                         const int32_t *__restrict__ cnt, int64_t n, int64_t per_block,
+                                                         double *__restrict__ part, long long *__restrict__ partc) {
+    __shared__ double sh[kDiagSums][kBlock];
+    __shared__ long long shc[kBlock];
+    double v[kDiagSums];
+    for (int k = 0; k < kDiagSums; k++) v[k] = 0.0;
+    long long c = 0;
+    const int64_t b0 = (int64_t)blockIdx.x * per_block;
+    const int64_t b1 = b0 + per_block < n ? b0 + per_block : n;
+    for (int64_t i = b0 + threadIdx.x; i < b1; i += kBlock) {
+        const double m = cur.m[i], x = cur.x[i], y = cur.y[i], z = cur.z[i];
+        const double vx = cur.vx[i], vy = cur.vy[i], vz = cur.vz[i];
+        v[0] += m;
+        v[1] += m * x; v[2] += m * y; v[3] += m * z;
+        v[4] += m * vx; v[5] += m * vy; v[6] += m * vz;
+        v[7] += m * (y * vz - z * vy);
+        v[8] += m * (z * vx - x * vz);
+        v[9] += m * (x * vy - y * vx);
+        v[10] += m * (vx * vx + vy * vy + vz * vz);
+        if (phi) {
+            v[11] += m * phi[i];
+            c += cnt[i];
+        }
+    }
+    diag_block_sum(sh, shc, v, c, part + (int64_t)blockIdx.x * kDiagSums, partc + blockIdx.x);
+}
+
+// one block: the partial sums of k_diag_partial's `nb` blocks, in block order per thread, then the same tree
+__global__ __launch_bounds__(kBlock) void k_diag_final(const double *__restrict__ part, const long long *__restrict__ partc,
+                                                       int nb, double *__restrict__ out, long long *__restrict__ outc) {
+    __shared__ double sh[kDiagSums][kBlock];
+    __shared__ long long shc[kBlock];
+    double v[kDiagSums];
+    for (int k = 0; k < kDiagSums; k++) v[k] = 0.0;
+    long long c = 0;
+    for (int b = threadIdx.x; b < nb; b += kBlock) {
+        for (int k = 0; k < kDiagSums; k++) v[k] += part[(int64_t)b * kDiagSums + k];
+        c += partc[b];
+    }
+    diag_block_sum(sh, shc, v, c, out, outc);
+}
+
+// phi from state rows to the caller's order (id: state row -> caller index)
+__global__ __launch_bounds__(kBlock) void k_unperm1_f64(const double *__restrict__ a, const int32_t *__restrict__ id, int64_t n,
+                                                        double *__restrict__ out) {
+    const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (r < n) out[id[r]] = a[r];
+}
+
 }  // namespace
 
 // =========================================================================================
@@ -3227,6 +3416,13 @@ struct nbmi_sim {
     int prec = 0;       // measurement: k_walk_diag arithmetic mode (NBMI_PREC), 0 = product walk
     double prec_near = 4.0;  // NBMI_PREC_NEAR: "near" = closer than this many softening lengths
     double4 *diag64 = nullptr;  // float64 {cx, cy, cz, G m} of every node (only with NBMI_PREC)
+    // conservation diagnostics (nbmi_diagnostics), allocated by the first call that needs them; no step touches them
+    double *diag_phi = nullptr;       // [n] phi per state row
+    int32_t *diag_cnt = nullptr;      // [n] applied potential terms per state row
+    double *diag_part = nullptr;      // [kDiagBlocksMax * kDiagSums + kDiagSums] block partials, then the totals
+    long long *diag_partc = nullptr;  // [kDiagBlocksMax + 1] the same for the term counts
+    double4 *diag_pot = nullptr;      // [node rows] float64 {cx, cy, cz, G m} of every node of the diagnostic's own build
+    TreeInfo *diag_info = nullptr;    // the tree header as the last step left it, put back after the diagnostic's build
     // one-wave walk: cursors per wave and where the array is cut.  -1 = by size: two cursors, cut at the middle of the
     // array, or (from kHomeSplitBodies = 1.5 M bodies on) at the leaf of the wave's middle body; NBMI_WALK_PAIR = 0 / 1 / 2 forces
     // one cursor / the middle cut / the home cut
@@ -3360,7 +3556,9 @@ int enqueue_local_sort(nbmi_sim *s, int ev_base, int64_t n_sort = -1, int64_t n_
 }
 
 // aux: also write node_ref / node_level (cell queries, owner-mode kernels)
-int enqueue_global_tree(nbmi_sim *s, bool aux = true) {
+// diag: where the float64 {cx, cy, cz, G m} row of every node goes (nbmi_diagnostics' tree potential; null: s->diag64,
+// which is null outside the NBMI_PREC measurement mode - a step never writes it)
+int enqueue_global_tree(nbmi_sim *s, bool aux = true, double4 *diag = nullptr) {
     const int64_t n = s->nt;
     hipStream_t st = s->stream;
     // (delta, the in-sub-tile prefixes S / PexL and the sub-tile totals: written by k_gather_scan)
@@ -3374,7 +3572,8 @@ int enqueue_global_tree(nbmi_sim *s, bool aux = true) {
         const int tile = n <= kEmitSmallBodies ? kEmitTileSmall : kEmitTile;
 #define NBMI_EMIT(TV) k_emit_tile<TV><<<(int)((n + TV - 1) / TV), kBlock, 0, st>>>(                                         \
         s->delta, s->Pex, s->subPex, s->S, s->T, s->t_posm, s->p64_s, s->t_hi, s->t_lo, n, s->own_node_rows, s->softening,       \
-        inv_theta2, s->nodes + ob, s->nodes64 + ob, aux ? s->node_level : nullptr, aux ? s->node_ref : nullptr, s->diag64,   \
+        inv_theta2, s->nodes + ob, s->nodes64 + ob, aux ? s->node_level : nullptr, aux ? s->node_ref : nullptr,              \
+        diag ? diag : s->diag64,                                                                                            \
         s->force_prec != 1 && s->nodesd ? s->nodesd + ob : nullptr, s->buf[s->curbuf], s->perm, s->G, s->info, ob)
         if (tile == kEmitTileSmall) NBMI_EMIT(kEmitTileSmall);
         else NBMI_EMIT(kEmitTile);
@@ -3387,7 +3586,7 @@ int enqueue_global_tree(nbmi_sim *s, bool aux = true) {
 }
 
 // Single-GPU build: the tree over the handle's own bodies.
-int enqueue_tree(nbmi_sim *s, int ev_base, bool aux = true) {
+int enqueue_tree(nbmi_sim *s, int ev_base, bool aux = true, double4 *diag = nullptr) {
     if (s->owner) {
         nbmi::set_error("this handle is in owner mode: use the nbmi_owner_* calls");
         return NBMI_ERR_ARG;
@@ -3395,7 +3594,7 @@ int enqueue_tree(nbmi_sim *s, int ev_base, bool aux = true) {
     if (ev_base >= 0) NBMI_HIP_CHECK(hipEventRecord(s->ev[0], s->stream));
     if (int rc = enqueue_maxabs(s)) return rc;
     if (int rc = enqueue_local_sort(s, ev_base)) return rc;
-    if (int rc = enqueue_global_tree(s, aux)) return rc;
+    if (int rc = enqueue_global_tree(s, aux, diag)) return rc;
     if (ev_base >= 0) NBMI_HIP_CHECK(hipEventRecord(s->ev[3], s->stream));
     s->tree_valid = aux;
     return 0;
@@ -3960,6 +4159,122 @@ int nbmi_get_accelerations_f64(nbmi_sim *s, double *out) {
     NBMI_HIP_CHECK(hipMemcpyAsync(out, acc, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
     if (s->method == NBMI_METHOD_BARNES_HUT) return check_device_error(s);
+    return 0;
+}
+
+namespace {
+// phi and the applied-term counts per state row (diag_phi / diag_cnt).  Barnes-Hut: the octree of the current positions
+// as nbmi_get_accelerations_f64 builds it, with the float64 node rows, then the potential walk.  The build overwrites the
+// tree header (maxabs_next, force_all64, ...) and the host-side flags; both are put back, so the next step finds the
+// handle as it would have without this call.
+int diag_potential(nbmi_sim *s) {
+    const int64_t n = s->n;
+    if (!s->diag_phi && (dev_alloc(s, &s->diag_phi, n) || dev_alloc(s, &s->diag_cnt, n))) return NBMI_ERR_HIP;
+    hipStream_t st = s->stream;
+    if (s->method != NBMI_METHOD_BARNES_HUT) {
+        k_potential_direct<<<nblocks(n), kBlock, 0, st>>>(s->buf[s->curbuf], n, s->G, s->softening * s->softening, s->diag_phi,
+                                                           s->diag_cnt);
+        NBMI_HIP_CHECK(hipGetLastError());
+        return 0;
+    }
+    if (!s->diag_pot && (dev_alloc(s, &s->diag_pot, s->node_capacity + 2) || dev_alloc(s, &s->diag_info, 1))) return NBMI_ERR_HIP;
+    // a capacity error of an earlier step is reported first, as a getter does
+    NBMI_HIP_CHECK(hipStreamSynchronize(st));
+    if (int rc = check_device_error(s)) return rc;
+    NBMI_HIP_CHECK(hipMemcpyAsync(s->diag_info, s->info, sizeof(TreeInfo), hipMemcpyDeviceToDevice, st));
+    const bool tree_valid = s->tree_valid, maxabs_fused = s->maxabs_fused;
+    const int sort_bits = s->sort_bits;
+    const double step_dt = s->step_dt;
+    s->step_dt = 0.0;  // no "auto" decision: the wave flags and force_all64 stay the last step's
+    int rc = enqueue_tree(s, -1, false, s->diag_pot);
+    if (rc == 0) {
+        k_potential_tree<<<nblocks(n), kBlock, 0, st>>>(s->nodes, s->diag_pot, s->wtab, s->info, s->posm_s, s->perm, s->curbuf,
+                                                        (float)(s->softening * s->softening), n, s->diag_phi, s->diag_cnt);
+        if (hipGetLastError() != hipSuccess) {
+            nbmi::set_error("k_potential_tree launch failed");
+            rc = NBMI_ERR_HIP;
+        }
+    }
+    if (rc == 0) {
+        NBMI_HIP_CHECK(hipStreamSynchronize(st));
+        rc = check_device_error(s);  // NBMI_ERR_CAPACITY: the message of a step
+    }
+    // the same positions give the same tree: what the queries read is still that tree if it was before
+    NBMI_HIP_CHECK(hipMemcpyAsync(s->info, s->diag_info, sizeof(TreeInfo), hipMemcpyDeviceToDevice, st));
+    NBMI_HIP_CHECK(hipStreamSynchronize(st));
+    s->tree_valid = tree_valid && rc == 0;
+    s->maxabs_fused = maxabs_fused;
+    s->sort_bits = sort_bits;
+    s->step_dt = step_dt;
+    return rc;
+}
+
+int diag_refuse(nbmi_sim *s, const char *what) {
+    if (s->owner) {
+        nbmi::set_error("%s: owner-mode handles are not supported (the potential needs the other ranks' trees)", what);
+        return NBMI_ERR_ARG;
+    }
+    if (s->shard_begin != 0 || s->shard_end != s->n) {
+        nbmi::set_error("%s: sharded handles are not supported", what);
+        return NBMI_ERR_ARG;
+    }
+    return 0;
+}
+}  // namespace
+
+int nbmi_diagnostics(nbmi_sim *s, int with_potential, double *out12, int64_t *terms) {
+    if (int rc = check_handle(s)) return rc;
+    if (int rc = diag_refuse(s, "nbmi_diagnostics")) return rc;
+    if (!out12) { nbmi::set_error("null output"); return NBMI_ERR_ARG; }
+    const int64_t n = s->n;
+    if (n == 0) {
+        for (int k = 0; k < 12; k++) out12[k] = 0.0;
+        if (!with_potential) out12[11] = NAN;
+        if (terms) *terms = 0;
+        return 0;
+    }
+    if (with_potential) {
+        if (int rc = diag_potential(s)) return rc;
+    }
+    if (!s->diag_part && (dev_alloc(s, &s->diag_part, (size_t)(kDiagBlocksMax + 1) * kDiagSums) ||
+                          dev_alloc(s, &s->diag_partc, kDiagBlocksMax + 1)))
+        return NBMI_ERR_HIP;
+    hipStream_t st = s->stream;
+    const int64_t want = (n + 4 * kBlock - 1) / (4 * kBlock);  // at least 1 024 rows per block
+    const int nb = (int)(want < kDiagBlocksMax ? want : kDiagBlocksMax);
+    const int64_t per_block = (n + nb - 1) / nb;
+    double *tot = s->diag_part + (size_t)kDiagBlocksMax * kDiagSums;
+    long long *totc = s->diag_partc + kDiagBlocksMax;
+    k_diag_partial<<<nb, kBlock, 0, st>>>(s->buf[s->curbuf], with_potential ? s->diag_phi : nullptr, s->diag_cnt, n, per_block,
+                                          s->diag_part, s->diag_partc);
+    k_diag_final<<<1, kBlock, 0, st>>>(s->diag_part, s->diag_partc, nb, tot, totc);
+    NBMI_HIP_CHECK(hipGetLastError());
+    double h[kDiagSums];
+    long long hc = 0;
+    NBMI_HIP_CHECK(hipMemcpyAsync(h, tot, sizeof(h), hipMemcpyDeviceToHost, st));
+    NBMI_HIP_CHECK(hipMemcpyAsync(&hc, totc, sizeof(hc), hipMemcpyDeviceToHost, st));
+    NBMI_HIP_CHECK(hipStreamSynchronize(st));
+    const double M = h[0];
+    out12[0] = M;
+    for (int k = 0; k < 3; k++) out12[1 + k] = M != 0.0 ? h[1 + k] / M : 0.0;
+    for (int k = 0; k < 6; k++) out12[4 + k] = h[4 + k];
+    out12[10] = 0.5 * h[10];
+    out12[11] = with_potential ? 0.5 * h[11] : NAN;
+    if (terms) *terms = with_potential ? (int64_t)hc : 0;
+    return 0;
+}
+
+int nbmi_get_potentials_f64(nbmi_sim *s, double *out) {
+    if (int rc = check_handle(s)) return rc;
+    if (int rc = diag_refuse(s, "nbmi_get_potentials_f64")) return rc;
+    const int64_t n = s->n;
+    if (n == 0) return 0;
+    if (!out) { nbmi::set_error("null output"); return NBMI_ERR_ARG; }
+    if (int rc = diag_potential(s)) return rc;
+    k_unperm1_f64<<<nblocks(n), kBlock, 0, s->stream>>>(s->diag_phi, s->buf[s->curbuf].id, n, (double *)s->stage);
+    NBMI_HIP_CHECK(hipGetLastError());
+    NBMI_HIP_CHECK(hipMemcpyAsync(out, s->stage, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
     return 0;
 }
 

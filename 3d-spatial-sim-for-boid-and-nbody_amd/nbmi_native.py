@@ -43,6 +43,8 @@ PROTOTYPES = {
     "nbmi_enable_timers": (C.c_int, [_vp, C.c_int]),
     "nbmi_get_timers": (C.c_int, [_vp, _vp, _vp, C.c_int]),
     "nbmi_walk_counters": (C.c_int, [_vp, _vp]),
+    "nbmi_diagnostics": (C.c_int, [_vp, C.c_int, _vp, _vp]),
+    "nbmi_get_potentials_f64": (C.c_int, [_vp, _vp]),
     "nbmi_set_shard": (C.c_int, [_vp, _i64, _i64]),
     "nbmi_export_shard": (C.c_int, [_vp, _vp]),
     "nbmi_import_ranks": (C.c_int, [_vp, _vp, _i64, _i64]),

@@ -14,6 +14,7 @@ callers (NBodySimulation, record) raise on ``None``.
 """
 import ctypes as C
 import os
+from dataclasses import dataclass
 from enum import Enum
 from typing import Optional, Tuple
 
@@ -78,6 +79,21 @@ def _as_f64(a, shape_tail):
     if a.shape[1:] != shape_tail:
         raise ValueError(f"expected array of shape (N,{','.join(map(str, shape_tail))}), got {a.shape}")
     return a
+
+
+@dataclass(frozen=True)
+class Diagnostics:
+    """Conserved quantities of a handle's current float64 state (include/nbmi.h, nbmi_diagnostics).
+    ``potential`` (W) and ``total`` (E = K + W) are None when the potential was not asked for; ``terms`` is the number
+    of (body, node) terms applied to it (0 then)."""
+    mass: float
+    center_of_mass: Tuple[float, float, float]
+    momentum: Tuple[float, float, float]
+    angular_momentum: Tuple[float, float, float]
+    kinetic: float
+    potential: Optional[float]
+    total: Optional[float]
+    terms: int
 
 
 class _HIPSimulation:
@@ -184,6 +200,27 @@ class _HIPSimulation:
         """Accelerations of the current positions (force pass only, no integration)."""
         out = np.empty((self.n, 3), dtype=np.float64)
         _nat.check(self._lib.nbmi_get_accelerations_f64(self._h, _nat.ptr(out)), "nbmi_get_accelerations_f64")
+        return out
+
+    def diagnostics(self, potential=True) -> Diagnostics:
+        """Mass, centre of mass, momentum, angular momentum (about the origin), kinetic and - with ``potential`` -
+        potential and total energy of the current state, computed on the device in float64 (deterministic: the same
+        state gives the same bits).  Barnes-Hut handles: the tree potential over the force walk's own accepted terms;
+        direct handles: the exact pair sum.  The call does not change what the next step computes."""
+        out = np.empty(12, dtype=np.float64)
+        terms = C.c_int64(0)
+        _nat.check(self._lib.nbmi_diagnostics(self._h, 1 if potential else 0, _nat.ptr(out), C.addressof(terms)),
+                   "nbmi_diagnostics")
+        w = float(out[11]) if potential else None
+        k = float(out[10])
+        return Diagnostics(mass=float(out[0]), center_of_mass=tuple(float(x) for x in out[1:4]),
+                           momentum=tuple(float(x) for x in out[4:7]), angular_momentum=tuple(float(x) for x in out[7:10]),
+                           kinetic=k, potential=w, total=(k + w) if potential else None, terms=int(terms.value))
+
+    def potentials(self) -> np.ndarray:
+        """phi (N,) float64 per unit mass, G included, in the caller's body order (see diagnostics())."""
+        out = np.empty(self.n, dtype=np.float64)
+        _nat.check(self._lib.nbmi_get_potentials_f64(self._h, _nat.ptr(out)), "nbmi_get_potentials_f64")
         return out
 
     def visible_points(self, cam_pos, cam_forward, cam_right, cam_up, tan_h, tan_v, far_dist):

@@ -266,6 +266,70 @@ def compress_recording(rec_dir: Path, upto: int = None, batch_size: int = COMPRE
 
 
 # ---- initial conditions + the recording loop ---------------------------------------------------
+# ---- conservation diagnostics (diagnostics_every: K) -------------------------------------------
+DIAGNOSTICS_FILE = "diagnostics.jsonl"
+
+
+def diagnostics_line(sim, frame: int, substeps: int, dt: float, extra=None) -> str:
+    """One JSON line (with its newline) for the state `sim` holds after `frame` (-1: the initial state).  Floats are
+    written with repr (json's float form), so every value reads back bit for bit."""
+    d = sim.diagnostics(potential=True)
+    steps = (frame + 1) * substeps
+    rec = {"frame": frame, "steps": steps, "time": steps * dt, "mass": d.mass, "center_of_mass": list(d.center_of_mass),
+           "momentum": list(d.momentum), "angular_momentum": list(d.angular_momentum), "kinetic": d.kinetic,
+           "potential": d.potential, "total": d.total, "terms": d.terms}
+    # (the share describes the last step: none before the first one)
+    share, all64 = sim.force_precision_share() if frame >= 0 and hasattr(sim, "force_precision_share") else (None, None)
+    rec["force_precision_share"] = share
+    rec["all_float64"] = all64
+    if extra:
+        rec.update(extra)
+    return json.dumps(rec) + "\n"
+
+
+def read_diagnostics(path: Path):
+    """The complete lines of a diagnostics.jsonl as dicts; a torn last line (no newline, or not JSON) is left out."""
+    path = Path(path)
+    if not path.exists():
+        return []
+    out = []
+    with open(path, "r") as f:
+        for line in f:
+            if not line.endswith("\n"):
+                break
+            try:
+                out.append(json.loads(line))
+            except ValueError:
+                break
+    return out
+
+
+def truncate_diagnostics(path: Path, last_frame: int):
+    """Keep the lines up to frame `last_frame` (a resume after the checkpoint of that frame), by an atomic rewrite."""
+    keep = [r for r in read_diagnostics(path) if r["frame"] <= last_frame]
+    _atomically(path, lambda f: f.write("".join(json.dumps(r) + "\n" for r in keep).encode()))
+    return keep
+
+
+def append_line(path: Path, line: str):
+    """One complete line per write call; readers skip a line that a killed process left without its newline."""
+    with open(path, "a") as f:
+        f.write(line)
+        f.flush()
+
+
+def diagnostics_drift(rows):
+    """(|E - E0| / |E0|, |P - P0| / sum m|v|_0, |L - L0| / |L0|) of the last row against the first."""
+    a, b = rows[0], rows[-1]
+    de = abs(b["total"] - a["total"]) / abs(a["total"]) if a["total"] else float("nan")
+    dp = float(np.linalg.norm(np.subtract(b["momentum"], a["momentum"])))
+    mv = a.get("abs_momentum")
+    dp = dp / mv if mv else float("nan")
+    l0 = float(np.linalg.norm(a["angular_momentum"]))
+    dl = float(np.linalg.norm(np.subtract(b["angular_momentum"], a["angular_momentum"]))) / l0 if l0 else float("nan")
+    return de, dp, dl
+
+
 def _generate_initial_conditions(config: dict):
     from tools.presets import generate_distribution
     p, v, m = generate_distribution(config.get("distribution", "galaxy"), config["num_bodies"],
@@ -339,6 +403,23 @@ def record(config: dict, resume: bool = False, root: Path = None, quiet: bool = 
         # the delta chain continues from what a reader reconstructs for the last frame on disk
         gpu_sim.frame_set_previous(*load_frame(rec_dir, start_frame - 1))
     t0 = time.time()
+    every = int(config.get("diagnostics_every") or 0)
+    diag_path = rec_dir / DIAGNOSTICS_FILE
+    last_diag = start_frame - 1
+    if every > 0:
+        if start_frame == 0:  # a run from frame 0 starts the file afresh, with the initial state
+            v0 = gpu_sim.get_velocities()
+            extra = {"abs_momentum": float(np.sum(masses * np.sqrt(np.sum(v0 * v0, axis=1))))}
+            first = diagnostics_line(gpu_sim, -1, substeps, dt, extra)
+            _atomically(diag_path, lambda f: f.write(first.encode()))
+        else:
+            truncate_diagnostics(diag_path, start_frame - 1)
+
+    def write_diag(frame):
+        nonlocal last_diag
+        if every > 0 and (frame + 1) % every == 0 and frame > last_diag:
+            append_line(diag_path, diagnostics_line(gpu_sim, frame, substeps, dt))
+            last_diag = frame
 
     def write_frame(frame):
         gpu_sim.compute_colors(15.0)
@@ -369,6 +450,7 @@ def record(config: dict, resume: bool = False, root: Path = None, quiet: bool = 
         for frame in range(start_frame, total_frames):
             gpu_sim.step_many(dt, substeps)
             write_frame(frame)
+            write_diag(frame)  # before the state checkpoint: a resume from it finds every line up to its frame
             if (frame + 1) % STATE_EVERY == 0:
                 write_state(frame)
                 old = rec_dir / f"state_{frame - STATE_EVERY:04d}.npz"
@@ -387,6 +469,7 @@ def record(config: dict, resume: bool = False, root: Path = None, quiet: bool = 
                 # (_atomically), so a cut-short write left nothing; the device-side delta chain may already have
                 # moved on, so this frame is written absolute
                 write_keyframe(at) if direct_zstd else write_frame(at)
+            write_diag(at)
             write_state(at, compressed=True)
         say(f"\n[Record] Paused at frame {at}; resume with record(config, resume=True)")
         gpu_sim.close()
@@ -438,6 +521,13 @@ def show_status(session_name: str, root: Path = None) -> bool:
     print(f"  Distribution: {meta.get('distribution', 'unknown')}")
     print(f"  Progress: {completed}/{total} frames ({completed / total * 100:.1f}%)")
     print(f"  Started: {meta.get('start_datetime', 'unknown')}")
+    rows = read_diagnostics(rec_dir / DIAGNOSTICS_FILE)
+    if rows:
+        de, dp, dl = diagnostics_drift(rows)
+        print(f"  Diagnostics: frame {rows[0]['frame']} -> {rows[-1]['frame']} ({len(rows)} lines)")
+        print(f"    |E - E0| / |E0|:        {de:.3e}")
+        print(f"    |P - P0| / sum m|v|_0:  {dp:.3e}")
+        print(f"    |L - L0| / |L0|:        {dl:.3e}")
     if completed < total:
         print(f"\n  To resume: python -m tools.record --resume {session_name}")
     else:
@@ -475,7 +565,7 @@ def build_parser():
         epilog="Differences from the reference's recorder: there is no interactive menu (give --preset or "
                "--preset-id); --preset-id indexes this build's preset list (python -m tools.record --presets shows "
                "it); --dt sets dt_per_frame (the reference writes an unused 'dt' key); --presets, --seed, "
-               "--device-ic and --root are additions.")
+               "--device-ic, --diagnostics and --root are additions.")
     ap.add_argument("session", nargs="?", help="session name (for --resume, --status or --extend)")
     ap.add_argument("--resume", action="store_true", help="resume an interrupted recording (default: the most recent)")
     ap.add_argument("--extend", type=int, metavar="FRAMES", help="extend an existing recording by N frames")
@@ -492,6 +582,9 @@ def build_parser():
     ap.add_argument("--device-ic", action="store_true",
                     help="draw the bodies on the GPU (statistically, not bitwise, like the host generator; "
                          "galaxy, collision, cluster, spiral and filament)")
+    ap.add_argument("--diagnostics", type=int, metavar="K",
+                    help="every K frames append energy, momentum and angular momentum to diagnostics.jsonl "
+                         "(stored in metadata.json as diagnostics_every)")
     ap.add_argument("--root", type=Path, default=None, help="directory holding recordings/ (default: the package's)")
     return ap
 
@@ -531,6 +624,10 @@ def build_config(args) -> dict:
             raise ValueError(f"--device-ic: no device generator for {config['distribution']!r} "
                              f"(have {', '.join(GENERATED_DISTRIBUTIONS)})")
         config["device_ic"] = True
+    if args.diagnostics is not None:
+        if args.diagnostics <= 0:
+            raise ValueError(f"--diagnostics: K must be positive, not {args.diagnostics}")
+        config["diagnostics_every"] = int(args.diagnostics)
     return config
 
 

@@ -140,6 +140,37 @@ int nbmi_get_timers(nbmi_sim *sim, double *ms5, int64_t *count, int reset);
  * (simulation.py:252-258)] (17 values). */
 int nbmi_walk_counters(nbmi_sim *sim, int64_t *out17);
 
+/* ---- conservation diagnostics ---------------------------------------------------------------
+ * Of the handle's current float64 state (positions x, velocities v as stored: the reference's kick-drift keeps them half
+ * a step apart, so E = K + W carries an O(dt) oscillation), masses m, constant G, softening eps:
+ *   M = sum m_i,  c = sum m_i x_i / M (0 when M == 0),  P = sum m_i v_i,  L = sum m_i (x_i X v_i) about the origin,
+ *   K = 1/2 sum m_i |v_i|^2,  W = 1/2 sum m_i phi_i,  E = K + W.
+ * phi_i is per unit mass of body i, G included:
+ *   Barnes-Hut handle (tree potential): phi_i = - sum G M_n / sqrt(d^2 + eps^2) over exactly the terms the reference's
+ *     walk applies to body i at the handle's theta (nbody/simulation.py:245-262): a node is accepted when it is a leaf or
+ *     node_size / dist < theta, else opened; the body's own leaf is skipped; a term is applied only when node_mass > 0
+ *     and dist_sq > eps^2, dist_sq = ((dx dx + dy dy) + dz dz) + eps^2 in float64.  G M_n and the centre of mass are the
+ *     node's float64 moments (the double-double prefix sums of the build); a leaf uses its body's float64 position and
+ *     G m.  A pair whose dist_sq rounds to eps^2 adds no force; it would add -G m / eps here, so the guard skips it too.
+ *     The accepted sets are the force walk's: the same octree of the current positions, the same opening decision.
+ *   Direct handle (exact pair sum): phi_i = - sum_{j != i} G m_j / sqrt(|x_j - x_i|^2 + eps^2); with eps == 0 pairs at
+ *     zero distance are skipped (as the force kernel skips them).
+ * All arithmetic is float64 (sqrt and divide correctly rounded); the sums are per-block partials over the state rows
+ * (the last step's key order; the caller's order before the first step, and always for direct handles) combined in a
+ * fixed order without floating-point atomics: two calls on an unchanged state return the same bits, and the result does
+ * not depend on the force precision or on whether the handle keeps float64 node records.
+ * A call changes nothing that a later step reads (state and its order, the tree header, the "auto" precision flags, the
+ * step count); the first call with the potential allocates 32 bytes per node row (Barnes-Hut) and 12 bytes per body.
+ * Owner-mode handles (and handles with a shard set) are refused with NBMI_ERR_ARG, message "<call>: owner-mode handles are
+ * not supported (...)".  n == 0 gives zeros (and terms = 0).  NBMI_ERR_CAPACITY from the call's own tree build is
+ * reported with a step's message.
+ *
+ * out12 = {M, c[3], P[3], L[3], K, W}; W = NaN when with_potential == 0 (no tree is built, no walk runs).
+ * *terms (may be NULL) = number of (body, node) terms applied to the potential (0 without it). */
+int nbmi_diagnostics(nbmi_sim *sim, int with_potential, double *out12, int64_t *terms);
+/* phi (N,) float64 in the caller's body order, as defined above. */
+int nbmi_get_potentials_f64(nbmi_sim *sim, double *out);
+
 /* Multi-GPU (one process per GPU).  A handle created with nbmi_create holds ALL bodies; with a
  * shard set, step() integrates only the key-sorted ranks [begin,end) (direct method: the body
  * indices [begin,end), its state is never re-ordered) and leaves the others untouched until
