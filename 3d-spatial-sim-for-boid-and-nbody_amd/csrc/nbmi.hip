@@ -1386,6 +1386,37 @@ __device__ __forceinline__ unsigned tie_visit64(const NodeD *nodesd, unsigned of
     return __builtin_amdgcn_readfirstlane(any_open ? off + kNodeDBytes : nd.next_off);
 }
 
+// The float64 visit of the guarded walk (k_walk<*, *, true>: eps == 0, or an eps so small that the fp32 self-term
+// overflows).  tie_visit64's decision and force arithmetic, plus the reference's dist_sq > eps^2 rule on the float64 d^2
+// (simulation.py:260) as k_potential_tree applies it: the own leaf has d = 0 exactly, and so has a coincident body.
+__device__ __forceinline__ unsigned guard_visit64(const NodeD *nodesd, unsigned off, double qx, double qy, double qz,
+                                                  double eps2, const Body64 &b64, unsigned &resume, double &sx,
+                                                  double &sy, double &sz) {
+    off = __builtin_amdgcn_readfirstlane(off);
+    const NodeD nd = *reinterpret_cast<const NodeD *>(reinterpret_cast<const char *>(nodesd) + off);
+    const double dx = nd.cx - qx, dy = nd.cy - qy, dz = nd.cz - qz;
+    const double d2 = __builtin_fma(dz, dz, __builtin_fma(dy, dy, __builtin_fma(dx, dx, eps2)));
+    const float d2f = (float)d2;
+    const bool active = resume <= off;
+    const int d2b = __float_as_int(d2f), hi = __float_as_int(nd.s2t), lo = hi - 2 * (int)kBand64;
+    bool geom = hi < d2b;
+    if (active && !geom && lo < d2b) geom = (hi == 0) || exact_take_idx(off / kNodeDBytes, b64);
+    const bool take = active && geom;
+    if (take && d2 > eps2) {
+        const double y0 = (double)__builtin_amdgcn_rsqf(d2f);
+        const double t = y0 * y0;
+        double w = nd.gm * y0;
+        const double e = __builtin_fma(-d2, t, 1.0);
+        w = w * t;
+        const double h = e * 1.5;
+        w = __builtin_fma(w, h, w);
+        sx = __builtin_fma(dx, w, sx); sy = __builtin_fma(dy, w, sy); sz = __builtin_fma(dz, w, sz);
+    }
+    if (take) resume = nd.next_off;
+    const unsigned long long any_open = __builtin_amdgcn_ballot_w64(active && !geom);
+    return __builtin_amdgcn_readfirstlane(any_open ? off + kNodeDBytes : nd.next_off);
+}
+
 // a wave-uniform 64-bit value the compiler no longer knows to be uniform (loaded behind something it treats as a
 // possible store, e.g. the cycle counter read of the balance mode) back into scalar registers
 __device__ __forceinline__ unsigned long long uniform_u64(unsigned long long v) {
@@ -1557,7 +1588,8 @@ __global__ __launch_bounds__(1024) void k_xcd_bounds(const unsigned *__restrict_
 }
 
 // The walk kernel.  kCount = parity/measurement build (C++ visit, work counters);
-// otherwise the hand-scheduled loop (eps > 0) or the C++ visit with the distance guard (eps == 0).
+// otherwise the hand-scheduled loop (eps > 0) or the C++ visit with the distance guard (kGuard: eps == 0 or tiny, see
+// guarded()), whose float64 waves visit through guard_visit64.
 template <bool kIntegrate, bool kCount, bool kGuard>
 __global__ __launch_bounds__(kBlock) void k_walk(const Node *__restrict__ nodes, const WalkTable *tab,
                                                  const TreeInfo *info_in, const float4 *__restrict__ posm_s,
@@ -1606,7 +1638,7 @@ __global__ __launch_bounds__(kBlock) void k_walk(const Node *__restrict__ nodes,
     // has the sorted bodies in registers anyway), or where most of the system is.  All lanes of a wave agree; which
     // 64 ranks form a wave does not depend on the sharding.
     bool use64 = false;
-    if (!kCount && !kGuard && kIntegrate && tab->nodesd && P.force_prec != 1) {
+    if (!kCount && kIntegrate && tab->nodesd && P.force_prec != 1) {
         if (P.force_prec == 2) {
             use64 = true;
         } else {
@@ -1628,7 +1660,11 @@ __global__ __launch_bounds__(kBlock) void k_walk(const Node *__restrict__ nodes,
         const double eps2d = __longlong_as_double((long long)uniform_u64((unsigned long long)__double_as_longlong(tab->eps2)));
         const unsigned nnd = __builtin_amdgcn_readfirstlane(frozen ? 0u : ((unsigned)info_in->walk_nodes * kNodeDBytes));
         unsigned off = 0u;
-        while (off < nnd) {
+        // (the guarded walk: every visit in C++, skipping the pairs at dist_sq <= eps^2)
+        if (kGuard) {
+            while (off < nnd) off = guard_visit64(nodesd, off, qx, qy, qz, eps2d, C.b64, resume, sx, sy, sz);
+        }
+        while (!kGuard && off < nnd) {
             unsigned which = 0u;
             walk4_asm64(nodesd, off, nnd, qx, qy, qz, eps2d, 2u * kBand64, resume, sx, sy, sz, which);
             off = __builtin_amdgcn_readfirstlane(off);
@@ -1680,6 +1716,7 @@ __global__ __launch_bounds__(kBlock) void k_walk(const Node *__restrict__ nodes,
         unsigned long long wm[4] = {0, 0, 0, 0};
         int wbase[4] = {-1000, -1000, -1000, -1000};
         unsigned off = 0u;
+        int since_flush = 0;  // guarded integrating walk: visits since the fp32 sums were emptied (two-level sums)
         while (off < nn) {
             bool a_, f_, j_, b_;
             const int c_old = (int)(off / kNodeBytes);
@@ -1689,6 +1726,11 @@ __global__ __launch_bounds__(kBlock) void k_walk(const Node *__restrict__ nodes,
                 dax += (double)tx; day += (double)ty; daz += (double)tz;
             } else {
                 off = visit<kGuard>(nodes, off, C.px, C.py, C.pz, C.b64, P, C.band2, resume, ax, ay, az, a_, f_, j_, b_);
+            }
+            if (kGuard && !kCount && ++since_flush == 12) {  // as NBMI_FLUSH does every 3 trips of 4 visits
+                sx += (double)ax; sy += (double)ay; sz += (double)az;
+                ax = ay = az = 0.f;
+                since_flush = 0;
             }
             if (kCount) {
                 wv += 1; lv += a_ ? 1 : 0; la += f_ ? 1 : 0; jm += j_ ? 1 : 0; bd += b_ ? 1 : 0;
@@ -2066,7 +2108,8 @@ __global__ __launch_bounds__(kBlock) void k_walk_diag(const Node *__restrict__ n
 // 256-thread blocks, IB bodies per thread, 256-body tiles of {x,y,z,G m} staged in LDS and read
 // back as wave-uniform broadcasts.  fp32 pair arithmetic, per-tile fp32 partial sums folded
 // into float64 accumulators.  The j == i term is exactly zero when eps > 0 (d = 0); with
-// kGuard (eps == 0) pairs at zero distance are skipped.  Fused update_bodies_cuda
+// kGuard (eps == 0, or so small that the fp32 j == i term would be 0 * inf: guarded()) the pairs whose
+// fp32 r2 does not exceed eps^2 are skipped, the reference's rule for its self and coincident pairs.  Fused update_bodies_cuda
 // (gpu_backend.py:243-257): v = (v + a dt) * damping; x += v dt, new positions go to `nxt`.
 // ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void k_pack_posm(Bodies cur, int64_t n, double G, float4 *__restrict__ posm) {
@@ -2127,7 +2170,7 @@ __global__ __launch_bounds__(kBlock) void k_direct(const float4 *__restrict__ po
                     const float r2 = fmaf(dz, dz, fmaf(dy, dy, fmaf(dx, dx, eps2)));
                     const float inv = __builtin_amdgcn_rsqf(r2);
                     float f = kUniform ? inv * inv * inv : q.w * inv * inv * inv;
-                    if (kGuard) f = (r2 > 0.f) ? f : 0.f;
+                    if (kGuard) f = (r2 > eps2) ? f : 0.f;
                     sx[k] = fmaf(f, dx, sx[k]);
                     sy[k] = fmaf(f, dy, sy[k]);
                     sz[k] = fmaf(f, dz, sz[k]);
@@ -3397,6 +3440,7 @@ struct nbmi_sim {
     int32_t *sub_flag = nullptr;         // device [one per tile]: waves of the tile that ask for float64
     double step_dt = 0.0;                // dt of the step being enqueued (0: a build without a step)
     double uniform_gm = -1.0;            // direct N^2: G m when every body has the same positive mass (the reference's presets: masses = 1), else < 0
+    double max_gm = 0.0;                 // largest |G m| of the bodies at creation (guarded())
     int owner_all64 = -1;                // owner mode: the system-wide "every wave float64" verdict for the next walk (-1: this rank's own rule)
     double owner_dt = 0.0;               // owner mode: the dt the next nbmi_owner_step will use (nbmi_owner_set_dt; "auto" needs it at build time)
     int balance_blocks = 0;           // the block count the bounds on the device were made for (0: none yet)
@@ -3600,6 +3644,24 @@ int enqueue_tree(nbmi_sim *s, int ev_base, bool aux = true, double4 *diag = null
     return 0;
 }
 
+// largest |G m| of a host mass array (nbmi_sim::max_gm)
+double largest_gm(double G, const double *mass, int64_t n) {
+    double m = 0.0;
+    for (int64_t i = 0; mass && i < n; i++) m = fabs(mass[i]) > m ? fabs(mass[i]) : m;
+    return fabs(G) * m;
+}
+
+// Whether the force kernels must skip the pairs at dist_sq <= eps^2 (kGuard) instead of relying on d = 0 to zero the
+// own leaf's / the j == i term: at eps == 0 that term is 0 * inf, and so it is at an eps small enough that the fp32
+// G m eps^-3 overflows (~1e-13 for G m = 1).  Masses are fixed at creation, so the largest G m decides once; the direct
+// kernel with equal masses forms eps^-3 alone, hence at least 1.  2^120 leaves 2^8 below FLT_MAX for the roundings.
+bool guarded(const nbmi_sim *s) {
+    const float eps2 = (float)(s->softening * s->softening);
+    if (!(eps2 > 0.f)) return true;
+    const double gm = s->max_gm > 1.0 ? s->max_gm : 1.0;
+    return gm / ((double)eps2 * sqrt((double)eps2)) > 0x1p120;
+}
+
 int enqueue_walk(nbmi_sim *s, bool integrate, double dt, double *acc_out) {
     const int64_t n = s->n;
     hipStream_t st = s->stream;
@@ -3611,7 +3673,7 @@ int enqueue_walk(nbmi_sim *s, bool integrate, double dt, double *acc_out) {
     P.rank_begin = integrate ? s->shard_begin : 0;
     P.rank_end = integrate ? s->shard_end : n;
     P.eps2 = (float)(s->softening * s->softening);
-    const bool guard = !(P.eps2 > 0.f);
+    const bool guard = guarded(s);
     P.dt = dt;
     P.damping = s->damping;
     const int64_t cntr = P.rank_end - P.rank_begin;
@@ -3716,7 +3778,7 @@ int launch_direct(nbmi_sim *s, double dt, double *acc_out) {
     Bodies cur = s->buf[s->curbuf], nxt = s->buf[1 - s->curbuf];
     k_pack_posm<<<nblocks(n), kBlock, 0, st>>>(cur, n, s->G, s->posm_s);
     const float eps2 = (float)(s->softening * s->softening);
-    const bool guard = !(eps2 > 0.f);
+    const bool guard = guarded(s);
     // multi-GPU: a sharded handle integrates only the bodies [shard_begin, shard_end) (index order:
     // the direct method never re-orders the state); the force pass always covers everything
     const int64_t ibeg = kIntegrate ? s->shard_begin : 0, iend = kIntegrate ? s->shard_end : n;
@@ -3874,7 +3936,7 @@ static int create_impl(nbmi_sim *s, const double *pos, const double *vel, const 
             (s->prec && dev_alloc(s, &s->diag64, own_rows)) ||
             dev_alloc(s, &s->xcd_bounds, 16) || dev_alloc(s, &s->wave_cycles, (size_t)4 * ((c + 63) / 64 + 8)) ||
             dev_alloc(s, &s->wave_flag, (size_t)(c + 63) / 64 + 64) || dev_alloc(s, &s->sub_flag, (c + 1) / kScanTile + 2) ||
-            (s->force_prec != 1 && s->softening > 1e-12 && s->node_capacity + 2 <= kMaxNodeDRows &&
+            (s->force_prec != 1 && s->node_capacity + 2 <= kMaxNodeDRows &&
              dev_alloc(s, &s->nodesd, s->node_capacity + 2)) ||
             false)
             return -2;
@@ -3932,6 +3994,7 @@ nbmi_sim *nbmi_create(int64_t n, const double *pos, const double *vel, const dou
     nbmi_sim *s = new nbmi_sim();
     s->n = n; s->method = method; s->device = device;
     s->G = G; s->softening = softening; s->damping = damping; s->theta = theta;
+    s->max_gm = largest_gm(G, mass, n);
     read_env_knobs(s);
     if (create_impl(s, pos, vel, mass) != 0) {
         std::string keep = nbmi::get_error();
@@ -3964,6 +4027,7 @@ nbmi_sim *nbmi_create_generated(int distribution, int64_t n, double spawn_radius
     nbmi_sim *s = new nbmi_sim();
     s->n = n; s->method = method; s->device = device;
     s->G = G; s->softening = softening; s->damping = damping; s->theta = theta;
+    s->max_gm = fabs(G);  // the generators' masses are 1 (filament: 0.1)
     read_env_knobs(s);
     int rc = create_impl(s, nullptr, nullptr, nullptr);
     if (rc == 0) {
@@ -4500,6 +4564,7 @@ nbmi_sim *nbmi_create_owner(int64_t n, const double *pos, const double *vel, con
     s->n = n; s->cap = capacity; s->method = NBMI_METHOD_BARNES_HUT; s->device = device;
     s->G = G; s->softening = softening; s->damping = damping; s->theta = theta;
     s->owner = true; s->world = world; s->rank = rank;
+    s->max_gm = largest_gm(G, mass, n);  // (the rank's own bodies at creation)
     s->let_capacity = let_capacity;
     // the own tree sits in the MIDDLE of the walk array: room for received pieces in front of it (lower ranks) and
     // behind it (higher ranks), a jump node at row 0
@@ -4986,8 +5051,8 @@ int nbmi_set_force_precision(nbmi_sim *s, int mode, double tau) {
     }
     if (s->method != NBMI_METHOD_BARNES_HUT) { nbmi::set_error("not a Barnes-Hut handle"); return NBMI_ERR_ARG; }
     if (mode != 1 && !s->nodesd) {
-        if (!(s->softening > 1e-12) || s->node_capacity + 2 > kMaxNodeDRows) {
-            nbmi::set_error("nbmi_set_force_precision: float64 forces need softening > 0 and at most %lld node rows",
+        if (s->node_capacity + 2 > kMaxNodeDRows) {
+            nbmi::set_error("nbmi_set_force_precision: float64 forces need at most %lld node rows",
                             (long long)kMaxNodeDRows);
             return NBMI_ERR_ARG;
         }

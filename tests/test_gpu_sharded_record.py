@@ -252,12 +252,22 @@ def test_owner_mode_three_ranks_agree_with_single_handle(gpu):
     ("galaxy", 9, 8, 0.5, 1.0),
     ("galaxy", 5, 8, 0.5, 1.0),           # fewer bodies than ranks
     ("galaxy", 20_000, 4, 0.0, 1.0),      # theta = 0: every cell is opened (direct sum through the tree)
+    ("galaxy", 20_000, 4, 0.5, 0.0),      # softening 0: the guarded walk (pairs at dist_sq <= eps^2 skipped)
 ])
 def test_owner_mode_walks_the_single_gpu_octree(gpu, dist, n, world, theta, eps):
     """The ranks' pieces put together are the single handle's pre-order array (global moments on the cells that span
     ranks, cells born on a boundary inserted, copies dropped): with float64 forces every body adds the same
     contributions in the same order as on one GPU.  Only the split walk of small systems associates its per-part sums
     by array position: 1e-13 of the largest coordinate after 4 steps, not bit for bit."""
+    _owner_against_single(dist, n, world, theta, eps, 1.0)
+
+
+def test_owner_mode_damped_walks_the_single_gpu_octree(gpu):
+    """The same with damping 0.99 in the fused kick-drift of every rank's walk."""
+    _owner_against_single("galaxy", 60_001, 3, 0.5, 3.0, 0.99)
+
+
+def _owner_against_single(dist, n, world, theta, eps, damping):
     from nbody.gpu_backend import HIPBarnesHutSimulation
     from nbody.sharded import HipLetEngine, LetBarnesHut
     from tools.presets import generate_distribution
@@ -265,13 +275,13 @@ def test_owner_mode_walks_the_single_gpu_octree(gpu, dist, n, world, theta, eps)
     pos, vel, mass = generate_distribution(dist, n, 300.0, 0.2)
     mass = mass * np.random.uniform(0.5, 1.5, n)
     G, dt, steps = 0.2, 0.02, 4
-    single = HIPBarnesHutSimulation(pos, vel, mass, G, eps, 1.0, theta)
+    single = HIPBarnesHutSimulation(pos, vel, mass, G, eps, damping, theta)
     single.set_force_precision("f64")
     single.step_many(dt, steps)
     ref_p, ref_v = single.get_positions_f64(), single.get_velocities()
     single.close()
     comm = _ThreadComm(world)
-    engines = [HipLetEngine(pos, vel, mass, G, eps, 1.0, theta, 0, r, world) for r in range(world)]
+    engines = [HipLetEngine(pos, vel, mass, G, eps, damping, theta, 0, r, world) for r in range(world)]
     for e in engines:
         e.sim.set_force_precision("f64")
     steppers = [LetBarnesHut(e, r, world, comm.bind(r)) for r, e in enumerate(engines)]
