@@ -946,7 +946,14 @@ struct WalkTable {
     unsigned long long *maxabs_next;  // TreeInfo::maxabs_next
     double theta, eps2;
     long long own_base;  // owner mode: row of the walk array at which the handle's own tree begins (0 otherwise)
+    // [leapfrog] which epilogue the integrating walks run: 0 = the reference's kick-drift, kLeapClose / kLeapPrime (see
+    // leap_epilogue).  The handle keeps one table per value (nbmi_sim::wtab[3]) and passes the one it wants: no kernel
+    // argument, no upload per step.
+    int leap;
+    double *ax, *ay, *az;  // acceleration columns beside the rows of the current state (leapfrog; null before its first step)
 };
+constexpr int kLeapClose = 1;  // closing half-kick, state and a written at the body's new rank of the other buffer
+constexpr int kLeapPrime = 2;  // a = F(x) written beside the body's row of the current buffer, state untouched
 
 // where a lane finds its body's float64 position (only read on the re-decision path)
 struct Body64 {
@@ -1488,10 +1495,42 @@ __device__ __forceinline__ unsigned seek(const WalkCtx &C, const WalkParams &P, 
     return off;
 }
 
+// [leapfrog] Epilogue of the synchronized kick-drift-kick step.  The state rows the walk reads
+// (P.curbuf) were written by k_kick_drift: x already drifted, v after the opening half-kick.
+//   kLeapClose: v = (v + a dt/2) damping, written with x, m, id and a at the body's new rank of the other buffer - the
+//               buffer k_kick_drift read, so after the step the current buffer is the same one again.
+//   kLeapPrime: a written beside the body's own row of the current buffer (the walk ran on the current state).
+// Frozen (a capacity error is pending): nothing is written, the pre-step rows (x, v, a) stay the state.
+__device__ __forceinline__ void leap_epilogue(const WalkTable *tab, int leap, uint32_t j, int64_t rank, double ax, double ay,
+                                              double az, const WalkParams &P, bool frozen) {
+    if (frozen) return;
+    if (leap == kLeapPrime) {
+        tab->ax[j] = ax; tab->ay[j] = ay; tab->az[j] = az;
+        return;
+    }
+    const Bodies cur = tab->buf[P.curbuf], nxt = tab->buf[1 - P.curbuf];
+    const double h = 0.5 * P.dt;
+    nxt.vx[rank] = (cur.vx[j] + ax * h) * P.damping;
+    nxt.vy[rank] = (cur.vy[j] + ay * h) * P.damping;
+    nxt.vz[rank] = (cur.vz[j] + az * h) * P.damping;
+    nxt.x[rank] = cur.x[j]; nxt.y[rank] = cur.y[j]; nxt.z[rank] = cur.z[j];
+    nxt.m[rank] = cur.m[j];
+    nxt.id[rank] = cur.id[j];
+    tab->ax[rank] = ax; tab->ay[rank] = ay; tab->az[rank] = az;
+}
+
 // fused kick-drift (simulation.py:291-305) of the body at sorted rank `rank`, written at that rank of the
-// other buffer; frozen (a capacity error is pending): the body moves to its rank unchanged
+// other buffer; frozen (a capacity error is pending): the body moves to its rank unchanged.  kLeap (the leapfrog
+// instantiations of the walks): leap_epilogue as tab->leap says (returns 0: the positions the next build reads are
+// published by k_kick_drift).  A template parameter, not a branch on tab->leap alone: the kick-drift instantiations keep
+// their code, registers and occupancy exactly.
+template <bool kLeap>
 __device__ __forceinline__ double integrate(const WalkTable *tab, uint32_t j, int64_t rank, double ax,
                                             double ay, double az, const WalkParams &P, bool frozen) {
+    if (kLeap) {
+        leap_epilogue(tab, tab->leap, j, rank, ax, ay, az, P, frozen);
+        return 0.0;
+    }
     const Bodies cur = tab->buf[P.curbuf], nxt = tab->buf[1 - P.curbuf];
     double vx = cur.vx[j], vy = cur.vy[j], vz = cur.vz[j];
     double x0 = cur.x[j], y0 = cur.y[j], z0 = cur.z[j];
@@ -1590,7 +1629,7 @@ __global__ __launch_bounds__(1024) void k_xcd_bounds(const unsigned *__restrict_
 // The walk kernel.  kCount = parity/measurement build (C++ visit, work counters);
 // otherwise the hand-scheduled loop (eps > 0) or the C++ visit with the distance guard (kGuard: eps == 0 or tiny, see
 // guarded()), whose float64 waves visit through guard_visit64.
-template <bool kIntegrate, bool kCount, bool kGuard>
+template <bool kIntegrate, bool kCount, bool kGuard, bool kLeap = false>
 __global__ __launch_bounds__(kBlock) void k_walk(const Node *__restrict__ nodes, const WalkTable *tab,
                                                  const TreeInfo *info_in, const float4 *__restrict__ posm_s,
                                                  const uint32_t *__restrict__ perm,
@@ -1756,7 +1795,7 @@ __global__ __launch_bounds__(kBlock) void k_walk(const Node *__restrict__ nodes,
         }
     }
     if (kIntegrate) {
-        publish_maxabs(tab, valid ? integrate(tab, j, rank, sx + (double)ax, sy + (double)ay, sz + (double)az, P, frozen) : 0.0);
+        publish_maxabs(tab, valid ? integrate<kLeap>(tab, j, rank, sx + (double)ax, sy + (double)ay, sz + (double)az, P, frozen) : 0.0);
         if (P.balance && lane == 0) {
             const unsigned long long dtc = __builtin_readcyclecounter() - t_start;
             tab->wave_cycles[4 * lb + (threadIdx.x >> 6)] = (unsigned)(dtc > 0xffffffffull ? 0xffffffffull : dtc);
@@ -1781,7 +1820,7 @@ __global__ __launch_bounds__(kBlock) void k_walk(const Node *__restrict__ nodes,
 // (body, node) set as the one-wave walk; the fp32 sums associate differently (by fixed node ranges,
 // so a body's result still does not depend on its group or on the sharding).
 // ---------------------------------------------------------------------------------------
-template <int K>
+template <int K, bool kLeap = false>
 __global__ __launch_bounds__(64 * K) void k_walk_split(const Node *__restrict__ nodes, const WalkTable *tab,
                                                        const TreeInfo *info_in, const float4 *__restrict__ posm_s,
                                                        const uint32_t *__restrict__ perm, WalkParams P) {
@@ -1855,7 +1894,7 @@ __global__ __launch_bounds__(64 * K) void k_walk_split(const Node *__restrict__ 
     for (int k = 1; k < K; k++) {
         sx += part[k][0][lane]; sy += part[k][1][lane]; sz += part[k][2][lane];
     }
-    publish_maxabs(tab, valid ? integrate(tab, j, rank, sx, sy, sz, P, frozen) : 0.0);
+    publish_maxabs(tab, valid ? integrate<kLeap>(tab, j, rank, sx, sy, sz, P, frozen) : 0.0);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1866,6 +1905,7 @@ __global__ __launch_bounds__(64 * K) void k_walk_split(const Node *__restrict__ 
 // skip / descend decision per visit.  Accepted (body, node) sets are unchanged; sums associate differently.
 // ---------------------------------------------------------------------------------------
 constexpr int kStackCap = 320;  // > 7 pending siblings on each of the 43 possible levels
+template <bool kLeap = false>
 __global__ __launch_bounds__(kBlock) void k_walk_stack(const Node *__restrict__ nodes, const uint32_t *__restrict__ child_tab,
                                                        const WalkTable *tab, const TreeInfo *info_in,
                                                        const float4 *__restrict__ posm_s, const uint32_t *__restrict__ perm,
@@ -1930,7 +1970,7 @@ __global__ __launch_bounds__(kBlock) void k_walk_stack(const Node *__restrict__ 
         }
     }
     if (!valid) return;
-    integrate(tab, j, rank, ax, ay, az, P, frozen);
+    integrate<kLeap>(tab, j, rank, ax, ay, az, P, frozen);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1967,7 +2007,7 @@ __global__ __launch_bounds__(kBlock) void k_walk_lane(const Node *__restrict__ n
         ax = fmaf(dx, f, ax); ay = fmaf(dy, f, ay); az = fmaf(dz, f, az);
         off = take ? __float_as_uint(b.y) : off + kNodeBytes;
     }
-    integrate(tab, j, rank, ax, ay, az, P, frozen);
+    integrate<false>(tab, j, rank, ax, ay, az, P, frozen);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2100,7 +2140,7 @@ __global__ __launch_bounds__(kBlock) void k_walk_diag(const Node *__restrict__ n
         const unsigned long long any_open = __builtin_amdgcn_ballot_w64(active && !geom);
         off = any_open ? off + kNodeBytes : nd.next_off;
     }
-    publish_maxabs(tab, valid ? integrate(tab, j, rank, sx + (double)fx, sy + (double)fy, sz + (double)fz, P, frozen) : 0.0);
+    publish_maxabs(tab, valid ? integrate<false>(tab, j, rank, sx + (double)fx, sy + (double)fy, sz + (double)fz, P, frozen) : 0.0);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2118,10 +2158,47 @@ __global__ __launch_bounds__(kBlock) void k_pack_posm(Bodies cur, int64_t n, dou
     posm[i] = make_float4((float)cur.x[i], (float)cur.y[i], (float)cur.z[i], (float)(G * cur.m[i]));
 }
 
+// [leapfrog] Opening half-kick and drift of every row of the current buffer, written to the same
+// row of the other buffer: v' = v + a dt/2, x' = x + v' dt; m and id travel along.  The pre-step rows stay untouched
+// (a step whose octree does not fit leaves them the state).  Barnes-Hut: max |x'| joins TreeInfo::maxabs_next, which the
+// build's k_header takes over (no pass of its own over the bodies); one atomic per block, so the grid is capped by the
+// caller.  Direct: the new positions and G m are also packed for k_direct (k_pack_posm's job).
+__global__ __launch_bounds__(kBlock) void k_kick_drift(Bodies cur, Bodies nxt, const double *__restrict__ ax,
+                                                       const double *__restrict__ ay, const double *__restrict__ az, int64_t n,
+                                                       double dt, double G, float4 *__restrict__ posm,
+                                                       unsigned long long *__restrict__ maxabs) {
+    __shared__ double red[kBlock / 64];
+    const double h = 0.5 * dt;
+    double mx = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+        const double vx = cur.vx[i] + ax[i] * h, vy = cur.vy[i] + ay[i] * h, vz = cur.vz[i] + az[i] * h;
+        const double x = cur.x[i] + vx * dt, y = cur.y[i] + vy * dt, z = cur.z[i] + vz * dt;
+        const double m = cur.m[i];
+        nxt.vx[i] = vx; nxt.vy[i] = vy; nxt.vz[i] = vz;
+        nxt.x[i] = x; nxt.y[i] = y; nxt.z[i] = z;
+        nxt.m[i] = m;
+        nxt.id[i] = cur.id[i];
+        if (posm) posm[i] = make_float4((float)x, (float)y, (float)z, (float)(G * m));
+        mx = fmax(mx, fmax(fmax(fabs(x), fabs(y)), fabs(z)));
+    }
+    if (!maxabs) return;
+    mx = wave_max(mx);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < kBlock / 64; w++) mx = fmax(mx, red[w]);
+        const unsigned long long bits = (unsigned long long)__double_as_longlong(mx);
+        if (bits > __atomic_load_n(maxabs, __ATOMIC_RELAXED)) atomicMax(maxabs, bits);
+    }
+}
+
 // [r4] kUniform: every body has the same mass (the reference's presets set masses = 1: tools/presets.py), so G m is ONE number:
 // it leaves the pair loop - f = inv^3 instead of G m inv^3, 12 vector instructions per pair instead of 13 - and multiplies
 // the float64 sums once per body.
-template <int IB, bool kGuard, bool kIntegrate, bool kUniform>
+// [leapfrog] kLeap (with kIntegrate): the epilogue of leap_epilogue in index order - kLeapClose reads the rows k_kick_drift
+// wrote (cur) and writes x, the closed v, m, id to `nxt` and a to the columns acc_out[i], acc_out[n + i], acc_out[2n + i];
+// kLeapPrime only writes a there.
+template <int IB, bool kGuard, bool kIntegrate, bool kUniform, int kLeap = 0>
 __global__ __launch_bounds__(kBlock) void k_direct(const float4 *__restrict__ posm, int64_t n, int64_t ibeg, int64_t iend,
                                                    float eps2, Bodies cur, Bodies nxt, double *__restrict__ acc_out,
                                                    double dt, double damping, double uniform_gm) {
@@ -2190,7 +2267,18 @@ __global__ __launch_bounds__(kBlock) void k_direct(const float4 *__restrict__ po
         const int64_t i = i0 + (int64_t)k * kBlock;
         if (i >= iend) continue;
         if (kUniform) { ax[k] *= uniform_gm; ay[k] *= uniform_gm; az[k] *= uniform_gm; }
-        if (kIntegrate) {
+        if (kIntegrate && kLeap != 0) {
+            if (kLeap == kLeapClose) {
+                const double h = 0.5 * dt;
+                nxt.vx[i] = (cur.vx[i] + ax[k] * h) * damping;
+                nxt.vy[i] = (cur.vy[i] + ay[k] * h) * damping;
+                nxt.vz[i] = (cur.vz[i] + az[k] * h) * damping;
+                nxt.x[i] = cur.x[i]; nxt.y[i] = cur.y[i]; nxt.z[i] = cur.z[i];
+                nxt.m[i] = cur.m[i];
+                nxt.id[i] = cur.id[i];
+            }
+            acc_out[i] = ax[k]; acc_out[n + i] = ay[k]; acc_out[2 * n + i] = az[k];
+        } else if (kIntegrate) {
             const double vx = (cur.vx[i] + ax[k] * dt) * damping;
             const double vy = (cur.vy[i] + ay[k] * dt) * damping;
             const double vz = (cur.vz[i] + az[k] * dt) * damping;
@@ -3387,7 +3475,7 @@ struct nbmi_sim {
     int force_prec = 0;         // 0 = per wave by local density, 1 = fp32 everywhere, 2 = float64 everywhere (NBMI_FORCE_PREC)
     int all64_enter_pm = kAll64Enter, all64_leave_pm = kAll64Leave;  // "auto": every wave float64 while most of the system asks (per mille of the waves)
     double prec_tau = 5.0e-5;   // force_prec 0: float64 where G rho dt^2 exceeds this (NBMI_PREC_TAU)
-    WalkTable *wtab = nullptr;  // device copy of the walk's per-handle constants
+    WalkTable *wtab = nullptr;  // device copies of the walk's per-handle constants: [0] kick-drift, [kLeapClose], [kLeapPrime]
     uint8_t *node_level = nullptr;
     int32_t *node_ref = nullptr;  // first body (sorted rank) of every node; queries only
     int64_t node_capacity = 0;   // rows of the walk array (own tree + received trees)
@@ -3467,6 +3555,11 @@ struct nbmi_sim {
     long long *diag_partc = nullptr;  // [kDiagBlocksMax + 1] the same for the term counts
     double4 *diag_pot = nullptr;      // [node rows] float64 {cx, cy, cz, G m} of every node of the diagnostic's own build
     TreeInfo *diag_info = nullptr;    // the tree header as the last step left it, put back after the diagnostic's build
+    // integrator (nbmi_set_integrator).  Leapfrog keeps a = F(x) of the current state beside its
+    // rows: acc = 3 columns of n doubles, allocated by the first leapfrog step; acc_valid = false until a step primes it
+    int integrator = NBMI_INTEGRATOR_KICK_DRIFT;
+    bool acc_valid = false;
+    double *acc = nullptr;
     // one-wave walk: cursors per wave and where the array is cut.  -1 = by size: two cursors, cut at the middle of the
     // array, or (from kHomeSplitBodies = 1.5 M bodies on) at the leaf of the wave's middle body; NBMI_WALK_PAIR = 0 / 1 / 2 forces
     // one cursor / the middle cut / the home cut
@@ -3514,8 +3607,15 @@ int upload_walk_table(nbmi_sim *s) {
     t.theta = s->theta;
     t.eps2 = s->softening * s->softening;
     t.own_base = s->own_base;
-    NBMI_HIP_CHECK(hipMemcpyAsync(s->wtab, &t, sizeof(t), hipMemcpyHostToDevice, s->stream));
-    NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));  // `t` is a stack object
+    t.ax = s->acc;
+    t.ay = s->acc ? s->acc + s->n : nullptr;
+    t.az = s->acc ? s->acc + 2 * s->n : nullptr;
+    WalkTable tabs[3] = {t, t, t};  // one per epilogue: kick-drift, kLeapClose, kLeapPrime
+    tabs[0].leap = 0;
+    tabs[kLeapClose].leap = kLeapClose;
+    tabs[kLeapPrime].leap = kLeapPrime;
+    NBMI_HIP_CHECK(hipMemcpyAsync(s->wtab, tabs, sizeof(tabs), hipMemcpyHostToDevice, s->stream));
+    NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));  // `tabs` is a stack object
     return 0;
 }
 
@@ -3629,13 +3729,14 @@ int enqueue_global_tree(nbmi_sim *s, bool aux = true, double4 *diag = nullptr) {
     return 0;
 }
 
-// Single-GPU build: the tree over the handle's own bodies.
+// Single-GPU build: the tree over the handle's own bodies.  ev_base: -1 untimed, 0 timed, 1 timed with the phase's first
+// event already recorded by the caller (a leapfrog step: its k_kick_drift counts as the bounds phase)
 int enqueue_tree(nbmi_sim *s, int ev_base, bool aux = true, double4 *diag = nullptr) {
     if (s->owner) {
         nbmi::set_error("this handle is in owner mode: use the nbmi_owner_* calls");
         return NBMI_ERR_ARG;
     }
-    if (ev_base >= 0) NBMI_HIP_CHECK(hipEventRecord(s->ev[0], s->stream));
+    if (ev_base == 0) NBMI_HIP_CHECK(hipEventRecord(s->ev[0], s->stream));
     if (int rc = enqueue_maxabs(s)) return rc;
     if (int rc = enqueue_local_sort(s, ev_base)) return rc;
     if (int rc = enqueue_global_tree(s, aux, diag)) return rc;
@@ -3662,13 +3763,15 @@ bool guarded(const nbmi_sim *s) {
     return gm / ((double)eps2 * sqrt((double)eps2)) > 0x1p120;
 }
 
-int enqueue_walk(nbmi_sim *s, bool integrate, double dt, double *acc_out) {
+// leap (integrating walks only): 0 = kick-drift, kLeapClose / kLeapPrime = the leapfrog epilogues (leap_epilogue)
+int enqueue_walk(nbmi_sim *s, bool integrate, double dt, double *acc_out, int leap = 0) {
     const int64_t n = s->n;
     hipStream_t st = s->stream;
     if (!s->wtab || !s->nodes64) {  // the kernels dereference both: never launch without them
         nbmi::set_error("internal: walk table not initialised");
         return NBMI_ERR_ARG;
     }
+    const WalkTable *tab = s->wtab + (integrate ? leap : 0);
     WalkParams P;
     P.rank_begin = integrate ? s->shard_begin : 0;
     P.rank_end = integrate ? s->shard_end : n;
@@ -3683,13 +3786,18 @@ int enqueue_walk(nbmi_sim *s, bool integrate, double dt, double *acc_out) {
     if (s->owner && s->world > 1 && P.pair == 1) P.pair = 2;  // (the middle of the array may lie in the unused rows in front of the pieces)
     P.curbuf = s->curbuf;
     P.acc64 = getenv("NBMI_ACC64") ? atoi(getenv("NBMI_ACC64")) : 0;
+    if (integrate && leap && (s->prec || s->walk_lane || P.acc64)) {
+        nbmi::set_error("nbmi_step: the leapfrog integrator is not available with the measurement-only walks (NBMI_PREC, "
+                        "NBMI_WALK_LANE, NBMI_ACC64)");
+        return NBMI_ERR_ARG;
+    }
     P.balance = 0;
     P.force_prec = s->nodesd ? s->force_prec : 1;
     P.prec_tau = (float)s->prec_tau;
     P.prec = s->prec;
     P.near2 = s->prec >= 20 ? (float)(s->prec_near * s->prec_near) : (float)(s->prec_near * s->prec_near * s->softening * s->softening);
     if (integrate && s->prec && s->diag64 && !guard && !s->owner) {  // measurement only, see k_walk_diag
-        k_walk_diag<<<(int)((cntr + kBlock - 1) / kBlock), kBlock, 0, st>>>(s->nodes, s->diag64, s->wtab, s->info, s->posm_s, s->perm, P);
+        k_walk_diag<<<(int)((cntr + kBlock - 1) / kBlock), kBlock, 0, st>>>(s->nodes, s->diag64, tab, s->info, s->posm_s, s->perm, P);
         NBMI_HIP_CHECK(hipGetLastError());
         return 0;
     }
@@ -3702,31 +3810,40 @@ int enqueue_walk(nbmi_sim *s, bool integrate, double dt, double *acc_out) {
     int parts = 1;
     while (parts < 16 && tree_groups <= 4300 && tree_groups * parts * 2 <= s->split_max_waves) parts *= 2;
     if (integrate && !guard && parts > 1) {
+#define NBMI_SPLIT_L(KV, L) \
+    k_walk_split<KV, L><<<(int)groups, 64 * KV, 0, st>>>(s->nodes, tab, s->info, s->posm_s, s->perm, P)
 #define NBMI_SPLIT(KV) \
-    k_walk_split<KV><<<(int)groups, 64 * KV, 0, st>>>(s->nodes, s->wtab, s->info, s->posm_s, s->perm, P)
+    do { if (leap) NBMI_SPLIT_L(KV, true); else NBMI_SPLIT_L(KV, false); } while (0)
         if (parts == 2) NBMI_SPLIT(2);
         else if (parts == 4) NBMI_SPLIT(4);
         else if (parts == 8) NBMI_SPLIT(8);
         else NBMI_SPLIT(16);
 #undef NBMI_SPLIT
+#undef NBMI_SPLIT_L
         NBMI_HIP_CHECK(hipGetLastError());
         return 0;
     }
     const int wb = s->walk_block;
     const int gb = (int)((cntr + wb - 1) / wb);
     if (integrate && s->walk_stack && !guard && !s->owner) {
-        k_walk_stack<<<(int)((cntr + kBlock - 1) / kBlock), kBlock, 0, st>>>(s->nodes, s->child_tab, s->wtab, s->info, s->posm_s,
-                                                                             s->perm, P);
+        if (leap)
+            k_walk_stack<true><<<(int)((cntr + kBlock - 1) / kBlock), kBlock, 0, st>>>(s->nodes, s->child_tab, tab, s->info,
+                                                                                       s->posm_s, s->perm, P);
+        else
+            k_walk_stack<false><<<(int)((cntr + kBlock - 1) / kBlock), kBlock, 0, st>>>(s->nodes, s->child_tab, tab, s->info,
+                                                                                        s->posm_s, s->perm, P);
         NBMI_HIP_CHECK(hipGetLastError());
         return 0;
     }
     if (integrate && s->walk_lane) {  // measurement only, see k_walk_lane
-        k_walk_lane<<<gb, wb, 0, st>>>(s->nodes, s->wtab, s->info, s->posm_s, s->perm, P);
+        k_walk_lane<<<gb, wb, 0, st>>>(s->nodes, tab, s->info, s->posm_s, s->perm, P);
         NBMI_HIP_CHECK(hipGetLastError());
         return 0;
     }
 #define NBMI_WALK(I, C, G) \
-    k_walk<I, C, G><<<gb, wb, 0, st>>>(s->nodes, s->wtab, s->info, s->posm_s, s->perm, acc_out, P, s->info)
+    k_walk<I, C, G><<<gb, wb, 0, st>>>(s->nodes, tab, s->info, s->posm_s, s->perm, acc_out, P, s->info)
+#define NBMI_WALK_LEAP(G) \
+    k_walk<true, false, G, true><<<gb, wb, 0, st>>>(s->nodes, tab, s->info, s->posm_s, s->perm, acc_out, P, s->info)
     // balance mode: full, unsharded integrating walks of the product kernel with the default block mapping
     // (measured: 10 M collision walk 15.9 -> 14.8 ms, fp32 10.4 -> 9.8; 4 M galaxy 6.96 -> 6.90; at 1 M bodies the eighths are
     // within 1 % of each other already and the half-empty launch costs 2 %: from 8 192 blocks = 2 M bodies on)
@@ -3750,7 +3867,8 @@ int enqueue_walk(nbmi_sim *s, bool integrate, double dt, double *acc_out) {
             NBMI_HIP_CHECK(hipEventCreateWithFlags(&s->ev_walked, hipEventDisableTiming));
             NBMI_HIP_CHECK(hipEventCreateWithFlags(&s->ev_cut, hipEventDisableTiming));
         }
-        k_walk<true, false, false><<<8 * jmax, wb, 0, st>>>(s->nodes, s->wtab, s->info, s->posm_s, s->perm, acc_out, P, s->info);
+        if (leap) k_walk<true, false, false, true><<<8 * jmax, wb, 0, st>>>(s->nodes, tab, s->info, s->posm_s, s->perm, acc_out, P, s->info);
+        else k_walk<true, false, false><<<8 * jmax, wb, 0, st>>>(s->nodes, tab, s->info, s->posm_s, s->perm, acc_out, P, s->info);
         NBMI_HIP_CHECK(hipGetLastError());
         // cuts for the next step: beside whatever the main stream does next (the next step's keys, sort and build)
         NBMI_HIP_CHECK(hipEventRecord(s->ev_walked, st));
@@ -3761,22 +3879,27 @@ int enqueue_walk(nbmi_sim *s, bool integrate, double dt, double *acc_out) {
         s->cut_pending = true;
         return 0;
     }
-    if (integrate) {
+    if (integrate && leap) {
+        if (guard) NBMI_WALK_LEAP(true); else NBMI_WALK_LEAP(false);
+    } else if (integrate) {
         if (guard) NBMI_WALK(true, false, true); else NBMI_WALK(true, false, false);
     } else {
         if (guard) NBMI_WALK(false, true, true); else NBMI_WALK(false, true, false);
     }
 #undef NBMI_WALK
+#undef NBMI_WALK_LEAP
     NBMI_HIP_CHECK(hipGetLastError());
     return 0;
 }
 
+// leap (kIntegrate only): 0 = kick-drift, kLeapClose / kLeapPrime = the leapfrog epilogues (acc_out: the acceleration
+// columns); kLeapClose finds posm_s already packed by k_kick_drift
 template <bool kIntegrate>
-int launch_direct(nbmi_sim *s, double dt, double *acc_out) {
+int launch_direct(nbmi_sim *s, double dt, double *acc_out, int leap = 0) {
     const int64_t n = s->n;
     hipStream_t st = s->stream;
     Bodies cur = s->buf[s->curbuf], nxt = s->buf[1 - s->curbuf];
-    k_pack_posm<<<nblocks(n), kBlock, 0, st>>>(cur, n, s->G, s->posm_s);
+    if (leap != kLeapClose) k_pack_posm<<<nblocks(n), kBlock, 0, st>>>(cur, n, s->G, s->posm_s);
     const float eps2 = (float)(s->softening * s->softening);
     const bool guard = guarded(s);
     // multi-GPU: a sharded handle integrates only the bodies [shard_begin, shard_end) (index order:
@@ -3786,24 +3909,69 @@ int launch_direct(nbmi_sim *s, double dt, double *acc_out) {
     if (cnt <= 0) return 0;
     // bodies per thread: enough blocks to cover 256 CUs a few times over
     int ib = cnt >= 512 * 1024 ? 4 : (cnt >= 128 * 1024 ? 2 : 1);
-#define NBMI_DIRECT(IBV)                                                                                      \
+#define NBMI_DIRECT_L(IBV, LV)                                                                                \
     do {                                                                                                      \
         const int gb = (int)((cnt + (int64_t)kBlock * IBV - 1) / ((int64_t)kBlock * IBV));                    \
         if (guard)                                                                                            \
-            k_direct<IBV, true, kIntegrate, false><<<gb, kBlock, 0, st>>>(s->posm_s, n, ibeg, iend, eps2, cur, nxt, \
+            k_direct<IBV, true, kIntegrate, false, LV><<<gb, kBlock, 0, st>>>(s->posm_s, n, ibeg, iend, eps2, cur, nxt, \
                                                                          acc_out, dt, s->damping, 0.0);        \
         else if (s->uniform_gm > 0.0)                                                                         \
-            k_direct<IBV, false, kIntegrate, true><<<gb, kBlock, 0, st>>>(s->posm_s, n, ibeg, iend, eps2, cur, nxt, \
+            k_direct<IBV, false, kIntegrate, true, LV><<<gb, kBlock, 0, st>>>(s->posm_s, n, ibeg, iend, eps2, cur, nxt, \
                                                                          acc_out, dt, s->damping, s->uniform_gm); \
         else                                                                                                  \
-            k_direct<IBV, false, kIntegrate, false><<<gb, kBlock, 0, st>>>(s->posm_s, n, ibeg, iend, eps2, cur, nxt, \
+            k_direct<IBV, false, kIntegrate, false, LV><<<gb, kBlock, 0, st>>>(s->posm_s, n, ibeg, iend, eps2, cur, nxt, \
                                                                           acc_out, dt, s->damping, 0.0);      \
+    } while (0)
+#define NBMI_DIRECT(IBV)                                                     \
+    do {                                                                     \
+        if (leap == kLeapClose) NBMI_DIRECT_L(IBV, kIntegrate ? kLeapClose : 0); \
+        else if (leap == kLeapPrime) NBMI_DIRECT_L(IBV, kIntegrate ? kLeapPrime : 0); \
+        else NBMI_DIRECT_L(IBV, 0);                                          \
     } while (0)
     if (ib == 4) NBMI_DIRECT(4);
     else if (ib == 2) NBMI_DIRECT(2);
     else NBMI_DIRECT(1);
 #undef NBMI_DIRECT
+#undef NBMI_DIRECT_L
     NBMI_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// [leapfrog] The acceleration columns exist (allocated by the first leapfrog step) and hold a = F(x) of the current state
+// (primed once after create / nbmi_set_state / a switch into leapfrog / a reported capacity error, inside the step so that
+// force precision "auto" sees its dt).
+int leap_prepare(nbmi_sim *s, double dt) {
+    if (!s->acc) {
+        if (dev_alloc(s, &s->acc, (size_t)3 * s->n)) return NBMI_ERR_HIP;
+        NBMI_HIP_CHECK(hipMemsetAsync(s->acc, 0, (size_t)3 * s->n * sizeof(double), s->stream));
+        if (s->method == NBMI_METHOD_BARNES_HUT && upload_walk_table(s)) return NBMI_ERR_HIP;
+    }
+    if (s->acc_valid) return 0;
+    if (s->method == NBMI_METHOD_BARNES_HUT) {
+        s->step_dt = dt;
+        const int rc_tree = enqueue_tree(s, -1, false);
+        s->step_dt = 0.0;
+        if (rc_tree) return rc_tree;
+        if (int rc = enqueue_walk(s, true, dt, nullptr, kLeapPrime)) return rc;
+        s->tree_valid = false;
+    } else {
+        if (int rc = launch_direct<true>(s, dt, s->acc, kLeapPrime)) return rc;
+    }
+    s->acc_valid = true;
+    return 0;
+}
+
+// [leapfrog] Opening half-kick + drift of the current buffer into the other one (k_kick_drift), which becomes current
+// for the force pass.  The grid is capped: one same-address atomic per block (as k_maxabs).
+int enqueue_kick_drift(nbmi_sim *s, double dt) {
+    const int64_t n = s->n;
+    int gb = nblocks(n);
+    if (gb > 2048) gb = 2048;
+    const bool bh = s->method == NBMI_METHOD_BARNES_HUT;
+    k_kick_drift<<<gb, kBlock, 0, s->stream>>>(s->buf[s->curbuf], s->buf[1 - s->curbuf], s->acc, s->acc + n, s->acc + 2 * n, n,
+                                                dt, s->G, bh ? nullptr : s->posm_s, bh ? &s->info->maxabs_next : nullptr);
+    NBMI_HIP_CHECK(hipGetLastError());
+    s->curbuf ^= 1;
     return 0;
 }
 
@@ -3833,6 +4001,7 @@ int check_device_error(nbmi_sim *s) {
         NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
         s->tree_valid = false;
         s->maxabs_fused = false;
+        s->acc_valid = false;  // leapfrog: a priming walk may have been frozen; the next step primes again
     }
     if (h.error || h.sticky_error) {
         nbmi::set_error("octree needs %lld nodes, more than the %lld rows allocated (4N, as the reference); the "
@@ -3946,7 +4115,7 @@ static int create_impl(nbmi_sim *s, const double *pos, const double *vel, const 
         if (dev_alloc(s, &t, s->tmp_sort_bytes + 256)) return -2;
         s->tmp_sort = t;
         NBMI_HIP_CHECK(nbmi::sort_init_temp(t, s->stream));
-        if (dev_alloc(s, &s->wtab, 1) || upload_walk_table(s)) return -2;
+        if (dev_alloc(s, &s->wtab, 3) || upload_walk_table(s)) return -2;
     }
     // upload AoS host arrays through the staging buffer and split to SoA
     double *dpos = (double *)s->stage, *dvel = dpos + 3 * n, *dm = dvel + 3 * n;
@@ -4079,14 +4248,35 @@ int nbmi_step(nbmi_sim *s, double dt, int substeps) {
         nbmi::set_error("nbmi_step: a sharded handle needs nbmi_import_ranks between steps (substeps must be 1)");
         return NBMI_ERR_ARG;
     }
+    const bool leap = s->integrator == NBMI_INTEGRATOR_LEAPFROG;
+    if (leap && substeps > 0) {
+        if (int rc = leap_prepare(s, dt)) return rc;
+    }
     for (int k = 0; k < substeps; k++) {
         if (s->method == NBMI_METHOD_BARNES_HUT) {
             const int evb = s->timers ? 0 : -1;
-            s->step_dt = dt;
-            const int rc_tree = enqueue_tree(s, evb, false);
-            s->step_dt = 0.0;
-            if (rc_tree) return rc_tree;
-            if (int rc = enqueue_walk(s, true, dt, nullptr)) return rc;
+            if (leap) {
+                // kick-drift into the other buffer, build + walk there, the closing kick writes back: one step leaves the
+                // current buffer where it was
+                if (s->timers) NBMI_HIP_CHECK(hipEventRecord(s->ev[0], s->stream));
+                if (int rc = enqueue_kick_drift(s, dt)) return rc;
+                s->maxabs_fused = true;  // k_kick_drift has published max |x'|
+                s->step_dt = dt;
+                int rc = enqueue_tree(s, s->timers ? 1 : -1, false);
+                s->step_dt = 0.0;
+                if (rc == 0) rc = enqueue_walk(s, true, dt, nullptr, kLeapClose);
+                s->curbuf ^= 1;
+                if (rc) {
+                    s->maxabs_fused = false;
+                    return rc;
+                }
+            } else {
+                s->step_dt = dt;
+                const int rc_tree = enqueue_tree(s, evb, false);
+                s->step_dt = 0.0;
+                if (rc_tree) return rc_tree;
+                if (int rc = enqueue_walk(s, true, dt, nullptr)) return rc;
+            }
             if (s->timers) {
                 NBMI_HIP_CHECK(hipEventRecord(s->ev[4], s->stream));
                 NBMI_HIP_CHECK(hipEventSynchronize(s->ev[4]));
@@ -4099,13 +4289,21 @@ int nbmi_step(nbmi_sim *s, double dt, int substeps) {
             }
             // a full (unsharded) step leaves every rank of the other buffer written
             // (sharded handles: the ranks outside [shard_begin, shard_end) arrive via nbmi_import_ranks)
-            s->curbuf ^= 1;
+            if (!leap) s->curbuf ^= 1;
             s->steps_taken++;
             s->tree_valid = false;
-            s->maxabs_fused = s->fuse_maxabs && s->shard_begin == 0 && s->shard_end == s->n && !s->walk_stack && !s->walk_lane;
+            // (leapfrog: the walk publishes nothing, the next k_kick_drift does)
+            s->maxabs_fused = !leap && s->fuse_maxabs && s->shard_begin == 0 && s->shard_end == s->n && !s->walk_stack && !s->walk_lane;
         } else {
             if (s->timers) NBMI_HIP_CHECK(hipEventRecord(s->ev[0], s->stream));
-            if (int rc = launch_direct<true>(s, dt, nullptr)) return rc;
+            if (leap) {
+                if (int rc = enqueue_kick_drift(s, dt)) return rc;
+                const int rc = launch_direct<true>(s, dt, s->acc, kLeapClose);
+                s->curbuf ^= 1;
+                if (rc) return rc;
+            } else {
+                if (int rc = launch_direct<true>(s, dt, nullptr)) return rc;
+            }
             if (s->timers) {
                 NBMI_HIP_CHECK(hipEventRecord(s->ev[1], s->stream));
                 NBMI_HIP_CHECK(hipEventSynchronize(s->ev[1]));
@@ -4114,7 +4312,7 @@ int nbmi_step(nbmi_sim *s, double dt, int substeps) {
                 s->ms[3] += ms;
                 s->timed_steps++;
             }
-            s->curbuf ^= 1;
+            if (!leap) s->curbuf ^= 1;
             s->steps_taken++;
         }
     }
@@ -4196,6 +4394,43 @@ int nbmi_set_state(nbmi_sim *s, const double *pos, const double *vel) {
     NBMI_HIP_CHECK(hipGetLastError());
     s->tree_valid = false;
     s->maxabs_fused = false;
+    s->acc_valid = false;  // leapfrog: the stored acceleration belongs to the old positions
+    return 0;
+}
+
+int nbmi_set_integrator(nbmi_sim *s, int integrator) {
+    if (int rc = check_handle(s)) return rc;
+    if (integrator != NBMI_INTEGRATOR_KICK_DRIFT && integrator != NBMI_INTEGRATOR_LEAPFROG) {
+        nbmi::set_error("nbmi_set_integrator: unknown integrator %d", integrator);
+        return NBMI_ERR_ARG;
+    }
+    if (integrator == NBMI_INTEGRATOR_LEAPFROG) {
+        if (s->owner) {
+            nbmi::set_error("nbmi_set_integrator: owner-mode handles are not supported (leapfrog needs acceleration columns "
+                            "that the exchange rows do not carry)");
+            return NBMI_ERR_ARG;
+        }
+        if (s->shard_begin != 0 || s->shard_end != s->n) {
+            nbmi::set_error("nbmi_set_integrator: sharded handles are not supported (leapfrog needs acceleration columns "
+                            "that the exchange rows do not carry)");
+            return NBMI_ERR_ARG;
+        }
+        const char *a64 = getenv("NBMI_ACC64");
+        if (s->prec || s->walk_lane || (a64 && atoi(a64))) {
+            nbmi::set_error("nbmi_set_integrator: leapfrog is not available with the measurement-only walks (NBMI_PREC, "
+                            "NBMI_WALK_LANE, NBMI_ACC64)");
+            return NBMI_ERR_ARG;
+        }
+        if (s->integrator != NBMI_INTEGRATOR_LEAPFROG) s->acc_valid = false;  // the next step primes a = F(x)
+    }
+    s->integrator = integrator;
+    return 0;
+}
+
+int nbmi_get_integrator(nbmi_sim *s, int *out) {
+    if (int rc = check_handle(s)) return rc;
+    if (!out) { nbmi::set_error("null output"); return NBMI_ERR_ARG; }
+    *out = s->integrator;
     return 0;
 }
 
@@ -4486,6 +4721,10 @@ int nbmi_set_shard(nbmi_sim *s, int64_t begin, int64_t end) {
     if (int rc = check_handle(s)) return rc;
     if (begin < 0 || end < begin || end > s->n) {
         nbmi::set_error("nbmi_set_shard: bad range [%lld,%lld) for n=%lld", (long long)begin, (long long)end, (long long)s->n);
+        return NBMI_ERR_ARG;
+    }
+    if (s->integrator == NBMI_INTEGRATOR_LEAPFROG && (begin != 0 || end != s->n)) {
+        nbmi::set_error("nbmi_set_shard: leapfrog handles cannot be sharded (the exchange rows carry no acceleration columns)");
         return NBMI_ERR_ARG;
     }
     s->shard_begin = begin;

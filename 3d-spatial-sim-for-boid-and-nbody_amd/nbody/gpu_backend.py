@@ -27,6 +27,14 @@ METHOD_DIRECT = 1
 
 # distributions nbmi_create_generated draws on the device (NBMI_IC_* of include/nbmi.h)
 GENERATED_DISTRIBUTIONS = {"galaxy": 0, "collision": 1, "cluster": 2, "spiral": 3, "filament": 4}
+# integrators of nbmi_set_integrator (NBMI_INTEGRATOR_* of include/nbmi.h)
+INTEGRATORS = {"kick_drift": 0, "leapfrog": 1}
+
+
+def _integrator_code(name):
+    if name not in INTEGRATORS:
+        raise ValueError(f"integrator must be one of {sorted(INTEGRATORS)}, not {name!r}")
+    return INTEGRATORS[name]
 
 
 class Backend(Enum):
@@ -101,7 +109,9 @@ class _HIPSimulation:
 
     _method = METHOD_BARNES_HUT
 
-    def __init__(self, positions, velocities, masses, G, softening, damping, theta=0.5, device=None):
+    def __init__(self, positions, velocities, masses, G, softening, damping, theta=0.5, device=None,
+                 integrator="kick_drift"):
+        _integrator_code(integrator)
         lib = _nat.load()
         pos = _as_f64(positions, (3,))
         vel = _as_f64(velocities, (3,))
@@ -120,14 +130,18 @@ class _HIPSimulation:
             raise RuntimeError(f"nbmi_create failed: {_nat.last_error()}")
         kind = "Barnes-Hut" if self._method == METHOD_BARNES_HUT else "direct N^2"
         print(f"[HIP] Initialized with {self.n:,} bodies ({kind}) on device {self.device}")
+        if integrator != "kick_drift":
+            self.set_integrator(integrator)
 
     @classmethod
-    def generated(cls, distribution, n, spawn_radius, G, softening, damping, theta=0.5, seed=42, device=None):
+    def generated(cls, distribution, n, spawn_radius, G, softening, damping, theta=0.5, seed=42, device=None,
+                  integrator="kick_drift"):
         """Same backend object, but the bodies are drawn ON THE DEVICE from the reference's
         generate_distribution formulas (tools/presets.py:104-295, :350-397, :609-684; `distribution`
         one of GENERATED_DISTRIBUTIONS) with a Philox stream keyed by `seed`: statistical, not bit,
         parity with the NumPy generator; no host arrays, no upload."""
         kinds = GENERATED_DISTRIBUTIONS
+        _integrator_code(integrator)
         if distribution not in kinds:
             raise ValueError(f"device-side generator has {sorted(kinds)}, not {distribution!r}")
         self = cls.__new__(cls)
@@ -143,6 +157,8 @@ class _HIPSimulation:
         if not self._h:
             raise RuntimeError(f"nbmi_create_generated failed: {_nat.last_error()}")
         print(f"[HIP] Generated {self.n:,} bodies ({distribution}, seed {seed}) on device {self.device}")
+        if integrator != "kick_drift":
+            self.set_integrator(integrator)
         return self
 
     def get_masses(self) -> np.ndarray:
@@ -179,6 +195,22 @@ class _HIPSimulation:
     def step_many(self, dt: float, substeps: int):
         """`substeps` steps enqueued back to back without host round trips."""
         _nat.check(self._lib.nbmi_step(self._h, float(dt), int(substeps)), "nbmi_step")
+
+    def set_integrator(self, integrator: str):
+        """"kick_drift" (default, the reference's scheme) or "leapfrog" (synchronized kick-drift-kick: second order,
+        time-reversible, positions and velocities at the same instant; include/nbmi.h nbmi_set_integrator).  Owner-mode
+        and sharded handles and the measurement-only walks refuse leapfrog with ValueError."""
+        code = _integrator_code(integrator)
+        rc = self._lib.nbmi_set_integrator(self._h, code)
+        if rc == -1:  # NBMI_ERR_ARG: refused for this handle
+            raise ValueError(f"set_integrator({integrator!r}): {_nat.last_error()}")
+        _nat.check(rc, "nbmi_set_integrator")
+
+    @property
+    def integrator(self) -> str:
+        out = C.c_int(0)
+        _nat.check(self._lib.nbmi_get_integrator(self._h, C.addressof(out)), "nbmi_get_integrator")
+        return {v: k for k, v in INTEGRATORS.items()}[out.value]
 
     def step_count(self) -> int:
         """Steps the device has been asked to take since the handle was created (counted by the library)."""
@@ -266,7 +298,10 @@ class _HIPSimulation:
 
     # multi-GPU row exchange (device pointers; see nbody/sharded.py)
     def set_shard(self, begin, end):
-        _nat.check(self._lib.nbmi_set_shard(self._h, int(begin), int(end)), "nbmi_set_shard")
+        rc = self._lib.nbmi_set_shard(self._h, int(begin), int(end))
+        if rc == -1 and self.integrator == "leapfrog":
+            raise ValueError(f"set_shard: {_nat.last_error()}")
+        _nat.check(rc, "nbmi_set_shard")
 
     def set_exchange_sync(self, sync: bool):
         _nat.check(self._lib.nbmi_set_exchange_sync(self._h, 1 if sync else 0), "nbmi_set_exchange_sync")
@@ -411,6 +446,12 @@ class HIPOwnerSimulation(HIPBarnesHutSimulation):
     def n(self):
         return int(self._lib.nbmi_owner_count(self._h)) if self._h else 0
 
+    def set_integrator(self, integrator: str):
+        if _integrator_code(integrator) != INTEGRATORS["kick_drift"]:
+            raise ValueError("owner-mode handles support only the kick_drift integrator (the exchanged rows carry no "
+                             "acceleration columns)")
+        super().set_integrator(integrator)
+
     def ids(self):
         out = np.empty(self.n, dtype=np.int32)
         _nat.check(self._lib.nbmi_owner_get_ids(self._h, _nat.ptr(out)), "nbmi_owner_get_ids")
@@ -475,8 +516,9 @@ class HIPDirectSimulation(_HIPSimulation):
 
     _method = METHOD_DIRECT
 
-    def __init__(self, positions, velocities, masses, G, softening, damping, device=None):
-        super().__init__(positions, velocities, masses, G, softening, damping, theta=0.0, device=device)
+    def __init__(self, positions, velocities, masses, G, softening, damping, device=None, integrator="kick_drift"):
+        super().__init__(positions, velocities, masses, G, softening, damping, theta=0.0, device=device,
+                         integrator=integrator)
 
 
 # Reference thresholds (:618-620) exist because its GPU paths are O(N^2); the HIP Barnes-Hut
@@ -486,8 +528,9 @@ HIP_BH_THRESHOLD = 100_000_000  # = kMaxBodies of libnbmi.so (node links are 32-
 
 def create_gpu_simulation(positions: np.ndarray, velocities: np.ndarray, masses: np.ndarray, G: float,
                           softening: float, damping: float, theta: float = 0.5, force_gpu: bool = False,
-                          method: Optional[str] = None):
-    """Reference signature (:623-625) plus ``method`` ("barnes_hut" default, or "direct").
+                          method: Optional[str] = None, integrator: str = "kick_drift"):
+    """Reference signature (:623-625) plus ``method`` ("barnes_hut" default, or "direct") and ``integrator``
+    ("kick_drift" default, or "leapfrog"; see _HIPSimulation.set_integrator).
 
     Returns a backend object, or None if the HIP backend is not available / not selected."""
     backend, _info = get_backend()
@@ -496,8 +539,8 @@ def create_gpu_simulation(positions: np.ndarray, velocities: np.ndarray, masses:
         return None
     method = method or os.environ.get("NBMI_METHOD", "barnes_hut")
     if method == "direct":
-        return HIPDirectSimulation(positions, velocities, masses, G, softening, damping)
+        return HIPDirectSimulation(positions, velocities, masses, G, softening, damping, integrator=integrator)
     if n <= HIP_BH_THRESHOLD or force_gpu:
-        return HIPBarnesHutSimulation(positions, velocities, masses, G, softening, damping, theta)
+        return HIPBarnesHutSimulation(positions, velocities, masses, G, softening, damping, theta, integrator=integrator)
     print(f"[GPU] {n:,} bodies exceeds the HIP Barnes-Hut limit ({HIP_BH_THRESHOLD:,})")
     return None

@@ -50,10 +50,18 @@ def shard_bounds(n: int, world: int, rank: int):
     return per, begin, end
 
 
+def _refuse_leapfrog(integrator):
+    """The exchanged rows carry no acceleration columns: sharded and owner-mode runs integrate with kick-drift only."""
+    if integrator != "kick_drift":
+        raise ValueError(f"sharded N-body runs support only the kick_drift integrator, not {integrator!r}")
+
+
 class HipShardEngine:
     """Shard engine on top of HIPBarnesHutSimulation; rows travel as torch CUDA tensors."""
 
-    def __init__(self, positions, velocities, masses, G, softening, damping, theta, device, method="barnes_hut"):
+    def __init__(self, positions, velocities, masses, G, softening, damping, theta, device, method="barnes_hut",
+                 integrator="kick_drift"):
+        _refuse_leapfrog(integrator)
         import torch
         from .gpu_backend import HIPBarnesHutSimulation, HIPDirectSimulation
         self.torch = torch
@@ -144,11 +152,13 @@ class ShardedBarnesHut:
 
 
 def create_sharded_simulation(positions, velocities, masses, G, softening, damping, theta=0.5, mode="rows",
-                              method="barnes_hut"):
+                              method="barnes_hut", integrator="kick_drift"):
     """Build the multi-GPU stepper from the torch.distributed environment (RANK/LOCAL_RANK/
     WORLD_SIZE).  Every rank passes the same full arrays.  mode: "rows" (stage 1, replicated state and
     tree, bit-exact) or "let" (stage 2, owned key ranges + locally essential trees); method "direct"
-    shards the all-pairs kernel by body index through the row exchange."""
+    shards the all-pairs kernel by body index through the row exchange.  Only the kick_drift integrator:
+    "leapfrog" raises ValueError (the exchanged rows carry no acceleration columns)."""
+    _refuse_leapfrog(integrator)
     import os
     import torch
     import torch.distributed as dist
@@ -182,7 +192,9 @@ class HipLetEngine:
     SAMPLES = 256        # key samples per rank for the splitters
     LET_ROW_BYTES = 48   # float64 {cx, cy, cz, G m}, float s2t, uint next, float64 half size (nbmi_owner_let_row_bytes)
 
-    def __init__(self, positions, velocities, masses, G, softening, damping, theta, device, rank, world):
+    def __init__(self, positions, velocities, masses, G, softening, damping, theta, device, rank, world,
+                 integrator="kick_drift"):
+        _refuse_leapfrog(integrator)
         import torch
         from .gpu_backend import HIPBarnesHutSimulation, HIPOwnerSimulation
         self.torch = torch

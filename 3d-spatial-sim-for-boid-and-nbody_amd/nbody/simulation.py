@@ -155,8 +155,10 @@ class NBodySimulation:
         backend, info = get_backend()
         if backend != Backend.HIP:
             raise RuntimeError(f"[NBody] no HIP backend ({info}); this build has no CPU fallback")
+        # optional config key "integrator": "kick_drift" (the reference's scheme, default) or "leapfrog"
         self._gpu_sim = create_gpu_simulation(self.positions, self.velocities, self.masses, self.G, self.softening,
-                                              self.damping, theta=self.theta)
+                                              self.damping, theta=self.theta,
+                                              integrator=config.NBODY.get("integrator", "kick_drift"))
         if self._gpu_sim is None:
             raise RuntimeError("[NBody] create_gpu_simulation returned None; this build has no CPU fallback")
         self._use_gpu = True

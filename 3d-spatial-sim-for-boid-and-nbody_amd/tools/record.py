@@ -381,6 +381,8 @@ def record(config: dict, resume: bool = False, root: Path = None, quiet: bool = 
     dt = config["dt_per_frame"] / substeps
     if masses is None:
         masses = np.ones(n, dtype=np.float64)  # reference :752-753 [quirk]
+    # extra config key (metadata.json, only when not the default): "leapfrog" = synchronized kick-drift-kick
+    integrator = config.get("integrator", "kick_drift")
 
     backend, info = get_backend()
     if backend != Backend.HIP:
@@ -389,10 +391,12 @@ def record(config: dict, resume: bool = False, root: Path = None, quiet: bool = 
         from tools.presets import generate_distribution_device
         gpu_sim = generate_distribution_device(config.get("distribution", "galaxy"), n, config["spawn_radius"],
                                                config["G"], config["softening"], config["damping"],
-                                               theta=config.get("theta", 0.5), seed=42 if seed is None else seed)
+                                               theta=config.get("theta", 0.5), seed=42 if seed is None else seed,
+                                               integrator=integrator)
     else:
         gpu_sim = create_gpu_simulation(positions, velocities, masses, config["G"], config["softening"],
-                                        config["damping"], theta=config.get("theta", 0.5), force_gpu=True)
+                                        config["damping"], theta=config.get("theta", 0.5), force_gpu=True,
+                                        integrator=integrator)
     if gpu_sim is None:
         raise RuntimeError("[Record] create_gpu_simulation returned None")
     if device_ic:  # the state checkpoints carry the generated masses (0.1 for "filament"), not the unit default
@@ -406,10 +410,12 @@ def record(config: dict, resume: bool = False, root: Path = None, quiet: bool = 
     every = int(config.get("diagnostics_every") or 0)
     diag_path = rec_dir / DIAGNOSTICS_FILE
     last_diag = start_frame - 1
+    # (a leapfrog session's lines say so: their velocities, hence K and E, are synchronized with the positions)
+    diag_extra = {"integrator": integrator} if integrator != "kick_drift" else None
     if every > 0:
         if start_frame == 0:  # a run from frame 0 starts the file afresh, with the initial state
             v0 = gpu_sim.get_velocities()
-            extra = {"abs_momentum": float(np.sum(masses * np.sqrt(np.sum(v0 * v0, axis=1))))}
+            extra = {"abs_momentum": float(np.sum(masses * np.sqrt(np.sum(v0 * v0, axis=1)))), **(diag_extra or {})}
             first = diagnostics_line(gpu_sim, -1, substeps, dt, extra)
             _atomically(diag_path, lambda f: f.write(first.encode()))
         else:
@@ -418,7 +424,7 @@ def record(config: dict, resume: bool = False, root: Path = None, quiet: bool = 
     def write_diag(frame):
         nonlocal last_diag
         if every > 0 and (frame + 1) % every == 0 and frame > last_diag:
-            append_line(diag_path, diagnostics_line(gpu_sim, frame, substeps, dt))
+            append_line(diag_path, diagnostics_line(gpu_sim, frame, substeps, dt, diag_extra))
             last_diag = frame
 
     def write_frame(frame):
@@ -519,6 +525,7 @@ def show_status(session_name: str, root: Path = None) -> bool:
     print(f"  Bodies: {meta['num_bodies']:,}")
     print(f"  Theta: {meta['theta']}")
     print(f"  Distribution: {meta.get('distribution', 'unknown')}")
+    print(f"  Integrator: {meta.get('integrator', 'kick_drift')}")
     print(f"  Progress: {completed}/{total} frames ({completed / total * 100:.1f}%)")
     print(f"  Started: {meta.get('start_datetime', 'unknown')}")
     rows = read_diagnostics(rec_dir / DIAGNOSTICS_FILE)
@@ -565,7 +572,7 @@ def build_parser():
         epilog="Differences from the reference's recorder: there is no interactive menu (give --preset or "
                "--preset-id); --preset-id indexes this build's preset list (python -m tools.record --presets shows "
                "it); --dt sets dt_per_frame (the reference writes an unused 'dt' key); --presets, --seed, "
-               "--device-ic, --diagnostics and --root are additions.")
+               "--device-ic, --diagnostics, --integrator and --root are additions.")
     ap.add_argument("session", nargs="?", help="session name (for --resume, --status or --extend)")
     ap.add_argument("--resume", action="store_true", help="resume an interrupted recording (default: the most recent)")
     ap.add_argument("--extend", type=int, metavar="FRAMES", help="extend an existing recording by N frames")
@@ -585,6 +592,9 @@ def build_parser():
     ap.add_argument("--diagnostics", type=int, metavar="K",
                     help="every K frames append energy, momentum and angular momentum to diagnostics.jsonl "
                          "(stored in metadata.json as diagnostics_every)")
+    ap.add_argument("--integrator", choices=("kick_drift", "leapfrog"), default=None,
+                    help="kick_drift (default, the reference's scheme) or leapfrog (synchronized kick-drift-kick: second "
+                         "order, time-reversible; stored in metadata.json as integrator)")
     ap.add_argument("--root", type=Path, default=None, help="directory holding recordings/ (default: the package's)")
     return ap
 
@@ -628,6 +638,8 @@ def build_config(args) -> dict:
         if args.diagnostics <= 0:
             raise ValueError(f"--diagnostics: K must be positive, not {args.diagnostics}")
         config["diagnostics_every"] = int(args.diagnostics)
+    if args.integrator is not None and args.integrator != "kick_drift":  # the default writes no key
+        config["integrator"] = args.integrator
     return config
 
 

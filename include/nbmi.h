@@ -77,6 +77,25 @@ void nbmi_destroy(nbmi_sim *sim);
  * frame, tools/record.py:823-824).  Barnes-Hut: bounds -> keys -> sort -> octree -> walk with the
  * reference's kick-drift update fused in (simulation.py:308-317, 63-198, 201-278, 281-305). */
 int nbmi_step(nbmi_sim *sim, double dt, int substeps);
+/* Integrator of nbmi_step.
+ *   NBMI_INTEGRATOR_KICK_DRIFT (default): the reference's v = (v + a dt) damping; x += v dt (simulation.py:291-305), a
+ *     first-order scheme whose stored velocities lie half a step from the positions.
+ *   NBMI_INTEGRATOR_LEAPFROG: synchronized kick-drift-kick, second order and time-reversible (damping 1).  With a the stored
+ *     acceleration of the current positions, every substep is
+ *       v <- v + a dt/2;  x <- x + v dt;  a <- F(x) (octree build + walk, or direct N^2);  v <- (v + a dt/2) damping
+ *     and leaves (x, v) at the same instant with a = F(x).  Forces use the machinery of the current mode unchanged
+ *     (octree and accepted sets, nbmi_set_force_precision, direct N^2).  The stored a is dropped on create, by
+ *     nbmi_set_state, by a switch into leapfrog and when a capacity error is reported; the next nbmi_step then "primes"
+ *     it with one extra force evaluation a = F(x) (inside the step, so force precision "auto" sees its dt).  The first
+ *     leapfrog step allocates 24 bytes per body for a.  Getters, colours, frames and nbmi_diagnostics therefore see
+ *     synchronized velocities (no half-step offset in K and E); nbmi_diagnostics and nbmi_get_accelerations_f64 leave the
+ *     state and the stored a as they were.  A capacity error leaves the state at the last completed step, as in
+ *     kick-drift.  Owner-mode handles, handles with a proper shard (nbmi_set_shard, in either order of the calls) and the
+ *     measurement-only walks (NBMI_PREC, NBMI_WALK_LANE, NBMI_ACC64) refuse leapfrog with NBMI_ERR_ARG. */
+#define NBMI_INTEGRATOR_KICK_DRIFT 0
+#define NBMI_INTEGRATOR_LEAPFROG 1
+int nbmi_set_integrator(nbmi_sim *sim, int integrator);
+int nbmi_get_integrator(nbmi_sim *sim, int *out);
 /* Number of steps enqueued on this handle since it was created (every substep of nbmi_step counts).  The
  * recorder's Ctrl-C path asks the library, not its own bookkeeping, which frame the device has reached: an
  * interrupt is delivered when nbmi_step returns, before the caller can note that the step was taken
