@@ -2299,11 +2299,9 @@ __global__ __launch_bounds__(kBlock) void k_direct(const float4 *__restrict__ po
 // colour ramp (simulation.py:320-400 == gpu_backend.py:259-325), float64 maths, f32 stores,
 // rows written in the caller's body order.
 // ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void k_colors(Bodies cur, int64_t n, double max_speed, bool by_rank,
-                                                   float *__restrict__ colors) {
-    const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (r >= n) return;
-    const double vx = cur.vx[r], vy = cur.vy[r], vz = cur.vz[r];
+// (shared by k_colors and k_frame_snapshot: one ramp, so a snapshot's colours are nbmi_compute_colors' bit for bit)
+__device__ __forceinline__ void color_ramp(double vx, double vy, double vz, double max_speed, float &out_r, float &out_g,
+                                           float &out_b) {
     const double speed = sqrt(__dadd_rn(__dadd_rn(__dmul_rn(vx, vx), __dmul_rn(vy, vy)), __dmul_rn(vz, vz)));
     double t = speed / max_speed;
     t = t > 1.0 ? 1.0 : t;
@@ -2337,8 +2335,16 @@ __global__ __launch_bounds__(kBlock) void k_colors(Bodies cur, int64_t n, double
         s = (t - 0.99) / 0.01;
         cr = 1.0; cg = __dsub_rn(0.5, __dmul_rn(0.5, s)); cb = 0.0;
     }
+    out_r = (float)cr; out_g = (float)cg; out_b = (float)cb;
+}
+__global__ __launch_bounds__(kBlock) void k_colors(Bodies cur, int64_t n, double max_speed, bool by_rank,
+                                                   float *__restrict__ colors) {
+    const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (r >= n) return;
+    float cr, cg, cb;
+    color_ramp(cur.vx[r], cur.vy[r], cur.vz[r], max_speed, cr, cg, cb);
     const int64_t o = 3 * (by_rank ? r : (int64_t)cur.id[r]);  // owner mode: rows stay in rank order
-    colors[o] = (float)cr; colors[o + 1] = (float)cg; colors[o + 2] = (float)cb;
+    colors[o] = cr; colors[o + 1] = cg; colors[o + 2] = cb;
 }
 
 // ---- un-permuting getters ------------------------------------------------------------
@@ -2363,16 +2369,79 @@ __global__ __launch_bounds__(kBlock) void k_unperm3_f64(const double *__restrict
 // (record.py:254-262; decoder :313-322), float32 arithmetic like NumPy's, C-cast wrap beyond +-32.767 kept
 // [quirk].  `prev` (float32, caller's body order) lives in HBM and is advanced to what the decoder will
 // reconstruct, prev + int16 / 1000, so only 6 bytes per body and array cross PCIe instead of 12.
+// (shared by k_frame_delta and k_frame_snapshot) the int16 of one value; `p` becomes what the decoder reconstructs
+__device__ __forceinline__ int16_t frame_quantize(float cur, float &p) {
+    const float t = __fmul_rn(__fsub_rn(cur, p), 1000.0f);
+    // float -> int32 (truncation toward zero) -> low 16 bits: what ndarray.astype(np.int16) does on x86-64
+    const int16_t q = (int16_t)(int)t;
+    p = __fadd_rn(p, __fdiv_rn((float)q, 1000.0f));
+    return q;
+}
 __global__ __launch_bounds__(kBlock) void k_frame_delta(const float *__restrict__ cur, float *__restrict__ prev, int64_t count,
                                                         int16_t *__restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= count) return;
-    const float p = prev[i];
-    const float t = __fmul_rn(__fsub_rn(cur[i], p), 1000.0f);
-    // float -> int32 (truncation toward zero) -> low 16 bits: what ndarray.astype(np.int16) does on x86-64
-    const int16_t q = (int16_t)(int)t;
-    out[i] = q;
-    prev[i] = __fadd_rn(p, __fdiv_rn((float)q, 1000.0f));
+    float p = prev[i];
+    out[i] = frame_quantize(cur[i], p);
+    prev[i] = p;
+}
+
+// ---- asynchronous frames (nbmi_frame_begin) -------------------------------------------------
+// What the snapshot copies of the device-side error words, so that nbmi_frame_wait can report them without touching the
+// compute stream.  64 bytes in front of a slot's payload.
+struct FrameHeader {
+    int error, sticky_error, max_run;
+    unsigned sort_error;
+    long long num_nodes, sticky_nodes;
+    long long pad[4];
+};
+static_assert(sizeof(FrameHeader) == 64, "slot payloads start 64 bytes into the slot");
+// One pass over the state in its own (key-sorted) order: colour (k_colors' ramp) and float32 position (k_unperm3_f32's
+// conversion) of every body go to row `id` of the slot - and the colour to `colors`, as nbmi_compute_colors leaves it.
+//   NBMI_FRAME_F32        first = positions, second = colours, float32
+//   NBMI_FRAME_KEY        the same, and the row also becomes the previous decoded frame
+//   NBMI_FRAME_DELTA_I16  positions go to the float32 staging rows; two k_frame_delta launches then write the int16 deltas
+//                         of positions and colours against the previous decoded frame into the slot and advance it
+// Nothing that a later step writes is read after this kernel: the copy to the host reads the slot only.
+template <int KIND>
+__global__ __launch_bounds__(kBlock) void k_frame_snapshot(Bodies cur, int64_t n, double max_speed, float *__restrict__ colors,
+                                                           float *__restrict__ prev, void *__restrict__ first,
+                                                           void *__restrict__ second, const TreeInfo *__restrict__ info,
+                                                           const unsigned *__restrict__ sort_error,
+                                                           FrameHeader *__restrict__ header) {
+    const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (r == 0) {
+        header->error = info->error;
+        header->sticky_error = info->sticky_error;
+        header->max_run = info->max_run;
+        header->sort_error = sort_error ? *sort_error : 0u;
+        header->num_nodes = info->num_nodes;
+        header->sticky_nodes = info->sticky_nodes;
+    }
+    if (r >= n) return;
+    float c[3], p[3];
+    color_ramp(cur.vx[r], cur.vy[r], cur.vz[r], max_speed, c[0], c[1], c[2]);
+    p[0] = (float)cur.x[r]; p[1] = (float)cur.y[r]; p[2] = (float)cur.z[r];
+    const int64_t o = 3 * (int64_t)cur.id[r];
+    for (int k = 0; k < 3; k++) colors[o + k] = c[k];
+    if (KIND == NBMI_FRAME_DELTA_I16) {
+        // `first` is the float32 staging row here: the quantisation against `prev` follows as k_frame_delta over the rows in
+        // memory order.  (Quantising here, per body, was measured at 249 us for 1 M bodies and 2.95 ms for 10 M against
+        // 65 / 565 us for the four kernels of the synchronous path: every access to prev and to the int16 rows is then a
+        // scattered partial line, seven scattered streams instead of two.)
+        float *fp = (float *)first;
+        for (int k = 0; k < 3; k++) fp[o + k] = p[k];
+    } else {
+        float *fp = (float *)first, *fc = (float *)second;
+        for (int k = 0; k < 3; k++) {
+            fp[o + k] = p[k];
+            fc[o + k] = c[k];
+            if (KIND == NBMI_FRAME_KEY) {
+                prev[o + k] = p[k];
+                prev[3 * n + o + k] = c[k];
+            }
+        }
+    }
 }
 
 __global__ __launch_bounds__(kBlock) void k_split_state(const double *__restrict__ pos, const double *__restrict__ vel,
@@ -3517,6 +3586,17 @@ struct nbmi_sim {
     float *frame_prev = nullptr;
     int16_t *frame_q = nullptr;
     bool frame_have_prev = false;
+    // asynchronous frames (nbmi_frame_begin): per slot one device and one pinned host buffer of a FrameHeader + 24 bytes
+    // per body, filled by k_frame_snapshot on `stream` and copied out on `frame_stream`; allocated by the first begin
+    struct FrameSlot {
+        char *dev = nullptr, *host = nullptr;
+        hipEvent_t ev_snap = nullptr, ev_done = nullptr;  // snapshot written (on stream) / copy complete (on frame_stream)
+        bool begun = false, used = false;
+        int kind = 0;
+        int64_t steps = 0, seq = 0;
+    } frame_slot[NBMI_FRAME_SLOTS];
+    hipStream_t frame_stream = nullptr;
+    int64_t frame_seq = 0;
     // render-side reduction scratch (nbmi_visible_points), allocated on first use
     uint8_t *vis_flag = nullptr;
     uint32_t *vis_slot = nullptr, *vis_tiles = nullptr;
@@ -4036,6 +4116,15 @@ void nbmi_destroy(nbmi_sim *s) {
         (void)hipStreamDestroy(s->side);
         (void)hipEventDestroy(s->ev_walked);
         (void)hipEventDestroy(s->ev_cut);
+    }
+    if (s->frame_stream) {
+        (void)hipStreamSynchronize(s->frame_stream);
+        (void)hipStreamDestroy(s->frame_stream);
+    }
+    for (auto &f : s->frame_slot) {
+        if (f.ev_snap) (void)hipEventDestroy(f.ev_snap);
+        if (f.ev_done) (void)hipEventDestroy(f.ev_done);
+        if (f.host) (void)hipHostFree(f.host);
     }
     for (void *p : s->allocs) (void)hipFree(p);
     for (auto &e : s->ev)
@@ -5221,6 +5310,143 @@ int nbmi_frame_set_previous(nbmi_sim *s, const float *pos, const float *col) {
     NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
     s->frame_have_prev = true;
     return 0;
+}
+
+// ---- asynchronous frames: snapshot on the compute stream, copy on a stream of its own ------
+namespace {
+int frame_slots_alloc(nbmi_sim *s) {
+    if (s->frame_stream) return 0;
+    const size_t bytes = sizeof(FrameHeader) + (size_t)24 * (size_t)(s->n ? s->n : 1);
+    for (auto &f : s->frame_slot) {
+        if (!f.dev && dev_alloc(s, &f.dev, bytes)) return NBMI_ERR_HIP;
+        if (!f.host) NBMI_HIP_CHECK(hipHostMalloc((void **)&f.host, bytes));
+        if (!f.ev_snap) NBMI_HIP_CHECK(hipEventCreateWithFlags(&f.ev_snap, hipEventDisableTiming));
+        if (!f.ev_done) NBMI_HIP_CHECK(hipEventCreateWithFlags(&f.ev_done, hipEventDisableTiming));
+    }
+    NBMI_HIP_CHECK(hipStreamCreateWithFlags(&s->frame_stream, hipStreamNonBlocking));
+    return 0;
+}
+int frame_slot_check(nbmi_sim *s, int slot, const char *what) {
+    if (slot < 0 || slot >= NBMI_FRAME_SLOTS || !s->frame_slot[slot].begun) {
+        nbmi::set_error("%s: slot %d holds no frame (not begun, or already released)", what, slot);
+        return NBMI_ERR_ARG;
+    }
+    return 0;
+}
+size_t frame_item_bytes(int kind) { return kind == NBMI_FRAME_DELTA_I16 ? 6 : 12; }  // per body and array
+}  // namespace
+
+int nbmi_frame_begin(nbmi_sim *s, int kind, double max_speed, int *slot) {
+    if (int rc = check_handle(s)) return rc;
+    if (!slot) { nbmi::set_error("nbmi_frame_begin: null output"); return NBMI_ERR_ARG; }
+    if (s->owner) { nbmi::set_error("nbmi_frame_begin: not available on an owner-mode handle"); return NBMI_ERR_ARG; }
+    if (kind != NBMI_FRAME_F32 && kind != NBMI_FRAME_KEY && kind != NBMI_FRAME_DELTA_I16) {
+        nbmi::set_error("nbmi_frame_begin: unknown kind %d", kind);
+        return NBMI_ERR_ARG;
+    }
+    const int64_t n = s->n;
+    if (kind == NBMI_FRAME_DELTA_I16 && !s->frame_have_prev && n != 0) {
+        nbmi::set_error("nbmi_frame_begin: no previous frame on the device (call nbmi_frame_keyframe or "
+                        "nbmi_frame_set_previous first)");
+        return NBMI_ERR_ARG;
+    }
+    int k = -1;
+    for (int i = 0; i < NBMI_FRAME_SLOTS && k < 0; i++)
+        if (!s->frame_slot[i].begun) k = i;
+    if (k < 0) { nbmi::set_error("nbmi_frame_begin: no free frame slot (release one first)"); return NBMI_ERR_ARG; }
+    if (int rc = frame_slots_alloc(s)) return rc;
+    if (kind != NBMI_FRAME_F32 && n != 0)
+        if (int rc = frame_alloc(s)) return rc;
+    nbmi_sim::FrameSlot &f = s->frame_slot[k];
+    if (n != 0) {
+        // (a slot released without a wait may still be in its copy: the stream waits, the host does not)
+        if (f.used) NBMI_HIP_CHECK(hipStreamWaitEvent(s->stream, f.ev_done, 0));
+        const size_t item = frame_item_bytes(kind) * (size_t)n;
+        FrameHeader *hd = (FrameHeader *)f.dev;
+        void *first = f.dev + sizeof(FrameHeader), *second = f.dev + sizeof(FrameHeader) + item;
+        const Bodies cur = s->buf[s->curbuf];
+        const unsigned *se = s->tmp_sort ? (const unsigned *)nbmi::sort_error_device_word(s->tmp_sort) : nullptr;
+        if (kind == NBMI_FRAME_F32)
+            k_frame_snapshot<NBMI_FRAME_F32><<<nblocks(n), kBlock, 0, s->stream>>>(cur, n, max_speed, s->colors, nullptr, first,
+                                                                                    second, s->info, se, hd);
+        else if (kind == NBMI_FRAME_KEY)
+            k_frame_snapshot<NBMI_FRAME_KEY><<<nblocks(n), kBlock, 0, s->stream>>>(cur, n, max_speed, s->colors, s->frame_prev,
+                                                                                    first, second, s->info, se, hd);
+        else {
+            float *rows = (float *)s->stage;  // (like frame_current) nothing later on the stream reads it before writing it
+            k_frame_snapshot<NBMI_FRAME_DELTA_I16><<<nblocks(n), kBlock, 0, s->stream>>>(cur, n, max_speed, s->colors, nullptr,
+                                                                                          rows, nullptr, s->info, se, hd);
+            k_frame_delta<<<nblocks(3 * n), kBlock, 0, s->stream>>>(rows, s->frame_prev, 3 * n, (int16_t *)first);
+            k_frame_delta<<<nblocks(3 * n), kBlock, 0, s->stream>>>(s->colors, s->frame_prev + 3 * n, 3 * n, (int16_t *)second);
+        }
+        NBMI_HIP_CHECK(hipGetLastError());
+        NBMI_HIP_CHECK(hipEventRecord(f.ev_snap, s->stream));
+        NBMI_HIP_CHECK(hipStreamWaitEvent(s->frame_stream, f.ev_snap, 0));
+        NBMI_HIP_CHECK(hipMemcpyAsync(f.host, f.dev, sizeof(FrameHeader) + 2 * item, hipMemcpyDeviceToHost, s->frame_stream));
+        NBMI_HIP_CHECK(hipEventRecord(f.ev_done, s->frame_stream));
+        f.used = true;
+        if (kind == NBMI_FRAME_KEY) s->frame_have_prev = true;
+    }
+    f.begun = true;
+    f.kind = kind;
+    f.steps = s->steps_taken;
+    f.seq = ++s->frame_seq;
+    *slot = k;
+    return 0;
+}
+
+int nbmi_frame_wait(nbmi_sim *s, int slot, const void **first, const void **second, int *kind, int64_t *steps) {
+    if (int rc = check_handle(s)) return rc;
+    if (int rc = frame_slot_check(s, slot, "nbmi_frame_wait")) return rc;
+    nbmi_sim::FrameSlot &f = s->frame_slot[slot];
+    const int64_t n = s->n;
+    if (n != 0) {
+        NBMI_HIP_CHECK(hipEventSynchronize(f.ev_done));  // this slot's copy only: the compute stream keeps running
+        const FrameHeader h = *(const FrameHeader *)f.host;
+        // the words check_device_error reads, as they stood at the snapshot; they stay set on the device, so the next
+        // nbmi_sync / getter still reports and clears them
+        if (h.sort_error) {
+            nbmi::set_error("device radix sort: a look-back spin timed out; the steps since the last synchronisation are invalid");
+            return NBMI_ERR_HIP;
+        }
+        if (h.max_run > 4096 && s->sort_bits < 63) s->sort_bits = s->sort_bits + 8 < 63 ? s->sort_bits + 8 : 63;
+        if (h.error || h.sticky_error) {
+            nbmi::set_error("octree needs %lld nodes, more than the %lld rows allocated (4N, as the reference); the "
+                            "bodies were not advanced from that step on",
+                            (long long)(h.sticky_error ? h.sticky_nodes : h.num_nodes), (long long)s->node_capacity);
+            return NBMI_ERR_CAPACITY;
+        }
+    }
+    const char *base = f.host + sizeof(FrameHeader);
+    if (first) *first = base;
+    if (second) *second = base + frame_item_bytes(f.kind) * (size_t)n;
+    if (kind) *kind = f.kind;
+    if (steps) *steps = f.steps;
+    return 0;
+}
+
+int nbmi_frame_release(nbmi_sim *s, int slot) {
+    if (int rc = check_handle(s)) return rc;
+    if (int rc = frame_slot_check(s, slot, "nbmi_frame_release")) return rc;
+    s->frame_slot[slot].begun = false;
+    return 0;
+}
+
+int nbmi_frame_pending(nbmi_sim *s, int *slots, int *kinds, int64_t *steps) {
+    if (int rc = check_handle(s)) return rc;
+    int order[NBMI_FRAME_SLOTS], count = 0;
+    for (int i = 0; i < NBMI_FRAME_SLOTS; i++) {
+        if (!s->frame_slot[i].begun) continue;
+        int j = count++;
+        for (; j > 0 && s->frame_slot[order[j - 1]].seq > s->frame_slot[i].seq; j--) order[j] = order[j - 1];
+        order[j] = i;
+    }
+    for (int j = 0; j < count; j++) {
+        if (slots) slots[j] = order[j];
+        if (kinds) kinds[j] = s->frame_slot[order[j]].kind;
+        if (steps) steps[j] = s->frame_slot[order[j]].steps;
+    }
+    return count;
 }
 
 namespace {

@@ -336,5 +336,6 @@ hipError_t radix_init_temp(void *temp, hipStream_t s) { return hipMemsetAsync(te
 hipError_t radix_error_word(const void *temp, unsigned *out, hipStream_t s) {
     return hipMemcpyAsync(out, &((const Control *)temp)->error, sizeof(unsigned), hipMemcpyDeviceToHost, s);
 }
+const void *radix_error_device_word(const void *temp) { return &((const Control *)temp)->error; }
 
 }  // namespace nbmi

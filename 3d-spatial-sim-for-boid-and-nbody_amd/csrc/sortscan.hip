@@ -21,6 +21,7 @@ hipError_t sort_pairs_u64_u32(void *temp, size_t temp_bytes, const uint64_t *kin
 // the sticky error word of the sort (a look-back spin that timed out)
 hipError_t sort_init_temp(void *temp, hipStream_t s) { return radix_init_temp(temp, s); }
 hipError_t sort_error_word(const void *temp, unsigned *out, hipStream_t s) { return radix_error_word(temp, out, s); }
+const void *sort_error_device_word(const void *temp) { return radix_error_device_word(temp); }
 
 size_t sort_pairs32_temp_bytes(size_t n, int begin_bit, int end_bit) { return radix_temp_bytes_u32(n, end_bit - begin_bit); }
 

@@ -74,6 +74,10 @@ PROTOTYPES = {
     "nbmi_frame_keyframe": (C.c_int, [_vp, _vp, _vp]),
     "nbmi_frame_delta_i16": (C.c_int, [_vp, _vp, _vp]),
     "nbmi_frame_set_previous": (C.c_int, [_vp, _vp, _vp]),
+    "nbmi_frame_begin": (C.c_int, [_vp, C.c_int, _dbl, _vp]),
+    "nbmi_frame_wait": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "nbmi_frame_release": (C.c_int, [_vp, C.c_int]),
+    "nbmi_frame_pending": (C.c_int, [_vp, _vp, _vp, _vp]),
     "nbmi_debug_sort_pairs": (C.c_int, [C.c_int, _i64, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "nbmi_render_create": (_vp, [C.c_int, C.c_int, C.c_int]),
     "nbmi_render_destroy": (None, [_vp]),

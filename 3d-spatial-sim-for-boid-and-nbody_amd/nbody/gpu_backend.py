@@ -296,6 +296,63 @@ class _HIPSimulation:
         c = np.ascontiguousarray(colors, dtype=np.float32)
         _nat.check(self._lib.nbmi_frame_set_previous(self._h, _nat.ptr(p), _nat.ptr(c)), "nbmi_frame_set_previous")
 
+    # asynchronous frames (include/nbmi.h nbmi_frame_begin)
+    FRAME_KINDS = {"f32": 0, "key": 1, "delta": 2}
+
+    def frame_begin(self, kind="f32", max_speed=15.0) -> int:
+        """Enqueue a frame of the current state and return its slot without waiting: "f32" = what compute_colors(max_speed)
+        + get_positions() + get_colors() return, "key" / "delta" = frame_keyframe() / frame_delta() with the colour pass
+        included.  Steps enqueued afterwards do not change the frame.  Two slots: a third begin without a frame_release
+        raises ValueError, as does "delta" without a previous frame."""
+        if kind not in self.FRAME_KINDS:
+            raise ValueError(f"frame kind must be one of {sorted(self.FRAME_KINDS)}, not {kind!r}")
+        slot = C.c_int(-1)
+        rc = self._lib.nbmi_frame_begin(self._h, self.FRAME_KINDS[kind], float(max_speed), C.addressof(slot))
+        if rc == -1:  # NBMI_ERR_ARG: no free slot / no previous frame / owner mode
+            raise ValueError(f"frame_begin({kind!r}): {_nat.last_error()}")
+        _nat.check(rc, "nbmi_frame_begin")
+        return int(slot.value)
+
+    def frame_wait(self, slot: int):
+        """Wait for that slot's copy (not for the steps enqueued since) and return its two (N,3) arrays: float32 positions
+        and colours, or int16 position and colour deltas.  They are read-only views of the slot's pinned memory, not
+        copies: they die with frame_release(slot) - copy what has to live longer.  Deferred device errors raise as in
+        sync(), as they stood at the begin."""
+        first, second = C.c_void_p(0), C.c_void_p(0)
+        kind, steps = C.c_int(0), C.c_int64(0)
+        rc = self._lib.nbmi_frame_wait(self._h, int(slot), C.addressof(first), C.addressof(second), C.addressof(kind),
+                                       C.addressof(steps))
+        if rc == -1:
+            raise ValueError(f"frame_wait({slot}): {_nat.last_error()}")
+        _nat.check(rc, "nbmi_frame_wait")
+        dtype = np.dtype(np.int16 if kind.value == self.FRAME_KINDS["delta"] else np.float32)
+
+        def view(p):
+            if self.n == 0:
+                a = np.empty((0, 3), dtype=dtype)
+            else:
+                a = np.frombuffer((C.c_char * (self.n * 3 * dtype.itemsize)).from_address(p.value), dtype=dtype).reshape(self.n, 3)
+            a.flags.writeable = False
+            return a
+        return view(first), view(second)
+
+    def frame_release(self, slot: int):
+        """Free the slot for the next frame_begin; the arrays frame_wait returned for it must no longer be used."""
+        rc = self._lib.nbmi_frame_release(self._h, int(slot))
+        if rc == -1:
+            raise ValueError(f"frame_release({slot}): {_nat.last_error()}")
+        _nat.check(rc, "nbmi_frame_release")
+
+    def frames_pending(self):
+        """[(slot, kind, steps), ...] of the frames begun and not released, oldest first; steps = step_count() at the
+        begin.  Kept by the library, so it is right even when an interrupt cut the call that began a frame."""
+        slots, kinds, steps = (C.c_int * 2)(), (C.c_int * 2)(), (C.c_int64 * 2)()
+        k = self._lib.nbmi_frame_pending(self._h, slots, kinds, steps)
+        if k < 0:
+            _nat.check(k, "nbmi_frame_pending")
+        names = {v: n for n, v in self.FRAME_KINDS.items()}
+        return [(int(slots[i]), names[kinds[i]], int(steps[i])) for i in range(k)]
+
     # multi-GPU row exchange (device pointers; see nbody/sharded.py)
     def set_shard(self, begin, end):
         rc = self._lib.nbmi_set_shard(self._h, int(begin), int(end))

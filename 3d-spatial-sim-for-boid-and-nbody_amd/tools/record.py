@@ -12,7 +12,10 @@ The interactive menus, progress bars and the background compressor thread are UX
 reproduced; ``compress_recording`` converts finished .npz frames to .zstd with the same delta
 chaining, and ``record(config with "zstd": True)`` writes .zstd frames directly: the int16 delta
 payload is quantised ON THE DEVICE against the previous decoded frame kept in HBM (12 instead of
-24 bytes per body over PCIe), zstd runs on the host.  ``extend_recording`` is the reference's
+24 bytes per body over PCIe), zstd runs on the host.  With the config key "pipeline" (``--pipeline``) the loop
+overlaps host and device instead of the reference's compressor thread: frames are fetched asynchronously
+(``frame_begin`` / ``frame_wait``) and frame k - 1 is written while the device computes frame k; the files are the
+same bytes (``record_pipelined``).  ``extend_recording`` is the reference's
 ``--extend`` (:1156-1199); Ctrl-C leaves a state checkpoint like the reference (:916-935).  ``main`` is the
 reference's command line (``python -m tools.record``, :1128-1283) without the interactive menu; its --help lists
 the differences.  zstd comes from the system libzstd through ctypes (python-zstandard is
@@ -337,6 +340,79 @@ def _generate_initial_conditions(config: dict):
     return p.astype(np.float64), v.astype(np.float64), m.astype(np.float64)
 
 
+def record_pipelined(gpu_sim, rec_dir: Path, start_frame: int, total_frames: int, substeps: int, dt: float,
+                     direct_zstd: bool, every: int, write_diag, write_state):
+    """The recording loop of ``record(config with "pipeline": True)``: the files of the sequential loop, but
+    the host compresses and writes frame k - 1 while the device computes frame k.  Per frame: step_many (enqueue),
+    frame_begin (enqueue: one snapshot kernel, then the copy on a stream of its own), then the PREVIOUS frame is finished:
+    frame_wait, its file through the sequential loop's writers, frame_release.  Where a diagnostics line (`every`) or a
+    state checkpoint is due the frame itself is finished first - write_diag(frame) / write_state(frame, compressed=False)
+    are the caller's synchronous writers, and the checkpoint stays the state of exactly the last frame on disk.
+
+    `gpu_sim` needs step_many, frame_begin, frame_wait, frame_release, frames_pending and step_count (the backend object,
+    or a stand-in: nothing here touches a device).  On Ctrl-C the library is asked which frames are in flight and where
+    the device stands; every pending frame is written from its slot (a delta frame as a delta: the slot still holds the
+    payload), a stepped frame that has no slot yet is taken, then the diagnostics line and the compressed checkpoint of
+    the frame the device is at, and the interrupt is re-raised.  Returns the last frame written."""
+    rec_dir = Path(rec_dir)
+
+    def kind_of(frame):
+        return ("key" if frame == 0 else "delta") if direct_zstd else "f32"
+
+    def on_disk(frame):
+        return any(q.exists() for q in _frame_paths(rec_dir, frame))
+
+    def finish(slot, frame, kind):
+        a, b = gpu_sim.frame_wait(slot)
+        if kind == "f32":
+            save_frame(rec_dir, frame, a, b)
+        else:
+            zf, _ = _frame_paths(rec_dir, frame)
+            write_bytes_atomic(zf, pack_container(1 if kind == "key" else 2, a.tobytes(), b.tobytes()))
+        gpu_sim.frame_release(slot)
+
+    frame = start_frame - 1
+    held = None  # the frame begun and not yet written: (slot, frame, kind)
+    try:
+        for frame in range(start_frame, total_frames):
+            gpu_sim.step_many(dt, substeps)
+            kind = kind_of(frame)
+            slot = gpu_sim.frame_begin(kind, 15.0)
+            if held is not None:
+                finish(*held)
+            held = (slot, frame, kind)
+            state_due = (frame + 1) % STATE_EVERY == 0
+            if state_due or (every > 0 and (frame + 1) % every == 0):
+                finish(*held)
+                held = None
+                write_diag(frame)  # before the state checkpoint: a resume from it finds every line up to its frame
+                if state_due:
+                    write_state(frame)
+                    old = rec_dir / f"state_{frame - STATE_EVERY:04d}.npz"
+                    if old.exists():
+                        old.unlink()
+        if held is not None:
+            finish(*held)
+            held = None
+    except KeyboardInterrupt:
+        # asked of the library, not of `held`: the interrupt may have come between a C call and the assignment
+        pending = gpu_sim.frames_pending()
+        at = start_frame - 1 + gpu_sim.step_count() // max(substeps, 1)
+        for slot, kind, steps in pending:
+            f = start_frame - 1 + steps // max(substeps, 1)
+            if on_disk(f):  # written, not yet released
+                gpu_sim.frame_release(slot)
+            else:           # not written - or its write was cut short, which left nothing (_atomically)
+                finish(slot, f, kind)
+        if at >= start_frame and not on_disk(at):  # stepped, no slot yet: the chain stands at frame at - 1, so the normal kind
+            finish(gpu_sim.frame_begin(kind_of(at), 15.0), at, kind_of(at))
+        if at >= 0:
+            write_diag(at)
+            write_state(at, compressed=True)
+        raise
+    return frame
+
+
 def record(config: dict, resume: bool = False, root: Path = None, quiet: bool = False, seed=None):
     """The reference's record() on the GPU branch (:760-775, :821-876): per frame `substeps` x
     step(dt_per_frame/substeps), compute_colors(15.0), get_positions, get_colors, raw frame;
@@ -451,6 +527,19 @@ def record(config: dict, resume: bool = False, root: Path = None, quiet: bool = 
         p32, c32 = gpu_sim.frame_keyframe()
         write_bytes_atomic(zf, pack_container(1, p32.tobytes(), c32.tobytes()))
 
+    if config.get("pipeline"):  # extra config key (metadata.json, only when set): the overlapped loop
+        try:
+            record_pipelined(gpu_sim, rec_dir, start_frame, total_frames, substeps, dt, direct_zstd, every, write_diag,
+                             write_state)
+        except KeyboardInterrupt:
+            at = start_frame - 1 + gpu_sim.step_count() // max(substeps, 1)
+            say(f"\n[Record] Paused at frame {at}; resume with record(config, resume=True)")
+            gpu_sim.close()
+            raise
+        say(f"[Record] {total_frames - start_frame} frames in {time.time() - t0:.2f}s -> {rec_dir} (pipelined)")
+        gpu_sim.close()
+        return rec_dir
+
     frame = start_frame - 1
     try:
         for frame in range(start_frame, total_frames):
@@ -526,6 +615,7 @@ def show_status(session_name: str, root: Path = None) -> bool:
     print(f"  Theta: {meta['theta']}")
     print(f"  Distribution: {meta.get('distribution', 'unknown')}")
     print(f"  Integrator: {meta.get('integrator', 'kick_drift')}")
+    print(f"  Pipeline: {'on' if meta.get('pipeline') else 'off'}")
     print(f"  Progress: {completed}/{total} frames ({completed / total * 100:.1f}%)")
     print(f"  Started: {meta.get('start_datetime', 'unknown')}")
     rows = read_diagnostics(rec_dir / DIAGNOSTICS_FILE)
@@ -572,7 +662,7 @@ def build_parser():
         epilog="Differences from the reference's recorder: there is no interactive menu (give --preset or "
                "--preset-id); --preset-id indexes this build's preset list (python -m tools.record --presets shows "
                "it); --dt sets dt_per_frame (the reference writes an unused 'dt' key); --presets, --seed, "
-               "--device-ic, --diagnostics, --integrator and --root are additions.")
+               "--device-ic, --diagnostics, --integrator, --pipeline and --root are additions.")
     ap.add_argument("session", nargs="?", help="session name (for --resume, --status or --extend)")
     ap.add_argument("--resume", action="store_true", help="resume an interrupted recording (default: the most recent)")
     ap.add_argument("--extend", type=int, metavar="FRAMES", help="extend an existing recording by N frames")
@@ -595,6 +685,9 @@ def build_parser():
     ap.add_argument("--integrator", choices=("kick_drift", "leapfrog"), default=None,
                     help="kick_drift (default, the reference's scheme) or leapfrog (synchronized kick-drift-kick: second "
                          "order, time-reversible; stored in metadata.json as integrator)")
+    ap.add_argument("--pipeline", action="store_true",
+                    help="write frame k - 1 while the device computes frame k (asynchronous frame fetch; the same files; "
+                         "stored in metadata.json as pipeline)")
     ap.add_argument("--root", type=Path, default=None, help="directory holding recordings/ (default: the package's)")
     return ap
 
@@ -640,6 +733,8 @@ def build_config(args) -> dict:
         config["diagnostics_every"] = int(args.diagnostics)
     if args.integrator is not None and args.integrator != "kick_drift":  # the default writes no key
         config["integrator"] = args.integrator
+    if getattr(args, "pipeline", False):  # the default writes no key
+        config["pipeline"] = True
     return config
 
 

@@ -346,6 +346,43 @@ int nbmi_frame_keyframe(nbmi_sim *sim, float *out_positions_xyz, float *out_colo
 int nbmi_frame_delta_i16(nbmi_sim *sim, int16_t *out_dpos, int16_t *out_dcol);
 int nbmi_frame_set_previous(nbmi_sim *sim, const float *positions_xyz, const float *colors_rgb);
 
+/* Asynchronous frames: take a frame without stopping the simulation.
+ * A handle has NBMI_FRAME_SLOTS = 2 slots.  A slot is one device buffer and one pinned host buffer (hipHostMalloc) of
+ * 24 bytes per body each, plus a 64-byte header.  They are allocated by the first nbmi_frame_begin - 2 x 24 bytes per
+ * body on the device and the same again pinned on the host: 2.4 GB each at 50 M bodies - together with a copy stream and
+ * two events per slot, and freed by nbmi_destroy.
+ *   nbmi_frame_begin    only enqueues and never waits.  On the handle's stream one kernel reads the state once and writes
+ *                       the frame (a delta frame: its float32 rows, which nbmi_frame_delta_i16's kernel then quantises)
+ *                       into a free slot's device buffer in the caller's body order: float32 positions (as
+ *                       nbmi_get_positions_f32) and the colours nbmi_compute_colors(sim, max_speed) computes - which it
+ *                       also leaves where that call leaves them, so nbmi_get_colors_f32, nbmi_visible_points and
+ *                       nbmi_render_sim afterwards see these colours.  The copy stream then copies the slot to its pinned
+ *                       buffer.  *slot = the slot taken.  Steps enqueued afterwards do not touch the slot: the frame is
+ *                       the state at the begin.  NBMI_FRAME_KEY / NBMI_FRAME_DELTA_I16 are nbmi_frame_keyframe /
+ *                       nbmi_frame_delta_i16 with the colour pass included; they and the synchronous calls all act on
+ *                       the one previous decoded frame in the order of the calls.  NBMI_ERR_ARG: no free frame slot
+ *                       (nothing is overwritten, nothing changes), NBMI_FRAME_DELTA_I16 without a previous frame,
+ *                       owner-mode handle.  n == 0 succeeds with empty payloads.
+ *   nbmi_frame_wait     waits until THAT slot's copy is complete - not for the handle's stream, so steps enqueued after
+ *                       the begin keep running.  *first / *second point into the pinned slot (positions and colours, or
+ *                       position deltas and colour deltas; (N,3) each) and stay valid until nbmi_frame_release; *kind =
+ *                       the kind, *steps = nbmi_step_count at the begin.  Any output pointer may be NULL.  Waiting twice
+ *                       is allowed.  Deferred device errors are reported as they stood at the snapshot: NBMI_ERR_CAPACITY
+ *                       / NBMI_ERR_HIP with nbmi_sync's messages; they are NOT cleared (the next nbmi_sync or getter
+ *                       still reports and clears them), and the slot stays taken until it is released.
+ *   nbmi_frame_release  frees the slot for the next begin.
+ *   nbmi_frame_pending  the slots begun and not released, oldest first, with their kinds and step counts (arrays of
+ *                       NBMI_FRAME_SLOTS; any may be NULL); returns how many (>= 0), or a negative error code.  The
+ *                       recorder's Ctrl-C path asks this for the reason it asks nbmi_step_count. */
+#define NBMI_FRAME_F32 0        /* float32 positions + colours (N,3) each: what get_positions + get_colors return   */
+#define NBMI_FRAME_KEY 1        /* the same payload, and it becomes the previous decoded frame (nbmi_frame_keyframe) */
+#define NBMI_FRAME_DELTA_I16 2  /* int16 deltas against the previous decoded frame, which advances (nbmi_frame_delta_i16) */
+#define NBMI_FRAME_SLOTS 2
+int nbmi_frame_begin(nbmi_sim *sim, int kind, double max_speed, int *slot);
+int nbmi_frame_wait(nbmi_sim *sim, int slot, const void **first, const void **second, int *kind, int64_t *steps);
+int nbmi_frame_release(nbmi_sim *sim, int slot);
+int nbmi_frame_pending(nbmi_sim *sim, int *slots, int *kinds, int64_t *steps);
+
 /* Test / measurement hook for the device sort behind the octree build ("Morton-code octree build via
  * device radix sort"; it replaces np.argsort of boids/flock.py:618 as well): sorts n (key, value) pairs
  * given as HOST arrays by the low `bits` bits of the key (key_bytes 4 or 8), stable.  impl must be 0 = the
