@@ -3,7 +3,8 @@
 Same constructor and ``update(dt)``; ``positions`` / ``velocities`` / ``colors`` are (N,3)
 float64 arrays like the reference's, fetched from the device lazily (state lives in HBM
 between updates).  One ``update`` = assign_cells -> sort -> cell table -> 27-cell sweep ->
-physics (reference :627-678) in bdmi_step.  ``draw`` (OpenGL, :730) is out of scope.
+physics (reference :627-678) in bdmi_step.  ``draw`` (OpenGL, :730) is out of scope; ``render`` gives the
+same frame without GL, rasterised on the device (boids/render.py).
 """
 import ctypes as C
 
@@ -156,6 +157,15 @@ class Flock:
         return dict(sort_ms=ms[0], table_ms=ms[1], sweep_ms=ms[2], steps=int(cnt.value))
 
     # ---- render-side reduction (reference :680-728) on the device -----------------------------
+    def frustum_tangents(self, fov=None, aspect=None):
+        """(tan_h, tan_v) of the visibility test for a vertical field of view in degrees (reference :737-739 and
+        _compute_visibility: the half angles widened by fov_margin)."""
+        fov_rad = math.radians(fov) if fov else math.radians(75)
+        aspect = aspect if aspect else (16 / 9)
+        half_fov_v = (fov_rad / 2) * self.fov_margin
+        half_fov_h = math.atan(math.tan(half_fov_v) * aspect)
+        return math.tan(half_fov_h), math.tan(half_fov_v)
+
     def visible_vertices(self, cam_pos=None, cam_forward=None, cam_right=None, cam_up=None, fov=None, aspect=None):
         """What draw() (reference :730-756) hands to its VBOs: (vertices, vert_colors) float32,
         6 rows per visible boid in ascending boid order; sets _visible_count.  Frustum test
@@ -168,11 +178,8 @@ class Flock:
             tan_h = tan_v = float("inf")
             fog = float("inf")
         else:
-            fov_rad = math.radians(fov) if fov else math.radians(75)
-            aspect = aspect if aspect else (16 / 9)
-            half_fov_v = (fov_rad / 2) * self.fov_margin
-            half_fov_h = math.atan(math.tan(half_fov_v) * aspect)
-            tan_h, tan_v, fog = math.tan(half_fov_h), math.tan(half_fov_v), self.fog_end
+            tan_h, tan_v = self.frustum_tangents(fov, aspect)
+            fog = self.fog_end
             cam = np.ascontiguousarray(np.concatenate([np.asarray(a, dtype=np.float64).reshape(3) for a in
                                                        (cam_pos, cam_forward, cam_right, cam_up)]))
         if getattr(self, "_vertices", None) is None:
@@ -186,6 +193,11 @@ class Flock:
         self._visible_count = int(cnt.value)
         k = self._visible_count * self.verts_per_boid
         return self._vertices[:k], self._vert_colors[:k]
+
+    def render(self, renderer, camera, out=None, **shading):
+        """The frame draw() would put on the screen, rasterised on the device by a boids.render.HIPFlockRenderer
+        through a boids.render.OrbitCamera; sets _visible_count.  Returns uint8 (H, W, 3)."""
+        return renderer.render_flock(self, camera, out=out, **shading)
 
     def draw(self, *args, **kwargs):
         raise NotImplementedError("OpenGL rendering (reference boids/flock.py:730) is out of scope of this build; "

@@ -1,6 +1,19 @@
 """Boids constants, values as reference config/boids.py:30-46."""
 
-CAMERA = {"far_clip": 1000.0}
+WINDOW = {"width": 1280, "height": 720}
+
+CAMERA = {
+    "fov": 90.0,
+    "near_clip": 0.1,
+    "far_clip": 1000.0,
+    "initial_radius": 120.0,
+    "initial_theta": 45.0,
+    "initial_phi": 25.0,
+    "min_phi": -89.0,
+    "max_phi": 89.0,
+}
+
+COLORS = {"background": (0.01, 0.01, 0.02, 1.0)}
 
 BOIDS = {
     "count": 500000,

@@ -1092,8 +1092,39 @@ int bdmi_visible_vertices(bdmi_flock *f, const double *cam12, double tan_h, doub
         nbmi::set_error("bdmi_visible_vertices: null argument");
         return -1;
     }
+    const float *d_verts = nullptr, *d_cols = nullptr;
+    if (int rc = nbmi::flock_visible_device(f, cam12, tan_h, tan_v, fog_end, cone_length, cone_radius, &d_verts, &d_cols,
+                                            count, nullptr))
+        return rc;
+    hipStream_t st = f->stream;
+    const int64_t rows = *count < capacity_boids ? *count : capacity_boids;
+    if (rows > 0) {
+        NBMI_HIP_CHECK(hipMemcpyAsync(out_vertices, d_verts, (size_t)rows * 72, hipMemcpyDeviceToHost, st));
+        NBMI_HIP_CHECK(hipMemcpyAsync(out_colors, d_cols, (size_t)rows * 72, hipMemcpyDeviceToHost, st));
+        NBMI_HIP_CHECK(hipStreamSynchronize(st));
+    }
+    return 0;
+}
+
+}  // extern "C"
+
+
+// ---- triangle rasteriser (raster.hip) reads a flock handle through these -----------------------------------
+int nbmi::flock_source(bdmi_flock *f, int64_t *n, int *device, int *slab) {
+    if (int rc = check(f)) return rc;
+    *n = f->n; *device = f->device; *slab = f->slab ? 1 : 0;
+    return 0;
+}
+
+// The device part of bdmi_visible_vertices: mark, count, scan, emit cones into the handle's scratch, then the
+// number of visible boids.  `done` (may be null) is recorded on the flock's stream behind the last kernel.
+int nbmi::flock_visible_device(bdmi_flock *f, const double *cam12, double tan_h, double tan_v, double fog_end,
+                               double cone_length, double cone_radius, const float **d_verts, const float **d_cols,
+                               int64_t *count, hipEvent_t done) {
+    if (int rc = check(f)) return rc;
     const int64_t n = f->n;
     *count = 0;
+    *d_verts = *d_cols = nullptr;
     if (n == 0) return 0;
     const int64_t ntiles = vis::tiles_for(n);
     if (!f->vis_flag) {
@@ -1114,17 +1145,12 @@ int bdmi_visible_vertices(bdmi_flock *f, const double *cam12, double tan_h, doub
     EmitCones e{a, cone_length, cone_radius, f->vis_verts, f->vis_cols};
     vis::k_emit<<<(int)ntiles, vis::kBlock, 0, st>>>(f->vis_flag, f->vis_slot, f->vis_tiles, n, n, e);
     NBMI_HIP_CHECK(hipGetLastError());
+    if (done) NBMI_HIP_CHECK(hipEventRecord(done, st));
     uint32_t total = 0;
     NBMI_HIP_CHECK(hipMemcpyAsync(&total, f->vis_tiles + ntiles, 4, hipMemcpyDeviceToHost, st));
     NBMI_HIP_CHECK(hipStreamSynchronize(st));
     *count = total;
-    const int64_t rows = (int64_t)total < capacity_boids ? (int64_t)total : capacity_boids;
-    if (rows > 0) {
-        NBMI_HIP_CHECK(hipMemcpyAsync(out_vertices, f->vis_verts, (size_t)rows * 72, hipMemcpyDeviceToHost, st));
-        NBMI_HIP_CHECK(hipMemcpyAsync(out_colors, f->vis_cols, (size_t)rows * 72, hipMemcpyDeviceToHost, st));
-        NBMI_HIP_CHECK(hipStreamSynchronize(st));
-    }
+    *d_verts = f->vis_verts;
+    *d_cols = f->vis_cols;
     return 0;
 }
-
-}  // extern "C"

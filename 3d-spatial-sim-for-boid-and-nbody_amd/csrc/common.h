@@ -57,6 +57,16 @@ struct nbmi_sim;
 namespace nbmi {
 int render_source(::nbmi_sim *s, int64_t *n, int *device);
 int render_fetch(::nbmi_sim *s, float *d_pos, float *d_col, hipEvent_t done);
+}  // namespace nbmi
+struct bdmi_flock;
+namespace nbmi {
+// ---- triangle rasteriser (raster.hip) reads a flock handle through these (bdmi.hip) ----------------
+int flock_source(::bdmi_flock *f, int64_t *n, int *device, int *slab);
+// Frustum test + cone building of bdmi_visible_vertices, left on the device: (6 count, 3) float32 vertices and
+// colours in the handle's scratch, valid until the handle's next call.  Returns with the flock's stream idle.
+int flock_visible_device(::bdmi_flock *f, const double *cam12, double tan_h, double tan_v, double fog_end,
+                         double cone_length, double cone_radius, const float **d_verts, const float **d_cols,
+                         int64_t *count, hipEvent_t done);
 
 // One body of a key-sorted run as it travels between GPUs (multi-GPU run exchange): the two
 // octant-path key words and the fp32 {x, y, z, G*m} the octree is built from.  32 bytes.

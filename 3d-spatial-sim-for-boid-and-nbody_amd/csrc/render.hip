@@ -25,6 +25,7 @@
 
 #include "../../include/nbmi.h"
 #include "common.h"
+#include "render_internal.h"
 
 namespace {
 
@@ -358,33 +359,6 @@ inline int grid_for(int64_t n, int64_t per) { return (int)((n + per - 1) / per);
 
 }  // namespace
 
-struct nbmi_render {
-    int W = 0, H = 0, device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[7] = {};
-    hipEvent_t ev_src = nullptr;
-    bool timed = false;
-    // inputs
-    float *d_pos = nullptr, *d_col = nullptr;  // N x 3 each
-    float *h_stage = nullptr;                  // pinned upload staging, 6 N floats
-    int64_t cap_pts = 0;
-    // per point / per tile
-    uint64_t *rec = nullptr;
-    uint32_t *tile_cnt = nullptr;
-    uint64_t *tile_off = nullptr;
-    // fragments
-    uint32_t *keys = nullptr, *vals = nullptr, *keys2 = nullptr, *vals2 = nullptr;
-    uint64_t *tile_min = nullptr, *tile_pre = nullptr;
-    void *sort_tmp = nullptr;
-    size_t sort_bytes = 0;
-    int64_t cap_frags = 0;
-    // image
-    unsigned long long *acc = nullptr, *stats = nullptr;
-    uint8_t *d_img = nullptr, *h_img = nullptr;
-    uint64_t *h_small = nullptr;  // pinned: [0] fragment total, [1..4] stats, [5] sort error word
-    int64_t last_stats[4] = {0, 0, 0, 0};
-};
-
 namespace {
 
 template <typename T>
@@ -547,6 +521,7 @@ int render_frame(nbmi_render *r, int64_t n, const View &v, const uint32_t bg8[3]
     NBMI_HIP_CHECK(hipEventRecord(r->ev[6], st));
     NBMI_HIP_CHECK(hipStreamSynchronize(st));
     r->timed = true;
+    r->tri_frame = false;
     if (r->h_small[5]) {
         NBMI_HIP_CHECK(nbmi::radix_init_temp(r->sort_tmp, st));
         NBMI_HIP_CHECK(hipStreamSynchronize(st));
@@ -577,6 +552,7 @@ void nbmi_render_destroy(nbmi_render *r) {
     if (r->stream) (void)hipStreamSynchronize(r->stream);
     free_points(r);
     free_frags(r);
+    nbmi::raster_free(r);
     (void)hipFree(r->acc); (void)hipFree(r->stats); (void)hipFree(r->d_img);
     (void)hipHostFree(r->h_img); (void)hipHostFree(r->h_small);
     for (hipEvent_t &e : r->ev)
@@ -675,6 +651,14 @@ int nbmi_render_timers(nbmi_render *r, double *out_ms4) {
     if (!out_ms4) { nbmi::set_error("nbmi_render_timers: null output"); return NBMI_ERR_ARG; }
     for (int k = 0; k < 4; k++) out_ms4[k] = 0.0;
     if (!r->timed) return 0;
+    if (r->tri_frame) {  // rasterise, resolve, copy
+        float t[3];
+        for (int k = 0; k < 3; k++) NBMI_HIP_CHECK(hipEventElapsedTime(&t[k], r->ev[k], r->ev[k + 1]));
+        out_ms4[0] = t[0];
+        out_ms4[2] = t[1];
+        out_ms4[3] = t[2];
+        return 0;
+    }
     float t[6];
     for (int k = 0; k < 6; k++) NBMI_HIP_CHECK(hipEventElapsedTime(&t[k], r->ev[k], r->ev[k + 1]));
     out_ms4[0] = (double)t[0] + (double)t[2];  // count + scan, emit (not the host's read of the total between them)

@@ -103,6 +103,8 @@ PROTOTYPES = {
     "bdmi_enable_timers": (C.c_int, [_vp, C.c_int]),
     "bdmi_get_timers": (C.c_int, [_vp, _vp, _vp, C.c_int]),
     "bdmi_visible_vertices": (C.c_int, [_vp, _vp, _dbl, _dbl, _dbl, _dbl, _dbl, _vp, _vp, _i64, _vp]),
+    "bdmi_render_triangles": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp]),
+    "bdmi_render_flock": (C.c_int, [_vp, _vp, _vp, _dbl, _dbl, _dbl, _dbl, _dbl, _vp, _vp, _vp]),
 }
 
 

@@ -1,0 +1,163 @@
+"""Frames or a video of a running flock, rendered headless on the GPU.
+
+The reference shows its boids only in a window; this tool steps a Flock and draws every frame with the device
+rasteriser (boids.render.HIPFlockRenderer; image semantics in include/bdmi.h), so a flock can be looked at on a
+machine without GL, display or window system.
+
+    python -m tools.flock_video --boids 500k --frames 300                  # ffmpeg if on PATH, else raw rgb24 + JSON
+    python -m tools.flock_video --boids 2m --resolution 1080p --camera orbit --format ppm -o frames/
+
+Each frame: flock.update(dt, substeps), render_flock, sink.  Output formats and sinks are those of tools.export.
+"""
+import argparse
+import json
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+from config import boids as config
+from tools.export import (CODECS, FORMATS, QUALITY_PRESETS, RESOLUTION_PRESETS, _FfmpegSink, _PpmSink, _RawSink,
+                          ffmpeg_command, format_time, have_ffmpeg)
+from tools.record import parse_number
+
+CAMERA_MODES = ("fixed", "orbit")
+MAX_DT = 0.05  # the reference application caps a frame's dt (Application._update)
+
+
+def build_parser():
+    cam = config.CAMERA
+    ap = argparse.ArgumentParser(prog="python -m tools.flock_video",
+                                 description="Run a flock and write its frames, rendered on the GPU")
+    ap.add_argument("--boids", type=parse_number, default=config.BOIDS["count"], help="number of boids (500k, 2m, ...)")
+    ap.add_argument("--frames", type=int, default=300, help="frames to write (default: 300)")
+    ap.add_argument("--fps", type=int, default=30, help="output FPS (default: 30)")
+    ap.add_argument("--dt", type=float, default=None, help=f"time per frame (default: 1 / fps, at most {MAX_DT})")
+    ap.add_argument("--substeps", type=int, default=1, help="flock updates of dt per frame (default: 1)")
+    ap.add_argument("--seed", type=int, default=None, help="seed of the initial state")
+    ap.add_argument("--warmup", type=int, default=0, help="updates before the first frame (default: 0)")
+    ap.add_argument("--resolution", choices=list(RESOLUTION_PRESETS), default="720p", help="output size (default: 720p)")
+    ap.add_argument("--camera", choices=CAMERA_MODES, default="orbit", help="camera animation (default: orbit)")
+    ap.add_argument("--camera-speed", type=float, default=0.3, help="orbit speed in degrees/frame (default: 0.3)")
+    ap.add_argument("--camera-radius", type=float, default=cam["initial_radius"], help="distance from the centre")
+    ap.add_argument("--camera-angle", type=float, default=cam["initial_phi"], help="vertical angle, 0 = horizon")
+    ap.add_argument("--camera-theta", type=float, default=cam["initial_theta"], help="horizontal starting angle")
+    ap.add_argument("--quality", choices=list(QUALITY_PRESETS), default="balanced", help="ffmpeg quality preset")
+    ap.add_argument("--crf", type=int, help="override the CRF value (0-51, lower = better)")
+    ap.add_argument("--codec", choices=CODECS, default="h264", help="video codec (default: h264)")
+    ap.add_argument("-o", "--output", type=str, help="output file (ffmpeg, raw) or directory (ppm)")
+    ap.add_argument("--format", choices=FORMATS, default=None,
+                    help="ffmpeg (default when ffmpeg is on PATH), raw rgb24 + JSON sidecar, or one PPM per frame")
+    ap.add_argument("--device", type=int, default=0, help="HIP device (default: 0)")
+    return ap
+
+
+def frame_dt(args) -> float:
+    return min(args.dt if args.dt is not None else 1.0 / args.fps, MAX_DT)
+
+
+def camera_at(args, frame_idx):
+    """The camera of frame `frame_idx`: fixed, or orbiting by --camera-speed degrees per frame."""
+    from boids.render import OrbitCamera
+    theta = args.camera_theta + (frame_idx * args.camera_speed if args.camera == "orbit" else 0.0)
+    return OrbitCamera(theta=theta, phi=args.camera_angle, radius=args.camera_radius)
+
+
+def resolve_format(args, say=print) -> str:
+    if args.format is not None:
+        return args.format
+    if have_ffmpeg():
+        return "ffmpeg"
+    say("[Flock] ffmpeg not found on PATH: writing raw rgb24 frames + a JSON sidecar instead")
+    return "raw"
+
+
+def default_output(fmt) -> Path:
+    suffix = {"ffmpeg": ".mp4", "raw": ".rgb", "ppm": "_frames"}[fmt]
+    path = Path(f"flock{suffix}")
+    k = 1
+    while path.exists():
+        path = Path(f"flock ({k}){suffix}")
+        k += 1
+    return path
+
+
+def make_sink(args, fmt, output, width, height):
+    if fmt == "ffmpeg":
+        if not have_ffmpeg():
+            raise RuntimeError("--format ffmpeg: ffmpeg is not on PATH (use --format raw or ppm)")
+        q = QUALITY_PRESETS[args.quality]
+        crf = args.crf if args.crf is not None else q["crf"]
+        return _FfmpegSink(ffmpeg_command(width, height, args.fps, args.codec, crf, q["encoding_preset"], output))
+    if fmt == "raw":
+        output.parent.mkdir(parents=True, exist_ok=True)
+        return _RawSink(output, width, height, args.fps)
+    return _PpmSink(output, 0)
+
+
+def run(args, make_flock=None, make_renderer=None, say=print) -> dict:
+    """Steps the flock and writes args.frames frames.  make_flock(count, seed, device) and
+    make_renderer(width, height, device) default to boids.Flock and boids.render.HIPFlockRenderer."""
+    if args.frames <= 0 or args.substeps <= 0 or args.boids <= 0 or args.warmup < 0:
+        raise ValueError("--frames, --substeps and --boids must be positive, --warmup not negative")
+    if make_flock is None:
+        from boids import Flock
+        make_flock = lambda n, seed, device: Flock(n, seed=seed, device=device)  # noqa: E731
+    if make_renderer is None:
+        from boids.render import HIPFlockRenderer
+        make_renderer = lambda w, h, device: HIPFlockRenderer(w, h, device=device)  # noqa: E731
+    width, height = RESOLUTION_PRESETS[args.resolution]
+    fmt = resolve_format(args, say)
+    output = Path(args.output) if args.output else default_output(fmt)
+    dt = frame_dt(args)
+    say(f"[Flock] {args.boids:,} boids, {args.frames} frames, {width}x{height} @ {args.fps} fps, dt {dt:.4f} x "
+        f"{args.substeps}, camera {args.camera}, {fmt} -> {output}")
+    flock = make_flock(args.boids, args.seed, args.device)
+    renderer = make_renderer(width, height, args.device)
+    sink = make_sink(args, fmt, output, width, height)
+    ok = False
+    t_step = t_render = t_write = 0.0
+    t0 = time.perf_counter()
+    try:
+        if args.warmup:
+            flock.update(dt, args.warmup)
+        img = np.empty((height, width, 3), dtype=np.uint8)
+        for i in range(args.frames):
+            ts = time.perf_counter()
+            flock.update(dt, args.substeps)
+            flock.sync()
+            tr = time.perf_counter()
+            renderer.render_flock(flock, camera_at(args, i), out=img)
+            tw = time.perf_counter()
+            sink.write(img)
+            t_step += tr - ts
+            t_render += tw - tr
+            t_write += time.perf_counter() - tw
+        ok = True
+    finally:
+        ok = sink.close(ok) and ok
+        renderer.close()
+        flock.close()
+    wall = time.perf_counter() - t0
+    timings = {"ok": ok, "frames": args.frames, "wall_s": wall, "step_s": t_step, "render_s": t_render,
+               "write_s": t_write, "fps": args.frames / wall if wall > 0 else 0.0, "output": str(output), "format": fmt}
+    if ok and fmt == "raw":  # the sink's sidecar, plus what produced the frames
+        meta = json.loads(sink.meta_path.read_text())
+        meta["flock"] = {"boids": args.boids, "seed": args.seed, "dt": dt, "substeps": args.substeps,
+                         "warmup": args.warmup, "params": {k: float(v) for k, v in config.BOIDS.items()}}
+        meta["camera"] = {"mode": args.camera, "speed": args.camera_speed, "radius": args.camera_radius,
+                          "angle": args.camera_angle, "theta": args.camera_theta}
+        sink.meta_path.write_text(json.dumps(meta, indent=2))
+    say(f"[Flock] {'done' if ok else 'FAILED'}: {output} ({args.frames} frames in {format_time(wall)}, "
+        f"{timings['fps']:.1f} fps; step {t_step:.2f}s, render {t_render:.2f}s, write {t_write:.2f}s)")
+    return timings
+
+
+def main(argv=None) -> int:
+    args = build_parser().parse_args(argv)
+    return 0 if run(args)["ok"] else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -93,6 +93,73 @@ int bdmi_visible_vertices(bdmi_flock *f, const double *cam12, double tan_h, doub
                           double cone_length, double cone_radius, float *out_vertices, float *out_colors,
                           int64_t capacity_boids, int64_t *count);
 
+/* ---- headless flock renderer (csrc/raster.hip; boids/render.py, tools/flock_video.py) -------------------------------
+ * Image semantics of a flock frame: the image fixed-function GL draws for the reference's Flock.draw (flock.py:730-782
+ * under core/application.py:44-95): opaque flat-coloured GL_TRIANGLES, GL_DEPTH_TEST (GL_LESS, depth writes on), linear
+ * fog towards the clear colour, gluLookAt + gluPerspective.  Where GL leaves the result to the implementation, one
+ * deterministic answer is fixed here; the kernels and the tests' NumPy restatement (tests/raster_ref.py) both follow
+ * this text.  Arithmetic is float64 in the order written, without FMA; the edge functions are exact integers.
+ *
+ * Input: vertices and colors, float32 (3T, 3); triangle t = rows 3t, 3t+1, 3t+2 (what bdmi_visible_vertices
+ * returns).  The colour of triangle t is the colour row of its first vertex.
+ * params (17 doubles): eye[3], target[3], up[3], fovy (degrees, in (0, 180); reference 90), near (0.1), far (1000),
+ * fog_start (50), fog_end (800), bg[3] (in [0, 1]; reference (0.01, 0.01, 0.02)).  near > 0, far > near and
+ * fog_end > fog_start are required (NBMI_ERR_ARG otherwise, as for any value that is not finite).
+ * View constants f, s, u, cot, aspect, za, zb and, per vertex, x_e, y_e, z_e, x_c, y_c, z_c, w_c exactly as in the
+ * point renderer's text (include/nbmi.h: same formulas, same association), p = the float32 vertex converted exactly.
+ *
+ * Per triangle:
+ *   discarded whole if any coordinate of any vertex is not finite, if any vertex has w_c < near, or if any vertex has
+ *     z_c > w_c.  (GL would clip at the near and far planes instead.  A boid that passes the reference's visibility
+ *     test has 0.5 <= z <= far at its centre and its cone reaches 1.2 further, so this touches only cones within 1.3
+ *     of the camera plane or of the far plane.)
+ *   x_w = (x_c / w_c)(W / 2) + W / 2, y_w = (y_c / w_c)(H / 2) + H / 2 per vertex; discarded whole if any |x_w| or
+ *     |y_w| exceeds 2^20
+ *   snap to 4 sub-pixel bits: X = floor(x_w 16 + 0.5), Y = floor(y_w 16 + 0.5) as int64.  Everything on X, Y below is
+ *     exact integer arithmetic (|X|, |Y| <= 2^24, so every product and every E stays below 2^52 and converts to
+ *     float64 exactly)
+ *   area2 = (X1 - X0)(Y2 - Y0) - (Y1 - Y0)(X2 - X0).  Zero: discarded.  Negative: vertices 1 and 2 change places
+ *     (no face culling: both windings are drawn), so that area2 > 0
+ *   pixel (i, j), 0 <= i < W, 0 <= j < H, is sampled at its centre P = (16 i + 8, 16 j + 8).  For the edge from vertex
+ *     b to vertex c opposite vertex a ((b, c) = (1, 2), (2, 0), (0, 1) for a = 0, 1, 2), dx = Xc - Xb, dy = Yc - Yb:
+ *       E_a = dx (P_y - Y_b) - dy (P_x - X_b)
+ *     The pixel is covered iff for every edge E_a > 0, or E_a == 0 and the edge owns its points:
+ *     dy < 0 or (dy == 0 and dx > 0).  Two triangles that share an edge cover a pixel centre on it exactly once.
+ *   depth: l_a = double(E_a) / double(area2), z_n = z_c / w_c per vertex, z_f = (l_0 z_n0 + l_1 z_n1) + l_2 z_n2,
+ *     d = floor((z_f 0.5 + 0.5)(2^24 - 1) + 0.5).  A covered pixel with 0 <= d < 2^24 - 1 is a fragment.
+ * The fragment that wins pixel (i, j) is the one with the smallest (d, t) in lexicographic order: GL_LESS against a
+ * depth buffer cleared to 2^24 - 1 with the triangles drawn in row order, so among equal depths the first drawn stays.
+ * Its colour: w_f = 1 / ((l_0 / w_c0 + l_1 / w_c1) + l_2 / w_c2) (the eye-space depth at the pixel),
+ *   fog = clamp((fog_end - w_f) / (fog_end - fog_start), 0, 1), C = clamp(colour, 0, 1) (NaN -> 0),
+ *   C' = fog C + (1 - fog) bg, channel = floor(C' 255 + 0.5).  Pixels without a fragment get floor(bg 255 + 0.5).
+ * Output uint8 (H, W, 3) RGB with row 0 at the TOP: window pixel (i, j) is image row H - 1 - j, as the point renderer.
+ * Only correctly rounded float64 operations and exact integers take part (there is no exp here), so the device image
+ * equals the restatement byte for byte, fog included, and is the same bytes on every run.
+ * Two deviations from GL: near / far clipping is replaced by the whole-triangle discard above, and depth and fog are
+ * interpolated as written rather than by an implementation's fixed-point set-up.
+ * Not drawn: the reference's wireframe cube (rendering/grid.py, twelve GL_LINES) and its HUD text.
+ *
+ * Both calls draw with an nbmi_render handle of include/nbmi.h (one per output size; its z-buffer is allocated at the
+ * first triangle frame) and return when the image is in out_rgb (W*H*3 bytes).  At most 2^31 - 1 triangles; zero
+ * triangles, or all discarded, give the background image.  A frame whose triangles with a box of more than 64 pixel
+ * centres number 2^28 - 1 or more, or whose boxes sum to 2^36 or more chunks of 32 x 8 pixels, is refused with
+ * NBMI_ERR_CAPACITY.
+ * After a triangle frame nbmi_render_stats gives {triangles drawn (not discarded, area2 != 0), fragments, winning
+ * fragments, pixels with a fragment} (the last two are equal here) and nbmi_render_timers gives
+ * {project + rasterise, 0, resolve, copy to the host} (the resolve kernel packs the RGB8 rows itself). */
+typedef struct nbmi_render nbmi_render; /* as in nbmi.h; a repeated typedef is legal C11 / C++ */
+/* Host arrays (3 triangles, 3) float32 each, uploaded through pinned staging. */
+int bdmi_render_triangles(nbmi_render *r, const float *vertices_xyz, const float *colors_rgb, int64_t triangles,
+                          const double *params17, uint8_t *out_rgb);
+/* The frame Flock.draw would put on the screen: visibility and cone building of bdmi_visible_vertices (same arguments,
+ * same masks, same float32 vertices, ascending boid order) left on the device and rasterised there; only the image
+ * crosses PCIe.  The image equals bdmi_render_triangles of what bdmi_visible_vertices returns for these arguments.
+ * *visible_boids (may be NULL) = the visible count.  The handle and the renderer must be on the same device; slab
+ * handles (bdmi_create_slab) are refused with NBMI_ERR_ARG.  The flock's state is not touched. */
+int bdmi_render_flock(nbmi_render *r, bdmi_flock *f, const double *cam12, double tan_h, double tan_v, double fog_end_vis,
+                      double cone_length, double cone_radius, const double *params17, uint8_t *out_rgb,
+                      int64_t *visible_boids);
+
 #ifdef __cplusplus
 }
 #endif
