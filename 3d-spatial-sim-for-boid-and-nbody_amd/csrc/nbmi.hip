@@ -3338,17 +3338,30 @@ __global__ void k_copy_ids(const int32_t *__restrict__ ids, int32_t *__restrict_
 // a leaf's body as the float64 state has it), and the reference's guard (simulation.py:260) on the float64 dist_sq.
 // The own leaf has d = 0 exactly, so the guard skips it as the reference's explicit test does.  phi and the number of
 // applied terms land at the body's state row j = perm[rank].
+// kQuad (quadrupole mode): an applied cell term also carries the second-order term
+// 1/2 [tr P u^-3/2 - 3 (d^T P d) u^-5/2] with the cell's float64 second moments quad[9 idx + 3 .. 9 idx + 8] (k_quad_level);
+// leaves are skipped.  Both instantiations share the decision, the near-pair rule below included.
+template <bool kQuad>
 __global__ __launch_bounds__(kBlock) void k_potential_tree(const Node *__restrict__ nodes, const double4 *__restrict__ pot,
                                                            const WalkTable *tab, const TreeInfo *info,
                                                            const float4 *__restrict__ posm_s, const uint32_t *__restrict__ perm,
                                                            int curbuf, float eps2f, int64_t n, double *__restrict__ phi,
-                                                           int32_t *__restrict__ cnt) {
+                                                           int32_t *__restrict__ cnt, const double *__restrict__ quad) {
     if (info->error != 0 || info->sticky_error != 0) return;  // the tree did not fit: the caller reports it
     const int64_t rank = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     const bool valid = rank < n;
     const unsigned nn = __builtin_amdgcn_readfirstlane((unsigned)info->num_nodes * kNodeBytes);
     const unsigned band2 = __builtin_amdgcn_readfirstlane(info->band2);
     const double eps2 = tab->eps2;
+    // The band's half width is capped at 2^21 ulps (band_half_ulps): enough for the fp32 error of d^2, (6.93 maxabs / d
+    // + 4) ulps, only while d >= 3.3e-6 maxabs.  At eps == 0 (or an eps below that) closer pairs exist, and their fp32
+    // d^2 says nothing about the test: a cell closer than 8e-6 maxabs (twice the limit plus the rounding of d itself) is
+    // decided in float64 whatever the fp32 test said, so that `terms` stays the reference's count there too.
+    float near2 = 0.f;
+    if (band2 >= 2u * 2097153u) {
+        const double r = 8.0e-6 * __longlong_as_double((long long)info->maxabs_bits);
+        near2 = eps2f + (float)(r * r);
+    }
     float px = 0.f, py = 0.f, pz = 0.f;
     double qx = 0.0, qy = 0.0, qz = 0.0;
     uint32_t j = 0;
@@ -3374,7 +3387,7 @@ __global__ __launch_bounds__(kBlock) void k_potential_tree(const Node *__restric
         const bool active = resume <= off;
         const int d2b = __float_as_int(dist_sq), hi = __float_as_int(nd.s2t), lo = hi - (int)band2;
         bool geom = hi < d2b;
-        const bool band = active && !geom && lo < d2b;
+        const bool band = active && ((!geom && lo < d2b) || (hi != 0 && dist_sq < near2));
         if (band) geom = (hi == 0) || exact_take_idx(idx, b64);
         const bool take = active && geom;
         if (take) {
@@ -3384,6 +3397,13 @@ __global__ __launch_bounds__(kBlock) void k_potential_tree(const Node *__restric
             if (q.w > 0.0 && d2 > eps2) {
                 acc -= q.w / sqrt(d2);
                 terms++;
+                if (kQuad && nd.next_off != off + kNodeBytes) {  // an internal cell
+                    const double *pq = quad + 9 * (size_t)idx + 3;
+                    const double pxx = pq[0], pyy = pq[1], pzz = pq[2], pxy = pq[3], pxz = pq[4], pyz = pq[5];
+                    const double dpd = ex * (pxx * ex + 2.0 * (pxy * ey + pxz * ez)) + ey * (pyy * ey + 2.0 * (pyz * ez)) + ez * (pzz * ez);
+                    const double i1 = 1.0 / sqrt(d2), i3 = i1 / d2;
+                    acc += 0.5 * ((pxx + pyy + pzz) * i3 - 3.0 * dpd * (i3 / d2));
+                }
             }
             resume = nd.next_off;
         }
@@ -3393,6 +3413,245 @@ __global__ __launch_bounds__(kBlock) void k_potential_tree(const Node *__restric
     if (valid) {
         phi[j] = acc;
         cnt[j] = terms;
+    }
+}
+
+// ---------------------------------------------------------------------------------------
+// K15: quadrupole mode (nbmi_set_multipole, include/nbmi.h).
+// ---------------------------------------------------------------------------------------
+// Second moments of an internal cell about its centre of mass, G folded in; a leaf's (and the sentinel's) row is zero.
+// 24 bytes, the stride of Node: the walk's byte cursor addresses both arrays.
+struct alignas(8) NodeQ {
+    float pxx, pyy, pzz, pxy, pxz, pyz;
+};
+static_assert(sizeof(NodeQ) == kNodeBytes, "NodeQ rows lie beside the Node rows");
+constexpr int kQuadDoubles = 9;  // float64 work row of a cell: bottom-up centre of mass (3), second moments (6)
+constexpr int kQuadGrid = 2048;  // workgroups of the passes over the node rows (grid-stride)
+
+// One level of the bottom-up pass: every internal cell of level `lev` from its (up to eight) children, which are
+// leaves or cells of level lev + 1 that the previous launch finished.  With child k's mass M_k, centre c_k and moments
+// P_k (a leaf: its float64 position, P = 0):
+//   c = c_0 + sum M_k (c_k - c_0) / M,     P = sum [ P_k + M_k (c_k - c)(c_k - c)^T ]
+// Only DIFFERENCES of nearby points are formed, so a cell 1e-3 across at coordinate 700 gets its moments to a few
+// ulps of their own size; sums about the origin (the prefix sums of K5-K7 with six more columns) lose them entirely
+// there.  The centre carried upwards is the pass's own (good to an ulp of the coordinate), not the build's prefix-sum
+// centre (good to 1e-13 of the largest coordinate in the tile: a first-order error 2 M |c_k - c| 1e-13 maxabs, which
+// exceeds the tolerance for cells below ~1e-4 across); about which of the two P is taken differs by G M |dc|^2, nothing.
+// pot = the build's float64 rows {cx, cy, cz, G M} (leaf: x, y, z, G m); links are Node::next_off.
+__global__ __launch_bounds__(kBlock) void k_quad_level(const Node *__restrict__ nodes, const uint8_t *__restrict__ node_level,
+                                                       const double4 *__restrict__ pot, const TreeInfo *__restrict__ info,
+                                                       int lev, double *__restrict__ work, NodeQ *__restrict__ nq) {
+    if (info->error != 0 || lev >= info->max_level) return;  // max_level = the deepest LEAF level (k_max_level)
+    const int64_t rows = info->num_nodes;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < rows; i += (int64_t)gridDim.x * kBlock) {
+        if (node_level[i] != (uint8_t)lev) continue;
+        const unsigned end = nodes[i].next_off / kNodeBytes;
+        if (end == (unsigned)i + 1u) continue;  // a leaf
+        // first sweep: the centre
+        unsigned c = (unsigned)i + 1u;
+        const double4 first = pot[c];
+        const bool first_leaf = nodes[c].next_off / kNodeBytes == c + 1u;
+        const double ox = first_leaf ? first.x : work[kQuadDoubles * (size_t)c], oy = first_leaf ? first.y : work[kQuadDoubles * (size_t)c + 1],
+                     oz = first_leaf ? first.z : work[kQuadDoubles * (size_t)c + 2];
+        double M = 0.0, sx = 0.0, sy = 0.0, sz = 0.0;
+        while (c < end) {
+            const unsigned nx = nodes[c].next_off / kNodeBytes;
+            const double4 q = pot[c];
+            const bool leaf = nx == c + 1u;
+            const double *w = work + kQuadDoubles * (size_t)c;
+            const double cx = leaf ? q.x : w[0], cy = leaf ? q.y : w[1], cz = leaf ? q.z : w[2];
+            M += q.w; sx += q.w * (cx - ox); sy += q.w * (cy - oy); sz += q.w * (cz - oz);
+            c = nx;
+        }
+        double cx = ox, cy = oy, cz = oz;
+        if (M > 0.0) { cx += sx / M; cy += sy / M; cz += sz / M; }
+        double pxx = 0.0, pyy = 0.0, pzz = 0.0, pxy = 0.0, pxz = 0.0, pyz = 0.0;
+        c = (unsigned)i + 1u;
+        while (c < end) {
+            const unsigned nx = nodes[c].next_off / kNodeBytes;
+            const double4 q = pot[c];
+            const bool leaf = nx == c + 1u;
+            const double *w = work + kQuadDoubles * (size_t)c;
+            const double dx = (leaf ? q.x : w[0]) - cx, dy = (leaf ? q.y : w[1]) - cy, dz = (leaf ? q.z : w[2]) - cz;
+            pxx += q.w * dx * dx; pyy += q.w * dy * dy; pzz += q.w * dz * dz;
+            pxy += q.w * dx * dy; pxz += q.w * dx * dz; pyz += q.w * dy * dz;
+            if (!leaf) { pxx += w[3]; pyy += w[4]; pzz += w[5]; pxy += w[6]; pxz += w[7]; pyz += w[8]; }
+            c = nx;
+        }
+        double *o = work + kQuadDoubles * (size_t)i;
+        o[0] = cx; o[1] = cy; o[2] = cz;
+        o[3] = pxx; o[4] = pyy; o[5] = pzz; o[6] = pxy; o[7] = pxz; o[8] = pyz;
+        nq[i] = NodeQ{(float)pxx, (float)pyy, (float)pzz, (float)pxy, (float)pxz, (float)pyz};
+    }
+}
+
+// nbmi_get_cell_moments: the fp32 records widened, rows as k_cells numbers them (a leaf's record is never written
+// and never read by the walks: zeros here)
+__global__ __launch_bounds__(kBlock) void k_quad_export(const Node *__restrict__ nodes, const NodeQ *__restrict__ nq,
+                                                        int64_t num_nodes, double *__restrict__ out) {
+    const int64_t u = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (u >= num_nodes) return;
+    const bool leaf = nodes[u].next_off == (unsigned)(u + 1) * kNodeBytes;
+    const NodeQ q = leaf ? NodeQ{0.f, 0.f, 0.f, 0.f, 0.f, 0.f} : nq[u];
+    double *o = out + 6 * u;
+    o[0] = q.pxx; o[1] = q.pyy; o[2] = q.pzz; o[3] = q.pxy; o[4] = q.pxz; o[5] = q.pyz;
+}
+
+// The second-order part of one applied cell term, fp32: with e = d u^-1/2 (inv = u^-1/2),
+//   q = u^-2 [ (7.5 e^T P e - 1.5 tr P) e - 3 P e ]
+// - nothing beyond u^-2 is formed (u^-7/2 leaves fp32 at d ~ 1e-5 when eps = 0), and P meets the first u^-1 before the
+// second: P / u <= G M theta^2 for an accepted cell, so the term is finite wherever the monopole term is.  inv = 0
+// switches the term off.
+__device__ __forceinline__ void quad_term(const NodeQ &Q, float dx, float dy, float dz, float inv, float &ax, float &ay, float &az) {
+    const float ex = dx * inv, ey = dy * inv, ez = dz * inv;
+    const float i2 = inv * inv;
+    const float wx = fmaf(Q.pxz, ez, fmaf(Q.pxy, ey, Q.pxx * ex)) * i2;
+    const float wy = fmaf(Q.pyz, ez, fmaf(Q.pyy, ey, Q.pxy * ex)) * i2;
+    const float wz = fmaf(Q.pzz, ez, fmaf(Q.pyz, ey, Q.pxz * ex)) * i2;
+    const float epe = fmaf(ez, wz, fmaf(ey, wy, ex * wx));
+    const float tr = ((Q.pxx + Q.pyy) + Q.pzz) * i2;
+    const float s = fmaf(7.5f, epe, -1.5f * tr) * i2, t = -3.0f * i2;
+    ax += fmaf(s, ex, t * wx);
+    ay += fmaf(s, ey, t * wy);
+    az += fmaf(s, ez, t * wz);
+}
+
+// The quadrupole walk.  k_potential_tree's shape: one wave per 64 key-adjacent bodies, one wave-uniform cursor, the Node
+// and the NodeQ record fetched at the same uniform byte offset (scalar loads), visit()'s decision (band, exact_take)
+// and its monopole arithmetic operation for operation; float64 waves (force precision, as k_walk decides it) take the
+// decision and the monopole of guard_visit64 / tie_visit64 from the NodeD row and start the correction from the float64
+// difference rounded to fp32.  fp32 partial sums are emptied into float64 every 12 visits (NBMI_FLUSH's rhythm).
+// Epilogues: k_walk's.  !kIntegrate: accelerations in the caller's order and the lane-accept count (nbmi_walk_counters).
+// Empty asm statements (the idiom of tie_visit64; no instruction is emitted) that pin every word of both records
+// behind their loads: the loads are all requested first and one wait covers them.  Without the pins the compiler sinks
+// the NodeQ load behind the leaf test, and a cell visit waits for scalar memory twice.
+#define NBMI_PIN_Q(Q) asm volatile("" : "+s"(Q.pxx), "+s"(Q.pyy), "+s"(Q.pzz), "+s"(Q.pxy), "+s"(Q.pxz), "+s"(Q.pyz))
+#define NBMI_PIN_N(N) asm volatile("" : "+s"(N.cx), "+s"(N.cy), "+s"(N.cz), "+s"(N.gm), "+s"(N.s2t), "+s"(N.next_off))
+#define NBMI_PIN_D(N) asm volatile("" : "+s"(N.cx), "+s"(N.cy), "+s"(N.cz), "+s"(N.gm), "+s"(N.s2t), "+s"(N.next_off))
+template <bool kIntegrate, bool kGuard, bool kLeap>
+__global__ __launch_bounds__(kBlock) void k_walk_quad(const Node *__restrict__ nodes, const NodeQ *__restrict__ nodesq,
+                                                      const NodeD *__restrict__ nodesd /* null: fp32 forces only */,
+                                                      const WalkTable *tab, const TreeInfo *info_in,
+                                                      const float4 *__restrict__ posm_s, const uint32_t *__restrict__ perm,
+                                                      double *__restrict__ acc_out, WalkParams P, TreeInfo *info_out) {
+    const int lb = logical_block(blockIdx.x, gridDim.x, P.xcd_chunk);
+    const int64_t rank = P.rank_begin + (int64_t)lb * blockDim.x + threadIdx.x;
+    const bool valid = rank < P.rank_end;
+    const bool frozen = info_in->error != 0 || info_in->sticky_error != 0;
+    const unsigned rows = __builtin_amdgcn_readfirstlane(frozen ? 0u : (unsigned)info_in->walk_nodes);
+    const unsigned band2 = __builtin_amdgcn_readfirstlane(info_in->band2);
+    float px = 0.f, py = 0.f, pz = 0.f;
+    uint32_t j = 0;
+    if (valid) {
+        const float4 p = posm_s[rank];
+        px = p.x; py = p.y; pz = p.z;
+        j = perm[rank];
+    }
+    const Body64 b64{tab, P.curbuf, j};
+    unsigned resume = valid ? 0u : 0xffffffffu;
+    float ax = 0.f, ay = 0.f, az = 0.f;
+    double sx = 0.0, sy = 0.0, sz = 0.0;
+    unsigned long long accepts = 0;
+    bool use64 = false;
+    if (nodesd && P.force_prec != 1) {
+        if (P.force_prec == 2) use64 = true;
+        else if (kIntegrate) use64 = tab->wave_flag[rank >> 6] != 0 || info_in->force_all64 != 0;
+        use64 = __builtin_amdgcn_readfirstlane((int)use64) != 0;
+    }
+    int since_flush = 0;
+    if (use64) {
+        // (the float64 records come as a kernel argument, not through the table as in k_walk: a pointer loaded from
+        // memory is a generic one to the compiler, and its loads become vector loads)
+        double qx = 0.0, qy = 0.0, qz = 0.0;
+        if (valid) {
+            const Bodies &cur = tab->buf[P.curbuf];
+            qx = cur.x[j]; qy = cur.y[j]; qz = cur.z[j];
+        }
+        const double eps2 = __longlong_as_double((long long)uniform_u64((unsigned long long)__double_as_longlong(tab->eps2)));
+        unsigned idx = 0u;
+        while (idx < rows) {
+            idx = __builtin_amdgcn_readfirstlane(idx);
+            NodeD nd = nodesd[idx];
+            NodeQ Q = *reinterpret_cast<const NodeQ *>(reinterpret_cast<const char *>(nodesq) + idx * kNodeBytes);
+            NBMI_PIN_D(nd);
+            NBMI_PIN_Q(Q);
+            const unsigned offd = idx * kNodeDBytes;
+            const double dx = nd.cx - qx, dy = nd.cy - qy, dz = nd.cz - qz;
+            const double d2 = __builtin_fma(dz, dz, __builtin_fma(dy, dy, __builtin_fma(dx, dx, eps2)));
+            const float d2f = (float)d2;
+            const bool active = resume <= offd;
+            const int d2b = __float_as_int(d2f), hi = __float_as_int(nd.s2t), lo = hi - 2 * (int)kBand64;
+            bool geom = hi < d2b;
+            if (active && !geom && lo < d2b) geom = (hi == 0) || exact_take_idx(idx, b64);
+            const bool take = active && geom;
+            const bool force = kGuard ? (take && d2 > eps2) : take;
+            if (!kIntegrate) accepts += (take && d2 > eps2) ? 1u : 0u;
+            if (force) {  // guard_visit64's monopole
+                const double y0 = (double)__builtin_amdgcn_rsqf(d2f);
+                const double t = y0 * y0;
+                double w = nd.gm * y0;
+                const double e = __builtin_fma(-d2, t, 1.0);
+                w = w * t;
+                const double h = e * 1.5;
+                w = __builtin_fma(w, h, w);
+                sx = __builtin_fma(dx, w, sx); sy = __builtin_fma(dy, w, sy); sz = __builtin_fma(dz, w, sz);
+            }
+            // (a leaf record, s2t == 0, carries no moments: a wave-uniform skip)
+            if (hi != 0) quad_term(Q, (float)dx, (float)dy, (float)dz, force ? __builtin_amdgcn_rsqf(d2f) : 0.f, ax, ay, az);
+            if (take) resume = nd.next_off;
+            if (++since_flush == 12) {
+                sx += (double)ax; sy += (double)ay; sz += (double)az;
+                ax = ay = az = 0.f;
+                since_flush = 0;
+            }
+            const unsigned long long any_open = __builtin_amdgcn_ballot_w64(active && !geom);
+            idx = any_open ? idx + 1u : nd.next_off / kNodeDBytes;
+        }
+    } else {
+        const unsigned nn = rows * kNodeBytes;
+        unsigned off = 0u;
+        while (off < nn) {
+            off = __builtin_amdgcn_readfirstlane(off);
+            Node nd = *reinterpret_cast<const Node *>(reinterpret_cast<const char *>(nodes) + off);
+            NodeQ Q = *reinterpret_cast<const NodeQ *>(reinterpret_cast<const char *>(nodesq) + off);
+            NBMI_PIN_N(nd);
+            NBMI_PIN_Q(Q);
+            // visit(): the same fp32 operations in the same order
+            const float dx = nd.cx - px, dy = nd.cy - py, dz = nd.cz - pz;
+            const float dist_sq = fmaf(dz, dz, fmaf(dy, dy, fmaf(dx, dx, P.eps2)));
+            const bool active = resume <= off;
+            const int d2b = __float_as_int(dist_sq), hi = __float_as_int(nd.s2t), lo = hi - (int)band2;
+            bool geom = hi < d2b;
+            const bool band = active && !geom && lo < d2b;
+            if (band) geom = (hi == 0) || exact_take(off, b64);
+            const bool take = active && geom;
+            const bool force = kGuard ? (take && dist_sq > P.eps2) : take;
+            if (!kIntegrate) accepts += (take && dist_sq > P.eps2) ? 1u : 0u;
+            const float inv = force ? __builtin_amdgcn_rsqf(dist_sq) : 0.f;
+            const float f = (nd.gm * inv) * (inv * inv);
+            ax = fmaf(dx, f, ax);
+            ay = fmaf(dy, f, ay);
+            az = fmaf(dz, f, az);
+            if (hi != 0) quad_term(Q, dx, dy, dz, inv, ax, ay, az);  // (a leaf record carries no moments: a wave-uniform skip)
+            resume = take ? nd.next_off : resume;
+            if (++since_flush == 12) {
+                sx += (double)ax; sy += (double)ay; sz += (double)az;
+                ax = ay = az = 0.f;
+                since_flush = 0;
+            }
+            const unsigned long long any_open = __builtin_amdgcn_ballot_w64(active && !geom);
+            off = any_open ? off + kNodeBytes : nd.next_off;
+        }
+    }
+    sx += (double)ax; sy += (double)ay; sz += (double)az;
+    if (kIntegrate) {
+        publish_maxabs(tab, valid ? integrate<kLeap>(tab, j, rank, sx, sy, sz, P, frozen) : 0.0);
+    } else {
+        if (valid) {
+            const int64_t o = 3 * (int64_t)tab->buf[P.curbuf].id[j];
+            acc_out[o] = sx; acc_out[o + 1] = sy; acc_out[o + 2] = sz;
+        }
+        atomicAdd(&info_out->lane_accepts, accepts);
     }
 }
 
@@ -3640,6 +3899,16 @@ struct nbmi_sim {
     int integrator = NBMI_INTEGRATOR_KICK_DRIFT;
     bool acc_valid = false;
     double *acc = nullptr;
+    // multipole order of an applied cell term (nbmi_set_multipole).  The three arrays exist from
+    // the first switch into quadrupole mode on: the walk's fp32 records, the float64 work rows of the bottom-up pass
+    // (kQuadDoubles per node row; the potential reads its moments there) and the float64 {cx, cy, cz, G m} rows of the
+    // mode's builds
+    int multipole = NBMI_MULTIPOLE_MONOPOLE;
+    int multipole_env = NBMI_MULTIPOLE_MONOPOLE;  // NBMI_MULTIPOLE: the initial value where the handle allows it
+    bool acc64_env = false;  // NBMI_ACC64 as it stood at creation: what nbmi_set_multipole's refusal goes by
+    NodeQ *nodesq = nullptr;
+    double *quad_work = nullptr;
+    double4 *quad_pot = nullptr;
     // one-wave walk: cursors per wave and where the array is cut.  -1 = by size: two cursors, cut at the middle of the
     // array, or (from kHomeSplitBodies = 1.5 M bodies on) at the leaf of the wave's middle body; NBMI_WALK_PAIR = 0 / 1 / 2 forces
     // one cursor / the middle cut / the home cut
@@ -3792,6 +4061,11 @@ int enqueue_global_tree(nbmi_sim *s, bool aux = true, double4 *diag = nullptr) {
     // theta = 0 means "never accept an internal node": s2t = +inf
     const double inv_theta2 = s->theta > 0.0 ? 1.0 / (s->theta * s->theta) : INFINITY;
     const int64_t ob = s->own_base;  // (owner mode: the own tree begins at this row of the walk array; node_level / node_ref / diag64 count from the tree's start)
+    const bool quad = s->multipole == NBMI_MULTIPOLE_QUADRUPOLE;
+    if (quad) {  // the bottom-up pass goes by level and reads the float64 rows
+        aux = true;
+        if (!diag) diag = s->quad_pot;
+    }
     {
         const int tile = n <= kEmitSmallBodies ? kEmitTileSmall : kEmitTile;
 #define NBMI_EMIT(TV) k_emit_tile<TV><<<(int)((n + TV - 1) / TV), kBlock, 0, st>>>(                                         \
@@ -3805,6 +4079,13 @@ int enqueue_global_tree(nbmi_sim *s, bool aux = true, double4 *diag = nullptr) {
     }
     if (s->walk_stack)
         k_child_table<<<nblocks(s->own_node_rows), kBlock, 0, st>>>(s->nodes, s->info, s->own_node_rows, s->child_tab);
+    if (quad && n > 0) {
+        // second moments, level by level from the deepest cells up (k_quad_level).  The host does not know the depth:
+        // every level is launched, and a launch above the deepest one returns at once
+        k_max_level<<<64, kBlock, 0, st>>>(s->delta, n, s->info);
+        for (int lev = kMaxLevel; lev >= 0; lev--)
+            k_quad_level<<<kQuadGrid, kBlock, 0, st>>>(s->nodes, s->node_level, diag, s->info, lev, s->quad_work, s->nodesq);
+    }
     NBMI_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -3821,7 +4102,7 @@ int enqueue_tree(nbmi_sim *s, int ev_base, bool aux = true, double4 *diag = null
     if (int rc = enqueue_local_sort(s, ev_base)) return rc;
     if (int rc = enqueue_global_tree(s, aux, diag)) return rc;
     if (ev_base >= 0) NBMI_HIP_CHECK(hipEventRecord(s->ev[3], s->stream));
-    s->tree_valid = aux;
+    s->tree_valid = aux || s->multipole == NBMI_MULTIPOLE_QUADRUPOLE;  // (a quadrupole build always writes node_ref / node_level)
     return 0;
 }
 
@@ -3882,6 +4163,21 @@ int enqueue_walk(nbmi_sim *s, bool integrate, double dt, double *acc_out, int le
         return 0;
     }
 
+    if (s->multipole == NBMI_MULTIPOLE_QUADRUPOLE) {  // one one-wave walk at every size
+        if (s->owner || s->prec || s->walk_lane || s->walk_stack || !s->nodesq) {
+            nbmi::set_error("internal: quadrupole walk on a handle that does not support it");
+            return NBMI_ERR_ARG;
+        }
+        const int gq = (int)((cntr + kBlock - 1) / kBlock);
+#define NBMI_WALK_QUAD(I, G, L) \
+    k_walk_quad<I, G, L><<<gq, kBlock, 0, st>>>(s->nodes, s->nodesq, P.force_prec != 1 ? s->nodesd : nullptr, tab, s->info, s->posm_s, s->perm, acc_out, P, s->info)
+        if (!integrate) { if (guard) NBMI_WALK_QUAD(false, true, false); else NBMI_WALK_QUAD(false, false, false); }
+        else if (leap) { if (guard) NBMI_WALK_QUAD(true, true, true); else NBMI_WALK_QUAD(true, false, true); }
+        else { if (guard) NBMI_WALK_QUAD(true, true, false); else NBMI_WALK_QUAD(true, false, false); }
+#undef NBMI_WALK_QUAD
+        NBMI_HIP_CHECK(hipGetLastError());
+        return 0;
+    }
     // few groups: a block of K waves per group, each walking one K-th of the array.  K depends only on
     // the size of the tree (not on the shard), so that every sharding adds up the same partial sums.
     const int64_t tree_groups = (s->nt + 63) / 64, groups = (cntr + 63) / 64;
@@ -4135,6 +4431,16 @@ void nbmi_destroy(nbmi_sim *s) {
     delete s;
 }
 
+// why this handle cannot run in quadrupole mode (nullptr: it can)
+static const char *multipole_refusal(const nbmi_sim *s) {
+    if (s->method != NBMI_METHOD_BARNES_HUT) return "direct N^2 handles have no cells";
+    if (s->owner) return "owner-mode handles are not supported (the exchanged tree rows carry no second moments)";
+    if (s->shard_begin != 0 || s->shard_end != s->n) return "sharded handles are not supported (the exchange rows carry no second moments)";
+    if (s->prec || s->walk_lane || s->walk_stack || s->acc64_env)
+        return "not available with the measurement-only walks (NBMI_PREC, NBMI_WALK_LANE, NBMI_ACC64, NBMI_WALK_STACK)";
+    return nullptr;
+}
+
 // measurement / tuning knobs, read once per handle by both constructors
 static void read_env_knobs(nbmi_sim *s) {
     if (const char *e = getenv("NBMI_XCD_CHUNK")) s->xcd_chunk = atoi(e);
@@ -4150,10 +4456,14 @@ static void read_env_knobs(nbmi_sim *s) {
         if (v >= 0 && v <= 2) s->force_prec = v;
     }
     if (const char *e = getenv("NBMI_PREC_TAU")) s->prec_tau = atof(e);
+    if (const char *e = getenv("NBMI_MULTIPOLE")) {
+        if (!strcmp(e, "quadrupole") || !strcmp(e, "1")) s->multipole_env = NBMI_MULTIPOLE_QUADRUPOLE;
+    }
     if (const char *e = getenv("NBMI_ALL64_ENTER")) s->all64_enter_pm = (int)(1000.0 * atof(e) + 0.5);
     if (const char *e = getenv("NBMI_ALL64_LEAVE")) s->all64_leave_pm = (int)(1000.0 * atof(e) + 0.5);
     if (const char *e = getenv("NBMI_PREC")) s->prec = atoi(e);
     if (const char *e = getenv("NBMI_PREC_NEAR")) s->prec_near = atof(e);
+    if (const char *e = getenv("NBMI_ACC64")) s->acc64_env = atoi(e) != 0;
     if (const char *e = getenv("NBMI_SORT_BITS")) {
         const int b = atoi(e);
         if (b >= 8 && b <= 63) s->sort_bits = b;
@@ -4260,6 +4570,7 @@ nbmi_sim *nbmi_create(int64_t n, const double *pos, const double *vel, const dou
         nbmi::set_error("%s", keep.c_str());
         return nullptr;
     }
+    if (s->multipole_env == NBMI_MULTIPOLE_QUADRUPOLE && !multipole_refusal(s)) (void)nbmi_set_multipole(s, s->multipole_env);
     if (method == NBMI_METHOD_DIRECT && n > 0 && mass[0] > 0.0) {
         bool same = true;
         for (int64_t i = 1; i < n && same; i++) same = mass[i] == mass[0];
@@ -4299,6 +4610,7 @@ nbmi_sim *nbmi_create_generated(int distribution, int64_t n, double spawn_radius
         nbmi::set_error("%s", keep.c_str());
         return nullptr;
     }
+    if (s->multipole_env == NBMI_MULTIPOLE_QUADRUPOLE && !multipole_refusal(s)) (void)nbmi_set_multipole(s, s->multipole_env);
     return s;
 }
 
@@ -4523,6 +4835,37 @@ int nbmi_get_integrator(nbmi_sim *s, int *out) {
     return 0;
 }
 
+int nbmi_set_multipole(nbmi_sim *s, int multipole) {
+    if (int rc = check_handle(s)) return rc;
+    if (multipole != NBMI_MULTIPOLE_MONOPOLE && multipole != NBMI_MULTIPOLE_QUADRUPOLE) {
+        nbmi::set_error("nbmi_set_multipole: unknown multipole order %d", multipole);
+        return NBMI_ERR_ARG;
+    }
+    if (multipole == NBMI_MULTIPOLE_QUADRUPOLE) {
+        if (const char *why = multipole_refusal(s)) {
+            nbmi::set_error("nbmi_set_multipole: %s", why);
+            return NBMI_ERR_ARG;
+        }
+        if (!s->nodesq && (dev_alloc(s, &s->nodesq, s->node_capacity + 2) ||
+                           dev_alloc(s, &s->quad_work, (size_t)kQuadDoubles * (s->node_capacity + 2)) ||
+                           dev_alloc(s, &s->quad_pot, s->node_capacity + 2)))
+            return NBMI_ERR_HIP;
+    }
+    if (multipole != s->multipole) {
+        s->tree_valid = false;  // the records the queries describe belong to the other mode's build
+        s->acc_valid = false;   // leapfrog: the stored a = F(x) is the other mode's force
+    }
+    s->multipole = multipole;
+    return 0;
+}
+
+int nbmi_get_multipole(nbmi_sim *s, int *out) {
+    if (int rc = check_handle(s)) return rc;
+    if (!out) { nbmi::set_error("null output"); return NBMI_ERR_ARG; }
+    *out = s->multipole;
+    return 0;
+}
+
 int nbmi_build_tree(nbmi_sim *s) {
     if (int rc = check_handle(s)) return rc;
     if (s->method != NBMI_METHOD_BARNES_HUT) { nbmi::set_error("not a Barnes-Hut handle"); return NBMI_ERR_ARG; }
@@ -4576,8 +4919,14 @@ int diag_potential(nbmi_sim *s) {
     s->step_dt = 0.0;  // no "auto" decision: the wave flags and force_all64 stay the last step's
     int rc = enqueue_tree(s, -1, false, s->diag_pot);
     if (rc == 0) {
-        k_potential_tree<<<nblocks(n), kBlock, 0, st>>>(s->nodes, s->diag_pot, s->wtab, s->info, s->posm_s, s->perm, s->curbuf,
-                                                        (float)(s->softening * s->softening), n, s->diag_phi, s->diag_cnt);
+        if (s->multipole == NBMI_MULTIPOLE_QUADRUPOLE)
+            k_potential_tree<true><<<nblocks(n), kBlock, 0, st>>>(s->nodes, s->diag_pot, s->wtab, s->info, s->posm_s, s->perm,
+                                                                  s->curbuf, (float)(s->softening * s->softening), n, s->diag_phi,
+                                                                  s->diag_cnt, s->quad_work);
+        else
+            k_potential_tree<false><<<nblocks(n), kBlock, 0, st>>>(s->nodes, s->diag_pot, s->wtab, s->info, s->posm_s, s->perm,
+                                                                   s->curbuf, (float)(s->softening * s->softening), n, s->diag_phi,
+                                                                   s->diag_cnt, nullptr);
         if (hipGetLastError() != hipSuccess) {
             nbmi::set_error("k_potential_tree launch failed");
             rc = NBMI_ERR_HIP;
@@ -4774,6 +5123,28 @@ int nbmi_get_cells(nbmi_sim *s, int32_t *level, uint64_t *key, int64_t capacity)
     return 0;
 }
 
+int nbmi_get_cell_moments(nbmi_sim *s, int32_t *level, uint64_t *key, double *moments6, int64_t capacity) {
+    if (int rc = check_handle(s)) return rc;
+    if (s->method != NBMI_METHOD_BARNES_HUT || !s->tree_valid || s->multipole != NBMI_MULTIPOLE_QUADRUPOLE) {
+        nbmi::set_error("nbmi_get_cell_moments: call nbmi_build_tree in quadrupole mode first");
+        return NBMI_ERR_ARG;
+    }
+    if (!moments6) { nbmi::set_error("null output"); return NBMI_ERR_ARG; }
+    if (int rc = nbmi_get_cells(s, level, key, capacity)) return rc;
+    if (s->n == 0) { for (int k = 0; k < 6; k++) moments6[k] = 0.0; return 0; }
+    int64_t nn = 0;
+    if (int rc = nbmi_tree_stats(s, &nn, nullptr, nullptr)) return rc;
+    double *dq = nullptr;
+    NBMI_HIP_CHECK(hipMalloc((void **)&dq, (size_t)nn * 48));
+    k_quad_export<<<nblocks(nn), kBlock, 0, s->stream>>>(s->nodes, s->nodesq, nn, dq);
+    hipError_t e1 = hipMemcpyAsync(moments6, dq, (size_t)nn * 48, hipMemcpyDeviceToHost, s->stream);
+    hipError_t e2 = hipStreamSynchronize(s->stream);
+    (void)hipFree(dq);
+    NBMI_HIP_CHECK(e1);
+    NBMI_HIP_CHECK(e2);
+    return 0;
+}
+
 int nbmi_enable_timers(nbmi_sim *s, int enable) {
     if (int rc = check_handle(s)) return rc;
     s->timers = enable != 0;
@@ -4810,6 +5181,10 @@ int nbmi_set_shard(nbmi_sim *s, int64_t begin, int64_t end) {
     if (int rc = check_handle(s)) return rc;
     if (begin < 0 || end < begin || end > s->n) {
         nbmi::set_error("nbmi_set_shard: bad range [%lld,%lld) for n=%lld", (long long)begin, (long long)end, (long long)s->n);
+        return NBMI_ERR_ARG;
+    }
+    if (s->multipole == NBMI_MULTIPOLE_QUADRUPOLE && (begin != 0 || end != s->n)) {
+        nbmi::set_error("nbmi_set_shard: quadrupole handles cannot be sharded (the exchange rows carry no second moments)");
         return NBMI_ERR_ARG;
     }
     if (s->integrator == NBMI_INTEGRATOR_LEAPFROG && (begin != 0 || end != s->n)) {

@@ -29,6 +29,9 @@ PROTOTYPES = {
     "nbmi_step_count": (_i64, [_vp]),
     "nbmi_set_integrator": (C.c_int, [_vp, C.c_int]),
     "nbmi_get_integrator": (C.c_int, [_vp, _vp]),
+    "nbmi_set_multipole": (C.c_int, [_vp, C.c_int]),
+    "nbmi_get_multipole": (C.c_int, [_vp, _vp]),
+    "nbmi_get_cell_moments": (C.c_int, [_vp, _vp, _vp, _vp, _i64]),
     "nbmi_compute_colors": (C.c_int, [_vp, _dbl]),
     "nbmi_get_positions_f32": (C.c_int, [_vp, _vp]),
     "nbmi_get_velocities_f64": (C.c_int, [_vp, _vp]),

@@ -29,6 +29,14 @@ METHOD_DIRECT = 1
 GENERATED_DISTRIBUTIONS = {"galaxy": 0, "collision": 1, "cluster": 2, "spiral": 3, "filament": 4}
 # integrators of nbmi_set_integrator (NBMI_INTEGRATOR_* of include/nbmi.h)
 INTEGRATORS = {"kick_drift": 0, "leapfrog": 1}
+# multipole orders of nbmi_set_multipole (NBMI_MULTIPOLE_* of include/nbmi.h)
+MULTIPOLES = {"monopole": 0, "quadrupole": 1}
+
+
+def _multipole_code(name):
+    if name not in MULTIPOLES:
+        raise ValueError(f"multipole must be one of {sorted(MULTIPOLES)}, not {name!r}")
+    return MULTIPOLES[name]
 
 
 def _integrator_code(name):
@@ -110,8 +118,9 @@ class _HIPSimulation:
     _method = METHOD_BARNES_HUT
 
     def __init__(self, positions, velocities, masses, G, softening, damping, theta=0.5, device=None,
-                 integrator="kick_drift"):
+                 integrator="kick_drift", multipole="monopole"):
         _integrator_code(integrator)
+        _multipole_code(multipole)
         lib = _nat.load()
         pos = _as_f64(positions, (3,))
         vel = _as_f64(velocities, (3,))
@@ -130,18 +139,18 @@ class _HIPSimulation:
             raise RuntimeError(f"nbmi_create failed: {_nat.last_error()}")
         kind = "Barnes-Hut" if self._method == METHOD_BARNES_HUT else "direct N^2"
         print(f"[HIP] Initialized with {self.n:,} bodies ({kind}) on device {self.device}")
-        if integrator != "kick_drift":
-            self.set_integrator(integrator)
+        self._apply_options(integrator, multipole)
 
     @classmethod
     def generated(cls, distribution, n, spawn_radius, G, softening, damping, theta=0.5, seed=42, device=None,
-                  integrator="kick_drift"):
+                  integrator="kick_drift", multipole="monopole"):
         """Same backend object, but the bodies are drawn ON THE DEVICE from the reference's
         generate_distribution formulas (tools/presets.py:104-295, :350-397, :609-684; `distribution`
         one of GENERATED_DISTRIBUTIONS) with a Philox stream keyed by `seed`: statistical, not bit,
         parity with the NumPy generator; no host arrays, no upload."""
         kinds = GENERATED_DISTRIBUTIONS
         _integrator_code(integrator)
+        _multipole_code(multipole)
         if distribution not in kinds:
             raise ValueError(f"device-side generator has {sorted(kinds)}, not {distribution!r}")
         self = cls.__new__(cls)
@@ -157,9 +166,19 @@ class _HIPSimulation:
         if not self._h:
             raise RuntimeError(f"nbmi_create_generated failed: {_nat.last_error()}")
         print(f"[HIP] Generated {self.n:,} bodies ({distribution}, seed {seed}) on device {self.device}")
-        if integrator != "kick_drift":
-            self.set_integrator(integrator)
+        self._apply_options(integrator, multipole)
         return self
+
+    def _apply_options(self, integrator, multipole):
+        """Constructor options that the library may refuse for this handle: a refusal closes the handle before it raises."""
+        try:
+            if integrator != "kick_drift":
+                self.set_integrator(integrator)
+            if multipole != "monopole":
+                self.set_multipole(multipole)
+        except Exception:
+            self.close()
+            raise
 
     def get_masses(self) -> np.ndarray:
         out = np.empty(self.n, dtype=np.float64)
@@ -211,6 +230,22 @@ class _HIPSimulation:
         out = C.c_int(0)
         _nat.check(self._lib.nbmi_get_integrator(self._h, C.addressof(out)), "nbmi_get_integrator")
         return {v: k for k, v in INTEGRATORS.items()}[out.value]
+
+    def set_multipole(self, multipole: str):
+        """"monopole" (default, the reference's term) or "quadrupole": an applied cell term also carries the cell's
+        second moments; the accepted (body, node) sets do not change (include/nbmi.h nbmi_set_multipole).  Direct,
+        owner-mode and sharded handles and the measurement-only walks refuse quadrupole with ValueError."""
+        code = _multipole_code(multipole)
+        rc = self._lib.nbmi_set_multipole(self._h, code)
+        if rc == -1:  # NBMI_ERR_ARG: refused for this handle
+            raise ValueError(f"set_multipole({multipole!r}): {_nat.last_error()}")
+        _nat.check(rc, "nbmi_set_multipole")
+
+    @property
+    def multipole(self) -> str:
+        out = C.c_int(0)
+        _nat.check(self._lib.nbmi_get_multipole(self._h, C.addressof(out)), "nbmi_get_multipole")
+        return {v: k for k, v in MULTIPOLES.items()}[out.value]
 
     def step_count(self) -> int:
         """Steps the device has been asked to take since the handle was created (counted by the library)."""
@@ -356,7 +391,7 @@ class _HIPSimulation:
     # multi-GPU row exchange (device pointers; see nbody/sharded.py)
     def set_shard(self, begin, end):
         rc = self._lib.nbmi_set_shard(self._h, int(begin), int(end))
-        if rc == -1 and self.integrator == "leapfrog":
+        if rc == -1 and (self.integrator == "leapfrog" or self.multipole == "quadrupole"):
             raise ValueError(f"set_shard: {_nat.last_error()}")
         _nat.check(rc, "nbmi_set_shard")
 
@@ -456,6 +491,19 @@ class HIPBarnesHutSimulation(_HIPSimulation):
         _nat.check(self._lib.nbmi_get_cells(self._h, _nat.ptr(level), _nat.ptr(key), nn), "nbmi_get_cells")
         return level, key
 
+    def cell_moments(self):
+        """(level, key, P) of every node of the last built tree in quadrupole mode: P (num_nodes, 6) float64 =
+        {Pxx, Pyy, Pzz, Pxy, Pxz, Pyz} of the walk's fp32 records (leaves: zeros)."""
+        nn = self.tree_stats()["num_nodes"]
+        level = np.empty(nn, dtype=np.int32)
+        key = np.empty(nn, dtype=np.uint64)
+        mom = np.empty((nn, 6), dtype=np.float64)
+        rc = self._lib.nbmi_get_cell_moments(self._h, _nat.ptr(level), _nat.ptr(key), _nat.ptr(mom), nn)
+        if rc == -1:
+            raise ValueError(f"cell_moments: {_nat.last_error()}")
+        _nat.check(rc, "nbmi_get_cell_moments")
+        return level, key, mom
+
     def walk_counters(self):
         out = np.zeros(17, dtype=np.int64)
         _nat.check(self._lib.nbmi_walk_counters(self._h, _nat.ptr(out)), "nbmi_walk_counters")
@@ -502,6 +550,12 @@ class HIPOwnerSimulation(HIPBarnesHutSimulation):
     @property
     def n(self):
         return int(self._lib.nbmi_owner_count(self._h)) if self._h else 0
+
+    def set_multipole(self, multipole: str):
+        if _multipole_code(multipole) != MULTIPOLES["monopole"]:
+            raise ValueError("owner-mode handles support only monopole terms (the exchanged tree rows carry no second "
+                             "moments)")
+        super().set_multipole(multipole)
 
     def set_integrator(self, integrator: str):
         if _integrator_code(integrator) != INTEGRATORS["kick_drift"]:
@@ -573,9 +627,10 @@ class HIPDirectSimulation(_HIPSimulation):
 
     _method = METHOD_DIRECT
 
-    def __init__(self, positions, velocities, masses, G, softening, damping, device=None, integrator="kick_drift"):
+    def __init__(self, positions, velocities, masses, G, softening, damping, device=None, integrator="kick_drift",
+                 multipole="monopole"):
         super().__init__(positions, velocities, masses, G, softening, damping, theta=0.0, device=device,
-                         integrator=integrator)
+                         integrator=integrator, multipole=multipole)
 
 
 # Reference thresholds (:618-620) exist because its GPU paths are O(N^2); the HIP Barnes-Hut
@@ -585,9 +640,10 @@ HIP_BH_THRESHOLD = 100_000_000  # = kMaxBodies of libnbmi.so (node links are 32-
 
 def create_gpu_simulation(positions: np.ndarray, velocities: np.ndarray, masses: np.ndarray, G: float,
                           softening: float, damping: float, theta: float = 0.5, force_gpu: bool = False,
-                          method: Optional[str] = None, integrator: str = "kick_drift"):
-    """Reference signature (:623-625) plus ``method`` ("barnes_hut" default, or "direct") and ``integrator``
-    ("kick_drift" default, or "leapfrog"; see _HIPSimulation.set_integrator).
+                          method: Optional[str] = None, integrator: str = "kick_drift", multipole: str = "monopole"):
+    """Reference signature (:623-625) plus ``method`` ("barnes_hut" default, or "direct"), ``integrator``
+    ("kick_drift" default, or "leapfrog"; see _HIPSimulation.set_integrator) and ``multipole`` ("monopole" default, or
+    "quadrupole"; see _HIPSimulation.set_multipole).
 
     Returns a backend object, or None if the HIP backend is not available / not selected."""
     backend, _info = get_backend()
@@ -596,8 +652,10 @@ def create_gpu_simulation(positions: np.ndarray, velocities: np.ndarray, masses:
         return None
     method = method or os.environ.get("NBMI_METHOD", "barnes_hut")
     if method == "direct":
-        return HIPDirectSimulation(positions, velocities, masses, G, softening, damping, integrator=integrator)
+        return HIPDirectSimulation(positions, velocities, masses, G, softening, damping, integrator=integrator,
+                                   multipole=multipole)
     if n <= HIP_BH_THRESHOLD or force_gpu:
-        return HIPBarnesHutSimulation(positions, velocities, masses, G, softening, damping, theta, integrator=integrator)
+        return HIPBarnesHutSimulation(positions, velocities, masses, G, softening, damping, theta, integrator=integrator,
+                                      multipole=multipole)
     print(f"[GPU] {n:,} bodies exceeds the HIP Barnes-Hut limit ({HIP_BH_THRESHOLD:,})")
     return None

@@ -56,12 +56,19 @@ def _refuse_leapfrog(integrator):
         raise ValueError(f"sharded N-body runs support only the kick_drift integrator, not {integrator!r}")
 
 
+def _refuse_quadrupole(multipole):
+    """The exchanged rows carry no second moments: sharded and owner-mode runs apply monopole terms only."""
+    if multipole != "monopole":
+        raise ValueError(f"sharded N-body runs support only monopole cell terms, not {multipole!r}")
+
+
 class HipShardEngine:
     """Shard engine on top of HIPBarnesHutSimulation; rows travel as torch CUDA tensors."""
 
     def __init__(self, positions, velocities, masses, G, softening, damping, theta, device, method="barnes_hut",
-                 integrator="kick_drift"):
+                 integrator="kick_drift", multipole="monopole"):
         _refuse_leapfrog(integrator)
+        _refuse_quadrupole(multipole)
         import torch
         from .gpu_backend import HIPBarnesHutSimulation, HIPDirectSimulation
         self.torch = torch
@@ -152,13 +159,15 @@ class ShardedBarnesHut:
 
 
 def create_sharded_simulation(positions, velocities, masses, G, softening, damping, theta=0.5, mode="rows",
-                              method="barnes_hut", integrator="kick_drift"):
+                              method="barnes_hut", integrator="kick_drift", multipole="monopole"):
     """Build the multi-GPU stepper from the torch.distributed environment (RANK/LOCAL_RANK/
     WORLD_SIZE).  Every rank passes the same full arrays.  mode: "rows" (stage 1, replicated state and
     tree, bit-exact) or "let" (stage 2, owned key ranges + locally essential trees); method "direct"
     shards the all-pairs kernel by body index through the row exchange.  Only the kick_drift integrator:
-    "leapfrog" raises ValueError (the exchanged rows carry no acceleration columns)."""
+    "leapfrog" raises ValueError (the exchanged rows carry no acceleration columns), and so does multipole
+    "quadrupole" (they carry no second moments either)."""
     _refuse_leapfrog(integrator)
+    _refuse_quadrupole(multipole)
     import os
     import torch
     import torch.distributed as dist
@@ -193,8 +202,9 @@ class HipLetEngine:
     LET_ROW_BYTES = 48   # float64 {cx, cy, cz, G m}, float s2t, uint next, float64 half size (nbmi_owner_let_row_bytes)
 
     def __init__(self, positions, velocities, masses, G, softening, damping, theta, device, rank, world,
-                 integrator="kick_drift"):
+                 integrator="kick_drift", multipole="monopole"):
         _refuse_leapfrog(integrator)
+        _refuse_quadrupole(multipole)
         import torch
         from .gpu_backend import HIPBarnesHutSimulation, HIPOwnerSimulation
         self.torch = torch

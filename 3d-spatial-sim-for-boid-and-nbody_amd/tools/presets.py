@@ -208,14 +208,15 @@ def generate_distribution(distribution: str, n: int, R: float, G: float) -> Tupl
 
 
 def generate_distribution_device(distribution: str, n: int, R: float, G: float, softening: float, damping: float = 1.0,
-                                 theta: float = 0.5, seed: int = 42, device=None, integrator: str = "kick_drift"):
+                                 theta: float = 0.5, seed: int = 42, device=None, integrator: str = "kick_drift",
+                                 multipole: str = "monopole"):
     """generate_distribution + backend construction in one step, on the GPU: returns a
     HIPBarnesHutSimulation whose bodies were drawn on the device (nbmi_create_generated; Philox
     stream, statistical parity with generate_distribution).  At 10 M bodies this replaces seconds of
     NumPy and a 640 MB upload by a few milliseconds."""
     from nbody.gpu_backend import HIPBarnesHutSimulation
     return HIPBarnesHutSimulation.generated(distribution, n, R, G, softening, damping, theta=theta, seed=seed,
-                                            device=device, integrator=integrator)
+                                            device=device, integrator=integrator, multipole=multipole)
 
 
 def _preset(name, desc, cat, n, theta, G, eps, R, dist, frames, dtf, sub, fps, est):

@@ -96,6 +96,49 @@ int nbmi_step(nbmi_sim *sim, double dt, int substeps);
 #define NBMI_INTEGRATOR_LEAPFROG 1
 int nbmi_set_integrator(nbmi_sim *sim, int integrator);
 int nbmi_get_integrator(nbmi_sim *sim, int *out);
+/* Multipole order of an applied Barnes-Hut cell term.
+ *   NBMI_MULTIPOLE_MONOPOLE (default): a point mass at the cell's centre of mass - the reference's term; everything this
+ *     header says elsewhere describes it.  A handle that never leaves it runs the force kernels and the octree build
+ *     unchanged.  (The tree potential of nbmi_diagnostics / nbmi_get_potentials_f64 changed together with the mode, in
+ *     both modes: see the note on near pairs there.)
+ *   NBMI_MULTIPOLE_QUADRUPOLE: the octree, the opening test, the float64 re-decision of ties, the own-leaf rule and the
+ *     node_mass > 0, dist_sq > eps^2 guards are untouched: a body's set of applied (body, node) terms at the handle's theta
+ *     is the reference's, in both modes.  Only the VALUE of a term changes, and only for internal cells.  An internal
+ *     cell n additionally carries the raw second moments of its bodies about its centre of mass c_n,
+ *       P_ab = sum_j G m_j (x_j - c_n)_a (x_j - c_n)_b
+ *     (six numbers, G folded in; raw, not traceless: the kernel is Plummer-softened, f(r) = -(r^2 + eps^2)^(-1/2), its
+ *     Laplacian does not vanish, so the trace carries force).  A leaf has P = 0.  With d = c_n - x_i and
+ *     u = |d|^2 + eps^2 (the dist_sq of the test) an applied cell term is
+ *       a_i   += G M d u^(-3/2)                                                     (the monopole term, arithmetic unchanged)
+ *              + [ 7.5 (d^T P d) u^(-7/2) - 1.5 tr(P) u^(-5/2) ] d  -  3 u^(-5/2) (P d)
+ *       phi_i += - G M u^(-1/2)  +  1/2 [ tr(P) u^(-3/2) - 3 (d^T P d) u^(-5/2) ]
+ *     the second-order Taylor term of sum_j G m_j f(x_i - x_j) about c_n (the dipole vanishes there); a = -grad phi holds
+ *     term by term.  The correction is evaluated through e = d u^(-1/2) as u^(-2) [(7.5 e^T P e - 1.5 tr P) e - 3 P e], which
+ *     forms nothing beyond u^(-2).
+ *     Precision: the monopole part of a term is computed as the handle's force precision computes it (fp32, per-wave
+ *     "auto", float64; the build's "auto" decision is unchanged).  The correction is fp32 arithmetic in every mode; in a
+ *     float64 wave it starts from the float64 difference d rounded to fp32, not from the difference of fp32-rounded
+ *     coordinates.  fp32 partial sums are emptied into float64 every 12 visits.
+ *     nbmi_get_accelerations_f64, nbmi_step (kick-drift and leapfrog, damping included), nbmi_get_potentials_f64 and
+ *     nbmi_diagnostics(with_potential = 1) all use the mode's terms, so E = K + W stays the energy of the force that moves
+ *     the bodies.  In quadrupole mode nbmi_get_accelerations_f64 HONOURS force precision 1 (fp32) and 2 (float64); 0
+ *     ("auto") has no wave flags without a step's dt and means fp32 (the monopole force pass is fp32 whatever the mode).
+ *     `terms` of nbmi_diagnostics and the lane-accept count of nbmi_walk_counters after nbmi_get_accelerations_f64 are the
+ *     same numbers in both modes; the other sixteen walk counters read 0 in quadrupole mode.  The mode's walk contains
+ *     no instruction written by hand; two empty asm statements pin its scalar loads in place.
+ *     One one-wave walk serves every size (no split walk below 280 k bodies, no XCD balance mode).  The first switch into
+ *     the mode allocates 24 + 72 + 32 bytes per node row; every build of the mode also writes the rows the cell queries read
+ *     and runs a bottom-up pass over the levels of the tree for the moments.
+ *     Refused with NBMI_ERR_ARG: direct N^2 handles, owner-mode handles, handles with a proper shard (nbmi_set_shard, in
+ *     either order of the calls: their exchanged rows carry no P), the measurement-only walks (NBMI_PREC, NBMI_WALK_LANE,
+ *     NBMI_ACC64, NBMI_WALK_STACK).
+ * A switch drops the stored leapfrog acceleration (the next step primes it in the new mode).  Environment NBMI_MULTIPOLE
+ * ("quadrupole" or "1"; anything else means monopole) sets the initial value on handles that allow it.  NBMI_ACC64 and the
+ * other measurement knobs are read when the handle is created. */
+#define NBMI_MULTIPOLE_MONOPOLE 0
+#define NBMI_MULTIPOLE_QUADRUPOLE 1
+int nbmi_set_multipole(nbmi_sim *sim, int multipole);
+int nbmi_get_multipole(nbmi_sim *sim, int *out);
 /* Number of steps enqueued on this handle since it was created (every substep of nbmi_step counts).  The
  * recorder's Ctrl-C path asks the library, not its own bookkeeping, which frame the device has reached: an
  * interrupt is delivered when nbmi_step returns, before the caller can note that the step was taken
@@ -147,6 +190,10 @@ int nbmi_get_order(nbmi_sim *sim, int32_t *order);
 /* (level, path key) of every node of the most recently built tree (num_nodes entries,
  * unspecified order).  Keys of levels > 21 are reported as UINT64_MAX. */
 int nbmi_get_cells(nbmi_sim *sim, int32_t *level, uint64_t *key, int64_t capacity);
+/* Quadrupole mode, after nbmi_build_tree: nbmi_get_cells' (level, key) of every node plus its six second moments
+ * {Pxx, Pyy, Pzz, Pxy, Pxz, Pyz} as the walk's fp32 records hold them, widened to float64 (num_nodes x 6; a leaf has no
+ * record: zeros). */
+int nbmi_get_cell_moments(nbmi_sim *sim, int32_t *level, uint64_t *key, double *moments6, int64_t capacity);
 /* Per-phase device time in ms accumulated since the last reset:
  * [bounds+keys, sort, tree build, walk+integrate, other]; count = steps accumulated.
  * Enabling timers adds hipEvent records to every step. */
@@ -172,6 +219,12 @@ int nbmi_walk_counters(nbmi_sim *sim, int64_t *out17);
  *     node's float64 moments (the double-double prefix sums of the build); a leaf uses its body's float64 position and
  *     G m.  A pair whose dist_sq rounds to eps^2 adds no force; it would add -G m / eps here, so the guard skips it too.
  *     The accepted sets are the force walk's: the same octree of the current positions, the same opening decision.
+ *     Near pairs: the fp32 opening test carries an uncertainty band of at most 2^21 ulps of d^2, which covers its rounding
+ *     only for pairs at least 3.3e-6 of the largest coordinate apart.  With softening 0, or one below that length, closer
+ *     pairs exist; a cell closer than 8e-6 of the largest coordinate is then decided by the reference's float64 test
+ *     outright, so `terms` and phi are the reference's there too.  (Before quadrupole mode was added such cells went by
+ *     the fp32 test alone: on 2 048 bodies within 1e-3 of a point at coordinate 700, `terms` read 19 above the reference's
+ *     1 628 049.)  Handles with a softening above 3.3e-6 of the largest coordinate are not affected.
  *   Direct handle (exact pair sum): phi_i = - sum_{j != i} G m_j / sqrt(|x_j - x_i|^2 + eps^2); with eps == 0 pairs at
  *     zero distance are skipped (as the force kernel skips them).
  * All arithmetic is float64 (sqrt and divide correctly rounded); the sums are per-block partials over the state rows
