@@ -2300,11 +2300,9 @@ __global__ __launch_bounds__(kBlock) void k_direct(const float4 *__restrict__ po
 // rows written in the caller's body order.
 // ---------------------------------------------------------------------------------------
 // (shared by k_colors and k_frame_snapshot: one ramp, so a snapshot's colours are nbmi_compute_colors' bit for bit)
-__device__ __forceinline__ void color_ramp(double vx, double vy, double vz, double max_speed, float &out_r, float &out_g,
-                                           float &out_b) {
-    const double speed = sqrt(__dadd_rn(__dadd_rn(__dmul_rn(vx, vx), __dmul_rn(vy, vy)), __dmul_rn(vz, vz)));
-    double t = speed / max_speed;
-    t = t > 1.0 ? 1.0 : t;
+// the ramp itself, a function of t (values above 1 are the caller's to clamp): the speed colours enter with
+// t = speed / max_speed, the density colours (K16) with t = the position of log10(rho) in its range
+__device__ __forceinline__ void color_ramp_t(double t, float &out_r, float &out_g, float &out_b) {
     double cr, cg, cb, s, s2;
     if (t < 0.55) {
         if (t < 0.15) {
@@ -2336,6 +2334,37 @@ __device__ __forceinline__ void color_ramp(double vx, double vy, double vz, doub
         cr = 1.0; cg = __dsub_rn(0.5, __dmul_rn(0.5, s)); cb = 0.0;
     }
     out_r = (float)cr; out_g = (float)cg; out_b = (float)cb;
+}
+__device__ __forceinline__ void color_ramp(double vx, double vy, double vz, double max_speed, float &out_r, float &out_g,
+                                           float &out_b) {
+    const double speed = sqrt(__dadd_rn(__dadd_rn(__dmul_rn(vx, vx), __dmul_rn(vy, vy)), __dmul_rn(vz, vz)));
+    double t = speed / max_speed;
+    t = t > 1.0 ? 1.0 : t;
+    color_ramp_t(t, out_r, out_g, out_b);
+}
+// density colours (nbmi_set_color_mode): rho = the mass inside the k-th neighbour sphere over
+// its volume, +inf where the sphere has no radius; t = where log10(rho) lies in [lo, hi].  Shared by k_colors_density
+// and k_frame_snapshot, like the ramp.
+__device__ __forceinline__ double knn_density(double r2, double mass) {
+    if (r2 == 0.0) return INFINITY;
+    return mass / __dmul_rn(4.1887902047863905, __dmul_rn(r2, sqrt(r2)));
+}
+__device__ __forceinline__ void color_density(double r2, double mass, double lo, double hi, float &out_r, float &out_g,
+                                              float &out_b) {
+    double t = __dsub_rn(log10(knn_density(r2, mass)), lo) / __dsub_rn(hi, lo);
+    t = t > 1.0 ? 1.0 : t;
+    t = t < 0.0 ? 0.0 : t;
+    color_ramp_t(t, out_r, out_g, out_b);
+}
+__global__ __launch_bounds__(kBlock) void k_colors_density(Bodies cur, int64_t n, const double *__restrict__ r2,
+                                                           const double *__restrict__ mass, double lo, double hi,
+                                                           float *__restrict__ colors) {
+    const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (r >= n) return;
+    float cr, cg, cb;
+    color_density(r2[r], mass[r], lo, hi, cr, cg, cb);
+    const int64_t o = 3 * (int64_t)cur.id[r];
+    colors[o] = cr; colors[o + 1] = cg; colors[o + 2] = cb;
 }
 __global__ __launch_bounds__(kBlock) void k_colors(Bodies cur, int64_t n, double max_speed, bool by_rank,
                                                    float *__restrict__ colors) {
@@ -2408,7 +2437,9 @@ __global__ __launch_bounds__(kBlock) void k_frame_snapshot(Bodies cur, int64_t n
                                                            float *__restrict__ prev, void *__restrict__ first,
                                                            void *__restrict__ second, const TreeInfo *__restrict__ info,
                                                            const unsigned *__restrict__ sort_error,
-                                                           FrameHeader *__restrict__ header) {
+                                                           FrameHeader *__restrict__ header,
+                                                           const double *__restrict__ knn_r2 /* null: speed colours */,
+                                                           const double *__restrict__ knn_mass, double rho_lo, double rho_hi) {
     const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (r == 0) {
         header->error = info->error;
@@ -2420,7 +2451,8 @@ __global__ __launch_bounds__(kBlock) void k_frame_snapshot(Bodies cur, int64_t n
     }
     if (r >= n) return;
     float c[3], p[3];
-    color_ramp(cur.vx[r], cur.vy[r], cur.vz[r], max_speed, c[0], c[1], c[2]);
+    if (knn_r2) color_density(knn_r2[r], knn_mass[r], rho_lo, rho_hi, c[0], c[1], c[2]);  // (k_colors_density's colours)
+    else color_ramp(cur.vx[r], cur.vy[r], cur.vz[r], max_speed, c[0], c[1], c[2]);
     p[0] = (float)cur.x[r]; p[1] = (float)cur.y[r]; p[2] = (float)cur.z[r];
     const int64_t o = 3 * (int64_t)cur.id[r];
     for (int k = 0; k < 3; k++) colors[o + k] = c[k];
@@ -3765,6 +3797,228 @@ __global__ __launch_bounds__(kBlock) void k_unperm1_f64(const double *__restrict
     if (r < n) out[id[r]] = a[r];
 }
 
+// ---------------------------------------------------------------------------------------
+// K16: exact k-nearest-neighbour query (nbmi_knn / nbmi_get_densities_f64 / density colours; include/nbmi.h,
+// DESIGN.md section 4.14).  Float64 throughout, every sum in a fixed order: two calls on one state agree bit for bit.
+// ---------------------------------------------------------------------------------------
+// The query's own row per node of its build, written after the emission from what the build left behind (the build
+// itself is untouched): node_ref gives the node's first body in key order, perm its state row.
+//   leaf           {x, y, z, m}   the body as the float64 state has it; m is the MASS (cur.m), not G m
+//   internal cell  {x, y, z, w}   the cell's FIRST body (the "anchor") and the reach w = 2 hs + 2^-44 bounds
+// Why the anchor and not the centre of mass: the bodies of a level-L cell share L key digits, so per axis they lie
+// between two of the centres k_keys computed on the way down - 2 hs apart in exact arithmetic, and at most
+// 43 roundings of half an ulp(bounds) each further apart as computed (hence the 2^-44 bounds, 2^9 times that).  So
+// every body of the cell is within w of the anchor on every axis, and that statement has no rounding of a sum of
+// masses in it.  (The computed centre of mass has: its error grows with the mass ratio of the sub-tile to the cell,
+// without bound relative to the cell's size.)
+constexpr int kKnnBlock = 64;  // one wave per workgroup: its k x 512 bytes of LDS are then the allocation unit
+constexpr int kKnnMaxK = 64;
+__global__ __launch_bounds__(kBlock) void k_knn_rows(const Node *__restrict__ nodes, const Node64 *__restrict__ n64,
+                                                     const int32_t *__restrict__ node_ref, const uint32_t *__restrict__ perm,
+                                                     Bodies cur, const TreeInfo *__restrict__ info, int64_t capacity,
+                                                     double4 *__restrict__ rows) {
+    if (info->error != 0 || info->sticky_error != 0) return;  // the tree did not fit: the caller reports it
+    const int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (idx >= info->num_nodes || idx >= capacity) return;
+    const uint32_t j = perm[node_ref[idx]];
+    const bool leaf = __float_as_int(nodes[idx].s2t) == 0;
+    const double w = leaf ? cur.m[j] : __dadd_rn(__dmul_rn(2.0, n64[idx].hs), __dmul_rn(info->bounds, 0x1p-44));
+    rows[idx] = make_double4(cur.x[j], cur.y[j], cur.z[j], w);
+}
+
+// d2(i, j) as the header defines it: float64, this association, no FMA
+__device__ __forceinline__ double knn_d2(double bx, double by, double bz, double qx, double qy, double qz) {
+    const double dx = __dsub_rn(bx, qx), dy = __dsub_rn(by, qy), dz = __dsub_rn(bz, qz);
+    return __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
+}
+// A lower bound on the COMPUTED d2 between q and every body within `w` per axis of the anchor (ax, ay, az).  Per axis the
+// true gap is G = |q - a| - w (or 0).  t = fl|q - a| is within u t of it (u = 2^-53), fl(t - w) within u t of t - w (when
+// it is positive, w < t), the stored w within u w < u t of the reach, the last subtraction within u t again: g <=
+// G - (2^-49 - 4 u) t < G.  A body's computed |dx| is >= G (1 - u), its computed d2 >= (sum G^2)(1 - u)^5; the bound
+// below is <= (sum g^2)(1 + u)^3 (1 - 2^-48).  2^-48 = 32 u leaves a factor four.  Below 2^-960 the products may be
+// subnormal and the relative bounds no longer hold: such a bound counts as 0 (never prunes).
+__device__ __forceinline__ double knn_lower(double4 a, double qx, double qy, double qz) {
+    const double tx = fabs(__dsub_rn(a.x, qx)), ty = fabs(__dsub_rn(a.y, qy)), tz = fabs(__dsub_rn(a.z, qz));
+    double gx = __dsub_rn(__dsub_rn(tx, a.w), __dmul_rn(tx, 0x1p-49));
+    double gy = __dsub_rn(__dsub_rn(ty, a.w), __dmul_rn(ty, 0x1p-49));
+    double gz = __dsub_rn(__dsub_rn(tz, a.w), __dmul_rn(tz, 0x1p-49));
+    gx = gx > 0.0 ? gx : 0.0; gy = gy > 0.0 ? gy : 0.0; gz = gz > 0.0 ? gz : 0.0;
+    const double lo = __dmul_rn(__dadd_rn(__dadd_rn(__dmul_rn(gx, gx), __dmul_rn(gy, gy)), __dmul_rn(gz, gz)), 1.0 - 0x1p-48);
+    return lo > 0x1p-960 ? lo : 0.0;
+}
+// A lane's candidate list: a binary max-heap of its k smallest d2 so far, slot s of lane l at h[64 s] (h = the
+// wave's array + l).  The column of a lane is 8 bytes wide, so whatever slots the 64 lanes address, a 32-lane group
+// of a ds_read_b64 touches 32 distinct bank pairs and a 16-lane group of a ds_write_b64 sixteen: no conflicts although
+// every lane sifts along its own path.  Replaces the root (the current k-th smallest) by v < root.
+__device__ __forceinline__ void knn_push(double *__restrict__ h, int k, double v) {
+    int i = 0;
+    for (;;) {
+        int c = 2 * i + 1;
+        if (c >= k) break;
+        double a = h[64 * c];
+        const double b = c + 1 < k ? h[64 * (c + 1)] : -1.0;  // (every d2 is >= 0)
+        if (b > a) { a = b; c = c + 1; }
+        if (!(a > v)) break;
+        h[64 * i] = a;
+        i = c;
+    }
+    h[64 * i] = v;
+}
+__device__ __forceinline__ double knn_bcast(double v, int lane) {  // lane is wave-uniform
+    const long long b = __double_as_longlong(v);
+    const int lo = __builtin_amdgcn_readlane((int)b, lane), hi = __builtin_amdgcn_readlane((int)(b >> 32), lane);
+    return __longlong_as_double(((long long)hi << 32) | (unsigned long long)(unsigned)lo);
+}
+// the 64 bodies at the key ranks base .. base + 63, one per lane (ranks outside [0, n) hold zeros and are never used)
+struct KnnGroup {
+    double x, y, z, m;
+    int64_t base;
+};
+__device__ __forceinline__ KnnGroup knn_group(const Bodies &cur, const uint32_t *__restrict__ perm, int64_t base, int64_t n) {
+    KnnGroup g{0.0, 0.0, 0.0, 0.0, base};
+    const int64_t r = base + (int64_t)(threadIdx.x & 63);
+    if (r >= 0 && r < n) {
+        const uint32_t j = perm[r];
+        g.x = cur.x[j]; g.y = cur.y[j]; g.z = cur.z[j]; g.m = cur.m[j];
+    }
+    return g;
+}
+// One pass over the tree for one wave, k_potential_tree's skeleton: a wave-uniform byte cursor over `Node` and its
+// skip links, per lane `resume` = the offset up to which it sits out because it pruned an ancestor; the wave
+// descends while any active lane cannot prune.  `bound` is what a lane prunes against, strictly: a subtree is
+// skipped only if the lower bound EXCEEDS it, so bodies AT the bound are always reached.
+//   kSum = false  bound = the lane's current k-th candidate (the heap's root), leaves are pushed
+//   kSum = true   bound = r2_k, fixed; leaves with d2 <= r2_k add their mass to `acc`
+// Leaves of the ranks [ex_lo, ex_hi) are skipped: the caller has dealt with those bodies (the wave's own among them,
+// which is how self is excluded by identity).
+template <bool kSum>
+__device__ __forceinline__ void knn_walk(const Node *__restrict__ nodes, const double4 *__restrict__ rows,
+                                         const int32_t *__restrict__ node_ref, unsigned nn, bool valid, double qx, double qy,
+                                         double qz, int64_t ex_lo, int64_t ex_hi, double *__restrict__ h, int k, double &bound,
+                                         double &acc, long long &evals) {
+    unsigned resume = valid ? 0u : 0xffffffffu;
+    unsigned off = 0u;
+    while (off < nn) {
+        off = __builtin_amdgcn_readfirstlane(off);
+        const unsigned idx = off / kNodeBytes;
+        const Node nd = nodes[idx];
+        const double4 row = rows[idx];
+        const bool active = resume <= off;
+        if (__float_as_int(nd.s2t) == 0) {  // a leaf
+            const int64_t r = node_ref[idx];
+            if (active && (r < ex_lo || r >= ex_hi)) {
+                const double d2 = knn_d2(row.x, row.y, row.z, qx, qy, qz);
+                evals++;
+                if (kSum) {
+                    if (d2 <= bound) acc = __dadd_rn(acc, row.w);
+                } else if (d2 < bound) {
+                    knn_push(h, k, d2);
+                    bound = h[0];
+                }
+            }
+            off += kNodeBytes;
+        } else {
+            bool open = false;
+            if (active) {
+                open = !(knn_lower(row, qx, qy, qz) > bound);
+                if (!open) resume = nd.next_off;
+            }
+            off = __builtin_amdgcn_ballot_w64(open) ? off + kNodeBytes : nd.next_off;
+        }
+    }
+}
+// One wave per 64 key-adjacent bodies, in one launch:
+//   seed     exact distances to the wave's own 64 bodies and the 64 before and after them in key order (Hilbert
+//            neighbours, exchanged through readlane) fill the lists, so the first bound is already tight
+//   phase 1  walk, pushing every other body's d2 that beats the k-th candidate: the root is then r2_k, the k-th smallest
+//            of the multiset (each body is looked at once: no duplicates; ties only ever compare by value)
+//   phase 2  mass_k = m_i + the masses at d2 <= r2_k: the seeded ranks again, then a second walk against the fixed bound
+// Results land at the body's state row j = perm[rank]; evals (may be null) counts the distances of all three parts.
+__global__ __launch_bounds__(kKnnBlock) void k_knn(const Node *__restrict__ nodes, const double4 *__restrict__ rows,
+                                                   const int32_t *__restrict__ node_ref, const TreeInfo *__restrict__ info,
+                                                   const uint32_t *__restrict__ perm, Bodies cur, int64_t n, int k,
+                                                   double *__restrict__ r2_out, double *__restrict__ mass_out,
+                                                   unsigned long long *__restrict__ evals_out) {
+    extern __shared__ double knn_lds[];  // [k][64]
+    if (info->error != 0 || info->sticky_error != 0) return;
+    const int lane = threadIdx.x;
+    const int64_t w0 = (int64_t)blockIdx.x * kKnnBlock, rank = w0 + lane;
+    const bool valid = rank < n;
+    const unsigned nn = __builtin_amdgcn_readfirstlane((unsigned)info->num_nodes * kNodeBytes);
+    double *h = knn_lds + lane;
+    for (int s = 0; s < k; s++) h[64 * s] = INFINITY;
+    const KnnGroup grp[3] = {knn_group(cur, perm, w0, n), knn_group(cur, perm, w0 - 64, n), knn_group(cur, perm, w0 + 64, n)};
+    const double qx = grp[0].x, qy = grp[0].y, qz = grp[0].z;
+    const int64_t ex_lo = w0 - 64 > 0 ? w0 - 64 : 0, ex_hi = w0 + 128 < n ? w0 + 128 : n;
+    long long evals = 0;
+    double bound = INFINITY, acc = 0.0;
+#pragma unroll
+    for (int g = 0; g < 3; g++) {
+        for (int i = 0; i < 64; i++) {
+            const int64_t r = grp[g].base + i;
+            if (r < 0 || r >= n) continue;
+            const double d2 = knn_d2(knn_bcast(grp[g].x, i), knn_bcast(grp[g].y, i), knn_bcast(grp[g].z, i), qx, qy, qz);
+            if (valid && r != rank) {
+                evals++;
+                if (d2 < bound) {
+                    knn_push(h, k, d2);
+                    bound = h[0];
+                }
+            }
+        }
+    }
+    knn_walk<false>(nodes, rows, node_ref, nn, valid, qx, qy, qz, ex_lo, ex_hi, h, k, bound, acc, evals);
+    const double r2k = bound;
+    acc = grp[0].m;
+#pragma unroll
+    for (int g = 0; g < 3; g++) {
+        for (int i = 0; i < 64; i++) {
+            const int64_t r = grp[g].base + i;
+            if (r < 0 || r >= n) continue;
+            const double d2 = knn_d2(knn_bcast(grp[g].x, i), knn_bcast(grp[g].y, i), knn_bcast(grp[g].z, i), qx, qy, qz);
+            const double m = knn_bcast(grp[g].m, i);
+            if (valid && r != rank) {
+                evals++;
+                if (d2 <= r2k) acc = __dadd_rn(acc, m);
+            }
+        }
+    }
+    knn_walk<true>(nodes, rows, node_ref, nn, valid, qx, qy, qz, ex_lo, ex_hi, h, k, bound, acc, evals);
+    if (valid) {
+        const uint32_t j = perm[rank];
+        r2_out[j] = r2k;
+        mass_out[j] = acc;
+    }
+    if (evals_out) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) evals += __shfl_xor(evals, o);
+        if (lane == 0) atomicAdd(evals_out, (unsigned long long)evals);
+    }
+}
+// After the query: the tree header as it stood before the query's build - except that a capacity error of that build
+// stays behind in the sticky words, to be reported by the next call that looks, as a step's is.
+__global__ void k_knn_restore(TreeInfo *info, const TreeInfo *__restrict__ saved) {
+    if (threadIdx.x != 0) return;
+    const int err = info->error | info->sticky_error;
+    const long long nodes = info->sticky_error ? info->sticky_nodes : info->num_nodes;
+    *info = *saved;
+    if (err && info->sticky_error == 0) {
+        info->sticky_error = 1;
+        info->sticky_nodes = nodes;
+    }
+}
+// state rows -> the caller's order (id), any of the three outputs
+__global__ __launch_bounds__(kBlock) void k_knn_out(const double *__restrict__ r2, const double *__restrict__ mass,
+                                                    const int32_t *__restrict__ id, int64_t n, double *__restrict__ out_r2,
+                                                    double *__restrict__ out_mass, double *__restrict__ out_rho) {
+    const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (r >= n) return;
+    const int64_t o = id[r];
+    if (out_r2) out_r2[o] = r2[r];
+    if (out_mass) out_mass[o] = mass[r];
+    if (out_rho) out_rho[o] = knn_density(r2[r], mass[r]);
+}
+
 }  // namespace
 
 // =========================================================================================
@@ -3894,6 +4148,15 @@ struct nbmi_sim {
     long long *diag_partc = nullptr;  // [kDiagBlocksMax + 1] the same for the term counts
     double4 *diag_pot = nullptr;      // [node rows] float64 {cx, cy, cz, G m} of every node of the diagnostic's own build
     TreeInfo *diag_info = nullptr;    // the tree header as the last step left it, put back after the diagnostic's build
+    // k-nearest-neighbour query (nbmi_knn), allocated by the first call; no step touches them.
+    // 16 bytes per body (r2_k and mass_k by state row) and 32 bytes per node row (k_knn_rows)
+    double *knn_r2 = nullptr, *knn_mass = nullptr;
+    double4 *knn_rows = nullptr;
+    TreeInfo *knn_info = nullptr;  // the tree header as it stood before the query's build
+    unsigned long long *knn_evals = nullptr;
+    // what nbmi_compute_colors / nbmi_frame_begin colour by (nbmi_set_color_mode)
+    int color_mode = NBMI_COLOR_SPEED, color_k = 32;
+    double color_lo = 0.0, color_hi = 1.0;
     // integrator (nbmi_set_integrator).  Leapfrog keeps a = F(x) of the current state beside its
     // rows: acc = 3 columns of n doubles, allocated by the first leapfrog step; acc_valid = false until a step primes it
     int integrator = NBMI_INTEGRATOR_KICK_DRIFT;
@@ -4722,9 +4985,22 @@ int nbmi_step(nbmi_sim *s, double dt, int substeps) {
 
 int64_t nbmi_step_count(nbmi_sim *s) { return s ? s->steps_taken : -1; }
 
+namespace {
+int knn_check(nbmi_sim *s, int k, const char *what);
+int knn_enqueue(nbmi_sim *s, int k, bool count);
+}  // namespace
+
 int nbmi_compute_colors(nbmi_sim *s, double max_speed) {
     if (int rc = check_handle(s)) return rc;
     if (s->n == 0) return 0;
+    if (s->color_mode == NBMI_COLOR_DENSITY) {  // (only handles the query accepts get into this mode; nothing waits)
+        if (int rc = knn_check(s, s->color_k, "nbmi_compute_colors")) return rc;
+        if (int rc = knn_enqueue(s, s->color_k, false)) return rc;
+        k_colors_density<<<nblocks(s->n), kBlock, 0, s->stream>>>(s->buf[s->curbuf], s->n, s->knn_r2, s->knn_mass, s->color_lo,
+                                                                  s->color_hi, s->colors);
+        NBMI_HIP_CHECK(hipGetLastError());
+        return 0;
+    }
     k_colors<<<nblocks(s->n), kBlock, 0, s->stream>>>(s->buf[s->curbuf], s->n, max_speed, s->owner, s->colors);
     NBMI_HIP_CHECK(hipGetLastError());
     return 0;
@@ -5012,6 +5288,141 @@ int nbmi_get_potentials_f64(nbmi_sim *s, double *out) {
     NBMI_HIP_CHECK(hipGetLastError());
     NBMI_HIP_CHECK(hipMemcpyAsync(out, s->stage, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
+    return 0;
+}
+
+namespace {
+// nbmi_knn and everything built on it: which handles have the tree the query walks
+const char *knn_refusal(const nbmi_sim *s) {
+    if (s->method != NBMI_METHOD_BARNES_HUT) return "direct N^2 handles have no tree";
+    if (s->owner) return "owner-mode handles are not supported (the neighbours may live on other ranks)";
+    if (s->shard_begin != 0 || s->shard_end != s->n) return "sharded handles are not supported";
+    if (s->prec || s->walk_lane || s->walk_stack || s->acc64_env)
+        return "not available with the measurement-only walks (NBMI_PREC, NBMI_WALK_LANE, NBMI_ACC64, NBMI_WALK_STACK)";
+    return nullptr;
+}
+int knn_check(nbmi_sim *s, int k, const char *what) {
+    if (const char *why = knn_refusal(s)) {
+        nbmi::set_error("%s: %s", what, why);
+        return NBMI_ERR_ARG;
+    }
+    if (k < 1 || k > kKnnMaxK || (int64_t)k > s->n - 1) {
+        nbmi::set_error("%s: k = %d is outside 1 .. min(%d, N - 1) (N = %lld)", what, k, kKnnMaxK, (long long)s->n);
+        return NBMI_ERR_ARG;
+    }
+    return 0;
+}
+// Enqueues the whole query on the compute stream and never waits: the header is saved, the octree of the current
+// positions built as nbmi_diagnostics builds it (step_dt = 0: no "auto" decision, the wave flags and force_all64 stay
+// the last step's; the host-side flags are put back), the rows written, the waves run, the header restored.  r2_k and
+// mass_k are in knn_r2 / knn_mass by state row afterwards.  A capacity error of the build stays in the sticky words
+// (k_knn_restore) for the next call that looks.  `count`: also sum the evaluated distances into knn_evals.
+int knn_enqueue(nbmi_sim *s, int k, bool count) {
+    const int64_t n = s->n;
+    if (!s->knn_r2 && (dev_alloc(s, &s->knn_r2, n) || dev_alloc(s, &s->knn_mass, n) ||
+                       dev_alloc(s, &s->knn_rows, s->node_capacity + 2) || dev_alloc(s, &s->knn_info, 1) ||
+                       dev_alloc(s, &s->knn_evals, 1)))
+        return NBMI_ERR_HIP;
+    hipStream_t st = s->stream;
+    NBMI_HIP_CHECK(hipMemcpyAsync(s->knn_info, s->info, sizeof(TreeInfo), hipMemcpyDeviceToDevice, st));
+    if (count) NBMI_HIP_CHECK(hipMemsetAsync(s->knn_evals, 0, sizeof(unsigned long long), st));
+    const bool tree_valid = s->tree_valid, maxabs_fused = s->maxabs_fused;
+    const int sort_bits = s->sort_bits;
+    const double step_dt = s->step_dt;
+    s->step_dt = 0.0;
+    int rc = enqueue_tree(s, -1, true);
+    if (rc == 0) {
+        k_knn_rows<<<nblocks(s->own_node_rows), kBlock, 0, st>>>(s->nodes, s->nodes64, s->node_ref, s->perm, s->buf[s->curbuf],
+                                                                  s->info, s->own_node_rows, s->knn_rows);
+        k_knn<<<(int)((n + kKnnBlock - 1) / kKnnBlock), kKnnBlock, (size_t)k * kKnnBlock * sizeof(double), st>>>(
+            s->nodes, s->knn_rows, s->node_ref, s->info, s->perm, s->buf[s->curbuf], n, k, s->knn_r2, s->knn_mass,
+            count ? s->knn_evals : nullptr);
+        if (hipGetLastError() != hipSuccess) {
+            nbmi::set_error("k_knn launch failed");
+            rc = NBMI_ERR_HIP;
+        }
+    }
+    k_knn_restore<<<1, 64, 0, st>>>(s->info, s->knn_info);
+    if (hipGetLastError() != hipSuccess && rc == 0) {
+        nbmi::set_error("k_knn_restore launch failed");
+        rc = NBMI_ERR_HIP;
+    }
+    // the same positions give the same tree: what the queries read is still that tree if it was before
+    s->tree_valid = tree_valid && rc == 0;
+    s->maxabs_fused = maxabs_fused;
+    s->sort_bits = sort_bits;
+    s->step_dt = step_dt;
+    return rc;
+}
+// the synchronous form behind nbmi_knn / nbmi_get_densities_f64: errors of earlier steps first, as a getter reports
+// them, then the query and its own
+int knn_query(nbmi_sim *s, int k, bool count) {
+    NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
+    if (int rc = check_device_error(s)) return rc;
+    if (int rc = knn_enqueue(s, k, count)) return rc;
+    NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
+    return check_device_error(s);
+}
+}  // namespace
+
+int nbmi_knn(nbmi_sim *s, int k, double *r2_k, double *mass_k, int64_t *evals) {
+    if (int rc = check_handle(s)) return rc;
+    if (int rc = knn_check(s, k, "nbmi_knn")) return rc;
+    if (int rc = knn_query(s, k, evals != nullptr)) return rc;
+    const int64_t n = s->n;
+    double *o_r2 = (double *)s->stage, *o_mass = o_r2 + n;
+    k_knn_out<<<nblocks(n), kBlock, 0, s->stream>>>(s->knn_r2, s->knn_mass, s->buf[s->curbuf].id, n, r2_k ? o_r2 : nullptr,
+                                                    mass_k ? o_mass : nullptr, nullptr);
+    NBMI_HIP_CHECK(hipGetLastError());
+    if (r2_k) NBMI_HIP_CHECK(hipMemcpyAsync(r2_k, o_r2, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    if (mass_k) NBMI_HIP_CHECK(hipMemcpyAsync(mass_k, o_mass, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    unsigned long long ev = 0;
+    if (evals) NBMI_HIP_CHECK(hipMemcpyAsync(&ev, s->knn_evals, sizeof(ev), hipMemcpyDeviceToHost, s->stream));
+    NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
+    if (evals) *evals = (int64_t)ev;
+    return 0;
+}
+
+int nbmi_get_densities_f64(nbmi_sim *s, int k, double *rho) {
+    if (int rc = check_handle(s)) return rc;
+    if (int rc = knn_check(s, k, "nbmi_get_densities_f64")) return rc;
+    if (!rho) { nbmi::set_error("null output"); return NBMI_ERR_ARG; }
+    if (int rc = knn_query(s, k, false)) return rc;
+    const int64_t n = s->n;
+    k_knn_out<<<nblocks(n), kBlock, 0, s->stream>>>(s->knn_r2, s->knn_mass, s->buf[s->curbuf].id, n, nullptr, nullptr,
+                                                    (double *)s->stage);
+    NBMI_HIP_CHECK(hipGetLastError());
+    NBMI_HIP_CHECK(hipMemcpyAsync(rho, s->stage, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
+    return 0;
+}
+
+int nbmi_set_color_mode(nbmi_sim *s, int mode, int k, double log10_lo, double log10_hi) {
+    if (int rc = check_handle(s)) return rc;
+    if (mode != NBMI_COLOR_SPEED && mode != NBMI_COLOR_DENSITY) {
+        nbmi::set_error("nbmi_set_color_mode: unknown colour mode %d", mode);
+        return NBMI_ERR_ARG;
+    }
+    if (mode == NBMI_COLOR_DENSITY) {  // (speed mode takes no parameters: k and the range keep their values)
+        if (int rc = knn_check(s, k, "nbmi_set_color_mode")) return rc;
+        if (!isfinite(log10_lo) || !isfinite(log10_hi) || !(log10_hi > log10_lo)) {
+            nbmi::set_error("nbmi_set_color_mode: the log10(rho) range [%g, %g] is not finite with hi > lo", log10_lo, log10_hi);
+            return NBMI_ERR_ARG;
+        }
+        s->color_k = k;
+        s->color_lo = log10_lo;
+        s->color_hi = log10_hi;
+    }
+    s->color_mode = mode;
+    return 0;
+}
+
+int nbmi_get_color_mode(nbmi_sim *s, int *mode, int *k, double *log10_lo, double *log10_hi) {
+    if (int rc = check_handle(s)) return rc;
+    if (mode) *mode = s->color_mode;
+    if (k) *k = s->color_k;
+    if (log10_lo) *log10_lo = s->color_lo;
+    if (log10_hi) *log10_hi = s->color_hi;
     return 0;
 }
 
@@ -5741,16 +6152,28 @@ int nbmi_frame_begin(nbmi_sim *s, int kind, double max_speed, int *slot) {
         void *first = f.dev + sizeof(FrameHeader), *second = f.dev + sizeof(FrameHeader) + item;
         const Bodies cur = s->buf[s->curbuf];
         const unsigned *se = s->tmp_sort ? (const unsigned *)nbmi::sort_error_device_word(s->tmp_sort) : nullptr;
+        // density colours: the query goes onto the stream in front of the snapshot (enqueued, not waited for; its
+        // restored header, a capacity error of its build included, is what the snapshot copies)
+        const double *dr2 = nullptr, *dmass = nullptr;
+        const double dlo = s->color_lo, dhi = s->color_hi;
+        if (s->color_mode == NBMI_COLOR_DENSITY) {
+            if (int rc = knn_check(s, s->color_k, "nbmi_frame_begin")) return rc;
+            if (int rc = knn_enqueue(s, s->color_k, false)) return rc;
+            dr2 = s->knn_r2;
+            dmass = s->knn_mass;
+        }
         if (kind == NBMI_FRAME_F32)
             k_frame_snapshot<NBMI_FRAME_F32><<<nblocks(n), kBlock, 0, s->stream>>>(cur, n, max_speed, s->colors, nullptr, first,
-                                                                                    second, s->info, se, hd);
+                                                                                    second, s->info, se, hd, dr2, dmass, dlo, dhi);
         else if (kind == NBMI_FRAME_KEY)
             k_frame_snapshot<NBMI_FRAME_KEY><<<nblocks(n), kBlock, 0, s->stream>>>(cur, n, max_speed, s->colors, s->frame_prev,
-                                                                                    first, second, s->info, se, hd);
+                                                                                    first, second, s->info, se, hd, dr2, dmass, dlo,
+                                                                                    dhi);
         else {
             float *rows = (float *)s->stage;  // (like frame_current) nothing later on the stream reads it before writing it
             k_frame_snapshot<NBMI_FRAME_DELTA_I16><<<nblocks(n), kBlock, 0, s->stream>>>(cur, n, max_speed, s->colors, nullptr,
-                                                                                          rows, nullptr, s->info, se, hd);
+                                                                                          rows, nullptr, s->info, se, hd, dr2, dmass,
+                                                                                          dlo, dhi);
             k_frame_delta<<<nblocks(3 * n), kBlock, 0, s->stream>>>(rows, s->frame_prev, 3 * n, (int16_t *)first);
             k_frame_delta<<<nblocks(3 * n), kBlock, 0, s->stream>>>(s->colors, s->frame_prev + 3 * n, 3 * n, (int16_t *)second);
         }

@@ -50,6 +50,10 @@ PROTOTYPES = {
     "nbmi_walk_counters": (C.c_int, [_vp, _vp]),
     "nbmi_diagnostics": (C.c_int, [_vp, C.c_int, _vp, _vp]),
     "nbmi_get_potentials_f64": (C.c_int, [_vp, _vp]),
+    "nbmi_knn": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
+    "nbmi_get_densities_f64": (C.c_int, [_vp, C.c_int, _vp]),
+    "nbmi_set_color_mode": (C.c_int, [_vp, C.c_int, C.c_int, _dbl, _dbl]),
+    "nbmi_get_color_mode": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "nbmi_set_shard": (C.c_int, [_vp, _i64, _i64]),
     "nbmi_export_shard": (C.c_int, [_vp, _vp]),
     "nbmi_import_ranks": (C.c_int, [_vp, _vp, _i64, _i64]),

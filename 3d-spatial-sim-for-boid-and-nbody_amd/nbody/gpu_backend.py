@@ -31,6 +31,9 @@ GENERATED_DISTRIBUTIONS = {"galaxy": 0, "collision": 1, "cluster": 2, "spiral": 
 INTEGRATORS = {"kick_drift": 0, "leapfrog": 1}
 # multipole orders of nbmi_set_multipole (NBMI_MULTIPOLE_* of include/nbmi.h)
 MULTIPOLES = {"monopole": 0, "quadrupole": 1}
+# colour modes of nbmi_set_color_mode (NBMI_COLOR_* of include/nbmi.h)
+COLOR_MODES = {"speed": 0, "density": 1}
+KNN_MAX_K = 64
 
 
 def _multipole_code(name):
@@ -289,6 +292,66 @@ class _HIPSimulation:
         out = np.empty(self.n, dtype=np.float64)
         _nat.check(self._lib.nbmi_get_potentials_f64(self._h, _nat.ptr(out)), "nbmi_get_potentials_f64")
         return out
+
+    # ---- k-nearest neighbours, densities, density colours (include/nbmi.h nbmi_knn) ----
+    _knn_refusal = None  # classes whose handles the library refuses say so here, and refuse before calling it
+
+    def _knn_call(self, what, rc):
+        if rc == -1:  # NBMI_ERR_ARG: refused for this handle, or a bad k / range
+            raise ValueError(f"{what}: {_nat.last_error()}")
+        _nat.check(rc, what)
+
+    def _knn_refuse(self, what):
+        if self._knn_refusal:
+            raise ValueError(f"{what}: {self._knn_refusal}")
+
+    def knn(self, k: int, evals=False):
+        """(r2_k, mass_k), (N,) float64 each in the caller's body order: the squared distance to the k-th nearest other
+        body - exact, equal to a brute force bit for bit - and the mass within it, own mass and ties included.
+        ``evals=True`` also returns the number of distances the call evaluated.  1 <= k <= min(64, N - 1).  Barnes-Hut
+        handles only; the call does not change what the next step computes."""
+        self._knn_refuse(f"knn({k})")
+        r2 = np.empty(self.n, dtype=np.float64)
+        mk = np.empty(self.n, dtype=np.float64)
+        ev = C.c_int64(0)
+        self._knn_call(f"knn({k})", self._lib.nbmi_knn(self._h, int(k), _nat.ptr(r2), _nat.ptr(mk),
+                                                      C.addressof(ev) if evals else None))
+        return (r2, mk, int(ev.value)) if evals else (r2, mk)
+
+    def densities(self, k: int = 32) -> np.ndarray:
+        """rho (N,) float64: mass_k over the volume of the k-th neighbour sphere; +inf where that radius is 0."""
+        self._knn_refuse(f"densities({k})")
+        out = np.empty(self.n, dtype=np.float64)
+        self._knn_call(f"densities({k})", self._lib.nbmi_get_densities_f64(self._h, int(k), _nat.ptr(out)))
+        return out
+
+    def set_color_mode(self, mode: str, k: int = 32, log10_range=(0.0, 1.0)):
+        """What compute_colors / frame_begin colour by: "speed" (default; the reference's ramp over speed / max_speed) or
+        "density" (the same ramp over where log10 of the k-NN density lies in ``log10_range``; max_speed is then
+        ignored).  Density mode is refused with ValueError where knn() is, and for a bad k or range."""
+        if mode not in COLOR_MODES:
+            raise ValueError(f"color mode must be one of {sorted(COLOR_MODES)}, not {mode!r}")
+        lo, hi = (float(x) for x in log10_range)
+        if mode == "density":
+            self._knn_refuse("set_color_mode('density')")
+        self._knn_call(f"set_color_mode({mode!r})", self._lib.nbmi_set_color_mode(self._h, COLOR_MODES[mode], int(k), lo, hi))
+
+    def _color_mode(self):
+        mode, k = C.c_int(0), C.c_int(0)
+        lo, hi = C.c_double(0.0), C.c_double(0.0)
+        _nat.check(self._lib.nbmi_get_color_mode(self._h, C.addressof(mode), C.addressof(k), C.addressof(lo), C.addressof(hi)),
+                   "nbmi_get_color_mode")
+        return {v: n for n, v in COLOR_MODES.items()}[mode.value], k.value, (lo.value, hi.value)
+
+    @property
+    def color_mode(self) -> str:
+        return self._color_mode()[0]
+
+    @property
+    def color_settings(self):
+        """{"mode", "k", "log10_range"} as the library holds them (k and the range are the last density mode's)."""
+        mode, k, rng = self._color_mode()
+        return {"mode": mode, "k": k, "log10_range": [rng[0], rng[1]]}
 
     def visible_points(self, cam_pos, cam_forward, cam_right, cam_up, tan_h, tan_v, far_dist):
         """Frustum culling + compaction on the device (reference compute_visibility_points,
@@ -551,6 +614,8 @@ class HIPOwnerSimulation(HIPBarnesHutSimulation):
     def n(self):
         return int(self._lib.nbmi_owner_count(self._h)) if self._h else 0
 
+    _knn_refusal = "owner-mode handles are not supported (the neighbours may live on other ranks)"
+
     def set_multipole(self, multipole: str):
         if _multipole_code(multipole) != MULTIPOLES["monopole"]:
             raise ValueError("owner-mode handles support only monopole terms (the exchanged tree rows carry no second "
@@ -626,6 +691,7 @@ class HIPDirectSimulation(_HIPSimulation):
     no theta)."""
 
     _method = METHOD_DIRECT
+    _knn_refusal = "direct N^2 handles have no tree"
 
     def __init__(self, positions, velocities, masses, G, softening, damping, device=None, integrator="kick_drift",
                  multipole="monopole"):

@@ -62,6 +62,13 @@ def _refuse_quadrupole(multipole):
         raise ValueError(f"sharded N-body runs support only monopole cell terms, not {multipole!r}")
 
 
+def _refuse_density_colors(color):
+    """The k nearest neighbours of a body may live on other ranks: sharded and owner-mode runs colour by speed only."""
+    if color != "speed":
+        raise ValueError(f"sharded N-body runs support only speed colours, not {color!r} (the k-nearest-neighbour query "
+                         "needs the whole system in one handle)")
+
+
 class HipShardEngine:
     """Shard engine on top of HIPBarnesHutSimulation; rows travel as torch CUDA tensors."""
 
@@ -159,15 +166,16 @@ class ShardedBarnesHut:
 
 
 def create_sharded_simulation(positions, velocities, masses, G, softening, damping, theta=0.5, mode="rows",
-                              method="barnes_hut", integrator="kick_drift", multipole="monopole"):
+                              method="barnes_hut", integrator="kick_drift", multipole="monopole", color="speed"):
     """Build the multi-GPU stepper from the torch.distributed environment (RANK/LOCAL_RANK/
     WORLD_SIZE).  Every rank passes the same full arrays.  mode: "rows" (stage 1, replicated state and
     tree, bit-exact) or "let" (stage 2, owned key ranges + locally essential trees); method "direct"
     shards the all-pairs kernel by body index through the row exchange.  Only the kick_drift integrator:
     "leapfrog" raises ValueError (the exchanged rows carry no acceleration columns), and so does multipole
-    "quadrupole" (they carry no second moments either)."""
+    "quadrupole" (they carry no second moments either) and color "density" (a body's neighbours may be on other ranks)."""
     _refuse_leapfrog(integrator)
     _refuse_quadrupole(multipole)
+    _refuse_density_colors(color)
     import os
     import torch
     import torch.distributed as dist

@@ -333,6 +333,55 @@ def diagnostics_drift(rows):
     return de, dp, dl
 
 
+# ---- density colours (extra config key "color") -------------------------------------------
+DENSITY_K = 32
+
+
+def default_density_range(rho):
+    """log10 range of the density ramp taken from a state's k-NN densities: from the 1st percentile of the finite
+    log10 rho to its 99.9th percentile plus 1.0 - a decade of headroom, because collapsing systems get denser."""
+    rho = np.asarray(rho, dtype=np.float64)
+    lg = np.log10(rho[np.isfinite(rho) & (rho > 0.0)])
+    if len(lg) == 0:
+        raise ValueError("--color density: the state has no finite density to take a range from (give --density-range)")
+    return float(np.percentile(lg, 1.0)), float(np.percentile(lg, 99.9)) + 1.0
+
+
+def color_config(config: dict):
+    """The "color" key of a config as (mode, k, range or None); ValueError for a malformed one.  Absent = speed."""
+    c = config.get("color")
+    if not c:
+        return "speed", DENSITY_K, None
+    mode = c.get("mode", "speed")
+    if mode not in ("speed", "density"):
+        raise ValueError(f"color mode must be speed or density, not {mode!r}")
+    rng = c.get("log10_range")
+    if rng is not None:
+        rng = (float(rng[0]), float(rng[1]))
+        if not (np.isfinite(rng[0]) and np.isfinite(rng[1]) and rng[1] > rng[0]):
+            raise ValueError(f"--density-range: need finite LO < HI, not {rng[0]} {rng[1]}")
+    return mode, int(c.get("k", DENSITY_K)), rng
+
+
+def apply_color_mode(gpu_sim, config: dict, rec_dir: Path = None):
+    """Put the handle into the config's colour mode.  A density session without a range takes it once, here, from the
+    handle's current state (the initial one for a new recording) on the host, and writes it into metadata.json, from
+    where --resume and --extend re-apply it.  Returns the config (with the range filled in)."""
+    mode, k, rng = color_config(config)
+    if mode != "density":
+        return config
+    if rng is None:
+        rng = default_density_range(gpu_sim.densities(k))
+        config = dict(config, color={"mode": "density", "k": k, "log10_range": [rng[0], rng[1]]})
+        if rec_dir is not None:
+            meta_path = Path(rec_dir) / "metadata.json"
+            meta = load_metadata(rec_dir) if meta_path.exists() else dict(config)
+            meta["color"] = config["color"]
+            _atomically(meta_path, lambda f: f.write(json.dumps(meta, indent=2).encode()))
+    gpu_sim.set_color_mode("density", k=k, log10_range=rng)
+    return config
+
+
 def _generate_initial_conditions(config: dict):
     from tools.presets import generate_distribution
     p, v, m = generate_distribution(config.get("distribution", "galaxy"), config["num_bodies"],
@@ -480,6 +529,13 @@ def record(config: dict, resume: bool = False, root: Path = None, quiet: bool = 
     if device_ic:  # the state checkpoints carry the generated masses (0.1 for "filament"), not the unit default
         masses = gpu_sim.get_masses()
     say(f"[Record] GPU acceleration: {backend.value} - {info}")
+    # extra config key "color": {"mode": "density", "k": K, "log10_range": [lo, hi]} = frames coloured by the k-NN
+    # density through the unchanged colour and frame calls of both loops
+    try:
+        config = apply_color_mode(gpu_sim, config, rec_dir)
+    except Exception:
+        gpu_sim.close()
+        raise
     direct_zstd = bool(config.get("zstd"))  # extra config key: write .zstd frames, delta payload quantised on the device
     if direct_zstd and start_frame > 0:
         # the delta chain continues from what a reader reconstructs for the last frame on disk
@@ -619,6 +675,13 @@ def show_status(session_name: str, root: Path = None) -> bool:
     print(f"  Integrator: {meta.get('integrator', 'kick_drift')}")
     print(f"  Multipole: {meta.get('multipole', 'monopole')}")
     print(f"  Pipeline: {'on' if meta.get('pipeline') else 'off'}")
+    color = meta.get("color") or {}
+    if color.get("mode") == "density":
+        rng = color.get("log10_range")
+        print(f"  Color: density (k = {color.get('k', DENSITY_K)}, log10 rho range "
+              + (f"{rng[0]:.3f} .. {rng[1]:.3f})" if rng else "not taken yet)"))
+    else:
+        print("  Color: speed")
     print(f"  Progress: {completed}/{total} frames ({completed / total * 100:.1f}%)")
     print(f"  Started: {meta.get('start_datetime', 'unknown')}")
     rows = read_diagnostics(rec_dir / DIAGNOSTICS_FILE)
@@ -665,7 +728,8 @@ def build_parser():
         epilog="Differences from the reference's recorder: there is no interactive menu (give --preset or "
                "--preset-id); --preset-id indexes this build's preset list (python -m tools.record --presets shows "
                "it); --dt sets dt_per_frame (the reference writes an unused 'dt' key); --presets, --seed, "
-               "--device-ic, --diagnostics, --integrator, --multipole, --pipeline and --root are additions.")
+               "--device-ic, --diagnostics, --integrator, --multipole, --pipeline, --color, --density-k, --density-range and "
+               "--root are additions.")
     ap.add_argument("session", nargs="?", help="session name (for --resume, --status or --extend)")
     ap.add_argument("--resume", action="store_true", help="resume an interrupted recording (default: the most recent)")
     ap.add_argument("--extend", type=int, metavar="FRAMES", help="extend an existing recording by N frames")
@@ -694,6 +758,14 @@ def build_parser():
     ap.add_argument("--pipeline", action="store_true",
                     help="write frame k - 1 while the device computes frame k (asynchronous frame fetch; the same files; "
                          "stored in metadata.json as pipeline)")
+    ap.add_argument("--color", choices=("speed", "density"), default=None,
+                    help="speed (default, the reference's ramp over |v| / 15) or density (the same ramp over log10 of the "
+                         "k-nearest-neighbour density; stored in metadata.json as color)")
+    ap.add_argument("--density-k", type=int, default=None, metavar="K",
+                    help=f"neighbours of the density estimate, 1 .. 64 (default {DENSITY_K})")
+    ap.add_argument("--density-range", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                    help="log10(rho) at the ends of the ramp (default: taken once from the initial state: its 1st "
+                         "percentile .. its 99.9th percentile + 1)")
     ap.add_argument("--root", type=Path, default=None, help="directory holding recordings/ (default: the package's)")
     return ap
 
@@ -743,6 +815,18 @@ def build_config(args) -> dict:
         config["multipole"] = args.multipole
     if getattr(args, "pipeline", False):  # the default writes no key
         config["pipeline"] = True
+    color = getattr(args, "color", None)
+    dk, dr = getattr(args, "density_k", None), getattr(args, "density_range", None)
+    if color != "density" and (dk is not None or dr is not None):
+        raise ValueError("--density-k and --density-range need --color density")
+    if color == "density":  # the default writes no key
+        k = DENSITY_K if dk is None else int(dk)
+        if not 1 <= k <= 64 or k > config["num_bodies"] - 1:
+            raise ValueError(f"--density-k: K must be in 1 .. min(64, bodies - 1), not {k}")
+        config["color"] = {"mode": "density", "k": k}
+        if dr is not None:
+            config["color"]["log10_range"] = [float(dr[0]), float(dr[1])]
+        color_config(config)  # (a bad range raises here)
     return config
 
 

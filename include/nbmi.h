@@ -243,6 +243,42 @@ int nbmi_diagnostics(nbmi_sim *sim, int with_potential, double *out12, int64_t *
 /* phi (N,) float64 in the caller's body order, as defined above. */
 int nbmi_get_potentials_f64(nbmi_sim *sim, double *out);
 
+/* ---- k-nearest-neighbour distances and densities -------------------------------------------
+ * Of the handle's current float64 state, for every body i, exactly:
+ *   d2(i, j)  = (dx dx + dy dy) + dz dz with dx = x_j - x_i, float64 in this association, no FMA.
+ *   r2_k[i]   = the k-th smallest of the multiset {d2(i, j) : j != i}, counted with multiplicity.  Self is excluded by
+ *               identity (equivalently: one zero entry is dropped); a coincident other body counts with d2 = 0.  The
+ *               value does not depend on how ties are ordered and equals a brute force's bit for bit.
+ *   mass_k[i] = m_i + sum of m_j over j != i with d2(i, j) <= r2_k[i].  Under ties this covers more than k bodies, which
+ *               is what makes it independent of their order.  A sum of masses (not of G m): the query reads the masses,
+ *               so handles with G == 0 work.  Summed in the order of the walk (fixed for a given state).
+ *   rho[i]    = mass_k / (4.1887902047863905 (r2_k sqrt(r2_k))), the mean density inside the k-th neighbour sphere;
+ *               +inf where r2_k == 0.
+ * 1 <= k <= 64 and k <= N - 1, else NBMI_ERR_ARG with a message naming k and N.  Outputs are (N,) float64 in the caller's
+ * body order; r2_k, mass_k and evals may each be NULL.  *evals = the number of (body, leaf) distances the call evaluated
+ * (seeding, the search and the mass sum together): a measurement hook like nbmi_walk_counters, to judge the pruning.
+ * Two calls on an unchanged state return the same bits.  A quadrupole or leapfrog handle returns a monopole kick-drift
+ * handle's bits: the tree is the same.
+ * A call changes nothing that a later step reads (state and its order, the tree header - saved and restored -, the
+ * "auto" precision flags and force_all64 - the build runs without a dt -, the step count, the stored leapfrog
+ * acceleration).  The first call allocates 16 bytes per body and 32 bytes per node row.  NBMI_ERR_CAPACITY from the
+ * call's own tree build is reported with a step's message.
+ * Refused with NBMI_ERR_ARG, message "<call>: ...": direct N^2 handles (there is no tree), owner-mode handles, handles
+ * with a proper shard, and the measurement-only walks (NBMI_PREC, NBMI_WALK_LANE, NBMI_ACC64, NBMI_WALK_STACK). */
+int nbmi_knn(nbmi_sim *sim, int k, double *r2_k, double *mass_k, int64_t *evals);
+int nbmi_get_densities_f64(nbmi_sim *sim, int k, double *rho);
+/* What nbmi_compute_colors and nbmi_frame_begin colour by.  NBMI_COLOR_SPEED (the default): the reference's ramp at
+ * t = min(speed / max_speed, 1); k and the range are ignored and keep their values, and every handle accepts it.
+ * NBMI_COLOR_DENSITY: max_speed is ignored; the call runs the k-NN query above on the handle's stream (enqueued, not
+ * waited for; NBMI_ERR_CAPACITY of its build is reported deferred, as a step's is) and colours body i by the same ramp
+ * at t = clamp((log10(rho_i) - log10_lo) / (log10_hi - log10_lo), 0, 1); rho = +inf gives t = 1.  nbmi_frame_begin
+ * produces exactly nbmi_compute_colors' colours and leaves them where that call leaves them.  Density mode needs
+ * log10_hi > log10_lo, both finite, a valid k, and a handle nbmi_knn accepts (else NBMI_ERR_ARG, mode unchanged). */
+#define NBMI_COLOR_SPEED 0
+#define NBMI_COLOR_DENSITY 1
+int nbmi_set_color_mode(nbmi_sim *sim, int mode, int k, double log10_lo, double log10_hi);
+int nbmi_get_color_mode(nbmi_sim *sim, int *mode, int *k, double *log10_lo, double *log10_hi); /* outputs may be NULL */
+
 /* Multi-GPU (one process per GPU).  A handle created with nbmi_create holds ALL bodies; with a
  * shard set, step() integrates only the key-sorted ranks [begin,end) (direct method: the body
  * indices [begin,end), its state is never re-ordered) and leaves the others untouched until
