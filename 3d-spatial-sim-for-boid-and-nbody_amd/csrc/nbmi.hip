@@ -31,6 +31,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -976,7 +977,33 @@ __device__ __forceinline__ bool exact_take_idx(unsigned idx, const Body64 &b) {
     const double dist = sqrt(dist_sq);
     return (c.hs * 2.0) / dist < t->theta;
 }
-__device__ __forceinline__ bool exact_take(unsigned off, const Body64 &b) { return exact_take_idx(off / kNodeBytes, b); }
+
+// THE opening decision: every walk, of whatever arithmetic and stride, asks it here, so the force, quadrupole and
+// potential walks accept the same (body, node) sets and a visit decides alike in the hand-scheduled loops' C++ twins.
+// `d2` is the fp32 dist_sq (the float64 walks pass their (float)d2), `s2t` the record's threshold (0: a leaf, always
+// taken).  Non-negative floats compare as integers; hi / lo are the edges of the uncertainty band, `band2` ulps wide.
+// A lane inside the band (or one the caller names in `also`: k_potential_tree's near pairs) that takes part in the
+// visit is re-decided in float64 - rare, divergent.  geom: the lane takes node `idx` if it takes part.
+struct Opening {
+    bool geom, band;
+};
+__device__ __forceinline__ Opening opening(float d2, float s2t, unsigned band2, bool active, unsigned idx, const Body64 &b64,
+                                           bool also = false) {
+    const int d2b = __float_as_int(d2), hi = __float_as_int(s2t), lo = hi - (int)band2;
+    bool geom = hi < d2b;
+    const bool band = active && ((!geom && lo < d2b) || also);
+    if (band) geom = (hi == 0) || exact_take_idx(idx, b64);
+    return Opening{geom, band};
+}
+// What follows the decision in the lock-step walks: a lane that takes the node skips its subtree (resume), and the
+// wave's cursor steps into the subtree if any lane opens it, past it otherwise.  kStride: kNodeBytes / kNodeDBytes.
+template <unsigned kStride>
+__device__ __forceinline__ unsigned advance(bool active, bool geom, unsigned off, unsigned next_off, unsigned &resume, bool &take) {
+    take = active && geom;
+    resume = take ? next_off : resume;
+    const unsigned long long any_open = __builtin_amdgcn_ballot_w64(active && !geom);
+    return any_open ? off + kStride : next_off;
+}
 
 // One node visit (C++ form: counted / eps == 0 kernels, seek(), and the product walk's re-decision visits).
 // `off` is the cursor as a byte offset into the node array; `resume` likewise.  Returns the next cursor.
@@ -990,14 +1017,9 @@ __device__ __forceinline__ unsigned visit(const Node *__restrict__ nodes, unsign
     const float dx = nd.cx - px, dy = nd.cy - py, dz = nd.cz - pz;
     const float dist_sq = fmaf(dz, dz, fmaf(dy, dy, fmaf(dx, dx, P.eps2)));
     const bool active = resume <= off;
-    // non-negative floats: compare bit patterns as integers.  hi / lo = edges of the uncertainty band.
-    const int d2b = __float_as_int(dist_sq), hi = __float_as_int(nd.s2t), lo = hi - (int)band2;
-    bool geom = hi < d2b;
-    const bool band = active && !geom && lo < d2b;
-    if (band) geom = (hi == 0) || exact_take(off, b64);  // rare, divergent
-    const unsigned long long m_active = __builtin_amdgcn_ballot_w64(active);
-    const unsigned long long m_geom = __builtin_amdgcn_ballot_w64(geom);
-    const bool take = active && geom;
+    const Opening o = opening(dist_sq, nd.s2t, band2, active, off / kNodeBytes, b64);
+    bool take;
+    const unsigned next = advance<kNodeBytes>(active, o.geom, off, nd.next_off, resume, take);
     bool force = take;
     if (kGuard) force = take && (dist_sq > P.eps2);
     // same association as the hand-scheduled loop, (G m / d) (1 / d^2): a body's sums must not depend on
@@ -1007,13 +1029,11 @@ __device__ __forceinline__ unsigned visit(const Node *__restrict__ nodes, unsign
     ax = fmaf(dx, f, ax);
     ay = fmaf(dy, f, ay);
     az = fmaf(dz, f, az);
-    resume = take ? nd.next_off : resume;
-    const unsigned long long any_open = m_active & ~m_geom;
     active_out = active;
     force_out = take && (dist_sq > P.eps2);
-    band_out = band;
-    jumped = !any_open && nd.next_off != off + kNodeBytes;
-    return any_open ? off + kNodeBytes : nd.next_off;
+    band_out = o.band;
+    jumped = next != off + kNodeBytes;
+    return next;
 }
 
 // Hand-scheduled walk loop for the product kernel (eps > 0, no counters): 16 VALU + 3 SALU + 2 SMEM
@@ -1355,8 +1375,20 @@ __device__ __forceinline__ void walk1_asm64(const NodeD *nodesd, unsigned &off, 
                    "s66", "vcc", "scc", "memory");
 }
 
+// The float64 monopole factor G m / d^3 as NBMI_V64_X computes it: v_rsq_f32 of the rounded d^2 as the seed, one
+// Newton step in float64.  A body's sums do not depend on which of its visits came through the C++ visits below.
+__device__ __forceinline__ double monopole64(double gm, double d2, float d2f) {
+    const double y0 = (double)__builtin_amdgcn_rsqf(d2f);
+    const double t = y0 * y0;
+    double w = gm * y0;
+    const double e = __builtin_fma(-d2, t, 1.0);
+    w = w * t;
+    const double h = e * 1.5;
+    return __builtin_fma(w, h, w);
+}
+
 // one float64 visit in C++ with the float64 re-decision of the lanes inside the band (the asm loop stopped on this
-// node).  Operation for operation the asm visit: a body's sums do not depend on which of its visits came through here.
+// node)
 __device__ __forceinline__ unsigned tie_visit64(const NodeD *nodesd, unsigned off, double qx, double qy, double qz,
                                                 double eps2, unsigned band2, const Body64 &b64, unsigned &resume,
                                                 double &sx, double &sy, double &sz) {
@@ -1368,34 +1400,24 @@ __device__ __forceinline__ unsigned tie_visit64(const NodeD *nodesd, unsigned of
         // force arithmetic below needs to be alive across it (the pointer is laundered so that it is recomputed)
         const double dx = np->cx - qx, dy = np->cy - qy, dz = np->cz - qz;
         const float d2f = (float)__builtin_fma(dz, dz, __builtin_fma(dy, dy, __builtin_fma(dx, dx, eps2)));
-        const int d2b = __float_as_int(d2f), hi = __float_as_int(np->s2t), lo = hi - (int)band2;
-        geom = hi < d2b;
-        if (active && !geom && lo < d2b) geom = (hi == 0) || exact_take_idx(off / kNodeDBytes, b64);
+        geom = opening(d2f, np->s2t, band2, active, off / kNodeDBytes, b64).geom;
     }
     asm volatile("" : "+s"(np));
     const NodeD nd = *np;
     const double dx = nd.cx - qx, dy = nd.cy - qy, dz = nd.cz - qz;
     const double d2 = __builtin_fma(dz, dz, __builtin_fma(dy, dy, __builtin_fma(dx, dx, eps2)));
-    const float d2f = (float)d2;
-    const bool take = active && geom;
-    const double y0 = (double)__builtin_amdgcn_rsqf(d2f);
-    const double t = y0 * y0;
-    double w = nd.gm * y0;
-    const double e = __builtin_fma(-d2, t, 1.0);
-    w = w * t;
-    const double h = e * 1.5;
-    w = __builtin_fma(w, h, w);
+    const double w = monopole64(nd.gm, d2, (float)d2);
+    bool take;
+    const unsigned next = advance<kNodeDBytes>(active, geom, off, nd.next_off, resume, take);
     if (take) {
         sx = __builtin_fma(dx, w, sx); sy = __builtin_fma(dy, w, sy); sz = __builtin_fma(dz, w, sz);
-        resume = nd.next_off;
     }
-    const unsigned long long any_open = __builtin_amdgcn_ballot_w64(active && !geom);
-    return __builtin_amdgcn_readfirstlane(any_open ? off + kNodeDBytes : nd.next_off);
+    return __builtin_amdgcn_readfirstlane(next);
 }
 
 // The float64 visit of the guarded walk (k_walk<*, *, true>: eps == 0, or an eps so small that the fp32 self-term
-// overflows).  tie_visit64's decision and force arithmetic, plus the reference's dist_sq > eps^2 rule on the float64 d^2
-// (simulation.py:260) as k_potential_tree applies it: the own leaf has d = 0 exactly, and so has a coincident body.
+// overflows): tie_visit64 plus the reference's dist_sq > eps^2 rule on the float64 d^2 (simulation.py:260) as
+// k_potential_tree applies it: the own leaf has d = 0 exactly, and so has a coincident body.
 __device__ __forceinline__ unsigned guard_visit64(const NodeD *nodesd, unsigned off, double qx, double qy, double qz,
                                                   double eps2, const Body64 &b64, unsigned &resume, double &sx,
                                                   double &sy, double &sz) {
@@ -1405,23 +1427,14 @@ __device__ __forceinline__ unsigned guard_visit64(const NodeD *nodesd, unsigned 
     const double d2 = __builtin_fma(dz, dz, __builtin_fma(dy, dy, __builtin_fma(dx, dx, eps2)));
     const float d2f = (float)d2;
     const bool active = resume <= off;
-    const int d2b = __float_as_int(d2f), hi = __float_as_int(nd.s2t), lo = hi - 2 * (int)kBand64;
-    bool geom = hi < d2b;
-    if (active && !geom && lo < d2b) geom = (hi == 0) || exact_take_idx(off / kNodeDBytes, b64);
-    const bool take = active && geom;
+    const bool geom = opening(d2f, nd.s2t, 2u * kBand64, active, off / kNodeDBytes, b64).geom;
+    bool take;
+    const unsigned next = advance<kNodeDBytes>(active, geom, off, nd.next_off, resume, take);
     if (take && d2 > eps2) {
-        const double y0 = (double)__builtin_amdgcn_rsqf(d2f);
-        const double t = y0 * y0;
-        double w = nd.gm * y0;
-        const double e = __builtin_fma(-d2, t, 1.0);
-        w = w * t;
-        const double h = e * 1.5;
-        w = __builtin_fma(w, h, w);
+        const double w = monopole64(nd.gm, d2, d2f);
         sx = __builtin_fma(dx, w, sx); sy = __builtin_fma(dy, w, sy); sz = __builtin_fma(dz, w, sz);
     }
-    if (take) resume = nd.next_off;
-    const unsigned long long any_open = __builtin_amdgcn_ballot_w64(active && !geom);
-    return __builtin_amdgcn_readfirstlane(any_open ? off + kNodeDBytes : nd.next_off);
+    return __builtin_amdgcn_readfirstlane(next);
 }
 
 // a wave-uniform 64-bit value the compiler no longer knows to be uniform (loaded behind something it treats as a
@@ -1430,13 +1443,88 @@ __device__ __forceinline__ unsigned long long uniform_u64(unsigned long long v) 
     const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
     return ((unsigned long long)hi << 32) | lo;
 }
-// everything a lane carries through a walk
+// Everything a lane carries through a walk.  lane_prologue() fills it for every walk kernel alike: which body the lane
+// has, what a lane without one looks like (resume = ~0: it never takes part, so every launched wave is full), and what a
+// pending capacity error does (frozen: nothing is walked, the epilogues leave the state as it is).
 struct WalkCtx {
     const Node *nodes;
+    bool valid, frozen;
+    uint32_t j;  // the body's row of the current state
     float px, py, pz;
     Body64 b64;
+    unsigned resume;  // the cursor value from which the lane takes part: 0 at the start
     unsigned band2;
+    unsigned rows;  // the walk ends behind this many node records
 };
+// a pending capacity error ends every walk before its first visit
+__device__ __forceinline__ unsigned walk_rows(const TreeInfo *info_in, bool frozen) {
+    return frozen ? 0u : (unsigned)info_in->walk_nodes;
+}
+__device__ __forceinline__ WalkCtx lane_prologue(const Node *nodes, const float4 *__restrict__ posm_s,
+                                                 const uint32_t *__restrict__ perm, int64_t rank, int64_t rank_end,
+                                                 const TreeInfo *info_in, const WalkTable *tab, int curbuf) {
+    WalkCtx C;
+    C.nodes = nodes;
+    C.valid = rank < rank_end;
+    C.frozen = info_in->error != 0 || info_in->sticky_error != 0;
+    C.rows = walk_rows(info_in, C.frozen);
+    C.band2 = __builtin_amdgcn_readfirstlane(info_in->band2);
+    C.px = C.py = C.pz = 0.f;
+    C.j = 0;
+    if (C.valid) {
+        const float4 p = posm_s[rank];
+        C.px = p.x; C.py = p.y; C.pz = p.z;
+        C.j = perm[rank];
+    }
+    C.b64 = Body64{tab, curbuf, C.j};
+    C.resume = C.valid ? 0u : 0xffffffffu;
+    return C;
+}
+// what the float64 walks need besides: the body's float64 position and the wave-uniform eps^2
+struct Lane64 {
+    double qx, qy, qz, eps2;
+};
+__device__ __forceinline__ Lane64 lane_f64(const WalkCtx &C) {
+    const WalkTable *tab = C.b64.tab;
+    Lane64 L{0.0, 0.0, 0.0, 0.0};
+    if (C.valid) {
+        const Bodies &cur = tab->buf[C.b64.curbuf];
+        L.qx = cur.x[C.j]; L.qy = cur.y[C.j]; L.qz = cur.z[C.j];
+    }
+    L.eps2 = __longlong_as_double((long long)uniform_u64((unsigned long long)__double_as_longlong(tab->eps2)));
+    return L;
+}
+
+// [r3] Force precision of a wave (see NBMI_V64_X); rank = any rank of the wave, its first lane's counts.  force_prec 0: float64 where the
+// bodies' own neighbourhood is dense enough that an error, once made, is amplified within a few hundred steps (decided
+// wave by wave in k_gather_scan, which has the sorted bodies in registers anyway), or where most of the system is
+// (k_scan_subtiles).  All lanes of a wave agree; which 64 ranks form a wave does not depend on the sharding.
+// per_wave = false (a force pass without a step, whose dt the per-wave decision needs): float64 only if every wave takes it.
+__device__ __forceinline__ bool wave_uses_f64(const WalkTable *tab, const TreeInfo *info, const WalkParams &P, int64_t rank,
+                                              bool per_wave = true) {
+    bool use64 = false;
+    if (tab->nodesd && P.force_prec != 1) {
+        if (P.force_prec == 2) return true;
+        if (per_wave) use64 = tab->wave_flag[rank >> 6] != 0 || info->force_all64 != 0;
+        use64 = __builtin_amdgcn_readfirstlane((int)use64) != 0;
+    }
+    return use64;
+}
+
+// Two-level sums: the fp32 accumulators of a C++ loop are emptied into the float64 ones every 12 visits, as NBMI_FLUSH
+// does every 3 trips of 4 visits.
+__device__ __forceinline__ void flush12(int &since_flush, float &ax, float &ay, float &az, double &sx, double &sy, double &sz) {
+    if (++since_flush != 12) return;
+    sx += (double)ax; sy += (double)ay; sz += (double)az;
+    ax = ay = az = 0.f;
+    since_flush = 0;
+}
+
+// epilogue of the walks that do not integrate: the acceleration in the caller's body order
+__device__ __forceinline__ void store_acc(double *__restrict__ acc_out, const Bodies &cur, uint32_t j, double x, double y, double z) {
+    const int64_t o = 3 * (int64_t)cur.id[j];
+    acc_out[o] = x; acc_out[o + 1] = y; acc_out[o + 2] = z;
+}
 
 // one visit with the float64 re-decision (the asm loop stopped on this node)
 __device__ __forceinline__ unsigned tie_visit(const WalkCtx &C, const WalkParams &P, unsigned off, unsigned &resume,
@@ -1474,16 +1562,15 @@ __device__ __forceinline__ unsigned seek(const WalkCtx &C, const WalkParams &P, 
         const float dx = nd.cx - C.px, dy = nd.cy - C.py, dz = nd.cz - C.pz;
         const float dist_sq = fmaf(dz, dz, fmaf(dy, dy, fmaf(dx, dx, P.eps2)));
         const bool active = resume <= off;
-        const int d2b = __float_as_int(dist_sq), hi = __float_as_int(nd.s2t), lo = hi - (int)C.band2;
-        bool geom = hi < d2b;
-        if (active && !geom && lo < d2b) geom = (hi == 0) || exact_take(off, C.b64);
-        if (active && geom) resume = nd.next_off;
-        if (__builtin_amdgcn_ballot_w64(active && !geom) == 0ull) {
-            off = nd.next_off;  // nobody opens this ancestor: the walk never enters it
+        bool take;
+        const unsigned next = advance<kNodeBytes>(active, opening(dist_sq, nd.s2t, C.band2, active, off / kNodeBytes, C.b64).geom,
+                                                  off, nd.next_off, resume, take);
+        if (next == nd.next_off) {
+            off = next;  // nobody opens this ancestor: the walk never enters it
             continue;
         }
         // descend to the child whose subtree contains S
-        unsigned c = off + kNodeBytes;
+        unsigned c = next;
         for (;;) {
             c = __builtin_amdgcn_readfirstlane(c);
             const unsigned nxt = reinterpret_cast<const Node *>(reinterpret_cast<const char *>(C.nodes) + c)->next_off;
@@ -1652,63 +1739,36 @@ __global__ __launch_bounds__(kBlock) void k_walk(const Node *__restrict__ nodes,
     }
     const int lane = threadIdx.x & 63;
     const int64_t rank = P.rank_begin + (int64_t)lb * blockDim.x + threadIdx.x;
-    const bool valid = rank < P.rank_end;
-    const bool frozen = info_in->error != 0 || info_in->sticky_error != 0;
-    const unsigned nn = frozen ? 0u : ((unsigned)info_in->walk_nodes * kNodeBytes);  // end offset
-
-    WalkCtx C;
-    C.nodes = nodes;
-    C.px = C.py = C.pz = 0.f;
-    C.band2 = __builtin_amdgcn_readfirstlane(info_in->band2);
-    uint32_t j = 0;
-    if (valid) {
-        const float4 p = posm_s[rank];
-        C.px = p.x; C.py = p.y; C.pz = p.z;
-        j = perm[rank];
-    }
-    C.b64 = Body64{tab, P.curbuf, j};
-    unsigned resume = valid ? 0u : 0xffffffffu;
+    const WalkCtx C = lane_prologue(nodes, posm_s, perm, rank, P.rank_end, info_in, tab, P.curbuf);
+    const bool valid = C.valid, frozen = C.frozen;
+    const uint32_t j = C.j;
+    const unsigned nn = C.rows * kNodeBytes;  // end offset
+    unsigned resume = C.resume;
     float ax = 0.f, ay = 0.f, az = 0.f;  // fp32 accumulators of the loops ...
     double sx = 0.0, sy = 0.0, sz = 0.0;  // ... emptied into these every few trips (two-level sums, NBMI_FLUSH)
     double acc64x = 0.0, acc64y = 0.0, acc64z = 0.0;
 
-    // [r3] force precision of this wave (see NBMI_V64_X).  force_prec 0: float64 where the bodies' own neighbourhood is
-    // dense enough that an error, once made, is amplified within a few hundred steps (decided in k_gather_scan, which
-    // has the sorted bodies in registers anyway), or where most of the system is.  All lanes of a wave agree; which
-    // 64 ranks form a wave does not depend on the sharding.
-    bool use64 = false;
-    if (!kCount && kIntegrate && tab->nodesd && P.force_prec != 1) {
-        if (P.force_prec == 2) {
-            use64 = true;
-        } else {
-            // k_gather_scan has already decided, wave by wave (and k_scan_subtiles for the system as a whole)
-            use64 = tab->wave_flag[(P.rank_begin + (int64_t)lb * blockDim.x + threadIdx.x) >> 6] != 0 || info_in->force_all64 != 0;
-        }
-        use64 = __builtin_amdgcn_readfirstlane((int)use64) != 0;
-    }
+    const bool use64 = !kCount && kIntegrate && wave_uses_f64(tab, info_in, P, rank);
     // (the clock is read here, behind the prologue's loads: the compiler treats the read as a possible store and
     // turns every scalar load that follows it into a vector load)
     const unsigned long long t_start = (kIntegrate && P.balance) ? __builtin_readcyclecounter() : 0ull;
     if (use64) {
         const NodeD *nodesd = reinterpret_cast<const NodeD *>(uniform_u64(reinterpret_cast<unsigned long long>(tab->nodesd)));
-        double qx = 0.0, qy = 0.0, qz = 0.0;
-        if (valid) {
-            const Bodies &cur = tab->buf[P.curbuf];
-            qx = cur.x[j]; qy = cur.y[j]; qz = cur.z[j];
-        }
-        const double eps2d = __longlong_as_double((long long)uniform_u64((unsigned long long)__double_as_longlong(tab->eps2)));
-        const unsigned nnd = __builtin_amdgcn_readfirstlane(frozen ? 0u : ((unsigned)info_in->walk_nodes * kNodeDBytes));
+        const Lane64 L = lane_f64(C);
+        // (read again, not kept from the prologue: one SGPR less, and the product instantiation sits at the 80 beyond which a
+        // CU holds one block fewer)
+        const unsigned nnd = __builtin_amdgcn_readfirstlane(walk_rows(info_in, frozen) * kNodeDBytes);
         unsigned off = 0u;
         // (the guarded walk: every visit in C++, skipping the pairs at dist_sq <= eps^2)
         if (kGuard) {
-            while (off < nnd) off = guard_visit64(nodesd, off, qx, qy, qz, eps2d, C.b64, resume, sx, sy, sz);
+            while (off < nnd) off = guard_visit64(nodesd, off, L.qx, L.qy, L.qz, L.eps2, C.b64, resume, sx, sy, sz);
         }
         while (!kGuard && off < nnd) {
             unsigned which = 0u;
-            walk4_asm64(nodesd, off, nnd, qx, qy, qz, eps2d, 2u * kBand64, resume, sx, sy, sz, which);
+            walk4_asm64(nodesd, off, nnd, L.qx, L.qy, L.qz, L.eps2, 2u * kBand64, resume, sx, sy, sz, which);
             off = __builtin_amdgcn_readfirstlane(off);
             if (!__builtin_amdgcn_readfirstlane(which)) break;
-            off = tie_visit64(nodesd, off, qx, qy, qz, eps2d, 2u * kBand64, C.b64, resume, sx, sy, sz);
+            off = tie_visit64(nodesd, off, L.qx, L.qy, L.qz, L.eps2, 2u * kBand64, C.b64, resume, sx, sy, sz);
         }
     } else if (!kCount && !kGuard) {
         if (nn && P.pair) {
@@ -1766,11 +1826,7 @@ __global__ __launch_bounds__(kBlock) void k_walk(const Node *__restrict__ nodes,
             } else {
                 off = visit<kGuard>(nodes, off, C.px, C.py, C.pz, C.b64, P, C.band2, resume, ax, ay, az, a_, f_, j_, b_);
             }
-            if (kGuard && !kCount && ++since_flush == 12) {  // as NBMI_FLUSH does every 3 trips of 4 visits
-                sx += (double)ax; sy += (double)ay; sz += (double)az;
-                ax = ay = az = 0.f;
-                since_flush = 0;
-            }
+            if (kGuard && !kCount) flush12(since_flush, ax, ay, az, sx, sy, sz);
             if (kCount) {
                 wv += 1; lv += a_ ? 1 : 0; la += f_ ? 1 : 0; jm += j_ ? 1 : 0; bd += b_ ? 1 : 0;
 #pragma unroll
@@ -1801,9 +1857,8 @@ __global__ __launch_bounds__(kBlock) void k_walk(const Node *__restrict__ nodes,
             tab->wave_cycles[4 * lb + (threadIdx.x >> 6)] = (unsigned)(dtc > 0xffffffffull ? 0xffffffffull : dtc);
         }
     } else if (valid) {
-        const int64_t o = 3 * (int64_t)tab->buf[P.curbuf].id[j];
         const bool d64 = kCount && P.acc64;
-        acc_out[o] = d64 ? acc64x : (double)ax; acc_out[o + 1] = d64 ? acc64y : (double)ay; acc_out[o + 2] = d64 ? acc64z : (double)az;
+        store_acc(acc_out, tab->buf[P.curbuf], j, d64 ? acc64x : (double)ax, d64 ? acc64y : (double)ay, d64 ? acc64z : (double)az);
     }
 }
 
@@ -1828,22 +1883,11 @@ __global__ __launch_bounds__(64 * K) void k_walk_split(const Node *__restrict__ 
     const int lb = logical_block(blockIdx.x, gridDim.x, P.xcd_chunk);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int64_t rank = P.rank_begin + (int64_t)lb * 64 + lane;
-    const bool valid = rank < P.rank_end;
-    const bool frozen = info_in->error != 0 || info_in->sticky_error != 0;
-    const int64_t num_nodes = frozen ? 0 : info_in->walk_nodes;
-
-    WalkCtx C;
-    C.nodes = nodes;
-    C.px = C.py = C.pz = 0.f;
-    C.band2 = __builtin_amdgcn_readfirstlane(info_in->band2);
-    uint32_t j = 0;
-    if (valid) {
-        const float4 p = posm_s[rank];
-        C.px = p.x; C.py = p.y; C.pz = p.z;
-        j = perm[rank];
-    }
-    C.b64 = Body64{tab, P.curbuf, j};
-    unsigned resume = valid ? 0u : 0xffffffffu;
+    const WalkCtx C = lane_prologue(nodes, posm_s, perm, rank, P.rank_end, info_in, tab, P.curbuf);
+    const bool valid = C.valid, frozen = C.frozen;
+    const uint32_t j = C.j;
+    const int64_t num_nodes = C.rows;
+    unsigned resume = C.resume;
     float ax = 0.f, ay = 0.f, az = 0.f;
     double sx = 0.0, sy = 0.0, sz = 0.0;  // two-level sums, see NBMI_FLUSH
     // wave-uniform range (w is the wave index): tell the compiler so
@@ -1855,11 +1899,8 @@ __global__ __launch_bounds__(64 * K) void k_walk_split(const Node *__restrict__ 
     // 262 k: a galaxy's visits are spread over the far field more evenly than one per octave, equal K-ths stay.)
     const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)(w == 0 ? 0 : first + span * w / K) * kNodeBytes);
     const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(first + span * (w + 1) / K) * kNodeBytes);
-    // [r3] force precision of the group (all K waves of the workgroup walk the same 64 bodies): as in k_walk
-    bool use64 = false;
-    if (tab->nodesd && P.force_prec != 1)
-        use64 = P.force_prec == 2 || tab->wave_flag[(P.rank_begin + (int64_t)lb * 64) >> 6] != 0 || info_in->force_all64 != 0;
-    use64 = __builtin_amdgcn_readfirstlane((int)use64) != 0;
+    // [r3] force precision of the group (all K waves of the workgroup walk the same 64 bodies)
+    const bool use64 = wave_uses_f64(tab, info_in, P, P.rank_begin + (int64_t)lb * 64);
     if (lo < hi) {
         // (seek works on the fp32 records in both cases: it only replays opening decisions, and those are the same)
         const unsigned c0 = __builtin_amdgcn_readfirstlane(lo == 0u ? 0u : seek(C, P, lo, resume));
@@ -1867,22 +1908,17 @@ __global__ __launch_bounds__(64 * K) void k_walk_split(const Node *__restrict__ 
             walk_span<false>(C, P, c0, hi, resume, ax, ay, az, sx, sy, sz);
         } else if (c0 < hi) {
             const NodeD *nodesd = reinterpret_cast<const NodeD *>(uniform_u64(reinterpret_cast<unsigned long long>(tab->nodesd)));
-            double qx = 0.0, qy = 0.0, qz = 0.0;
-            if (valid) {
-                const Bodies &cur = tab->buf[P.curbuf];
-                qx = cur.x[j]; qy = cur.y[j]; qz = cur.z[j];
-            }
-            const double eps2d = __longlong_as_double((long long)uniform_u64((unsigned long long)__double_as_longlong(tab->eps2)));
+            const Lane64 L = lane_f64(C);
             // offsets of the 24-byte records -> offsets of the 40-byte ones (same node indices)
             unsigned off = c0 / kNodeBytes * kNodeDBytes;
             const unsigned end = hi / kNodeBytes * kNodeDBytes;
             unsigned res64 = resume == 0xffffffffu ? resume : resume / kNodeBytes * kNodeDBytes;
             while (off < end) {
                 unsigned which = 0u;
-                walk1_asm64(nodesd, off, end, qx, qy, qz, eps2d, 2u * kBand64, res64, sx, sy, sz, which);
+                walk1_asm64(nodesd, off, end, L.qx, L.qy, L.qz, L.eps2, 2u * kBand64, res64, sx, sy, sz, which);
                 off = __builtin_amdgcn_readfirstlane(off);
                 if (!__builtin_amdgcn_readfirstlane(which)) break;
-                off = tie_visit64(nodesd, off, qx, qy, qz, eps2d, 2u * kBand64, C.b64, res64, sx, sy, sz);
+                off = tie_visit64(nodesd, off, L.qx, L.qy, L.qz, L.eps2, 2u * kBand64, C.b64, res64, sx, sy, sz);
             }
         }
     }
@@ -1915,17 +1951,7 @@ __global__ __launch_bounds__(kBlock) void k_walk_stack(const Node *__restrict__ 
     const int lb = logical_block(blockIdx.x, gridDim.x, P.xcd_chunk);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int64_t rank = P.rank_begin + (int64_t)lb * blockDim.x + threadIdx.x;
-    const bool valid = rank < P.rank_end;
-    const bool frozen = info_in->error != 0 || info_in->sticky_error != 0;
-    const unsigned band2 = __builtin_amdgcn_readfirstlane(info_in->band2);
-    float px = 0.f, py = 0.f, pz = 0.f;
-    uint32_t j = 0;
-    if (valid) {
-        const float4 p = posm_s[rank];
-        px = p.x; py = p.y; pz = p.z;
-        j = perm[rank];
-    }
-    const Body64 b64{tab, P.curbuf, j};
+    const WalkCtx C = lane_prologue(nodes, posm_s, perm, rank, P.rank_end, info_in, tab, P.curbuf);
     float ax = 0.f, ay = 0.f, az = 0.f;
     int sp = 0;
     const unsigned long long lane_bit = 1ull << lane;
@@ -1933,12 +1959,10 @@ __global__ __launch_bounds__(kBlock) void k_walk_stack(const Node *__restrict__ 
     // one node for the lanes in M: force for the lanes that take it, (offset, openers) pushed if anybody opens it
     auto visit = [&](unsigned off, unsigned long long M) {
         const Node nd = *reinterpret_cast<const Node *>(reinterpret_cast<const char *>(nodes) + off);
-        const float dx = nd.cx - px, dy = nd.cy - py, dz = nd.cz - pz;
+        const float dx = nd.cx - C.px, dy = nd.cy - C.py, dz = nd.cz - C.pz;
         const float d2 = fmaf(dz, dz, fmaf(dy, dy, fmaf(dx, dx, P.eps2)));
         const bool in = (M & lane_bit) != 0ull;
-        const int d2b = __float_as_int(d2), hi = __float_as_int(nd.s2t), lo = hi - (int)band2;
-        bool geom = hi < d2b;
-        if (in && !geom && lo < d2b) geom = (hi == 0) || exact_take(off, b64);
+        const bool geom = opening(d2, nd.s2t, C.band2, in, off / kNodeBytes, C.b64).geom;
         const bool take = in && geom;
         const float inv = __builtin_amdgcn_rsqf(d2);
         const float f = take ? (nd.gm * inv) * (inv * inv) : 0.f;
@@ -1950,8 +1974,8 @@ __global__ __launch_bounds__(kBlock) void k_walk_stack(const Node *__restrict__ 
         }
     };
 
-    if (!frozen) {
-        visit(0u, __builtin_amdgcn_ballot_w64(valid));
+    if (!C.frozen) {
+        visit(0u, __builtin_amdgcn_ballot_w64(C.valid));
         while (sp > 0) {
             sp--;
             const unsigned cell = __builtin_amdgcn_readfirstlane(st_off[w][sp]);
@@ -1969,8 +1993,8 @@ __global__ __launch_bounds__(kBlock) void k_walk_stack(const Node *__restrict__ 
             }
         }
     }
-    if (!valid) return;
-    integrate<kLeap>(tab, j, rank, ax, ay, az, P, frozen);
+    if (!C.valid) return;
+    integrate<kLeap>(tab, C.j, rank, ax, ay, az, P, C.frozen);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1983,13 +2007,9 @@ __global__ __launch_bounds__(kBlock) void k_walk_lane(const Node *__restrict__ n
                                                       const uint32_t *__restrict__ perm, WalkParams P) {
     const int lb = logical_block(blockIdx.x, gridDim.x, P.xcd_chunk);
     const int64_t rank = P.rank_begin + (int64_t)lb * blockDim.x + threadIdx.x;
-    if (rank >= P.rank_end) return;
-    const bool frozen = info_in->error != 0 || info_in->sticky_error != 0;
-    const unsigned nn = frozen ? 0u : ((unsigned)info_in->walk_nodes * kNodeBytes);
-    const unsigned band2 = info_in->band2;
-    const float4 p = posm_s[rank];
-    const uint32_t j = perm[rank];
-    const Body64 b64{tab, P.curbuf, j};
+    const WalkCtx C = lane_prologue(nodes, posm_s, perm, rank, P.rank_end, info_in, tab, P.curbuf);
+    if (!C.valid) return;
+    const unsigned nn = C.rows * kNodeBytes;
     float ax = 0.f, ay = 0.f, az = 0.f;
     unsigned off = 0u;
     while (off < nn) {
@@ -1997,17 +2017,15 @@ __global__ __launch_bounds__(kBlock) void k_walk_lane(const Node *__restrict__ n
         const float2 a0 = *reinterpret_cast<const float2 *>(q), a1 = *reinterpret_cast<const float2 *>(q + 8);
         const float2 b = *reinterpret_cast<const float2 *>(q + 16);
         const float4 a = make_float4(a0.x, a0.y, a1.x, a1.y);
-        const float dx = a.x - p.x, dy = a.y - p.y, dz = a.z - p.z;
+        const float dx = a.x - C.px, dy = a.y - C.py, dz = a.z - C.pz;
         const float d2 = fmaf(dz, dz, fmaf(dy, dy, fmaf(dx, dx, P.eps2)));
-        const int d2b = __float_as_int(d2), hi = __float_as_int(b.x), lo = hi - (int)band2;
-        bool take = hi < d2b;
-        if (!take && lo < d2b) take = (hi == 0) || exact_take(off, b64);
+        const bool take = opening(d2, b.x, C.band2, true, off / kNodeBytes, C.b64).geom;
         const float inv = __builtin_amdgcn_rsqf(d2);
         const float f = take ? (a.w * inv) * (inv * inv) : 0.f;
         ax = fmaf(dx, f, ax); ay = fmaf(dy, f, ay); az = fmaf(dz, f, az);
         off = take ? __float_as_uint(b.y) : off + kNodeBytes;
     }
-    integrate<false>(tab, j, rank, ax, ay, az, P, frozen);
+    integrate<false>(tab, C.j, rank, ax, ay, az, P, C.frozen);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2036,28 +2054,18 @@ __global__ __launch_bounds__(kBlock) void k_walk_diag(const Node *__restrict__ n
                                                       const float4 *__restrict__ posm_s, const uint32_t *__restrict__ perm,
                                                       WalkParams P) {
     const int64_t rank = P.rank_begin + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool valid = rank < P.rank_end;
-    const bool frozen = info_in->error != 0 || info_in->sticky_error != 0;
-    const unsigned nn = frozen ? 0u : ((unsigned)info_in->walk_nodes * kNodeBytes);
-    const unsigned band2 = __builtin_amdgcn_readfirstlane(info_in->band2);
-    float px = 0.f, py = 0.f, pz = 0.f;
-    double qx = 0.0, qy = 0.0, qz = 0.0;
-    uint32_t j = 0;
-    if (valid) {
-        const float4 p = posm_s[rank];
-        px = p.x; py = p.y; pz = p.z;
-        j = perm[rank];
-        const Bodies &cur = tab->buf[P.curbuf];
-        qx = cur.x[j]; qy = cur.y[j]; qz = cur.z[j];
-    }
+    const WalkCtx C = lane_prologue(nodes, posm_s, perm, rank, P.rank_end, info_in, tab, P.curbuf);
+    const Lane64 L = lane_f64(C);
+    const unsigned nn = C.rows * kNodeBytes;
+    const float px = C.px, py = C.py, pz = C.pz;
+    const double qx = L.qx, qy = L.qy, qz = L.qz;
     const float plx = (float)(qx - (double)px), ply = (float)(qy - (double)py), plz = (float)(qz - (double)pz);
-    const Body64 b64{tab, P.curbuf, j};
-    unsigned resume = valid ? 0u : 0xffffffffu;
+    unsigned resume = C.resume;
     double sx = 0.0, sy = 0.0, sz = 0.0;
     float fx = 0.f, fy = 0.f, fz = 0.f;
     int nflush = 0;
     const int mode = P.prec;
-    const double eps2d = tab->eps2;
+    const double eps2d = L.eps2;
     unsigned off = 0u;
     while (off < nn) {
         off = __builtin_amdgcn_readfirstlane(off);
@@ -2065,12 +2073,11 @@ __global__ __launch_bounds__(kBlock) void k_walk_diag(const Node *__restrict__ n
         const float dx = nd.cx - px, dy = nd.cy - py, dz = nd.cz - pz;
         const float dist_sq = fmaf(dz, dz, fmaf(dy, dy, fmaf(dx, dx, P.eps2)));
         const bool active = resume <= off;
-        const int d2b = __float_as_int(dist_sq), hi = __float_as_int(nd.s2t), lo = hi - (int)band2;
-        bool geom = hi < d2b;
-        if (active && !geom && lo < d2b) geom = (hi == 0) || exact_take(off, b64);
-        const bool take = active && geom;
+        const bool geom = opening(dist_sq, nd.s2t, C.band2, active, off / kNodeBytes, C.b64).geom;
+        bool take;
+        const unsigned next = advance<kNodeBytes>(active, geom, off, nd.next_off, resume, take);
         if (take) {
-            const bool leaf = hi == 0;
+            const bool leaf = __float_as_int(nd.s2t) == 0;
             const double rc2 = (double)P.near2;  // modes >= 20: bodies inside this cylindrical radius^2 (x, z) take float64
             const bool core = mode >= 20 && (qx * qx + qz * qz) < rc2;
             const bool use64 = mode == 2 || (mode >= 9 && mode <= 14) || (mode == 3 && leaf) || (mode == 4 && dist_sq < P.near2) || core;
@@ -2135,12 +2142,10 @@ __global__ __launch_bounds__(kBlock) void k_walk_diag(const Node *__restrict__ n
                     sx += (double)(ex * f); sy += (double)(ey * f); sz += (double)(ez * f);
                 }
             }
-            resume = nd.next_off;
         }
-        const unsigned long long any_open = __builtin_amdgcn_ballot_w64(active && !geom);
-        off = any_open ? off + kNodeBytes : nd.next_off;
+        off = next;
     }
-    publish_maxabs(tab, valid ? integrate<false>(tab, j, rank, sx + (double)fx, sy + (double)fy, sz + (double)fz, P, frozen) : 0.0);
+    publish_maxabs(tab, C.valid ? integrate<false>(tab, C.j, rank, sx + (double)fx, sy + (double)fy, sz + (double)fz, P, C.frozen) : 0.0);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -3362,8 +3367,8 @@ __global__ void k_copy_ids(const int32_t *__restrict__ ids, int32_t *__restrict_
 // for bit.
 // ---------------------------------------------------------------------------------------
 // Tree potential.  The walk of K9 in its C++ form, one wave per 64 key-adjacent bodies, one wave-uniform cursor over
-// the same pre-order array and skip links, and per lane the same opening decision as visit(): the fp32 test on the
-// Node record, re-decided in float64 through Node64 (exact_take) where d^2 falls inside the uncertainty band.  A lane's
+// the same pre-order array and skip links, and per lane the force walks' opening decision (opening()): the fp32 test on
+// the Node record, re-decided in float64 through Node64 where d^2 falls inside the uncertainty band.  A lane's
 // accepted set does not depend on the other lanes of its wave (it takes part in every node none of its own accepted
 // ancestors covers), so it is the force walk's set.  What differs is the term: the node's float64 row pot[idx] =
 // {cx, cy, cz, G M} (written by k_emit_tile into the diag64 slot for this build only: a cell's double-double moments,
@@ -3381,31 +3386,20 @@ __global__ __launch_bounds__(kBlock) void k_potential_tree(const Node *__restric
                                                            int32_t *__restrict__ cnt, const double *__restrict__ quad) {
     if (info->error != 0 || info->sticky_error != 0) return;  // the tree did not fit: the caller reports it
     const int64_t rank = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    const bool valid = rank < n;
+    const WalkCtx C = lane_prologue(nodes, posm_s, perm, rank, n, info, tab, curbuf);
+    const Lane64 L = lane_f64(C);
     const unsigned nn = __builtin_amdgcn_readfirstlane((unsigned)info->num_nodes * kNodeBytes);
-    const unsigned band2 = __builtin_amdgcn_readfirstlane(info->band2);
-    const double eps2 = tab->eps2;
+    const double eps2 = L.eps2, qx = L.qx, qy = L.qy, qz = L.qz;
     // The band's half width is capped at 2^21 ulps (band_half_ulps): enough for the fp32 error of d^2, (6.93 maxabs / d
     // + 4) ulps, only while d >= 3.3e-6 maxabs.  At eps == 0 (or an eps below that) closer pairs exist, and their fp32
     // d^2 says nothing about the test: a cell closer than 8e-6 maxabs (twice the limit plus the rounding of d itself) is
     // decided in float64 whatever the fp32 test said, so that `terms` stays the reference's count there too.
     float near2 = 0.f;
-    if (band2 >= 2u * 2097153u) {
+    if (C.band2 >= 2u * 2097153u) {
         const double r = 8.0e-6 * __longlong_as_double((long long)info->maxabs_bits);
         near2 = eps2f + (float)(r * r);
     }
-    float px = 0.f, py = 0.f, pz = 0.f;
-    double qx = 0.0, qy = 0.0, qz = 0.0;
-    uint32_t j = 0;
-    if (valid) {
-        const float4 p = posm_s[rank];
-        px = p.x; py = p.y; pz = p.z;
-        j = perm[rank];
-        const Bodies &cur = tab->buf[curbuf];
-        qx = cur.x[j]; qy = cur.y[j]; qz = cur.z[j];
-    }
-    const Body64 b64{tab, curbuf, j};
-    unsigned resume = valid ? 0u : 0xffffffffu;
+    unsigned resume = C.resume;
     double acc = 0.0;
     int32_t terms = 0;
     unsigned off = 0u;
@@ -3413,15 +3407,13 @@ __global__ __launch_bounds__(kBlock) void k_potential_tree(const Node *__restric
         off = __builtin_amdgcn_readfirstlane(off);
         const unsigned idx = off / kNodeBytes;
         const Node nd = nodes[idx];
-        // visit(): the same fp32 operations in the same order
-        const float dx = nd.cx - px, dy = nd.cy - py, dz = nd.cz - pz;
+        const float dx = nd.cx - C.px, dy = nd.cy - C.py, dz = nd.cz - C.pz;
         const float dist_sq = fmaf(dz, dz, fmaf(dy, dy, fmaf(dx, dx, eps2f)));
         const bool active = resume <= off;
-        const int d2b = __float_as_int(dist_sq), hi = __float_as_int(nd.s2t), lo = hi - (int)band2;
-        bool geom = hi < d2b;
-        const bool band = active && ((!geom && lo < d2b) || (hi != 0 && dist_sq < near2));
-        if (band) geom = (hi == 0) || exact_take_idx(idx, b64);
-        const bool take = active && geom;
+        const bool near = __float_as_int(nd.s2t) != 0 && dist_sq < near2;  // a cell, see near2
+        const bool geom = opening(dist_sq, nd.s2t, C.band2, active, idx, C.b64, near).geom;
+        bool take;
+        const unsigned next = advance<kNodeBytes>(active, geom, off, nd.next_off, resume, take);
         if (take) {
             const double4 q = pot[idx];
             const double ex = q.x - qx, ey = q.y - qy, ez = q.z - qz;
@@ -3437,14 +3429,12 @@ __global__ __launch_bounds__(kBlock) void k_potential_tree(const Node *__restric
                     acc += 0.5 * ((pxx + pyy + pzz) * i3 - 3.0 * dpd * (i3 / d2));
                 }
             }
-            resume = nd.next_off;
         }
-        const unsigned long long any_open = __builtin_amdgcn_ballot_w64(active && !geom);
-        off = any_open ? off + kNodeBytes : nd.next_off;
+        off = next;
     }
-    if (valid) {
-        phi[j] = acc;
-        cnt[j] = terms;
+    if (C.valid) {
+        phi[C.j] = acc;
+        cnt[C.j] = terms;
     }
 }
 
@@ -3549,10 +3539,9 @@ __device__ __forceinline__ void quad_term(const NodeQ &Q, float dx, float dy, fl
 }
 
 // The quadrupole walk.  k_potential_tree's shape: one wave per 64 key-adjacent bodies, one wave-uniform cursor, the Node
-// and the NodeQ record fetched at the same uniform byte offset (scalar loads), visit()'s decision (band, exact_take)
-// and its monopole arithmetic operation for operation; float64 waves (force precision, as k_walk decides it) take the
-// decision and the monopole of guard_visit64 / tie_visit64 from the NodeD row and start the correction from the float64
-// difference rounded to fp32.  fp32 partial sums are emptied into float64 every 12 visits (NBMI_FLUSH's rhythm).
+// and the NodeQ record fetched at the same uniform byte offset (scalar loads), opening() and visit()'s fp32 monopole
+// (its association, (G m / d) (1 / d^2)); float64 waves (wave_uses_f64) take the decision and monopole64() from the NodeD
+// row and start the correction from the float64 difference rounded to fp32.  fp32 partial sums: flush12().
 // Epilogues: k_walk's.  !kIntegrate: accelerations in the caller's order and the lane-accept count (nbmi_walk_counters).
 // Empty asm statements (the idiom of tie_visit64; no instruction is emitted) that pin every word of both records
 // behind their loads: the loads are all requested first and one wait covers them.  Without the pins the compiler sinks
@@ -3568,38 +3557,19 @@ __global__ __launch_bounds__(kBlock) void k_walk_quad(const Node *__restrict__ n
                                                       double *__restrict__ acc_out, WalkParams P, TreeInfo *info_out) {
     const int lb = logical_block(blockIdx.x, gridDim.x, P.xcd_chunk);
     const int64_t rank = P.rank_begin + (int64_t)lb * blockDim.x + threadIdx.x;
-    const bool valid = rank < P.rank_end;
-    const bool frozen = info_in->error != 0 || info_in->sticky_error != 0;
-    const unsigned rows = __builtin_amdgcn_readfirstlane(frozen ? 0u : (unsigned)info_in->walk_nodes);
-    const unsigned band2 = __builtin_amdgcn_readfirstlane(info_in->band2);
-    float px = 0.f, py = 0.f, pz = 0.f;
-    uint32_t j = 0;
-    if (valid) {
-        const float4 p = posm_s[rank];
-        px = p.x; py = p.y; pz = p.z;
-        j = perm[rank];
-    }
-    const Body64 b64{tab, P.curbuf, j};
-    unsigned resume = valid ? 0u : 0xffffffffu;
+    const WalkCtx C = lane_prologue(nodes, posm_s, perm, rank, P.rank_end, info_in, tab, P.curbuf);
+    const unsigned rows = __builtin_amdgcn_readfirstlane(C.rows);
+    unsigned resume = C.resume;
     float ax = 0.f, ay = 0.f, az = 0.f;
     double sx = 0.0, sy = 0.0, sz = 0.0;
     unsigned long long accepts = 0;
-    bool use64 = false;
-    if (nodesd && P.force_prec != 1) {
-        if (P.force_prec == 2) use64 = true;
-        else if (kIntegrate) use64 = tab->wave_flag[rank >> 6] != 0 || info_in->force_all64 != 0;
-        use64 = __builtin_amdgcn_readfirstlane((int)use64) != 0;
-    }
+    const bool use64 = wave_uses_f64(tab, info_in, P, rank, kIntegrate);
     int since_flush = 0;
     if (use64) {
         // (the float64 records come as a kernel argument, not through the table as in k_walk: a pointer loaded from
         // memory is a generic one to the compiler, and its loads become vector loads)
-        double qx = 0.0, qy = 0.0, qz = 0.0;
-        if (valid) {
-            const Bodies &cur = tab->buf[P.curbuf];
-            qx = cur.x[j]; qy = cur.y[j]; qz = cur.z[j];
-        }
-        const double eps2 = __longlong_as_double((long long)uniform_u64((unsigned long long)__double_as_longlong(tab->eps2)));
+        const Lane64 L = lane_f64(C);
+        const double qx = L.qx, qy = L.qy, qz = L.qz, eps2 = L.eps2;
         unsigned idx = 0u;
         while (idx < rows) {
             idx = __builtin_amdgcn_readfirstlane(idx);
@@ -3612,32 +3582,20 @@ __global__ __launch_bounds__(kBlock) void k_walk_quad(const Node *__restrict__ n
             const double d2 = __builtin_fma(dz, dz, __builtin_fma(dy, dy, __builtin_fma(dx, dx, eps2)));
             const float d2f = (float)d2;
             const bool active = resume <= offd;
-            const int d2b = __float_as_int(d2f), hi = __float_as_int(nd.s2t), lo = hi - 2 * (int)kBand64;
-            bool geom = hi < d2b;
-            if (active && !geom && lo < d2b) geom = (hi == 0) || exact_take_idx(idx, b64);
-            const bool take = active && geom;
+            const bool geom = opening(d2f, nd.s2t, 2u * kBand64, active, idx, C.b64).geom;
+            bool take;
+            const unsigned next = advance<kNodeDBytes>(active, geom, offd, nd.next_off, resume, take);
             const bool force = kGuard ? (take && d2 > eps2) : take;
             if (!kIntegrate) accepts += (take && d2 > eps2) ? 1u : 0u;
-            if (force) {  // guard_visit64's monopole
-                const double y0 = (double)__builtin_amdgcn_rsqf(d2f);
-                const double t = y0 * y0;
-                double w = nd.gm * y0;
-                const double e = __builtin_fma(-d2, t, 1.0);
-                w = w * t;
-                const double h = e * 1.5;
-                w = __builtin_fma(w, h, w);
+            if (force) {
+                const double w = monopole64(nd.gm, d2, d2f);
                 sx = __builtin_fma(dx, w, sx); sy = __builtin_fma(dy, w, sy); sz = __builtin_fma(dz, w, sz);
             }
             // (a leaf record, s2t == 0, carries no moments: a wave-uniform skip)
-            if (hi != 0) quad_term(Q, (float)dx, (float)dy, (float)dz, force ? __builtin_amdgcn_rsqf(d2f) : 0.f, ax, ay, az);
-            if (take) resume = nd.next_off;
-            if (++since_flush == 12) {
-                sx += (double)ax; sy += (double)ay; sz += (double)az;
-                ax = ay = az = 0.f;
-                since_flush = 0;
-            }
-            const unsigned long long any_open = __builtin_amdgcn_ballot_w64(active && !geom);
-            idx = any_open ? idx + 1u : nd.next_off / kNodeDBytes;
+            if (__float_as_int(nd.s2t) != 0)
+                quad_term(Q, (float)dx, (float)dy, (float)dz, force ? __builtin_amdgcn_rsqf(d2f) : 0.f, ax, ay, az);
+            flush12(since_flush, ax, ay, az, sx, sy, sz);
+            idx = next / kNodeDBytes;
         }
     } else {
         const unsigned nn = rows * kNodeBytes;
@@ -3648,15 +3606,12 @@ __global__ __launch_bounds__(kBlock) void k_walk_quad(const Node *__restrict__ n
             NodeQ Q = *reinterpret_cast<const NodeQ *>(reinterpret_cast<const char *>(nodesq) + off);
             NBMI_PIN_N(nd);
             NBMI_PIN_Q(Q);
-            // visit(): the same fp32 operations in the same order
-            const float dx = nd.cx - px, dy = nd.cy - py, dz = nd.cz - pz;
+            const float dx = nd.cx - C.px, dy = nd.cy - C.py, dz = nd.cz - C.pz;
             const float dist_sq = fmaf(dz, dz, fmaf(dy, dy, fmaf(dx, dx, P.eps2)));
             const bool active = resume <= off;
-            const int d2b = __float_as_int(dist_sq), hi = __float_as_int(nd.s2t), lo = hi - (int)band2;
-            bool geom = hi < d2b;
-            const bool band = active && !geom && lo < d2b;
-            if (band) geom = (hi == 0) || exact_take(off, b64);
-            const bool take = active && geom;
+            const bool geom = opening(dist_sq, nd.s2t, C.band2, active, off / kNodeBytes, C.b64).geom;
+            bool take;
+            const unsigned next = advance<kNodeBytes>(active, geom, off, nd.next_off, resume, take);
             const bool force = kGuard ? (take && dist_sq > P.eps2) : take;
             if (!kIntegrate) accepts += (take && dist_sq > P.eps2) ? 1u : 0u;
             const float inv = force ? __builtin_amdgcn_rsqf(dist_sq) : 0.f;
@@ -3664,25 +3619,16 @@ __global__ __launch_bounds__(kBlock) void k_walk_quad(const Node *__restrict__ n
             ax = fmaf(dx, f, ax);
             ay = fmaf(dy, f, ay);
             az = fmaf(dz, f, az);
-            if (hi != 0) quad_term(Q, dx, dy, dz, inv, ax, ay, az);  // (a leaf record carries no moments: a wave-uniform skip)
-            resume = take ? nd.next_off : resume;
-            if (++since_flush == 12) {
-                sx += (double)ax; sy += (double)ay; sz += (double)az;
-                ax = ay = az = 0.f;
-                since_flush = 0;
-            }
-            const unsigned long long any_open = __builtin_amdgcn_ballot_w64(active && !geom);
-            off = any_open ? off + kNodeBytes : nd.next_off;
+            if (__float_as_int(nd.s2t) != 0) quad_term(Q, dx, dy, dz, inv, ax, ay, az);  // (a leaf record carries no moments: a wave-uniform skip)
+            flush12(since_flush, ax, ay, az, sx, sy, sz);
+            off = next;
         }
     }
     sx += (double)ax; sy += (double)ay; sz += (double)az;
     if (kIntegrate) {
-        publish_maxabs(tab, valid ? integrate<kLeap>(tab, j, rank, sx, sy, sz, P, frozen) : 0.0);
+        publish_maxabs(tab, C.valid ? integrate<kLeap>(tab, C.j, rank, sx, sy, sz, P, C.frozen) : 0.0);
     } else {
-        if (valid) {
-            const int64_t o = 3 * (int64_t)tab->buf[P.curbuf].id[j];
-            acc_out[o] = sx; acc_out[o + 1] = sy; acc_out[o + 2] = sz;
-        }
+        if (C.valid) store_acc(acc_out, tab->buf[P.curbuf], C.j, sx, sy, sz);
         atomicAdd(&info_out->lane_accepts, accepts);
     }
 }
@@ -4387,6 +4333,22 @@ bool guarded(const nbmi_sim *s) {
     return gm / ((double)eps2 * sqrt((double)eps2)) > 0x1p120;
 }
 
+// Runtime values as template arguments: f is a generic lambda and gets std::true_type / std::false_type, or the
+// std::integral_constant of the one of Vs... that v equals (v is always one of them).
+template <class F>
+void with_bool(bool b, F &&f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+template <int... Vs, class F>
+void with_int(int v, F &&f) {
+    (void)((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
+// what a force walk does with its result (with_int<kWalkForces, kWalkStep, kWalkLeap>)
+constexpr int kWalkForces = 0;  // accelerations in the caller's order, work counters (no integration)
+constexpr int kWalkStep = 1;    // the fused kick-drift
+constexpr int kWalkLeap = 2;    // a leapfrog epilogue (WalkTable::leap)
+
 // leap (integrating walks only): 0 = kick-drift, kLeapClose / kLeapPrime = the leapfrog epilogues (leap_epilogue)
 int enqueue_walk(nbmi_sim *s, bool integrate, double dt, double *acc_out, int leap = 0) {
     const int64_t n = s->n;
@@ -4401,6 +4363,7 @@ int enqueue_walk(nbmi_sim *s, bool integrate, double dt, double *acc_out, int le
     P.rank_end = integrate ? s->shard_end : n;
     P.eps2 = (float)(s->softening * s->softening);
     const bool guard = guarded(s);
+    const int what = !integrate ? kWalkForces : (leap ? kWalkLeap : kWalkStep);
     P.dt = dt;
     P.damping = s->damping;
     const int64_t cntr = P.rank_end - P.rank_begin;
@@ -4432,12 +4395,13 @@ int enqueue_walk(nbmi_sim *s, bool integrate, double dt, double *acc_out, int le
             return NBMI_ERR_ARG;
         }
         const int gq = (int)((cntr + kBlock - 1) / kBlock);
-#define NBMI_WALK_QUAD(I, G, L) \
-    k_walk_quad<I, G, L><<<gq, kBlock, 0, st>>>(s->nodes, s->nodesq, P.force_prec != 1 ? s->nodesd : nullptr, tab, s->info, s->posm_s, s->perm, acc_out, P, s->info)
-        if (!integrate) { if (guard) NBMI_WALK_QUAD(false, true, false); else NBMI_WALK_QUAD(false, false, false); }
-        else if (leap) { if (guard) NBMI_WALK_QUAD(true, true, true); else NBMI_WALK_QUAD(true, false, true); }
-        else { if (guard) NBMI_WALK_QUAD(true, true, false); else NBMI_WALK_QUAD(true, false, false); }
-#undef NBMI_WALK_QUAD
+        with_int<kWalkForces, kWalkStep, kWalkLeap>(what, [&](auto w) {
+            with_bool(guard, [&](auto g) {
+                constexpr int kW = decltype(w)::value;
+                k_walk_quad<kW != kWalkForces, decltype(g)::value, kW == kWalkLeap><<<gq, kBlock, 0, st>>>(
+                    s->nodes, s->nodesq, P.force_prec != 1 ? s->nodesd : nullptr, tab, s->info, s->posm_s, s->perm, acc_out, P, s->info);
+            });
+        });
         NBMI_HIP_CHECK(hipGetLastError());
         return 0;
     }
@@ -4449,28 +4413,22 @@ int enqueue_walk(nbmi_sim *s, bool integrate, double dt, double *acc_out, int le
     int parts = 1;
     while (parts < 16 && tree_groups <= 4300 && tree_groups * parts * 2 <= s->split_max_waves) parts *= 2;
     if (integrate && !guard && parts > 1) {
-#define NBMI_SPLIT_L(KV, L) \
-    k_walk_split<KV, L><<<(int)groups, 64 * KV, 0, st>>>(s->nodes, tab, s->info, s->posm_s, s->perm, P)
-#define NBMI_SPLIT(KV) \
-    do { if (leap) NBMI_SPLIT_L(KV, true); else NBMI_SPLIT_L(KV, false); } while (0)
-        if (parts == 2) NBMI_SPLIT(2);
-        else if (parts == 4) NBMI_SPLIT(4);
-        else if (parts == 8) NBMI_SPLIT(8);
-        else NBMI_SPLIT(16);
-#undef NBMI_SPLIT
-#undef NBMI_SPLIT_L
+        with_int<2, 4, 8, 16>(parts, [&](auto k) {
+            with_bool(leap != 0, [&](auto l) {
+                constexpr int K = decltype(k)::value;
+                k_walk_split<K, decltype(l)::value><<<(int)groups, 64 * K, 0, st>>>(s->nodes, tab, s->info, s->posm_s, s->perm, P);
+            });
+        });
         NBMI_HIP_CHECK(hipGetLastError());
         return 0;
     }
     const int wb = s->walk_block;
     const int gb = (int)((cntr + wb - 1) / wb);
     if (integrate && s->walk_stack && !guard && !s->owner) {
-        if (leap)
-            k_walk_stack<true><<<(int)((cntr + kBlock - 1) / kBlock), kBlock, 0, st>>>(s->nodes, s->child_tab, tab, s->info,
-                                                                                       s->posm_s, s->perm, P);
-        else
-            k_walk_stack<false><<<(int)((cntr + kBlock - 1) / kBlock), kBlock, 0, st>>>(s->nodes, s->child_tab, tab, s->info,
-                                                                                        s->posm_s, s->perm, P);
+        with_bool(leap != 0, [&](auto l) {
+            k_walk_stack<decltype(l)::value><<<(int)((cntr + kBlock - 1) / kBlock), kBlock, 0, st>>>(s->nodes, s->child_tab, tab,
+                                                                                                    s->info, s->posm_s, s->perm, P);
+        });
         NBMI_HIP_CHECK(hipGetLastError());
         return 0;
     }
@@ -4479,18 +4437,14 @@ int enqueue_walk(nbmi_sim *s, bool integrate, double dt, double *acc_out, int le
         NBMI_HIP_CHECK(hipGetLastError());
         return 0;
     }
-#define NBMI_WALK(I, C, G) \
-    k_walk<I, C, G><<<gb, wb, 0, st>>>(s->nodes, tab, s->info, s->posm_s, s->perm, acc_out, P, s->info)
-#define NBMI_WALK_LEAP(G) \
-    k_walk<true, false, G, true><<<gb, wb, 0, st>>>(s->nodes, tab, s->info, s->posm_s, s->perm, acc_out, P, s->info)
     // balance mode: full, unsharded integrating walks of the product kernel with the default block mapping
     // (measured: 10 M collision walk 15.9 -> 14.8 ms, fp32 10.4 -> 9.8; 4 M galaxy 6.96 -> 6.90; at 1 M bodies the eighths are
     // within 1 % of each other already and the half-empty launch costs 2 %: from 8 192 blocks = 2 M bodies on)
     const bool balance = integrate && !guard && s->xcd_balance && s->xcd_chunk == 0 && wb == kBlock && !s->owner &&
                          (gb >= 8192 || s->xcd_balance > 1) &&
                          P.rank_begin == 0 && P.rank_end == n && getenv("NBMI_XCD_CHUNK") == nullptr;
+    const int jmax = ((gb + 7) / 8) * 3 / 2 + 1;  // balance mode: the launch has 8 jmax workgroups
     if (balance) {
-        const int jmax = ((gb + 7) / 8) * 3 / 2 + 1;
         if (s->cut_pending) {  // the cuts made from the last walk's times (on the side stream)
             NBMI_HIP_CHECK(hipStreamWaitEvent(st, s->ev_cut, 0));
             s->cut_pending = false;
@@ -4506,9 +4460,17 @@ int enqueue_walk(nbmi_sim *s, bool integrate, double dt, double *acc_out, int le
             NBMI_HIP_CHECK(hipEventCreateWithFlags(&s->ev_walked, hipEventDisableTiming));
             NBMI_HIP_CHECK(hipEventCreateWithFlags(&s->ev_cut, hipEventDisableTiming));
         }
-        if (leap) k_walk<true, false, false, true><<<8 * jmax, wb, 0, st>>>(s->nodes, tab, s->info, s->posm_s, s->perm, acc_out, P, s->info);
-        else k_walk<true, false, false><<<8 * jmax, wb, 0, st>>>(s->nodes, tab, s->info, s->posm_s, s->perm, acc_out, P, s->info);
-        NBMI_HIP_CHECK(hipGetLastError());
+    }
+    const int grid = balance ? 8 * jmax : gb;
+    with_int<kWalkForces, kWalkStep, kWalkLeap>(what, [&](auto w) {
+        with_bool(guard, [&](auto g) {
+            constexpr int kW = decltype(w)::value;
+            k_walk<kW != kWalkForces, kW == kWalkForces, decltype(g)::value, kW == kWalkLeap><<<grid, wb, 0, st>>>(
+                s->nodes, tab, s->info, s->posm_s, s->perm, acc_out, P, s->info);
+        });
+    });
+    NBMI_HIP_CHECK(hipGetLastError());
+    if (balance) {
         // cuts for the next step: beside whatever the main stream does next (the next step's keys, sort and build)
         NBMI_HIP_CHECK(hipEventRecord(s->ev_walked, st));
         NBMI_HIP_CHECK(hipStreamWaitEvent(s->side, s->ev_walked, 0));
@@ -4516,18 +4478,7 @@ int enqueue_walk(nbmi_sim *s, bool integrate, double dt, double *acc_out, int le
         NBMI_HIP_CHECK(hipGetLastError());
         NBMI_HIP_CHECK(hipEventRecord(s->ev_cut, s->side));
         s->cut_pending = true;
-        return 0;
     }
-    if (integrate && leap) {
-        if (guard) NBMI_WALK_LEAP(true); else NBMI_WALK_LEAP(false);
-    } else if (integrate) {
-        if (guard) NBMI_WALK(true, false, true); else NBMI_WALK(true, false, false);
-    } else {
-        if (guard) NBMI_WALK(false, true, true); else NBMI_WALK(false, true, false);
-    }
-#undef NBMI_WALK
-#undef NBMI_WALK_LEAP
-    NBMI_HIP_CHECK(hipGetLastError());
     return 0;
 }
 
@@ -4548,30 +4499,19 @@ int launch_direct(nbmi_sim *s, double dt, double *acc_out, int leap = 0) {
     if (cnt <= 0) return 0;
     // bodies per thread: enough blocks to cover 256 CUs a few times over
     int ib = cnt >= 512 * 1024 ? 4 : (cnt >= 128 * 1024 ? 2 : 1);
-#define NBMI_DIRECT_L(IBV, LV)                                                                                \
-    do {                                                                                                      \
-        const int gb = (int)((cnt + (int64_t)kBlock * IBV - 1) / ((int64_t)kBlock * IBV));                    \
-        if (guard)                                                                                            \
-            k_direct<IBV, true, kIntegrate, false, LV><<<gb, kBlock, 0, st>>>(s->posm_s, n, ibeg, iend, eps2, cur, nxt, \
-                                                                         acc_out, dt, s->damping, 0.0);        \
-        else if (s->uniform_gm > 0.0)                                                                         \
-            k_direct<IBV, false, kIntegrate, true, LV><<<gb, kBlock, 0, st>>>(s->posm_s, n, ibeg, iend, eps2, cur, nxt, \
-                                                                         acc_out, dt, s->damping, s->uniform_gm); \
-        else                                                                                                  \
-            k_direct<IBV, false, kIntegrate, false, LV><<<gb, kBlock, 0, st>>>(s->posm_s, n, ibeg, iend, eps2, cur, nxt, \
-                                                                          acc_out, dt, s->damping, 0.0);      \
-    } while (0)
-#define NBMI_DIRECT(IBV)                                                     \
-    do {                                                                     \
-        if (leap == kLeapClose) NBMI_DIRECT_L(IBV, kIntegrate ? kLeapClose : 0); \
-        else if (leap == kLeapPrime) NBMI_DIRECT_L(IBV, kIntegrate ? kLeapPrime : 0); \
-        else NBMI_DIRECT_L(IBV, 0);                                          \
-    } while (0)
-    if (ib == 4) NBMI_DIRECT(4);
-    else if (ib == 2) NBMI_DIRECT(2);
-    else NBMI_DIRECT(1);
-#undef NBMI_DIRECT
-#undef NBMI_DIRECT_L
+    // pair arithmetic: 0 = guarded, 1 = all masses equal (G m is a constant), 2 = the general form
+    const int pairs = guard ? 0 : (s->uniform_gm > 0.0 ? 1 : 2);
+    with_int<1, 2, 4>(ib, [&](auto ibv) {
+        with_int<0, 1, 2>(pairs, [&](auto pv) {
+            with_int<0, kLeapClose, kLeapPrime>(leap, [&](auto lv) {
+                constexpr int kIB = decltype(ibv)::value, kPairs = decltype(pv)::value;
+                constexpr int kLV = kIntegrate ? decltype(lv)::value : 0;  // (the force pass has no epilogue to choose)
+                const int gb = (int)((cnt + (int64_t)kBlock * kIB - 1) / ((int64_t)kBlock * kIB));
+                k_direct<kIB, kPairs == 0, kIntegrate, kPairs == 1, kLV><<<gb, kBlock, 0, st>>>(
+                    s->posm_s, n, ibeg, iend, eps2, cur, nxt, acc_out, dt, s->damping, kPairs == 1 ? s->uniform_gm : 0.0);
+            });
+        });
+    });
     NBMI_HIP_CHECK(hipGetLastError());
     return 0;
 }
