@@ -228,11 +228,63 @@ __global__ void k_header(TreeInfo *info) {
 // bodies share a wave: waves along the Hilbert curve are more compact and visit 7 % fewer nodes (1 M galaxy;
 // 5 % at the 10 M collision; scripts/analysis/hilbert_groups.py).  nbmi_get_keys / nbmi_get_cells decode back
 // to the reference's octant digits.  kHilbert = false (NBMI_HILBERT=0): plain octant digits.
-template <bool kHilbert>
+// The packed sort word: (upper key word >> shift) << 24 | body index.  It holds while the sorted prefix has at most
+// 40 bits and the index fits in 24 (packed_sort_ok() is the one place that decides).
+constexpr int kPackIdxBits = 24, kPackMaxSortBits = 64 - kPackIdxBits;
+constexpr uint64_t kPackIdxMask = (1ull << kPackIdxBits) - 1ull;
+
+// 21 levels of the descent from the cell (cx, cy, cz, hs) in orientation st: one key word.  hd / hn: the Hilbert tables
+// (k_keys: its copy in LDS; key_low_word: the constant tables).
+template <bool kHilbert, typename TD, typename TN>
+__device__ __forceinline__ uint64_t key_word(double px, double py, double pz, double &cx, double &cy, double &cz, double &hs,
+                                             unsigned &st, const TD *hd, const TN *hn) {
+    uint64_t kk = 0;
+    for (int l = 0; l < 21; l++) {
+        const double q = hs * 0.5;
+        const bool bx = px >= cx, by = py >= cy, bz = pz >= cz;
+        cx = bx ? cx + q : cx - q;
+        cy = by ? cy + q : cy - q;
+        cz = bz ? cz + q : cz - q;
+        hs = q;
+        const unsigned oct = (bx ? 1u : 0u) | (by ? 2u : 0u) | (bz ? 4u : 0u);
+        if (kHilbert) {
+            kk = (kk << 3) | (uint64_t)((hd[st] >> (3u * oct)) & 7u);
+            st = (unsigned)(hn[st] >> (5u * oct)) & 31u;
+        } else {
+            kk = (kk << 3) | (uint64_t)oct;
+        }
+    }
+    return kk;
+}
+
+// The low key word (levels 22 - 42) of one body, recomputed from its float64 position: the lean stepping build
+// (k_keys<., true>) does not store it, and the three places that read it - members of a tie run whose upper words
+// agree (k_tiefix), neighbours with equal upper words (k_gather_scan), cells below level 21 that reach beyond their
+// tile (k_emit_tile) - meet such bodies essentially never (two bodies inside one cell of edge 2 bounds / 2^21).  The
+// same recurrence, the same tables, the same bounds as k_keys: the same bits.
+__device__ __noinline__ uint64_t key_low_word(bool hilbert, double px, double py, double pz, double bounds) {
+    double cx = 0.0, cy = 0.0, cz = 0.0, hs = bounds;
+    unsigned st = 0u;
+    if (hilbert) {
+        (void)key_word<true>(px, py, pz, cx, cy, cz, hs, st, nbmi::kHilDigit, nbmi::kHilNext);
+        return key_word<true>(px, py, pz, cx, cy, cz, hs, st, nbmi::kHilDigit, nbmi::kHilNext);
+    }
+    (void)key_word<false>(px, py, pz, cx, cy, cz, hs, st, nbmi::kHilDigit, nbmi::kHilNext);
+    return key_word<false>(px, py, pz, cx, cy, cz, hs, st, nbmi::kHilDigit, nbmi::kHilNext);
+}
+// where the low word of body b comes from: the stored array, or (lean build: key_lo == null) the position
+__device__ __forceinline__ uint64_t low_word_of(const uint64_t *__restrict__ key_lo, const Bodies &cur, uint32_t b, int hilbert,
+                                                const TreeInfo *info) {
+    return key_lo ? key_lo[b] : key_low_word(hilbert != 0, cur.x[b], cur.y[b], cur.z[b], info->bounds);
+}
+
+// kLean: the upper word only, 21 levels, key_lo not written (the stepping build of a plain handle)
+template <bool kHilbert, bool kLean = false>
 __global__ __launch_bounds__(kBlock) void k_keys(const double *__restrict__ x, const double *__restrict__ y,
                                                  const double *__restrict__ z, int64_t n, TreeInfo *info,
                                                  uint64_t *__restrict__ key_hi, uint64_t *__restrict__ key_lo,
-                                                 uint32_t *__restrict__ idx, const uint8_t *__restrict__ dead = nullptr) {
+                                                 uint32_t *__restrict__ idx, const uint8_t *__restrict__ dead = nullptr,
+                                                 uint64_t *__restrict__ packed = nullptr, int shift = 0) {
     __shared__ uint32_t hd[nbmi::kHilStates];
     __shared__ uint64_t hn[nbmi::kHilStates];
     if (kHilbert) {
@@ -258,29 +310,15 @@ __global__ __launch_bounds__(kBlock) void k_keys(const double *__restrict__ x, c
     double cx = 0.0, cy = 0.0, cz = 0.0, hs = bounds;
     uint64_t k[2];
     unsigned st = 0u;  // orientation of the current cell (root: 0)
-#pragma unroll
-    for (int w = 0; w < 2; w++) {
-        uint64_t kk = 0;
-        for (int l = 0; l < 21; l++) {
-            const double q = hs * 0.5;
-            const bool bx = px >= cx, by = py >= cy, bz = pz >= cz;
-            cx = bx ? cx + q : cx - q;
-            cy = by ? cy + q : cy - q;
-            cz = bz ? cz + q : cz - q;
-            hs = q;
-            const unsigned oct = (bx ? 1u : 0u) | (by ? 2u : 0u) | (bz ? 4u : 0u);
-            if (kHilbert) {
-                kk = (kk << 3) | (uint64_t)((hd[st] >> (3u * oct)) & 7u);
-                st = (unsigned)(hn[st] >> (5u * oct)) & 31u;
-            } else {
-                kk = (kk << 3) | (uint64_t)oct;
-            }
-        }
-        k[w] = kk;
-    }
+    k[0] = key_word<kHilbert>(px, py, pz, cx, cy, cz, hs, st, hd, hn);
     key_hi[i] = k[0];
-    key_lo[i] = k[1];
-    idx[i] = (uint32_t)i;
+    if (!kLean) {
+        k[1] = key_word<kHilbert>(px, py, pz, cx, cy, cz, hs, st, hd, hn);
+        key_lo[i] = k[1];
+    }
+    // packed sort (enqueue_local_sort): the sorted prefix with the body index below it, ONE word for the keys-only sort
+    if (packed) packed[i] = ((k[0] >> shift) << kPackIdxBits) | (uint64_t)i;
+    else idx[i] = (uint32_t)i;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -293,18 +331,28 @@ __global__ __launch_bounds__(kBlock) void k_keys(const double *__restrict__ x, c
 // about a millisecond (a one-thread insertion sort of it took minutes).  Equal keys keep the input order
 // (the sort is stable and idx ascends), like the reference's insertion order.  Writes the final
 // permutation and the fully sorted upper words; the longest run is recorded so that the host can widen
-// the sorted prefix for the following steps.
+// the sorted prefix for the following steps (and the stepping build goes back to full keys: a lean build
+// recomputes the low words of a run's members, key_low_word, which is for runs of a few bodies).
 // ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void k_tiefix(const uint64_t *__restrict__ hi_s, const uint64_t *__restrict__ key_lo,
+// kPacked: `srt` holds the sorted PACKED words (k_keys) instead of the sorted upper words, and there is no `perm`: the
+// body is the word's low 24 bits, the prefix the bits above them, and the full upper word comes from key_hi[body]
+// (the unsorted array; nearly sequential, the state being kept in last step's order).  Same perm_out / hi_out / max_run.
+template <bool kPacked>
+__global__ __launch_bounds__(kBlock) void k_tiefix(const uint64_t *__restrict__ srt, const uint64_t *__restrict__ key_hi,
+                                                   const uint64_t *__restrict__ key_lo,
                                                    const uint32_t *__restrict__ perm, int shift,
                                                    uint32_t *__restrict__ perm_out, uint64_t *__restrict__ hi_out, int64_t n,
-                                                   TreeInfo *info, const int32_t *__restrict__ dead_rank = nullptr,
-                                                   int64_t n_dead = 0) {
+                                                   TreeInfo *info, Bodies cur, int hilbert,
+                                                   const int32_t *__restrict__ dead_rank = nullptr, int64_t n_dead = 0) {
     const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (r >= n) return;
-    const uint64_t h = hi_s[r], hp = h >> shift;
-    const uint32_t p = perm[r];
-    if (dead_rank && h == ~0ull) {
+    // sorted prefix / body / full upper word of rank t
+    auto prefix = [&](int64_t t) { return kPacked ? srt[t] >> kPackIdxBits : srt[t] >> shift; };
+    auto body = [&](int64_t t) { return kPacked ? (uint32_t)(srt[t] & kPackIdxMask) : perm[t]; };
+    auto upper = [&](int64_t t, uint32_t b) { return kPacked ? key_hi[b] : srt[t]; };
+    const uint32_t p = body(r);
+    const uint64_t h = upper(r, p), hp = prefix(r);
+    if (!kPacked && dead_rank && h == ~0ull) {
         // owner mode: the row of a body that has left (all-ones key, larger than any real one): the n_dead of them
         // take the last n_dead places, in row order - no run to search, however many there are
         const int64_t slot = n - n_dead + dead_rank[p];
@@ -312,7 +360,7 @@ __global__ __launch_bounds__(kBlock) void k_tiefix(const uint64_t *__restrict__ 
         hi_out[slot] = h;
         return;
     }
-    const bool tie = (r + 1 < n && (hi_s[r + 1] >> shift) == hp) || (r > 0 && (hi_s[r - 1] >> shift) == hp);
+    const bool tie = (r + 1 < n && prefix(r + 1) == hp) || (r > 0 && prefix(r - 1) == hp);
     if (!tie) {
         perm_out[r] = p;
         hi_out[r] = h;
@@ -323,34 +371,38 @@ __global__ __launch_bounds__(kBlock) void k_tiefix(const uint64_t *__restrict__ 
     for (;;) {  // backwards
         const int64_t t = r - step;
         if (t < 0) { lo_bad = -1; break; }
-        if ((hi_s[t] >> shift) == hp) { lo_ok = t; step <<= 1; } else { lo_bad = t; break; }
+        if (prefix(t) == hp) { lo_ok = t; step <<= 1; } else { lo_bad = t; break; }
     }
     while (lo_ok - lo_bad > 1) {
         const int64_t mid = lo_bad + ((lo_ok - lo_bad) >> 1);
-        if ((hi_s[mid] >> shift) == hp) lo_ok = mid; else lo_bad = mid;
+        if (prefix(mid) == hp) lo_ok = mid; else lo_bad = mid;
     }
     int64_t hi_ok = r, hi_bad;
     step = 1;
     for (;;) {  // forwards
         const int64_t t = r + step;
         if (t >= n) { hi_bad = n; break; }
-        if ((hi_s[t] >> shift) == hp) { hi_ok = t; step <<= 1; } else { hi_bad = t; break; }
+        if (prefix(t) == hp) { hi_ok = t; step <<= 1; } else { hi_bad = t; break; }
     }
     while (hi_bad - hi_ok > 1) {
         const int64_t mid = hi_ok + ((hi_bad - hi_ok) >> 1);
-        if ((hi_s[mid] >> shift) == hp) hi_ok = mid; else hi_bad = mid;
+        if (prefix(mid) == hp) hi_ok = mid; else hi_bad = mid;
     }
     const int64_t s = lo_ok, e = hi_bad;
-    if (r == s && e - s > 64 && !(dead_rank && hi_s[e - 1] == ~0ull)) atomicMax(&info->max_run, (int)(e - s < 0x7fffffff ? e - s : 0x7fffffff));
-    const uint64_t la = key_lo[p];
+    if (r == s && e - s > 64 && !(!kPacked && dead_rank && srt[e - 1] == ~0ull)) atomicMax(&info->max_run, (int)(e - s < 0x7fffffff ? e - s : 0x7fffffff));
+    // key_lo == null (lean build): the low words are recomputed, and only once a member with this upper word shows up
+    uint64_t la = key_lo ? key_lo[p] : 0ull;
+    bool have_la = key_lo != nullptr;
     int64_t before = 0;
     for (int64_t j = s; j < e; j++) {
-        const uint64_t hj = hi_s[j];
-        const uint32_t pj = perm[j];
+        const uint32_t pj = body(j);
+        const uint64_t hj = upper(j, pj);
         if (hj != h) {
             before += hj < h ? 1 : 0;
         } else {
-            const uint64_t lj = key_lo[pj];
+            if (pj == p) continue;
+            if (!have_la) { la = low_word_of(key_lo, cur, p, hilbert, info); have_la = true; }
+            const uint64_t lj = low_word_of(key_lo, cur, pj, hilbert, info);
             before += (lj < la || (lj == la && pj < p)) ? 1 : 0;
         }
     }
@@ -420,6 +472,7 @@ __device__ __forceinline__ float dpp_f(float v) {
 }
 __device__ __forceinline__ float add_f(float a, float b) { return a + b; }
 
+template <bool kLean>
 __global__ __launch_bounds__(kBlock) void k_gather_scan(Bodies cur, const uint32_t *__restrict__ perm,
                                                         const uint64_t *__restrict__ hi_s, const uint64_t *__restrict__ key_lo,
                                                         int64_t n, double G, float4 *__restrict__ posm_s,
@@ -427,7 +480,10 @@ __global__ __launch_bounds__(kBlock) void k_gather_scan(Bodies cur, const uint32
                                                         int32_t *__restrict__ delta, double4 *__restrict__ S,
                                                         int32_t *__restrict__ PexL, double4 *__restrict__ sub_tot,
                                                         int32_t *__restrict__ sub_cnt, unsigned char *__restrict__ wave_flag,
-                                                        int32_t *__restrict__ sub_flag, float dens_thr, float edge_floor) {
+                                                        int32_t *__restrict__ sub_flag, float dens_thr, float edge_floor,
+                                                        const TreeInfo *__restrict__ info, int hilbert) {
+    // kLean (lean build; key_lo and lo_s are null): no low word is gathered or stored; the rare neighbours with equal
+    // upper words get theirs from key_low_word
     __shared__ Mom4 wtot[kBlock / 64];
     __shared__ int wflag[kBlock / 64];
     int nflag = 0;  // (thread 0) waves of this tile whose density asks for float64 forces
@@ -450,11 +506,19 @@ __global__ __launch_bounds__(kBlock) void k_gather_scan(Bodies cur, const uint32
             posm_s[r] = make_float4((float)x, (float)y, (float)z, (float)gm);
             if (p64_s) p64_s[r] = make_double4(x, y, z, gm);
             h = hi_s[r];
-            l = key_lo[j];
-            lo_s[r] = l;
+            if (!kLean) {
+                l = key_lo[j];
+                lo_s[r] = l;
+            }
             if (r + 1 < n) {
                 const uint64_t hn = hi_s[r + 1];
-                d = cpl_digits(h, l, hn, hn == h ? key_lo[perm[r + 1]] : 0ull);
+                uint64_t ln = 0ull;
+                uint64_t lr = l;
+                if (hn == h) {
+                    if (kLean) lr = low_word_of(nullptr, cur, j, hilbert, info);
+                    ln = kLean ? low_word_of(nullptr, cur, perm[r + 1], hilbert, info) : key_lo[perm[r + 1]];
+                }
+                d = cpl_digits(h, lr, hn, ln);
             }
             delta[r] = d;
             v = Mom4{gm, gm * x, gm * y, gm * z, 0};
@@ -495,7 +559,12 @@ __global__ __launch_bounds__(kBlock) void k_gather_scan(Bodies cur, const uint32
             int dp = -1;
             if (r > 0 && r < n) {
                 const uint64_t hp = hi_s[r - 1];
-                dp = cpl_digits(hp, hp == h ? key_lo[perm[r - 1]] : 0ull, h, l);
+                uint64_t lp = 0ull, lr = l;
+                if (hp == h) {
+                    if (kLean) lr = low_word_of(nullptr, cur, perm[r], hilbert, info);
+                    lp = kLean ? low_word_of(nullptr, cur, perm[r - 1], hilbert, info) : key_lo[perm[r - 1]];
+                }
+                dp = cpl_digits(hp, lp, h, lr);
             }
             dl[0] = dp;
         }
@@ -684,7 +753,7 @@ __global__ __launch_bounds__(kBlock) void k_emit_tile(const int32_t *__restrict_
                                                       Node64 *__restrict__ nodes64, uint8_t *__restrict__ node_level,
                                                       int32_t *__restrict__ node_ref, double4 *__restrict__ diag64,
                                                       NodeD *__restrict__ nodesd /* may be null */, Bodies cur,
-                                                      const uint32_t *__restrict__ perm, double G, TreeInfo *info,
+                                                      const uint32_t *__restrict__ perm, double G, TreeInfo *info, int hilbert,
                                                       int64_t link_base /* owner mode: the arrays passed in begin at this row of
                                                                            the walk array, and the links count from ITS start */) {
     __shared__ uint8_t tree[2 * TILE];   // heap: tree[TILE + i] = delta[base + i] + 1, inner nodes = min of children
@@ -802,17 +871,26 @@ __global__ __launch_bounds__(kBlock) void k_emit_tile(const int32_t *__restrict_
                 e = base + (int64_t)(h - (unsigned)TILE) + 1;
             } else {
                 // the cell reaches beyond the tile: gallop + binary search on the sorted keys from the tile's end on
-                const uint64_t kh = hi_s[r], kl = lo_s[r];
+                // (lo_s == null, lean build: a low word matters only to a cell below level 21 and only where the upper
+                // words agree; it is recomputed there)
+                const uint64_t kh = hi_s[r];
+                const bool deep = lev > 21;
+                const uint64_t kl = lo_s ? lo_s[r] : (deep ? low_word_of(nullptr, cur, perm[r], hilbert, info) : 0ull);
+                auto reaches = [&](int64_t u) {
+                    const uint64_t hu = hi_s[u];
+                    const uint64_t lu = lo_s ? lo_s[u] : (deep && hu == kh ? low_word_of(nullptr, cur, perm[u], hilbert, info) : 0ull);
+                    return cpl_digits(kh, kl, hu, lu) >= lev;
+                };
                 int64_t ok = base + TILE - 1, bad, step = 1;
                 for (;;) {
                     const int64_t u = ok + step;
                     if (u >= n) { bad = n; break; }
-                    if (cpl_digits(kh, kl, hi_s[u], lo_s[u]) >= lev) { ok = u; step <<= 1; }
+                    if (reaches(u)) { ok = u; step <<= 1; }
                     else { bad = u; break; }
                 }
                 while (bad - ok > 1) {
                     const int64_t mid = ok + ((bad - ok) >> 1);
-                    if (cpl_digits(kh, kl, hi_s[mid], lo_s[mid]) >= lev) ok = mid; else bad = mid;
+                    if (reaches(mid)) ok = mid; else bad = mid;
                 }
                 e = bad;
             }
@@ -4077,6 +4155,13 @@ struct nbmi_sim {
     hipEvent_t ev_walked = nullptr, ev_cut = nullptr;
     bool cut_pending = false;         // a k_xcd_bounds on `side` that the next balanced walk has to wait for
     int walk_block = kBlock;  // threads per walk block (64, 128 or 256; measurement knob NBMI_WALK_BLOCK)
+    bool keys_lean = true;    // the stepping build (enqueue_tree(..., aux = false) of a plain handle) computes and stores
+                              // the upper key word only (key_low_word); NBMI_KEYS_LEAN=0: full keys.  Dropped for good
+                              // once a long run shows up (synchronise): every member of a run recomputes the others' words
+    bool lean_build = false;  // the build being enqueued / the last one built is lean: key_lo and lo_s do not hold it
+    bool sort_packed = true;  // sort ONE packed word (prefix << 24 | body index) with the keys-only sort where it fits
+                              // (packed_sort_ok); NBMI_SORT_PACKED=0: always (key, index) pairs
+    uint64_t *packed = nullptr, *packed_s = nullptr;  // the packed words of k_keys and their sorted order
     int sort_bits = 0;   // upper-word bits the radix sort looks at (0: chosen from n; NBMI_SORT_BITS); widened when long runs show up
     bool maxabs_fused = false;  // TreeInfo::maxabs_next holds max |coordinate| of the CURRENT positions (set by a full
                                 // integrating walk, dropped by anything else that writes positions); NBMI_FUSE_MAXABS=0: never
@@ -4219,14 +4304,22 @@ int enqueue_maxabs(nbmi_sim *s) {
 // force precision "auto" is decided during the build of a step (it needs dt); anything else leaves the flags alone
 static inline bool auto_prec(const nbmi_sim *s) { return s->nodesd && s->force_prec == 0 && s->step_dt > 0.0; }
 
-int enqueue_local_sort(nbmi_sim *s, int ev_base, int64_t n_sort = -1, int64_t n_live = -1, const uint8_t *dead = nullptr) {
+// Whether a local sort can take the packed, keys-only form: the prefix fits above the index (a prefix widened past 40
+// bits by long runs does not), every index fits in 24 bits, and there are no dead rows (owner mode: their all-ones key
+// needs one bit more than the prefix).  Everything else sorts (key, index) pairs as before.
+static inline bool packed_sort_ok(const nbmi_sim *s, int64_t n, const uint8_t *dead) {
+    return s->sort_packed && s->packed && s->sort_bits <= kPackMaxSortBits && n <= ((int64_t)1 << kPackIdxBits) && !dead;
+}
+
+int enqueue_local_sort(nbmi_sim *s, int ev_base, int64_t n_sort = -1, int64_t n_live = -1, const uint8_t *dead = nullptr,
+                       bool lean = false) {
+    s->lean_build = lean;
+    const uint64_t *key_lo = lean ? nullptr : s->key_lo;  // what the tie-fix and the gather read
+    const int hil = s->hilbert ? 1 : 0;
     const int64_t n = n_sort < 0 ? s->n : n_sort;
     if (n_live < 0) n_live = n;
     hipStream_t st = s->stream;
     Bodies cur = s->buf[s->curbuf];
-    if (s->hilbert) k_keys<true><<<nblocks(n), kBlock, 0, st>>>(cur.x, cur.y, cur.z, n, s->info, s->key_hi, s->key_lo, s->idx, dead);
-    else k_keys<false><<<nblocks(n), kBlock, 0, st>>>(cur.x, cur.y, cur.z, n, s->info, s->key_hi, s->key_lo, s->idx, dead);
-    if (ev_base >= 0) NBMI_HIP_CHECK(hipEventRecord(s->ev[1], st));
     // radix sort on the top sort_bits bits of the upper word, then the tie-fix completes the 126-bit order
     if (s->sort_bits == 0) {
         // enough levels that cells of that level hold about one body on average, plus four: 3 (log8 n + 4) bits,
@@ -4239,21 +4332,43 @@ int enqueue_local_sort(nbmi_sim *s, int ev_base, int64_t n_sort = -1, int64_t n_
         s->sort_bits = bits < 63 ? bits : 63;
     }
     const int shift = 63 - s->sort_bits;
-    NBMI_HIP_CHECK(nbmi::sort_pairs_u64_u32(s->tmp_sort, s->tmp_sort_bytes, s->key_hi, s->hi_s, s->idx, s->perm,
-                                            (size_t)n, shift, 63, st));
-    k_tiefix<<<nblocks(n), kBlock, 0, st>>>(s->hi_s, s->key_lo, s->perm, shift, s->idx, s->key_hi, n, s->info,
-                                            dead ? s->let_scan : nullptr, n - n_live);
-    // the finished permutation / sorted upper words are `perm` / `hi_s` from here on; the old buffers take
-    // the next step's indices and keys
-    std::swap(s->perm, s->idx);
-    std::swap(s->hi_s, s->key_hi);
+    const bool packed = packed_sort_ok(s, n, dead);
+    uint64_t *pk = packed ? s->packed : nullptr;
+#define NBMI_KEYS(H, L) k_keys<H, L><<<nblocks(n), kBlock, 0, st>>>(cur.x, cur.y, cur.z, n, s->info, s->key_hi, s->key_lo, s->idx, dead, pk, shift)
+    if (s->hilbert && lean) NBMI_KEYS(true, true);
+    else if (s->hilbert) NBMI_KEYS(true, false);
+    else if (lean) NBMI_KEYS(false, true);
+    else NBMI_KEYS(false, false);
+#undef NBMI_KEYS
+    if (ev_base >= 0) NBMI_HIP_CHECK(hipEventRecord(s->ev[1], st));
+    if (packed) {
+        // one 8-byte word per body through the passes instead of an 8-byte key and a 4-byte index: the index sits
+        // below the prefix, so a stable sort of the pairs and a sort of the words on the prefix bits give the same order
+        NBMI_HIP_CHECK(nbmi::sort_keys_u64(s->tmp_sort, s->tmp_sort_bytes, s->packed, s->packed_s, (size_t)n, kPackIdxBits,
+                                           kPackIdxBits + s->sort_bits, st));
+        // the tie-fix reads the unsorted key_hi, so it writes where the pair sort would have put its output: `perm` /
+        // `hi_s` are final without a swap
+        k_tiefix<true><<<nblocks(n), kBlock, 0, st>>>(s->packed_s, s->key_hi, key_lo, nullptr, shift, s->perm, s->hi_s, n, s->info, cur, hil);
+    } else {
+        NBMI_HIP_CHECK(nbmi::sort_pairs_u64_u32(s->tmp_sort, s->tmp_sort_bytes, s->key_hi, s->hi_s, s->idx, s->perm,
+                                                (size_t)n, shift, 63, st));
+        k_tiefix<false><<<nblocks(n), kBlock, 0, st>>>(s->hi_s, nullptr, key_lo, s->perm, shift, s->idx, s->key_hi, n, s->info, cur, hil,
+                                                       dead ? s->let_scan : nullptr, n - n_live);
+        // the finished permutation / sorted upper words are `perm` / `hi_s` from here on; the old buffers take
+        // the next step's indices and keys
+        std::swap(s->perm, s->idx);
+        std::swap(s->hi_s, s->key_hi);
+    }
     s->t_hi = s->hi_s;
     if (ev_base >= 0) NBMI_HIP_CHECK(hipEventRecord(s->ev[2], st));
     // ranks 0 .. n_live: entry n_live is the slot of the totals
-    k_gather_scan<<<(int)((n_live + 1 + kScanTile - 1) / kScanTile), kBlock, 0, st>>>(
-        cur, s->perm, s->hi_s, s->key_lo, n_live, s->G, s->posm_s, s->p64_s, s->lo_s, s->delta, s->S, s->Pex, s->sub_tot, s->sub_cnt,
-        auto_prec(s) ? s->wave_flag : nullptr, s->sub_flag, auto_prec(s) ? (float)(s->prec_tau / (s->step_dt * s->step_dt)) : 0.f,
-        (float)s->softening);
+#define NBMI_GATHER(L) k_gather_scan<L><<<(int)((n_live + 1 + kScanTile - 1) / kScanTile), kBlock, 0, st>>>(                      \
+        cur, s->perm, s->hi_s, key_lo, n_live, s->G, s->posm_s, s->p64_s, lean ? nullptr : s->lo_s, s->delta, s->S, s->Pex, s->sub_tot, s->sub_cnt, \
+        auto_prec(s) ? s->wave_flag : nullptr, s->sub_flag, auto_prec(s) ? (float)(s->prec_tau / (s->step_dt * s->step_dt)) : 0.f, \
+        (float)s->softening, s->info, hil)
+    if (lean) NBMI_GATHER(true);
+    else NBMI_GATHER(false);
+#undef NBMI_GATHER
     return 0;
 }
 
@@ -4278,10 +4393,10 @@ int enqueue_global_tree(nbmi_sim *s, bool aux = true, double4 *diag = nullptr) {
     {
         const int tile = n <= kEmitSmallBodies ? kEmitTileSmall : kEmitTile;
 #define NBMI_EMIT(TV) k_emit_tile<TV><<<(int)((n + TV - 1) / TV), kBlock, 0, st>>>(                                         \
-        s->delta, s->Pex, s->subPex, s->S, s->T, s->t_posm, s->p64_s, s->t_hi, s->t_lo, n, s->own_node_rows, s->softening,       \
+        s->delta, s->Pex, s->subPex, s->S, s->T, s->t_posm, s->p64_s, s->t_hi, s->lean_build ? nullptr : s->t_lo, n, s->own_node_rows, s->softening,       \
         inv_theta2, s->nodes + ob, s->nodes64 + ob, aux ? s->node_level : nullptr, aux ? s->node_ref : nullptr,              \
         diag ? diag : s->diag64,                                                                                            \
-        s->force_prec != 1 && s->nodesd ? s->nodesd + ob : nullptr, s->buf[s->curbuf], s->perm, s->G, s->info, ob)
+        s->force_prec != 1 && s->nodesd ? s->nodesd + ob : nullptr, s->buf[s->curbuf], s->perm, s->G, s->info, s->hilbert ? 1 : 0, ob)
         if (tile == kEmitTileSmall) NBMI_EMIT(kEmitTileSmall);
         else NBMI_EMIT(kEmitTile);
 #undef NBMI_EMIT
@@ -4301,14 +4416,17 @@ int enqueue_global_tree(nbmi_sim *s, bool aux = true, double4 *diag = nullptr) {
 
 // Single-GPU build: the tree over the handle's own bodies.  ev_base: -1 untimed, 0 timed, 1 timed with the phase's first
 // event already recorded by the caller (a leapfrog step: its k_kick_drift counts as the bounds phase)
-int enqueue_tree(nbmi_sim *s, int ev_base, bool aux = true, double4 *diag = nullptr) {
+// step: the build of a step (the lean key form may serve it: nothing reads its keys afterwards)
+int enqueue_tree(nbmi_sim *s, int ev_base, bool aux = true, double4 *diag = nullptr, bool step = false) {
     if (s->owner) {
         nbmi::set_error("this handle is in owner mode: use the nbmi_owner_* calls");
         return NBMI_ERR_ARG;
     }
     if (ev_base == 0) NBMI_HIP_CHECK(hipEventRecord(s->ev[0], s->stream));
     if (int rc = enqueue_maxabs(s)) return rc;
-    if (int rc = enqueue_local_sort(s, ev_base)) return rc;
+    // a step's build (no queries on it: aux = false) needs no stored low key word; the quadrupole build is one with aux
+    const bool lean = s->keys_lean && step && !aux && s->multipole != NBMI_MULTIPOLE_QUADRUPOLE;
+    if (int rc = enqueue_local_sort(s, ev_base, -1, -1, nullptr, lean)) return rc;
     if (int rc = enqueue_global_tree(s, aux, diag)) return rc;
     if (ev_base >= 0) NBMI_HIP_CHECK(hipEventRecord(s->ev[3], s->stream));
     s->tree_valid = aux || s->multipole == NBMI_MULTIPOLE_QUADRUPOLE;  // (a quadrupole build always writes node_ref / node_level)
@@ -4528,7 +4646,7 @@ int leap_prepare(nbmi_sim *s, double dt) {
     if (s->acc_valid) return 0;
     if (s->method == NBMI_METHOD_BARNES_HUT) {
         s->step_dt = dt;
-        const int rc_tree = enqueue_tree(s, -1, false);
+        const int rc_tree = enqueue_tree(s, -1, false, nullptr, true);
         s->step_dt = 0.0;
         if (rc_tree) return rc_tree;
         if (int rc = enqueue_walk(s, true, dt, nullptr, kLeapPrime)) return rc;
@@ -4572,6 +4690,8 @@ int check_device_error(nbmi_sim *s) {
         // rest correctly but at L reads per member - sort on more bits from the next step on
         s->sort_bits = s->sort_bits + 8 < 63 ? s->sort_bits + 8 : 63;
     }
+    if (h.max_run > 4096) s->keys_lean = false;  // (a long run may be one in the whole upper word, where every member
+                                                 // recomputes the others' low words: full keys from now on)
     if (h.error || h.sticky_error) {
         // reported once: clear the sticky word so the handle can go on after nbmi_set_state / a retry.  The
         // bodies stand at the last step that completed (the walk froze them while the word was set).
@@ -4652,6 +4772,8 @@ static void read_env_knobs(nbmi_sim *s) {
     if (const char *e = getenv("NBMI_WALK_PAIR")) s->walk_pair = atoi(e);
     if (const char *e = getenv("NBMI_FUSE_MAXABS")) s->fuse_maxabs = atoi(e) != 0;
     if (const char *e = getenv("NBMI_HILBERT")) s->hilbert = atoi(e) != 0;
+    if (const char *e = getenv("NBMI_SORT_PACKED")) s->sort_packed = atoi(e) != 0;
+    if (const char *e = getenv("NBMI_KEYS_LEAN")) s->keys_lean = atoi(e) != 0;
     if (const char *e = getenv("NBMI_WALK_LANE")) s->walk_lane = atoi(e);
     if (const char *e = getenv("NBMI_WALK_STACK")) s->walk_stack = atoi(e);
     if (const char *e = getenv("NBMI_FORCE_PREC")) {
@@ -4696,7 +4818,8 @@ static int create_impl(nbmi_sim *s, const double *pos, const double *vel, const 
         s->node_capacity = node_rows_for(c) + s->node_extra;
         const int64_t own_rows = node_rows_for(c);
         if (dev_alloc(s, &s->key_hi, c) || dev_alloc(s, &s->key_lo, c) || dev_alloc(s, &s->hi_s, c) ||
-            dev_alloc(s, &s->lo_s, c) || ((s->owner || s->prec) && dev_alloc(s, &s->p64_s, c)) || dev_alloc(s, &s->idx, c) ||
+            dev_alloc(s, &s->lo_s, c) ||
+            (s->sort_packed && !s->owner && (dev_alloc(s, &s->packed, c) || dev_alloc(s, &s->packed_s, c))) || ((s->owner || s->prec) && dev_alloc(s, &s->p64_s, c)) || dev_alloc(s, &s->idx, c) ||
             dev_alloc(s, &s->perm, c) || dev_alloc(s, &s->delta, c) || dev_alloc(s, &s->Pex, c + 1) ||
             dev_alloc(s, &s->S, c + 1) || dev_alloc(s, &s->sub_tot, (c + 1) / kScanTile + 2) ||
             dev_alloc(s, &s->sub_cnt, (c + 1) / kScanTile + 2) || dev_alloc(s, &s->subPex, (c + 1) / kScanTile + 2) ||
@@ -4866,7 +4989,7 @@ int nbmi_step(nbmi_sim *s, double dt, int substeps) {
                 if (int rc = enqueue_kick_drift(s, dt)) return rc;
                 s->maxabs_fused = true;  // k_kick_drift has published max |x'|
                 s->step_dt = dt;
-                int rc = enqueue_tree(s, s->timers ? 1 : -1, false);
+                int rc = enqueue_tree(s, s->timers ? 1 : -1, false, nullptr, true);
                 s->step_dt = 0.0;
                 if (rc == 0) rc = enqueue_walk(s, true, dt, nullptr, kLeapClose);
                 s->curbuf ^= 1;
@@ -4876,7 +4999,7 @@ int nbmi_step(nbmi_sim *s, double dt, int substeps) {
                 }
             } else {
                 s->step_dt = dt;
-                const int rc_tree = enqueue_tree(s, evb, false);
+                const int rc_tree = enqueue_tree(s, evb, false, nullptr, true);
                 s->step_dt = 0.0;
                 if (rc_tree) return rc_tree;
                 if (int rc = enqueue_walk(s, true, dt, nullptr)) return rc;

@@ -1,19 +1,24 @@
-// Hand-written device radix sort of (key, 32-bit value) pairs for gfx950: the octant-path keys of the
-// octree build (63-bit key word + body index) and the boids' 24-bit cell indices.
+// Hand-written device radix sort for gfx950, in two forms: (key, 32-bit value) pairs - the boids' 24-bit cell indices,
+// the octree build's 63-bit key word + body index where the packed form does not fit - and bare keys sorted on a bit
+// field [begin_bit, end_bit), the bits outside it travelling along: the octree build's packed word (sorted key prefix
+// << 24 | body index), which moves 8 bytes per body and pass in each direction instead of 12 and reorders the tile in
+// LDS once instead of twice.
 //
 // Least-significant-digit first, 8-bit digits, ONE kernel per pass ("onesweep"): a workgroup owns a tile of
 // 4 096 pairs, ranks them by digit with wave-level match operations (ballots), learns how many pairs of
 // each digit the tiles before it hold through a decoupled look-back over per-tile status words, reorders
 // the tile in LDS so that every digit's pairs leave as one contiguous run, and writes them to their final
 // place of this pass.  Stable.  Per pass every pair is read once and written once (24 B of traffic for a
-// u64 key + u32 value); the digit histograms of ALL passes come from one extra read of the keys up front.
+// u64 key + u32 value, 16 B for a bare u64 key); the digit histograms of ALL passes come from one extra read of the
+// keys up front.
 //
 // Look-back notes (gfx950: eight XCDs, L2s not coherent with each other): a status word carries flag and
 // count in ONE 32-bit granule and is written / polled with agent-scope relaxed atomics (sc1), so no
 // payload has to be ordered behind a flag.  Tile numbers come from an atomic ticket, so a tile only ever
-// waits for tiles whose workgroups are already running.  A tile inspects 8 predecessors per round trip
+// waits for tiles whose workgroups are already running.  A tile inspects kLookBatch = 8 predecessors per round trip
 // (their loads are issued together): with a whole grid starting at once the serial form would walk up to
-// `tiles` predecessors one memory round trip at a time.  Every spin is bounded; a timeout sets an error
+// `tiles` predecessors one memory round trip at a time.  Batches of 16 and 32 were measured and lose at 1 M keys
+// (profiles/build_lean_ab.txt).  Every spin is bounded; a timeout sets an error
 // word instead of hanging the GPU.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -32,7 +37,12 @@ constexpr int kItems = 16, kItemsMin = 4;   // pairs per thread: a workgroup's t
                                             // consecutive ones (template parameter of k_radix_pass; the status words are
                                             // sized for the smaller tile)
 constexpr unsigned kFlagAgg = 1u << 30, kFlagIncl = 2u << 30, kValueMask = (1u << 30) - 1;
-constexpr int kLookBatch = 8;
+// predecessors a tile inspects per look-back round trip (their loads are issued together and consumed in order);
+// a compile-time constant of the pass
+#ifndef NBMI_LOOK_BATCH
+#define NBMI_LOOK_BATCH 8
+#endif
+constexpr int kLookBatch = NBMI_LOOK_BATCH;
 constexpr int kMaxPasses = 8;
 
 struct Control {                 // lives at the start of the temp buffer
@@ -44,15 +54,21 @@ struct Control {                 // lives at the start of the temp buffer
     unsigned hist[kMaxPasses][kBins];  // global digit counts, then exclusive offsets
 };
 
+// dmask: 255, or fewer ones in the last pass of a field that is no whole number of digits wide
 template <typename K>
-__device__ __forceinline__ unsigned digit_of(K k, int shift) {
-    return (unsigned)(k >> shift) & (kBins - 1);
+__device__ __forceinline__ unsigned digit_of(K k, int shift, unsigned dmask) {
+    return (unsigned)(k >> shift) & dmask;
+}
+inline __host__ __device__ unsigned digit_mask(int bits, int pass) {
+    const int left = bits - pass * kRadixBits;
+    return left >= kRadixBits ? (unsigned)(kBins - 1) : (1u << left) - 1u;
 }
 
 // ---- digit histograms of all passes: one read of the keys ------------------------------------
 template <typename K>
-__global__ __launch_bounds__(kThreads) void k_radix_hist(const K *__restrict__ keys, int64_t n, int passes, int first_bit,
+__global__ __launch_bounds__(kThreads) void k_radix_hist(const K *__restrict__ keys, int64_t n, int bits, int first_bit,
                                                         Control *ctl) {
+    const int passes = (bits + kRadixBits - 1) / kRadixBits;
     __shared__ unsigned h[kMaxPasses][kBins];
     for (int i = threadIdx.x; i < kMaxPasses * kBins; i += kThreads) (&h[0][0])[i] = 0u;
     __syncthreads();
@@ -63,7 +79,7 @@ __global__ __launch_bounds__(kThreads) void k_radix_hist(const K *__restrict__ k
         // were LDS stalls).  A digit the whole wave agrees on is counted by one lane.
         const unsigned live = (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64(true));
         for (int p = 0; p < passes; p++) {
-            const unsigned d = digit_of(k, first_bit + p * kRadixBits);
+            const unsigned d = digit_of(k, first_bit + p * kRadixBits, digit_mask(bits, p));
             const unsigned d0 = __builtin_amdgcn_readfirstlane(d);
             if (__builtin_amdgcn_ballot_w64(d != d0) == 0ull) {
                 if (__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == 0u) atomicAdd(&h[p][d0], live);
@@ -99,10 +115,12 @@ __global__ __launch_bounds__(kBins) void k_radix_offsets(Control *ctl) {
 }
 
 // ---- one pass --------------------------------------------------------------------------------
-template <typename K, int ITEMS>
+// kPairs = false: the keys-only form (no vin / vout, no second trip through the reorder buffer, no slot registers) -
+// for keys that carry their value in the bits below the sorted field, like the octree build's packed word
+template <typename K, int ITEMS, bool kPairs, int LOOK = kLookBatch>
 __global__ __launch_bounds__(kThreads) void k_radix_pass(const K *__restrict__ kin, K *__restrict__ kout,
                                                         const uint32_t *__restrict__ vin, uint32_t *__restrict__ vout,
-                                                        int64_t n, int shift, int pass, Control *ctl,
+                                                        int64_t n, int shift, unsigned dmask, int pass, Control *ctl,
                                                         unsigned *__restrict__ status /* [tiles][256] of this pass */) {
     __shared__ unsigned s_tile;
     __shared__ unsigned cnt_w[kWaves][kBins];   // per-wave digit counts, then the wave's base inside the digit
@@ -124,7 +142,7 @@ __global__ __launch_bounds__(kThreads) void k_radix_pass(const K *__restrict__ k
     // a wave owns (64 * ITEMS) consecutive pairs and loads them 64 at a time (coalesced); the order inside
     // the tile is wave-major, then round, then lane
     K key[ITEMS];
-    uint32_t val[ITEMS];
+    uint32_t val[kPairs ? ITEMS : 1];
     unsigned rank[ITEMS];
     const int64_t wave_base = tile_base + (int64_t)w * (64 * ITEMS);
 #pragma unroll
@@ -132,14 +150,14 @@ __global__ __launch_bounds__(kThreads) void k_radix_pass(const K *__restrict__ k
         const int64_t idx = wave_base + i * 64 + lane;
         const bool ok = idx < n;
         key[i] = ok ? kin[idx] : (K)~(K)0;
-        val[i] = ok ? vin[idx] : 0u;
+        if (kPairs) val[i] = ok ? vin[idx] : 0u;
     }
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
 #pragma unroll
     for (int i = 0; i < ITEMS; i++) {
         const int64_t idx = wave_base + i * 64 + lane;
         const bool ok = idx < n;
-        const unsigned d = digit_of(key[i], shift);
+        const unsigned d = digit_of(key[i], shift, dmask);
         // lanes of this round with the same digit
         unsigned long long peers = __builtin_amdgcn_ballot_w64(ok);
 #pragma unroll
@@ -190,15 +208,15 @@ __global__ __launch_bounds__(kThreads) void k_radix_pass(const K *__restrict__ k
         unsigned spins = 0;
         bool done = false;
         while (!done) {
-            unsigned sw[kLookBatch];
+            unsigned sw[LOOK];
 #pragma unroll
-            for (int j = 0; j < kLookBatch; j++) {
+            for (int j = 0; j < LOOK; j++) {
                 const int q = p - j;
                 sw[j] = q >= 0 ? __hip_atomic_load(status + (size_t)q * kBins + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
                                : kFlagIncl;  // before tile 0: nothing
             }
 #pragma unroll
-            for (int j = 0; j < kLookBatch; j++) {
+            for (int j = 0; j < LOOK; j++) {
                 if (done) break;
                 const unsigned flag = sw[j] & ~kValueMask;
                 if (flag == 0u) {  // not published yet: poll again from this tile
@@ -217,29 +235,33 @@ __global__ __launch_bounds__(kThreads) void k_radix_pass(const K *__restrict__ k
     __syncthreads();
 
     // reorder inside the tile: digit runs, each in input order
-    unsigned slot[ITEMS / 2];  // two 16-bit slots per register
+    unsigned slot[kPairs ? ITEMS / 2 : 1];  // two 16-bit slots per register
 #pragma unroll
     for (int i = 0; i < ITEMS; i++) {
         const int64_t idx = wave_base + i * 64 + lane;
         unsigned q = 0;
         if (idx < n) {
-            const unsigned d = digit_of(key[i], shift);
+            const unsigned d = digit_of(key[i], shift, dmask);
             q = tile_off[d] + cnt_w[w][d] + rank[i];
             lds_k[q] = key[i];
         }
-        if (i & 1) slot[i >> 1] |= q << 16; else slot[i >> 1] = q;
+        if (kPairs) {
+            if (i & 1) slot[i >> 1] |= q << 16; else slot[i >> 1] = q;
+        }
     }
     __syncthreads();
-    unsigned dst[ITEMS];
+    unsigned dst[kPairs ? ITEMS : 1];
 #pragma unroll
     for (int i = 0; i < ITEMS; i++) {
         const int q = i * kThreads + t;
         if (q < valid_in_tile) {
             const K k = lds_k[q];
-            dst[i] = glob_off[digit_of(k, shift)] + (unsigned)q;
-            kout[dst[i]] = k;
+            const unsigned g = glob_off[digit_of(k, shift, dmask)] + (unsigned)q;
+            kout[g] = k;
+            if (kPairs) dst[i] = g;
         }
     }
+    if (!kPairs) return;
     __syncthreads();
     uint32_t *lds_v = reinterpret_cast<uint32_t *>(lds_k);
 #pragma unroll
@@ -259,21 +281,24 @@ inline int passes_for(int bits) { return (bits + kRadixBits - 1) / kRadixBits; }
 inline size_t tiles_for(size_t n, int items = kItemsMin) { return (n + (size_t)kThreads * items - 1) / ((size_t)kThreads * items); }
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
-template <typename K>
+// kPairs = false: the keys-only sort needs no value buffer
+template <typename K, bool kPairs = true>
 size_t temp_bytes(size_t n, int bits) {
     const int passes = passes_for(bits);
     return align256(sizeof(Control)) + align256((size_t)passes * tiles_for(n) * kBins * sizeof(unsigned)) +
-           align256(n * sizeof(K)) + align256(n * sizeof(uint32_t));
+           align256(n * sizeof(K)) + (kPairs ? align256(n * sizeof(uint32_t)) : 0);
 }
 
-template <typename K>
-hipError_t sort_pairs(void *temp, size_t temp_size, const K *kin, K *kout, const uint32_t *vin, uint32_t *vout,
-                      size_t n, int begin_bit, int end_bit, hipStream_t st) {
+// Sorts on the bits [begin_bit, end_bit) of the keys.  kPairs = false (sort_keys): vin / vout are not touched; the
+// bits outside the sorted field travel with their key, and keys equal in the field keep their input order.
+template <typename K, bool kPairs>
+hipError_t sort_impl(void *temp, size_t temp_size, const K *kin, K *kout, const uint32_t *vin, uint32_t *vout,
+                     size_t n, int begin_bit, int end_bit, hipStream_t st) {
     const int bits = end_bit - begin_bit;
     if (n == 0) return hipSuccess;
     if (n > (size_t)kValueMask) return hipErrorInvalidValue;  // counts travel in 30 bits
     const int passes = passes_for(bits);
-    if (passes < 1 || passes > kMaxPasses || temp_size < temp_bytes<K>(n, bits)) return hipErrorInvalidValue;
+    if (passes < 1 || passes > kMaxPasses || temp_size < temp_bytes<K, kPairs>(n, bits)) return hipErrorInvalidValue;
     char *base = (char *)temp;
     Control *ctl = (Control *)base;
     // [r4] pairs per thread by size (profiles/r04_small_systems.txt): a pass over few pairs is a chain of latencies, and
@@ -284,14 +309,14 @@ hipError_t sort_pairs(void *temp, size_t temp_size, const K *kin, K *kout, const
     unsigned *status = (unsigned *)(base + align256(sizeof(Control)));
     const size_t status_bytes = align256((size_t)passes * tiles_for(n) * kBins * sizeof(unsigned));
     K *ktmp = (K *)((char *)status + status_bytes);
-    uint32_t *vtmp = (uint32_t *)((char *)ktmp + align256(n * sizeof(K)));
+    uint32_t *vtmp = kPairs ? (uint32_t *)((char *)ktmp + align256(n * sizeof(K))) : nullptr;
     // everything but the sticky error word at the head of the control block
     hipError_t e = hipMemsetAsync(base + offsetof(Control, tile_ticket), 0,
                                   align256(sizeof(Control)) - offsetof(Control, tile_ticket) + status_bytes, st);
     if (e != hipSuccess) return e;
     int hb = (int)((n + kThreads * 8 - 1) / (kThreads * 8));
     if (hb > 1024) hb = 1024;
-    k_radix_hist<K><<<hb, kThreads, 0, st>>>(kin, (int64_t)n, passes, begin_bit, ctl);
+    k_radix_hist<K><<<hb, kThreads, 0, st>>>(kin, (int64_t)n, bits, begin_bit, ctl);
     k_radix_offsets<<<passes, kBins, 0, st>>>(ctl);
     // ping-pong so that the last pass writes the caller's output: ... -> tmp -> out
     const K *ksrc = kin;
@@ -301,18 +326,31 @@ hipError_t sort_pairs(void *temp, size_t temp_size, const K *kin, K *kout, const
         K *kdst = to_out ? kout : ktmp;
         uint32_t *vdst = to_out ? vout : vtmp;
         if (items == 4)
-            k_radix_pass<K, 4><<<(int)tiles, kThreads, 0, st>>>(ksrc, kdst, vsrc, vdst, (int64_t)n, begin_bit + p * kRadixBits, p, ctl,
+            k_radix_pass<K, 4, kPairs><<<(int)tiles, kThreads, 0, st>>>(ksrc, kdst, vsrc, vdst, (int64_t)n, begin_bit + p * kRadixBits, digit_mask(bits, p), p, ctl,
                                                                 status + (size_t)p * tiles * kBins);
         else if (items == 8)
-            k_radix_pass<K, 8><<<(int)tiles, kThreads, 0, st>>>(ksrc, kdst, vsrc, vdst, (int64_t)n, begin_bit + p * kRadixBits, p, ctl,
+            k_radix_pass<K, 8, kPairs><<<(int)tiles, kThreads, 0, st>>>(ksrc, kdst, vsrc, vdst, (int64_t)n, begin_bit + p * kRadixBits, digit_mask(bits, p), p, ctl,
                                                                 status + (size_t)p * tiles * kBins);
         else
-            k_radix_pass<K, 16><<<(int)tiles, kThreads, 0, st>>>(ksrc, kdst, vsrc, vdst, (int64_t)n, begin_bit + p * kRadixBits, p, ctl,
+            k_radix_pass<K, 16, kPairs><<<(int)tiles, kThreads, 0, st>>>(ksrc, kdst, vsrc, vdst, (int64_t)n, begin_bit + p * kRadixBits, digit_mask(bits, p), p, ctl,
                                                                  status + (size_t)p * tiles * kBins);
         ksrc = kdst;
         vsrc = vdst;
     }
     return hipGetLastError();
+}
+
+template <typename K>
+hipError_t sort_pairs(void *temp, size_t temp_size, const K *kin, K *kout, const uint32_t *vin, uint32_t *vout,
+                      size_t n, int begin_bit, int end_bit, hipStream_t st) {
+    return sort_impl<K, true>(temp, temp_size, kin, kout, vin, vout, n, begin_bit, end_bit, st);
+}
+
+template <typename K>
+hipError_t sort_keys(void *temp, size_t temp_size, const K *kin, K *kout, size_t n, int begin_bit, int end_bit,
+                     hipStream_t st) {
+    if (begin_bit < 0 || end_bit > (int)(8 * sizeof(K)) || begin_bit >= end_bit) return hipErrorInvalidValue;
+    return sort_impl<K, false>(temp, temp_size, kin, kout, nullptr, nullptr, n, begin_bit, end_bit, st);
 }
 
 }  // namespace
@@ -327,6 +365,16 @@ hipError_t radix_sort_pairs_u64(void *temp, size_t temp_size, const uint64_t *ki
 hipError_t radix_sort_pairs_u32(void *temp, size_t temp_size, const uint32_t *kin, uint32_t *kout, const uint32_t *vin,
                                 uint32_t *vout, size_t n, int begin_bit, int end_bit, hipStream_t s) {
     return sort_pairs<uint32_t>(temp, temp_size, kin, kout, vin, vout, n, begin_bit, end_bit, s);
+}
+size_t radix_keys_temp_bytes_u64(size_t n, int bits) { return temp_bytes<uint64_t, false>(n, bits); }
+size_t radix_keys_temp_bytes_u32(size_t n, int bits) { return temp_bytes<uint32_t, false>(n, bits); }
+hipError_t radix_sort_keys_u64(void *temp, size_t temp_size, const uint64_t *kin, uint64_t *kout, size_t n, int begin_bit,
+                               int end_bit, hipStream_t s) {
+    return sort_keys<uint64_t>(temp, temp_size, kin, kout, n, begin_bit, end_bit, s);
+}
+hipError_t radix_sort_keys_u32(void *temp, size_t temp_size, const uint32_t *kin, uint32_t *kout, size_t n, int begin_bit,
+                               int end_bit, hipStream_t s) {
+    return sort_keys<uint32_t>(temp, temp_size, kin, kout, n, begin_bit, end_bit, s);
 }
 // A freshly allocated temp buffer: clears the sticky error word (once, by whoever allocated the buffer).
 hipError_t radix_init_temp(void *temp, hipStream_t s) { return hipMemsetAsync(temp, 0, offsetof(Control, tile_ticket), s); }

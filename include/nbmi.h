@@ -480,6 +480,10 @@ int nbmi_frame_pending(nbmi_sim *sim, int *slots, int *kinds, int64_t *steps);
  * *ms_per_sort = mean device time of `repeats` sorts after one untimed run. */
 int nbmi_debug_sort_pairs(int key_bytes, int64_t n, const void *keys, const uint32_t *values, void *keys_out,
                           uint32_t *values_out, int bits, int impl, int repeats, double *ms_per_sort);
+/* Its keys-only twin: sorts n HOST keys by their bits [begin_bit, end_bit), stable; the bits outside the field travel
+ * with their key (the octree build sorts (prefix << 24 | body index) words this way). */
+int nbmi_debug_sort_keys(int key_bytes, int64_t n, const void *keys, void *keys_out, int begin_bit, int end_bit,
+                         int repeats, double *ms_per_sort);
 
 /* ---- headless point renderer (csrc/render.hip; tools/export.py) ------------------------------------------------
  * The image fixed-function GL draws for the exporter's frame: GL_POINTS with GL_POINT_SMOOTH, glBlendFunc(GL_SRC_ALPHA,
