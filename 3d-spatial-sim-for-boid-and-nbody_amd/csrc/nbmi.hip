@@ -4143,7 +4143,7 @@ struct nbmi_sim {
     unsigned *wave_cycles = nullptr;  // device [4 per walk block]
     unsigned char *wave_flag = nullptr;  // device [one per wave]
     int32_t *sub_flag = nullptr;         // device [one per tile]: waves of the tile that ask for float64
-    double step_dt = 0.0;                // dt of the step being enqueued (0: a build without a step)
+    double step_dt = 0.0;                // dt of the step whose build is being enqueued (DtScope; 0: a build without a step)
     double uniform_gm = -1.0;            // direct N^2: G m when every body has the same positive mass (the reference's presets: masses = 1), else < 0
     double max_gm = 0.0;                 // largest |G m| of the bodies at creation (guarded())
     int owner_all64 = -1;                // owner mode: the system-wide "every wave float64" verdict for the next walk (-1: this rank's own rule)
@@ -4155,9 +4155,9 @@ struct nbmi_sim {
     hipEvent_t ev_walked = nullptr, ev_cut = nullptr;
     bool cut_pending = false;         // a k_xcd_bounds on `side` that the next balanced walk has to wait for
     int walk_block = kBlock;  // threads per walk block (64, 128 or 256; measurement knob NBMI_WALK_BLOCK)
-    bool keys_lean = true;    // the stepping build (enqueue_tree(..., aux = false) of a plain handle) computes and stores
-                              // the upper key word only (key_low_word); NBMI_KEYS_LEAN=0: full keys.  Dropped for good
-                              // once a long run shows up (synchronise): every member of a run recomputes the others' words
+    bool keys_lean = true;    // the stepping build (a BuildRequest with step_dt > 0 and no aux, plain handle) computes and
+                              // stores the upper key word only (key_low_word); NBMI_KEYS_LEAN=0: full keys.  Dropped for good
+                              // once a long run shows up (decode_device_error): every member of a run recomputes the others' words
     bool lean_build = false;  // the build being enqueued / the last one built is lean: key_lo and lo_s do not hold it
     bool sort_packed = true;  // sort ONE packed word (prefix << 24 | body index) with the keys-only sort where it fits
                               // (packed_sort_ok); NBMI_SORT_PACKED=0: always (key, index) pairs
@@ -4178,12 +4178,11 @@ struct nbmi_sim {
     double *diag_part = nullptr;      // [kDiagBlocksMax * kDiagSums + kDiagSums] block partials, then the totals
     long long *diag_partc = nullptr;  // [kDiagBlocksMax + 1] the same for the term counts
     double4 *diag_pot = nullptr;      // [node rows] float64 {cx, cy, cz, G m} of every node of the diagnostic's own build
-    TreeInfo *diag_info = nullptr;    // the tree header as the last step left it, put back after the diagnostic's build
+    TreeInfo *side_info = nullptr;    // the tree header as it stood before a query's own build (SideBuild puts it back)
     // k-nearest-neighbour query (nbmi_knn), allocated by the first call; no step touches them.
     // 16 bytes per body (r2_k and mass_k by state row) and 32 bytes per node row (k_knn_rows)
     double *knn_r2 = nullptr, *knn_mass = nullptr;
     double4 *knn_rows = nullptr;
-    TreeInfo *knn_info = nullptr;  // the tree header as it stood before the query's build
     unsigned long long *knn_evals = nullptr;
     // what nbmi_compute_colors / nbmi_frame_begin colour by (nbmi_set_color_mode)
     int color_mode = NBMI_COLOR_SPEED, color_k = 32;
@@ -4274,6 +4273,58 @@ int check_handle(nbmi_sim *s) {
     return 0;
 }
 
+// the null check of a getter's output (or, with another `what`, of any pointer argument)
+int require_out(const void *p, const char *what = "null output") {
+    if (!p) nbmi::set_error("%s", what);
+    return p ? 0 : NBMI_ERR_ARG;
+}
+// The positions changed behind the handle's back, or what a mass or a force means did: the tree no longer describes
+// the state, maxabs_next is not its extent, and the leapfrog's stored a = F(x) is not its force.  A site that drops
+// fewer than these three says which survive and why.
+void state_changed(nbmi_sim *s) { s->tree_valid = s->maxabs_fused = s->acc_valid = false; }
+
+// Runtime values as template arguments: f is a generic lambda and gets std::true_type / std::false_type, or the
+// std::integral_constant of the one of Vs... that v equals (v is always one of them).
+template <class F>
+void with_bool(bool b, F &&f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+template <int... Vs, class F>
+void with_int(int v, F &&f) {
+    (void)((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
+
+// s->step_dt is a step's dt exactly while that step's build is being enqueued: force precision "auto" is decided
+// during the build and needs it (auto_prec)
+struct DtScope {
+    nbmi_sim *s;
+    DtScope(nbmi_sim *sim, double dt) : s(sim) { s->step_dt = dt; }
+    ~DtScope() { s->step_dt = 0.0; }
+};
+// What enqueue_tree is asked for.  timing: none, all phase events, or all but the first, which the caller has recorded
+// (a leapfrog step: its k_kick_drift counts as the bounds phase).  step_dt > 0 makes it the build of a step with that
+// dt: "auto" takes its decision, and the lean key form may serve it (nothing reads a step's keys afterwards).
+enum class BuildTiming { kNone, kAll, kCaller };
+struct BuildRequest {
+    BuildTiming timing = BuildTiming::kNone;
+    bool aux = true;  // also write node_ref / node_level (cell queries, owner-mode kernels)
+    // where the float64 {cx, cy, cz, G m} row of every node goes (nbmi_diagnostics' tree potential; null: s->diag64,
+    // which is null outside the NBMI_PREC measurement mode - a step never writes it)
+    double4 *diag_rows = nullptr;
+    double step_dt = 0.0;
+};
+BuildRequest step_build(const nbmi_sim *s, double dt, BuildTiming timed) {
+    return BuildRequest{s->timers ? timed : BuildTiming::kNone, false, nullptr, dt};
+}
+// What enqueue_local_sort is asked for.  Owner mode: n_sort rows are keyed and sorted (rows of emigrants are still in
+// place, flagged `dead`, and sort to the end); the first n_live of the order are gathered for the tree.
+struct SortRequest {
+    bool timed = false, lean = false;  // record the key and sort phase events / upper key word only (nbmi_sim::keys_lean)
+    int64_t n_sort = -1, n_live = -1;  // -1: all of the handle's rows
+    const uint8_t *dead = nullptr;
+};
+
 // The octree build in three enqueue stages (one after the other for a single-GPU step; the
 // multi-GPU run exchange puts its two collectives between them):
 //   enqueue_maxabs      reset the tree header, max |coordinate| of the handle's own bodies
@@ -4299,8 +4350,6 @@ int enqueue_maxabs(nbmi_sim *s) {
     return 0;
 }
 
-// n_sort rows are keyed and sorted (owner mode: rows of emigrants are still in place, flagged dead, and sort to
-// the end); the first n_live of the order are gathered for the tree
 // force precision "auto" is decided during the build of a step (it needs dt); anything else leaves the flags alone
 static inline bool auto_prec(const nbmi_sim *s) { return s->nodesd && s->force_prec == 0 && s->step_dt > 0.0; }
 
@@ -4311,13 +4360,13 @@ static inline bool packed_sort_ok(const nbmi_sim *s, int64_t n, const uint8_t *d
     return s->sort_packed && s->packed && s->sort_bits <= kPackMaxSortBits && n <= ((int64_t)1 << kPackIdxBits) && !dead;
 }
 
-int enqueue_local_sort(nbmi_sim *s, int ev_base, int64_t n_sort = -1, int64_t n_live = -1, const uint8_t *dead = nullptr,
-                       bool lean = false) {
+int enqueue_local_sort(nbmi_sim *s, const SortRequest &req = {}) {
+    const bool lean = req.lean;
+    const uint8_t *dead = req.dead;
     s->lean_build = lean;
     const uint64_t *key_lo = lean ? nullptr : s->key_lo;  // what the tie-fix and the gather read
     const int hil = s->hilbert ? 1 : 0;
-    const int64_t n = n_sort < 0 ? s->n : n_sort;
-    if (n_live < 0) n_live = n;
+    const int64_t n = req.n_sort < 0 ? s->n : req.n_sort, n_live = req.n_live < 0 ? n : req.n_live;
     hipStream_t st = s->stream;
     Bodies cur = s->buf[s->curbuf];
     // radix sort on the top sort_bits bits of the upper word, then the tie-fix completes the 126-bit order
@@ -4334,13 +4383,13 @@ int enqueue_local_sort(nbmi_sim *s, int ev_base, int64_t n_sort = -1, int64_t n_
     const int shift = 63 - s->sort_bits;
     const bool packed = packed_sort_ok(s, n, dead);
     uint64_t *pk = packed ? s->packed : nullptr;
-#define NBMI_KEYS(H, L) k_keys<H, L><<<nblocks(n), kBlock, 0, st>>>(cur.x, cur.y, cur.z, n, s->info, s->key_hi, s->key_lo, s->idx, dead, pk, shift)
-    if (s->hilbert && lean) NBMI_KEYS(true, true);
-    else if (s->hilbert) NBMI_KEYS(true, false);
-    else if (lean) NBMI_KEYS(false, true);
-    else NBMI_KEYS(false, false);
-#undef NBMI_KEYS
-    if (ev_base >= 0) NBMI_HIP_CHECK(hipEventRecord(s->ev[1], st));
+    with_bool(s->hilbert, [&](auto h) {
+        with_bool(lean, [&](auto l) {
+            k_keys<decltype(h)::value, decltype(l)::value><<<nblocks(n), kBlock, 0, st>>>(cur.x, cur.y, cur.z, n, s->info, s->key_hi,
+                                                                                         s->key_lo, s->idx, dead, pk, shift);
+        });
+    });
+    if (req.timed) NBMI_HIP_CHECK(hipEventRecord(s->ev[1], st));
     if (packed) {
         // one 8-byte word per body through the passes instead of an 8-byte key and a 4-byte index: the index sits
         // below the prefix, so a stable sort of the pairs and a sort of the words on the prefix bits give the same order
@@ -4360,21 +4409,18 @@ int enqueue_local_sort(nbmi_sim *s, int ev_base, int64_t n_sort = -1, int64_t n_
         std::swap(s->hi_s, s->key_hi);
     }
     s->t_hi = s->hi_s;
-    if (ev_base >= 0) NBMI_HIP_CHECK(hipEventRecord(s->ev[2], st));
+    if (req.timed) NBMI_HIP_CHECK(hipEventRecord(s->ev[2], st));
     // ranks 0 .. n_live: entry n_live is the slot of the totals
-#define NBMI_GATHER(L) k_gather_scan<L><<<(int)((n_live + 1 + kScanTile - 1) / kScanTile), kBlock, 0, st>>>(                      \
-        cur, s->perm, s->hi_s, key_lo, n_live, s->G, s->posm_s, s->p64_s, lean ? nullptr : s->lo_s, s->delta, s->S, s->Pex, s->sub_tot, s->sub_cnt, \
-        auto_prec(s) ? s->wave_flag : nullptr, s->sub_flag, auto_prec(s) ? (float)(s->prec_tau / (s->step_dt * s->step_dt)) : 0.f, \
-        (float)s->softening, s->info, hil)
-    if (lean) NBMI_GATHER(true);
-    else NBMI_GATHER(false);
-#undef NBMI_GATHER
+    with_bool(lean, [&](auto l) {
+        k_gather_scan<decltype(l)::value><<<(int)((n_live + 1 + kScanTile - 1) / kScanTile), kBlock, 0, st>>>(
+            cur, s->perm, s->hi_s, key_lo, n_live, s->G, s->posm_s, s->p64_s, lean ? nullptr : s->lo_s, s->delta, s->S, s->Pex,
+            s->sub_tot, s->sub_cnt, auto_prec(s) ? s->wave_flag : nullptr, s->sub_flag,
+            auto_prec(s) ? (float)(s->prec_tau / (s->step_dt * s->step_dt)) : 0.f, (float)s->softening, s->info, hil);
+    });
     return 0;
 }
 
-// aux: also write node_ref / node_level (cell queries, owner-mode kernels)
-// diag: where the float64 {cx, cy, cz, G m} row of every node goes (nbmi_diagnostics' tree potential; null: s->diag64,
-// which is null outside the NBMI_PREC measurement mode - a step never writes it)
+// aux, diag: BuildRequest's aux and diag_rows
 int enqueue_global_tree(nbmi_sim *s, bool aux = true, double4 *diag = nullptr) {
     const int64_t n = s->nt;
     hipStream_t st = s->stream;
@@ -4390,17 +4436,14 @@ int enqueue_global_tree(nbmi_sim *s, bool aux = true, double4 *diag = nullptr) {
         aux = true;
         if (!diag) diag = s->quad_pot;
     }
-    {
-        const int tile = n <= kEmitSmallBodies ? kEmitTileSmall : kEmitTile;
-#define NBMI_EMIT(TV) k_emit_tile<TV><<<(int)((n + TV - 1) / TV), kBlock, 0, st>>>(                                         \
-        s->delta, s->Pex, s->subPex, s->S, s->T, s->t_posm, s->p64_s, s->t_hi, s->lean_build ? nullptr : s->t_lo, n, s->own_node_rows, s->softening,       \
-        inv_theta2, s->nodes + ob, s->nodes64 + ob, aux ? s->node_level : nullptr, aux ? s->node_ref : nullptr,              \
-        diag ? diag : s->diag64,                                                                                            \
-        s->force_prec != 1 && s->nodesd ? s->nodesd + ob : nullptr, s->buf[s->curbuf], s->perm, s->G, s->info, s->hilbert ? 1 : 0, ob)
-        if (tile == kEmitTileSmall) NBMI_EMIT(kEmitTileSmall);
-        else NBMI_EMIT(kEmitTile);
-#undef NBMI_EMIT
-    }
+    with_int<kEmitTileSmall, kEmitTile>(n <= kEmitSmallBodies ? kEmitTileSmall : kEmitTile, [&](auto tile) {
+        constexpr int kTile = decltype(tile)::value;
+        k_emit_tile<kTile><<<(int)((n + kTile - 1) / kTile), kBlock, 0, st>>>(
+            s->delta, s->Pex, s->subPex, s->S, s->T, s->t_posm, s->p64_s, s->t_hi, s->lean_build ? nullptr : s->t_lo, n,
+            s->own_node_rows, s->softening, inv_theta2, s->nodes + ob, s->nodes64 + ob, aux ? s->node_level : nullptr,
+            aux ? s->node_ref : nullptr, diag ? diag : s->diag64, s->force_prec != 1 && s->nodesd ? s->nodesd + ob : nullptr,
+            s->buf[s->curbuf], s->perm, s->G, s->info, s->hilbert ? 1 : 0, ob);
+    });
     if (s->walk_stack)
         k_child_table<<<nblocks(s->own_node_rows), kBlock, 0, st>>>(s->nodes, s->info, s->own_node_rows, s->child_tab);
     if (quad && n > 0) {
@@ -4414,22 +4457,22 @@ int enqueue_global_tree(nbmi_sim *s, bool aux = true, double4 *diag = nullptr) {
     return 0;
 }
 
-// Single-GPU build: the tree over the handle's own bodies.  ev_base: -1 untimed, 0 timed, 1 timed with the phase's first
-// event already recorded by the caller (a leapfrog step: its k_kick_drift counts as the bounds phase)
-// step: the build of a step (the lean key form may serve it: nothing reads its keys afterwards)
-int enqueue_tree(nbmi_sim *s, int ev_base, bool aux = true, double4 *diag = nullptr, bool step = false) {
+// Single-GPU build: the tree over the handle's own bodies
+int enqueue_tree(nbmi_sim *s, const BuildRequest &req = {}) {
     if (s->owner) {
         nbmi::set_error("this handle is in owner mode: use the nbmi_owner_* calls");
         return NBMI_ERR_ARG;
     }
-    if (ev_base == 0) NBMI_HIP_CHECK(hipEventRecord(s->ev[0], s->stream));
+    const DtScope dt_scope(s, req.step_dt);
+    const bool timed = req.timing != BuildTiming::kNone;
+    if (req.timing == BuildTiming::kAll) NBMI_HIP_CHECK(hipEventRecord(s->ev[0], s->stream));
     if (int rc = enqueue_maxabs(s)) return rc;
     // a step's build (no queries on it: aux = false) needs no stored low key word; the quadrupole build is one with aux
-    const bool lean = s->keys_lean && step && !aux && s->multipole != NBMI_MULTIPOLE_QUADRUPOLE;
-    if (int rc = enqueue_local_sort(s, ev_base, -1, -1, nullptr, lean)) return rc;
-    if (int rc = enqueue_global_tree(s, aux, diag)) return rc;
-    if (ev_base >= 0) NBMI_HIP_CHECK(hipEventRecord(s->ev[3], s->stream));
-    s->tree_valid = aux || s->multipole == NBMI_MULTIPOLE_QUADRUPOLE;  // (a quadrupole build always writes node_ref / node_level)
+    const bool lean = s->keys_lean && req.step_dt > 0.0 && !req.aux && s->multipole != NBMI_MULTIPOLE_QUADRUPOLE;
+    if (int rc = enqueue_local_sort(s, SortRequest{timed, lean})) return rc;
+    if (int rc = enqueue_global_tree(s, req.aux, req.diag_rows)) return rc;
+    if (timed) NBMI_HIP_CHECK(hipEventRecord(s->ev[3], s->stream));
+    s->tree_valid = req.aux || s->multipole == NBMI_MULTIPOLE_QUADRUPOLE;  // (a quadrupole build always writes node_ref / node_level)
     return 0;
 }
 
@@ -4451,17 +4494,6 @@ bool guarded(const nbmi_sim *s) {
     return gm / ((double)eps2 * sqrt((double)eps2)) > 0x1p120;
 }
 
-// Runtime values as template arguments: f is a generic lambda and gets std::true_type / std::false_type, or the
-// std::integral_constant of the one of Vs... that v equals (v is always one of them).
-template <class F>
-void with_bool(bool b, F &&f) {
-    if (b) f(std::true_type{});
-    else f(std::false_type{});
-}
-template <int... Vs, class F>
-void with_int(int v, F &&f) {
-    (void)((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
-}
 // what a force walk does with its result (with_int<kWalkForces, kWalkStep, kWalkLeap>)
 constexpr int kWalkForces = 0;  // accelerations in the caller's order, work counters (no integration)
 constexpr int kWalkStep = 1;    // the fused kick-drift
@@ -4645,10 +4677,7 @@ int leap_prepare(nbmi_sim *s, double dt) {
     }
     if (s->acc_valid) return 0;
     if (s->method == NBMI_METHOD_BARNES_HUT) {
-        s->step_dt = dt;
-        const int rc_tree = enqueue_tree(s, -1, false, nullptr, true);
-        s->step_dt = 0.0;
-        if (rc_tree) return rc_tree;
+        if (int rc = enqueue_tree(s, step_build(s, dt, BuildTiming::kNone))) return rc;
         if (int rc = enqueue_walk(s, true, dt, nullptr, kLeapPrime)) return rc;
         s->tree_valid = false;
     } else {
@@ -4672,44 +4701,100 @@ int enqueue_kick_drift(nbmi_sim *s, double dt) {
     return 0;
 }
 
+// NBMI_ERR_CAPACITY with the message of a build that ran out of node rows; `tail`: what that meant for the bodies
+int capacity_error(const nbmi_sim *s, long long nodes, const char *tail) {
+    nbmi::set_error("octree needs %lld nodes, more than the %lld rows allocated%s", nodes, (long long)s->node_capacity, tail);
+    return NBMI_ERR_CAPACITY;
+}
+
+// What the device error words mean, whoever fetched them (check_device_error from the device, nbmi_frame_wait from its
+// snapshot's header): the host-side consequences, the message and the code.
+int decode_device_error(nbmi_sim *s, const FrameHeader &w) {
+    if (w.sort_error) {  // a look-back spin of the radix sort timed out: that pass scattered to wrong offsets
+        nbmi::set_error("device radix sort: a look-back spin timed out; the steps since the last synchronisation are invalid");
+        return NBMI_ERR_HIP;
+    }
+    if (w.max_run > 4096) {
+        // many bodies agree on the sorted prefix (a dense core inside one level-13 cell): the tie-fix did the rest
+        // correctly but at L reads per member - sort on more bits from the next step on.  The run may be one in the whole
+        // upper word, where every member recomputes the others' low words: full keys from now on
+        if (s->sort_bits < 63) s->sort_bits = s->sort_bits + 8 < 63 ? s->sort_bits + 8 : 63;
+        s->keys_lean = false;
+    }
+    if (w.error || w.sticky_error)
+        return capacity_error(s, w.sticky_error ? w.sticky_nodes : w.num_nodes,
+                              " (4N, as the reference); the bodies were not advanced from that step on");
+    return 0;
+}
+
+// Fetches and decodes the error words behind everything on the stream, and puts device and handle in order again
 int check_device_error(nbmi_sim *s) {
+    if (s->method != NBMI_METHOD_BARNES_HUT) return 0;  // (a direct handle builds and sorts nothing)
     TreeInfo h;
     unsigned sort_err = 0u;
     NBMI_HIP_CHECK(hipMemcpyAsync(&h, s->info, sizeof(h), hipMemcpyDeviceToHost, s->stream));
     if (s->tmp_sort) NBMI_HIP_CHECK(nbmi::sort_error_word(s->tmp_sort, &sort_err, s->stream));
     NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
-    if (sort_err) {  // a look-back spin of the radix sort timed out: that pass scattered to wrong offsets
+    const int rc = decode_device_error(s, FrameHeader{h.error, h.sticky_error, h.max_run, sort_err, h.num_nodes, h.sticky_nodes, {}});
+    if (sort_err) {
         NBMI_HIP_CHECK(nbmi::sort_init_temp(s->tmp_sort, s->stream));
         NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
-        s->tree_valid = false;
-        nbmi::set_error("device radix sort: a look-back spin timed out; the steps since the last synchronisation are invalid");
-        return NBMI_ERR_HIP;
-    }
-    if (h.max_run > 4096 && s->sort_bits < 63) {
-        // many bodies agree on the sorted prefix (a dense core inside one level-13 cell): the tie-fix did the
-        // rest correctly but at L reads per member - sort on more bits from the next step on
-        s->sort_bits = s->sort_bits + 8 < 63 ? s->sort_bits + 8 : 63;
-    }
-    if (h.max_run > 4096) s->keys_lean = false;  // (a long run may be one in the whole upper word, where every member
-                                                 // recomputes the others' low words: full keys from now on)
-    if (h.error || h.sticky_error) {
+        s->tree_valid = false;  // (the positions and the header are as they were: the other two survive)
+    } else if (rc) {
         // reported once: clear the sticky word so the handle can go on after nbmi_set_state / a retry.  The
         // bodies stand at the last step that completed (the walk froze them while the word was set).
         NBMI_HIP_CHECK(hipMemsetAsync(&s->info->sticky_error, 0, sizeof(int), s->stream));
         NBMI_HIP_CHECK(hipMemsetAsync(&s->info->error, 0, sizeof(int), s->stream));
         NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
-        s->tree_valid = false;
-        s->maxabs_fused = false;
-        s->acc_valid = false;  // leapfrog: a priming walk may have been frozen; the next step primes again
+        state_changed(s);  // (leapfrog: a priming walk may have been frozen; the next step primes again)
     }
-    if (h.error || h.sticky_error) {
-        nbmi::set_error("octree needs %lld nodes, more than the %lld rows allocated (4N, as the reference); the "
-                        "bodies were not advanced from that step on",
-                        (long long)(h.sticky_error ? h.sticky_nodes : h.num_nodes), (long long)s->node_capacity);
-        return NBMI_ERR_CAPACITY;
-    }
-    return 0;
+    return rc;
 }
+
+// A query's own octree build between two steps (nbmi_diagnostics' potential, the k-NN query).  The build overwrites the
+// tree header (maxabs_next, force_all64, the counters) and host fields of the handle; the scope puts both back, so the
+// next step finds the handle as it would have without the query.
+struct SideBuild {
+    nbmi_sim *s;
+    // The host fields that a build which is no step's, or the report of its error, changes.  (step_dt is none:
+    // enqueue_tree installs its request's 0 itself.)  Left out, after a look at enqueue_tree, enqueue_local_sort and
+    // decode_device_error:
+    //   lean_build  every enqueue_local_sort writes it before its one reader, the same build's enqueue_global_tree
+    //   t_hi, and perm / idx, hi_s / key_hi, which a pair sort swaps: they name the last build's arrays - what a tree
+    //               that is valid afterwards is read through - and every build writes them before it reads them
+    //   acc_valid   no build touches it, and a reported capacity error is to drop it for good
+    struct Saved {
+        bool tree_valid, maxabs_fused;
+        int sort_bits;   // chosen by the first build; widened, and ...
+        bool keys_lean;  // ... dropped, where the query's own error check sees a long run: the next step's build shows it again
+    } saved;
+    int rc;  // of the construction: nothing to finish if set
+    explicit SideBuild(nbmi_sim *sim)
+        : s(sim), saved{s->tree_valid, s->maxabs_fused, s->sort_bits, s->keys_lean}, rc(save_header()) {}
+    int save_header() {
+        if (!s->side_info && dev_alloc(s, &s->side_info, 1)) return NBMI_ERR_HIP;
+        NBMI_HIP_CHECK(hipMemcpyAsync(s->side_info, s->info, sizeof(TreeInfo), hipMemcpyDeviceToDevice, s->stream));
+        return 0;
+    }
+    // r: of the build and the query's kernels.  wait (the diagnostic): the query is waited for and a capacity error of
+    // its build reported at once - check_device_error clears the words, so k_knn_restore then writes the saved header
+    // as it is.  Otherwise (k-NN) nothing waits, and k_knn_restore keeps the build's error in the sticky words for the
+    // next call that looks.
+    int finish(int r, bool wait) {
+        if (wait && r == 0) r = check_device_error(s);  // NBMI_ERR_CAPACITY: the message of a step
+        k_knn_restore<<<1, 64, 0, s->stream>>>(s->info, s->side_info);
+        if (hipGetLastError() != hipSuccess && r == 0) {
+            nbmi::set_error("k_knn_restore launch failed");
+            r = NBMI_ERR_HIP;
+        }
+        // the same positions give the same tree: what the queries read is still that tree if it was before
+        s->tree_valid = saved.tree_valid && r == 0;
+        s->maxabs_fused = saved.maxabs_fused;
+        s->sort_bits = saved.sort_bits;
+        s->keys_lean = saved.keys_lean;
+        return r;
+    }
+};
 
 }  // namespace
 
@@ -4797,6 +4882,14 @@ static void read_env_knobs(nbmi_sim *s) {
         const int b = atoi(e);
         if (b == 64 || b == 128 || b == 256) s->walk_block = b;
     }
+}
+
+// a create that failed: the handle goes, the message stays
+static nbmi_sim *create_failed(nbmi_sim *s) {
+    std::string keep = nbmi::get_error();
+    nbmi_destroy(s);
+    nbmi::set_error("%s", keep.c_str());
+    return nullptr;
 }
 
 static int create_impl(nbmi_sim *s, const double *pos, const double *vel, const double *mass) {
@@ -4890,12 +4983,7 @@ nbmi_sim *nbmi_create(int64_t n, const double *pos, const double *vel, const dou
     s->G = G; s->softening = softening; s->damping = damping; s->theta = theta;
     s->max_gm = largest_gm(G, mass, n);
     read_env_knobs(s);
-    if (create_impl(s, pos, vel, mass) != 0) {
-        std::string keep = nbmi::get_error();
-        nbmi_destroy(s);
-        nbmi::set_error("%s", keep.c_str());
-        return nullptr;
-    }
+    if (create_impl(s, pos, vel, mass) != 0) return create_failed(s);
     if (s->multipole_env == NBMI_MULTIPOLE_QUADRUPOLE && !multipole_refusal(s)) (void)nbmi_set_multipole(s, s->multipole_env);
     if (method == NBMI_METHOD_DIRECT && n > 0 && mass[0] > 0.0) {
         bool same = true;
@@ -4930,12 +5018,7 @@ nbmi_sim *nbmi_create_generated(int distribution, int64_t n, double spawn_radius
         rc = nbmi::ic_generate(distribution, n, spawn_radius, G, seed, nbmi::IcArrays{b.x, b.y, b.z, b.vx, b.vy, b.vz, b.m, b.id},
                                s->stream);
     }
-    if (rc != 0) {
-        std::string keep = nbmi::get_error();
-        nbmi_destroy(s);
-        nbmi::set_error("%s", keep.c_str());
-        return nullptr;
-    }
+    if (rc != 0) return create_failed(s);
     if (s->multipole_env == NBMI_MULTIPOLE_QUADRUPOLE && !multipole_refusal(s)) (void)nbmi_set_multipole(s, s->multipole_env);
     return s;
 }
@@ -4948,15 +5031,15 @@ int nbmi_get_masses_f64(nbmi_sim *s, double *out) {
     if (int rc = check_handle(s)) return rc;
     const int64_t n = s->n;
     if (n == 0) return 0;
-    if (!out) { nbmi::set_error("null output"); return NBMI_ERR_ARG; }
-    Bodies cur = s->buf[s->curbuf];
-    // scatter to the caller's order through the 3-component un-permute (components 1, 2 unused)
-    k_unperm3_f64<<<nblocks(n), kBlock, 0, s->stream>>>(cur.m, cur.m, cur.m, s->owner ? nullptr : cur.id, n, (double *)s->stage);
-    NBMI_HIP_CHECK(hipGetLastError());
-    std::vector<double> tmp((size_t)n * 3);
-    NBMI_HIP_CHECK(hipMemcpyAsync(tmp.data(), s->stage, (size_t)n * 24, hipMemcpyDeviceToHost, s->stream));
+    if (int rc = require_out(out)) return rc;
+    const double *m = s->buf[s->curbuf].m;  // (owner mode: the rows are the caller's order)
+    if (!s->owner) {
+        k_unperm1_f64<<<nblocks(n), kBlock, 0, s->stream>>>(m, s->buf[s->curbuf].id, n, (double *)s->stage);
+        NBMI_HIP_CHECK(hipGetLastError());
+        m = (const double *)s->stage;
+    }
+    NBMI_HIP_CHECK(hipMemcpyAsync(out, m, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
-    for (int64_t i = 0; i < n; i++) out[i] = tmp[3 * i];
     return 0;
 }
 
@@ -4981,16 +5064,13 @@ int nbmi_step(nbmi_sim *s, double dt, int substeps) {
     }
     for (int k = 0; k < substeps; k++) {
         if (s->method == NBMI_METHOD_BARNES_HUT) {
-            const int evb = s->timers ? 0 : -1;
             if (leap) {
                 // kick-drift into the other buffer, build + walk there, the closing kick writes back: one step leaves the
                 // current buffer where it was
                 if (s->timers) NBMI_HIP_CHECK(hipEventRecord(s->ev[0], s->stream));
                 if (int rc = enqueue_kick_drift(s, dt)) return rc;
                 s->maxabs_fused = true;  // k_kick_drift has published max |x'|
-                s->step_dt = dt;
-                int rc = enqueue_tree(s, s->timers ? 1 : -1, false, nullptr, true);
-                s->step_dt = 0.0;
+                int rc = enqueue_tree(s, step_build(s, dt, BuildTiming::kCaller));
                 if (rc == 0) rc = enqueue_walk(s, true, dt, nullptr, kLeapClose);
                 s->curbuf ^= 1;
                 if (rc) {
@@ -4998,10 +5078,7 @@ int nbmi_step(nbmi_sim *s, double dt, int substeps) {
                     return rc;
                 }
             } else {
-                s->step_dt = dt;
-                const int rc_tree = enqueue_tree(s, evb, false, nullptr, true);
-                s->step_dt = 0.0;
-                if (rc_tree) return rc_tree;
+                if (int rc = enqueue_tree(s, step_build(s, dt, BuildTiming::kAll))) return rc;
                 if (int rc = enqueue_walk(s, true, dt, nullptr)) return rc;
             }
             if (s->timers) {
@@ -5072,14 +5149,17 @@ int nbmi_compute_colors(nbmi_sim *s, double max_speed) {
 int nbmi_sync(nbmi_sim *s) {
     if (int rc = check_handle(s)) return rc;
     NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
-    if (s->method == NBMI_METHOD_BARNES_HUT) return check_device_error(s);
-    return 0;
+    return check_device_error(s);
 }
 
-static int get3(nbmi_sim *s, const double *a, const double *b, const double *c, void *out, bool f32) {
+// positions or velocities (N,3) in the caller's order
+static int get3(nbmi_sim *s, bool vel, void *out, bool f32) {
+    if (int rc = check_handle(s)) return rc;
     const int64_t n = s->n;
     if (n == 0) return 0;
+    if (int rc = require_out(out)) return rc;
     Bodies cur = s->buf[s->curbuf];
+    const double *a = vel ? cur.vx : cur.x, *b = vel ? cur.vy : cur.y, *c = vel ? cur.vz : cur.z;
     const int32_t *id = s->owner ? nullptr : cur.id;
     if (f32) k_unperm3_f32<<<nblocks(n), kBlock, 0, s->stream>>>(a, b, c, id, n, (float *)s->stage);
     else k_unperm3_f64<<<nblocks(n), kBlock, 0, s->stream>>>(a, b, c, id, n, (double *)s->stage);
@@ -5087,32 +5167,15 @@ static int get3(nbmi_sim *s, const double *a, const double *b, const double *c, 
     NBMI_HIP_CHECK(hipMemcpyAsync(out, s->stage, (size_t)n * 3 * (f32 ? sizeof(float) : sizeof(double)),
                                   hipMemcpyDeviceToHost, s->stream));
     NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
-    if (s->method == NBMI_METHOD_BARNES_HUT) return check_device_error(s);
-    return 0;
+    return check_device_error(s);
 }
-
-int nbmi_get_positions_f32(nbmi_sim *s, float *out) {
-    if (int rc = check_handle(s)) return rc;
-    if (!out && s->n) { nbmi::set_error("null output"); return NBMI_ERR_ARG; }
-    Bodies cur = s->buf[s->curbuf];
-    return get3(s, cur.x, cur.y, cur.z, out, true);
-}
-int nbmi_get_positions_f64(nbmi_sim *s, double *out) {
-    if (int rc = check_handle(s)) return rc;
-    if (!out && s->n) { nbmi::set_error("null output"); return NBMI_ERR_ARG; }
-    Bodies cur = s->buf[s->curbuf];
-    return get3(s, cur.x, cur.y, cur.z, out, false);
-}
-int nbmi_get_velocities_f64(nbmi_sim *s, double *out) {
-    if (int rc = check_handle(s)) return rc;
-    if (!out && s->n) { nbmi::set_error("null output"); return NBMI_ERR_ARG; }
-    Bodies cur = s->buf[s->curbuf];
-    return get3(s, cur.vx, cur.vy, cur.vz, out, false);
-}
+int nbmi_get_positions_f32(nbmi_sim *s, float *out) { return get3(s, false, out, true); }
+int nbmi_get_positions_f64(nbmi_sim *s, double *out) { return get3(s, false, out, false); }
+int nbmi_get_velocities_f64(nbmi_sim *s, double *out) { return get3(s, true, out, false); }
 int nbmi_get_colors_f32(nbmi_sim *s, float *out) {
     if (int rc = check_handle(s)) return rc;
     if (s->n == 0) return 0;
-    if (!out) { nbmi::set_error("null output"); return NBMI_ERR_ARG; }
+    if (int rc = require_out(out)) return rc;
     NBMI_HIP_CHECK(hipMemcpyAsync(out, s->colors, (size_t)s->n * 3 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
     NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
     return 0;
@@ -5132,9 +5195,7 @@ int nbmi_set_state(nbmi_sim *s, const double *pos, const double *vel) {
     NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
     k_set_all64<<<1, 1, 0, s->stream>>>(s->info, 0);  // a new state: the "most of the system asks" history is the old system's
     NBMI_HIP_CHECK(hipGetLastError());
-    s->tree_valid = false;
-    s->maxabs_fused = false;
-    s->acc_valid = false;  // leapfrog: the stored acceleration belongs to the old positions
+    state_changed(s);
     return 0;
 }
 
@@ -5169,7 +5230,7 @@ int nbmi_set_integrator(nbmi_sim *s, int integrator) {
 
 int nbmi_get_integrator(nbmi_sim *s, int *out) {
     if (int rc = check_handle(s)) return rc;
-    if (!out) { nbmi::set_error("null output"); return NBMI_ERR_ARG; }
+    if (int rc = require_out(out)) return rc;
     *out = s->integrator;
     return 0;
 }
@@ -5190,7 +5251,7 @@ int nbmi_set_multipole(nbmi_sim *s, int multipole) {
                            dev_alloc(s, &s->quad_pot, s->node_capacity + 2)))
             return NBMI_ERR_HIP;
     }
-    if (multipole != s->multipole) {
+    if (multipole != s->multipole) {  // (the positions are the same: maxabs_fused survives)
         s->tree_valid = false;  // the records the queries describe belong to the other mode's build
         s->acc_valid = false;   // leapfrog: the stored a = F(x) is the other mode's force
     }
@@ -5200,7 +5261,7 @@ int nbmi_set_multipole(nbmi_sim *s, int multipole) {
 
 int nbmi_get_multipole(nbmi_sim *s, int *out) {
     if (int rc = check_handle(s)) return rc;
-    if (!out) { nbmi::set_error("null output"); return NBMI_ERR_ARG; }
+    if (int rc = require_out(out)) return rc;
     *out = s->multipole;
     return 0;
 }
@@ -5209,7 +5270,7 @@ int nbmi_build_tree(nbmi_sim *s) {
     if (int rc = check_handle(s)) return rc;
     if (s->method != NBMI_METHOD_BARNES_HUT) { nbmi::set_error("not a Barnes-Hut handle"); return NBMI_ERR_ARG; }
     if (s->n == 0) return 0;
-    if (int rc = enqueue_tree(s, -1)) return rc;
+    if (int rc = enqueue_tree(s)) return rc;
     return check_device_error(s);
 }
 
@@ -5217,10 +5278,10 @@ int nbmi_get_accelerations_f64(nbmi_sim *s, double *out) {
     if (int rc = check_handle(s)) return rc;
     const int64_t n = s->n;
     if (n == 0) return 0;
-    if (!out) { nbmi::set_error("null output"); return NBMI_ERR_ARG; }
+    if (int rc = require_out(out)) return rc;
     double *acc = (double *)s->stage;
     if (s->method == NBMI_METHOD_BARNES_HUT) {
-        if (int rc = enqueue_tree(s, -1)) return rc;
+        if (int rc = enqueue_tree(s)) return rc;
         NBMI_HIP_CHECK(hipMemsetAsync(&s->info->wave_visits, 0, 17 * sizeof(unsigned long long), s->stream));
         if (int rc = enqueue_walk(s, false, 0.0, acc)) return rc;
     } else {
@@ -5228,15 +5289,12 @@ int nbmi_get_accelerations_f64(nbmi_sim *s, double *out) {
     }
     NBMI_HIP_CHECK(hipMemcpyAsync(out, acc, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
-    if (s->method == NBMI_METHOD_BARNES_HUT) return check_device_error(s);
-    return 0;
+    return check_device_error(s);
 }
 
 namespace {
 // phi and the applied-term counts per state row (diag_phi / diag_cnt).  Barnes-Hut: the octree of the current positions
-// as nbmi_get_accelerations_f64 builds it, with the float64 node rows, then the potential walk.  The build overwrites the
-// tree header (maxabs_next, force_all64, ...) and the host-side flags; both are put back, so the next step finds the
-// handle as it would have without this call.
+// as nbmi_get_accelerations_f64 builds it, with the float64 node rows, then the potential walk, all inside a SideBuild.
 int diag_potential(nbmi_sim *s) {
     const int64_t n = s->n;
     if (!s->diag_phi && (dev_alloc(s, &s->diag_phi, n) || dev_alloc(s, &s->diag_cnt, n))) return NBMI_ERR_HIP;
@@ -5247,42 +5305,27 @@ int diag_potential(nbmi_sim *s) {
         NBMI_HIP_CHECK(hipGetLastError());
         return 0;
     }
-    if (!s->diag_pot && (dev_alloc(s, &s->diag_pot, s->node_capacity + 2) || dev_alloc(s, &s->diag_info, 1))) return NBMI_ERR_HIP;
+    if (!s->diag_pot && dev_alloc(s, &s->diag_pot, s->node_capacity + 2)) return NBMI_ERR_HIP;
     // a capacity error of an earlier step is reported first, as a getter does
     NBMI_HIP_CHECK(hipStreamSynchronize(st));
     if (int rc = check_device_error(s)) return rc;
-    NBMI_HIP_CHECK(hipMemcpyAsync(s->diag_info, s->info, sizeof(TreeInfo), hipMemcpyDeviceToDevice, st));
-    const bool tree_valid = s->tree_valid, maxabs_fused = s->maxabs_fused;
-    const int sort_bits = s->sort_bits;
-    const double step_dt = s->step_dt;
-    s->step_dt = 0.0;  // no "auto" decision: the wave flags and force_all64 stay the last step's
-    int rc = enqueue_tree(s, -1, false, s->diag_pot);
+    SideBuild side(s);  // (no "auto" decision in its build: the wave flags and force_all64 stay the last step's)
+    if (side.rc) return side.rc;
+    BuildRequest build;
+    build.aux = false; build.diag_rows = s->diag_pot;
+    int rc = enqueue_tree(s, build);
     if (rc == 0) {
-        if (s->multipole == NBMI_MULTIPOLE_QUADRUPOLE)
-            k_potential_tree<true><<<nblocks(n), kBlock, 0, st>>>(s->nodes, s->diag_pot, s->wtab, s->info, s->posm_s, s->perm,
-                                                                  s->curbuf, (float)(s->softening * s->softening), n, s->diag_phi,
-                                                                  s->diag_cnt, s->quad_work);
-        else
-            k_potential_tree<false><<<nblocks(n), kBlock, 0, st>>>(s->nodes, s->diag_pot, s->wtab, s->info, s->posm_s, s->perm,
-                                                                   s->curbuf, (float)(s->softening * s->softening), n, s->diag_phi,
-                                                                   s->diag_cnt, nullptr);
+        with_bool(s->multipole == NBMI_MULTIPOLE_QUADRUPOLE, [&](auto q) {
+            k_potential_tree<decltype(q)::value><<<nblocks(n), kBlock, 0, st>>>(
+                s->nodes, s->diag_pot, s->wtab, s->info, s->posm_s, s->perm, s->curbuf, (float)(s->softening * s->softening), n,
+                s->diag_phi, s->diag_cnt, decltype(q)::value ? s->quad_work : nullptr);
+        });
         if (hipGetLastError() != hipSuccess) {
             nbmi::set_error("k_potential_tree launch failed");
             rc = NBMI_ERR_HIP;
         }
     }
-    if (rc == 0) {
-        NBMI_HIP_CHECK(hipStreamSynchronize(st));
-        rc = check_device_error(s);  // NBMI_ERR_CAPACITY: the message of a step
-    }
-    // the same positions give the same tree: what the queries read is still that tree if it was before
-    NBMI_HIP_CHECK(hipMemcpyAsync(s->info, s->diag_info, sizeof(TreeInfo), hipMemcpyDeviceToDevice, st));
-    NBMI_HIP_CHECK(hipStreamSynchronize(st));
-    s->tree_valid = tree_valid && rc == 0;
-    s->maxabs_fused = maxabs_fused;
-    s->sort_bits = sort_bits;
-    s->step_dt = step_dt;
-    return rc;
+    return side.finish(rc, true);
 }
 
 int diag_refuse(nbmi_sim *s, const char *what) {
@@ -5301,7 +5344,7 @@ int diag_refuse(nbmi_sim *s, const char *what) {
 int nbmi_diagnostics(nbmi_sim *s, int with_potential, double *out12, int64_t *terms) {
     if (int rc = check_handle(s)) return rc;
     if (int rc = diag_refuse(s, "nbmi_diagnostics")) return rc;
-    if (!out12) { nbmi::set_error("null output"); return NBMI_ERR_ARG; }
+    if (int rc = require_out(out12)) return rc;
     const int64_t n = s->n;
     if (n == 0) {
         for (int k = 0; k < 12; k++) out12[k] = 0.0;
@@ -5345,7 +5388,7 @@ int nbmi_get_potentials_f64(nbmi_sim *s, double *out) {
     if (int rc = diag_refuse(s, "nbmi_get_potentials_f64")) return rc;
     const int64_t n = s->n;
     if (n == 0) return 0;
-    if (!out) { nbmi::set_error("null output"); return NBMI_ERR_ARG; }
+    if (int rc = require_out(out)) return rc;
     if (int rc = diag_potential(s)) return rc;
     k_unperm1_f64<<<nblocks(n), kBlock, 0, s->stream>>>(s->diag_phi, s->buf[s->curbuf].id, n, (double *)s->stage);
     NBMI_HIP_CHECK(hipGetLastError());
@@ -5375,25 +5418,20 @@ int knn_check(nbmi_sim *s, int k, const char *what) {
     }
     return 0;
 }
-// Enqueues the whole query on the compute stream and never waits: the header is saved, the octree of the current
-// positions built as nbmi_diagnostics builds it (step_dt = 0: no "auto" decision, the wave flags and force_all64 stay
-// the last step's; the host-side flags are put back), the rows written, the waves run, the header restored.  r2_k and
-// mass_k are in knn_r2 / knn_mass by state row afterwards.  A capacity error of the build stays in the sticky words
-// (k_knn_restore) for the next call that looks.  `count`: also sum the evaluated distances into knn_evals.
+// Enqueues the whole query on the compute stream and never waits: inside a SideBuild the octree of the current positions
+// is built with the query rows (node_ref), the rows written and the waves run.  r2_k and mass_k are in knn_r2 / knn_mass
+// by state row afterwards.  A capacity error of the build stays in the sticky words for the next call that looks.
+// `count`: also sum the evaluated distances into knn_evals.
 int knn_enqueue(nbmi_sim *s, int k, bool count) {
     const int64_t n = s->n;
     if (!s->knn_r2 && (dev_alloc(s, &s->knn_r2, n) || dev_alloc(s, &s->knn_mass, n) ||
-                       dev_alloc(s, &s->knn_rows, s->node_capacity + 2) || dev_alloc(s, &s->knn_info, 1) ||
-                       dev_alloc(s, &s->knn_evals, 1)))
+                       dev_alloc(s, &s->knn_rows, s->node_capacity + 2) || dev_alloc(s, &s->knn_evals, 1)))
         return NBMI_ERR_HIP;
     hipStream_t st = s->stream;
-    NBMI_HIP_CHECK(hipMemcpyAsync(s->knn_info, s->info, sizeof(TreeInfo), hipMemcpyDeviceToDevice, st));
     if (count) NBMI_HIP_CHECK(hipMemsetAsync(s->knn_evals, 0, sizeof(unsigned long long), st));
-    const bool tree_valid = s->tree_valid, maxabs_fused = s->maxabs_fused;
-    const int sort_bits = s->sort_bits;
-    const double step_dt = s->step_dt;
-    s->step_dt = 0.0;
-    int rc = enqueue_tree(s, -1, true);
+    SideBuild side(s);
+    if (side.rc) return side.rc;
+    int rc = enqueue_tree(s);
     if (rc == 0) {
         k_knn_rows<<<nblocks(s->own_node_rows), kBlock, 0, st>>>(s->nodes, s->nodes64, s->node_ref, s->perm, s->buf[s->curbuf],
                                                                   s->info, s->own_node_rows, s->knn_rows);
@@ -5405,17 +5443,7 @@ int knn_enqueue(nbmi_sim *s, int k, bool count) {
             rc = NBMI_ERR_HIP;
         }
     }
-    k_knn_restore<<<1, 64, 0, st>>>(s->info, s->knn_info);
-    if (hipGetLastError() != hipSuccess && rc == 0) {
-        nbmi::set_error("k_knn_restore launch failed");
-        rc = NBMI_ERR_HIP;
-    }
-    // the same positions give the same tree: what the queries read is still that tree if it was before
-    s->tree_valid = tree_valid && rc == 0;
-    s->maxabs_fused = maxabs_fused;
-    s->sort_bits = sort_bits;
-    s->step_dt = step_dt;
-    return rc;
+    return side.finish(rc, false);
 }
 // the synchronous form behind nbmi_knn / nbmi_get_densities_f64: errors of earlier steps first, as a getter reports
 // them, then the query and its own
@@ -5449,7 +5477,7 @@ int nbmi_knn(nbmi_sim *s, int k, double *r2_k, double *mass_k, int64_t *evals) {
 int nbmi_get_densities_f64(nbmi_sim *s, int k, double *rho) {
     if (int rc = check_handle(s)) return rc;
     if (int rc = knn_check(s, k, "nbmi_get_densities_f64")) return rc;
-    if (!rho) { nbmi::set_error("null output"); return NBMI_ERR_ARG; }
+    if (int rc = require_out(rho)) return rc;
     if (int rc = knn_query(s, k, false)) return rc;
     const int64_t n = s->n;
     k_knn_out<<<nblocks(n), kBlock, 0, s->stream>>>(s->knn_r2, s->knn_mass, s->buf[s->curbuf].id, n, nullptr, nullptr,
@@ -5510,47 +5538,29 @@ int nbmi_tree_stats(nbmi_sim *s, int64_t *num_nodes, int32_t *max_depth, double 
     if (num_nodes) *num_nodes = h.num_nodes;
     if (max_depth) *max_depth = h.max_level;
     if (bounds) *bounds = h.bounds;
-    if (h.error) {
-        nbmi::set_error("octree needs %lld nodes, more than the %lld rows allocated", (long long)h.num_nodes,
-                        (long long)s->node_capacity);
-        return NBMI_ERR_CAPACITY;
-    }
+    if (h.error) return capacity_error(s, h.num_nodes, "");
     return 0;
 }
 
-int nbmi_get_keys(nbmi_sim *s, uint64_t *key_hi, uint64_t *key_lo) {
+// both key getters; `decode`: back to the reference's octant digits where the handle sorts by Hilbert digits
+static int get_keys(nbmi_sim *s, uint64_t *key_hi, uint64_t *key_lo, bool decode, const char *what) {
     if (int rc = check_handle(s)) return rc;
     if (s->method != NBMI_METHOD_BARNES_HUT || !s->tree_valid) {
-        nbmi::set_error("nbmi_get_keys: call nbmi_build_tree first");
+        nbmi::set_error("%s: call nbmi_build_tree first", what);
         return NBMI_ERR_ARG;
     }
     const int64_t n = s->n;
     if (n == 0) return 0;
     uint64_t *o_hi = (uint64_t *)s->stage, *o_lo = o_hi + n;
-    k_keys_to_orig<<<nblocks(n), kBlock, 0, s->stream>>>(s->hi_s, s->lo_s, s->perm, s->buf[s->curbuf].id, n, s->hilbert ? 1 : 0, o_hi, o_lo);
+    k_keys_to_orig<<<nblocks(n), kBlock, 0, s->stream>>>(s->hi_s, s->lo_s, s->perm, s->buf[s->curbuf].id, n, decode && s->hilbert ? 1 : 0, o_hi, o_lo);
     NBMI_HIP_CHECK(hipGetLastError());
     if (key_hi) NBMI_HIP_CHECK(hipMemcpyAsync(key_hi, o_hi, (size_t)n * 8, hipMemcpyDeviceToHost, s->stream));
     if (key_lo) NBMI_HIP_CHECK(hipMemcpyAsync(key_lo, o_lo, (size_t)n * 8, hipMemcpyDeviceToHost, s->stream));
     NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
     return 0;
 }
-
-int nbmi_get_sort_keys(nbmi_sim *s, uint64_t *key_hi, uint64_t *key_lo) {
-    if (int rc = check_handle(s)) return rc;
-    if (s->method != NBMI_METHOD_BARNES_HUT || !s->tree_valid) {
-        nbmi::set_error("nbmi_get_sort_keys: call nbmi_build_tree first");
-        return NBMI_ERR_ARG;
-    }
-    const int64_t n = s->n;
-    if (n == 0) return 0;
-    uint64_t *o_hi = (uint64_t *)s->stage, *o_lo = o_hi + n;
-    k_keys_to_orig<<<nblocks(n), kBlock, 0, s->stream>>>(s->hi_s, s->lo_s, s->perm, s->buf[s->curbuf].id, n, 0, o_hi, o_lo);
-    NBMI_HIP_CHECK(hipGetLastError());
-    if (key_hi) NBMI_HIP_CHECK(hipMemcpyAsync(key_hi, o_hi, (size_t)n * 8, hipMemcpyDeviceToHost, s->stream));
-    if (key_lo) NBMI_HIP_CHECK(hipMemcpyAsync(key_lo, o_lo, (size_t)n * 8, hipMemcpyDeviceToHost, s->stream));
-    NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
-    return 0;
-}
+int nbmi_get_keys(nbmi_sim *s, uint64_t *key_hi, uint64_t *key_lo) { return get_keys(s, key_hi, key_lo, true, "nbmi_get_keys"); }
+int nbmi_get_sort_keys(nbmi_sim *s, uint64_t *key_hi, uint64_t *key_lo) { return get_keys(s, key_hi, key_lo, false, "nbmi_get_sort_keys"); }
 
 int nbmi_get_order(nbmi_sim *s, int32_t *order) {
     if (int rc = check_handle(s)) return rc;
@@ -5560,7 +5570,7 @@ int nbmi_get_order(nbmi_sim *s, int32_t *order) {
     }
     const int64_t n = s->n;
     if (n == 0) return 0;
-    if (!order) { nbmi::set_error("null output"); return NBMI_ERR_ARG; }
+    if (int rc = require_out(order)) return rc;
     k_order<<<nblocks(n), kBlock, 0, s->stream>>>(s->perm, s->buf[s->curbuf].id, n, (int32_t *)s->stage);
     NBMI_HIP_CHECK(hipGetLastError());
     NBMI_HIP_CHECK(hipMemcpyAsync(order, s->stage, (size_t)n * 4, hipMemcpyDeviceToHost, s->stream));
@@ -5603,7 +5613,7 @@ int nbmi_get_cell_moments(nbmi_sim *s, int32_t *level, uint64_t *key, double *mo
         nbmi::set_error("nbmi_get_cell_moments: call nbmi_build_tree in quadrupole mode first");
         return NBMI_ERR_ARG;
     }
-    if (!moments6) { nbmi::set_error("null output"); return NBMI_ERR_ARG; }
+    if (int rc = require_out(moments6)) return rc;
     if (int rc = nbmi_get_cells(s, level, key, capacity)) return rc;
     if (s->n == 0) { for (int k = 0; k < 6; k++) moments6[k] = 0.0; return 0; }
     int64_t nn = 0;
@@ -5639,7 +5649,7 @@ int nbmi_get_timers(nbmi_sim *s, double *ms5, int64_t *count, int reset) {
 int nbmi_walk_counters(nbmi_sim *s, int64_t *out8 /* 17 entries */) {
     if (int rc = check_handle(s)) return rc;
     int64_t *out3 = out8;
-    if (!out3) { nbmi::set_error("null output"); return NBMI_ERR_ARG; }
+    if (int rc = require_out(out3)) return rc;
     TreeInfo h;
     NBMI_HIP_CHECK(hipMemcpyAsync(&h, s->info, sizeof(h), hipMemcpyDeviceToHost, s->stream));
     NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
@@ -5667,6 +5677,8 @@ int nbmi_set_shard(nbmi_sim *s, int64_t begin, int64_t end) {
     }
     s->shard_begin = begin;
     s->shard_end = end;
+    // the next walk's maxabs_next may cover the shard only.  Nothing moved, so a built tree stays valid, and acc_valid
+    // is moot: a leapfrog handle gets here with the full range only
     s->maxabs_fused = false;
     return 0;
 }
@@ -5675,7 +5687,7 @@ int nbmi_export_shard(nbmi_sim *s, void *dev_rows) {
     if (int rc = check_handle(s)) return rc;
     const int64_t c = s->shard_end - s->shard_begin;
     if (c <= 0) return 0;
-    if (!dev_rows) { nbmi::set_error("null device buffer"); return NBMI_ERR_ARG; }
+    if (int rc = require_out(dev_rows, "null device buffer")) return rc;
     k_pack_rows<<<nblocks(c), kBlock, 0, s->stream>>>(s->buf[s->curbuf], s->shard_begin, s->shard_end, (double *)dev_rows);
     NBMI_HIP_CHECK(hipGetLastError());
     if (s->exchange_sync) NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
@@ -5687,10 +5699,12 @@ int nbmi_import_ranks(nbmi_sim *s, const void *dev_rows, int64_t begin, int64_t 
     if (begin < 0 || end < begin || end > s->n) { nbmi::set_error("nbmi_import_ranks: bad range"); return NBMI_ERR_ARG; }
     const int64_t c = end - begin;
     if (c == 0) return 0;
-    if (!dev_rows) { nbmi::set_error("null device buffer"); return NBMI_ERR_ARG; }
+    if (int rc = require_out(dev_rows, "null device buffer")) return rc;
     k_unpack_rows<<<nblocks(c), kBlock, 0, s->stream>>>(s->buf[s->curbuf], begin, end, (const double *)dev_rows);
     NBMI_HIP_CHECK(hipGetLastError());
     if (s->exchange_sync) NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
+    // rows of the state were replaced.  acc_valid is left alone: leapfrog handles are never sharded (nbmi_set_shard), and
+    // the exchange is the sharded protocol
     s->maxabs_fused = false;
     s->tree_valid = false;
     return 0;
@@ -5777,12 +5791,7 @@ nbmi_sim *nbmi_create_owner(int64_t n, const double *pos, const double *vel, con
         }
         if (e != hipSuccess) { nbmi::set_error("nbmi_create_owner: id upload failed: %s", hipGetErrorString(e)); rc = -2; }
     }
-    if (rc != 0) {
-        std::string keep = nbmi::get_error();
-        nbmi_destroy(s);
-        nbmi::set_error("%s", keep.c_str());
-        return nullptr;
-    }
+    if (rc != 0) return create_failed(s);
     return s;
 }
 
@@ -5792,7 +5801,7 @@ int nbmi_owner_boxes_per_rank(void) { return kBoxesPerRank; }
 int nbmi_owner_get_ids(nbmi_sim *s, int32_t *out) {
     if (int rc = owner_check(s, "nbmi_owner_get_ids")) return rc;
     if (s->n == 0) return 0;
-    if (!out) { nbmi::set_error("null output"); return NBMI_ERR_ARG; }
+    if (int rc = require_out(out)) return rc;
     NBMI_HIP_CHECK(hipMemcpyAsync(out, s->buf[s->curbuf].id, (size_t)s->n * 4, hipMemcpyDeviceToHost, s->stream));
     NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
     return 0;
@@ -5800,7 +5809,7 @@ int nbmi_owner_get_ids(nbmi_sim *s, int32_t *out) {
 
 int nbmi_owner_maxabs(nbmi_sim *s, void *dev_maxabs) {
     if (int rc = owner_check(s, "nbmi_owner_maxabs")) return rc;
-    if (!dev_maxabs) { nbmi::set_error("nbmi_owner_maxabs: null buffer"); return NBMI_ERR_ARG; }
+    if (int rc = require_out(dev_maxabs, "nbmi_owner_maxabs: null buffer")) return rc;
     if (int rc = enqueue_maxabs(s)) return rc;  // also clears the per-step tree header
     // a non-negative double and its bit pattern order the same way: the word IS the double
     NBMI_HIP_CHECK(hipMemcpyAsync(dev_maxabs, &s->info->maxabs_bits, 8, hipMemcpyDeviceToDevice, s->stream));
@@ -5888,17 +5897,18 @@ int nbmi_owner_adopt(nbmi_sim *s, const void *dev_recv_rows, int64_t n_recv, con
     // the tree header of this step: cleared, then the GLOBAL extent (every rank builds inside the same root cube)
     NBMI_HIP_CHECK(hipMemsetAsync(s->info, 0, offsetof(TreeInfo, wave_visits), st));
     NBMI_HIP_CHECK(hipMemcpyAsync(&s->info->maxabs_bits, dev_maxabs, 8, hipMemcpyDeviceToDevice, st));
-    s->step_dt = s->owner_dt;  // "auto" force precision is decided during the build
-    struct DtScope { nbmi_sim *s; ~DtScope() { s->step_dt = 0.0; } } dt_scope{s};
+    const DtScope dt_scope(s, s->owner_dt);
     if (n_new > 0 && s->world == 1) {
         // one owner: the plain build (no dead rows, no boxes to publish)
-        if (int rc = enqueue_local_sort(s, -1)) return rc;
+        if (int rc = enqueue_local_sort(s)) return rc;
         if (int rc = enqueue_global_tree(s, false)) return rc;
     } else if (n_new > 0) {
         // rank of every dead row among the dead rows (exclusive scan of the flags): their place behind the live ones
         k_dead_flags<<<nblocks(n_work), kBlock, 0, st>>>(s->let_dead, n_work, s->let_keep);
         if (int rc = enqueue_iscan(s, s->let_keep, n_work, s->let_scan)) return rc;
-        if (int rc = enqueue_local_sort(s, -1, n_work, n_new, s->let_dead)) return rc;
+        SortRequest sort;
+        sort.n_sort = n_work; sort.n_live = n_new; sort.dead = s->let_dead;
+        if (int rc = enqueue_local_sort(s, sort)) return rc;
         if (int rc = enqueue_global_tree(s)) return rc;
         // where this rank's bodies are: boxes of the cells of its tree (see k_box_flags).  The node count lives on
         // the device: launch for the row budget, the kernels stop at num_nodes themselves.
@@ -6009,7 +6019,7 @@ int nbmi_owner_export_let(nbmi_sim *s, const void *dev_boxes, const void *dev_ch
 
 int nbmi_owner_step_facts(nbmi_sim *s, int64_t *out4) {
     if (int rc = owner_check(s, "nbmi_owner_step_facts")) return rc;
-    if (!out4) { nbmi::set_error("nbmi_owner_step_facts: null output"); return NBMI_ERR_ARG; }
+    if (int rc = require_out(out4, "nbmi_owner_step_facts: null output")) return rc;
     out4[0] = out4[1] = 0;
     out4[2] = out4[3] = (int64_t)1 << 62;
     if (s->n == 0 || s->world == 1 || !s->h_info) return 0;
@@ -6121,8 +6131,7 @@ int nbmi_frame_keyframe(nbmi_sim *s, float *out_pos, float *out_col) {
     NBMI_HIP_CHECK(hipMemcpyAsync(out_col, s->colors, (size_t)n * 12, hipMemcpyDeviceToHost, st));
     NBMI_HIP_CHECK(hipStreamSynchronize(st));
     s->frame_have_prev = true;
-    if (s->method == NBMI_METHOD_BARNES_HUT) return check_device_error(s);
-    return 0;
+    return check_device_error(s);
 }
 
 int nbmi_frame_delta_i16(nbmi_sim *s, int16_t *out_dpos, int16_t *out_dcol) {
@@ -6144,8 +6153,7 @@ int nbmi_frame_delta_i16(nbmi_sim *s, int16_t *out_dpos, int16_t *out_dcol) {
     NBMI_HIP_CHECK(hipMemcpyAsync(out_dpos, s->frame_q, (size_t)n * 6, hipMemcpyDeviceToHost, st));
     NBMI_HIP_CHECK(hipMemcpyAsync(out_dcol, s->frame_q + 3 * n, (size_t)n * 6, hipMemcpyDeviceToHost, st));
     NBMI_HIP_CHECK(hipStreamSynchronize(st));
-    if (s->method == NBMI_METHOD_BARNES_HUT) return check_device_error(s);
-    return 0;
+    return check_device_error(s);
 }
 
 int nbmi_frame_set_previous(nbmi_sim *s, const float *pos, const float *col) {
@@ -6187,7 +6195,7 @@ size_t frame_item_bytes(int kind) { return kind == NBMI_FRAME_DELTA_I16 ? 6 : 12
 
 int nbmi_frame_begin(nbmi_sim *s, int kind, double max_speed, int *slot) {
     if (int rc = check_handle(s)) return rc;
-    if (!slot) { nbmi::set_error("nbmi_frame_begin: null output"); return NBMI_ERR_ARG; }
+    if (int rc = require_out(slot, "nbmi_frame_begin: null output")) return rc;
     if (s->owner) { nbmi::set_error("nbmi_frame_begin: not available on an owner-mode handle"); return NBMI_ERR_ARG; }
     if (kind != NBMI_FRAME_F32 && kind != NBMI_FRAME_KEY && kind != NBMI_FRAME_DELTA_I16) {
         nbmi::set_error("nbmi_frame_begin: unknown kind %d", kind);
@@ -6225,18 +6233,17 @@ int nbmi_frame_begin(nbmi_sim *s, int kind, double max_speed, int *slot) {
             dr2 = s->knn_r2;
             dmass = s->knn_mass;
         }
-        if (kind == NBMI_FRAME_F32)
-            k_frame_snapshot<NBMI_FRAME_F32><<<nblocks(n), kBlock, 0, s->stream>>>(cur, n, max_speed, s->colors, nullptr, first,
-                                                                                    second, s->info, se, hd, dr2, dmass, dlo, dhi);
-        else if (kind == NBMI_FRAME_KEY)
-            k_frame_snapshot<NBMI_FRAME_KEY><<<nblocks(n), kBlock, 0, s->stream>>>(cur, n, max_speed, s->colors, s->frame_prev,
-                                                                                    first, second, s->info, se, hd, dr2, dmass, dlo,
-                                                                                    dhi);
-        else {
-            float *rows = (float *)s->stage;  // (like frame_current) nothing later on the stream reads it before writing it
-            k_frame_snapshot<NBMI_FRAME_DELTA_I16><<<nblocks(n), kBlock, 0, s->stream>>>(cur, n, max_speed, s->colors, nullptr,
-                                                                                          rows, nullptr, s->info, se, hd, dr2, dmass,
-                                                                                          dlo, dhi);
+        // a delta frame's positions go to the staging rows: (like frame_current) nothing later on the stream reads them
+        // before writing them
+        float *rows = (float *)s->stage;
+        with_int<NBMI_FRAME_F32, NBMI_FRAME_KEY, NBMI_FRAME_DELTA_I16>(kind, [&](auto kv) {
+            constexpr int kKind = decltype(kv)::value;
+            constexpr bool kDelta = kKind == NBMI_FRAME_DELTA_I16;
+            k_frame_snapshot<kKind><<<nblocks(n), kBlock, 0, s->stream>>>(
+                cur, n, max_speed, s->colors, kKind == NBMI_FRAME_KEY ? s->frame_prev : nullptr, kDelta ? rows : first,
+                kDelta ? nullptr : second, s->info, se, hd, dr2, dmass, dlo, dhi);
+        });
+        if (kind == NBMI_FRAME_DELTA_I16) {
             k_frame_delta<<<nblocks(3 * n), kBlock, 0, s->stream>>>(rows, s->frame_prev, 3 * n, (int16_t *)first);
             k_frame_delta<<<nblocks(3 * n), kBlock, 0, s->stream>>>(s->colors, s->frame_prev + 3 * n, 3 * n, (int16_t *)second);
         }
@@ -6263,20 +6270,9 @@ int nbmi_frame_wait(nbmi_sim *s, int slot, const void **first, const void **seco
     const int64_t n = s->n;
     if (n != 0) {
         NBMI_HIP_CHECK(hipEventSynchronize(f.ev_done));  // this slot's copy only: the compute stream keeps running
-        const FrameHeader h = *(const FrameHeader *)f.host;
         // the words check_device_error reads, as they stood at the snapshot; they stay set on the device, so the next
         // nbmi_sync / getter still reports and clears them
-        if (h.sort_error) {
-            nbmi::set_error("device radix sort: a look-back spin timed out; the steps since the last synchronisation are invalid");
-            return NBMI_ERR_HIP;
-        }
-        if (h.max_run > 4096 && s->sort_bits < 63) s->sort_bits = s->sort_bits + 8 < 63 ? s->sort_bits + 8 : 63;
-        if (h.error || h.sticky_error) {
-            nbmi::set_error("octree needs %lld nodes, more than the %lld rows allocated (4N, as the reference); the "
-                            "bodies were not advanced from that step on",
-                            (long long)(h.sticky_error ? h.sticky_nodes : h.num_nodes), (long long)s->node_capacity);
-            return NBMI_ERR_CAPACITY;
-        }
+        if (int rc = decode_device_error(s, *(const FrameHeader *)f.host)) return rc;
     }
     const char *base = f.host + sizeof(FrameHeader);
     if (first) *first = base;
@@ -6384,7 +6380,7 @@ int nbmi_set_force_precision(nbmi_sim *s, int mode, double tau) {
         }
         if (dev_alloc(s, &s->nodesd, s->node_capacity + 2)) return NBMI_ERR_HIP;
         if (int rc = upload_walk_table(s)) return rc;
-        s->tree_valid = false;
+        s->tree_valid = false;  // the tree lacks the new records; positions and forces as computed stand (the other two survive)
     }
     s->force_prec = mode;
     if (mode == 0 && tau > 0.0) s->prec_tau = tau;

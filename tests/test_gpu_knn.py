@@ -232,6 +232,39 @@ def test_queries_do_not_disturb_the_run(gpu, integrator):
     assert a[3] == b[3], (a[3], b[3])
 
 
+@pytest.mark.parametrize("integrator", ["kick_drift", "leapfrog"])
+@pytest.mark.parametrize("multipole", ["monopole", "quadrupole"])
+def test_side_builds_between_steps_do_not_disturb_the_run(gpu, multipole, integrator):
+    """Every query that builds an octree of its own between two steps - the diagnostics' potential, the k-NN query, the
+    density-coloured frame - on 4 099 bodies (64 waves and a ragged one), in both multipole orders: the quadrupole
+    build always writes the query rows, and nbmi_frame_begin issues its query without waiting."""
+    p, v, m, G = _dist("galaxy", 4099)
+
+    def run(disturb):
+        sim = _bh(p, v, m, G=G, multipole=multipole, integrator=integrator)
+        try:
+            sim.set_force_precision("auto")
+            if disturb:
+                sim.set_color_mode("density", k=8, log10_range=(-6.0, 2.0))
+            shares = []
+            for i in range(8):
+                if disturb and i % 2 == 0:
+                    sim.diagnostics(potential=True)
+                    sim.knn(8)
+                    slot = sim.frame_begin("f32", 15.0)
+                    sim.frame_wait(slot)
+                    sim.frame_release(slot)
+                sim.step(0.2)
+                shares.append(sim.force_precision_share())
+            return sim.get_positions_f64(), sim.get_velocities(), sim.step_count(), shares
+        finally:
+            sim.close()
+    a, b = run(False), run(True)
+    assert np.array_equal(_bits(a[0]), _bits(b[0])) and np.array_equal(_bits(a[1]), _bits(b[1]))
+    assert a[2] == b[2] == 8
+    assert a[3] == b[3], (a[3], b[3])
+
+
 def test_density_colours(gpu):
     p, v, m, G = _dist("galaxy", 4096, seed=3)
     sim = _bh(p, v, m, G=G)
