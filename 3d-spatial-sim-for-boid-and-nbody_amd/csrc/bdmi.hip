@@ -84,52 +84,44 @@ __global__ __launch_bounds__(kBlock) void k_reorder(Boids a, BoidsAoS b, const u
 //     rank(cell) = occ[cell >> 5].prefix + popcount(occ[cell >> 5].bits & ((1 << (cell & 31)) - 1)).
 // 2 MB + 4 B per non-empty cell, all cache resident; the table indexed by cell (66 MB at the
 // reference grid, one random 128-byte line per lookup) was where the sweep's HBM traffic came from.
-// Two passes over the sorted keys (count "first boid of a cell" per tile, scan, emit).
-__device__ __forceinline__ bool first_of_cell(const uint32_t *keys_s, int64_t r, int64_t n) {
-    return r < n && (r == 0 || keys_s[r - 1] != keys_s[r]);
-}
-
-__global__ __launch_bounds__(kBlock) void k_first_count(const uint32_t *__restrict__ keys_s, int64_t n,
-                                                        uint32_t *__restrict__ tile_cnt) {
-    const int64_t base = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * vis::kItems;
-    unsigned c = 0;
-#pragma unroll
-    for (int k = 0; k < vis::kItems; k++) c += first_of_cell(keys_s, base + k, n) ? 1u : 0u;
-    unsigned total;
-    (void)vis::block_exclusive_scan(c, &total);
-    if (threadIdx.x == 0) tile_cnt[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(kBlock) void k_table(const uint32_t *__restrict__ keys_s, int64_t n,
-                                                  const uint32_t *__restrict__ tile_cnt, int64_t ntiles,
-                                                  uint2 *__restrict__ occ, int32_t *__restrict__ cell_start) {
-    const int64_t base = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * vis::kItems;
-    unsigned m = 0;
-#pragma unroll
-    for (int k = 0; k < vis::kItems; k++) m |= (first_of_cell(keys_s, base + k, n) ? 1u : 0u) << k;
-    unsigned total;
-    unsigned rank = tile_cnt[blockIdx.x] + vis::block_exclusive_scan(__popc(m), &total);
-    // a thread's 8 consecutive boids usually fall into one or two occupancy words: OR their bits
-    // locally and issue one atomic per word
-    uint32_t pend_word = 0xffffffffu, pend_bits = 0u;
-#pragma unroll
-    for (int k = 0; k < vis::kItems; k++) {
-        if (!((m >> k) & 1u)) continue;
-        const int64_t r = base + k;
-        const uint32_t c = keys_s[r];
-        cell_start[rank] = (int32_t)r;
-        if ((c >> 5) != pend_word) {
-            if (pend_bits) atomicOr(&occ[pend_word].x, pend_bits);
-            pend_word = c >> 5;
-            pend_bits = 0u;
-        }
-        pend_bits |= 1u << (c & 31);
-        if (r == 0 || (keys_s[r - 1] >> 5) != (c >> 5)) occ[c >> 5].y = rank;
-        rank++;
+// The tile compaction of scan.h over the sorted keys, selecting the first boid of each cell.
+struct FirstOfCell {
+    const uint32_t *keys_s;
+    __device__ unsigned operator()(int64_t first, int64_t n) const {
+        return scan::item_mask(first, n, [&](int64_t r) { return r == 0 || keys_s[r - 1] != keys_s[r]; });
     }
-    if (pend_bits) atomicOr(&occ[pend_word].x, pend_bits);
-    if (blockIdx.x == 0 && threadIdx.x == 0) cell_start[tile_cnt[ntiles]] = (int32_t)n;  // end of the last cell
-}
+};
+struct EmitTable {
+    const uint32_t *keys_s;
+    int64_t n;
+    const uint32_t *tile_cnt;
+    int64_t ntiles;
+    uint2 *occ;
+    int32_t *cell_start;
+    __device__ void operator()(unsigned m, int64_t first, int64_t slot) const {
+        unsigned rank = (unsigned)slot;
+        // a thread's 8 consecutive boids usually fall into one or two occupancy words: OR their bits
+        // locally and issue one atomic per word
+        uint32_t pend_word = 0xffffffffu, pend_bits = 0u;
+#pragma unroll
+        for (int k = 0; k < scan::kItems; k++) {
+            if (!((m >> k) & 1u)) continue;
+            const int64_t r = first + k;
+            const uint32_t c = keys_s[r];
+            cell_start[rank] = (int32_t)r;
+            if ((c >> 5) != pend_word) {
+                if (pend_bits) atomicOr(&occ[pend_word].x, pend_bits);
+                pend_word = c >> 5;
+                pend_bits = 0u;
+            }
+            pend_bits |= 1u << (c & 31);
+            if (r == 0 || (keys_s[r - 1] >> 5) != (c >> 5)) occ[c >> 5].y = rank;
+            rank++;
+        }
+        if (pend_bits) atomicOr(&occ[pend_word].x, pend_bits);
+        if (blockIdx.x == 0 && threadIdx.x == 0) cell_start[tile_cnt[ntiles]] = (int32_t)n;  // end of the last cell
+    }
+};
 
 // number of non-empty cells of the last grid; on demand only (bdmi_grid_info), one atomic per block
 __global__ __launch_bounds__(kBlock) void k_count_cells(const uint32_t *__restrict__ keys_s, int64_t n,
@@ -491,43 +483,31 @@ struct SlabSel {
         return what == 1 ? px[r] < lo_edge : px[r] >= hi_edge;
     }
 };
-__global__ __launch_bounds__(kBlock) void k_sel_count(SlabSel sel, int64_t n, uint32_t *__restrict__ tile_cnt) {
-    const int64_t base = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * vis::kItems;
-    unsigned c = 0;
-#pragma unroll
-    for (int k = 0; k < vis::kItems; k++) c += (base + k < n && sel(base + k)) ? 1u : 0u;
-    unsigned total;
-    (void)vis::block_exclusive_scan(c, &total);
-    if (threadIdx.x == 0) tile_cnt[blockIdx.x] = total;
-}
+struct SlabMask {
+    SlabSel sel;
+    __device__ unsigned operator()(int64_t first, int64_t n) const { return scan::item_mask(first, n, sel); }
+};
 // selected rows -> packed rows {p, v, c, id} of 10 doubles (dst_rows) or -> the SoA arrays `dst` (compaction)
-__global__ __launch_bounds__(kBlock) void k_sel_emit(SlabSel sel, Boids src, int64_t n, const uint32_t *__restrict__ tile_cnt,
-                                                     Boids dst, double *__restrict__ dst_rows) {
-    const int64_t base = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * vis::kItems;
-    unsigned m = 0;
-#pragma unroll
-    for (int k = 0; k < vis::kItems; k++) m |= ((base + k < n && sel(base + k)) ? 1u : 0u) << k;
-    unsigned total;
-    int64_t slot = (int64_t)tile_cnt[blockIdx.x] + vis::block_exclusive_scan(__popc(m), &total);
-#pragma unroll
-    for (int k = 0; k < vis::kItems; k++) {
-        if (!((m >> k) & 1u)) continue;
-        const int64_t r = base + k;
-        if (dst_rows) {
-            double *o = dst_rows + 10 * slot;
-            o[0] = src.px[r]; o[1] = src.py[r]; o[2] = src.pz[r];
-            o[3] = src.vx[r]; o[4] = src.vy[r]; o[5] = src.vz[r];
-            o[6] = src.cr[r]; o[7] = src.cg[r]; o[8] = src.cb[r];
-            o[9] = (double)src.id[r];
-        } else {
-            dst.px[slot] = src.px[r]; dst.py[slot] = src.py[r]; dst.pz[slot] = src.pz[r];
-            dst.vx[slot] = src.vx[r]; dst.vy[slot] = src.vy[r]; dst.vz[slot] = src.vz[r];
-            dst.cr[slot] = src.cr[r]; dst.cg[slot] = src.cg[r]; dst.cb[slot] = src.cb[r];
-            dst.id[slot] = src.id[r];
-        }
-        slot++;
+struct EmitRows {
+    Boids src, dst;
+    double *dst_rows;
+    __device__ void operator()(unsigned m, int64_t first, int64_t first_slot) const {
+        scan::for_each_item(m, first, first_slot, [&](int64_t r, int64_t slot) {
+            if (dst_rows) {
+                double *o = dst_rows + 10 * slot;
+                o[0] = src.px[r]; o[1] = src.py[r]; o[2] = src.pz[r];
+                o[3] = src.vx[r]; o[4] = src.vy[r]; o[5] = src.vz[r];
+                o[6] = src.cr[r]; o[7] = src.cg[r]; o[8] = src.cb[r];
+                o[9] = (double)src.id[r];
+            } else {
+                dst.px[slot] = src.px[r]; dst.py[slot] = src.py[r]; dst.pz[slot] = src.pz[r];
+                dst.vx[slot] = src.vx[r]; dst.vy[slot] = src.vy[r]; dst.vz[slot] = src.vz[r];
+                dst.cr[slot] = src.cr[r]; dst.cg[slot] = src.cg[r]; dst.cb[slot] = src.cb[r];
+                dst.id[slot] = src.id[r];
+            }
+        });
     }
-}
+};
 // owned rows that have left the slab stay for this step as ghosts (their new owner got a copy)
 __global__ __launch_bounds__(kBlock) void k_slab_demote(Boids a, int64_t n, double x_lo, double x_hi) {
     const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -640,17 +620,13 @@ int enqueue_grid(bdmi_flock *f, bool timed) {
     hipStream_t st = f->stream;
     if (timed) NBMI_HIP_CHECK(hipEventRecord(f->ev[0], st));
     k_assign<<<nblocks(n), kBlock, 0, st>>>(f->A, n, f->grid, f->keys, f->idx);
-    NBMI_HIP_CHECK(nbmi::sort_pairs_u32_u32(f->tmp_sort, f->tmp_sort_bytes, f->keys, f->keys_s, f->idx, f->perm,
-                                            (size_t)n, 0, f->key_bits, st));
+    NBMI_HIP_CHECK(nbmi::radix_sort_pairs_u32(f->tmp_sort, f->tmp_sort_bytes, f->keys, f->keys_s, f->idx, f->perm,
+                                              (size_t)n, 0, f->key_bits, st));
     if (timed) NBMI_HIP_CHECK(hipEventRecord(f->ev[1], st));
     k_reorder<<<nblocks(n), kBlock, 0, st>>>(f->A, f->B, f->perm, n);
     NBMI_HIP_CHECK(hipMemsetAsync(f->occ, 0, (size_t)f->occ_words * sizeof(uint2), st));
-    {
-        const int64_t ntiles = vis::tiles_for(n);
-        k_first_count<<<(int)ntiles, kBlock, 0, st>>>(f->keys_s, n, f->tile_cnt);
-        vis::k_scan_tiles<<<1, vis::kBlock, 0, st>>>(f->tile_cnt, ntiles);
-        k_table<<<(int)ntiles, kBlock, 0, st>>>(f->keys_s, n, f->tile_cnt, ntiles, f->occ, f->cell_start);
-    }
+    scan::enqueue_compact(FirstOfCell{f->keys_s}, n, f->tile_cnt,
+                          EmitTable{f->keys_s, n, f->tile_cnt, scan::tiles_for(n), f->occ, f->cell_start}, st);
     if (timed) NBMI_HIP_CHECK(hipEventRecord(f->ev[2], st));
     NBMI_HIP_CHECK(hipGetLastError());
     return 0;
@@ -687,14 +663,14 @@ static int bd_create_impl(bdmi_flock *f, const double *pos, const double *vel, c
     if (dev_alloc(f, &f->keys, c) || dev_alloc(f, &f->keys_s, c) || dev_alloc(f, &f->idx, c) ||
         dev_alloc(f, &f->perm, c) || dev_alloc(f, &f->occ, (size_t)f->occ_words) ||
         dev_alloc(f, &f->cell_start, (size_t)c + 2) ||
-        dev_alloc(f, &f->tile_cnt, (size_t)vis::tiles_for(c) + 2) || dev_alloc(f, &f->occupied, 1) ||
+        dev_alloc(f, &f->tile_cnt, (size_t)scan::tiles_for(c) + 2) || dev_alloc(f, &f->occupied, 1) ||
         dev_alloc(f, &f->stage, (size_t)12 * (c ? c : 1)))
         return -2;
-    f->tmp_sort_bytes = nbmi::sort_pairs32_temp_bytes((size_t)c, 0, f->key_bits);
+    f->tmp_sort_bytes = nbmi::radix_temp_bytes_u32((size_t)c, f->key_bits);
     char *t = nullptr;
     if (dev_alloc(f, &t, f->tmp_sort_bytes + 256)) return -2;
     f->tmp_sort = t;
-    NBMI_HIP_CHECK(nbmi::sort_init_temp(t, f->stream));
+    NBMI_HIP_CHECK(nbmi::radix_init_temp(t, f->stream));
     if (n > 0) {
         double *dp = f->stage, *dv = dp + 3 * n, *dc = dv + 3 * n;
         NBMI_HIP_CHECK(hipMemcpyAsync(dp, pos, (size_t)n * 24, hipMemcpyHostToDevice, f->stream));
@@ -787,10 +763,7 @@ bdmi_flock *bdmi_create_slab(int64_t n, const double *pos, const double *vel, co
 namespace {
 // rows selected by `sel`, in row order, to packed rows or to the SoA arrays `dst`; the count stays on the device
 int enqueue_select(bdmi_flock *f, const SlabSel &sel, int64_t n, Boids dst, double *dst_rows) {
-    const int64_t ntiles = vis::tiles_for(n);
-    k_sel_count<<<(int)ntiles, kBlock, 0, f->stream>>>(sel, n, f->tile_cnt);
-    vis::k_scan_tiles<<<1, vis::kBlock, 0, f->stream>>>(f->tile_cnt, ntiles);
-    k_sel_emit<<<(int)ntiles, kBlock, 0, f->stream>>>(sel, f->A, n, f->tile_cnt, dst, dst_rows);
+    scan::enqueue_compact(SlabMask{sel}, n, f->tile_cnt, EmitRows{f->A, dst, dst_rows}, f->stream);
     NBMI_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -805,7 +778,7 @@ int slab_compact_owned(bdmi_flock *f, int64_t *n_owned) {
     if (f->n > 0) {
         const SlabSel own{f->A.px, f->A.id, 0, 0.0, 0.0};
         if (int rc = enqueue_select(f, own, f->n, f->T, nullptr)) return rc;
-        NBMI_HIP_CHECK(hipMemcpyAsync(&total, f->tile_cnt + vis::tiles_for(f->n), 4, hipMemcpyDeviceToHost, f->stream));
+        NBMI_HIP_CHECK(hipMemcpyAsync(&total, f->tile_cnt + scan::tiles_for(f->n), 4, hipMemcpyDeviceToHost, f->stream));
         NBMI_HIP_CHECK(hipStreamSynchronize(f->stream));
         std::swap(f->A, f->T);
     }
@@ -834,7 +807,7 @@ int bdmi_slab_export(bdmi_flock *f, void *dev_left, int64_t *n_left, void *dev_r
     if (owned == 0) return 0;
     const double cell = f->grid.cell_size;
     uint32_t cl = 0, cr = 0;
-    const int64_t ntiles = vis::tiles_for(owned);
+    const int64_t ntiles = scan::tiles_for(owned);
     if (f->has_left) {
         const SlabSel sel{f->A.px, f->A.id, 1, f->x_lo + cell, 0.0};
         if (int rc = enqueue_select(f, sel, owned, Boids{}, (double *)dev_left)) return rc;
@@ -882,7 +855,7 @@ int bdmi_slab_get(bdmi_flock *f, double *rows10, int64_t capacity, int64_t *coun
     const SlabSel own{f->A.px, f->A.id, 0, 0.0, 0.0};
     if (int rc = enqueue_select(f, own, f->n, Boids{}, f->stage)) return rc;
     uint32_t total = 0;
-    NBMI_HIP_CHECK(hipMemcpyAsync(&total, f->tile_cnt + vis::tiles_for(f->n), 4, hipMemcpyDeviceToHost, f->stream));
+    NBMI_HIP_CHECK(hipMemcpyAsync(&total, f->tile_cnt + scan::tiles_for(f->n), 4, hipMemcpyDeviceToHost, f->stream));
     NBMI_HIP_CHECK(hipStreamSynchronize(f->stream));
     *count = total;
     const int64_t rows = (int64_t)total < capacity ? (int64_t)total : capacity;
@@ -921,10 +894,10 @@ int bdmi_step(bdmi_flock *f, double dt, int substeps) {
 // synchronise, then look at the radix sort's sticky error word (a timed-out look-back = a corrupt cell order)
 static int sync_checked(bdmi_flock *f) {
     unsigned sort_err = 0u;
-    if (f->tmp_sort) NBMI_HIP_CHECK(nbmi::sort_error_word(f->tmp_sort, &sort_err, f->stream));
+    if (f->tmp_sort) NBMI_HIP_CHECK(nbmi::radix_error_word(f->tmp_sort, &sort_err, f->stream));
     NBMI_HIP_CHECK(hipStreamSynchronize(f->stream));
     if (sort_err) {
-        NBMI_HIP_CHECK(nbmi::sort_init_temp(f->tmp_sort, f->stream));
+        NBMI_HIP_CHECK(nbmi::radix_init_temp(f->tmp_sort, f->stream));
         NBMI_HIP_CHECK(hipStreamSynchronize(f->stream));
         nbmi::set_error("device radix sort: a look-back spin timed out; the steps since the last synchronisation are invalid");
         return -2;
@@ -1126,9 +1099,9 @@ int nbmi::flock_visible_device(bdmi_flock *f, const double *cam12, double tan_h,
     *count = 0;
     *d_verts = *d_cols = nullptr;
     if (n == 0) return 0;
-    const int64_t ntiles = vis::tiles_for(n);
+    const int64_t ntiles = scan::tiles_for(n);
     if (!f->vis_flag) {
-        if (dev_alloc(f, &f->vis_flag, vis::flag_bytes(n)) || dev_alloc(f, &f->vis_slot, (size_t)ntiles * vis::kTile) ||
+        if (dev_alloc(f, &f->vis_flag, vis::flag_bytes(n)) || dev_alloc(f, &f->vis_slot, (size_t)ntiles * scan::kTile) ||
             dev_alloc(f, &f->vis_tiles, ntiles + 1) || dev_alloc(f, &f->vis_verts, (size_t)n * 18) ||
             dev_alloc(f, &f->vis_cols, (size_t)n * 18))
             return -2;
@@ -1140,10 +1113,8 @@ int nbmi::flock_visible_device(bdmi_flock *f, const double *cam12, double tan_h,
     const Boids &a = f->A;
     hipStream_t st = f->stream;
     vis::k_mark<<<nblocks(n), kBlock, 0, st>>>(a.px, a.py, a.pz, a.id, n, c, f->vis_flag, f->vis_slot);
-    vis::k_count<<<(int)ntiles, vis::kBlock, 0, st>>>(f->vis_flag, n, f->vis_tiles);
-    vis::k_scan_tiles<<<1, vis::kBlock, 0, st>>>(f->vis_tiles, ntiles);
-    EmitCones e{a, cone_length, cone_radius, f->vis_verts, f->vis_cols};
-    vis::k_emit<<<(int)ntiles, vis::kBlock, 0, st>>>(f->vis_flag, f->vis_slot, f->vis_tiles, n, n, e);
+    vis::enqueue_visible(f->vis_flag, f->vis_slot, n, f->vis_tiles,
+                         EmitCones{a, cone_length, cone_radius, f->vis_verts, f->vis_cols}, st);
     NBMI_HIP_CHECK(hipGetLastError());
     if (done) NBMI_HIP_CHECK(hipEventRecord(done, st));
     uint32_t total = 0;

@@ -27,38 +27,25 @@ struct Moment {
     double m, ml, x, xl, y, yl, z, zl;
 };
 
-// ---- sort / scan primitives (sortscan.hip) ---------------------------------------------
-size_t sort_pairs_temp_bytes(size_t n, int begin_bit, int end_bit);
-hipError_t sort_pairs_u64_u32(void *temp, size_t temp_bytes, const uint64_t *kin, uint64_t *kout,
-                              const uint32_t *vin, uint32_t *vout, size_t n, int begin_bit,
-                              int end_bit, hipStream_t s);
-hipError_t sort_keys_u64(void *temp, size_t temp_bytes, const uint64_t *kin, uint64_t *kout, size_t n, int begin_bit,
-                         int end_bit, hipStream_t s);  // keys only, on the bits [begin_bit, end_bit); same temp buffer
-size_t sort_pairs32_temp_bytes(size_t n, int begin_bit, int end_bit);
-hipError_t sort_init_temp(void *temp, hipStream_t s);                          // once per freshly allocated temp buffer
-hipError_t sort_error_word(const void *temp, unsigned *out, hipStream_t s);  // sticky: 1 = some sort since then went wrong
-const void *sort_error_device_word(const void *temp);  // where that word lives on the device (kernels that copy it along)
-hipError_t sort_pairs_u32_u32(void *temp, size_t temp_bytes, const uint32_t *kin, uint32_t *kout,
-                              const uint32_t *vin, uint32_t *vout, size_t n, int begin_bit,
-                              int end_bit, hipStream_t s);
-
-// the hand-written radix sort (radix.hip): by key bits [begin_bit, end_bit), stable, ping-pong inside `temp`
+// ---- device sort (radix.hip) ------------------------------------------------------------
+// by key bits [begin_bit, end_bit), stable, ping-pong inside `temp`
 size_t radix_temp_bytes_u64(size_t n, int bits);
 size_t radix_temp_bytes_u32(size_t n, int bits);
 hipError_t radix_sort_pairs_u64(void *temp, size_t temp_bytes, const uint64_t *kin, uint64_t *kout, const uint32_t *vin,
                                 uint32_t *vout, size_t n, int begin_bit, int end_bit, hipStream_t s);
 hipError_t radix_sort_pairs_u32(void *temp, size_t temp_bytes, const uint32_t *kin, uint32_t *kout, const uint32_t *vin,
                                 uint32_t *vout, size_t n, int begin_bit, int end_bit, hipStream_t s);
-// keys-only: sorts on the bits [begin_bit, end_bit) of the keys, the other bits travel along (stable)
+// keys-only: sorts on the bits [begin_bit, end_bit) of the keys, the other bits travel along (stable); the pair
+// form's temp buffer is the larger and serves both
 size_t radix_keys_temp_bytes_u64(size_t n, int bits);
 size_t radix_keys_temp_bytes_u32(size_t n, int bits);
 hipError_t radix_sort_keys_u64(void *temp, size_t temp_bytes, const uint64_t *kin, uint64_t *kout, size_t n, int begin_bit,
                                int end_bit, hipStream_t s);
 hipError_t radix_sort_keys_u32(void *temp, size_t temp_bytes, const uint32_t *kin, uint32_t *kout, size_t n, int begin_bit,
                                int end_bit, hipStream_t s);
-hipError_t radix_init_temp(void *temp, hipStream_t s);
-hipError_t radix_error_word(const void *temp, unsigned *out, hipStream_t s);
-const void *radix_error_device_word(const void *temp);
+hipError_t radix_init_temp(void *temp, hipStream_t s);                          // once per freshly allocated temp buffer
+hipError_t radix_error_word(const void *temp, unsigned *out, hipStream_t s);  // sticky: 1 = some sort since then went wrong
+const void *radix_error_device_word(const void *temp);  // where that word lives on the device (kernels that copy it along)
 
 // ---- point renderer (render.hip) reads a simulation handle through these (nbmi.hip) ---------------
 }  // namespace nbmi

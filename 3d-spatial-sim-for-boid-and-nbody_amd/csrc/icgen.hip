@@ -332,7 +332,7 @@ struct Scratch {
 int disk(const DiskP &P, uint64_t seed, IcArrays A, Scratch &S, size_t tmp_bytes, hipStream_t st) {
     if (P.count == 0) return 0;
     k_disk_positions<<<nblocks(P.count), kBlock, 0, st>>>(P, seed, A.x, A.y, A.z, S.radius, S.angle, S.rkey, S.ridx);
-    NBMI_HIP_CHECK(sort_pairs_u64_u32(S.tmp, tmp_bytes, S.rkey, S.rkey_s, S.ridx, S.ridx_s, (size_t)P.count, 0, 63, st));
+    NBMI_HIP_CHECK(radix_sort_pairs_u64(S.tmp, tmp_bytes, S.rkey, S.rkey_s, S.ridx, S.ridx_s, (size_t)P.count, 0, 63, st));
     k_disk_velocities<<<nblocks(P.count), kBlock, 0, st>>>(P, seed, S.radius, S.angle, S.ridx_s, A.vx, A.vy, A.vz);
     NBMI_HIP_CHECK(hipGetLastError());
     return 0;
@@ -343,7 +343,7 @@ int disk(const DiskP &P, uint64_t seed, IcArrays A, Scratch &S, size_t tmp_bytes
 int ic_generate(int distribution, int64_t n, double R, double G, uint64_t seed, IcArrays A, hipStream_t st) {
     if (n == 0) return 0;
     Scratch S;
-    const size_t tmp_bytes = sort_pairs_temp_bytes((size_t)n, 0, 63);
+    const size_t tmp_bytes = radix_temp_bytes_u64((size_t)n, 63);
     NBMI_HIP_CHECK(hipMalloc((void **)&S.radius, n * 8));
     NBMI_HIP_CHECK(hipMalloc((void **)&S.angle, n * 8));
     NBMI_HIP_CHECK(hipMalloc((void **)&S.part, kSumBlocks * 3 * 8));
@@ -352,7 +352,7 @@ int ic_generate(int distribution, int64_t n, double R, double G, uint64_t seed, 
     NBMI_HIP_CHECK(hipMalloc((void **)&S.ridx, n * 4));
     NBMI_HIP_CHECK(hipMalloc((void **)&S.ridx_s, n * 4));
     NBMI_HIP_CHECK(hipMalloc(&S.tmp, tmp_bytes + 256));
-    NBMI_HIP_CHECK(sort_init_temp(S.tmp, st));
+    NBMI_HIP_CHECK(radix_init_temp(S.tmp, st));
     k_fill_mass_id<<<nblocks(n), kBlock, 0, st>>>(n, distribution == NBMI_IC_FILAMENT ? 0.1 : 1.0, A.m, A.id);
     bool remove_com = false;
     if (distribution == NBMI_IC_GALAXY) {  // presets.py:104-146
@@ -397,7 +397,7 @@ int ic_generate(int distribution, int64_t n, double R, double G, uint64_t seed, 
     }
     NBMI_HIP_CHECK(hipGetLastError());
     unsigned sort_err = 0u;
-    NBMI_HIP_CHECK(sort_error_word(S.tmp, &sort_err, st));
+    NBMI_HIP_CHECK(radix_error_word(S.tmp, &sort_err, st));
     NBMI_HIP_CHECK(hipStreamSynchronize(st));  // scratch is freed on return
     if (sort_err) {
         set_error("device radix sort: a look-back spin timed out while ranking the generated bodies");

@@ -459,8 +459,8 @@ struct Mom4 {
     double m, x, y, z;
     int c;
 };
-__device__ __forceinline__ Mom4 m4_add(const Mom4 &a, const Mom4 &b) { return Mom4{a.m + b.m, a.x + b.x, a.y + b.y, a.z + b.z, a.c + b.c}; }
-__device__ __forceinline__ Mom4 m4_shfl_up(const Mom4 &v, int d) {
+__device__ __forceinline__ Mom4 operator+(const Mom4 &a, const Mom4 &b) { return Mom4{a.m + b.m, a.x + b.x, a.y + b.y, a.z + b.z, a.c + b.c}; }
+__device__ __forceinline__ Mom4 lane_up(const Mom4 &v, int d) {  // scan.h's lane shift for this type
     return Mom4{__shfl_up(v.m, d), __shfl_up(v.x, d), __shfl_up(v.y, d), __shfl_up(v.z, d), __shfl_up(v.c, d)};
 }
 
@@ -484,9 +484,8 @@ __global__ __launch_bounds__(kBlock) void k_gather_scan(Bodies cur, const uint32
                                                         const TreeInfo *__restrict__ info, int hilbert) {
     // kLean (lean build; key_lo and lo_s are null): no low word is gathered or stored; the rare neighbours with equal
     // upper words get theirs from key_low_word
-    __shared__ Mom4 wtot[kBlock / 64];
     __shared__ int wflag[kBlock / 64];
-    int nflag = 0;  // (thread 0) waves of this tile whose density asks for float64 forces
+    int nflag = 0;  // (lane 0 of each wave) the wave's rounds whose density asks for float64 forces
     __shared__ int dl[kBlock + 1];  // delta of the round's ranks, dl[0] = delta of the rank before the round
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     Mom4 carry{0.0, 0.0, 0.0, 0.0, 0};  // the rounds before this one (plain float64: at most 2047 terms)
@@ -551,7 +550,7 @@ __global__ __launch_bounds__(kBlock) void k_gather_scan(Bodies cur, const uint32
             const int flag = dens > dens_thr ? 1 : 0;
             if (lane == 0) {
                 if (r0 + 64 * w < n) wave_flag[(r0 >> 6) + w] = (unsigned char)flag;
-                wflag[w] = (r0 + 64 * w < n) ? flag : 0;
+                nflag += (r0 + 64 * w < n) ? flag : 0;
             }
         }
         dl[t + 1] = d;
@@ -573,38 +572,24 @@ __global__ __launch_bounds__(kBlock) void k_gather_scan(Bodies cur, const uint32
             const int dp = dl[t];
             v.c = d > dp ? d - dp : 0;
         }
-        // inclusive scan over the 256 ranks of the round
-        Mom4 inc = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const Mom4 u = m4_shfl_up(inc, o);
-            if (lane >= o) inc = m4_add(u, inc);
-        }
-        if (lane == 63) wtot[w] = inc;
-        __syncthreads();
-        if (wave_flag && t == 0) nflag += wflag[0] + wflag[1] + wflag[2] + wflag[3];
-        Mom4 off = carry, tot{0.0, 0.0, 0.0, 0.0, 0};
-#pragma unroll
-        for (int q = 0; q < kBlock / 64; q++) {
-            if (q < w) off = m4_add(off, wtot[q]);
-            tot = m4_add(tot, wtot[q]);
-        }
-        inc = m4_add(off, inc);
-        carry = m4_add(carry, tot);
+        // scan over the 256 ranks of the round, continued from the rounds before it.  The exclusive value is the
+        // neighbour's inclusive one, not inclusive - own (own is exactly representable in the sum only for cnt).
+        // The scan's trailing barrier also covers the reuse of dl by the next round.
+        const scan::Scanned<Mom4> sc = scan::block_scan<kBlock>(v, carry, scan::Sum());
+        carry = carry + sc.total;
         if (r <= n) {
-            // exclusive = inclusive - own (own is exactly representable in the sum only for cnt; for the moments take
-            // the neighbour's inclusive value instead of subtracting)
-            Mom4 ex = m4_shfl_up(inc, 1);
-            if (lane == 0) ex = off;
-            S[r] = make_double4(ex.m, ex.x, ex.y, ex.z);
-            PexL[r] = ex.c;
+            S[r] = make_double4(sc.excl.m, sc.excl.x, sc.excl.y, sc.excl.z);
+            PexL[r] = sc.excl.c;
         }
-        __syncthreads();  // wtot / dl are reused by the next round
+    }
+    if (wave_flag) {
+        if (lane == 0) wflag[w] = nflag;
+        __syncthreads();
     }
     if (t == 0) {
         sub_tot[blockIdx.x] = make_double4(carry.m, carry.x, carry.y, carry.z);
         sub_cnt[blockIdx.x] = carry.c;
-        if (wave_flag) sub_flag[blockIdx.x] = nflag;
+        if (wave_flag) sub_flag[blockIdx.x] = wflag[0] + wflag[1] + wflag[2] + wflag[3];
     }
 }
 
@@ -616,12 +601,12 @@ struct SubVal {
     dd m, x, y, z;
     long long c;
 };
-__device__ __forceinline__ SubVal sub_add(const SubVal &a, const SubVal &b) {
+__device__ __forceinline__ SubVal operator+(const SubVal &a, const SubVal &b) {
     return SubVal{dd_add(a.m, b.m), dd_add(a.x, b.x), dd_add(a.y, b.y), dd_add(a.z, b.z), a.c + b.c};
 }
 __device__ __forceinline__ SubVal sub_zero() { return SubVal{{0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}, 0}; }
 __device__ __forceinline__ dd dd_shfl_up(const dd &v, int d) { return dd{__shfl_up(v.h, d), __shfl_up(v.l, d)}; }
-__device__ __forceinline__ SubVal sub_shfl_up(const SubVal &v, int d) {
+__device__ __forceinline__ SubVal lane_up(const SubVal &v, int d) {  // scan.h's lane shift for this type
     return SubVal{dd_shfl_up(v.m, d), dd_shfl_up(v.x, d), dd_shfl_up(v.y, d), dd_shfl_up(v.z, d), __shfl_up(v.c, d)};
 }
 // the system-wide half of force precision "auto" (TreeInfo::force_all64): enter above a third of the waves, leave below a quarter
@@ -637,7 +622,6 @@ __global__ __launch_bounds__(kSubScanThreads) void k_scan_subtiles(const double4
                                                                    Moment *__restrict__ T, int32_t *__restrict__ subPex,
                                                                    const int32_t *__restrict__ sub_flag, int64_t nwaves,
                                                                    int enter_pm, int leave_pm, TreeInfo *info) {
-    __shared__ SubVal wsum[kSubScanThreads / 64];
     __shared__ long long fsum[kSubScanThreads / 64];
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     const int64_t chunk = (nsub + kSubScanThreads - 1) / kSubScanThreads;
@@ -646,7 +630,7 @@ __global__ __launch_bounds__(kSubScanThreads) void k_scan_subtiles(const double4
     long long fl = 0;
     for (int64_t i = b; i < e; i++) {
         const double4 q = sub_tot[i];
-        acc = sub_add(acc, SubVal{{q.x, 0.0}, {q.y, 0.0}, {q.z, 0.0}, {q.w, 0.0}, (long long)sub_cnt[i]});
+        acc = acc + SubVal{{q.x, 0.0}, {q.y, 0.0}, {q.z, 0.0}, {q.w, 0.0}, (long long)sub_cnt[i]};
         if (sub_flag) fl += sub_flag[i];
     }
     if (sub_flag) {
@@ -659,14 +643,8 @@ __global__ __launch_bounds__(kSubScanThreads) void k_scan_subtiles(const double4
         for (int o = 32; o > 0; o >>= 1) fl += __shfl_xor(fl, o);
         if (lane == 0) fsum[w] = fl;
     }
-    SubVal inc = acc;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const SubVal u = sub_shfl_up(inc, o);
-        if (lane >= o) inc = sub_add(u, inc);
-    }
-    if (lane == 63) wsum[w] = inc;
-    __syncthreads();
+    // exclusive prefix of this thread's chunk
+    SubVal run = scan::block_scan<kSubScanThreads>(acc, sub_zero(), scan::Sum()).excl;
     if (sub_flag && t == 0) {
         long long tot = 0;
         for (int q = 0; q < kSubScanThreads / 64; q++) tot += fsum[q];
@@ -674,16 +652,11 @@ __global__ __launch_bounds__(kSubScanThreads) void k_scan_subtiles(const double4
         info->n_waves = (int)nwaves;
         info->force_all64 = all64_rule(info->force_all64, tot, nwaves, enter_pm, leave_pm);
     }
-    SubVal off = sub_zero();
-    for (int q = 0; q < w; q++) off = sub_add(off, wsum[q]);
-    SubVal run = sub_shfl_up(inc, 1);
-    if (lane == 0) run = sub_zero();
-    run = sub_add(off, run);  // exclusive prefix of this thread's chunk
     for (int64_t i = b; i < e; i++) {
         T[i] = Moment{run.m.h, run.m.l, run.x.h, run.x.l, run.y.h, run.y.l, run.z.h, run.z.l};
         subPex[i] = (int32_t)run.c;
         const double4 q = sub_tot[i];
-        run = sub_add(run, SubVal{{q.x, 0.0}, {q.y, 0.0}, {q.z, 0.0}, {q.w, 0.0}, (long long)sub_cnt[i]});
+        run = run + SubVal{{q.x, 0.0}, {q.y, 0.0}, {q.z, 0.0}, {q.w, 0.0}, (long long)sub_cnt[i]};
     }
 }
 
@@ -1729,10 +1702,8 @@ __device__ __forceinline__ void publish_maxabs(const WalkTable *tab, double lane
 // (the launch has 8 jmax workgroups) and at least one.  One workgroup: per-thread chunk sums, scan, the seven
 // thread(s) whose chunk holds a cut find it.  All-zero times (first step) give equal ranges.
 __global__ __launch_bounds__(1024) void k_xcd_bounds(const unsigned *__restrict__ wave_cycles, int nb, int jmax, int *__restrict__ bounds) {
-    __shared__ unsigned long long wsum[16];
-    __shared__ unsigned long long total_s;
     __shared__ int cut[9];
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int t = threadIdx.x;
     const int chunk = (nb + 1023) / 1024;
     const int b = t * chunk < nb ? t * chunk : nb, e = b + chunk < nb ? b + chunk : nb;
     unsigned long long acc = 0;
@@ -1740,25 +1711,11 @@ __global__ __launch_bounds__(1024) void k_xcd_bounds(const unsigned *__restrict_
         const uint4 q = reinterpret_cast<const uint4 *>(wave_cycles)[i];
         acc += (unsigned long long)q.x + q.y + q.z + q.w + 1ull;  // + 1: all-zero input still cuts into equal parts
     }
-    unsigned long long inc = acc;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned long long u = __shfl_up(inc, o);
-        if (lane >= o) inc += u;
-    }
-    if (lane == 63) wsum[w] = inc;
-    __syncthreads();
-    unsigned long long off = 0, total = 0;
-    for (int q = 0; q < 16; q++) {
-        if (q < w) off += wsum[q];
-        total += wsum[q];
-    }
-    inc += off;
-    if (t == 0) { total_s = total; cut[0] = 0; cut[8] = nb; }
-    __syncthreads();
-    const unsigned long long ex = inc - acc;  // work before this thread's chunk
+    const scan::Scanned<unsigned long long> sc = scan::block_scan<1024>(acc, 0ull, scan::Sum());
+    const unsigned long long ex = sc.excl, inc = sc.incl;  // work before this thread's chunk, and with it
+    if (t == 0) { cut[0] = 0; cut[8] = nb; }
     for (int k = 1; k < 8; k++) {
-        const unsigned long long target = total_s / 8ull * (unsigned long long)k;
+        const unsigned long long target = sc.total / 8ull * (unsigned long long)k;
         if (b < e && ex <= target && target < inc) {
             unsigned long long run = ex;
             int i = b;
@@ -2867,11 +2824,10 @@ __global__ void k_super_boxes(const double *__restrict__ boxes, int nsupers, dou
     for (int c = 0; c < 6; c++) supers[6 * sidx + c] = v[c];
 }
 
-// ---- plain int32 exclusive scan (three phases, like the moment scan); blockIdx.y selects one of several
-// equally long arrays `stride` elements apart (one per destination rank) ---------------------------------
+// ---- plain int32 exclusive scan (three phases: tile sums, scan::k_scan_values over them, apply); blockIdx.y selects
+// one of several equally long arrays `stride` elements apart (one per destination rank) -------------------
 __global__ __launch_bounds__(kBlock) void k_iscan_reduce(const int32_t *__restrict__ in, int64_t n, int64_t stride,
                                                          int32_t *__restrict__ tile_sum, int64_t tstride) {
-    __shared__ int red[kBlock / 64];
     in += (int64_t)blockIdx.y * stride;
     tile_sum += (int64_t)blockIdx.y * tstride;
     const int64_t base = (int64_t)blockIdx.x * kScanTile;
@@ -2881,47 +2837,13 @@ __global__ __launch_bounds__(kBlock) void k_iscan_reduce(const int32_t *__restri
         const int64_t i = base + (int64_t)k * kBlock + threadIdx.x;
         acc += i < n ? in[i] : 0;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int t = 0;
-        for (int w = 0; w < kBlock / 64; w++) t += red[w];
-        tile_sum[blockIdx.x] = t;
-    }
-}
-__global__ __launch_bounds__(kBlock) void k_iscan_tiles(int32_t *__restrict__ tile_sum, int64_t ntiles, int64_t tstride) {
-    __shared__ int wsum[kBlock / 64];
-    __shared__ int carry_s;
-    tile_sum += (int64_t)blockIdx.y * tstride;
-    if (threadIdx.x == 0) carry_s = 0;
-    __syncthreads();
-    for (int64_t base = 0; base < ntiles; base += kBlock) {
-        const int64_t i = base + threadIdx.x;
-        const int own = i < ntiles ? tile_sum[i] : 0;
-        int v = own;
-        const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int o = __shfl_up(v, d);
-            if (lane >= d) v += o;
-        }
-        if (lane == 63) wsum[w] = v;
-        __syncthreads();
-        int off = carry_s;
-        for (int k = 0; k < w; k++) off += wsum[k];
-        if (i < ntiles) tile_sum[i] = off + v - own;
-        __syncthreads();
-        if (threadIdx.x == kBlock - 1) carry_s = off + v;
-        __syncthreads();
-    }
+    const int total = scan::block_scan<kBlock>(acc, 0, scan::Sum()).total;
+    if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
 }
 // out[i] = sum of in[0..i); entry n receives the total
 __global__ __launch_bounds__(kBlock) void k_iscan_apply(const int32_t *__restrict__ in, int64_t n, int64_t stride,
                                                         const int32_t *__restrict__ tile_off, int64_t tstride,
                                                         int32_t *__restrict__ out) {
-    __shared__ int wsum[kBlock / 64];
     in += (int64_t)blockIdx.y * stride;
     out += (int64_t)blockIdx.y * stride;
     tile_off += (int64_t)blockIdx.y * tstride;
@@ -2929,17 +2851,7 @@ __global__ __launch_bounds__(kBlock) void k_iscan_apply(const int32_t *__restric
     int v[kScanItems], sum = 0;
 #pragma unroll
     for (int k = 0; k < kScanItems; k++) { v[k] = base + k < n ? in[base + k] : 0; sum += v[k]; }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int inc = sum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(inc, d);
-        if (lane >= d) inc += o;
-    }
-    if (lane == 63) wsum[w] = inc;
-    __syncthreads();
-    int run = tile_off[blockIdx.x] + inc - sum;
-    for (int k = 0; k < w; k++) run += wsum[k];
+    int run = scan::block_scan<kBlock>(sum, tile_off[blockIdx.x], scan::Sum()).excl;
 #pragma unroll
     for (int k = 0; k < kScanItems; k++) {
         if (base + k <= n) out[base + k] = run;
@@ -4393,14 +4305,14 @@ int enqueue_local_sort(nbmi_sim *s, const SortRequest &req = {}) {
     if (packed) {
         // one 8-byte word per body through the passes instead of an 8-byte key and a 4-byte index: the index sits
         // below the prefix, so a stable sort of the pairs and a sort of the words on the prefix bits give the same order
-        NBMI_HIP_CHECK(nbmi::sort_keys_u64(s->tmp_sort, s->tmp_sort_bytes, s->packed, s->packed_s, (size_t)n, kPackIdxBits,
-                                           kPackIdxBits + s->sort_bits, st));
+        NBMI_HIP_CHECK(nbmi::radix_sort_keys_u64(s->tmp_sort, s->tmp_sort_bytes, s->packed, s->packed_s, (size_t)n, kPackIdxBits,
+                                                 kPackIdxBits + s->sort_bits, st));
         // the tie-fix reads the unsorted key_hi, so it writes where the pair sort would have put its output: `perm` /
         // `hi_s` are final without a swap
         k_tiefix<true><<<nblocks(n), kBlock, 0, st>>>(s->packed_s, s->key_hi, key_lo, nullptr, shift, s->perm, s->hi_s, n, s->info, cur, hil);
     } else {
-        NBMI_HIP_CHECK(nbmi::sort_pairs_u64_u32(s->tmp_sort, s->tmp_sort_bytes, s->key_hi, s->hi_s, s->idx, s->perm,
-                                                (size_t)n, shift, 63, st));
+        NBMI_HIP_CHECK(nbmi::radix_sort_pairs_u64(s->tmp_sort, s->tmp_sort_bytes, s->key_hi, s->hi_s, s->idx, s->perm,
+                                                  (size_t)n, shift, 63, st));
         k_tiefix<false><<<nblocks(n), kBlock, 0, st>>>(s->hi_s, nullptr, key_lo, s->perm, shift, s->idx, s->key_hi, n, s->info, cur, hil,
                                                        dead ? s->let_scan : nullptr, n - n_live);
         // the finished permutation / sorted upper words are `perm` / `hi_s` from here on; the old buffers take
@@ -4733,11 +4645,11 @@ int check_device_error(nbmi_sim *s) {
     TreeInfo h;
     unsigned sort_err = 0u;
     NBMI_HIP_CHECK(hipMemcpyAsync(&h, s->info, sizeof(h), hipMemcpyDeviceToHost, s->stream));
-    if (s->tmp_sort) NBMI_HIP_CHECK(nbmi::sort_error_word(s->tmp_sort, &sort_err, s->stream));
+    if (s->tmp_sort) NBMI_HIP_CHECK(nbmi::radix_error_word(s->tmp_sort, &sort_err, s->stream));
     NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
     const int rc = decode_device_error(s, FrameHeader{h.error, h.sticky_error, h.max_run, sort_err, h.num_nodes, h.sticky_nodes, {}});
     if (sort_err) {
-        NBMI_HIP_CHECK(nbmi::sort_init_temp(s->tmp_sort, s->stream));
+        NBMI_HIP_CHECK(nbmi::radix_init_temp(s->tmp_sort, s->stream));
         NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
         s->tree_valid = false;  // (the positions and the header are as they were: the other two survive)
     } else if (rc) {
@@ -4928,11 +4840,11 @@ static int create_impl(nbmi_sim *s, const double *pos, const double *vel, const 
             false)
             return -2;
         s->own_node_rows = own_rows;
-        s->tmp_sort_bytes = nbmi::sort_pairs_temp_bytes((size_t)c, 0, 63);
+        s->tmp_sort_bytes = nbmi::radix_temp_bytes_u64((size_t)c, 63);
         char *t = nullptr;
         if (dev_alloc(s, &t, s->tmp_sort_bytes + 256)) return -2;
         s->tmp_sort = t;
-        NBMI_HIP_CHECK(nbmi::sort_init_temp(t, s->stream));
+        NBMI_HIP_CHECK(nbmi::radix_init_temp(t, s->stream));
         if (dev_alloc(s, &s->wtab, 3) || upload_walk_table(s)) return -2;
     }
     // upload AoS host arrays through the staging buffer and split to SoA
@@ -5728,7 +5640,8 @@ int enqueue_iscan(nbmi_sim *s, const int32_t *in, int64_t n, int32_t *out, int b
     const int64_t tstride = s->let_tile_stride;
     const dim3 grid((unsigned)ntiles, (unsigned)batch);
     k_iscan_reduce<<<grid, kBlock, 0, s->stream>>>(in, n, stride, s->let_tiles, tstride);
-    k_iscan_tiles<<<dim3(1, (unsigned)batch), kBlock, 0, s->stream>>>(s->let_tiles, ntiles, tstride);
+    scan::k_scan_values<<<dim3(1, (unsigned)batch), scan::kScanThreads, 0, s->stream>>>(s->let_tiles, s->let_tiles, ntiles,
+                                                                                        tstride, 0, scan::Sum());
     k_iscan_apply<<<grid, kBlock, 0, s->stream>>>(in, n, stride, s->let_tiles, tstride, out);
     NBMI_HIP_CHECK(hipGetLastError());
     return 0;
@@ -6222,7 +6135,7 @@ int nbmi_frame_begin(nbmi_sim *s, int kind, double max_speed, int *slot) {
         FrameHeader *hd = (FrameHeader *)f.dev;
         void *first = f.dev + sizeof(FrameHeader), *second = f.dev + sizeof(FrameHeader) + item;
         const Bodies cur = s->buf[s->curbuf];
-        const unsigned *se = s->tmp_sort ? (const unsigned *)nbmi::sort_error_device_word(s->tmp_sort) : nullptr;
+        const unsigned *se = s->tmp_sort ? (const unsigned *)nbmi::radix_error_device_word(s->tmp_sort) : nullptr;
         // density colours: the query goes onto the stream in front of the snapshot (enqueued, not waited for; its
         // restored header, a capacity error of its build included, is what the snapshot copies)
         const double *dr2 = nullptr, *dmass = nullptr;
@@ -6333,9 +6246,9 @@ int nbmi_visible_points(nbmi_sim *s, const double *cam12, double tan_h, double t
     const int64_t n = s->n;
     *count = 0;
     if (n == 0) return 0;
-    const int64_t ntiles = vis::tiles_for(n);
+    const int64_t ntiles = scan::tiles_for(n);
     if (!s->vis_flag) {
-        if (dev_alloc(s, &s->vis_flag, vis::flag_bytes(n)) || dev_alloc(s, &s->vis_slot, (size_t)ntiles * vis::kTile) ||
+        if (dev_alloc(s, &s->vis_flag, vis::flag_bytes(n)) || dev_alloc(s, &s->vis_slot, (size_t)ntiles * scan::kTile) ||
             dev_alloc(s, &s->vis_tiles, ntiles + 1))
             return NBMI_ERR_HIP;
         NBMI_HIP_CHECK(hipMemsetAsync(s->vis_flag, 0, vis::flag_bytes(n), s->stream));
@@ -6347,10 +6260,8 @@ int nbmi_visible_points(nbmi_sim *s, const double *cam12, double tan_h, double t
     hipStream_t st = s->stream;
     float *d_pos = (float *)s->stage, *d_col = d_pos + 3 * n;  // stage holds 7 N doubles
     vis::k_mark<<<nblocks(n), kBlock, 0, st>>>(cur.x, cur.y, cur.z, cur.id, n, c, s->vis_flag, s->vis_slot);
-    vis::k_count<<<(int)ntiles, vis::kBlock, 0, st>>>(s->vis_flag, n, s->vis_tiles);
-    vis::k_scan_tiles<<<1, vis::kBlock, 0, st>>>(s->vis_tiles, ntiles);
-    EmitPoints e{cur.x, cur.y, cur.z, s->colors, d_pos, d_col};
-    vis::k_emit<<<(int)ntiles, vis::kBlock, 0, st>>>(s->vis_flag, s->vis_slot, s->vis_tiles, n, n, e);
+    vis::enqueue_visible(s->vis_flag, s->vis_slot, n, s->vis_tiles,
+                         EmitPoints{cur.x, cur.y, cur.z, s->colors, d_pos, d_col}, st);
     NBMI_HIP_CHECK(hipGetLastError());
     uint32_t total = 0;
     NBMI_HIP_CHECK(hipMemcpyAsync(&total, s->vis_tiles + ntiles, 4, hipMemcpyDeviceToHost, st));

@@ -24,6 +24,7 @@
 #include <stdint.h>
 
 #include "common.h"
+#include "scan.h"
 #include <stddef.h>
 
 namespace nbmi {
@@ -97,21 +98,8 @@ __global__ __launch_bounds__(kThreads) void k_radix_hist(const K *__restrict__ k
 
 // exclusive scan of each pass's 256 counts (one workgroup per pass)
 __global__ __launch_bounds__(kBins) void k_radix_offsets(Control *ctl) {
-    __shared__ unsigned wsum[kBins / 64];
     unsigned *h = ctl->hist[blockIdx.x];
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    const unsigned own = h[t];
-    unsigned v = own;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned o = __shfl_up(v, d);
-        if (lane >= d) v += o;
-    }
-    if (lane == 63) wsum[w] = v;
-    __syncthreads();
-    unsigned base = 0;
-    for (int k = 0; k < w; k++) base += wsum[k];
-    h[t] = base + v - own;
+    h[threadIdx.x] = scan::block_scan<kBins>(h[threadIdx.x], 0u, scan::Sum()).excl;
 }
 
 // ---- one pass --------------------------------------------------------------------------------
@@ -126,7 +114,6 @@ __global__ __launch_bounds__(kThreads) void k_radix_pass(const K *__restrict__ k
     __shared__ unsigned cnt_w[kWaves][kBins];   // per-wave digit counts, then the wave's base inside the digit
     __shared__ unsigned tile_off[kBins];        // first slot of the digit inside the reordered tile
     __shared__ unsigned glob_off[kBins];        // global slot of reordered slot q of digit d = glob_off[d] + q
-    __shared__ unsigned wave_tot[kWaves];
     // the reorder buffer is used twice, for the keys and then for the values (38 KB instead of 54 KB of LDS:
     // four workgroups per CU instead of two)
     __shared__ K lds_k[(kThreads * ITEMS)];
@@ -184,17 +171,7 @@ __global__ __launch_bounds__(kThreads) void k_radix_pass(const K *__restrict__ k
         for (int k = 0; k < kWaves; k++) { cnt_w[k][t] = total; total += c[k]; }
     }
     // exclusive scan of the 256 totals across the workgroup
-    unsigned incl = total;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned o = __shfl_up(incl, d);
-        if (lane >= d) incl += o;
-    }
-    if (lane == 63) wave_tot[w] = incl;
-    __syncthreads();
-    unsigned wbase = 0;
-    for (int k = 0; k < w; k++) wbase += wave_tot[k];
-    const unsigned my_tile_off = wbase + incl - total;
+    const unsigned my_tile_off = scan::block_scan<kThreads>(total, 0u, scan::Sum()).excl;
     tile_off[t] = my_tile_off;
 
     // decoupled look-back: pairs of digit t in the tiles before this one

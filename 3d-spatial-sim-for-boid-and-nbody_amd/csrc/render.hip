@@ -4,13 +4,13 @@
 // One frame, all on the renderer's stream:
 //   project   k_count   one thread per point: view, projection, clip, depth, fog'd colour -> 8-byte point record;
 //                       fragments (pixels with coverage >= 1) per 256-point tile
-//             k_scan    exclusive scan of the tile counts (one workgroup); the total goes to the host
+//             scan::k_scan_values  exclusive scan of the tile counts (one workgroup); the total goes to the host
 //   emit      k_emit    the same per-point work again, fragments written as (pixel, point << 5 | coverage) in row order
 //   sort      the hand-written stable radix sort (radix.hip) by pixel, ceil(log2(W H)) key bits: draw order inside a pixel
 //   resolve   k_resolve_min  per 2 048-fragment tile: min of (P - pixel) << 24 | depth.  Pixels ascend, so the composite
 //                            of any earlier pixel is larger than every composite of a later one and a plain running
 //                            minimum over the whole array never crosses a pixel boundary
-//             k_scan    exclusive min-scan of the tile minima (one workgroup)
+//             scan::k_scan_values  exclusive min-scan of the tile minima (one workgroup)
 //             k_resolve fragment passes iff composite < running minimum of everything before it (and depth < 2^24-1);
 //                       coverage x colour of the passing ones summed per pixel run inside the tile, one 64-bit integer
 //                       atomic per (pixel, tile, channel) - a pixel's run may span any number of tiles
@@ -26,13 +26,13 @@
 #include "../../include/nbmi.h"
 #include "common.h"
 #include "render_internal.h"
+#include "scan.h"
 
 namespace {
 
 constexpr int kBlock = 256;                    // points per workgroup (project / emit)
 constexpr int kResItems = 8;                   // fragments per thread (resolve)
 constexpr int kResTile = kBlock * kResItems;   // fragments per resolve workgroup
-constexpr int kScanThreads = 1024;
 constexpr int kMaxWin = 5;                     // pixels per axis a point can reach: ceil(2R) + 1 with R <= 2
 constexpr uint32_t kDepthClear = (1u << 24) - 1u;
 constexpr int64_t kMaxPoints = (int64_t)1 << 27;      // point index << 5 | coverage in 32 bits
@@ -118,38 +118,9 @@ __device__ __forceinline__ uint32_t shade(const View &v, const float *__restrict
     return (uint32_t)floor(cf * 4080.0 + 0.5);
 }
 
-template <typename T>
-struct OpSum {
-    __device__ T operator()(T a, T b) const { return a + b; }
-};
-template <typename T>
-struct OpMin {
-    __device__ T operator()(T a, T b) const { return b < a ? b : a; }
-};
-
-// Exclusive scan over the NT threads of a workgroup; *total = the reduction of all of them.  sh: NT elements of LDS.
-template <int NT, typename T, typename Op>
-__device__ T block_scan_excl(T v, T ident, Op op, T *sh, T *total) {
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int o = 1; o < NT; o <<= 1) {
-        const T a = t >= o ? sh[t - o] : ident;
-        const T cur = sh[t];
-        __syncthreads();
-        sh[t] = op(a, cur);
-        __syncthreads();
-    }
-    *total = sh[NT - 1];
-    const T ex = t ? sh[t - 1] : ident;
-    __syncthreads();
-    return ex;
-}
-
 __global__ __launch_bounds__(kBlock) void k_count(View v, const float *__restrict__ pos, const float *__restrict__ col,
                                                  int64_t n, uint64_t *__restrict__ rec, uint32_t *__restrict__ tile_cnt,
                                                  unsigned long long *__restrict__ stats) {
-    __shared__ uint32_t sh[kBlock];
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     uint32_t nf = 0, drawn = 0;
     double xw, yw, ze;
@@ -165,39 +136,17 @@ __global__ __launch_bounds__(kBlock) void k_count(View v, const float *__restric
         rec[i] = ((uint64_t)d << 36) | ((uint64_t)shade(v, col, i, 0, fog) << 24) |
                  ((uint64_t)shade(v, col, i, 1, fog) << 12) | (uint64_t)shade(v, col, i, 2, fog);
     }
-    uint32_t tot_f, tot_d;
-    (void)block_scan_excl<kBlock>(nf, 0u, OpSum<uint32_t>(), sh, &tot_f);
-    (void)block_scan_excl<kBlock>(drawn, 0u, OpSum<uint32_t>(), sh, &tot_d);
+    const uint32_t tot_f = scan::block_scan<kBlock>(nf, 0u, scan::Sum()).total;
+    const uint32_t tot_d = scan::block_scan<kBlock>(drawn, 0u, scan::Sum()).total;
     if (threadIdx.x == 0) {
         tile_cnt[blockIdx.x] = tot_f;
         if (tot_d) atomicAdd(&stats[0], (unsigned long long)tot_d);
     }
 }
 
-// Exclusive scan of m values in one workgroup: each thread folds a contiguous chunk, the chunk totals are scanned,
-// then each thread writes its chunk.  out[m] = the total.
-template <typename TI, typename T, typename Op>
-__global__ __launch_bounds__(kScanThreads) void k_scan(const TI *__restrict__ in, T *__restrict__ out, int64_t m, T ident,
-                                                      Op op) {
-    __shared__ T sh[kScanThreads];
-    const int64_t chunk = (m + kScanThreads - 1) / kScanThreads;
-    const int64_t b = (int64_t)threadIdx.x * chunk, e = b + chunk < m ? b + chunk : m;
-    T acc = ident;
-    for (int64_t k = b; k < e; k++) acc = op(acc, (T)in[k]);
-    T total;
-    T run = block_scan_excl<kScanThreads>(acc, ident, op, sh, &total);
-    for (int64_t k = b; k < e; k++) {
-        const T x = (T)in[k];
-        out[k] = run;
-        run = op(run, x);
-    }
-    if (threadIdx.x == 0) out[m] = total;
-}
-
 __global__ __launch_bounds__(kBlock) void k_emit(View v, const float *__restrict__ pos, int64_t n,
                                                 const uint64_t *__restrict__ tile_off, uint32_t *__restrict__ keys,
                                                 uint32_t *__restrict__ vals) {
-    __shared__ uint32_t sh[kBlock];
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     double xw = 0, yw = 0, ze;
     uint32_t d, m = 0;
@@ -207,8 +156,7 @@ __global__ __launch_bounds__(kBlock) void k_emit(View v, const float *__restrict
         window(yw, v.R, v.H, j0, nj);
         m = frag_mask(v, xw, yw, i0, ni, j0, nj);
     }
-    uint32_t tot;
-    uint64_t o = tile_off[blockIdx.x] + block_scan_excl<kBlock>((uint32_t)__popc(m), 0u, OpSum<uint32_t>(), sh, &tot);
+    uint64_t o = (uint64_t)scan::tile_slot<kBlock>(tile_off, (unsigned)__popc(m));
     for (int jj = 0; jj < nj && m; jj++) {
         double dy2[4];
         sample_d2(j0 + jj, yw, dy2);
@@ -233,15 +181,13 @@ __device__ __forceinline__ uint64_t composite(uint32_t key, uint64_t rec, uint64
 __global__ __launch_bounds__(kBlock) void k_resolve_min(const uint32_t *__restrict__ keys, const uint32_t *__restrict__ vals,
                                                        const uint64_t *__restrict__ rec, int64_t nf, uint64_t P,
                                                        uint64_t *__restrict__ tile_min) {
-    __shared__ uint64_t sh[kBlock];
     const int64_t first = (int64_t)blockIdx.x * kResTile + (int64_t)threadIdx.x * kResItems;
     uint64_t mn = ~0ull;
     for (int k = 0; k < kResItems; k++) {
         const int64_t q = first + k;
         if (q < nf) mn = umin64(mn, composite(keys[q], rec[vals[q] >> 5], P));
     }
-    uint64_t tot;
-    (void)block_scan_excl<kBlock>(mn, ~(uint64_t)0, OpMin<uint64_t>(), sh, &tot);
+    const uint64_t tot = scan::block_scan<kBlock>(mn, ~(uint64_t)0, scan::Min()).total;
     if (threadIdx.x == 0) tile_min[blockIdx.x] = tot;
 }
 
@@ -249,6 +195,9 @@ struct Seg {  // segmented sum element: a run head inside, and the sums since th
     uint32_t head;
     uint64_t s[3];
 };
+__device__ __forceinline__ Seg lane_up(const Seg &v, int d) {  // scan.h's lane shift for this type
+    return Seg{__shfl_up(v.head, d), {__shfl_up(v.s[0], d), __shfl_up(v.s[1], d), __shfl_up(v.s[2], d)}};
+}
 struct OpSeg {
     __device__ Seg operator()(const Seg &a, const Seg &b) const {  // a before b
         Seg r;
@@ -263,9 +212,6 @@ __global__ __launch_bounds__(kBlock) void k_resolve(const uint32_t *__restrict__
                                                    const uint64_t *__restrict__ tile_pre,
                                                    unsigned long long *__restrict__ acc,
                                                    unsigned long long *__restrict__ stats) {
-    __shared__ uint64_t shm[kBlock];
-    __shared__ Seg shs[kBlock];
-    __shared__ uint32_t shc[kBlock];
     const int64_t tile_first = (int64_t)blockIdx.x * kResTile;
     const int64_t tile_end = tile_first + kResTile < nf ? tile_first + kResTile : nf;
     const int64_t first = tile_first + (int64_t)threadIdx.x * kResItems;
@@ -286,8 +232,7 @@ __global__ __launch_bounds__(kBlock) void k_resolve(const uint32_t *__restrict__
             mn = umin64(mn, cm[k]);
         }
     }
-    uint64_t tot;
-    uint64_t run = block_scan_excl<kBlock>(mn, ~(uint64_t)0, OpMin<uint64_t>(), shm, &tot);
+    uint64_t run = scan::block_scan<kBlock>(mn, ~(uint64_t)0, scan::Min()).excl;
     run = umin64(run, tile_pre[blockIdx.x]);
     // which fragments pass, their contributions, and the run heads
     uint32_t pass = 0, head = 0;
@@ -317,8 +262,7 @@ __global__ __launch_bounds__(kBlock) void k_resolve(const uint32_t *__restrict__
         if ((head >> k) & 1u) { agg.head = 1u; agg.s[0] = agg.s[1] = agg.s[2] = 0; }
         for (int ch = 0; ch < 3; ch++) agg.s[ch] += con[k][ch];
     }
-    Seg seg_tot;
-    const Seg carry = block_scan_excl<kBlock>(agg, Seg{0u, {0, 0, 0}}, OpSeg(), shs, &seg_tot);
+    const Seg carry = scan::block_scan<kBlock>(agg, Seg{0u, {0, 0, 0}}, OpSeg()).excl;
     uint64_t s[3] = {carry.s[0], carry.s[1], carry.s[2]};
 #pragma unroll
     for (int k = 0; k < kResItems; k++) {
@@ -332,9 +276,8 @@ __global__ __launch_bounds__(kBlock) void k_resolve(const uint32_t *__restrict__
                 if (s[ch]) atomicAdd(&acc[3 * (uint64_t)key[k] + ch], (unsigned long long)s[ch]);
         }
     }
-    uint32_t t_pass, t_head;
-    (void)block_scan_excl<kBlock>((uint32_t)__popc(pass), 0u, OpSum<uint32_t>(), shc, &t_pass);
-    (void)block_scan_excl<kBlock>((uint32_t)__popc(head), 0u, OpSum<uint32_t>(), shc, &t_head);
+    const uint32_t t_pass = scan::block_scan<kBlock>((uint32_t)__popc(pass), 0u, scan::Sum()).total;
+    const uint32_t t_head = scan::block_scan<kBlock>((uint32_t)__popc(head), 0u, scan::Sum()).total;
     if (threadIdx.x == 0) {
         if (t_pass) atomicAdd(&stats[2], (unsigned long long)t_pass);
         if (t_head) atomicAdd(&stats[3], (unsigned long long)t_head);
@@ -478,7 +421,8 @@ int render_frame(nbmi_render *r, int64_t n, const View &v, const uint32_t bg8[3]
     const int64_t tiles = grid_for(n, kBlock);
     if (n > 0) {
         k_count<<<(int)tiles, kBlock, 0, st>>>(v, r->d_pos, r->d_col, n, r->rec, r->tile_cnt, r->stats);
-        k_scan<<<1, kScanThreads, 0, st>>>(r->tile_cnt, r->tile_off, tiles, (uint64_t)0, OpSum<uint64_t>());
+        scan::k_scan_values<<<1, scan::kScanThreads, 0, st>>>(r->tile_cnt, r->tile_off, tiles, (int64_t)0, (uint64_t)0,
+                                                              scan::Sum());
         NBMI_HIP_CHECK(hipGetLastError());
         NBMI_HIP_CHECK(hipMemcpyAsync(r->h_small, r->tile_off + tiles, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     }
@@ -507,7 +451,8 @@ int render_frame(nbmi_render *r, int64_t n, const View &v, const uint32_t bg8[3]
     if (nf > 0) {
         const int64_t rt = grid_for(nf, kResTile);
         k_resolve_min<<<(int)rt, kBlock, 0, st>>>(r->keys2, r->vals2, r->rec, nf, (uint64_t)P, r->tile_min);
-        k_scan<<<1, kScanThreads, 0, st>>>(r->tile_min, r->tile_pre, rt, ~(uint64_t)0, OpMin<uint64_t>());
+        scan::k_scan_values<<<1, scan::kScanThreads, 0, st>>>(r->tile_min, r->tile_pre, rt, (int64_t)0, ~(uint64_t)0,
+                                                              scan::Min());
         k_resolve<<<(int)rt, kBlock, 0, st>>>(r->keys2, r->vals2, r->rec, nf, (uint64_t)P, r->tile_pre, r->acc, r->stats);
         NBMI_HIP_CHECK(hipGetLastError());
     }

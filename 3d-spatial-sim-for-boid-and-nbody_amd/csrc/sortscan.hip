@@ -1,47 +1,13 @@
-// Device sorts of (key, 32-bit value) pairs and of bare keys used by the octree build and the boids grid: the hand-written radix sort
-// of radix.hip behind one small interface.  [r4] rocPRIM is no longer compiled into the product: its cross-check lives
-// in tests/native/rocprim_check.hip (a test-only library that tests/test_gpu_sort.py compares this sort with, bit for
-// bit); nbmi_debug_sort_pairs / nbmi_debug_sort_keys run the product's sorts on caller-supplied arrays for the tests.
+// Test / measurement hooks of the device sort (radix.hip): nbmi_debug_sort_pairs / nbmi_debug_sort_keys run the product's
+// sorts on caller-supplied host arrays.  rocPRIM is not compiled into the product: its cross-check lives in
+// tests/native/rocprim_check.hip (a test-only library that tests/test_gpu_sort.py compares this sort with, bit for bit).
 #include <cstdlib>
 #include <cstring>
 
 #include "../../include/nbmi.h"
 #include "common.h"
 
-namespace nbmi {
-
-size_t sort_pairs_temp_bytes(size_t n, int begin_bit, int end_bit) { return radix_temp_bytes_u64(n, end_bit - begin_bit); }
-
-hipError_t sort_pairs_u64_u32(void *temp, size_t temp_bytes, const uint64_t *kin, uint64_t *kout,
-                              const uint32_t *vin, uint32_t *vout, size_t n, int begin_bit, int end_bit,
-                              hipStream_t s) {
-    return radix_sort_pairs_u64(temp, temp_bytes, kin, kout, vin, vout, n, begin_bit, end_bit, s);
-}
-
-// keys-only sort on the bits [begin_bit, end_bit): the value rides in the key's lower bits (the octree build's packed
-// word); the same temp buffer serves both forms (the pair form's is the larger)
-hipError_t sort_keys_u64(void *temp, size_t temp_bytes, const uint64_t *kin, uint64_t *kout, size_t n, int begin_bit,
-                         int end_bit, hipStream_t s) {
-    return radix_sort_keys_u64(temp, temp_bytes, kin, kout, n, begin_bit, end_bit, s);
-}
-
-// the sticky error word of the sort (a look-back spin that timed out)
-hipError_t sort_init_temp(void *temp, hipStream_t s) { return radix_init_temp(temp, s); }
-hipError_t sort_error_word(const void *temp, unsigned *out, hipStream_t s) { return radix_error_word(temp, out, s); }
-const void *sort_error_device_word(const void *temp) { return radix_error_device_word(temp); }
-
-size_t sort_pairs32_temp_bytes(size_t n, int begin_bit, int end_bit) { return radix_temp_bytes_u32(n, end_bit - begin_bit); }
-
-hipError_t sort_pairs_u32_u32(void *temp, size_t temp_bytes, const uint32_t *kin, uint32_t *kout,
-                              const uint32_t *vin, uint32_t *vout, size_t n, int begin_bit, int end_bit,
-                              hipStream_t s) {
-    return radix_sort_pairs_u32(temp, temp_bytes, kin, kout, vin, vout, n, begin_bit, end_bit, s);
-}
-
-}  // namespace nbmi
-
-// Test / measurement hooks: sort caller-supplied host arrays on the device with the product's sort.  values == null:
-// the keys-only form on the bits [begin_bit, end_bit); otherwise pairs.
+// values == null: the keys-only form on the bits [begin_bit, end_bit); otherwise pairs.
 static int debug_sort(const char *who, int key_bytes, int64_t n, const void *keys, const uint32_t *values, void *keys_out,
                       uint32_t *values_out, int begin_bit, int end_bit, int repeats, double *ms_per_sort) {
     if (n == 0) return 0;

@@ -98,6 +98,45 @@ def test_flock_class_api(gpu, oracle):
     fl.close()
 
 
+def _numpy_cells(pos, cell, dim, offset):
+    c = np.clip(((pos + offset) / cell).astype(np.int64), 0, dim - 1)  # int() truncation, then the clamp
+    return (c[:, 0] + c[:, 1] * dim + c[:, 2] * dim * dim).astype(np.int32)
+
+
+def _table_case(n):
+    """(bounds, pos): below the large size a dense random flock (nearly every boid starts a cell of the table); at
+    the large size 16 cells far from each other (few tiles of the table's compaction emit, the sweep stays cheap)."""
+    rng = np.random.RandomState(n)
+    if n < 100_000:
+        return 30.0, rng.uniform(-30.0, 30.0, (n, 3))
+    centres = rng.randint(-9, 10, (16, 3)) * 50.0 + 2.5
+    assert len(np.unique(centres, axis=0)) == 16
+    return 500.0, centres[rng.randint(0, 16, n)] + rng.uniform(-1.0, 1.0, (n, 3))
+
+
+@pytest.mark.parametrize("n", [2047, 2048, 2049, 524_289])
+def test_cell_table_at_tile_edges(gpu, oracle, n):
+    bounds, pos = _table_case(n)
+    rng = np.random.RandomState(1)
+    vel, col = rng.normal(0.0, 5.0, (n, 3)), rng.rand(n, 3)
+    params = oracle.boids_params(bounds=bounds)
+    cell, dim, offset = oracle.boids_grid(params)
+    cells = _numpy_cells(pos, cell, dim, offset)
+    f = RawFlock(gpu, pos, vel, col, params)
+    assert np.array_equal(f.cells(), cells)
+    f.step(1.0 / 60.0)  # grid, table and sweep of `pos`
+    occ = C.c_int64(0)
+    gpu.check(f.lib.bdmi_grid_info(f.h, None, None, C.addressof(occ)), "bdmi_grid_info")
+    assert occ.value == len(np.unique(cells)) and (occ.value == 16 or n < 100_000)
+    if n < 100_000:  # the step went through the table: same bounds as test_flock_vs_reference's first step
+        st = oracle.FlockStepper(pos, vel, col, params)
+        st.step(1.0 / 60.0)
+        p, v, c = f.state()
+        assert np.abs(p - st.pos).max() <= 1e-9 and np.abs(v - st.vel).max() <= 1e-9
+        assert np.abs(c - st.col).max() <= 1e-12
+    f.close()
+
+
 def test_edge_empty_single_and_clamped(gpu, oracle):
     params = oracle.boids_params(bounds=10.0)
     z = np.zeros((0, 3))

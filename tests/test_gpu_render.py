@@ -117,6 +117,24 @@ def test_one_pixel_stack_spans_many_tiles(gpu):
         assert st[2] > n  # a third of the 1.5 M fragments pass (the rest tie in 24-bit depth)
 
 
+@pytest.mark.parametrize("n", [262_144, 262_145])
+def test_tile_scan_round_edge(gpu, n):
+    """1 024 and 1 025 tiles of 256 points (one full round of the tile scan, and one entry carried into the next):
+    everything behind the eye except one point in the first tile and one in the last."""
+    from nbody.render import HIPPointRenderer
+    rng = np.random.default_rng(n)
+    pos = rng.uniform(-50.0, 50.0, (n, 3)).astype(np.float32)
+    pos[:, 2] += 500.0  # eye at z = 300 looking down -z: all behind it
+    pos[3] = (-20.0, 10.0, 0.0)
+    pos[n - 1] = (25.0, -15.0, 40.0)
+    col = rng.random((n, 3)).astype(np.float32)
+    W, H = 333, 197
+    with HIPPointRenderer(W, H) as r:
+        for ps in (1.5, 4.0):
+            _, st = _check(r, pos, col, W, H, make_params((0, 0, 300), point_size=ps, fog_density=0.0), f"{n} points ps {ps}")
+            assert st[0] == 2 and st[1] >= 2
+
+
 def test_everything_clipped_and_empty(gpu):
     from nbody.render import HIPPointRenderer
     rng = np.random.default_rng(9)

@@ -175,3 +175,68 @@ def test_visibility_edge_cases(gpu, oracle):
     fl = Flock(0, seed=1)
     v, c = fl.visible_vertices((0, 0, 0), (0, 0, 1), (1, 0, 0), (0, 1, 0), fov=75, aspect=1.5)
     assert len(v) == 0 and fl._visible_count == 0
+
+
+# ---- compaction edges: thread (8), tile (2 048), one round of the tile scan (1 024 tiles), two carries of it ----
+PATTERNS = ("none", "all", "last", "tile_firsts", "random_half")
+AXIS_CAM = ((0.0, 0.0, 0.0), (0.0, 0.0, 1.0), (1.0, 0.0, 0.0), (0.0, 1.0, 0.0))
+
+
+def _pattern(name, n):
+    """Which of the caller's n bodies are visible."""
+    m = np.zeros(n, dtype=bool)
+    if name == "all":
+        m[:] = True
+    elif name == "last":
+        m[-1] = True
+    elif name == "tile_firsts":
+        m[::2048] = True
+    elif name == "random_half":
+        m = np.random.RandomState(n).rand(n) < 0.5
+    return m
+
+
+def _on_axis(mask, lo, hi):
+    """Bodies on the camera axis of AXIS_CAM at distinct depths in [lo, hi]: in front where mask, else behind."""
+    n = len(mask)
+    depth = np.random.RandomState(7).permutation(n) * ((hi - lo) / max(n - 1, 1)) + lo
+    pos = np.zeros((n, 3))
+    pos[:, 2] = np.where(mask, depth, -depth)
+    return pos
+
+
+@pytest.mark.parametrize("n", [1, 255, 256, 257, 2047, 2048, 2049, 524_288, 524_289, 1_048_577])
+def test_visible_points_at_compaction_edges(gpu, oracle, n):
+    from nbody.gpu_backend import HIPBarnesHutSimulation
+    sim = HIPBarnesHutSimulation(np.zeros((n, 3)), np.zeros((n, 3)), np.ones(n), 1.0, 1.0, 1.0, 0.5)
+    sim.compute_colors(15.0)
+    col = sim.get_colors()
+    for name in PATTERNS:
+        mask = _pattern(name, n)
+        pos = _on_axis(mask, 1.0, 100.0)
+        assert np.array_equal(mask, oracle.compute_visibility_points(pos, *AXIS_CAM, 1.0, 1.0, 1000.0)), name
+        sim.set_state(pos, np.zeros((n, 3)))
+        p, c = sim.visible_points(*AXIS_CAM, 1.0, 1.0, 1000.0)
+        assert len(p) == mask.sum(), name
+        assert np.array_equal(p, pos[mask].astype(np.float32)), name
+        assert np.array_equal(c, col[mask]), name
+    sim.close()
+
+
+@pytest.mark.parametrize("n", [2047, 2048, 2049, 524_289])
+def test_visible_vertices_at_compaction_edges(gpu, oracle, n):
+    from boids.flock import Flock
+    fl = Flock(n, seed=3)
+    vel, col = fl.velocities, fl.colors
+    th, tv = fl.frustum_tangents(75, 16 / 9)
+    for name in PATTERNS:
+        mask = _pattern(name, n)
+        pos = _on_axis(mask, 1.0, 100.0)
+        assert np.array_equal(mask, oracle.compute_visibility_boids(pos, *AXIS_CAM, th, tv, fl.fog_end)), name
+        fl.set_state(positions=pos)
+        v, c = fl.visible_vertices(*AXIS_CAM, fov=75, aspect=16 / 9)
+        ev, ec = oracle.build_vertices(pos, vel, col, np.where(mask)[0].astype(np.int32), float(fl.cone_length),
+                                       float(fl.cone_radius))
+        assert fl._visible_count == mask.sum(), name
+        assert np.array_equal(v, ev) and np.array_equal(c, ec), name
+    fl.close()
