@@ -29,20 +29,31 @@ struct Moment {
 
 // ---- device sort (radix.hip) ------------------------------------------------------------
 // by key bits [begin_bit, end_bit), stable, ping-pong inside `temp`
+// Digit width (8 or 10 bits) and threads per tile (256, 512 or 1024) of the passes; 0 = chosen by size and form.
+struct RadixConfig {
+    int digit_bits = 0, threads = 0;
+};
+struct RadixHist;  // radix_hist.h
+bool radix_config_ok(RadixConfig cfg);
 size_t radix_temp_bytes_u64(size_t n, int bits);
 size_t radix_temp_bytes_u32(size_t n, int bits);
 hipError_t radix_sort_pairs_u64(void *temp, size_t temp_bytes, const uint64_t *kin, uint64_t *kout, const uint32_t *vin,
-                                uint32_t *vout, size_t n, int begin_bit, int end_bit, hipStream_t s);
+                                uint32_t *vout, size_t n, int begin_bit, int end_bit, hipStream_t s, RadixConfig cfg = {});
 hipError_t radix_sort_pairs_u32(void *temp, size_t temp_bytes, const uint32_t *kin, uint32_t *kout, const uint32_t *vin,
-                                uint32_t *vout, size_t n, int begin_bit, int end_bit, hipStream_t s);
+                                uint32_t *vout, size_t n, int begin_bit, int end_bit, hipStream_t s, RadixConfig cfg = {});
 // keys-only: sorts on the bits [begin_bit, end_bit) of the keys, the other bits travel along (stable); the pair
 // form's temp buffer is the larger and serves both
 size_t radix_keys_temp_bytes_u64(size_t n, int bits);
 size_t radix_keys_temp_bytes_u32(size_t n, int bits);
+// have_hist: radix_keys_prepare_u64 ran for this sort and the caller's own kernel has counted the digits since
 hipError_t radix_sort_keys_u64(void *temp, size_t temp_bytes, const uint64_t *kin, uint64_t *kout, size_t n, int begin_bit,
-                               int end_bit, hipStream_t s);
+                               int end_bit, hipStream_t s, RadixConfig cfg = {}, bool have_hist = false);
 hipError_t radix_sort_keys_u32(void *temp, size_t temp_bytes, const uint32_t *kin, uint32_t *kout, size_t n, int begin_bit,
-                               int end_bit, hipStream_t s);
+                               int end_bit, hipStream_t s, RadixConfig cfg = {});
+// clears the temp buffer for one keys-only sort and hands out its device histogram (to be enqueued BEFORE the kernel
+// that counts into it)
+hipError_t radix_keys_prepare_u64(void *temp, size_t temp_bytes, size_t n, int begin_bit, int end_bit, RadixConfig cfg,
+                                  hipStream_t s, RadixHist *out);
 hipError_t radix_init_temp(void *temp, hipStream_t s);                          // once per freshly allocated temp buffer
 hipError_t radix_error_word(const void *temp, unsigned *out, hipStream_t s);  // sticky: 1 = some sort since then went wrong
 const void *radix_error_device_word(const void *temp);  // where that word lives on the device (kernels that copy it along)

@@ -37,6 +37,7 @@
 
 #include "../../include/nbmi.h"
 #include "common.h"
+#include "radix_hist.h"
 #include "hilbert.h"
 #include "visible.h"
 
@@ -279,6 +280,47 @@ __device__ __forceinline__ uint64_t low_word_of(const uint64_t *__restrict__ key
 }
 
 // kLean: the upper word only, 21 levels, key_lo not written (the stepping build of a plain handle)
+// k_keys_hist (packed path only): the kernel also counts the digits of the sorted prefix for every pass of the sort that
+// follows, which then needs no read of `packed` for its histogram.  Its workgroups are 1 024 threads and cover `rounds`
+// x 1 024 consecutive bodies each, at least 2 048 and few enough workgroups (keys_hist_grid) that the flush of their
+// LDS counters - up to a thousand per pass, mostly ones after 256 bodies, every one a device-scope atomic on the same
+// few cache lines - stays small: 256-thread workgroups of 2 048 bodies made 2.9 M such atomics at 10 M bodies and the
+// kernel 0.057 ms slower, and left a SIMD two waves to hide the key recurrence's latency behind at 1 M (0.040 against
+// 0.024 ms; profiles/sort_wide_ab.txt).  The Hilbert tables are copied once per workgroup.  Per body the same
+// arithmetic either way.
+constexpr int kKeysHistBlock = 1024, kKeysHistMaxGrid = 512;
+constexpr int kKeysHistCounters = 4096;  // passes << digit bits of a packed field: 5 x 256 or 4 x 1 024 at the most
+// Counting costs k_keys_hist what k_radix_hist costs on its own (the LDS atomics of a wave whose keys hold two or three
+// values of a digit serialise in either); what the fusion saves is a launch, the read of `packed` and an emptier chip:
+// keys + sort 0.150 -> 0.141 ms at 1 M bodies, but 0.741 -> 0.749 at 10 M (profiles/sort_wide_ab.txt).  Measured at those
+// two sizes only; the boundary is the sort's own between its two large forms, an estimate.
+static inline bool fused_hist_pays(int64_t n) { return n <= 2097152; }
+static inline int keys_hist_grid(int64_t n) {
+    const int64_t g = (n + 2 * kKeysHistBlock - 1) / (2 * kKeysHistBlock);
+    return (int)(g < 1 ? 1 : (g > kKeysHistMaxGrid ? kKeysHistMaxGrid : g));
+}
+// one body's key words, index and (packed != null) packed sort word; returns the upper word
+template <bool kHilbert, bool kLean>
+__device__ __forceinline__ uint64_t keys_of_body(int64_t i, const double *__restrict__ x, const double *__restrict__ y,
+                                                 const double *__restrict__ z, double bounds, uint64_t *__restrict__ key_hi,
+                                                 uint64_t *__restrict__ key_lo, uint32_t *__restrict__ idx,
+                                                 uint64_t *__restrict__ packed, int shift, const uint32_t *hd, const uint64_t *hn) {
+    const double px = x[i], py = y[i], pz = z[i];
+    double cx = 0.0, cy = 0.0, cz = 0.0, hs = bounds;
+    uint64_t k[2];
+    unsigned st = 0u;  // orientation of the current cell (root: 0)
+    k[0] = key_word<kHilbert>(px, py, pz, cx, cy, cz, hs, st, hd, hn);
+    key_hi[i] = k[0];
+    if (!kLean) {
+        k[1] = key_word<kHilbert>(px, py, pz, cx, cy, cz, hs, st, hd, hn);
+        key_lo[i] = k[1];
+    }
+    // packed sort (enqueue_local_sort): the sorted prefix with the body index below it, ONE word for the keys-only sort
+    if (packed) packed[i] = ((k[0] >> shift) << kPackIdxBits) | (uint64_t)i;
+    else idx[i] = (uint32_t)i;
+    return k[0];
+}
+
 template <bool kHilbert, bool kLean = false>
 __global__ __launch_bounds__(kBlock) void k_keys(const double *__restrict__ x, const double *__restrict__ y,
                                                  const double *__restrict__ z, int64_t n, TreeInfo *info,
@@ -306,19 +348,47 @@ __global__ __launch_bounds__(kBlock) void k_keys(const double *__restrict__ x, c
         idx[i] = (uint32_t)i;
         return;
     }
-    const double px = x[i], py = y[i], pz = z[i];
-    double cx = 0.0, cy = 0.0, cz = 0.0, hs = bounds;
-    uint64_t k[2];
-    unsigned st = 0u;  // orientation of the current cell (root: 0)
-    k[0] = key_word<kHilbert>(px, py, pz, cx, cy, cz, hs, st, hd, hn);
-    key_hi[i] = k[0];
-    if (!kLean) {
-        k[1] = key_word<kHilbert>(px, py, pz, cx, cy, cz, hs, st, hd, hn);
-        key_lo[i] = k[1];
+    (void)keys_of_body<kHilbert, kLean>(i, x, y, z, bounds, key_hi, key_lo, idx, packed, shift, hd, hn);
+}
+
+// Out of line for k_keys_hist: inlined into its loop over the rounds the same code takes 95 VGPRs (128 and a spill with
+// the low word) instead of k_keys' 46, and two workgroups of 1 024 threads no longer fit a CU.
+template <bool kHilbert, bool kLean>
+__device__ __noinline__ uint64_t keys_of_body_call(int64_t i, const double *__restrict__ x, const double *__restrict__ y,
+                                                   const double *__restrict__ z, double bounds, uint64_t *__restrict__ key_hi,
+                                                   uint64_t *__restrict__ key_lo, uint64_t *__restrict__ packed, int shift,
+                                                   const uint32_t *hd, const uint64_t *hn) {
+    return keys_of_body<kHilbert, kLean>(i, x, y, z, bounds, key_hi, key_lo, nullptr, packed, shift, hd, hn);
+}
+
+// k_keys of the packed path with the sort's histogram (see above): no dead rows, `packed` is written
+template <bool kHilbert, bool kLean>
+__global__ __launch_bounds__(kKeysHistBlock) void k_keys_hist(const double *__restrict__ x, const double *__restrict__ y,
+                                                              const double *__restrict__ z, int64_t n, TreeInfo *info,
+                                                              uint64_t *__restrict__ key_hi, uint64_t *__restrict__ key_lo,
+                                                              uint64_t *__restrict__ packed, int shift, nbmi::RadixHist hist,
+                                                              int rounds) {
+    __shared__ uint32_t hd[nbmi::kHilStates];
+    __shared__ uint64_t hn[nbmi::kHilStates];
+    __shared__ unsigned hcnt[kKeysHistCounters];
+    for (int c = threadIdx.x; c < (hist.passes << hist.digit_bits); c += kKeysHistBlock) hcnt[c] = 0u;
+    if (kHilbert && threadIdx.x < nbmi::kHilStates) {
+        hd[threadIdx.x] = nbmi::kHilDigit[threadIdx.x];
+        hn[threadIdx.x] = nbmi::kHilNext[threadIdx.x];
     }
-    // packed sort (enqueue_local_sort): the sorted prefix with the body index below it, ONE word for the keys-only sort
-    if (packed) packed[i] = ((k[0] >> shift) << kPackIdxBits) | (uint64_t)i;
-    else idx[i] = (uint32_t)i;
+    __syncthreads();
+    const double maxabs = __longlong_as_double((long long)info->maxabs_bits);
+    const double bounds = __dadd_rn(__dmul_rn(maxabs, 1.1), 10.0);
+    if (blockIdx.x == 0 && threadIdx.x == 0) info->bounds = bounds;
+#pragma unroll 1
+    for (int r = 0; r < rounds; r++) {
+        const int64_t i = ((int64_t)blockIdx.x * rounds + r) * kKeysHistBlock + threadIdx.x;
+        if (i >= n) break;
+        const uint64_t hi = keys_of_body_call<kHilbert, kLean>(i, x, y, z, bounds, key_hi, key_lo, packed, shift, hd, hn);
+        nbmi::radix_hist_count(hcnt, hi >> shift, hist.bits, hist.digit_bits, hist.passes);
+    }
+    __syncthreads();
+    nbmi::radix_hist_flush(hcnt, hist.counts, hist.digit_bits, hist.passes, kKeysHistBlock);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -4074,6 +4144,10 @@ struct nbmi_sim {
     bool sort_packed = true;  // sort ONE packed word (prefix << 24 | body index) with the keys-only sort where it fits
                               // (packed_sort_ok); NBMI_SORT_PACKED=0: always (key, index) pairs
     uint64_t *packed = nullptr, *packed_s = nullptr;  // the packed words of k_keys and their sorted order
+    nbmi::RadixConfig sort_cfg;   // digit bits / threads per tile of the packed sort's passes; 0 = by size
+                                  // (NBMI_SORT_DIGIT_BITS = 8 | 10, NBMI_SORT_THREADS = 256 | 512 | 1024)
+    int sort_fused_hist = -1;     // k_keys_hist counts the packed sort's digit histogram instead of k_radix_hist: -1 by size
+                                  // (fused_hist_pays), NBMI_SORT_FUSED_HIST=0 never, =1 always
     int sort_bits = 0;   // upper-word bits the radix sort looks at (0: chosen from n; NBMI_SORT_BITS); widened when long runs show up
     bool maxabs_fused = false;  // TreeInfo::maxabs_next holds max |coordinate| of the CURRENT positions (set by a full
                                 // integrating walk, dropped by anything else that writes positions); NBMI_FUSE_MAXABS=0: never
@@ -4295,10 +4369,24 @@ int enqueue_local_sort(nbmi_sim *s, const SortRequest &req = {}) {
     const int shift = 63 - s->sort_bits;
     const bool packed = packed_sort_ok(s, n, dead);
     uint64_t *pk = packed ? s->packed : nullptr;
+    // the packed sort's histogram is counted by k_keys_hist, which has the prefixes in registers: the sort's clear goes
+    // in front of it, and the sort is told the counts are there (otherwise the sort reads `packed` for them)
+    const bool fused = packed && n > 0 && (s->sort_fused_hist < 0 ? fused_hist_pays(n) : s->sort_fused_hist != 0);
+    nbmi::RadixHist hist;
+    if (fused)
+        NBMI_HIP_CHECK(nbmi::radix_keys_prepare_u64(s->tmp_sort, s->tmp_sort_bytes, (size_t)n, kPackIdxBits, kPackIdxBits + s->sort_bits,
+                                                    s->sort_cfg, st, &hist));
     with_bool(s->hilbert, [&](auto h) {
         with_bool(lean, [&](auto l) {
-            k_keys<decltype(h)::value, decltype(l)::value><<<nblocks(n), kBlock, 0, st>>>(cur.x, cur.y, cur.z, n, s->info, s->key_hi,
-                                                                                         s->key_lo, s->idx, dead, pk, shift);
+            if (fused) {
+                const int grid = keys_hist_grid(n);
+                const int rounds = (int)((n + (int64_t)grid * kKeysHistBlock - 1) / ((int64_t)grid * kKeysHistBlock));
+                k_keys_hist<decltype(h)::value, decltype(l)::value><<<grid, kKeysHistBlock, 0, st>>>(
+                    cur.x, cur.y, cur.z, n, s->info, s->key_hi, s->key_lo, pk, shift, hist, rounds);
+            }
+            else
+                k_keys<decltype(h)::value, decltype(l)::value><<<nblocks(n), kBlock, 0, st>>>(cur.x, cur.y, cur.z, n, s->info, s->key_hi,
+                                                                                             s->key_lo, s->idx, dead, pk, shift);
         });
     });
     if (req.timed) NBMI_HIP_CHECK(hipEventRecord(s->ev[1], st));
@@ -4306,7 +4394,7 @@ int enqueue_local_sort(nbmi_sim *s, const SortRequest &req = {}) {
         // one 8-byte word per body through the passes instead of an 8-byte key and a 4-byte index: the index sits
         // below the prefix, so a stable sort of the pairs and a sort of the words on the prefix bits give the same order
         NBMI_HIP_CHECK(nbmi::radix_sort_keys_u64(s->tmp_sort, s->tmp_sort_bytes, s->packed, s->packed_s, (size_t)n, kPackIdxBits,
-                                                 kPackIdxBits + s->sort_bits, st));
+                                                 kPackIdxBits + s->sort_bits, st, s->sort_cfg, fused));
         // the tie-fix reads the unsorted key_hi, so it writes where the pair sort would have put its output: `perm` /
         // `hi_s` are final without a swap
         k_tiefix<true><<<nblocks(n), kBlock, 0, st>>>(s->packed_s, s->key_hi, key_lo, nullptr, shift, s->perm, s->hi_s, n, s->info, cur, hil);
@@ -4770,6 +4858,9 @@ static void read_env_knobs(nbmi_sim *s) {
     if (const char *e = getenv("NBMI_FUSE_MAXABS")) s->fuse_maxabs = atoi(e) != 0;
     if (const char *e = getenv("NBMI_HILBERT")) s->hilbert = atoi(e) != 0;
     if (const char *e = getenv("NBMI_SORT_PACKED")) s->sort_packed = atoi(e) != 0;
+    if (const char *e = getenv("NBMI_SORT_DIGIT_BITS")) s->sort_cfg.digit_bits = atoi(e);
+    if (const char *e = getenv("NBMI_SORT_THREADS")) s->sort_cfg.threads = atoi(e);
+    if (const char *e = getenv("NBMI_SORT_FUSED_HIST")) s->sort_fused_hist = atoi(e) != 0 ? 1 : 0;
     if (const char *e = getenv("NBMI_KEYS_LEAN")) s->keys_lean = atoi(e) != 0;
     if (const char *e = getenv("NBMI_WALK_LANE")) s->walk_lane = atoi(e);
     if (const char *e = getenv("NBMI_WALK_STACK")) s->walk_stack = atoi(e);
@@ -4807,6 +4898,11 @@ static nbmi_sim *create_failed(nbmi_sim *s) {
 static int create_impl(nbmi_sim *s, const double *pos, const double *vel, const double *mass) {
     const int64_t n = s->n;
     const int64_t c = s->cap > n ? s->cap : n;  // rows allocated (owner mode keeps head room for immigrants)
+    if (!nbmi::radix_config_ok(s->sort_cfg)) {
+        nbmi::set_error("NBMI_SORT_DIGIT_BITS must be 8 or 10 and NBMI_SORT_THREADS 256, 512 or 1024 (got %d, %d)", s->sort_cfg.digit_bits,
+                        s->sort_cfg.threads);
+        return NBMI_ERR_ARG;
+    }
     NBMI_HIP_CHECK(hipSetDevice(s->device));
     NBMI_HIP_CHECK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
     for (auto &e : s->ev) NBMI_HIP_CHECK(hipEventCreate(&e));

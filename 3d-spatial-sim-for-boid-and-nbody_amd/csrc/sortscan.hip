@@ -7,9 +7,28 @@
 #include "../../include/nbmi.h"
 #include "common.h"
 
+// The hooks' temp buffer: ONE per process, kept from call to call and only ever grown, so that successive sorts of
+// different sizes, fields and configurations run on the same buffer as a handle's do - what a sort leaves behind in it
+// is the next one's to clear.  Used on the default device, one call at a time.
+static void *g_tmp = nullptr;
+static size_t g_tmp_bytes = 0;
+static hipError_t debug_temp(size_t need, hipStream_t st, void **out) {
+    if (need > g_tmp_bytes) {
+        if (g_tmp) (void)hipFree(g_tmp);
+        g_tmp = nullptr;
+        g_tmp_bytes = 0;
+        if (hipError_t e = hipMalloc(&g_tmp, need)) return e;
+        g_tmp_bytes = need;
+        if (hipError_t e = nbmi::radix_init_temp(g_tmp, st)) return e;
+    }
+    *out = g_tmp;
+    return hipSuccess;
+}
+
 // values == null: the keys-only form on the bits [begin_bit, end_bit); otherwise pairs.
 static int debug_sort(const char *who, int key_bytes, int64_t n, const void *keys, const uint32_t *values, void *keys_out,
-                      uint32_t *values_out, int begin_bit, int end_bit, int repeats, double *ms_per_sort) {
+                      uint32_t *values_out, int begin_bit, int end_bit, int repeats, double *ms_per_sort,
+                      nbmi::RadixConfig cfg = {}) {
     if (n == 0) return 0;
     const bool pairs = values != nullptr;
     const int bits = end_bit - begin_bit;
@@ -27,22 +46,22 @@ static int debug_sort(const char *who, int key_bytes, int64_t n, const void *key
     };
     hipError_t e;
     if ((e = hipMalloc(&dk, kb)) || (e = hipMalloc(&dko, kb)) || (pairs && ((e = hipMalloc(&dv, vb)) || (e = hipMalloc(&dvo, vb)))) ||
-        (e = hipMalloc(&tmp, tb)) || (e = hipStreamCreate(&st)) || (e = nbmi::radix_init_temp(tmp, st)) || (e = hipEventCreate(&e0)) || (e = hipEventCreate(&e1)) ||
+        (e = hipStreamCreate(&st)) || (e = debug_temp(tb, st, &tmp)) || (e = hipEventCreate(&e0)) || (e = hipEventCreate(&e1)) ||
         (e = hipMemcpyAsync(dk, keys, kb, hipMemcpyHostToDevice, st)) ||
         (pairs && (e = hipMemcpyAsync(dv, values, vb, hipMemcpyHostToDevice, st))))
         fail("setup", e);
     for (int r = 0; rc == 0 && r < (repeats < 1 ? 1 : repeats) + 1; r++) {  // first run untimed
         if (r == 1) (void)hipEventRecord(e0, st);
         if (!pairs && key_bytes == 8) {
-            e = nbmi::radix_sort_keys_u64(tmp, tb, (const uint64_t *)dk, (uint64_t *)dko, (size_t)n, begin_bit, end_bit, st);
+            e = nbmi::radix_sort_keys_u64(tmp, tb, (const uint64_t *)dk, (uint64_t *)dko, (size_t)n, begin_bit, end_bit, st, cfg);
         } else if (!pairs) {
-            e = nbmi::radix_sort_keys_u32(tmp, tb, (const uint32_t *)dk, (uint32_t *)dko, (size_t)n, begin_bit, end_bit, st);
+            e = nbmi::radix_sort_keys_u32(tmp, tb, (const uint32_t *)dk, (uint32_t *)dko, (size_t)n, begin_bit, end_bit, st, cfg);
         } else if (key_bytes == 8) {
             e = nbmi::radix_sort_pairs_u64(tmp, tb, (const uint64_t *)dk, (uint64_t *)dko, (const uint32_t *)dv,
-                                           (uint32_t *)dvo, (size_t)n, begin_bit, end_bit, st);
+                                           (uint32_t *)dvo, (size_t)n, begin_bit, end_bit, st, cfg);
         } else {
             e = nbmi::radix_sort_pairs_u32(tmp, tb, (const uint32_t *)dk, (uint32_t *)dko, (const uint32_t *)dv,
-                                           (uint32_t *)dvo, (size_t)n, begin_bit, end_bit, st);
+                                           (uint32_t *)dvo, (size_t)n, begin_bit, end_bit, st, cfg);
         }
         if (e != hipSuccess) fail("sort", e);
     }
@@ -59,12 +78,14 @@ static int debug_sort(const char *who, int key_bytes, int64_t n, const void *key
         if (rc == 0 && err) {
             nbmi::set_error("%s: a look-back spin timed out", who);
             rc = NBMI_ERR_HIP;
+            (void)nbmi::radix_init_temp(tmp, st);  // the sticky word has been reported
+            (void)hipStreamSynchronize(st);
         }
     }
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
     if (st) (void)hipStreamDestroy(st);
-    for (void *q : {dk, dko, dv, dvo, tmp})
+    for (void *q : {dk, dko, dv, dvo})
         if (q) (void)hipFree(q);
     return rc;
 }
@@ -87,4 +108,19 @@ extern "C" int nbmi_debug_sort_keys(int key_bytes, int64_t n, const void *keys, 
         return NBMI_ERR_ARG;
     }
     return debug_sort("nbmi_debug_sort_keys", key_bytes, n, keys, nullptr, keys_out, nullptr, begin_bit, end_bit, repeats, ms_per_sort);
+}
+
+// Either form (values == null: keys only) with the passes' digit width (8 or 10) and threads per tile (256, 512 or
+// 1024) given, so that small inputs reach the configurations the size rule keeps for large ones; 0 = by the size rule.
+extern "C" int nbmi_debug_sort_config(int key_bytes, int64_t n, const void *keys, const uint32_t *values, void *keys_out,
+                                      uint32_t *values_out, int begin_bit, int end_bit, int digit_bits, int threads, int repeats,
+                                      double *ms_per_sort) {
+    const nbmi::RadixConfig cfg{digit_bits, threads};
+    if ((key_bytes != 4 && key_bytes != 8) || n < 0 || begin_bit < 0 || end_bit <= begin_bit || end_bit > 8 * key_bytes ||
+        (n && (!keys || !keys_out)) || (n && values && !values_out) || !nbmi::radix_config_ok(cfg)) {
+        nbmi::set_error("nbmi_debug_sort_config: bad arguments");
+        return NBMI_ERR_ARG;
+    }
+    return debug_sort("nbmi_debug_sort_config", key_bytes, n, keys, values, keys_out, values_out, begin_bit, end_bit, repeats, ms_per_sort,
+                      cfg);
 }

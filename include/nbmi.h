@@ -484,6 +484,13 @@ int nbmi_debug_sort_pairs(int key_bytes, int64_t n, const void *keys, const uint
  * with their key (the octree build sorts (prefix << 24 | body index) words this way). */
 int nbmi_debug_sort_keys(int key_bytes, int64_t n, const void *keys, void *keys_out, int begin_bit, int end_bit,
                          int repeats, double *ms_per_sort);
+/* Either form with the configuration of the passes given: digit_bits 8 or 10, threads per 4 096-key tile 256, 512 or
+ * 1024, 0 = what the sort would choose for this size (the octree build reads NBMI_SORT_DIGIT_BITS / NBMI_SORT_THREADS
+ * for the same two).  values == NULL: keys only, on the bits [begin_bit, end_bit); otherwise (key, value) pairs on
+ * those bits.  Anything else is refused with NBMI_ERR_ARG before a launch. */
+int nbmi_debug_sort_config(int key_bytes, int64_t n, const void *keys, const uint32_t *values, void *keys_out,
+                           uint32_t *values_out, int begin_bit, int end_bit, int digit_bits, int threads, int repeats,
+                           double *ms_per_sort);
 
 /* ---- headless point renderer (csrc/render.hip; tools/export.py) ------------------------------------------------
  * The image fixed-function GL draws for the exporter's frame: GL_POINTS with GL_POINT_SMOOTH, glBlendFunc(GL_SRC_ALPHA,
