@@ -31,6 +31,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <type_traits>
 #include <utility>
 #include <vector>
@@ -3892,18 +3893,19 @@ __device__ __forceinline__ KnnGroup knn_group(const Bodies &cur, const uint32_t 
 // One pass over the tree for one wave, k_potential_tree's skeleton: a wave-uniform byte cursor over `Node` and its
 // skip links, per lane `resume` = the offset up to which it sits out because it pruned an ancestor; the wave
 // descends while any active lane cannot prune.  `bound` is what a lane prunes against, strictly: a subtree is
-// skipped only if the lower bound EXCEEDS it, so bodies AT the bound are always reached.
-//   kSum = false  bound = the lane's current k-th candidate (the heap's root), leaves are pushed
-//   kSum = true   bound = r2_k, fixed; leaves with d2 <= r2_k add their mass to `acc`
+// skipped only if the lower bound EXCEEDS it, so bodies AT the bound are always reached.  Shared by K16 and K17.
+// The cursor starts at byte offset `start` (0: the root; the offset of a leaf: everything behind it in key order -
+// the cells that hold that leaf lie in front of it and are never tested, so nothing of theirs is pruned).
 // Leaves of the ranks [ex_lo, ex_hi) are skipped: the caller has dealt with those bodies (the wave's own among them,
-// which is how self is excluded by identity).
-template <bool kSum>
-__device__ __forceinline__ void knn_walk(const Node *__restrict__ nodes, const double4 *__restrict__ rows,
-                                         const int32_t *__restrict__ node_ref, unsigned nn, bool valid, double qx, double qy,
-                                         double qz, int64_t ex_lo, int64_t ex_hi, double *__restrict__ h, int k, double &bound,
-                                         double &acc, long long &evals) {
+// which is how self is excluded by identity).  leaf(d2, row, rank) sees every other leaf a lane reaches and may
+// lower `bound`.
+template <class Leaf>
+__device__ __forceinline__ void query_walk(const Node *__restrict__ nodes, const double4 *__restrict__ rows,
+                                           const int32_t *__restrict__ node_ref, unsigned start, unsigned nn, bool valid,
+                                           double qx, double qy, double qz, int64_t ex_lo, int64_t ex_hi, const double &bound,
+                                           long long &evals, Leaf leaf) {
     unsigned resume = valid ? 0u : 0xffffffffu;
-    unsigned off = 0u;
+    unsigned off = start;
     while (off < nn) {
         off = __builtin_amdgcn_readfirstlane(off);
         const unsigned idx = off / kNodeBytes;
@@ -3915,12 +3917,7 @@ __device__ __forceinline__ void knn_walk(const Node *__restrict__ nodes, const d
             if (active && (r < ex_lo || r >= ex_hi)) {
                 const double d2 = knn_d2(row.x, row.y, row.z, qx, qy, qz);
                 evals++;
-                if (kSum) {
-                    if (d2 <= bound) acc = __dadd_rn(acc, row.w);
-                } else if (d2 < bound) {
-                    knn_push(h, k, d2);
-                    bound = h[0];
-                }
+                leaf(d2, row, r);
             }
             off += kNodeBytes;
         } else {
@@ -3932,6 +3929,24 @@ __device__ __forceinline__ void knn_walk(const Node *__restrict__ nodes, const d
             off = __builtin_amdgcn_ballot_w64(open) ? off + kNodeBytes : nd.next_off;
         }
     }
+}
+// K16's two passes:
+//   kSum = false  bound = the lane's current k-th candidate (the heap's root), leaves are pushed
+//   kSum = true   bound = r2_k, fixed; leaves with d2 <= r2_k add their mass to `acc`
+template <bool kSum>
+__device__ __forceinline__ void knn_walk(const Node *__restrict__ nodes, const double4 *__restrict__ rows,
+                                         const int32_t *__restrict__ node_ref, unsigned nn, bool valid, double qx, double qy,
+                                         double qz, int64_t ex_lo, int64_t ex_hi, double *__restrict__ h, int k, double &bound,
+                                         double &acc, long long &evals) {
+    query_walk(nodes, rows, node_ref, 0u, nn, valid, qx, qy, qz, ex_lo, ex_hi, bound, evals,
+               [&](double d2, const double4 &row, int64_t) {
+                   if (kSum) {
+                       if (d2 <= bound) acc = __dadd_rn(acc, row.w);
+                   } else if (d2 < bound) {
+                       knn_push(h, k, d2);
+                       bound = h[0];
+                   }
+               });
 }
 // One wave per 64 key-adjacent bodies, in one launch:
 //   seed     exact distances to the wave's own 64 bodies and the 64 before and after them in key order (Hilbert
@@ -4023,6 +4038,373 @@ __global__ __launch_bounds__(kBlock) void k_knn_out(const double *__restrict__ r
     if (out_r2) out_r2[o] = r2[r];
     if (out_mass) out_mass[o] = mass[r];
     if (out_rho) out_rho[o] = knn_density(r2[r], mass[r]);
+}
+
+
+// ---------------------------------------------------------------------------------------
+// K17: friends-of-friends groups (nbmi_fof / nbmi_fof_catalogue / nbmi_compute_group_colors; include/nbmi.h, DESIGN.md
+// section 4.15).  The build, the node rows, d2, the lower bound and the walk are K16's; new are the fixed-radius pair
+// search, a lock-free union-find over key ranks and the per-group reductions.
+// ---------------------------------------------------------------------------------------
+// The union-find.  parent[] is int32 over key ranks, parent[r] = r before the link kernel.  Invariants:
+//   (a) A store only ever LOWERS parent[r] (a root is hooked under a smaller rank by a CAS, path halving is an atomic
+//       min).  So parent[r] <= r always, every parent chain strictly decreases, and fof_find terminates even on stale
+//       values - a stale parent is still an ancestor.
+//   (b) Two roots are hooked only by CAS(&parent[hi], hi, lo) with lo < hi.  On failure the thread goes on from the
+//       value the CAS returned: another thread has lowered that word, so the system as a whole always progresses.
+//   (c) NO loop waits for another thread's progress: no spin, no flag, no barrier across waves.  Every iteration of
+//       fof_find steps down a strictly decreasing chain; every iteration of fof_unite ends in a return or follows a
+//       word that somebody lowered.
+//   (d) During the link kernel EVERY access to parent[] is an agent-scope relaxed atomic (load, min, CAS): the eight
+//       XCDs have private L2s and a CU's L1 is never refreshed by other CUs' stores (radix.hip's discipline for its
+//       status words).  Plain accesses begin behind the next kernel boundary (k_fof_flatten).
+__device__ __forceinline__ int fof_load(int32_t *parent, int r) {
+    return __hip_atomic_load(parent + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ int fof_find(int32_t *parent, int r) {
+    int p = fof_load(parent, r);
+    while (p != r) {
+        const int g = fof_load(parent, p);
+        if (g != p) (void)__hip_atomic_fetch_min(parent + r, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // path halving
+        r = p;
+        p = g;
+    }
+    return r;
+}
+// joins the sets of a and b; returns the root of the joined set as this thread saw it last (an ancestor of both from now on)
+__device__ __forceinline__ int fof_unite(int32_t *parent, int a, int b) {
+    for (;;) {
+        a = fof_find(parent, a);
+        b = fof_find(parent, b);
+        if (a == b) return a;
+        const int hi = a > b ? a : b, lo = a > b ? b : a;
+        int seen = hi;
+        if (__hip_atomic_compare_exchange_strong(parent + hi, &seen, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                                 __HIP_MEMORY_SCOPE_AGENT))
+            return lo;
+        a = seen;  // (< hi: whoever won the word lowered it)
+        b = lo;
+    }
+}
+// The lanes of a wave that found a link to the body of rank r (wave-uniform) at the same moment.  Every lane carries
+// `mine`, an ancestor of its own rank (its rank at first, then whatever root it saw last): lanes with equal ancestors are
+// in one set already, so of those that share the first linking lane's ancestor only that lane goes to memory, and the
+// others take over the root it comes back with.  An optimisation only: every set that links to r is united with r.
+// Called by all lanes that evaluated r (link = false for those that are too far), in one branch.
+__device__ __forceinline__ void fof_link_lanes(int32_t *parent, bool link, int &mine, int r) {
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(link);
+    if (m == 0ull) return;
+    const int leader = __builtin_amdgcn_readfirstlane(__ffsll((long long)m) - 1);
+    const int lane = threadIdx.x & 63;
+    const int shared = __builtin_amdgcn_readlane(mine, leader);
+    const bool follows = link && lane != leader && mine == shared;
+    if (link && !follows) mine = fof_unite(parent, mine, r);
+    const int joined = __builtin_amdgcn_readlane(mine, leader);
+    if (follows) mine = joined;
+}
+constexpr int kFofBlock = 64;  // one wave per workgroup, as K16
+// parent / minid / cnt of every rank, and for every wave the node index of its first body's leaf (the node array is
+// in key order: everything of a higher rank lies behind that leaf)
+__global__ __launch_bounds__(kBlock) void k_fof_init(const Node *__restrict__ nodes, const int32_t *__restrict__ node_ref,
+                                                     const TreeInfo *__restrict__ info, int64_t n, int64_t capacity,
+                                                     int32_t *__restrict__ parent, int32_t *__restrict__ minid,
+                                                     int32_t *__restrict__ cnt, uint32_t *__restrict__ wleaf) {
+    const int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (idx < n) {
+        parent[idx] = (int32_t)idx;
+        minid[idx] = INT32_MAX;
+        cnt[idx] = 0;
+    }
+    if (info->error != 0 || info->sticky_error != 0) return;
+    if (idx >= info->num_nodes || idx >= capacity) return;
+    if (__float_as_int(nodes[idx].s2t) != 0) return;
+    const int32_t r = node_ref[idx];
+    if ((r & 63) == 0) wleaf[r >> 6] = (uint32_t)idx;
+}
+// The pair search: one wave per 64 key-adjacent bodies.  Pairs inside the wave are tested directly (the bodies go round
+// by readlane, each pair once: the higher lane tests the lower); every other pair is found by the walk against the
+// fixed bound b2 - a cell is pruned only if knn_lower EXCEEDS b2, so a pair AT the linking length is always reached.
+//   half = 1  the cursor starts at the leaf of the wave's first body and the wave's own ranks are skipped: the wave
+//             sees exactly the bodies of a higher rank, every pair of two waves is found once, by the lower wave
+//   half = 0  the whole tree (every such pair twice; the measurement's other side)
+// Every link found goes to fof_link_lanes, which unites the two sets.  evals (may be null) counts the distances evaluated.
+__global__ __launch_bounds__(kFofBlock) void k_fof_link(const Node *__restrict__ nodes, const double4 *__restrict__ rows,
+                                                        const int32_t *__restrict__ node_ref, const TreeInfo *__restrict__ info,
+                                                        const uint32_t *__restrict__ perm, Bodies cur, int64_t n, double b2,
+                                                        int half, const uint32_t *__restrict__ wleaf, int32_t *parent,
+                                                        unsigned long long *__restrict__ evals_out) {
+    if (info->error != 0 || info->sticky_error != 0) return;
+    const int lane = threadIdx.x;
+    const int64_t w0 = (int64_t)blockIdx.x * kFofBlock, rank = w0 + lane;
+    const bool valid = rank < n;
+    const unsigned nn = __builtin_amdgcn_readfirstlane((unsigned)info->num_nodes * kNodeBytes);
+    const KnnGroup own = knn_group(cur, perm, w0, n);
+    const double qx = own.x, qy = own.y, qz = own.z;
+    long long evals = 0;
+    int mine = (int)rank;  // an ancestor of this lane's rank (fof_link_lanes)
+    for (int i = 0; i < 63; i++) {
+        if (w0 + i >= n) break;
+        const double d2 = knn_d2(knn_bcast(own.x, i), knn_bcast(own.y, i), knn_bcast(own.z, i), qx, qy, qz);
+        if (valid && lane > i) {
+            evals++;
+            fof_link_lanes(parent, d2 <= b2, mine, (int)(w0 + i));
+        }
+    }
+    const unsigned start = half ? __builtin_amdgcn_readfirstlane(wleaf[blockIdx.x]) * kNodeBytes : 0u;
+    query_walk(nodes, rows, node_ref, start, nn, valid, qx, qy, qz, half ? (int64_t)0 : w0, w0 + kFofBlock, b2, evals,
+               [&](double d2, const double4 &, int64_t r) { fof_link_lanes(parent, d2 <= b2, mine, (int)r); });
+    if (evals_out) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) evals += __shfl_xor(evals, o);
+        if (lane == 0) atomicAdd(evals_out, (unsigned long long)evals);
+    }
+}
+// Behind the kernel boundary parent[] is final and read plainly: root[r] = the root of r's tree, minid[root] = the
+// smallest caller index and cnt[root] = the number of bodies below it (integer atomics: order independent).
+__global__ __launch_bounds__(kBlock) void k_fof_flatten(const TreeInfo *__restrict__ info, int64_t n,
+                                                        const int32_t *__restrict__ parent, const uint32_t *__restrict__ perm,
+                                                        const int32_t *__restrict__ id, int32_t *__restrict__ root,
+                                                        int32_t *__restrict__ minid, int32_t *__restrict__ cnt) {
+    if (info->error != 0 || info->sticky_error != 0) return;
+    const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const bool valid = r < n;
+    const int lane = threadIdx.x & 63;
+    int f = -1, own = INT32_MAX;
+    if (valid) {
+        f = (int)r;
+        for (int p = parent[f]; p != f; p = parent[f]) f = p;
+        root[r] = f;
+        own = id[perm[r]];
+    }
+    // Key-adjacent ranks mostly share their root, and a root that a large group hangs on would otherwise take one
+    // same-address atomic per member: the lanes that share the root of the first lane left go in as one (twice), the
+    // rest on their own.
+    unsigned long long todo = __builtin_amdgcn_ballot_w64(valid);
+    for (int round = 0; round < 2 && todo != 0ull; round++) {
+        const int leader = __builtin_amdgcn_readfirstlane(__ffsll((long long)todo) - 1);
+        const int f0 = __builtin_amdgcn_readlane(f, leader);
+        const bool with = ((todo >> lane) & 1ull) != 0ull && f == f0;
+        const unsigned long long same = __builtin_amdgcn_ballot_w64(with);
+        int least = with ? own : INT32_MAX;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const int other = __shfl_xor(least, o);
+            least = other < least ? other : least;
+        }
+        if (lane == leader) {
+            atomicMin(&minid[f0], least);
+            atomicAdd(&cnt[f0], (int)__popcll(same));
+        }
+        todo &= ~same;
+    }
+    if ((todo >> lane) & 1ull) {
+        atomicMin(&minid[f], own);
+        atomicAdd(&cnt[f], 1);
+    }
+}
+// label of every body in the caller's order (may be null), and the number of roots
+__global__ __launch_bounds__(kBlock) void k_fof_labels(const TreeInfo *__restrict__ info, int64_t n,
+                                                       const int32_t *__restrict__ root, const int32_t *__restrict__ minid,
+                                                       const uint32_t *__restrict__ perm, const int32_t *__restrict__ id,
+                                                       int32_t *__restrict__ labels, unsigned long long *__restrict__ n_roots) {
+    if (info->error != 0 || info->sticky_error != 0) return;
+    const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const bool is_root = r < n && root[r] == (int32_t)r;
+    if (r < n && labels) labels[id[perm[r]]] = minid[root[r]];
+    const unsigned long long roots = __builtin_amdgcn_ballot_w64(is_root);
+    if ((threadIdx.x & 63) == 0 && roots) atomicAdd(n_roots, (unsigned long long)__popcll(roots));
+}
+// group colours: the speed ramp at a hash of the label for the bodies of a group of at least min_members, grey
+// for the others.  Runs behind k_knn_restore: a build that did not fit has left its mark in the sticky word.
+__global__ __launch_bounds__(kBlock) void k_fof_colors(const TreeInfo *__restrict__ info, int64_t n,
+                                                       const int32_t *__restrict__ root, const int32_t *__restrict__ minid,
+                                                       const int32_t *__restrict__ cnt, const uint32_t *__restrict__ perm,
+                                                       const int32_t *__restrict__ id, int64_t min_members,
+                                                       float *__restrict__ colors) {
+    if (info->error != 0 || info->sticky_error != 0) return;
+    const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (r >= n) return;
+    const int32_t f = root[r];
+    float cr = 0.25f, cg = 0.25f, cb = 0.25f;
+    if ((int64_t)cnt[f] >= min_members)
+        color_ramp_t((double)(((uint32_t)minid[f] * 2654435761u) >> 8) / 16777216.0, cr, cg, cb);
+    const int64_t o = 3 * (int64_t)id[perm[r]];
+    colors[o] = cr; colors[o + 1] = cg; colors[o + 2] = cb;
+}
+
+// ---- the catalogue ----------------------------------------------------------------------------------------------
+// The ranks are sorted by root (stable: inside a group they stay in key order), so a group is one segment [h, h + cnt)
+// of the sorted array.  The array is cut into chunks of kFofChunk entries at fixed positions; a workgroup reduces the
+// parts of the segments inside its chunk by a segmented block scan (scan.h's order contract: the tree is fixed), and a
+// segment that crosses chunks - a group may hold nearly all the bodies - is put together from its chunks' partials in
+// chunk order by one wave (a fixed strided order per lane, then a fixed tree).  No floating-point atomics anywhere:
+// two calls on one state give the same bits.
+constexpr int kFofChunk = 256;
+constexpr int kFofSums = 13;  // M, m x[3], m v[3], x[3], v[3]
+constexpr int kFofVals = 19;  // ... then lo[3], hi[3]
+struct FofSeg {
+    double v;
+    int head;  // a segment starts at or in front of this entry (inside the scanned range)
+};
+__device__ __forceinline__ FofSeg lane_up(const FofSeg &s, int d) { return FofSeg{__shfl_up(s.v, d), __shfl_up(s.head, d)}; }
+struct FofMax {
+    __device__ double operator()(double a, double b) const { return b > a ? b : a; }
+};
+template <class Inner>
+struct FofSegOp {
+    Inner in;
+    __device__ FofSeg operator()(const FofSeg &a, const FofSeg &b) const {
+        return FofSeg{b.head ? b.v : in(a.v, b.v), a.head | b.head};
+    }
+};
+// what a value of column c is combined by, and its identity
+__device__ __forceinline__ double fof_combine(int c, double a, double b) {
+    return c < kFofSums ? __dadd_rn(a, b) : c < kFofSums + 3 ? (b < a ? b : a) : (b > a ? b : a);
+}
+__device__ __forceinline__ double fof_identity(int c) { return c < kFofSums ? 0.0 : c < kFofSums + 3 ? INFINITY : -INFINITY; }
+
+// heads of the segments: where a root's segment begins, and "no catalogue row" until the compaction says otherwise
+__global__ __launch_bounds__(kBlock) void k_fof_heads(int64_t n, const uint32_t *__restrict__ key_s, int32_t *__restrict__ hpos,
+                                                      int32_t *__restrict__ slot_of) {
+    const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (e >= n) return;
+    const uint32_t k = key_s[e];
+    if (e == 0 || key_s[e - 1] != k) {
+        hpos[k] = (int32_t)e;
+        slot_of[k] = -1;
+    }
+}
+__global__ __launch_bounds__(kBlock) void k_fof_iota(int64_t n, uint32_t *__restrict__ out) {
+    const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (r < n) out[r] = (uint32_t)r;
+}
+// the qualifying groups in the order of their segments: row `slot` is the group whose segment begins at qhead[slot]
+struct FofQualifies {
+    const uint32_t *key_s;
+    const int32_t *cnt;
+    int64_t min_members;
+    __device__ unsigned operator()(int64_t first, int64_t n) const {
+        return scan::item_mask(first, n, [&](int64_t e) {
+            const uint32_t k = key_s[e];
+            return (e == 0 || key_s[e - 1] != k) && (int64_t)cnt[k] >= min_members;
+        });
+    }
+};
+struct FofEmitHead {
+    const uint32_t *key_s;
+    int32_t *qhead, *slot_of;
+    __device__ void operator()(unsigned m, int64_t first, int64_t slot) const {
+        scan::for_each_item(m, first, slot, [&](int64_t e, int64_t row) {
+            qhead[row] = (int32_t)e;
+            slot_of[key_s[e]] = (int32_t)row;
+        });
+    }
+};
+// One workgroup per chunk, one sorted entry per thread.  The scanned value at the LAST entry of a segment's part
+// inside the chunk is that part's reduction; it goes
+//   to the group's row           if the whole segment lies inside the chunk (and the group has a row),
+//   to last_part[chunk]          else if the part ends at the chunk's last entry,
+//   to first_part[chunk]         else (the part then begins at the chunk's first entry).
+__global__ __launch_bounds__(kFofChunk) void k_fof_chunks(int64_t n, const uint32_t *__restrict__ key_s,
+                                                          const uint32_t *__restrict__ rank_s, const uint32_t *__restrict__ perm,
+                                                          Bodies cur, const int32_t *__restrict__ hpos,
+                                                          const int32_t *__restrict__ cnt, const int32_t *__restrict__ slot_of,
+                                                          double *__restrict__ row_vals, double *__restrict__ last_part,
+                                                          double *__restrict__ first_part) {
+    const int64_t cs = (int64_t)blockIdx.x * kFofChunk, e = cs + threadIdx.x;
+    const int64_t ce = cs + kFofChunk - 1 < n - 1 ? cs + kFofChunk - 1 : n - 1;
+    const bool in = e < n;
+    double val[kFofVals];
+#pragma unroll
+    for (int c = 0; c < kFofVals; c++) val[c] = fof_identity(c);
+    int head = 1;
+    int64_t h = 0, end = 0;
+    uint32_t k = 0;
+    if (in) {
+        k = key_s[e];
+        h = hpos[k];
+        end = h + cnt[k] - 1;
+        head = e == h;
+        const uint32_t j = perm[rank_s[e]];
+        const double m = cur.m[j];
+        const double p[3] = {cur.x[j], cur.y[j], cur.z[j]}, v[3] = {cur.vx[j], cur.vy[j], cur.vz[j]};
+        val[0] = m;
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            val[1 + a] = __dmul_rn(m, p[a]);
+            val[4 + a] = __dmul_rn(m, v[a]);
+            val[7 + a] = p[a];
+            val[10 + a] = v[a];
+            val[13 + a] = p[a];
+            val[16 + a] = p[a];
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < kFofVals; c++) {
+        const FofSeg x{val[c], head}, seed{fof_identity(c), 0};
+        if (c < kFofSums) val[c] = scan::block_scan<kFofChunk>(x, seed, FofSegOp<scan::Sum>{}).incl.v;
+        else if (c < kFofSums + 3) val[c] = scan::block_scan<kFofChunk>(x, seed, FofSegOp<scan::Min>{}).incl.v;
+        else val[c] = scan::block_scan<kFofChunk>(x, seed, FofSegOp<FofMax>{}).incl.v;
+    }
+    if (!in || e != (end < ce ? end : ce)) return;
+    double *dst;
+    if (h >= cs && end <= ce) {
+        const int32_t slot = slot_of[k];
+        if (slot < 0) return;
+        dst = row_vals + (int64_t)slot * kFofVals;
+    } else {
+        dst = (e == ce ? last_part : first_part) + (int64_t)blockIdx.x * kFofVals;
+    }
+#pragma unroll
+    for (int c = 0; c < kFofVals; c++) dst[c] = val[c];
+}
+// One wave per catalogue row: the group's 19 values - its row as k_fof_chunks left it, or its chunks' partials, lane l
+// taking the chunks c0 + l, c0 + l + 64, .. in this order, the lanes then combined by the halving tree - and from them
+// {M, c[3], v[3], lo[3], hi[3]}, the label and the member count.
+__global__ __launch_bounds__(kFofBlock) void k_fof_rows(int64_t n, int64_t count, const int32_t *__restrict__ qhead,
+                                                        const uint32_t *__restrict__ key_s, const int32_t *__restrict__ cnt,
+                                                        const int32_t *__restrict__ minid, const double *__restrict__ row_vals,
+                                                        const double *__restrict__ last_part,
+                                                        const double *__restrict__ first_part, double *__restrict__ out13,
+                                                        int32_t *__restrict__ label, int64_t *__restrict__ members) {
+    const int64_t slot = blockIdx.x;
+    if (slot >= count) return;
+    const int lane = threadIdx.x;
+    const int64_t e0 = qhead[slot];
+    const uint32_t k = key_s[e0];
+    const int64_t m = cnt[k], e1 = e0 + m - 1;
+    const int64_t c0 = e0 / kFofChunk, c1 = e1 / kFofChunk;
+    double val[kFofVals];
+    if (c0 == c1) {
+#pragma unroll
+        for (int c = 0; c < kFofVals; c++) val[c] = row_vals[slot * kFofVals + c];
+    } else {
+#pragma unroll
+        for (int c = 0; c < kFofVals; c++) val[c] = fof_identity(c);
+        const int64_t last_of_c1 = c1 * kFofChunk + kFofChunk - 1 < n - 1 ? c1 * kFofChunk + kFofChunk - 1 : n - 1;
+        for (int64_t ch = c0 + lane; ch <= c1; ch += kFofBlock) {
+            const double *part = (ch < c1 || e1 == last_of_c1 ? last_part : first_part) + ch * kFofVals;
+#pragma unroll
+            for (int c = 0; c < kFofVals; c++) val[c] = fof_combine(c, val[c], part[c]);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+            for (int c = 0; c < kFofVals; c++) val[c] = fof_combine(c, val[c], __shfl_down(val[c], o));
+        }
+    }
+    if (lane != 0) return;
+    double *o = out13 + slot * 13;
+    const double M = val[0];
+    const double div = M != 0.0 ? M : (double)m;  // M == 0: the unweighted means of positions and velocities
+    const int from = M != 0.0 ? 1 : 7;
+    o[0] = M;
+#pragma unroll
+    for (int a = 0; a < 6; a++) o[1 + a] = val[from + a] / div;
+#pragma unroll
+    for (int a = 0; a < 6; a++) o[7 + a] = val[13 + a];
+    label[slot] = minid[k];
+    members[slot] = m;
 }
 
 }  // namespace
@@ -4170,6 +4552,26 @@ struct nbmi_sim {
     double *knn_r2 = nullptr, *knn_mass = nullptr;
     double4 *knn_rows = nullptr;
     unsigned long long *knn_evals = nullptr;
+    // friends-of-friends groups (nbmi_fof), allocated by the first call; no step touches them.
+    // 16 bytes per body (parent, root, smallest caller index and member count by key rank), 4 bytes per 64 bodies (the
+    // waves' first leaves) and the node rows of the k-NN query
+    int32_t *fof_parent = nullptr, *fof_root = nullptr, *fof_minid = nullptr, *fof_cnt = nullptr;
+    uint32_t *fof_wleaf = nullptr;
+    unsigned long long *fof_counters = nullptr;  // [0] distances evaluated, [1] roots
+    bool fof_ready = false, fof_cat_ready = false;  // every array of the query / of the catalogue is there (set after the last allocation)
+    bool fof_half = true;  // the pair search starts at the wave's own first leaf (NBMI_FOF_HALF=0: at the root; measurement)
+    // its catalogue (nbmi_fof_catalogue), allocated by the first call: 24 bytes per body (sorted roots, ranks in and
+    // out, segment heads, row of a root, head of a row), the sort's temp buffer, 304 bytes per chunk of 256 bodies and
+    // 268 bytes per catalogue row (a power of two of rows, regrown - the smaller arrays freed - when a call needs more)
+    uint32_t *fof_key_s = nullptr, *fof_rank = nullptr, *fof_rank_s = nullptr, *fof_tiles = nullptr;
+    int32_t *fof_hpos = nullptr, *fof_slot = nullptr, *fof_qhead = nullptr;
+    char *fof_sort_tmp = nullptr;
+    size_t fof_sort_bytes = 0;
+    double *fof_last = nullptr, *fof_first = nullptr;
+    int64_t fof_row_cap = 0;
+    double *fof_row_vals = nullptr, *fof_out13 = nullptr;
+    int32_t *fof_label = nullptr;
+    int64_t *fof_members = nullptr;
     // what nbmi_compute_colors / nbmi_frame_begin colour by (nbmi_set_color_mode)
     int color_mode = NBMI_COLOR_SPEED, color_k = 32;
     double color_lo = 0.0, color_hi = 1.0;
@@ -4210,6 +4612,16 @@ int dev_alloc(nbmi_sim *s, T **p, size_t count) {
     s->allocs.push_back(q);
     *p = (T *)q;
     return 0;
+}
+
+// gives back one array of dev_alloc (the caller knows that nothing enqueued uses it)
+template <typename T>
+void dev_free(nbmi_sim *s, T **p) {
+    if (!*p) return;
+    auto it = std::find(s->allocs.begin(), s->allocs.end(), (void *)*p);
+    if (it != s->allocs.end()) s->allocs.erase(it);
+    (void)hipFree(*p);
+    *p = nullptr;
 }
 
 int alloc_bodies(nbmi_sim *s, Bodies *b, int64_t n) {
@@ -4751,7 +5163,7 @@ int check_device_error(nbmi_sim *s) {
     return rc;
 }
 
-// A query's own octree build between two steps (nbmi_diagnostics' potential, the k-NN query).  The build overwrites the
+// A query's own octree build between two steps (nbmi_diagnostics' potential, the k-NN query, the group finder).  The build overwrites the
 // tree header (maxabs_next, force_all64, the counters) and host fields of the handle; the scope puts both back, so the
 // next step finds the handle as it would have without the query.
 struct SideBuild {
@@ -4795,6 +5207,31 @@ struct SideBuild {
         return r;
     }
 };
+
+// What every query of this family enqueues on the compute stream without ever waiting: inside a SideBuild the octree of
+// the current positions is built with the query rows (node_ref) and the rows are written (knn_rows: query_buffers
+// first), then `launch` adds the query's own kernels.  A capacity error of the build stays in the sticky words for the
+// next call that looks.
+int query_buffers(nbmi_sim *s) {
+    if (!s->knn_rows && (dev_alloc(s, &s->knn_rows, s->node_capacity + 2) || dev_alloc(s, &s->knn_evals, 1))) return NBMI_ERR_HIP;
+    return 0;
+}
+template <class Launch>
+int query_enqueue(nbmi_sim *s, const char *what, Launch launch) {
+    SideBuild side(s);
+    if (side.rc) return side.rc;
+    int rc = enqueue_tree(s);
+    if (rc == 0) {
+        k_knn_rows<<<nblocks(s->own_node_rows), kBlock, 0, s->stream>>>(s->nodes, s->nodes64, s->node_ref, s->perm,
+                                                                         s->buf[s->curbuf], s->info, s->own_node_rows, s->knn_rows);
+        launch();
+        if (hipGetLastError() != hipSuccess) {
+            nbmi::set_error("%s launch failed", what);
+            rc = NBMI_ERR_HIP;
+        }
+    }
+    return side.finish(rc, false);
+}
 
 }  // namespace
 
@@ -4862,6 +5299,7 @@ static void read_env_knobs(nbmi_sim *s) {
     if (const char *e = getenv("NBMI_SORT_THREADS")) s->sort_cfg.threads = atoi(e);
     if (const char *e = getenv("NBMI_SORT_FUSED_HIST")) s->sort_fused_hist = atoi(e) != 0 ? 1 : 0;
     if (const char *e = getenv("NBMI_KEYS_LEAN")) s->keys_lean = atoi(e) != 0;
+    if (const char *e = getenv("NBMI_FOF_HALF")) s->fof_half = atoi(e) != 0;
     if (const char *e = getenv("NBMI_WALK_LANE")) s->walk_lane = atoi(e);
     if (const char *e = getenv("NBMI_WALK_STACK")) s->walk_stack = atoi(e);
     if (const char *e = getenv("NBMI_FORCE_PREC")) {
@@ -5426,32 +5864,18 @@ int knn_check(nbmi_sim *s, int k, const char *what) {
     }
     return 0;
 }
-// Enqueues the whole query on the compute stream and never waits: inside a SideBuild the octree of the current positions
-// is built with the query rows (node_ref), the rows written and the waves run.  r2_k and mass_k are in knn_r2 / knn_mass
-// by state row afterwards.  A capacity error of the build stays in the sticky words for the next call that looks.
-// `count`: also sum the evaluated distances into knn_evals.
+// The k-NN query: r2_k and mass_k are in knn_r2 / knn_mass by state row afterwards.  `count`: also sum the evaluated
+// distances into knn_evals.
 int knn_enqueue(nbmi_sim *s, int k, bool count) {
     const int64_t n = s->n;
-    if (!s->knn_r2 && (dev_alloc(s, &s->knn_r2, n) || dev_alloc(s, &s->knn_mass, n) ||
-                       dev_alloc(s, &s->knn_rows, s->node_capacity + 2) || dev_alloc(s, &s->knn_evals, 1)))
-        return NBMI_ERR_HIP;
+    if (query_buffers(s) || (!s->knn_r2 && (dev_alloc(s, &s->knn_r2, n) || dev_alloc(s, &s->knn_mass, n)))) return NBMI_ERR_HIP;
     hipStream_t st = s->stream;
     if (count) NBMI_HIP_CHECK(hipMemsetAsync(s->knn_evals, 0, sizeof(unsigned long long), st));
-    SideBuild side(s);
-    if (side.rc) return side.rc;
-    int rc = enqueue_tree(s);
-    if (rc == 0) {
-        k_knn_rows<<<nblocks(s->own_node_rows), kBlock, 0, st>>>(s->nodes, s->nodes64, s->node_ref, s->perm, s->buf[s->curbuf],
-                                                                  s->info, s->own_node_rows, s->knn_rows);
+    return query_enqueue(s, "k_knn", [&] {
         k_knn<<<(int)((n + kKnnBlock - 1) / kKnnBlock), kKnnBlock, (size_t)k * kKnnBlock * sizeof(double), st>>>(
             s->nodes, s->knn_rows, s->node_ref, s->info, s->perm, s->buf[s->curbuf], n, k, s->knn_r2, s->knn_mass,
             count ? s->knn_evals : nullptr);
-        if (hipGetLastError() != hipSuccess) {
-            nbmi::set_error("k_knn launch failed");
-            rc = NBMI_ERR_HIP;
-        }
-    }
-    return side.finish(rc, false);
+    });
 }
 // the synchronous form behind nbmi_knn / nbmi_get_densities_f64: errors of earlier steps first, as a getter reports
 // them, then the query and its own
@@ -5493,6 +5917,194 @@ int nbmi_get_densities_f64(nbmi_sim *s, int k, double *rho) {
     NBMI_HIP_CHECK(hipGetLastError());
     NBMI_HIP_CHECK(hipMemcpyAsync(rho, s->stage, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
+    return 0;
+}
+
+namespace {
+// nbmi_fof and everything built on it: the handles the k-NN query accepts, a positive finite linking length
+int fof_check(nbmi_sim *s, double link, int64_t min_members, int64_t capacity, const char *what) {
+    if (const char *why = knn_refusal(s)) {
+        nbmi::set_error("%s: %s", what, why);
+        return NBMI_ERR_ARG;
+    }
+    if (!isfinite(link) || !(link > 0.0)) {
+        nbmi::set_error("%s: the linking length %g is not finite and > 0", what, link);
+        return NBMI_ERR_ARG;
+    }
+    if (min_members < 1) {
+        nbmi::set_error("%s: min_members = %lld is < 1", what, (long long)min_members);
+        return NBMI_ERR_ARG;
+    }
+    if (capacity < 0) {
+        nbmi::set_error("%s: capacity = %lld is < 0", what, (long long)capacity);
+        return NBMI_ERR_ARG;
+    }
+    return 0;
+}
+// Enqueues build, pair search and flattening and never waits.  Afterwards, by key rank: fof_root, fof_minid[root] (the
+// label), fof_cnt[root]; fof_counters = {distances evaluated (if `count`), roots}; `labels` (device, may be null) in the
+// caller's order.
+int fof_enqueue(nbmi_sim *s, double b2, bool count, int32_t *labels) {
+    const int64_t n = s->n;
+    if (query_buffers(s)) return NBMI_ERR_HIP;
+    if (!s->fof_ready) {
+        if (dev_alloc(s, &s->fof_parent, n) || dev_alloc(s, &s->fof_root, n) || dev_alloc(s, &s->fof_minid, n) ||
+            dev_alloc(s, &s->fof_cnt, n) || dev_alloc(s, &s->fof_wleaf, (n + 63) / 64) || dev_alloc(s, &s->fof_counters, 2))
+            return NBMI_ERR_HIP;
+        s->fof_ready = true;
+    }
+    hipStream_t st = s->stream;
+    NBMI_HIP_CHECK(hipMemsetAsync(s->fof_counters, 0, 2 * sizeof(unsigned long long), st));
+    return query_enqueue(s, "k_fof_link", [&] {
+        const Bodies cur = s->buf[s->curbuf];
+        const int64_t rows = s->own_node_rows > n ? s->own_node_rows : n;
+        k_fof_init<<<nblocks(rows), kBlock, 0, st>>>(s->nodes, s->node_ref, s->info, n, s->own_node_rows, s->fof_parent,
+                                                     s->fof_minid, s->fof_cnt, s->fof_wleaf);
+        k_fof_link<<<(int)((n + kFofBlock - 1) / kFofBlock), kFofBlock, 0, st>>>(
+            s->nodes, s->knn_rows, s->node_ref, s->info, s->perm, cur, n, b2, s->fof_half ? 1 : 0, s->fof_wleaf, s->fof_parent,
+            count ? s->fof_counters : nullptr);
+        k_fof_flatten<<<nblocks(n), kBlock, 0, st>>>(s->info, n, s->fof_parent, s->perm, cur.id, s->fof_root, s->fof_minid,
+                                                     s->fof_cnt);
+        k_fof_labels<<<nblocks(n), kBlock, 0, st>>>(s->info, n, s->fof_root, s->fof_minid, s->perm, cur.id, labels,
+                                                    s->fof_counters + 1);
+    });
+}
+// the synchronous form, as knn_query
+int fof_query(nbmi_sim *s, double b2, bool count, int32_t *labels) {
+    NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
+    if (int rc = check_device_error(s)) return rc;
+    if (int rc = fof_enqueue(s, b2, count, labels)) return rc;
+    NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
+    return check_device_error(s);
+}
+int fof_catalogue_buffers(nbmi_sim *s) {
+    if (s->fof_cat_ready) return 0;
+    const int64_t n = s->n, chunks = (n + kFofChunk - 1) / kFofChunk;
+    if (dev_alloc(s, &s->fof_key_s, n) || dev_alloc(s, &s->fof_rank, n) || dev_alloc(s, &s->fof_rank_s, n) ||
+        dev_alloc(s, &s->fof_hpos, n) || dev_alloc(s, &s->fof_slot, n) || dev_alloc(s, &s->fof_qhead, n) ||
+        dev_alloc(s, &s->fof_tiles, scan::tiles_for(n) + 1) || dev_alloc(s, &s->fof_last, chunks * kFofVals) ||
+        dev_alloc(s, &s->fof_first, chunks * kFofVals))
+        return NBMI_ERR_HIP;
+    s->fof_sort_bytes = nbmi::radix_temp_bytes_u32((size_t)n, 32);
+    if (dev_alloc(s, &s->fof_sort_tmp, s->fof_sort_bytes + 256)) return NBMI_ERR_HIP;
+    NBMI_HIP_CHECK(nbmi::radix_init_temp(s->fof_sort_tmp, s->stream));
+    s->fof_cat_ready = true;
+    return 0;
+}
+// The catalogue's row arrays for at least `rows` rows, in powers of two.  Arrays that are too small are freed: the
+// caller has just waited for the stream, and nothing enqueued reads them.
+int fof_row_buffers(nbmi_sim *s, int64_t rows) {
+    if (rows <= s->fof_row_cap) return 0;
+    s->fof_row_cap = 0;
+    dev_free(s, &s->fof_row_vals);
+    dev_free(s, &s->fof_out13);
+    dev_free(s, &s->fof_label);
+    dev_free(s, &s->fof_members);
+    int64_t cap = 1024;
+    while (cap < rows) cap *= 2;
+    if (dev_alloc(s, &s->fof_row_vals, cap * kFofVals) || dev_alloc(s, &s->fof_out13, cap * 13) ||
+        dev_alloc(s, &s->fof_label, cap) || dev_alloc(s, &s->fof_members, cap))
+        return NBMI_ERR_HIP;
+    s->fof_row_cap = cap;
+    return 0;
+}
+}  // namespace
+
+int nbmi_fof(nbmi_sim *s, double link, int32_t *labels, int64_t *n_groups, int64_t *evals) {
+    if (int rc = check_handle(s)) return rc;
+    if (int rc = fof_check(s, link, 1, 0, "nbmi_fof")) return rc;
+    if (n_groups) *n_groups = 0;
+    if (evals) *evals = 0;
+    const int64_t n = s->n;
+    if (n == 0) return 0;
+    if (int rc = fof_query(s, link * link, evals != nullptr, labels ? (int32_t *)s->stage : nullptr)) return rc;
+    unsigned long long c[2] = {0, 0};
+    if (labels) NBMI_HIP_CHECK(hipMemcpyAsync(labels, s->stage, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
+    NBMI_HIP_CHECK(hipMemcpyAsync(c, s->fof_counters, sizeof(c), hipMemcpyDeviceToHost, s->stream));
+    NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
+    if (evals) *evals = (int64_t)c[0];
+    if (n_groups) *n_groups = (int64_t)c[1];
+    return 0;
+}
+
+int nbmi_fof_catalogue(nbmi_sim *s, double link, int64_t min_members, int64_t capacity, int32_t *label, int64_t *members,
+                       double *out13, int64_t *count) {
+    if (int rc = check_handle(s)) return rc;
+    if (int rc = fof_check(s, link, min_members, capacity, "nbmi_fof_catalogue")) return rc;
+    if (int rc = require_out(count, "nbmi_fof_catalogue: null count")) return rc;
+    if (capacity > 0 && (!label || !members || !out13)) {
+        nbmi::set_error("nbmi_fof_catalogue: null output with capacity > 0");
+        return NBMI_ERR_ARG;
+    }
+    *count = 0;
+    const int64_t n = s->n;
+    if (n == 0) return 0;
+    if (int rc = fof_query(s, link * link, false, nullptr)) return rc;
+    if (int rc = fof_catalogue_buffers(s)) return rc;
+    hipStream_t st = s->stream;
+    // the ranks by root, stable; the heads of the segments; the rows of the qualifying groups in segment order
+    int bits = 1;
+    while (bits < 32 && ((int64_t)1 << bits) < n) bits++;
+    k_fof_iota<<<nblocks(n), kBlock, 0, st>>>(n, s->fof_rank);
+    NBMI_HIP_CHECK(nbmi::radix_sort_pairs_u32(s->fof_sort_tmp, s->fof_sort_bytes, (const uint32_t *)s->fof_root, s->fof_key_s,
+                                              s->fof_rank, s->fof_rank_s, (size_t)n, 0, bits, st));
+    k_fof_heads<<<nblocks(n), kBlock, 0, st>>>(n, s->fof_key_s, s->fof_hpos, s->fof_slot);
+    scan::enqueue_compact(FofQualifies{s->fof_key_s, s->fof_cnt, min_members}, n, s->fof_tiles,
+                          FofEmitHead{s->fof_key_s, s->fof_qhead, s->fof_slot}, st);
+    NBMI_HIP_CHECK(hipGetLastError());
+    uint32_t rows = 0;
+    unsigned sort_err = 0u;
+    NBMI_HIP_CHECK(hipMemcpyAsync(&rows, s->fof_tiles + scan::tiles_for(n), sizeof(rows), hipMemcpyDeviceToHost, st));
+    NBMI_HIP_CHECK(nbmi::radix_error_word(s->fof_sort_tmp, &sort_err, st));
+    NBMI_HIP_CHECK(hipStreamSynchronize(st));
+    if (sort_err) {
+        NBMI_HIP_CHECK(nbmi::radix_init_temp(s->fof_sort_tmp, st));
+        nbmi::set_error("nbmi_fof_catalogue: device radix sort: a look-back spin timed out");
+        return NBMI_ERR_HIP;
+    }
+    *count = (int64_t)rows;
+    if (rows == 0) return 0;
+    if (int rc = fof_row_buffers(s, (int64_t)rows)) return rc;
+    k_fof_chunks<<<(int)((n + kFofChunk - 1) / kFofChunk), kFofChunk, 0, st>>>(n, s->fof_key_s, s->fof_rank_s, s->perm,
+                                                                               s->buf[s->curbuf], s->fof_hpos, s->fof_cnt,
+                                                                               s->fof_slot, s->fof_row_vals, s->fof_last,
+                                                                               s->fof_first);
+    k_fof_rows<<<(int)rows, kFofBlock, 0, st>>>(n, (int64_t)rows, s->fof_qhead, s->fof_key_s, s->fof_cnt, s->fof_minid,
+                                                s->fof_row_vals, s->fof_last, s->fof_first, s->fof_out13, s->fof_label,
+                                                s->fof_members);
+    NBMI_HIP_CHECK(hipGetLastError());
+    std::vector<double> h13((size_t)rows * 13);
+    std::vector<int32_t> hlabel(rows);
+    std::vector<int64_t> hmembers(rows);
+    NBMI_HIP_CHECK(hipMemcpyAsync(h13.data(), s->fof_out13, h13.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    NBMI_HIP_CHECK(hipMemcpyAsync(hlabel.data(), s->fof_label, hlabel.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    NBMI_HIP_CHECK(hipMemcpyAsync(hmembers.data(), s->fof_members, hmembers.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    NBMI_HIP_CHECK(hipStreamSynchronize(st));
+    // the catalogue's order: members descending, ties by label ascending (labels are distinct)
+    std::vector<uint32_t> order(rows);
+    for (uint32_t i = 0; i < rows; i++) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+        return hmembers[a] != hmembers[b] ? hmembers[a] > hmembers[b] : hlabel[a] < hlabel[b];
+    });
+    const int64_t out_rows = (int64_t)rows < capacity ? (int64_t)rows : capacity;
+    for (int64_t i = 0; i < out_rows; i++) {
+        const uint32_t r = order[i];
+        label[i] = hlabel[r];
+        members[i] = hmembers[r];
+        for (int c = 0; c < 13; c++) out13[i * 13 + c] = h13[(size_t)r * 13 + c];
+    }
+    return 0;
+}
+
+int nbmi_compute_group_colors(nbmi_sim *s, double link, int64_t min_members) {
+    if (int rc = check_handle(s)) return rc;
+    if (int rc = fof_check(s, link, min_members, 0, "nbmi_compute_group_colors")) return rc;
+    const int64_t n = s->n;
+    if (n == 0) return 0;
+    if (int rc = fof_enqueue(s, link * link, false, nullptr)) return rc;
+    k_fof_colors<<<nblocks(n), kBlock, 0, s->stream>>>(s->info, n, s->fof_root, s->fof_minid, s->fof_cnt, s->perm,
+                                                       s->buf[s->curbuf].id, min_members, s->colors);
+    NBMI_HIP_CHECK(hipGetLastError());
     return 0;
 }
 

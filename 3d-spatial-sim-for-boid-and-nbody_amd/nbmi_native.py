@@ -54,6 +54,9 @@ PROTOTYPES = {
     "nbmi_get_densities_f64": (C.c_int, [_vp, C.c_int, _vp]),
     "nbmi_set_color_mode": (C.c_int, [_vp, C.c_int, C.c_int, _dbl, _dbl]),
     "nbmi_get_color_mode": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "nbmi_fof": (C.c_int, [_vp, _dbl, _vp, _vp, _vp]),
+    "nbmi_fof_catalogue": (C.c_int, [_vp, _dbl, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "nbmi_compute_group_colors": (C.c_int, [_vp, _dbl, _i64]),
     "nbmi_set_shard": (C.c_int, [_vp, _i64, _i64]),
     "nbmi_export_shard": (C.c_int, [_vp, _vp]),
     "nbmi_import_ranks": (C.c_int, [_vp, _vp, _i64, _i64]),

@@ -353,6 +353,52 @@ class _HIPSimulation:
         mode, k, rng = self._color_mode()
         return {"mode": mode, "k": k, "log10_range": [rng[0], rng[1]]}
 
+    # ---- friends-of-friends groups (include/nbmi.h nbmi_fof) ----
+    n_groups = None  # of the last find_groups(), singletons included
+
+    def find_groups(self, link: float, evals=False):
+        """labels (N,) int32 in the caller's body order: the smallest body index of the connected component that body i
+        belongs to when two bodies are linked iff d2 <= link * link - exact, equal to a brute force.  The number of
+        groups (singletons included) is left in ``n_groups``; ``evals=True`` also returns the number of distances the
+        call evaluated.  Refused with ValueError where knn() is and for a link that is not finite and > 0; the call
+        does not change what the next step computes."""
+        what = f"find_groups({link})"
+        self._knn_refuse(what)
+        labels = np.empty(self.n, dtype=np.int32)
+        ng, ev = C.c_int64(0), C.c_int64(0)
+        self._knn_call(what, self._lib.nbmi_fof(self._h, float(link), _nat.ptr(labels), C.addressof(ng),
+                                                C.addressof(ev) if evals else None))
+        self.n_groups = int(ng.value)
+        return (labels, int(ev.value)) if evals else labels
+
+    def group_catalogue(self, link: float, min_members: int = 20, capacity=None):
+        """The groups of find_groups(link) with at least ``min_members`` bodies, largest first (ties by label): a dict of
+        ``count`` (the number of such groups, which may exceed the rows returned), ``label`` int32, ``members`` int64,
+        ``mass``, ``center`` (rows, 3), ``velocity`` (rows, 3), ``lo`` / ``hi`` (rows, 3: the bounding box).
+        ``capacity`` limits the rows returned (default: all).  The same state gives the same bits."""
+        what = f"group_catalogue({link}, min_members={min_members})"
+        self._knn_refuse(what)
+        cap = self.n // max(1, int(min_members)) if capacity is None else int(capacity)
+        rows = max(cap, 0)
+        label = np.empty(rows, dtype=np.int32)
+        members = np.empty(rows, dtype=np.int64)
+        out = np.empty((rows, 13), dtype=np.float64)
+        cnt = C.c_int64(0)
+        self._knn_call(what, self._lib.nbmi_fof_catalogue(self._h, float(link), int(min_members), cap, _nat.ptr(label),
+                                                          _nat.ptr(members), _nat.ptr(out), C.addressof(cnt)))
+        k = min(int(cnt.value), rows)
+        return {"count": int(cnt.value), "label": label[:k], "members": members[:k], "mass": out[:k, 0].copy(),
+                "center": out[:k, 1:4].copy(), "velocity": out[:k, 4:7].copy(), "lo": out[:k, 7:10].copy(),
+                "hi": out[:k, 10:13].copy()}
+
+    def color_by_groups(self, link: float, min_members: int = 20):
+        """One shot: the colours compute_colors leaves (get_colors, visible_points, render) become group colours - every
+        group of at least ``min_members`` bodies in a colour of its own (the speed ramp at a hash of its label), every
+        other body grey.  The colour mode is not touched: the next compute_colors colours as before."""
+        what = f"color_by_groups({link}, min_members={min_members})"
+        self._knn_refuse(what)
+        self._knn_call(what, self._lib.nbmi_compute_group_colors(self._h, float(link), int(min_members)))
+
     def visible_points(self, cam_pos, cam_forward, cam_right, cam_up, tan_h, tan_v, far_dist):
         """Frustum culling + compaction on the device (reference compute_visibility_points,
         nbody/simulation.py:403-434, and the gather of draw(), :927-928): returns

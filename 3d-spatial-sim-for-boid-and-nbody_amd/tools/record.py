@@ -382,6 +382,75 @@ def apply_color_mode(gpu_sim, config: dict, rec_dir: Path = None):
     return config
 
 
+# ---- friends-of-friends groups (extra config key "groups") ---------------------------------
+GROUPS_FILE = "groups.jsonl"
+GROUPS_MIN_MEMBERS = 20
+GROUPS_ROWS = 64  # catalogue rows kept per line
+
+
+def default_linking_length(r2_1):
+    """The linking length "auto" stands for: twice the median nearest-neighbour distance of a state (its knn(1)
+    squared distances).  The factor 2 is a convention, not a measured optimum."""
+    d = np.sqrt(np.asarray(r2_1, dtype=np.float64))
+    b = 2.0 * float(np.median(d)) if len(d) else 0.0
+    if not (np.isfinite(b) and b > 0.0):
+        raise ValueError("--linking-length auto: the state's median nearest-neighbour distance is not finite and > 0 "
+                         "(give --linking-length B)")
+    return b
+
+
+def groups_config(config: dict):
+    """The "groups" key of a config as (every, link or None for an "auto" not yet taken, min_members); None without the
+    key; ValueError for a malformed one."""
+    g = config.get("groups")
+    if not g:
+        return None
+    every, mm, link = int(g.get("every", 0)), int(g.get("min_members", GROUPS_MIN_MEMBERS)), g.get("link", "auto")
+    if every <= 0:
+        raise ValueError(f"--groups: K must be positive, not {every}")
+    if mm < 1:
+        raise ValueError(f"--min-members: M must be at least 1, not {mm}")
+    if link == "auto" or link is None:
+        return every, None, mm
+    link = float(link)
+    if not (np.isfinite(link) and link > 0.0):
+        raise ValueError(f"--linking-length: B must be finite and > 0 (or auto), not {link}")
+    return every, link, mm
+
+
+def apply_groups(gpu_sim, config: dict, rec_dir: Path = None):
+    """Resolve the config's linking length.  "auto" is taken once, here, from the handle's current state (the initial one
+    for a new recording) and written into metadata.json, from where --resume and --extend re-apply it.  Returns the
+    config (with the length filled in)."""
+    g = groups_config(config)
+    if g is None or g[1] is not None:
+        return config
+    every, _, mm = g
+    link = default_linking_length(gpu_sim.knn(1)[0])
+    config = dict(config, groups={"every": every, "link": link, "min_members": mm})
+    if rec_dir is not None:
+        meta_path = Path(rec_dir) / "metadata.json"
+        meta = load_metadata(rec_dir) if meta_path.exists() else dict(config)
+        meta["groups"] = config["groups"]
+        _atomically(meta_path, lambda f: f.write(json.dumps(meta, indent=2).encode()))
+    return config
+
+
+def groups_line(sim, frame: int, link: float, min_members: int) -> str:
+    """One JSON line (with its newline) for the groups of the state `sim` holds after `frame`: their number, the number
+    of those with at least min_members bodies and the first GROUPS_ROWS rows of the catalogue, largest first.  Two
+    queries per line: the catalogue call runs the build and the pair search again (its C call has no output for the
+    number of all groups)."""
+    sim.find_groups(link)
+    cat = sim.group_catalogue(link, min_members=min_members, capacity=GROUPS_ROWS)
+    rows = [{"label": int(cat["label"][i]), "members": int(cat["members"][i]), "mass": float(cat["mass"][i]),
+             "center": [float(x) for x in cat["center"][i]], "velocity": [float(x) for x in cat["velocity"][i]],
+             "lo": [float(x) for x in cat["lo"][i]], "hi": [float(x) for x in cat["hi"][i]]}
+            for i in range(len(cat["label"]))]
+    return json.dumps({"frame": frame, "link": link, "min_members": min_members, "n_groups": int(sim.n_groups),
+                       "count": int(cat["count"]), "groups": rows}) + "\n"
+
+
 def _generate_initial_conditions(config: dict):
     from tools.presets import generate_distribution
     p, v, m = generate_distribution(config.get("distribution", "galaxy"), config["num_bodies"],
@@ -390,13 +459,14 @@ def _generate_initial_conditions(config: dict):
 
 
 def record_pipelined(gpu_sim, rec_dir: Path, start_frame: int, total_frames: int, substeps: int, dt: float,
-                     direct_zstd: bool, every: int, write_diag, write_state):
+                     direct_zstd: bool, every: int, write_diag, write_state, also_every: int = 0):
     """The recording loop of ``record(config with "pipeline": True)``: the files of the sequential loop, but
     the host compresses and writes frame k - 1 while the device computes frame k.  Per frame: step_many (enqueue),
     frame_begin (enqueue: one snapshot kernel, then the copy on a stream of its own), then the PREVIOUS frame is finished:
     frame_wait, its file through the sequential loop's writers, frame_release.  Where a diagnostics line (`every`) or a
     state checkpoint is due the frame itself is finished first - write_diag(frame) / write_state(frame, compressed=False)
     are the caller's synchronous writers, and the checkpoint stays the state of exactly the last frame on disk.
+    `also_every`: a second period at which write_diag is due (the groups lines, which the caller's writer adds).
 
     `gpu_sim` needs step_many, frame_begin, frame_wait, frame_release, frames_pending and step_count (the backend object,
     or a stand-in: nothing here touches a device).  On Ctrl-C the library is asked which frames are in flight and where
@@ -431,7 +501,7 @@ def record_pipelined(gpu_sim, rec_dir: Path, start_frame: int, total_frames: int
                 finish(*held)
             held = (slot, frame, kind)
             state_due = (frame + 1) % STATE_EVERY == 0
-            if state_due or (every > 0 and (frame + 1) % every == 0):
+            if state_due or (every > 0 and (frame + 1) % every == 0) or (also_every > 0 and (frame + 1) % also_every == 0):
                 finish(*held)
                 held = None
                 write_diag(frame)  # before the state checkpoint: a resume from it finds every line up to its frame
@@ -531,8 +601,12 @@ def record(config: dict, resume: bool = False, root: Path = None, quiet: bool = 
     say(f"[Record] GPU acceleration: {backend.value} - {info}")
     # extra config key "color": {"mode": "density", "k": K, "log10_range": [lo, hi]} = frames coloured by the k-NN
     # density through the unchanged colour and frame calls of both loops
+    # extra config key "groups": {"every": K, "link": b, "min_members": M} = every K-th frame a line of friends-of-friends
+    # groups in groups.jsonl
     try:
         config = apply_color_mode(gpu_sim, config, rec_dir)
+        config = apply_groups(gpu_sim, config, rec_dir)
+        groups = groups_config(config)
     except Exception:
         gpu_sim.close()
         raise
@@ -555,11 +629,22 @@ def record(config: dict, resume: bool = False, root: Path = None, quiet: bool = 
         else:
             truncate_diagnostics(diag_path, start_frame - 1)
 
-    def write_diag(frame):
-        nonlocal last_diag
+    groups_path = rec_dir / GROUPS_FILE
+    last_groups = start_frame - 1
+    if groups:
+        if start_frame == 0:  # a run from frame 0 starts the file afresh
+            _atomically(groups_path, lambda f: f.write(b""))
+        else:
+            truncate_diagnostics(groups_path, start_frame - 1)
+
+    def write_diag(frame):  # the synchronous per-frame lines of both loops: diagnostics, then groups
+        nonlocal last_diag, last_groups
         if every > 0 and (frame + 1) % every == 0 and frame > last_diag:
             append_line(diag_path, diagnostics_line(gpu_sim, frame, substeps, dt, diag_extra))
             last_diag = frame
+        if groups and (frame + 1) % groups[0] == 0 and frame > last_groups:
+            append_line(groups_path, groups_line(gpu_sim, frame, groups[1], groups[2]))
+            last_groups = frame
 
     def write_frame(frame):
         gpu_sim.compute_colors(15.0)
@@ -588,7 +673,7 @@ def record(config: dict, resume: bool = False, root: Path = None, quiet: bool = 
     if config.get("pipeline"):  # extra config key (metadata.json, only when set): the overlapped loop
         try:
             record_pipelined(gpu_sim, rec_dir, start_frame, total_frames, substeps, dt, direct_zstd, every, write_diag,
-                             write_state)
+                             write_state, also_every=groups[0] if groups else 0)
         except KeyboardInterrupt:
             at = start_frame - 1 + gpu_sim.step_count() // max(substeps, 1)
             say(f"\n[Record] Paused at frame {at}; resume with record(config, resume=True)")
@@ -691,6 +776,18 @@ def show_status(session_name: str, root: Path = None) -> bool:
         print(f"    |E - E0| / |E0|:        {de:.3e}")
         print(f"    |P - P0| / sum m|v|_0:  {dp:.3e}")
         print(f"    |L - L0| / |L0|:        {dl:.3e}")
+    g = meta.get("groups")
+    if g:
+        link = g.get("link", "auto")
+        print(f"  Groups: every {g.get('every')} frames, linking length "
+              + (f"{link:.6g}" if isinstance(link, (int, float)) else "auto (not taken yet)")
+              + f", min members {g.get('min_members', GROUPS_MIN_MEMBERS)}")
+        grows = read_diagnostics(rec_dir / GROUPS_FILE)
+        if grows:
+            last = grows[-1]
+            largest = last["groups"][0]["members"] if last["groups"] else 0
+            print(f"    frame {last['frame']}: {last['count']} groups of at least {last['min_members']} "
+                  f"(of {last['n_groups']}), largest {largest} bodies")
     if completed < total:
         print(f"\n  To resume: python -m tools.record --resume {session_name}")
     else:
@@ -728,8 +825,8 @@ def build_parser():
         epilog="Differences from the reference's recorder: there is no interactive menu (give --preset or "
                "--preset-id); --preset-id indexes this build's preset list (python -m tools.record --presets shows "
                "it); --dt sets dt_per_frame (the reference writes an unused 'dt' key); --presets, --seed, "
-               "--device-ic, --diagnostics, --integrator, --multipole, --pipeline, --color, --density-k, --density-range and "
-               "--root are additions.")
+               "--device-ic, --diagnostics, --integrator, --multipole, --pipeline, --color, --density-k, --density-range, "
+               "--groups, --linking-length, --min-members and --root are additions.")
     ap.add_argument("session", nargs="?", help="session name (for --resume, --status or --extend)")
     ap.add_argument("--resume", action="store_true", help="resume an interrupted recording (default: the most recent)")
     ap.add_argument("--extend", type=int, metavar="FRAMES", help="extend an existing recording by N frames")
@@ -766,6 +863,14 @@ def build_parser():
     ap.add_argument("--density-range", type=float, nargs=2, default=None, metavar=("LO", "HI"),
                     help="log10(rho) at the ends of the ramp (default: taken once from the initial state: its 1st "
                          "percentile .. its 99.9th percentile + 1)")
+    ap.add_argument("--groups", type=int, default=None, metavar="K",
+                    help="every K frames append the friends-of-friends groups (their number and the 64 largest with "
+                         "members, mass, centre, velocity and box) to groups.jsonl (stored in metadata.json as groups)")
+    ap.add_argument("--linking-length", type=str, default=None, metavar="B|auto",
+                    help="two bodies no further apart than B belong to one group (default auto: taken once from the "
+                         "initial state, twice its median nearest-neighbour distance)")
+    ap.add_argument("--min-members", type=int, default=None, metavar="M",
+                    help=f"smallest group listed (default {GROUPS_MIN_MEMBERS})")
     ap.add_argument("--root", type=Path, default=None, help="directory holding recordings/ (default: the package's)")
     return ap
 
@@ -827,6 +932,18 @@ def build_config(args) -> dict:
         if dr is not None:
             config["color"]["log10_range"] = [float(dr[0]), float(dr[1])]
         color_config(config)  # (a bad range raises here)
+    gk, gl, gm = (getattr(args, a, None) for a in ("groups", "linking_length", "min_members"))
+    if gk is None and (gl is not None or gm is not None):
+        raise ValueError("--linking-length and --min-members need --groups K")
+    if gk is not None:  # the default writes no key
+        link = "auto"
+        if gl is not None and gl.strip().lower() != "auto":
+            try:
+                link = float(gl)
+            except ValueError:
+                raise ValueError(f"--linking-length: B must be a number or auto, not {gl!r}") from None
+        config["groups"] = {"every": int(gk), "link": link, "min_members": GROUPS_MIN_MEMBERS if gm is None else int(gm)}
+        groups_config(config)  # (a bad K, B or M raises here)
     return config
 
 

@@ -279,6 +279,47 @@ int nbmi_get_densities_f64(nbmi_sim *sim, int k, double *rho);
 int nbmi_set_color_mode(nbmi_sim *sim, int mode, int k, double log10_lo, double log10_hi);
 int nbmi_get_color_mode(nbmi_sim *sim, int *mode, int *k, double *log10_lo, double *log10_hi); /* outputs may be NULL */
 
+/* ---- friends-of-friends groups --------------------------------------------------------------
+ * Of the handle's current float64 state, exactly:
+ *   d2(i, j)  as above: (dx dx + dy dy) + dz dz with dx = x_j - x_i, float64 in this association, no FMA.
+ *   b2        = link * link, one float64 product computed on the host.
+ *   linked    bodies i != j are linked iff d2(i, j) <= b2.  Equality links; a coincident pair (d2 = 0) is linked for
+ *             every valid link.
+ *   group     a connected component of the link graph; a body without a friend is a group of one.
+ *   labels[i] (int32, caller's body order) = the smallest caller index in i's group.  Partition and labels are unique
+ *             and independent of any order of evaluation: they equal a brute force's exactly.
+ *   n_groups  = the number of distinct labels, singletons included.
+ * nbmi_fof: labels, n_groups and evals may each be NULL.  *evals = the number of d2 the call evaluated (a measurement
+ * hook like nbmi_knn's).
+ * nbmi_fof_catalogue: the groups with members >= min_members (min_members >= 1), ordered by members descending, ties
+ * by label ascending.  Per group label, members and 13 doubles {M, c[3], v[3], lo[3], hi[3]}:
+ *   M = sum m_j;  c = sum m_j x_j / M;  v = sum m_j v_j / M;  a group with M == 0 has the unweighted means of its
+ *   members' positions and velocities instead;  lo / hi = the per-axis min / max of the members' positions (exact).
+ * The sums are float64 in a fixed order (no floating-point atomics): two calls on an unchanged state return the same
+ * bits.  *count = the number of qualifying groups, which may exceed capacity; at most capacity rows are copied out (the
+ * first ones of the order), as nbmi_visible_points does.  label, members and out13 may be NULL when capacity == 0.
+ * nbmi_compute_group_colors: one shot, does NOT touch the colour mode; leaves colours where nbmi_compute_colors leaves
+ * them (nbmi_get_colors_f32, nbmi_visible_points and nbmi_render_sim see them): a body of a group with members >=
+ * min_members gets the speed ramp at t = ((uint32)(label * 2654435761u) >> 8) / 2^24, every other body (0.25, 0.25,
+ * 0.25).  It only enqueues; NBMI_ERR_CAPACITY of its build is reported deferred, as a step's is.
+ * Refused with NBMI_ERR_ARG, message "<call>: ...": link not finite or <= 0, min_members < 1, capacity < 0, and the
+ * handles nbmi_knn refuses (direct N^2, owner mode, a proper shard, the measurement-only walks).  N == 0: success,
+ * n_groups = 0, count = 0.  N == 1: one singleton.
+ * A call changes nothing that a later step reads (as nbmi_knn).  NBMI_ERR_CAPACITY of the call's own tree build is
+ * reported with a step's message.  Quadrupole and leapfrog handles return a plain handle's bits.
+ * The first nbmi_fof allocates 16 bytes per body, 4 bytes per 64 bodies and (shared with nbmi_knn) 32 bytes per node
+ * row; the first catalogue 24 bytes per body more, a radix sort buffer (about 8 bytes per body), 304 bytes per 256
+ * bodies and 268 bytes per catalogue row (for the next power of two of rows, at least 1 024; a call that needs more frees
+ * the arrays and allocates larger ones).
+ * Environment NBMI_FOF_HALF (read when the handle is created, like the other measurement knobs): 0 starts every wave's
+ * pair search at the root of the tree instead of at the wave's own first leaf.  Results are the same; evals and the
+ * time are not (DESIGN.md section 4.15 has the A/B). */
+int nbmi_fof(nbmi_sim *sim, double link, int32_t *labels /* (N,), may be NULL */, int64_t *n_groups /* may be NULL */,
+             int64_t *evals /* may be NULL */);
+int nbmi_fof_catalogue(nbmi_sim *sim, double link, int64_t min_members, int64_t capacity, int32_t *label,
+                       int64_t *members, double *out13, int64_t *count);
+int nbmi_compute_group_colors(nbmi_sim *sim, double link, int64_t min_members);
+
 /* Multi-GPU (one process per GPU).  A handle created with nbmi_create holds ALL bodies; with a
  * shard set, step() integrates only the key-sorted ranks [begin,end) (direct method: the body
  * indices [begin,end), its state is never re-ordered) and leaves the others untouched until

@@ -1,0 +1,245 @@
+"""Friends-of-friends groups, host side: the NumPy restatement against the definition as a double loop, equality and
+coincident bodies by hand, the catalogue and the colours, the C ABI's declarations, the Python classes' refusals and the
+recorder's options, metadata and groups.jsonl with stand-in backends (no device)."""
+import ctypes
+import json
+import os
+import re
+
+import numpy as np
+import pytest
+
+import fof_ref as fr
+import knn_ref as kr
+from conftest import ROOT
+
+FOF_CALLS = ("nbmi_fof", "nbmi_fof_catalogue", "nbmi_compute_group_colors")
+
+
+def test_restatement_against_the_double_loop():
+    rng = np.random.RandomState(0)
+    for n, span, links in ((300, 5.0, (0.5, 1.0, 2.0)), (257, 1e-3, (5e-5, 2e-4)), (64, 1e6, (1e5, 4e5))):
+        p = rng.uniform(-span, span, (n, 3))
+        for b in links:
+            got, want = fr.fof(p, b), fr.fof_naive(p, b)
+            assert np.array_equal(got[0], want[0]) and got[1] == want[1], (n, span, b)
+            assert got[0].dtype == np.int32 and (got[0] <= np.arange(n)).all()
+    # lattice points: most candidate pairs sit exactly at the linking length
+    g = np.arange(6, dtype=np.float64)
+    p = np.stack(np.meshgrid(g, g, g, indexing="ij"), -1).reshape(-1, 3)[rng.permutation(216)]
+    for b in (np.nextafter(1.0, 0.0), 1.0, np.sqrt(2.0), 1.5):
+        got, want = fr.fof(p, b), fr.fof_naive(p, b)
+        assert np.array_equal(got[0], want[0]) and got[1] == want[1], b
+    assert fr.fof(p, 1.0)[1] == 1 and fr.fof(p, np.nextafter(1.0, 0.0))[1] == 216
+    try:
+        from scipy.sparse import coo_matrix
+        from scipy.sparse.csgraph import connected_components
+    except ImportError:
+        return
+    p = rng.uniform(-5.0, 5.0, (300, 3))
+    pairs = [np.concatenate(x) for x in zip(*fr.linked_chunks(p, 1.0))]
+    ncomp, comp = connected_components(coo_matrix((np.ones(len(pairs[0])), (pairs[0], pairs[1])), shape=(300, 300)), directed=False)
+    lab, ng = fr.fof(p, 1.0)
+    assert ncomp == ng and len(set(zip(comp.tolist(), lab.tolist()))) == ng  # the same partition
+
+
+def test_equality_coincident_bodies_and_chains_by_hand():
+    # 0 - 1 at distance 5 exactly (3-4-5); 2 coincides with 1; 3 hangs on 2 by a link of 1; 4 is alone; 5 and 6 coincide far away
+    p = np.array([[0, 0, 0], [3, 4, 0], [3, 4, 0], [3, 4, 1], [100, 0, 0], [-50, 0, 0], [-50, 0, 0]], np.float64)
+    lab, ng = fr.fof(p, 5.0)
+    assert lab.tolist() == [0, 0, 0, 0, 4, 5, 5] and ng == 3              # equality links
+    lab, ng = fr.fof(p, np.nextafter(5.0, 0.0))
+    assert lab.tolist() == [0, 1, 1, 1, 4, 5, 5] and ng == 4              # ... and only equality did
+    lab, ng = fr.fof(p, 1e-300)                                           # (b2 underflows to 0: d2 = 0 <= 0 still links)
+    assert lab.tolist() == [0, 1, 1, 3, 4, 5, 5] and ng == 5              # a coincident pair is linked for every valid b
+    order = np.array([6, 3, 0, 5, 2, 4, 1])                               # the caller's order decides the labels, not the partition
+    lab2, ng2 = fr.fof(p[order], 5.0)
+    assert ng2 == 3 and lab2.tolist() == [0, 1, 1, 0, 1, 5, 1]
+    assert fr.group_sizes(lab2).tolist() == [4, 2, 1]
+    assert fr.fof(np.zeros((1, 3)), 1.0)[0].tolist() == [0] and fr.fof(np.zeros((0, 3)), 1.0)[1] == 0
+
+
+def test_catalogue_restatement_by_hand():
+    p = np.array([[0, 0, 0], [2, 0, 0], [10, 10, 10], [0, 2, 0], [10, 10, 11], [50, 0, 0]], np.float64)
+    v = np.array([[1, 0, 0], [0, 1, 0], [0, 0, 1], [1, 1, 1], [0, 0, 3], [9, 9, 9]], np.float64)
+    m = np.array([1.0, 3.0, 0.0, 4.0, 0.0, 2.0])
+    lab = fr.fof(p, 2.0)[0]
+    assert lab.tolist() == [0, 0, 2, 0, 2, 5]
+    cat = fr.catalogue(p, v, m, lab, 1)
+    assert cat["count"] == 3 and cat["label"].tolist() == [0, 2, 5] and cat["members"].tolist() == [3, 2, 1]
+    assert cat["mass"].tolist() == [8.0, 0.0, 2.0]
+    assert cat["center"].tolist() == [[0.75, 1.0, 0.0], [10.0, 10.0, 10.5], [50.0, 0.0, 0.0]]   # M == 0: the unweighted mean
+    assert cat["velocity"].tolist() == [[0.625, 0.875, 0.5], [0.0, 0.0, 2.0], [9.0, 9.0, 9.0]]
+    assert cat["lo"].tolist() == [[0, 0, 0], [10, 10, 10], [50, 0, 0]] and cat["hi"].tolist() == [[2, 2, 0], [10, 10, 11], [50, 0, 0]]
+    assert fr.catalogue(p, v, m, lab, 2)["label"].tolist() == [0, 2] and fr.catalogue(p, v, m, lab, 4)["count"] == 0
+    # ties in the member count go by label
+    lab = np.array([3, 1, 1, 3, 4, 4, 6], np.int32)
+    assert fr.catalogue(np.zeros((7, 3)), np.zeros((7, 3)), np.ones(7), lab, 1)["label"].tolist() == [1, 3, 4, 6]
+
+
+def test_group_colours_restate_the_library_source():
+    src = open(os.path.join(ROOT, "3d-spatial-sim-for-boid-and-nbody_amd", "csrc", "nbmi.hip")).read()
+    body = src[src.index("void k_fof_colors("):]
+    body = body[:body.index("\n}\n")]
+    for piece in ("cr = 0.25f, cg = 0.25f, cb = 0.25f", "* 2654435761u) >> 8) / 16777216.0", "color_ramp_t(", ">= min_members"):
+        assert piece in body, piece
+    assert fr.GREY == 0.25 and 16777216.0 == 2.0 ** 24
+    assert fr.group_t(0) == 0.0 and fr.group_t(1) == (2654435761 >> 8) / 2.0 ** 24
+    assert fr.group_t(19_999) == (((19_999 * 2654435761) & 0xFFFFFFFF) >> 8) / 2.0 ** 24
+    t = fr.group_t(np.arange(100_000))
+    assert (t >= 0.0).all() and (t < 1.0).all() and len(np.unique(t)) > 99_000   # neighbouring labels get far-apart colours
+    lab = np.array([0, 0, 0, 3, 4, 4], np.int32)
+    col = fr.group_colors(lab, 2)
+    assert np.array_equal(col[0], kr.ramp(fr.group_t(0))) and np.array_equal(col[3], [0.25, 0.25, 0.25])
+    assert np.array_equal(col[4], kr.ramp(fr.group_t(4))) and np.array_equal(fr.group_colors(lab, 4), np.full((6, 3), 0.25))
+
+
+def test_header_declares_and_library_exports_the_fof_calls():
+    import nbmi_native
+    text = open(os.path.join(ROOT, "include", "nbmi.h")).read()
+    for name in FOF_CALLS:
+        assert re.search(r"^int %s\(nbmi_sim \*sim, double link" % name, text, re.M), f"include/nbmi.h does not declare {name}"
+        assert name in nbmi_native.PROTOTYPES
+    assert [len(nbmi_native.PROTOTYPES[n][1]) for n in FOF_CALLS] == [5, 8, 3]
+    lib = ctypes.CDLL(nbmi_native.LIB_PATH)
+    for name in FOF_CALLS:
+        assert hasattr(lib, name), f"libnbmi.so lacks {name}"
+
+
+def test_python_classes_refuse_without_a_device():
+    from nbody.gpu_backend import COLOR_MODES, HIPDirectSimulation, HIPOwnerSimulation
+    assert COLOR_MODES == {"speed": 0, "density": 1}  # group colours are a call, not a mode
+    for cls, word in ((HIPDirectSimulation, "direct"), (HIPOwnerSimulation, "owner")):
+        sim = cls.__new__(cls)  # no handle: the refusal must come before any library call
+        sim._h = None
+        for call in (lambda: sim.find_groups(2.0), lambda: sim.find_groups(2.0, evals=True), lambda: sim.group_catalogue(2.0),
+                     lambda: sim.color_by_groups(2.0, min_members=5)):
+            with pytest.raises(ValueError, match=word):
+                call()
+
+
+# ---- the recorder ----------------------------------------------------------------------------------------------------
+def _args(*extra):
+    from tools import record as rec
+    return rec.build_parser().parse_args(["--preset", "quick_galaxy", *extra])
+
+
+def test_recorder_options():
+    from tools import record as rec
+    assert "groups" not in rec.build_config(_args())  # the default writes no key
+    assert rec.groups_config({}) is None
+    cfg = rec.build_config(_args("--groups", "5"))
+    assert cfg["groups"] == {"every": 5, "link": "auto", "min_members": 20} and rec.groups_config(cfg) == (5, None, 20)
+    assert rec.build_config(_args("--groups", "5", "--linking-length", "AUTO"))["groups"]["link"] == "auto"
+    cfg = rec.build_config(_args("--groups", "2", "--linking-length", "7.5", "--min-members", "3"))
+    assert cfg["groups"] == {"every": 2, "link": 7.5, "min_members": 3} and rec.groups_config(cfg) == (2, 7.5, 3)
+    for bad, word in ((("--linking-length", "3"), "need --groups"), (("--min-members", "3"), "need --groups"),
+                      (("--linking-length", "auto"), "need --groups"), (("--groups", "0"), "--groups"),
+                      (("--groups", "-2"), "--groups"), (("--groups", "2", "--linking-length", "0"), "--linking-length"),
+                      (("--groups", "2", "--linking-length", "-1"), "--linking-length"),
+                      (("--groups", "2", "--linking-length", "inf"), "--linking-length"),
+                      (("--groups", "2", "--linking-length", "nan"), "--linking-length"),
+                      (("--groups", "2", "--linking-length", "wide"), "--linking-length"),
+                      (("--groups", "2", "--min-members", "0"), "--min-members")):
+        with pytest.raises(ValueError, match=word):
+            rec.build_config(_args(*bad))
+
+
+class FakeSim:
+    """knn / find_groups / group_catalogue of the backend object: nearest-neighbour distances 1 .. n, two listed groups"""
+
+    def __init__(self, n=1001):
+        self.n = n
+        self.r2 = np.arange(1, n + 1, dtype=np.float64) ** 2
+        self.calls = []
+        self.n_groups = None
+
+    def knn(self, k, evals=False):
+        self.calls.append(("knn", k))
+        return self.r2.copy(), np.ones(self.n)
+
+    def find_groups(self, link, evals=False):
+        self.calls.append(("find_groups", link))
+        self.n_groups = 7
+        return np.zeros(self.n, np.int32)
+
+    def group_catalogue(self, link, min_members=20, capacity=None):
+        self.calls.append(("group_catalogue", link, min_members, capacity))
+        three = np.arange(6, dtype=np.float64).reshape(2, 3)
+        return {"count": 2, "label": np.array([4, 0], np.int32), "members": np.array([900, 30], np.int64),
+                "mass": np.array([0.1, 30.0]), "center": three, "velocity": -three, "lo": three - 1.0, "hi": three + 1.0}
+
+
+def test_recorder_metadata_round_trip_line_and_status(tmp_path, capsys):
+    from tools import record as rec
+    cfg = rec.build_config(_args("--groups", "4", "--min-members", "25"))
+    d = rec.get_recording_dir("grp", tmp_path)
+    rec.save_metadata(d, cfg, 0.0)
+    sim = FakeSim()
+    out = rec.apply_groups(sim, cfg, d)
+    assert out["groups"] == {"every": 4, "link": 2.0 * 501.0, "min_members": 25}  # twice the median nearest-neighbour distance
+    assert rec.default_linking_length(sim.r2) == 1002.0 and sim.calls == [("knn", 1)]
+    meta = rec.load_metadata(d)
+    assert meta["groups"] == out["groups"] and meta["start_time"] == 0.0 and meta["num_bodies"] == cfg["num_bodies"]
+    # --resume / --extend: the length comes from metadata.json, the state is not asked again
+    again = FakeSim()
+    again.r2 *= 9.0
+    assert rec.apply_groups(again, meta, d)["groups"] == meta["groups"] and again.calls == []
+    assert rec.load_metadata(d) == meta
+    # a given length is used as given; a session without groups touches nothing
+    given = FakeSim()
+    assert rec.apply_groups(given, rec.build_config(_args("--groups", "1", "--linking-length", "3")), None)["groups"]["link"] == 3.0
+    assert rec.apply_groups(given, rec.build_config(_args()), None) == rec.build_config(_args()) and given.calls == []
+    flat = FakeSim()
+    flat.r2[:] = 0.0
+    with pytest.raises(ValueError, match="median nearest-neighbour"):
+        rec.apply_groups(flat, cfg, None)
+    # the line
+    line = rec.groups_line(sim, 7, 1002.0, 25)
+    assert line.endswith("\n") and sim.calls[1:] == [("find_groups", 1002.0), ("group_catalogue", 1002.0, 25, rec.GROUPS_ROWS)]
+    row = json.loads(line)
+    assert {k: row[k] for k in ("frame", "link", "min_members", "n_groups", "count")} == \
+        {"frame": 7, "link": 1002.0, "min_members": 25, "n_groups": 7, "count": 2}
+    assert row["groups"][0] == {"label": 4, "members": 900, "mass": 0.1, "center": [0.0, 1.0, 2.0],
+                                "velocity": [-0.0, -1.0, -2.0], "lo": [-1.0, 0.0, 1.0], "hi": [1.0, 2.0, 3.0]}
+    assert len(row["groups"]) == 2 and row["groups"][1]["label"] == 0
+    # --status: the last line's count and the largest group
+    rec.append_line(d / rec.GROUPS_FILE, line)
+    capsys.readouterr()
+    assert rec.show_status("grp", root=tmp_path)
+    text = capsys.readouterr().out
+    assert "Groups: every 4 frames, linking length 1002, min members 25" in text
+    assert "frame 7: 2 groups of at least 25 (of 7), largest 900 bodies" in text
+    rec.save_metadata(rec.get_recording_dir("plain", tmp_path), rec.build_config(_args()), 0.0)
+    assert rec.show_status("plain", root=tmp_path) and "Groups" not in capsys.readouterr().out
+
+
+def test_groups_file_truncation_on_resume(tmp_path):
+    from tools import record as rec
+    path = tmp_path / rec.GROUPS_FILE
+    sim = FakeSim()
+    for frame in (1, 3, 5, 7):
+        rec.append_line(path, rec.groups_line(sim, frame, 2.0, 20))
+    with open(path, "a") as f:
+        f.write('{"frame": 9, "link": 2.0, "min_mem')  # a killed process left a torn line
+    assert [r["frame"] for r in rec.read_diagnostics(path)] == [1, 3, 5, 7]
+    before = path.read_text().splitlines(keepends=True)
+    kept = rec.truncate_diagnostics(path, 4)  # a resume after the checkpoint of frame 4
+    assert [r["frame"] for r in kept] == [1, 3] and path.read_text() == "".join(before[:2])
+    rec.append_line(path, rec.groups_line(sim, 5, 2.0, 20))
+    assert [r["frame"] for r in rec.read_diagnostics(path)] == [1, 3, 5] and path.read_text() == "".join(before[:3])
+
+
+def test_pipelined_loop_finishes_the_frame_before_a_groups_line(tmp_path):
+    """the second period of record_pipelined: the writer is called where a groups line is due, after the frame's file"""
+    from tools import record as rec
+    import test_record_pipeline_host as tp
+    d = rec.get_recording_dir("piped", tmp_path)
+    sim = tp.FakeSim(rec)
+    seen = []
+
+    def write_lines(frame):
+        assert any(q.exists() for q in rec._frame_paths(d, frame)) and not sim.frames_pending()
+        seen.append(frame)
+    rec.record_pipelined(sim, d, 0, 7, 2, 0.01, False, 0, write_lines, lambda frame, compressed=False: None, also_every=3)
+    assert seen == [2, 5] and not sim.slots and rec.get_completed_frames(d) == 7
