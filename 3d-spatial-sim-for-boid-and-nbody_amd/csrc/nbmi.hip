@@ -3898,12 +3898,13 @@ __device__ __forceinline__ KnnGroup knn_group(const Bodies &cur, const uint32_t 
 // the cells that hold that leaf lie in front of it and are never tested, so nothing of theirs is pruned).
 // Leaves of the ranks [ex_lo, ex_hi) are skipped: the caller has dealt with those bodies (the wave's own among them,
 // which is how self is excluded by identity).  leaf(d2, row, rank) sees every other leaf a lane reaches and may
-// lower `bound`.
-template <class Leaf>
-__device__ __forceinline__ void query_walk(const Node *__restrict__ nodes, const double4 *__restrict__ rows,
+// lower `bound`.  cell(idx, row, next_off) decides an internal cell for an active lane: true = the lane keeps it open,
+// false = it is done with the whole subtree (K16 / K17: pruned; K18 may also have counted it).
+template <class Cell, class Leaf>
+__device__ __forceinline__ void query_walk_cells(const Node *__restrict__ nodes, const double4 *__restrict__ rows,
                                            const int32_t *__restrict__ node_ref, unsigned start, unsigned nn, bool valid,
-                                           double qx, double qy, double qz, int64_t ex_lo, int64_t ex_hi, const double &bound,
-                                           long long &evals, Leaf leaf) {
+                                           double qx, double qy, double qz, int64_t ex_lo, int64_t ex_hi, long long &evals,
+                                           Cell cell, Leaf leaf) {
     unsigned resume = valid ? 0u : 0xffffffffu;
     unsigned off = start;
     while (off < nn) {
@@ -3923,12 +3924,21 @@ __device__ __forceinline__ void query_walk(const Node *__restrict__ nodes, const
         } else {
             bool open = false;
             if (active) {
-                open = !(knn_lower(row, qx, qy, qz) > bound);
+                open = cell(idx, row, nd.next_off);
                 if (!open) resume = nd.next_off;
             }
             off = __builtin_amdgcn_ballot_w64(open) ? off + kNodeBytes : nd.next_off;
         }
     }
+}
+// K16 / K17: a cell is open unless its lower bound exceeds `bound`
+template <class Leaf>
+__device__ __forceinline__ void query_walk(const Node *__restrict__ nodes, const double4 *__restrict__ rows,
+                                           const int32_t *__restrict__ node_ref, unsigned start, unsigned nn, bool valid,
+                                           double qx, double qy, double qz, int64_t ex_lo, int64_t ex_hi, const double &bound,
+                                           long long &evals, Leaf leaf) {
+    query_walk_cells(nodes, rows, node_ref, start, nn, valid, qx, qy, qz, ex_lo, ex_hi, evals,
+                     [&](unsigned, const double4 &row, unsigned) { return !(knn_lower(row, qx, qy, qz) > bound); }, leaf);
 }
 // K16's two passes:
 //   kSum = false  bound = the lane's current k-th candidate (the heap's root), leaves are pushed
@@ -4407,6 +4417,160 @@ __global__ __launch_bounds__(kFofBlock) void k_fof_rows(int64_t n, int64_t count
     members[slot] = m;
 }
 
+// ---------------------------------------------------------------------------------------
+// K18: exact binned pair counts (nbmi_pair_counts; include/nbmi.h).  The build, the node rows, d2,
+// the lower bound, the walk and the half search are K16's and K17's; new are the per-cell body count, an UPPER bound on
+// the computed d2 and with both the cell that is counted whole.
+// ---------------------------------------------------------------------------------------
+constexpr int kPairBlock = 64;    // one wave per workgroup, as K16 / K17
+constexpr int kPairMaxBins = 64;  // nb <= 64: nb + 1 edges, nb + 1 counters per lane (`below` and the bins)
+struct PairEdges {
+    double e2[kPairMaxBins + 1];  // E[k] = edges[k]^2, k <= nb (the rest unused)
+};
+// cnt[idx] = the number of bodies below node idx: its ranks are [node_ref[idx], node_ref[idx] + cnt[idx]).  The node behind
+// the subtree is next_off / kNodeBytes; k_emit_tile gives a subtree that reaches the end of the key order the link
+// num_nodes (e = n: nxt = n + pex(n) = total) - the sentinel's row, whose node_ref is -1 and is therefore NOT read: the
+// end is recognised by comparing with num_nodes.  A leaf counts 1.  Also, for every wave of 64 ranks, the node index of
+// its first body's leaf (k_fof_init's computation).
+__global__ __launch_bounds__(kBlock) void k_pair_cells(const Node *__restrict__ nodes, const int32_t *__restrict__ node_ref,
+                                                       const TreeInfo *__restrict__ info, int64_t n, int64_t capacity,
+                                                       int32_t *__restrict__ cnt, uint32_t *__restrict__ wleaf) {
+    if (info->error != 0 || info->sticky_error != 0) return;
+    const int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const int64_t num_nodes = info->num_nodes;
+    if (idx >= num_nodes || idx >= capacity) return;
+    const Node nd = nodes[idx];
+    const int64_t nx = (int64_t)(nd.next_off / kNodeBytes);
+    const int32_t r = node_ref[idx];
+    const int64_t end = nx >= num_nodes ? n : (int64_t)node_ref[nx];
+    cnt[idx] = (int32_t)(end - (int64_t)r);
+    if (__float_as_int(nd.s2t) == 0 && (r & 63) == 0) wleaf[r >> 6] = (uint32_t)idx;
+}
+// knn_lower's twin: an upper bound on the COMPUTED d2 between q and every body within `w` per axis of the anchor, so that
+// knn_lower <= computed d2 <= knn_upper for every body of the cell.  u = 2^-53.  Per axis, with T = |q - a| exact and R
+// the body's true distance from the anchor on that axis:
+//   what the computed |dx| can exceed: nothing beyond (T + R)(1 + u) - it is one rounding of the exact |b - q| <= T + R.
+//   t = fl(T) >= T (1 - u), so T <= t (1 + 2 u).  The stored w is NOT below the true reach: that is at most 2 hs + 43
+//     half ulps of bounds < 2 hs + 2^-47 bounds (k_knn_rows), w is one rounding of 2 hs + 2^-44 bounds (both terms
+//     exact), which takes at most u (2 bounds + 2^-44 bounds) < 2^-51 bounds of the 2^-44 bounds.  So R <= w and
+//     computed |dx| <= (t + w)(1 + 2 u)(1 + u).
+//   s = fl(t + w) >= (t + w)(1 - u);  h = fl(s + s 2^-49) >= s (1 + 16 u)(1 - u) >= (t + w)(1 + 13 u) >= computed |dx|.
+//     (The inflation is relative to s, not to t as in knn_lower: here the roundings scale with t + w, and w may be the
+//     larger part.)
+//   five roundings: the computed d2 is <= (sum dx^2)(1 + u)^3 - a product and two sums above each term - with two more
+//     (1 + u) from the squared |dx|: <= (sum (T + R)^2)(1 + u)^5 <= (sum (t + w)^2)(1 + 2 u)^2 (1 + u)^5 < (sum (t + w)^2)
+//     (1 + 10 u).  The value below is >= (sum h^2)(1 - u)^4 (1 + 2^-48) >= (sum (t + w)^2)(1 + 13 u)^2 (1 - u)^4 (1 + 32 u)
+//     > (sum (t + w)^2)(1 + 50 u): a factor five to spare.
+//   near the subnormal range: sums and differences are exact there, only products lose their relative bound.  s 2^-49 is
+//     inexact only for s < 2^-973; then that axis' |dx| < 2^-971 and its square rounds to 0, which any h^2 >= 0 covers.
+//     A value above 2^-960 has a normal largest term, and a subnormal product's absolute error (2^-1075 each, on either
+//     side) is below 2^-113 of it: inside the margin.  A value of at most 2^-960 means every h <= 2^-480 (1 + u), every
+//     computed |dx| <= h, the computed d2 < 3 x 2^-960 (1 + 4 u) + 3 x 2^-1075 < 2^-958: that is returned instead.
+//   An overflow to +inf is harmless: +inf is <= no edge, the cell is never accepted.
+__device__ __forceinline__ double knn_upper(double4 a, double qx, double qy, double qz) {
+    const double sx = __dadd_rn(fabs(__dsub_rn(a.x, qx)), a.w), sy = __dadd_rn(fabs(__dsub_rn(a.y, qy)), a.w),
+                 sz = __dadd_rn(fabs(__dsub_rn(a.z, qz)), a.w);
+    const double hx = __dadd_rn(sx, __dmul_rn(sx, 0x1p-49)), hy = __dadd_rn(sy, __dmul_rn(sy, 0x1p-49)),
+                 hz = __dadd_rn(sz, __dmul_rn(sz, 0x1p-49));
+    const double hi = __dmul_rn(__dadd_rn(__dadd_rn(__dmul_rn(hx, hx), __dmul_rn(hy, hy)), __dmul_rn(hz, hz)), 1.0 + 0x1p-48);
+    return hi > 0x1p-960 ? hi : 0x1p-958;
+}
+// the number of E[0 .. nb] that are < v (E strictly increasing, in LDS): 0 = `below`, k + 1 = bin k, nb + 1 = beyond the
+// last edge.  An edge that equals v is not below it: the upper edge belongs to the bin.
+__device__ __forceinline__ int pair_bin(const double *__restrict__ E, int nb, double v) {
+    int pos = 0;
+#pragma unroll
+    for (int step = 64; step > 0; step >>= 1) {
+        const int np = pos + step;
+        const bool in = np <= nb + 1;
+        if (in && E[in ? np - 1 : 0] < v) pos = np;
+    }
+    return pos;
+}
+// One wave per 64 key-adjacent bodies, as k_fof_link with half = 1: pairs inside the wave directly (the higher lane tests
+// the lower), every other pair by the walk that starts at the wave's own first leaf and skips the leaves of the ranks
+// below w0 + 64 - the wave sees exactly the bodies of a higher rank, every pair of two waves once.  At an internal cell an
+// active lane, in this order:
+//   prunes          if knn_lower > E[nb], strictly (a pair AT the last edge is always reached)
+//   accepts whole   if knn_upper <= E[0] (all of the cell into `below`), or E[k] < knn_lower and knn_upper <= E[k + 1] (all
+//                   of it into bin k): cnt bodies without a distance.  With p = pair_bin(knn_lower) both read
+//                   knn_upper <= E[p], counter p.
+//   else keeps the cell open.
+// A cell whose ranks reach below w0 + 64 is NEVER accepted whole (it may be pruned): it holds bodies of the wave itself,
+// already counted directly, the lane's own among them.  The walk begins behind the leaf of rank w0, so every cell it
+// meets starts above w0 and the condition is node_ref < w0 + 64, wave-uniform.  accept = 0 (NBMI_PAIRS_CELLS=0) accepts
+// nothing.
+// Counters: nb + 1 uint32 per lane in LDS, [counter][lane] - consecutive lanes, consecutive words, no bank conflicts; a
+// lane counts at most n - 1 < 2^31 pairs.  The E[k] sit in LDS in front of them (the search's indices diverge by lane).
+// At the end every counter is summed over the wave in 64 bits and added to out[2 + counter] by one agent-scope integer
+// atomic per non-empty counter: integers, so the result does not depend on any order.  out[0] += distances evaluated,
+// out[1] += pairs counted through whole cells.
+__global__ __launch_bounds__(kPairBlock) void k_pair_counts(const Node *__restrict__ nodes, const double4 *__restrict__ rows,
+                                                            const int32_t *__restrict__ node_ref,
+                                                            const int32_t *__restrict__ cnt, const TreeInfo *__restrict__ info,
+                                                            const uint32_t *__restrict__ perm, Bodies cur, int64_t n, int nb,
+                                                            PairEdges edges, int accept, const uint32_t *__restrict__ wleaf,
+                                                            unsigned long long *__restrict__ out) {
+    extern __shared__ double pair_lds[];  // E[nb + 1], then uint32 [nb + 1][64]
+    if (info->error != 0 || info->sticky_error != 0) return;
+    const int lane = threadIdx.x;
+    const int64_t w0 = (int64_t)blockIdx.x * kPairBlock, rank = w0 + lane;
+    const bool valid = rank < n;
+    const unsigned nn = __builtin_amdgcn_readfirstlane((unsigned)info->num_nodes * kNodeBytes);
+    double *E = pair_lds;
+    uint32_t *c = reinterpret_cast<uint32_t *>(pair_lds + nb + 1) + lane;
+    for (int k = 0; k <= nb; k++) {
+        E[k] = edges.e2[k];  // (every lane stores the same value)
+        c[64 * k] = 0u;
+    }
+    __syncthreads();
+    const KnnGroup own = knn_group(cur, perm, w0, n);
+    const double qx = own.x, qy = own.y, qz = own.z;
+    long long evals = 0, whole = 0;
+    for (int i = 0; i < 63; i++) {
+        if (w0 + i >= n) break;
+        const double d2 = knn_d2(knn_bcast(own.x, i), knn_bcast(own.y, i), knn_bcast(own.z, i), qx, qy, qz);
+        if (valid && lane > i) {
+            evals++;
+            const int b = pair_bin(E, nb, d2);
+            if (b <= nb) c[64 * b]++;
+        }
+    }
+    const unsigned start = __builtin_amdgcn_readfirstlane(wleaf[blockIdx.x]) * kNodeBytes;
+    const int64_t own_end = w0 + kPairBlock;
+    query_walk_cells(
+        nodes, rows, node_ref, start, nn, valid, qx, qy, qz, (int64_t)0, own_end, evals,
+        [&](unsigned idx, const double4 &row, unsigned) {
+            const int p = pair_bin(E, nb, knn_lower(row, qx, qy, qz));
+            if (p > nb) return false;  // pruned
+            if (!accept || (int64_t)node_ref[idx] < own_end) return true;
+            if (!(knn_upper(row, qx, qy, qz) <= E[p])) return true;
+            const uint32_t m = (uint32_t)cnt[idx];
+            c[64 * p] += m;
+            whole += (long long)m;
+            return false;
+        },
+        [&](double d2, const double4 &, int64_t) {
+            const int b = pair_bin(E, nb, d2);
+            if (b <= nb) c[64 * b]++;
+        });
+    for (int k = 0; k <= nb; k++) {
+        unsigned long long v = c[64 * k];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+        if (lane == 0 && v != 0ull) (void)__hip_atomic_fetch_add(out + 2 + k, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        evals += __shfl_xor(evals, o);
+        whole += __shfl_xor(whole, o);
+    }
+    if (lane == 0) {
+        (void)__hip_atomic_fetch_add(out, (unsigned long long)evals, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (whole) (void)__hip_atomic_fetch_add(out + 1, (unsigned long long)whole, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
 }  // namespace
 
 // =========================================================================================
@@ -4572,6 +4736,14 @@ struct nbmi_sim {
     double *fof_row_vals = nullptr, *fof_out13 = nullptr;
     int32_t *fof_label = nullptr;
     int64_t *fof_members = nullptr;
+    // binned pair counts (nbmi_pair_counts), allocated by the first call; no step touches them.
+    // 4 bytes per node row (the cells' body counts), 4 bytes per 64 bodies (the waves' first leaves), 67 words of results
+    // and the node rows of the k-NN query
+    int32_t *pair_cnt = nullptr;
+    uint32_t *pair_wleaf = nullptr;
+    unsigned long long *pair_out = nullptr;  // [0] distances evaluated, [1] pairs counted through whole cells, [2 + c] counter c
+    bool pair_ready = false;
+    bool pair_cells = true;  // cells inside one bin are counted whole (NBMI_PAIRS_CELLS=0: never; measurement)
     // what nbmi_compute_colors / nbmi_frame_begin colour by (nbmi_set_color_mode)
     int color_mode = NBMI_COLOR_SPEED, color_k = 32;
     double color_lo = 0.0, color_hi = 1.0;
@@ -5300,6 +5472,7 @@ static void read_env_knobs(nbmi_sim *s) {
     if (const char *e = getenv("NBMI_SORT_FUSED_HIST")) s->sort_fused_hist = atoi(e) != 0 ? 1 : 0;
     if (const char *e = getenv("NBMI_KEYS_LEAN")) s->keys_lean = atoi(e) != 0;
     if (const char *e = getenv("NBMI_FOF_HALF")) s->fof_half = atoi(e) != 0;
+    if (const char *e = getenv("NBMI_PAIRS_CELLS")) s->pair_cells = atoi(e) != 0;
     if (const char *e = getenv("NBMI_WALK_LANE")) s->walk_lane = atoi(e);
     if (const char *e = getenv("NBMI_WALK_STACK")) s->walk_stack = atoi(e);
     if (const char *e = getenv("NBMI_FORCE_PREC")) {
@@ -6105,6 +6278,78 @@ int nbmi_compute_group_colors(nbmi_sim *s, double link, int64_t min_members) {
     k_fof_colors<<<nblocks(n), kBlock, 0, s->stream>>>(s->info, n, s->fof_root, s->fof_minid, s->fof_cnt, s->perm,
                                                        s->buf[s->curbuf].id, min_members, s->colors);
     NBMI_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+namespace {
+// Enqueues build, cell counts and the pair search and never waits.  Afterwards pair_out = {distances evaluated, pairs
+// counted through whole cells, below, counts[0 .. nb)}.
+int pairs_enqueue(nbmi_sim *s, int nb, const PairEdges &e2) {
+    const int64_t n = s->n;
+    if (query_buffers(s)) return NBMI_ERR_HIP;
+    if (!s->pair_ready) {
+        if (dev_alloc(s, &s->pair_cnt, s->node_capacity + 2) || dev_alloc(s, &s->pair_wleaf, (n + 63) / 64) ||
+            dev_alloc(s, &s->pair_out, kPairMaxBins + 3))
+            return NBMI_ERR_HIP;
+        s->pair_ready = true;
+    }
+    hipStream_t st = s->stream;
+    NBMI_HIP_CHECK(hipMemsetAsync(s->pair_out, 0, (kPairMaxBins + 3) * sizeof(unsigned long long), st));
+    return query_enqueue(s, "k_pair_counts", [&] {
+        k_pair_cells<<<nblocks(s->own_node_rows), kBlock, 0, st>>>(s->nodes, s->node_ref, s->info, n, s->own_node_rows,
+                                                                   s->pair_cnt, s->pair_wleaf);
+        const size_t lds = (size_t)(nb + 1) * (sizeof(double) + kPairBlock * sizeof(uint32_t));
+        k_pair_counts<<<(int)((n + kPairBlock - 1) / kPairBlock), kPairBlock, lds, st>>>(
+            s->nodes, s->knn_rows, s->node_ref, s->pair_cnt, s->info, s->perm, s->buf[s->curbuf], n, nb, e2,
+            s->pair_cells ? 1 : 0, s->pair_wleaf, s->pair_out);
+    });
+}
+}  // namespace
+
+int nbmi_pair_counts(nbmi_sim *s, int nb, const double *edges, int64_t *counts, int64_t *below, int64_t *evals,
+                     int64_t *cell_pairs) {
+    if (int rc = check_handle(s)) return rc;
+    if (const char *why = knn_refusal(s)) {
+        nbmi::set_error("nbmi_pair_counts: %s", why);
+        return NBMI_ERR_ARG;
+    }
+    if (nb < 1 || nb > kPairMaxBins) {
+        nbmi::set_error("nbmi_pair_counts: nb = %d is outside 1 .. %d", nb, kPairMaxBins);
+        return NBMI_ERR_ARG;
+    }
+    if (!edges) {
+        nbmi::set_error("nbmi_pair_counts: null edges");
+        return NBMI_ERR_ARG;
+    }
+    PairEdges e2{};
+    for (int k = 0; k <= nb; k++) {
+        if (!isfinite(edges[k]) || edges[k] < 0.0 || (k > 0 && !(edges[k] > edges[k - 1]))) {
+            nbmi::set_error("nbmi_pair_counts: edges[%d] = %g: the edges must be finite, >= 0 and strictly increasing", k, edges[k]);
+            return NBMI_ERR_ARG;
+        }
+        e2.e2[k] = edges[k] * edges[k];
+        if (!isfinite(e2.e2[k]) || (k > 0 && !(e2.e2[k] > e2.e2[k - 1]))) {
+            nbmi::set_error("nbmi_pair_counts: the square of edges[%d] = %g is not finite or not above the one before it", k, edges[k]);
+            return NBMI_ERR_ARG;
+        }
+    }
+    for (int k = 0; counts && k < nb; k++) counts[k] = 0;
+    if (below) *below = 0;
+    if (evals) *evals = 0;
+    if (cell_pairs) *cell_pairs = 0;
+    if (s->n < 2) return 0;
+    NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
+    if (int rc = check_device_error(s)) return rc;
+    if (int rc = pairs_enqueue(s, nb, e2)) return rc;
+    NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
+    if (int rc = check_device_error(s)) return rc;
+    unsigned long long h[kPairMaxBins + 3];
+    NBMI_HIP_CHECK(hipMemcpyAsync(h, s->pair_out, (size_t)(nb + 3) * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->stream));
+    NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
+    if (evals) *evals = (int64_t)h[0];
+    if (cell_pairs) *cell_pairs = (int64_t)h[1];
+    if (below) *below = (int64_t)h[2];
+    for (int k = 0; counts && k < nb; k++) counts[k] = (int64_t)h[3 + k];
     return 0;
 }
 

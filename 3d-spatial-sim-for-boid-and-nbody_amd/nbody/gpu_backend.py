@@ -399,6 +399,38 @@ class _HIPSimulation:
         self._knn_refuse(what)
         self._knn_call(what, self._lib.nbmi_compute_group_colors(self._h, float(link), int(min_members)))
 
+    # ---- binned pair counts (include/nbmi.h nbmi_pair_counts) ----
+    def pair_counts(self, edges, evals=False):
+        """(counts int64 (nb,), below int) for the nb + 1 ``edges`` (1 <= nb <= 64, finite, >= 0, strictly increasing):
+        counts[k] = the number of unordered pairs of bodies with edges[k]^2 < d2 <= edges[k + 1]^2, below = those with
+        d2 <= edges[0]^2 - exact, equal to a brute force.  ``evals=True`` returns (counts, below, evals, cell_pairs): the
+        distances the call evaluated and the pairs it counted through whole cells.  Refused with ValueError where knn()
+        is and for bad edges; the call does not change what the next step computes."""
+        e = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+        what = f"pair_counts({len(e)} edges)"
+        self._knn_refuse(what)
+        nb = len(e) - 1
+        counts = np.zeros(max(nb, 0), dtype=np.int64)
+        below, ev, cells = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._knn_call(what, self._lib.nbmi_pair_counts(self._h, nb, _nat.ptr(e) if len(e) else None, _nat.ptr(counts),
+                                                        C.addressof(below), C.addressof(ev) if evals else None,
+                                                        C.addressof(cells) if evals else None))
+        return (counts, int(below.value), int(ev.value), int(cells.value)) if evals else (counts, int(below.value))
+
+    def correlation_function(self, edges, randoms):
+        """xi (nb,) float64: the natural estimator DD / RR x M (M - 1) / (N (N - 1)) - 1 of the two-point correlation
+        function, DD = this handle's pair_counts(edges), RR = those of the (M, 3) random catalogue ``randoms`` (a temporary
+        Barnes-Hut handle with unit masses at rest); nan where RR == 0."""
+        from nbody.pairs import xi_natural
+        r = _as_f64(randoms, (3,))
+        dd = self.pair_counts(edges)[0]
+        tmp = HIPBarnesHutSimulation(r, np.zeros_like(r), np.ones(len(r)), 1.0, 0.1, 1.0)
+        try:
+            rr = tmp.pair_counts(edges)[0]
+        finally:
+            tmp.close()
+        return xi_natural(dd, rr, self.n, len(r))
+
     def visible_points(self, cam_pos, cam_forward, cam_right, cam_up, tan_h, tan_v, far_dist):
         """Frustum culling + compaction on the device (reference compute_visibility_points,
         nbody/simulation.py:403-434, and the gather of draw(), :927-928): returns

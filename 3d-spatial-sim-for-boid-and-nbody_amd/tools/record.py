@@ -31,6 +31,8 @@ from pathlib import Path
 
 import numpy as np
 
+from nbody.pairs import auto_pair_edges, check_edges, correlation_dimension, xi_natural  # noqa: F401 (re-exported)
+
 PROJECT_ROOT = Path(__file__).resolve().parent.parent
 COMPRESSION_BATCH_SIZE = 50  # reference :225
 ZSTD_LEVEL = 19              # reference :252
@@ -451,6 +453,58 @@ def groups_line(sim, frame: int, link: float, min_members: int) -> str:
                        "count": int(cat["count"]), "groups": rows}) + "\n"
 
 
+# ---- binned pair counts (extra config key "pairs") -----------------------------------------
+PAIRS_FILE = "pairs.jsonl"
+
+
+def pairs_config(config: dict):
+    """The "pairs" key of a config as (every, edges or None for an "auto" not yet taken); None without the key;
+    ValueError for a malformed one."""
+    g = config.get("pairs")
+    if not g:
+        return None
+    every, edges = int(g.get("every", 0)), g.get("edges", "auto")
+    if every <= 0:
+        raise ValueError(f"--pairs: K must be positive, not {every}")
+    if edges is None or (isinstance(edges, str) and edges == "auto"):
+        return every, None
+    try:
+        return every, [float(x) for x in check_edges(edges)]
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"--pair-edges: {e}") from None
+
+
+def apply_pairs(gpu_sim, config: dict, rec_dir: Path = None):
+    """Resolve the config's pair edges.  "auto" is taken once, here, from the handle's current state (the initial one for
+    a new recording) - auto_pair_edges of its knn(1) - and written into metadata.json, from where --resume and --extend
+    re-apply it.  Returns the config (with the edges filled in)."""
+    g = pairs_config(config)
+    if g is None or g[1] is not None:
+        return config
+    edges = auto_pair_edges(gpu_sim.knn(1)[0])
+    config = dict(config, pairs={"every": g[0], "edges": edges})
+    if rec_dir is not None:
+        meta_path = Path(rec_dir) / "metadata.json"
+        meta = load_metadata(rec_dir) if meta_path.exists() else dict(config)
+        meta["pairs"] = config["pairs"]
+        _atomically(meta_path, lambda f: f.write(json.dumps(meta, indent=2).encode()))
+    return config
+
+
+def pairs_line(sim, frame: int, edges) -> str:
+    """One JSON line (with its newline) for the pair counts of the state `sim` holds after `frame`: the edges, the pairs
+    within the first edge, the pairs per bin, and the correlation dimension over all edges with the number of points it
+    used (null and 0 where fewer than two edges have a pair within them)."""
+    counts, below = sim.pair_counts(edges)
+    counts = [int(c) for c in counts]
+    try:
+        d2, points = correlation_dimension(edges, below, counts)
+    except ValueError:
+        d2, points = None, 0
+    return json.dumps({"frame": frame, "edges": [float(e) for e in edges], "below": int(below), "counts": counts,
+                       "d2": d2, "d2_points": points}) + "\n"
+
+
 def _generate_initial_conditions(config: dict):
     from tools.presets import generate_distribution
     p, v, m = generate_distribution(config.get("distribution", "galaxy"), config["num_bodies"],
@@ -466,7 +520,8 @@ def record_pipelined(gpu_sim, rec_dir: Path, start_frame: int, total_frames: int
     frame_wait, its file through the sequential loop's writers, frame_release.  Where a diagnostics line (`every`) or a
     state checkpoint is due the frame itself is finished first - write_diag(frame) / write_state(frame, compressed=False)
     are the caller's synchronous writers, and the checkpoint stays the state of exactly the last frame on disk.
-    `also_every`: a second period at which write_diag is due (the groups lines, which the caller's writer adds).
+    `also_every`: further periods at which write_diag is due (the groups and the pairs lines, which the caller's writer
+    adds): one number or several.
 
     `gpu_sim` needs step_many, frame_begin, frame_wait, frame_release, frames_pending and step_count (the backend object,
     or a stand-in: nothing here touches a device).  On Ctrl-C the library is asked which frames are in flight and where
@@ -490,6 +545,7 @@ def record_pipelined(gpu_sim, rec_dir: Path, start_frame: int, total_frames: int
             write_bytes_atomic(zf, pack_container(1 if kind == "key" else 2, a.tobytes(), b.tobytes()))
         gpu_sim.frame_release(slot)
 
+    also = tuple(k for k in (also_every if isinstance(also_every, (tuple, list)) else (also_every,)) if k and k > 0)
     frame = start_frame - 1
     held = None  # the frame begun and not yet written: (slot, frame, kind)
     try:
@@ -501,7 +557,7 @@ def record_pipelined(gpu_sim, rec_dir: Path, start_frame: int, total_frames: int
                 finish(*held)
             held = (slot, frame, kind)
             state_due = (frame + 1) % STATE_EVERY == 0
-            if state_due or (every > 0 and (frame + 1) % every == 0) or (also_every > 0 and (frame + 1) % also_every == 0):
+            if state_due or (every > 0 and (frame + 1) % every == 0) or any((frame + 1) % k == 0 for k in also):
                 finish(*held)
                 held = None
                 write_diag(frame)  # before the state checkpoint: a resume from it finds every line up to its frame
@@ -603,10 +659,14 @@ def record(config: dict, resume: bool = False, root: Path = None, quiet: bool = 
     # density through the unchanged colour and frame calls of both loops
     # extra config key "groups": {"every": K, "link": b, "min_members": M} = every K-th frame a line of friends-of-friends
     # groups in groups.jsonl
+    # extra config key "pairs": {"every": K, "edges": [e0, e1, ...]} = every K-th frame a line of binned pair counts in
+    # pairs.jsonl
     try:
         config = apply_color_mode(gpu_sim, config, rec_dir)
         config = apply_groups(gpu_sim, config, rec_dir)
         groups = groups_config(config)
+        config = apply_pairs(gpu_sim, config, rec_dir)
+        pairs = pairs_config(config)
     except Exception:
         gpu_sim.close()
         raise
@@ -637,14 +697,25 @@ def record(config: dict, resume: bool = False, root: Path = None, quiet: bool = 
         else:
             truncate_diagnostics(groups_path, start_frame - 1)
 
-    def write_diag(frame):  # the synchronous per-frame lines of both loops: diagnostics, then groups
-        nonlocal last_diag, last_groups
+    pairs_path = rec_dir / PAIRS_FILE
+    last_pairs = start_frame - 1
+    if pairs:
+        if start_frame == 0:  # a run from frame 0 starts the file afresh
+            _atomically(pairs_path, lambda f: f.write(b""))
+        else:
+            truncate_diagnostics(pairs_path, start_frame - 1)
+
+    def write_diag(frame):  # the synchronous per-frame lines of both loops: diagnostics, then groups, then pairs
+        nonlocal last_diag, last_groups, last_pairs
         if every > 0 and (frame + 1) % every == 0 and frame > last_diag:
             append_line(diag_path, diagnostics_line(gpu_sim, frame, substeps, dt, diag_extra))
             last_diag = frame
         if groups and (frame + 1) % groups[0] == 0 and frame > last_groups:
             append_line(groups_path, groups_line(gpu_sim, frame, groups[1], groups[2]))
             last_groups = frame
+        if pairs and (frame + 1) % pairs[0] == 0 and frame > last_pairs:
+            append_line(pairs_path, pairs_line(gpu_sim, frame, pairs[1]))
+            last_pairs = frame
 
     def write_frame(frame):
         gpu_sim.compute_colors(15.0)
@@ -673,7 +744,7 @@ def record(config: dict, resume: bool = False, root: Path = None, quiet: bool = 
     if config.get("pipeline"):  # extra config key (metadata.json, only when set): the overlapped loop
         try:
             record_pipelined(gpu_sim, rec_dir, start_frame, total_frames, substeps, dt, direct_zstd, every, write_diag,
-                             write_state, also_every=groups[0] if groups else 0)
+                             write_state, also_every=(groups[0] if groups else 0, pairs[0] if pairs else 0))
         except KeyboardInterrupt:
             at = start_frame - 1 + gpu_sim.step_count() // max(substeps, 1)
             say(f"\n[Record] Paused at frame {at}; resume with record(config, resume=True)")
@@ -788,6 +859,19 @@ def show_status(session_name: str, root: Path = None) -> bool:
             largest = last["groups"][0]["members"] if last["groups"] else 0
             print(f"    frame {last['frame']}: {last['count']} groups of at least {last['min_members']} "
                   f"(of {last['n_groups']}), largest {largest} bodies")
+    pk = meta.get("pairs")
+    if pk:
+        edges = pk.get("edges", "auto")
+        print(f"  Pairs: every {pk.get('every')} frames, "
+              + (f"{len(edges) - 1} bins from {edges[0]:.6g} to {edges[-1]:.6g}" if isinstance(edges, list)
+                 else "edges auto (not taken yet)"))
+        prows = read_diagnostics(rec_dir / PAIRS_FILE)
+        if prows:
+            last = prows[-1]
+            within = int(last["below"]) + sum(int(c) for c in last["counts"])
+            print(f"    frame {last['frame']}: D2 = "
+                  + (f"{last['d2']:.3f} over {last['d2_points']} edges" if last.get("d2") is not None else "n/a")
+                  + f", {within:,} pairs within {last['edges'][-1]:.6g}")
     if completed < total:
         print(f"\n  To resume: python -m tools.record --resume {session_name}")
     else:
@@ -826,7 +910,7 @@ def build_parser():
                "--preset-id); --preset-id indexes this build's preset list (python -m tools.record --presets shows "
                "it); --dt sets dt_per_frame (the reference writes an unused 'dt' key); --presets, --seed, "
                "--device-ic, --diagnostics, --integrator, --multipole, --pipeline, --color, --density-k, --density-range, "
-               "--groups, --linking-length, --min-members and --root are additions.")
+               "--groups, --linking-length, --min-members, --pairs, --pair-edges and --root are additions.")
     ap.add_argument("session", nargs="?", help="session name (for --resume, --status or --extend)")
     ap.add_argument("--resume", action="store_true", help="resume an interrupted recording (default: the most recent)")
     ap.add_argument("--extend", type=int, metavar="FRAMES", help="extend an existing recording by N frames")
@@ -871,6 +955,12 @@ def build_parser():
                          "initial state, twice its median nearest-neighbour distance)")
     ap.add_argument("--min-members", type=int, default=None, metavar="M",
                     help=f"smallest group listed (default {GROUPS_MIN_MEMBERS})")
+    ap.add_argument("--pairs", type=int, default=None, metavar="K",
+                    help="every K frames append the binned pair counts (pairs within the first edge, pairs per bin, the "
+                         "correlation dimension) to pairs.jsonl (stored in metadata.json as pairs)")
+    ap.add_argument("--pair-edges", type=str, default=None, metavar="auto|e0,e1,...",
+                    help="bin edges, 2 .. 65 increasing distances (default auto: taken once from the initial state, 12 "
+                         "bins from half to 32 median nearest-neighbour distances, a factor sqrt 2 apart)")
     ap.add_argument("--root", type=Path, default=None, help="directory holding recordings/ (default: the package's)")
     return ap
 
@@ -944,6 +1034,18 @@ def build_config(args) -> dict:
                 raise ValueError(f"--linking-length: B must be a number or auto, not {gl!r}") from None
         config["groups"] = {"every": int(gk), "link": link, "min_members": GROUPS_MIN_MEMBERS if gm is None else int(gm)}
         groups_config(config)  # (a bad K, B or M raises here)
+    pk, pe = (getattr(args, a, None) for a in ("pairs", "pair_edges"))
+    if pk is None and pe is not None:
+        raise ValueError("--pair-edges needs --pairs K")
+    if pk is not None:  # the default writes no key
+        edges = "auto"
+        if pe is not None and pe.strip().lower() != "auto":
+            try:
+                edges = [float(x) for x in pe.split(",")]
+            except ValueError:
+                raise ValueError(f"--pair-edges: need auto or comma-separated numbers, not {pe!r}") from None
+        config["pairs"] = {"every": int(pk), "edges": edges}
+        pairs_config(config)  # (a bad K or bad edges raise here)
     return config
 
 

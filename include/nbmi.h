@@ -320,6 +320,39 @@ int nbmi_fof_catalogue(nbmi_sim *sim, double link, int64_t min_members, int64_t 
                        int64_t *members, double *out13, int64_t *count);
 int nbmi_compute_group_colors(nbmi_sim *sim, double link, int64_t min_members);
 
+/* ---- exact binned pair counts ---------------------------------------------------------------
+ * Of the handle's current float64 state, exactly:
+ *   d2(i, j)   as above: (dx dx + dy dy) + dz dz with dx = x_j - x_i, float64 in this association, no FMA.
+ *   edges      nb + 1 float64 with 1 <= nb <= 64, all finite, edges[0] >= 0, strictly increasing.
+ *   E[k]       = edges[k] * edges[k], one float64 product each, computed on the host.  The E[k] must themselves be finite
+ *              and strictly increasing (two close edges may square to one value), else NBMI_ERR_ARG.
+ *   below      = the number of unordered pairs i < j with d2(i, j) <= E[0].  With edges[0] == 0 these are the coincident
+ *              pairs.
+ *   counts[k]  = the number of unordered pairs with E[k] < d2(i, j) <= E[k + 1].  The upper edge belongs to the bin, as
+ *              equality links in nbmi_fof: below + counts[0 .. k] is C(edges[k + 1]), the number of pairs within that
+ *              distance, and at edges[k + 1] = link it is the number of links of nbmi_fof.
+ * The counts are integers summed by integer atomics: the result is unique, independent of any order of evaluation, and
+ * equals a brute force's exactly.  counts ((nb,) int64), below, evals and cell_pairs may each be NULL.
+ *   *evals      = the number of d2 the call evaluated;
+ *   *cell_pairs = the number of pairs it counted through whole cells, without a d2 (a cell of the tree that provably lies
+ *              inside one bin as seen from a body adds its body count at once).
+ * Both are measurement hooks like nbmi_fof's evals.  N == 0 or N == 1: success, all zeros.
+ * Two calls on an unchanged state return the same numbers.  A quadrupole or leapfrog handle returns a plain handle's
+ * numbers: the tree is the same.
+ * A call changes nothing that a later step reads (state and its order, the tree header - saved and restored -, the
+ * "auto" precision flags and force_all64 - the build runs without a dt -, the step count, the stored leapfrog
+ * acceleration).  NBMI_ERR_CAPACITY of the call's own tree build is reported with a step's message.
+ * Refused with NBMI_ERR_ARG, message "nbmi_pair_counts: ...": nb outside 1 .. 64, null edges, an edge that is not finite,
+ * negative or not above the one before it (or whose square is not), and the handles nbmi_knn refuses (direct N^2, owner
+ * mode, a proper shard, the measurement-only walks).
+ * The first call allocates 4 bytes per node row, 4 bytes per 64 bodies, 536 bytes of results and (shared with nbmi_knn
+ * and nbmi_fof) 32 bytes per node row.
+ * Environment NBMI_PAIRS_CELLS (read when the handle is created, like the other measurement knobs): 0 never counts a
+ * cell whole (pruning stays).  Results are the same; evals, cell_pairs (then 0) and the time are not (DESIGN.md section
+ * 4.16 has the A/B). */
+int nbmi_pair_counts(nbmi_sim *sim, int nb, const double *edges, int64_t *counts /* (nb,), may be NULL */,
+                     int64_t *below /* may be NULL */, int64_t *evals /* may be NULL */, int64_t *cell_pairs /* may be NULL */);
+
 /* Multi-GPU (one process per GPU).  A handle created with nbmi_create holds ALL bodies; with a
  * shard set, step() integrates only the key-sorted ranks [begin,end) (direct method: the body
  * indices [begin,end), its state is never re-ordered) and leaves the others untouched until
