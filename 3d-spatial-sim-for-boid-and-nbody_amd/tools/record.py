@@ -26,8 +26,10 @@ import json
 import os
 import struct
 import time
+from dataclasses import dataclass
 from datetime import datetime
 from pathlib import Path
+from typing import Callable
 
 import numpy as np
 
@@ -97,10 +99,25 @@ def get_recording_dir(session_name: str, root: Path = None) -> Path:
     return base
 
 
+def write_metadata(rec_dir: Path, meta: dict):
+    """The one writer of metadata.json (atomic: a resume depends on this file)."""
+    _atomically(Path(rec_dir) / "metadata.json", lambda f: f.write(json.dumps(meta, indent=2).encode()))
+
+
 def save_metadata(rec_dir: Path, config: dict, start_time: float):
-    meta = {**config, "start_time": start_time, "start_datetime": datetime.fromtimestamp(start_time).isoformat()}
-    with open(Path(rec_dir) / "metadata.json", "w") as f:
-        json.dump(meta, f, indent=2)
+    write_metadata(rec_dir, {**config, "start_time": start_time,
+                             "start_datetime": datetime.fromtimestamp(start_time).isoformat()})
+
+
+def set_metadata_key(config: dict, rec_dir, key: str, value):
+    """The config with `key` set to a value that was just taken from the handle's state (an "auto" parameter), written
+    into the session's metadata.json too, from where --resume and --extend read it back."""
+    config = dict(config, **{key: value})
+    if rec_dir is not None:
+        meta = load_metadata(rec_dir) if (Path(rec_dir) / "metadata.json").exists() else dict(config)
+        meta[key] = value
+        write_metadata(rec_dir, meta)
+    return config
 
 
 def load_metadata(rec_dir: Path) -> dict:
@@ -113,10 +130,14 @@ def _frame_paths(rec_dir, idx):
     return rec_dir / f"frame_{idx:04d}.zstd", rec_dir / f"frame_{idx:04d}.npz"
 
 
+def _frame_on_disk(rec_dir, idx) -> bool:
+    return any(p.exists() for p in _frame_paths(rec_dir, idx))
+
+
 def get_completed_frames(rec_dir: Path) -> int:
     """Number of contiguous frames from 0 present as .npz or .zstd (reference :67-76)."""
     count = 0
-    while any(p.exists() for p in _frame_paths(rec_dir, count)):
+    while _frame_on_disk(rec_dir, count):
         count += 1
     return count
 
@@ -270,14 +291,14 @@ def compress_recording(rec_dir: Path, upto: int = None, batch_size: int = COMPRE
     return done
 
 
-# ---- initial conditions + the recording loop ---------------------------------------------------
 # ---- conservation diagnostics (diagnostics_every: K) -------------------------------------------
 DIAGNOSTICS_FILE = "diagnostics.jsonl"
 
 
-def diagnostics_line(sim, frame: int, substeps: int, dt: float, extra=None) -> str:
-    """One JSON line (with its newline) for the state `sim` holds after `frame` (-1: the initial state).  Floats are
-    written with repr (json's float form), so every value reads back bit for bit."""
+def diagnostics_line(sim, frame: int, substeps: int, dt: float, extra=None, masses=None) -> str:
+    """One JSON line (with its newline) for the state `sim` holds after `frame` (-1: the initial state; with `masses` it
+    also carries abs_momentum, the scale that the momentum drift is measured against).  Floats are written with repr
+    (json's float form), so every value reads back bit for bit."""
     d = sim.diagnostics(potential=True)
     steps = (frame + 1) * substeps
     rec = {"frame": frame, "steps": steps, "time": steps * dt, "mass": d.mass, "center_of_mass": list(d.center_of_mass),
@@ -287,6 +308,9 @@ def diagnostics_line(sim, frame: int, substeps: int, dt: float, extra=None) -> s
     share, all64 = sim.force_precision_share() if frame >= 0 and hasattr(sim, "force_precision_share") else (None, None)
     rec["force_precision_share"] = share
     rec["all_float64"] = all64
+    if masses is not None:
+        v = sim.get_velocities()
+        rec["abs_momentum"] = float(np.sum(masses * np.sqrt(np.sum(v * v, axis=1))))
     if extra:
         rec.update(extra)
     return json.dumps(rec) + "\n"
@@ -374,12 +398,7 @@ def apply_color_mode(gpu_sim, config: dict, rec_dir: Path = None):
         return config
     if rng is None:
         rng = default_density_range(gpu_sim.densities(k))
-        config = dict(config, color={"mode": "density", "k": k, "log10_range": [rng[0], rng[1]]})
-        if rec_dir is not None:
-            meta_path = Path(rec_dir) / "metadata.json"
-            meta = load_metadata(rec_dir) if meta_path.exists() else dict(config)
-            meta["color"] = config["color"]
-            _atomically(meta_path, lambda f: f.write(json.dumps(meta, indent=2).encode()))
+        config = set_metadata_key(config, rec_dir, "color", {"mode": "density", "k": k, "log10_range": [rng[0], rng[1]]})
     gpu_sim.set_color_mode("density", k=k, log10_range=rng)
     return config
 
@@ -402,8 +421,8 @@ def default_linking_length(r2_1):
 
 
 def groups_config(config: dict):
-    """The "groups" key of a config as (every, link or None for an "auto" not yet taken, min_members); None without the
-    key; ValueError for a malformed one."""
+    """The "groups" key of a config, {"every": K, "link": b, "min_members": M}, as (every, link or None for an "auto" not
+    yet taken, min_members); None without the key; ValueError for a malformed one."""
     g = config.get("groups")
     if not g:
         return None
@@ -418,24 +437,6 @@ def groups_config(config: dict):
     if not (np.isfinite(link) and link > 0.0):
         raise ValueError(f"--linking-length: B must be finite and > 0 (or auto), not {link}")
     return every, link, mm
-
-
-def apply_groups(gpu_sim, config: dict, rec_dir: Path = None):
-    """Resolve the config's linking length.  "auto" is taken once, here, from the handle's current state (the initial one
-    for a new recording) and written into metadata.json, from where --resume and --extend re-apply it.  Returns the
-    config (with the length filled in)."""
-    g = groups_config(config)
-    if g is None or g[1] is not None:
-        return config
-    every, _, mm = g
-    link = default_linking_length(gpu_sim.knn(1)[0])
-    config = dict(config, groups={"every": every, "link": link, "min_members": mm})
-    if rec_dir is not None:
-        meta_path = Path(rec_dir) / "metadata.json"
-        meta = load_metadata(rec_dir) if meta_path.exists() else dict(config)
-        meta["groups"] = config["groups"]
-        _atomically(meta_path, lambda f: f.write(json.dumps(meta, indent=2).encode()))
-    return config
 
 
 def groups_line(sim, frame: int, link: float, min_members: int) -> str:
@@ -458,8 +459,8 @@ PAIRS_FILE = "pairs.jsonl"
 
 
 def pairs_config(config: dict):
-    """The "pairs" key of a config as (every, edges or None for an "auto" not yet taken); None without the key;
-    ValueError for a malformed one."""
+    """The "pairs" key of a config, {"every": K, "edges": [e0, e1, ...]}, as (every, edges or None for an "auto" not yet
+    taken); None without the key; ValueError for a malformed one."""
     g = config.get("pairs")
     if not g:
         return None
@@ -472,23 +473,6 @@ def pairs_config(config: dict):
         return every, [float(x) for x in check_edges(edges)]
     except (TypeError, ValueError) as e:
         raise ValueError(f"--pair-edges: {e}") from None
-
-
-def apply_pairs(gpu_sim, config: dict, rec_dir: Path = None):
-    """Resolve the config's pair edges.  "auto" is taken once, here, from the handle's current state (the initial one for
-    a new recording) - auto_pair_edges of its knn(1) - and written into metadata.json, from where --resume and --extend
-    re-apply it.  Returns the config (with the edges filled in)."""
-    g = pairs_config(config)
-    if g is None or g[1] is not None:
-        return config
-    edges = auto_pair_edges(gpu_sim.knn(1)[0])
-    config = dict(config, pairs={"every": g[0], "edges": edges})
-    if rec_dir is not None:
-        meta_path = Path(rec_dir) / "metadata.json"
-        meta = load_metadata(rec_dir) if meta_path.exists() else dict(config)
-        meta["pairs"] = config["pairs"]
-        _atomically(meta_path, lambda f: f.write(json.dumps(meta, indent=2).encode()))
-    return config
 
 
 def pairs_line(sim, frame: int, edges) -> str:
@@ -505,6 +489,77 @@ def pairs_line(sim, frame: int, edges) -> str:
                        "d2": d2, "d2_points": points}) + "\n"
 
 
+# ---- periodic side files: one description each, one mechanism for all -----------------------
+@dataclass(frozen=True)
+class LineStream:
+    """A side file that gets one JSON line every K-th frame."""
+    file: str
+    settings: Callable           # config -> None (absent) or (every, parameters ...); ValueError for a malformed config
+    line: Callable               # (sim, frame, parameters ...) -> the line for the state after `frame`
+    key: str = None              # where the first parameter may be "auto" (None in the settings until taken): the config key
+    auto: Callable = None        # and (sim, settings) -> its value with "auto" taken from the handle's current state
+    first_line: Callable = None  # (sim, masses, parameters ...) -> the line a file that starts at frame 0 begins with
+
+    def apply(self, gpu_sim, config: dict, rec_dir: Path = None):
+        """The config with an "auto" parameter resolved: taken once, here, from the handle's current state (the initial one
+        for a new recording) and written into metadata.json, from where --resume and --extend re-apply it."""
+        s = self.settings(config)
+        if s is None or self.auto is None or s[1] is not None:
+            return config
+        return set_metadata_key(config, rec_dir, self.key, self.auto(gpu_sim, s))
+
+
+def diagnostics_config(config: dict):
+    """The bare "diagnostics_every" key as (every, substeps, dt, extra keys of every line); None without it."""
+    every, substeps, integrator = int(config.get("diagnostics_every") or 0), config["substeps"], config.get("integrator")
+    # (a leapfrog session's lines say so: their velocities, hence K and E, are synchronized with the positions)
+    extra = {"integrator": integrator} if integrator not in (None, "kick_drift") else None
+    return (every, substeps, config["dt_per_frame"] / substeps, extra) if every > 0 else None
+
+
+DIAGNOSTICS = LineStream(DIAGNOSTICS_FILE, diagnostics_config, diagnostics_line,
+                         first_line=lambda sim, masses, *p: diagnostics_line(sim, -1, *p, masses=masses))
+GROUPS = LineStream(GROUPS_FILE, groups_config, groups_line, key="groups",
+                    auto=lambda sim, s: {"every": s[0], "link": default_linking_length(sim.knn(1)[0]), "min_members": s[2]})
+PAIRS = LineStream(PAIRS_FILE, pairs_config, pairs_line, key="pairs",
+                   auto=lambda sim, s: {"every": s[0], "edges": auto_pair_edges(sim.knn(1)[0])})
+apply_groups, apply_pairs = GROUPS.apply, PAIRS.apply  # (gpu_sim, config, rec_dir=None) -> the config, "auto" resolved
+LINE_STREAMS = (DIAGNOSTICS, GROUPS, PAIRS)  # in the order of their lines after a frame; a new side file is one more entry
+
+
+def line_due(frame: int, every: int) -> bool:
+    return every > 0 and (frame + 1) % every == 0
+
+
+def open_lines(gpu_sim, config: dict, rec_dir: Path, start_frame: int, masses):
+    """Start (at frame 0) or truncate (a resume) the side file of every stream the config has on.  Returns (due, write):
+    due(frame) says whether any stream has a line after `frame`, write(frame) appends the lines that are due and not yet
+    written - the synchronous per-frame lines of both loops."""
+    on, last = [], {}  # per stream: (stream, settings, path), and by path the last frame it has a line for
+    for stream in LINE_STREAMS:
+        s = stream.settings(config)
+        if s is None:
+            continue
+        path = Path(rec_dir) / stream.file
+        if start_frame == 0:  # a run from frame 0 starts the file afresh
+            first = stream.first_line(gpu_sim, masses, *s[1:]) if stream.first_line else ""
+            _atomically(path, lambda f: f.write(first.encode()))
+        else:
+            truncate_diagnostics(path, start_frame - 1)
+        on.append((stream, s, path))
+
+    def due(frame):
+        return any(line_due(frame, s[0]) for _, s, _ in on)
+
+    def write(frame):
+        for stream, s, path in on:
+            if line_due(frame, s[0]) and frame > last.get(path, start_frame - 1):
+                append_line(path, stream.line(gpu_sim, frame, *s[1:]))
+                last[path] = frame
+    return due, write
+
+
+# ---- initial conditions + the recording loops -----------------------------------------------------------------------
 def _generate_initial_conditions(config: dict):
     from tools.presets import generate_distribution
     p, v, m = generate_distribution(config.get("distribution", "galaxy"), config["num_bodies"],
@@ -512,78 +567,99 @@ def _generate_initial_conditions(config: dict):
     return p.astype(np.float64), v.astype(np.float64), m.astype(np.float64)
 
 
+def frame_kind(frame: int, direct_zstd: bool, absolute: bool = False) -> str:
+    """"f32" (raw .npz), or in a .zstd session "key" (format 1: frame 0, or a frame that must not depend on the delta
+    chain - format 1 is legal anywhere) or "delta" (format 2)."""
+    return ("key" if frame == 0 or absolute else "delta") if direct_zstd else "f32"
+
+
+def write_frame_file(rec_dir: Path, frame: int, kind: str, a, b):
+    """The file of one frame from the two arrays of its kind: positions and colours, or their int16 deltas."""
+    if kind == "f32":
+        save_frame(rec_dir, frame, a, b)
+    else:
+        zf, _ = _frame_paths(rec_dir, frame)
+        write_bytes_atomic(zf, pack_container(1 if kind == "key" else 2, a.tobytes(), b.tobytes()))
+
+
+def _after_frame(rec_dir: Path, frame: int, write_lines, write_state):
+    """What follows a frame's file: its lines, and every STATE_EVERY frames the checkpoint that replaces the older one."""
+    write_lines(frame)  # before the state checkpoint: a resume from it finds every line up to its frame
+    if (frame + 1) % STATE_EVERY == 0:
+        write_state(frame)
+        old = Path(rec_dir) / f"state_{frame - STATE_EVERY:04d}.npz"
+        if old.exists():
+            old.unlink()
+
+
+def device_frame(gpu_sim, start_frame: int, substeps: int) -> int:
+    """The frame the DEVICE stands at, asked of the library: an interrupt is delivered when the step call returns,
+    before a loop could note anything."""
+    return start_frame - 1 + gpu_sim.step_count() // max(substeps, 1)
+
+
+def _pause(at: int, write_lines, write_state):
+    """Ctrl-C in either loop (reference :916-935), once every frame up to `at`, where the device stands, is on disk: its
+    lines and a compressed state file so that --resume continues from there.  The checkpoint must be the state of
+    exactly the last frame on disk, or a resume would skip or repeat one frame interval."""
+    if at >= 0:
+        write_lines(at)
+        write_state(at, compressed=True)
+
+
 def record_pipelined(gpu_sim, rec_dir: Path, start_frame: int, total_frames: int, substeps: int, dt: float,
-                     direct_zstd: bool, every: int, write_diag, write_state, also_every: int = 0):
+                     direct_zstd: bool, lines_due, write_lines, write_state):
     """The recording loop of ``record(config with "pipeline": True)``: the files of the sequential loop, but
     the host compresses and writes frame k - 1 while the device computes frame k.  Per frame: step_many (enqueue),
     frame_begin (enqueue: one snapshot kernel, then the copy on a stream of its own), then the PREVIOUS frame is finished:
-    frame_wait, its file through the sequential loop's writers, frame_release.  Where a diagnostics line (`every`) or a
-    state checkpoint is due the frame itself is finished first - write_diag(frame) / write_state(frame, compressed=False)
-    are the caller's synchronous writers, and the checkpoint stays the state of exactly the last frame on disk.
-    `also_every`: further periods at which write_diag is due (the groups and the pairs lines, which the caller's writer
-    adds): one number or several.
+    frame_wait, its file through the sequential loop's writer, frame_release.  Where a line is due - `lines_due(frame)`
+    says so, once for all side files; one period K given in its place stands for line_due(frame, K) - or a state
+    checkpoint is, the frame itself is finished first: write_lines(frame) / write_state(frame, compressed=False) are the
+    caller's synchronous writers, and the checkpoint stays the state of exactly the last frame on disk.
 
     `gpu_sim` needs step_many, frame_begin, frame_wait, frame_release, frames_pending and step_count (the backend object,
     or a stand-in: nothing here touches a device).  On Ctrl-C the library is asked which frames are in flight and where
     the device stands; every pending frame is written from its slot (a delta frame as a delta: the slot still holds the
-    payload), a stepped frame that has no slot yet is taken, then the diagnostics line and the compressed checkpoint of
-    the frame the device is at, and the interrupt is re-raised.  Returns the last frame written."""
-    rec_dir = Path(rec_dir)
-
-    def kind_of(frame):
-        return ("key" if frame == 0 else "delta") if direct_zstd else "f32"
-
-    def on_disk(frame):
-        return any(q.exists() for q in _frame_paths(rec_dir, frame))
+    payload), a stepped frame that has no slot yet is taken, then the lines and the compressed checkpoint of the frame
+    the device is at, and the interrupt is re-raised.  Returns the last frame written."""
+    if not callable(lines_due):
+        every, lines_due = int(lines_due), lambda frame: line_due(frame, every)
 
     def finish(slot, frame, kind):
-        a, b = gpu_sim.frame_wait(slot)
-        if kind == "f32":
-            save_frame(rec_dir, frame, a, b)
-        else:
-            zf, _ = _frame_paths(rec_dir, frame)
-            write_bytes_atomic(zf, pack_container(1 if kind == "key" else 2, a.tobytes(), b.tobytes()))
+        write_frame_file(rec_dir, frame, kind, *gpu_sim.frame_wait(slot))
         gpu_sim.frame_release(slot)
 
-    also = tuple(k for k in (also_every if isinstance(also_every, (tuple, list)) else (also_every,)) if k and k > 0)
     frame = start_frame - 1
     held = None  # the frame begun and not yet written: (slot, frame, kind)
     try:
         for frame in range(start_frame, total_frames):
             gpu_sim.step_many(dt, substeps)
-            kind = kind_of(frame)
+            kind = frame_kind(frame, direct_zstd)
             slot = gpu_sim.frame_begin(kind, 15.0)
             if held is not None:
                 finish(*held)
             held = (slot, frame, kind)
-            state_due = (frame + 1) % STATE_EVERY == 0
-            if state_due or (every > 0 and (frame + 1) % every == 0) or any((frame + 1) % k == 0 for k in also):
+            if (frame + 1) % STATE_EVERY == 0 or lines_due(frame):
                 finish(*held)
                 held = None
-                write_diag(frame)  # before the state checkpoint: a resume from it finds every line up to its frame
-                if state_due:
-                    write_state(frame)
-                    old = rec_dir / f"state_{frame - STATE_EVERY:04d}.npz"
-                    if old.exists():
-                        old.unlink()
+                _after_frame(rec_dir, frame, write_lines, write_state)
         if held is not None:
             finish(*held)
-            held = None
     except KeyboardInterrupt:
         # asked of the library, not of `held`: the interrupt may have come between a C call and the assignment
         pending = gpu_sim.frames_pending()
-        at = start_frame - 1 + gpu_sim.step_count() // max(substeps, 1)
+        at = device_frame(gpu_sim, start_frame, substeps)
         for slot, kind, steps in pending:
             f = start_frame - 1 + steps // max(substeps, 1)
-            if on_disk(f):  # written, not yet released
+            if _frame_on_disk(rec_dir, f):  # written, not yet released
                 gpu_sim.frame_release(slot)
-            else:           # not written - or its write was cut short, which left nothing (_atomically)
+            else:                           # not written - or its write was cut short, which left nothing (_atomically)
                 finish(slot, f, kind)
-        if at >= start_frame and not on_disk(at):  # stepped, no slot yet: the chain stands at frame at - 1, so the normal kind
-            finish(gpu_sim.frame_begin(kind_of(at), 15.0), at, kind_of(at))
-        if at >= 0:
-            write_diag(at)
-            write_state(at, compressed=True)
+        if at >= start_frame and not _frame_on_disk(rec_dir, at):
+            # stepped, no slot yet: the chain stands at frame at - 1, so the normal kind
+            kind = frame_kind(at, direct_zstd)
+            finish(gpu_sim.frame_begin(kind, 15.0), at, kind)
+        _pause(at, write_lines, write_state)
         raise
     return frame
 
@@ -657,134 +733,56 @@ def record(config: dict, resume: bool = False, root: Path = None, quiet: bool = 
     say(f"[Record] GPU acceleration: {backend.value} - {info}")
     # extra config key "color": {"mode": "density", "k": K, "log10_range": [lo, hi]} = frames coloured by the k-NN
     # density through the unchanged colour and frame calls of both loops
-    # extra config key "groups": {"every": K, "link": b, "min_members": M} = every K-th frame a line of friends-of-friends
-    # groups in groups.jsonl
-    # extra config key "pairs": {"every": K, "edges": [e0, e1, ...]} = every K-th frame a line of binned pair counts in
-    # pairs.jsonl
+    # extra config keys "diagnostics_every", "groups", "pairs": every K-th frame a line in a side file (LINE_STREAMS)
     try:
         config = apply_color_mode(gpu_sim, config, rec_dir)
-        config = apply_groups(gpu_sim, config, rec_dir)
-        groups = groups_config(config)
-        config = apply_pairs(gpu_sim, config, rec_dir)
-        pairs = pairs_config(config)
-    except Exception:
-        gpu_sim.close()
-        raise
-    direct_zstd = bool(config.get("zstd"))  # extra config key: write .zstd frames, delta payload quantised on the device
-    if direct_zstd and start_frame > 0:
-        # the delta chain continues from what a reader reconstructs for the last frame on disk
-        gpu_sim.frame_set_previous(*load_frame(rec_dir, start_frame - 1))
-    t0 = time.time()
-    every = int(config.get("diagnostics_every") or 0)
-    diag_path = rec_dir / DIAGNOSTICS_FILE
-    last_diag = start_frame - 1
-    # (a leapfrog session's lines say so: their velocities, hence K and E, are synchronized with the positions)
-    diag_extra = {"integrator": integrator} if integrator != "kick_drift" else None
-    if every > 0:
-        if start_frame == 0:  # a run from frame 0 starts the file afresh, with the initial state
-            v0 = gpu_sim.get_velocities()
-            extra = {"abs_momentum": float(np.sum(masses * np.sqrt(np.sum(v0 * v0, axis=1)))), **(diag_extra or {})}
-            first = diagnostics_line(gpu_sim, -1, substeps, dt, extra)
-            _atomically(diag_path, lambda f: f.write(first.encode()))
-        else:
-            truncate_diagnostics(diag_path, start_frame - 1)
+        for stream in LINE_STREAMS:
+            config = stream.apply(gpu_sim, config, rec_dir)
+        direct_zstd = bool(config.get("zstd"))  # extra config key: write .zstd frames, delta payload quantised on the device
+        if direct_zstd and start_frame > 0:
+            # the delta chain continues from what a reader reconstructs for the last frame on disk
+            gpu_sim.frame_set_previous(*load_frame(rec_dir, start_frame - 1))
+        t0 = time.time()
+        lines_due, write_lines = open_lines(gpu_sim, config, rec_dir, start_frame, masses)
 
-    groups_path = rec_dir / GROUPS_FILE
-    last_groups = start_frame - 1
-    if groups:
-        if start_frame == 0:  # a run from frame 0 starts the file afresh
-            _atomically(groups_path, lambda f: f.write(b""))
-        else:
-            truncate_diagnostics(groups_path, start_frame - 1)
+        def write_frame(frame, absolute=False):
+            gpu_sim.compute_colors(15.0)
+            kind = frame_kind(frame, direct_zstd, absolute)
+            a, b = (gpu_sim.frame_keyframe() if kind == "key" else gpu_sim.frame_delta() if kind == "delta"
+                    else (gpu_sim.get_positions(), gpu_sim.get_colors()))
+            write_frame_file(rec_dir, frame, kind, a, b)
 
-    pairs_path = rec_dir / PAIRS_FILE
-    last_pairs = start_frame - 1
-    if pairs:
-        if start_frame == 0:  # a run from frame 0 starts the file afresh
-            _atomically(pairs_path, lambda f: f.write(b""))
-        else:
-            truncate_diagnostics(pairs_path, start_frame - 1)
+        def write_state(frame, compressed=False):
+            x, v = gpu_sim.get_positions_f64(), gpu_sim.get_velocities()
+            _atomically(rec_dir / f"state_{frame:04d}.npz", lambda f: (np.savez_compressed if compressed else np.savez)(
+                f, positions=x, velocities=v, masses=masses))
 
-    def write_diag(frame):  # the synchronous per-frame lines of both loops: diagnostics, then groups, then pairs
-        nonlocal last_diag, last_groups, last_pairs
-        if every > 0 and (frame + 1) % every == 0 and frame > last_diag:
-            append_line(diag_path, diagnostics_line(gpu_sim, frame, substeps, dt, diag_extra))
-            last_diag = frame
-        if groups and (frame + 1) % groups[0] == 0 and frame > last_groups:
-            append_line(groups_path, groups_line(gpu_sim, frame, groups[1], groups[2]))
-            last_groups = frame
-        if pairs and (frame + 1) % pairs[0] == 0 and frame > last_pairs:
-            append_line(pairs_path, pairs_line(gpu_sim, frame, pairs[1]))
-            last_pairs = frame
-
-    def write_frame(frame):
-        gpu_sim.compute_colors(15.0)
-        if direct_zstd:
-            zf, _ = _frame_paths(rec_dir, frame)
-            if frame == 0:
-                p32, c32 = gpu_sim.frame_keyframe()
-                write_bytes_atomic(zf, pack_container(1, p32.tobytes(), c32.tobytes()))
-            else:
-                dp, dc = gpu_sim.frame_delta()
-                write_bytes_atomic(zf, pack_container(2, dp.tobytes(), dc.tobytes()))
-        else:
-            save_frame(rec_dir, frame, gpu_sim.get_positions(), gpu_sim.get_colors())
-
-    def write_state(frame, compressed=False):
-        x, v = gpu_sim.get_positions_f64(), gpu_sim.get_velocities()
-        _atomically(rec_dir / f"state_{frame:04d}.npz",
-                    lambda f: (np.savez_compressed if compressed else np.savez)(f, positions=x, velocities=v, masses=masses))
-
-    def write_keyframe(frame):  # a frame that does not depend on the delta chain (format 1 is legal anywhere)
-        gpu_sim.compute_colors(15.0)
-        zf, _ = _frame_paths(rec_dir, frame)
-        p32, c32 = gpu_sim.frame_keyframe()
-        write_bytes_atomic(zf, pack_container(1, p32.tobytes(), c32.tobytes()))
-
-    if config.get("pipeline"):  # extra config key (metadata.json, only when set): the overlapped loop
+        pipeline = bool(config.get("pipeline"))  # extra config key (metadata.json, only when set): the loop of DESIGN 4.11
+        frame = start_frame - 1
         try:
-            record_pipelined(gpu_sim, rec_dir, start_frame, total_frames, substeps, dt, direct_zstd, every, write_diag,
-                             write_state, also_every=(groups[0] if groups else 0, pairs[0] if pairs else 0))
+            if pipeline:
+                record_pipelined(gpu_sim, rec_dir, start_frame, total_frames, substeps, dt, direct_zstd, lines_due,
+                                 write_lines, write_state)
+            else:
+                for frame in range(start_frame, total_frames):
+                    gpu_sim.step_many(dt, substeps)
+                    write_frame(frame)
+                    _after_frame(rec_dir, frame, write_lines, write_state)
         except KeyboardInterrupt:
-            at = start_frame - 1 + gpu_sim.step_count() // max(substeps, 1)
+            at = device_frame(gpu_sim, start_frame, substeps)
+            if not pipeline:  # (record_pipelined has done the same for its frames in flight)
+                if at >= 0 and at == frame and not _frame_on_disk(rec_dir, at):
+                    # stepped, frame not written - or its write was cut short: frames reach their name only complete
+                    # (_atomically), so a cut-short write left nothing; the device-side delta chain may already have
+                    # moved on, so this frame is written absolute
+                    write_frame(at, absolute=True)
+                _pause(at, write_lines, write_state)
             say(f"\n[Record] Paused at frame {at}; resume with record(config, resume=True)")
-            gpu_sim.close()
             raise
-        say(f"[Record] {total_frames - start_frame} frames in {time.time() - t0:.2f}s -> {rec_dir} (pipelined)")
+        say(f"[Record] {total_frames - start_frame} frames in {time.time() - t0:.2f}s -> {rec_dir}"
+            + (" (pipelined)" if pipeline else ""))
+    finally:
         gpu_sim.close()
-        return rec_dir
-
-    frame = start_frame - 1
-    try:
-        for frame in range(start_frame, total_frames):
-            gpu_sim.step_many(dt, substeps)
-            write_frame(frame)
-            write_diag(frame)  # before the state checkpoint: a resume from it finds every line up to its frame
-            if (frame + 1) % STATE_EVERY == 0:
-                write_state(frame)
-                old = rec_dir / f"state_{frame - STATE_EVERY:04d}.npz"
-                if old.exists():
-                    old.unlink()
-    except KeyboardInterrupt:
-        # reference :916-935: "Paused at frame N" + a state file so that --resume continues from there.  Which
-        # frame the DEVICE stands at is asked of the library (the interrupt is delivered when the step call
-        # returns, before this loop could note anything): the checkpoint must be the state of exactly the last
-        # frame on disk, or a resume would skip or repeat one frame interval.
-        at = start_frame - 1 + gpu_sim.step_count() // max(substeps, 1)
-        if at >= 0:
-            on_disk = any(q.exists() for q in _frame_paths(rec_dir, at))
-            if at == frame and not on_disk:
-                # stepped, frame not written - or its write was cut short: frames reach their name only complete
-                # (_atomically), so a cut-short write left nothing; the device-side delta chain may already have
-                # moved on, so this frame is written absolute
-                write_keyframe(at) if direct_zstd else write_frame(at)
-            write_diag(at)
-            write_state(at, compressed=True)
-        say(f"\n[Record] Paused at frame {at}; resume with record(config, resume=True)")
-        gpu_sim.close()
-        raise
-    say(f"[Record] {total_frames - start_frame} frames in {time.time() - t0:.2f}s -> {rec_dir}")
-    gpu_sim.close()
     return rec_dir
 
 
@@ -795,8 +793,7 @@ def extend_recording(session_name: str, extra_frames: int, root: Path = None, qu
         raise FileNotFoundError(f"[Record] No recording found: {session_name}")
     config = load_metadata(rec_dir)
     config["total_frames"] = int(config["total_frames"]) + int(extra_frames)
-    with open(rec_dir / "metadata.json", "w") as f:
-        json.dump(config, f, indent=2)
+    write_metadata(rec_dir, config)
     config["session_name"] = session_name
     return record(config, resume=True, root=root, quiet=quiet)
 

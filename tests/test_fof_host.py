@@ -231,7 +231,7 @@ def test_groups_file_truncation_on_resume(tmp_path):
 
 
 def test_pipelined_loop_finishes_the_frame_before_a_groups_line(tmp_path):
-    """the second period of record_pipelined: the writer is called where a groups line is due, after the frame's file"""
+    """a period of record_pipelined's predicate: the writer is called where a groups line is due, after the frame's file"""
     from tools import record as rec
     import test_record_pipeline_host as tp
     d = rec.get_recording_dir("piped", tmp_path)
@@ -241,5 +241,6 @@ def test_pipelined_loop_finishes_the_frame_before_a_groups_line(tmp_path):
     def write_lines(frame):
         assert any(q.exists() for q in rec._frame_paths(d, frame)) and not sim.frames_pending()
         seen.append(frame)
-    rec.record_pipelined(sim, d, 0, 7, 2, 0.01, False, 0, write_lines, lambda frame, compressed=False: None, also_every=3)
+    rec.record_pipelined(sim, d, 0, 7, 2, 0.01, False, lambda frame: rec.line_due(frame, 3), write_lines,
+                         lambda frame, compressed=False: None)
     assert seen == [2, 5] and not sim.slots and rec.get_completed_frames(d) == 7

@@ -248,8 +248,8 @@ def test_pairs_file_truncation_on_resume(tmp_path):
 
 
 def test_pipelined_loop_finishes_the_frame_before_a_line_of_either_period(tmp_path):
-    """record_pipelined with two further periods (groups and pairs): the writer is called where either is due, after the
-    frame's file; a single number still works"""
+    """record_pipelined with a predicate over two periods (groups and pairs): the writer is called where either is due,
+    after the frame's file; one period alone and none work too"""
     from tools import record as rec
     import test_record_pipeline_host as tp
     for also, want in (((3, 2), [1, 2, 3, 5]), ((0, 2), [1, 3, 5]), (3, [2, 5]), ((0, 0), [])):
@@ -260,5 +260,7 @@ def test_pipelined_loop_finishes_the_frame_before_a_line_of_either_period(tmp_pa
         def write_lines(frame):
             assert any(q.exists() for q in rec._frame_paths(d, frame)) and not sim.frames_pending()
             seen.append(frame)
-        rec.record_pipelined(sim, d, 0, 7, 2, 0.01, False, 0, write_lines, lambda frame, compressed=False: None, also_every=also)
+        periods = also if isinstance(also, tuple) else (also,)
+        rec.record_pipelined(sim, d, 0, 7, 2, 0.01, False, lambda frame: any(rec.line_due(frame, k) for k in periods),
+                             write_lines, lambda frame, compressed=False: None)
         assert seen == want and not sim.slots and rec.get_completed_frames(d) == 7
