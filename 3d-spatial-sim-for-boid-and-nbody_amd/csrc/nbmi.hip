@@ -791,7 +791,7 @@ template <int TILE>
 __global__ __launch_bounds__(kBlock) void k_emit_tile(const int32_t *__restrict__ delta, const int32_t *__restrict__ PexL,
                                                       const int32_t *__restrict__ subPex, const double4 *__restrict__ S,
                                                       const Moment *__restrict__ T, const float4 *__restrict__ posm_s,
-                                                      const double4 *__restrict__ p64_s, const uint64_t *__restrict__ hi_s,
+                                                      const uint64_t *__restrict__ hi_s,
                                                       const uint64_t *__restrict__ lo_s, int64_t n, int64_t capacity,
                                                       double eps, double inv_theta2, Node *__restrict__ nodes,
                                                       Node64 *__restrict__ nodes64, uint8_t *__restrict__ node_level,
@@ -878,13 +878,9 @@ __global__ __launch_bounds__(kBlock) void k_emit_tile(const int32_t *__restrict_
                 lf.s2t = 0.0f;
                 lf.next_off = (unsigned)(idx + 1 + link_base) * kNodeBytes;
                 nodes[idx] = lf;
-                if (diag64) {  // the body as the float64 state has it (p64_s holds the same values where it exists)
-                    if (p64_s) {
-                        diag64[idx] = p64_s[r];
-                    } else {
-                        const uint32_t j = perm[r];
-                        diag64[idx] = make_double4(cur.x[j], cur.y[j], cur.z[j], G * cur.m[j]);
-                    }
+                if (diag64) {  // the body as the float64 state has it
+                    const uint32_t j = perm[r];
+                    diag64[idx] = make_double4(cur.x[j], cur.y[j], cur.z[j], G * cur.m[j]);
                 }
                 if (nodesd) {  // the body as the float64 state has it (nearly sequential: the state is in last step's key order)
                     const uint32_t j = perm[r];
@@ -989,29 +985,6 @@ __global__ __launch_bounds__(kBlock) void k_max_level(const int32_t *__restrict_
 }
 
 // ---------------------------------------------------------------------------------------
-// K8b: child table (stack-walk prototype only).  Row i of an internal cell holds the byte offsets of its (up to
-// 8) children in pre-order (0 = no more children; offset 0 is the root and never a child).  One thread per node
-// row, after all nodes exist: first child = next row, siblings via the skip links.
-// ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void k_child_table(const Node *__restrict__ nodes, const TreeInfo *__restrict__ info,
-                                                        int64_t capacity, uint32_t *__restrict__ child_tab) {
-    const int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (info->error || idx >= info->num_nodes || idx >= capacity) return;
-    if (__float_as_int(nodes[idx].s2t) == 0) return;  // a leaf
-    const unsigned end = nodes[idx].next_off;
-    unsigned c = (unsigned)(idx + 1) * kNodeBytes;
-    uint32_t t[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-        t[k] = c < end ? c : 0u;
-        if (c < end) c = reinterpret_cast<const Node *>(reinterpret_cast<const char *>(nodes) + c)->next_off;
-    }
-    uint4 *row = reinterpret_cast<uint4 *>(child_tab + 8 * idx);
-    row[0] = make_uint4(t[0], t[1], t[2], t[3]);
-    row[1] = make_uint4(t[4], t[5], t[6], t[7]);
-}
-
-// ---------------------------------------------------------------------------------------
 // K9: the walk.  One wave64 = 64 consecutive sorted bodies; wave-uniform cursor over the
 // pre-order node array (scalar loads of the 24-byte record); per lane the reference's test
 // (simulation.py:245-274):
@@ -1047,11 +1020,8 @@ struct WalkParams {
     int pair;       // one-wave walk with two cursors (the two halves of the array)
     double dt, damping;
     int curbuf;  // which of WalkTable.buf holds the current state
-    int acc64;   // measurement (counted walk only, NBMI_ACC64=1): every visit's contribution summed in float64
     int force_prec;  // 0 = per wave by local density (see k_walk), 1 = fp32 pair forces everywhere, 2 = float64 everywhere
     float prec_tau;  // force_prec 0: a wave takes float64 when G rho dt^2 of its bodies exceeds this
-    int prec;    // measurement (k_walk_diag, NBMI_PREC=<mode>): which visits compute their force in which arithmetic
-    float near2; // k_walk_diag: "near" visits have fp32 dist_sq below this
 };
 
 // Per-handle constants the walk needs only rarely (float64 re-decision) or only at its end (the state
@@ -1368,7 +1338,7 @@ __device__ __forceinline__ void walk_pair_asm(const Node *nodes, unsigned &off1,
 }
 
 // ---------------------------------------------------------------------------------------
-// [r3] The float64 visit.  Why it exists (scripts/gpu_prec_diag.py, profiles/r03_precision_modes.jsonl): at 1 M
+// [r3] The float64 visit.  Why it exists (scripts/experiments/walk_prec_modes.patch, profiles/r03_precision/): at 1 M
 // bodies x 100 steps the position error against the float64 reference is made by fp32 pair arithmetic, and not by
 // its random roundings but by its SYSTEMATIC ones - G m rounded to fp32 (alone: max 6.6e-5 of the largest
 // coordinate), v_rsq_f32's one-ulp error pattern (alone: 9.5e-5), fp32-rounded coordinates of near pairs - which act
@@ -1852,7 +1822,6 @@ __global__ __launch_bounds__(kBlock) void k_walk(const Node *__restrict__ nodes,
     unsigned resume = C.resume;
     float ax = 0.f, ay = 0.f, az = 0.f;  // fp32 accumulators of the loops ...
     double sx = 0.0, sy = 0.0, sz = 0.0;  // ... emptied into these every few trips (two-level sums, NBMI_FLUSH)
-    double acc64x = 0.0, acc64y = 0.0, acc64z = 0.0;
 
     const bool use64 = !kCount && kIntegrate && wave_uses_f64(tab, info_in, P, rank);
     // (the clock is read here, behind the prologue's loads: the compiler treats the read as a possible store and
@@ -1917,7 +1886,6 @@ __global__ __launch_bounds__(kBlock) void k_walk(const Node *__restrict__ nodes,
         }
     } else {
         unsigned long long wv = 0, lv = 0, la = 0, jm = 0, bd = 0;
-        double dax = 0.0, day = 0.0, daz = 0.0;
         unsigned long long wm[4] = {0, 0, 0, 0};
         int wbase[4] = {-1000, -1000, -1000, -1000};
         unsigned off = 0u;
@@ -1925,13 +1893,7 @@ __global__ __launch_bounds__(kBlock) void k_walk(const Node *__restrict__ nodes,
         while (off < nn) {
             bool a_, f_, j_, b_;
             const int c_old = (int)(off / kNodeBytes);
-            if (kCount && P.acc64) {
-                float tx = 0.f, ty = 0.f, tz = 0.f;
-                off = visit<kGuard>(nodes, off, C.px, C.py, C.pz, C.b64, P, C.band2, resume, tx, ty, tz, a_, f_, j_, b_);
-                dax += (double)tx; day += (double)ty; daz += (double)tz;
-            } else {
-                off = visit<kGuard>(nodes, off, C.px, C.py, C.pz, C.b64, P, C.band2, resume, ax, ay, az, a_, f_, j_, b_);
-            }
+            off = visit<kGuard>(nodes, off, C.px, C.py, C.pz, C.b64, P, C.band2, resume, ax, ay, az, a_, f_, j_, b_);
             if (kGuard && !kCount) flush12(since_flush, ax, ay, az, sx, sy, sz);
             if (kCount) {
                 wv += 1; lv += a_ ? 1 : 0; la += f_ ? 1 : 0; jm += j_ ? 1 : 0; bd += b_ ? 1 : 0;
@@ -1941,7 +1903,6 @@ __global__ __launch_bounds__(kBlock) void k_walk(const Node *__restrict__ nodes,
                 }
             }
         }
-        if (kCount && P.acc64) { acc64x = dax; acc64y = day; acc64z = daz; }
         if (kCount) {
             // wave_visits counted once per wave (lane 0), lane counters summed over lanes
             if (lane == 0) {
@@ -1963,8 +1924,7 @@ __global__ __launch_bounds__(kBlock) void k_walk(const Node *__restrict__ nodes,
             tab->wave_cycles[4 * lb + (threadIdx.x >> 6)] = (unsigned)(dtc > 0xffffffffull ? 0xffffffffull : dtc);
         }
     } else if (valid) {
-        const bool d64 = kCount && P.acc64;
-        store_acc(acc_out, tab->buf[P.curbuf], j, d64 ? acc64x : (double)ax, d64 ? acc64y : (double)ay, d64 ? acc64z : (double)az);
+        store_acc(acc_out, tab->buf[P.curbuf], j, (double)ax, (double)ay, (double)az);
     }
 }
 
@@ -2037,221 +1997,6 @@ __global__ __launch_bounds__(64 * K) void k_walk_split(const Node *__restrict__ 
         sx += part[k][0][lane]; sy += part[k][1][lane]; sz += part[k][2][lane];
     }
     publish_maxabs(tab, valid ? integrate<kLeap>(tab, j, rank, sx, sy, sz, P, frozen) : 0.0);
-}
-
-// ---------------------------------------------------------------------------------------
-// Stack walk (NBMI_WALK_STACK=1, prototype): the same 64 bodies per wave and the same per-lane opening test,
-// but the wave keeps a stack of (cell, mask of the lanes that opened it) and expands a cell by visiting all
-// its children back to back: their offsets come from ONE load of the child table, their records are requested
-// together, the lanes taking part are a scalar mask (no per-visit `resume` compare / update) and there is no
-// skip / descend decision per visit.  Accepted (body, node) sets are unchanged; sums associate differently.
-// ---------------------------------------------------------------------------------------
-constexpr int kStackCap = 320;  // > 7 pending siblings on each of the 43 possible levels
-template <bool kLeap = false>
-__global__ __launch_bounds__(kBlock) void k_walk_stack(const Node *__restrict__ nodes, const uint32_t *__restrict__ child_tab,
-                                                       const WalkTable *tab, const TreeInfo *info_in,
-                                                       const float4 *__restrict__ posm_s, const uint32_t *__restrict__ perm,
-                                                       WalkParams P) {
-    __shared__ unsigned st_off[kBlock / 64][kStackCap];
-    __shared__ unsigned long long st_mask[kBlock / 64][kStackCap];
-    const int lb = logical_block(blockIdx.x, gridDim.x, P.xcd_chunk);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int64_t rank = P.rank_begin + (int64_t)lb * blockDim.x + threadIdx.x;
-    const WalkCtx C = lane_prologue(nodes, posm_s, perm, rank, P.rank_end, info_in, tab, P.curbuf);
-    float ax = 0.f, ay = 0.f, az = 0.f;
-    int sp = 0;
-    const unsigned long long lane_bit = 1ull << lane;
-
-    // one node for the lanes in M: force for the lanes that take it, (offset, openers) pushed if anybody opens it
-    auto visit = [&](unsigned off, unsigned long long M) {
-        const Node nd = *reinterpret_cast<const Node *>(reinterpret_cast<const char *>(nodes) + off);
-        const float dx = nd.cx - C.px, dy = nd.cy - C.py, dz = nd.cz - C.pz;
-        const float d2 = fmaf(dz, dz, fmaf(dy, dy, fmaf(dx, dx, P.eps2)));
-        const bool in = (M & lane_bit) != 0ull;
-        const bool geom = opening(d2, nd.s2t, C.band2, in, off / kNodeBytes, C.b64).geom;
-        const bool take = in && geom;
-        const float inv = __builtin_amdgcn_rsqf(d2);
-        const float f = take ? (nd.gm * inv) * (inv * inv) : 0.f;
-        ax = fmaf(dx, f, ax); ay = fmaf(dy, f, ay); az = fmaf(dz, f, az);
-        const unsigned long long openers = __builtin_amdgcn_ballot_w64(in && !geom);
-        if (openers && sp < kStackCap) {
-            if (lane == 0) { st_off[w][sp] = off; st_mask[w][sp] = openers; }
-            sp++;
-        }
-    };
-
-    if (!C.frozen) {
-        visit(0u, __builtin_amdgcn_ballot_w64(C.valid));
-        while (sp > 0) {
-            sp--;
-            const unsigned cell = __builtin_amdgcn_readfirstlane(st_off[w][sp]);
-            const unsigned mlo = __builtin_amdgcn_readfirstlane((unsigned)st_mask[w][sp]);
-            const unsigned mhi = __builtin_amdgcn_readfirstlane((unsigned)(st_mask[w][sp] >> 32));
-            const unsigned long long M = ((unsigned long long)mhi << 32) | mlo;
-            const uint4 *row = reinterpret_cast<const uint4 *>(child_tab + 8 * (size_t)(cell / kNodeBytes));
-            const uint4 t0 = row[0], t1 = row[1];
-            const unsigned ch[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
-#pragma unroll
-            for (int k = 0; k < 8; k++) {
-                const unsigned c = __builtin_amdgcn_readfirstlane(ch[k]);
-                if (c == 0u) break;
-                visit(c, M);
-            }
-        }
-    }
-    if (!C.valid) return;
-    integrate<kLeap>(tab, C.j, rank, ax, ay, az, P, C.frozen);
-}
-
-// ---------------------------------------------------------------------------------------
-// Measurement only (NBMI_WALK_LANE=1): every lane walks on its own (own cursor, vector loads of the node
-// record).  No lane ever idles for another's descent, but every visit is a 64-address gather.  Same
-// accepted sets; kept as the yardstick for what a divergent visit costs on this chip.
-// ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void k_walk_lane(const Node *__restrict__ nodes, const WalkTable *tab,
-                                                      const TreeInfo *info_in, const float4 *__restrict__ posm_s,
-                                                      const uint32_t *__restrict__ perm, WalkParams P) {
-    const int lb = logical_block(blockIdx.x, gridDim.x, P.xcd_chunk);
-    const int64_t rank = P.rank_begin + (int64_t)lb * blockDim.x + threadIdx.x;
-    const WalkCtx C = lane_prologue(nodes, posm_s, perm, rank, P.rank_end, info_in, tab, P.curbuf);
-    if (!C.valid) return;
-    const unsigned nn = C.rows * kNodeBytes;
-    float ax = 0.f, ay = 0.f, az = 0.f;
-    unsigned off = 0u;
-    while (off < nn) {
-        const char *q = reinterpret_cast<const char *>(nodes) + off;
-        const float2 a0 = *reinterpret_cast<const float2 *>(q), a1 = *reinterpret_cast<const float2 *>(q + 8);
-        const float2 b = *reinterpret_cast<const float2 *>(q + 16);
-        const float4 a = make_float4(a0.x, a0.y, a1.x, a1.y);
-        const float dx = a.x - C.px, dy = a.y - C.py, dz = a.z - C.pz;
-        const float d2 = fmaf(dz, dz, fmaf(dy, dy, fmaf(dx, dx, P.eps2)));
-        const bool take = opening(d2, b.x, C.band2, true, off / kNodeBytes, C.b64).geom;
-        const float inv = __builtin_amdgcn_rsqf(d2);
-        const float f = take ? (a.w * inv) * (inv * inv) : 0.f;
-        ax = fmaf(dx, f, ax); ay = fmaf(dy, f, ay); az = fmaf(dz, f, az);
-        off = take ? __float_as_uint(b.y) : off + kNodeBytes;
-    }
-    integrate<false>(tab, C.j, rank, ax, ay, az, P, C.frozen);
-}
-
-// ---------------------------------------------------------------------------------------
-// Measurement only (NBMI_PREC=<mode>): the lock-step walk in C++ with the product walk's opening decisions
-// (fp32 test, uncertainty band, float64 re-decision - the accepted sets are the product's) and a selectable
-// arithmetic for the force of an accepted visit.  Answers "which rounding makes the 100-step error at 1 M
-// bodies" (scripts/gpu_prec_diag.py).  diag64 = {cx, cy, cz, G m} of EVERY node in float64.
-//   1  fp32 pair arithmetic on fp32-rounded coordinates, every contribution added to float64 sums (= the product's
-//      arithmetic with ideal accumulation)
-//   2  float64 throughout
-//   3  float64 for leaves, 1 otherwise          4  float64 where fp32 dist_sq < near2, 1 otherwise
-//   5  two-word coordinates (hi + lo floats of body and node), fp32 arithmetic
-//   6  exact float64 differences rounded to fp32, then fp32 arithmetic (coordinate rounding removed altogether)
-//   7  as 1 with fp32 running sums (no float64 accumulation at all)
-//   8  as 6, one Newton step on the reciprocal square root
-//   9  as 2 but G m rounded to fp32
-//   10 ... 14  as 2 with ONE quantity rounded to fp32: the coordinate differences / dist_sq / the reciprocal square
-//      root (v_rsq_f32) / [13: v_rsq_f32 seed + one Newton step in float64 - the candidate product form] / each
-//      contribution before it is added
-//   15 fp32 with the systematic errors removed (exact-residual Newton step on v_rsq_f32, G m as two floats), float64
-//      accumulation;  16 the same on exact coordinate differences rounded to fp32;  17 = 16 with two-level fp32 sums
-//   20 float64 (as 13) for the bodies inside the cylindrical radius NBMI_PREC_NEAR (length units), 1 for the others
-// ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void k_walk_diag(const Node *__restrict__ nodes, const double4 *__restrict__ diag64,
-                                                      const WalkTable *tab, const TreeInfo *info_in,
-                                                      const float4 *__restrict__ posm_s, const uint32_t *__restrict__ perm,
-                                                      WalkParams P) {
-    const int64_t rank = P.rank_begin + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const WalkCtx C = lane_prologue(nodes, posm_s, perm, rank, P.rank_end, info_in, tab, P.curbuf);
-    const Lane64 L = lane_f64(C);
-    const unsigned nn = C.rows * kNodeBytes;
-    const float px = C.px, py = C.py, pz = C.pz;
-    const double qx = L.qx, qy = L.qy, qz = L.qz;
-    const float plx = (float)(qx - (double)px), ply = (float)(qy - (double)py), plz = (float)(qz - (double)pz);
-    unsigned resume = C.resume;
-    double sx = 0.0, sy = 0.0, sz = 0.0;
-    float fx = 0.f, fy = 0.f, fz = 0.f;
-    int nflush = 0;
-    const int mode = P.prec;
-    const double eps2d = L.eps2;
-    unsigned off = 0u;
-    while (off < nn) {
-        off = __builtin_amdgcn_readfirstlane(off);
-        const Node nd = *reinterpret_cast<const Node *>(reinterpret_cast<const char *>(nodes) + off);
-        const float dx = nd.cx - px, dy = nd.cy - py, dz = nd.cz - pz;
-        const float dist_sq = fmaf(dz, dz, fmaf(dy, dy, fmaf(dx, dx, P.eps2)));
-        const bool active = resume <= off;
-        const bool geom = opening(dist_sq, nd.s2t, C.band2, active, off / kNodeBytes, C.b64).geom;
-        bool take;
-        const unsigned next = advance<kNodeBytes>(active, geom, off, nd.next_off, resume, take);
-        if (take) {
-            const bool leaf = __float_as_int(nd.s2t) == 0;
-            const double rc2 = (double)P.near2;  // modes >= 20: bodies inside this cylindrical radius^2 (x, z) take float64
-            const bool core = mode >= 20 && (qx * qx + qz * qz) < rc2;
-            const bool use64 = mode == 2 || (mode >= 9 && mode <= 14) || (mode == 3 && leaf) || (mode == 4 && dist_sq < P.near2) || core;
-            if (use64) {
-                const double4 c = diag64[off / kNodeBytes];
-                double ex = c.x - qx, ey = c.y - qy, ez = c.z - qz;
-                if (mode == 10) { ex = (double)(float)ex; ey = (double)(float)ey; ez = (double)(float)ez; }
-                double d2 = ex * ex + ey * ey + ez * ez + eps2d;
-                if (mode == 11) d2 = (double)(float)d2;
-                double inv;
-                if (mode == 12) {
-                    inv = (double)__builtin_amdgcn_rsqf((float)d2);
-                } else if (mode == 13 || mode >= 20) {  // fp32 seed + one Newton step in float64
-                    const double y0 = (double)__builtin_amdgcn_rsqf((float)d2);
-                    const double e = fma(-d2 * y0, y0, 1.0);
-                    inv = fma(0.5 * y0, e, y0);
-                } else {
-                    inv = 1.0 / sqrt(d2);
-                }
-                const double gm = mode == 9 ? (double)nd.gm : c.w;
-                const double f = gm * inv * inv * inv;
-                if (mode == 14) {
-                    sx += (double)(float)(ex * f); sy += (double)(float)(ey * f); sz += (double)(float)(ez * f);
-                } else {
-                    sx += ex * f; sy += ey * f; sz += ez * f;
-                }
-            } else {
-                float ex = dx, ey = dy, ez = dz;
-                if (mode == 5) {
-                    const double4 c = diag64[off / kNodeBytes];
-                    const float clx = (float)(c.x - (double)nd.cx), cly = (float)(c.y - (double)nd.cy), clz = (float)(c.z - (double)nd.cz);
-                    ex = dx + (clx - plx); ey = dy + (cly - ply); ez = dz + (clz - plz);
-                } else if (mode == 6 || mode == 8 || mode == 16 || mode == 17) {
-                    const double4 c = diag64[off / kNodeBytes];
-                    ex = (float)(c.x - qx); ey = (float)(c.y - qy); ez = (float)(c.z - qz);
-                }
-                const float d2 = (mode == 5 || mode == 6 || mode == 8 || mode == 16 || mode == 17) ? fmaf(ez, ez, fmaf(ey, ey, fmaf(ex, ex, P.eps2))) : dist_sq;
-                float inv = __builtin_amdgcn_rsqf(d2);
-                if (mode == 8) inv = inv * fmaf(-0.5f * d2 * inv, inv, 1.5f);
-                float f;
-                if (mode >= 15 && mode <= 17) {
-                    // "enhanced fp32": the SYSTEMATIC errors removed (one Newton step with the exact residual, G m as two
-                    // floats), the random roundings of fp32 kept
-                    const float t = d2 * inv, tl = fmaf(d2, inv, -t);
-                    float e = fmaf(-t, inv, 1.0f);
-                    e = fmaf(-tl, inv, e);
-                    inv = fmaf(0.5f * inv, e, inv);
-                    const double4 c = diag64[off / kNodeBytes];
-                    const float gml = (float)(c.w - (double)nd.gm);
-                    const float g3 = (inv * inv) * inv;
-                    f = fmaf(gml, g3, nd.gm * g3);
-                } else {
-                    f = (nd.gm * inv) * (inv * inv);
-                }
-                if (mode == 7 || mode == 17) {
-                    fx = fmaf(ex, f, fx); fy = fmaf(ey, f, fy); fz = fmaf(ez, f, fz);
-                    if (mode == 17 && (++nflush & 15) == 0) {  // two-level sums like the product loop
-                        sx += (double)fx; sy += (double)fy; sz += (double)fz;
-                        fx = fy = fz = 0.f;
-                    }
-                } else {
-                    sx += (double)(ex * f); sy += (double)(ey * f); sz += (double)(ez * f);
-                }
-            }
-        }
-        off = next;
-    }
-    publish_maxabs(tab, C.valid ? integrate<false>(tab, C.j, rank, sx + (double)fx, sy + (double)fy, sz + (double)fz, P, C.frozen) : 0.0);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -4134,14 +3879,13 @@ __global__ __launch_bounds__(kBlock) void k_fof_init(const Node *__restrict__ no
 // The pair search: one wave per 64 key-adjacent bodies.  Pairs inside the wave are tested directly (the bodies go round
 // by readlane, each pair once: the higher lane tests the lower); every other pair is found by the walk against the
 // fixed bound b2 - a cell is pruned only if knn_lower EXCEEDS b2, so a pair AT the linking length is always reached.
-//   half = 1  the cursor starts at the leaf of the wave's first body and the wave's own ranks are skipped: the wave
-//             sees exactly the bodies of a higher rank, every pair of two waves is found once, by the lower wave
-//   half = 0  the whole tree (every such pair twice; the measurement's other side)
+// The cursor starts at the leaf of the wave's first body and the wave's own ranks are skipped: the wave sees exactly
+// the bodies of a higher rank, every pair of two waves is found once, by the lower wave.
 // Every link found goes to fof_link_lanes, which unites the two sets.  evals (may be null) counts the distances evaluated.
 __global__ __launch_bounds__(kFofBlock) void k_fof_link(const Node *__restrict__ nodes, const double4 *__restrict__ rows,
                                                         const int32_t *__restrict__ node_ref, const TreeInfo *__restrict__ info,
                                                         const uint32_t *__restrict__ perm, Bodies cur, int64_t n, double b2,
-                                                        int half, const uint32_t *__restrict__ wleaf, int32_t *parent,
+                                                        const uint32_t *__restrict__ wleaf, int32_t *parent,
                                                         unsigned long long *__restrict__ evals_out) {
     if (info->error != 0 || info->sticky_error != 0) return;
     const int lane = threadIdx.x;
@@ -4160,8 +3904,8 @@ __global__ __launch_bounds__(kFofBlock) void k_fof_link(const Node *__restrict__
             fof_link_lanes(parent, d2 <= b2, mine, (int)(w0 + i));
         }
     }
-    const unsigned start = half ? __builtin_amdgcn_readfirstlane(wleaf[blockIdx.x]) * kNodeBytes : 0u;
-    query_walk(nodes, rows, node_ref, start, nn, valid, qx, qy, qz, half ? (int64_t)0 : w0, w0 + kFofBlock, b2, evals,
+    const unsigned start = __builtin_amdgcn_readfirstlane(wleaf[blockIdx.x]) * kNodeBytes;
+    query_walk(nodes, rows, node_ref, start, nn, valid, qx, qy, qz, (int64_t)0, w0 + kFofBlock, b2, evals,
                [&](double d2, const double4 &, int64_t r) { fof_link_lanes(parent, d2 <= b2, mine, (int)r); });
     if (evals_out) {
 #pragma unroll
@@ -4487,7 +4231,7 @@ __device__ __forceinline__ int pair_bin(const double *__restrict__ E, int nb, do
     }
     return pos;
 }
-// One wave per 64 key-adjacent bodies, as k_fof_link with half = 1: pairs inside the wave directly (the higher lane tests
+// One wave per 64 key-adjacent bodies, as k_fof_link: pairs inside the wave directly (the higher lane tests
 // the lower), every other pair by the walk that starts at the wave's own first leaf and skips the leaves of the ranks
 // below w0 + 64 - the wave sees exactly the bodies of a higher rank, every pair of two waves once.  At an internal cell an
 // active lane, in this order:
@@ -4598,12 +4342,11 @@ struct nbmi_sim {
     int32_t *delta = nullptr, *Pex = nullptr;  // Pex: exclusive prefix of the cell counts INSIDE a sub-tile (PexL)
     int32_t *subPex = nullptr, *sub_cnt = nullptr;  // per sub-tile: exclusive prefix / total of the cell counts
     float4 *posm_s = nullptr;
-    double4 *p64_s = nullptr;  // float64 twin of posm_s: owner mode (bounding boxes) and NBMI_PREC only
+    double4 *p64_s = nullptr;  // float64 twin of posm_s: owner mode only (bounding boxes)
     double4 *S = nullptr;      // in-sub-tile exclusive prefix of {G m, G m x, G m y, G m z}
     double4 *sub_tot = nullptr;  // per sub-tile totals of the same
     Moment *T = nullptr;         // per sub-tile exclusive prefix, double-double
     Node *nodes = nullptr;
-    uint32_t *child_tab = nullptr;  // 8 child offsets per node row (stack walk)
     Node64 *nodes64 = nullptr;  // float64 twin rows of the internal cells (near-tie re-decision)
     NodeD *nodesd = nullptr;    // float64 node records of every node (waves that compute forces in float64)
     int force_prec = 0;         // 0 = per wave by local density, 1 = fp32 everywhere, 2 = float64 everywhere (NBMI_FORCE_PREC)
@@ -4699,11 +4442,6 @@ struct nbmi_sim {
                                 // integrating walk, dropped by anything else that writes positions); NBMI_FUSE_MAXABS=0: never
     bool fuse_maxabs = true;
     bool hilbert = true;  // sort keys relabelled along the Hilbert curve (k_keys); NBMI_HILBERT=0: plain octant digits
-    int walk_stack = 0;  // prototype: stack walk with batched children (NBMI_WALK_STACK=1)
-    int walk_lane = 0;  // measurement: per-lane walk (NBMI_WALK_LANE=1)
-    int prec = 0;       // measurement: k_walk_diag arithmetic mode (NBMI_PREC), 0 = product walk
-    double prec_near = 4.0;  // NBMI_PREC_NEAR: "near" = closer than this many softening lengths
-    double4 *diag64 = nullptr;  // float64 {cx, cy, cz, G m} of every node (only with NBMI_PREC)
     // conservation diagnostics (nbmi_diagnostics), allocated by the first call that needs them; no step touches them
     double *diag_phi = nullptr;       // [n] phi per state row
     int32_t *diag_cnt = nullptr;      // [n] applied potential terms per state row
@@ -4723,7 +4461,6 @@ struct nbmi_sim {
     uint32_t *fof_wleaf = nullptr;
     unsigned long long *fof_counters = nullptr;  // [0] distances evaluated, [1] roots
     bool fof_ready = false, fof_cat_ready = false;  // every array of the query / of the catalogue is there (set after the last allocation)
-    bool fof_half = true;  // the pair search starts at the wave's own first leaf (NBMI_FOF_HALF=0: at the root; measurement)
     // its catalogue (nbmi_fof_catalogue), allocated by the first call: 24 bytes per body (sorted roots, ranks in and
     // out, segment heads, row of a root, head of a row), the sort's temp buffer, 304 bytes per chunk of 256 bodies and
     // 268 bytes per catalogue row (a power of two of rows, regrown - the smaller arrays freed - when a call needs more)
@@ -4758,7 +4495,6 @@ struct nbmi_sim {
     // mode's builds
     int multipole = NBMI_MULTIPOLE_MONOPOLE;
     int multipole_env = NBMI_MULTIPOLE_MONOPOLE;  // NBMI_MULTIPOLE: the initial value where the handle allows it
-    bool acc64_env = false;  // NBMI_ACC64 as it stood at creation: what nbmi_set_multipole's refusal goes by
     NodeQ *nodesq = nullptr;
     double *quad_work = nullptr;
     double4 *quad_pot = nullptr;
@@ -4879,8 +4615,8 @@ enum class BuildTiming { kNone, kAll, kCaller };
 struct BuildRequest {
     BuildTiming timing = BuildTiming::kNone;
     bool aux = true;  // also write node_ref / node_level (cell queries, owner-mode kernels)
-    // where the float64 {cx, cy, cz, G m} row of every node goes (nbmi_diagnostics' tree potential; null: s->diag64,
-    // which is null outside the NBMI_PREC measurement mode - a step never writes it)
+    // where the float64 {cx, cy, cz, G m} row of every node goes (nbmi_diagnostics' tree potential; null: none, a step
+    // never writes them)
     double4 *diag_rows = nullptr;
     double step_dt = 0.0;
 };
@@ -5023,13 +4759,11 @@ int enqueue_global_tree(nbmi_sim *s, bool aux = true, double4 *diag = nullptr) {
     with_int<kEmitTileSmall, kEmitTile>(n <= kEmitSmallBodies ? kEmitTileSmall : kEmitTile, [&](auto tile) {
         constexpr int kTile = decltype(tile)::value;
         k_emit_tile<kTile><<<(int)((n + kTile - 1) / kTile), kBlock, 0, st>>>(
-            s->delta, s->Pex, s->subPex, s->S, s->T, s->t_posm, s->p64_s, s->t_hi, s->lean_build ? nullptr : s->t_lo, n,
+            s->delta, s->Pex, s->subPex, s->S, s->T, s->t_posm, s->t_hi, s->lean_build ? nullptr : s->t_lo, n,
             s->own_node_rows, s->softening, inv_theta2, s->nodes + ob, s->nodes64 + ob, aux ? s->node_level : nullptr,
-            aux ? s->node_ref : nullptr, diag ? diag : s->diag64, s->force_prec != 1 && s->nodesd ? s->nodesd + ob : nullptr,
+            aux ? s->node_ref : nullptr, diag, s->force_prec != 1 && s->nodesd ? s->nodesd + ob : nullptr,
             s->buf[s->curbuf], s->perm, s->G, s->info, s->hilbert ? 1 : 0, ob);
     });
-    if (s->walk_stack)
-        k_child_table<<<nblocks(s->own_node_rows), kBlock, 0, st>>>(s->nodes, s->info, s->own_node_rows, s->child_tab);
     if (quad && n > 0) {
         // second moments, level by level from the deepest cells up (k_quad_level).  The host does not know the depth:
         // every level is launched, and a launch above the deepest one returns at once
@@ -5106,25 +4840,12 @@ int enqueue_walk(nbmi_sim *s, bool integrate, double dt, double *acc_out, int le
     P.pair = s->walk_pair >= 0 ? s->walk_pair : (s->nt >= kHomeSplitBodies ? 2 : 1);
     if (s->owner && s->world > 1 && P.pair == 1) P.pair = 2;  // (the middle of the array may lie in the unused rows in front of the pieces)
     P.curbuf = s->curbuf;
-    P.acc64 = getenv("NBMI_ACC64") ? atoi(getenv("NBMI_ACC64")) : 0;
-    if (integrate && leap && (s->prec || s->walk_lane || P.acc64)) {
-        nbmi::set_error("nbmi_step: the leapfrog integrator is not available with the measurement-only walks (NBMI_PREC, "
-                        "NBMI_WALK_LANE, NBMI_ACC64)");
-        return NBMI_ERR_ARG;
-    }
     P.balance = 0;
     P.force_prec = s->nodesd ? s->force_prec : 1;
     P.prec_tau = (float)s->prec_tau;
-    P.prec = s->prec;
-    P.near2 = s->prec >= 20 ? (float)(s->prec_near * s->prec_near) : (float)(s->prec_near * s->prec_near * s->softening * s->softening);
-    if (integrate && s->prec && s->diag64 && !guard && !s->owner) {  // measurement only, see k_walk_diag
-        k_walk_diag<<<(int)((cntr + kBlock - 1) / kBlock), kBlock, 0, st>>>(s->nodes, s->diag64, tab, s->info, s->posm_s, s->perm, P);
-        NBMI_HIP_CHECK(hipGetLastError());
-        return 0;
-    }
 
     if (s->multipole == NBMI_MULTIPOLE_QUADRUPOLE) {  // one one-wave walk at every size
-        if (s->owner || s->prec || s->walk_lane || s->walk_stack || !s->nodesq) {
+        if (s->owner || !s->nodesq) {
             nbmi::set_error("internal: quadrupole walk on a handle that does not support it");
             return NBMI_ERR_ARG;
         }
@@ -5158,19 +4879,6 @@ int enqueue_walk(nbmi_sim *s, bool integrate, double dt, double *acc_out, int le
     }
     const int wb = s->walk_block;
     const int gb = (int)((cntr + wb - 1) / wb);
-    if (integrate && s->walk_stack && !guard && !s->owner) {
-        with_bool(leap != 0, [&](auto l) {
-            k_walk_stack<decltype(l)::value><<<(int)((cntr + kBlock - 1) / kBlock), kBlock, 0, st>>>(s->nodes, s->child_tab, tab,
-                                                                                                    s->info, s->posm_s, s->perm, P);
-        });
-        NBMI_HIP_CHECK(hipGetLastError());
-        return 0;
-    }
-    if (integrate && s->walk_lane) {  // measurement only, see k_walk_lane
-        k_walk_lane<<<gb, wb, 0, st>>>(s->nodes, tab, s->info, s->posm_s, s->perm, P);
-        NBMI_HIP_CHECK(hipGetLastError());
-        return 0;
-    }
     // balance mode: full, unsharded integrating walks of the product kernel with the default block mapping
     // (measured: 10 M collision walk 15.9 -> 14.8 ms, fp32 10.4 -> 9.8; 4 M galaxy 6.96 -> 6.90; at 1 M bodies the eighths are
     // within 1 % of each other already and the half-empty launch costs 2 %: from 8 192 blocks = 2 M bodies on)
@@ -5453,8 +5161,6 @@ static const char *multipole_refusal(const nbmi_sim *s) {
     if (s->method != NBMI_METHOD_BARNES_HUT) return "direct N^2 handles have no cells";
     if (s->owner) return "owner-mode handles are not supported (the exchanged tree rows carry no second moments)";
     if (s->shard_begin != 0 || s->shard_end != s->n) return "sharded handles are not supported (the exchange rows carry no second moments)";
-    if (s->prec || s->walk_lane || s->walk_stack || s->acc64_env)
-        return "not available with the measurement-only walks (NBMI_PREC, NBMI_WALK_LANE, NBMI_ACC64, NBMI_WALK_STACK)";
     return nullptr;
 }
 
@@ -5471,10 +5177,7 @@ static void read_env_knobs(nbmi_sim *s) {
     if (const char *e = getenv("NBMI_SORT_THREADS")) s->sort_cfg.threads = atoi(e);
     if (const char *e = getenv("NBMI_SORT_FUSED_HIST")) s->sort_fused_hist = atoi(e) != 0 ? 1 : 0;
     if (const char *e = getenv("NBMI_KEYS_LEAN")) s->keys_lean = atoi(e) != 0;
-    if (const char *e = getenv("NBMI_FOF_HALF")) s->fof_half = atoi(e) != 0;
     if (const char *e = getenv("NBMI_PAIRS_CELLS")) s->pair_cells = atoi(e) != 0;
-    if (const char *e = getenv("NBMI_WALK_LANE")) s->walk_lane = atoi(e);
-    if (const char *e = getenv("NBMI_WALK_STACK")) s->walk_stack = atoi(e);
     if (const char *e = getenv("NBMI_FORCE_PREC")) {
         const int v = atoi(e);
         if (v >= 0 && v <= 2) s->force_prec = v;
@@ -5485,9 +5188,6 @@ static void read_env_knobs(nbmi_sim *s) {
     }
     if (const char *e = getenv("NBMI_ALL64_ENTER")) s->all64_enter_pm = (int)(1000.0 * atof(e) + 0.5);
     if (const char *e = getenv("NBMI_ALL64_LEAVE")) s->all64_leave_pm = (int)(1000.0 * atof(e) + 0.5);
-    if (const char *e = getenv("NBMI_PREC")) s->prec = atoi(e);
-    if (const char *e = getenv("NBMI_PREC_NEAR")) s->prec_near = atof(e);
-    if (const char *e = getenv("NBMI_ACC64")) s->acc64_env = atoi(e) != 0;
     if (const char *e = getenv("NBMI_SORT_BITS")) {
         const int b = atoi(e);
         if (b >= 8 && b <= 63) s->sort_bits = b;
@@ -5531,15 +5231,13 @@ static int create_impl(nbmi_sim *s, const double *pos, const double *vel, const 
         const int64_t own_rows = node_rows_for(c);
         if (dev_alloc(s, &s->key_hi, c) || dev_alloc(s, &s->key_lo, c) || dev_alloc(s, &s->hi_s, c) ||
             dev_alloc(s, &s->lo_s, c) ||
-            (s->sort_packed && !s->owner && (dev_alloc(s, &s->packed, c) || dev_alloc(s, &s->packed_s, c))) || ((s->owner || s->prec) && dev_alloc(s, &s->p64_s, c)) || dev_alloc(s, &s->idx, c) ||
+            (s->sort_packed && !s->owner && (dev_alloc(s, &s->packed, c) || dev_alloc(s, &s->packed_s, c))) || (s->owner && dev_alloc(s, &s->p64_s, c)) || dev_alloc(s, &s->idx, c) ||
             dev_alloc(s, &s->perm, c) || dev_alloc(s, &s->delta, c) || dev_alloc(s, &s->Pex, c + 1) ||
             dev_alloc(s, &s->S, c + 1) || dev_alloc(s, &s->sub_tot, (c + 1) / kScanTile + 2) ||
             dev_alloc(s, &s->sub_cnt, (c + 1) / kScanTile + 2) || dev_alloc(s, &s->subPex, (c + 1) / kScanTile + 2) ||
             dev_alloc(s, &s->T, (c + 1) / kScanTile + 2) ||
             dev_alloc(s, &s->nodes, s->node_capacity + 2) || dev_alloc(s, &s->nodes64, s->node_capacity + 2) ||
             dev_alloc(s, &s->node_level, own_rows) || dev_alloc(s, &s->node_ref, own_rows) ||
-            (s->walk_stack && dev_alloc(s, &s->child_tab, (size_t)8 * own_rows)) ||
-            (s->prec && dev_alloc(s, &s->diag64, own_rows)) ||
             dev_alloc(s, &s->xcd_bounds, 16) || dev_alloc(s, &s->wave_cycles, (size_t)4 * ((c + 63) / 64 + 8)) ||
             dev_alloc(s, &s->wave_flag, (size_t)(c + 63) / 64 + 64) || dev_alloc(s, &s->sub_flag, (c + 1) / kScanTile + 2) ||
             (s->force_prec != 1 && s->node_capacity + 2 <= kMaxNodeDRows &&
@@ -5716,7 +5414,7 @@ int nbmi_step(nbmi_sim *s, double dt, int substeps) {
             s->steps_taken++;
             s->tree_valid = false;
             // (leapfrog: the walk publishes nothing, the next k_kick_drift does)
-            s->maxabs_fused = !leap && s->fuse_maxabs && s->shard_begin == 0 && s->shard_end == s->n && !s->walk_stack && !s->walk_lane;
+            s->maxabs_fused = !leap && s->fuse_maxabs && s->shard_begin == 0 && s->shard_end == s->n;
         } else {
             if (s->timers) NBMI_HIP_CHECK(hipEventRecord(s->ev[0], s->stream));
             if (leap) {
@@ -5833,12 +5531,6 @@ int nbmi_set_integrator(nbmi_sim *s, int integrator) {
         if (s->shard_begin != 0 || s->shard_end != s->n) {
             nbmi::set_error("nbmi_set_integrator: sharded handles are not supported (leapfrog needs acceleration columns "
                             "that the exchange rows do not carry)");
-            return NBMI_ERR_ARG;
-        }
-        const char *a64 = getenv("NBMI_ACC64");
-        if (s->prec || s->walk_lane || (a64 && atoi(a64))) {
-            nbmi::set_error("nbmi_set_integrator: leapfrog is not available with the measurement-only walks (NBMI_PREC, "
-                            "NBMI_WALK_LANE, NBMI_ACC64)");
             return NBMI_ERR_ARG;
         }
         if (s->integrator != NBMI_INTEGRATOR_LEAPFROG) s->acc_valid = false;  // the next step primes a = F(x)
@@ -6022,8 +5714,6 @@ const char *knn_refusal(const nbmi_sim *s) {
     if (s->method != NBMI_METHOD_BARNES_HUT) return "direct N^2 handles have no tree";
     if (s->owner) return "owner-mode handles are not supported (the neighbours may live on other ranks)";
     if (s->shard_begin != 0 || s->shard_end != s->n) return "sharded handles are not supported";
-    if (s->prec || s->walk_lane || s->walk_stack || s->acc64_env)
-        return "not available with the measurement-only walks (NBMI_PREC, NBMI_WALK_LANE, NBMI_ACC64, NBMI_WALK_STACK)";
     return nullptr;
 }
 int knn_check(nbmi_sim *s, int k, const char *what) {
@@ -6134,7 +5824,7 @@ int fof_enqueue(nbmi_sim *s, double b2, bool count, int32_t *labels) {
         k_fof_init<<<nblocks(rows), kBlock, 0, st>>>(s->nodes, s->node_ref, s->info, n, s->own_node_rows, s->fof_parent,
                                                      s->fof_minid, s->fof_cnt, s->fof_wleaf);
         k_fof_link<<<(int)((n + kFofBlock - 1) / kFofBlock), kFofBlock, 0, st>>>(
-            s->nodes, s->knn_rows, s->node_ref, s->info, s->perm, cur, n, b2, s->fof_half ? 1 : 0, s->fof_wleaf, s->fof_parent,
+            s->nodes, s->knn_rows, s->node_ref, s->info, s->perm, cur, n, b2, s->fof_wleaf, s->fof_parent,
             count ? s->fof_counters : nullptr);
         k_fof_flatten<<<nblocks(n), kBlock, 0, st>>>(s->info, n, s->fof_parent, s->perm, cur.id, s->fof_root, s->fof_minid,
                                                      s->fof_cnt);

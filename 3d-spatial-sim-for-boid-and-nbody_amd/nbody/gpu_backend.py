@@ -221,7 +221,7 @@ class _HIPSimulation:
     def set_integrator(self, integrator: str):
         """"kick_drift" (default, the reference's scheme) or "leapfrog" (synchronized kick-drift-kick: second order,
         time-reversible, positions and velocities at the same instant; include/nbmi.h nbmi_set_integrator).  Owner-mode
-        and sharded handles and the measurement-only walks refuse leapfrog with ValueError."""
+        and sharded handles refuse leapfrog with ValueError."""
         code = _integrator_code(integrator)
         rc = self._lib.nbmi_set_integrator(self._h, code)
         if rc == -1:  # NBMI_ERR_ARG: refused for this handle
@@ -237,7 +237,7 @@ class _HIPSimulation:
     def set_multipole(self, multipole: str):
         """"monopole" (default, the reference's term) or "quadrupole": an applied cell term also carries the cell's
         second moments; the accepted (body, node) sets do not change (include/nbmi.h nbmi_set_multipole).  Direct,
-        owner-mode and sharded handles and the measurement-only walks refuse quadrupole with ValueError."""
+        owner-mode and sharded handles refuse quadrupole with ValueError."""
         code = _multipole_code(multipole)
         rc = self._lib.nbmi_set_multipole(self._h, code)
         if rc == -1:  # NBMI_ERR_ARG: refused for this handle

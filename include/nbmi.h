@@ -90,8 +90,8 @@ int nbmi_step(nbmi_sim *sim, double dt, int substeps);
  *     leapfrog step allocates 24 bytes per body for a.  Getters, colours, frames and nbmi_diagnostics therefore see
  *     synchronized velocities (no half-step offset in K and E); nbmi_diagnostics and nbmi_get_accelerations_f64 leave the
  *     state and the stored a as they were.  A capacity error leaves the state at the last completed step, as in
- *     kick-drift.  Owner-mode handles, handles with a proper shard (nbmi_set_shard, in either order of the calls) and the
- *     measurement-only walks (NBMI_PREC, NBMI_WALK_LANE, NBMI_ACC64) refuse leapfrog with NBMI_ERR_ARG. */
+ *     kick-drift.  Owner-mode handles and handles with a proper shard (nbmi_set_shard, in either order of the calls)
+ *     refuse leapfrog with NBMI_ERR_ARG. */
 #define NBMI_INTEGRATOR_KICK_DRIFT 0
 #define NBMI_INTEGRATOR_LEAPFROG 1
 int nbmi_set_integrator(nbmi_sim *sim, int integrator);
@@ -130,11 +130,9 @@ int nbmi_get_integrator(nbmi_sim *sim, int *out);
  *     the mode allocates 24 + 72 + 32 bytes per node row; every build of the mode also writes the rows the cell queries read
  *     and runs a bottom-up pass over the levels of the tree for the moments.
  *     Refused with NBMI_ERR_ARG: direct N^2 handles, owner-mode handles, handles with a proper shard (nbmi_set_shard, in
- *     either order of the calls: their exchanged rows carry no P), the measurement-only walks (NBMI_PREC, NBMI_WALK_LANE,
- *     NBMI_ACC64, NBMI_WALK_STACK).
+ *     either order of the calls: their exchanged rows carry no P).
  * A switch drops the stored leapfrog acceleration (the next step primes it in the new mode).  Environment NBMI_MULTIPOLE
- * ("quadrupole" or "1"; anything else means monopole) sets the initial value on handles that allow it.  NBMI_ACC64 and the
- * other measurement knobs are read when the handle is created. */
+ * ("quadrupole" or "1"; anything else means monopole) sets the initial value on handles that allow it. */
 #define NBMI_MULTIPOLE_MONOPOLE 0
 #define NBMI_MULTIPOLE_QUADRUPOLE 1
 int nbmi_set_multipole(nbmi_sim *sim, int multipole);
@@ -263,8 +261,8 @@ int nbmi_get_potentials_f64(nbmi_sim *sim, double *out);
  * "auto" precision flags and force_all64 - the build runs without a dt -, the step count, the stored leapfrog
  * acceleration).  The first call allocates 16 bytes per body and 32 bytes per node row.  NBMI_ERR_CAPACITY from the
  * call's own tree build is reported with a step's message.
- * Refused with NBMI_ERR_ARG, message "<call>: ...": direct N^2 handles (there is no tree), owner-mode handles, handles
- * with a proper shard, and the measurement-only walks (NBMI_PREC, NBMI_WALK_LANE, NBMI_ACC64, NBMI_WALK_STACK). */
+ * Refused with NBMI_ERR_ARG, message "<call>: ...": direct N^2 handles (there is no tree), owner-mode handles and
+ * handles with a proper shard. */
 int nbmi_knn(nbmi_sim *sim, int k, double *r2_k, double *mass_k, int64_t *evals);
 int nbmi_get_densities_f64(nbmi_sim *sim, int k, double *rho);
 /* What nbmi_compute_colors and nbmi_frame_begin colour by.  NBMI_COLOR_SPEED (the default): the reference's ramp at
@@ -303,17 +301,14 @@ int nbmi_get_color_mode(nbmi_sim *sim, int *mode, int *k, double *log10_lo, doub
  * min_members gets the speed ramp at t = ((uint32)(label * 2654435761u) >> 8) / 2^24, every other body (0.25, 0.25,
  * 0.25).  It only enqueues; NBMI_ERR_CAPACITY of its build is reported deferred, as a step's is.
  * Refused with NBMI_ERR_ARG, message "<call>: ...": link not finite or <= 0, min_members < 1, capacity < 0, and the
- * handles nbmi_knn refuses (direct N^2, owner mode, a proper shard, the measurement-only walks).  N == 0: success,
+ * handles nbmi_knn refuses (direct N^2, owner mode, a proper shard).  N == 0: success,
  * n_groups = 0, count = 0.  N == 1: one singleton.
  * A call changes nothing that a later step reads (as nbmi_knn).  NBMI_ERR_CAPACITY of the call's own tree build is
  * reported with a step's message.  Quadrupole and leapfrog handles return a plain handle's bits.
  * The first nbmi_fof allocates 16 bytes per body, 4 bytes per 64 bodies and (shared with nbmi_knn) 32 bytes per node
  * row; the first catalogue 24 bytes per body more, a radix sort buffer (about 8 bytes per body), 304 bytes per 256
  * bodies and 268 bytes per catalogue row (for the next power of two of rows, at least 1 024; a call that needs more frees
- * the arrays and allocates larger ones).
- * Environment NBMI_FOF_HALF (read when the handle is created, like the other measurement knobs): 0 starts every wave's
- * pair search at the root of the tree instead of at the wave's own first leaf.  Results are the same; evals and the
- * time are not (DESIGN.md section 4.15 has the A/B). */
+ * the arrays and allocates larger ones). */
 int nbmi_fof(nbmi_sim *sim, double link, int32_t *labels /* (N,), may be NULL */, int64_t *n_groups /* may be NULL */,
              int64_t *evals /* may be NULL */);
 int nbmi_fof_catalogue(nbmi_sim *sim, double link, int64_t min_members, int64_t capacity, int32_t *label,
@@ -344,7 +339,7 @@ int nbmi_compute_group_colors(nbmi_sim *sim, double link, int64_t min_members);
  * acceleration).  NBMI_ERR_CAPACITY of the call's own tree build is reported with a step's message.
  * Refused with NBMI_ERR_ARG, message "nbmi_pair_counts: ...": nb outside 1 .. 64, null edges, an edge that is not finite,
  * negative or not above the one before it (or whose square is not), and the handles nbmi_knn refuses (direct N^2, owner
- * mode, a proper shard, the measurement-only walks).
+ * mode, a proper shard).
  * The first call allocates 4 bytes per node row, 4 bytes per 64 bodies, 536 bytes of results and (shared with nbmi_knn
  * and nbmi_fof) 32 bytes per node row.
  * Environment NBMI_PAIRS_CELLS (read when the handle is created, like the other measurement knobs): 0 never counts a

@@ -1,18 +1,16 @@
 """Cost of the friends-of-friends query (nbmi_fof).  JSON lines in <out>/fof_bench.jsonl, one per case:
 
-  {"kind": "fof", "case": ..., "half_walk": 1 | 0, "link": ..., "fof_ms": ..., "evals_per_body": ..., "n_groups": ...,
-   "largest": ..., "catalogue_ms": ..., "colors_ms": ..., "knn8_ms": ..., "step_ms": ..., "fof_over_knn8": ...,
-   "fof_over_step": ...}
+  {"kind": "fof", "case": ..., "link": ..., "fof_ms": ..., "evals_per_body": ..., "n_groups": ..., "largest": ...,
+   "catalogue_ms": ..., "colors_ms": ..., "knn8_ms": ..., "step_ms": ..., "fof_over_knn8": ..., "fof_over_step": ...}
 
 link = twice the median nearest-neighbour distance of the state (one knn(1)), the recorder's "auto".  ms = host wall time of
 one blocking call (mean over --reps after one warm-up call): find_groups(link), group_catalogue(link, 20) (which runs the
 query again), color_by_groups + sync, knn(8), and one default step (mean over --reps after --warmup, synchronised) of
-the same handle.  evals_per_body = the distances one find_groups evaluated / N.  half_walk = 0 is the other side of the
-A/B: every wave walks the whole tree (NBMI_FOF_HALF=0) instead of starting at its own first leaf.
+the same handle.  evals_per_body = the distances one find_groups evaluated / N.
 
     python scripts/fof_bench.py [--out profiles]      every step below as a child process under its own `timeout`, each
                                                       started only if the one before succeeded:
-        --what calls --case galaxy_1m                 the line of one case, then the same with NBMI_FOF_HALF=0
+        --what calls --case galaxy_1m                 the line of one case
         --what calls --case collision_10m
         rocprofv3 --kernel-trace --stats ... -- --what one --case galaxy_1m
                                                       one 1 M call on its own, no counters -> <out>/fof_1m_kernel_stats.csv
@@ -81,8 +79,8 @@ def calls(case, reps, warmup, out):
         sim.color_by_groups(link, 20)
         sim.sync()
     col_ms = _timed(colours, reps)
-    rec = {"kind": "fof", "case": case, "n": n, "half_walk": 0 if os.environ.get("NBMI_FOF_HALF") == "0" else 1,
-           "link": link, "fof_ms": round(fof_ms, 3), "evals_per_body": round(ev / n, 1), "n_groups": sim.n_groups,
+    rec = {"kind": "fof", "case": case, "n": n, "link": link, "fof_ms": round(fof_ms, 3),
+           "evals_per_body": round(ev / n, 1), "n_groups": sim.n_groups,
            "groups_of_20": cat["count"], "largest": int(cat["members"][0]) if len(cat["members"]) else 0,
            "catalogue_ms": round(cat_ms, 3), "colors_ms": round(col_ms, 3), "knn8_ms": round(knn_ms, 3),
            "step_ms": round(step_ms, 3), "fof_over_knn8": round(fof_ms / knn_ms, 2), "fof_over_step": round(fof_ms / step_ms, 2)}
@@ -112,14 +110,8 @@ def drive(out, reps, warmup, cases):
         os.remove(path)
     raw = os.path.join(out, "fof_1m_raw")
 
-    def call(case, half):
-        return (["timeout", "-k", "10", str(STEP_TIMEOUT[case]), sys.executable, me, "--what", "calls", "--case", case, "--out",
-                 out, "--reps", str(reps), "--warmup", str(warmup)], dict(os.environ, NBMI_FOF_HALF="1" if half else "0"))
-    steps = []
-    for c in cases:
-        steps.append(call(c, True))
-        if c == "galaxy_1m":
-            steps.append(call(c, False))
+    steps = [(["timeout", "-k", "10", str(STEP_TIMEOUT[c]), sys.executable, me, "--what", "calls", "--case", c, "--out", out,
+               "--reps", str(reps), "--warmup", str(warmup)], dict(os.environ)) for c in cases]
     if "galaxy_1m" in cases:
         steps.append((["timeout", "-k", "10", str(STEP_TIMEOUT["profile"]), "rocprofv3", "--kernel-trace", "--stats",
                        "--output-format", "csv", "-d", raw, "--", sys.executable, me, "--what", "one", "--case", "galaxy_1m"],

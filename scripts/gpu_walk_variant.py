@@ -1,4 +1,4 @@
-"""A/B of a walk variant selected by an environment knob (e.g. NBMI_WALK_STACK=1) against the default kernel:
+"""A/B of a walk variant selected by an environment knob (e.g. NBMI_WALK_PAIR=1) against the default kernel:
 positions after a few steps (same accepted sets: differences are fp32 summation order) and ms per step."""
 import importlib, json, os, sys, time
 import numpy as np

@@ -482,37 +482,3 @@ def test_recorder_groups_sessions_plain_and_pipelined(gpu, tmp_path):
     assert [r["members"] for r in first["groups"]] == cat["members"][:rec.GROUPS_ROWS].tolist()
     assert first["groups"][0]["lo"] == cat["lo"][0].tolist() and first["groups"][0]["hi"] == cat["hi"][0].tolist()
     assert rec.show_status("plain", root=tmp_path)
-
-
-@pytest.mark.parametrize("knob", ["NBMI_WALK_LANE", "NBMI_PREC", "NBMI_ACC64", "NBMI_WALK_STACK"])
-def test_measurement_only_walks_are_refused(gpu, monkeypatch, knob):
-    """the knobs are read when the handle is created: such a handle refuses the three calls, in C with "<call>: ...
-    measurement-only", in Python with ValueError, and goes on stepping"""
-    lib = gpu.load()
-    rng = np.random.RandomState(2)
-    n = 256
-    p = rng.uniform(-10, 10, (n, 3))
-    lab, mem, out, cnt = np.empty(n, np.int32), np.empty(n, np.int64), np.empty((n, 13)), np.zeros(1, np.int64)
-    monkeypatch.setenv(knob, "1")
-    sim = _bh(p)
-    monkeypatch.delenv(knob)
-    try:
-        for name, call in (("nbmi_fof", lambda: lib.nbmi_fof(sim._h, 2.0, gpu.ptr(lab), None, None)),
-                           ("nbmi_fof_catalogue", lambda: lib.nbmi_fof_catalogue(sim._h, 2.0, 1, n, gpu.ptr(lab), gpu.ptr(mem),
-                                                                                 gpu.ptr(out), gpu.ptr(cnt))),
-                           ("nbmi_compute_group_colors", lambda: lib.nbmi_compute_group_colors(sim._h, 2.0, 1))):
-            rc = call()
-            msg = gpu.last_error()
-            assert rc == NBMI_ERR_ARG and msg.startswith(name + ": ") and "measurement-only" in msg, (name, rc, msg)
-        for call in (lambda: sim.find_groups(2.0), lambda: sim.group_catalogue(2.0), lambda: sim.color_by_groups(2.0)):
-            with pytest.raises(ValueError, match="measurement-only"):
-                call()
-        sim.step(0.1)
-        sim.sync()
-    finally:
-        sim.close()
-    plain = _bh(p)  # a handle created without the knob is served
-    try:
-        _check_labels(f"after {knob}", plain.find_groups(2.0), plain.n_groups, fr.fof(p, 2.0))
-    finally:
-        plain.close()

@@ -574,21 +574,10 @@ def test_refusals_in_both_orders(gpu, monkeypatch):
     with pytest.raises(ValueError, match="quadrupole mode first"):
         s.cell_moments()  # no tree built for queries yet
     s.close()
-    for knob in ("NBMI_WALK_LANE", "NBMI_ACC64", "NBMI_PREC", "NBMI_WALK_STACK"):
-        monkeypatch.setenv(knob, "1")
-        s = _bh(x, v, m, 1.0, 0.05, multipole="monopole")
-        with pytest.raises(ValueError, match="measurement-only"):
-            s.set_multipole("quadrupole")
-        s.step(0.01)
-        s.sync()
-        s.close()
-        monkeypatch.setenv("NBMI_MULTIPOLE", "quadrupole")  # the environment's initial value does not override a refusal
-        s = _bh(x, v, m, 1.0, 0.05, multipole="monopole")
-        assert s.multipole == "monopole"
-        s.close()
-        monkeypatch.delenv("NBMI_MULTIPOLE")
-        monkeypatch.delenv(knob)
-    monkeypatch.setenv("NBMI_MULTIPOLE", "quadrupole")
+    monkeypatch.setenv("NBMI_MULTIPOLE", "quadrupole")  # the environment's initial value does not override a refusal
+    d = HIPDirectSimulation(x, v, m, 1.0, 0.05, 1.0)
+    assert d.multipole == "monopole"
+    d.close()
     s = _bh(x, v, m, 1.0, 0.05, multipole="monopole")
     assert s.multipole == "quadrupole"
     s.close()

@@ -49,11 +49,6 @@ def _cases():
                                                         want=("acc", "accepts"))
     c["count_eps"] = _case(want=("acc", "counters"))
     c["count_eps0"] = _case(eps=0.0, want=("acc", "counters"))
-    c["count_acc64"] = _case({"NBMI_ACC64": "1"}, want=("acc", "counters"))
-    c["stack"] = _case(dict(ONE_WAVE, NBMI_WALK_STACK="1"))
-    c["lane"] = _case(dict(ONE_WAVE, NBMI_WALK_LANE="1"))
-    for mode in (1, 2, 13):
-        c[f"prec_mode{mode}"] = _case(dict(ONE_WAVE, NBMI_PREC=str(mode)))
     for prec in ("f32", "auto"):  # the same bits as wave_pair1_<prec>: BALANCE_TWINS
         c[f"balance_{prec}"] = _case(dict(ONE_WAVE, NBMI_WALK_PAIR="1", NBMI_XCD_BALANCE="2"), prec=prec)
     for mp in ("monopole", "quadrupole"):
