@@ -4,8 +4,9 @@
 // 104-232 galaxy / collision via the disk helper and compute_rotation_curve :52-88, :234-295 spiral,
 // :350-397 cluster, :609-684 filament); the random stream is a counter-based Philox4x32-10 (key =
 // seed, counter = body index, draw block, stream tag), so the result depends only on (seed, n, R, G)
-// - STATISTICAL parity with the NumPy generator, not bit parity (tests/test_gpu_icgen.py and
-// tests/test_gpu_icgen_more.py compare the distributions).
+// - two kinds of parity: STATISTICAL with the NumPy generator, whose stream is another (tests/test_gpu_icgen.py
+// and tests/test_gpu_icgen_more.py compare the distributions), and PER BODY, to a few hundred ulp (DESIGN.md has the
+// measured bound), with the host replay of this file's draws in tests/icgen_ref.py (tests/test_gpu_icgen_replay.py).
 #include <cstring>
 #include <math.h>
 

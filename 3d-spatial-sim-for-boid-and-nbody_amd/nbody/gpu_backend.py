@@ -149,8 +149,9 @@ class _HIPSimulation:
                   integrator="kick_drift", multipole="monopole"):
         """Same backend object, but the bodies are drawn ON THE DEVICE from the reference's
         generate_distribution formulas (tools/presets.py:104-295, :350-397, :609-684; `distribution`
-        one of GENERATED_DISTRIBUTIONS) with a Philox stream keyed by `seed`: statistical, not bit,
-        parity with the NumPy generator; no host arrays, no upload."""
+        one of GENERATED_DISTRIBUTIONS) with a Philox stream keyed by `seed`: statistical parity
+        with the NumPy generator, per-body parity (to the bound recorded in DESIGN.md) with the host replay
+        in tests/icgen_ref.py; no host arrays, no upload."""
         kinds = GENERATED_DISTRIBUTIONS
         _integrator_code(integrator)
         _multipole_code(multipole)

@@ -212,7 +212,8 @@ def generate_distribution_device(distribution: str, n: int, R: float, G: float, 
                                  multipole: str = "monopole"):
     """generate_distribution + backend construction in one step, on the GPU: returns a
     HIPBarnesHutSimulation whose bodies were drawn on the device (nbmi_create_generated; Philox
-    stream, statistical parity with generate_distribution).  At 10 M bodies this replaces seconds of
+    stream: statistical parity with generate_distribution, per-body parity with the host replay of that
+    stream in tests/icgen_ref.py).  At 10 M bodies this replaces seconds of
     NumPy and a 640 MB upload by a few milliseconds."""
     from nbody.gpu_backend import HIPBarnesHutSimulation
     return HIPBarnesHutSimulation.generated(distribution, n, R, G, softening, damping, theta=theta, seed=seed,

@@ -53,8 +53,10 @@ nbmi_sim *nbmi_create(int64_t n, const double *positions_xyz, const double *velo
  * GPU from generate_distribution's formulas (tools/presets.py:104-232 "galaxy" / "collision",
  * :234-295 "spiral", :350-397 "cluster": unit masses; :609-684 "filament", the cosmic web: masses
  * 0.1) with a counter-based Philox4x32-10 stream keyed by `seed`, so a 10-50 M-body start needs no
- * host generator and no multi-GB upload.  Statistical, not bit, parity with the NumPy generator;
- * the same (seed, n, radius, G) always gives the same bodies.  G is used both for the rotation
+ * host generator and no multi-GB upload.  Statistical parity with the NumPy generator (another
+ * random stream), and per-body parity, to the bound recorded in DESIGN.md, with the host replay of
+ * the same stream in tests/icgen_ref.py; the same (seed, n, radius, G) always gives the same
+ * bodies.  G is used both for the rotation
  * curve / dispersions and for the simulation, as record() does (tools/record.py:747-758).  Body i
  * of the getters is the i-th generated body.  "filament" fails (NULL) in the ~1e-96 case that none
  * of its 512 grid nodes is active, as the reference does. */
