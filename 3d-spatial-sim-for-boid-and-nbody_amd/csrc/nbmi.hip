@@ -3550,10 +3550,12 @@ __global__ __launch_bounds__(kBlock) void k_unperm1_f64(const double *__restrict
 }
 
 // ---------------------------------------------------------------------------------------
-// K16: exact k-nearest-neighbour query (nbmi_knn / nbmi_get_densities_f64 / density colours; include/nbmi.h,
-// DESIGN.md section 4.14).  Float64 throughout, every sum in a fixed order: two calls on one state agree bit for bit.
+// K16 - K18: the exact tree queries - k nearest neighbours, friends-of-friends groups, binned pair counts (include/nbmi.h,
+// DESIGN.md sections 4.14 - 4.16).  Float64 throughout, every sum in a fixed order: two calls on one state agree bit for
+// bit.  First what all three share: the node rows and the waves' first leaves, d2 and its lower
+// bound, the wave's prologue, the walk, the half search inside a wave and the sum of a counter over it.
 // ---------------------------------------------------------------------------------------
-// The query's own row per node of its build, written after the emission from what the build left behind (the build
+// A query's own row per node of its build, written after the emission from what the build left behind (the build
 // itself is untouched): node_ref gives the node's first body in key order, perm its state row.
 //   leaf           {x, y, z, m}   the body as the float64 state has it; m is the MASS (cur.m), not G m
 //   internal cell  {x, y, z, w}   the cell's FIRST body (the "anchor") and the reach w = 2 hs + 2^-44 bounds
@@ -3563,23 +3565,38 @@ __global__ __launch_bounds__(kBlock) void k_unperm1_f64(const double *__restrict
 // every body of the cell is within w of the anchor on every axis, and that statement has no rounding of a sum of
 // masses in it.  (The computed centre of mass has: its error grows with the mass ratio of the sub-tile to the cell,
 // without bound relative to the cell's size.)
-constexpr int kKnnBlock = 64;  // one wave per workgroup: its k x 512 bytes of LDS are then the allocation unit
-constexpr int kKnnMaxK = 64;
-__global__ __launch_bounds__(kBlock) void k_knn_rows(const Node *__restrict__ nodes, const Node64 *__restrict__ n64,
-                                                     const int32_t *__restrict__ node_ref, const uint32_t *__restrict__ perm,
-                                                     Bodies cur, const TreeInfo *__restrict__ info, int64_t capacity,
-                                                     double4 *__restrict__ rows) {
+// Also, for every wave of 64 key ranks, wleaf = the node index of its first body's leaf (the node array is in key order:
+// everything of a higher rank lies behind that leaf), where K17 and K18 start their walks.
+constexpr int kQueryBlock = 64;  // one wave per workgroup (K16: its k x 512 bytes of LDS are then the allocation unit)
+__global__ __launch_bounds__(kBlock) void k_query_rows(const Node *__restrict__ nodes, const Node64 *__restrict__ n64,
+                                                       const int32_t *__restrict__ node_ref, const uint32_t *__restrict__ perm,
+                                                       Bodies cur, const TreeInfo *__restrict__ info, int64_t capacity,
+                                                       double4 *__restrict__ rows, uint32_t *__restrict__ wleaf) {
     if (info->error != 0 || info->sticky_error != 0) return;  // the tree did not fit: the caller reports it
     const int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (idx >= info->num_nodes || idx >= capacity) return;
-    const uint32_t j = perm[node_ref[idx]];
+    const int32_t r = node_ref[idx];
+    const uint32_t j = perm[r];
     const bool leaf = __float_as_int(nodes[idx].s2t) == 0;
     const double w = leaf ? cur.m[j] : __dadd_rn(__dmul_rn(2.0, n64[idx].hs), __dmul_rn(info->bounds, 0x1p-44));
     rows[idx] = make_double4(cur.x[j], cur.y[j], cur.z[j], w);
+    if (leaf && (r & 63) == 0) wleaf[r >> 6] = (uint32_t)idx;
+}
+// After a query (or the diagnostics' potential): the tree header as it stood before its own build - except that a capacity
+// error of that build stays behind in the sticky words, to be reported by the next call that looks, as a step's is.
+__global__ void k_query_restore(TreeInfo *info, const TreeInfo *__restrict__ saved) {
+    if (threadIdx.x != 0) return;
+    const int err = info->error | info->sticky_error;
+    const long long nodes = info->sticky_error ? info->sticky_nodes : info->num_nodes;
+    *info = *saved;
+    if (err && info->sticky_error == 0) {
+        info->sticky_error = 1;
+        info->sticky_nodes = nodes;
+    }
 }
 
 // d2(i, j) as the header defines it: float64, this association, no FMA
-__device__ __forceinline__ double knn_d2(double bx, double by, double bz, double qx, double qy, double qz) {
+__device__ __forceinline__ double query_d2(double bx, double by, double bz, double qx, double qy, double qz) {
     const double dx = __dsub_rn(bx, qx), dy = __dsub_rn(by, qy), dz = __dsub_rn(bz, qz);
     return __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
 }
@@ -3589,7 +3606,7 @@ __device__ __forceinline__ double knn_d2(double bx, double by, double bz, double
 // G - (2^-49 - 4 u) t < G.  A body's computed |dx| is >= G (1 - u), its computed d2 >= (sum G^2)(1 - u)^5; the bound
 // below is <= (sum g^2)(1 + u)^3 (1 - 2^-48).  2^-48 = 32 u leaves a factor four.  Below 2^-960 the products may be
 // subnormal and the relative bounds no longer hold: such a bound counts as 0 (never prunes).
-__device__ __forceinline__ double knn_lower(double4 a, double qx, double qy, double qz) {
+__device__ __forceinline__ double query_lower(double4 a, double qx, double qy, double qz) {
     const double tx = fabs(__dsub_rn(a.x, qx)), ty = fabs(__dsub_rn(a.y, qy)), tz = fabs(__dsub_rn(a.z, qz));
     double gx = __dsub_rn(__dsub_rn(tx, a.w), __dmul_rn(tx, 0x1p-49));
     double gy = __dsub_rn(__dsub_rn(ty, a.w), __dmul_rn(ty, 0x1p-49));
@@ -3598,6 +3615,121 @@ __device__ __forceinline__ double knn_lower(double4 a, double qx, double qy, dou
     const double lo = __dmul_rn(__dadd_rn(__dadd_rn(__dmul_rn(gx, gx), __dmul_rn(gy, gy)), __dmul_rn(gz, gz)), 1.0 - 0x1p-48);
     return lo > 0x1p-960 ? lo : 0.0;
 }
+__device__ __forceinline__ double query_bcast(double v, int lane) {  // lane is wave-uniform
+    const long long b = __double_as_longlong(v);
+    const int lo = __builtin_amdgcn_readlane((int)b, lane), hi = __builtin_amdgcn_readlane((int)(b >> 32), lane);
+    return __longlong_as_double(((long long)hi << 32) | (unsigned long long)(unsigned)lo);
+}
+// the 64 bodies at the key ranks base .. base + 63, one per lane (ranks outside [0, n) hold zeros and are never used)
+struct QueryGroup {
+    double x, y, z, m;
+    int64_t base;
+};
+__device__ __forceinline__ QueryGroup query_group(const Bodies &cur, const uint32_t *__restrict__ perm, int64_t base, int64_t n) {
+    QueryGroup g{0.0, 0.0, 0.0, 0.0, base};
+    const int64_t r = base + (int64_t)(threadIdx.x & 63);
+    if (r >= 0 && r < n) {
+        const uint32_t j = perm[r];
+        g.x = cur.x[j]; g.y = cur.y[j]; g.z = cur.z[j]; g.m = cur.m[j];
+    }
+    return g;
+}
+// What a lane of a query kernel starts from - one wave per 64 key-adjacent bodies, one body per lane: its key rank (valid:
+// it has a body), the end offset of the node array, the wave's own 64 bodies and among them its own, the query point.
+// frozen: the build did not fit (the caller reports it): the kernel returns at once.
+struct QueryCtx {
+    bool frozen, valid;
+    int lane;
+    int64_t w0, rank;
+    unsigned nn;
+    QueryGroup own;
+    double qx, qy, qz;
+};
+__device__ __forceinline__ QueryCtx query_prologue(const TreeInfo *__restrict__ info, const Bodies &cur,
+                                                   const uint32_t *__restrict__ perm, int64_t n) {
+    QueryCtx C;
+    C.frozen = info->error != 0 || info->sticky_error != 0;
+    const int64_t bodies = C.frozen ? 0 : n;  // (a frozen wave has no valid lane and loads nothing)
+    C.lane = threadIdx.x;
+    C.w0 = (int64_t)blockIdx.x * kQueryBlock;
+    C.rank = C.w0 + C.lane;
+    C.valid = C.rank < bodies;
+    C.nn = __builtin_amdgcn_readfirstlane((unsigned)info->num_nodes * kNodeBytes);
+    C.own = query_group(cur, perm, C.w0, bodies);
+    C.qx = C.own.x; C.qy = C.own.y; C.qz = C.own.z;
+    return C;
+}
+// One pass over the tree for one wave, k_potential_tree's skeleton: a wave-uniform byte cursor over `Node` and its
+// skip links, per lane `resume` = the offset up to which it sits out because it pruned an ancestor; the wave
+// descends while any active lane cannot prune.  `bound` is what a lane prunes against, strictly: a subtree is
+// skipped only if the lower bound EXCEEDS it, so bodies AT the bound are always reached.
+// The cursor starts at byte offset `start` (0: the root; the offset of a leaf: everything behind it in key order -
+// the cells that hold that leaf lie in front of it and are never tested, so nothing of theirs is pruned).
+// Leaves of the ranks [ex_lo, ex_hi) are skipped: the caller has dealt with those bodies (the wave's own among them,
+// which is how self is excluded by identity).  leaf(d2, row, rank) sees every other leaf a lane reaches and may
+// lower `bound`.  cell(idx, row, next_off) decides an internal cell for an active lane: true = the lane keeps it open,
+// false = it is done with the whole subtree (K16 / K17: pruned; K18 may also have counted it).
+template <class Cell, class Leaf>
+__device__ __forceinline__ void query_walk_cells(const Node *__restrict__ nodes, const double4 *__restrict__ rows,
+                                                 const int32_t *__restrict__ node_ref, unsigned start, const QueryCtx &C,
+                                                 int64_t ex_lo, int64_t ex_hi, long long &evals, Cell cell, Leaf leaf) {
+    unsigned resume = C.valid ? 0u : 0xffffffffu;
+    unsigned off = start;
+    while (off < C.nn) {
+        off = __builtin_amdgcn_readfirstlane(off);
+        const unsigned idx = off / kNodeBytes;
+        const Node nd = nodes[idx];
+        const double4 row = rows[idx];
+        const bool active = resume <= off;
+        if (__float_as_int(nd.s2t) == 0) {  // a leaf
+            const int64_t r = node_ref[idx];
+            if (active && (r < ex_lo || r >= ex_hi)) {
+                const double d2 = query_d2(row.x, row.y, row.z, C.qx, C.qy, C.qz);
+                evals++;
+                leaf(d2, row, r);
+            }
+            off += kNodeBytes;
+        } else {
+            bool open = false;
+            if (active) {
+                open = cell(idx, row, nd.next_off);
+                if (!open) resume = nd.next_off;
+            }
+            off = __builtin_amdgcn_ballot_w64(open) ? off + kNodeBytes : nd.next_off;
+        }
+    }
+}
+// K16 / K17: a cell is open unless its lower bound exceeds `bound`
+template <class Leaf>
+__device__ __forceinline__ void query_walk(const Node *__restrict__ nodes, const double4 *__restrict__ rows,
+                                           const int32_t *__restrict__ node_ref, unsigned start, const QueryCtx &C,
+                                           int64_t ex_lo, int64_t ex_hi, const double &bound, long long &evals, Leaf leaf) {
+    query_walk_cells(nodes, rows, node_ref, start, C, ex_lo, ex_hi, evals,
+                     [&](unsigned, const double4 &row, unsigned) { return !(query_lower(row, C.qx, C.qy, C.qz) > bound); }, leaf);
+}
+// K17 / K18, the half search inside the wave: the wave's own bodies go round by readlane and each pair is tested once - the
+// higher lane tests the lower.  f(d2, rank of the lower body) sees every such pair, in one branch for the lanes above it.
+template <class Pair>
+__device__ __forceinline__ void query_half_search(const QueryCtx &C, int64_t n, long long &evals, Pair f) {
+    for (int i = 0; i < 63; i++) {
+        if (C.w0 + i >= n) break;
+        const double d2 = query_d2(query_bcast(C.own.x, i), query_bcast(C.own.y, i), query_bcast(C.own.z, i), C.qx, C.qy, C.qz);
+        if (C.valid && C.lane > i) {
+            evals++;
+            f(d2, C.w0 + i);
+        }
+    }
+}
+// The sum of a counter over the wave, added to *dst by one agent-scope relaxed integer atomic (what atomicAdd is) unless
+// it is 0: integers, so the result does not depend on any order.
+__device__ __forceinline__ void query_wave_add(unsigned long long *dst, long long v, int lane) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if (lane == 0 && v != 0ll) (void)__hip_atomic_fetch_add(dst, (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// ---- K16: k nearest neighbours (nbmi_knn / nbmi_get_densities_f64 / density colours) --------
+constexpr int kKnnMaxK = 64;
 // A lane's candidate list: a binary max-heap of its k smallest d2 so far, slot s of lane l at h[64 s] (h = the
 // wave's array + l).  The column of a lane is 8 bytes wide, so whatever slots the 64 lanes address, a 32-lane group
 // of a ds_read_b64 touches 32 distinct bank pairs and a 16-lane group of a ds_write_b64 sixteen: no conflicts although
@@ -3616,92 +3748,39 @@ __device__ __forceinline__ void knn_push(double *__restrict__ h, int k, double v
     }
     h[64 * i] = v;
 }
-__device__ __forceinline__ double knn_bcast(double v, int lane) {  // lane is wave-uniform
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readlane((int)b, lane), hi = __builtin_amdgcn_readlane((int)(b >> 32), lane);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned long long)(unsigned)lo);
-}
-// the 64 bodies at the key ranks base .. base + 63, one per lane (ranks outside [0, n) hold zeros and are never used)
-struct KnnGroup {
-    double x, y, z, m;
-    int64_t base;
-};
-__device__ __forceinline__ KnnGroup knn_group(const Bodies &cur, const uint32_t *__restrict__ perm, int64_t base, int64_t n) {
-    KnnGroup g{0.0, 0.0, 0.0, 0.0, base};
-    const int64_t r = base + (int64_t)(threadIdx.x & 63);
-    if (r >= 0 && r < n) {
-        const uint32_t j = perm[r];
-        g.x = cur.x[j]; g.y = cur.y[j]; g.z = cur.z[j]; g.m = cur.m[j];
-    }
-    return g;
-}
-// One pass over the tree for one wave, k_potential_tree's skeleton: a wave-uniform byte cursor over `Node` and its
-// skip links, per lane `resume` = the offset up to which it sits out because it pruned an ancestor; the wave
-// descends while any active lane cannot prune.  `bound` is what a lane prunes against, strictly: a subtree is
-// skipped only if the lower bound EXCEEDS it, so bodies AT the bound are always reached.  Shared by K16 and K17.
-// The cursor starts at byte offset `start` (0: the root; the offset of a leaf: everything behind it in key order -
-// the cells that hold that leaf lie in front of it and are never tested, so nothing of theirs is pruned).
-// Leaves of the ranks [ex_lo, ex_hi) are skipped: the caller has dealt with those bodies (the wave's own among them,
-// which is how self is excluded by identity).  leaf(d2, row, rank) sees every other leaf a lane reaches and may
-// lower `bound`.  cell(idx, row, next_off) decides an internal cell for an active lane: true = the lane keeps it open,
-// false = it is done with the whole subtree (K16 / K17: pruned; K18 may also have counted it).
-template <class Cell, class Leaf>
-__device__ __forceinline__ void query_walk_cells(const Node *__restrict__ nodes, const double4 *__restrict__ rows,
-                                           const int32_t *__restrict__ node_ref, unsigned start, unsigned nn, bool valid,
-                                           double qx, double qy, double qz, int64_t ex_lo, int64_t ex_hi, long long &evals,
-                                           Cell cell, Leaf leaf) {
-    unsigned resume = valid ? 0u : 0xffffffffu;
-    unsigned off = start;
-    while (off < nn) {
-        off = __builtin_amdgcn_readfirstlane(off);
-        const unsigned idx = off / kNodeBytes;
-        const Node nd = nodes[idx];
-        const double4 row = rows[idx];
-        const bool active = resume <= off;
-        if (__float_as_int(nd.s2t) == 0) {  // a leaf
-            const int64_t r = node_ref[idx];
-            if (active && (r < ex_lo || r >= ex_hi)) {
-                const double d2 = knn_d2(row.x, row.y, row.z, qx, qy, qz);
+// The seeded ranks: every other body of the three groups (the wave's own 64 bodies and the 64 before and after them in key
+// order), exchanged through readlane.  f(d2, mass of that body).
+template <class Body>
+__device__ __forceinline__ void knn_seed(const QueryGroup (&grp)[3], const QueryCtx &C, int64_t n, long long &evals, Body f) {
+#pragma unroll
+    for (int g = 0; g < 3; g++) {
+        for (int i = 0; i < 64; i++) {
+            const int64_t r = grp[g].base + i;
+            if (r < 0 || r >= n) continue;
+            const double d2 = query_d2(query_bcast(grp[g].x, i), query_bcast(grp[g].y, i), query_bcast(grp[g].z, i), C.qx, C.qy, C.qz);
+            const double m = query_bcast(grp[g].m, i);
+            if (C.valid && r != C.rank) {
                 evals++;
-                leaf(d2, row, r);
+                f(d2, m);
             }
-            off += kNodeBytes;
-        } else {
-            bool open = false;
-            if (active) {
-                open = cell(idx, row, nd.next_off);
-                if (!open) resume = nd.next_off;
-            }
-            off = __builtin_amdgcn_ballot_w64(open) ? off + kNodeBytes : nd.next_off;
         }
     }
-}
-// K16 / K17: a cell is open unless its lower bound exceeds `bound`
-template <class Leaf>
-__device__ __forceinline__ void query_walk(const Node *__restrict__ nodes, const double4 *__restrict__ rows,
-                                           const int32_t *__restrict__ node_ref, unsigned start, unsigned nn, bool valid,
-                                           double qx, double qy, double qz, int64_t ex_lo, int64_t ex_hi, const double &bound,
-                                           long long &evals, Leaf leaf) {
-    query_walk_cells(nodes, rows, node_ref, start, nn, valid, qx, qy, qz, ex_lo, ex_hi, evals,
-                     [&](unsigned, const double4 &row, unsigned) { return !(knn_lower(row, qx, qy, qz) > bound); }, leaf);
 }
 // K16's two passes:
 //   kSum = false  bound = the lane's current k-th candidate (the heap's root), leaves are pushed
 //   kSum = true   bound = r2_k, fixed; leaves with d2 <= r2_k add their mass to `acc`
 template <bool kSum>
 __device__ __forceinline__ void knn_walk(const Node *__restrict__ nodes, const double4 *__restrict__ rows,
-                                         const int32_t *__restrict__ node_ref, unsigned nn, bool valid, double qx, double qy,
-                                         double qz, int64_t ex_lo, int64_t ex_hi, double *__restrict__ h, int k, double &bound,
-                                         double &acc, long long &evals) {
-    query_walk(nodes, rows, node_ref, 0u, nn, valid, qx, qy, qz, ex_lo, ex_hi, bound, evals,
-               [&](double d2, const double4 &row, int64_t) {
-                   if (kSum) {
-                       if (d2 <= bound) acc = __dadd_rn(acc, row.w);
-                   } else if (d2 < bound) {
-                       knn_push(h, k, d2);
-                       bound = h[0];
-                   }
-               });
+                                         const int32_t *__restrict__ node_ref, const QueryCtx &C, int64_t ex_lo, int64_t ex_hi,
+                                         double *__restrict__ h, int k, double &bound, double &acc, long long &evals) {
+    query_walk(nodes, rows, node_ref, 0u, C, ex_lo, ex_hi, bound, evals, [&](double d2, const double4 &row, int64_t) {
+        if (kSum) {
+            if (d2 <= bound) acc = __dadd_rn(acc, row.w);
+        } else if (d2 < bound) {
+            knn_push(h, k, d2);
+            bound = h[0];
+        }
+    });
 }
 // One wave per 64 key-adjacent bodies, in one launch:
 //   seed     exact distances to the wave's own 64 bodies and the 64 before and after them in key order (Hilbert
@@ -3710,78 +3789,40 @@ __device__ __forceinline__ void knn_walk(const Node *__restrict__ nodes, const d
 //            of the multiset (each body is looked at once: no duplicates; ties only ever compare by value)
 //   phase 2  mass_k = m_i + the masses at d2 <= r2_k: the seeded ranks again, then a second walk against the fixed bound
 // Results land at the body's state row j = perm[rank]; evals (may be null) counts the distances of all three parts.
-__global__ __launch_bounds__(kKnnBlock) void k_knn(const Node *__restrict__ nodes, const double4 *__restrict__ rows,
-                                                   const int32_t *__restrict__ node_ref, const TreeInfo *__restrict__ info,
-                                                   const uint32_t *__restrict__ perm, Bodies cur, int64_t n, int k,
-                                                   double *__restrict__ r2_out, double *__restrict__ mass_out,
-                                                   unsigned long long *__restrict__ evals_out) {
+__global__ __launch_bounds__(kQueryBlock) void k_knn(const Node *__restrict__ nodes, const double4 *__restrict__ rows,
+                                                     const int32_t *__restrict__ node_ref, const TreeInfo *__restrict__ info,
+                                                     const uint32_t *__restrict__ perm, Bodies cur, int64_t n, int k,
+                                                     double *__restrict__ r2_out, double *__restrict__ mass_out,
+                                                     unsigned long long *__restrict__ evals_out) {
     extern __shared__ double knn_lds[];  // [k][64]
-    if (info->error != 0 || info->sticky_error != 0) return;
-    const int lane = threadIdx.x;
-    const int64_t w0 = (int64_t)blockIdx.x * kKnnBlock, rank = w0 + lane;
-    const bool valid = rank < n;
-    const unsigned nn = __builtin_amdgcn_readfirstlane((unsigned)info->num_nodes * kNodeBytes);
-    double *h = knn_lds + lane;
+    const QueryCtx C = query_prologue(info, cur, perm, n);
+    if (C.frozen) return;
+    const int64_t w0 = C.w0;
+    double *h = knn_lds + C.lane;
     for (int s = 0; s < k; s++) h[64 * s] = INFINITY;
-    const KnnGroup grp[3] = {knn_group(cur, perm, w0, n), knn_group(cur, perm, w0 - 64, n), knn_group(cur, perm, w0 + 64, n)};
-    const double qx = grp[0].x, qy = grp[0].y, qz = grp[0].z;
+    const QueryGroup grp[3] = {C.own, query_group(cur, perm, w0 - 64, n), query_group(cur, perm, w0 + 64, n)};
     const int64_t ex_lo = w0 - 64 > 0 ? w0 - 64 : 0, ex_hi = w0 + 128 < n ? w0 + 128 : n;
     long long evals = 0;
     double bound = INFINITY, acc = 0.0;
-#pragma unroll
-    for (int g = 0; g < 3; g++) {
-        for (int i = 0; i < 64; i++) {
-            const int64_t r = grp[g].base + i;
-            if (r < 0 || r >= n) continue;
-            const double d2 = knn_d2(knn_bcast(grp[g].x, i), knn_bcast(grp[g].y, i), knn_bcast(grp[g].z, i), qx, qy, qz);
-            if (valid && r != rank) {
-                evals++;
-                if (d2 < bound) {
-                    knn_push(h, k, d2);
-                    bound = h[0];
-                }
-            }
+    knn_seed(grp, C, n, evals, [&](double d2, double) {
+        if (d2 < bound) {
+            knn_push(h, k, d2);
+            bound = h[0];
         }
-    }
-    knn_walk<false>(nodes, rows, node_ref, nn, valid, qx, qy, qz, ex_lo, ex_hi, h, k, bound, acc, evals);
+    });
+    knn_walk<false>(nodes, rows, node_ref, C, ex_lo, ex_hi, h, k, bound, acc, evals);
     const double r2k = bound;
-    acc = grp[0].m;
-#pragma unroll
-    for (int g = 0; g < 3; g++) {
-        for (int i = 0; i < 64; i++) {
-            const int64_t r = grp[g].base + i;
-            if (r < 0 || r >= n) continue;
-            const double d2 = knn_d2(knn_bcast(grp[g].x, i), knn_bcast(grp[g].y, i), knn_bcast(grp[g].z, i), qx, qy, qz);
-            const double m = knn_bcast(grp[g].m, i);
-            if (valid && r != rank) {
-                evals++;
-                if (d2 <= r2k) acc = __dadd_rn(acc, m);
-            }
-        }
-    }
-    knn_walk<true>(nodes, rows, node_ref, nn, valid, qx, qy, qz, ex_lo, ex_hi, h, k, bound, acc, evals);
-    if (valid) {
-        const uint32_t j = perm[rank];
+    acc = C.own.m;
+    knn_seed(grp, C, n, evals, [&](double d2, double m) {
+        if (d2 <= r2k) acc = __dadd_rn(acc, m);
+    });
+    knn_walk<true>(nodes, rows, node_ref, C, ex_lo, ex_hi, h, k, bound, acc, evals);
+    if (C.valid) {
+        const uint32_t j = perm[C.rank];
         r2_out[j] = r2k;
         mass_out[j] = acc;
     }
-    if (evals_out) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) evals += __shfl_xor(evals, o);
-        if (lane == 0) atomicAdd(evals_out, (unsigned long long)evals);
-    }
-}
-// After the query: the tree header as it stood before the query's build - except that a capacity error of that build
-// stays behind in the sticky words, to be reported by the next call that looks, as a step's is.
-__global__ void k_knn_restore(TreeInfo *info, const TreeInfo *__restrict__ saved) {
-    if (threadIdx.x != 0) return;
-    const int err = info->error | info->sticky_error;
-    const long long nodes = info->sticky_error ? info->sticky_nodes : info->num_nodes;
-    *info = *saved;
-    if (err && info->sticky_error == 0) {
-        info->sticky_error = 1;
-        info->sticky_nodes = nodes;
-    }
+    if (evals_out) query_wave_add(evals_out, evals, C.lane);
 }
 // state rows -> the caller's order (id), any of the three outputs
 __global__ __launch_bounds__(kBlock) void k_knn_out(const double *__restrict__ r2, const double *__restrict__ mass,
@@ -3798,8 +3839,8 @@ __global__ __launch_bounds__(kBlock) void k_knn_out(const double *__restrict__ r
 
 // ---------------------------------------------------------------------------------------
 // K17: friends-of-friends groups (nbmi_fof / nbmi_fof_catalogue / nbmi_compute_group_colors; include/nbmi.h, DESIGN.md
-// section 4.15).  The build, the node rows, d2, the lower bound and the walk are K16's; new are the fixed-radius pair
-// search, a lock-free union-find over key ranks and the per-group reductions.
+// section 4.15).  On top of the shared part: the fixed-radius pair search, a lock-free union-find over key ranks and the
+// per-group reductions.
 // ---------------------------------------------------------------------------------------
 // The union-find.  parent[] is int32 over key ranks, parent[r] = r before the link kernel.  Invariants:
 //   (a) A store only ever LOWERS parent[r] (a root is hooked under a smaller rank by a CAS, path halving is an atomic
@@ -3857,61 +3898,35 @@ __device__ __forceinline__ void fof_link_lanes(int32_t *parent, bool link, int &
     const int joined = __builtin_amdgcn_readlane(mine, leader);
     if (follows) mine = joined;
 }
-constexpr int kFofBlock = 64;  // one wave per workgroup, as K16
-// parent / minid / cnt of every rank, and for every wave the node index of its first body's leaf (the node array is
-// in key order: everything of a higher rank lies behind that leaf)
-__global__ __launch_bounds__(kBlock) void k_fof_init(const Node *__restrict__ nodes, const int32_t *__restrict__ node_ref,
-                                                     const TreeInfo *__restrict__ info, int64_t n, int64_t capacity,
-                                                     int32_t *__restrict__ parent, int32_t *__restrict__ minid,
-                                                     int32_t *__restrict__ cnt, uint32_t *__restrict__ wleaf) {
-    const int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (idx < n) {
-        parent[idx] = (int32_t)idx;
-        minid[idx] = INT32_MAX;
-        cnt[idx] = 0;
-    }
-    if (info->error != 0 || info->sticky_error != 0) return;
-    if (idx >= info->num_nodes || idx >= capacity) return;
-    if (__float_as_int(nodes[idx].s2t) != 0) return;
-    const int32_t r = node_ref[idx];
-    if ((r & 63) == 0) wleaf[r >> 6] = (uint32_t)idx;
+// parent / minid / cnt of every rank
+__global__ __launch_bounds__(kBlock) void k_fof_init(int64_t n, int32_t *__restrict__ parent, int32_t *__restrict__ minid,
+                                                     int32_t *__restrict__ cnt) {
+    const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (r >= n) return;
+    parent[r] = (int32_t)r;
+    minid[r] = INT32_MAX;
+    cnt[r] = 0;
 }
-// The pair search: one wave per 64 key-adjacent bodies.  Pairs inside the wave are tested directly (the bodies go round
-// by readlane, each pair once: the higher lane tests the lower); every other pair is found by the walk against the
-// fixed bound b2 - a cell is pruned only if knn_lower EXCEEDS b2, so a pair AT the linking length is always reached.
-// The cursor starts at the leaf of the wave's first body and the wave's own ranks are skipped: the wave sees exactly
-// the bodies of a higher rank, every pair of two waves is found once, by the lower wave.
+// The pair search: one wave per 64 key-adjacent bodies.  Pairs inside the wave are tested directly (query_half_search);
+// every other pair is found by the walk against the fixed bound b2 - a cell is pruned only if query_lower EXCEEDS b2, so a
+// pair AT the linking length is always reached.  The cursor starts at the leaf of the wave's first body and the wave's own
+// ranks are skipped: the wave sees exactly the bodies of a higher rank, every pair of two waves is found once, by the lower
+// wave.
 // Every link found goes to fof_link_lanes, which unites the two sets.  evals (may be null) counts the distances evaluated.
-__global__ __launch_bounds__(kFofBlock) void k_fof_link(const Node *__restrict__ nodes, const double4 *__restrict__ rows,
-                                                        const int32_t *__restrict__ node_ref, const TreeInfo *__restrict__ info,
-                                                        const uint32_t *__restrict__ perm, Bodies cur, int64_t n, double b2,
-                                                        const uint32_t *__restrict__ wleaf, int32_t *parent,
-                                                        unsigned long long *__restrict__ evals_out) {
-    if (info->error != 0 || info->sticky_error != 0) return;
-    const int lane = threadIdx.x;
-    const int64_t w0 = (int64_t)blockIdx.x * kFofBlock, rank = w0 + lane;
-    const bool valid = rank < n;
-    const unsigned nn = __builtin_amdgcn_readfirstlane((unsigned)info->num_nodes * kNodeBytes);
-    const KnnGroup own = knn_group(cur, perm, w0, n);
-    const double qx = own.x, qy = own.y, qz = own.z;
+__global__ __launch_bounds__(kQueryBlock) void k_fof_link(const Node *__restrict__ nodes, const double4 *__restrict__ rows,
+                                                          const int32_t *__restrict__ node_ref, const TreeInfo *__restrict__ info,
+                                                          const uint32_t *__restrict__ perm, Bodies cur, int64_t n, double b2,
+                                                          const uint32_t *__restrict__ wleaf, int32_t *parent,
+                                                          unsigned long long *__restrict__ evals_out) {
+    const QueryCtx C = query_prologue(info, cur, perm, n);
+    if (C.frozen) return;
     long long evals = 0;
-    int mine = (int)rank;  // an ancestor of this lane's rank (fof_link_lanes)
-    for (int i = 0; i < 63; i++) {
-        if (w0 + i >= n) break;
-        const double d2 = knn_d2(knn_bcast(own.x, i), knn_bcast(own.y, i), knn_bcast(own.z, i), qx, qy, qz);
-        if (valid && lane > i) {
-            evals++;
-            fof_link_lanes(parent, d2 <= b2, mine, (int)(w0 + i));
-        }
-    }
+    int mine = (int)C.rank;  // an ancestor of this lane's rank (fof_link_lanes)
+    query_half_search(C, n, evals, [&](double d2, int64_t r) { fof_link_lanes(parent, d2 <= b2, mine, (int)r); });
     const unsigned start = __builtin_amdgcn_readfirstlane(wleaf[blockIdx.x]) * kNodeBytes;
-    query_walk(nodes, rows, node_ref, start, nn, valid, qx, qy, qz, (int64_t)0, w0 + kFofBlock, b2, evals,
+    query_walk(nodes, rows, node_ref, start, C, (int64_t)0, C.w0 + kQueryBlock, b2, evals,
                [&](double d2, const double4 &, int64_t r) { fof_link_lanes(parent, d2 <= b2, mine, (int)r); });
-    if (evals_out) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) evals += __shfl_xor(evals, o);
-        if (lane == 0) atomicAdd(evals_out, (unsigned long long)evals);
-    }
+    if (evals_out) query_wave_add(evals_out, evals, C.lane);
 }
 // Behind the kernel boundary parent[] is final and read plainly: root[r] = the root of r's tree, minid[root] = the
 // smallest caller index and cnt[root] = the number of bodies below it (integer atomics: order independent).
@@ -3969,7 +3984,7 @@ __global__ __launch_bounds__(kBlock) void k_fof_labels(const TreeInfo *__restric
     if ((threadIdx.x & 63) == 0 && roots) atomicAdd(n_roots, (unsigned long long)__popcll(roots));
 }
 // group colours: the speed ramp at a hash of the label for the bodies of a group of at least min_members, grey
-// for the others.  Runs behind k_knn_restore: a build that did not fit has left its mark in the sticky word.
+// for the others.  Runs behind k_query_restore: a build that did not fit has left its mark in the sticky word.
 __global__ __launch_bounds__(kBlock) void k_fof_colors(const TreeInfo *__restrict__ info, int64_t n,
                                                        const int32_t *__restrict__ root, const int32_t *__restrict__ minid,
                                                        const int32_t *__restrict__ cnt, const uint32_t *__restrict__ perm,
@@ -4115,7 +4130,7 @@ __global__ __launch_bounds__(kFofChunk) void k_fof_chunks(int64_t n, const uint3
 // One wave per catalogue row: the group's 19 values - its row as k_fof_chunks left it, or its chunks' partials, lane l
 // taking the chunks c0 + l, c0 + l + 64, .. in this order, the lanes then combined by the halving tree - and from them
 // {M, c[3], v[3], lo[3], hi[3]}, the label and the member count.
-__global__ __launch_bounds__(kFofBlock) void k_fof_rows(int64_t n, int64_t count, const int32_t *__restrict__ qhead,
+__global__ __launch_bounds__(kQueryBlock) void k_fof_rows(int64_t n, int64_t count, const int32_t *__restrict__ qhead,
                                                         const uint32_t *__restrict__ key_s, const int32_t *__restrict__ cnt,
                                                         const int32_t *__restrict__ minid, const double *__restrict__ row_vals,
                                                         const double *__restrict__ last_part,
@@ -4136,7 +4151,7 @@ __global__ __launch_bounds__(kFofBlock) void k_fof_rows(int64_t n, int64_t count
 #pragma unroll
         for (int c = 0; c < kFofVals; c++) val[c] = fof_identity(c);
         const int64_t last_of_c1 = c1 * kFofChunk + kFofChunk - 1 < n - 1 ? c1 * kFofChunk + kFofChunk - 1 : n - 1;
-        for (int64_t ch = c0 + lane; ch <= c1; ch += kFofBlock) {
+        for (int64_t ch = c0 + lane; ch <= c1; ch += kQueryBlock) {
             const double *part = (ch < c1 || e1 == last_of_c1 ? last_part : first_part) + ch * kFofVals;
 #pragma unroll
             for (int c = 0; c < kFofVals; c++) val[c] = fof_combine(c, val[c], part[c]);
@@ -4162,11 +4177,9 @@ __global__ __launch_bounds__(kFofBlock) void k_fof_rows(int64_t n, int64_t count
 }
 
 // ---------------------------------------------------------------------------------------
-// K18: exact binned pair counts (nbmi_pair_counts; include/nbmi.h).  The build, the node rows, d2,
-// the lower bound, the walk and the half search are K16's and K17's; new are the per-cell body count, an UPPER bound on
-// the computed d2 and with both the cell that is counted whole.
+// K18: exact binned pair counts (nbmi_pair_counts; include/nbmi.h).  On top of the shared part: the
+// per-cell body count, an UPPER bound on the computed d2 and with both the cell that is counted whole.
 // ---------------------------------------------------------------------------------------
-constexpr int kPairBlock = 64;    // one wave per workgroup, as K16 / K17
 constexpr int kPairMaxBins = 64;  // nb <= 64: nb + 1 edges, nb + 1 counters per lane (`below` and the bins)
 struct PairEdges {
     double e2[kPairMaxBins + 1];  // E[k] = edges[k]^2, k <= nb (the rest unused)
@@ -4174,32 +4187,28 @@ struct PairEdges {
 // cnt[idx] = the number of bodies below node idx: its ranks are [node_ref[idx], node_ref[idx] + cnt[idx]).  The node behind
 // the subtree is next_off / kNodeBytes; k_emit_tile gives a subtree that reaches the end of the key order the link
 // num_nodes (e = n: nxt = n + pex(n) = total) - the sentinel's row, whose node_ref is -1 and is therefore NOT read: the
-// end is recognised by comparing with num_nodes.  A leaf counts 1.  Also, for every wave of 64 ranks, the node index of
-// its first body's leaf (k_fof_init's computation).
+// end is recognised by comparing with num_nodes.  A leaf counts 1.
 __global__ __launch_bounds__(kBlock) void k_pair_cells(const Node *__restrict__ nodes, const int32_t *__restrict__ node_ref,
                                                        const TreeInfo *__restrict__ info, int64_t n, int64_t capacity,
-                                                       int32_t *__restrict__ cnt, uint32_t *__restrict__ wleaf) {
+                                                       int32_t *__restrict__ cnt) {
     if (info->error != 0 || info->sticky_error != 0) return;
     const int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     const int64_t num_nodes = info->num_nodes;
     if (idx >= num_nodes || idx >= capacity) return;
-    const Node nd = nodes[idx];
-    const int64_t nx = (int64_t)(nd.next_off / kNodeBytes);
-    const int32_t r = node_ref[idx];
+    const int64_t nx = (int64_t)(nodes[idx].next_off / kNodeBytes);
     const int64_t end = nx >= num_nodes ? n : (int64_t)node_ref[nx];
-    cnt[idx] = (int32_t)(end - (int64_t)r);
-    if (__float_as_int(nd.s2t) == 0 && (r & 63) == 0) wleaf[r >> 6] = (uint32_t)idx;
+    cnt[idx] = (int32_t)(end - (int64_t)node_ref[idx]);
 }
-// knn_lower's twin: an upper bound on the COMPUTED d2 between q and every body within `w` per axis of the anchor, so that
-// knn_lower <= computed d2 <= knn_upper for every body of the cell.  u = 2^-53.  Per axis, with T = |q - a| exact and R
+// query_lower's twin: an upper bound on the COMPUTED d2 between q and every body within `w` per axis of the anchor, so that
+// query_lower <= computed d2 <= query_upper for every body of the cell.  u = 2^-53.  Per axis, with T = |q - a| exact and R
 // the body's true distance from the anchor on that axis:
 //   what the computed |dx| can exceed: nothing beyond (T + R)(1 + u) - it is one rounding of the exact |b - q| <= T + R.
 //   t = fl(T) >= T (1 - u), so T <= t (1 + 2 u).  The stored w is NOT below the true reach: that is at most 2 hs + 43
-//     half ulps of bounds < 2 hs + 2^-47 bounds (k_knn_rows), w is one rounding of 2 hs + 2^-44 bounds (both terms
+//     half ulps of bounds < 2 hs + 2^-47 bounds (k_query_rows), w is one rounding of 2 hs + 2^-44 bounds (both terms
 //     exact), which takes at most u (2 bounds + 2^-44 bounds) < 2^-51 bounds of the 2^-44 bounds.  So R <= w and
 //     computed |dx| <= (t + w)(1 + 2 u)(1 + u).
 //   s = fl(t + w) >= (t + w)(1 - u);  h = fl(s + s 2^-49) >= s (1 + 16 u)(1 - u) >= (t + w)(1 + 13 u) >= computed |dx|.
-//     (The inflation is relative to s, not to t as in knn_lower: here the roundings scale with t + w, and w may be the
+//     (The inflation is relative to s, not to t as in query_lower: here the roundings scale with t + w, and w may be the
 //     larger part.)
 //   five roundings: the computed d2 is <= (sum dx^2)(1 + u)^3 - a product and two sums above each term - with two more
 //     (1 + u) from the squared |dx|: <= (sum (T + R)^2)(1 + u)^5 <= (sum (t + w)^2)(1 + 2 u)^2 (1 + u)^5 < (sum (t + w)^2)
@@ -4211,7 +4220,7 @@ __global__ __launch_bounds__(kBlock) void k_pair_cells(const Node *__restrict__ 
 //     side) is below 2^-113 of it: inside the margin.  A value of at most 2^-960 means every h <= 2^-480 (1 + u), every
 //     computed |dx| <= h, the computed d2 < 3 x 2^-960 (1 + 4 u) + 3 x 2^-1075 < 2^-958: that is returned instead.
 //   An overflow to +inf is harmless: +inf is <= no edge, the cell is never accepted.
-__device__ __forceinline__ double knn_upper(double4 a, double qx, double qy, double qz) {
+__device__ __forceinline__ double query_upper(double4 a, double qx, double qy, double qz) {
     const double sx = __dadd_rn(fabs(__dsub_rn(a.x, qx)), a.w), sy = __dadd_rn(fabs(__dsub_rn(a.y, qy)), a.w),
                  sz = __dadd_rn(fabs(__dsub_rn(a.z, qz)), a.w);
     const double hx = __dadd_rn(sx, __dmul_rn(sx, 0x1p-49)), hy = __dadd_rn(sy, __dmul_rn(sy, 0x1p-49)),
@@ -4231,14 +4240,13 @@ __device__ __forceinline__ int pair_bin(const double *__restrict__ E, int nb, do
     }
     return pos;
 }
-// One wave per 64 key-adjacent bodies, as k_fof_link: pairs inside the wave directly (the higher lane tests
-// the lower), every other pair by the walk that starts at the wave's own first leaf and skips the leaves of the ranks
-// below w0 + 64 - the wave sees exactly the bodies of a higher rank, every pair of two waves once.  At an internal cell an
-// active lane, in this order:
-//   prunes          if knn_lower > E[nb], strictly (a pair AT the last edge is always reached)
-//   accepts whole   if knn_upper <= E[0] (all of the cell into `below`), or E[k] < knn_lower and knn_upper <= E[k + 1] (all
-//                   of it into bin k): cnt bodies without a distance.  With p = pair_bin(knn_lower) both read
-//                   knn_upper <= E[p], counter p.
+// One wave per 64 key-adjacent bodies, as k_fof_link: pairs inside the wave directly (query_half_search), every other
+// pair by the walk that starts at the wave's own first leaf and skips the leaves of the ranks below w0 + 64 - the wave
+// sees exactly the bodies of a higher rank, every pair of two waves once.  At an internal cell an active lane, in this order:
+//   prunes          if query_lower > E[nb], strictly (a pair AT the last edge is always reached)
+//   accepts whole   if query_upper <= E[0] (all of the cell into `below`), or E[k] < query_lower and query_upper <= E[k + 1] (all
+//                   of it into bin k): cnt bodies without a distance.  With p = pair_bin(query_lower) both read
+//                   query_upper <= E[p], counter p.
 //   else keeps the cell open.
 // A cell whose ranks reach below w0 + 64 is NEVER accepted whole (it may be pruned): it holds bodies of the wave itself,
 // already counted directly, the lane's own among them.  The walk begins behind the leaf of rank w0, so every cell it
@@ -4246,73 +4254,48 @@ __device__ __forceinline__ int pair_bin(const double *__restrict__ E, int nb, do
 // nothing.
 // Counters: nb + 1 uint32 per lane in LDS, [counter][lane] - consecutive lanes, consecutive words, no bank conflicts; a
 // lane counts at most n - 1 < 2^31 pairs.  The E[k] sit in LDS in front of them (the search's indices diverge by lane).
-// At the end every counter is summed over the wave in 64 bits and added to out[2 + counter] by one agent-scope integer
-// atomic per non-empty counter: integers, so the result does not depend on any order.  out[0] += distances evaluated,
-// out[1] += pairs counted through whole cells.
-__global__ __launch_bounds__(kPairBlock) void k_pair_counts(const Node *__restrict__ nodes, const double4 *__restrict__ rows,
+// At the end every counter is summed over the wave in 64 bits and added to out[2 + counter] (query_wave_add).  out[0] +=
+// distances evaluated, out[1] += pairs counted through whole cells.
+__global__ __launch_bounds__(kQueryBlock) void k_pair_counts(const Node *__restrict__ nodes, const double4 *__restrict__ rows,
                                                             const int32_t *__restrict__ node_ref,
                                                             const int32_t *__restrict__ cnt, const TreeInfo *__restrict__ info,
                                                             const uint32_t *__restrict__ perm, Bodies cur, int64_t n, int nb,
                                                             PairEdges edges, int accept, const uint32_t *__restrict__ wleaf,
                                                             unsigned long long *__restrict__ out) {
     extern __shared__ double pair_lds[];  // E[nb + 1], then uint32 [nb + 1][64]
-    if (info->error != 0 || info->sticky_error != 0) return;
-    const int lane = threadIdx.x;
-    const int64_t w0 = (int64_t)blockIdx.x * kPairBlock, rank = w0 + lane;
-    const bool valid = rank < n;
-    const unsigned nn = __builtin_amdgcn_readfirstlane((unsigned)info->num_nodes * kNodeBytes);
+    const QueryCtx C = query_prologue(info, cur, perm, n);
+    if (C.frozen) return;
     double *E = pair_lds;
-    uint32_t *c = reinterpret_cast<uint32_t *>(pair_lds + nb + 1) + lane;
+    uint32_t *c = reinterpret_cast<uint32_t *>(pair_lds + nb + 1) + C.lane;
     for (int k = 0; k <= nb; k++) {
         E[k] = edges.e2[k];  // (every lane stores the same value)
         c[64 * k] = 0u;
     }
     __syncthreads();
-    const KnnGroup own = knn_group(cur, perm, w0, n);
-    const double qx = own.x, qy = own.y, qz = own.z;
     long long evals = 0, whole = 0;
-    for (int i = 0; i < 63; i++) {
-        if (w0 + i >= n) break;
-        const double d2 = knn_d2(knn_bcast(own.x, i), knn_bcast(own.y, i), knn_bcast(own.z, i), qx, qy, qz);
-        if (valid && lane > i) {
-            evals++;
-            const int b = pair_bin(E, nb, d2);
-            if (b <= nb) c[64 * b]++;
-        }
-    }
+    const auto count = [&](double d2) {
+        const int b = pair_bin(E, nb, d2);
+        if (b <= nb) c[64 * b]++;
+    };
+    query_half_search(C, n, evals, [&](double d2, int64_t) { count(d2); });
     const unsigned start = __builtin_amdgcn_readfirstlane(wleaf[blockIdx.x]) * kNodeBytes;
-    const int64_t own_end = w0 + kPairBlock;
+    const int64_t own_end = C.w0 + kQueryBlock;
     query_walk_cells(
-        nodes, rows, node_ref, start, nn, valid, qx, qy, qz, (int64_t)0, own_end, evals,
+        nodes, rows, node_ref, start, C, (int64_t)0, own_end, evals,
         [&](unsigned idx, const double4 &row, unsigned) {
-            const int p = pair_bin(E, nb, knn_lower(row, qx, qy, qz));
+            const int p = pair_bin(E, nb, query_lower(row, C.qx, C.qy, C.qz));
             if (p > nb) return false;  // pruned
             if (!accept || (int64_t)node_ref[idx] < own_end) return true;
-            if (!(knn_upper(row, qx, qy, qz) <= E[p])) return true;
+            if (!(query_upper(row, C.qx, C.qy, C.qz) <= E[p])) return true;
             const uint32_t m = (uint32_t)cnt[idx];
             c[64 * p] += m;
             whole += (long long)m;
             return false;
         },
-        [&](double d2, const double4 &, int64_t) {
-            const int b = pair_bin(E, nb, d2);
-            if (b <= nb) c[64 * b]++;
-        });
-    for (int k = 0; k <= nb; k++) {
-        unsigned long long v = c[64 * k];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-        if (lane == 0 && v != 0ull) (void)__hip_atomic_fetch_add(out + 2 + k, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        evals += __shfl_xor(evals, o);
-        whole += __shfl_xor(whole, o);
-    }
-    if (lane == 0) {
-        (void)__hip_atomic_fetch_add(out, (unsigned long long)evals, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (whole) (void)__hip_atomic_fetch_add(out + 1, (unsigned long long)whole, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+        [&](double d2, const double4 &, int64_t) { count(d2); });
+    for (int k = 0; k <= nb; k++) query_wave_add(out + 2 + k, (long long)c[64 * k], C.lane);
+    query_wave_add(out, evals, C.lane);
+    query_wave_add(out + 1, whole, C.lane);
 }
 
 }  // namespace
@@ -4449,37 +4432,45 @@ struct nbmi_sim {
     long long *diag_partc = nullptr;  // [kDiagBlocksMax + 1] the same for the term counts
     double4 *diag_pot = nullptr;      // [node rows] float64 {cx, cy, cz, G m} of every node of the diagnostic's own build
     TreeInfo *side_info = nullptr;    // the tree header as it stood before a query's own build (SideBuild puts it back)
-    // k-nearest-neighbour query (nbmi_knn), allocated by the first call; no step touches them.
-    // 16 bytes per body (r2_k and mass_k by state row) and 32 bytes per node row (k_knn_rows)
-    double *knn_r2 = nullptr, *knn_mass = nullptr;
-    double4 *knn_rows = nullptr;
-    unsigned long long *knn_evals = nullptr;
-    // friends-of-friends groups (nbmi_fof), allocated by the first call; no step touches them.
-    // 16 bytes per body (parent, root, smallest caller index and member count by key rank), 4 bytes per 64 bodies (the
-    // waves' first leaves) and the node rows of the k-NN query
-    int32_t *fof_parent = nullptr, *fof_root = nullptr, *fof_minid = nullptr, *fof_cnt = nullptr;
-    uint32_t *fof_wleaf = nullptr;
-    unsigned long long *fof_counters = nullptr;  // [0] distances evaluated, [1] roots
-    bool fof_ready = false, fof_cat_ready = false;  // every array of the query / of the catalogue is there (set after the last allocation)
-    // its catalogue (nbmi_fof_catalogue), allocated by the first call: 24 bytes per body (sorted roots, ranks in and
-    // out, segment heads, row of a root, head of a row), the sort's temp buffer, 304 bytes per chunk of 256 bodies and
-    // 268 bytes per catalogue row (a power of two of rows, regrown - the smaller arrays freed - when a call needs more)
-    uint32_t *fof_key_s = nullptr, *fof_rank = nullptr, *fof_rank_s = nullptr, *fof_tiles = nullptr;
-    int32_t *fof_hpos = nullptr, *fof_slot = nullptr, *fof_qhead = nullptr;
-    char *fof_sort_tmp = nullptr;
-    size_t fof_sort_bytes = 0;
-    double *fof_last = nullptr, *fof_first = nullptr;
-    int64_t fof_row_cap = 0;
-    double *fof_row_vals = nullptr, *fof_out13 = nullptr;
-    int32_t *fof_label = nullptr;
-    int64_t *fof_members = nullptr;
-    // binned pair counts (nbmi_pair_counts), allocated by the first call; no step touches them.
-    // 4 bytes per node row (the cells' body counts), 4 bytes per 64 bodies (the waves' first leaves), 67 words of results
-    // and the node rows of the k-NN query
-    int32_t *pair_cnt = nullptr;
-    uint32_t *pair_wleaf = nullptr;
-    unsigned long long *pair_out = nullptr;  // [0] distances evaluated, [1] pairs counted through whole cells, [2 + c] counter c
-    bool pair_ready = false;
+    // Scratch of the tree queries; no step touches it.  Every group is allocated by the first
+    // call that needs it (query_alloc) and holds `ready` from its last allocation on.
+    struct QueryScratch {
+        struct {  // every query: 32 bytes per node row (k_query_rows), 4 bytes per 64 bodies (the waves' first leaves)
+            bool ready = false;
+            double4 *rows = nullptr;
+            uint32_t *wleaf = nullptr;
+            unsigned long long *evals = nullptr;  // distances evaluated by k_knn
+        } shared;
+        struct {  // nbmi_knn (section 4.14): 16 bytes per body (r2_k and mass_k by state row)
+            bool ready = false;
+            double *r2 = nullptr, *mass = nullptr;
+        } knn;
+        struct {  // nbmi_fof (section 4.15): 16 bytes per body (parent, root, smallest caller index and member count by key rank)
+            bool ready = false;
+            int32_t *parent = nullptr, *root = nullptr, *minid = nullptr, *cnt = nullptr;
+            unsigned long long *counters = nullptr;  // [0] distances evaluated, [1] roots
+        } fof;
+        // nbmi_fof_catalogue: 24 bytes per body (sorted roots, ranks in and out, segment heads, row of a root, head of a
+        // row), the sort's temp buffer, 304 bytes per chunk of 256 bodies and - outside `ready` - 268 bytes per catalogue
+        // row (a power of two of rows, regrown - the smaller arrays freed - when a call needs more)
+        struct {
+            bool ready = false;
+            uint32_t *key_s = nullptr, *rank = nullptr, *rank_s = nullptr, *tiles = nullptr;
+            int32_t *hpos = nullptr, *slot = nullptr, *qhead = nullptr;
+            char *sort_tmp = nullptr;
+            size_t sort_bytes = 0;
+            double *last = nullptr, *first = nullptr;
+            int64_t row_cap = 0;
+            double *row_vals = nullptr, *out13 = nullptr;
+            int32_t *label = nullptr;
+            int64_t *members = nullptr;
+        } cat;
+        struct {  // nbmi_pair_counts (section 4.16): 4 bytes per node row (the cells' body counts), 67 words of results
+            bool ready = false;
+            int32_t *cnt = nullptr;
+            unsigned long long *out = nullptr;  // [0] distances evaluated, [1] pairs counted through whole cells, [2 + c] counter c
+        } pairs;
+    } q;
     bool pair_cells = true;  // cells inside one bin are counted whole (NBMI_PAIRS_CELLS=0: never; measurement)
     // what nbmi_compute_colors / nbmi_frame_begin colour by (nbmi_set_color_mode)
     int color_mode = NBMI_COLOR_SPEED, color_k = 32;
@@ -5069,14 +5060,14 @@ struct SideBuild {
         return 0;
     }
     // r: of the build and the query's kernels.  wait (the diagnostic): the query is waited for and a capacity error of
-    // its build reported at once - check_device_error clears the words, so k_knn_restore then writes the saved header
-    // as it is.  Otherwise (k-NN) nothing waits, and k_knn_restore keeps the build's error in the sticky words for the
+    // its build reported at once - check_device_error clears the words, so k_query_restore then writes the saved header
+    // as it is.  Otherwise (k-NN) nothing waits, and k_query_restore keeps the build's error in the sticky words for the
     // next call that looks.
     int finish(int r, bool wait) {
         if (wait && r == 0) r = check_device_error(s);  // NBMI_ERR_CAPACITY: the message of a step
-        k_knn_restore<<<1, 64, 0, s->stream>>>(s->info, s->side_info);
+        k_query_restore<<<1, 64, 0, s->stream>>>(s->info, s->side_info);
         if (hipGetLastError() != hipSuccess && r == 0) {
-            nbmi::set_error("k_knn_restore launch failed");
+            nbmi::set_error("k_query_restore launch failed");
             r = NBMI_ERR_HIP;
         }
         // the same positions give the same tree: what the queries read is still that tree if it was before
@@ -5088,13 +5079,22 @@ struct SideBuild {
     }
 };
 
-// What every query of this family enqueues on the compute stream without ever waiting: inside a SideBuild the octree of
-// the current positions is built with the query rows (node_ref) and the rows are written (knn_rows: query_buffers
-// first), then `launch` adds the query's own kernels.  A capacity error of the build stays in the sticky words for the
-// next call that looks.
-int query_buffers(nbmi_sim *s) {
-    if (!s->knn_rows && (dev_alloc(s, &s->knn_rows, s->node_capacity + 2) || dev_alloc(s, &s->knn_evals, 1))) return NBMI_ERR_HIP;
+// One group of the queries' scratch (nbmi_sim::q), once: `alloc` makes its dev_allocs and returns nonzero if one failed.
+template <class Group, class Alloc>
+int query_alloc(Group &g, Alloc alloc) {
+    if (!g.ready && alloc()) return NBMI_ERR_HIP;
+    g.ready = true;
     return 0;
+}
+// What every query of this family enqueues on the compute stream without ever waiting: inside a SideBuild the octree of
+// the current positions is built with the query rows (node_ref), the rows and the waves' first leaves are written
+// (query_buffers first), then `launch` adds the query's own kernels.  A capacity error of the build stays in the sticky
+// words for the next call that looks.
+int query_buffers(nbmi_sim *s) {
+    auto &g = s->q.shared;
+    return query_alloc(g, [&] {
+        return dev_alloc(s, &g.rows, s->node_capacity + 2) || dev_alloc(s, &g.wleaf, (s->n + 63) / 64) || dev_alloc(s, &g.evals, 1);
+    });
 }
 template <class Launch>
 int query_enqueue(nbmi_sim *s, const char *what, Launch launch) {
@@ -5102,8 +5102,9 @@ int query_enqueue(nbmi_sim *s, const char *what, Launch launch) {
     if (side.rc) return side.rc;
     int rc = enqueue_tree(s);
     if (rc == 0) {
-        k_knn_rows<<<nblocks(s->own_node_rows), kBlock, 0, s->stream>>>(s->nodes, s->nodes64, s->node_ref, s->perm,
-                                                                         s->buf[s->curbuf], s->info, s->own_node_rows, s->knn_rows);
+        k_query_rows<<<nblocks(s->own_node_rows), kBlock, 0, s->stream>>>(s->nodes, s->nodes64, s->node_ref, s->perm,
+                                                                           s->buf[s->curbuf], s->info, s->own_node_rows,
+                                                                           s->q.shared.rows, s->q.shared.wleaf);
         launch();
         if (hipGetLastError() != hipSuccess) {
             nbmi::set_error("%s launch failed", what);
@@ -5111,6 +5112,26 @@ int query_enqueue(nbmi_sim *s, const char *what, Launch launch) {
         }
     }
     return side.finish(rc, false);
+}
+// The synchronous form of a query: errors of earlier steps first, as a getter reports them, then the query (`enqueue`,
+// one of the *_enqueue forms, which never wait) and its own.
+template <class Enqueue>
+int query_sync(nbmi_sim *s, Enqueue enqueue) {
+    NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
+    if (int rc = check_device_error(s)) return rc;
+    if (int rc = enqueue()) return rc;
+    NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
+    return check_device_error(s);
+}
+// Which handles have the tree the queries walk: every other is refused as `what`.
+int query_refuse(const nbmi_sim *s, const char *what) {
+    const char *why = s->method != NBMI_METHOD_BARNES_HUT ? "direct N^2 handles have no tree"
+                      : s->owner ? "owner-mode handles are not supported (the neighbours may live on other ranks)"
+                      : s->shard_begin != 0 || s->shard_end != s->n ? "sharded handles are not supported"
+                                                                    : nullptr;
+    if (!why) return 0;
+    nbmi::set_error("%s: %s", what, why);
+    return NBMI_ERR_ARG;
 }
 
 }  // namespace
@@ -5453,7 +5474,7 @@ int nbmi_compute_colors(nbmi_sim *s, double max_speed) {
     if (s->color_mode == NBMI_COLOR_DENSITY) {  // (only handles the query accepts get into this mode; nothing waits)
         if (int rc = knn_check(s, s->color_k, "nbmi_compute_colors")) return rc;
         if (int rc = knn_enqueue(s, s->color_k, false)) return rc;
-        k_colors_density<<<nblocks(s->n), kBlock, 0, s->stream>>>(s->buf[s->curbuf], s->n, s->knn_r2, s->knn_mass, s->color_lo,
+        k_colors_density<<<nblocks(s->n), kBlock, 0, s->stream>>>(s->buf[s->curbuf], s->n, s->q.knn.r2, s->q.knn.mass, s->color_lo,
                                                                   s->color_hi, s->colors);
         NBMI_HIP_CHECK(hipGetLastError());
         return 0;
@@ -5709,61 +5730,43 @@ int nbmi_get_potentials_f64(nbmi_sim *s, double *out) {
 }
 
 namespace {
-// nbmi_knn and everything built on it: which handles have the tree the query walks
-const char *knn_refusal(const nbmi_sim *s) {
-    if (s->method != NBMI_METHOD_BARNES_HUT) return "direct N^2 handles have no tree";
-    if (s->owner) return "owner-mode handles are not supported (the neighbours may live on other ranks)";
-    if (s->shard_begin != 0 || s->shard_end != s->n) return "sharded handles are not supported";
-    return nullptr;
-}
 int knn_check(nbmi_sim *s, int k, const char *what) {
-    if (const char *why = knn_refusal(s)) {
-        nbmi::set_error("%s: %s", what, why);
-        return NBMI_ERR_ARG;
-    }
+    if (int rc = query_refuse(s, what)) return rc;
     if (k < 1 || k > kKnnMaxK || (int64_t)k > s->n - 1) {
         nbmi::set_error("%s: k = %d is outside 1 .. min(%d, N - 1) (N = %lld)", what, k, kKnnMaxK, (long long)s->n);
         return NBMI_ERR_ARG;
     }
     return 0;
 }
-// The k-NN query: r2_k and mass_k are in knn_r2 / knn_mass by state row afterwards.  `count`: also sum the evaluated
-// distances into knn_evals.
+// The k-NN query: r2_k and mass_k are in q.knn.r2 / q.knn.mass by state row afterwards.  `count`: also sum the evaluated
+// distances into q.shared.evals.
 int knn_enqueue(nbmi_sim *s, int k, bool count) {
     const int64_t n = s->n;
-    if (query_buffers(s) || (!s->knn_r2 && (dev_alloc(s, &s->knn_r2, n) || dev_alloc(s, &s->knn_mass, n)))) return NBMI_ERR_HIP;
+    auto &g = s->q.knn;
+    if (query_buffers(s) || query_alloc(g, [&] { return dev_alloc(s, &g.r2, n) || dev_alloc(s, &g.mass, n); })) return NBMI_ERR_HIP;
     hipStream_t st = s->stream;
-    if (count) NBMI_HIP_CHECK(hipMemsetAsync(s->knn_evals, 0, sizeof(unsigned long long), st));
+    if (count) NBMI_HIP_CHECK(hipMemsetAsync(s->q.shared.evals, 0, sizeof(unsigned long long), st));
     return query_enqueue(s, "k_knn", [&] {
-        k_knn<<<(int)((n + kKnnBlock - 1) / kKnnBlock), kKnnBlock, (size_t)k * kKnnBlock * sizeof(double), st>>>(
-            s->nodes, s->knn_rows, s->node_ref, s->info, s->perm, s->buf[s->curbuf], n, k, s->knn_r2, s->knn_mass,
-            count ? s->knn_evals : nullptr);
+        k_knn<<<(int)((n + kQueryBlock - 1) / kQueryBlock), kQueryBlock, (size_t)k * kQueryBlock * sizeof(double), st>>>(
+            s->nodes, s->q.shared.rows, s->node_ref, s->info, s->perm, s->buf[s->curbuf], n, k, g.r2, g.mass,
+            count ? s->q.shared.evals : nullptr);
     });
-}
-// the synchronous form behind nbmi_knn / nbmi_get_densities_f64: errors of earlier steps first, as a getter reports
-// them, then the query and its own
-int knn_query(nbmi_sim *s, int k, bool count) {
-    NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
-    if (int rc = check_device_error(s)) return rc;
-    if (int rc = knn_enqueue(s, k, count)) return rc;
-    NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
-    return check_device_error(s);
 }
 }  // namespace
 
 int nbmi_knn(nbmi_sim *s, int k, double *r2_k, double *mass_k, int64_t *evals) {
     if (int rc = check_handle(s)) return rc;
     if (int rc = knn_check(s, k, "nbmi_knn")) return rc;
-    if (int rc = knn_query(s, k, evals != nullptr)) return rc;
+    if (int rc = query_sync(s, [&] { return knn_enqueue(s, k, evals != nullptr); })) return rc;
     const int64_t n = s->n;
     double *o_r2 = (double *)s->stage, *o_mass = o_r2 + n;
-    k_knn_out<<<nblocks(n), kBlock, 0, s->stream>>>(s->knn_r2, s->knn_mass, s->buf[s->curbuf].id, n, r2_k ? o_r2 : nullptr,
+    k_knn_out<<<nblocks(n), kBlock, 0, s->stream>>>(s->q.knn.r2, s->q.knn.mass, s->buf[s->curbuf].id, n, r2_k ? o_r2 : nullptr,
                                                     mass_k ? o_mass : nullptr, nullptr);
     NBMI_HIP_CHECK(hipGetLastError());
     if (r2_k) NBMI_HIP_CHECK(hipMemcpyAsync(r2_k, o_r2, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     if (mass_k) NBMI_HIP_CHECK(hipMemcpyAsync(mass_k, o_mass, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     unsigned long long ev = 0;
-    if (evals) NBMI_HIP_CHECK(hipMemcpyAsync(&ev, s->knn_evals, sizeof(ev), hipMemcpyDeviceToHost, s->stream));
+    if (evals) NBMI_HIP_CHECK(hipMemcpyAsync(&ev, s->q.shared.evals, sizeof(ev), hipMemcpyDeviceToHost, s->stream));
     NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
     if (evals) *evals = (int64_t)ev;
     return 0;
@@ -5773,9 +5776,9 @@ int nbmi_get_densities_f64(nbmi_sim *s, int k, double *rho) {
     if (int rc = check_handle(s)) return rc;
     if (int rc = knn_check(s, k, "nbmi_get_densities_f64")) return rc;
     if (int rc = require_out(rho)) return rc;
-    if (int rc = knn_query(s, k, false)) return rc;
+    if (int rc = query_sync(s, [&] { return knn_enqueue(s, k, false); })) return rc;
     const int64_t n = s->n;
-    k_knn_out<<<nblocks(n), kBlock, 0, s->stream>>>(s->knn_r2, s->knn_mass, s->buf[s->curbuf].id, n, nullptr, nullptr,
+    k_knn_out<<<nblocks(n), kBlock, 0, s->stream>>>(s->q.knn.r2, s->q.knn.mass, s->buf[s->curbuf].id, n, nullptr, nullptr,
                                                     (double *)s->stage);
     NBMI_HIP_CHECK(hipGetLastError());
     NBMI_HIP_CHECK(hipMemcpyAsync(rho, s->stage, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
@@ -5786,10 +5789,7 @@ int nbmi_get_densities_f64(nbmi_sim *s, int k, double *rho) {
 namespace {
 // nbmi_fof and everything built on it: the handles the k-NN query accepts, a positive finite linking length
 int fof_check(nbmi_sim *s, double link, int64_t min_members, int64_t capacity, const char *what) {
-    if (const char *why = knn_refusal(s)) {
-        nbmi::set_error("%s: %s", what, why);
-        return NBMI_ERR_ARG;
-    }
+    if (int rc = query_refuse(s, what)) return rc;
     if (!isfinite(link) || !(link > 0.0)) {
         nbmi::set_error("%s: the linking length %g is not finite and > 0", what, link);
         return NBMI_ERR_ARG;
@@ -5804,71 +5804,59 @@ int fof_check(nbmi_sim *s, double link, int64_t min_members, int64_t capacity, c
     }
     return 0;
 }
-// Enqueues build, pair search and flattening and never waits.  Afterwards, by key rank: fof_root, fof_minid[root] (the
-// label), fof_cnt[root]; fof_counters = {distances evaluated (if `count`), roots}; `labels` (device, may be null) in the
-// caller's order.
+// Enqueues build, pair search and flattening and never waits.  Afterwards, by key rank: q.fof.root, minid[root] (the
+// label), cnt[root]; counters = {distances evaluated (if `count`), roots}; `labels` (device, may be null) in the caller's
+// order.
 int fof_enqueue(nbmi_sim *s, double b2, bool count, int32_t *labels) {
     const int64_t n = s->n;
-    if (query_buffers(s)) return NBMI_ERR_HIP;
-    if (!s->fof_ready) {
-        if (dev_alloc(s, &s->fof_parent, n) || dev_alloc(s, &s->fof_root, n) || dev_alloc(s, &s->fof_minid, n) ||
-            dev_alloc(s, &s->fof_cnt, n) || dev_alloc(s, &s->fof_wleaf, (n + 63) / 64) || dev_alloc(s, &s->fof_counters, 2))
-            return NBMI_ERR_HIP;
-        s->fof_ready = true;
-    }
+    auto &g = s->q.fof;
+    if (query_buffers(s) || query_alloc(g, [&] {
+            return dev_alloc(s, &g.parent, n) || dev_alloc(s, &g.root, n) || dev_alloc(s, &g.minid, n) ||
+                   dev_alloc(s, &g.cnt, n) || dev_alloc(s, &g.counters, 2);
+        }))
+        return NBMI_ERR_HIP;
     hipStream_t st = s->stream;
-    NBMI_HIP_CHECK(hipMemsetAsync(s->fof_counters, 0, 2 * sizeof(unsigned long long), st));
+    NBMI_HIP_CHECK(hipMemsetAsync(g.counters, 0, 2 * sizeof(unsigned long long), st));
     return query_enqueue(s, "k_fof_link", [&] {
         const Bodies cur = s->buf[s->curbuf];
-        const int64_t rows = s->own_node_rows > n ? s->own_node_rows : n;
-        k_fof_init<<<nblocks(rows), kBlock, 0, st>>>(s->nodes, s->node_ref, s->info, n, s->own_node_rows, s->fof_parent,
-                                                     s->fof_minid, s->fof_cnt, s->fof_wleaf);
-        k_fof_link<<<(int)((n + kFofBlock - 1) / kFofBlock), kFofBlock, 0, st>>>(
-            s->nodes, s->knn_rows, s->node_ref, s->info, s->perm, cur, n, b2, s->fof_wleaf, s->fof_parent,
-            count ? s->fof_counters : nullptr);
-        k_fof_flatten<<<nblocks(n), kBlock, 0, st>>>(s->info, n, s->fof_parent, s->perm, cur.id, s->fof_root, s->fof_minid,
-                                                     s->fof_cnt);
-        k_fof_labels<<<nblocks(n), kBlock, 0, st>>>(s->info, n, s->fof_root, s->fof_minid, s->perm, cur.id, labels,
-                                                    s->fof_counters + 1);
+        k_fof_init<<<nblocks(n), kBlock, 0, st>>>(n, g.parent, g.minid, g.cnt);
+        k_fof_link<<<(int)((n + kQueryBlock - 1) / kQueryBlock), kQueryBlock, 0, st>>>(
+            s->nodes, s->q.shared.rows, s->node_ref, s->info, s->perm, cur, n, b2, s->q.shared.wleaf, g.parent,
+            count ? g.counters : nullptr);
+        k_fof_flatten<<<nblocks(n), kBlock, 0, st>>>(s->info, n, g.parent, s->perm, cur.id, g.root, g.minid, g.cnt);
+        k_fof_labels<<<nblocks(n), kBlock, 0, st>>>(s->info, n, g.root, g.minid, s->perm, cur.id, labels, g.counters + 1);
     });
 }
-// the synchronous form, as knn_query
-int fof_query(nbmi_sim *s, double b2, bool count, int32_t *labels) {
-    NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
-    if (int rc = check_device_error(s)) return rc;
-    if (int rc = fof_enqueue(s, b2, count, labels)) return rc;
-    NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
-    return check_device_error(s);
-}
 int fof_catalogue_buffers(nbmi_sim *s) {
-    if (s->fof_cat_ready) return 0;
+    auto &g = s->q.cat;
     const int64_t n = s->n, chunks = (n + kFofChunk - 1) / kFofChunk;
-    if (dev_alloc(s, &s->fof_key_s, n) || dev_alloc(s, &s->fof_rank, n) || dev_alloc(s, &s->fof_rank_s, n) ||
-        dev_alloc(s, &s->fof_hpos, n) || dev_alloc(s, &s->fof_slot, n) || dev_alloc(s, &s->fof_qhead, n) ||
-        dev_alloc(s, &s->fof_tiles, scan::tiles_for(n) + 1) || dev_alloc(s, &s->fof_last, chunks * kFofVals) ||
-        dev_alloc(s, &s->fof_first, chunks * kFofVals))
-        return NBMI_ERR_HIP;
-    s->fof_sort_bytes = nbmi::radix_temp_bytes_u32((size_t)n, 32);
-    if (dev_alloc(s, &s->fof_sort_tmp, s->fof_sort_bytes + 256)) return NBMI_ERR_HIP;
-    NBMI_HIP_CHECK(nbmi::radix_init_temp(s->fof_sort_tmp, s->stream));
-    s->fof_cat_ready = true;
-    return 0;
+    return query_alloc(g, [&]() -> int {
+        g.sort_bytes = nbmi::radix_temp_bytes_u32((size_t)n, 32);
+        if (dev_alloc(s, &g.key_s, n) || dev_alloc(s, &g.rank, n) || dev_alloc(s, &g.rank_s, n) || dev_alloc(s, &g.hpos, n) ||
+            dev_alloc(s, &g.slot, n) || dev_alloc(s, &g.qhead, n) || dev_alloc(s, &g.tiles, scan::tiles_for(n) + 1) ||
+            dev_alloc(s, &g.last, chunks * kFofVals) || dev_alloc(s, &g.first, chunks * kFofVals) ||
+            dev_alloc(s, &g.sort_tmp, g.sort_bytes + 256))
+            return NBMI_ERR_HIP;
+        NBMI_HIP_CHECK(nbmi::radix_init_temp(g.sort_tmp, s->stream));
+        return 0;
+    });
 }
 // The catalogue's row arrays for at least `rows` rows, in powers of two.  Arrays that are too small are freed: the
 // caller has just waited for the stream, and nothing enqueued reads them.
 int fof_row_buffers(nbmi_sim *s, int64_t rows) {
-    if (rows <= s->fof_row_cap) return 0;
-    s->fof_row_cap = 0;
-    dev_free(s, &s->fof_row_vals);
-    dev_free(s, &s->fof_out13);
-    dev_free(s, &s->fof_label);
-    dev_free(s, &s->fof_members);
+    auto &g = s->q.cat;
+    if (rows <= g.row_cap) return 0;
+    g.row_cap = 0;
+    dev_free(s, &g.row_vals);
+    dev_free(s, &g.out13);
+    dev_free(s, &g.label);
+    dev_free(s, &g.members);
     int64_t cap = 1024;
     while (cap < rows) cap *= 2;
-    if (dev_alloc(s, &s->fof_row_vals, cap * kFofVals) || dev_alloc(s, &s->fof_out13, cap * 13) ||
-        dev_alloc(s, &s->fof_label, cap) || dev_alloc(s, &s->fof_members, cap))
+    if (dev_alloc(s, &g.row_vals, cap * kFofVals) || dev_alloc(s, &g.out13, cap * 13) || dev_alloc(s, &g.label, cap) ||
+        dev_alloc(s, &g.members, cap))
         return NBMI_ERR_HIP;
-    s->fof_row_cap = cap;
+    g.row_cap = cap;
     return 0;
 }
 }  // namespace
@@ -5880,10 +5868,11 @@ int nbmi_fof(nbmi_sim *s, double link, int32_t *labels, int64_t *n_groups, int64
     if (evals) *evals = 0;
     const int64_t n = s->n;
     if (n == 0) return 0;
-    if (int rc = fof_query(s, link * link, evals != nullptr, labels ? (int32_t *)s->stage : nullptr)) return rc;
+    int32_t *dev_labels = labels ? (int32_t *)s->stage : nullptr;
+    if (int rc = query_sync(s, [&] { return fof_enqueue(s, link * link, evals != nullptr, dev_labels); })) return rc;
     unsigned long long c[2] = {0, 0};
     if (labels) NBMI_HIP_CHECK(hipMemcpyAsync(labels, s->stage, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
-    NBMI_HIP_CHECK(hipMemcpyAsync(c, s->fof_counters, sizeof(c), hipMemcpyDeviceToHost, s->stream));
+    NBMI_HIP_CHECK(hipMemcpyAsync(c, s->q.fof.counters, sizeof(c), hipMemcpyDeviceToHost, s->stream));
     NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
     if (evals) *evals = (int64_t)c[0];
     if (n_groups) *n_groups = (int64_t)c[1];
@@ -5902,46 +5891,46 @@ int nbmi_fof_catalogue(nbmi_sim *s, double link, int64_t min_members, int64_t ca
     *count = 0;
     const int64_t n = s->n;
     if (n == 0) return 0;
-    if (int rc = fof_query(s, link * link, false, nullptr)) return rc;
+    if (int rc = query_sync(s, [&] { return fof_enqueue(s, link * link, false, nullptr); })) return rc;
     if (int rc = fof_catalogue_buffers(s)) return rc;
     hipStream_t st = s->stream;
     // the ranks by root, stable; the heads of the segments; the rows of the qualifying groups in segment order
     int bits = 1;
     while (bits < 32 && ((int64_t)1 << bits) < n) bits++;
-    k_fof_iota<<<nblocks(n), kBlock, 0, st>>>(n, s->fof_rank);
-    NBMI_HIP_CHECK(nbmi::radix_sort_pairs_u32(s->fof_sort_tmp, s->fof_sort_bytes, (const uint32_t *)s->fof_root, s->fof_key_s,
-                                              s->fof_rank, s->fof_rank_s, (size_t)n, 0, bits, st));
-    k_fof_heads<<<nblocks(n), kBlock, 0, st>>>(n, s->fof_key_s, s->fof_hpos, s->fof_slot);
-    scan::enqueue_compact(FofQualifies{s->fof_key_s, s->fof_cnt, min_members}, n, s->fof_tiles,
-                          FofEmitHead{s->fof_key_s, s->fof_qhead, s->fof_slot}, st);
+    k_fof_iota<<<nblocks(n), kBlock, 0, st>>>(n, s->q.cat.rank);
+    NBMI_HIP_CHECK(nbmi::radix_sort_pairs_u32(s->q.cat.sort_tmp, s->q.cat.sort_bytes, (const uint32_t *)s->q.fof.root, s->q.cat.key_s,
+                                              s->q.cat.rank, s->q.cat.rank_s, (size_t)n, 0, bits, st));
+    k_fof_heads<<<nblocks(n), kBlock, 0, st>>>(n, s->q.cat.key_s, s->q.cat.hpos, s->q.cat.slot);
+    scan::enqueue_compact(FofQualifies{s->q.cat.key_s, s->q.fof.cnt, min_members}, n, s->q.cat.tiles,
+                          FofEmitHead{s->q.cat.key_s, s->q.cat.qhead, s->q.cat.slot}, st);
     NBMI_HIP_CHECK(hipGetLastError());
     uint32_t rows = 0;
     unsigned sort_err = 0u;
-    NBMI_HIP_CHECK(hipMemcpyAsync(&rows, s->fof_tiles + scan::tiles_for(n), sizeof(rows), hipMemcpyDeviceToHost, st));
-    NBMI_HIP_CHECK(nbmi::radix_error_word(s->fof_sort_tmp, &sort_err, st));
+    NBMI_HIP_CHECK(hipMemcpyAsync(&rows, s->q.cat.tiles + scan::tiles_for(n), sizeof(rows), hipMemcpyDeviceToHost, st));
+    NBMI_HIP_CHECK(nbmi::radix_error_word(s->q.cat.sort_tmp, &sort_err, st));
     NBMI_HIP_CHECK(hipStreamSynchronize(st));
     if (sort_err) {
-        NBMI_HIP_CHECK(nbmi::radix_init_temp(s->fof_sort_tmp, st));
+        NBMI_HIP_CHECK(nbmi::radix_init_temp(s->q.cat.sort_tmp, st));
         nbmi::set_error("nbmi_fof_catalogue: device radix sort: a look-back spin timed out");
         return NBMI_ERR_HIP;
     }
     *count = (int64_t)rows;
     if (rows == 0) return 0;
     if (int rc = fof_row_buffers(s, (int64_t)rows)) return rc;
-    k_fof_chunks<<<(int)((n + kFofChunk - 1) / kFofChunk), kFofChunk, 0, st>>>(n, s->fof_key_s, s->fof_rank_s, s->perm,
-                                                                               s->buf[s->curbuf], s->fof_hpos, s->fof_cnt,
-                                                                               s->fof_slot, s->fof_row_vals, s->fof_last,
-                                                                               s->fof_first);
-    k_fof_rows<<<(int)rows, kFofBlock, 0, st>>>(n, (int64_t)rows, s->fof_qhead, s->fof_key_s, s->fof_cnt, s->fof_minid,
-                                                s->fof_row_vals, s->fof_last, s->fof_first, s->fof_out13, s->fof_label,
-                                                s->fof_members);
+    k_fof_chunks<<<(int)((n + kFofChunk - 1) / kFofChunk), kFofChunk, 0, st>>>(n, s->q.cat.key_s, s->q.cat.rank_s, s->perm,
+                                                                               s->buf[s->curbuf], s->q.cat.hpos, s->q.fof.cnt,
+                                                                               s->q.cat.slot, s->q.cat.row_vals, s->q.cat.last,
+                                                                               s->q.cat.first);
+    k_fof_rows<<<(int)rows, kQueryBlock, 0, st>>>(n, (int64_t)rows, s->q.cat.qhead, s->q.cat.key_s, s->q.fof.cnt, s->q.fof.minid,
+                                                s->q.cat.row_vals, s->q.cat.last, s->q.cat.first, s->q.cat.out13, s->q.cat.label,
+                                                s->q.cat.members);
     NBMI_HIP_CHECK(hipGetLastError());
     std::vector<double> h13((size_t)rows * 13);
     std::vector<int32_t> hlabel(rows);
     std::vector<int64_t> hmembers(rows);
-    NBMI_HIP_CHECK(hipMemcpyAsync(h13.data(), s->fof_out13, h13.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    NBMI_HIP_CHECK(hipMemcpyAsync(hlabel.data(), s->fof_label, hlabel.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    NBMI_HIP_CHECK(hipMemcpyAsync(hmembers.data(), s->fof_members, hmembers.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    NBMI_HIP_CHECK(hipMemcpyAsync(h13.data(), s->q.cat.out13, h13.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    NBMI_HIP_CHECK(hipMemcpyAsync(hlabel.data(), s->q.cat.label, hlabel.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    NBMI_HIP_CHECK(hipMemcpyAsync(hmembers.data(), s->q.cat.members, hmembers.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     NBMI_HIP_CHECK(hipStreamSynchronize(st));
     // the catalogue's order: members descending, ties by label ascending (labels are distinct)
     std::vector<uint32_t> order(rows);
@@ -5965,33 +5954,30 @@ int nbmi_compute_group_colors(nbmi_sim *s, double link, int64_t min_members) {
     const int64_t n = s->n;
     if (n == 0) return 0;
     if (int rc = fof_enqueue(s, link * link, false, nullptr)) return rc;
-    k_fof_colors<<<nblocks(n), kBlock, 0, s->stream>>>(s->info, n, s->fof_root, s->fof_minid, s->fof_cnt, s->perm,
+    k_fof_colors<<<nblocks(n), kBlock, 0, s->stream>>>(s->info, n, s->q.fof.root, s->q.fof.minid, s->q.fof.cnt, s->perm,
                                                        s->buf[s->curbuf].id, min_members, s->colors);
     NBMI_HIP_CHECK(hipGetLastError());
     return 0;
 }
 
 namespace {
-// Enqueues build, cell counts and the pair search and never waits.  Afterwards pair_out = {distances evaluated, pairs
+// Enqueues build, cell counts and the pair search and never waits.  Afterwards q.pairs.out = {distances evaluated, pairs
 // counted through whole cells, below, counts[0 .. nb)}.
 int pairs_enqueue(nbmi_sim *s, int nb, const PairEdges &e2) {
     const int64_t n = s->n;
-    if (query_buffers(s)) return NBMI_ERR_HIP;
-    if (!s->pair_ready) {
-        if (dev_alloc(s, &s->pair_cnt, s->node_capacity + 2) || dev_alloc(s, &s->pair_wleaf, (n + 63) / 64) ||
-            dev_alloc(s, &s->pair_out, kPairMaxBins + 3))
-            return NBMI_ERR_HIP;
-        s->pair_ready = true;
-    }
+    auto &g = s->q.pairs;
+    if (query_buffers(s) || query_alloc(g, [&] {
+            return dev_alloc(s, &g.cnt, s->node_capacity + 2) || dev_alloc(s, &g.out, kPairMaxBins + 3);
+        }))
+        return NBMI_ERR_HIP;
     hipStream_t st = s->stream;
-    NBMI_HIP_CHECK(hipMemsetAsync(s->pair_out, 0, (kPairMaxBins + 3) * sizeof(unsigned long long), st));
+    NBMI_HIP_CHECK(hipMemsetAsync(g.out, 0, (kPairMaxBins + 3) * sizeof(unsigned long long), st));
     return query_enqueue(s, "k_pair_counts", [&] {
-        k_pair_cells<<<nblocks(s->own_node_rows), kBlock, 0, st>>>(s->nodes, s->node_ref, s->info, n, s->own_node_rows,
-                                                                   s->pair_cnt, s->pair_wleaf);
-        const size_t lds = (size_t)(nb + 1) * (sizeof(double) + kPairBlock * sizeof(uint32_t));
-        k_pair_counts<<<(int)((n + kPairBlock - 1) / kPairBlock), kPairBlock, lds, st>>>(
-            s->nodes, s->knn_rows, s->node_ref, s->pair_cnt, s->info, s->perm, s->buf[s->curbuf], n, nb, e2,
-            s->pair_cells ? 1 : 0, s->pair_wleaf, s->pair_out);
+        k_pair_cells<<<nblocks(s->own_node_rows), kBlock, 0, st>>>(s->nodes, s->node_ref, s->info, n, s->own_node_rows, g.cnt);
+        const size_t lds = (size_t)(nb + 1) * (sizeof(double) + kQueryBlock * sizeof(uint32_t));
+        k_pair_counts<<<(int)((n + kQueryBlock - 1) / kQueryBlock), kQueryBlock, lds, st>>>(
+            s->nodes, s->q.shared.rows, s->node_ref, g.cnt, s->info, s->perm, s->buf[s->curbuf], n, nb, e2,
+            s->pair_cells ? 1 : 0, s->q.shared.wleaf, g.out);
     });
 }
 }  // namespace
@@ -5999,10 +5985,7 @@ int pairs_enqueue(nbmi_sim *s, int nb, const PairEdges &e2) {
 int nbmi_pair_counts(nbmi_sim *s, int nb, const double *edges, int64_t *counts, int64_t *below, int64_t *evals,
                      int64_t *cell_pairs) {
     if (int rc = check_handle(s)) return rc;
-    if (const char *why = knn_refusal(s)) {
-        nbmi::set_error("nbmi_pair_counts: %s", why);
-        return NBMI_ERR_ARG;
-    }
+    if (int rc = query_refuse(s, "nbmi_pair_counts")) return rc;
     if (nb < 1 || nb > kPairMaxBins) {
         nbmi::set_error("nbmi_pair_counts: nb = %d is outside 1 .. %d", nb, kPairMaxBins);
         return NBMI_ERR_ARG;
@@ -6028,13 +6011,9 @@ int nbmi_pair_counts(nbmi_sim *s, int nb, const double *edges, int64_t *counts, 
     if (evals) *evals = 0;
     if (cell_pairs) *cell_pairs = 0;
     if (s->n < 2) return 0;
-    NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
-    if (int rc = check_device_error(s)) return rc;
-    if (int rc = pairs_enqueue(s, nb, e2)) return rc;
-    NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
-    if (int rc = check_device_error(s)) return rc;
+    if (int rc = query_sync(s, [&] { return pairs_enqueue(s, nb, e2); })) return rc;
     unsigned long long h[kPairMaxBins + 3];
-    NBMI_HIP_CHECK(hipMemcpyAsync(h, s->pair_out, (size_t)(nb + 3) * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->stream));
+    NBMI_HIP_CHECK(hipMemcpyAsync(h, s->q.pairs.out, (size_t)(nb + 3) * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->stream));
     NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
     if (evals) *evals = (int64_t)h[0];
     if (cell_pairs) *cell_pairs = (int64_t)h[1];
@@ -6786,8 +6765,8 @@ int nbmi_frame_begin(nbmi_sim *s, int kind, double max_speed, int *slot) {
         if (s->color_mode == NBMI_COLOR_DENSITY) {
             if (int rc = knn_check(s, s->color_k, "nbmi_frame_begin")) return rc;
             if (int rc = knn_enqueue(s, s->color_k, false)) return rc;
-            dr2 = s->knn_r2;
-            dmass = s->knn_mass;
+            dr2 = s->q.knn.r2;
+            dmass = s->q.knn.mass;
         }
         // a delta frame's positions go to the staging rows: (like frame_current) nothing later on the stream reads them
         // before writing them

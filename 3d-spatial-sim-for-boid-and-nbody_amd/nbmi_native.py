@@ -167,6 +167,14 @@ def check(rc, what):
         raise RuntimeError(f"{what} failed (code {rc}): {last_error()}")
 
 
+def check_arg(rc, what, name=None):
+    """check(rc, name or what), except that NBMI_ERR_ARG (-1: the library refused the arguments, or this handle) raises
+    ValueError(f"{what}: <the library's message>")."""
+    if rc == -1:
+        raise ValueError(f"{what}: {last_error()}")
+    check(rc, name or what)
+
+
 def device_count():
     return int(load().nbmi_device_count())
 

@@ -93,6 +93,11 @@ def force_backend(backend: Backend):
     _BACKEND_INFO = f"Forced: {backend.value}"
 
 
+def _default_device():
+    """the device of this process's local rank (torchrun's LOCAL_RANK), modulo the devices present"""
+    return int(os.environ.get("LOCAL_RANK", "0")) % max(1, _nat.device_count())
+
+
 def _as_f64(a, shape_tail):
     a = np.ascontiguousarray(a, dtype=np.float64)
     if a.shape[1:] != shape_tail:
@@ -131,7 +136,7 @@ class _HIPSimulation:
         if not (len(pos) == len(vel) == len(m)):
             raise ValueError("positions, velocities and masses must have the same length")
         if device is None:
-            device = int(os.environ.get("LOCAL_RANK", "0")) % max(1, _nat.device_count())
+            device = _default_device()
         self.n = len(pos)
         self.G, self.softening, self.damping, self.theta = float(G), float(softening), float(damping), float(theta)
         self.device = int(device)
@@ -160,7 +165,7 @@ class _HIPSimulation:
         self = cls.__new__(cls)
         lib = _nat.load()
         if device is None:
-            device = int(os.environ.get("LOCAL_RANK", "0")) % max(1, _nat.device_count())
+            device = _default_device()
         self.n = int(n)
         self.G, self.softening, self.damping, self.theta = float(G), float(softening), float(damping), float(theta)
         self.device = int(device)
@@ -224,10 +229,7 @@ class _HIPSimulation:
         time-reversible, positions and velocities at the same instant; include/nbmi.h nbmi_set_integrator).  Owner-mode
         and sharded handles refuse leapfrog with ValueError."""
         code = _integrator_code(integrator)
-        rc = self._lib.nbmi_set_integrator(self._h, code)
-        if rc == -1:  # NBMI_ERR_ARG: refused for this handle
-            raise ValueError(f"set_integrator({integrator!r}): {_nat.last_error()}")
-        _nat.check(rc, "nbmi_set_integrator")
+        _nat.check_arg(self._lib.nbmi_set_integrator(self._h, code), f"set_integrator({integrator!r})", "nbmi_set_integrator")
 
     @property
     def integrator(self) -> str:
@@ -240,10 +242,7 @@ class _HIPSimulation:
         second moments; the accepted (body, node) sets do not change (include/nbmi.h nbmi_set_multipole).  Direct,
         owner-mode and sharded handles refuse quadrupole with ValueError."""
         code = _multipole_code(multipole)
-        rc = self._lib.nbmi_set_multipole(self._h, code)
-        if rc == -1:  # NBMI_ERR_ARG: refused for this handle
-            raise ValueError(f"set_multipole({multipole!r}): {_nat.last_error()}")
-        _nat.check(rc, "nbmi_set_multipole")
+        _nat.check_arg(self._lib.nbmi_set_multipole(self._h, code), f"set_multipole({multipole!r})", "nbmi_set_multipole")
 
     @property
     def multipole(self) -> str:
@@ -295,35 +294,33 @@ class _HIPSimulation:
         return out
 
     # ---- k-nearest neighbours, densities, density colours (include/nbmi.h nbmi_knn) ----
-    _knn_refusal = None  # classes whose handles the library refuses say so here, and refuse before calling it
+    _query_refusal = None  # classes whose handles the library refuses say so here, and refuse before calling it
 
-    def _knn_call(self, what, rc):
-        if rc == -1:  # NBMI_ERR_ARG: refused for this handle, or a bad k / range
-            raise ValueError(f"{what}: {_nat.last_error()}")
-        _nat.check(rc, what)
+    def _query_call(self, what, rc):
+        _nat.check_arg(rc, what)  # ValueError: refused for this handle, or a bad argument
 
-    def _knn_refuse(self, what):
-        if self._knn_refusal:
-            raise ValueError(f"{what}: {self._knn_refusal}")
+    def _query_refuse(self, what):
+        if self._query_refusal:
+            raise ValueError(f"{what}: {self._query_refusal}")
 
     def knn(self, k: int, evals=False):
         """(r2_k, mass_k), (N,) float64 each in the caller's body order: the squared distance to the k-th nearest other
         body - exact, equal to a brute force bit for bit - and the mass within it, own mass and ties included.
         ``evals=True`` also returns the number of distances the call evaluated.  1 <= k <= min(64, N - 1).  Barnes-Hut
         handles only; the call does not change what the next step computes."""
-        self._knn_refuse(f"knn({k})")
+        self._query_refuse(f"knn({k})")
         r2 = np.empty(self.n, dtype=np.float64)
         mk = np.empty(self.n, dtype=np.float64)
         ev = C.c_int64(0)
-        self._knn_call(f"knn({k})", self._lib.nbmi_knn(self._h, int(k), _nat.ptr(r2), _nat.ptr(mk),
+        self._query_call(f"knn({k})", self._lib.nbmi_knn(self._h, int(k), _nat.ptr(r2), _nat.ptr(mk),
                                                       C.addressof(ev) if evals else None))
         return (r2, mk, int(ev.value)) if evals else (r2, mk)
 
     def densities(self, k: int = 32) -> np.ndarray:
         """rho (N,) float64: mass_k over the volume of the k-th neighbour sphere; +inf where that radius is 0."""
-        self._knn_refuse(f"densities({k})")
+        self._query_refuse(f"densities({k})")
         out = np.empty(self.n, dtype=np.float64)
-        self._knn_call(f"densities({k})", self._lib.nbmi_get_densities_f64(self._h, int(k), _nat.ptr(out)))
+        self._query_call(f"densities({k})", self._lib.nbmi_get_densities_f64(self._h, int(k), _nat.ptr(out)))
         return out
 
     def set_color_mode(self, mode: str, k: int = 32, log10_range=(0.0, 1.0)):
@@ -334,8 +331,8 @@ class _HIPSimulation:
             raise ValueError(f"color mode must be one of {sorted(COLOR_MODES)}, not {mode!r}")
         lo, hi = (float(x) for x in log10_range)
         if mode == "density":
-            self._knn_refuse("set_color_mode('density')")
-        self._knn_call(f"set_color_mode({mode!r})", self._lib.nbmi_set_color_mode(self._h, COLOR_MODES[mode], int(k), lo, hi))
+            self._query_refuse("set_color_mode('density')")
+        self._query_call(f"set_color_mode({mode!r})", self._lib.nbmi_set_color_mode(self._h, COLOR_MODES[mode], int(k), lo, hi))
 
     def _color_mode(self):
         mode, k = C.c_int(0), C.c_int(0)
@@ -364,10 +361,10 @@ class _HIPSimulation:
         call evaluated.  Refused with ValueError where knn() is and for a link that is not finite and > 0; the call
         does not change what the next step computes."""
         what = f"find_groups({link})"
-        self._knn_refuse(what)
+        self._query_refuse(what)
         labels = np.empty(self.n, dtype=np.int32)
         ng, ev = C.c_int64(0), C.c_int64(0)
-        self._knn_call(what, self._lib.nbmi_fof(self._h, float(link), _nat.ptr(labels), C.addressof(ng),
+        self._query_call(what, self._lib.nbmi_fof(self._h, float(link), _nat.ptr(labels), C.addressof(ng),
                                                 C.addressof(ev) if evals else None))
         self.n_groups = int(ng.value)
         return (labels, int(ev.value)) if evals else labels
@@ -378,14 +375,14 @@ class _HIPSimulation:
         ``mass``, ``center`` (rows, 3), ``velocity`` (rows, 3), ``lo`` / ``hi`` (rows, 3: the bounding box).
         ``capacity`` limits the rows returned (default: all).  The same state gives the same bits."""
         what = f"group_catalogue({link}, min_members={min_members})"
-        self._knn_refuse(what)
+        self._query_refuse(what)
         cap = self.n // max(1, int(min_members)) if capacity is None else int(capacity)
         rows = max(cap, 0)
         label = np.empty(rows, dtype=np.int32)
         members = np.empty(rows, dtype=np.int64)
         out = np.empty((rows, 13), dtype=np.float64)
         cnt = C.c_int64(0)
-        self._knn_call(what, self._lib.nbmi_fof_catalogue(self._h, float(link), int(min_members), cap, _nat.ptr(label),
+        self._query_call(what, self._lib.nbmi_fof_catalogue(self._h, float(link), int(min_members), cap, _nat.ptr(label),
                                                           _nat.ptr(members), _nat.ptr(out), C.addressof(cnt)))
         k = min(int(cnt.value), rows)
         return {"count": int(cnt.value), "label": label[:k], "members": members[:k], "mass": out[:k, 0].copy(),
@@ -397,8 +394,8 @@ class _HIPSimulation:
         group of at least ``min_members`` bodies in a colour of its own (the speed ramp at a hash of its label), every
         other body grey.  The colour mode is not touched: the next compute_colors colours as before."""
         what = f"color_by_groups({link}, min_members={min_members})"
-        self._knn_refuse(what)
-        self._knn_call(what, self._lib.nbmi_compute_group_colors(self._h, float(link), int(min_members)))
+        self._query_refuse(what)
+        self._query_call(what, self._lib.nbmi_compute_group_colors(self._h, float(link), int(min_members)))
 
     # ---- binned pair counts (include/nbmi.h nbmi_pair_counts; DESIGN.md section 4.16) ----
     def pair_counts(self, edges, evals=False):
@@ -409,11 +406,11 @@ class _HIPSimulation:
         is and for bad edges; the call does not change what the next step computes."""
         e = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
         what = f"pair_counts({len(e)} edges)"
-        self._knn_refuse(what)
+        self._query_refuse(what)
         nb = len(e) - 1
         counts = np.zeros(max(nb, 0), dtype=np.int64)
         below, ev, cells = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        self._knn_call(what, self._lib.nbmi_pair_counts(self._h, nb, _nat.ptr(e) if len(e) else None, _nat.ptr(counts),
+        self._query_call(what, self._lib.nbmi_pair_counts(self._h, nb, _nat.ptr(e) if len(e) else None, _nat.ptr(counts),
                                                         C.addressof(below), C.addressof(ev) if evals else None,
                                                         C.addressof(cells) if evals else None))
         return (counts, int(below.value), int(ev.value), int(cells.value)) if evals else (counts, int(below.value))
@@ -485,9 +482,7 @@ class _HIPSimulation:
             raise ValueError(f"frame kind must be one of {sorted(self.FRAME_KINDS)}, not {kind!r}")
         slot = C.c_int(-1)
         rc = self._lib.nbmi_frame_begin(self._h, self.FRAME_KINDS[kind], float(max_speed), C.addressof(slot))
-        if rc == -1:  # NBMI_ERR_ARG: no free slot / no previous frame / owner mode
-            raise ValueError(f"frame_begin({kind!r}): {_nat.last_error()}")
-        _nat.check(rc, "nbmi_frame_begin")
+        _nat.check_arg(rc, f"frame_begin({kind!r})", "nbmi_frame_begin")  # refused: no free slot / no previous frame / owner mode
         return int(slot.value)
 
     def frame_wait(self, slot: int):
@@ -499,9 +494,7 @@ class _HIPSimulation:
         kind, steps = C.c_int(0), C.c_int64(0)
         rc = self._lib.nbmi_frame_wait(self._h, int(slot), C.addressof(first), C.addressof(second), C.addressof(kind),
                                        C.addressof(steps))
-        if rc == -1:
-            raise ValueError(f"frame_wait({slot}): {_nat.last_error()}")
-        _nat.check(rc, "nbmi_frame_wait")
+        _nat.check_arg(rc, f"frame_wait({slot})", "nbmi_frame_wait")
         dtype = np.dtype(np.int16 if kind.value == self.FRAME_KINDS["delta"] else np.float32)
 
         def view(p):
@@ -515,10 +508,7 @@ class _HIPSimulation:
 
     def frame_release(self, slot: int):
         """Free the slot for the next frame_begin; the arrays frame_wait returned for it must no longer be used."""
-        rc = self._lib.nbmi_frame_release(self._h, int(slot))
-        if rc == -1:
-            raise ValueError(f"frame_release({slot}): {_nat.last_error()}")
-        _nat.check(rc, "nbmi_frame_release")
+        _nat.check_arg(self._lib.nbmi_frame_release(self._h, int(slot)), f"frame_release({slot})", "nbmi_frame_release")
 
     def frames_pending(self):
         """[(slot, kind, steps), ...] of the frames begun and not released, oldest first; steps = step_count() at the
@@ -641,9 +631,7 @@ class HIPBarnesHutSimulation(_HIPSimulation):
         key = np.empty(nn, dtype=np.uint64)
         mom = np.empty((nn, 6), dtype=np.float64)
         rc = self._lib.nbmi_get_cell_moments(self._h, _nat.ptr(level), _nat.ptr(key), _nat.ptr(mom), nn)
-        if rc == -1:
-            raise ValueError(f"cell_moments: {_nat.last_error()}")
-        _nat.check(rc, "nbmi_get_cell_moments")
+        _nat.check_arg(rc, "cell_moments", "nbmi_get_cell_moments")
         return level, key, mom
 
     def walk_counters(self):
@@ -676,7 +664,7 @@ class HIPOwnerSimulation(HIPBarnesHutSimulation):
         if not (len(pos) == len(vel) == len(m) == len(ids)):
             raise ValueError("positions, velocities, masses and ids must have the same length")
         if device is None:
-            device = int(os.environ.get("LOCAL_RANK", "0")) % max(1, _nat.device_count())
+            device = _default_device()
         self.G, self.softening, self.damping, self.theta = float(G), float(softening), float(damping), float(theta)
         self.device = int(device)
         self.world, self.rank = int(world), int(rank)
@@ -693,7 +681,7 @@ class HIPOwnerSimulation(HIPBarnesHutSimulation):
     def n(self):
         return int(self._lib.nbmi_owner_count(self._h)) if self._h else 0
 
-    _knn_refusal = "owner-mode handles are not supported (the neighbours may live on other ranks)"
+    _query_refusal = "owner-mode handles are not supported (the neighbours may live on other ranks)"
 
     def set_multipole(self, multipole: str):
         if _multipole_code(multipole) != MULTIPOLES["monopole"]:
@@ -770,7 +758,7 @@ class HIPDirectSimulation(_HIPSimulation):
     no theta)."""
 
     _method = METHOD_DIRECT
-    _knn_refusal = "direct N^2 handles have no tree"
+    _query_refusal = "direct N^2 handles have no tree"
 
     def __init__(self, positions, velocities, masses, G, softening, damping, device=None, integrator="kick_drift",
                  multipole="monopole"):

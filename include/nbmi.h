@@ -261,7 +261,8 @@ int nbmi_get_potentials_f64(nbmi_sim *sim, double *out);
  * handle's bits: the tree is the same.
  * A call changes nothing that a later step reads (state and its order, the tree header - saved and restored -, the
  * "auto" precision flags and force_all64 - the build runs without a dt -, the step count, the stored leapfrog
- * acceleration).  The first call allocates 16 bytes per body and 32 bytes per node row.  NBMI_ERR_CAPACITY from the
+ * acceleration).  The first call allocates 16 bytes per body and - once for nbmi_knn, nbmi_fof and nbmi_pair_counts
+ * together, by whichever is called first - 32 bytes per node row and 4 bytes per 64 bodies.  NBMI_ERR_CAPACITY from the
  * call's own tree build is reported with a step's message.
  * Refused with NBMI_ERR_ARG, message "<call>: ...": direct N^2 handles (there is no tree), owner-mode handles and
  * handles with a proper shard. */
@@ -307,8 +308,8 @@ int nbmi_get_color_mode(nbmi_sim *sim, int *mode, int *k, double *log10_lo, doub
  * n_groups = 0, count = 0.  N == 1: one singleton.
  * A call changes nothing that a later step reads (as nbmi_knn).  NBMI_ERR_CAPACITY of the call's own tree build is
  * reported with a step's message.  Quadrupole and leapfrog handles return a plain handle's bits.
- * The first nbmi_fof allocates 16 bytes per body, 4 bytes per 64 bodies and (shared with nbmi_knn) 32 bytes per node
- * row; the first catalogue 24 bytes per body more, a radix sort buffer (about 8 bytes per body), 304 bytes per 256
+ * The first nbmi_fof allocates 16 bytes per body and (shared with nbmi_knn) 32 bytes per node row and 4 bytes per 64
+ * bodies; the first catalogue 24 bytes per body more, a radix sort buffer (about 8 bytes per body), 304 bytes per 256
  * bodies and 268 bytes per catalogue row (for the next power of two of rows, at least 1 024; a call that needs more frees
  * the arrays and allocates larger ones). */
 int nbmi_fof(nbmi_sim *sim, double link, int32_t *labels /* (N,), may be NULL */, int64_t *n_groups /* may be NULL */,
@@ -342,8 +343,8 @@ int nbmi_compute_group_colors(nbmi_sim *sim, double link, int64_t min_members);
  * Refused with NBMI_ERR_ARG, message "nbmi_pair_counts: ...": nb outside 1 .. 64, null edges, an edge that is not finite,
  * negative or not above the one before it (or whose square is not), and the handles nbmi_knn refuses (direct N^2, owner
  * mode, a proper shard).
- * The first call allocates 4 bytes per node row, 4 bytes per 64 bodies, 536 bytes of results and (shared with nbmi_knn
- * and nbmi_fof) 32 bytes per node row.
+ * The first call allocates 4 bytes per node row, 536 bytes of results and (shared with nbmi_knn and nbmi_fof) 32 bytes
+ * per node row and 4 bytes per 64 bodies.
  * Environment NBMI_PAIRS_CELLS (read when the handle is created, like the other measurement knobs): 0 never counts a
  * cell whole (pruning stays).  Results are the same; evals, cell_pairs (then 0) and the time are not (DESIGN.md section
  * 4.16 has the A/B). */

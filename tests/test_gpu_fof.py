@@ -13,6 +13,8 @@ import pytest
 
 import fof_ref as fr
 import knn_ref as kr
+import query_cases as qc
+from query_cases import bh as _bh, preset as _preset
 
 pytestmark = pytest.mark.gpu
 
@@ -21,58 +23,10 @@ NBMI_ERR_CAPACITY = -4
 U = 2.0 ** -53
 
 
-def _bh(p, v=None, m=None, G=0.07, eps=1.5, theta=0.5, **kw):
-    from nbody.gpu_backend import HIPBarnesHutSimulation
-    p = np.ascontiguousarray(p, np.float64)
-    v = np.zeros_like(p) if v is None else np.ascontiguousarray(v, np.float64)
-    m = np.ones(len(p)) if m is None else np.ascontiguousarray(m, np.float64)
-    return HIPBarnesHutSimulation(p, v, m, G, eps, 1.0, theta, **kw)
+def _system(name):
+    return qc.system(name)[0]
 
 
-def _preset(dist, n=20_000, seed=7):
-    from tools.presets import generate_distribution
-    R, G = 800.0, 0.07
-    np.random.seed(seed)
-    p, v, m = generate_distribution(dist, n, R, G)
-    rng = np.random.RandomState(seed)
-    m = np.ascontiguousarray(m, np.float64) * rng.uniform(0.5, 2.0, n)  # unequal masses: M is not a count
-    return np.ascontiguousarray(p, np.float64), np.ascontiguousarray(v, np.float64), m
-
-
-def _ball(n, seed, radius=1.0, centre=(0.0, 0.0, 0.0)):
-    rng = np.random.RandomState(seed)
-    u = rng.normal(size=(n, 3))
-    u *= (rng.uniform(size=n) ** (1.0 / 3.0) / np.linalg.norm(u, axis=1))[:, None]
-    return np.asarray(centre) + radius * u
-
-
-def _trap(seed=11):
-    """section 4.14's trap: 2 048 bodies within 1e-3 of a point at coordinate 700 plus 2 048 in +-800"""
-    rng = np.random.RandomState(seed)
-    return np.concatenate([_ball(2048, seed, 1e-3, (700.0, -650.0, 300.0)), rng.uniform(-800.0, 800.0, (2048, 3))])
-
-
-def _far():
-    """section 4.14's far body: one body 1e6 away from a ball of 4 096, which inflates the root cube"""
-    return np.concatenate([_ball(4096, 3, 50.0), [[1.0e6, -2.0e5, 3.0e5]]])
-
-
-def _uniform(n, seed):
-    return np.random.RandomState(seed).uniform(-100.0, 100.0, (n, 3))
-
-
-SYSTEMS = {
-    "galaxy": lambda: _preset("galaxy")[0],
-    "collision": lambda: _preset("collision")[0],
-    "filament": lambda: _preset("filament")[0],
-    "n2049": lambda: _uniform(2049, 1),  # the last wave has one lane
-    "n4097": lambda: _uniform(4097, 2),
-    "trap": _trap,
-    "far": _far,
-    "n1": lambda: np.array([[1.0, 2.0, 3.0]]),
-    "n2": lambda: np.array([[0.0, 0.0, 0.0], [3.0, 4.0, 0.0]]),  # d2 = 25 exactly
-    "n65": lambda: _uniform(65, 6),
-}
 # what each case is for, checked on the reference before anything is asserted of the device:
 # (largest group at least, groups at least, singletons at least)
 CASES = [
@@ -94,13 +48,7 @@ CASES = [
     ("n2", 4.999, (1, 2, 2)),                # not linked
     ("n65", 30.0, (5, 30, 20)),           # one full wave and a one-lane wave
 ]
-_SYS, _REF = {}, {}
-
-
-def _system(name):
-    if name not in _SYS:
-        _SYS[name] = SYSTEMS[name]()
-    return _SYS[name]
+_REF = {}
 
 
 def _reference(name, b):
@@ -136,9 +84,7 @@ def test_labels_exact_against_the_reference(gpu, name, b, shape):
 def test_equality_links_and_nothing_at_the_bound_is_pruned(gpu):
     """16^3 integer lattice, spacing 1, shuffled: at b = 1 every link has d2 == b2 exactly (one group of 4 096 - lost
     if equality is pruned or tested with <), just below 1 there are no links at all"""
-    g = np.arange(16, dtype=np.float64)
-    p = np.stack(np.meshgrid(g, g, g, indexing="ij"), -1).reshape(-1, 3)
-    p = p[np.random.RandomState(5).permutation(len(p))]
+    p = qc.lattice()[0]
     sim = _bh(p)
     try:
         lab = sim.find_groups(1.0)

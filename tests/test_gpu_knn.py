@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 
 import knn_ref as kr
+import query_cases as qc
+from query_cases import bh as _bh, system as _system
 
 pytestmark = pytest.mark.gpu
 
@@ -16,71 +18,13 @@ KS = (1, 8, 32, 64)
 NBMI_ERR_ARG = -1
 
 
-def _bh(p, v=None, m=None, G=0.07, eps=1.5, theta=0.5, **kw):
-    from nbody.gpu_backend import HIPBarnesHutSimulation
-    p = np.ascontiguousarray(p, np.float64)
-    v = np.zeros_like(p) if v is None else np.ascontiguousarray(v, np.float64)
-    m = np.ones(len(p)) if m is None else np.ascontiguousarray(m, np.float64)
-    return HIPBarnesHutSimulation(p, v, m, G, eps, 1.0, theta, **kw)
-
-
 def _dist(dist, n, seed=7):
-    from tools.presets import generate_distribution
     R, G = {"galaxy": (800.0, 0.07), "cluster": (300.0, 0.05)}[dist]
-    np.random.seed(seed)
-    p, v, m = generate_distribution(dist, n, R, G)
-    rng = np.random.RandomState(seed)
-    m = np.ascontiguousarray(m, np.float64) * rng.uniform(0.5, 2.0, n)  # unequal masses: mass_k is not a count
-    return np.ascontiguousarray(p, np.float64), np.ascontiguousarray(v, np.float64), m, G
+    p, v, m = qc.preset(dist, n, seed, R, G)  # unequal masses: mass_k is not a count
+    return p, v, m, G
 
 
-def _ball(n, seed, radius=1.0, centre=(0.0, 0.0, 0.0)):
-    rng = np.random.RandomState(seed)
-    u = rng.normal(size=(n, 3))
-    u *= (rng.uniform(size=n) ** (1.0 / 3.0) / np.linalg.norm(u, axis=1))[:, None]
-    return np.asarray(centre) + radius * u
-
-
-def _trap(seed=11):
-    """tests/test_gpu_quadrupole.py's shape: 2 048 bodies within 1e-3 of a point at coordinate 700 plus 2 048 in +-800"""
-    rng = np.random.RandomState(seed)
-    p = np.concatenate([_ball(2048, seed, 1e-3, (700.0, -650.0, 300.0)), rng.uniform(-800.0, 800.0, (2048, 3))])
-    return p, rng.uniform(0.5, 1.5, len(p))
-
-
-def _far():
-    """one body 1e6 away from a ball of 4 096: all of its neighbours are far, and it inflates the root cube"""
-    p = np.concatenate([_ball(4096, 3, 50.0), [[1.0e6, -2.0e5, 3.0e5]]])
-    return p, np.random.RandomState(4).uniform(0.5, 1.5, len(p))
-
-
-def _uniform(n, seed):
-    rng = np.random.RandomState(seed)
-    return rng.uniform(-100.0, 100.0, (n, 3)), rng.uniform(0.5, 1.5, n)
-
-
-def _preset(dist):
-    p, _v, m, _G = _dist(dist, 20_000)
-    return p, m
-
-
-SYSTEMS = {
-    "galaxy20k": lambda: _preset("galaxy"),   # a strong density contrast
-    "cluster20k": lambda: _preset("cluster"),
-    "n2049": lambda: _uniform(2049, 1),       # the last wave has one lane
-    "n4097": lambda: _uniform(4097, 2),
-    "trap": _trap,                            # where a bound computed in fp32 breaks
-    "far": _far,
-    "n9": lambda: _uniform(9, 5),             # n = k + 1
-    "n65": lambda: _uniform(65, 6),
-}
-_SYS, _REF = {}, {}
-
-
-def _system(name):
-    if name not in _SYS:
-        _SYS[name] = SYSTEMS[name]()
-    return _SYS[name]
+_REF = {}
 
 
 def _reference(name):
@@ -124,9 +68,7 @@ def test_exact_against_brute_force(gpu, name, k):
 def test_ties_on_an_integer_lattice(gpu):
     """16^3 lattice, unit masses: most distances tie, so r2_k only comes out right if equal candidates are kept, and
     mass_k (an integer) only if subtrees AT the bound are never pruned"""
-    g = np.arange(16, dtype=np.float64)
-    p = np.stack(np.meshgrid(g, g, g, indexing="ij"), -1).reshape(-1, 3)
-    m = np.ones(len(p))
+    p, m = qc.lattice(shuffle=False)
     ref = kr.knn_many(p, m, KS)
     sim = _bh(p, m=m)
     try:

@@ -14,6 +14,8 @@ import numpy as np
 import pytest
 
 import pairs_ref as pr
+import query_cases as qc
+from query_cases import bh as _bh
 from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
@@ -24,59 +26,16 @@ R_SPAWN = 800.0
 LINEAR = np.linspace(0.05 * R_SPAWN, 0.25 * R_SPAWN, 5)  # 5 linear edges out to a quarter of the spawn radius
 
 
-def _bh(p, v=None, m=None, G=0.07, eps=1.5, theta=0.5, **kw):
-    from nbody.gpu_backend import HIPBarnesHutSimulation
-    p = np.ascontiguousarray(p, np.float64)
-    v = np.zeros_like(p) if v is None else np.ascontiguousarray(v, np.float64)
-    m = np.ones(len(p)) if m is None else np.ascontiguousarray(m, np.float64)
-    return HIPBarnesHutSimulation(p, v, m, G, eps, 1.0, theta, **kw)
-
-
 def _preset(dist, n=20_000, seed=7):
-    from tools.presets import generate_distribution
-    np.random.seed(seed)
-    p, v, m = generate_distribution(dist, n, R_SPAWN, 0.07)
-    return np.ascontiguousarray(p, np.float64), np.ascontiguousarray(v, np.float64), np.ascontiguousarray(m, np.float64)
-
-
-def _ball(n, seed, radius=1.0, centre=(0.0, 0.0, 0.0)):
-    rng = np.random.RandomState(seed)
-    u = rng.normal(size=(n, 3))
-    u *= (rng.uniform(size=n) ** (1.0 / 3.0) / np.linalg.norm(u, axis=1))[:, None]
-    return np.asarray(centre) + radius * u
-
-
-def _trap(seed=11):
-    """DESIGN 4.14's trap: 2 048 bodies within 1e-3 of a point at coordinate 700 plus 2 048 in +-800"""
-    rng = np.random.RandomState(seed)
-    return np.concatenate([_ball(2048, seed, 1e-3, (700.0, -650.0, 300.0)), rng.uniform(-800.0, 800.0, (2048, 3))])
-
-
-def _far():
-    """DESIGN 4.14's far body: one body 1e6 away from a ball of 4 096, which inflates the root cube"""
-    return np.concatenate([_ball(4096, 3, 50.0), [[1.0e6, -2.0e5, 3.0e5]]])
-
-
-def _uniform(n, seed):
-    return np.random.RandomState(seed).uniform(-100.0, 100.0, (n, 3))
-
-
-def _lattice(spacing):
-    g = spacing * np.arange(16, dtype=np.float64)
-    p = np.stack(np.meshgrid(g, g, g, indexing="ij"), -1).reshape(-1, 3)
-    return p[np.random.RandomState(5).permutation(len(p))]
-
-
-_SYS = {}
+    return qc.preset(dist, n, seed, R_SPAWN, 0.07, scale_masses=False)
 
 
 def _system(name):
-    if name not in _SYS:
-        _SYS[name] = {"n2049": lambda: _uniform(2049, 1), "n4097": lambda: _uniform(4097, 2), "trap": _trap, "far": _far,
-                      "galaxy": lambda: _preset("galaxy")[0], "collision": lambda: _preset("collision")[0],
-                      "filament": lambda: _preset("filament")[0], "cluster": lambda: _preset("cluster")[0],
-                      "lattice33": lambda: _lattice(33.0)}[name]()
-    return _SYS[name]
+    return qc.system(name)[0]
+
+
+def _lattice(spacing):
+    return qc.lattice(spacing)[0]
 
 
 def _check(tag, got, ref):
@@ -245,7 +204,7 @@ def test_small_sizes(gpu):
         finally:
             sim.close()
     for n in (64, 65, 129):  # a full wave; a last wave with one valid lane
-        p = _uniform(n, n)
+        p = qc.uniform(n, n)[0]
         edges = [0.0, 20.0, 60.0, 120.0, 400.0]
         ref = pr.pair_counts(p, edges)
         assert ref[1] + ref[0].sum() == n * (n - 1) // 2 and (ref[0] > 0).all()
