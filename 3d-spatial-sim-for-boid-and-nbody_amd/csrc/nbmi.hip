@@ -5265,6 +5265,10 @@ static int create_impl(nbmi_sim *s, const double *pos, const double *vel, const 
              dev_alloc(s, &s->nodesd, s->node_capacity + 2)) ||
             false)
             return -2;
+        // no step yet: no wave has asked for float64 (the flags are written only by the build of a step with a dt, and
+        // read before that by nbmi_force_precision_share and by the walk of an owner handle whose dt was never set)
+        NBMI_HIP_CHECK(hipMemsetAsync(s->wave_flag, 0, (size_t)(c + 63) / 64 + 64, s->stream));
+        NBMI_HIP_CHECK(hipMemsetAsync(s->sub_flag, 0, ((size_t)(c + 1) / kScanTile + 2) * sizeof(int32_t), s->stream));
         s->own_node_rows = own_rows;
         s->tmp_sort_bytes = nbmi::radix_temp_bytes_u64((size_t)c, 63);
         char *t = nullptr;

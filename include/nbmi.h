@@ -485,10 +485,33 @@ int nbmi_set_exchange_sync(nbmi_sim *sim, int sync);
  * Every mode holds at softening 0 and at softenings so small that the fp32 self-term G m eps^-3 overflows: there the
  * walk skips the pairs whose dist_sq does not exceed eps^2 (the reference's rule for its own leaf and for coincident
  * bodies), in fp32 and in float64 alike.
- * Environment NBMI_FORCE_PREC / NBMI_PREC_TAU set the initial values. */
+ * Environment NBMI_FORCE_PREC / NBMI_PREC_TAU set the initial values.
+ *
+ * Mode 0 exactly (tests/prec_ref.py restates it, tests/test_gpu_prec_auto.py compares the device with it).  With the
+ * bodies in sort-key order (rank r = 0 .. n-1), for a step of size dt:
+ *   p32      = (float)x per coordinate;  g32 = (float)(G * m), the product formed in float64.
+ *   group g  = the ranks [16g, 16g+16) within [0, n), aligned to the rank index;
+ *   wave w   = the ranks [64w, 64w+64), that is groups 4w .. 4w+3.
+ *   gsum     = the fp32 sum of the group's g32, absent ranks counting 0, associated ((w0+w1)+(w2+w3)) per four
+ *              consecutive ranks, then (q0+q1)+(q2+q3) over the four quads.
+ *   edge_a   = fmaxf(max p32_a - min p32_a, (float)softening) per axis, the difference taken in fp32.
+ *   vol      = (edge_x * edge_y) * edge_z.
+ *   dens     = gsum > 0 ? gsum / vol : 0 - vol == 0 with mass gives +inf; a group without mass or without bodies 0.
+ *   D_w      = the largest dens of the wave's four groups.
+ *   flag_w   = D_w > (float)(tau / dt^2)   (a threshold that overflows to +inf flags nothing: inf > inf is false).
+ *   share    = (number of set flags) / ceil(n / 64).
+ *   all64    = all64_rule(previous all64, ask = number of set flags, waves = ceil(n / 64), 333, 250): entered at
+ *              1000 ask > 333 waves, kept while 1000 ask >= 250 waves.  nbmi_create and nbmi_set_state reset the
+ *              previous value to 0.  A build that is not part of a step (nbmi_build_tree, the queries, the
+ *              diagnostics, nbmi_get_accelerations_f64) changes neither the flags nor all64.  The first leapfrog step
+ *              after create / nbmi_set_state contains two builds of a step - the one that primes a = F(x) at the
+ *              initial positions, then the one at the drifted positions - and applies the rule once for each.
+ *   In an integrating walk a wave computes in float64 iff flag_w || all64; all lanes of the wave agree.
+ * The flags are cleared when the handle is created: before the first step no wave asks. */
 int nbmi_set_force_precision(nbmi_sim *sim, int mode, double tau);
 /* Mode 0, after a step: the share of the waves whose own density asked for float64, and whether the step ran every
- * wave in float64 (the system-wide rule above: entered when more than a third asked, left below a quarter). */
+ * wave in float64 (the system-wide rule above: entered when more than a third asked, left below a quarter).  Before
+ * the handle's first step: (0, false).  Mode 1: (0, false); mode 2: (1, true). */
 int nbmi_force_precision_share(nbmi_sim *sim, double *share, int *all_float64);
 /* Native HIP stream of the handle (for ordering against framework streams). */
 void *nbmi_stream(nbmi_sim *sim);
