@@ -4298,6 +4298,173 @@ __global__ __launch_bounds__(kQueryBlock) void k_pair_counts(const Node *__restr
     query_wave_add(out + 1, whole, C.lane);
 }
 
+// ---------------------------------------------------------------------------------------
+// K19: the field at arbitrary points (nbmi_field_at; include/nbmi.h).
+// k_potential_tree with a probe in the lane instead of a body: float64 throughout, per-lane sums in pre-order of the
+// node array, per-lane stores.  A lane's accepted set and the order of its sum depend on nothing but the probe and the
+// tree, so which probes share a wave - the sort below, the chunks of the call, the other points - decides the speed of a
+// call and never a bit of its result.
+// ---------------------------------------------------------------------------------------
+// A call is cut into chunks of at most this many points: the scratch never holds more.
+constexpr int64_t kFieldChunk = 1048576;
+constexpr int64_t kFieldMinRows = 1024;  // smallest scratch (rows double from here up to the chunk)
+constexpr int kFieldSortBits = 40;       // the sort looks at the top 40 key bits, as the build of a million bodies does
+
+// Sort key of a probe: the digits of k_keys (key_word, the handle's curve) in the tree's root cube, coordinates outside
+// the cube clamped to its faces.  pts: the chunk, (m, 3).
+template <bool kHilbert>
+__global__ __launch_bounds__(kBlock) void k_field_keys(const double *__restrict__ pts, int64_t m, const TreeInfo *__restrict__ info,
+                                                       uint64_t *__restrict__ key, uint32_t *__restrict__ idx) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= m) return;
+    const double b = info->bounds;
+    const double px = fmin(fmax(pts[3 * i], -b), b), py = fmin(fmax(pts[3 * i + 1], -b), b), pz = fmin(fmax(pts[3 * i + 2], -b), b);
+    double cx = 0.0, cy = 0.0, cz = 0.0, hs = b;
+    unsigned st = 0u;
+    key[i] = key_word<kHilbert>(px, py, pz, cx, cy, cz, hs, st, nbmi::kHilDigit, nbmi::kHilNext);
+    idx[i] = (uint32_t)i;
+}
+
+// The probes of a chunk as columns in walk order: rank r holds point order[r] (order == null: point r).
+__global__ __launch_bounds__(kBlock) void k_field_gather(const double *__restrict__ pts, const uint32_t *__restrict__ order, int64_t m,
+                                                         double *__restrict__ sx, double *__restrict__ sy, double *__restrict__ sz) {
+    const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (r >= m) return;
+    const int64_t i = order ? (int64_t)order[r] : r;
+    sx[r] = pts[3 * i]; sy[r] = pts[3 * i + 1]; sz[r] = pts[3 * i + 2];
+}
+
+// The probe walk.  `tab` is the handle's walk table with buf[0].x / y / z pointing at the probe columns (sx, sy, sz):
+// opening()'s float64 re-decision reads "body" `rank` of buffer 0 there and so computes, operation for operation, what
+// it computes for a body at that place.
+// The band.  The node records carry the upper edge bits(s2t) + K of the band for K = band_half_ulps(maxabs of the
+// bodies): the fp32 error of d^2 grows with the larger of |p| and |c|, and a probe may lie far outside the root cube.
+// The walk widens the band to K' = band_half_ulps(max(maxabs, pmax)) about the same centre - upper edge + (K' - K),
+// width 2 K' - where pmax is the call's largest |coordinate|, and takes k_potential_tree's near-pair rule from the same
+// maximum.  pmax <= maxabs: K' = K, and every decision is k_potential_tree's bit for bit.  (Either way a decision is
+// the float64 one; the band only settles which visits compute it.)
+// kQuad: an applied internal cell adds the second-order terms to phi (k_potential_tree<true>'s expression) and to acc,
+//   a += [7.5 (d^T P d) u^-7/2 - 1.5 tr P u^-5/2] d - 3 u^-5/2 P d,   u = dist_sq,
+// from the float64 moments of k_quad_level, in a scope of their own.
+// Results land at the probe's row of the chunk, order[rank].
+template <bool kQuad>
+__global__ __launch_bounds__(kBlock) void k_field_tree(const Node *__restrict__ nodes, const double4 *__restrict__ pot,
+                                                       const WalkTable *tab, const TreeInfo *info,
+                                                       const double *__restrict__ sx, const double *__restrict__ sy,
+                                                       const double *__restrict__ sz, const uint32_t *__restrict__ order, int64_t m,
+                                                       float eps2f, double eps, double pmax, const double *__restrict__ quad,
+                                                       double *__restrict__ acc_out, double *__restrict__ phi_out,
+                                                       int32_t *__restrict__ cnt_out) {
+    if (info->error != 0 || info->sticky_error != 0) return;  // the tree did not fit: the caller reports it
+    const int64_t rank = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const bool valid = rank < m;
+    double qx = 0.0, qy = 0.0, qz = 0.0;
+    if (valid) { qx = sx[rank]; qy = sy[rank]; qz = sz[rank]; }
+    const float px = (float)qx, py = (float)qy, pz = (float)qz;
+    const Body64 b64{tab, 0, (uint32_t)(valid ? rank : 0)};
+    const unsigned nn = __builtin_amdgcn_readfirstlane((unsigned)info->num_nodes * kNodeBytes);
+    const double eps2 = __longlong_as_double((long long)uniform_u64((unsigned long long)__double_as_longlong(tab->eps2)));
+    const double maxabs = fmax(__longlong_as_double((long long)info->maxabs_bits), pmax);
+    const unsigned kb = info->band2 >> 1;
+    unsigned kp = band_half_ulps(maxabs, eps);
+    kp = kp > kb ? kp : kb;
+    const int dk = __builtin_amdgcn_readfirstlane((int)(kp - kb));
+    const unsigned band2 = __builtin_amdgcn_readfirstlane(2u * kp);
+    float near2 = 0.f;  // see k_potential_tree
+    if (band2 >= 2u * 2097153u) {
+        const double r = 8.0e-6 * maxabs;
+        near2 = eps2f + (float)(r * r);
+    }
+    unsigned resume = valid ? 0u : 0xffffffffu;
+    double ax = 0.0, ay = 0.0, az = 0.0, phi = 0.0;
+    int32_t terms = 0;
+    unsigned off = 0u;
+    while (off < nn) {
+        off = __builtin_amdgcn_readfirstlane(off);
+        const unsigned idx = off / kNodeBytes;
+        const Node nd = nodes[idx];
+        const bool cell = __float_as_int(nd.s2t) != 0;
+        const float s2t = cell ? __int_as_float(__float_as_int(nd.s2t) + dk) : 0.f;
+        const float dx = nd.cx - px, dy = nd.cy - py, dz = nd.cz - pz;
+        const float dist_sq = fmaf(dz, dz, fmaf(dy, dy, fmaf(dx, dx, eps2f)));
+        const bool active = resume <= off;
+        const bool near = cell && dist_sq < near2;
+        const bool geom = opening(dist_sq, s2t, band2, active, idx, b64, near).geom;
+        bool take;
+        const unsigned next = advance<kNodeBytes>(active, geom, off, nd.next_off, resume, take);
+        if (take) {
+            const double4 q = pot[idx];
+            const double ex = q.x - qx, ey = q.y - qy, ez = q.z - qz;
+            const double d2 = ex * ex + ey * ey + ez * ez + eps2;  // (-ffp-contract=off: the reference's roundings)
+            if (q.w > 0.0 && d2 > eps2) {
+                const double dist = sqrt(d2);
+                const double w = q.w / (dist * d2);
+                phi -= q.w / dist;
+                ax += ex * w; ay += ey * w; az += ez * w;
+                terms++;
+                if (kQuad && nd.next_off != off + kNodeBytes) {  // an internal cell
+                    const double *pq = quad + 9 * (size_t)idx + 3;
+                    const double pxx = pq[0], pyy = pq[1], pzz = pq[2], pxy = pq[3], pxz = pq[4], pyz = pq[5];
+                    const double dpd = ex * (pxx * ex + 2.0 * (pxy * ey + pxz * ez)) + ey * (pyy * ey + 2.0 * (pyz * ez)) + ez * (pzz * ez);
+                    const double tr = pxx + pyy + pzz;
+                    const double i1 = 1.0 / dist, i3 = i1 / d2, i5 = i3 / d2;
+                    phi += 0.5 * (tr * i3 - 3.0 * dpd * i5);
+                    const double sc = 7.5 * dpd * (i5 / d2) - 1.5 * tr * i5, t3 = 3.0 * i5;
+                    ax += sc * ex - t3 * (pxx * ex + pxy * ey + pxz * ez);
+                    ay += sc * ey - t3 * (pxy * ex + pyy * ey + pyz * ez);
+                    az += sc * ez - t3 * (pxz * ex + pyz * ey + pzz * ez);
+                }
+            }
+        }
+        off = next;
+    }
+    if (valid) {
+        const int64_t o = order ? (int64_t)order[rank] : rank;
+        if (acc_out) { acc_out[3 * o] = ax; acc_out[3 * o + 1] = ay; acc_out[3 * o + 2] = az; }
+        if (phi_out) phi_out[o] = phi;
+        if (cnt_out) cnt_out[o] = terms;
+    }
+}
+
+// Direct handle: the sum over all bodies in body order, k_potential_direct's twin with a point in the thread.  The only
+// guard is the definition's dist_sq > eps^2.
+__global__ __launch_bounds__(kBlock) void k_field_direct(Bodies cur, int64_t n, double G, double eps2, const double *__restrict__ pts,
+                                                         int64_t m, double *__restrict__ acc_out, double *__restrict__ phi_out,
+                                                         int32_t *__restrict__ cnt_out) {
+    __shared__ double4 tile[kBlock];
+    const int t = threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * kBlock + t;
+    const bool valid = i < m;
+    double x = 0.0, y = 0.0, z = 0.0;
+    if (valid) { x = pts[3 * i]; y = pts[3 * i + 1]; z = pts[3 * i + 2]; }
+    double ax = 0.0, ay = 0.0, az = 0.0, phi = 0.0;
+    int32_t terms = 0;
+    for (int64_t base = 0; base < n; base += kBlock) {
+        const int64_t jj = base + t;
+        tile[t] = jj < n ? make_double4(cur.x[jj], cur.y[jj], cur.z[jj], G * cur.m[jj]) : make_double4(0.0, 0.0, 0.0, 0.0);
+        __syncthreads();
+        const int lim = n - base < kBlock ? (int)(n - base) : kBlock;
+        for (int k = 0; k < lim; k++) {
+            const double4 q = tile[k];
+            const double ex = q.x - x, ey = q.y - y, ez = q.z - z;
+            const double d2 = ex * ex + ey * ey + ez * ez + eps2;
+            if (d2 > eps2) {
+                const double dist = sqrt(d2);
+                const double w = q.w / (dist * d2);
+                phi -= q.w / dist;
+                ax += ex * w; ay += ey * w; az += ez * w;
+                terms++;
+            }
+        }
+        __syncthreads();
+    }
+    if (valid) {
+        if (acc_out) { acc_out[3 * i] = ax; acc_out[3 * i + 1] = ay; acc_out[3 * i + 2] = az; }
+        if (phi_out) phi_out[i] = phi;
+        if (cnt_out) cnt_out[i] = terms;
+    }
+}
+
 }  // namespace
 
 // =========================================================================================
@@ -4472,6 +4639,21 @@ struct nbmi_sim {
         } pairs;
     } q;
     bool pair_cells = true;  // cells inside one bin are counted whole (NBMI_PAIRS_CELLS=0: never; measurement)
+    // Scratch of nbmi_field_at (section 4.18): `rows` points of a chunk - 108 bytes each: the points as they came, their
+    // columns in walk order, acc, phi, terms, sort keys and indices in and out - the sort's temp buffer for that many
+    // pairs, and the walk table whose buffer 0 names the probe columns.  Grown by the call that needs more, never beyond
+    // kFieldChunk rows; no step touches it.
+    struct {
+        int64_t rows = 0;
+        double *pts = nullptr, *sx = nullptr, *sy = nullptr, *sz = nullptr, *acc = nullptr, *phi = nullptr;
+        int32_t *cnt = nullptr;
+        uint64_t *key = nullptr, *key_s = nullptr;
+        uint32_t *idx = nullptr, *order = nullptr;
+        char *sort_tmp = nullptr;
+        size_t sort_bytes = 0;
+        WalkTable *wtab = nullptr;
+    } field;
+    bool field_sort = true;  // probes walk in key order (NBMI_FIELD_SORT=0: in the caller's order; measurement)
     // what nbmi_compute_colors / nbmi_frame_begin colour by (nbmi_set_color_mode)
     int color_mode = NBMI_COLOR_SPEED, color_k = 32;
     double color_lo = 0.0, color_hi = 1.0;
@@ -4530,8 +4712,8 @@ int alloc_bodies(nbmi_sim *s, Bodies *b, int64_t n) {
     return 0;
 }
 
-// (re)writes the device copy of the walk's per-handle constants
-int upload_walk_table(nbmi_sim *s) {
+// the walk's per-handle constants as the handle stands
+WalkTable walk_table(const nbmi_sim *s) {
     WalkTable t;
     t.buf[0] = s->buf[0];
     t.buf[1] = s->buf[1];
@@ -4549,6 +4731,12 @@ int upload_walk_table(nbmi_sim *s) {
     t.ax = s->acc;
     t.ay = s->acc ? s->acc + s->n : nullptr;
     t.az = s->acc ? s->acc + 2 * s->n : nullptr;
+    t.leap = 0;
+    return t;
+}
+// (re)writes the device copy of them
+int upload_walk_table(nbmi_sim *s) {
+    const WalkTable t = walk_table(s);
     WalkTable tabs[3] = {t, t, t};  // one per epilogue: kick-drift, kLeapClose, kLeapPrime
     tabs[0].leap = 0;
     tabs[kLeapClose].leap = kLeapClose;
@@ -5199,6 +5387,7 @@ static void read_env_knobs(nbmi_sim *s) {
     if (const char *e = getenv("NBMI_SORT_FUSED_HIST")) s->sort_fused_hist = atoi(e) != 0 ? 1 : 0;
     if (const char *e = getenv("NBMI_KEYS_LEAN")) s->keys_lean = atoi(e) != 0;
     if (const char *e = getenv("NBMI_PAIRS_CELLS")) s->pair_cells = atoi(e) != 0;
+    if (const char *e = getenv("NBMI_FIELD_SORT")) s->field_sort = atoi(e) != 0;
     if (const char *e = getenv("NBMI_FORCE_PREC")) {
         const int v = atoi(e);
         if (v >= 0 && v <= 2) s->force_prec = v;
@@ -6024,6 +6213,141 @@ int nbmi_pair_counts(nbmi_sim *s, int nb, const double *edges, int64_t *counts, 
     if (below) *below = (int64_t)h[2];
     for (int k = 0; counts && k < nb; k++) counts[k] = (int64_t)h[3 + k];
     return 0;
+}
+
+namespace {
+// nbmi_field_at's scratch for chunks of `need` points (nbmi_sim::field): rows double up to the chunk.  Nothing enqueued
+// uses the old arrays - the call that filled them has waited for its copies.
+int field_alloc(nbmi_sim *s, int64_t need) {
+    auto &f = s->field;
+    if (need <= f.rows) return 0;
+    int64_t rows = f.rows ? f.rows : kFieldMinRows;
+    while (rows < need) rows *= 2;
+    if (rows > kFieldChunk) rows = kFieldChunk;
+    dev_free(s, &f.pts); dev_free(s, &f.sx); dev_free(s, &f.sy); dev_free(s, &f.sz); dev_free(s, &f.acc); dev_free(s, &f.phi);
+    dev_free(s, &f.cnt); dev_free(s, &f.key); dev_free(s, &f.key_s); dev_free(s, &f.idx); dev_free(s, &f.order);
+    dev_free(s, &f.sort_tmp);
+    f.rows = 0;
+    const size_t r = (size_t)rows;
+    f.sort_bytes = nbmi::radix_temp_bytes_u64(r, kFieldSortBits);
+    if (dev_alloc(s, &f.pts, 3 * r) || dev_alloc(s, &f.sx, r) || dev_alloc(s, &f.sy, r) || dev_alloc(s, &f.sz, r) ||
+        dev_alloc(s, &f.acc, 3 * r) || dev_alloc(s, &f.phi, r) || dev_alloc(s, &f.cnt, r) || dev_alloc(s, &f.key, r) ||
+        dev_alloc(s, &f.key_s, r) || dev_alloc(s, &f.idx, r) || dev_alloc(s, &f.order, r) ||
+        dev_alloc(s, &f.sort_tmp, f.sort_bytes + 256) || (!f.wtab && dev_alloc(s, &f.wtab, 1)))
+        return NBMI_ERR_HIP;
+    NBMI_HIP_CHECK(nbmi::radix_init_temp(f.sort_tmp, s->stream));
+    f.rows = rows;
+    return 0;
+}
+
+// The chunks of one call, enqueued and copied out one after the other; the tree (Barnes-Hut) stands.  pmax: the call's
+// largest |coordinate|.
+int field_chunks(nbmi_sim *s, int64_t m, const double *pts, double pmax, double *acc, double *phi, int32_t *terms) {
+    auto &f = s->field;
+    hipStream_t st = s->stream;
+    const bool tree = s->method == NBMI_METHOD_BARNES_HUT;
+    const double eps2 = s->softening * s->softening;
+    for (int64_t b = 0; b < m; b += f.rows) {
+        const int64_t mc = m - b < f.rows ? m - b : f.rows;
+        NBMI_HIP_CHECK(hipMemcpyAsync(f.pts, pts + 3 * b, (size_t)mc * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+        if (!tree) {
+            k_field_direct<<<nblocks(mc), kBlock, 0, st>>>(s->buf[s->curbuf], s->n, s->G, eps2, f.pts, mc, acc ? f.acc : nullptr,
+                                                           phi ? f.phi : nullptr, terms ? f.cnt : nullptr);
+        } else {
+            // (a chunk of one wave is walked as it came: there is no neighbour to choose)
+            const bool sort = s->field_sort && mc > 64;
+            if (sort) {
+                if (s->hilbert) k_field_keys<true><<<nblocks(mc), kBlock, 0, st>>>(f.pts, mc, s->info, f.key, f.idx);
+                else k_field_keys<false><<<nblocks(mc), kBlock, 0, st>>>(f.pts, mc, s->info, f.key, f.idx);
+                NBMI_HIP_CHECK(nbmi::radix_sort_pairs_u64(f.sort_tmp, f.sort_bytes, f.key, f.key_s, f.idx, f.order, (size_t)mc,
+                                                          63 - kFieldSortBits, 63, st));
+            }
+            const uint32_t *order = sort ? f.order : nullptr;
+            k_field_gather<<<nblocks(mc), kBlock, 0, st>>>(f.pts, order, mc, f.sx, f.sy, f.sz);
+            with_bool(s->multipole == NBMI_MULTIPOLE_QUADRUPOLE, [&](auto q) {
+                k_field_tree<decltype(q)::value><<<nblocks(mc), kBlock, 0, st>>>(
+                    s->nodes, s->diag_pot, f.wtab, s->info, f.sx, f.sy, f.sz, order, mc, (float)eps2, s->softening, pmax,
+                    decltype(q)::value ? s->quad_work : nullptr, acc ? f.acc : nullptr, phi ? f.phi : nullptr,
+                    terms ? f.cnt : nullptr);
+            });
+        }
+        if (hipGetLastError() != hipSuccess) {
+            nbmi::set_error("nbmi_field_at: a kernel launch failed");
+            return NBMI_ERR_HIP;
+        }
+        if (acc) NBMI_HIP_CHECK(hipMemcpyAsync(acc + 3 * b, f.acc, (size_t)mc * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (phi) NBMI_HIP_CHECK(hipMemcpyAsync(phi + b, f.phi, (size_t)mc * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (terms) NBMI_HIP_CHECK(hipMemcpyAsync(terms + b, f.cnt, (size_t)mc * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        NBMI_HIP_CHECK(hipStreamSynchronize(st));  // the next chunk overwrites the scratch
+    }
+    if (tree) {
+        unsigned sort_err = 0u;
+        NBMI_HIP_CHECK(nbmi::radix_error_word(f.sort_tmp, &sort_err, st));
+        NBMI_HIP_CHECK(hipStreamSynchronize(st));
+        if (sort_err) {
+            NBMI_HIP_CHECK(nbmi::radix_init_temp(f.sort_tmp, st));
+            nbmi::set_error("nbmi_field_at: the sort of the points failed");
+            return NBMI_ERR_HIP;
+        }
+    }
+    return 0;
+}
+}  // namespace
+
+int nbmi_field_at(nbmi_sim *s, int64_t m, const double *points_xyz, double *acc_xyz, double *phi, int32_t *terms) {
+    if (int rc = check_handle(s)) return rc;
+    if (int rc = diag_refuse(s, "nbmi_field_at")) return rc;
+    if (m < 0) {
+        nbmi::set_error("nbmi_field_at: m = %lld is negative", (long long)m);
+        return NBMI_ERR_ARG;
+    }
+    if (m == 0) return 0;
+    if (int rc = require_out(points_xyz, "nbmi_field_at: null points_xyz")) return rc;
+    double pmax = 0.0;
+    for (int64_t i = 0; i < 3 * m; i++) {
+        const double v = fabs(points_xyz[i]);
+        if (!(v <= 1e18)) {  // (a NaN fails the comparison too)
+            nbmi::set_error("nbmi_field_at: points_xyz row %lld holds %g: coordinates must be finite and at most 1e18 in magnitude",
+                            (long long)(i / 3), points_xyz[i]);
+            return NBMI_ERR_ARG;
+        }
+        pmax = v > pmax ? v : pmax;
+    }
+    const int64_t n = s->n;
+    if (n == 0) {
+        for (int64_t i = 0; i < m; i++) {
+            if (acc_xyz) acc_xyz[3 * i] = acc_xyz[3 * i + 1] = acc_xyz[3 * i + 2] = 0.0;
+            if (phi) phi[i] = 0.0;
+            if (terms) terms[i] = 0;
+        }
+        return 0;
+    }
+    if (!acc_xyz && !phi && !terms) return 0;
+    hipStream_t st = s->stream;
+    if (s->method != NBMI_METHOD_BARNES_HUT) {
+        if (int rc = field_alloc(s, m)) return rc;
+        return field_chunks(s, m, points_xyz, pmax, acc_xyz, phi, terms);
+    }
+    if (!s->diag_pot && dev_alloc(s, &s->diag_pot, s->node_capacity + 2)) return NBMI_ERR_HIP;
+    // a capacity error of an earlier step is reported first, as a getter does
+    NBMI_HIP_CHECK(hipStreamSynchronize(st));
+    if (int rc = check_device_error(s)) return rc;
+    if (int rc = field_alloc(s, m)) return rc;
+    {
+        WalkTable t = walk_table(s);  // buffer 0 = the probes: see k_field_tree
+        t.buf[0].x = s->field.sx; t.buf[0].y = s->field.sy; t.buf[0].z = s->field.sz;
+        NBMI_HIP_CHECK(hipMemcpyAsync(s->field.wtab, &t, sizeof(t), hipMemcpyHostToDevice, st));
+        NBMI_HIP_CHECK(hipStreamSynchronize(st));  // `t` is a stack object
+    }
+    SideBuild side(s);  // (no "auto" decision in its build: the wave flags and force_all64 stay the last step's)
+    if (side.rc) return side.rc;
+    BuildRequest build;
+    build.aux = false; build.diag_rows = s->diag_pot;
+    int rc = enqueue_tree(s, build);
+    // the build's own capacity error before a point is walked: nothing is copied out of a walk that did not run
+    if (rc == 0) rc = check_device_error(s);
+    if (rc == 0) rc = field_chunks(s, m, points_xyz, pmax, acc_xyz, phi, terms);
+    return side.finish(rc, false);
 }
 
 int nbmi_set_color_mode(nbmi_sim *s, int mode, int k, double log10_lo, double log10_hi) {

@@ -1,0 +1,86 @@
+"""Host side of the field evaluation (include/nbmi.h nbmi_field_at): what is derived from the
+field at chosen points.  Pure NumPy over any object with ``field_at(points, potential=True)`` -> (acc (m, 3), phi (m,));
+no device."""
+import numpy as np
+
+
+def _unit(v, what):
+    v = np.asarray(v, dtype=np.float64).reshape(-1)
+    if v.shape != (3,) or not np.all(np.isfinite(v)) or not np.linalg.norm(v) > 0.0:
+        raise ValueError(f"{what} must be a finite, non-zero 3-vector, got {v}")
+    return v / np.linalg.norm(v)
+
+
+def _ring_frame(normal):
+    """Two unit vectors (e1, e2) that span the plane with the given normal, e1 x e2 = normal / |normal|."""
+    n = _unit(normal, "normal")
+    helper = np.zeros(3)
+    helper[int(np.argmin(np.abs(n)))] = 1.0  # the axis least aligned with the normal
+    if abs(n[2]) == 1.0:
+        helper = np.array([1.0, 0.0, 0.0])  # z normal: e1 = x, e2 = +-y
+    e1 = helper - np.dot(helper, n) * n
+    e1 /= np.linalg.norm(e1)
+    return e1, np.cross(n, e1)
+
+
+def _ring_dirs(azimuths, normal):
+    k = int(azimuths)
+    if k < 1:
+        raise ValueError(f"azimuths must be at least 1, got {azimuths}")
+    e1, e2 = _ring_frame(normal)
+    a = 2.0 * np.pi * np.arange(k) / k
+    return np.cos(a)[:, None] * e1 + np.sin(a)[:, None] * e2  # (k, 3) unit radial directions
+
+
+def _radii(radii):
+    r = np.asarray(radii, dtype=np.float64).reshape(-1)
+    if not np.all(np.isfinite(r)) or np.any(r <= 0.0):
+        raise ValueError("radii must be finite and positive")
+    return r
+
+
+def ring_points(center, radii, azimuths=16, normal=(0, 0, 1)):
+    """(len(radii) * azimuths, 3) points: for every radius, ``azimuths`` equally spaced points of the circle of that
+    radius about ``center`` in the plane with the given normal; row r * azimuths + k is radius r, azimuth k."""
+    c = np.asarray(center, dtype=np.float64).reshape(3)
+    r = _radii(radii)
+    d = _ring_dirs(azimuths, normal)
+    return (c + r[:, None, None] * d[None, :, :]).reshape(-1, 3)
+
+
+def rotation_curve(sim, radii, center, azimuths=16, normal=(0, 0, 1)):
+    """dict of (len(radii),) float64 arrays: ``radii``; ``a_radial``, the azimuthal mean of the inward acceleration
+    -a . r_hat on the ring; ``v_circ`` = sqrt(R max(a_radial, 0)), the speed of a circular orbit in that mean field;
+    ``phi``, the azimuthal mean of the potential."""
+    r = _radii(radii)
+    d = _ring_dirs(azimuths, normal)
+    acc, phi = sim.field_at(ring_points(center, r, azimuths, normal), potential=True)
+    acc = np.asarray(acc, dtype=np.float64).reshape(len(r), len(d), 3)
+    a_radial = -(acc * d[None, :, :]).sum(axis=2).mean(axis=1)
+    return {"radii": r, "a_radial": a_radial, "v_circ": np.sqrt(r * np.maximum(a_radial, 0.0)),
+            "phi": np.asarray(phi, dtype=np.float64).reshape(len(r), len(d)).mean(axis=1)}
+
+
+def potential_slice(sim, center, half_extent, resolution, axes=(0, 1)):
+    """(resolution, resolution) float64 image of phi on the square of half width ``half_extent`` through ``center``
+    spanned by the two coordinate ``axes``: pixel [i, j] is at center + u_j along axes[0] and + u_i along axes[1], u the
+    ``resolution`` pixel centres of [-half_extent, half_extent]."""
+    c = np.asarray(center, dtype=np.float64).reshape(3)
+    res = int(resolution)
+    a0, a1 = (int(a) for a in axes)
+    if res < 1 or not float(half_extent) > 0.0 or not np.isfinite(half_extent):
+        raise ValueError("potential_slice needs resolution >= 1 and a finite half_extent > 0")
+    if a0 == a1 or not {a0, a1} <= {0, 1, 2}:
+        raise ValueError(f"axes must be two different coordinates of 0, 1, 2, got {axes}")
+    u = (np.arange(res) + 0.5) * (2.0 * float(half_extent) / res) - float(half_extent)
+    pts = np.empty((res, res, 3), dtype=np.float64)
+    pts[:] = c
+    pts[:, :, a0] += u[None, :]
+    pts[:, :, a1] += u[:, None]
+    _, phi = sim.field_at(pts.reshape(-1, 3), potential=True)
+    return np.asarray(phi, dtype=np.float64).reshape(res, res)
+
+
+def escape_speed(phi):
+    """sqrt(max(-2 phi, 0)): the speed at which a test particle at potential phi is unbound (phi -> 0 at infinity)."""
+    return np.sqrt(np.maximum(-2.0 * np.asarray(phi, dtype=np.float64), 0.0))

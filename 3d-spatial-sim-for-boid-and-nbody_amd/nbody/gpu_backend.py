@@ -293,8 +293,35 @@ class _HIPSimulation:
         _nat.check(self._lib.nbmi_get_potentials_f64(self._h, _nat.ptr(out)), "nbmi_get_potentials_f64")
         return out
 
+    # ---- the field at arbitrary points (include/nbmi.h nbmi_field_at) ----
+    _field_refusal = None  # as _query_refusal below: the owner-mode class refuses before calling the library
+
+    def field_at(self, points, potential=True, terms=False):
+        """The gravitational field of the current float64 state at the (m, 3) ``points`` (any array-like): acc (m, 3)
+        float64, or (acc, phi) with ``potential``, or (acc, phi, terms) with ``terms`` (phi None without ``potential``)
+        - phi (m,) per unit mass, G included, terms (m,) int32 the nodes (direct handles: bodies) applied per point.
+        Barnes-Hut handles walk the tree of the current positions as a body at the point would, direct handles sum
+        over all bodies; a point's row does not depend on the other points.  ValueError for a wrong shape (before the
+        library is called), for a coordinate that is not finite or beyond 1e18, and for owner-mode and sharded handles.
+        The call does not change what the next step computes."""
+        what = "field_at"
+        if self._field_refusal:
+            raise ValueError(f"{what}: {self._field_refusal}")
+        p = np.ascontiguousarray(points, dtype=np.float64)
+        if p.ndim != 2 or p.shape[1] != 3:
+            raise ValueError(f"{what}: expected points of shape (m, 3), got {p.shape}")
+        m = len(p)
+        acc = np.zeros((m, 3), dtype=np.float64)
+        phi = np.zeros(m, dtype=np.float64) if potential else None
+        cnt = np.zeros(m, dtype=np.int32) if terms else None
+        _nat.check_arg(self._lib.nbmi_field_at(self._h, m, _nat.ptr(p), _nat.ptr(acc), _nat.ptr(phi), _nat.ptr(cnt)),
+                       what, "nbmi_field_at")
+        if terms:
+            return acc, phi, cnt
+        return (acc, phi) if potential else acc
+
     # ---- k-nearest neighbours, densities, density colours (include/nbmi.h nbmi_knn; DESIGN.md section 4.14) ----
-    _query_refusal = None  # classes whose handles the library refuses say so here, and refuse before calling it
+    _query_refusal = None # classes whose handles the library refuses say so here, and refuse before calling it
 
     def _query_call(self, what, rc):
         _nat.check_arg(rc, what)  # ValueError: refused for this handle, or a bad argument
@@ -682,6 +709,7 @@ class HIPOwnerSimulation(HIPBarnesHutSimulation):
         return int(self._lib.nbmi_owner_count(self._h)) if self._h else 0
 
     _query_refusal = "owner-mode handles are not supported (the neighbours may live on other ranks)"
+    _field_refusal = "owner-mode handles are not supported (the field needs the other ranks' trees)"
 
     def set_multipole(self, multipole: str):
         if _multipole_code(multipole) != MULTIPOLES["monopole"]:

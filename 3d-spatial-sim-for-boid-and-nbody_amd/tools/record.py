@@ -489,6 +489,51 @@ def pairs_line(sim, frame: int, edges) -> str:
                        "d2": d2, "d2_points": points}) + "\n"
 
 
+# ---- rotation curve (extra config key "rotation_curve") -------------------------------------
+ROTATION_FILE = "rotation.jsonl"
+CURVE_AUTO_RADII = 16  # "auto": spawn_radius * k / 16, k = 1 .. 16
+CURVE_MAX_RADII = 256
+CURVE_AZIMUTHS = 16
+
+
+def check_curve_radii(radii):
+    """The radii as a list of floats if a rotation curve can take them (ValueError otherwise): 1 .. 256 finite, positive,
+    strictly increasing values."""
+    r = np.asarray(radii, dtype=np.float64).reshape(-1)
+    if not 1 <= len(r) <= CURVE_MAX_RADII:
+        raise ValueError(f"need 1 .. {CURVE_MAX_RADII} radii, got {len(r)}")
+    if not np.all(np.isfinite(r)) or np.any(r <= 0.0) or np.any(np.diff(r) <= 0.0):
+        raise ValueError("the radii must be finite, positive and strictly increasing")
+    return [float(x) for x in r]
+
+
+def rotation_config(config: dict):
+    """The "rotation_curve" key of a config, {"every": K, "radii": [r0, r1, ...]}, as (every, radii); None without the
+    key; ValueError for a malformed one."""
+    g = config.get("rotation_curve")
+    if not g:
+        return None
+    every = int(g.get("every", 0))
+    if every <= 0:
+        raise ValueError(f"--rotation-curve: K must be positive, not {every}")
+    try:
+        return every, check_curve_radii(g.get("radii"))
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"--curve-radii: {e}") from None
+
+
+def rotation_line(sim, frame: int, radii) -> str:
+    """One JSON line (with its newline) for the rotation curve of the state `sim` holds after `frame`, about its centre
+    of mass in the plane z = const: per radius the azimuthal means of the inward acceleration and of the potential over
+    CURVE_AZIMUTHS points of the ring, and the circular speed in that mean field (nbody/field.py)."""
+    from nbody.field import rotation_curve
+    center = [float(x) for x in sim.diagnostics(potential=False).center_of_mass]
+    c = rotation_curve(sim, radii, center, azimuths=CURVE_AZIMUTHS, normal=(0, 0, 1))
+    return json.dumps({"frame": frame, "center": center, "radii": [float(r) for r in radii],
+                       "a_radial": [float(x) for x in c["a_radial"]], "v_circ": [float(x) for x in c["v_circ"]],
+                       "phi": [float(x) for x in c["phi"]]}) + "\n"
+
+
 # ---- periodic side files: one description each, one mechanism for all (DESIGN.md section 4.17) -----------------------
 @dataclass(frozen=True)
 class LineStream:
@@ -523,8 +568,9 @@ GROUPS = LineStream(GROUPS_FILE, groups_config, groups_line, key="groups",
                     auto=lambda sim, s: {"every": s[0], "link": default_linking_length(sim.knn(1)[0]), "min_members": s[2]})
 PAIRS = LineStream(PAIRS_FILE, pairs_config, pairs_line, key="pairs",
                    auto=lambda sim, s: {"every": s[0], "edges": auto_pair_edges(sim.knn(1)[0])})
+ROTATION = LineStream(ROTATION_FILE, rotation_config, rotation_line)  # ("auto" radii need no state: build_config)
 apply_groups, apply_pairs = GROUPS.apply, PAIRS.apply  # (gpu_sim, config, rec_dir=None) -> the config, "auto" resolved
-LINE_STREAMS = (DIAGNOSTICS, GROUPS, PAIRS)  # in the order of their lines after a frame; a new side file is one more entry
+LINE_STREAMS = (DIAGNOSTICS, GROUPS, PAIRS, ROTATION)  # in the order of their lines after a frame; a new side file is one more entry
 
 
 def line_due(frame: int, every: int) -> bool:
@@ -733,7 +779,7 @@ def record(config: dict, resume: bool = False, root: Path = None, quiet: bool = 
     say(f"[Record] GPU acceleration: {backend.value} - {info}")
     # extra config key "color": {"mode": "density", "k": K, "log10_range": [lo, hi]} = frames coloured by the k-NN
     # density through the unchanged colour and frame calls of both loops
-    # extra config keys "diagnostics_every", "groups", "pairs": every K-th frame a line in a side file (LINE_STREAMS)
+    # extra config keys "diagnostics_every", "groups", "pairs", "rotation_curve": every K-th frame a line in a side file (LINE_STREAMS)
     try:
         config = apply_color_mode(gpu_sim, config, rec_dir)
         for stream in LINE_STREAMS:
@@ -869,6 +915,15 @@ def show_status(session_name: str, root: Path = None) -> bool:
             print(f"    frame {last['frame']}: D2 = "
                   + (f"{last['d2']:.3f} over {last['d2_points']} edges" if last.get("d2") is not None else "n/a")
                   + f", {within:,} pairs within {last['edges'][-1]:.6g}")
+    rc = meta.get("rotation_curve")
+    if rc:
+        radii = rc.get("radii") or [0.0]
+        print(f"  Rotation curve: every {rc.get('every')} frames, {len(radii)} radii from {radii[0]:.6g} to {radii[-1]:.6g}")
+        rrows = read_diagnostics(rec_dir / ROTATION_FILE)
+        if rrows:
+            last = rrows[-1]
+            k = int(np.argmax(last["v_circ"]))
+            print(f"    frame {last['frame']}: peak v_circ = {last['v_circ'][k]:.6g} at R = {last['radii'][k]:.6g}")
     if completed < total:
         print(f"\n  To resume: python -m tools.record --resume {session_name}")
     else:
@@ -907,7 +962,8 @@ def build_parser():
                "--preset-id); --preset-id indexes this build's preset list (python -m tools.record --presets shows "
                "it); --dt sets dt_per_frame (the reference writes an unused 'dt' key); --presets, --seed, "
                "--device-ic, --diagnostics, --integrator, --multipole, --pipeline, --color, --density-k, --density-range, "
-               "--groups, --linking-length, --min-members, --pairs, --pair-edges and --root are additions.")
+               "--groups, --linking-length, --min-members, --pairs, --pair-edges, --rotation-curve, --curve-radii and --root are "
+               "additions.")
     ap.add_argument("session", nargs="?", help="session name (for --resume, --status or --extend)")
     ap.add_argument("--resume", action="store_true", help="resume an interrupted recording (default: the most recent)")
     ap.add_argument("--extend", type=int, metavar="FRAMES", help="extend an existing recording by N frames")
@@ -958,6 +1014,12 @@ def build_parser():
     ap.add_argument("--pair-edges", type=str, default=None, metavar="auto|e0,e1,...",
                     help="bin edges, 2 .. 65 increasing distances (default auto: taken once from the initial state, 12 "
                          "bins from half to 32 median nearest-neighbour distances, a factor sqrt 2 apart)")
+    ap.add_argument("--rotation-curve", type=int, default=None, metavar="K",
+                    help="every K frames append the rotation curve about the centre of mass (inward acceleration, circular "
+                         "speed and potential per radius, means over 16 azimuths in the plane z = const) to rotation.jsonl "
+                         "(stored in metadata.json as rotation_curve)")
+    ap.add_argument("--curve-radii", type=str, default=None, metavar="auto|r0,r1,...",
+                    help="1 .. 256 increasing radii (default auto: 16 radii, spawn_radius k / 16 for k = 1 .. 16)")
     ap.add_argument("--root", type=Path, default=None, help="directory holding recordings/ (default: the package's)")
     return ap
 
@@ -1043,6 +1105,19 @@ def build_config(args) -> dict:
                 raise ValueError(f"--pair-edges: need auto or comma-separated numbers, not {pe!r}") from None
         config["pairs"] = {"every": int(pk), "edges": edges}
         pairs_config(config)  # (a bad K or bad edges raise here)
+    ck, cr = (getattr(args, a, None) for a in ("rotation_curve", "curve_radii"))
+    if ck is None and cr is not None:
+        raise ValueError("--curve-radii needs --rotation-curve K")
+    if ck is not None:  # the default writes no key
+        if cr is None or cr.strip().lower() == "auto":
+            radii = [config["spawn_radius"] * k / CURVE_AUTO_RADII for k in range(1, CURVE_AUTO_RADII + 1)]
+        else:
+            try:
+                radii = [float(x) for x in cr.split(",")]
+            except ValueError:
+                raise ValueError(f"--curve-radii: need auto or comma-separated numbers, not {cr!r}") from None
+        config["rotation_curve"] = {"every": int(ck), "radii": radii}
+        rotation_config(config)  # (a bad K or bad radii raise here)
     return config
 
 

@@ -351,6 +351,55 @@ int nbmi_compute_group_colors(nbmi_sim *sim, double link, int64_t min_members);
 int nbmi_pair_counts(nbmi_sim *sim, int nb, const double *edges, int64_t *counts /* (nb,), may be NULL */,
                      int64_t *below /* may be NULL */, int64_t *evals /* may be NULL */, int64_t *cell_pairs /* may be NULL */);
 
+/* The gravitational field of the handle's current float64 state at m arbitrary points: what a
+ * test particle at points_xyz[i] would feel.  The kernels and the tests' NumPy restatement (tests/field_ref.py) both
+ * follow this text.  All arithmetic is float64 in the association written, without FMA contraction.
+ *
+ * Barnes-Hut handle.  The walk is the reference's (nbody/simulation.py:237-274) for a body at p that is not in the tree,
+ * over the octree every other call builds for the current positions.  There is no own-leaf rule.  With c the node's
+ * centre of mass (a leaf: its body's position), G M its mass times G - both from the build's float64 node rows, the rows
+ * nbmi_get_potentials_f64 reads - and half its half size:
+ *   d       = c - p per component
+ *   dist_sq = ((dx dx + dy dy) + dz dz) + eps^2,   dist = sqrt(dist_sq)
+ *   a node is accepted when it is a leaf or (2 half) / dist < theta; otherwise it is opened;
+ *   an accepted node is applied only when G M > 0 and dist_sq > eps^2: a point that coincides with a body gets nothing
+ *   from that body's leaf - the rule the force and potential walks have for coincident bodies;
+ *   an applied node adds   acc += d * (G M / (dist * dist_sq)),   phi -= G M / dist.
+ * terms[i] = the number of nodes applied to point i.
+ * In quadrupole mode (nbmi_set_multipole) an applied internal cell also carries the second-order terms, evaluated in
+ * float64 from the cell's float64 second moments P about its centre of mass (G folded in), with u = dist_sq:
+ *   phi += 1/2 [tr P u^-3/2 - 3 (d^T P d) u^-5/2]
+ *   acc += [7.5 (d^T P d) u^-7/2 - 1.5 tr P u^-5/2] d - 3 u^-5/2 P d
+ * terms is the same in both modes.
+ * Direct handle.  The exact sum over all N bodies with the same two formulas (G M = G m_j, c = x_j) and the one guard
+ * dist_sq > eps^2; terms[i] = the number of bodies applied.
+ *
+ * Fixed summation order.  Each point sums its terms in pre-order of the node array (direct: in body order).  A point's
+ * result does not depend on the other points of the call, on their order or on how the call is split: two calls give the
+ * same bits, duplicated points give identical rows, a permutation of the points permutes the rows.
+ * Consequences (tested bit for bit, monopole and quadrupole), Barnes-Hut: the accepted set at a body's own position is
+ * that body's set, so with points = nbmi_get_positions_f64, phi equals nbmi_get_potentials_f64 and the sum of terms
+ * equals nbmi_diagnostics' terms.
+ *
+ * acc_xyz ((m,3)), phi ((m,)) and terms ((m,) int32) may each be NULL.  m == 0: success, nothing is touched.  N == 0:
+ * zeros.  NBMI_ERR_ARG, message "nbmi_field_at: ...": m < 0, null points_xyz with m > 0, a coordinate that is not finite
+ * or exceeds 1e18 in magnitude (the message names the first bad row), owner-mode handles and handles with a proper shard.
+ * Points may lie anywhere, outside the root cube too.
+ * A call changes nothing that a later step reads (state and its order, the tree header - saved and restored -, the
+ * "auto" precision flags and force_all64 - the build runs without a dt -, the step count, the stored leapfrog
+ * acceleration): a leapfrog handle returns a plain handle's bits.  NBMI_ERR_CAPACITY of the call's own tree build is
+ * reported with a step's message.
+ * The points are processed in chunks of at most 1 048 576; within a chunk of more than 64 points they are walked in the
+ * order of their octant keys in the tree's root cube (outside coordinates clamped to its faces) - speed only, see the
+ * fixed order above.  Scratch: 108 bytes per point of the largest chunk so far plus the sort's temp buffer for that many
+ * (key, index) pairs - at most 113 MB and that buffer, however large m is - and, shared with nbmi_get_potentials_f64, 32
+ * bytes per node row.  Uploads and downloads go chunk by chunk through that scratch.
+ * Environment NBMI_FIELD_SORT (read when the handle is created, like the other measurement knobs): 0 walks the points
+ * in the caller's order.  Results are the same; the time is not. */
+int nbmi_field_at(nbmi_sim *sim, int64_t m, const double *points_xyz /* (m,3) */,
+                  double *acc_xyz /* (m,3), may be NULL */, double *phi /* (m,), may be NULL */,
+                  int32_t *terms /* (m,), may be NULL */);
+
 /* Multi-GPU (one process per GPU).  A handle created with nbmi_create holds ALL bodies; with a
  * shard set, step() integrates only the key-sorted ranks [begin,end) (direct method: the body
  * indices [begin,end), its state is never re-ordered) and leaves the others untouched until
