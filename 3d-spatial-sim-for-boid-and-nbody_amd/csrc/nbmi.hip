@@ -4347,21 +4347,18 @@ __global__ __launch_bounds__(kBlock) void k_field_gather(const double *__restric
 //   a += [7.5 (d^T P d) u^-7/2 - 1.5 tr P u^-5/2] d - 3 u^-5/2 P d,   u = dist_sq,
 // from the float64 moments of k_quad_level, in a scope of their own.
 // Results land at the probe's row of the chunk, order[rank].
+// The per-lane walk itself, shared by k_field_tree and k_tracer_tree: the probe (qx, qy, qz) is row `row` of the probe
+// columns; a lane with valid == false walks nothing and returns zeros.
+struct FieldSum {
+    double ax, ay, az, phi;
+    int32_t terms;
+};
 template <bool kQuad>
-__global__ __launch_bounds__(kBlock) void k_field_tree(const Node *__restrict__ nodes, const double4 *__restrict__ pot,
-                                                       const WalkTable *tab, const TreeInfo *info,
-                                                       const double *__restrict__ sx, const double *__restrict__ sy,
-                                                       const double *__restrict__ sz, const uint32_t *__restrict__ order, int64_t m,
-                                                       float eps2f, double eps, double pmax, const double *__restrict__ quad,
-                                                       double *__restrict__ acc_out, double *__restrict__ phi_out,
-                                                       int32_t *__restrict__ cnt_out) {
-    if (info->error != 0 || info->sticky_error != 0) return;  // the tree did not fit: the caller reports it
-    const int64_t rank = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    const bool valid = rank < m;
-    double qx = 0.0, qy = 0.0, qz = 0.0;
-    if (valid) { qx = sx[rank]; qy = sy[rank]; qz = sz[rank]; }
+__device__ __forceinline__ FieldSum field_walk(const Node *__restrict__ nodes, const double4 *__restrict__ pot, const WalkTable *tab,
+                                               const TreeInfo *info, double qx, double qy, double qz, uint32_t row, bool valid,
+                                               float eps2f, double eps, double pmax, const double *__restrict__ quad) {
     const float px = (float)qx, py = (float)qy, pz = (float)qz;
-    const Body64 b64{tab, 0, (uint32_t)(valid ? rank : 0)};
+    const Body64 b64{tab, 0, row};
     const unsigned nn = __builtin_amdgcn_readfirstlane((unsigned)info->num_nodes * kNodeBytes);
     const double eps2 = __longlong_as_double((long long)uniform_u64((unsigned long long)__double_as_longlong(tab->eps2)));
     const double maxabs = fmax(__longlong_as_double((long long)info->maxabs_bits), pmax);
@@ -4418,25 +4415,38 @@ __global__ __launch_bounds__(kBlock) void k_field_tree(const Node *__restrict__ 
         }
         off = next;
     }
+    return FieldSum{ax, ay, az, phi, terms};
+}
+
+template <bool kQuad>
+__global__ __launch_bounds__(kBlock) void k_field_tree(const Node *__restrict__ nodes, const double4 *__restrict__ pot,
+                                                       const WalkTable *tab, const TreeInfo *info,
+                                                       const double *__restrict__ sx, const double *__restrict__ sy,
+                                                       const double *__restrict__ sz, const uint32_t *__restrict__ order, int64_t m,
+                                                       float eps2f, double eps, double pmax, const double *__restrict__ quad,
+                                                       double *__restrict__ acc_out, double *__restrict__ phi_out,
+                                                       int32_t *__restrict__ cnt_out) {
+    if (info->error != 0 || info->sticky_error != 0) return;  // the tree did not fit: the caller reports it
+    const int64_t rank = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const bool valid = rank < m;
+    double qx = 0.0, qy = 0.0, qz = 0.0;
+    if (valid) { qx = sx[rank]; qy = sy[rank]; qz = sz[rank]; }
+    const FieldSum f = field_walk<kQuad>(nodes, pot, tab, info, qx, qy, qz, (uint32_t)(valid ? rank : 0), valid, eps2f, eps, pmax, quad);
     if (valid) {
         const int64_t o = order ? (int64_t)order[rank] : rank;
-        if (acc_out) { acc_out[3 * o] = ax; acc_out[3 * o + 1] = ay; acc_out[3 * o + 2] = az; }
-        if (phi_out) phi_out[o] = phi;
-        if (cnt_out) cnt_out[o] = terms;
+        if (acc_out) { acc_out[3 * o] = f.ax; acc_out[3 * o + 1] = f.ay; acc_out[3 * o + 2] = f.az; }
+        if (phi_out) phi_out[o] = f.phi;
+        if (cnt_out) cnt_out[o] = f.terms;
     }
 }
 
 // Direct handle: the sum over all bodies in body order, k_potential_direct's twin with a point in the thread.  The only
 // guard is the definition's dist_sq > eps^2.
-__global__ __launch_bounds__(kBlock) void k_field_direct(Bodies cur, int64_t n, double G, double eps2, const double *__restrict__ pts,
-                                                         int64_t m, double *__restrict__ acc_out, double *__restrict__ phi_out,
-                                                         int32_t *__restrict__ cnt_out) {
-    __shared__ double4 tile[kBlock];
+// The sum itself, shared by k_field_direct and k_tracer_direct; every thread of the block calls it (`tile`: kBlock rows of
+// shared memory).
+__device__ __forceinline__ FieldSum field_direct_sum(const Bodies &cur, int64_t n, double G, double eps2, double x, double y, double z,
+                                                     double4 *tile) {
     const int t = threadIdx.x;
-    const int64_t i = (int64_t)blockIdx.x * kBlock + t;
-    const bool valid = i < m;
-    double x = 0.0, y = 0.0, z = 0.0;
-    if (valid) { x = pts[3 * i]; y = pts[3 * i + 1]; z = pts[3 * i + 2]; }
     double ax = 0.0, ay = 0.0, az = 0.0, phi = 0.0;
     int32_t terms = 0;
     for (int64_t base = 0; base < n; base += kBlock) {
@@ -4458,11 +4468,137 @@ __global__ __launch_bounds__(kBlock) void k_field_direct(Bodies cur, int64_t n, 
         }
         __syncthreads();
     }
+    return FieldSum{ax, ay, az, phi, terms};
+}
+
+__global__ __launch_bounds__(kBlock) void k_field_direct(Bodies cur, int64_t n, double G, double eps2, const double *__restrict__ pts,
+                                                         int64_t m, double *__restrict__ acc_out, double *__restrict__ phi_out,
+                                                         int32_t *__restrict__ cnt_out) {
+    __shared__ double4 tile[kBlock];
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const bool valid = i < m;
+    double x = 0.0, y = 0.0, z = 0.0;
+    if (valid) { x = pts[3 * i]; y = pts[3 * i + 1]; z = pts[3 * i + 2]; }
+    const FieldSum f = field_direct_sum(cur, n, G, eps2, x, y, z, tile);
     if (valid) {
-        if (acc_out) { acc_out[3 * i] = ax; acc_out[3 * i + 1] = ay; acc_out[3 * i + 2] = az; }
-        if (phi_out) phi_out[i] = phi;
-        if (cnt_out) cnt_out[i] = terms;
+        if (acc_out) { acc_out[3 * i] = f.ax; acc_out[3 * i + 1] = f.ay; acc_out[3 * i + 2] = f.az; }
+        if (phi_out) phi_out[i] = f.phi;
+        if (cnt_out) cnt_out[i] = f.terms;
     }
+}
+
+// ---------------------------------------------------------------------------------------
+// K20: massless tracers carried by the integrator (nbmi_set_tracers; include/nbmi.h).
+// The probe walks of K19 with the handle's integrator as their epilogue, on the tree the step has just built.  State:
+// p, v (and the leapfrog's a), (m, 3) float64 rows in the caller's order.  kLeap: 0 = kick-drift, kLeapClose = the
+// leapfrog's closing half-kick (a is stored), kLeapPrime = a = F(p) stored, state untouched.
+// ---------------------------------------------------------------------------------------
+constexpr int64_t kTracerMax = (int64_t)1 << 26;  // the largest m nbmi_set_tracers accepts
+
+// A retired tracer's row is left alone: a position beyond 1e18 (nbmi_field_at's limit) or anything that is not finite.
+__device__ __forceinline__ bool tracer_live(double px, double py, double pz, double vx, double vy, double vz) {
+    return fabs(px) <= 1e18 && fabs(py) <= 1e18 && fabs(pz) <= 1e18 && isfinite(vx) && isfinite(vy) && isfinite(vz);
+}
+
+// The largest |coordinate| the tracers have reached since nbmi_set_tracers, as the bit pattern of a non-negative double
+// (k_field_tree's pmax, kept on the device: it only ever grows, and a band wider than needed changes no decision).  One
+// atomic per wave, and only where it would raise the word.  Positions of tracers that retire with this move do not count.
+__device__ __forceinline__ void tracer_raise_pmax(unsigned long long *pmax, bool moved, double px, double py, double pz) {
+    double mx = moved ? fmax(fmax(fabs(px), fabs(py)), fabs(pz)) : 0.0;
+    mx = mx <= 1e18 ? mx : 0.0;  // (a NaN fails the comparison too)
+    mx = wave_max(mx);
+    if ((threadIdx.x & 63) == 0) {
+        const unsigned long long bits = (unsigned long long)__double_as_longlong(mx);
+        if (bits > __atomic_load_n(pmax, __ATOMIC_RELAXED)) atomicMax(pmax, bits);
+    }
+}
+
+// What the integrator does with a = F(p) of one live tracer, row o.  Returns whether p moved.
+template <int kLeap>
+__device__ __forceinline__ bool tracer_epilogue(double *__restrict__ p, double *__restrict__ v, double *__restrict__ a, int64_t o,
+                                                double &px, double &py, double &pz, double vx, double vy, double vz,
+                                                const FieldSum &f, double dt, double damping) {
+    if (kLeap != 0) { a[3 * o] = f.ax; a[3 * o + 1] = f.ay; a[3 * o + 2] = f.az; }
+    if (kLeap == kLeapPrime) return false;
+    const double k = kLeap == kLeapClose ? 0.5 * dt : dt;
+    vx = (vx + f.ax * k) * damping; vy = (vy + f.ay * k) * damping; vz = (vz + f.az * k) * damping;
+    v[3 * o] = vx; v[3 * o + 1] = vy; v[3 * o + 2] = vz;
+    if (kLeap != 0) return false;
+    px = px + vx * dt; py = py + vy * dt; pz = pz + vz * dt;
+    p[3 * o] = px; p[3 * o + 1] = py; p[3 * o + 2] = pz;
+    return true;
+}
+
+// One chunk of tracers on the tree that stands: lane `rank` walks the probe of the sorted columns (k_field_gather of the
+// chunk's rows of p) and integrates row order[rank] of the chunk (p, v, a: the chunk's first row).  Writing p in place is
+// safe: opening()'s float64 re-decision reads the sorted copies.
+template <bool kQuad, int kLeap>
+__global__ __launch_bounds__(kBlock) void k_tracer_tree(const Node *__restrict__ nodes, const double4 *__restrict__ pot,
+                                                        const WalkTable *tab, const TreeInfo *info,
+                                                        const double *__restrict__ sx, const double *__restrict__ sy,
+                                                        const double *__restrict__ sz, const uint32_t *__restrict__ order, int64_t m,
+                                                        float eps2f, double eps, unsigned long long *pmax_word,
+                                                        const double *__restrict__ quad, double *__restrict__ p,
+                                                        double *__restrict__ v, double *__restrict__ a, double dt, double damping) {
+    if (info->error != 0 || info->sticky_error != 0) return;  // the tree did not fit: neither bodies nor tracers advance
+    const int64_t rank = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const bool inside = rank < m;
+    double qx = 0.0, qy = 0.0, qz = 0.0, vx = 0.0, vy = 0.0, vz = 0.0;
+    int64_t o = 0;
+    if (inside) {
+        o = order ? (int64_t)order[rank] : rank;
+        qx = sx[rank]; qy = sy[rank]; qz = sz[rank];
+        vx = v[3 * o]; vy = v[3 * o + 1]; vz = v[3 * o + 2];
+    }
+    const bool live = inside && tracer_live(qx, qy, qz, vx, vy, vz);
+    const double pmax = __longlong_as_double((long long)__atomic_load_n(pmax_word, __ATOMIC_RELAXED));
+    const FieldSum f = field_walk<kQuad>(nodes, pot, tab, info, qx, qy, qz, (uint32_t)(inside ? rank : 0), live, eps2f, eps, pmax, quad);
+    bool moved = false;
+    if (live) moved = tracer_epilogue<kLeap>(p, v, a, o, qx, qy, qz, vx, vy, vz, f, dt, damping);
+    if (kLeap == 0) tracer_raise_pmax(pmax_word, moved, qx, qy, qz);
+}
+
+// Direct handle (and any handle without bodies: a = 0): all m tracers in the caller's order, k_field_direct's sum.
+template <int kLeap>
+__global__ __launch_bounds__(kBlock) void k_tracer_direct(Bodies cur, int64_t n, double G, double eps2, int64_t m,
+                                                          double *__restrict__ p, double *__restrict__ v, double *__restrict__ a,
+                                                          double dt, double damping) {
+    __shared__ double4 tile[kBlock];
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const bool inside = i < m;
+    double x = 0.0, y = 0.0, z = 0.0, vx = 0.0, vy = 0.0, vz = 0.0;
+    if (inside) {
+        x = p[3 * i]; y = p[3 * i + 1]; z = p[3 * i + 2];
+        vx = v[3 * i]; vy = v[3 * i + 1]; vz = v[3 * i + 2];
+    }
+    const FieldSum f = field_direct_sum(cur, n, G, eps2, x, y, z, tile);
+    if (inside && tracer_live(x, y, z, vx, vy, vz)) tracer_epilogue<kLeap>(p, v, a, i, x, y, z, vx, vy, vz, f, dt, damping);
+}
+
+// [leapfrog] The tracers' opening half-kick and drift, in place: v = v + a dt/2, p = p + v dt.  info (Barnes-Hut): the
+// header of the substep's tree - a build that did not fit leaves the tracers where they were, as it leaves the bodies.
+// pmax (Barnes-Hut): see tracer_raise_pmax; every thread of the grid takes part in its wave's maximum.
+__global__ __launch_bounds__(kBlock) void k_tracer_kick_drift(const TreeInfo *info, int64_t m, double *__restrict__ p,
+                                                              double *__restrict__ v, const double *__restrict__ a, double dt,
+                                                              unsigned long long *pmax) {
+    if (info && (info->error != 0 || info->sticky_error != 0)) return;
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const double h = 0.5 * dt;
+    bool moved = false;
+    double x = 0.0, y = 0.0, z = 0.0;
+    if (i < m) {
+        x = p[3 * i]; y = p[3 * i + 1]; z = p[3 * i + 2];
+        double vx = v[3 * i], vy = v[3 * i + 1], vz = v[3 * i + 2];
+        const double ax = a[3 * i], ay = a[3 * i + 1], az = a[3 * i + 2];
+        if (tracer_live(x, y, z, vx, vy, vz) && isfinite(ax) && isfinite(ay) && isfinite(az)) {
+            vx = vx + ax * h; vy = vy + ay * h; vz = vz + az * h;
+            x = x + vx * dt; y = y + vy * dt; z = z + vz * dt;
+            v[3 * i] = vx; v[3 * i + 1] = vy; v[3 * i + 2] = vz;
+            p[3 * i] = x; p[3 * i + 1] = y; p[3 * i + 2] = z;
+            moved = true;
+        }
+    }
+    if (pmax) tracer_raise_pmax(pmax, moved, x, y, z);
 }
 
 }  // namespace
@@ -4654,6 +4790,24 @@ struct nbmi_sim {
         WalkTable *wtab = nullptr;
     } field;
     bool field_sort = true;  // probes walk in key order (NBMI_FIELD_SORT=0: in the caller's order; measurement)
+    // Massless tracers (nbmi_set_tracers, section 4.19); all null / 0 on a handle without them.  State: p and v, (m, 3)
+    // rows in the caller's order, and the leapfrog's a (allocated by the first leapfrog step; acc_valid as the bodies').
+    // pmax: the device word of tracer_raise_pmax.  Scratch (Barnes-Hut): `rows` = min(m, kFieldChunk) probes in walk order,
+    // sort keys and indices in and out, the sort's temp buffer and a walk table whose buffer 0 names the columns.  The
+    // steps enqueue work on it without waiting, so it is the tracers' own: nbmi_field_at's regrowth never frees it.
+    struct {
+        int64_t m = 0;
+        double *p = nullptr, *v = nullptr, *a = nullptr;
+        bool acc_valid = false;
+        unsigned long long *pmax = nullptr;
+        int64_t rows = 0;
+        double *sx = nullptr, *sy = nullptr, *sz = nullptr;
+        uint64_t *key = nullptr, *key_s = nullptr;
+        uint32_t *idx = nullptr, *order = nullptr;
+        char *sort_tmp = nullptr;
+        size_t sort_bytes = 0;
+        WalkTable *wtab = nullptr;
+    } tr;
     // what nbmi_compute_colors / nbmi_frame_begin colour by (nbmi_set_color_mode)
     int color_mode = NBMI_COLOR_SPEED, color_k = 32;
     double color_lo = 0.0, color_hi = 1.0;
@@ -4766,7 +4920,7 @@ int require_out(const void *p, const char *what = "null output") {
 // The positions changed behind the handle's back, or what a mass or a force means did: the tree no longer describes
 // the state, maxabs_next is not its extent, and the leapfrog's stored a = F(x) is not its force.  A site that drops
 // fewer than these three says which survive and why.
-void state_changed(nbmi_sim *s) { s->tree_valid = s->maxabs_fused = s->acc_valid = false; }
+void state_changed(nbmi_sim *s) { s->tree_valid = s->maxabs_fused = s->acc_valid = s->tr.acc_valid = false; }
 
 // Runtime values as template arguments: f is a generic lambda and gets std::true_type / std::false_type, or the
 // std::integral_constant of the one of Vs... that v equals (v is always one of them).
@@ -4799,8 +4953,10 @@ struct BuildRequest {
     double4 *diag_rows = nullptr;
     double step_dt = 0.0;
 };
+// (A handle with tracers also asks for the float64 node rows their walk reads; a quadrupole build writes its own.)
 BuildRequest step_build(const nbmi_sim *s, double dt, BuildTiming timed) {
-    return BuildRequest{s->timers ? timed : BuildTiming::kNone, false, nullptr, dt};
+    double4 *rows = s->tr.m && s->multipole != NBMI_MULTIPOLE_QUADRUPOLE ? s->diag_pot : nullptr;
+    return BuildRequest{s->timers ? timed : BuildTiming::kNone, false, rows, dt};
 }
 // What enqueue_local_sort is asked for.  Owner mode: n_sort rows are keyed and sorted (rows of emigrants are still in
 // place, flagged `dead`, and sort to the end); the first n_live of the order are gathered for the tree.
@@ -5140,7 +5296,7 @@ int launch_direct(nbmi_sim *s, double dt, double *acc_out, int leap = 0) {
 // [leapfrog] The acceleration columns exist (allocated by the first leapfrog step) and hold a = F(x) of the current state
 // (primed once after create / nbmi_set_state / a switch into leapfrog / a reported capacity error, inside the step so that
 // force precision "auto" sees its dt).
-int leap_prepare(nbmi_sim *s, double dt) {
+int leap_prepare_bodies(nbmi_sim *s, double dt) {
     if (!s->acc) {
         if (dev_alloc(s, &s->acc, (size_t)3 * s->n)) return NBMI_ERR_HIP;
         NBMI_HIP_CHECK(hipMemsetAsync(s->acc, 0, (size_t)3 * s->n * sizeof(double), s->stream));
@@ -5156,6 +5312,12 @@ int leap_prepare(nbmi_sim *s, double dt) {
     }
     s->acc_valid = true;
     return 0;
+}
+int tracer_leap_prepare(nbmi_sim *s);  // (below, beside the other tracer stages)
+// the bodies' stored acceleration, then the tracers'
+int leap_prepare(nbmi_sim *s, double dt) {
+    if (int rc = leap_prepare_bodies(s, dt)) return rc;
+    return s->tr.m ? tracer_leap_prepare(s) : 0;
 }
 
 // [leapfrog] Opening half-kick + drift of the current buffer into the other one (k_kick_drift), which becomes current
@@ -5266,6 +5428,92 @@ struct SideBuild {
         return r;
     }
 };
+
+// ---- tracers (section 4.19): what a step enqueues for them; nothing here waits for the device ----
+// Whether the tracers' field comes from k_field_direct's sum: a direct handle, or no bodies at all (a = 0).
+bool tracers_direct(const nbmi_sim *s) { return s->method != NBMI_METHOD_BARNES_HUT || s->n == 0; }
+
+// All tracers through one walk with epilogue `leap` (0 / kLeapClose / kLeapPrime).  Barnes-Hut: on the tree that stands,
+// built with the float64 node rows (step_build); chunk by chunk through the tracers' scratch - keys in the tree's root
+// cube, sort, gather, walk - as nbmi_field_at's chunks go.
+int enqueue_tracers(nbmi_sim *s, int leap, double dt) {
+    auto &t = s->tr;
+    hipStream_t st = s->stream;
+    const double eps2 = s->softening * s->softening;
+    if (tracers_direct(s)) {  // (one launch per chunk too: m x N pair terms in one kernel would hold the device for long)
+        for (int64_t b = 0; b < t.m; b += kFieldChunk) {
+            const int64_t mc = t.m - b < kFieldChunk ? t.m - b : kFieldChunk;
+            with_int<0, kLeapClose, kLeapPrime>(leap, [&](auto lv) {
+                k_tracer_direct<decltype(lv)::value><<<nblocks(mc), kBlock, 0, st>>>(
+                    s->buf[s->curbuf], s->n, s->G, eps2, mc, t.p + 3 * b, t.v + 3 * b, t.a ? t.a + 3 * b : nullptr, dt, s->damping);
+            });
+            NBMI_HIP_CHECK(hipGetLastError());
+        }
+        return 0;
+    }
+    const bool quad = s->multipole == NBMI_MULTIPOLE_QUADRUPOLE;
+    for (int64_t b = 0; b < t.m; b += t.rows) {
+        const int64_t mc = t.m - b < t.rows ? t.m - b : t.rows;
+        double *p = t.p + 3 * b, *v = t.v + 3 * b, *a = t.a ? t.a + 3 * b : nullptr;
+        const bool sort = s->field_sort && mc > 64;
+        if (sort) {
+            if (s->hilbert) k_field_keys<true><<<nblocks(mc), kBlock, 0, st>>>(p, mc, s->info, t.key, t.idx);
+            else k_field_keys<false><<<nblocks(mc), kBlock, 0, st>>>(p, mc, s->info, t.key, t.idx);
+            NBMI_HIP_CHECK(nbmi::radix_sort_pairs_u64(t.sort_tmp, t.sort_bytes, t.key, t.key_s, t.idx, t.order, (size_t)mc,
+                                                      63 - kFieldSortBits, 63, st));
+        }
+        const uint32_t *order = sort ? t.order : nullptr;
+        k_field_gather<<<nblocks(mc), kBlock, 0, st>>>(p, order, mc, t.sx, t.sy, t.sz);
+        with_bool(quad, [&](auto q) {
+            with_int<0, kLeapClose, kLeapPrime>(leap, [&](auto lv) {
+                k_tracer_tree<decltype(q)::value, decltype(lv)::value><<<nblocks(mc), kBlock, 0, st>>>(
+                    s->nodes, quad ? s->quad_pot : s->diag_pot, t.wtab, s->info, t.sx, t.sy, t.sz, order, mc, (float)eps2,
+                    s->softening, t.pmax, quad ? s->quad_work : nullptr, p, v, a, dt, s->damping);
+            });
+        });
+        NBMI_HIP_CHECK(hipGetLastError());
+    }
+    return 0;
+}
+
+// [leapfrog] the tracers' opening half-kick and drift.  Barnes-Hut: after the substep's build, whose error words it reads.
+int enqueue_tracer_kick_drift(nbmi_sim *s, double dt) {
+    auto &t = s->tr;
+    const bool direct = tracers_direct(s);
+    k_tracer_kick_drift<<<nblocks(t.m), kBlock, 0, s->stream>>>(direct ? nullptr : s->info, t.m, t.p, t.v, t.a, dt,
+                                                                 direct ? nullptr : t.pmax);
+    NBMI_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// [leapfrog] The tracers' acceleration rows exist and hold a = F(p) for the current bodies and tracers.  Barnes-Hut: the
+// priming walk needs a tree of the current positions with the float64 rows, and the step has none at this point (the
+// bodies may not need priming): a build of its own inside a SideBuild, as a query's, so the bodies' next step finds the
+// handle as it would without tracers.
+int tracer_leap_prepare(nbmi_sim *s) {
+    auto &t = s->tr;
+    if (!t.a) {
+        if (dev_alloc(s, &t.a, (size_t)3 * t.m)) return NBMI_ERR_HIP;
+        NBMI_HIP_CHECK(hipMemsetAsync(t.a, 0, (size_t)3 * t.m * sizeof(double), s->stream));
+        t.acc_valid = false;
+    }
+    if (t.acc_valid) return 0;
+    int rc;
+    if (tracers_direct(s)) {
+        rc = enqueue_tracers(s, kLeapPrime, 0.0);
+    } else {
+        SideBuild side(s);
+        if (side.rc) return side.rc;
+        BuildRequest build;
+        build.aux = false;
+        build.diag_rows = s->multipole == NBMI_MULTIPOLE_QUADRUPOLE ? nullptr : s->diag_pot;
+        rc = enqueue_tree(s, build);
+        if (rc == 0) rc = enqueue_tracers(s, kLeapPrime, 0.0);
+        rc = side.finish(rc, false);
+    }
+    if (rc == 0) t.acc_valid = true;  // (only once everything is enqueued, as the bodies')
+    return rc;
+}
 
 // One group of the queries' scratch (nbmi_sim::q), once: `alloc` makes its dev_allocs and returns nonzero if one failed.
 template <class Group, class Alloc>
@@ -5580,7 +5828,20 @@ int nbmi_step(nbmi_sim *s, double dt, int substeps) {
         nbmi::set_error("nbmi_step: substeps < 0");
         return NBMI_ERR_ARG;
     }
-    if (s->n == 0) return 0;
+    if (s->n == 0) {  // nothing to step but tracers, and those on straight lines (a = 0)
+        const bool leap0 = s->integrator == NBMI_INTEGRATOR_LEAPFROG;
+        if (s->tr.m == 0 || substeps == 0) return 0;
+        if (leap0) {
+            if (int rc = tracer_leap_prepare(s)) return rc;
+        }
+        for (int k = 0; k < substeps; k++) {
+            if (leap0) {
+                if (int rc = enqueue_tracer_kick_drift(s, dt)) return rc;
+            }
+            if (int rc = enqueue_tracers(s, leap0 ? kLeapClose : 0, dt)) return rc;
+        }
+        return 0;
+    }
     if (s->owner) {
         nbmi::set_error("nbmi_step: this handle is in owner mode, use the nbmi_owner_* calls");
         return NBMI_ERR_ARG;
@@ -5602,6 +5863,10 @@ int nbmi_step(nbmi_sim *s, double dt, int substeps) {
                 if (int rc = enqueue_kick_drift(s, dt)) return rc;
                 s->maxabs_fused = true;  // k_kick_drift has published max |x'|
                 int rc = enqueue_tree(s, step_build(s, dt, BuildTiming::kCaller));
+                if (rc == 0 && s->tr.m) {  // the tracers' whole substep on the tree of the drifted bodies
+                    rc = enqueue_tracer_kick_drift(s, dt);
+                    if (rc == 0) rc = enqueue_tracers(s, kLeapClose, dt);
+                }
                 if (rc == 0) rc = enqueue_walk(s, true, dt, nullptr, kLeapClose);
                 s->curbuf ^= 1;
                 if (rc) {
@@ -5610,6 +5875,9 @@ int nbmi_step(nbmi_sim *s, double dt, int substeps) {
                 }
             } else {
                 if (int rc = enqueue_tree(s, step_build(s, dt, BuildTiming::kAll))) return rc;
+                if (s->tr.m) {
+                    if (int rc = enqueue_tracers(s, 0, dt)) return rc;
+                }
                 if (int rc = enqueue_walk(s, true, dt, nullptr)) return rc;
             }
             if (s->timers) {
@@ -5633,10 +5901,18 @@ int nbmi_step(nbmi_sim *s, double dt, int substeps) {
             if (s->timers) NBMI_HIP_CHECK(hipEventRecord(s->ev[0], s->stream));
             if (leap) {
                 if (int rc = enqueue_kick_drift(s, dt)) return rc;
-                const int rc = launch_direct<true>(s, dt, s->acc, kLeapClose);
+                int rc = 0;
+                if (s->tr.m) {  // (the current buffer holds the drifted bodies)
+                    rc = enqueue_tracer_kick_drift(s, dt);
+                    if (rc == 0) rc = enqueue_tracers(s, kLeapClose, dt);
+                }
+                if (rc == 0) rc = launch_direct<true>(s, dt, s->acc, kLeapClose);
                 s->curbuf ^= 1;
                 if (rc) return rc;
             } else {
+                if (s->tr.m) {
+                    if (int rc = enqueue_tracers(s, 0, dt)) return rc;
+                }
                 if (int rc = launch_direct<true>(s, dt, nullptr)) return rc;
             }
             if (s->timers) {
@@ -5747,7 +6023,7 @@ int nbmi_set_integrator(nbmi_sim *s, int integrator) {
                             "that the exchange rows do not carry)");
             return NBMI_ERR_ARG;
         }
-        if (s->integrator != NBMI_INTEGRATOR_LEAPFROG) s->acc_valid = false;  // the next step primes a = F(x)
+        if (s->integrator != NBMI_INTEGRATOR_LEAPFROG) s->acc_valid = s->tr.acc_valid = false;  // the next step primes a = F(x)
     }
     s->integrator = integrator;
     return 0;
@@ -5778,7 +6054,7 @@ int nbmi_set_multipole(nbmi_sim *s, int multipole) {
     }
     if (multipole != s->multipole) {  // (the positions are the same: maxabs_fused survives)
         s->tree_valid = false;  // the records the queries describe belong to the other mode's build
-        s->acc_valid = false;   // leapfrog: the stored a = F(x) is the other mode's force
+        s->acc_valid = s->tr.acc_valid = false;  // leapfrog: the stored a = F(x) is the other mode's force
     }
     s->multipole = multipole;
     return 0;
@@ -6350,6 +6626,141 @@ int nbmi_field_at(nbmi_sim *s, int64_t m, const double *points_xyz, double *acc_
     return side.finish(rc, false);
 }
 
+namespace {
+// Gives back every array of the tracers.  The steps enqueue work on them without waiting: the device is waited for first.
+int tracers_release(nbmi_sim *s) {
+    auto &t = s->tr;
+    NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
+    dev_free(s, &t.p); dev_free(s, &t.v); dev_free(s, &t.a); dev_free(s, &t.pmax);
+    dev_free(s, &t.sx); dev_free(s, &t.sy); dev_free(s, &t.sz); dev_free(s, &t.key); dev_free(s, &t.key_s);
+    dev_free(s, &t.idx); dev_free(s, &t.order); dev_free(s, &t.sort_tmp); dev_free(s, &t.wtab);
+    t.m = t.rows = 0;
+    t.sort_bytes = 0;
+    t.acc_valid = false;
+    return 0;
+}
+
+// the first row of an (m, 3) array with a value that is not finite or above `limit` in magnitude; -1: none
+int64_t first_bad_row(const double *a, int64_t m, double limit, double *pmax) {
+    for (int64_t i = 0; i < 3 * m; i++) {
+        const double v = fabs(a[i]);
+        if (!(v <= limit)) return i / 3;  // (a NaN fails the comparison too)
+        if (pmax && v > *pmax) *pmax = v;
+    }
+    return -1;
+}
+}  // namespace
+
+int nbmi_set_tracers(nbmi_sim *s, int64_t m, const double *positions_xyz, const double *velocities_xyz) {
+    if (int rc = check_handle(s)) return rc;
+    if (int rc = diag_refuse(s, "nbmi_set_tracers")) return rc;
+    if (m < 0 || m > kTracerMax) {
+        nbmi::set_error(m < 0 ? "nbmi_set_tracers: m = %lld is negative" : "nbmi_set_tracers: m = %lld is above the largest accepted, %lld",
+                        (long long)m, (long long)kTracerMax);
+        return NBMI_ERR_ARG;
+    }
+    double pmax = 0.0;
+    if (m > 0) {
+        if (int rc = require_out(positions_xyz, "nbmi_set_tracers: null positions_xyz")) return rc;
+        const int64_t bp = first_bad_row(positions_xyz, m, 1e18, &pmax);
+        if (bp >= 0) {
+            nbmi::set_error("nbmi_set_tracers: positions_xyz row %lld holds (%g, %g, %g): coordinates must be finite and at most 1e18 "
+                            "in magnitude", (long long)bp, positions_xyz[3 * bp], positions_xyz[3 * bp + 1], positions_xyz[3 * bp + 2]);
+            return NBMI_ERR_ARG;
+        }
+        const int64_t bv = velocities_xyz ? first_bad_row(velocities_xyz, m, 1.7976931348623157e308, nullptr) : -1;
+        if (bv >= 0) {
+            nbmi::set_error("nbmi_set_tracers: velocities_xyz row %lld holds (%g, %g, %g): velocities must be finite", (long long)bv,
+                            velocities_xyz[3 * bv], velocities_xyz[3 * bv + 1], velocities_xyz[3 * bv + 2]);
+            return NBMI_ERR_ARG;
+        }
+    }
+    if (int rc = tracers_release(s)) return rc;
+    if (m == 0) return 0;
+    auto &t = s->tr;
+    hipStream_t st = s->stream;
+    const size_t bytes = (size_t)m * 3 * sizeof(double);
+    const bool tree = !tracers_direct(s);
+    const size_t r = (size_t)(m < kFieldChunk ? m : kFieldChunk);
+    bool bad = dev_alloc(s, &t.p, 3 * (size_t)m) || dev_alloc(s, &t.v, 3 * (size_t)m) || dev_alloc(s, &t.pmax, 1);
+    if (!bad && tree) {
+        t.sort_bytes = nbmi::radix_temp_bytes_u64(r, kFieldSortBits);
+        bad = dev_alloc(s, &t.sx, r) || dev_alloc(s, &t.sy, r) || dev_alloc(s, &t.sz, r) || dev_alloc(s, &t.key, r) ||
+              dev_alloc(s, &t.key_s, r) || dev_alloc(s, &t.idx, r) || dev_alloc(s, &t.order, r) ||
+              dev_alloc(s, &t.sort_tmp, t.sort_bytes + 256) || dev_alloc(s, &t.wtab, 1) ||
+              (!s->diag_pot && dev_alloc(s, &s->diag_pot, s->node_capacity + 2));
+    }
+    if (bad) {
+        tracers_release(s);
+        return NBMI_ERR_HIP;
+    }
+    WalkTable wt = walk_table(s);  // buffer 0 = the probes: see k_field_tree
+    wt.buf[0].x = t.sx; wt.buf[0].y = t.sy; wt.buf[0].z = t.sz;
+    int rc = 0;
+    auto ok = [&](hipError_t e) { if (e != hipSuccess && rc == 0) { nbmi::set_error("nbmi_set_tracers: %s", hipGetErrorString(e)); rc = NBMI_ERR_HIP; } };
+    ok(hipMemcpyAsync(t.p, positions_xyz, bytes, hipMemcpyHostToDevice, st));
+    if (velocities_xyz) ok(hipMemcpyAsync(t.v, velocities_xyz, bytes, hipMemcpyHostToDevice, st));
+    else ok(hipMemsetAsync(t.v, 0, bytes, st));
+    ok(hipMemcpyAsync(t.pmax, &pmax, sizeof(double), hipMemcpyHostToDevice, st));  // (the bit pattern of the non-negative double)
+    if (tree) {
+        ok(hipMemcpyAsync(t.wtab, &wt, sizeof(wt), hipMemcpyHostToDevice, st));
+        ok(nbmi::radix_init_temp(t.sort_tmp, st));
+    }
+    ok(hipStreamSynchronize(st));  // the sources are the caller's arrays and stack objects
+    if (rc) {
+        tracers_release(s);
+        return rc;
+    }
+    t.m = m;
+    t.rows = (int64_t)r;
+    return 0;
+}
+
+int64_t nbmi_tracer_count(nbmi_sim *s) { return s ? s->tr.m : -1; }
+
+int nbmi_get_tracers_f64(nbmi_sim *s, double *positions_xyz, double *velocities_xyz) {
+    if (int rc = check_handle(s)) return rc;
+    auto &t = s->tr;
+    if (t.m == 0) return 0;
+    hipStream_t st = s->stream;
+    const size_t bytes = (size_t)t.m * 3 * sizeof(double);
+    if (positions_xyz) NBMI_HIP_CHECK(hipMemcpyAsync(positions_xyz, t.p, bytes, hipMemcpyDeviceToHost, st));
+    if (velocities_xyz) NBMI_HIP_CHECK(hipMemcpyAsync(velocities_xyz, t.v, bytes, hipMemcpyDeviceToHost, st));
+    unsigned sort_err = 0u;
+    if (t.sort_tmp) NBMI_HIP_CHECK(nbmi::radix_error_word(t.sort_tmp, &sort_err, st));
+    NBMI_HIP_CHECK(hipStreamSynchronize(st));
+    if (sort_err) {
+        NBMI_HIP_CHECK(nbmi::radix_init_temp(t.sort_tmp, st));
+        nbmi::set_error("nbmi_get_tracers_f64: the sort of the tracers failed; the steps since the last synchronisation are invalid");
+        return NBMI_ERR_HIP;
+    }
+    return check_device_error(s);
+}
+
+int nbmi_get_tracer_positions_f32(nbmi_sim *s, float *positions_xyz) {
+    if (int rc = check_handle(s)) return rc;
+    const int64_t m = s->tr.m;
+    if (m == 0) return 0;
+    if (int rc = require_out(positions_xyz)) return rc;
+    // errors of the steps first (and the wait for them), then the rows chunk by chunk through a bounded host buffer
+    if (int rc = nbmi_get_tracers_f64(s, nullptr, nullptr)) return rc;
+    const int64_t rows = m < kFieldChunk ? m : kFieldChunk;
+    std::vector<double> p;
+    try {
+        p.resize((size_t)rows * 3);
+    } catch (const std::exception &) {  // (no exception crosses the C ABI)
+        nbmi::set_error("nbmi_get_tracer_positions_f32: no host memory for a buffer of %lld rows", (long long)rows);
+        return NBMI_ERR_HIP;
+    }
+    for (int64_t b = 0; b < m; b += rows) {
+        const int64_t mc = m - b < rows ? m - b : rows;
+        NBMI_HIP_CHECK(hipMemcpyAsync(p.data(), s->tr.p + 3 * b, (size_t)mc * 3 * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
+        for (int64_t i = 0; i < 3 * mc; i++) positions_xyz[3 * b + i] = (float)p[(size_t)i];
+    }
+    return 0;
+}
+
 int nbmi_set_color_mode(nbmi_sim *s, int mode, int k, double log10_lo, double log10_hi) {
     if (int rc = check_handle(s)) return rc;
     if (mode != NBMI_COLOR_SPEED && mode != NBMI_COLOR_DENSITY) {
@@ -6535,6 +6946,10 @@ int nbmi_set_shard(nbmi_sim *s, int64_t begin, int64_t end) {
     }
     if (s->integrator == NBMI_INTEGRATOR_LEAPFROG && (begin != 0 || end != s->n)) {
         nbmi::set_error("nbmi_set_shard: leapfrog handles cannot be sharded (the exchange rows carry no acceleration columns)");
+        return NBMI_ERR_ARG;
+    }
+    if (s->tr.m && (begin != 0 || end != s->n)) {
+        nbmi::set_error("nbmi_set_shard: handles with tracers cannot be sharded (nbmi_set_tracers: sharded handles are not supported)");
         return NBMI_ERR_ARG;
     }
     s->shard_begin = begin;

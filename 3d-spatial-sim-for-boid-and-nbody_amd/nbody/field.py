@@ -1,6 +1,6 @@
 """Host side of the field evaluation (include/nbmi.h nbmi_field_at): what is derived from the
-field at chosen points.  Pure NumPy over any object with ``field_at(points, potential=True)`` -> (acc (m, 3), phi (m,));
-no device."""
+field at chosen points.  Pure NumPy over any object with ``field_at(points, potential=True)`` -> (acc (m, 3), phi (m,))
+(and, for the tracers of section 4.19, ``get_tracers()`` -> (positions, velocities)); no device."""
 import numpy as np
 
 
@@ -79,6 +79,29 @@ def potential_slice(sim, center, half_extent, resolution, axes=(0, 1)):
     pts[:, :, a1] += u[:, None]
     _, phi = sim.field_at(pts.reshape(-1, 3), potential=True)
     return np.asarray(phi, dtype=np.float64).reshape(res, res)
+
+
+def circular_tracers(sim, radii, center, per_ring=16, normal=(0, 0, 1)):
+    """(positions, velocities), (len(radii) * per_ring, 3) float64 each: seeds for ``sim.set_tracers`` on ring_points'
+    rings (row r * per_ring + k is radius r, azimuth k), every one moving at rotation_curve's ``v_circ`` of its ring along
+    the ring, counter-clockwise about ``normal``.  The bodies' bulk motion is not added."""
+    r = _radii(radii)
+    d = _ring_dirs(per_ring, normal)
+    v_circ = rotation_curve(sim, r, center, per_ring, normal)["v_circ"]
+    tangent = np.cross(_unit(normal, "normal"), d)  # (per_ring, 3) unit vectors along the ring
+    vel = (v_circ[:, None, None] * tangent[None, :, :]).reshape(-1, 3)
+    return ring_points(center, r, per_ring, normal), vel
+
+
+def tracer_energies(sim):
+    """(m,) float64: the specific energy 0.5 |v|^2 + phi of every tracer of ``sim`` (``get_tracers``) in the bodies'
+    current potential (``field_at``).  In a static potential it is conserved along a tracer's orbit."""
+    p, v = sim.get_tracers()
+    p, v = np.asarray(p, dtype=np.float64), np.asarray(v, dtype=np.float64)
+    if len(p) == 0:
+        return np.zeros(0, dtype=np.float64)
+    _, phi = sim.field_at(p, potential=True)
+    return 0.5 * (v * v).sum(axis=1) + np.asarray(phi, dtype=np.float64)
 
 
 def escape_speed(phi):

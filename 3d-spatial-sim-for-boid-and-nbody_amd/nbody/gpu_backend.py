@@ -320,6 +320,41 @@ class _HIPSimulation:
             return acc, phi, cnt
         return (acc, phi) if potential else acc
 
+    # ---- massless tracers carried by the integrator (include/nbmi.h nbmi_set_tracers) ----
+    def set_tracers(self, positions, velocities=None):
+        """Replace the handle's tracers by the (m, 3) ``positions`` with ``velocities`` (None: at rest): test particles
+        that every later step moves in the bodies' field - nbmi_field_at's acceleration, the handle's integrator, all
+        float64 - and that pull on nothing.  m == 0 removes them.  ValueError for a wrong shape (before the library is
+        called), for a value that is not finite or a coordinate beyond 1e18, and for owner-mode and sharded handles."""
+        what = "set_tracers"
+        if self._field_refusal:
+            raise ValueError(f"{what}: {self._field_refusal}")
+        p = np.ascontiguousarray(positions, dtype=np.float64)
+        if p.ndim != 2 or p.shape[1] != 3:
+            raise ValueError(f"{what}: expected positions of shape (m, 3), got {p.shape}")
+        v = None
+        if velocities is not None:
+            v = np.ascontiguousarray(velocities, dtype=np.float64)
+            if v.shape != p.shape:
+                raise ValueError(f"{what}: expected velocities of shape {p.shape}, got {v.shape}")
+        _nat.check_arg(self._lib.nbmi_set_tracers(self._h, len(p), _nat.ptr(p), _nat.ptr(v)), what, "nbmi_set_tracers")
+
+    @property
+    def tracer_count(self) -> int:
+        return int(self._lib.nbmi_tracer_count(self._h))
+
+    def get_tracers(self):
+        """(positions, velocities), (m, 3) float64 each, rows in the order of set_tracers."""
+        m = self.tracer_count
+        p, v = np.empty((m, 3), dtype=np.float64), np.empty((m, 3), dtype=np.float64)
+        _nat.check(self._lib.nbmi_get_tracers_f64(self._h, _nat.ptr(p), _nat.ptr(v)), "nbmi_get_tracers_f64")
+        return p, v
+
+    def tracer_positions_f32(self) -> np.ndarray:
+        out = np.empty((self.tracer_count, 3), dtype=np.float32)
+        _nat.check(self._lib.nbmi_get_tracer_positions_f32(self._h, _nat.ptr(out)), "nbmi_get_tracer_positions_f32")
+        return out
+
     # ---- k-nearest neighbours, densities, density colours (include/nbmi.h nbmi_knn; DESIGN.md section 4.14) ----
     _query_refusal = None # classes whose handles the library refuses say so here, and refuse before calling it
 
@@ -550,7 +585,7 @@ class _HIPSimulation:
     # multi-GPU row exchange (device pointers; see nbody/sharded.py)
     def set_shard(self, begin, end):
         rc = self._lib.nbmi_set_shard(self._h, int(begin), int(end))
-        if rc == -1 and (self.integrator == "leapfrog" or self.multipole == "quadrupole"):
+        if rc == -1 and (self.integrator == "leapfrog" or self.multipole == "quadrupole" or self.tracer_count):
             raise ValueError(f"set_shard: {_nat.last_error()}")
         _nat.check(rc, "nbmi_set_shard")
 

@@ -7,7 +7,8 @@ On-disk contract kept so the reference's playback can read the output (SURVEY 8b
   frame_%04d.zstd  = u8 format (1 absolute | 2 delta) + u32 len + zstd(positions) +
                      u32 len + zstd(colors); format 2 payload = int16((cur-prev)*1000)   (:231-326)
   state_%04d.npz   = positions, velocities every 50 frames, previous one deleted   (:867-876)
-                     (+ `masses`, a superset key: the reference loses masses on resume [quirk])
+                     (+ `masses`, a superset key: the reference loses masses on resume [quirk];
+                     + `tracer_positions`, `tracer_velocities` in a --tracers session, with tracers_%06d.npy beside the frames)
 The interactive menus, progress bars and the background compressor thread are UX and are not
 reproduced; ``compress_recording`` converts finished .npz frames to .zstd with the same delta
 chaining, and ``record(config with "zstd": True)`` writes .zstd frames directly: the int16 delta
@@ -605,6 +606,46 @@ def open_lines(gpu_sim, config: dict, rec_dir: Path, start_frame: int, masses):
     return due, write
 
 
+# ---- massless tracers (extra config key "tracers") ------------------------------------------
+def tracers_config(config: dict):
+    """The "tracers" key of a config, {"file": the .npy of the seeds, "every": K}, as (file, every); None without the
+    key.  every == 0: the tracers are carried (and checkpointed) but no tracer file is written."""
+    t = config.get("tracers")
+    if not t:
+        return None
+    every = int(t.get("every") or 0)
+    if every < 0 or not t.get("file"):
+        raise ValueError(f"--tracers: need a file and a period K >= 0, not {t}")
+    return str(t["file"]), every
+
+
+def load_tracer_seeds(path):
+    """(positions, velocities) float64 from an .npy array (m, 3) or (m, 6), rows x y z [vx vy vz]; velocities None for
+    (m, 3): the tracers start at rest."""
+    a = np.load(path, allow_pickle=False)
+    if a.ndim != 2 or a.shape[1] not in (3, 6):
+        raise ValueError(f"--tracers: {path} holds an array of shape {a.shape}, not (m, 3) or (m, 6)")
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    return np.ascontiguousarray(a[:, :3]), (np.ascontiguousarray(a[:, 3:]) if a.shape[1] == 6 else None)
+
+
+def tracer_file(rec_dir, frame: int) -> Path:
+    return Path(rec_dir) / f"tracers_{frame:06d}.npy"
+
+
+def write_tracer_file(gpu_sim, rec_dir, frame: int):
+    """tracers_%06d.npy: the tracers' positions after `frame`, (m, 3) float32 in the order of the seed file."""
+    p = np.ascontiguousarray(gpu_sim.tracer_positions_f32(), dtype=np.float32)
+    _atomically(tracer_file(rec_dir, frame), lambda f: np.save(f, p))
+
+
+def last_tracer_file(rec_dir, upto: int):
+    """The newest tracer file of a frame below `upto` (files beyond the completed frames are a cut-short run's), or None."""
+    frames = sorted(int(p.stem.split("_")[1]) for p in Path(rec_dir).glob("tracers_[0-9][0-9][0-9][0-9][0-9][0-9].npy"))
+    frames = [f for f in frames if f < upto]
+    return tracer_file(rec_dir, frames[-1]) if frames else None
+
+
 # ---- initial conditions + the recording loops -----------------------------------------------------------------------
 def _generate_initial_conditions(config: dict):
     from tools.presets import generate_distribution
@@ -723,6 +764,7 @@ def record(config: dict, resume: bool = False, root: Path = None, quiet: bool = 
     rec_dir = get_recording_dir(config["session_name"], root)
     start_frame = 0
     positions = velocities = masses = None
+    tracer_state = None  # (positions, velocities) of the tracers in the checkpoint a resume starts from
     if resume:
         completed = get_completed_frames(rec_dir)
         if completed > 0:
@@ -732,6 +774,8 @@ def record(config: dict, resume: bool = False, root: Path = None, quiet: bool = 
                     positions = st["positions"].astype(np.float64)
                     velocities = st["velocities"].astype(np.float64)
                     masses = st["masses"].astype(np.float64) if "masses" in st.files else None
+                    if "tracer_positions" in st.files:
+                        tracer_state = (st["tracer_positions"].astype(np.float64), st["tracer_velocities"].astype(np.float64))
                 start_frame = state_frame + 1
                 say(f"[Record] Resuming from frame {start_frame}")
     device_ic = bool(config.get("device_ic")) and positions is None
@@ -790,6 +834,22 @@ def record(config: dict, resume: bool = False, root: Path = None, quiet: bool = 
             gpu_sim.frame_set_previous(*load_frame(rec_dir, start_frame - 1))
         t0 = time.time()
         lines_due, write_lines = open_lines(gpu_sim, config, rec_dir, start_frame, masses)
+        # extra config key "tracers": massless tracers carried by the steps, from the checkpoint on a
+        # resume, from the seed file otherwise; every K-th frame their positions in a file of their own, which both
+        # loops write where they write the lines
+        tracers = tracers_config(config)
+        if tracers is not None:
+            gpu_sim.set_tracers(*(tracer_state if tracer_state is not None else load_tracer_seeds(tracers[0])))
+            say(f"[Record] {gpu_sim.tracer_count:,} tracers" + (f", a file every {tracers[1]} frames" if tracers[1] else ""))
+            side_due, side_lines = lines_due, write_lines
+
+            def lines_due(frame):
+                return side_due(frame) or line_due(frame, tracers[1])
+
+            def write_lines(frame):
+                side_lines(frame)
+                if line_due(frame, tracers[1]):
+                    write_tracer_file(gpu_sim, rec_dir, frame)
 
         def write_frame(frame, absolute=False):
             gpu_sim.compute_colors(15.0)
@@ -800,8 +860,9 @@ def record(config: dict, resume: bool = False, root: Path = None, quiet: bool = 
 
         def write_state(frame, compressed=False):
             x, v = gpu_sim.get_positions_f64(), gpu_sim.get_velocities()
+            more = dict(zip(("tracer_positions", "tracer_velocities"), gpu_sim.get_tracers())) if tracers is not None else {}
             _atomically(rec_dir / f"state_{frame:04d}.npz", lambda f: (np.savez_compressed if compressed else np.savez)(
-                f, positions=x, velocities=v, masses=masses))
+                f, positions=x, velocities=v, masses=masses, **more))
 
         pipeline = bool(config.get("pipeline"))  # extra config key (metadata.json, only when set): the loop of DESIGN 4.11
         frame = start_frame - 1
@@ -924,6 +985,17 @@ def show_status(session_name: str, root: Path = None) -> bool:
             last = rrows[-1]
             k = int(np.argmax(last["v_circ"]))
             print(f"    frame {last['frame']}: peak v_circ = {last['v_circ'][k]:.6g} at R = {last['radii'][k]:.6g}")
+    tc = meta.get("tracers")
+    if tc:
+        try:
+            count = f"{len(np.load(tc.get('file'), mmap_mode='r', allow_pickle=False)):,}"
+        except (OSError, ValueError, TypeError):
+            count = "?"
+        every = int(tc.get("every") or 0)
+        print(f"  Tracers: {count} from {tc.get('file')}, " + (f"a file every {every} frames" if every else "no files"))
+        last = last_tracer_file(rec_dir, completed)
+        if last is not None:
+            print(f"    last file: {last.name} ({len(np.load(last, mmap_mode='r')):,} rows)")
     if completed < total:
         print(f"\n  To resume: python -m tools.record --resume {session_name}")
     else:
@@ -962,7 +1034,7 @@ def build_parser():
                "--preset-id); --preset-id indexes this build's preset list (python -m tools.record --presets shows "
                "it); --dt sets dt_per_frame (the reference writes an unused 'dt' key); --presets, --seed, "
                "--device-ic, --diagnostics, --integrator, --multipole, --pipeline, --color, --density-k, --density-range, "
-               "--groups, --linking-length, --min-members, --pairs, --pair-edges, --rotation-curve, --curve-radii and --root are "
+               "--groups, --linking-length, --min-members, --pairs, --pair-edges, --rotation-curve, --curve-radii, --tracers, --tracers-every and --root are "
                "additions.")
     ap.add_argument("session", nargs="?", help="session name (for --resume, --status or --extend)")
     ap.add_argument("--resume", action="store_true", help="resume an interrupted recording (default: the most recent)")
@@ -1020,6 +1092,11 @@ def build_parser():
                          "(stored in metadata.json as rotation_curve)")
     ap.add_argument("--curve-radii", type=str, default=None, metavar="auto|r0,r1,...",
                     help="1 .. 256 increasing radii (default auto: 16 radii, spawn_radius k / 16 for k = 1 .. 16)")
+    ap.add_argument("--tracers", type=Path, default=None, metavar="FILE.npy",
+                    help="massless tracers carried by the integrator: an array (m, 3) or (m, 6), rows x y z [vx vy vz] "
+                         "(stored in metadata.json as tracers; state checkpoints carry them)")
+    ap.add_argument("--tracers-every", type=int, default=None, metavar="K",
+                    help="every K frames write the tracers' positions, (m, 3) float32, to tracers_%%06d.npy")
     ap.add_argument("--root", type=Path, default=None, help="directory holding recordings/ (default: the package's)")
     return ap
 
@@ -1118,6 +1195,14 @@ def build_config(args) -> dict:
                 raise ValueError(f"--curve-radii: need auto or comma-separated numbers, not {cr!r}") from None
         config["rotation_curve"] = {"every": int(ck), "radii": radii}
         rotation_config(config)  # (a bad K or bad radii raise here)
+    tf, tk = (getattr(args, a, None) for a in ("tracers", "tracers_every"))
+    if tf is None and tk is not None:
+        raise ValueError("--tracers-every needs --tracers FILE.npy")
+    if tf is not None:  # the default writes no key
+        if tk is not None and tk <= 0:
+            raise ValueError(f"--tracers-every: K must be positive, not {tk}")
+        config["tracers"] = {"file": str(Path(tf).resolve()), "every": 0 if tk is None else int(tk)}
+        tracers_config(config)
     return config
 
 

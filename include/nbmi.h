@@ -400,6 +400,56 @@ int nbmi_field_at(nbmi_sim *sim, int64_t m, const double *points_xyz /* (m,3) */
                   double *acc_xyz /* (m,3), may be NULL */, double *phi /* (m,), may be NULL */,
                   int32_t *terms /* (m,), may be NULL */);
 
+/* Massless tracer particles carried by the handle's integrator: m test particles that feel the
+ * bodies and pull on nothing.  They appear in no tree, no body getter, no diagnostic, no frame and no colour pass; the
+ * bodies' trajectories, nbmi_force_precision_share, the walk counters and every query are bit for bit what they are on
+ * a handle without tracers.  The kernels and the tests' NumPy replay (tests/tracer_ref.py) both follow this text.
+ *
+ * Field.  In every substep a tracer at p is accelerated by a = F(p), exactly nbmi_field_at's acc for the point p: the
+ * octree of the bodies' positions at which that substep evaluates its forces, the handle's theta, eps and multipole mode,
+ * float64 without FMA, sums in pre-order of the node array (direct handles: the exact sum in body order).
+ * Integration.  The handle's integrator (nbmi_set_integrator), float64 without FMA, per component, as written:
+ *   kick-drift:  a = F(p) on the tree of x_n;  v = (v + a * dt) * damping;  p = p + v * dt.
+ *   leapfrog, h = 0.5 * dt:  v = v + a * h;  p = p + v * dt;  a = F(p) on the tree of the drifted bodies;
+ *                v = (v + a * h) * damping.
+ * The leapfrog's stored a costs 24 bytes per tracer, allocated by the first leapfrog step with tracers.  It is dropped
+ * and primed again (a = F(p), inside the next step, state untouched) whenever the bodies' stored acceleration is - after
+ * nbmi_create, nbmi_set_state, a switch of integrator or multipole order, a reported NBMI_ERR_CAPACITY - and after
+ * nbmi_set_tracers.
+ * Retired tracers.  A tracer whose row holds a value that is not finite, or a position coordinate beyond 1e18 in
+ * magnitude, when a kernel of a substep reaches it is not walked by that kernel and its row stays as it is.  Kick-drift
+ * has one such kernel per substep, so the row of a retired tracer is the one its last whole substep left.  Leapfrog has
+ * two, the opening half-kick and drift and the closing walk: a tracer whose drift carries it beyond 1e18 retires in the
+ * middle of that substep - it keeps the drifted position and the half-kicked velocity, gets no closing half-kick and no
+ * new stored a - and stays so from then on.
+ * On a leapfrog handle the tracers' opening half-kick and drift are enqueued after the substep's octree build (the
+ * bodies' come before it): the tracers are updated in place, and a build that does not fit must find them untouched.
+ * Errors.  A substep whose octree did not fit advances neither bodies nor tracers.
+ * N == 0: a = 0, the tracers move on straight lines.  nbmi_set_state leaves the tracers where they are.
+ *
+ * nbmi_set_tracers replaces all tracers by m new ones (it waits for the work enqueued so far); m == 0 removes them and
+ * frees their arrays.  velocities_xyz == NULL: zero velocities.  NBMI_ERR_ARG, message "nbmi_set_tracers: ...": m < 0,
+ * m above 67 108 864 (2^26, the largest m accepted), null positions_xyz with m > 0, a position coordinate that is not
+ * finite or exceeds 1e18 in magnitude, a velocity that is not finite (the message names the first bad row), owner-mode
+ * handles and handles with a proper shard; nbmi_set_shard in turn refuses a proper shard while tracers exist.  A refused
+ * call leaves the tracers as they were.
+ * Memory: 48 bytes per tracer of state (positions and velocities, (m,3) float64 in the caller's order) and, on a
+ * Barnes-Hut handle, 48 bytes per tracer of one chunk - min(m, 1 048 576) rows - of scratch that belongs to the tracers
+ * (columns in walk order, sort keys and indices in and out), the sort's temp buffer for that many pairs and, shared with
+ * nbmi_get_potentials_f64, 32 bytes per node row.  A step walks the tracers chunk by chunk, each chunk of more than 64
+ * in the order of its octant keys in the step's root cube (NBMI_FIELD_SORT=0: in the caller's order) - speed only - and
+ * never waits for the host.  A handle without tracers enqueues and allocates what it did before.
+ *
+ * nbmi_tracer_count: m (-1 for a null handle).  nbmi_get_tracers_f64: rows in the caller's order, either pointer may be
+ * NULL; it waits for the steps enqueued and reports their errors as the body getters do.  nbmi_get_tracer_positions_f32
+ * rounds the float64 positions to float32 on the host.  With no tracers the getters touch nothing. */
+int nbmi_set_tracers(nbmi_sim *sim, int64_t m, const double *positions_xyz /* (m,3) */,
+                     const double *velocities_xyz /* (m,3), may be NULL */);
+int64_t nbmi_tracer_count(nbmi_sim *sim);
+int nbmi_get_tracers_f64(nbmi_sim *sim, double *positions_xyz /* (m,3), may be NULL */,
+                         double *velocities_xyz /* (m,3), may be NULL */);
+int nbmi_get_tracer_positions_f32(nbmi_sim *sim, float *positions_xyz /* (m,3) */);
+
 /* Multi-GPU (one process per GPU).  A handle created with nbmi_create holds ALL bodies; with a
  * shard set, step() integrates only the key-sorted ranks [begin,end) (direct method: the body
  * indices [begin,end), its state is never re-ordered) and leaves the others untouched until
