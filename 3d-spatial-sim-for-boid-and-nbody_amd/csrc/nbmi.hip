@@ -4601,6 +4601,199 @@ __global__ __launch_bounds__(kBlock) void k_tracer_kick_drift(const TreeInfo *in
     if (pmax) tracer_raise_pmax(pmax, moved, x, y, z);
 }
 
+// ---------------------------------------------------------------------------------------
+// K20: grid deposit (nbmi_deposit; include/nbmi.h).  A scatter of fixed-point integers: every
+// (body, cell) contribution is rounded to a multiple of the plane's quantum 2^e and added with 64-bit integer atomics,
+// so the sum of a cell is one unique integer whatever the order and however the kernel combines contributions first.
+// k_deposit_max finds max |q| per plane (exact in any order; the bit pattern of a non-negative double orders as an
+// integer, and a NaN lies above +inf), the host turns it into e, k_deposit scatters, k_deposit_out converts in place.
+// ---------------------------------------------------------------------------------------
+constexpr int kDepPlanes = 6;      // NUMBER, MASS, MOMENTUM x 3, KINETIC
+constexpr int kDepRows = 8;        // state rows per thread of k_deposit: a workgroup covers 2 048 consecutive rows
+constexpr int kDepSlots = 1024;    // aggregating form: cells the workgroup's LDS table can hold
+constexpr int kDepSlotBits = 10;
+constexpr int kDepProbes = 4;      // ... linear probes before a contribution goes to memory directly
+struct DepositArgs {
+    double lo[3], inv[3], dimd[3];
+    int dims[3];
+    int cic[3];               // the axis splits a body over two cells (scheme CIC and dims >= 2)
+    int planes;
+    int slot[kDepPlanes];     // plane -> quantity: 0 = 1, 1 = m, 2 .. 4 = m v, 5 = m |v|^2
+    int e[kDepPlanes];        // the plane's exponent
+    int live[kDepPlanes];     // max |q| != 0
+    long long cells;
+};
+
+// the six quantities of a body, as the header writes them (float64, no FMA), then the one a plane asks for
+struct DepQ { double q0, q1, q2, q3, q4, q5; };
+__device__ __forceinline__ DepQ dep_quantities(double m, double vx, double vy, double vz) {
+    DepQ q;
+    q.q0 = 1.0;
+    q.q1 = m;
+    q.q2 = __dmul_rn(m, vx);
+    q.q3 = __dmul_rn(m, vy);
+    q.q4 = __dmul_rn(m, vz);
+    q.q5 = __dmul_rn(m, __dadd_rn(__dadd_rn(__dmul_rn(vx, vx), __dmul_rn(vy, vy)), __dmul_rn(vz, vz)));
+    return q;
+}
+__device__ __forceinline__ double dep_select(const DepQ &q, int slot) {
+    return slot == 0 ? q.q0 : slot == 1 ? q.q1 : slot == 2 ? q.q2 : slot == 3 ? q.q3 : slot == 4 ? q.q4 : q.q5;
+}
+
+__global__ __launch_bounds__(kBlock) void k_deposit_max(Bodies cur, int64_t n, DepositArgs a,
+                                                        unsigned long long *__restrict__ out /* [kDepPlanes] */) {
+    __shared__ unsigned long long sh[kBlock];
+    unsigned long long mx[kDepPlanes];
+#pragma unroll
+    for (int p = 0; p < kDepPlanes; p++) mx[p] = 0ull;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+        const DepQ q = dep_quantities(cur.m[i], cur.vx[i], cur.vy[i], cur.vz[i]);
+#pragma unroll
+        for (int p = 0; p < kDepPlanes; p++) {
+            if (p < a.planes) {
+                const unsigned long long b = (unsigned long long)__double_as_longlong(fabs(dep_select(q, a.slot[p])));
+                mx[p] = b > mx[p] ? b : mx[p];
+            }
+        }
+    }
+#pragma unroll
+    for (int p = 0; p < kDepPlanes; p++) {
+        if (p >= a.planes) break;
+        sh[threadIdx.x] = mx[p];
+        __syncthreads();
+        for (int w = kBlock / 2; w > 0; w >>= 1) {
+            if ((int)threadIdx.x < w) sh[threadIdx.x] = sh[threadIdx.x] > sh[threadIdx.x + w] ? sh[threadIdx.x] : sh[threadIdx.x + w];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0 && sh[0] != 0ull) atomicMax(&out[p], sh[0]);
+        __syncthreads();
+    }
+}
+
+// A body's cells and weights on one axis.  The range test is made on the floored double; an index is converted only
+// when it passed.
+struct DepAxis {
+    int i0, i1;
+    double w0, w1;
+    bool ok0, ok1;
+};
+__device__ __forceinline__ DepAxis dep_axis(double x, double lo, double inv, double dimd, bool cic) {
+    DepAxis r;
+    const double u = __dmul_rn(__dsub_rn(x, lo), inv);
+    if (!cic) {
+        const double fl = floor(u);
+        r.ok0 = fl >= 0.0 && fl < dimd;
+        r.i0 = r.ok0 ? (int)fl : 0;
+        r.w0 = 1.0;
+        r.ok1 = false;
+        r.i1 = 0;
+        r.w1 = 0.0;
+    } else {
+        const double s = __dsub_rn(u, 0.5), fl = floor(s), f = __dsub_rn(s, fl), f1 = __dadd_rn(fl, 1.0);
+        r.ok0 = fl >= 0.0 && fl < dimd;
+        r.i0 = r.ok0 ? (int)fl : 0;
+        r.w0 = __dsub_rn(1.0, f);
+        r.ok1 = f1 >= 0.0 && f1 < dimd;
+        r.i1 = r.ok1 ? (int)f1 : 0;
+        r.w1 = f;
+    }
+    return r;
+}
+
+// One pass over the state rows.  AGG = false: one global atomic per (contribution, plane).  AGG = true: the workgroup
+// first adds into an LDS table keyed by cell (open addressing, kDepProbes probes; a contribution that finds no slot goes
+// to memory directly) and flushes one atomic per (distinct cell, plane) at the end.  Both give the same integers.
+// stats = {bodies with a contribution, contributions, bodies skipped as not finite}.  Dynamic LDS (AGG):
+// planes * kDepSlots sums, then kDepSlots keys.
+template <bool AGG>
+__global__ __launch_bounds__(kBlock) void k_deposit(Bodies cur, int64_t n, DepositArgs a, unsigned long long *__restrict__ K,
+                                                    unsigned long long *__restrict__ stats) {
+    extern __shared__ unsigned long long dep_lds[];
+    __shared__ unsigned int sh_stats[3];
+    unsigned long long *vals = dep_lds;
+    int *keys = (int *)(dep_lds + (size_t)a.planes * kDepSlots);
+    if (threadIdx.x < 3) sh_stats[threadIdx.x] = 0u;
+    if (AGG) {
+        for (int t = threadIdx.x; t < kDepSlots; t += kBlock) keys[t] = -1;
+        for (int t = threadIdx.x; t < a.planes * kDepSlots; t += kBlock) vals[t] = 0ull;
+    }
+    __syncthreads();
+    unsigned int hit = 0u, contributions = 0u, skipped = 0u;
+    const int64_t base = (int64_t)blockIdx.x * (kBlock * kDepRows);
+    for (int r = 0; r < kDepRows; r++) {
+        const int64_t i = base + (int64_t)r * kBlock + threadIdx.x;
+        if (i >= n) continue;
+        const double x = cur.x[i], y = cur.y[i], z = cur.z[i];
+        if (!(isfinite(x) && isfinite(y) && isfinite(z))) {
+            skipped++;
+            continue;
+        }
+        const DepAxis ax = dep_axis(x, a.lo[0], a.inv[0], a.dimd[0], a.cic[0] != 0);
+        const DepAxis ay = dep_axis(y, a.lo[1], a.inv[1], a.dimd[1], a.cic[1] != 0);
+        const DepAxis az = dep_axis(z, a.lo[2], a.inv[2], a.dimd[2], a.cic[2] != 0);
+        if (!((ax.ok0 || ax.ok1) && (ay.ok0 || ay.ok1) && (az.ok0 || az.ok1))) continue;
+        hit++;
+        const DepQ q = dep_quantities(cur.m[i], cur.vx[i], cur.vy[i], cur.vz[i]);
+        double qp[kDepPlanes];
+#pragma unroll
+        for (int p = 0; p < kDepPlanes; p++) qp[p] = p < a.planes ? dep_select(q, a.slot[p]) : 0.0;
+#pragma unroll
+        for (int c = 0; c < 8; c++) {
+            const bool ok = ((c & 1) ? ax.ok1 : ax.ok0) && ((c & 2) ? ay.ok1 : ay.ok0) && ((c & 4) ? az.ok1 : az.ok0);
+            if (!ok) continue;
+            contributions++;
+            const double w = __dmul_rn(__dmul_rn((c & 1) ? ax.w1 : ax.w0, (c & 2) ? ay.w1 : ay.w0), (c & 4) ? az.w1 : az.w0);
+            const int ix = (c & 1) ? ax.i1 : ax.i0, iy = (c & 2) ? ay.i1 : ay.i0, iz = (c & 4) ? az.i1 : az.i0;
+            const int cell = (iz * a.dims[1] + iy) * a.dims[0] + ix;  // < cells <= 2^28
+            int slot = -1;
+            if (AGG) {
+                int h = (int)(((unsigned)cell * 2654435761u) >> (32 - kDepSlotBits));
+                for (int t = 0; t < kDepProbes; t++) {
+                    const int old = atomicCAS(&keys[h], -1, cell);
+                    if (old == -1 || old == cell) {
+                        slot = h;
+                        break;
+                    }
+                    h = (h + 1) & (kDepSlots - 1);
+                }
+            }
+#pragma unroll
+            for (int p = 0; p < kDepPlanes; p++) {
+                if (p >= a.planes || !a.live[p]) continue;
+                const long long k = (long long)rint(ldexp(__dmul_rn(qp[p], w), -a.e[p]));
+                if (k == 0) continue;
+                if (AGG && slot >= 0) atomicAdd(&vals[p * kDepSlots + slot], (unsigned long long)k);
+                else atomicAdd(&K[(long long)p * a.cells + cell], (unsigned long long)k);
+            }
+        }
+    }
+    if (hit) atomicAdd(&sh_stats[0], hit);
+    if (contributions) atomicAdd(&sh_stats[1], contributions);
+    if (skipped) atomicAdd(&sh_stats[2], skipped);
+    __syncthreads();
+    if (threadIdx.x < 3 && sh_stats[threadIdx.x]) atomicAdd(&stats[threadIdx.x], (unsigned long long)sh_stats[threadIdx.x]);
+    if (AGG) {
+        for (int t = threadIdx.x; t < kDepSlots; t += kBlock) {
+            const int cell = keys[t];
+            if (cell < 0) continue;
+            for (int p = 0; p < a.planes; p++) {
+                const unsigned long long v = vals[p * kDepSlots + t];
+                if (v) atomicAdd(&K[(long long)p * a.cells + cell], v);
+            }
+        }
+    }
+}
+
+// K (int64, in place) -> out = ldexp((double) K, e) per plane
+__global__ __launch_bounds__(kBlock) void k_deposit_out(unsigned long long *__restrict__ K, DepositArgs a) {
+    const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= a.cells) return;
+    for (int p = 0; p < a.planes; p++) {
+        const long long j = (long long)p * a.cells + i;
+        K[j] = (unsigned long long)__double_as_longlong(ldexp((double)(long long)K[j], a.e[p]));
+    }
+}
+
 }  // namespace
 
 // =========================================================================================
@@ -4775,6 +4968,14 @@ struct nbmi_sim {
         } pairs;
     } q;
     bool pair_cells = true;  // cells inside one bin are counted whole (NBMI_PAIRS_CELLS=0: never; measurement)
+    // Scratch of nbmi_deposit (section 4.20): `words` 64-bit sums (planes x cells of the largest call so far, regrown by
+    // the call that needs more) and 9 words of results: max |q| per plane, then the three stats.  No step touches it.
+    struct {
+        int64_t words = 0;
+        unsigned long long *K = nullptr, *res = nullptr;
+    } dep;
+    bool deposit_agg = true;  // the workgroup combines contributions per cell in LDS first (NBMI_DEPOSIT_AGG=0: one global
+                              // atomic per contribution; same bits, 3.1 - 134 x the time: DESIGN.md section 4.20)
     // Scratch of nbmi_field_at (section 4.18): `rows` points of a chunk - 108 bytes each: the points as they came, their
     // columns in walk order, acc, phi, terms, sort keys and indices in and out - the sort's temp buffer for that many
     // pairs, and the walk table whose buffer 0 names the probe columns.  Grown by the call that needs more, never beyond
@@ -5636,6 +5837,7 @@ static void read_env_knobs(nbmi_sim *s) {
     if (const char *e = getenv("NBMI_KEYS_LEAN")) s->keys_lean = atoi(e) != 0;
     if (const char *e = getenv("NBMI_PAIRS_CELLS")) s->pair_cells = atoi(e) != 0;
     if (const char *e = getenv("NBMI_FIELD_SORT")) s->field_sort = atoi(e) != 0;
+    if (const char *e = getenv("NBMI_DEPOSIT_AGG")) s->deposit_agg = atoi(e) != 0;
     if (const char *e = getenv("NBMI_FORCE_PREC")) {
         const int v = atoi(e);
         if (v >= 0 && v <= 2) s->force_prec = v;
@@ -6488,6 +6690,128 @@ int nbmi_pair_counts(nbmi_sim *s, int nb, const double *edges, int64_t *counts, 
     if (cell_pairs) *cell_pairs = (int64_t)h[1];
     if (below) *below = (int64_t)h[2];
     for (int k = 0; counts && k < nb; k++) counts[k] = (int64_t)h[3 + k];
+    return 0;
+}
+
+int nbmi_deposit(nbmi_sim *s, const double *lo, const double *hi, const int32_t *dims, int scheme, int quantities,
+                 double *out, int64_t *stats3, int32_t *exponents) {
+    static const char *const kPlaneName[kDepPlanes] = {"NUMBER", "MASS", "MOMENTUM x", "MOMENTUM y", "MOMENTUM z", "KINETIC"};
+    constexpr int64_t kDepMaxWords = (int64_t)1 << 28;
+    if (int rc = check_handle(s)) return rc;
+    if (s->owner) {
+        nbmi::set_error("nbmi_deposit: owner-mode handles are not supported (the other ranks hold the rest of the bodies)");
+        return NBMI_ERR_ARG;
+    }
+    if (s->shard_begin != 0 || s->shard_end != s->n) {
+        nbmi::set_error("nbmi_deposit: sharded handles are not supported");
+        return NBMI_ERR_ARG;
+    }
+    if (!lo || !hi || !dims || !out) {
+        nbmi::set_error("nbmi_deposit: null %s", !lo ? "lo" : !hi ? "hi" : !dims ? "dims" : "out");
+        return NBMI_ERR_ARG;
+    }
+    if (scheme != NBMI_DEPOSIT_NGP && scheme != NBMI_DEPOSIT_CIC) {
+        nbmi::set_error("nbmi_deposit: scheme = %d is neither NBMI_DEPOSIT_NGP (0) nor NBMI_DEPOSIT_CIC (1)", scheme);
+        return NBMI_ERR_ARG;
+    }
+    if (quantities == 0 || (quantities & ~15) != 0) {
+        nbmi::set_error("nbmi_deposit: quantities = %d selects nothing or has unknown bits", quantities);
+        return NBMI_ERR_ARG;
+    }
+    DepositArgs a{};
+    a.cells = 1;
+    for (int k = 0; k < 3; k++) {
+        if (!isfinite(lo[k]) || !isfinite(hi[k]) || !(hi[k] > lo[k])) {
+            nbmi::set_error("nbmi_deposit: axis %d: the bounds [%g, %g] must be finite with hi > lo", k, lo[k], hi[k]);
+            return NBMI_ERR_ARG;
+        }
+        if (dims[k] < 1) {
+            nbmi::set_error("nbmi_deposit: dims[%d] = %d is < 1", k, (int)dims[k]);
+            return NBMI_ERR_ARG;
+        }
+        const double width = hi[k] - lo[k], inv = (double)dims[k] / width;
+        if (!isfinite(width) || !isfinite(inv)) {
+            nbmi::set_error("nbmi_deposit: axis %d: the width %g or dims / width = %g is not finite", k, width, inv);
+            return NBMI_ERR_ARG;
+        }
+        a.lo[k] = lo[k];
+        a.inv[k] = inv;
+        a.dims[k] = dims[k];
+        a.dimd[k] = (double)dims[k];
+        a.cic[k] = scheme == NBMI_DEPOSIT_CIC && dims[k] >= 2;
+        a.cells = a.cells <= kDepMaxWords ? a.cells * dims[k] : a.cells;  // (stays above the limit once it is)
+    }
+    if (quantities & NBMI_DEPOSIT_NUMBER) a.slot[a.planes++] = 0;
+    if (quantities & NBMI_DEPOSIT_MASS) a.slot[a.planes++] = 1;
+    if (quantities & NBMI_DEPOSIT_MOMENTUM)
+        for (int c = 0; c < 3; c++) a.slot[a.planes++] = 2 + c;
+    if (quantities & NBMI_DEPOSIT_KINETIC) a.slot[a.planes++] = 5;
+    if (a.cells > kDepMaxWords || a.planes * a.cells > kDepMaxWords) {
+        nbmi::set_error("nbmi_deposit: %d planes of %d x %d x %d cells are more than 2^28 values", a.planes, (int)dims[0],
+                        (int)dims[1], (int)dims[2]);
+        return NBMI_ERR_ARG;
+    }
+    const int64_t n = s->n, words = a.planes * a.cells;
+    hipStream_t st = s->stream;
+    NBMI_HIP_CHECK(hipStreamSynchronize(st));
+    if (int rc = check_device_error(s)) return rc;
+    unsigned long long h[kDepPlanes + 3] = {};
+    if (n > 0) {
+        if (!s->dep.res && dev_alloc(s, &s->dep.res, kDepPlanes + 3)) return NBMI_ERR_HIP;
+        if (words > s->dep.words) {  // (nothing enqueued uses the old array: every call waits for its copies)
+            dev_free(s, &s->dep.K);
+            s->dep.words = 0;
+            if (dev_alloc(s, &s->dep.K, (size_t)words)) return NBMI_ERR_HIP;
+            s->dep.words = words;
+        }
+        const Bodies cur = s->buf[s->curbuf];
+        float ms = 0.0f, ms2 = 0.0f;
+        NBMI_HIP_CHECK(hipMemsetAsync(s->dep.res, 0, sizeof(h), st));
+        if (s->timers) NBMI_HIP_CHECK(hipEventRecord(s->ev[0], st));
+        const int64_t want = nblocks(n);
+        k_deposit_max<<<(int)(want < 1024 ? want : 1024), kBlock, 0, st>>>(cur, n, a, s->dep.res);
+        NBMI_HIP_CHECK(hipGetLastError());
+        if (s->timers) NBMI_HIP_CHECK(hipEventRecord(s->ev[1], st));
+        NBMI_HIP_CHECK(hipMemcpyAsync(h, s->dep.res, kDepPlanes * sizeof(h[0]), hipMemcpyDeviceToHost, st));
+        NBMI_HIP_CHECK(hipStreamSynchronize(st));
+        const int L = 64 - __builtin_clzll((unsigned long long)n);  // the bit length of N
+        for (int p = 0; p < a.planes; p++) {
+            double mx;
+            memcpy(&mx, &h[p], sizeof(mx));
+            if (!isfinite(mx)) {
+                nbmi::set_error("nbmi_deposit: the largest |q| of plane %d (%s) is not finite", p, kPlaneName[a.slot[p]]);
+                return NBMI_ERR_ARG;
+            }
+            int E = 0;
+            if (mx != 0.0) (void)frexp(mx, &E);
+            a.live[p] = mx != 0.0;
+            a.e[p] = mx != 0.0 ? E + L - 62 : 0;
+        }
+        NBMI_HIP_CHECK(hipMemsetAsync(s->dep.K, 0, (size_t)words * sizeof(unsigned long long), st));
+        if (s->timers) NBMI_HIP_CHECK(hipEventRecord(s->ev[2], st));
+        const int blocks = (int)((n + kBlock * kDepRows - 1) / (kBlock * kDepRows));
+        if (s->deposit_agg) {
+            const size_t lds = (size_t)kDepSlots * (a.planes * sizeof(unsigned long long) + sizeof(int));
+            k_deposit<true><<<blocks, kBlock, lds, st>>>(cur, n, a, s->dep.K, s->dep.res + kDepPlanes);
+        } else {
+            k_deposit<false><<<blocks, kBlock, 0, st>>>(cur, n, a, s->dep.K, s->dep.res + kDepPlanes);
+        }
+        k_deposit_out<<<nblocks(a.cells), kBlock, 0, st>>>(s->dep.K, a);
+        NBMI_HIP_CHECK(hipGetLastError());
+        if (s->timers) NBMI_HIP_CHECK(hipEventRecord(s->ev[3], st));
+        NBMI_HIP_CHECK(hipMemcpyAsync(h + kDepPlanes, s->dep.res + kDepPlanes, 3 * sizeof(h[0]), hipMemcpyDeviceToHost, st));
+        NBMI_HIP_CHECK(hipMemcpyAsync(out, s->dep.K, (size_t)words * sizeof(double), hipMemcpyDeviceToHost, st));
+        NBMI_HIP_CHECK(hipStreamSynchronize(st));
+        if (s->timers) {  // the device time of the two passes, without the copies: "other"
+            NBMI_HIP_CHECK(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
+            NBMI_HIP_CHECK(hipEventElapsedTime(&ms2, s->ev[2], s->ev[3]));
+            s->ms[4] += (double)ms + (double)ms2;
+        }
+    } else {
+        for (int64_t i = 0; i < words; i++) out[i] = 0.0;
+    }
+    for (int p = 0; exponents && p < a.planes; p++) exponents[p] = a.e[p];
+    for (int k = 0; stats3 && k < 3; k++) stats3[k] = (int64_t)h[kDepPlanes + k];
     return 0;
 }
 

@@ -33,6 +33,8 @@ INTEGRATORS = {"kick_drift": 0, "leapfrog": 1}
 MULTIPOLES = {"monopole": 0, "quadrupole": 1}
 # colour modes of nbmi_set_color_mode (NBMI_COLOR_* of include/nbmi.h)
 COLOR_MODES = {"speed": 0, "density": 1}
+DEPOSIT_SCHEMES = {"ngp": 0, "cic": 1}  # NBMI_DEPOSIT_*
+DEPOSIT_QUANTITIES = {"number": 1, "mass": 2, "momentum": 4, "kinetic": 8}  # in the order of the planes
 KNN_MAX_K = 64
 
 
@@ -361,9 +363,56 @@ class _HIPSimulation:
     def _query_call(self, what, rc):
         _nat.check_arg(rc, what)  # ValueError: refused for this handle, or a bad argument
 
-    def _query_refuse(self, what):
-        if self._query_refusal:
-            raise ValueError(f"{what}: {self._query_refusal}")
+    def _query_refuse(self, what, tree=True):
+        """``tree=False``: a call that needs the whole state but no tree (direct handles pass; owner mode does not)."""
+        why = self._query_refusal if tree else self._field_refusal
+        if why:
+            raise ValueError(f"{what}: {why}")
+
+    # ---- fields on a regular grid (include/nbmi.h nbmi_deposit; DESIGN.md section 4.20; helpers in nbody/grid.py) ----
+    def deposit(self, lo, hi, dims, scheme="cic", quantities=("mass",), stats=False):
+        """Deposit the current float64 state on a grid of ``dims`` = (nx, ny, nz) cells covering [lo, hi) per axis
+        (a dims of 1 projects along that axis).  ``scheme``: "ngp" or "cic"; ``quantities``: any of "number", "mass",
+        "momentum", "kinetic" (q = 1, m, m v, m |v|^2).  Returns a dict with one float64 array of shape (nz, ny, nx) per
+        quantity - "momentum": (3, nz, ny, nx) -, "exponents" (int32, one per plane in the library's order: every value
+        of a plane is an integer multiple of 2 ** exponent) and, with ``stats``, "stats" = (bodies deposited,
+        contributions, bodies skipped as not finite).  The sums are exact integer sums of fixed-point contributions:
+        the result is independent of the order of the bodies and the same bits on every call.  Velocities are read as
+        stored (kick-drift: half a step from the positions).  Barnes-Hut and direct handles; ValueError for bad
+        arguments, a quantity whose maximum is not finite, and owner-mode and sharded handles.  The call does not change
+        what the next step computes."""
+        what = "deposit"
+        self._query_refuse(what, tree=False)
+        if isinstance(quantities, str):
+            quantities = (quantities,)
+        unknown = [q for q in quantities if q not in DEPOSIT_QUANTITIES]
+        if unknown or not quantities:
+            raise ValueError(f"{what}: quantities must be some of {list(DEPOSIT_QUANTITIES)}, not {list(quantities)}")
+        if scheme not in DEPOSIT_SCHEMES:
+            raise ValueError(f"{what}: scheme must be one of {list(DEPOSIT_SCHEMES)}, not {scheme!r}")
+        lo_, hi_ = (np.ascontiguousarray(a, dtype=np.float64).reshape(-1) for a in (lo, hi))
+        d = np.ascontiguousarray(dims, dtype=np.int64).reshape(-1)
+        if len(lo_) != 3 or len(hi_) != 3 or len(d) != 3:
+            raise ValueError(f"{what}: lo, hi and dims must have three entries each")
+        if (d < 1).any() or int(d.max()) > 1 << 28 or int(d[0]) * int(d[1]) * int(d[2]) > 1 << 28:
+            raise ValueError(f"{what}: dims {d.tolist()} must be >= 1 with at most 2^28 values in all planes")
+        names = [q for q in DEPOSIT_QUANTITIES if q in quantities]  # the library's plane order
+        bits = sum(DEPOSIT_QUANTITIES[q] for q in names)
+        planes = sum(3 if q == "momentum" else 1 for q in names)
+        d32 = d.astype(np.int32)
+        out = np.zeros((planes, int(d[2]), int(d[1]), int(d[0])), dtype=np.float64)
+        st = np.zeros(3, dtype=np.int64)
+        ex = np.zeros(planes, dtype=np.int32)
+        self._query_call(what, self._lib.nbmi_deposit(self._h, _nat.ptr(lo_), _nat.ptr(hi_), _nat.ptr(d32),
+                                                    DEPOSIT_SCHEMES[scheme], bits, _nat.ptr(out), _nat.ptr(st), _nat.ptr(ex)))
+        res, p = {}, 0
+        for q in names:
+            res[q] = out[p:p + 3] if q == "momentum" else out[p]
+            p += 3 if q == "momentum" else 1
+        res["exponents"] = ex
+        if stats:
+            res["stats"] = tuple(int(x) for x in st)
+        return res
 
     def knn(self, k: int, evals=False):
         """(r2_k, mass_k), (N,) float64 each in the caller's body order: the squared distance to the k-th nearest other

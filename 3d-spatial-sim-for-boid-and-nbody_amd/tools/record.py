@@ -9,6 +9,7 @@ On-disk contract kept so the reference's playback can read the output (SURVEY 8b
   state_%04d.npz   = positions, velocities every 50 frames, previous one deleted   (:867-876)
                      (+ `masses`, a superset key: the reference loses masses on resume [quirk];
                      + `tracer_positions`, `tracer_velocities` in a --tracers session, with tracers_%06d.npy beside the frames)
+  map_%06d.npy     = float32 (pixels, pixels) surface density every K frames in a --density-map session (a superset file)
 The interactive menus, progress bars and the background compressor thread are UX and are not
 reproduced; ``compress_recording`` converts finished .npz frames to .zstd with the same delta
 chaining, and ``record(config with "zstd": True)`` writes .zstd frames directly: the int16 delta
@@ -646,6 +647,61 @@ def last_tracer_file(rec_dir, upto: int):
     return tracer_file(rec_dir, frames[-1]) if frames else None
 
 
+# ---- surface-density maps (extra config key "density_map") ----------------------------------
+MAP_PIXELS = 512
+MAP_HALF_WIDTH_FACTOR = 1.5  # x the preset's spawn radius
+
+
+def density_map_config(config: dict):
+    """The "density_map" key of a config, {"every": K, "pixels": n, "half_width": w, "axis": "x" | "y" | "z"}, as
+    (every, pixels, half_width, axis); None without the key."""
+    d = config.get("density_map")
+    if not d:
+        return None
+    every, pixels, axis = int(d.get("every") or 0), int(d.get("pixels", MAP_PIXELS)), d.get("axis", "z")
+    hw = float(d.get("half_width", MAP_HALF_WIDTH_FACTOR * config["spawn_radius"]))
+    if every <= 0:
+        raise ValueError(f"--density-map: K must be positive, not {d.get('every')}")
+    if not 1 <= pixels <= 16384:
+        raise ValueError(f"--map-pixels: need 1 .. 16384, not {pixels}")
+    if not (np.isfinite(hw) and hw > 0.0):
+        raise ValueError(f"--map-half-width: need a finite width > 0, not {hw}")
+    if axis not in ("x", "y", "z"):
+        raise ValueError(f"--map-axis: need x, y or z, not {axis!r}")
+    return every, pixels, hw, axis
+
+
+def map_file(rec_dir, frame: int) -> Path:
+    return Path(rec_dir) / f"map_{frame:06d}.npy"
+
+
+def write_map_file(gpu_sim, rec_dir, frame: int, pixels: int, half_width: float, axis: str):
+    """map_%06d.npy: the surface density (mass per area, CIC) about the origin after `frame`, (pixels, pixels) float32."""
+    from nbody.grid import surface_density
+    m = np.ascontiguousarray(surface_density(gpu_sim, axis=axis, half_width=half_width, pixels=pixels), dtype=np.float32)
+    _atomically(map_file(rec_dir, frame), lambda f: np.save(f, m))
+
+
+def _with_maps(gpu_sim, rec_dir, dmap, lines_due, write_lines):
+    """(due, write) of both loops with the maps added: a map is due like a line, and written after the lines."""
+    every, pixels, half_width, axis = dmap
+
+    def due(frame):
+        return lines_due(frame) or line_due(frame, every)
+
+    def write(frame):
+        write_lines(frame)
+        if line_due(frame, every):
+            write_map_file(gpu_sim, rec_dir, frame, pixels, half_width, axis)
+    return due, write
+
+
+def map_frames(rec_dir, upto: int):
+    """The frames below `upto` that have a map file, ascending (files beyond the completed frames are a cut-short run's)."""
+    frames = sorted(int(p.stem.split("_")[1]) for p in Path(rec_dir).glob("map_[0-9][0-9][0-9][0-9][0-9][0-9].npy"))
+    return [f for f in frames if f < upto]
+
+
 # ---- initial conditions + the recording loops -----------------------------------------------------------------------
 def _generate_initial_conditions(config: dict):
     from tools.presets import generate_distribution
@@ -850,6 +906,11 @@ def record(config: dict, resume: bool = False, root: Path = None, quiet: bool = 
                 side_lines(frame)
                 if line_due(frame, tracers[1]):
                     write_tracer_file(gpu_sim, rec_dir, frame)
+        # extra config key "density_map": every K-th frame a surface-density map, written like the tracer files
+        dmap = density_map_config(config)
+        if dmap is not None:
+            say(f"[Record] a {dmap[1]} x {dmap[1]} surface-density map along {dmap[3]} every {dmap[0]} frames")
+            lines_due, write_lines = _with_maps(gpu_sim, rec_dir, dmap, lines_due, write_lines)
 
         def write_frame(frame, absolute=False):
             gpu_sim.compute_colors(15.0)
@@ -996,6 +1057,12 @@ def show_status(session_name: str, root: Path = None) -> bool:
         last = last_tracer_file(rec_dir, completed)
         if last is not None:
             print(f"    last file: {last.name} ({len(np.load(last, mmap_mode='r')):,} rows)")
+    dm = meta.get("density_map")
+    if dm:
+        print(f"  Density maps: every {dm.get('every')} frames, {dm.get('pixels')} x {dm.get('pixels')} pixels along "
+              f"{dm.get('axis')}, half width {dm.get('half_width'):.6g}")
+        frames = map_frames(rec_dir, completed)
+        print(f"    {len(frames)} maps" + (f", the last after frame {frames[-1]}" if frames else ""))
     if completed < total:
         print(f"\n  To resume: python -m tools.record --resume {session_name}")
     else:
@@ -1034,7 +1101,8 @@ def build_parser():
                "--preset-id); --preset-id indexes this build's preset list (python -m tools.record --presets shows "
                "it); --dt sets dt_per_frame (the reference writes an unused 'dt' key); --presets, --seed, "
                "--device-ic, --diagnostics, --integrator, --multipole, --pipeline, --color, --density-k, --density-range, "
-               "--groups, --linking-length, --min-members, --pairs, --pair-edges, --rotation-curve, --curve-radii, --tracers, --tracers-every and --root are "
+               "--groups, --linking-length, --min-members, --pairs, --pair-edges, --rotation-curve, --curve-radii, --tracers, --tracers-every, "
+               "--density-map, --map-pixels, --map-half-width, --map-axis and --root are "
                "additions.")
     ap.add_argument("session", nargs="?", help="session name (for --resume, --status or --extend)")
     ap.add_argument("--resume", action="store_true", help="resume an interrupted recording (default: the most recent)")
@@ -1097,6 +1165,13 @@ def build_parser():
                          "(stored in metadata.json as tracers; state checkpoints carry them)")
     ap.add_argument("--tracers-every", type=int, default=None, metavar="K",
                     help="every K frames write the tracers' positions, (m, 3) float32, to tracers_%%06d.npy")
+    ap.add_argument("--density-map", type=int, default=None, metavar="K",
+                    help="every K frames write the surface density about the origin (mass per area, cloud-in-cell), "
+                         "(pixels, pixels) float32, to map_%%06d.npy (stored in metadata.json as density_map)")
+    ap.add_argument("--map-pixels", type=int, default=None, metavar="N", help=f"pixels per side (default {MAP_PIXELS})")
+    ap.add_argument("--map-half-width", type=float, default=None, metavar="W",
+                    help=f"half the side of the map (default {MAP_HALF_WIDTH_FACTOR} x the preset's spawn radius)")
+    ap.add_argument("--map-axis", choices=("x", "y", "z"), default=None, help="the axis projected along (default z)")
     ap.add_argument("--root", type=Path, default=None, help="directory holding recordings/ (default: the package's)")
     return ap
 
@@ -1203,6 +1278,14 @@ def build_config(args) -> dict:
             raise ValueError(f"--tracers-every: K must be positive, not {tk}")
         config["tracers"] = {"file": str(Path(tf).resolve()), "every": 0 if tk is None else int(tk)}
         tracers_config(config)
+    mk, mp, mw, ma = (getattr(args, a, None) for a in ("density_map", "map_pixels", "map_half_width", "map_axis"))
+    if mk is None and (mp is not None or mw is not None or ma is not None):
+        raise ValueError("--map-pixels, --map-half-width and --map-axis need --density-map K")
+    if mk is not None:  # the default writes no key
+        config["density_map"] = {"every": int(mk), "pixels": MAP_PIXELS if mp is None else int(mp),
+                                 "half_width": MAP_HALF_WIDTH_FACTOR * config["spawn_radius"] if mw is None else float(mw),
+                                 "axis": "z" if ma is None else ma}
+        density_map_config(config)  # (a bad K, N, W or axis raises here)
     return config
 
 

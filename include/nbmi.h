@@ -450,6 +450,62 @@ int nbmi_get_tracers_f64(nbmi_sim *sim, double *positions_xyz /* (m,3), may be N
                          double *velocities_xyz /* (m,3), may be NULL */);
 int nbmi_get_tracer_positions_f32(nbmi_sim *sim, float *positions_xyz /* (m,3) */);
 
+/* ---- mass and velocity fields on a regular grid --------------------------------------------
+ * Deposits the handle's current float64 state on a grid of dims[0] x dims[1] x dims[2] cells that covers [lo, hi) per
+ * axis: surface-density maps (a dims of 1 projects along that axis), density cubes, and the planes that mean-velocity and
+ * dispersion maps are made of.  `quantities` selects the planes, in the order of the bits: P is their number (at most 6).
+ * Masses are m, not G m, as in nbmi_knn.  Velocities are read as stored: the reference's kick-drift keeps them half a step
+ * apart from the positions (as in nbmi_diagnostics); a leapfrog handle's are synchronized.
+ *
+ * This text is the specification; the kernels and the tests' NumPy restatement (tests/deposit_ref.py) both follow it.
+ * All arithmetic is float64 in the association written, without FMA contraction.  Per call:
+ *   Grid constants.  inv_a = (double) dims_a / (hi_a - lo_a) per axis, computed once on the host.
+ *   Quantum of a plane.  mx = the maximum of |q_j| over ALL N bodies, inside the grid or not (a maximum is exact in any
+ *     order).  mx == 0 (or N == 0): the plane is zeros and its exponent reads 0.  Otherwise, with frexp(mx) = (f, E) and
+ *     L = the bit length of N, the exponent is e = E + L - 62, so that |k_j| <= 2^(62 - L) + 0.5 and, with N < 2^L, every
+ *     cell's integer sum stays inside int64.  exponents[p] = e.
+ *   Position on an axis.  u_a = (x_a - lo_a) * inv_a.  A body with a coordinate that is not finite is skipped and counted
+ *     in stats3[2].
+ *   NGP (nearest grid point), and any axis with dims_a == 1 under either scheme: i_a = floor(u_a) with weight 1.  (A
+ *     projection is asked for with dims_a == 1; CIC on such an axis would drop half of every body.)
+ *   CIC (cloud in cell), on an axis with dims_a >= 2: s = u_a - 0.5, i = floor(s), f = s - i; cell i gets the weight
+ *     1.0 - f and cell i + 1 the weight f.
+ *   Which cells take part.  A cell index takes part only if 0 <= i < dims_a, compared on the floored double (i + 1 is
+ *     that double plus 1.0) before any conversion to an integer.  The rest is dropped: no wrap-around, no clamping.
+ *   One contribution.  A (body, cell) pair whose three indices all take part - a weight of 0 included - with the weights
+ *     wx, wy, wz is c = q * ((wx * wy) * wz); its integer is k = (int64) rint(ldexp(c, -e)), to nearest, ties to even.
+ *   Output.  K[plane][cell] = the sum of k over all contributions, an exact integer sum (64-bit integer atomics);
+ *     out = ldexp((double) K, e).  stats3 = {bodies with at least one contribution, contributions applied, bodies skipped
+ *     as not finite}.
+ * Consequences (tested):
+ *   The result does not depend on the order of the state rows, on the handle type (Barnes-Hut or direct N^2) or on how
+ *   the kernel aggregates; two calls give the same bits.
+ *   The NUMBER plane under NGP holds exact counts, and its cell sum equals stats3[0].
+ *   |out - exact sum of c| <= 0.5 * 2^e * (contributions of that cell), plus one rounding of the final conversion.
+ *   The price of exactness: a body whose |q| is below 2^(e - 1) contributes nothing - about 2^-36 of the largest body at
+ *   2^26 bodies.
+ * NBMI_ERR_ARG, message "nbmi_deposit: ...", before anything is launched and with `out` untouched: null lo, hi, dims or
+ * out; a bound that is not finite; hi_a <= lo_a, or hi_a - lo_a or inv_a not finite; dims_a < 1; P * cells > 2^28; a scheme
+ * other than 0 or 1; quantities equal to 0 or with unknown bits; owner-mode handles and handles with a proper shard.
+ * After the pass over the maxima, `out` still untouched: a selected quantity whose maximum is not finite (the message
+ * names the plane).  Barnes-Hut and direct handles are accepted; no tree is built.  N == 0 gives zeros.
+ * A call changes nothing that a later step or query reads (the state and its order, the tree header, the precision flags,
+ * the step count, the stored leapfrog acceleration, the tracers).  It waits for the work enqueued so far and reports
+ * deferred errors as the getters do.  Scratch: 8 * P * cells bytes on the device, kept and grown on demand, and 72 bytes of
+ * results.  With nbmi_enable_timers the device time of the call's kernels (without its copies) is added to "other".
+ * Environment NBMI_DEPOSIT_AGG (read when the handle is created, like the other measurement knobs): 1 = the lanes of a
+ * workgroup that hit the same cell are combined in LDS first and one atomic leaves per distinct cell, 0 = one global
+ * atomic per contribution.  The results are the same bits; the time is not (DESIGN.md section 4.20 has the A/B). */
+#define NBMI_DEPOSIT_NGP 0
+#define NBMI_DEPOSIT_CIC 1
+#define NBMI_DEPOSIT_NUMBER 1   /* 1 plane:  q = 1                                   */
+#define NBMI_DEPOSIT_MASS 2     /* 1 plane:  q = m                                   */
+#define NBMI_DEPOSIT_MOMENTUM 4 /* 3 planes: q = m * vx, m * vy, m * vz              */
+#define NBMI_DEPOSIT_KINETIC 8  /* 1 plane:  q = m * ((vx*vx + vy*vy) + vz*vz)       */
+int nbmi_deposit(nbmi_sim *sim, const double lo[3], const double hi[3], const int32_t dims[3], int scheme,
+                 int quantities, double *out /* (P, dims[2], dims[1], dims[0]) C order */,
+                 int64_t *stats3 /* may be NULL */, int32_t *exponents /* (P,), may be NULL */);
+
 /* Multi-GPU (one process per GPU).  A handle created with nbmi_create holds ALL bodies; with a
  * shard set, step() integrates only the key-sorted ranks [begin,end) (direct method: the body
  * indices [begin,end), its state is never re-ordered) and leaves the others untouched until
