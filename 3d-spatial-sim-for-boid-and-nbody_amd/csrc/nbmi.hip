@@ -1074,7 +1074,7 @@ __device__ __forceinline__ bool exact_take_idx(unsigned idx, const Body64 &b) {
 // potential walks accept the same (body, node) sets and a visit decides alike in the hand-scheduled loops' C++ twins.
 // `d2` is the fp32 dist_sq (the float64 walks pass their (float)d2), `s2t` the record's threshold (0: a leaf, always
 // taken).  Non-negative floats compare as integers; hi / lo are the edges of the uncertainty band, `band2` ulps wide.
-// A lane inside the band (or one the caller names in `also`: k_potential_tree's near pairs) that takes part in the
+// A lane inside the band (or one the caller names in `also`: field_walk's near pairs) that takes part in the
 // visit is re-decided in float64 - rare, divergent.  geom: the lane takes node `idx` if it takes part.
 struct Opening {
     bool geom, band;
@@ -3172,18 +3172,120 @@ __global__ void k_copy_ids(const int32_t *__restrict__ ids, int32_t *__restrict_
 // Float64 throughout; every sum has a fixed order (no floating-point atomics), so two calls on one state agree bit
 // for bit.
 // ---------------------------------------------------------------------------------------
-// Tree potential.  The walk of K9 in its C++ form, one wave per 64 key-adjacent bodies, one wave-uniform cursor over
-// the same pre-order array and skip links, and per lane the force walks' opening decision (opening()): the fp32 test on
-// the Node record, re-decided in float64 through Node64 where d^2 falls inside the uncertainty band.  A lane's
-// accepted set does not depend on the other lanes of its wave (it takes part in every node none of its own accepted
-// ancestors covers), so it is the force walk's set.  What differs is the term: the node's float64 row pot[idx] =
-// {cx, cy, cz, G M} (written by k_emit_tile into the diag64 slot for this build only: a cell's double-double moments,
-// a leaf's body as the float64 state has it), and the reference's guard (simulation.py:260) on the float64 dist_sq.
-// The own leaf has d = 0 exactly, so the guard skips it as the reference's explicit test does.  phi and the number of
-// applied terms land at the body's state row j = perm[rank].
-// kQuad (quadrupole mode): an applied cell term also carries the second-order term
-// 1/2 [tr P u^-3/2 - 3 (d^T P d) u^-5/2] with the cell's float64 second moments quad[9 idx + 3 .. 9 idx + 8] (k_quad_level);
-// leaves are skipped.  Both instantiations share the decision, the near-pair rule below included.
+// The float64 probe walk: the one walk of the potentials (K14), nbmi_field_at (K19) and the tracers (K20).  The walk of
+// K9 in its C++ form, one wave per 64 key-adjacent lanes, one wave-uniform cursor over the same pre-order array and skip
+// links, and per lane the force walks' opening decision (opening()): the fp32 test on the Node record, re-decided in
+// float64 through Node64 where d^2 falls inside the uncertainty band.  A lane's accepted set does not depend on the other
+// lanes of its wave (it takes part in every node none of its own accepted ancestors covers), so at a body it is the force
+// walk's set, and which probes share a wave decides the speed of a call and never a bit of its result.  What differs is
+// the term: the node's float64 row pot[idx] = {cx, cy, cz, G M} (written by k_emit_tile into the diag64 slot for this
+// build only: a cell's double-double moments, a leaf's body as the float64 state has it), and the reference's guard
+// (simulation.py:260) on the float64 dist_sq.  A body's own leaf has d = 0 exactly, so the guard skips it as the
+// reference's explicit test does.
+// The lane.  (qx, qy, qz) is its float64 position and `b64` says where opening()'s float64 re-decision reads the same
+// three numbers: a body's row perm[rank] of the current state (lane_prologue), or row `rank` of buffer 0 of a table that
+// names the probe columns there (probe_alloc) - either way it computes, operation for operation, what it computes for a
+// body at that place.  (px, py, pz) is the same position in fp32, for the fp32 test: a probe's caller rounds q, a
+// body's has it from posm_s - a coalesced load, so the first visit need not wait for the gathered float64 row (with
+// the rounding in here the potential measured 0.4 - 0.7 % slower).  A lane with valid == false walks nothing and
+// returns zeros.
+// The band.  The node records carry the upper edge bits(s2t) + K of the band for K = band_half_ulps(maxabs of the
+// bodies): the fp32 error of d^2 grows with the larger of |p| and |c|, and a probe may lie far outside the root cube.
+// kWiden (probes; pmax: the largest |coordinate| among them, eps: the softening): the walk widens the band to K' =
+// band_half_ulps(max(maxabs, pmax)) about the same centre - upper edge + (K' - K), width 2 K'.  pmax <= maxabs: K' = K.
+// Without kWiden (bodies: nothing lies outside maxabs) the band is the build's own by construction, pmax and eps are not
+// looked at, and a visit pays nothing for the widening.  (Either way a decision is the float64 one; the band only settles
+// which visits compute it.)
+// Near pairs.  The band's half width is capped at 2^21 ulps (band_half_ulps): enough for the fp32 error of d^2, (6.93
+// maxabs / d + 4) ulps, only while d >= 3.3e-6 maxabs.  At eps == 0 (or an eps below that) closer pairs exist, and their
+// fp32 d^2 says nothing about the test: a cell closer than 8e-6 maxabs (twice the limit plus the rounding of d itself;
+// maxabs: the larger of the bodies' and pmax) is decided in float64 whatever the fp32 test said, so that `terms` stays
+// the reference's count there too.
+// kAcc: the acceleration is summed beside phi and the term count; without it the lane carries neither the sums nor
+// their arithmetic.
+// kQuad (quadrupole mode): an applied internal cell (leaves are skipped) also adds the
+// second-order terms, with u = dist_sq and the cell's float64 second moments P = quad[9 idx + 3 .. 9 idx + 8]
+// (k_quad_level), in a scope of their own:
+//   phi += 1/2 [tr P u^-3/2 - 3 (d^T P d) u^-5/2],   a += [7.5 (d^T P d) u^-7/2 - 1.5 tr P u^-5/2] d - 3 u^-5/2 P d.
+struct FieldSum {
+    double ax, ay, az, phi;
+    int32_t terms;
+};
+template <bool kQuad, bool kAcc, bool kWiden>
+__device__ __forceinline__ FieldSum field_walk(const Node *__restrict__ nodes, const double4 *__restrict__ pot, const TreeInfo *info,
+                                               const Body64 &b64, double qx, double qy, double qz, float px, float py, float pz,
+                                               bool valid, float eps2f, double eps, double pmax,
+                                               const double *__restrict__ quad) {
+    const unsigned nn = __builtin_amdgcn_readfirstlane((unsigned)info->num_nodes * kNodeBytes);
+    const double eps2 = __longlong_as_double((long long)uniform_u64((unsigned long long)__double_as_longlong(b64.tab->eps2)));
+    double maxabs = __longlong_as_double((long long)info->maxabs_bits);
+    int dk = 0;
+    unsigned band2 = __builtin_amdgcn_readfirstlane(info->band2);
+    if (kWiden) {
+        maxabs = fmax(maxabs, pmax);
+        const unsigned kb = info->band2 >> 1;
+        unsigned kp = band_half_ulps(maxabs, eps);
+        kp = kp > kb ? kp : kb;
+        dk = __builtin_amdgcn_readfirstlane((int)(kp - kb));
+        band2 = __builtin_amdgcn_readfirstlane(2u * kp);
+    }
+    float near2 = 0.f;
+    if (band2 >= 2u * 2097153u) {
+        const double r = 8.0e-6 * maxabs;
+        near2 = eps2f + (float)(r * r);
+    }
+    unsigned resume = valid ? 0u : 0xffffffffu;
+    double ax = 0.0, ay = 0.0, az = 0.0, phi = 0.0;
+    int32_t terms = 0;
+    unsigned off = 0u;
+    while (off < nn) {
+        off = __builtin_amdgcn_readfirstlane(off);
+        const unsigned idx = off / kNodeBytes;
+        const Node nd = nodes[idx];
+        const bool cell = __float_as_int(nd.s2t) != 0;
+        const float s2t = kWiden && cell ? __int_as_float(__float_as_int(nd.s2t) + dk) : nd.s2t;  // (a leaf keeps its 0)
+        const float dx = nd.cx - px, dy = nd.cy - py, dz = nd.cz - pz;
+        const float dist_sq = fmaf(dz, dz, fmaf(dy, dy, fmaf(dx, dx, eps2f)));
+        const bool active = resume <= off;
+        const bool near = cell && dist_sq < near2;
+        const bool geom = opening(dist_sq, s2t, band2, active, idx, b64, near).geom;
+        bool take;
+        const unsigned next = advance<kNodeBytes>(active, geom, off, nd.next_off, resume, take);
+        if (take) {
+            const double4 q = pot[idx];
+            const double ex = q.x - qx, ey = q.y - qy, ez = q.z - qz;
+            const double d2 = ex * ex + ey * ey + ez * ez + eps2;  // (-ffp-contract=off: the reference's roundings)
+            if (q.w > 0.0 && d2 > eps2) {
+                const double dist = sqrt(d2);
+                phi -= q.w / dist;
+                terms++;
+                if (kAcc) {
+                    const double w = q.w / (dist * d2);
+                    ax += ex * w; ay += ey * w; az += ez * w;
+                }
+                if (kQuad && nd.next_off != off + kNodeBytes) {  // an internal cell
+                    const double *pq = quad + 9 * (size_t)idx + 3;
+                    const double pxx = pq[0], pyy = pq[1], pzz = pq[2], pxy = pq[3], pxz = pq[4], pyz = pq[5];
+                    const double dpd = ex * (pxx * ex + 2.0 * (pxy * ey + pxz * ez)) + ey * (pyy * ey + 2.0 * (pyz * ez)) + ez * (pzz * ez);
+                    const double tr = pxx + pyy + pzz;
+                    const double i1 = 1.0 / dist, i3 = i1 / d2, i5 = i3 / d2;
+                    phi += 0.5 * (tr * i3 - 3.0 * dpd * i5);
+                    if (kAcc) {
+                        const double sc = 7.5 * dpd * (i5 / d2) - 1.5 * tr * i5, t3 = 3.0 * i5;
+                        ax += sc * ex - t3 * (pxx * ex + pxy * ey + pxz * ez);
+                        ay += sc * ey - t3 * (pxy * ex + pyy * ey + pyz * ez);
+                        az += sc * ez - t3 * (pxz * ex + pyz * ey + pzz * ez);
+                    }
+                }
+            }
+        }
+        off = next;
+    }
+    return FieldSum{ax, ay, az, phi, terms};
+}
+
+// Tree potential: the probe walk with a body in the lane - the build's band, phi and the term count only.  Both land at
+// the body's state row j = perm[rank].
 template <bool kQuad>
 __global__ __launch_bounds__(kBlock) void k_potential_tree(const Node *__restrict__ nodes, const double4 *__restrict__ pot,
                                                            const WalkTable *tab, const TreeInfo *info,
@@ -3194,53 +3296,11 @@ __global__ __launch_bounds__(kBlock) void k_potential_tree(const Node *__restric
     const int64_t rank = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     const WalkCtx C = lane_prologue(nodes, posm_s, perm, rank, n, info, tab, curbuf);
     const Lane64 L = lane_f64(C);
-    const unsigned nn = __builtin_amdgcn_readfirstlane((unsigned)info->num_nodes * kNodeBytes);
-    const double eps2 = L.eps2, qx = L.qx, qy = L.qy, qz = L.qz;
-    // The band's half width is capped at 2^21 ulps (band_half_ulps): enough for the fp32 error of d^2, (6.93 maxabs / d
-    // + 4) ulps, only while d >= 3.3e-6 maxabs.  At eps == 0 (or an eps below that) closer pairs exist, and their fp32
-    // d^2 says nothing about the test: a cell closer than 8e-6 maxabs (twice the limit plus the rounding of d itself) is
-    // decided in float64 whatever the fp32 test said, so that `terms` stays the reference's count there too.
-    float near2 = 0.f;
-    if (C.band2 >= 2u * 2097153u) {
-        const double r = 8.0e-6 * __longlong_as_double((long long)info->maxabs_bits);
-        near2 = eps2f + (float)(r * r);
-    }
-    unsigned resume = C.resume;
-    double acc = 0.0;
-    int32_t terms = 0;
-    unsigned off = 0u;
-    while (off < nn) {
-        off = __builtin_amdgcn_readfirstlane(off);
-        const unsigned idx = off / kNodeBytes;
-        const Node nd = nodes[idx];
-        const float dx = nd.cx - C.px, dy = nd.cy - C.py, dz = nd.cz - C.pz;
-        const float dist_sq = fmaf(dz, dz, fmaf(dy, dy, fmaf(dx, dx, eps2f)));
-        const bool active = resume <= off;
-        const bool near = __float_as_int(nd.s2t) != 0 && dist_sq < near2;  // a cell, see near2
-        const bool geom = opening(dist_sq, nd.s2t, C.band2, active, idx, C.b64, near).geom;
-        bool take;
-        const unsigned next = advance<kNodeBytes>(active, geom, off, nd.next_off, resume, take);
-        if (take) {
-            const double4 q = pot[idx];
-            const double ex = q.x - qx, ey = q.y - qy, ez = q.z - qz;
-            const double d2 = ex * ex + ey * ey + ez * ez + eps2;  // (-ffp-contract=off: the reference's roundings)
-            if (q.w > 0.0 && d2 > eps2) {
-                acc -= q.w / sqrt(d2);
-                terms++;
-                if (kQuad && nd.next_off != off + kNodeBytes) {  // an internal cell
-                    const double *pq = quad + 9 * (size_t)idx + 3;
-                    const double pxx = pq[0], pyy = pq[1], pzz = pq[2], pxy = pq[3], pxz = pq[4], pyz = pq[5];
-                    const double dpd = ex * (pxx * ex + 2.0 * (pxy * ey + pxz * ez)) + ey * (pyy * ey + 2.0 * (pyz * ez)) + ez * (pzz * ez);
-                    const double i1 = 1.0 / sqrt(d2), i3 = i1 / d2;
-                    acc += 0.5 * ((pxx + pyy + pzz) * i3 - 3.0 * dpd * (i3 / d2));
-                }
-            }
-        }
-        off = next;
-    }
+    const FieldSum f = field_walk<kQuad, false, false>(nodes, pot, info, C.b64, L.qx, L.qy, L.qz, C.px, C.py, C.pz, C.valid, eps2f, 0.0,
+                                                       0.0, quad);
     if (C.valid) {
-        phi[C.j] = acc;
-        cnt[C.j] = terms;
+        phi[C.j] = f.phi;
+        cnt[C.j] = f.terms;
     }
 }
 
@@ -3441,7 +3501,7 @@ __global__ __launch_bounds__(kBlock) void k_walk_quad(const Node *__restrict__ n
 
 // Direct potential: phi_i = -sum_{j != i} G m_j / sqrt(|x_j - x_i|^2 + eps^2), float64 bodies staged through LDS
 // tiles of kBlock, every thread one body, j in index order.  eps == 0: pairs at zero distance are skipped (k_direct's
-// guard).
+// guard).  (Not field_direct_sum: this guard counts a coincident distinct body when eps > 0, the probe sum's skips it.)
 __global__ __launch_bounds__(kBlock) void k_potential_direct(Bodies cur, int64_t n, double G, double eps2,
                                                              double *__restrict__ phi, int32_t *__restrict__ cnt) {
     __shared__ double4 tile[kBlock];
@@ -4300,10 +4360,9 @@ __global__ __launch_bounds__(kQueryBlock) void k_pair_counts(const Node *__restr
 
 // ---------------------------------------------------------------------------------------
 // K19: the field at arbitrary points (nbmi_field_at; include/nbmi.h).
-// k_potential_tree with a probe in the lane instead of a body: float64 throughout, per-lane sums in pre-order of the
-// node array, per-lane stores.  A lane's accepted set and the order of its sum depend on nothing but the probe and the
-// tree, so which probes share a wave - the sort below, the chunks of the call, the other points - decides the speed of a
-// call and never a bit of its result.
+// The probe walk of K14 (field_walk) with a probe in the lane instead of a body, the acceleration summed as well.  Which
+// probes share a wave - the sort below, the chunks of the call, the other points - decides the speed of a call and never
+// a bit of its result.
 // ---------------------------------------------------------------------------------------
 // A call is cut into chunks of at most this many points: the scratch never holds more.
 constexpr int64_t kFieldChunk = 1048576;
@@ -4334,90 +4393,9 @@ __global__ __launch_bounds__(kBlock) void k_field_gather(const double *__restric
     sx[r] = pts[3 * i]; sy[r] = pts[3 * i + 1]; sz[r] = pts[3 * i + 2];
 }
 
-// The probe walk.  `tab` is the handle's walk table with buf[0].x / y / z pointing at the probe columns (sx, sy, sz):
-// opening()'s float64 re-decision reads "body" `rank` of buffer 0 there and so computes, operation for operation, what
-// it computes for a body at that place.
-// The band.  The node records carry the upper edge bits(s2t) + K of the band for K = band_half_ulps(maxabs of the
-// bodies): the fp32 error of d^2 grows with the larger of |p| and |c|, and a probe may lie far outside the root cube.
-// The walk widens the band to K' = band_half_ulps(max(maxabs, pmax)) about the same centre - upper edge + (K' - K),
-// width 2 K' - where pmax is the call's largest |coordinate|, and takes k_potential_tree's near-pair rule from the same
-// maximum.  pmax <= maxabs: K' = K, and every decision is k_potential_tree's bit for bit.  (Either way a decision is
-// the float64 one; the band only settles which visits compute it.)
-// kQuad: an applied internal cell adds the second-order terms to phi (k_potential_tree<true>'s expression) and to acc,
-//   a += [7.5 (d^T P d) u^-7/2 - 1.5 tr P u^-5/2] d - 3 u^-5/2 P d,   u = dist_sq,
-// from the float64 moments of k_quad_level, in a scope of their own.
-// Results land at the probe's row of the chunk, order[rank].
-// The per-lane walk itself, shared by k_field_tree and k_tracer_tree: the probe (qx, qy, qz) is row `row` of the probe
-// columns; a lane with valid == false walks nothing and returns zeros.
-struct FieldSum {
-    double ax, ay, az, phi;
-    int32_t terms;
-};
-template <bool kQuad>
-__device__ __forceinline__ FieldSum field_walk(const Node *__restrict__ nodes, const double4 *__restrict__ pot, const WalkTable *tab,
-                                               const TreeInfo *info, double qx, double qy, double qz, uint32_t row, bool valid,
-                                               float eps2f, double eps, double pmax, const double *__restrict__ quad) {
-    const float px = (float)qx, py = (float)qy, pz = (float)qz;
-    const Body64 b64{tab, 0, row};
-    const unsigned nn = __builtin_amdgcn_readfirstlane((unsigned)info->num_nodes * kNodeBytes);
-    const double eps2 = __longlong_as_double((long long)uniform_u64((unsigned long long)__double_as_longlong(tab->eps2)));
-    const double maxabs = fmax(__longlong_as_double((long long)info->maxabs_bits), pmax);
-    const unsigned kb = info->band2 >> 1;
-    unsigned kp = band_half_ulps(maxabs, eps);
-    kp = kp > kb ? kp : kb;
-    const int dk = __builtin_amdgcn_readfirstlane((int)(kp - kb));
-    const unsigned band2 = __builtin_amdgcn_readfirstlane(2u * kp);
-    float near2 = 0.f;  // see k_potential_tree
-    if (band2 >= 2u * 2097153u) {
-        const double r = 8.0e-6 * maxabs;
-        near2 = eps2f + (float)(r * r);
-    }
-    unsigned resume = valid ? 0u : 0xffffffffu;
-    double ax = 0.0, ay = 0.0, az = 0.0, phi = 0.0;
-    int32_t terms = 0;
-    unsigned off = 0u;
-    while (off < nn) {
-        off = __builtin_amdgcn_readfirstlane(off);
-        const unsigned idx = off / kNodeBytes;
-        const Node nd = nodes[idx];
-        const bool cell = __float_as_int(nd.s2t) != 0;
-        const float s2t = cell ? __int_as_float(__float_as_int(nd.s2t) + dk) : 0.f;
-        const float dx = nd.cx - px, dy = nd.cy - py, dz = nd.cz - pz;
-        const float dist_sq = fmaf(dz, dz, fmaf(dy, dy, fmaf(dx, dx, eps2f)));
-        const bool active = resume <= off;
-        const bool near = cell && dist_sq < near2;
-        const bool geom = opening(dist_sq, s2t, band2, active, idx, b64, near).geom;
-        bool take;
-        const unsigned next = advance<kNodeBytes>(active, geom, off, nd.next_off, resume, take);
-        if (take) {
-            const double4 q = pot[idx];
-            const double ex = q.x - qx, ey = q.y - qy, ez = q.z - qz;
-            const double d2 = ex * ex + ey * ey + ez * ez + eps2;  // (-ffp-contract=off: the reference's roundings)
-            if (q.w > 0.0 && d2 > eps2) {
-                const double dist = sqrt(d2);
-                const double w = q.w / (dist * d2);
-                phi -= q.w / dist;
-                ax += ex * w; ay += ey * w; az += ez * w;
-                terms++;
-                if (kQuad && nd.next_off != off + kNodeBytes) {  // an internal cell
-                    const double *pq = quad + 9 * (size_t)idx + 3;
-                    const double pxx = pq[0], pyy = pq[1], pzz = pq[2], pxy = pq[3], pxz = pq[4], pyz = pq[5];
-                    const double dpd = ex * (pxx * ex + 2.0 * (pxy * ey + pxz * ez)) + ey * (pyy * ey + 2.0 * (pyz * ez)) + ez * (pzz * ez);
-                    const double tr = pxx + pyy + pzz;
-                    const double i1 = 1.0 / dist, i3 = i1 / d2, i5 = i3 / d2;
-                    phi += 0.5 * (tr * i3 - 3.0 * dpd * i5);
-                    const double sc = 7.5 * dpd * (i5 / d2) - 1.5 * tr * i5, t3 = 3.0 * i5;
-                    ax += sc * ex - t3 * (pxx * ex + pxy * ey + pxz * ez);
-                    ay += sc * ey - t3 * (pxy * ex + pyy * ey + pyz * ez);
-                    az += sc * ez - t3 * (pxz * ex + pyz * ey + pzz * ez);
-                }
-            }
-        }
-        off = next;
-    }
-    return FieldSum{ax, ay, az, phi, terms};
-}
-
+// One chunk of probes through the probe walk (field_walk, K14): lane `rank` has row `rank` of the probe columns, which
+// `tab` names as buffer 0 (probe_alloc); pmax is the call's largest |coordinate|.  Results land at the probe's row of the
+// chunk, order[rank].
 template <bool kQuad>
 __global__ __launch_bounds__(kBlock) void k_field_tree(const Node *__restrict__ nodes, const double4 *__restrict__ pot,
                                                        const WalkTable *tab, const TreeInfo *info,
@@ -4431,7 +4409,8 @@ __global__ __launch_bounds__(kBlock) void k_field_tree(const Node *__restrict__ 
     const bool valid = rank < m;
     double qx = 0.0, qy = 0.0, qz = 0.0;
     if (valid) { qx = sx[rank]; qy = sy[rank]; qz = sz[rank]; }
-    const FieldSum f = field_walk<kQuad>(nodes, pot, tab, info, qx, qy, qz, (uint32_t)(valid ? rank : 0), valid, eps2f, eps, pmax, quad);
+    const FieldSum f = field_walk<kQuad, true, true>(nodes, pot, info, Body64{tab, 0, (uint32_t)(valid ? rank : 0)}, qx, qy, qz, (float)qx,
+                                                     (float)qy, (float)qz, valid, eps2f, eps, pmax, quad);
     if (valid) {
         const int64_t o = order ? (int64_t)order[rank] : rank;
         if (acc_out) { acc_out[3 * o] = f.ax; acc_out[3 * o + 1] = f.ay; acc_out[3 * o + 2] = f.az; }
@@ -4552,7 +4531,8 @@ __global__ __launch_bounds__(kBlock) void k_tracer_tree(const Node *__restrict__
     }
     const bool live = inside && tracer_live(qx, qy, qz, vx, vy, vz);
     const double pmax = __longlong_as_double((long long)__atomic_load_n(pmax_word, __ATOMIC_RELAXED));
-    const FieldSum f = field_walk<kQuad>(nodes, pot, tab, info, qx, qy, qz, (uint32_t)(inside ? rank : 0), live, eps2f, eps, pmax, quad);
+    const FieldSum f = field_walk<kQuad, true, true>(nodes, pot, info, Body64{tab, 0, (uint32_t)(inside ? rank : 0)}, qx, qy, qz, (float)qx,
+                                                     (float)qy, (float)qz, live, eps2f, eps, pmax, quad);
     bool moved = false;
     if (live) moved = tracer_epilogue<kLeap>(p, v, a, o, qx, qy, qz, vx, vy, vz, f, dt, damping);
     if (kLeap == 0) tracer_raise_pmax(pmax_word, moved, qx, qy, qz);
@@ -4807,6 +4787,19 @@ __global__ __launch_bounds__(kBlock) void k_deposit_out(unsigned long long *__re
 // visits are - 75 % instead of 68 % at 1 M - measured the same or slower.)
 constexpr int64_t kHomeSplitBodies = 1500000;
 
+// The walk-order side of a chunk of probes (nbmi_field_at and the tracers, sections 4.18 / 4.19): `rows` probes as
+// columns in walk order - 56 bytes each with their sort keys and indices in and out - the sort's temp buffer for that
+// many pairs, and the walk table whose buffer 0 names the columns.  probe_alloc / probe_free.
+struct ProbeScratch {
+    int64_t rows = 0;
+    double *sx = nullptr, *sy = nullptr, *sz = nullptr;
+    uint64_t *key = nullptr, *key_s = nullptr;
+    uint32_t *idx = nullptr, *order = nullptr;
+    char *sort_tmp = nullptr;
+    size_t sort_bytes = 0;
+    WalkTable *wtab = nullptr;
+};
+
 struct nbmi_sim {
     int64_t n = 0;
     int method = 0, device = 0;
@@ -4976,38 +4969,24 @@ struct nbmi_sim {
     } dep;
     bool deposit_agg = true;  // the workgroup combines contributions per cell in LDS first (NBMI_DEPOSIT_AGG=0: one global
                               // atomic per contribution; same bits, 3.1 - 134 x the time: DESIGN.md section 4.20)
-    // Scratch of nbmi_field_at (section 4.18): `rows` points of a chunk - 108 bytes each: the points as they came, their
-    // columns in walk order, acc, phi, terms, sort keys and indices in and out - the sort's temp buffer for that many
-    // pairs, and the walk table whose buffer 0 names the probe columns.  Grown by the call that needs more, never beyond
-    // kFieldChunk rows; no step touches it.
-    struct {
-        int64_t rows = 0;
-        double *pts = nullptr, *sx = nullptr, *sy = nullptr, *sz = nullptr, *acc = nullptr, *phi = nullptr;
+    // Scratch of nbmi_field_at (section 4.18): `rows` points of a chunk - 108 bytes each: the points as they came, acc,
+    // phi, terms, and their walk-order side.  Grown by the call that needs more, never beyond kFieldChunk rows; no step
+    // touches it.
+    struct : ProbeScratch {
+        double *pts = nullptr, *acc = nullptr, *phi = nullptr;
         int32_t *cnt = nullptr;
-        uint64_t *key = nullptr, *key_s = nullptr;
-        uint32_t *idx = nullptr, *order = nullptr;
-        char *sort_tmp = nullptr;
-        size_t sort_bytes = 0;
-        WalkTable *wtab = nullptr;
     } field;
     bool field_sort = true;  // probes walk in key order (NBMI_FIELD_SORT=0: in the caller's order; measurement)
     // Massless tracers (nbmi_set_tracers, section 4.19); all null / 0 on a handle without them.  State: p and v, (m, 3)
     // rows in the caller's order, and the leapfrog's a (allocated by the first leapfrog step; acc_valid as the bodies').
-    // pmax: the device word of tracer_raise_pmax.  Scratch (Barnes-Hut): `rows` = min(m, kFieldChunk) probes in walk order,
-    // sort keys and indices in and out, the sort's temp buffer and a walk table whose buffer 0 names the columns.  The
-    // steps enqueue work on it without waiting, so it is the tracers' own: nbmi_field_at's regrowth never frees it.
-    struct {
+    // pmax: the device word of tracer_raise_pmax.  Scratch (Barnes-Hut): the walk-order side for `rows` = min(m,
+    // kFieldChunk) probes.  The steps enqueue work on it without waiting, so it is the tracers' own: nbmi_field_at's
+    // regrowth never frees it.
+    struct : ProbeScratch {
         int64_t m = 0;
         double *p = nullptr, *v = nullptr, *a = nullptr;
         bool acc_valid = false;
         unsigned long long *pmax = nullptr;
-        int64_t rows = 0;
-        double *sx = nullptr, *sy = nullptr, *sz = nullptr;
-        uint64_t *key = nullptr, *key_s = nullptr;
-        uint32_t *idx = nullptr, *order = nullptr;
-        char *sort_tmp = nullptr;
-        size_t sort_bytes = 0;
-        WalkTable *wtab = nullptr;
     } tr;
     // what nbmi_compute_colors / nbmi_frame_begin colour by (nbmi_set_color_mode)
     int color_mode = NBMI_COLOR_SPEED, color_k = 32;
@@ -5630,13 +5609,102 @@ struct SideBuild {
     }
 };
 
+// ---- the float64 probe family (potentials, nbmi_field_at, tracers: sections 4.9, 4.18, 4.19) ----
+// The octree of the current positions with the float64 node rows {cx, cy, cz, G M}, inside a SideBuild, and on it what
+// `walk` enqueues (its result is the call's).  What the callers differ in:
+//   report_first  a capacity error of an earlier step is waited for and reported first, as a getter does (the tracers'
+//                 priming is part of a step and never waits)
+//   check_build   the build's own capacity error is reported before `walk` runs: nothing is copied out of a walk that
+//                 did not run
+//   wait          SideBuild::finish's
+//   step_rows     the rows go where a step's build puts them (step_build).  A quadrupole build writes them to the rows it
+//                 is given or, given none, to quad_pot: the tracers' walk reads quad_pot in that mode, on this tree as
+//                 on a step's, so their build is given none there; the other two read diag_pot in either mode.
+template <class Walk>
+int side_tree(nbmi_sim *s, bool report_first, bool check_build, bool wait, bool step_rows, Walk walk) {
+    if (!s->diag_pot && dev_alloc(s, &s->diag_pot, s->node_capacity + 2)) return NBMI_ERR_HIP;
+    if (report_first) {
+        NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
+        if (int rc = check_device_error(s)) return rc;
+    }
+    SideBuild side(s);  // (no "auto" decision in its build: the wave flags and force_all64 stay the last step's)
+    if (side.rc) return side.rc;
+    BuildRequest build;
+    build.aux = false;
+    build.diag_rows = step_rows && s->multipole == NBMI_MULTIPOLE_QUADRUPOLE ? nullptr : s->diag_pot;
+    int rc = enqueue_tree(s, build);
+    if (rc == 0 && check_build) rc = check_device_error(s);
+    if (rc == 0) rc = walk();
+    return side.finish(rc, wait);
+}
+
+void probe_free(nbmi_sim *s, ProbeScratch &g) {
+    dev_free(s, &g.sx); dev_free(s, &g.sy); dev_free(s, &g.sz); dev_free(s, &g.key); dev_free(s, &g.key_s);
+    dev_free(s, &g.idx); dev_free(s, &g.order); dev_free(s, &g.sort_tmp); dev_free(s, &g.wtab);
+    g.rows = 0;
+    g.sort_bytes = 0;
+}
+// An empty scratch for chunks of `rows` probes, its sort buffer initialised and its walk table on the device; on failure
+// nothing is left allocated.  Of the table the probe walk reads n64, theta, eps2 (exact_take_idx, field_walk) and
+// buf[0].x / y / z, the columns.  None of them changes after create_impl - the later uploads of the handle's own table
+// (upload_walk_table) bring the acceleration columns and nodesd - so one upload per allocation serves.  Waits for the
+// stream: the table is a stack object.
+int probe_alloc(nbmi_sim *s, ProbeScratch &g, int64_t rows) {
+    const size_t r = (size_t)rows;
+    g.sort_bytes = nbmi::radix_temp_bytes_u64(r, kFieldSortBits);
+    auto fill = [&]() -> int {
+        if (dev_alloc(s, &g.sx, r) || dev_alloc(s, &g.sy, r) || dev_alloc(s, &g.sz, r) || dev_alloc(s, &g.key, r) ||
+            dev_alloc(s, &g.key_s, r) || dev_alloc(s, &g.idx, r) || dev_alloc(s, &g.order, r) ||
+            dev_alloc(s, &g.sort_tmp, g.sort_bytes + 256) || dev_alloc(s, &g.wtab, 1))
+            return NBMI_ERR_HIP;
+        WalkTable t = walk_table(s);
+        t.buf[0].x = g.sx; t.buf[0].y = g.sy; t.buf[0].z = g.sz;
+        NBMI_HIP_CHECK(nbmi::radix_init_temp(g.sort_tmp, s->stream));
+        NBMI_HIP_CHECK(hipMemcpyAsync(g.wtab, &t, sizeof(t), hipMemcpyHostToDevice, s->stream));
+        NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
+        return 0;
+    };
+    if (int rc = fill()) {
+        probe_free(s, g);
+        return rc;
+    }
+    g.rows = rows;
+    return 0;
+}
+// One chunk of mc <= g.rows probes, pts (mc, 3), into the columns in walk order: keys in the tree's root cube, sort,
+// gather.  *order: the probe at each rank, or null where the chunk is walked as it came (NBMI_FIELD_SORT=0, or a chunk
+// of one wave: there is no neighbour to choose).
+int probe_order_chunk(nbmi_sim *s, ProbeScratch &g, const double *pts, int64_t mc, const uint32_t **order) {
+    hipStream_t st = s->stream;
+    *order = nullptr;
+    if (s->field_sort && mc > 64) {
+        if (s->hilbert) k_field_keys<true><<<nblocks(mc), kBlock, 0, st>>>(pts, mc, s->info, g.key, g.idx);
+        else k_field_keys<false><<<nblocks(mc), kBlock, 0, st>>>(pts, mc, s->info, g.key, g.idx);
+        NBMI_HIP_CHECK(nbmi::radix_sort_pairs_u64(g.sort_tmp, g.sort_bytes, g.key, g.key_s, g.idx, g.order, (size_t)mc,
+                                                  63 - kFieldSortBits, 63, st));
+        *order = g.order;
+    }
+    k_field_gather<<<nblocks(mc), kBlock, 0, st>>>(pts, *order, mc, g.sx, g.sy, g.sz);
+    return 0;
+}
+// Waits for the stream and looks at the sort's error word: set, the temp buffer is made ready again and `what` reported.
+int probe_sort_error(nbmi_sim *s, ProbeScratch &g, const char *what) {
+    unsigned sort_err = 0u;
+    if (g.sort_tmp) NBMI_HIP_CHECK(nbmi::radix_error_word(g.sort_tmp, &sort_err, s->stream));
+    NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
+    if (!sort_err) return 0;
+    NBMI_HIP_CHECK(nbmi::radix_init_temp(g.sort_tmp, s->stream));
+    nbmi::set_error("%s", what);
+    return NBMI_ERR_HIP;
+}
+
 // ---- tracers (section 4.19): what a step enqueues for them; nothing here waits for the device ----
 // Whether the tracers' field comes from k_field_direct's sum: a direct handle, or no bodies at all (a = 0).
 bool tracers_direct(const nbmi_sim *s) { return s->method != NBMI_METHOD_BARNES_HUT || s->n == 0; }
 
 // All tracers through one walk with epilogue `leap` (0 / kLeapClose / kLeapPrime).  Barnes-Hut: on the tree that stands,
-// built with the float64 node rows (step_build); chunk by chunk through the tracers' scratch - keys in the tree's root
-// cube, sort, gather, walk - as nbmi_field_at's chunks go.
+// built with the float64 node rows (step_build); chunk by chunk through the tracers' scratch (probe_order_chunk, walk) as
+// nbmi_field_at's chunks go.
 int enqueue_tracers(nbmi_sim *s, int leap, double dt) {
     auto &t = s->tr;
     hipStream_t st = s->stream;
@@ -5656,15 +5724,8 @@ int enqueue_tracers(nbmi_sim *s, int leap, double dt) {
     for (int64_t b = 0; b < t.m; b += t.rows) {
         const int64_t mc = t.m - b < t.rows ? t.m - b : t.rows;
         double *p = t.p + 3 * b, *v = t.v + 3 * b, *a = t.a ? t.a + 3 * b : nullptr;
-        const bool sort = s->field_sort && mc > 64;
-        if (sort) {
-            if (s->hilbert) k_field_keys<true><<<nblocks(mc), kBlock, 0, st>>>(p, mc, s->info, t.key, t.idx);
-            else k_field_keys<false><<<nblocks(mc), kBlock, 0, st>>>(p, mc, s->info, t.key, t.idx);
-            NBMI_HIP_CHECK(nbmi::radix_sort_pairs_u64(t.sort_tmp, t.sort_bytes, t.key, t.key_s, t.idx, t.order, (size_t)mc,
-                                                      63 - kFieldSortBits, 63, st));
-        }
-        const uint32_t *order = sort ? t.order : nullptr;
-        k_field_gather<<<nblocks(mc), kBlock, 0, st>>>(p, order, mc, t.sx, t.sy, t.sz);
+        const uint32_t *order;
+        if (int rc = probe_order_chunk(s, t, p, mc, &order)) return rc;
         with_bool(quad, [&](auto q) {
             with_int<0, kLeapClose, kLeapPrime>(leap, [&](auto lv) {
                 k_tracer_tree<decltype(q)::value, decltype(lv)::value><<<nblocks(mc), kBlock, 0, st>>>(
@@ -5689,8 +5750,8 @@ int enqueue_tracer_kick_drift(nbmi_sim *s, double dt) {
 
 // [leapfrog] The tracers' acceleration rows exist and hold a = F(p) for the current bodies and tracers.  Barnes-Hut: the
 // priming walk needs a tree of the current positions with the float64 rows, and the step has none at this point (the
-// bodies may not need priming): a build of its own inside a SideBuild, as a query's, so the bodies' next step finds the
-// handle as it would without tracers.
+// bodies may not need priming): a side_tree of its own, as a query's, so the bodies' next step finds the handle as it
+// would without tracers.
 int tracer_leap_prepare(nbmi_sim *s) {
     auto &t = s->tr;
     if (!t.a) {
@@ -5699,19 +5760,8 @@ int tracer_leap_prepare(nbmi_sim *s) {
         t.acc_valid = false;
     }
     if (t.acc_valid) return 0;
-    int rc;
-    if (tracers_direct(s)) {
-        rc = enqueue_tracers(s, kLeapPrime, 0.0);
-    } else {
-        SideBuild side(s);
-        if (side.rc) return side.rc;
-        BuildRequest build;
-        build.aux = false;
-        build.diag_rows = s->multipole == NBMI_MULTIPOLE_QUADRUPOLE ? nullptr : s->diag_pot;
-        rc = enqueue_tree(s, build);
-        if (rc == 0) rc = enqueue_tracers(s, kLeapPrime, 0.0);
-        rc = side.finish(rc, false);
-    }
+    auto prime = [&] { return enqueue_tracers(s, kLeapPrime, 0.0); };
+    const int rc = tracers_direct(s) ? prime() : side_tree(s, false, false, false, true, prime);
     if (rc == 0) t.acc_valid = true;  // (only once everything is enqueued, as the bodies')
     return rc;
 }
@@ -6308,27 +6358,16 @@ int diag_potential(nbmi_sim *s) {
         NBMI_HIP_CHECK(hipGetLastError());
         return 0;
     }
-    if (!s->diag_pot && dev_alloc(s, &s->diag_pot, s->node_capacity + 2)) return NBMI_ERR_HIP;
-    // a capacity error of an earlier step is reported first, as a getter does
-    NBMI_HIP_CHECK(hipStreamSynchronize(st));
-    if (int rc = check_device_error(s)) return rc;
-    SideBuild side(s);  // (no "auto" decision in its build: the wave flags and force_all64 stay the last step's)
-    if (side.rc) return side.rc;
-    BuildRequest build;
-    build.aux = false; build.diag_rows = s->diag_pot;
-    int rc = enqueue_tree(s, build);
-    if (rc == 0) {
+    return side_tree(s, true, false, true, false, [&] {
         with_bool(s->multipole == NBMI_MULTIPOLE_QUADRUPOLE, [&](auto q) {
             k_potential_tree<decltype(q)::value><<<nblocks(n), kBlock, 0, st>>>(
                 s->nodes, s->diag_pot, s->wtab, s->info, s->posm_s, s->perm, s->curbuf, (float)(s->softening * s->softening), n,
                 s->diag_phi, s->diag_cnt, decltype(q)::value ? s->quad_work : nullptr);
         });
-        if (hipGetLastError() != hipSuccess) {
-            nbmi::set_error("k_potential_tree launch failed");
-            rc = NBMI_ERR_HIP;
-        }
-    }
-    return side.finish(rc, true);
+        if (hipGetLastError() == hipSuccess) return 0;
+        nbmi::set_error("k_potential_tree launch failed");
+        return (int)NBMI_ERR_HIP;
+    });
 }
 
 int diag_refuse(nbmi_sim *s, const char *what) {
@@ -6816,6 +6855,20 @@ int nbmi_deposit(nbmi_sim *s, const double *lo, const double *hi, const int32_t 
 }
 
 namespace {
+// the first row of an (m, 3) array with a value that is not finite or above `limit` in magnitude; -1: none, and *pmax
+// (if asked for) is raised to the largest magnitude.  (The maximum stays in a register: nbmi_field_at scans 3 m values
+// on every call.)
+int64_t first_bad_row(const double *a, int64_t m, double limit, double *pmax) {
+    double mx = 0.0;
+    for (int64_t i = 0; i < 3 * m; i++) {
+        const double v = fabs(a[i]);
+        if (!(v <= limit)) return i / 3;  // (a NaN fails the comparison too)
+        mx = v > mx ? v : mx;
+    }
+    if (pmax && mx > *pmax) *pmax = mx;
+    return -1;
+}
+
 // nbmi_field_at's scratch for chunks of `need` points (nbmi_sim::field): rows double up to the chunk.  Nothing enqueued
 // uses the old arrays - the call that filled them has waited for its copies.
 int field_alloc(nbmi_sim *s, int64_t need) {
@@ -6824,19 +6877,13 @@ int field_alloc(nbmi_sim *s, int64_t need) {
     int64_t rows = f.rows ? f.rows : kFieldMinRows;
     while (rows < need) rows *= 2;
     if (rows > kFieldChunk) rows = kFieldChunk;
-    dev_free(s, &f.pts); dev_free(s, &f.sx); dev_free(s, &f.sy); dev_free(s, &f.sz); dev_free(s, &f.acc); dev_free(s, &f.phi);
-    dev_free(s, &f.cnt); dev_free(s, &f.key); dev_free(s, &f.key_s); dev_free(s, &f.idx); dev_free(s, &f.order);
-    dev_free(s, &f.sort_tmp);
-    f.rows = 0;
+    probe_free(s, f);
+    dev_free(s, &f.pts); dev_free(s, &f.acc); dev_free(s, &f.phi); dev_free(s, &f.cnt);
     const size_t r = (size_t)rows;
-    f.sort_bytes = nbmi::radix_temp_bytes_u64(r, kFieldSortBits);
-    if (dev_alloc(s, &f.pts, 3 * r) || dev_alloc(s, &f.sx, r) || dev_alloc(s, &f.sy, r) || dev_alloc(s, &f.sz, r) ||
-        dev_alloc(s, &f.acc, 3 * r) || dev_alloc(s, &f.phi, r) || dev_alloc(s, &f.cnt, r) || dev_alloc(s, &f.key, r) ||
-        dev_alloc(s, &f.key_s, r) || dev_alloc(s, &f.idx, r) || dev_alloc(s, &f.order, r) ||
-        dev_alloc(s, &f.sort_tmp, f.sort_bytes + 256) || (!f.wtab && dev_alloc(s, &f.wtab, 1)))
+    if (dev_alloc(s, &f.pts, 3 * r) || dev_alloc(s, &f.acc, 3 * r) || dev_alloc(s, &f.phi, r) || dev_alloc(s, &f.cnt, r))
         return NBMI_ERR_HIP;
-    NBMI_HIP_CHECK(nbmi::radix_init_temp(f.sort_tmp, s->stream));
-    f.rows = rows;
+    if (s->method == NBMI_METHOD_BARNES_HUT) return probe_alloc(s, f, rows);
+    f.rows = rows;  // (a direct handle walks nothing)
     return 0;
 }
 
@@ -6854,16 +6901,8 @@ int field_chunks(nbmi_sim *s, int64_t m, const double *pts, double pmax, double 
             k_field_direct<<<nblocks(mc), kBlock, 0, st>>>(s->buf[s->curbuf], s->n, s->G, eps2, f.pts, mc, acc ? f.acc : nullptr,
                                                            phi ? f.phi : nullptr, terms ? f.cnt : nullptr);
         } else {
-            // (a chunk of one wave is walked as it came: there is no neighbour to choose)
-            const bool sort = s->field_sort && mc > 64;
-            if (sort) {
-                if (s->hilbert) k_field_keys<true><<<nblocks(mc), kBlock, 0, st>>>(f.pts, mc, s->info, f.key, f.idx);
-                else k_field_keys<false><<<nblocks(mc), kBlock, 0, st>>>(f.pts, mc, s->info, f.key, f.idx);
-                NBMI_HIP_CHECK(nbmi::radix_sort_pairs_u64(f.sort_tmp, f.sort_bytes, f.key, f.key_s, f.idx, f.order, (size_t)mc,
-                                                          63 - kFieldSortBits, 63, st));
-            }
-            const uint32_t *order = sort ? f.order : nullptr;
-            k_field_gather<<<nblocks(mc), kBlock, 0, st>>>(f.pts, order, mc, f.sx, f.sy, f.sz);
+            const uint32_t *order;
+            if (int rc = probe_order_chunk(s, f, f.pts, mc, &order)) return rc;
             with_bool(s->multipole == NBMI_MULTIPOLE_QUADRUPOLE, [&](auto q) {
                 k_field_tree<decltype(q)::value><<<nblocks(mc), kBlock, 0, st>>>(
                     s->nodes, s->diag_pot, f.wtab, s->info, f.sx, f.sy, f.sz, order, mc, (float)eps2, s->softening, pmax,
@@ -6880,17 +6919,7 @@ int field_chunks(nbmi_sim *s, int64_t m, const double *pts, double pmax, double 
         if (terms) NBMI_HIP_CHECK(hipMemcpyAsync(terms + b, f.cnt, (size_t)mc * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         NBMI_HIP_CHECK(hipStreamSynchronize(st));  // the next chunk overwrites the scratch
     }
-    if (tree) {
-        unsigned sort_err = 0u;
-        NBMI_HIP_CHECK(nbmi::radix_error_word(f.sort_tmp, &sort_err, st));
-        NBMI_HIP_CHECK(hipStreamSynchronize(st));
-        if (sort_err) {
-            NBMI_HIP_CHECK(nbmi::radix_init_temp(f.sort_tmp, st));
-            nbmi::set_error("nbmi_field_at: the sort of the points failed");
-            return NBMI_ERR_HIP;
-        }
-    }
-    return 0;
+    return tree ? probe_sort_error(s, f, "nbmi_field_at: the sort of the points failed") : 0;
 }
 }  // namespace
 
@@ -6904,14 +6933,12 @@ int nbmi_field_at(nbmi_sim *s, int64_t m, const double *points_xyz, double *acc_
     if (m == 0) return 0;
     if (int rc = require_out(points_xyz, "nbmi_field_at: null points_xyz")) return rc;
     double pmax = 0.0;
-    for (int64_t i = 0; i < 3 * m; i++) {
-        const double v = fabs(points_xyz[i]);
-        if (!(v <= 1e18)) {  // (a NaN fails the comparison too)
-            nbmi::set_error("nbmi_field_at: points_xyz row %lld holds %g: coordinates must be finite and at most 1e18 in magnitude",
-                            (long long)(i / 3), points_xyz[i]);
-            return NBMI_ERR_ARG;
-        }
-        pmax = v > pmax ? v : pmax;
+    const int64_t bad = first_bad_row(points_xyz, m, 1e18, &pmax);
+    if (bad >= 0) {
+        const double *r = points_xyz + 3 * bad;
+        nbmi::set_error("nbmi_field_at: points_xyz row %lld holds %g: coordinates must be finite and at most 1e18 in magnitude",
+                        (long long)bad, !(fabs(r[0]) <= 1e18) ? r[0] : !(fabs(r[1]) <= 1e18) ? r[1] : r[2]);
+        return NBMI_ERR_ARG;
     }
     const int64_t n = s->n;
     if (n == 0) {
@@ -6923,31 +6950,9 @@ int nbmi_field_at(nbmi_sim *s, int64_t m, const double *points_xyz, double *acc_
         return 0;
     }
     if (!acc_xyz && !phi && !terms) return 0;
-    hipStream_t st = s->stream;
-    if (s->method != NBMI_METHOD_BARNES_HUT) {
-        if (int rc = field_alloc(s, m)) return rc;
-        return field_chunks(s, m, points_xyz, pmax, acc_xyz, phi, terms);
-    }
-    if (!s->diag_pot && dev_alloc(s, &s->diag_pot, s->node_capacity + 2)) return NBMI_ERR_HIP;
-    // a capacity error of an earlier step is reported first, as a getter does
-    NBMI_HIP_CHECK(hipStreamSynchronize(st));
-    if (int rc = check_device_error(s)) return rc;
     if (int rc = field_alloc(s, m)) return rc;
-    {
-        WalkTable t = walk_table(s);  // buffer 0 = the probes: see k_field_tree
-        t.buf[0].x = s->field.sx; t.buf[0].y = s->field.sy; t.buf[0].z = s->field.sz;
-        NBMI_HIP_CHECK(hipMemcpyAsync(s->field.wtab, &t, sizeof(t), hipMemcpyHostToDevice, st));
-        NBMI_HIP_CHECK(hipStreamSynchronize(st));  // `t` is a stack object
-    }
-    SideBuild side(s);  // (no "auto" decision in its build: the wave flags and force_all64 stay the last step's)
-    if (side.rc) return side.rc;
-    BuildRequest build;
-    build.aux = false; build.diag_rows = s->diag_pot;
-    int rc = enqueue_tree(s, build);
-    // the build's own capacity error before a point is walked: nothing is copied out of a walk that did not run
-    if (rc == 0) rc = check_device_error(s);
-    if (rc == 0) rc = field_chunks(s, m, points_xyz, pmax, acc_xyz, phi, terms);
-    return side.finish(rc, false);
+    auto chunks = [&] { return field_chunks(s, m, points_xyz, pmax, acc_xyz, phi, terms); };
+    return s->method != NBMI_METHOD_BARNES_HUT ? chunks() : side_tree(s, true, true, false, false, chunks);
 }
 
 namespace {
@@ -6956,22 +6961,10 @@ int tracers_release(nbmi_sim *s) {
     auto &t = s->tr;
     NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
     dev_free(s, &t.p); dev_free(s, &t.v); dev_free(s, &t.a); dev_free(s, &t.pmax);
-    dev_free(s, &t.sx); dev_free(s, &t.sy); dev_free(s, &t.sz); dev_free(s, &t.key); dev_free(s, &t.key_s);
-    dev_free(s, &t.idx); dev_free(s, &t.order); dev_free(s, &t.sort_tmp); dev_free(s, &t.wtab);
-    t.m = t.rows = 0;
-    t.sort_bytes = 0;
+    probe_free(s, t);
+    t.m = 0;
     t.acc_valid = false;
     return 0;
-}
-
-// the first row of an (m, 3) array with a value that is not finite or above `limit` in magnitude; -1: none
-int64_t first_bad_row(const double *a, int64_t m, double limit, double *pmax) {
-    for (int64_t i = 0; i < 3 * m; i++) {
-        const double v = fabs(a[i]);
-        if (!(v <= limit)) return i / 3;  // (a NaN fails the comparison too)
-        if (pmax && v > *pmax) *pmax = v;
-    }
-    return -1;
 }
 }  // namespace
 
@@ -7005,38 +6998,24 @@ int nbmi_set_tracers(nbmi_sim *s, int64_t m, const double *positions_xyz, const 
     hipStream_t st = s->stream;
     const size_t bytes = (size_t)m * 3 * sizeof(double);
     const bool tree = !tracers_direct(s);
-    const size_t r = (size_t)(m < kFieldChunk ? m : kFieldChunk);
-    bool bad = dev_alloc(s, &t.p, 3 * (size_t)m) || dev_alloc(s, &t.v, 3 * (size_t)m) || dev_alloc(s, &t.pmax, 1);
-    if (!bad && tree) {
-        t.sort_bytes = nbmi::radix_temp_bytes_u64(r, kFieldSortBits);
-        bad = dev_alloc(s, &t.sx, r) || dev_alloc(s, &t.sy, r) || dev_alloc(s, &t.sz, r) || dev_alloc(s, &t.key, r) ||
-              dev_alloc(s, &t.key_s, r) || dev_alloc(s, &t.idx, r) || dev_alloc(s, &t.order, r) ||
-              dev_alloc(s, &t.sort_tmp, t.sort_bytes + 256) || dev_alloc(s, &t.wtab, 1) ||
-              (!s->diag_pot && dev_alloc(s, &s->diag_pot, s->node_capacity + 2));
-    }
-    if (bad) {
-        tracers_release(s);
-        return NBMI_ERR_HIP;
-    }
-    WalkTable wt = walk_table(s);  // buffer 0 = the probes: see k_field_tree
-    wt.buf[0].x = t.sx; wt.buf[0].y = t.sy; wt.buf[0].z = t.sz;
-    int rc = 0;
+    int rc = dev_alloc(s, &t.p, 3 * (size_t)m) || dev_alloc(s, &t.v, 3 * (size_t)m) || dev_alloc(s, &t.pmax, 1) ||
+                     (tree && !s->diag_pot && dev_alloc(s, &s->diag_pot, s->node_capacity + 2))  // (the steps' builds write it)
+                 ? NBMI_ERR_HIP
+                 : 0;
+    if (rc == 0 && tree) rc = probe_alloc(s, t, m < kFieldChunk ? m : kFieldChunk);
     auto ok = [&](hipError_t e) { if (e != hipSuccess && rc == 0) { nbmi::set_error("nbmi_set_tracers: %s", hipGetErrorString(e)); rc = NBMI_ERR_HIP; } };
-    ok(hipMemcpyAsync(t.p, positions_xyz, bytes, hipMemcpyHostToDevice, st));
-    if (velocities_xyz) ok(hipMemcpyAsync(t.v, velocities_xyz, bytes, hipMemcpyHostToDevice, st));
-    else ok(hipMemsetAsync(t.v, 0, bytes, st));
-    ok(hipMemcpyAsync(t.pmax, &pmax, sizeof(double), hipMemcpyHostToDevice, st));  // (the bit pattern of the non-negative double)
-    if (tree) {
-        ok(hipMemcpyAsync(t.wtab, &wt, sizeof(wt), hipMemcpyHostToDevice, st));
-        ok(nbmi::radix_init_temp(t.sort_tmp, st));
+    if (rc == 0) {
+        ok(hipMemcpyAsync(t.p, positions_xyz, bytes, hipMemcpyHostToDevice, st));
+        if (velocities_xyz) ok(hipMemcpyAsync(t.v, velocities_xyz, bytes, hipMemcpyHostToDevice, st));
+        else ok(hipMemsetAsync(t.v, 0, bytes, st));
+        ok(hipMemcpyAsync(t.pmax, &pmax, sizeof(double), hipMemcpyHostToDevice, st));  // (the bit pattern of the non-negative double)
+        ok(hipStreamSynchronize(st));  // the sources are the caller's arrays and a stack object
     }
-    ok(hipStreamSynchronize(st));  // the sources are the caller's arrays and stack objects
     if (rc) {
         tracers_release(s);
         return rc;
     }
     t.m = m;
-    t.rows = (int64_t)r;
     return 0;
 }
 
@@ -7050,14 +7029,8 @@ int nbmi_get_tracers_f64(nbmi_sim *s, double *positions_xyz, double *velocities_
     const size_t bytes = (size_t)t.m * 3 * sizeof(double);
     if (positions_xyz) NBMI_HIP_CHECK(hipMemcpyAsync(positions_xyz, t.p, bytes, hipMemcpyDeviceToHost, st));
     if (velocities_xyz) NBMI_HIP_CHECK(hipMemcpyAsync(velocities_xyz, t.v, bytes, hipMemcpyDeviceToHost, st));
-    unsigned sort_err = 0u;
-    if (t.sort_tmp) NBMI_HIP_CHECK(nbmi::radix_error_word(t.sort_tmp, &sort_err, st));
-    NBMI_HIP_CHECK(hipStreamSynchronize(st));
-    if (sort_err) {
-        NBMI_HIP_CHECK(nbmi::radix_init_temp(t.sort_tmp, st));
-        nbmi::set_error("nbmi_get_tracers_f64: the sort of the tracers failed; the steps since the last synchronisation are invalid");
-        return NBMI_ERR_HIP;
-    }
+    if (int rc = probe_sort_error(s, t, "nbmi_get_tracers_f64: the sort of the tracers failed; the steps since the last synchronisation are invalid"))
+        return rc;
     return check_device_error(s);
 }
 
