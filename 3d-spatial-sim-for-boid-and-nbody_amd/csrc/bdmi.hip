@@ -772,6 +772,17 @@ int slab_check(bdmi_flock *f, const char *what) {
     if (!f->slab) { nbmi::set_error("%s: not a slab-mode handle (bdmi_create_slab)", what); return -1; }
     return 0;
 }
+// The calls that address their buffers by A.id: a slab handle holds GLOBAL ids there (and -1 - id for a ghost), its row
+// count changes with every exchange, and it holds only a part of the flock, so a caller-order array has no meaning.
+int whole_flock_check(bdmi_flock *f, const char *what) {
+    if (int rc = check(f)) return rc;
+    if (f->slab) {
+        nbmi::set_error("%s: refused on a slab handle (bdmi_create_slab), whose rows carry global ids and ghosts; read a "
+                        "slab with bdmi_slab_get", what);
+        return -1;
+    }
+    return 0;
+}
 // drop the ghosts: owned rows to the front, in row order
 int slab_compact_owned(bdmi_flock *f, int64_t *n_owned) {
     uint32_t total = 0;
@@ -870,6 +881,16 @@ int bdmi_slab_get(bdmi_flock *f, double *rows10, int64_t capacity, int64_t *coun
 int bdmi_step(bdmi_flock *f, double dt, int substeps) {
     if (int rc = check(f)) return rc;
     if (substeps < 0) { nbmi::set_error("bdmi_step: substeps < 0"); return -1; }
+    // A slab handle knows only that its neighbours are at least two cells wide (as it is itself).  The speed clamp
+    // bounds a step's displacement by max_speed * |dt|; below two cells a boid that leaves its slab lands inside the
+    // adjacent one, which got a copy of it at the exchange.  Beyond that it could land in a slab that never saw it:
+    // demoted here, a ghost there, and dropped by every rank at the next export.
+    if (f->slab && !(f->params[3] * fabs(dt) < 2.0 * f->params[5])) {
+        nbmi::set_error("bdmi_step: on a slab handle max_speed * |dt| = %g must stay below two cells = 2 * "
+                        "perception_radius = %g (a boid may only ever move to the adjacent slab)",
+                        f->params[3] * fabs(dt), 2.0 * f->params[5]);
+        return -1;
+    }
     if (f->n == 0) return 0;
     const FlockP P = make_params(f, dt);
     for (int k = 0; k < substeps; k++) {
@@ -911,7 +932,7 @@ int bdmi_sync(bdmi_flock *f) {
 }
 
 int bdmi_get_state(bdmi_flock *f, double *pos, double *vel, double *col) {
-    if (int rc = check(f)) return rc;
+    if (int rc = whole_flock_check(f, "bdmi_get_state")) return rc;
     const int64_t n = f->n;
     if (n == 0) return 0;
     double *dp = f->stage, *dv = dp + 3 * n, *dc = dv + 3 * n;
@@ -933,7 +954,7 @@ int bdmi_get_state(bdmi_flock *f, double *pos, double *vel, double *col) {
 }
 
 int bdmi_set_state(bdmi_flock *f, const double *pos, const double *vel, const double *col) {
-    if (int rc = check(f)) return rc;
+    if (int rc = whole_flock_check(f, "bdmi_set_state")) return rc;
     const int64_t n = f->n;
     if (n == 0) return 0;
     double *dp = f->stage, *dv = dp + 3 * n, *dc = dv + 3 * n;
@@ -947,7 +968,7 @@ int bdmi_set_state(bdmi_flock *f, const double *pos, const double *vel, const do
 }
 
 int bdmi_get_cell_indices(bdmi_flock *f, int32_t *out) {
-    if (int rc = check(f)) return rc;
+    if (int rc = whole_flock_check(f, "bdmi_get_cell_indices")) return rc;
     const int64_t n = f->n;
     if (n == 0) return 0;
     if (!out) { nbmi::set_error("null output"); return -1; }
@@ -960,7 +981,7 @@ int bdmi_get_cell_indices(bdmi_flock *f, int32_t *out) {
 }
 
 int bdmi_get_forces(bdmi_flock *f, double *sep, double *ali, double *coh, double *avg) {
-    if (int rc = check(f)) return rc;
+    if (int rc = whole_flock_check(f, "bdmi_get_forces")) return rc;
     const int64_t n = f->n;
     if (n == 0) return 0;
     if (!sep || !ali || !coh || !avg) { nbmi::set_error("null output"); return -1; }
@@ -1060,7 +1081,7 @@ struct EmitCones {
 int bdmi_visible_vertices(bdmi_flock *f, const double *cam12, double tan_h, double tan_v, double fog_end,
                           double cone_length, double cone_radius, float *out_vertices, float *out_colors,
                           int64_t capacity_boids, int64_t *count) {
-    if (int rc = check(f)) return rc;
+    if (int rc = whole_flock_check(f, "bdmi_visible_vertices")) return rc;
     if (!cam12 || !count || capacity_boids < 0 || (capacity_boids > 0 && (!out_vertices || !out_colors))) {
         nbmi::set_error("bdmi_visible_vertices: null argument");
         return -1;

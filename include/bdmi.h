@@ -60,8 +60,12 @@ int bdmi_get_timers(bdmi_flock *f, double *ms3, int64_t *count, int reset);
  * A rank owns the boids with x_lo <= x < x_hi (a whole number of cell planes, at least two cells wide); the
  * neighbour sweep needs the boids within one cell (= the perception radius, flock.py:479) on the other side
  * of each face.  The handle holds the owned boids plus this step's ghosts (read-only copies of the
- * neighbours' boundary boids).  A boid moves at most max_speed * dt << one cell per step, so it can only
- * ever change to an adjacent slab, and ONE exchange per step carries migrants and halo alike:
+ * neighbours' boundary boids).  The speed clamp bounds a step's displacement by max_speed * |dt|, and a handle knows
+ * of its neighbours only that they are at least two cells wide, so bdmi_step on a slab handle REQUIRES
+ * max_speed * |dt| < 2 * perception_radius (-1 otherwise, nothing is run): then a boid that leaves its slab lands
+ * inside the adjacent one, and ONE exchange per step carries migrants and halo alike.  (Beyond that a boid could land
+ * in a slab that never received it, and no rank would own it after the next export.  The halo does not depend on
+ * the step: it is taken from the positions at the start of the step.  Ordinary handles are not limited.)
  *
  *   bdmi_slab_export(h, left, &nl, right, &nr)   drop last step's ghosts; rows {p, v, c, global id} (10 doubles)
  *                                                of the owned boids with x < x_lo + cell -> `left`, with
@@ -73,7 +77,15 @@ int bdmi_get_timers(bdmi_flock *f, double *ms3, int64_t *count, int reset);
  *                                                neighbours
  *
  * The candidate set of every owned boid equals the single-GPU one, so forces agree to float64 summation
- * order.  bdmi_slab_get returns the owned rows (10 doubles each, any order). */
+ * order.  bdmi_slab_get returns the owned rows (10 doubles each, any order): at most `capacity` rows are copied,
+ * *count is the full number.  bdmi_slab_import beyond the handle's capacity returns -4 and changes nothing.
+ * bdmi_slab_count compacts the handle to its owned rows (this step's ghosts are dropped) and returns their number.
+ *
+ * A slab handle keeps GLOBAL ids (and -1 - id for a ghost), a part of the flock, and a row count that changes with
+ * every exchange, so the calls that address caller-order arrays by id - bdmi_get_state, bdmi_set_state,
+ * bdmi_get_cell_indices, bdmi_get_forces, bdmi_visible_vertices (and bdmi_render_flock) - refuse it with -1 before
+ * anything is launched or written; read a slab with bdmi_slab_get.  bdmi_grid_info, the timers, bdmi_sync and
+ * bdmi_step work on both kinds of handle. */
 bdmi_flock *bdmi_create_slab(int64_t n, const double *positions_xyz, const double *velocities_xyz, const double *colors_rgb,
                              const int32_t *global_ids, int64_t capacity, const double *params11, double x_lo, double x_hi,
                              int has_left_neighbour, int has_right_neighbour, int device);
