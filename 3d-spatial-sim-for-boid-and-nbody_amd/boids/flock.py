@@ -156,6 +156,51 @@ class Flock:
                    "bdmi_get_timers")
         return dict(sort_ms=ms[0], table_ms=ms[1], sweep_ms=ms[2], steps=int(cnt.value))
 
+    # ---- flock analysis (include/bdmi.h: flock finder, catalogue, order parameters, neighbour statistics) ----
+    def _link(self, link):
+        return float(self.perception_radius if link is None else link)
+
+    def flocks(self, link=None):
+        """The flocks of the current state: boids no further apart than ``link`` (default: the perception radius) are
+        linked, a flock is a connected component.  dict of ``labels`` (int32 (N,), the smallest boid index of each
+        boid's flock), ``n_flocks``, ``links`` (linked pairs) and ``evals`` (distances evaluated)."""
+        labels = np.empty(self.num_boids, dtype=np.int32)
+        nf, links, evals = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        _nat.check_arg(self._lib.bdmi_flocks(self._h, self._link(link), _nat.ptr(labels), C.addressof(nf),
+                                             C.addressof(links), C.addressof(evals)), "bdmi_flocks")
+        return dict(labels=labels, n_flocks=int(nf.value), links=int(links.value), evals=int(evals.value))
+
+    def flock_catalogue(self, link=None, min_members=1, capacity=64):
+        """The flocks with at least ``min_members`` members, largest first (ties by label): dict of ``count`` (all
+        qualifying flocks), ``label``, ``members`` and ``rows`` ((rows, 16) float64, see boids.analysis.row_dict) of
+        the first ``capacity`` of them."""
+        cap = int(capacity)
+        label = np.empty(max(cap, 0), dtype=np.int32)
+        members = np.empty(max(cap, 0), dtype=np.int64)
+        rows = np.empty((max(cap, 0), 16), dtype=np.float64)
+        cnt = C.c_int64(0)
+        _nat.check_arg(self._lib.bdmi_flock_catalogue(self._h, self._link(link), int(min_members), cap, _nat.ptr(label),
+                                                      _nat.ptr(members), _nat.ptr(rows), C.addressof(cnt)),
+                       "bdmi_flock_catalogue")
+        k = min(int(cnt.value), cap)
+        return dict(count=int(cnt.value), label=label[:k], members=members[:k], rows=rows[:k])
+
+    def diagnostics(self):
+        """The row of the whole flock (float64 (16,)): centre, mean velocity, polarisation, mean speed, milling, box."""
+        row = np.empty(16, dtype=np.float64)
+        _nat.check_arg(self._lib.bdmi_diagnostics(self._h, _nat.ptr(row)), "bdmi_diagnostics")
+        return row
+
+    def neighbour_stats(self, radius=None):
+        """Per boid: ``count`` of the others within ``radius`` (default: the perception radius) and ``nn_d2``, the
+        squared distance of the nearest of them (inf without one); plus ``evals``."""
+        count = np.empty(self.num_boids, dtype=np.int32)
+        nn = np.empty(self.num_boids, dtype=np.float64)
+        evals = C.c_int64(0)
+        _nat.check_arg(self._lib.bdmi_neighbour_stats(self._h, self._link(radius), _nat.ptr(count), _nat.ptr(nn),
+                                                      C.addressof(evals)), "bdmi_neighbour_stats")
+        return dict(count=count, nn_d2=nn, evals=int(evals.value))
+
     # ---- render-side reduction (reference :680-728) on the device -----------------------------
     def frustum_tangents(self, fov=None, aspect=None):
         """(tan_h, tan_v) of the visibility test for a vertical field of view in degrees (reference :737-739 and

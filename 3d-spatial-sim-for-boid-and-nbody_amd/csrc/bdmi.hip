@@ -23,6 +23,7 @@
 #include "../../include/bdmi.h"
 #include "common.h"
 #include "visible.h"
+#include "unionfind.h"
 
 namespace {
 
@@ -533,6 +534,354 @@ __global__ __launch_bounds__(kBlock) void k_set_ids(const int32_t *__restrict__ 
     if (i < n) dst[i] = ids[i];
 }
 
+// ---- flock analysis: bdmi_flocks / bdmi_flock_catalogue / bdmi_diagnostics / bdmi_neighbour_stats ----------------
+// (include/bdmi.h has the definitions, DESIGN.md section 4.21 the measurements.)  All four work on the grid that
+// enqueue_grid builds for the current positions: B = the boids in cell order, occ / cell_start = the compact table.
+struct FlockStats {
+    int32_t *parent = nullptr, *root = nullptr, *minid = nullptr, *cnt = nullptr;  // union-find over ranks; per root
+    int32_t *lcnt = nullptr;                                 // members of the flock with this label (at [label])
+    uint32_t *lab = nullptr, *lab_s = nullptr;               // label of rank r; the same, sorted
+    uint32_t *rank = nullptr, *rank_s = nullptr;             // 0 .. n-1; the ranks in the order a stable sort by label leaves
+    uint32_t *qkey = nullptr, *qkey_s = nullptr, *qval = nullptr, *qval_s = nullptr;  // qualifying heads: n - members, position
+    unsigned long long *counters = nullptr;                  // links, evals, flocks, neighbour evals
+    // catalogue rows, grown on demand: chunk offsets, per-chunk partials of the two passes, the rows themselves
+    int32_t *chunk_off = nullptr;
+    double *part = nullptr, *rows16 = nullptr;
+    int32_t *row_label = nullptr;
+    int64_t *row_members = nullptr;
+    int64_t rows_cap = 0, chunks_cap = 0;
+};
+
+// The candidates of one (y, z) row of cells [c_lo, c_hi]: one contiguous run of ranks, found with the occupancy words as
+// k_flock finds it (its loop for any `range`; with range 1 a row is at most two words).
+__device__ __forceinline__ bool fs_row_run(const uint2 *__restrict__ occ, const int32_t *__restrict__ cell_start, int64_t c_lo,
+                                           int64_t c_hi, int32_t &q_begin, int32_t &q_end) {
+    int first = -1, last = -1;  // bit positions inside their words
+    uint2 first_w = make_uint2(0u, 0u), last_w = make_uint2(0u, 0u);
+    for (int64_t w = c_lo >> 5; w <= (c_hi >> 5); w++) {
+        const uint2 e = occ[w];
+        uint32_t bits = e.x;
+        if (w == (c_lo >> 5)) bits &= ~0u << (c_lo & 31);
+        if (w == (c_hi >> 5)) bits &= ~0u >> (31 - (c_hi & 31));
+        if (bits) {
+            if (first < 0) { first = __ffs(bits) - 1; first_w = e; }
+            last = 31 - __clz(bits);
+            last_w = e;
+        }
+    }
+    if (first < 0) return false;  // the whole row is empty: no table read
+    const uint32_t k_lo = first_w.y + __popc(first_w.x & ((1u << first) - 1u));
+    const uint32_t k_hi = last_w.y + __popc(last_w.x & ((1u << last) - 1u)) + 1u;
+    q_begin = cell_start[k_lo];
+    q_end = cell_start[k_hi];
+    return true;
+}
+// f(q_begin, q_end) for the non-empty rows around the boid at p, in row order ((2 range + 1)^2 rows: nine)
+template <class F>
+__device__ __forceinline__ void fs_for_each_run(const double4 &p, const GridP &g, const uint2 *__restrict__ occ,
+                                                const int32_t *__restrict__ cell_start, F f) {
+    const int cx = cell_coord(p.x, g), cy = cell_coord(p.y, g), cz = cell_coord(p.z, g);
+    const int x_lo = cx - g.range < 0 ? 0 : cx - g.range;
+    const int x_hi = cx + g.range > g.dim - 1 ? g.dim - 1 : cx + g.range;
+    for (int dcz = -g.range; dcz <= g.range; dcz++) {
+        const int ncz = cz + dcz;
+        if (ncz < 0 || ncz >= g.dim) continue;
+        for (int dcy = -g.range; dcy <= g.range; dcy++) {
+            const int ncy = cy + dcy;
+            if (ncy < 0 || ncy >= g.dim) continue;
+            const int64_t row = (int64_t)ncy * g.dim + (int64_t)ncz * g.dim * g.dim;
+            int32_t qb = 0, qe = 0;
+            if (fs_row_run(occ, cell_start, row + x_lo, row + x_hi, qb, qe)) f(qb, qe);
+        }
+    }
+}
+// d2(i, j) of the header: three products, two sums, symmetric in its arguments
+__device__ __forceinline__ double fs_d2(const double4 &a, const double4 &b) {
+    const double dx = b.x - a.x, dy = b.y - a.y, dz = b.z - a.z;
+    return (dx * dx + dy * dy) + dz * dz;
+}
+// one atomic per wave; every lane of the wave calls it
+__device__ __forceinline__ void fs_wave_add(unsigned long long *dst, long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if ((threadIdx.x & 63) == 0 && v != 0ll)
+        (void)__hip_atomic_fetch_add(dst, (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ __launch_bounds__(kBlock) void k_fs_init(int64_t n, int32_t *__restrict__ parent, int32_t *__restrict__ minid,
+                                                    int32_t *__restrict__ cnt, uint32_t *__restrict__ rank) {
+    const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (r >= n) return;
+    parent[r] = (int32_t)r;
+    minid[r] = INT32_MAX;
+    cnt[r] = 0;
+    rank[r] = (uint32_t)r;
+}
+// The link kernel: one lane per rank r takes the candidates q < r of its nine rows, so every candidate pair is evaluated
+// exactly once (by its higher rank) and `links` is the exact number of linked pairs - a pair is NOT skipped because its
+// boids are in one set already.  A run of any length is walked in place: there are no 16-bit notes here.  Every access
+// to parent[] goes through unionfind.h (agent-scope relaxed atomics, invariants (a)-(d)); no loop waits on another thread.
+__global__ __launch_bounds__(kBlock) void k_fs_link(const double4 *__restrict__ pos, const uint2 *__restrict__ occ,
+                                                    const int32_t *__restrict__ cell_start, int64_t n, GridP g, double b2,
+                                                    int32_t *parent, unsigned long long *counters) {
+    const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    long long links = 0, evals = 0;
+    if (r < n) {
+        const double4 pi = pos[r];
+        int mine = (int)r;  // an ancestor of r: its own rank at first, then the root the last unite came back with
+        fs_for_each_run(pi, g, occ, cell_start, [&](int32_t qb, int32_t qe) {
+            const int32_t e = qe < (int32_t)r ? qe : (int32_t)r;
+            for (int32_t q = qb; q < e; q++) {
+                const double d2 = fs_d2(pi, pos[q]);
+                evals++;
+                if (d2 <= b2) {
+                    links++;
+                    mine = fof_unite(parent, mine, q);
+                }
+            }
+        });
+    }
+    fs_wave_add(counters + 0, links);
+    fs_wave_add(counters + 1, evals);
+}
+// Behind the kernel boundary parent[] is final and read plainly: root[r], minid[root] = the smallest caller index and
+// cnt[root] = the members below it (integer atomics: order independent).  Ranks next to each other mostly share their
+// root: the lanes that share the root of the first lane left go in as one (twice), the rest on their own.
+__global__ __launch_bounds__(kBlock) void k_fs_flatten(int64_t n, const int32_t *__restrict__ parent,
+                                                       const int32_t *__restrict__ id, int32_t *__restrict__ root,
+                                                       int32_t *__restrict__ minid, int32_t *__restrict__ cnt) {
+    const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const bool valid = r < n;
+    const int lane = threadIdx.x & 63;
+    int f = -1, own = INT32_MAX;
+    if (valid) {
+        f = (int)r;
+        for (int p = parent[f]; p != f; p = parent[f]) f = p;
+        root[r] = f;
+        own = id[r];
+    }
+    unsigned long long todo = __builtin_amdgcn_ballot_w64(valid);
+    for (int round = 0; round < 2 && todo != 0ull; round++) {
+        const int leader = __builtin_amdgcn_readfirstlane(__ffsll((long long)todo) - 1);
+        const int f0 = __builtin_amdgcn_readlane(f, leader);
+        const bool with = ((todo >> lane) & 1ull) != 0ull && f == f0;
+        const unsigned long long same = __builtin_amdgcn_ballot_w64(with);
+        int least = with ? own : INT32_MAX;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const int other = __shfl_xor(least, o);
+            least = other < least ? other : least;
+        }
+        if (lane == leader) {
+            atomicMin(&minid[f0], least);
+            atomicAdd(&cnt[f0], (int)__popcll(same));
+        }
+        todo &= ~same;
+    }
+    if ((todo >> lane) & 1ull) {
+        atomicMin(&minid[f], own);
+        atomicAdd(&cnt[f], 1);
+    }
+}
+// label of every rank, of every boid in the caller's order, the members per label, and the number of roots
+__global__ __launch_bounds__(kBlock) void k_fs_labels(int64_t n, const int32_t *__restrict__ root,
+                                                      const int32_t *__restrict__ minid, const int32_t *__restrict__ cnt,
+                                                      const int32_t *__restrict__ id, uint32_t *__restrict__ lab,
+                                                      int32_t *__restrict__ lcnt, int32_t *__restrict__ labels,
+                                                      unsigned long long *__restrict__ n_roots) {
+    const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    bool is_root = false;
+    if (r < n) {
+        const int32_t f = root[r], l = minid[f];
+        is_root = f == (int32_t)r;
+        lab[r] = (uint32_t)l;
+        labels[id[r]] = l;
+        if (is_root) lcnt[l] = cnt[r];
+    }
+    fs_wave_add(n_roots, is_root ? 1ll : 0ll);
+}
+// The full sweep of the nine rows per boid: count[i] = #{j != i : d2 <= r2}, nn_d2[i] = the least such d2 or +inf.
+// An integer count and a minimum: exact whatever the order.
+__global__ __launch_bounds__(kBlock) void k_fs_neighbours(const double4 *__restrict__ pos, const int32_t *__restrict__ id,
+                                                          const uint2 *__restrict__ occ, const int32_t *__restrict__ cell_start,
+                                                          int64_t n, GridP g, double r2, int32_t *__restrict__ count,
+                                                          double *__restrict__ nn_d2, unsigned long long *evals_out) {
+    const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    long long evals = 0;
+    if (r < n) {
+        const double4 pi = pos[r];
+        int32_t c = 0;
+        double least = INFINITY;
+        fs_for_each_run(pi, g, occ, cell_start, [&](int32_t qb, int32_t qe) {
+            for (int32_t q = qb; q < qe; q++) {
+                if (q == (int32_t)r) continue;
+                const double d2 = fs_d2(pi, pos[q]);
+                evals++;
+                if (d2 <= r2) {
+                    c++;
+                    least = d2 < least ? d2 : least;
+                }
+            }
+        });
+        const int32_t i = id[r];
+        count[i] = c;
+        nn_d2[i] = least;
+    }
+    fs_wave_add(evals_out, evals);
+}
+
+// the heads (first member) of the flocks with at least min_members members, in label order
+struct FsHeadSel {
+    const uint32_t *lab_s;
+    const int32_t *lcnt;
+    int64_t min_members;
+    __device__ unsigned operator()(int64_t first, int64_t n) const {
+        return scan::item_mask(first, n, [&](int64_t h) {
+            return (h == 0 || lab_s[h - 1] != lab_s[h]) && (int64_t)lcnt[lab_s[h]] >= min_members;
+        });
+    }
+};
+struct FsEmitHead {
+    const uint32_t *lab_s;
+    const int32_t *lcnt;
+    int64_t n;
+    uint32_t *qkey, *qval;
+    __device__ void operator()(unsigned m, int64_t first, int64_t first_slot) const {
+        scan::for_each_item(m, first, first_slot, [&](int64_t h, int64_t slot) {
+            qkey[slot] = (uint32_t)(n - (int64_t)lcnt[lab_s[h]]);  // ascending = members descending
+            qval[slot] = (uint32_t)h;
+        });
+    }
+};
+
+// ---- the rows of 16 doubles ------------------------------------------------------------------------------------------
+// Row `row` has the members [head, head + m) of the sorted member list (head = rhead[row], m = n - rkey[row]), member j
+// being the boid of rank rank_s[j] (rank j where rank_s is null: bdmi_diagnostics).  The members are cut into chunks of
+// 4096; chunk_off[row] = the first chunk of the row in the partials, chunk_off[rows] = their number.  One block per
+// chunk: thread t adds the members t, t + 256, .. of the chunk in this order, the 64 lanes of a wave are folded by the
+// butterfly over the distances 32, 16, .. 1, the four waves left to right; k_fs_combine then adds a row's chunks in chunk
+// order.  Nothing here depends on timing: the same state gives the same bits.
+constexpr int kFsChunk = 4096;
+constexpr int kFsVals = 16;  // pass 1: Sp[3], Sv[3], Su[3], Ss, lo[3], hi[3]; pass 2: Sw[3]
+
+__device__ __forceinline__ int fs_row_of(const int32_t *__restrict__ chunk_off, int rows, int b) {
+    int lo = 0, hi = rows;  // chunk_off[lo] <= b < chunk_off[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (chunk_off[mid] <= b) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+// op 0: sum, 1: min, 2: max
+__device__ __forceinline__ double fs_fold(int op, double a, double b) { return op == 0 ? a + b : op == 1 ? (b < a ? b : a) : (b > a ? b : a); }
+template <int K>
+__device__ __forceinline__ void fs_block_fold(double (&v)[K], const int (&op)[K], double *__restrict__ out) {
+    __shared__ double red[K][kBlock / 64];
+#pragma unroll
+    for (int c = 0; c < K; c++) {
+        double x = v[c];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) x = fs_fold(op[c], x, __shfl_xor(x, o));
+        if ((threadIdx.x & 63) == 0) red[c][threadIdx.x >> 6] = x;
+    }
+    __syncthreads();
+    if (threadIdx.x < K) {
+        const int c = threadIdx.x;
+        double x = red[c][0];
+        for (int w = 1; w < kBlock / 64; w++) x = fs_fold(op[c], x, red[c][w]);
+        out[c] = x;
+    }
+}
+// u = v / |v| per component (0 for a boid at rest) and the speed
+__device__ __forceinline__ double fs_heading(const double4 &v, double &ux, double &uy, double &uz) {
+    const double s = sqrt((v.x * v.x + v.y * v.y) + v.z * v.z);
+    ux = uy = uz = 0.0;
+    if (s != 0.0) { ux = v.x / s; uy = v.y / s; uz = v.z / s; }
+    return s;
+}
+template <int kPass>
+__global__ __launch_bounds__(kBlock) void k_fs_chunks(const double4 *__restrict__ pos, const double4 *__restrict__ vel,
+                                                      const uint32_t *__restrict__ rank_s, const uint32_t *__restrict__ rkey,
+                                                      const uint32_t *__restrict__ rhead, int64_t n,
+                                                      const int32_t *__restrict__ chunk_off, int rows,
+                                                      const double *__restrict__ rows16, double *__restrict__ part) {
+    const int row = fs_row_of(chunk_off, rows, (int)blockIdx.x);
+    const int64_t m = n - (int64_t)rkey[row], head = rhead[row];
+    const int64_t first = head + (int64_t)((int)blockIdx.x - chunk_off[row]) * kFsChunk;
+    const int64_t end = first + kFsChunk < head + m ? first + kFsChunk : head + m;
+    double *out = part + (int64_t)blockIdx.x * kFsVals;
+    if (kPass == 1) {
+        double v[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
+        for (int64_t j = first + threadIdx.x; j < end; j += kBlock) {
+            const int64_t r = rank_s ? (int64_t)rank_s[j] : j;
+            const double4 p = pos[r], w = vel[r];
+            double ux, uy, uz;
+            const double s = fs_heading(w, ux, uy, uz);
+            v[0] += p.x; v[1] += p.y; v[2] += p.z;
+            v[3] += w.x; v[4] += w.y; v[5] += w.z;
+            v[6] += ux; v[7] += uy; v[8] += uz;
+            v[9] += s;
+            v[10] = p.x < v[10] ? p.x : v[10]; v[11] = p.y < v[11] ? p.y : v[11]; v[12] = p.z < v[12] ? p.z : v[12];
+            v[13] = p.x > v[13] ? p.x : v[13]; v[14] = p.y > v[14] ? p.y : v[14]; v[15] = p.z > v[15] ? p.z : v[15];
+        }
+        const int op[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 2, 2, 2};
+        fs_block_fold(v, op, out);
+    } else {
+        const double cx = rows16[16 * (int64_t)row + 1], cy = rows16[16 * (int64_t)row + 2], cz = rows16[16 * (int64_t)row + 3];
+        double v[3] = {0, 0, 0};
+        for (int64_t j = first + threadIdx.x; j < end; j += kBlock) {
+            const int64_t r = rank_s ? (int64_t)rank_s[j] : j;
+            const double4 p = pos[r], w = vel[r];
+            double ux, uy, uz;
+            (void)fs_heading(w, ux, uy, uz);
+            double rx = p.x - cx, ry = p.y - cy, rz = p.z - cz;
+            const double rho = sqrt((rx * rx + ry * ry) + rz * rz);
+            if (rho != 0.0) { rx /= rho; ry /= rho; rz /= rho; } else { rx = ry = rz = 0.0; }
+            v[0] += ry * uz - rz * uy;
+            v[1] += rz * ux - rx * uz;
+            v[2] += rx * uy - ry * ux;
+        }
+        const int op[3] = {0, 0, 0};
+        fs_block_fold(v, op, out);
+    }
+}
+// one thread per row: the chunks' partials in chunk order, then the row's fields
+template <int kPass>
+__global__ __launch_bounds__(kBlock) void k_fs_combine(const uint32_t *__restrict__ lab_s, const uint32_t *__restrict__ rkey,
+                                                       const uint32_t *__restrict__ rhead, int64_t n,
+                                                       const int32_t *__restrict__ chunk_off, int rows,
+                                                       const double *__restrict__ part, double *__restrict__ rows16,
+                                                       int32_t *__restrict__ row_label, int64_t *__restrict__ row_members) {
+    const int row = blockIdx.x * kBlock + threadIdx.x;
+    if (row >= rows) return;
+    const int64_t members = n - (int64_t)rkey[row];
+    const double m = (double)members;
+    double *o = rows16 + 16 * (int64_t)row;
+    const int c0 = chunk_off[row], c1 = chunk_off[row + 1];
+    if (kPass == 1) {
+        const int op[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 2, 2, 2};
+        double v[16];
+        for (int k = 0; k < 16; k++) v[k] = part[(int64_t)c0 * kFsVals + k];
+        for (int c = c0 + 1; c < c1; c++)
+            for (int k = 0; k < 16; k++) v[k] = fs_fold(op[k], v[k], part[(int64_t)c * kFsVals + k]);
+        o[0] = m;
+        o[1] = v[0] / m; o[2] = v[1] / m; o[3] = v[2] / m;
+        o[4] = v[3] / m; o[5] = v[4] / m; o[6] = v[5] / m;
+        o[7] = sqrt((v[6] * v[6] + v[7] * v[7]) + v[8] * v[8]) / m;
+        o[8] = v[9] / m;
+        o[9] = 0.0;
+        for (int k = 0; k < 6; k++) o[10 + k] = v[10 + k];
+        if (row_label) row_label[row] = (int32_t)lab_s[rhead[row]];
+        if (row_members) row_members[row] = members;
+    } else {
+        double v[3];
+        for (int k = 0; k < 3; k++) v[k] = part[(int64_t)c0 * kFsVals + k];
+        for (int c = c0 + 1; c < c1; c++)
+            for (int k = 0; k < 3; k++) v[k] += part[(int64_t)c * kFsVals + k];
+        o[9] = sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]) / m;
+    }
+}
+
 inline int nblocks(int64_t n) { return (int)((n + kBlock - 1) / kBlock); }
 
 }  // namespace
@@ -567,6 +916,7 @@ struct bdmi_flock {
     uint8_t *vis_flag = nullptr;
     uint32_t *vis_slot = nullptr, *vis_tiles = nullptr;
     float *vis_verts = nullptr, *vis_cols = nullptr;  // 18 floats per boid each
+    FlockStats fs = {};  // flock analysis scratch (bdmi_flocks and the calls next to it), allocated on first use
     bool timers = false;
     hipEvent_t ev[4] = {};
     double ms[3] = {0, 0, 0};
@@ -1097,6 +1447,224 @@ int bdmi_visible_vertices(bdmi_flock *f, const double *cam12, double tan_h, doub
         NBMI_HIP_CHECK(hipMemcpyAsync(out_colors, d_cols, (size_t)rows * 72, hipMemcpyDeviceToHost, st));
         NBMI_HIP_CHECK(hipStreamSynchronize(st));
     }
+    return 0;
+}
+
+// ---- flock analysis (the kernels are above, next to the sweep whose grid they share) ---------------------------------
+namespace {
+// frees one of the handle's allocations ahead of bdmi_destroy (the caller clears its pointer)
+void dev_release(bdmi_flock *f, void *p) {
+    if (!p) return;
+    for (size_t k = 0; k < f->allocs.size(); k++)
+        if (f->allocs[k] == p) { f->allocs.erase(f->allocs.begin() + (long)k); break; }
+    (void)hipFree(p);
+}
+int fs_radius_check(bdmi_flock *f, const char *what, const char *name, double v) {
+    if (int rc = whole_flock_check(f, what)) return rc;
+    const double perception = f->params[5];
+    if (!(v > 0) || !(v <= perception)) {  // NaN fails the first test, +inf the second
+        nbmi::set_error("%s: %s = %g must be finite, > 0 and at most the perception radius %g (the grid cell)", what, name, v,
+                        perception);
+        return -1;
+    }
+    return 0;
+}
+int fs_bits(int64_t n) {
+    int bits = 1;
+    while (bits < 32 && ((int64_t)1 << bits) < n) bits++;
+    return bits;
+}
+// the handle's one sort scratch (whose sticky error word sync_checked reports) must also hold a sort of n pairs on `bits`
+int fs_sort_temp(bdmi_flock *f, int64_t n, int bits) {
+    const size_t need = nbmi::radix_temp_bytes_u32((size_t)n, bits);
+    if (need <= f->tmp_sort_bytes) return 0;
+    if (int rc = sync_checked(f)) return rc;
+    char *t = nullptr;
+    dev_release(f, f->tmp_sort);
+    f->tmp_sort = nullptr;
+    f->tmp_sort_bytes = 0;
+    if (dev_alloc(f, &t, need + 256)) return -2;
+    f->tmp_sort = t;
+    f->tmp_sort_bytes = need;
+    NBMI_HIP_CHECK(nbmi::radix_init_temp(t, f->stream));
+    return 0;
+}
+int fs_buffers(bdmi_flock *f) {
+    FlockStats &s = f->fs;
+    if (s.parent) return 0;
+    const size_t n = (size_t)(f->n > 0 ? f->n : 1);
+    if (dev_alloc(f, &s.parent, n) || dev_alloc(f, &s.root, n) || dev_alloc(f, &s.minid, n) || dev_alloc(f, &s.cnt, n) ||
+        dev_alloc(f, &s.lcnt, n) || dev_alloc(f, &s.lab, n) || dev_alloc(f, &s.lab_s, n) || dev_alloc(f, &s.rank, n) ||
+        dev_alloc(f, &s.rank_s, n) || dev_alloc(f, &s.qkey, n) || dev_alloc(f, &s.qkey_s, n) || dev_alloc(f, &s.qval, n) ||
+        dev_alloc(f, &s.qval_s, n) || dev_alloc(f, &s.counters, 4))
+        return -2;
+    return 0;
+}
+int fs_row_buffers(bdmi_flock *f, int64_t rows, int64_t chunks) {
+    FlockStats &s = f->fs;
+    if (rows > s.rows_cap) {
+        dev_release(f, s.chunk_off); dev_release(f, s.rows16); dev_release(f, s.row_label); dev_release(f, s.row_members);
+        s.chunk_off = nullptr; s.rows16 = nullptr; s.row_label = nullptr; s.row_members = nullptr;
+        s.rows_cap = 0;
+        if (dev_alloc(f, &s.chunk_off, (size_t)rows + 1) || dev_alloc(f, &s.rows16, (size_t)rows * 16) ||
+            dev_alloc(f, &s.row_label, (size_t)rows) || dev_alloc(f, &s.row_members, (size_t)rows))
+            return -2;
+        s.rows_cap = rows;
+    }
+    if (chunks > s.chunks_cap) {
+        dev_release(f, s.part);
+        s.part = nullptr;
+        s.chunks_cap = 0;
+        if (dev_alloc(f, &s.part, (size_t)chunks * kFsVals)) return -2;
+        s.chunks_cap = chunks;
+    }
+    return 0;
+}
+// grid, union-find over the links, labels: leaves root / minid / cnt / lab / lcnt, the labels in the caller's order in
+// the staging buffer and the counters {links, evals, flocks}
+int fs_enqueue_flocks(bdmi_flock *f, double b2) {
+    const int64_t n = f->n;
+    FlockStats &s = f->fs;
+    hipStream_t st = f->stream;
+    if (int rc = fs_buffers(f)) return rc;
+    if (int rc = enqueue_grid(f, false)) return rc;
+    NBMI_HIP_CHECK(hipMemsetAsync(s.counters, 0, 4 * sizeof(unsigned long long), st));
+    k_fs_init<<<nblocks(n), kBlock, 0, st>>>(n, s.parent, s.minid, s.cnt, s.rank);
+    k_fs_link<<<nblocks(n), kBlock, 0, st>>>(f->B.p, f->occ, f->cell_start, n, f->grid, b2, s.parent, s.counters);
+    k_fs_flatten<<<nblocks(n), kBlock, 0, st>>>(n, s.parent, f->B.id, s.root, s.minid, s.cnt);
+    k_fs_labels<<<nblocks(n), kBlock, 0, st>>>(n, s.root, s.minid, s.cnt, f->B.id, s.lab, s.lcnt, (int32_t *)f->stage,
+                                               s.counters + 2);
+    NBMI_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+// the two passes over `rows` rows whose members (host copy: members[]) are described by rkey / rhead on the device
+int fs_enqueue_rows(bdmi_flock *f, int64_t rows, const int64_t *members, const uint32_t *rank_s, const uint32_t *lab_s,
+                    const uint32_t *rkey, const uint32_t *rhead, bool with_labels) {
+    FlockStats &s = f->fs;
+    hipStream_t st = f->stream;
+    std::vector<int32_t> off((size_t)rows + 1);
+    int64_t chunks = 0;
+    for (int64_t i = 0; i < rows; i++) {
+        off[(size_t)i] = (int32_t)chunks;
+        chunks += (members[i] + kFsChunk - 1) / kFsChunk;
+    }
+    off[(size_t)rows] = (int32_t)chunks;
+    if (int rc = fs_row_buffers(f, rows, chunks)) return rc;
+    NBMI_HIP_CHECK(hipMemcpyAsync(s.chunk_off, off.data(), off.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    NBMI_HIP_CHECK(hipStreamSynchronize(st));  // `off` is pageable host memory that ends with this function
+    k_fs_chunks<1><<<(int)chunks, kBlock, 0, st>>>(f->B.p, f->B.v, rank_s, rkey, rhead, f->n, s.chunk_off, (int)rows, s.rows16,
+                                                  s.part);
+    k_fs_combine<1><<<nblocks(rows), kBlock, 0, st>>>(lab_s, rkey, rhead, f->n, s.chunk_off, (int)rows, s.part, s.rows16,
+                                                     with_labels ? s.row_label : nullptr, with_labels ? s.row_members : nullptr);
+    k_fs_chunks<2><<<(int)chunks, kBlock, 0, st>>>(f->B.p, f->B.v, rank_s, rkey, rhead, f->n, s.chunk_off, (int)rows, s.rows16,
+                                                  s.part);
+    k_fs_combine<2><<<nblocks(rows), kBlock, 0, st>>>(lab_s, rkey, rhead, f->n, s.chunk_off, (int)rows, s.part, s.rows16, nullptr,
+                                                     nullptr);
+    NBMI_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+}  // namespace
+
+int bdmi_flocks(bdmi_flock *f, double link, int32_t *labels, int64_t *n_flocks, int64_t *links, int64_t *evals) {
+    if (int rc = fs_radius_check(f, "bdmi_flocks", "link", link)) return rc;
+    const int64_t n = f->n;
+    unsigned long long h[4] = {0, 0, 0, 0};
+    if (n > 0) {
+        if (int rc = fs_enqueue_flocks(f, link * link)) return rc;
+        hipStream_t st = f->stream;
+        NBMI_HIP_CHECK(hipMemcpyAsync(h, f->fs.counters, sizeof(h), hipMemcpyDeviceToHost, st));
+        if (labels) NBMI_HIP_CHECK(hipMemcpyAsync(labels, f->stage, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+        if (int rc = sync_checked(f)) return rc;
+    }
+    if (links) *links = (int64_t)h[0];
+    if (evals) *evals = (int64_t)h[1];
+    if (n_flocks) *n_flocks = (int64_t)h[2];
+    return 0;
+}
+
+int bdmi_flock_catalogue(bdmi_flock *f, double link, int64_t min_members, int64_t capacity, int32_t *label, int64_t *members,
+                         double *rows16, int64_t *count) {
+    if (int rc = fs_radius_check(f, "bdmi_flock_catalogue", "link", link)) return rc;
+    if (min_members < 1 || capacity < 0) {
+        nbmi::set_error("bdmi_flock_catalogue: min_members = %lld must be >= 1 and capacity = %lld >= 0", (long long)min_members,
+                        (long long)capacity);
+        return -1;
+    }
+    if (!count || (capacity > 0 && (!label || !members || !rows16))) {
+        nbmi::set_error("bdmi_flock_catalogue: null count, or null output with capacity > 0");
+        return -1;
+    }
+    const int64_t n = f->n;
+    if (n == 0) { *count = 0; return 0; }
+    const int bits = fs_bits(n);
+    if (int rc = fs_sort_temp(f, n, bits)) return rc;
+    if (int rc = fs_enqueue_flocks(f, link * link)) return rc;
+    FlockStats &s = f->fs;
+    hipStream_t st = f->stream;
+    // the ranks by label, stable; the heads of the qualifying flocks in label order; those by n - members, stable
+    NBMI_HIP_CHECK(nbmi::radix_sort_pairs_u32(f->tmp_sort, f->tmp_sort_bytes, s.lab, s.lab_s, s.rank, s.rank_s, (size_t)n, 0, bits,
+                                              st));
+    scan::enqueue_compact(FsHeadSel{s.lab_s, s.lcnt, min_members}, n, f->tile_cnt, FsEmitHead{s.lab_s, s.lcnt, n, s.qkey, s.qval},
+                          st);
+    NBMI_HIP_CHECK(hipGetLastError());
+    uint32_t total = 0;
+    NBMI_HIP_CHECK(hipMemcpyAsync(&total, f->tile_cnt + scan::tiles_for(n), 4, hipMemcpyDeviceToHost, st));
+    if (int rc = sync_checked(f)) return rc;
+    const int64_t rows = (int64_t)total < capacity ? (int64_t)total : capacity;
+    if (rows > 0) {
+        if (int rc = fs_sort_temp(f, (int64_t)total, bits)) return rc;
+        NBMI_HIP_CHECK(nbmi::radix_sort_pairs_u32(f->tmp_sort, f->tmp_sort_bytes, s.qkey, s.qkey_s, s.qval, s.qval_s, (size_t)total,
+                                                  0, bits, st));
+        std::vector<uint32_t> hkey((size_t)rows);
+        NBMI_HIP_CHECK(hipMemcpyAsync(hkey.data(), s.qkey_s, (size_t)rows * 4, hipMemcpyDeviceToHost, st));
+        if (int rc = sync_checked(f)) return rc;
+        for (int64_t i = 0; i < rows; i++) members[i] = n - (int64_t)hkey[(size_t)i];
+        if (int rc = fs_enqueue_rows(f, rows, members, s.rank_s, s.lab_s, s.qkey_s, s.qval_s, true)) return rc;
+        NBMI_HIP_CHECK(hipMemcpyAsync(rows16, s.rows16, (size_t)rows * 16 * sizeof(double), hipMemcpyDeviceToHost, st));
+        NBMI_HIP_CHECK(hipMemcpyAsync(label, s.row_label, (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        if (int rc = sync_checked(f)) return rc;
+    }
+    *count = (int64_t)total;
+    return 0;
+}
+
+int bdmi_diagnostics(bdmi_flock *f, double *row16) {
+    if (int rc = whole_flock_check(f, "bdmi_diagnostics")) return rc;
+    if (!row16) { nbmi::set_error("bdmi_diagnostics: null output"); return -1; }
+    const int64_t n = f->n;
+    if (n == 0) { memset(row16, 0, 16 * sizeof(double)); return 0; }
+    if (int rc = fs_buffers(f)) return rc;
+    if (int rc = enqueue_grid(f, false)) return rc;
+    FlockStats &s = f->fs;
+    hipStream_t st = f->stream;
+    // one row of all the boids in rank order: head 0, key n - n = 0
+    NBMI_HIP_CHECK(hipMemsetAsync(s.qkey, 0, 4, st));
+    NBMI_HIP_CHECK(hipMemsetAsync(s.qval, 0, 4, st));
+    if (int rc = fs_enqueue_rows(f, 1, &n, nullptr, nullptr, s.qkey, s.qval, false)) return rc;
+    NBMI_HIP_CHECK(hipMemcpyAsync(row16, s.rows16, 16 * sizeof(double), hipMemcpyDeviceToHost, st));
+    return sync_checked(f);
+}
+
+int bdmi_neighbour_stats(bdmi_flock *f, double radius, int32_t *count, double *nn_d2, int64_t *evals) {
+    if (int rc = fs_radius_check(f, "bdmi_neighbour_stats", "radius", radius)) return rc;
+    const int64_t n = f->n;
+    unsigned long long h = 0;
+    if (n > 0) {
+        if (int rc = fs_buffers(f)) return rc;
+        if (int rc = enqueue_grid(f, false)) return rc;
+        hipStream_t st = f->stream;
+        int32_t *d_count = (int32_t *)f->stage;
+        double *d_nn = f->stage + n;  // behind the n int32 counts (n doubles hold them twice over)
+        NBMI_HIP_CHECK(hipMemsetAsync(f->fs.counters + 3, 0, sizeof(unsigned long long), st));
+        k_fs_neighbours<<<nblocks(n), kBlock, 0, st>>>(f->B.p, f->B.id, f->occ, f->cell_start, n, f->grid, radius * radius, d_count,
+                                                       d_nn, f->fs.counters + 3);
+        NBMI_HIP_CHECK(hipGetLastError());
+        if (count) NBMI_HIP_CHECK(hipMemcpyAsync(count, d_count, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+        if (nn_d2) NBMI_HIP_CHECK(hipMemcpyAsync(nn_d2, d_nn, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+        NBMI_HIP_CHECK(hipMemcpyAsync(&h, f->fs.counters + 3, sizeof(h), hipMemcpyDeviceToHost, st));
+        if (int rc = sync_checked(f)) return rc;
+    }
+    if (evals) *evals = (int64_t)h;
     return 0;
 }
 

@@ -6,8 +6,12 @@ machine without GL, display or window system.
 
     python -m tools.flock_video --boids 500k --frames 300                  # ffmpeg if on PATH, else raw rgb24 + JSON
     python -m tools.flock_video --boids 2m --resolution 1080p --camera orbit --format ppm -o frames/
+    python -m tools.flock_video --boids 2m --frames 600 --diagnostics 10   # + flock.flock.jsonl: flocks, order parameters
 
 Each frame: flock.update(dt, substeps), render_flock, sink.  Output formats and sinks are those of tools.export.
+With --diagnostics K every K-th frame also appends one JSON line (boids.analysis.jsonl_line) to <output stem>.flock.jsonl:
+the whole flock's row, the number of flocks and links at --link, the mean neighbour count and the rows of the 16 largest
+flocks of at least --min-members boids, all computed on the device (include/bdmi.h).
 """
 import argparse
 import json
@@ -50,6 +54,12 @@ def build_parser():
     ap.add_argument("--format", choices=FORMATS, default=None,
                     help="ffmpeg (default when ffmpeg is on PATH), raw rgb24 + JSON sidecar, or one PPM per frame")
     ap.add_argument("--device", type=int, default=0, help="HIP device (default: 0)")
+    ap.add_argument("--diagnostics", type=int, default=0, metavar="K",
+                    help="every K-th frame, append a flock-analysis JSON line to <output stem>.flock.jsonl (default: off)")
+    ap.add_argument("--link", type=float, default=None, metavar="B",
+                    help="linking length of the flock finder (default and at most: the perception radius)")
+    ap.add_argument("--min-members", type=int, default=20, metavar="M",
+                    help="smallest flock listed in the analysis lines (default: 20)")
     return ap
 
 
@@ -96,11 +106,35 @@ def make_sink(args, fmt, output, width, height):
     return _PpmSink(output, 0)
 
 
+LARGEST_FLOCKS = 16  # rows per analysis line
+
+
+def diagnostics_path(output: Path) -> Path:
+    """<output stem>.flock.jsonl next to the output (a frame directory keeps its whole name)."""
+    return output.with_name((output.stem if output.suffix else output.name) + ".flock.jsonl")
+
+
+def analysis_line(flock, frame, steps, link, min_members) -> str:
+    """One line of the analysis file for the flock's current state (four device calls, no state copied out)."""
+    from boids.analysis import jsonl_line
+    fl = flock.flocks(link)
+    cat = flock.flock_catalogue(link, min_members=min_members, capacity=LARGEST_FLOCKS)
+    nb = flock.neighbour_stats(link)
+    count = np.asarray(nb["count"])
+    return jsonl_line(frame, steps, flock.diagnostics(), fl["n_flocks"], fl["links"],
+                      float(count.mean()) if count.size else 0.0, cat["rows"], flock_labels=cat["label"],
+                      link=link, min_members=min_members, qualifying=cat["count"])
+
+
 def run(args, make_flock=None, make_renderer=None, say=print) -> dict:
     """Steps the flock and writes args.frames frames.  make_flock(count, seed, device) and
     make_renderer(width, height, device) default to boids.Flock and boids.render.HIPFlockRenderer."""
     if args.frames <= 0 or args.substeps <= 0 or args.boids <= 0 or args.warmup < 0:
         raise ValueError("--frames, --substeps and --boids must be positive, --warmup not negative")
+    every = int(getattr(args, "diagnostics", 0) or 0)
+    min_members = int(getattr(args, "min_members", 20))
+    if every < 0 or min_members < 1:
+        raise ValueError("--diagnostics must not be negative and --min-members at least 1")
     if make_flock is None:
         from boids import Flock
         make_flock = lambda n, seed, device: Flock(n, seed=seed, device=device)  # noqa: E731
@@ -116,13 +150,19 @@ def run(args, make_flock=None, make_renderer=None, say=print) -> dict:
     flock = make_flock(args.boids, args.seed, args.device)
     renderer = make_renderer(width, height, args.device)
     sink = make_sink(args, fmt, output, width, height)
+    diag_path = diagnostics_path(output) if every else None
+    diag_file = None
+    diag_lines = 0
     ok = False
-    t_step = t_render = t_write = 0.0
+    t_step = t_render = t_write = t_analysis = 0.0
     t0 = time.perf_counter()
     try:
         if args.warmup:
             flock.update(dt, args.warmup)
         img = np.empty((height, width, 3), dtype=np.uint8)
+        if every:
+            diag_path.parent.mkdir(parents=True, exist_ok=True)
+            diag_file = open(diag_path, "w")
         for i in range(args.frames):
             ts = time.perf_counter()
             flock.update(dt, args.substeps)
@@ -134,23 +174,38 @@ def run(args, make_flock=None, make_renderer=None, say=print) -> dict:
             t_step += tr - ts
             t_render += tw - tr
             t_write += time.perf_counter() - tw
+            if every and i % every == 0:
+                ta = time.perf_counter()
+                steps = args.warmup + (i + 1) * args.substeps
+                diag_file.write(analysis_line(flock, i, steps, getattr(args, "link", None), min_members) + "\n")
+                diag_lines += 1
+                t_analysis += time.perf_counter() - ta
         ok = True
     finally:
+        if diag_file is not None:
+            diag_file.close()
         ok = sink.close(ok) and ok
         renderer.close()
         flock.close()
     wall = time.perf_counter() - t0
     timings = {"ok": ok, "frames": args.frames, "wall_s": wall, "step_s": t_step, "render_s": t_render,
                "write_s": t_write, "fps": args.frames / wall if wall > 0 else 0.0, "output": str(output), "format": fmt}
+    if every:
+        timings.update({"diagnostics": str(diag_path), "diagnostics_lines": diag_lines, "analysis_s": t_analysis})
     if ok and fmt == "raw":  # the sink's sidecar, plus what produced the frames
         meta = json.loads(sink.meta_path.read_text())
         meta["flock"] = {"boids": args.boids, "seed": args.seed, "dt": dt, "substeps": args.substeps,
                          "warmup": args.warmup, "params": {k: float(v) for k, v in config.BOIDS.items()}}
         meta["camera"] = {"mode": args.camera, "speed": args.camera_speed, "radius": args.camera_radius,
                           "angle": args.camera_angle, "theta": args.camera_theta}
+        if every:
+            meta["diagnostics"] = {"file": diag_path.name, "every": every, "link": getattr(args, "link", None),
+                                   "min_members": min_members, "lines": diag_lines}
         sink.meta_path.write_text(json.dumps(meta, indent=2))
     say(f"[Flock] {'done' if ok else 'FAILED'}: {output} ({args.frames} frames in {format_time(wall)}, "
         f"{timings['fps']:.1f} fps; step {t_step:.2f}s, render {t_render:.2f}s, write {t_write:.2f}s)")
+    if every:
+        say(f"[Flock] flock analysis: {diag_lines} lines in {diag_path} ({t_analysis:.2f}s)")
     return timings
 
 

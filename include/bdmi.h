@@ -49,12 +49,76 @@ int bdmi_get_cell_indices(bdmi_flock *f, int32_t *cell_indices);
  * separation / alignment / cohesion forces and avg_colors, (N,3) float64 each, with the
  * caller-side pre-fill of Flock.update (forces 0, avg_colors = colors; flock.py:633-636). */
 int bdmi_get_forces(bdmi_flock *f, double *sep, double *ali, double *coh, double *avg_colors);
-/* grid facts: dim, num_cells, non-empty cells of the last built grid. */
+/* grid facts: dim, num_cells, non-empty cells of the last built grid.  The last built grid is that of the last
+ * bdmi_step, or of the current positions after bdmi_get_forces or one of the four flock-analysis calls below. */
 int bdmi_grid_info(bdmi_flock *f, int32_t *grid_dim, int64_t *num_cells, int64_t *occupied);
 /* device ms accumulated per phase [cells+sort, reorder+table, sweep+physics], steps counted */
 int bdmi_enable_timers(bdmi_flock *f, int enable);
 int bdmi_get_timers(bdmi_flock *f, double *ms3, int64_t *count, int reset);
 
+
+/* ---- flock analysis: flock finder, catalogue, order parameters, neighbour statistics ----------
+ * The boids counterpart of nbmi_diagnostics + nbmi_fof + nbmi_fof_catalogue, on the sweep's own grid.  This text is the
+ * specification; the kernels (csrc/bdmi.hip) and the tests' NumPy restatement (tests/flockstats_ref.py) both follow it.
+ * Arithmetic is float64 in the association written, without FMA; sqrt and divide are correctly rounded.
+ *
+ * For the handle's current state:
+ *   d2(i, j) = (dx dx + dy dy) + dz dz with dx = x_j - x_i (k_flock's association; symmetric in i and j).
+ *   b2 = link * link, one float64 product computed on the host.  `link` (and `radius` below) must be finite, > 0 and
+ *     <= perception_radius: the grid cell is the perception radius, so the 27-cell neighbourhood covers it.
+ *   Boids i != j are LINKED iff d2(i, j) <= b2.  Equality links and a coincident pair is linked: nbmi_fof's rule.  This
+ *     is deliberately NOT the sweep's window 1e-4 < d2 < r^2 (flock.py:148): a clustering that splits coincident boids
+ *     is useless.
+ *   A FLOCK is a connected component of the link graph; a boid without a friend is a flock of one.
+ *   Boids outside the grid are clamped into its border cells as in get_cell_index (flock.py:16-27).  Clamping is monotone
+ *     per axis, so two linked boids (at most one cell apart per axis before clamping) are still in the same or in
+ *     adjacent cells: every result below stays exact there.
+ *
+ * bdmi_flocks: labels[i] (caller's boid order) = the smallest caller index in i's flock: unique, independent of the
+ *   evaluation order, equal to a brute force's.  *n_flocks = the number of distinct labels.  *links = the exact number of
+ *   unordered linked pairs: every candidate pair is evaluated exactly once, and a pair is not skipped because its boids
+ *   are in one set already.  *evals = the number of d2 evaluated (a measurement hook like nbmi_fof's).
+ * bdmi_flock_catalogue: the flocks with members >= min_members (min_members >= 1), ordered by members descending, ties
+ *   by label ascending.  *count = the number of qualifying flocks, which may exceed `capacity`; at most `capacity` rows
+ *   are copied out, the first ones of that order (as nbmi_fof_catalogue).  label / members / rows16 may be NULL when
+ *   capacity == 0.
+ * The ROW of 16 doubles, of one flock here and of the whole flock in bdmi_diagnostics (every boid in one group, no link
+ *   evaluated):  {m, c[3], vbar[3], polarisation, mean_speed, milling, lo[3], hi[3]}.  For the group's members j = 1..m:
+ *     s_j = sqrt((vx vx + vy vy) + vz vz);  u_j = v_j / s_j per component, 0 when s_j == 0
+ *     Sp = sum p_j, Sv = sum v_j, Su = sum u_j, Ss = sum s_j
+ *     c = Sp / m, vbar = Sv / m, mean_speed = Ss / m
+ *     polarisation = sqrt((Su_x^2 + Su_y^2) + Su_z^2) / m        (1: perfectly aligned; about m^-1/2: disordered)
+ *   second pass, with r_j = p_j - c (the rounded c):
+ *     rho_j = sqrt((rx rx + ry ry) + rz rz);  rhat_j = r_j / rho_j per component, 0 when rho_j == 0
+ *     w_j = rhat_j x u_j = (ry uz - rz uy, rz ux - rx uz, rx uy - ry ux)
+ *     milling = sqrt((Wx^2 + Wy^2) + Wz^2) / m with W = sum w_j  (the rotational order parameter)
+ *   lo / hi = the exact per-axis minimum / maximum of the positions.
+ *   The sums are float64 in an order fixed for a given state, without floating-point atomics: two calls on an unchanged
+ *   state return the same bits.  Members are taken in the order a stable sort by label leaves the cell-sorted boids, cut
+ *   into chunks of 4096 consecutive members; one block reduces a chunk with a fixed tree and the chunks' partials are
+ *   added in chunk order, so a flock of all N boids is N / 4096 blocks and not one wave's loop.  bdmi_diagnostics uses
+ *   the same chunk reduction over the cell-sorted boids, without the sort by label: where one flock covers all boids its
+ *   catalogue row and the bdmi_diagnostics row are the same bits.  N == 0: m = 0 and the rest zeros.
+ * bdmi_neighbour_stats: count[i] = #{j != i : d2(i, j) <= radius^2}, nn_d2[i] = the smallest such d2, +inf when
+ *   count[i] == 0.  Exact and order independent; the sum of count is 2 * links of bdmi_flocks at link == radius.
+ *
+ * All four build the grid for the current positions (as bdmi_get_forces does; bdmi_grid_info's `occupied` then describes
+ * that grid), change nothing a later step reads - a run with calls between its steps gives the same state bits as one
+ * without - wait for their own work and report the sort's sticky error like bdmi_sync.  N == 0: success, zeros,
+ * *count = 0; N == 1: one flock of one.  Refused with NBMI_ERR_ARG (message "<call>: ..."), before anything is launched
+ * and with the outputs untouched: a link or radius that is not finite, <= 0 or above the perception radius (the message
+ * names both numbers), min_members < 1, capacity < 0, and slab handles (bdmi_create_slab).
+ * Scratch, allocated at the first of these calls and freed by bdmi_destroy: 52 bytes per boid (union-find parent, root,
+ * least id and members per root, members per label, labels and ranks unsorted and sorted, two key / value pairs for
+ * the catalogue's heads); per catalogue row copied out 144 bytes plus 128 bytes per chunk of 4096 members.  The labels
+ * and neighbour statistics travel through the state staging buffer. */
+int bdmi_flocks(bdmi_flock *f, double link, int32_t *labels /* (N,), may be NULL */, int64_t *n_flocks,
+                int64_t *links, int64_t *evals); /* each may be NULL */
+int bdmi_flock_catalogue(bdmi_flock *f, double link, int64_t min_members, int64_t capacity, int32_t *label,
+                         int64_t *members, double *rows16, int64_t *count);
+int bdmi_diagnostics(bdmi_flock *f, double *row16);
+int bdmi_neighbour_stats(bdmi_flock *f, double radius, int32_t *count /* (N,) */, double *nn_d2 /* (N,) */,
+                         int64_t *evals); /* each output may be NULL */
 
 /* ---- multi-GPU: x-slabs with a one-cell halo -----------------------------------------
  * A rank owns the boids with x_lo <= x < x_hi (a whole number of cell planes, at least two cells wide); the
