@@ -31,9 +31,10 @@ def size_histogram(members) -> dict:
 
 
 def jsonl_line(frame, steps, global_row, n_flocks, links, mean_neighbours, flock_rows, flock_labels=None,
-               link=None, min_members=None, qualifying=None) -> str:
+               link=None, min_members=None, qualifying=None, neighbours=None) -> str:
     """One flock-analysis line: the frame, the step count, the whole flock's row, the number of flocks and links, the
-    mean neighbour count and the rows of the largest flocks (largest first), as one JSON object without a newline."""
+    mean neighbour count and the rows of the largest flocks (largest first), as one JSON object without a newline.
+    ``neighbours`` ({"mode": "topological", "k": K}) names the interaction rule where it is not the metric default."""
     rows = [row_dict(r) for r in np.asarray(flock_rows, dtype=np.float64).reshape(-1, 16)]
     if flock_labels is not None:
         for r, l in zip(rows, np.asarray(flock_labels).tolist()):
@@ -46,4 +47,19 @@ def jsonl_line(frame, steps, global_row, n_flocks, links, mean_neighbours, flock
         rec["min_members"] = int(min_members)
     if qualifying is not None:
         rec["qualifying_flocks"] = int(qualifying)
+    if neighbours is not None:
+        rec["neighbours"] = {"mode": str(neighbours["mode"]), "k": int(neighbours["k"])}
     return json.dumps(rec)
+
+
+def neighbour_rank_profile(d2) -> np.ndarray:
+    """The mean distance to the 1st .. k-th neighbour, from the ``d2`` of Flock.topological_neighbours ((N, k) squared
+    distances, padded with +inf): float64 (k,).  Entry s averages sqrt(d2[:, s]) over the boids that have an (s + 1)-th
+    neighbour (+inf ignored) and is NaN where none has one."""
+    d2 = np.asarray(d2, dtype=np.float64)
+    if d2.ndim != 2:
+        raise ValueError(f"d2 must be (N, k), got shape {d2.shape}")
+    have = np.isfinite(d2)
+    total = np.where(have, np.sqrt(np.where(have, d2, 0.0)), 0.0).sum(axis=0)
+    cnt = have.sum(axis=0)
+    return np.where(cnt > 0, total / np.maximum(cnt, 1), np.nan)

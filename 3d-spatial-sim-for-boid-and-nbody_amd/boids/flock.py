@@ -16,6 +16,9 @@ import nbmi_native as _nat
 from config import boids as config
 
 
+NEIGHBOUR_MODES = ("metric", "topological")  # BDMI_NEIGHBOURS_METRIC = 0, BDMI_NEIGHBOURS_TOPOLOGICAL = 1
+
+
 def rainbow_colors(count: int) -> np.ndarray:
     """Shuffled HSV rainbow, s=0.9 v=1.0, float32 maths (reference _generate_colors :587-608).
     Consumes the global NumPy RNG exactly once (np.random.shuffle)."""
@@ -200,6 +203,37 @@ class Flock:
         _nat.check_arg(self._lib.bdmi_neighbour_stats(self._h, self._link(radius), _nat.ptr(count), _nat.ptr(nn),
                                                       C.addressof(evals)), "bdmi_neighbour_stats")
         return dict(count=count, nn_d2=nn, evals=int(evals.value))
+
+    # ---- topological interaction (include/bdmi.h: the k nearest neighbours within sight) ---------------------
+    def set_neighbour_mode(self, mode, k=7):
+        """``"metric"`` (the default: every boid within the perception radius counts, the reference's rule) or
+        ``"topological"``: each boid interacts with its ``k`` nearest neighbours within the perception radius
+        (1 <= k <= 16).  ``update`` and ``forces`` follow the mode; ``k`` is ignored for ``"metric"``."""
+        if mode not in NEIGHBOUR_MODES:
+            raise ValueError(f"set_neighbour_mode: mode must be one of {NEIGHBOUR_MODES}, got {mode!r}")
+        _nat.check_arg(self._lib.bdmi_set_neighbour_mode(self._h, NEIGHBOUR_MODES.index(mode), int(k)),
+                       "bdmi_set_neighbour_mode")
+
+    @property
+    def neighbour_mode(self):
+        """``(name, k)`` of the handle's interaction rule."""
+        mode, k = C.c_int(0), C.c_int(0)
+        _nat.check_arg(self._lib.bdmi_get_neighbour_mode(self._h, C.addressof(mode), C.addressof(k)),
+                       "bdmi_get_neighbour_mode")
+        return NEIGHBOUR_MODES[int(mode.value)], int(k.value)
+
+    def topological_neighbours(self, k=None):
+        """Per boid its ``k`` nearest neighbours within the perception radius (default: the handle's k), nearest
+        first, ties by boid index: dict of ``ids`` (int32 (N, k), padded with -1), ``d2`` (float64 (N, k), squared
+        distances, padded with inf) and ``count`` (int32 (N,)).  Works in either mode."""
+        k = self.neighbour_mode[1] if k is None else int(k)
+        rows = max(k, 0)
+        ids = np.empty((self.num_boids, rows), dtype=np.int32)
+        d2 = np.empty((self.num_boids, rows), dtype=np.float64)
+        count = np.zeros(self.num_boids, dtype=np.int32)
+        _nat.check_arg(self._lib.bdmi_topological_neighbours(self._h, k, _nat.ptr(ids), _nat.ptr(d2), _nat.ptr(count)),
+                       "bdmi_topological_neighbours")
+        return dict(ids=ids, d2=d2, count=count)
 
     # ---- render-side reduction (reference :680-728) on the device -----------------------------
     def frustum_tangents(self, fov=None, aspect=None):

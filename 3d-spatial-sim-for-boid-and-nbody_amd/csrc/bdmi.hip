@@ -13,6 +13,7 @@
 // sweep kernel tests the occupancy bit (L2 resident) before touching the pair table, reads
 // neighbours from B and writes the updated boid back to A at the same rank, physics fused.
 #include <stddef.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -172,6 +173,118 @@ __device__ __forceinline__ int64_t logical_block(int b, int nb, int xcd_contiguo
     return (int64_t)xcd * q + (xcd < rem ? xcd : rem) + j;
 }
 
+// The end of compute_flocking_spatial (means and steer(), flock.py:174-238) and update_physics_numba (flock.py:241-308)
+// for the boid at rank r, from its neighbour sums: shared by the metric sweep (k_flock) and the topological one
+// (k_flock_topo).  kPhysics=false: write the four force arrays (caller's boid order) instead of integrating.
+template <bool kPhysics>
+__device__ __forceinline__ void flock_finish(const BoidsAoS &b, const Boids &a, int64_t r, const FlockP &P, double pix, double piy,
+                                             double piz, double vix, double viy, double viz, double cir, double cig, double cib,
+                                             double sx, double sy, double sz, double alx, double aly, double alz, double cox,
+                                             double coy, double coz, double clr, double clg, double clb, int sep_count,
+                                             int nb_count, double *__restrict__ o_sep, double *__restrict__ o_ali,
+                                             double *__restrict__ o_coh, double *__restrict__ o_avg) {
+    double fsx = 0, fsy = 0, fsz = 0, fax = 0, fay = 0, faz = 0, fcx = 0, fcy = 0, fcz = 0;
+    double avr = cir, avg = cig, avb = cib;  // caller pre-fill: avg_colors <- colors (flock.py:636)
+    if (sep_count > 0) {
+        sx /= sep_count; sy /= sep_count; sz /= sep_count;
+        if (steer(sx, sy, sz, vix, viy, viz, P.max_speed, P.max_force, P.sep_w)) { fsx = sx; fsy = sy; fsz = sz; }
+    }
+    if (nb_count > 0) {
+        alx /= nb_count; aly /= nb_count; alz /= nb_count;
+        if (steer(alx, aly, alz, vix, viy, viz, P.max_speed, P.max_force, P.ali_w)) { fax = alx; fay = aly; faz = alz; }
+        cox = cox / nb_count - pix; coy = coy / nb_count - piy; coz = coz / nb_count - piz;
+        if (steer(cox, coy, coz, vix, viy, viz, P.max_speed, P.max_force, P.coh_w)) { fcx = cox; fcy = coy; fcz = coz; }
+        avr = (clr + cir) / (nb_count + 1);
+        avg = (clg + cig) / (nb_count + 1);
+        avb = (clb + cib) / (nb_count + 1);
+    }
+    if (!kPhysics) {
+        const int64_t o = 3 * (int64_t)b.id[r];
+        o_sep[o] = fsx; o_sep[o + 1] = fsy; o_sep[o + 2] = fsz;
+        o_ali[o] = fax; o_ali[o + 1] = fay; o_ali[o + 2] = faz;
+        o_coh[o] = fcx; o_coh[o + 1] = fcy; o_coh[o + 2] = fcz;
+        o_avg[o] = avr; o_avg[o + 1] = avg; o_avg[o + 2] = avb;
+        return;
+    }
+    double acc[3] = {fsx + fax + fcx, fsy + fay + fcy, fsz + faz + fcz};
+    const double pos[3] = {pix, piy, piz};
+#pragma unroll
+    for (int d = 0; d < 3; d++) {
+        const double dist_pos = pos[d] - (P.bounds - P.margin);
+        if (dist_pos > 0) acc[d] -= fmin(dist_pos / P.margin * 2.0, 1.0) * P.wall_force;
+        const double dist_neg = (-P.bounds + P.margin) - pos[d];
+        if (dist_neg > 0) acc[d] += fmin(dist_neg / P.margin * 2.0, 1.0) * P.wall_force;
+    }
+    double nvx = vix + acc[0] * P.dt, nvy = viy + acc[1] * P.dt, nvz = viz + acc[2] * P.dt;
+    const double speed = sqrt(nvx * nvx + nvy * nvy + nvz * nvz);
+    if (speed > P.max_speed) {
+        const double scale = P.max_speed / speed;
+        nvx *= scale; nvy *= scale; nvz *= scale;
+    }
+    a.vx[r] = nvx; a.vy[r] = nvy; a.vz[r] = nvz;
+    a.px[r] = pix + nvx * P.dt; a.py[r] = piy + nvy * P.dt; a.pz[r] = piz + nvz * P.dt;
+    a.cr[r] = cir + (avr - cir) * P.blend;
+    a.cg[r] = cig + (avg - cig) * P.blend;
+    a.cb[r] = cib + (avb - cib) * P.blend;
+    a.id[r] = b.id[r];
+}
+
+// The candidate runs of the three rows (cy - 1 .. cy + 1) of cell plane ncz on the usual grid (range == 1), appended to
+// the lane's notes runs[2 nr], runs[2 nr + 1] in row order; returns whether one of them is longer than 4095.  Shared by
+// the metric sweep (k_flock) and the topological one (topo_select).
+template <int kThreads>
+__device__ __forceinline__ bool plane_runs(const uint2 *__restrict__ occ, const int32_t *__restrict__ cell_start, const GridP &g,
+                                           int x_lo, int x_hi, int cy, int ncz, int32_t (*runs)[kThreads], int &nr) {
+    bool big = false;
+    const bool zok = ncz >= 0 && ncz < g.dim;
+    uint2 wa[3], wb[3];
+    int lo_bit[3], hi_bit[3];
+    bool two[3], rok[3];
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        const int ncy = cy + j - 1;
+        rok[j] = zok && ncy >= 0 && ncy < g.dim;
+        const int64_t row = (int64_t)ncy * g.dim + (int64_t)ncz * g.dim * g.dim;
+        const int64_t c_lo = row + x_lo, c_hi = row + x_hi;
+        lo_bit[j] = (int)(c_lo & 31);
+        hi_bit[j] = (int)(c_hi & 31);
+        two[j] = (c_lo >> 5) != (c_hi >> 5);
+        wa[j] = rok[j] ? occ[c_lo >> 5] : make_uint2(0u, 0u);
+        wb[j] = (rok[j] && two[j]) ? occ[c_hi >> 5] : make_uint2(0u, 0u);
+    }
+    int32_t qb[3], qe[3];
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        uint32_t ba = wa[j].x & (~0u << lo_bit[j]);
+        uint32_t bb = wb[j].x & (~0u >> (31 - hi_bit[j]));
+        if (!two[j]) { ba &= ~0u >> (31 - hi_bit[j]); bb = 0u; }
+        qb[j] = 0; qe[j] = 0;
+        if (rok[j] && (ba | bb)) {
+            // first and last non-empty cell of the row
+            const uint2 fw = ba ? wa[j] : wb[j];
+            const int first = ba ? __ffs(ba) - 1 : __ffs(bb) - 1;
+            const uint2 lw = bb ? wb[j] : wa[j];
+            const int last = bb ? 31 - __clz(bb) : 31 - __clz(ba);
+            const uint32_t k_lo = fw.y + __popc(fw.x & ((1u << first) - 1u));
+            const uint32_t k_hi = lw.y + __popc(lw.x & ((1u << last) - 1u)) + 1u;
+            qb[j] = cell_start[k_lo];
+            qe[j] = cell_start[k_hi];
+        }
+    }
+    // [r4] the runs are only noted here; ONE loop behind the three planes walks all nine (below)
+    // (only the NON-EMPTY runs are noted, in row order: the loop below then never has to step over an empty one)
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        if (qe[j] > qb[j]) {
+            runs[2 * nr][threadIdx.x] = qb[j];
+            runs[2 * nr + 1][threadIdx.x] = qe[j];
+            nr++;
+        }
+        big = big || qe[j] - qb[j] > 4095;
+    }
+    return big;
+}
+
 // compute_flocking_spatial (flock.py:68-238) + update_physics_numba (flock.py:241-308).
 // kPhysics=false: write the four force arrays (caller's boid order) instead of integrating.
 template <bool kPhysics>
@@ -237,55 +350,8 @@ __global__ __launch_bounds__(kBlock) void k_flock(BoidsAoS b, Boids a, const uin
         // that their loads are in flight at the same time.  Same rows, same order, same sums as the loop below.
         bool big = false;
         int nr = 0;  // non-empty runs noted so far
-        for (int dcz = -1; dcz <= 1; dcz++) {
-            const int ncz = cz + dcz;
-            const bool zok = ncz >= 0 && ncz < g.dim;
-            uint2 wa[3], wb[3];
-            int lo_bit[3], hi_bit[3];
-            bool two[3], rok[3];
-#pragma unroll
-            for (int j = 0; j < 3; j++) {
-                const int ncy = cy + j - 1;
-                rok[j] = zok && ncy >= 0 && ncy < g.dim;
-                const int64_t row = (int64_t)ncy * g.dim + (int64_t)ncz * g.dim * g.dim;
-                const int64_t c_lo = row + x_lo, c_hi = row + x_hi;
-                lo_bit[j] = (int)(c_lo & 31);
-                hi_bit[j] = (int)(c_hi & 31);
-                two[j] = (c_lo >> 5) != (c_hi >> 5);
-                wa[j] = rok[j] ? occ[c_lo >> 5] : make_uint2(0u, 0u);
-                wb[j] = (rok[j] && two[j]) ? occ[c_hi >> 5] : make_uint2(0u, 0u);
-            }
-            int32_t qb[3], qe[3];
-#pragma unroll
-            for (int j = 0; j < 3; j++) {
-                uint32_t ba = wa[j].x & (~0u << lo_bit[j]);
-                uint32_t bb = wb[j].x & (~0u >> (31 - hi_bit[j]));
-                if (!two[j]) { ba &= ~0u >> (31 - hi_bit[j]); bb = 0u; }
-                qb[j] = 0; qe[j] = 0;
-                if (rok[j] && (ba | bb)) {
-                    // first and last non-empty cell of the row
-                    const uint2 fw = ba ? wa[j] : wb[j];
-                    const int first = ba ? __ffs(ba) - 1 : __ffs(bb) - 1;
-                    const uint2 lw = bb ? wb[j] : wa[j];
-                    const int last = bb ? 31 - __clz(bb) : 31 - __clz(ba);
-                    const uint32_t k_lo = fw.y + __popc(fw.x & ((1u << first) - 1u));
-                    const uint32_t k_hi = lw.y + __popc(lw.x & ((1u << last) - 1u)) + 1u;
-                    qb[j] = cell_start[k_lo];
-                    qe[j] = cell_start[k_hi];
-                }
-            }
-            // [r4] the runs are only noted here; ONE loop behind the three planes walks all nine (below)
-            // (only the NON-EMPTY runs are noted, in row order: the loop below then never has to step over an empty one)
-#pragma unroll
-            for (int j = 0; j < 3; j++) {
-                if (qe[j] > qb[j]) {
-                    runs[2 * nr][threadIdx.x] = qb[j];
-                    runs[2 * nr + 1][threadIdx.x] = qe[j];
-                    nr++;
-                }
-                big = big || qe[j] - qb[j] > 4095;
-            }
-        }
+        for (int dcz = -1; dcz <= 1; dcz++)
+            big = plane_runs<kBlock>(occ, cell_start, g, x_lo, x_hi, cy, cz + dcz, runs, nr) || big;
         // [r4] One flattened candidate loop per boid instead of nine, in two phases.  In the state flocks reach (53
         // candidates per boid instead of 9, two thirds of the cells empty, the rest holding more) the nine per-row
         // loops cost a wave the SUM of the rows' longest runs among its 64 boids; one loop over a lane's nine runs back
@@ -398,50 +464,171 @@ __global__ __launch_bounds__(kBlock) void k_flock(BoidsAoS b, Boids a, const uin
         }
     }
     }
-    double fsx = 0, fsy = 0, fsz = 0, fax = 0, fay = 0, faz = 0, fcx = 0, fcy = 0, fcz = 0;
-    double avr = cir, avg = cig, avb = cib;  // caller pre-fill: avg_colors <- colors (flock.py:636)
-    if (sep_count > 0) {
-        sx /= sep_count; sy /= sep_count; sz /= sep_count;
-        if (steer(sx, sy, sz, vix, viy, viz, P.max_speed, P.max_force, P.sep_w)) { fsx = sx; fsy = sy; fsz = sz; }
+    flock_finish<kPhysics>(b, a, r, P, pix, piy, piz, vix, viy, viz, cir, cig, cib, sx, sy, sz, alx, aly, alz, cox, coy, coz, clr,
+                           clg, clb, sep_count, nb_count, o_sep, o_ali, o_coh, o_avg);
+}
+
+// ---- topological interaction: the k nearest within sight (include/bdmi.h has the specification) ------
+// T_i = the first min(k, |N_i|) members of the metric set N_i in ascending (d2, caller's id) order.  The selection below
+// keeps, per lane, an ascending list of at most k entries {d2, rank q} in LDS columns [slot][thread]; the sums then run
+// over that list in its order, from +0.0, so the forces are a function of the state and the ids alone - not of the cell
+// order, the row order or the block order.
+template <class F>
+__device__ __forceinline__ void fs_for_each_run(const double4 &p, const GridP &g, const uint2 *__restrict__ occ,
+                                                const int32_t *__restrict__ cell_start, F f);  // defined with the flock analysis
+
+constexpr int kTopoMaxK = 16;
+constexpr int kTopoRuns = 9;  // runs noted per lane before they are walked (all of them when range == 1)
+
+// The list of the boid at rank r (position pi4): ld2 / lq [slot][thread], ascending; returns its length.  Candidates come
+// from the (2 range + 1)^2 row runs, noted kTopoRuns at a time and walked back to back, four position records per trip as
+// in k_flock.  The common case of a candidate inside the window is a reject against the current k-th d2 (kept in a
+// register); ids are loaded only to break an exact d2 tie.  Ranks are stored whole, so a run may have any length.
+template <int kCap, int kThreads>
+__device__ __forceinline__ int topo_select(const BoidsAoS &b, const uint2 *__restrict__ occ, const int32_t *__restrict__ cell_start,
+                                           const GridP &g, int64_t r, const double4 &pi4, double perception_sq, int k,
+                                           int32_t (*runs)[kThreads], double (*ld2)[kThreads], int32_t (*lq)[kThreads]) {
+    const int t = threadIdx.x;
+    const double pix = pi4.x, piy = pi4.y, piz = pi4.z;
+    int cnt = 0;
+    double worst = INFINITY;  // d2 of the k-th entry once the list is full
+    auto insert = [&](double d2, int32_t q) {
+        // (d2, id_q) before (pd, id_pq)?  ids differ, so the order is total
+        auto before = [&](double pd, int32_t pq) { return d2 < pd || (d2 == pd && b.id[q] < b.id[pq]); };
+        int pos;
+        if (cnt == k) {
+            if (d2 > worst) return;
+            if (!before(worst, lq[k - 1][t])) return;
+            pos = k - 1;  // the last entry falls out
+        } else {
+            pos = cnt++;
+        }
+        while (pos > 0) {
+            const double pd = ld2[pos - 1][t];
+            const int32_t pq = lq[pos - 1][t];
+            if (!before(pd, pq)) break;
+            ld2[pos][t] = pd;
+            lq[pos][t] = pq;
+            pos--;
+        }
+        ld2[pos][t] = d2;
+        lq[pos][t] = q;
+        if (cnt == k) worst = ld2[k - 1][t];
+    };
+    auto test = [&](int32_t c, const double4 qp) {
+        if (c < 0 || c == r) return;
+        const double dx = pix - qp.x, dy = piy - qp.y, dz = piz - qp.z;
+        const double d2 = (dx * dx + dy * dy) + dz * dz;
+        if (d2 < perception_sq && d2 > 0.0001) insert(d2, c);
+    };
+    int nr = 0;
+    auto walk = [&]() {  // the nr noted runs (none empty), back to back
+        int row = 0;
+        int32_t q = runs[0][t], e = runs[1][t];
+        auto next = [&]() -> int32_t {
+            if (q >= e) {
+                if (row + 1 >= nr) { row = nr; return -1; }
+                row++;
+                q = runs[2 * row][t];
+                e = runs[2 * row + 1][t];
+            }
+            return q++;
+        };
+        for (;;) {
+            const int32_t c0 = next();
+            if (c0 < 0) break;
+            const int32_t c1 = next(), c2 = next(), c3 = next();
+            const double4 p0 = b.p[c0], p1 = b.p[c1 < 0 ? c0 : c1], p2 = b.p[c2 < 0 ? c0 : c2], p3 = b.p[c3 < 0 ? c0 : c3];
+            test(c0, p0);
+            test(c1, p1);
+            test(c2, p2);
+            test(c3, p3);
+        }
+        nr = 0;
+    };
+    if (g.range == 1) {
+        // the usual grid: nine rows, looked up three at a time as k_flock does, walked in one go
+        const int cx = cell_coord(pix, g), cy = cell_coord(piy, g), cz = cell_coord(piz, g);
+        const int x_lo = cx - 1 < 0 ? 0 : cx - 1;
+        const int x_hi = cx + 1 > g.dim - 1 ? g.dim - 1 : cx + 1;
+        for (int dcz = -1; dcz <= 1; dcz++) (void)plane_runs<kThreads>(occ, cell_start, g, x_lo, x_hi, cy, cz + dcz, runs, nr);
+    } else {
+        fs_for_each_run(pi4, g, occ, cell_start, [&](int32_t qb, int32_t qe) {
+            if (qe <= qb) return;
+            runs[2 * nr][t] = qb;
+            runs[2 * nr + 1][t] = qe;
+            if (++nr == kTopoRuns) walk();
+        });
     }
-    if (nb_count > 0) {
-        alx /= nb_count; aly /= nb_count; alz /= nb_count;
-        if (steer(alx, aly, alz, vix, viy, viz, P.max_speed, P.max_force, P.ali_w)) { fax = alx; fay = aly; faz = alz; }
-        cox = cox / nb_count - pix; coy = coy / nb_count - piy; coz = coz / nb_count - piz;
-        if (steer(cox, coy, coz, vix, viy, viz, P.max_speed, P.max_force, P.coh_w)) { fcx = cox; fcy = coy; fcz = coz; }
-        avr = (clr + cir) / (nb_count + 1);
-        avg = (clg + cig) / (nb_count + 1);
-        avb = (clb + cib) / (nb_count + 1);
+    if (nr > 0) walk();
+    return cnt;
+}
+
+// compute_flocking_spatial with T_i in the place of the neighbour set + update_physics_numba.  kCap = the largest k this
+// instance serves: k <= 8 runs 256 threads per block (18 KiB of runs + 24 KiB of list = 42 KiB, 3 blocks = 12 waves per
+// CU), k <= 16 runs 128 threads per block (9 + 24 = 33 KiB, 4 blocks = 8 waves per CU).
+template <bool kPhysics, int kCap, int kThreads>
+__global__ __launch_bounds__(kThreads) void k_flock_topo(BoidsAoS b, Boids a, const uint2 *__restrict__ occ,
+                                                         const int32_t *__restrict__ cell_start, int64_t n, GridP g, FlockP P,
+                                                         int k, double *__restrict__ o_sep, double *__restrict__ o_ali,
+                                                         double *__restrict__ o_coh, double *__restrict__ o_avg,
+                                                         int xcd_contiguous) {
+    __shared__ int32_t runs[2 * kTopoRuns][kThreads];
+    __shared__ double ld2[kCap][kThreads];
+    __shared__ int32_t lq[kCap][kThreads];
+    const int t = threadIdx.x;
+    const int64_t r = logical_block(blockIdx.x, gridDim.x, xcd_contiguous) * kThreads + t;
+    if (r >= n) return;
+    const double4 pi4 = b.p[r], vi4 = b.v[r], ci4 = b.c[r];
+    const double pix = pi4.x, piy = pi4.y, piz = pi4.z;
+    const int cnt = topo_select<kCap, kThreads>(b, occ, cell_start, g, r, pi4, P.perception_sq, k, runs, ld2, lq);
+    double sx = 0, sy = 0, sz = 0, alx = 0, aly = 0, alz = 0, cox = 0, coy = 0, coz = 0, clr = 0, clg = 0, clb = 0;
+    int sep_count = 0;
+    auto neighbour = [&](const double4 qp, const double4 qv, const double4 qc) {  // flock.py:150-172
+        const double dx = pix - qp.x, dy = piy - qp.y, dz = piz - qp.z;
+        const double dist_sq = (dx * dx + dy * dy) + dz * dz;
+        if (dist_sq < P.separation_sq) {
+            const double dist = sqrt(dist_sq);
+            const double inv_dist = 1.0 / dist;
+            sx += dx * inv_dist / dist;
+            sy += dy * inv_dist / dist;
+            sz += dz * inv_dist / dist;
+            sep_count++;
+        }
+        alx += qv.x; aly += qv.y; alz += qv.z;
+        cox += qp.x; coy += qp.y; coz += qp.z;
+        clr += qc.x; clg += qc.y; clb += qc.z;
+    };
+    // the list in its order, two entries at a time with all six records in flight
+    for (int h = 0; h < cnt; h += 2) {
+        const int32_t q0 = lq[h][t], q1 = lq[h + 1 < cnt ? h + 1 : h][t];
+        const double4 p0 = b.p[q0], v0 = b.v[q0], c0 = b.c[q0], p1 = b.p[q1], v1 = b.v[q1], c1 = b.c[q1];
+        neighbour(p0, v0, c0);
+        if (h + 1 < cnt) neighbour(p1, v1, c1);
     }
-    if (!kPhysics) {
-        const int64_t o = 3 * (int64_t)b.id[r];
-        o_sep[o] = fsx; o_sep[o + 1] = fsy; o_sep[o + 2] = fsz;
-        o_ali[o] = fax; o_ali[o + 1] = fay; o_ali[o + 2] = faz;
-        o_coh[o] = fcx; o_coh[o + 1] = fcy; o_coh[o + 2] = fcz;
-        o_avg[o] = avr; o_avg[o + 1] = avg; o_avg[o + 2] = avb;
-        return;
+    flock_finish<kPhysics>(b, a, r, P, pix, piy, piz, vi4.x, vi4.y, vi4.z, ci4.x, ci4.y, ci4.z, sx, sy, sz, alx, aly, alz, cox,
+                           coy, coz, clr, clg, clb, sep_count, cnt, o_sep, o_ali, o_coh, o_avg);
+}
+
+// bdmi_topological_neighbours: the lists themselves, rows in the caller's order, padded with -1 / +inf
+template <int kCap, int kThreads>
+__global__ __launch_bounds__(kThreads) void k_topo_rows(BoidsAoS b, const uint2 *__restrict__ occ,
+                                                        const int32_t *__restrict__ cell_start, int64_t n, GridP g,
+                                                        double perception_sq, int k, int32_t *__restrict__ o_ids,
+                                                        double *__restrict__ o_d2, int32_t *__restrict__ o_count) {
+    __shared__ int32_t runs[2 * kTopoRuns][kThreads];
+    __shared__ double ld2[kCap][kThreads];
+    __shared__ int32_t lq[kCap][kThreads];
+    const int t = threadIdx.x;
+    const int64_t r = (int64_t)blockIdx.x * kThreads + t;
+    if (r >= n) return;
+    const int cnt = topo_select<kCap, kThreads>(b, occ, cell_start, g, r, b.p[r], perception_sq, k, runs, ld2, lq);
+    const int64_t i = b.id[r];
+    for (int s = 0; s < k; s++) {
+        o_ids[i * k + s] = s < cnt ? b.id[lq[s][t]] : -1;
+        o_d2[i * k + s] = s < cnt ? ld2[s][t] : INFINITY;
     }
-    double acc[3] = {fsx + fax + fcx, fsy + fay + fcy, fsz + faz + fcz};
-    const double pos[3] = {pix, piy, piz};
-#pragma unroll
-    for (int d = 0; d < 3; d++) {
-        const double dist_pos = pos[d] - (P.bounds - P.margin);
-        if (dist_pos > 0) acc[d] -= fmin(dist_pos / P.margin * 2.0, 1.0) * P.wall_force;
-        const double dist_neg = (-P.bounds + P.margin) - pos[d];
-        if (dist_neg > 0) acc[d] += fmin(dist_neg / P.margin * 2.0, 1.0) * P.wall_force;
-    }
-    double nvx = vix + acc[0] * P.dt, nvy = viy + acc[1] * P.dt, nvz = viz + acc[2] * P.dt;
-    const double speed = sqrt(nvx * nvx + nvy * nvy + nvz * nvz);
-    if (speed > P.max_speed) {
-        const double scale = P.max_speed / speed;
-        nvx *= scale; nvy *= scale; nvz *= scale;
-    }
-    a.vx[r] = nvx; a.vy[r] = nvy; a.vz[r] = nvz;
-    a.px[r] = pix + nvx * P.dt; a.py[r] = piy + nvy * P.dt; a.pz[r] = piz + nvz * P.dt;
-    a.cr[r] = cir + (avr - cir) * P.blend;
-    a.cg[r] = cig + (avg - cig) * P.blend;
-    a.cb[r] = cib + (avb - cib) * P.blend;
-    a.id[r] = b.id[r];
+    o_count[i] = cnt;
 }
 
 __global__ __launch_bounds__(kBlock) void k_split(const double *__restrict__ p, const double *__restrict__ v,
@@ -912,6 +1099,11 @@ struct bdmi_flock {
     size_t tmp_sort_bytes = 0;
     double *stage = nullptr;  // 12 N doubles
     int xcd_contiguous = 1;   // sweep block -> XCD mapping, see logical_block()
+    int nb_mode = BDMI_NEIGHBOURS_METRIC, nb_k = 7;  // bdmi_set_neighbour_mode; BDMI_NEIGHBOURS at create
+    // bdmi_topological_neighbours scratch ((N, topo_cap) ids and d2, (N,) counts), allocated on first use
+    int32_t *topo_ids = nullptr, *topo_cnt = nullptr;
+    double *topo_d2 = nullptr;
+    int topo_cap = 0;
     // render-side reduction scratch (bdmi_visible_vertices), allocated on first use
     uint8_t *vis_flag = nullptr;
     uint32_t *vis_slot = nullptr, *vis_tiles = nullptr;
@@ -980,6 +1172,23 @@ int enqueue_grid(bdmi_flock *f, bool timed) {
     if (timed) NBMI_HIP_CHECK(hipEventRecord(f->ev[2], st));
     NBMI_HIP_CHECK(hipGetLastError());
     return 0;
+}
+
+void dev_release(bdmi_flock *f, void *p);  // defined with the flock analysis
+
+// the sweep of the handle's neighbour mode over the grid enqueue_grid has just built
+template <bool kPhysics>
+void enqueue_sweep(bdmi_flock *f, const FlockP &P, double *d0, double *d1, double *d2, double *d3) {
+    const int64_t n = f->n;
+    if (f->nb_mode != BDMI_NEIGHBOURS_TOPOLOGICAL)
+        k_flock<kPhysics><<<nblocks(n), kBlock, 0, f->stream>>>(f->B, f->A, f->occ, f->cell_start, n, f->grid, P, d0, d1, d2, d3,
+                                                               f->xcd_contiguous);
+    else if (f->nb_k <= 8)
+        k_flock_topo<kPhysics, 8, 256><<<(int)((n + 255) / 256), 256, 0, f->stream>>>(
+            f->B, f->A, f->occ, f->cell_start, n, f->grid, P, f->nb_k, d0, d1, d2, d3, f->xcd_contiguous);
+    else
+        k_flock_topo<kPhysics, kTopoMaxK, 128><<<(int)((n + 127) / 128), 128, 0, f->stream>>>(
+            f->B, f->A, f->occ, f->cell_start, n, f->grid, P, f->nb_k, d0, d1, d2, d3, f->xcd_contiguous);
 }
 
 }  // namespace
@@ -1061,6 +1270,17 @@ static bdmi_flock *bd_create(int64_t n, const double *pos, const double *vel, co
     }
     bdmi_flock *f = new bdmi_flock();
     if (const char *e = getenv("BDMI_XCD")) f->xcd_contiguous = atoi(e) != 0;  // measurement knob
+    // BDMI_NEIGHBOURS=topological or topological:K (K in 1..16, default 7): the initial neighbour mode of ordinary
+    // handles, so that unchanged drivers can be run in it; anything else means metric
+    if (const char *e = getenv("BDMI_NEIGHBOURS")) {
+        int k = 7;
+        char tail = 0;
+        const bool plain = strcmp(e, "topological") == 0;
+        if (!slab && (plain || (sscanf(e, "topological:%d%c", &k, &tail) == 1 && k >= 1 && k <= kTopoMaxK))) {
+            f->nb_mode = BDMI_NEIGHBOURS_TOPOLOGICAL;
+            f->nb_k = k;
+        }
+    }
     f->n = n;
     f->device = device;
     f->slab = slab; f->cap = slab ? capacity : 0;
@@ -1245,8 +1465,7 @@ int bdmi_step(bdmi_flock *f, double dt, int substeps) {
     const FlockP P = make_params(f, dt);
     for (int k = 0; k < substeps; k++) {
         if (int rc = enqueue_grid(f, f->timers)) return rc;
-        k_flock<true><<<nblocks(f->n), kBlock, 0, f->stream>>>(f->B, f->A, f->occ, f->cell_start, f->n, f->grid, P,
-                                                               nullptr, nullptr, nullptr, nullptr, f->xcd_contiguous);
+        enqueue_sweep<true>(f, P, nullptr, nullptr, nullptr, nullptr);
         NBMI_HIP_CHECK(hipGetLastError());
         if (f->timers) {
             NBMI_HIP_CHECK(hipEventRecord(f->ev[3], f->stream));
@@ -1338,8 +1557,7 @@ int bdmi_get_forces(bdmi_flock *f, double *sep, double *ali, double *coh, double
     if (int rc = enqueue_grid(f, false)) return rc;
     double *d0 = f->stage, *d1 = d0 + 3 * n, *d2 = d1 + 3 * n, *d3 = d2 + 3 * n;
     const FlockP P = make_params(f, 0.0);
-    k_flock<false><<<nblocks(n), kBlock, 0, f->stream>>>(f->B, f->A, f->occ, f->cell_start, n, f->grid, P, d0, d1,
-                                                         d2, d3, f->xcd_contiguous);
+    enqueue_sweep<false>(f, P, d0, d1, d2, d3);
     NBMI_HIP_CHECK(hipGetLastError());
     NBMI_HIP_CHECK(hipMemcpyAsync(sep, d0, (size_t)n * 24, hipMemcpyDeviceToHost, f->stream));
     NBMI_HIP_CHECK(hipMemcpyAsync(ali, d1, (size_t)n * 24, hipMemcpyDeviceToHost, f->stream));
@@ -1347,6 +1565,70 @@ int bdmi_get_forces(bdmi_flock *f, double *sep, double *ali, double *coh, double
     NBMI_HIP_CHECK(hipMemcpyAsync(avg, d3, (size_t)n * 24, hipMemcpyDeviceToHost, f->stream));
     NBMI_HIP_CHECK(hipStreamSynchronize(f->stream));
     return 0;
+}
+
+// ---- topological interaction (include/bdmi.h) ---------------------------------------------------------------------
+static int topo_k_check(const char *what, int k) {
+    if (k < 1 || k > kTopoMaxK) {
+        nbmi::set_error("%s: k = %d must be in 1..%d", what, k, kTopoMaxK);
+        return -1;
+    }
+    return 0;
+}
+static int topo_handle_check(bdmi_flock *f, const char *what) {
+    if (!f) { nbmi::set_error("%s: null bdmi_flock handle", what); return -1; }
+    return whole_flock_check(f, what);
+}
+
+int bdmi_set_neighbour_mode(bdmi_flock *f, int mode, int k) {
+    if (int rc = topo_handle_check(f, "bdmi_set_neighbour_mode")) return rc;
+    if (mode != BDMI_NEIGHBOURS_METRIC && mode != BDMI_NEIGHBOURS_TOPOLOGICAL) {
+        nbmi::set_error("bdmi_set_neighbour_mode: unknown mode %d (BDMI_NEIGHBOURS_METRIC = 0, BDMI_NEIGHBOURS_TOPOLOGICAL = 1)",
+                        mode);
+        return -1;
+    }
+    if (mode == BDMI_NEIGHBOURS_TOPOLOGICAL) {
+        if (int rc = topo_k_check("bdmi_set_neighbour_mode", k)) return rc;
+        f->nb_k = k;
+    }
+    f->nb_mode = mode;
+    return 0;
+}
+
+int bdmi_get_neighbour_mode(bdmi_flock *f, int *mode, int *k) {
+    if (!f) { nbmi::set_error("bdmi_get_neighbour_mode: null bdmi_flock handle"); return -1; }
+    if (mode) *mode = f->nb_mode;
+    if (k) *k = f->nb_k;
+    return 0;
+}
+
+int bdmi_topological_neighbours(bdmi_flock *f, int k, int32_t *ids, double *d2, int32_t *count) {
+    if (int rc = topo_handle_check(f, "bdmi_topological_neighbours")) return rc;
+    if (int rc = topo_k_check("bdmi_topological_neighbours", k)) return rc;
+    const int64_t n = f->n;
+    if (n == 0) return 0;
+    if (k > f->topo_cap) {
+        dev_release(f, f->topo_ids); dev_release(f, f->topo_d2);
+        f->topo_ids = nullptr; f->topo_d2 = nullptr;
+        f->topo_cap = 0;
+        if (dev_alloc(f, &f->topo_ids, (size_t)n * k) || dev_alloc(f, &f->topo_d2, (size_t)n * k)) return -2;
+        f->topo_cap = k;
+    }
+    if (!f->topo_cnt && dev_alloc(f, &f->topo_cnt, (size_t)n)) return -2;
+    if (int rc = enqueue_grid(f, false)) return rc;
+    hipStream_t st = f->stream;
+    const double psq = f->params[5] * f->params[5];
+    if (k <= 8)
+        k_topo_rows<8, 256><<<(int)((n + 255) / 256), 256, 0, st>>>(f->B, f->occ, f->cell_start, n, f->grid, psq, k, f->topo_ids,
+                                                                    f->topo_d2, f->topo_cnt);
+    else
+        k_topo_rows<kTopoMaxK, 128><<<(int)((n + 127) / 128), 128, 0, st>>>(f->B, f->occ, f->cell_start, n, f->grid, psq, k,
+                                                                            f->topo_ids, f->topo_d2, f->topo_cnt);
+    NBMI_HIP_CHECK(hipGetLastError());
+    if (ids) NBMI_HIP_CHECK(hipMemcpyAsync(ids, f->topo_ids, (size_t)n * k * 4, hipMemcpyDeviceToHost, st));
+    if (d2) NBMI_HIP_CHECK(hipMemcpyAsync(d2, f->topo_d2, (size_t)n * k * 8, hipMemcpyDeviceToHost, st));
+    if (count) NBMI_HIP_CHECK(hipMemcpyAsync(count, f->topo_cnt, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    return sync_checked(f);
 }
 
 int bdmi_grid_info(bdmi_flock *f, int32_t *grid_dim, int64_t *num_cells, int64_t *occupied) {

@@ -125,6 +125,9 @@ PROTOTYPES = {
     "bdmi_flock_catalogue": (C.c_int, [_vp, _dbl, _i64, _i64, _vp, _vp, _vp, _vp]),
     "bdmi_diagnostics": (C.c_int, [_vp, _vp]),
     "bdmi_neighbour_stats": (C.c_int, [_vp, _dbl, _vp, _vp, _vp]),
+    "bdmi_set_neighbour_mode": (C.c_int, [_vp, C.c_int, C.c_int]),
+    "bdmi_get_neighbour_mode": (C.c_int, [_vp, _vp, _vp]),
+    "bdmi_topological_neighbours": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "bdmi_visible_vertices": (C.c_int, [_vp, _vp, _dbl, _dbl, _dbl, _dbl, _dbl, _vp, _vp, _i64, _vp]),
     "bdmi_render_triangles": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp]),
     "bdmi_render_flock": (C.c_int, [_vp, _vp, _vp, _dbl, _dbl, _dbl, _dbl, _dbl, _vp, _vp, _vp]),

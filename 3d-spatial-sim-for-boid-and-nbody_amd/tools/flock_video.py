@@ -7,11 +7,14 @@ machine without GL, display or window system.
     python -m tools.flock_video --boids 500k --frames 300                  # ffmpeg if on PATH, else raw rgb24 + JSON
     python -m tools.flock_video --boids 2m --resolution 1080p --camera orbit --format ppm -o frames/
     python -m tools.flock_video --boids 2m --frames 600 --diagnostics 10   # + flock.flock.jsonl: flocks, order parameters
+    python -m tools.flock_video --boids 500k --neighbours topological --topological-k 7   # the k nearest within sight
 
 Each frame: flock.update(dt, substeps), render_flock, sink.  Output formats and sinks are those of tools.export.
 With --diagnostics K every K-th frame also appends one JSON line (boids.analysis.jsonl_line) to <output stem>.flock.jsonl:
 the whole flock's row, the number of flocks and links at --link, the mean neighbour count and the rows of the 16 largest
 flocks of at least --min-members boids, all computed on the device (include/bdmi.h).
+With --neighbours topological the flock interacts by the topological rule of include/bdmi.h (--topological-k nearest
+neighbours within the perception radius); the clip's metadata and the analysis lines then name the mode.
 """
 import argparse
 import json
@@ -27,6 +30,7 @@ from tools.export import (CODECS, FORMATS, QUALITY_PRESETS, RESOLUTION_PRESETS, 
 from tools.record import parse_number
 
 CAMERA_MODES = ("fixed", "orbit")
+NEIGHBOUR_MODES = ("metric", "topological")
 MAX_DT = 0.05  # the reference application caps a frame's dt (Application._update)
 
 
@@ -60,6 +64,11 @@ def build_parser():
                     help="linking length of the flock finder (default and at most: the perception radius)")
     ap.add_argument("--min-members", type=int, default=20, metavar="M",
                     help="smallest flock listed in the analysis lines (default: 20)")
+    ap.add_argument("--neighbours", choices=NEIGHBOUR_MODES, default="metric",
+                    help="interaction rule: every boid within the perception radius (metric, the default) or the "
+                         "--topological-k nearest of them (topological)")
+    ap.add_argument("--topological-k", type=int, default=7, metavar="K",
+                    help="neighbours per boid with --neighbours topological, 1..16 (default: 7)")
     return ap
 
 
@@ -114,7 +123,7 @@ def diagnostics_path(output: Path) -> Path:
     return output.with_name((output.stem if output.suffix else output.name) + ".flock.jsonl")
 
 
-def analysis_line(flock, frame, steps, link, min_members) -> str:
+def analysis_line(flock, frame, steps, link, min_members, neighbours=None) -> str:
     """One line of the analysis file for the flock's current state (four device calls, no state copied out)."""
     from boids.analysis import jsonl_line
     fl = flock.flocks(link)
@@ -123,7 +132,7 @@ def analysis_line(flock, frame, steps, link, min_members) -> str:
     count = np.asarray(nb["count"])
     return jsonl_line(frame, steps, flock.diagnostics(), fl["n_flocks"], fl["links"],
                       float(count.mean()) if count.size else 0.0, cat["rows"], flock_labels=cat["label"],
-                      link=link, min_members=min_members, qualifying=cat["count"])
+                      link=link, min_members=min_members, qualifying=cat["count"], neighbours=neighbours)
 
 
 def run(args, make_flock=None, make_renderer=None, say=print) -> dict:
@@ -135,6 +144,11 @@ def run(args, make_flock=None, make_renderer=None, say=print) -> dict:
     min_members = int(getattr(args, "min_members", 20))
     if every < 0 or min_members < 1:
         raise ValueError("--diagnostics must not be negative and --min-members at least 1")
+    topo_k = int(getattr(args, "topological_k", 7))
+    topological = getattr(args, "neighbours", "metric") == "topological"
+    if topological and not 1 <= topo_k <= 16:
+        raise ValueError("--topological-k must be in 1..16")
+    neighbours = {"mode": "topological", "k": topo_k} if topological else None
     if make_flock is None:
         from boids import Flock
         make_flock = lambda n, seed, device: Flock(n, seed=seed, device=device)  # noqa: E731
@@ -157,6 +171,8 @@ def run(args, make_flock=None, make_renderer=None, say=print) -> dict:
     t_step = t_render = t_write = t_analysis = 0.0
     t0 = time.perf_counter()
     try:
+        if topological:
+            flock.set_neighbour_mode("topological", topo_k)
         if args.warmup:
             flock.update(dt, args.warmup)
         img = np.empty((height, width, 3), dtype=np.uint8)
@@ -177,7 +193,8 @@ def run(args, make_flock=None, make_renderer=None, say=print) -> dict:
             if every and i % every == 0:
                 ta = time.perf_counter()
                 steps = args.warmup + (i + 1) * args.substeps
-                diag_file.write(analysis_line(flock, i, steps, getattr(args, "link", None), min_members) + "\n")
+                diag_file.write(analysis_line(flock, i, steps, getattr(args, "link", None), min_members,
+                                              neighbours) + "\n")
                 diag_lines += 1
                 t_analysis += time.perf_counter() - ta
         ok = True
@@ -198,6 +215,8 @@ def run(args, make_flock=None, make_renderer=None, say=print) -> dict:
                          "warmup": args.warmup, "params": {k: float(v) for k, v in config.BOIDS.items()}}
         meta["camera"] = {"mode": args.camera, "speed": args.camera_speed, "radius": args.camera_radius,
                           "angle": args.camera_angle, "theta": args.camera_theta}
+        if topological:
+            meta["flock"]["neighbours"] = neighbours
         if every:
             meta["diagnostics"] = {"file": diag_path.name, "every": every, "link": getattr(args, "link", None),
                                    "min_members": min_members, "lines": diag_lines}

@@ -50,7 +50,8 @@ int bdmi_get_cell_indices(bdmi_flock *f, int32_t *cell_indices);
  * caller-side pre-fill of Flock.update (forces 0, avg_colors = colors; flock.py:633-636). */
 int bdmi_get_forces(bdmi_flock *f, double *sep, double *ali, double *coh, double *avg_colors);
 /* grid facts: dim, num_cells, non-empty cells of the last built grid.  The last built grid is that of the last
- * bdmi_step, or of the current positions after bdmi_get_forces or one of the four flock-analysis calls below. */
+ * bdmi_step, or of the current positions after bdmi_get_forces, one of the four flock-analysis calls or
+ * bdmi_topological_neighbours below. */
 int bdmi_grid_info(bdmi_flock *f, int32_t *grid_dim, int64_t *num_cells, int64_t *occupied);
 /* device ms accumulated per phase [cells+sort, reorder+table, sweep+physics], steps counted */
 int bdmi_enable_timers(bdmi_flock *f, int enable);
@@ -119,6 +120,51 @@ int bdmi_flock_catalogue(bdmi_flock *f, double link, int64_t min_members, int64_
 int bdmi_diagnostics(bdmi_flock *f, double *row16);
 int bdmi_neighbour_stats(bdmi_flock *f, double radius, int32_t *count /* (N,) */, double *nn_d2 /* (N,) */,
                          int64_t *evals); /* each output may be NULL */
+
+/* ---- topological interaction: the k nearest neighbours within sight ----------------------------
+ * The reference knows one interaction rule, the metric one: every boid within perception_radius counts.  The other
+ * standard flocking model is topological (Ballerini et al. 2008: starlings interact with their 6-7 nearest neighbours,
+ * whatever their distance), which gives flocks whose cohesion does not depend on their density.  It is opt-in per handle:
+ * a handle that never enables it runs the metric kernels and gives their bits.  This text is the specification; the
+ * kernel (csrc/bdmi.hip, k_flock_topo) and the tests' NumPy restatement (tests/topo_ref.py) both follow it.
+ *
+ * For the handle's current state and a boid i:
+ *   d2(i, j) = (dx dx + dy dy) + dz dz with dx = p_i - p_j, float64, no FMA: the sweep's own expression.
+ *   The METRIC set N_i = { j != i : 1e-4 < d2(i, j) < perception_radius^2 }: exactly the reference's window (flock.py:150).
+ *   The TOPOLOGICAL set T_i = the min(k, |N_i|) members of N_i that come first in ascending lexicographic order of
+ *     (d2(i, j), id_j), id_j being the caller's boid index.  The tie-break makes T_i unique.
+ *   STILL BOUNDED BY PERCEPTION: a neighbour is never further away than the perception radius.  This is "the k nearest
+ *     within sight", not an unbounded k-nearest search: the 27-cell neighbourhood of the sweep's grid covers it exactly.
+ *   Forces and colours: compute_flocking_spatial's formulas (flock.py:150-238) with T_i in the place of the neighbour
+ *     set: neighbor_count = |T_i|; the separation terms come from those members of T_i with d2 < separation_radius^2;
+ *     avg_colors = (sum over T_i + own) / (|T_i| + 1); steer(), the pre-fill and update_physics_numba are unchanged.
+ *   FIXED SUMMATION ORDER: every per-boid sum (separation, alignment, cohesion, colour) starts at +0.0 and adds its terms
+ *     one by one in the order of T_i above.  With correctly rounded sqrt and divide and without FMA, the four force arrays
+ *     and the stepped state are a pure function of the state and the ids: they do not depend on the cell order, on what
+ *     earlier steps did to the row order, or on the block order (BDMI_XCD), and a NumPy restatement reproduces them bit
+ *     for bit, separation included (the metric sweep's separation sum has no such order).
+ *   1 <= k <= 16.
+ *
+ * bdmi_set_neighbour_mode: BDMI_NEIGHBOURS_METRIC (the default: the reference's rule, the metric kernels; k is ignored and
+ *   the handle's k is kept) or BDMI_NEIGHBOURS_TOPOLOGICAL with k.  bdmi_step and bdmi_get_forces follow the handle's mode;
+ *   the topological sweep counts in phase 3 of the timers.  bdmi_get_neighbour_mode reads the mode and k back.
+ * bdmi_topological_neighbours: a parity hook like bdmi_get_cell_indices, in either mode and with its own k.  Row i
+ *   (caller's order) of ids / d2 lists T_i's ids in order and their d2, padded with -1 / +inf; count[i] = |T_i|.  It
+ *   builds the grid for the current positions as bdmi_get_forces does and changes nothing a later step reads.
+ * Refused with NBMI_ERR_ARG (message "<call>: ..."), before anything is launched and with the outputs and the mode
+ *   untouched: an unknown mode, k outside 1..16 (the message names k), a null handle, and slab handles
+ *   (bdmi_create_slab) for both the setter and the hook.  Slab support is a follow-up: the order (d2, GLOBAL id) would
+ *   make the slabs' results bit-identical to one GPU's, since nothing else of a slab's row order enters the sums.
+ * N == 0 and N == 1 succeed: zero forces, count = 0.
+ * Environment BDMI_NEIGHBOURS, read at create like BDMI_XCD: "topological" or "topological:K" (K in 1..16, default 7) sets
+ *   the initial mode of handles that allow it; anything else means metric.  It lets unchanged drivers run in this mode.
+ * Scratch of the hook, allocated at its first call: 12 k + 4 bytes per boid. */
+#define BDMI_NEIGHBOURS_METRIC 0
+#define BDMI_NEIGHBOURS_TOPOLOGICAL 1
+int bdmi_set_neighbour_mode(bdmi_flock *f, int mode, int k);
+int bdmi_get_neighbour_mode(bdmi_flock *f, int *mode, int *k); /* either may be NULL */
+int bdmi_topological_neighbours(bdmi_flock *f, int k, int32_t *ids /* (N,k) */, double *d2 /* (N,k) */,
+                                int32_t *count /* (N,) */); /* each may be NULL */
 
 /* ---- multi-GPU: x-slabs with a one-cell halo -----------------------------------------
  * A rank owns the boids with x_lo <= x < x_hi (a whole number of cell planes, at least two cells wide); the
