@@ -18,6 +18,7 @@
 #include <string.h>
 
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -42,9 +43,11 @@ struct BoidsAoS {
     int32_t *id;
 };
 
+// Flock.__init__'s grid (flock.py:478-481): the cell is the perception radius, so a boid's neighbours lie in the 3 x 3 x 3
+// cells around its own, whatever the parameters
 struct GridP {
     double cell_size, offset;
-    int dim, range;
+    int dim;
 };
 
 struct FlockP {
@@ -173,30 +176,53 @@ __device__ __forceinline__ int64_t logical_block(int b, int nb, int xcd_contiguo
     return (int64_t)xcd * q + (xcd < rem ? xcd : rem) + j;
 }
 
+// The neighbour sums of one boid, and one neighbour's contribution to them (flock.py:150-172): shared by the metric
+// sweep (k_flock, both of its candidate loops) and the topological one (k_flock_topo).
+struct FlockSums {
+    double sx = 0, sy = 0, sz = 0, alx = 0, aly = 0, alz = 0, cox = 0, coy = 0, coz = 0, clr = 0, clg = 0, clb = 0;
+    int sep_count = 0, nb_count = 0;
+    __device__ __forceinline__ void add(const double4 &pi, const double4 &qp, const double4 &qv, const double4 &qc,
+                                        double separation_sq) {
+        const double dx = pi.x - qp.x, dy = pi.y - qp.y, dz = pi.z - qp.z;
+        const double dist_sq = dx * dx + dy * dy + dz * dz;
+        if (dist_sq < separation_sq) {
+            const double dist = sqrt(dist_sq);
+            const double inv_dist = 1.0 / dist;
+            sx += dx * inv_dist / dist;
+            sy += dy * inv_dist / dist;
+            sz += dz * inv_dist / dist;
+            sep_count++;
+        }
+        alx += qv.x; aly += qv.y; alz += qv.z;
+        cox += qp.x; coy += qp.y; coz += qp.z;
+        clr += qc.x; clg += qc.y; clb += qc.z;
+        nb_count++;
+    }
+};
+
 // The end of compute_flocking_spatial (means and steer(), flock.py:174-238) and update_physics_numba (flock.py:241-308)
-// for the boid at rank r, from its neighbour sums: shared by the metric sweep (k_flock) and the topological one
-// (k_flock_topo).  kPhysics=false: write the four force arrays (caller's boid order) instead of integrating.
+// for the boid at rank r (records pi4, vi4, ci4), from its neighbour sums.  kPhysics=false: write the four force arrays
+// (caller's boid order) instead of integrating.
 template <bool kPhysics>
-__device__ __forceinline__ void flock_finish(const BoidsAoS &b, const Boids &a, int64_t r, const FlockP &P, double pix, double piy,
-                                             double piz, double vix, double viy, double viz, double cir, double cig, double cib,
-                                             double sx, double sy, double sz, double alx, double aly, double alz, double cox,
-                                             double coy, double coz, double clr, double clg, double clb, int sep_count,
-                                             int nb_count, double *__restrict__ o_sep, double *__restrict__ o_ali,
-                                             double *__restrict__ o_coh, double *__restrict__ o_avg) {
+__device__ __forceinline__ void flock_finish(const BoidsAoS &b, const Boids &a, int64_t r, const FlockP &P, const double4 &pi4,
+                                             const double4 &vi4, const double4 &ci4, FlockSums S, double *__restrict__ o_sep,
+                                             double *__restrict__ o_ali, double *__restrict__ o_coh, double *__restrict__ o_avg) {
+    const double pix = pi4.x, piy = pi4.y, piz = pi4.z, vix = vi4.x, viy = vi4.y, viz = vi4.z, cir = ci4.x, cig = ci4.y, cib = ci4.z;
+    const int nb_count = S.nb_count;
     double fsx = 0, fsy = 0, fsz = 0, fax = 0, fay = 0, faz = 0, fcx = 0, fcy = 0, fcz = 0;
     double avr = cir, avg = cig, avb = cib;  // caller pre-fill: avg_colors <- colors (flock.py:636)
-    if (sep_count > 0) {
-        sx /= sep_count; sy /= sep_count; sz /= sep_count;
-        if (steer(sx, sy, sz, vix, viy, viz, P.max_speed, P.max_force, P.sep_w)) { fsx = sx; fsy = sy; fsz = sz; }
+    if (S.sep_count > 0) {
+        S.sx /= S.sep_count; S.sy /= S.sep_count; S.sz /= S.sep_count;
+        if (steer(S.sx, S.sy, S.sz, vix, viy, viz, P.max_speed, P.max_force, P.sep_w)) { fsx = S.sx; fsy = S.sy; fsz = S.sz; }
     }
     if (nb_count > 0) {
-        alx /= nb_count; aly /= nb_count; alz /= nb_count;
-        if (steer(alx, aly, alz, vix, viy, viz, P.max_speed, P.max_force, P.ali_w)) { fax = alx; fay = aly; faz = alz; }
-        cox = cox / nb_count - pix; coy = coy / nb_count - piy; coz = coz / nb_count - piz;
-        if (steer(cox, coy, coz, vix, viy, viz, P.max_speed, P.max_force, P.coh_w)) { fcx = cox; fcy = coy; fcz = coz; }
-        avr = (clr + cir) / (nb_count + 1);
-        avg = (clg + cig) / (nb_count + 1);
-        avb = (clb + cib) / (nb_count + 1);
+        S.alx /= nb_count; S.aly /= nb_count; S.alz /= nb_count;
+        if (steer(S.alx, S.aly, S.alz, vix, viy, viz, P.max_speed, P.max_force, P.ali_w)) { fax = S.alx; fay = S.aly; faz = S.alz; }
+        S.cox = S.cox / nb_count - pix; S.coy = S.coy / nb_count - piy; S.coz = S.coz / nb_count - piz;
+        if (steer(S.cox, S.coy, S.coz, vix, viy, viz, P.max_speed, P.max_force, P.coh_w)) { fcx = S.cox; fcy = S.coy; fcz = S.coz; }
+        avr = (S.clr + cir) / (nb_count + 1);
+        avg = (S.clg + cig) / (nb_count + 1);
+        avb = (S.clb + cib) / (nb_count + 1);
     }
     if (!kPhysics) {
         const int64_t o = 3 * (int64_t)b.id[r];
@@ -229,60 +255,125 @@ __device__ __forceinline__ void flock_finish(const BoidsAoS &b, const Boids &a, 
     a.id[r] = b.id[r];
 }
 
-// The candidate runs of the three rows (cy - 1 .. cy + 1) of cell plane ncz on the usual grid (range == 1), appended to
-// the lane's notes runs[2 nr], runs[2 nr + 1] in row order; returns whether one of them is longer than 4095.  Shared by
-// the metric sweep (k_flock) and the topological one (topo_select).
+// ---- the candidate runs of a boid ----------------------------------------------------------------------------------------
+// The reference visits the 27 cells around a boid one by one (flock.py:117-132).  Cells that differ only in x have
+// consecutive indices, and boids are sorted by cell index, so the candidates of one (y, z) row of cells are ONE contiguous
+// run of sorted boids: nine runs instead of 27 cell visits, each found with two rank lookups in the compact table.  Same
+// candidate set as the reference; the floating-point sums run in a different order (the reference's own order inside a
+// cell is unspecified anyway: np.argsort, flock.py:618).
+//
+// emit(q_begin, q_end) for the non-empty rows around the boid at p, in row order (z outer, y inner): the one lookup of
+// every kernel that sweeps the grid.  A row of cells is 3 cells = at most two words of the occupancy table, and what a row
+// costs is a chain of dependent loads (table word -> run bounds -> candidates), not arithmetic: the three rows of a z plane
+// go through each stage TOGETHER, so that their loads are in flight at the same time.
+template <class Emit>
+__device__ __forceinline__ void for_each_run(const double4 &p, const GridP &g, const uint2 *__restrict__ occ,
+                                             const int32_t *__restrict__ cell_start, Emit emit) {
+    const int cx = cell_coord(p.x, g), cy = cell_coord(p.y, g), cz = cell_coord(p.z, g);
+    const int x_lo = cx - 1 < 0 ? 0 : cx - 1;
+    const int x_hi = cx + 1 > g.dim - 1 ? g.dim - 1 : cx + 1;
+    for (int ncz = cz - 1; ncz <= cz + 1; ncz++) {
+        const bool zok = ncz >= 0 && ncz < g.dim;
+        uint2 wa[3], wb[3];
+        int lo_bit[3], hi_bit[3];
+        bool two[3], rok[3];
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            const int ncy = cy + j - 1;
+            rok[j] = zok && ncy >= 0 && ncy < g.dim;
+            const int64_t row = (int64_t)ncy * g.dim + (int64_t)ncz * g.dim * g.dim;
+            const int64_t c_lo = row + x_lo, c_hi = row + x_hi;
+            lo_bit[j] = (int)(c_lo & 31);
+            hi_bit[j] = (int)(c_hi & 31);
+            two[j] = (c_lo >> 5) != (c_hi >> 5);
+            wa[j] = rok[j] ? occ[c_lo >> 5] : make_uint2(0u, 0u);
+            wb[j] = (rok[j] && two[j]) ? occ[c_hi >> 5] : make_uint2(0u, 0u);
+        }
+        int32_t qb[3], qe[3];
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            uint32_t ba = wa[j].x & (~0u << lo_bit[j]);
+            uint32_t bb = wb[j].x & (~0u >> (31 - hi_bit[j]));
+            if (!two[j]) { ba &= ~0u >> (31 - hi_bit[j]); bb = 0u; }
+            qb[j] = 0; qe[j] = 0;
+            if (rok[j] && (ba | bb)) {
+                // first and last non-empty cell of the row
+                const uint2 fw = ba ? wa[j] : wb[j];
+                const int first = ba ? __ffs(ba) - 1 : __ffs(bb) - 1;
+                const uint2 lw = bb ? wb[j] : wa[j];
+                const int last = bb ? 31 - __clz(bb) : 31 - __clz(ba);
+                const uint32_t k_lo = fw.y + __popc(fw.x & ((1u << first) - 1u));
+                const uint32_t k_hi = lw.y + __popc(lw.x & ((1u << last) - 1u)) + 1u;
+                qb[j] = cell_start[k_lo];
+                qe[j] = cell_start[k_hi];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 3; j++)
+            if (qe[j] > qb[j]) emit(qb[j], qe[j]);
+    }
+}
+
+// The sweeps (k_flock, topo_select) only NOTE the runs, in the lane's LDS column runs[2 row], runs[2 row + 1][thread], and
+// walk all nine in ONE loop behind the lookups [r4]; only the non-empty runs are noted, so that loop never has to step over
+// an empty one.  Returns their number; big = one of them is longer than 4095.
 template <int kThreads>
-__device__ __forceinline__ bool plane_runs(const uint2 *__restrict__ occ, const int32_t *__restrict__ cell_start, const GridP &g,
-                                           int x_lo, int x_hi, int cy, int ncz, int32_t (*runs)[kThreads], int &nr) {
-    bool big = false;
-    const bool zok = ncz >= 0 && ncz < g.dim;
-    uint2 wa[3], wb[3];
-    int lo_bit[3], hi_bit[3];
-    bool two[3], rok[3];
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-        const int ncy = cy + j - 1;
-        rok[j] = zok && ncy >= 0 && ncy < g.dim;
-        const int64_t row = (int64_t)ncy * g.dim + (int64_t)ncz * g.dim * g.dim;
-        const int64_t c_lo = row + x_lo, c_hi = row + x_hi;
-        lo_bit[j] = (int)(c_lo & 31);
-        hi_bit[j] = (int)(c_hi & 31);
-        two[j] = (c_lo >> 5) != (c_hi >> 5);
-        wa[j] = rok[j] ? occ[c_lo >> 5] : make_uint2(0u, 0u);
-        wb[j] = (rok[j] && two[j]) ? occ[c_hi >> 5] : make_uint2(0u, 0u);
+__device__ __forceinline__ int note_runs(const double4 &p, const GridP &g, const uint2 *__restrict__ occ,
+                                         const int32_t *__restrict__ cell_start, int32_t (*runs)[kThreads], bool &big) {
+    int nr = 0;
+    big = false;
+    for_each_run(p, g, occ, cell_start, [&](int32_t qb, int32_t qe) {
+        runs[2 * nr][threadIdx.x] = qb;
+        runs[2 * nr + 1][threadIdx.x] = qe;
+        nr++;
+        big = big || qe - qb > 4095;
+    });
+    return nr;
+}
+
+// A lane's nr > 0 noted runs back to back: next() is the next candidate rank, or -1 behind the last one, and `code` its
+// (row << 12) | offset in the row's run (k_flock's 16-bit note of a neighbour).
+template <int kThreads>
+struct RunCursor {
+    const int32_t (*runs)[kThreads];
+    int nr, row = 0;
+    int32_t q, e, q_first;
+    __device__ __forceinline__ RunCursor(const int32_t (*runs_)[kThreads], int nr_) : runs(runs_), nr(nr_) {
+        q = q_first = runs[0][threadIdx.x];
+        e = runs[1][threadIdx.x];
     }
-    int32_t qb[3], qe[3];
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-        uint32_t ba = wa[j].x & (~0u << lo_bit[j]);
-        uint32_t bb = wb[j].x & (~0u >> (31 - hi_bit[j]));
-        if (!two[j]) { ba &= ~0u >> (31 - hi_bit[j]); bb = 0u; }
-        qb[j] = 0; qe[j] = 0;
-        if (rok[j] && (ba | bb)) {
-            // first and last non-empty cell of the row
-            const uint2 fw = ba ? wa[j] : wb[j];
-            const int first = ba ? __ffs(ba) - 1 : __ffs(bb) - 1;
-            const uint2 lw = bb ? wb[j] : wa[j];
-            const int last = bb ? 31 - __clz(bb) : 31 - __clz(ba);
-            const uint32_t k_lo = fw.y + __popc(fw.x & ((1u << first) - 1u));
-            const uint32_t k_hi = lw.y + __popc(lw.x & ((1u << last) - 1u)) + 1u;
-            qb[j] = cell_start[k_lo];
-            qe[j] = cell_start[k_hi];
+    __device__ __forceinline__ int32_t next(unsigned &code) {
+        if (q >= e) {  // the run is used up: on to the next noted one (none of them is empty)
+            if (row + 1 >= nr) { row = nr; return -1; }
+            row++;
+            q = q_first = runs[2 * row][threadIdx.x];
+            e = runs[2 * row + 1][threadIdx.x];
         }
+        code = ((unsigned)row << 12) | (unsigned)(q - q_first);
+        return q++;
     }
-    // [r4] the runs are only noted here; ONE loop behind the three planes walks all nine (below)
-    // (only the NON-EMPTY runs are noted, in row order: the loop below then never has to step over an empty one)
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-        if (qe[j] > qb[j]) {
-            runs[2 * nr][threadIdx.x] = qb[j];
-            runs[2 * nr + 1][threadIdx.x] = qe[j];
-            nr++;
-        }
-        big = big || qe[j] - qb[j] > 4095;
+};
+// The walk over a lane's noted runs: four candidates per trip with their position records requested together;
+// before_trip() ahead of every trip, test(rank, code, position record) for every candidate in run order.  (A lane
+// without runs leaves at once: with the cursor's first loads behind a condition of their own the compiler wrapped lookup
+// and walk into one wave-level loop, 1.1 - 1.6 % on the topological sweep at k = 16: profiles/boids_runs_ab.txt.)
+template <int kThreads, class Before, class Test>
+__device__ __forceinline__ void walk_runs(const double4 *__restrict__ pos, const int32_t (*runs)[kThreads], int nr,
+                                          Before before_trip, Test test) {
+    if (nr == 0) return;
+    RunCursor<kThreads> cur(runs, nr);
+    for (;;) {
+        before_trip();
+        unsigned k0 = 0, k1 = 0, k2 = 0, k3 = 0;
+        const int32_t c0 = cur.next(k0);
+        if (c0 < 0) break;
+        const int32_t c1 = cur.next(k1), c2 = cur.next(k2), c3 = cur.next(k3);
+        const double4 p0 = pos[c0], p1 = pos[c1 < 0 ? c0 : c1], p2 = pos[c2 < 0 ? c0 : c2], p3 = pos[c3 < 0 ? c0 : c3];
+        test(c0, k0, p0);
+        if (c1 >= 0) test(c1, k1, p1);
+        if (c2 >= 0) test(c2, k2, p2);
+        if (c3 >= 0) test(c3, k3, p3);
     }
-    return big;
 }
 
 // compute_flocking_spatial (flock.py:68-238) + update_physics_numba (flock.py:241-308).
@@ -307,165 +398,60 @@ __global__ __launch_bounds__(kBlock) void k_flock(BoidsAoS b, Boids a, const uin
         a.id[r] = b.id[r];
         return;
     }
-    const double pix = pi4.x, piy = pi4.y, piz = pi4.z;
-    const double vix = vi4.x, viy = vi4.y, viz = vi4.z;
-    const double cir = ci4.x, cig = ci4.y, cib = ci4.z;
-    const int cx = cell_coord(pix, g), cy = cell_coord(piy, g), cz = cell_coord(piz, g);
-    double sx = 0, sy = 0, sz = 0, alx = 0, aly = 0, alz = 0, cox = 0, coy = 0, coz = 0, clr = 0, clg = 0, clb = 0;
-    int sep_count = 0, nb_count = 0;
-    // The reference visits the (2 range + 1)^3 neighbour cells one by one (flock.py:117-132).  Cells that
-    // differ only in x have consecutive indices, and boids are sorted by cell index, so the candidates
-    // of one (y, z) row of cells are ONE contiguous run of sorted boids: (2 range + 1)^2 runs instead of
-    // (2 range + 1)^3 cell visits, found with two rank lookups in the compact table.  Same candidate
-    // set as the reference; the floating-point sums run in a different order (the reference's own
-    // order inside a cell is unspecified anyway: np.argsort, flock.py:618).
-    const int x_lo = cx - g.range < 0 ? 0 : cx - g.range;
-    const int x_hi = cx + g.range > g.dim - 1 ? g.dim - 1 : cx + g.range;
-    // one candidate: the reference's test and sums (flock.py:134-172)
-    auto candidate = [&](int32_t q) {
-        if (q == r) return;
-        const double4 qp = b.p[q];
-        const double dx = pix - qp.x, dy = piy - qp.y, dz = piz - qp.z;
+    FlockSums S;
+    // the reference's test of one candidate (flock.py:134-148)
+    auto in_sight = [&](const double4 &qp) {
+        const double dx = pi4.x - qp.x, dy = pi4.y - qp.y, dz = pi4.z - qp.z;
         const double dist_sq = dx * dx + dy * dy + dz * dz;
-        if (dist_sq < P.perception_sq && dist_sq > 0.0001) {
-            const double dist = sqrt(dist_sq);
-            if (dist_sq < P.separation_sq) {
-                const double inv_dist = 1.0 / dist;
-                sx += dx * inv_dist / dist;
-                sy += dy * inv_dist / dist;
-                sz += dz * inv_dist / dist;
-                sep_count++;
-            }
-            const double4 qv = b.v[q], qc = b.c[q];
-            alx += qv.x; aly += qv.y; alz += qv.z;
-            cox += qp.x; coy += qp.y; coz += qp.z;
-            clr += qc.x; clg += qc.y; clb += qc.z;
-            nb_count++;
-        }
+        return dist_sq < P.perception_sq && dist_sq > 0.0001;
     };
-    if (g.range == 1) {
-        // The usual grid (cell = perception radius, flock.py:478-481).  A row of cells is 3 cells = at most two
-        // words of the occupancy table, and what a row costs is a chain of dependent loads (table word -> run
-        // bounds -> candidates), not arithmetic: the three rows of a z plane go through each stage TOGETHER, so
-        // that their loads are in flight at the same time.  Same rows, same order, same sums as the loop below.
-        bool big = false;
-        int nr = 0;  // non-empty runs noted so far
-        for (int dcz = -1; dcz <= 1; dcz++)
-            big = plane_runs<kBlock>(occ, cell_start, g, x_lo, x_hi, cy, cz + dcz, runs, nr) || big;
-        // [r4] One flattened candidate loop per boid instead of nine, in two phases.  In the state flocks reach (53
-        // candidates per boid instead of 9, two thirds of the cells empty, the rest holding more) the nine per-row
-        // loops cost a wave the SUM of the rows' longest runs among its 64 boids; one loop over a lane's nine runs back
-        // to back costs the longest TOTAL.  And only one candidate in six is a neighbour (a sphere of one cell size in
-        // a cube of three), yet nearly every trip of the loop had SOME lane with one, so the wave ran the expensive
-        // half of the body - a float64 square root, four divisions, two dependent 32-byte loads - on every trip with
-        // a sixth of its lanes (66 % of the sweep's wave cycles were waits, 85 vector instructions per trip:
-        // profiles/r04_boids_steady_state_ab.txt).  Now phase 1 only tests distances, four candidates per trip
-        // with their position records requested together, and notes the neighbours (16 bits each: row and offset in
-        // the row's run) in a per-lane list in LDS; phase 2 walks that list - every lane busy with a real neighbour,
-        // two at a time with all six records in flight.  Same neighbours in the same order: results unchanged bit
-        // for bit.  Sweep at 2 M boids: 0.275 -> 0.205 ms on the initial state, 0.783 -> 0.579 ms after 1000 steps.
-        // (Measured and dropped: phase 1 on an fp32 copy of the positions relative to the cell centres, eight per trip,
-        // float64 re-test inside the fp32 error band - same sets, 0.67 ms: the sweep waits for its gathers, it is not
-        // short of arithmetic or bytes.)
-        int nh = 0;
-        auto neighbour = [&](const double4 qp, const double4 qv, const double4 qc) {  // flock.py:150-172
-            const double dx = pix - qp.x, dy = piy - qp.y, dz = piz - qp.z;
-            const double dist_sq = dx * dx + dy * dy + dz * dz;
-            if (dist_sq < P.separation_sq) {
-                const double dist = sqrt(dist_sq);
-                const double inv_dist = 1.0 / dist;
-                sx += dx * inv_dist / dist;
-                sy += dy * inv_dist / dist;
-                sz += dz * inv_dist / dist;
-                sep_count++;
-            }
-            alx += qv.x; aly += qv.y; alz += qv.z;
-            cox += qp.x; coy += qp.y; coz += qp.z;
-            clr += qc.x; clg += qc.y; clb += qc.z;
-            nb_count++;
-        };
-        auto flush = [&]() {
-            for (int h = 0; h < nh; h += 2) {
-                const unsigned e0 = hits[h][threadIdx.x], e1 = hits[h + 1 < nh ? h + 1 : h][threadIdx.x];
-                const int32_t q0 = runs[2 * (e0 >> 12)][threadIdx.x] + (int32_t)(e0 & 4095u);
-                const int32_t q1 = runs[2 * (e1 >> 12)][threadIdx.x] + (int32_t)(e1 & 4095u);
-                const double4 p0 = b.p[q0], v0 = b.v[q0], c0 = b.c[q0], p1 = b.p[q1], v1 = b.v[q1], c1 = b.c[q1];
-                neighbour(p0, v0, c0);
-                if (h + 1 < nh) neighbour(p1, v1, c1);
-            }
-            nh = 0;
-        };
-        int row = 0;
-        int32_t q = 0, e = 0, q_first = 0;
-        if (nr > 0) { q = q_first = runs[0][threadIdx.x]; e = runs[1][threadIdx.x]; }
-        auto next = [&](unsigned &code) -> int32_t {
-            if (q >= e) {  // the run is used up: on to the next noted one (none of them is empty)
-                if (row + 1 >= nr) { row = nr; return -1; }
-                row++;
-                q = q_first = runs[2 * row][threadIdx.x];
-                e = runs[2 * row + 1][threadIdx.x];
-            }
-            code = ((unsigned)row << 12) | (unsigned)(q - q_first);
-            return q++;
-        };
-        auto test = [&](int32_t c, unsigned code, const double4 qp) {
-            if (c < 0 || c == r) return;
-            const double dx = pix - qp.x, dy = piy - qp.y, dz = piz - qp.z;
-            const double dist_sq = dx * dx + dy * dy + dz * dz;
-            if (dist_sq < P.perception_sq && dist_sq > 0.0001) hits[nh++][threadIdx.x] = (unsigned short)code;
-        };
-        if (big) {
-            // a run of more than 4095 boids (three cells!): its offsets do not fit the 16-bit notes - such a boid
-            // takes its candidates one by one, as the loop for other grids below does
-            for (int k = 0; k < nr; k++)
-                for (int32_t c = runs[2 * k][threadIdx.x]; c < runs[2 * k + 1][threadIdx.x]; c++) candidate(c);
-        } else
-        for (;;) {
-            if (nh > kHitCap - 4) flush();
-            unsigned k0 = 0, k1 = 0, k2 = 0, k3 = 0;
-            const int32_t c0 = next(k0);
-            if (c0 < 0) break;
-            const int32_t c1 = next(k1), c2 = next(k2), c3 = next(k3);
-            const double4 p0 = b.p[c0], p1 = b.p[c1 < 0 ? c0 : c1], p2 = b.p[c2 < 0 ? c0 : c2], p3 = b.p[c3 < 0 ? c0 : c3];
-            test(c0, k0, p0);
-            test(c1, k1, p1);
-            test(c2, k2, p2);
-            test(c3, k3, p3);
+    bool big;
+    const int nr = note_runs<kBlock>(pi4, g, occ, cell_start, runs, big);
+    // [r4] One flattened candidate loop per boid instead of nine, in two phases.  In the state flocks reach (53
+    // candidates per boid instead of 9, two thirds of the cells empty, the rest holding more) the nine per-row
+    // loops cost a wave the SUM of the rows' longest runs among its 64 boids; one loop over a lane's nine runs back
+    // to back costs the longest TOTAL.  And only one candidate in six is a neighbour (a sphere of one cell size in
+    // a cube of three), yet nearly every trip of the loop had SOME lane with one, so the wave ran the expensive
+    // half of the body - a float64 square root, four divisions, two dependent 32-byte loads - on every trip with
+    // a sixth of its lanes (66 % of the sweep's wave cycles were waits, 85 vector instructions per trip:
+    // profiles/r04_boids_steady_state_ab.txt).  Now phase 1 only tests distances, four candidates per trip
+    // with their position records requested together, and notes the neighbours (16 bits each: row and offset in
+    // the row's run) in a per-lane list in LDS; phase 2 walks that list - every lane busy with a real neighbour,
+    // two at a time with all six records in flight.  Same neighbours in the same order: results unchanged bit
+    // for bit.  Sweep at 2 M boids: 0.275 -> 0.205 ms on the initial state, 0.783 -> 0.579 ms after 1000 steps.
+    // (Measured and dropped: phase 1 on an fp32 copy of the positions relative to the cell centres, eight per trip,
+    // float64 re-test inside the fp32 error band - same sets, 0.67 ms: the sweep waits for its gathers, it is not
+    // short of arithmetic or bytes.)
+    int nh = 0;
+    auto flush = [&]() {
+        for (int h = 0; h < nh; h += 2) {
+            const unsigned e0 = hits[h][threadIdx.x], e1 = hits[h + 1 < nh ? h + 1 : h][threadIdx.x];
+            const int32_t q0 = runs[2 * (e0 >> 12)][threadIdx.x] + (int32_t)(e0 & 4095u);
+            const int32_t q1 = runs[2 * (e1 >> 12)][threadIdx.x] + (int32_t)(e1 & 4095u);
+            const double4 p0 = b.p[q0], v0 = b.v[q0], c0 = b.c[q0], p1 = b.p[q1], v1 = b.v[q1], c1 = b.c[q1];
+            S.add(pi4, p0, v0, c0, P.separation_sq);
+            if (h + 1 < nh) S.add(pi4, p1, v1, c1, P.separation_sq);
         }
-        flush();
+        nh = 0;
+    };
+    if (big) {
+        // a run of more than 4095 boids (three cells!): its offsets do not fit the 16-bit notes - such a boid
+        // takes its candidates one by one
+        for (int k = 0; k < nr; k++)
+            for (int32_t q = runs[2 * k][threadIdx.x]; q < runs[2 * k + 1][threadIdx.x]; q++) {
+                if (q == r) continue;
+                const double4 qp = b.p[q];
+                if (in_sight(qp)) S.add(pi4, qp, b.v[q], b.c[q], P.separation_sq);
+            }
     } else {
-    for (int dcz = -g.range; dcz <= g.range; dcz++) {
-        const int ncz = cz + dcz;
-        if (ncz < 0 || ncz >= g.dim) continue;
-        for (int dcy = -g.range; dcy <= g.range; dcy++) {
-            const int ncy = cy + dcy;
-            if (ncy < 0 || ncy >= g.dim) continue;
-            const int64_t row = (int64_t)ncy * g.dim + (int64_t)ncz * g.dim * g.dim;
-            const int64_t c_lo = row + x_lo, c_hi = row + x_hi;
-            // first and last non-empty cell of [c_lo, c_hi]
-            int first = -1, last = -1;  // bit positions inside their words
-            uint2 first_w = make_uint2(0u, 0u), last_w = make_uint2(0u, 0u);
-            for (int64_t w = c_lo >> 5; w <= (c_hi >> 5); w++) {
-                const uint2 e = occ[w];
-                uint32_t bits = e.x;
-                if (w == (c_lo >> 5)) bits &= ~0u << (c_lo & 31);
-                if (w == (c_hi >> 5)) bits &= ~0u >> (31 - (c_hi & 31));
-                if (bits) {
-                    if (first < 0) { first = __ffs(bits) - 1; first_w = e; }
-                    last = 31 - __clz(bits);
-                    last_w = e;
-                }
-            }
-            if (first < 0) continue;  // the whole row is empty: no table read
-            const uint32_t k_lo = first_w.y + __popc(first_w.x & ((1u << first) - 1u));
-            const uint32_t k_hi = last_w.y + __popc(last_w.x & ((1u << last) - 1u)) + 1u;
-            const int32_t q_begin = cell_start[k_lo], q_end = cell_start[k_hi];
-            for (int32_t q = q_begin; q < q_end; q++) candidate(q);
-        }
+        walk_runs<kBlock>(
+            b.p, runs, nr, [&]() { if (nh > kHitCap - 4) flush(); },
+            [&](int32_t c, unsigned code, const double4 &qp) {
+                if (c != r && in_sight(qp)) hits[nh++][threadIdx.x] = (unsigned short)code;
+            });
+        flush();
     }
-    }
-    flock_finish<kPhysics>(b, a, r, P, pix, piy, piz, vix, viy, viz, cir, cig, cib, sx, sy, sz, alx, aly, alz, cox, coy, coz, clr,
-                           clg, clb, sep_count, nb_count, o_sep, o_ali, o_coh, o_avg);
+    flock_finish<kPhysics>(b, a, r, P, pi4, vi4, ci4, S, o_sep, o_ali, o_coh, o_avg);
 }
 
 // ---- topological interaction: the k nearest within sight (include/bdmi.h has the specification) ------
@@ -473,23 +459,18 @@ __global__ __launch_bounds__(kBlock) void k_flock(BoidsAoS b, Boids a, const uin
 // keeps, per lane, an ascending list of at most k entries {d2, rank q} in LDS columns [slot][thread]; the sums then run
 // over that list in its order, from +0.0, so the forces are a function of the state and the ids alone - not of the cell
 // order, the row order or the block order.
-template <class F>
-__device__ __forceinline__ void fs_for_each_run(const double4 &p, const GridP &g, const uint2 *__restrict__ occ,
-                                                const int32_t *__restrict__ cell_start, F f);  // defined with the flock analysis
-
 constexpr int kTopoMaxK = 16;
-constexpr int kTopoRuns = 9;  // runs noted per lane before they are walked (all of them when range == 1)
+constexpr int kTopoRuns = 9;  // the runs noted per lane: all nine rows
 
 // The list of the boid at rank r (position pi4): ld2 / lq [slot][thread], ascending; returns its length.  Candidates come
-// from the (2 range + 1)^2 row runs, noted kTopoRuns at a time and walked back to back, four position records per trip as
-// in k_flock.  The common case of a candidate inside the window is a reject against the current k-th d2 (kept in a
-// register); ids are loaded only to break an exact d2 tie.  Ranks are stored whole, so a run may have any length.
+// from the nine row runs, noted and walked back to back as in k_flock.  The common case of a candidate inside the window
+// is a reject against the current k-th d2 (kept in a register); ids are loaded only to break an exact d2 tie.  Ranks are
+// stored whole, so a run may have any length.
 template <int kCap, int kThreads>
 __device__ __forceinline__ int topo_select(const BoidsAoS &b, const uint2 *__restrict__ occ, const int32_t *__restrict__ cell_start,
                                            const GridP &g, int64_t r, const double4 &pi4, double perception_sq, int k,
                                            int32_t (*runs)[kThreads], double (*ld2)[kThreads], int32_t (*lq)[kThreads]) {
     const int t = threadIdx.x;
-    const double pix = pi4.x, piy = pi4.y, piz = pi4.z;
     int cnt = 0;
     double worst = INFINITY;  // d2 of the k-th entry once the list is full
     auto insert = [&](double d2, int32_t q) {
@@ -515,52 +496,16 @@ __device__ __forceinline__ int topo_select(const BoidsAoS &b, const uint2 *__res
         lq[pos][t] = q;
         if (cnt == k) worst = ld2[k - 1][t];
     };
-    auto test = [&](int32_t c, const double4 qp) {
-        if (c < 0 || c == r) return;
-        const double dx = pix - qp.x, dy = piy - qp.y, dz = piz - qp.z;
-        const double d2 = (dx * dx + dy * dy) + dz * dz;
-        if (d2 < perception_sq && d2 > 0.0001) insert(d2, c);
-    };
-    int nr = 0;
-    auto walk = [&]() {  // the nr noted runs (none empty), back to back
-        int row = 0;
-        int32_t q = runs[0][t], e = runs[1][t];
-        auto next = [&]() -> int32_t {
-            if (q >= e) {
-                if (row + 1 >= nr) { row = nr; return -1; }
-                row++;
-                q = runs[2 * row][t];
-                e = runs[2 * row + 1][t];
-            }
-            return q++;
-        };
-        for (;;) {
-            const int32_t c0 = next();
-            if (c0 < 0) break;
-            const int32_t c1 = next(), c2 = next(), c3 = next();
-            const double4 p0 = b.p[c0], p1 = b.p[c1 < 0 ? c0 : c1], p2 = b.p[c2 < 0 ? c0 : c2], p3 = b.p[c3 < 0 ? c0 : c3];
-            test(c0, p0);
-            test(c1, p1);
-            test(c2, p2);
-            test(c3, p3);
-        }
-        nr = 0;
-    };
-    if (g.range == 1) {
-        // the usual grid: nine rows, looked up three at a time as k_flock does, walked in one go
-        const int cx = cell_coord(pix, g), cy = cell_coord(piy, g), cz = cell_coord(piz, g);
-        const int x_lo = cx - 1 < 0 ? 0 : cx - 1;
-        const int x_hi = cx + 1 > g.dim - 1 ? g.dim - 1 : cx + 1;
-        for (int dcz = -1; dcz <= 1; dcz++) (void)plane_runs<kThreads>(occ, cell_start, g, x_lo, x_hi, cy, cz + dcz, runs, nr);
-    } else {
-        fs_for_each_run(pi4, g, occ, cell_start, [&](int32_t qb, int32_t qe) {
-            if (qe <= qb) return;
-            runs[2 * nr][t] = qb;
-            runs[2 * nr + 1][t] = qe;
-            if (++nr == kTopoRuns) walk();
+    bool big;  // (no 16-bit notes here)
+    const int nr = note_runs<kThreads>(pi4, g, occ, cell_start, runs, big);
+    walk_runs<kThreads>(
+        b.p, runs, nr, [] {},
+        [&](int32_t c, unsigned, const double4 &qp) {
+            if (c == r) return;
+            const double dx = pi4.x - qp.x, dy = pi4.y - qp.y, dz = pi4.z - qp.z;
+            const double d2 = (dx * dx + dy * dy) + dz * dz;
+            if (d2 < perception_sq && d2 > 0.0001) insert(d2, c);
         });
-    }
-    if (nr > 0) walk();
     return cnt;
 }
 
@@ -580,34 +525,16 @@ __global__ __launch_bounds__(kThreads) void k_flock_topo(BoidsAoS b, Boids a, co
     const int64_t r = logical_block(blockIdx.x, gridDim.x, xcd_contiguous) * kThreads + t;
     if (r >= n) return;
     const double4 pi4 = b.p[r], vi4 = b.v[r], ci4 = b.c[r];
-    const double pix = pi4.x, piy = pi4.y, piz = pi4.z;
     const int cnt = topo_select<kCap, kThreads>(b, occ, cell_start, g, r, pi4, P.perception_sq, k, runs, ld2, lq);
-    double sx = 0, sy = 0, sz = 0, alx = 0, aly = 0, alz = 0, cox = 0, coy = 0, coz = 0, clr = 0, clg = 0, clb = 0;
-    int sep_count = 0;
-    auto neighbour = [&](const double4 qp, const double4 qv, const double4 qc) {  // flock.py:150-172
-        const double dx = pix - qp.x, dy = piy - qp.y, dz = piz - qp.z;
-        const double dist_sq = (dx * dx + dy * dy) + dz * dz;
-        if (dist_sq < P.separation_sq) {
-            const double dist = sqrt(dist_sq);
-            const double inv_dist = 1.0 / dist;
-            sx += dx * inv_dist / dist;
-            sy += dy * inv_dist / dist;
-            sz += dz * inv_dist / dist;
-            sep_count++;
-        }
-        alx += qv.x; aly += qv.y; alz += qv.z;
-        cox += qp.x; coy += qp.y; coz += qp.z;
-        clr += qc.x; clg += qc.y; clb += qc.z;
-    };
+    FlockSums S;
     // the list in its order, two entries at a time with all six records in flight
     for (int h = 0; h < cnt; h += 2) {
         const int32_t q0 = lq[h][t], q1 = lq[h + 1 < cnt ? h + 1 : h][t];
         const double4 p0 = b.p[q0], v0 = b.v[q0], c0 = b.c[q0], p1 = b.p[q1], v1 = b.v[q1], c1 = b.c[q1];
-        neighbour(p0, v0, c0);
-        if (h + 1 < cnt) neighbour(p1, v1, c1);
+        S.add(pi4, p0, v0, c0, P.separation_sq);
+        if (h + 1 < cnt) S.add(pi4, p1, v1, c1, P.separation_sq);
     }
-    flock_finish<kPhysics>(b, a, r, P, pix, piy, piz, vi4.x, vi4.y, vi4.z, ci4.x, ci4.y, ci4.z, sx, sy, sz, alx, aly, alz, cox,
-                           coy, coz, clr, clg, clb, sep_count, cnt, o_sep, o_ali, o_coh, o_avg);
+    flock_finish<kPhysics>(b, a, r, P, pi4, vi4, ci4, S, o_sep, o_ali, o_coh, o_avg);
 }
 
 // bdmi_topological_neighbours: the lists themselves, rows in the caller's order, padded with -1 / +inf
@@ -739,69 +666,17 @@ struct FlockStats {
     int64_t rows_cap = 0, chunks_cap = 0;
 };
 
-// The candidates of one (y, z) row of cells [c_lo, c_hi]: one contiguous run of ranks, found with the occupancy words as
-// k_flock finds it (its loop for any `range`; with range 1 a row is at most two words).
-__device__ __forceinline__ bool fs_row_run(const uint2 *__restrict__ occ, const int32_t *__restrict__ cell_start, int64_t c_lo,
-                                           int64_t c_hi, int32_t &q_begin, int32_t &q_end) {
-    int first = -1, last = -1;  // bit positions inside their words
-    uint2 first_w = make_uint2(0u, 0u), last_w = make_uint2(0u, 0u);
-    for (int64_t w = c_lo >> 5; w <= (c_hi >> 5); w++) {
-        const uint2 e = occ[w];
-        uint32_t bits = e.x;
-        if (w == (c_lo >> 5)) bits &= ~0u << (c_lo & 31);
-        if (w == (c_hi >> 5)) bits &= ~0u >> (31 - (c_hi & 31));
-        if (bits) {
-            if (first < 0) { first = __ffs(bits) - 1; first_w = e; }
-            last = 31 - __clz(bits);
-            last_w = e;
-        }
-    }
-    if (first < 0) return false;  // the whole row is empty: no table read
-    const uint32_t k_lo = first_w.y + __popc(first_w.x & ((1u << first) - 1u));
-    const uint32_t k_hi = last_w.y + __popc(last_w.x & ((1u << last) - 1u)) + 1u;
-    q_begin = cell_start[k_lo];
-    q_end = cell_start[k_hi];
-    return true;
-}
-// f(q_begin, q_end) for the non-empty rows around the boid at p, in row order ((2 range + 1)^2 rows: nine)
-template <class F>
-__device__ __forceinline__ void fs_for_each_run(const double4 &p, const GridP &g, const uint2 *__restrict__ occ,
-                                                const int32_t *__restrict__ cell_start, F f) {
-    const int cx = cell_coord(p.x, g), cy = cell_coord(p.y, g), cz = cell_coord(p.z, g);
-    const int x_lo = cx - g.range < 0 ? 0 : cx - g.range;
-    const int x_hi = cx + g.range > g.dim - 1 ? g.dim - 1 : cx + g.range;
-    for (int dcz = -g.range; dcz <= g.range; dcz++) {
-        const int ncz = cz + dcz;
-        if (ncz < 0 || ncz >= g.dim) continue;
-        for (int dcy = -g.range; dcy <= g.range; dcy++) {
-            const int ncy = cy + dcy;
-            if (ncy < 0 || ncy >= g.dim) continue;
-            const int64_t row = (int64_t)ncy * g.dim + (int64_t)ncz * g.dim * g.dim;
-            int32_t qb = 0, qe = 0;
-            if (fs_row_run(occ, cell_start, row + x_lo, row + x_hi, qb, qe)) f(qb, qe);
-        }
-    }
-}
 // d2(i, j) of the header: three products, two sums, symmetric in its arguments
 __device__ __forceinline__ double fs_d2(const double4 &a, const double4 &b) {
     const double dx = b.x - a.x, dy = b.y - a.y, dz = b.z - a.z;
     return (dx * dx + dy * dy) + dz * dz;
-}
-// one atomic per wave; every lane of the wave calls it
-__device__ __forceinline__ void fs_wave_add(unsigned long long *dst, long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if ((threadIdx.x & 63) == 0 && v != 0ll)
-        (void)__hip_atomic_fetch_add(dst, (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 __global__ __launch_bounds__(kBlock) void k_fs_init(int64_t n, int32_t *__restrict__ parent, int32_t *__restrict__ minid,
                                                     int32_t *__restrict__ cnt, uint32_t *__restrict__ rank) {
     const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (r >= n) return;
-    parent[r] = (int32_t)r;
-    minid[r] = INT32_MAX;
-    cnt[r] = 0;
+    fof_init(r, parent, minid, cnt);
     rank[r] = (uint32_t)r;
 }
 // The link kernel: one lane per rank r takes the candidates q < r of its nine rows, so every candidate pair is evaluated
@@ -816,7 +691,7 @@ __global__ __launch_bounds__(kBlock) void k_fs_link(const double4 *__restrict__ 
     if (r < n) {
         const double4 pi = pos[r];
         int mine = (int)r;  // an ancestor of r: its own rank at first, then the root the last unite came back with
-        fs_for_each_run(pi, g, occ, cell_start, [&](int32_t qb, int32_t qe) {
+        for_each_run(pi, g, occ, cell_start, [&](int32_t qb, int32_t qe) {
             const int32_t e = qe < (int32_t)r ? qe : (int32_t)r;
             for (int32_t q = qb; q < e; q++) {
                 const double d2 = fs_d2(pi, pos[q]);
@@ -828,47 +703,16 @@ __global__ __launch_bounds__(kBlock) void k_fs_link(const double4 *__restrict__ 
             }
         });
     }
-    fs_wave_add(counters + 0, links);
-    fs_wave_add(counters + 1, evals);
+    nbmi::wave_add(counters + 0, links, threadIdx.x & 63);
+    nbmi::wave_add(counters + 1, evals, threadIdx.x & 63);
 }
-// Behind the kernel boundary parent[] is final and read plainly: root[r], minid[root] = the smallest caller index and
-// cnt[root] = the members below it (integer atomics: order independent).  Ranks next to each other mostly share their
-// root: the lanes that share the root of the first lane left go in as one (twice), the rest on their own.
+// Behind the kernel boundary parent[] is final and read plainly (fof_flatten): root[r], minid[root] = the smallest caller
+// index and cnt[root] = the members below it.
 __global__ __launch_bounds__(kBlock) void k_fs_flatten(int64_t n, const int32_t *__restrict__ parent,
                                                        const int32_t *__restrict__ id, int32_t *__restrict__ root,
                                                        int32_t *__restrict__ minid, int32_t *__restrict__ cnt) {
     const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    const bool valid = r < n;
-    const int lane = threadIdx.x & 63;
-    int f = -1, own = INT32_MAX;
-    if (valid) {
-        f = (int)r;
-        for (int p = parent[f]; p != f; p = parent[f]) f = p;
-        root[r] = f;
-        own = id[r];
-    }
-    unsigned long long todo = __builtin_amdgcn_ballot_w64(valid);
-    for (int round = 0; round < 2 && todo != 0ull; round++) {
-        const int leader = __builtin_amdgcn_readfirstlane(__ffsll((long long)todo) - 1);
-        const int f0 = __builtin_amdgcn_readlane(f, leader);
-        const bool with = ((todo >> lane) & 1ull) != 0ull && f == f0;
-        const unsigned long long same = __builtin_amdgcn_ballot_w64(with);
-        int least = with ? own : INT32_MAX;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const int other = __shfl_xor(least, o);
-            least = other < least ? other : least;
-        }
-        if (lane == leader) {
-            atomicMin(&minid[f0], least);
-            atomicAdd(&cnt[f0], (int)__popcll(same));
-        }
-        todo &= ~same;
-    }
-    if ((todo >> lane) & 1ull) {
-        atomicMin(&minid[f], own);
-        atomicAdd(&cnt[f], 1);
-    }
+    fof_flatten(r, n, parent, root, minid, cnt, [&](int64_t q) { return id[q]; });
 }
 // label of every rank, of every boid in the caller's order, the members per label, and the number of roots
 __global__ __launch_bounds__(kBlock) void k_fs_labels(int64_t n, const int32_t *__restrict__ root,
@@ -885,7 +729,7 @@ __global__ __launch_bounds__(kBlock) void k_fs_labels(int64_t n, const int32_t *
         labels[id[r]] = l;
         if (is_root) lcnt[l] = cnt[r];
     }
-    fs_wave_add(n_roots, is_root ? 1ll : 0ll);
+    nbmi::wave_add(n_roots, is_root ? 1ll : 0ll, threadIdx.x & 63);
 }
 // The full sweep of the nine rows per boid: count[i] = #{j != i : d2 <= r2}, nn_d2[i] = the least such d2 or +inf.
 // An integer count and a minimum: exact whatever the order.
@@ -899,7 +743,7 @@ __global__ __launch_bounds__(kBlock) void k_fs_neighbours(const double4 *__restr
         const double4 pi = pos[r];
         int32_t c = 0;
         double least = INFINITY;
-        fs_for_each_run(pi, g, occ, cell_start, [&](int32_t qb, int32_t qe) {
+        for_each_run(pi, g, occ, cell_start, [&](int32_t qb, int32_t qe) {
             for (int32_t q = qb; q < qe; q++) {
                 if (q == (int32_t)r) continue;
                 const double d2 = fs_d2(pi, pos[q]);
@@ -914,7 +758,7 @@ __global__ __launch_bounds__(kBlock) void k_fs_neighbours(const double4 *__restr
         count[i] = c;
         nn_d2[i] = least;
     }
-    fs_wave_add(evals_out, evals);
+    nbmi::wave_add(evals_out, evals, threadIdx.x & 63);
 }
 
 // the heads (first member) of the flocks with at least min_members members, in label order
@@ -1126,6 +970,21 @@ int dev_alloc(bdmi_flock *f, T **p, size_t count) {
     *p = (T *)q;
     return 0;
 }
+// frees one of the handle's allocations ahead of bdmi_destroy (the caller clears its pointer)
+void dev_release(bdmi_flock *f, void *p) {
+    if (!p) return;
+    for (size_t k = 0; k < f->allocs.size(); k++)
+        if (f->allocs[k] == p) { f->allocs.erase(f->allocs.begin() + (long)k); break; }
+    (void)hipFree(p);
+}
+// a scratch buffer that has become too small: released and allocated again (null if that fails).  The caller keeps the
+// capacity: 0 ahead of the calls, the new one behind them.
+template <typename T>
+int dev_regrow(bdmi_flock *f, T **p, size_t count) {
+    dev_release(f, *p);
+    *p = nullptr;
+    return dev_alloc(f, p, count);
+}
 
 int alloc_boids(bdmi_flock *f, Boids *b, int64_t n) {
     if (dev_alloc(f, &b->px, n) || dev_alloc(f, &b->py, n) || dev_alloc(f, &b->pz, n) || dev_alloc(f, &b->vx, n) ||
@@ -1174,7 +1033,16 @@ int enqueue_grid(bdmi_flock *f, bool timed) {
     return 0;
 }
 
-void dev_release(bdmi_flock *f, void *p);  // defined with the flock analysis
+// The two instances of the topological kernels (k_flock_topo, k_topo_rows): k <= 8 runs 256 threads per block with a list
+// of 8, a larger k 128 threads with a list of kTopoMaxK.  launch(list capacity, threads per block, blocks for n boids),
+// the first two as integral constants.
+template <class F>
+void topo_launch(int k, int64_t n, F launch) {
+    if (k <= 8)
+        launch(std::integral_constant<int, 8>{}, std::integral_constant<int, 256>{}, (int)((n + 255) / 256));
+    else
+        launch(std::integral_constant<int, kTopoMaxK>{}, std::integral_constant<int, 128>{}, (int)((n + 127) / 128));
+}
 
 // the sweep of the handle's neighbour mode over the grid enqueue_grid has just built
 template <bool kPhysics>
@@ -1183,12 +1051,11 @@ void enqueue_sweep(bdmi_flock *f, const FlockP &P, double *d0, double *d1, doubl
     if (f->nb_mode != BDMI_NEIGHBOURS_TOPOLOGICAL)
         k_flock<kPhysics><<<nblocks(n), kBlock, 0, f->stream>>>(f->B, f->A, f->occ, f->cell_start, n, f->grid, P, d0, d1, d2, d3,
                                                                f->xcd_contiguous);
-    else if (f->nb_k <= 8)
-        k_flock_topo<kPhysics, 8, 256><<<(int)((n + 255) / 256), 256, 0, f->stream>>>(
-            f->B, f->A, f->occ, f->cell_start, n, f->grid, P, f->nb_k, d0, d1, d2, d3, f->xcd_contiguous);
     else
-        k_flock_topo<kPhysics, kTopoMaxK, 128><<<(int)((n + 127) / 128), 128, 0, f->stream>>>(
-            f->B, f->A, f->occ, f->cell_start, n, f->grid, P, f->nb_k, d0, d1, d2, d3, f->xcd_contiguous);
+        topo_launch(f->nb_k, n, [&](auto cap, auto threads, int blocks) {
+            k_flock_topo<kPhysics, decltype(cap)::value, decltype(threads)::value><<<blocks, decltype(threads)::value, 0, f->stream>>>(
+                f->B, f->A, f->occ, f->cell_start, n, f->grid, P, f->nb_k, d0, d1, d2, d3, f->xcd_contiguous);
+        });
 }
 
 }  // namespace
@@ -1296,7 +1163,6 @@ static bdmi_flock *bd_create(int64_t n, const double *pos, const double *vel, co
     }
     f->grid.dim = (int)dimf;
     f->grid.offset = bounds + perception;
-    f->grid.range = (int)ceil(perception / f->grid.cell_size);
     f->num_cells = (int64_t)f->grid.dim * f->grid.dim * f->grid.dim;
     f->key_bits = 1;
     while (((int64_t)1 << f->key_bits) < f->num_cells) f->key_bits++;
@@ -1608,22 +1474,18 @@ int bdmi_topological_neighbours(bdmi_flock *f, int k, int32_t *ids, double *d2, 
     const int64_t n = f->n;
     if (n == 0) return 0;
     if (k > f->topo_cap) {
-        dev_release(f, f->topo_ids); dev_release(f, f->topo_d2);
-        f->topo_ids = nullptr; f->topo_d2 = nullptr;
         f->topo_cap = 0;
-        if (dev_alloc(f, &f->topo_ids, (size_t)n * k) || dev_alloc(f, &f->topo_d2, (size_t)n * k)) return -2;
+        if (dev_regrow(f, &f->topo_ids, (size_t)n * k) || dev_regrow(f, &f->topo_d2, (size_t)n * k)) return -2;
         f->topo_cap = k;
     }
     if (!f->topo_cnt && dev_alloc(f, &f->topo_cnt, (size_t)n)) return -2;
     if (int rc = enqueue_grid(f, false)) return rc;
     hipStream_t st = f->stream;
     const double psq = f->params[5] * f->params[5];
-    if (k <= 8)
-        k_topo_rows<8, 256><<<(int)((n + 255) / 256), 256, 0, st>>>(f->B, f->occ, f->cell_start, n, f->grid, psq, k, f->topo_ids,
-                                                                    f->topo_d2, f->topo_cnt);
-    else
-        k_topo_rows<kTopoMaxK, 128><<<(int)((n + 127) / 128), 128, 0, st>>>(f->B, f->occ, f->cell_start, n, f->grid, psq, k,
-                                                                            f->topo_ids, f->topo_d2, f->topo_cnt);
+    topo_launch(k, n, [&](auto cap, auto threads, int blocks) {
+        k_topo_rows<decltype(cap)::value, decltype(threads)::value><<<blocks, decltype(threads)::value, 0, st>>>(
+            f->B, f->occ, f->cell_start, n, f->grid, psq, k, f->topo_ids, f->topo_d2, f->topo_cnt);
+    });
     NBMI_HIP_CHECK(hipGetLastError());
     if (ids) NBMI_HIP_CHECK(hipMemcpyAsync(ids, f->topo_ids, (size_t)n * k * 4, hipMemcpyDeviceToHost, st));
     if (d2) NBMI_HIP_CHECK(hipMemcpyAsync(d2, f->topo_d2, (size_t)n * k * 8, hipMemcpyDeviceToHost, st));
@@ -1734,13 +1596,6 @@ int bdmi_visible_vertices(bdmi_flock *f, const double *cam12, double tan_h, doub
 
 // ---- flock analysis (the kernels are above, next to the sweep whose grid they share) ---------------------------------
 namespace {
-// frees one of the handle's allocations ahead of bdmi_destroy (the caller clears its pointer)
-void dev_release(bdmi_flock *f, void *p) {
-    if (!p) return;
-    for (size_t k = 0; k < f->allocs.size(); k++)
-        if (f->allocs[k] == p) { f->allocs.erase(f->allocs.begin() + (long)k); break; }
-    (void)hipFree(p);
-}
 int fs_radius_check(bdmi_flock *f, const char *what, const char *name, double v) {
     if (int rc = whole_flock_check(f, what)) return rc;
     const double perception = f->params[5];
@@ -1761,11 +1616,10 @@ int fs_sort_temp(bdmi_flock *f, int64_t n, int bits) {
     const size_t need = nbmi::radix_temp_bytes_u32((size_t)n, bits);
     if (need <= f->tmp_sort_bytes) return 0;
     if (int rc = sync_checked(f)) return rc;
-    char *t = nullptr;
-    dev_release(f, f->tmp_sort);
+    char *t = (char *)f->tmp_sort;
     f->tmp_sort = nullptr;
     f->tmp_sort_bytes = 0;
-    if (dev_alloc(f, &t, need + 256)) return -2;
+    if (dev_regrow(f, &t, need + 256)) return -2;
     f->tmp_sort = t;
     f->tmp_sort_bytes = need;
     NBMI_HIP_CHECK(nbmi::radix_init_temp(t, f->stream));
@@ -1785,19 +1639,15 @@ int fs_buffers(bdmi_flock *f) {
 int fs_row_buffers(bdmi_flock *f, int64_t rows, int64_t chunks) {
     FlockStats &s = f->fs;
     if (rows > s.rows_cap) {
-        dev_release(f, s.chunk_off); dev_release(f, s.rows16); dev_release(f, s.row_label); dev_release(f, s.row_members);
-        s.chunk_off = nullptr; s.rows16 = nullptr; s.row_label = nullptr; s.row_members = nullptr;
         s.rows_cap = 0;
-        if (dev_alloc(f, &s.chunk_off, (size_t)rows + 1) || dev_alloc(f, &s.rows16, (size_t)rows * 16) ||
-            dev_alloc(f, &s.row_label, (size_t)rows) || dev_alloc(f, &s.row_members, (size_t)rows))
+        if (dev_regrow(f, &s.chunk_off, (size_t)rows + 1) || dev_regrow(f, &s.rows16, (size_t)rows * 16) ||
+            dev_regrow(f, &s.row_label, (size_t)rows) || dev_regrow(f, &s.row_members, (size_t)rows))
             return -2;
         s.rows_cap = rows;
     }
     if (chunks > s.chunks_cap) {
-        dev_release(f, s.part);
-        s.part = nullptr;
         s.chunks_cap = 0;
-        if (dev_alloc(f, &s.part, (size_t)chunks * kFsVals)) return -2;
+        if (dev_regrow(f, &s.part, (size_t)chunks * kFsVals)) return -2;
         s.chunks_cap = chunks;
     }
     return 0;

@@ -22,6 +22,14 @@ void clear_error();
         }                                                                                   \
     } while (0)
 
+// The sum of a counter over the wave, added to *dst by one agent-scope relaxed integer atomic (what atomicAdd is) unless
+// it is 0: integers, so the result does not depend on any order.  Every lane of the wave calls it, with its lane number.
+__device__ __forceinline__ void wave_add(unsigned long long *dst, long long v, int lane) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if (lane == 0 && v != 0ll) (void)__hip_atomic_fetch_add(dst, (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // {m, m*x, m*y, m*z} prefix-sum element, each a double-double (high word, low word).
 struct Moment {
     double m, ml, x, xl, y, yl, z, zl;

@@ -3781,13 +3781,6 @@ __device__ __forceinline__ void query_half_search(const QueryCtx &C, int64_t n, 
         }
     }
 }
-// The sum of a counter over the wave, added to *dst by one agent-scope relaxed integer atomic (what atomicAdd is) unless
-// it is 0: integers, so the result does not depend on any order.
-__device__ __forceinline__ void query_wave_add(unsigned long long *dst, long long v, int lane) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if (lane == 0 && v != 0ll) (void)__hip_atomic_fetch_add(dst, (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 // ---- K16: k nearest neighbours (nbmi_knn / nbmi_get_densities_f64 / density colours) --------
 constexpr int kKnnMaxK = 64;
@@ -3883,7 +3876,7 @@ __global__ __launch_bounds__(kQueryBlock) void k_knn(const Node *__restrict__ no
         r2_out[j] = r2k;
         mass_out[j] = acc;
     }
-    if (evals_out) query_wave_add(evals_out, evals, C.lane);
+    if (evals_out) nbmi::wave_add(evals_out, evals, C.lane);
 }
 // state rows -> the caller's order (id), any of the three outputs
 __global__ __launch_bounds__(kBlock) void k_knn_out(const double *__restrict__ r2, const double *__restrict__ mass,
@@ -3908,9 +3901,7 @@ __global__ __launch_bounds__(kBlock) void k_fof_init(int64_t n, int32_t *__restr
                                                      int32_t *__restrict__ cnt) {
     const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (r >= n) return;
-    parent[r] = (int32_t)r;
-    minid[r] = INT32_MAX;
-    cnt[r] = 0;
+    fof_init(r, parent, minid, cnt);
 }
 // The pair search: one wave per 64 key-adjacent bodies.  Pairs inside the wave are tested directly (query_half_search);
 // every other pair is found by the walk against the fixed bound b2 - a cell is pruned only if query_lower EXCEEDS b2, so a
@@ -3931,50 +3922,17 @@ __global__ __launch_bounds__(kQueryBlock) void k_fof_link(const Node *__restrict
     const unsigned start = __builtin_amdgcn_readfirstlane(wleaf[blockIdx.x]) * kNodeBytes;
     query_walk(nodes, rows, node_ref, start, C, (int64_t)0, C.w0 + kQueryBlock, b2, evals,
                [&](double d2, const double4 &, int64_t r) { fof_link_lanes(parent, d2 <= b2, mine, (int)r); });
-    if (evals_out) query_wave_add(evals_out, evals, C.lane);
+    if (evals_out) nbmi::wave_add(evals_out, evals, C.lane);
 }
-// Behind the kernel boundary parent[] is final and read plainly: root[r] = the root of r's tree, minid[root] = the
-// smallest caller index and cnt[root] = the number of bodies below it (integer atomics: order independent).
+// Behind the kernel boundary parent[] is final and read plainly (fof_flatten): root[r] = the root of r's tree,
+// minid[root] = the smallest caller index and cnt[root] = the number of bodies below it.
 __global__ __launch_bounds__(kBlock) void k_fof_flatten(const TreeInfo *__restrict__ info, int64_t n,
                                                         const int32_t *__restrict__ parent, const uint32_t *__restrict__ perm,
                                                         const int32_t *__restrict__ id, int32_t *__restrict__ root,
                                                         int32_t *__restrict__ minid, int32_t *__restrict__ cnt) {
     if (info->error != 0 || info->sticky_error != 0) return;
     const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    const bool valid = r < n;
-    const int lane = threadIdx.x & 63;
-    int f = -1, own = INT32_MAX;
-    if (valid) {
-        f = (int)r;
-        for (int p = parent[f]; p != f; p = parent[f]) f = p;
-        root[r] = f;
-        own = id[perm[r]];
-    }
-    // Key-adjacent ranks mostly share their root, and a root that a large group hangs on would otherwise take one
-    // same-address atomic per member: the lanes that share the root of the first lane left go in as one (twice), the
-    // rest on their own.
-    unsigned long long todo = __builtin_amdgcn_ballot_w64(valid);
-    for (int round = 0; round < 2 && todo != 0ull; round++) {
-        const int leader = __builtin_amdgcn_readfirstlane(__ffsll((long long)todo) - 1);
-        const int f0 = __builtin_amdgcn_readlane(f, leader);
-        const bool with = ((todo >> lane) & 1ull) != 0ull && f == f0;
-        const unsigned long long same = __builtin_amdgcn_ballot_w64(with);
-        int least = with ? own : INT32_MAX;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const int other = __shfl_xor(least, o);
-            least = other < least ? other : least;
-        }
-        if (lane == leader) {
-            atomicMin(&minid[f0], least);
-            atomicAdd(&cnt[f0], (int)__popcll(same));
-        }
-        todo &= ~same;
-    }
-    if ((todo >> lane) & 1ull) {
-        atomicMin(&minid[f], own);
-        atomicAdd(&cnt[f], 1);
-    }
+    fof_flatten(r, n, parent, root, minid, cnt, [&](int64_t q) { return id[perm[q]]; });
 }
 // label of every body in the caller's order (may be null), and the number of roots
 __global__ __launch_bounds__(kBlock) void k_fof_labels(const TreeInfo *__restrict__ info, int64_t n,
@@ -4259,7 +4217,7 @@ __device__ __forceinline__ int pair_bin(const double *__restrict__ E, int nb, do
 // nothing.
 // Counters: nb + 1 uint32 per lane in LDS, [counter][lane] - consecutive lanes, consecutive words, no bank conflicts; a
 // lane counts at most n - 1 < 2^31 pairs.  The E[k] sit in LDS in front of them (the search's indices diverge by lane).
-// At the end every counter is summed over the wave in 64 bits and added to out[2 + counter] (query_wave_add).  out[0] +=
+// At the end every counter is summed over the wave in 64 bits and added to out[2 + counter] (nbmi::wave_add).  out[0] +=
 // distances evaluated, out[1] += pairs counted through whole cells.
 __global__ __launch_bounds__(kQueryBlock) void k_pair_counts(const Node *__restrict__ nodes, const double4 *__restrict__ rows,
                                                             const int32_t *__restrict__ node_ref,
@@ -4298,9 +4256,9 @@ __global__ __launch_bounds__(kQueryBlock) void k_pair_counts(const Node *__restr
             return false;
         },
         [&](double d2, const double4 &, int64_t) { count(d2); });
-    for (int k = 0; k <= nb; k++) query_wave_add(out + 2 + k, (long long)c[64 * k], C.lane);
-    query_wave_add(out, evals, C.lane);
-    query_wave_add(out + 1, whole, C.lane);
+    for (int k = 0; k <= nb; k++) nbmi::wave_add(out + 2 + k, (long long)c[64 * k], C.lane);
+    nbmi::wave_add(out, evals, C.lane);
+    nbmi::wave_add(out + 1, whole, C.lane);
 }
 
 // ---------------------------------------------------------------------------------------
