@@ -1,6 +1,8 @@
 """Pure NumPy helpers around the flock-analysis calls of include/bdmi.h (Flock.flocks, flock_catalogue, diagnostics,
 neighbour_stats): the named fields of a row of 16 doubles, the size histogram of a catalogue, and the builder of the
-JSON line that tools.flock_video writes with --diagnostics.  Nothing here touches the device.
+JSON line that tools.flock_video writes with --diagnostics; and the order-against-noise experiment over
+Flock.set_noise / Flock.diagnostics (order_parameter_series, binder_cumulant, noise_sweep).  Nothing here touches the
+device itself: the helpers work on any object with the Flock methods they name.
 """
 import json
 
@@ -30,11 +32,30 @@ def size_histogram(members) -> dict:
     return out
 
 
+def _settings(rec, neighbours, periodic, noise):
+    """The keys that name what is not the default: present only when used."""
+    if neighbours is not None:
+        rec["neighbours"] = {"mode": str(neighbours["mode"]), "k": int(neighbours["k"])}
+    if periodic:
+        rec["periodic"] = True
+    if noise is not None:
+        rec["noise"] = {"eta": float(noise["eta"]), "seed": int(noise["seed"])}
+    return rec
+
+
+def global_line(frame, steps, global_row, neighbours=None, periodic=False, noise=None) -> str:
+    """The analysis line of a periodic flock: the frame, the step count and the whole flock's row, without flocks or
+    neighbour counts (the flock finder does not follow links through the faces of the box)."""
+    rec = {"frame": int(frame), "steps": int(steps), "global": row_dict(global_row)}
+    return json.dumps(_settings(rec, neighbours, periodic, noise))
+
+
 def jsonl_line(frame, steps, global_row, n_flocks, links, mean_neighbours, flock_rows, flock_labels=None,
-               link=None, min_members=None, qualifying=None, neighbours=None) -> str:
+               link=None, min_members=None, qualifying=None, neighbours=None, noise=None) -> str:
     """One flock-analysis line: the frame, the step count, the whole flock's row, the number of flocks and links, the
     mean neighbour count and the rows of the largest flocks (largest first), as one JSON object without a newline.
-    ``neighbours`` ({"mode": "topological", "k": K}) names the interaction rule where it is not the metric default."""
+    ``neighbours`` ({"mode": "topological", "k": K}) names the interaction rule where it is not the metric default,
+    ``noise`` ({"eta": E, "seed": S}) the noise where there is one."""
     rows = [row_dict(r) for r in np.asarray(flock_rows, dtype=np.float64).reshape(-1, 16)]
     if flock_labels is not None:
         for r, l in zip(rows, np.asarray(flock_labels).tolist()):
@@ -47,9 +68,7 @@ def jsonl_line(frame, steps, global_row, n_flocks, links, mean_neighbours, flock
         rec["min_members"] = int(min_members)
     if qualifying is not None:
         rec["qualifying_flocks"] = int(qualifying)
-    if neighbours is not None:
-        rec["neighbours"] = {"mode": str(neighbours["mode"]), "k": int(neighbours["k"])}
-    return json.dumps(rec)
+    return json.dumps(_settings(rec, neighbours, False, noise))
 
 
 def neighbour_rank_profile(d2) -> np.ndarray:
@@ -63,3 +82,52 @@ def neighbour_rank_profile(d2) -> np.ndarray:
     total = np.where(have, np.sqrt(np.where(have, d2, 0.0)), 0.0).sum(axis=0)
     cnt = have.sum(axis=0)
     return np.where(cnt > 0, total / np.maximum(cnt, 1), np.nan)
+
+
+# ---- order against noise (Vicsek et al. 1995): the polarisation of a flock as a function of the noise amplitude --------
+def order_parameter_series(rows) -> dict:
+    """The time series of the order parameters from the rows of Flock.diagnostics() ((T, 16) float64, one row per
+    sample): dict of ``polarisation``, ``milling`` and ``mean_speed``, float64 (T,) each."""
+    r = np.asarray(rows, dtype=np.float64)
+    if r.ndim != 2 or r.shape[1] != 16:
+        raise ValueError(f"rows must be (T, 16), got shape {r.shape}")
+    return {"polarisation": r[:, 7].copy(), "milling": r[:, 9].copy(), "mean_speed": r[:, 8].copy()}
+
+
+def binder_cumulant(phi) -> float:
+    """1 - <phi^4> / (3 <phi^2>^2) of the samples ``phi``: 2/3 in the ordered phase, towards 1/3 for the polarisation of
+    a disordered flock in three dimensions; NaN without samples or where <phi^2> is 0."""
+    phi = np.asarray(phi, dtype=np.float64)
+    if phi.size == 0:
+        return float("nan")
+    m2, m4 = float(np.mean(phi ** 2)), float(np.mean(phi ** 4))
+    return 1.0 - m4 / (3.0 * m2 * m2) if m2 > 0 else float("nan")
+
+
+def noise_sweep(make_flock, etas, steps, discard, every, dt) -> list:
+    """Order against noise.  For every ``eta`` of ``etas``: a fresh flock from ``make_flock()`` (any object with
+    ``set_noise``, ``update`` and ``diagnostics``, closed afterwards if it has ``close``), ``set_noise(eta)`` with
+    whatever seed and step the flock has, ``steps`` updates of ``dt``; behind the first ``discard`` updates every
+    ``every``-th one is sampled.  Returns one dict per eta: ``eta``, ``samples``, ``polarisation_mean``,
+    ``polarisation_std`` (population standard deviation) and ``binder`` (binder_cumulant of the samples)."""
+    steps, discard, every = int(steps), int(discard), int(every)
+    if steps < 1 or every < 1 or not 0 <= discard < steps:
+        raise ValueError("noise_sweep: steps and every must be at least 1 and 0 <= discard < steps")
+    out = []
+    for eta in etas:
+        flock = make_flock()
+        try:
+            seed = flock.noise[1] if hasattr(flock, "noise") else 0
+            flock.set_noise(float(eta), seed=seed)
+            rows = []
+            for s in range(steps):
+                flock.update(dt)
+                if s >= discard and (s - discard) % every == 0:
+                    rows.append(np.array(flock.diagnostics(), dtype=np.float64))
+            phi = order_parameter_series(np.array(rows).reshape(-1, 16))["polarisation"]
+        finally:
+            if hasattr(flock, "close"):
+                flock.close()
+        out.append({"eta": float(eta), "samples": int(phi.size), "polarisation_mean": float(phi.mean()),
+                    "polarisation_std": float(phi.std()), "binder": binder_cumulant(phi)})
+    return out

@@ -52,10 +52,14 @@ def generate_initial_state(num_boids: int, bounds: float, max_speed: float):
 
 
 class Flock:
-    """Drop-in for reference boids.Flock (:454): ``Flock(num_boids)``, ``update(dt)``."""
+    """Drop-in for reference boids.Flock (:454): ``Flock(num_boids)``, ``update(dt)``.
 
-    def __init__(self, num_boids: int = 1000, seed=None, device: int = 0):
+    ``periodic=True`` (not in the reference) makes the domain the periodic box [-bounds, bounds]^3 of include/bdmi.h:
+    no walls, neighbours through the faces by their minimum image, positions wrapped by ``update``."""
+
+    def __init__(self, num_boids: int = 1000, seed=None, device: int = 0, periodic: bool = False):
         self.num_boids = num_boids
+        self._periodic = bool(periodic)
         B = config.BOIDS
         self.bounds = np.float64(B["bounds"])
         self.wall_margin = np.float64(B["wall_margin"])
@@ -84,11 +88,53 @@ class Flock:
         self._visible_count = num_boids
         self._lib = _nat.load()
         params = np.array([float(B[k]) for k in config.PARAM_ORDER], dtype=np.float64)
-        self._h = self._lib.bdmi_create(num_boids, _nat.ptr(pos), _nat.ptr(vel), _nat.ptr(col), _nat.ptr(params),
-                                        int(device))
+        create = self._lib.bdmi_create_periodic if self._periodic else self._lib.bdmi_create
+        self._h = create(num_boids, _nat.ptr(pos), _nat.ptr(vel), _nat.ptr(col), _nat.ptr(params), int(device))
         if not self._h:
+            if _nat.last_error().startswith("bdmi_create_periodic: "):  # the library refused the box, not the device
+                raise ValueError(_nat.last_error())
             raise RuntimeError(f"bdmi_create failed: {_nat.last_error()} (this build has no CPU fallback)")
+        if self._periodic:  # the periodic grid in the place of the reference's (include/bdmi.h)
+            self.grid_dim = self.grid_info()["grid_dim"]
+            self.cell_size = self.box["cell_size"]
+            self.num_cells = self.grid_dim ** 3
+            self.grid_offset = float(self.bounds)
         self._cache = {"positions": pos, "velocities": vel, "colors": col}
+
+    # ---- periodic box and noise (include/bdmi.h) -----------------------------------------------
+    @property
+    def periodic(self):
+        return self._periodic
+
+    @property
+    def box(self):
+        """dict of ``periodic``, ``length`` (2 * bounds) and ``cell_size`` of the handle's grid."""
+        per, length, cell = C.c_int(0), C.c_double(0), C.c_double(0)
+        _nat.check_arg(self._lib.bdmi_get_box(self._h, C.addressof(per), C.addressof(length), C.addressof(cell)),
+                       "bdmi_get_box")
+        return dict(periodic=bool(per.value), length=float(length.value), cell_size=float(cell.value))
+
+    def set_noise(self, eta, seed=0, step=None):
+        """Vectorial noise of amplitude ``eta * max_force``: every ``update`` adds ``eta * max_force * xi_i(step)`` to boid
+        i's acceleration, xi a unit vector drawn from (seed, step, i) alone.  ``step=None`` keeps the handle's noise step,
+        which counts the updates since the flock was made; ``eta=0`` is the step without noise."""
+        _nat.check_arg(self._lib.bdmi_set_noise(self._h, float(eta), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                -1 if step is None else int(step)), "bdmi_set_noise")
+
+    @property
+    def noise(self):
+        """``(eta, seed, step)``."""
+        eta, seed, step = C.c_double(0), C.c_uint64(0), C.c_int64(0)
+        _nat.check_arg(self._lib.bdmi_get_noise(self._h, C.addressof(eta), C.addressof(seed), C.addressof(step)),
+                       "bdmi_get_noise")
+        return float(eta.value), int(seed.value), int(step.value)
+
+    def noise_vectors(self, step=None):
+        """The unit vectors xi_i(step), float64 (N, 3) (default: the handle's current noise step)."""
+        out = np.empty((self.num_boids, 3), dtype=np.float64)
+        _nat.check_arg(self._lib.bdmi_noise_vectors(self._h, -1 if step is None else int(step), _nat.ptr(out)),
+                       "bdmi_noise_vectors")
+        return out
 
     # ---- state access (reference attributes) ----------------------------------------------
     def _fetch(self):
@@ -118,13 +164,15 @@ class Flock:
         for a in arrs:
             if a is not None and a.shape != (self.num_boids, 3):
                 raise ValueError("state arrays must be (N,3)")
-        _nat.check(self._lib.bdmi_set_state(self._h, *[_nat.ptr(a) for a in arrs]), "bdmi_set_state")
+        check = _nat.check_arg if self._periodic else _nat.check  # a periodic handle refuses positions outside its box
+        check(self._lib.bdmi_set_state(self._h, *[_nat.ptr(a) for a in arrs]), "bdmi_set_state")
         self._cache = None
 
     # ---- the hot path -----------------------------------------------------------------------
     def update(self, dt: float, substeps: int = 1):
         """Flock.update(dt) (reference :627); no dt cap here - callers cap at 0.05."""
-        _nat.check(self._lib.bdmi_step(self._h, float(np.float64(dt)), int(substeps)), "bdmi_step")
+        check = _nat.check_arg if self._periodic else _nat.check  # a periodic handle refuses max_speed * |dt| >= its box
+        check(self._lib.bdmi_step(self._h, float(np.float64(dt)), int(substeps)), "bdmi_step")
         self._cache = None
 
     def sync(self):

@@ -46,23 +46,42 @@ struct BoidsAoS {
 // Flock.__init__'s grid (flock.py:478-481): the cell is the perception radius, so a boid's neighbours lie in the 3 x 3 x 3
 // cells around its own, whatever the parameters
 struct GridP {
+    static constexpr bool kPeriodic = false;
     double cell_size, offset;
     int dim;
 };
+// The grid of a periodic handle (include/bdmi.h, "Periodic handles"): the box [-B, B]^3 cut into dim^3 cells of
+// L / dim >= the perception radius, offset = B; the 27 cells around a boid wrap modulo dim.  The same members first, so
+// that cell_coord is one function; B and L serve the minimum image and the wrap of the integration.
+struct GridPer {
+    static constexpr bool kPeriodic = true;
+    double cell_size, offset;
+    int dim;
+    double B, L;
+};
 
 struct FlockP {
+    static constexpr bool kNoisy = false;
     double perception_sq, separation_sq, sep_w, ali_w, coh_w, max_speed, max_force;
     double bounds, margin, wall_force, blend, dt;
 };
+// A step with the noise term of include/bdmi.h ("Noise"): amp = eta * max_force, and the Philox key and counter words
+struct FlockPN : FlockP {
+    static constexpr bool kNoisy = true;
+    double amp;
+    uint32_t seed_lo, seed_hi, step_lo, step_hi;
+};
 
 // get_cell_index (flock.py:16-27): int() truncation toward zero, then clamp
-__device__ __forceinline__ int cell_coord(double v, const GridP &g) {
+template <class G>
+__device__ __forceinline__ int cell_coord(double v, const G &g) {
     int c = (int)((v + g.offset) / g.cell_size);
     c = c < 0 ? 0 : c;
     c = c > g.dim - 1 ? g.dim - 1 : c;
     return c;
 }
 
+// (A periodic handle runs k_assign and k_cells_out as they are: its grid is the GridP part of its GridPer.)
 __global__ __launch_bounds__(kBlock) void k_assign(Boids a, int64_t n, GridP g, uint32_t *__restrict__ keys,
                                                    uint32_t *__restrict__ idx) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -176,6 +195,44 @@ __device__ __forceinline__ int64_t logical_block(int b, int nb, int xcd_contiguo
     return (int64_t)xcd * q + (xcd < rem ? xcd : rem) + j;
 }
 
+// The image of a candidate q for the boid at p (include/bdmi.h): per axis q + L if p - q > B, q - L if p - q < -B, else q
+// itself (equality does not shift).  Every formula of the sweep then takes the image for the neighbour's position.  On a
+// walled grid this is the identity and costs nothing.
+template <class G>
+__device__ __forceinline__ double4 image_of(const double4 &p, const double4 &q, const G &g) {
+    if constexpr (G::kPeriodic) {
+        auto axis = [&](double pc, double qc) {
+            const double d0 = pc - qc;
+            return d0 > g.B ? qc + g.L : (d0 < -g.B ? qc - g.L : qc);
+        };
+        return make_double4(axis(p.x, q.x), axis(p.y, q.y), axis(p.z, q.z), q.w);
+    } else {
+        return q;
+    }
+}
+
+// xi_i(step) of include/bdmi.h: Marsaglia's (1972) unit vector from the first pair of Philox words inside the unit disc.
+// One Philox block in the common case (two pairs, each accepted with probability pi / 4); the rejection loop is per lane.
+__device__ __forceinline__ void noise_xi(uint32_t id, uint32_t step_lo, uint32_t step_hi, uint32_t seed_lo, uint32_t seed_hi,
+                                         double &x, double &y, double &z) {
+    const uint32_t key[2] = {seed_lo, seed_hi};
+    for (uint32_t a = 0;; a++) {
+        const uint32_t ctr[4] = {id, step_lo, step_hi, a};
+        uint32_t w[4];
+        nbmi::philox4x32_10(ctr, key, w);
+#pragma unroll
+        for (int pr = 0; pr < 2; pr++) {
+            const double x1 = ((double)w[2 * pr] + 0.5) * 0x1p-31 - 1.0, x2 = ((double)w[2 * pr + 1] + 0.5) * 0x1p-31 - 1.0;
+            const double s = x1 * x1 + x2 * x2;
+            if (s < 1.0) {
+                const double t = sqrt(1.0 - s);
+                x = (2.0 * x1) * t; y = (2.0 * x2) * t; z = 1.0 - 2.0 * s;
+                return;
+            }
+        }
+    }
+}
+
 // The neighbour sums of one boid, and one neighbour's contribution to them (flock.py:150-172): shared by the metric
 // sweep (k_flock, both of its candidate loops) and the topological one (k_flock_topo).
 struct FlockSums {
@@ -202,9 +259,11 @@ struct FlockSums {
 
 // The end of compute_flocking_spatial (means and steer(), flock.py:174-238) and update_physics_numba (flock.py:241-308)
 // for the boid at rank r (records pi4, vi4, ci4), from its neighbour sums.  kPhysics=false: write the four force arrays
-// (caller's boid order) instead of integrating.
-template <bool kPhysics>
-__device__ __forceinline__ void flock_finish(const BoidsAoS &b, const Boids &a, int64_t r, const FlockP &P, const double4 &pi4,
+// (caller's boid order) instead of integrating.  A periodic grid drops the wall terms and wraps the new position once; a
+// noisy PP adds amp * xi to the acceleration (not to the four force arrays).  Both are compile-time: the walled,
+// noise-free instance is the code it was.
+template <bool kPhysics, class G, class PP>
+__device__ __forceinline__ void flock_finish(const BoidsAoS &b, const Boids &a, int64_t r, const G &g, const PP &P, const double4 &pi4,
                                              const double4 &vi4, const double4 &ci4, FlockSums S, double *__restrict__ o_sep,
                                              double *__restrict__ o_ali, double *__restrict__ o_coh, double *__restrict__ o_avg) {
     const double pix = pi4.x, piy = pi4.y, piz = pi4.z, vix = vi4.x, viy = vi4.y, viz = vi4.z, cir = ci4.x, cig = ci4.y, cib = ci4.z;
@@ -233,13 +292,21 @@ __device__ __forceinline__ void flock_finish(const BoidsAoS &b, const Boids &a, 
         return;
     }
     double acc[3] = {fsx + fax + fcx, fsy + fay + fcy, fsz + faz + fcz};
-    const double pos[3] = {pix, piy, piz};
+    if constexpr (PP::kNoisy) {
+        double xi[3];
+        noise_xi((uint32_t)b.id[r], P.step_lo, P.step_hi, P.seed_lo, P.seed_hi, xi[0], xi[1], xi[2]);
 #pragma unroll
-    for (int d = 0; d < 3; d++) {
-        const double dist_pos = pos[d] - (P.bounds - P.margin);
-        if (dist_pos > 0) acc[d] -= fmin(dist_pos / P.margin * 2.0, 1.0) * P.wall_force;
-        const double dist_neg = (-P.bounds + P.margin) - pos[d];
-        if (dist_neg > 0) acc[d] += fmin(dist_neg / P.margin * 2.0, 1.0) * P.wall_force;
+        for (int d = 0; d < 3; d++) acc[d] += P.amp * xi[d];
+    }
+    const double pos[3] = {pix, piy, piz};
+    if constexpr (!G::kPeriodic) {
+#pragma unroll
+        for (int d = 0; d < 3; d++) {
+            const double dist_pos = pos[d] - (P.bounds - P.margin);
+            if (dist_pos > 0) acc[d] -= fmin(dist_pos / P.margin * 2.0, 1.0) * P.wall_force;
+            const double dist_neg = (-P.bounds + P.margin) - pos[d];
+            if (dist_neg > 0) acc[d] += fmin(dist_neg / P.margin * 2.0, 1.0) * P.wall_force;
+        }
     }
     double nvx = vix + acc[0] * P.dt, nvy = viy + acc[1] * P.dt, nvz = viz + acc[2] * P.dt;
     const double speed = sqrt(nvx * nvx + nvy * nvy + nvz * nvz);
@@ -248,7 +315,13 @@ __device__ __forceinline__ void flock_finish(const BoidsAoS &b, const Boids &a, 
         nvx *= scale; nvy *= scale; nvz *= scale;
     }
     a.vx[r] = nvx; a.vy[r] = nvy; a.vz[r] = nvz;
-    a.px[r] = pix + nvx * P.dt; a.py[r] = piy + nvy * P.dt; a.pz[r] = piz + nvz * P.dt;
+    if constexpr (G::kPeriodic) {
+        // bdmi_step has checked max_speed * |dt| < L: one wrap brings the boid back into [-B, B]
+        auto wrapped = [&](double x) { return x > g.B ? x - g.L : (x < -g.B ? x + g.L : x); };
+        a.px[r] = wrapped(pix + nvx * P.dt); a.py[r] = wrapped(piy + nvy * P.dt); a.pz[r] = wrapped(piz + nvz * P.dt);
+    } else {
+        a.px[r] = pix + nvx * P.dt; a.py[r] = piy + nvy * P.dt; a.pz[r] = piz + nvz * P.dt;
+    }
     a.cr[r] = cir + (avr - cir) * P.blend;
     a.cg[r] = cig + (avg - cig) * P.blend;
     a.cb[r] = cib + (avb - cib) * P.blend;
@@ -266,6 +339,74 @@ __device__ __forceinline__ void flock_finish(const BoidsAoS &b, const Boids &a, 
 // every kernel that sweeps the grid.  A row of cells is 3 cells = at most two words of the occupancy table, and what a row
 // costs is a chain of dependent loads (table word -> run bounds -> candidates), not arithmetic: the three rows of a z plane
 // go through each stage TOGETHER, so that their loads are in flight at the same time.
+//
+// On a periodic grid (GridPer) the rows wrap in y and z, and in x a boid in cell 0 or dim - 1 has its three cells in TWO
+// runs of the sorted order ({dim-1} and {0, 1}, or {dim-2, dim-1} and {0}): up to 18 runs per boid, one row's two segments
+// next to each other.  dim >= 3 keeps the 27 wrapped cells distinct, so every boid is a candidate once.  Same shape: the
+// table words of a z plane's six segments are requested before any is used.
+struct RunWords {
+    uint2 wa, wb;
+    int lo_bit, hi_bit;
+    bool two, ok;
+};
+// the occupancy words of the cells [c_lo, c_hi] of one row (at most two words)
+__device__ __forceinline__ RunWords run_words(const uint2 *__restrict__ occ, int64_t c_lo, int64_t c_hi, bool ok) {
+    RunWords w;
+    w.ok = ok;
+    w.lo_bit = (int)(c_lo & 31);
+    w.hi_bit = (int)(c_hi & 31);
+    w.two = (c_lo >> 5) != (c_hi >> 5);
+    w.wa = ok ? occ[c_lo >> 5] : make_uint2(0u, 0u);
+    w.wb = (ok && w.two) ? occ[c_hi >> 5] : make_uint2(0u, 0u);
+    return w;
+}
+// the run [qb, qe) of sorted boids in those cells; qb == qe == 0 when all are empty
+__device__ __forceinline__ void run_bounds(const RunWords &w, const int32_t *__restrict__ cell_start, int32_t &qb, int32_t &qe) {
+    uint32_t ba = w.wa.x & (~0u << w.lo_bit);
+    uint32_t bb = w.wb.x & (~0u >> (31 - w.hi_bit));
+    if (!w.two) { ba &= ~0u >> (31 - w.hi_bit); bb = 0u; }
+    qb = 0; qe = 0;
+    if (w.ok && (ba | bb)) {
+        const uint2 fw = ba ? w.wa : w.wb;
+        const int first = ba ? __ffs(ba) - 1 : __ffs(bb) - 1;
+        const uint2 lw = bb ? w.wb : w.wa;
+        const int last = bb ? 31 - __clz(bb) : 31 - __clz(ba);
+        qb = cell_start[fw.y + __popc(fw.x & ((1u << first) - 1u))];
+        qe = cell_start[lw.y + __popc(lw.x & ((1u << last) - 1u)) + 1u];
+    }
+}
+template <class Emit>
+__device__ __forceinline__ void for_each_run(const double4 &p, const GridPer &g, const uint2 *__restrict__ occ,
+                                             const int32_t *__restrict__ cell_start, Emit emit) {
+    const int dim = g.dim;
+    const int cx = cell_coord(p.x, g), cy = cell_coord(p.y, g), cz = cell_coord(p.z, g);
+    // segment 0 = the cells next to each other, segment 1 = the one cell through the x face (face cells only)
+    int lo[2] = {cx - 1, 0}, hi[2] = {cx + 1, 0};
+    const bool face = cx == 0 || cx == dim - 1;
+    if (cx == 0) { lo[0] = 0; hi[0] = 1; lo[1] = hi[1] = dim - 1; }
+    if (cx == dim - 1) { lo[0] = dim - 2; hi[0] = dim - 1; lo[1] = hi[1] = 0; }
+    for (int dz = -1; dz <= 1; dz++) {
+        int ncz = cz + dz;
+        ncz = ncz < 0 ? dim - 1 : (ncz >= dim ? 0 : ncz);
+        RunWords w[6];
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            int ncy = cy + j - 1;
+            ncy = ncy < 0 ? dim - 1 : (ncy >= dim ? 0 : ncy);
+            const int64_t row = (int64_t)ncy * dim + (int64_t)ncz * dim * dim;
+            w[2 * j] = run_words(occ, row + lo[0], row + hi[0], true);
+            w[2 * j + 1] = run_words(occ, row + lo[1], row + hi[1], face);
+        }
+        int32_t qb[6], qe[6];
+#pragma unroll
+        for (int j = 0; j < 6; j++) run_bounds(w[j], cell_start, qb[j], qe[j]);
+#pragma unroll
+        for (int j = 0; j < 6; j++)
+            if (qe[j] > qb[j]) emit(qb[j], qe[j]);
+    }
+}
+
+// ... and the walled grid's nine runs (the periodic overload is above)
 template <class Emit>
 __device__ __forceinline__ void for_each_run(const double4 &p, const GridP &g, const uint2 *__restrict__ occ,
                                              const int32_t *__restrict__ cell_start, Emit emit) {
@@ -316,9 +457,17 @@ __device__ __forceinline__ void for_each_run(const double4 &p, const GridP &g, c
 
 // The sweeps (k_flock, topo_select) only NOTE the runs, in the lane's LDS column runs[2 row], runs[2 row + 1][thread], and
 // walk all nine in ONE loop behind the lookups [r4]; only the non-empty runs are noted, so that loop never has to step over
-// an empty one.  Returns their number; big = one of them is longer than 4095.
-template <int kThreads>
-__device__ __forceinline__ int note_runs(const double4 &p, const GridP &g, const uint2 *__restrict__ occ,
+// an empty one.  Returns their number; big = one of them is longer than the 16-bit notes of k_flock can address.
+// A walled boid has up to 9 runs: 4 bits of row, 12 of offset.  A periodic one has up to 18: 5 bits of row, 11 of offset,
+// and the one-by-one path above 2047.
+template <class G>
+struct RunNotes {
+    static constexpr int kRuns = G::kPeriodic ? 18 : 9;
+    static constexpr int kOffBits = G::kPeriodic ? 11 : 12;
+    static constexpr int kMaxLen = (1 << kOffBits) - 1;
+};
+template <int kThreads, class G>
+__device__ __forceinline__ int note_runs(const double4 &p, const G &g, const uint2 *__restrict__ occ,
                                          const int32_t *__restrict__ cell_start, int32_t (*runs)[kThreads], bool &big) {
     int nr = 0;
     big = false;
@@ -326,14 +475,14 @@ __device__ __forceinline__ int note_runs(const double4 &p, const GridP &g, const
         runs[2 * nr][threadIdx.x] = qb;
         runs[2 * nr + 1][threadIdx.x] = qe;
         nr++;
-        big = big || qe - qb > 4095;
+        big = big || qe - qb > RunNotes<G>::kMaxLen;
     });
     return nr;
 }
 
 // A lane's nr > 0 noted runs back to back: next() is the next candidate rank, or -1 behind the last one, and `code` its
-// (row << 12) | offset in the row's run (k_flock's 16-bit note of a neighbour).
-template <int kThreads>
+// (row << kOffBits) | offset in the row's run (k_flock's 16-bit note of a neighbour).
+template <int kThreads, int kOffBits>
 struct RunCursor {
     const int32_t (*runs)[kThreads];
     int nr, row = 0;
@@ -349,7 +498,7 @@ struct RunCursor {
             q = q_first = runs[2 * row][threadIdx.x];
             e = runs[2 * row + 1][threadIdx.x];
         }
-        code = ((unsigned)row << 12) | (unsigned)(q - q_first);
+        code = ((unsigned)row << kOffBits) | (unsigned)(q - q_first);
         return q++;
     }
 };
@@ -357,11 +506,11 @@ struct RunCursor {
 // before_trip() ahead of every trip, test(rank, code, position record) for every candidate in run order.  (A lane
 // without runs leaves at once: with the cursor's first loads behind a condition of their own the compiler wrapped lookup
 // and walk into one wave-level loop, 1.1 - 1.6 % on the topological sweep at k = 16: profiles/boids_runs_ab.txt.)
-template <int kThreads, class Before, class Test>
+template <int kThreads, int kOffBits, class Before, class Test>
 __device__ __forceinline__ void walk_runs(const double4 *__restrict__ pos, const int32_t (*runs)[kThreads], int nr,
                                           Before before_trip, Test test) {
     if (nr == 0) return;
-    RunCursor<kThreads> cur(runs, nr);
+    RunCursor<kThreads, kOffBits> cur(runs, nr);
     for (;;) {
         before_trip();
         unsigned k0 = 0, k1 = 0, k2 = 0, k3 = 0;
@@ -378,15 +527,19 @@ __device__ __forceinline__ void walk_runs(const double4 *__restrict__ pos, const
 
 // compute_flocking_spatial (flock.py:68-238) + update_physics_numba (flock.py:241-308).
 // kPhysics=false: write the four force arrays (caller's boid order) instead of integrating.
-template <bool kPhysics>
+// G = GridP or GridPer, PP = FlockP or FlockPN (a noisy step): the walled, noise-free instances are the kernels they
+// were.  LDS per block: 18 KiB of runs + 16 KiB of notes = 34 KiB walled (4 blocks = 16 waves per CU), 36 + 16 = 52 KiB
+// periodic (3 blocks = 12 waves per CU).
+template <bool kPhysics, class G, class PP>
 __global__ __launch_bounds__(kBlock) void k_flock(BoidsAoS b, Boids a, const uint2 *__restrict__ occ,
-                                                  const int32_t *__restrict__ cell_start, int64_t n, GridP g, FlockP P,
+                                                  const int32_t *__restrict__ cell_start, int64_t n, G g, PP P,
                                                   double *__restrict__ o_sep, double *__restrict__ o_ali,
                                                   double *__restrict__ o_coh, double *__restrict__ o_avg,
                                                   int xcd_contiguous) {
-    __shared__ int32_t runs[18][kBlock];  // [2 row, 2 row + 1][thread]: candidate run of the thread's boid in each of its nine rows
+    constexpr int kOffBits = RunNotes<G>::kOffBits;
+    __shared__ int32_t runs[2 * RunNotes<G>::kRuns][kBlock];  // [2 row, 2 row + 1][thread]: candidate run of the thread's boid in each of its rows
     constexpr int kHitCap = 32;
-    __shared__ unsigned short hits[kHitCap][kBlock];  // [k][thread]: the boid's neighbours found so far, (row << 12) | offset in the row's run
+    __shared__ unsigned short hits[kHitCap][kBlock];  // [k][thread]: the boid's neighbours found so far, (row << kOffBits) | offset in the row's run
     const int64_t r = logical_block(blockIdx.x, gridDim.x, xcd_contiguous) * kBlock + threadIdx.x;
     if (r >= n) return;
     const double4 pi4 = b.p[r], vi4 = b.v[r], ci4 = b.c[r];
@@ -400,7 +553,8 @@ __global__ __launch_bounds__(kBlock) void k_flock(BoidsAoS b, Boids a, const uin
     }
     FlockSums S;
     // the reference's test of one candidate (flock.py:134-148)
-    auto in_sight = [&](const double4 &qp) {
+    auto in_sight = [&](const double4 &q) {
+        const double4 qp = image_of(pi4, q, g);
         const double dx = pi4.x - qp.x, dy = pi4.y - qp.y, dz = pi4.z - qp.z;
         const double dist_sq = dx * dx + dy * dy + dz * dz;
         return dist_sq < P.perception_sq && dist_sq > 0.0001;
@@ -426,32 +580,32 @@ __global__ __launch_bounds__(kBlock) void k_flock(BoidsAoS b, Boids a, const uin
     auto flush = [&]() {
         for (int h = 0; h < nh; h += 2) {
             const unsigned e0 = hits[h][threadIdx.x], e1 = hits[h + 1 < nh ? h + 1 : h][threadIdx.x];
-            const int32_t q0 = runs[2 * (e0 >> 12)][threadIdx.x] + (int32_t)(e0 & 4095u);
-            const int32_t q1 = runs[2 * (e1 >> 12)][threadIdx.x] + (int32_t)(e1 & 4095u);
+            const int32_t q0 = runs[2 * (e0 >> kOffBits)][threadIdx.x] + (int32_t)(e0 & ((1u << kOffBits) - 1u));
+            const int32_t q1 = runs[2 * (e1 >> kOffBits)][threadIdx.x] + (int32_t)(e1 & ((1u << kOffBits) - 1u));
             const double4 p0 = b.p[q0], v0 = b.v[q0], c0 = b.c[q0], p1 = b.p[q1], v1 = b.v[q1], c1 = b.c[q1];
-            S.add(pi4, p0, v0, c0, P.separation_sq);
-            if (h + 1 < nh) S.add(pi4, p1, v1, c1, P.separation_sq);
+            S.add(pi4, image_of(pi4, p0, g), v0, c0, P.separation_sq);
+            if (h + 1 < nh) S.add(pi4, image_of(pi4, p1, g), v1, c1, P.separation_sq);
         }
         nh = 0;
     };
     if (big) {
-        // a run of more than 4095 boids (three cells!): its offsets do not fit the 16-bit notes - such a boid
-        // takes its candidates one by one
+        // a run of more than 4095 boids (three cells!; 2047 on a periodic grid): its offsets do not fit the 16-bit
+        // notes - such a boid takes its candidates one by one
         for (int k = 0; k < nr; k++)
             for (int32_t q = runs[2 * k][threadIdx.x]; q < runs[2 * k + 1][threadIdx.x]; q++) {
                 if (q == r) continue;
                 const double4 qp = b.p[q];
-                if (in_sight(qp)) S.add(pi4, qp, b.v[q], b.c[q], P.separation_sq);
+                if (in_sight(qp)) S.add(pi4, image_of(pi4, qp, g), b.v[q], b.c[q], P.separation_sq);
             }
     } else {
-        walk_runs<kBlock>(
+        walk_runs<kBlock, kOffBits>(
             b.p, runs, nr, [&]() { if (nh > kHitCap - 4) flush(); },
             [&](int32_t c, unsigned code, const double4 &qp) {
                 if (c != r && in_sight(qp)) hits[nh++][threadIdx.x] = (unsigned short)code;
             });
         flush();
     }
-    flock_finish<kPhysics>(b, a, r, P, pi4, vi4, ci4, S, o_sep, o_ali, o_coh, o_avg);
+    flock_finish<kPhysics>(b, a, r, g, P, pi4, vi4, ci4, S, o_sep, o_ali, o_coh, o_avg);
 }
 
 // ---- topological interaction: the k nearest within sight (include/bdmi.h has the specification) ------
@@ -460,15 +614,14 @@ __global__ __launch_bounds__(kBlock) void k_flock(BoidsAoS b, Boids a, const uin
 // over that list in its order, from +0.0, so the forces are a function of the state and the ids alone - not of the cell
 // order, the row order or the block order.
 constexpr int kTopoMaxK = 16;
-constexpr int kTopoRuns = 9;  // the runs noted per lane: all nine rows
 
 // The list of the boid at rank r (position pi4): ld2 / lq [slot][thread], ascending; returns its length.  Candidates come
 // from the nine row runs, noted and walked back to back as in k_flock.  The common case of a candidate inside the window
 // is a reject against the current k-th d2 (kept in a register); ids are loaded only to break an exact d2 tie.  Ranks are
 // stored whole, so a run may have any length.
-template <int kCap, int kThreads>
+template <int kCap, int kThreads, class G>
 __device__ __forceinline__ int topo_select(const BoidsAoS &b, const uint2 *__restrict__ occ, const int32_t *__restrict__ cell_start,
-                                           const GridP &g, int64_t r, const double4 &pi4, double perception_sq, int k,
+                                           const G &g, int64_t r, const double4 &pi4, double perception_sq, int k,
                                            int32_t (*runs)[kThreads], double (*ld2)[kThreads], int32_t (*lq)[kThreads]) {
     const int t = threadIdx.x;
     int cnt = 0;
@@ -498,10 +651,11 @@ __device__ __forceinline__ int topo_select(const BoidsAoS &b, const uint2 *__res
     };
     bool big;  // (no 16-bit notes here)
     const int nr = note_runs<kThreads>(pi4, g, occ, cell_start, runs, big);
-    walk_runs<kThreads>(
+    walk_runs<kThreads, RunNotes<G>::kOffBits>(
         b.p, runs, nr, [] {},
-        [&](int32_t c, unsigned, const double4 &qp) {
+        [&](int32_t c, unsigned, const double4 &q) {
             if (c == r) return;
+            const double4 qp = image_of(pi4, q, g);  // d2 is the image's
             const double dx = pi4.x - qp.x, dy = pi4.y - qp.y, dz = pi4.z - qp.z;
             const double d2 = (dx * dx + dy * dy) + dz * dz;
             if (d2 < perception_sq && d2 > 0.0001) insert(d2, c);
@@ -511,14 +665,15 @@ __device__ __forceinline__ int topo_select(const BoidsAoS &b, const uint2 *__res
 
 // compute_flocking_spatial with T_i in the place of the neighbour set + update_physics_numba.  kCap = the largest k this
 // instance serves: k <= 8 runs 256 threads per block (18 KiB of runs + 24 KiB of list = 42 KiB, 3 blocks = 12 waves per
-// CU), k <= 16 runs 128 threads per block (9 + 24 = 33 KiB, 4 blocks = 8 waves per CU).
-template <bool kPhysics, int kCap, int kThreads>
+// CU), k <= 16 runs 128 threads per block (9 + 24 = 33 KiB, 4 blocks = 8 waves per CU).  On a periodic grid the runs
+// are twice as many: 36 + 24 = 60 KiB (2 blocks = 8 waves per CU) and 18 + 24 = 42 KiB (3 blocks = 6 waves per CU).
+template <bool kPhysics, int kCap, int kThreads, class G, class PP>
 __global__ __launch_bounds__(kThreads) void k_flock_topo(BoidsAoS b, Boids a, const uint2 *__restrict__ occ,
-                                                         const int32_t *__restrict__ cell_start, int64_t n, GridP g, FlockP P,
+                                                         const int32_t *__restrict__ cell_start, int64_t n, G g, PP P,
                                                          int k, double *__restrict__ o_sep, double *__restrict__ o_ali,
                                                          double *__restrict__ o_coh, double *__restrict__ o_avg,
                                                          int xcd_contiguous) {
-    __shared__ int32_t runs[2 * kTopoRuns][kThreads];
+    __shared__ int32_t runs[2 * RunNotes<G>::kRuns][kThreads];
     __shared__ double ld2[kCap][kThreads];
     __shared__ int32_t lq[kCap][kThreads];
     const int t = threadIdx.x;
@@ -531,19 +686,19 @@ __global__ __launch_bounds__(kThreads) void k_flock_topo(BoidsAoS b, Boids a, co
     for (int h = 0; h < cnt; h += 2) {
         const int32_t q0 = lq[h][t], q1 = lq[h + 1 < cnt ? h + 1 : h][t];
         const double4 p0 = b.p[q0], v0 = b.v[q0], c0 = b.c[q0], p1 = b.p[q1], v1 = b.v[q1], c1 = b.c[q1];
-        S.add(pi4, p0, v0, c0, P.separation_sq);
-        if (h + 1 < cnt) S.add(pi4, p1, v1, c1, P.separation_sq);
+        S.add(pi4, image_of(pi4, p0, g), v0, c0, P.separation_sq);
+        if (h + 1 < cnt) S.add(pi4, image_of(pi4, p1, g), v1, c1, P.separation_sq);
     }
-    flock_finish<kPhysics>(b, a, r, P, pi4, vi4, ci4, S, o_sep, o_ali, o_coh, o_avg);
+    flock_finish<kPhysics>(b, a, r, g, P, pi4, vi4, ci4, S, o_sep, o_ali, o_coh, o_avg);
 }
 
 // bdmi_topological_neighbours: the lists themselves, rows in the caller's order, padded with -1 / +inf
-template <int kCap, int kThreads>
+template <int kCap, int kThreads, class G>
 __global__ __launch_bounds__(kThreads) void k_topo_rows(BoidsAoS b, const uint2 *__restrict__ occ,
-                                                        const int32_t *__restrict__ cell_start, int64_t n, GridP g,
+                                                        const int32_t *__restrict__ cell_start, int64_t n, G g,
                                                         double perception_sq, int k, int32_t *__restrict__ o_ids,
                                                         double *__restrict__ o_d2, int32_t *__restrict__ o_count) {
-    __shared__ int32_t runs[2 * kTopoRuns][kThreads];
+    __shared__ int32_t runs[2 * RunNotes<G>::kRuns][kThreads];
     __shared__ double ld2[kCap][kThreads];
     __shared__ int32_t lq[kCap][kThreads];
     const int t = threadIdx.x;
@@ -583,6 +738,16 @@ __global__ __launch_bounds__(kBlock) void k_cells_out(Boids a, int64_t n, GridP 
     if (r >= n) return;
     const int cx = cell_coord(a.px[r], g), cy = cell_coord(a.py[r], g), cz = cell_coord(a.pz[r], g);
     out[a.id[r]] = cx + cy * g.dim + cz * g.dim * g.dim;
+}
+
+// bdmi_noise_vectors: xi_i(step) for the caller ids i = 0 .. n - 1
+__global__ __launch_bounds__(kBlock) void k_noise_vectors(int64_t n, uint32_t seed_lo, uint32_t seed_hi, uint32_t step_lo,
+                                                          uint32_t step_hi, double *__restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    double x, y, z;
+    noise_xi((uint32_t)i, step_lo, step_hi, seed_lo, seed_hi, x, y, z);
+    out[3 * i] = x; out[3 * i + 1] = y; out[3 * i + 2] = z;
 }
 
 // ---- slab mode (multi-GPU): selections of rows by a predicate, in row order ------------------------------
@@ -944,6 +1109,13 @@ struct bdmi_flock {
     double *stage = nullptr;  // 12 N doubles
     int xcd_contiguous = 1;   // sweep block -> XCD mapping, see logical_block()
     int nb_mode = BDMI_NEIGHBOURS_METRIC, nb_k = 7;  // bdmi_set_neighbour_mode; BDMI_NEIGHBOURS at create
+    // bdmi_create_periodic: the box [-box_b, box_b]^3 of edge box_l; `grid` is then the periodic grid
+    bool periodic = false;
+    double box_b = 0, box_l = 0;
+    // bdmi_set_noise; the step counts the substeps since create whether or not eta > 0
+    double noise_eta = 0;
+    uint64_t noise_seed = 0;
+    int64_t noise_step = 0;
     // bdmi_topological_neighbours scratch ((N, topo_cap) ids and d2, (N,) counts), allocated on first use
     int32_t *topo_ids = nullptr, *topo_cnt = nullptr;
     double *topo_d2 = nullptr;
@@ -1044,18 +1216,48 @@ void topo_launch(int k, int64_t n, F launch) {
         launch(std::integral_constant<int, kTopoMaxK>{}, std::integral_constant<int, 128>{}, (int)((n + 127) / 128));
 }
 
-// the sweep of the handle's neighbour mode over the grid enqueue_grid has just built
-template <bool kPhysics>
-void enqueue_sweep(bdmi_flock *f, const FlockP &P, double *d0, double *d1, double *d2, double *d3) {
+GridPer periodic_grid(const bdmi_flock *f) {
+    GridPer g;
+    g.cell_size = f->grid.cell_size; g.offset = f->grid.offset; g.dim = f->grid.dim;
+    g.B = f->box_b; g.L = f->box_l;
+    return g;
+}
+
+// the sweep of the handle's neighbour mode over the grid enqueue_grid has just built, as the instance of its grid G and
+// its parameters PP
+template <bool kPhysics, class G, class PP>
+void enqueue_sweep_as(bdmi_flock *f, const G &g, const PP &P, double *d0, double *d1, double *d2, double *d3) {
     const int64_t n = f->n;
     if (f->nb_mode != BDMI_NEIGHBOURS_TOPOLOGICAL)
-        k_flock<kPhysics><<<nblocks(n), kBlock, 0, f->stream>>>(f->B, f->A, f->occ, f->cell_start, n, f->grid, P, d0, d1, d2, d3,
-                                                               f->xcd_contiguous);
+        k_flock<kPhysics, G, PP><<<nblocks(n), kBlock, 0, f->stream>>>(f->B, f->A, f->occ, f->cell_start, n, g, P, d0, d1, d2, d3,
+                                                                      f->xcd_contiguous);
     else
         topo_launch(f->nb_k, n, [&](auto cap, auto threads, int blocks) {
-            k_flock_topo<kPhysics, decltype(cap)::value, decltype(threads)::value><<<blocks, decltype(threads)::value, 0, f->stream>>>(
-                f->B, f->A, f->occ, f->cell_start, n, f->grid, P, f->nb_k, d0, d1, d2, d3, f->xcd_contiguous);
+            k_flock_topo<kPhysics, decltype(cap)::value, decltype(threads)::value, G, PP>
+                <<<blocks, decltype(threads)::value, 0, f->stream>>>(f->B, f->A, f->occ, f->cell_start, n, g, P, f->nb_k, d0, d1,
+                                                                     d2, d3, f->xcd_contiguous);
         });
+}
+// walled or periodic; a step (kPhysics) of a handle with eta > 0 runs the noisy instance with the noise step `step`, every
+// other sweep the instance without the term (no "+ 0.0 * xi")
+template <bool kPhysics>
+void enqueue_sweep(bdmi_flock *f, const FlockP &P, int64_t step, double *d0, double *d1, double *d2, double *d3) {
+    auto with_grid = [&](const auto &PP) {
+        if (f->periodic) enqueue_sweep_as<kPhysics>(f, periodic_grid(f), PP, d0, d1, d2, d3);
+        else enqueue_sweep_as<kPhysics>(f, f->grid, PP, d0, d1, d2, d3);
+    };
+    if constexpr (kPhysics) {
+        if (f->noise_eta > 0) {
+            FlockPN N;
+            static_cast<FlockP &>(N) = P;
+            N.amp = f->noise_eta * P.max_force;
+            N.seed_lo = (uint32_t)f->noise_seed; N.seed_hi = (uint32_t)(f->noise_seed >> 32);
+            N.step_lo = (uint32_t)(uint64_t)step; N.step_hi = (uint32_t)((uint64_t)step >> 32);
+            with_grid(N);
+            return;
+        }
+    }
+    with_grid(P);
 }
 
 }  // namespace
@@ -1109,16 +1311,42 @@ static int bd_create_impl(bdmi_flock *f, const double *pos, const double *vel, c
     return 0;
 }
 
+// A periodic handle takes only positions inside its box: the first row of (n, 3) positions with a coordinate that is not
+// finite or outside [-b, b], or -1
+static int64_t first_row_outside(const double *pos, int64_t n, double b) {
+    for (int64_t i = 0; i < 3 * n; i++)
+        if (!(pos[i] >= -b && pos[i] <= b)) return i / 3;  // NaN fails both
+    return -1;
+}
+
 static bdmi_flock *bd_create(int64_t n, const double *pos, const double *vel, const double *col, const double *params,
                              int device, bool slab, int64_t capacity, const int32_t *ids, double x_lo, double x_hi,
-                             int has_left, int has_right) {
+                             int has_left, int has_right, bool periodic = false) {
     nbmi::clear_error();
     if (n < 0 || n > 1000000000 || !params || (n > 0 && (!pos || !vel || !col))) {
-        nbmi::set_error("bdmi_create: bad arguments (n=%lld)", (long long)n);
+        nbmi::set_error("%s: bad arguments (n=%lld)", periodic ? "bdmi_create_periodic" : "bdmi_create", (long long)n);
         return nullptr;
     }
     const double bounds = params[0], perception = params[5], margin = params[1];
-    if (!(bounds > 0) || !(perception > 0) || !(margin > 0)) {
+    if (periodic) {
+        // wall_margin and wall_weight are ignored; the grid is dim = floor(L / perception) cells of L / dim per axis
+        if (!(bounds > 0) || !(perception > 0) || !(bounds < INFINITY)) {
+            nbmi::set_error("bdmi_create_periodic: bounds and perception_radius must be finite and > 0");
+            return nullptr;
+        }
+        const double dimf = floor(2 * bounds / perception);
+        if (!(dimf >= 3) || dimf > 1290) {
+            nbmi::set_error("bdmi_create_periodic: grid dimension floor(2 * bounds / perception_radius) = %.0f must be in "
+                            "3..1290 (below 3 the 27 wrapped cells are not distinct)", dimf);
+            return nullptr;
+        }
+        const int64_t bad = first_row_outside(pos, n, bounds);
+        if (bad >= 0) {
+            nbmi::set_error("bdmi_create_periodic: position row %lld = (%g, %g, %g) is not finite or outside the box [-%g, %g]",
+                            (long long)bad, pos[3 * bad], pos[3 * bad + 1], pos[3 * bad + 2], bounds, bounds);
+            return nullptr;
+        }
+    } else if (!(bounds > 0) || !(perception > 0) || !(margin > 0)) {
         nbmi::set_error("bdmi_create: bounds, perception_radius and wall_margin must be > 0");
         return nullptr;
     }
@@ -1153,16 +1381,25 @@ static bdmi_flock *bd_create(int64_t n, const double *pos, const double *vel, co
     f->slab = slab; f->cap = slab ? capacity : 0;
     f->x_lo = x_lo; f->x_hi = x_hi; f->has_left = has_left; f->has_right = has_right;
     memcpy(f->params, params, sizeof(f->params));
-    // Flock.__init__ grid (flock.py:478-481)
-    f->grid.cell_size = perception;
-    const double dimf = ceil(bounds * 2 / perception) + 2;
-    if (!(dimf >= 1) || dimf > 1290) {  // dim^3 must fit int32 cell ids
-        nbmi::set_error("bdmi_create: grid dimension %.0f out of range", dimf);
-        delete f;
-        return nullptr;
+    if (periodic) {
+        f->periodic = true;
+        f->box_b = bounds;
+        f->box_l = 2 * bounds;
+        f->grid.dim = (int)floor(f->box_l / perception);
+        f->grid.cell_size = f->box_l / f->grid.dim;
+        f->grid.offset = bounds;
+    } else {
+        // Flock.__init__ grid (flock.py:478-481)
+        f->grid.cell_size = perception;
+        const double dimf = ceil(bounds * 2 / perception) + 2;
+        if (!(dimf >= 1) || dimf > 1290) {  // dim^3 must fit int32 cell ids
+            nbmi::set_error("bdmi_create: grid dimension %.0f out of range", dimf);
+            delete f;
+            return nullptr;
+        }
+        f->grid.dim = (int)dimf;
+        f->grid.offset = bounds + perception;
     }
-    f->grid.dim = (int)dimf;
-    f->grid.offset = bounds + perception;
     f->num_cells = (int64_t)f->grid.dim * f->grid.dim * f->grid.dim;
     f->key_bits = 1;
     while (((int64_t)1 << f->key_bits) < f->num_cells) f->key_bits++;
@@ -1187,6 +1424,11 @@ static bdmi_flock *bd_create(int64_t n, const double *pos, const double *vel, co
 bdmi_flock *bdmi_create(int64_t n, const double *pos, const double *vel, const double *col, const double *params,
                         int device) {
     return bd_create(n, pos, vel, col, params, device, false, 0, nullptr, 0.0, 0.0, 0, 0);
+}
+
+bdmi_flock *bdmi_create_periodic(int64_t n, const double *pos, const double *vel, const double *col, const double *params,
+                                 int device) {
+    return bd_create(n, pos, vel, col, params, device, false, 0, nullptr, 0.0, 0.0, 0, 0, true);
 }
 
 // ---- slab mode --------------------------------------------------------------------------
@@ -1327,12 +1569,20 @@ int bdmi_step(bdmi_flock *f, double dt, int substeps) {
                         f->params[3] * fabs(dt), 2.0 * f->params[5]);
         return -1;
     }
-    if (f->n == 0) return 0;
+    // A periodic handle wraps a boid once per step: the displacement must stay below one box length.
+    if (f->periodic && !(f->params[3] * fabs(dt) < f->box_l)) {
+        nbmi::set_error("bdmi_step: on a periodic handle max_speed * |dt| = %g must stay below the box length %g (a boid is "
+                        "wrapped once per step)", f->params[3] * fabs(dt), f->box_l);
+        return -1;
+    }
+    // (the noise step counts the substeps of ordinary handles; a slab handle has no noise and no counter to keep)
+    if (f->n == 0) { if (!f->slab) f->noise_step += substeps; return 0; }
     const FlockP P = make_params(f, dt);
     for (int k = 0; k < substeps; k++) {
         if (int rc = enqueue_grid(f, f->timers)) return rc;
-        enqueue_sweep<true>(f, P, nullptr, nullptr, nullptr, nullptr);
+        enqueue_sweep<true>(f, P, f->noise_step, nullptr, nullptr, nullptr, nullptr);
         NBMI_HIP_CHECK(hipGetLastError());
+        if (!f->slab) f->noise_step++;
         if (f->timers) {
             NBMI_HIP_CHECK(hipEventRecord(f->ev[3], f->stream));
             NBMI_HIP_CHECK(hipEventSynchronize(f->ev[3]));
@@ -1392,6 +1642,15 @@ int bdmi_set_state(bdmi_flock *f, const double *pos, const double *vel, const do
     if (int rc = whole_flock_check(f, "bdmi_set_state")) return rc;
     const int64_t n = f->n;
     if (n == 0) return 0;
+    if (f->periodic && pos) {
+        const int64_t bad = first_row_outside(pos, n, f->box_b);
+        if (bad >= 0) {
+            nbmi::set_error("bdmi_set_state: position row %lld = (%g, %g, %g) is not finite or outside the periodic box "
+                            "[-%g, %g]; nothing was uploaded", (long long)bad, pos[3 * bad], pos[3 * bad + 1], pos[3 * bad + 2],
+                            f->box_b, f->box_b);
+            return -1;
+        }
+    }
     double *dp = f->stage, *dv = dp + 3 * n, *dc = dv + 3 * n;
     if (pos) NBMI_HIP_CHECK(hipMemcpyAsync(dp, pos, (size_t)n * 24, hipMemcpyHostToDevice, f->stream));
     if (vel) NBMI_HIP_CHECK(hipMemcpyAsync(dv, vel, (size_t)n * 24, hipMemcpyHostToDevice, f->stream));
@@ -1423,7 +1682,7 @@ int bdmi_get_forces(bdmi_flock *f, double *sep, double *ali, double *coh, double
     if (int rc = enqueue_grid(f, false)) return rc;
     double *d0 = f->stage, *d1 = d0 + 3 * n, *d2 = d1 + 3 * n, *d3 = d2 + 3 * n;
     const FlockP P = make_params(f, 0.0);
-    enqueue_sweep<false>(f, P, d0, d1, d2, d3);
+    enqueue_sweep<false>(f, P, 0, d0, d1, d2, d3);
     NBMI_HIP_CHECK(hipGetLastError());
     NBMI_HIP_CHECK(hipMemcpyAsync(sep, d0, (size_t)n * 24, hipMemcpyDeviceToHost, f->stream));
     NBMI_HIP_CHECK(hipMemcpyAsync(ali, d1, (size_t)n * 24, hipMemcpyDeviceToHost, f->stream));
@@ -1483,14 +1742,68 @@ int bdmi_topological_neighbours(bdmi_flock *f, int k, int32_t *ids, double *d2, 
     hipStream_t st = f->stream;
     const double psq = f->params[5] * f->params[5];
     topo_launch(k, n, [&](auto cap, auto threads, int blocks) {
-        k_topo_rows<decltype(cap)::value, decltype(threads)::value><<<blocks, decltype(threads)::value, 0, st>>>(
-            f->B, f->occ, f->cell_start, n, f->grid, psq, k, f->topo_ids, f->topo_d2, f->topo_cnt);
+        auto rows = [&](const auto &g) {
+            k_topo_rows<decltype(cap)::value, decltype(threads)::value><<<blocks, decltype(threads)::value, 0, st>>>(
+                f->B, f->occ, f->cell_start, n, g, psq, k, f->topo_ids, f->topo_d2, f->topo_cnt);
+        };
+        if (f->periodic) rows(periodic_grid(f)); else rows(f->grid);
     });
     NBMI_HIP_CHECK(hipGetLastError());
     if (ids) NBMI_HIP_CHECK(hipMemcpyAsync(ids, f->topo_ids, (size_t)n * k * 4, hipMemcpyDeviceToHost, st));
     if (d2) NBMI_HIP_CHECK(hipMemcpyAsync(d2, f->topo_d2, (size_t)n * k * 8, hipMemcpyDeviceToHost, st));
     if (count) NBMI_HIP_CHECK(hipMemcpyAsync(count, f->topo_cnt, (size_t)n * 4, hipMemcpyDeviceToHost, st));
     return sync_checked(f);
+}
+
+// ---- periodic box and noise (include/bdmi.h) --------------------------------------------------------------------------
+int bdmi_get_box(bdmi_flock *f, int *periodic, double *length, double *cell_size) {
+    if (int rc = topo_handle_check(f, "bdmi_get_box")) return rc;
+    if (periodic) *periodic = f->periodic ? 1 : 0;
+    if (length) *length = f->periodic ? f->box_l : 2 * f->params[0];
+    if (cell_size) *cell_size = f->grid.cell_size;
+    return 0;
+}
+
+int bdmi_set_noise(bdmi_flock *f, double eta, uint64_t seed, int64_t step) {
+    if (int rc = topo_handle_check(f, "bdmi_set_noise")) return rc;
+    if (!(eta >= 0) || !(eta < INFINITY)) {
+        nbmi::set_error("bdmi_set_noise: eta = %g must be finite and >= 0", eta);
+        return -1;
+    }
+    if (step < -1) {
+        nbmi::set_error("bdmi_set_noise: step = %lld must be >= 0, or -1 to keep the handle's step", (long long)step);
+        return -1;
+    }
+    f->noise_eta = eta;
+    f->noise_seed = seed;
+    if (step >= 0) f->noise_step = step;
+    return 0;
+}
+
+int bdmi_get_noise(bdmi_flock *f, double *eta, uint64_t *seed, int64_t *step) {
+    if (int rc = topo_handle_check(f, "bdmi_get_noise")) return rc;
+    if (eta) *eta = f->noise_eta;
+    if (seed) *seed = f->noise_seed;
+    if (step) *step = f->noise_step;
+    return 0;
+}
+
+int bdmi_noise_vectors(bdmi_flock *f, int64_t step, double *out_xyz) {
+    if (int rc = topo_handle_check(f, "bdmi_noise_vectors")) return rc;
+    if (step < -1) {
+        nbmi::set_error("bdmi_noise_vectors: step = %lld must be >= 0, or -1 for the handle's step", (long long)step);
+        return -1;
+    }
+    const int64_t n = f->n;
+    if (n == 0) return 0;
+    if (!out_xyz) { nbmi::set_error("bdmi_noise_vectors: null output"); return -1; }
+    const uint64_t s = (uint64_t)(step >= 0 ? step : f->noise_step);
+    k_noise_vectors<<<nblocks(n), kBlock, 0, f->stream>>>(n, (uint32_t)f->noise_seed, (uint32_t)(f->noise_seed >> 32), (uint32_t)s,
+                                                         (uint32_t)(s >> 32), f->stage);
+    NBMI_HIP_CHECK(hipGetLastError());
+    NBMI_HIP_CHECK(hipMemcpyAsync(out_xyz, f->stage, (size_t)n * 24, hipMemcpyDeviceToHost, f->stream));
+    NBMI_HIP_CHECK(hipStreamSynchronize(f->stream));
+    return 0;
 }
 
 int bdmi_grid_info(bdmi_flock *f, int32_t *grid_dim, int64_t *num_cells, int64_t *occupied) {
@@ -1598,6 +1911,11 @@ int bdmi_visible_vertices(bdmi_flock *f, const double *cam12, double tan_h, doub
 namespace {
 int fs_radius_check(bdmi_flock *f, const char *what, const char *name, double v) {
     if (int rc = whole_flock_check(f, what)) return rc;
+    if (f->periodic) {
+        nbmi::set_error("%s: refused on a periodic handle (bdmi_create_periodic): links through the faces of the box are "
+                        "not followed yet", what);
+        return -1;
+    }
     const double perception = f->params[5];
     if (!(v > 0) || !(v <= perception)) {  // NaN fails the first test, +inf the second
         nbmi::set_error("%s: %s = %g must be finite, > 0 and at most the perception radius %g (the grid cell)", what, name, v,

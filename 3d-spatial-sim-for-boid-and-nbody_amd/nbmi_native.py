@@ -128,6 +128,11 @@ PROTOTYPES = {
     "bdmi_set_neighbour_mode": (C.c_int, [_vp, C.c_int, C.c_int]),
     "bdmi_get_neighbour_mode": (C.c_int, [_vp, _vp, _vp]),
     "bdmi_topological_neighbours": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
+    "bdmi_create_periodic": (_vp, [_i64, _vp, _vp, _vp, _vp, C.c_int]),
+    "bdmi_get_box": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "bdmi_set_noise": (C.c_int, [_vp, _dbl, C.c_uint64, _i64]),
+    "bdmi_get_noise": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "bdmi_noise_vectors": (C.c_int, [_vp, _i64, _vp]),
     "bdmi_visible_vertices": (C.c_int, [_vp, _vp, _dbl, _dbl, _dbl, _dbl, _dbl, _vp, _vp, _i64, _vp]),
     "bdmi_render_triangles": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp]),
     "bdmi_render_flock": (C.c_int, [_vp, _vp, _vp, _dbl, _dbl, _dbl, _dbl, _dbl, _vp, _vp, _vp]),

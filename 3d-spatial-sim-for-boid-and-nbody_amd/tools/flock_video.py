@@ -8,6 +8,7 @@ machine without GL, display or window system.
     python -m tools.flock_video --boids 2m --resolution 1080p --camera orbit --format ppm -o frames/
     python -m tools.flock_video --boids 2m --frames 600 --diagnostics 10   # + flock.flock.jsonl: flocks, order parameters
     python -m tools.flock_video --boids 500k --neighbours topological --topological-k 7   # the k nearest within sight
+    python -m tools.flock_video --boids 100k --periodic --noise 0.5 --noise-seed 3        # no walls, vectorial noise
 
 Each frame: flock.update(dt, substeps), render_flock, sink.  Output formats and sinks are those of tools.export.
 With --diagnostics K every K-th frame also appends one JSON line (boids.analysis.jsonl_line) to <output stem>.flock.jsonl:
@@ -15,6 +16,10 @@ the whole flock's row, the number of flocks and links at --link, the mean neighb
 flocks of at least --min-members boids, all computed on the device (include/bdmi.h).
 With --neighbours topological the flock interacts by the topological rule of include/bdmi.h (--topological-k nearest
 neighbours within the perception radius); the clip's metadata and the analysis lines then name the mode.
+With --periodic the domain is the periodic box of include/bdmi.h (no walls, neighbours through the faces), with --noise ETA
+every update adds a unit vector of amplitude ETA * max_force, drawn from (--noise-seed, update, boid), to each boid's
+acceleration; both are set before the warm-up and named in the metadata and the analysis lines.  The flock finder does not
+follow links through the faces yet: with --periodic, --diagnostics writes the whole flock's row only.
 """
 import argparse
 import json
@@ -69,6 +74,12 @@ def build_parser():
                          "--topological-k nearest of them (topological)")
     ap.add_argument("--topological-k", type=int, default=7, metavar="K",
                     help="neighbours per boid with --neighbours topological, 1..16 (default: 7)")
+    ap.add_argument("--periodic", action="store_true",
+                    help="periodic box instead of walls; --diagnostics then writes the whole-flock row only, without flocks "
+                         "or neighbour counts")
+    ap.add_argument("--noise", type=float, default=0.0, metavar="ETA",
+                    help="vectorial noise: ETA * max_force times a random unit vector per boid and update (default: 0, off)")
+    ap.add_argument("--noise-seed", type=int, default=0, metavar="S", help="seed of the noise (default: 0)")
     return ap
 
 
@@ -123,16 +134,19 @@ def diagnostics_path(output: Path) -> Path:
     return output.with_name((output.stem if output.suffix else output.name) + ".flock.jsonl")
 
 
-def analysis_line(flock, frame, steps, link, min_members, neighbours=None) -> str:
-    """One line of the analysis file for the flock's current state (four device calls, no state copied out)."""
-    from boids.analysis import jsonl_line
+def analysis_line(flock, frame, steps, link, min_members, neighbours=None, periodic=False, noise=None) -> str:
+    """One line of the analysis file for the flock's current state (four device calls, no state copied out; on a
+    periodic flock one call: the whole flock's row)."""
+    from boids.analysis import global_line, jsonl_line
+    if periodic:
+        return global_line(frame, steps, flock.diagnostics(), neighbours=neighbours, periodic=True, noise=noise)
     fl = flock.flocks(link)
     cat = flock.flock_catalogue(link, min_members=min_members, capacity=LARGEST_FLOCKS)
     nb = flock.neighbour_stats(link)
     count = np.asarray(nb["count"])
     return jsonl_line(frame, steps, flock.diagnostics(), fl["n_flocks"], fl["links"],
                       float(count.mean()) if count.size else 0.0, cat["rows"], flock_labels=cat["label"],
-                      link=link, min_members=min_members, qualifying=cat["count"], neighbours=neighbours)
+                      link=link, min_members=min_members, qualifying=cat["count"], neighbours=neighbours, noise=noise)
 
 
 def run(args, make_flock=None, make_renderer=None, say=print) -> dict:
@@ -149,9 +163,14 @@ def run(args, make_flock=None, make_renderer=None, say=print) -> dict:
     if topological and not 1 <= topo_k <= 16:
         raise ValueError("--topological-k must be in 1..16")
     neighbours = {"mode": "topological", "k": topo_k} if topological else None
+    periodic = bool(getattr(args, "periodic", False))
+    eta = float(getattr(args, "noise", 0.0) or 0.0)
+    if not (0.0 <= eta < float("inf")):
+        raise ValueError("--noise must be finite and not negative")
+    noise = {"eta": eta, "seed": int(getattr(args, "noise_seed", 0))} if eta > 0 else None
     if make_flock is None:
         from boids import Flock
-        make_flock = lambda n, seed, device: Flock(n, seed=seed, device=device)  # noqa: E731
+        make_flock = lambda n, seed, device, **kw: Flock(n, seed=seed, device=device, **kw)  # noqa: E731
     if make_renderer is None:
         from boids.render import HIPFlockRenderer
         make_renderer = lambda w, h, device: HIPFlockRenderer(w, h, device=device)  # noqa: E731
@@ -161,7 +180,8 @@ def run(args, make_flock=None, make_renderer=None, say=print) -> dict:
     dt = frame_dt(args)
     say(f"[Flock] {args.boids:,} boids, {args.frames} frames, {width}x{height} @ {args.fps} fps, dt {dt:.4f} x "
         f"{args.substeps}, camera {args.camera}, {fmt} -> {output}")
-    flock = make_flock(args.boids, args.seed, args.device)
+    flock = make_flock(args.boids, args.seed, args.device, periodic=True) if periodic else \
+        make_flock(args.boids, args.seed, args.device)
     renderer = make_renderer(width, height, args.device)
     sink = make_sink(args, fmt, output, width, height)
     diag_path = diagnostics_path(output) if every else None
@@ -173,6 +193,8 @@ def run(args, make_flock=None, make_renderer=None, say=print) -> dict:
     try:
         if topological:
             flock.set_neighbour_mode("topological", topo_k)
+        if noise:
+            flock.set_noise(noise["eta"], seed=noise["seed"])
         if args.warmup:
             flock.update(dt, args.warmup)
         img = np.empty((height, width, 3), dtype=np.uint8)
@@ -194,7 +216,7 @@ def run(args, make_flock=None, make_renderer=None, say=print) -> dict:
                 ta = time.perf_counter()
                 steps = args.warmup + (i + 1) * args.substeps
                 diag_file.write(analysis_line(flock, i, steps, getattr(args, "link", None), min_members,
-                                              neighbours) + "\n")
+                                              neighbours, periodic, noise) + "\n")
                 diag_lines += 1
                 t_analysis += time.perf_counter() - ta
         ok = True
@@ -217,6 +239,10 @@ def run(args, make_flock=None, make_renderer=None, say=print) -> dict:
                           "angle": args.camera_angle, "theta": args.camera_theta}
         if topological:
             meta["flock"]["neighbours"] = neighbours
+        if periodic:
+            meta["flock"]["periodic"] = True
+        if noise:
+            meta["flock"]["noise"] = noise
         if every:
             meta["diagnostics"] = {"file": diag_path.name, "every": every, "link": getattr(args, "link", None),
                                    "min_members": min_members, "lines": diag_lines}

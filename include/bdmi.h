@@ -166,6 +166,71 @@ int bdmi_get_neighbour_mode(bdmi_flock *f, int *mode, int *k); /* either may be 
 int bdmi_topological_neighbours(bdmi_flock *f, int k, int32_t *ids /* (N,k) */, double *d2 /* (N,k) */,
                                 int32_t *count /* (N,) */); /* each may be NULL */
 
+/* ---- periodic box and seeded vectorial noise ----------------------------------------------------
+ * The experiment the order parameters of bdmi_diagnostics exist for - order against noise (Vicsek et al. 1995; Gregoire &
+ * Chate 2004; Ballerini et al. 2008 for the topological rule) - needs a domain without walls and a noise amplitude to
+ * sweep.  Both are opt-in: a handle made by bdmi_create that never sets noise runs the kernels it ran before and gives
+ * their bits.  This text is the specification; the kernels (csrc/bdmi.hip) and the tests' NumPy restatements
+ * (tests/periodic_ref.py, tests/noise_ref.py) both follow it.  All arithmetic is float64 in the association written,
+ * without FMA, with correctly rounded sqrt and divide.
+ *
+ * PERIODIC HANDLES: bdmi_create_periodic, same arguments as bdmi_create.
+ *   Box and grid: B = bounds, L = 2 * B (one float64 product); the box is [-B, B] per axis.  dim = floor(L /
+ *     perception_radius), cell_size = L / dim (so cell_size >= perception_radius), offset = B.  The cell coordinate of x is
+ *     int((x + offset) / cell_size) clamped to [0, dim - 1], so x == +B falls into the last cell.
+ *   Refused with NBMI_ERR_ARG: dim < 3 or dim > 1290 (with dim < 3 the 27 wrapped cells are not distinct, and a neighbour
+ *     has more than one image in sight); at create and at bdmi_set_state a position that is not finite or outside [-B, B]:
+ *     the message names the first offending row and nothing is uploaded.  wall_margin and wall_weight are ignored
+ *     (wall_margin > 0 is not required).
+ *   The IMAGE of a candidate j for boid i, per axis: d0 = p_i - q_j; q' = q_j + L if d0 > B, q' = q_j - L if d0 < -B,
+ *     otherwise q' = q_j.  Equality does not shift.  From here on q' stands in for the neighbour's position in every
+ *     formula of compute_flocking_spatial: dx = p_i - q', d2 = (dx dx + dy dy) + dz dz, the window 1e-4 < d2 <
+ *     perception_radius^2 is unchanged, the separation terms come from dx, the cohesion sum adds q'.  Where no shift
+ *     happens the operations and the bits are those of a walled handle.
+ *   The candidate cells are the 27 cells (cx+a, cy+b, cz+c) mod dim.  With dim >= 3 and cell_size >= perception_radius
+ *     each boid is a candidate exactly once, and its image above is the only one that can be in the window.
+ *   Both neighbour modes work.  In topological mode the order is (d2, id) with the d2 above and the fixed summation order
+ *     holds, so forces and stepped state are a pure function of state and ids.
+ *   Physics: update_physics_numba without the wall terms.  After p' = p + v' dt, per axis: if p' > B then p' = p' - L,
+ *     else if p' < -B then p' = p' + L.  bdmi_step on a periodic handle requires max_speed * |dt| < L (-1 otherwise and
+ *     nothing is run, like the slab rule): one wrap is then enough and the state stays inside [-B, B].
+ *   bdmi_get_box: each output may be NULL.  Walled handles give periodic = 0, length = 2 * bounds, cell_size =
+ *     perception_radius; periodic ones 1, L and L / dim.
+ *   Work unchanged on periodic handles: bdmi_get_state, bdmi_set_state, bdmi_get_cell_indices (the periodic grid's
+ *     indices), bdmi_get_forces, bdmi_topological_neighbours (d2 is the image d2), bdmi_set_neighbour_mode /
+ *     bdmi_get_neighbour_mode, BDMI_NEIGHBOURS, bdmi_grid_info, the timers, bdmi_visible_vertices, bdmi_render_flock, and
+ *     bdmi_diagnostics: polarisation, mean speed and vbar do not depend on positions; c, milling, lo and hi are computed
+ *     from the coordinates in the box as they stand (a flock that straddles a face has its centre in between).
+ *   Refused on periodic handles with NBMI_ERR_ARG ("<call>: ... periodic ..."), before anything is launched and with the
+ *     outputs untouched: bdmi_flocks, bdmi_flock_catalogue, bdmi_neighbour_stats.  (A follow-up: linking through the
+ *     faces is easy, a flock's centre on a torus is not.)  There is no periodic slab handle.
+ *
+ * NOISE, on walled and periodic handles, not on slab handles.
+ *   bdmi_set_noise(f, eta, seed, step): eta must be finite and >= 0.  step >= 0 sets the handle's noise step, step == -1
+ *     keeps it.  bdmi_get_noise reads all three back; each output may be NULL.
+ *   The noise step of a handle starts at 0 at create and advances by one per Flock.update, that is per substep of
+ *     bdmi_step, whether or not eta > 0.  bdmi_set_state does not touch it.
+ *   The unit vector xi_i(step) of the boid with caller id i.  For attempts a = 0, 1, 2, ...: the Philox4x32-10 block with
+ *     counter {i, (uint32)step, (uint32)(step >> 32), a} and key {(uint32)seed, (uint32)(seed >> 32)} yields words
+ *     w0..w3; pair 0 is (w0, w1), pair 1 is (w2, w3).  For a pair (u, v): x1 = ((double)u + 0.5) * 2^-31 - 1, x2 likewise
+ *     from v, s = x1 x1 + x2 x2.  The first pair with s < 1 is accepted (pair 0 before pair 1, attempt a before a + 1).
+ *     Then t = sqrt(1 - s) and xi = ((2 x1) t, (2 x2) t, 1 - 2 s): Marsaglia 1972, correctly rounded operations only.
+ *   How it enters the step: A = eta * max_force is one host product; acc_c = ((sep_c + ali_c) + coh_c) + A * xi_c; the
+ *     wall terms of a walled handle follow, then the unchanged velocity clamp and integration.  The four arrays of
+ *     bdmi_get_forces do not contain the noise.  With eta == 0 the step's operations are exactly those without noise: no
+ *     "+ 0.0 * xi".
+ *   bdmi_noise_vectors(f, step, out): a parity hook: xi_i(step) under the handle's seed, rows in the caller's order, for
+ *     any step >= 0; step == -1 means the handle's current step.  It works with eta == 0 and changes nothing a later step
+ *     reads.
+ *   Refused with NBMI_ERR_ARG ("<call>: ..."), outputs and settings untouched: a null handle, a slab handle (for
+ *     bdmi_get_box too), an eta that is negative or not finite (the message names it), step < -1. */
+bdmi_flock *bdmi_create_periodic(int64_t n, const double *positions_xyz, const double *velocities_xyz,
+                                 const double *colors_rgb, const double *params11, int device);
+int bdmi_get_box(bdmi_flock *f, int *periodic, double *length, double *cell_size); /* each may be NULL */
+int bdmi_set_noise(bdmi_flock *f, double eta, uint64_t seed, int64_t step);
+int bdmi_get_noise(bdmi_flock *f, double *eta, uint64_t *seed, int64_t *step); /* each may be NULL */
+int bdmi_noise_vectors(bdmi_flock *f, int64_t step, double *out_xyz /* (N,3) */);
+
 /* ---- multi-GPU: x-slabs with a one-cell halo -----------------------------------------
  * A rank owns the boids with x_lo <= x < x_hi (a whole number of cell planes, at least two cells wide); the
  * neighbour sweep needs the boids within one cell (= the perception radius, flock.py:479) on the other side

@@ -1,0 +1,75 @@
+"""Are the kernels of csrc/bdmi.hip the same instructions in two source trees?  (the walled, noise-free
+sweep against the commit before the periodic box.)  Needs hipcc and c++filt, no GPU.
+
+    git worktree add /tmp/parent <commit>
+    python scripts/compare_kernel_asm.py /tmp/parent . [kernel name fragments ...]
+
+Each tree's bdmi.hip is compiled to device assembly for gfx950 with the Makefile's flags.  Kernels are matched by their
+demangled name up to the argument list, with the template arguments this tree added for the walled, noise-free instances
+(", GridP, FlockP" / ", GridP") dropped, so k_flock<true> of the old tree meets k_flock<true, GridP, FlockP> of the new
+one.  Compared: the instruction lines, with symbol names and block labels normalised, and the register, LDS and scratch
+figures of the kernel descriptor.  Exit status 1 if a kernel present in both trees differs.
+"""
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+PKG = "3d-spatial-sim-for-boid-and-nbody_amd"
+FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "--cuda-device-only", "-S"]
+FACTS = ("next_free_vgpr", "next_free_sgpr", "group_segment_fixed_size", "private_segment_fixed_size")
+ANON = "(anonymous namespace)::"
+
+
+def kernels(tree, tmp, tag):
+    out = os.path.join(tmp, tag + ".s")
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    subprocess.run([hipcc, *FLAGS, "-o", out, os.path.join(tree, PKG, "csrc", "bdmi.hip")], check=True,
+                   stderr=subprocess.DEVNULL)
+    text = open(out).read()
+    found = {m.group(1): m.group(2)
+             for m in re.finditer(r"^(_Z\w+):[^\n]*\n(.*?)^\s*\.end_amdhsa_kernel", text, re.S | re.M)}
+    names = subprocess.run(["c++filt", *found], capture_output=True, text=True, check=True).stdout.split("\n")
+    res = {}
+    for name, body in zip(names, found.values()):
+        short = name.replace(ANON, "").split("(")[0]
+        res[short.replace(", GridP, FlockP>", ">").replace(", GridP>", ">")] = body
+    return res
+
+
+def instructions(body):
+    lines = []
+    for line in body.split("\n"):
+        line = line.split(";")[0].rstrip()
+        if line.strip() and not line.lstrip().startswith("."):
+            lines.append(re.sub(r"\.LBB\d+_", ".LBB_", re.sub(r"_Z\w+", "SYM", line)))
+    return lines
+
+
+def facts(body):
+    return tuple(int(re.search(r"\.amdhsa_" + k + r"\s+(\d+)", body).group(1)) for k in FACTS)
+
+
+def main(argv):
+    if len(argv) < 2:
+        raise SystemExit(__doc__)
+    with tempfile.TemporaryDirectory() as tmp:
+        a, b = kernels(argv[0], tmp, "a"), kernels(argv[1], tmp, "b")
+    differ = 0
+    for name in sorted(set(a) & set(b)):
+        if argv[2:] and not any(f in name for f in argv[2:]):
+            continue
+        ia, ib = instructions(a[name]), instructions(b[name])
+        moved = sum(x != y for x, y in zip(ia, ib)) + abs(len(ia) - len(ib))
+        same = ia == ib and facts(a[name]) == facts(b[name])
+        differ += not same
+        print(f"{'identical' if same else 'DIFFERS  '} {name}: {len(ia)} / {len(ib)} instructions"
+              + ("" if same else f", {moved} lines differ") + f", vgpr/sgpr/lds/scratch {facts(a[name])} / {facts(b[name])}")
+    only = sorted(set(b) - set(a))
+    print(f"{len(only)} kernels only in {argv[1]}:", ", ".join(only))
+    return 1 if differ else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv[1:]))
