@@ -1,7 +1,8 @@
 """Pure NumPy helpers around the flock-analysis calls of include/bdmi.h (Flock.flocks, flock_catalogue, diagnostics,
 neighbour_stats): the named fields of a row of 16 doubles, the size histogram of a catalogue, and the builder of the
 JSON line that tools.flock_video writes with --diagnostics; and the order-against-noise experiment over
-Flock.set_noise / Flock.diagnostics (order_parameter_series, binder_cumulant, noise_sweep).  Nothing here touches the
+Flock.set_noise / Flock.diagnostics (order_parameter_series, binder_cumulant, noise_sweep), with percolation_summary for
+the catalogue of a periodic flock (Flock.periodic_flock_catalogue).  Nothing here touches the
 device itself: the helpers work on any object with the Flock methods they name.
 """
 import json
@@ -44,19 +45,28 @@ def _settings(rec, neighbours, periodic, noise):
 
 
 def global_line(frame, steps, global_row, neighbours=None, periodic=False, noise=None) -> str:
-    """The analysis line of a periodic flock: the frame, the step count and the whole flock's row, without flocks or
-    neighbour counts (the flock finder does not follow links through the faces of the box)."""
+    """The short analysis line of a periodic flock: the frame, the step count and the whole flock's row, without flocks or
+    neighbour counts (jsonl_line with ``flock_spans`` is the full one, from the Flock.periodic_* calls)."""
     rec = {"frame": int(frame), "steps": int(steps), "global": row_dict(global_row)}
     return json.dumps(_settings(rec, neighbours, periodic, noise))
 
 
 def jsonl_line(frame, steps, global_row, n_flocks, links, mean_neighbours, flock_rows, flock_labels=None,
-               link=None, min_members=None, qualifying=None, neighbours=None, noise=None) -> str:
+               link=None, min_members=None, qualifying=None, neighbours=None, noise=None, flock_spans=None,
+               periodic=False) -> str:
     """One flock-analysis line: the frame, the step count, the whole flock's row, the number of flocks and links, the
     mean neighbour count and the rows of the largest flocks (largest first), as one JSON object without a newline.
     ``neighbours`` ({"mode": "topological", "k": K}) names the interaction rule where it is not the metric default,
-    ``noise`` ({"eta": E, "seed": S}) the noise where there is one."""
+    ``noise`` ({"eta": E, "seed": S}) the noise where there is one, ``periodic`` the periodic box.  ``flock_spans`` (the
+    ``spans`` of Flock.periodic_flock_catalogue, bool (rows, 3)) adds ``"spans"`` to every listed flock; without it the
+    line has no such key."""
     rows = [row_dict(r) for r in np.asarray(flock_rows, dtype=np.float64).reshape(-1, 16)]
+    if flock_spans is not None:
+        spans = np.asarray(flock_spans, dtype=bool).reshape(-1, 3)
+        if len(spans) != len(rows):
+            raise ValueError(f"flock_spans has {len(spans)} rows for {len(rows)} flocks")
+        for r, sp in zip(rows, spans.tolist()):
+            r["spans"] = sp
     if flock_labels is not None:
         for r, l in zip(rows, np.asarray(flock_labels).tolist()):
             r["label"] = int(l)
@@ -68,7 +78,7 @@ def jsonl_line(frame, steps, global_row, n_flocks, links, mean_neighbours, flock
         rec["min_members"] = int(min_members)
     if qualifying is not None:
         rec["qualifying_flocks"] = int(qualifying)
-    return json.dumps(_settings(rec, neighbours, False, noise))
+    return json.dumps(_settings(rec, neighbours, periodic, noise))
 
 
 def neighbour_rank_profile(d2) -> np.ndarray:
@@ -82,6 +92,24 @@ def neighbour_rank_profile(d2) -> np.ndarray:
     total = np.where(have, np.sqrt(np.where(have, d2, 0.0)), 0.0).sum(axis=0)
     cnt = have.sum(axis=0)
     return np.where(cnt > 0, total / np.maximum(cnt, 1), np.nan)
+
+
+def percolation_summary(catalogue, n) -> dict:
+    """What the catalogue of a periodic flock of ``n`` boids (Flock.periodic_flock_catalogue, largest flock first) says
+    about percolation: ``largest_fraction`` = members of the largest flock / n (0 without a flock), ``spanning_flocks`` =
+    how many of the catalogued flocks occupy every slab of at least one axis, ``largest_spans`` = the three per-axis
+    flags of the largest.  Spanning is the header's conservative test: a flock that reaches around the box spans, and so
+    does a C-shaped one that does not close."""
+    members = np.asarray(catalogue["members"], dtype=np.int64)
+    spans = np.asarray(catalogue["spans"], dtype=bool).reshape(-1, 3)
+    if len(spans) != len(members):
+        raise ValueError(f"the catalogue has {len(members)} flocks and {len(spans)} rows of spans")
+    if int(n) < 0 or (members.size and int(members[0]) > int(n)):
+        raise ValueError(f"n = {n} is smaller than the largest flock")
+    if members.size == 0:
+        return {"largest_fraction": 0.0, "spanning_flocks": 0, "largest_spans": [False, False, False]}
+    return {"largest_fraction": float(members[0]) / float(n), "spanning_flocks": int(spans.any(axis=1).sum()),
+            "largest_spans": spans[0].tolist()}
 
 
 # ---- order against noise (Vicsek et al. 1995): the polarisation of a flock as a function of the noise amplitude --------

@@ -252,6 +252,44 @@ class Flock:
                                                       C.addressof(evals)), "bdmi_neighbour_stats")
         return dict(count=count, nn_d2=nn, evals=int(evals.value))
 
+    # ---- flock analysis on a periodic flock (include/bdmi.h: links through the faces, a flock's row on the torus) ----
+    def periodic_flocks(self, link=None):
+        """``flocks`` on a periodic flock: links are followed through the faces of the box.  The same dict."""
+        labels = np.empty(self.num_boids, dtype=np.int32)
+        nf, links, evals = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        _nat.check_arg(self._lib.bdmi_periodic_flocks(self._h, self._link(link), _nat.ptr(labels), C.addressof(nf),
+                                                      C.addressof(links), C.addressof(evals)), "bdmi_periodic_flocks")
+        return dict(labels=labels, n_flocks=int(nf.value), links=int(links.value), evals=int(evals.value))
+
+    def periodic_flock_catalogue(self, link=None, min_members=1, capacity=64):
+        """``flock_catalogue`` on a periodic flock.  A flock that straddles a face is unwrapped before its row is taken:
+        its centre lies inside the flock (brought back into the box), ``hi`` may exceed the bounds and ``hi - lo`` is its
+        extent.  The dict of ``flock_catalogue`` plus ``wrap`` (int32 (rows, 3): per axis the cell coordinate the flock
+        was cut at, -1 where it occupies every slab of the axis) and ``spans`` (bool (rows, 3): ``wrap == -1``; a flock
+        that reaches around the box spans, and so does one that merely has a member in every slab)."""
+        cap = int(capacity)
+        label = np.empty(max(cap, 0), dtype=np.int32)
+        members = np.empty(max(cap, 0), dtype=np.int64)
+        rows = np.empty((max(cap, 0), 16), dtype=np.float64)
+        wrap = np.empty((max(cap, 0), 3), dtype=np.int32)
+        cnt = C.c_int64(0)
+        _nat.check_arg(self._lib.bdmi_periodic_flock_catalogue(self._h, self._link(link), int(min_members), cap,
+                                                               _nat.ptr(label), _nat.ptr(members), _nat.ptr(rows),
+                                                               _nat.ptr(wrap), C.addressof(cnt)),
+                       "bdmi_periodic_flock_catalogue")
+        k = min(int(cnt.value), cap)
+        return dict(count=int(cnt.value), label=label[:k], members=members[:k], rows=rows[:k], wrap=wrap[:k],
+                    spans=wrap[:k] == -1)
+
+    def periodic_neighbour_stats(self, radius=None):
+        """``neighbour_stats`` on a periodic flock: the others within ``radius`` through the faces.  The same dict."""
+        count = np.empty(self.num_boids, dtype=np.int32)
+        nn = np.empty(self.num_boids, dtype=np.float64)
+        evals = C.c_int64(0)
+        _nat.check_arg(self._lib.bdmi_periodic_neighbour_stats(self._h, self._link(radius), _nat.ptr(count), _nat.ptr(nn),
+                                                               C.addressof(evals)), "bdmi_periodic_neighbour_stats")
+        return dict(count=count, nn_d2=nn, evals=int(evals.value))
+
     # ---- topological interaction (include/bdmi.h: the k nearest neighbours within sight) ---------------------
     def set_neighbour_mode(self, mode, k=7):
         """``"metric"`` (the default: every boid within the perception radius counts, the reference's rule) or

@@ -828,6 +828,10 @@ struct FlockStats {
     double *part = nullptr, *rows16 = nullptr;
     int32_t *row_label = nullptr;
     int64_t *row_members = nullptr;
+    // ... on a periodic handle also per row: the occupancy words of its three axes, the cuts, the unwrapped centre
+    uint32_t *occ_mask = nullptr;
+    int32_t *wrap3 = nullptr;
+    double *centre = nullptr;
     int64_t rows_cap = 0, chunks_cap = 0;
 };
 
@@ -835,6 +839,19 @@ struct FlockStats {
 __device__ __forceinline__ double fs_d2(const double4 &a, const double4 &b) {
     const double dx = b.x - a.x, dy = b.y - a.y, dz = b.z - a.z;
     return (dx * dx + dy * dy) + dz * dz;
+}
+// ... and the d2 of the periodic flock analysis (include/bdmi.h, "Flock analysis on periodic handles"): the DIFFERENCE is
+// brought into [-B, B], not the neighbour's position as in image_of, so d2(i, j) and d2(j, i) are the same bits and the
+// link relation does not depend on which boid of a pair evaluates it.  Equality does not shift.
+template <class G>
+__device__ __forceinline__ double fs_dist(const double4 &a, const double4 &b, const G &g) {
+    if constexpr (G::kPeriodic) {
+        auto axis = [&](double d) { return d > g.B ? d - g.L : (d < -g.B ? d + g.L : d); };
+        const double dx = axis(b.x - a.x), dy = axis(b.y - a.y), dz = axis(b.z - a.z);
+        return (dx * dx + dy * dy) + dz * dz;
+    } else {
+        return fs_d2(a, b);
+    }
 }
 
 __global__ __launch_bounds__(kBlock) void k_fs_init(int64_t n, int32_t *__restrict__ parent, int32_t *__restrict__ minid,
@@ -848,8 +865,11 @@ __global__ __launch_bounds__(kBlock) void k_fs_init(int64_t n, int32_t *__restri
 // exactly once (by its higher rank) and `links` is the exact number of linked pairs - a pair is NOT skipped because its
 // boids are in one set already.  A run of any length is walked in place: there are no 16-bit notes here.  Every access
 // to parent[] goes through unionfind.h (agent-scope relaxed atomics, invariants (a)-(d)); no loop waits on another thread.
+// G = GridP or GridPer (the up to 18 wrapped runs and fs_dist's d2; dim >= 3 keeps the 27 cells distinct, so a pair is
+// still met once): the GridP instance is the kernel it was.
+template <class G>
 __global__ __launch_bounds__(kBlock) void k_fs_link(const double4 *__restrict__ pos, const uint2 *__restrict__ occ,
-                                                    const int32_t *__restrict__ cell_start, int64_t n, GridP g, double b2,
+                                                    const int32_t *__restrict__ cell_start, int64_t n, G g, double b2,
                                                     int32_t *parent, unsigned long long *counters) {
     const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     long long links = 0, evals = 0;
@@ -859,7 +879,7 @@ __global__ __launch_bounds__(kBlock) void k_fs_link(const double4 *__restrict__ 
         for_each_run(pi, g, occ, cell_start, [&](int32_t qb, int32_t qe) {
             const int32_t e = qe < (int32_t)r ? qe : (int32_t)r;
             for (int32_t q = qb; q < e; q++) {
-                const double d2 = fs_d2(pi, pos[q]);
+                const double d2 = fs_dist(pi, pos[q], g);
                 evals++;
                 if (d2 <= b2) {
                     links++;
@@ -897,10 +917,11 @@ __global__ __launch_bounds__(kBlock) void k_fs_labels(int64_t n, const int32_t *
     nbmi::wave_add(n_roots, is_root ? 1ll : 0ll, threadIdx.x & 63);
 }
 // The full sweep of the nine rows per boid: count[i] = #{j != i : d2 <= r2}, nn_d2[i] = the least such d2 or +inf.
-// An integer count and a minimum: exact whatever the order.
+// An integer count and a minimum: exact whatever the order.  G as in k_fs_link.
+template <class G>
 __global__ __launch_bounds__(kBlock) void k_fs_neighbours(const double4 *__restrict__ pos, const int32_t *__restrict__ id,
                                                           const uint2 *__restrict__ occ, const int32_t *__restrict__ cell_start,
-                                                          int64_t n, GridP g, double r2, int32_t *__restrict__ count,
+                                                          int64_t n, G g, double r2, int32_t *__restrict__ count,
                                                           double *__restrict__ nn_d2, unsigned long long *evals_out) {
     const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     long long evals = 0;
@@ -911,7 +932,7 @@ __global__ __launch_bounds__(kBlock) void k_fs_neighbours(const double4 *__restr
         for_each_run(pi, g, occ, cell_start, [&](int32_t qb, int32_t qe) {
             for (int32_t q = qb; q < qe; q++) {
                 if (q == (int32_t)r) continue;
-                const double d2 = fs_d2(pi, pos[q]);
+                const double d2 = fs_dist(pi, pos[q], g);
                 evals++;
                 if (d2 <= r2) {
                     c++;
@@ -995,22 +1016,45 @@ __device__ __forceinline__ double fs_heading(const double4 &v, double &ux, doubl
     if (s != 0.0) { ux = v.x / s; uy = v.y / s; uz = v.z / s; }
     return s;
 }
-template <int kPass>
+// Where the positions of a row's members come from: FsBox takes them as they stand (walled handles, and bdmi_diagnostics
+// on either kind); FsTorus unwraps them first (bdmi_periodic_flock_catalogue): y = x + L on an axis where the member's cell
+// coordinate lies below the row's cut wrap3[3 row + axis] (k_fs_wrap; -1 = the flock spans the axis, nothing is moved),
+// the milling pass takes the unwrapped centre c~ kept in centre[3 row ..], and the row's c is c~ brought back into the box.
+// A compile-time policy like GridP / GridPer: the FsBox instances are the kernels they were.
+struct FsBox {
+    static constexpr bool kTorus = false;
+};
+struct FsTorus {
+    static constexpr bool kTorus = true;
+    GridPer g;
+    const int32_t *wrap3;
+    double *centre;
+    __device__ __forceinline__ double4 unwrapped(const double4 &p, int row) const {
+        const int32_t *s = wrap3 + 3 * (int64_t)row;
+        return make_double4(cell_coord(p.x, g) < s[0] ? p.x + g.L : p.x, cell_coord(p.y, g) < s[1] ? p.y + g.L : p.y,
+                            cell_coord(p.z, g) < s[2] ? p.z + g.L : p.z, p.w);
+    }
+};
+template <int kPass, class X>
 __global__ __launch_bounds__(kBlock) void k_fs_chunks(const double4 *__restrict__ pos, const double4 *__restrict__ vel,
                                                       const uint32_t *__restrict__ rank_s, const uint32_t *__restrict__ rkey,
                                                       const uint32_t *__restrict__ rhead, int64_t n,
                                                       const int32_t *__restrict__ chunk_off, int rows,
-                                                      const double *__restrict__ rows16, double *__restrict__ part) {
+                                                      const double *__restrict__ rows16, double *__restrict__ part, X tor) {
     const int row = fs_row_of(chunk_off, rows, (int)blockIdx.x);
     const int64_t m = n - (int64_t)rkey[row], head = rhead[row];
     const int64_t first = head + (int64_t)((int)blockIdx.x - chunk_off[row]) * kFsChunk;
     const int64_t end = first + kFsChunk < head + m ? first + kFsChunk : head + m;
     double *out = part + (int64_t)blockIdx.x * kFsVals;
+    auto position = [&](int64_t r) {
+        if constexpr (X::kTorus) return tor.unwrapped(pos[r], row);
+        else return pos[r];
+    };
     if (kPass == 1) {
         double v[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
         for (int64_t j = first + threadIdx.x; j < end; j += kBlock) {
             const int64_t r = rank_s ? (int64_t)rank_s[j] : j;
-            const double4 p = pos[r], w = vel[r];
+            const double4 p = position(r), w = vel[r];
             double ux, uy, uz;
             const double s = fs_heading(w, ux, uy, uz);
             v[0] += p.x; v[1] += p.y; v[2] += p.z;
@@ -1023,11 +1067,13 @@ __global__ __launch_bounds__(kBlock) void k_fs_chunks(const double4 *__restrict_
         const int op[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 2, 2, 2};
         fs_block_fold(v, op, out);
     } else {
-        const double cx = rows16[16 * (int64_t)row + 1], cy = rows16[16 * (int64_t)row + 2], cz = rows16[16 * (int64_t)row + 3];
+        const double *centre = rows16 + 16 * (int64_t)row + 1;
+        if constexpr (X::kTorus) centre = tor.centre + 3 * (int64_t)row;
+        const double cx = centre[0], cy = centre[1], cz = centre[2];
         double v[3] = {0, 0, 0};
         for (int64_t j = first + threadIdx.x; j < end; j += kBlock) {
             const int64_t r = rank_s ? (int64_t)rank_s[j] : j;
-            const double4 p = pos[r], w = vel[r];
+            const double4 p = position(r), w = vel[r];
             double ux, uy, uz;
             (void)fs_heading(w, ux, uy, uz);
             double rx = p.x - cx, ry = p.y - cy, rz = p.z - cz;
@@ -1042,12 +1088,13 @@ __global__ __launch_bounds__(kBlock) void k_fs_chunks(const double4 *__restrict_
     }
 }
 // one thread per row: the chunks' partials in chunk order, then the row's fields
-template <int kPass>
+template <int kPass, class X>
 __global__ __launch_bounds__(kBlock) void k_fs_combine(const uint32_t *__restrict__ lab_s, const uint32_t *__restrict__ rkey,
                                                        const uint32_t *__restrict__ rhead, int64_t n,
                                                        const int32_t *__restrict__ chunk_off, int rows,
                                                        const double *__restrict__ part, double *__restrict__ rows16,
-                                                       int32_t *__restrict__ row_label, int64_t *__restrict__ row_members) {
+                                                       int32_t *__restrict__ row_label, int64_t *__restrict__ row_members,
+                                                       X tor) {
     const int row = blockIdx.x * kBlock + threadIdx.x;
     if (row >= rows) return;
     const int64_t members = n - (int64_t)rkey[row];
@@ -1061,7 +1108,16 @@ __global__ __launch_bounds__(kBlock) void k_fs_combine(const uint32_t *__restric
         for (int c = c0 + 1; c < c1; c++)
             for (int k = 0; k < 16; k++) v[k] = fs_fold(op[k], v[k], part[(int64_t)c * kFsVals + k]);
         o[0] = m;
-        o[1] = v[0] / m; o[2] = v[1] / m; o[3] = v[2] / m;
+        if constexpr (X::kTorus) {
+            // the unwrapped centre stays for the milling pass; the row gets it brought back into the box
+            for (int k = 0; k < 3; k++) {
+                const double c = v[k] / m;
+                tor.centre[3 * (int64_t)row + k] = c;
+                o[1 + k] = c > tor.g.B ? c - tor.g.L : c;
+            }
+        } else {
+            o[1] = v[0] / m; o[2] = v[1] / m; o[3] = v[2] / m;
+        }
         o[4] = v[3] / m; o[5] = v[4] / m; o[6] = v[5] / m;
         o[7] = sqrt((v[6] * v[6] + v[7] * v[7]) + v[8] * v[8]) / m;
         o[8] = v[9] / m;
@@ -1076,6 +1132,55 @@ __global__ __launch_bounds__(kBlock) void k_fs_combine(const uint32_t *__restric
             for (int k = 0; k < 3; k++) v[k] += part[(int64_t)c * kFsVals + k];
         o[9] = sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]) / m;
     }
+}
+
+// ---- a flock's cut on the torus (include/bdmi.h, "Flock analysis on periodic handles") --------------------------------------
+// O_a of a row = one bit per cell coordinate that its members occupy on axis a: `words` = ceil(dim / 32) words per axis,
+// mask[(3 row + a) words ..].  One block per chunk of the rows' member list, as k_fs_chunks: the members' bits are ORed
+// into an LDS mask (integer atomics: the result does not depend on their order), then the block's non-zero words into the
+// row's mask in global memory.  cell_coord clamps into [0, dim - 1] and a periodic handle has dim <= 1290, so a word index
+// stays below `words` <= kFsOccWords.
+constexpr int kFsOccWords = (1290 + 31) / 32;
+__global__ __launch_bounds__(kBlock) void k_fs_occupancy(const double4 *__restrict__ pos, const uint32_t *__restrict__ rank_s,
+                                                         const uint32_t *__restrict__ rkey, const uint32_t *__restrict__ rhead,
+                                                         int64_t n, const int32_t *__restrict__ chunk_off, int rows, GridPer g,
+                                                         int words, uint32_t *__restrict__ mask) {
+    __shared__ uint32_t bits[3 * kFsOccWords];
+    const int row = fs_row_of(chunk_off, rows, (int)blockIdx.x);
+    const int64_t m = n - (int64_t)rkey[row], head = rhead[row];
+    const int64_t first = head + (int64_t)((int)blockIdx.x - chunk_off[row]) * kFsChunk;
+    const int64_t end = first + kFsChunk < head + m ? first + kFsChunk : head + m;
+    for (int k = threadIdx.x; k < 3 * words; k += kBlock) bits[k] = 0u;
+    __syncthreads();
+    for (int64_t j = first + threadIdx.x; j < end; j += kBlock) {
+        const double4 p = pos[rank_s[j]];
+        const int c[3] = {cell_coord(p.x, g), cell_coord(p.y, g), cell_coord(p.z, g)};
+#pragma unroll
+        for (int a = 0; a < 3; a++) atomicOr(&bits[a * words + (c[a] >> 5)], 1u << (c[a] & 31));
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < 3 * words; k += kBlock)
+        if (bits[k]) atomicOr(&mask[(int64_t)row * 3 * words + k], bits[k]);
+}
+// One thread per (row, axis): wrap = -1 where all dim coordinates are occupied (the flock spans the axis), else the
+// smallest occupied coordinate whose cyclic predecessor is free.  A row has a member, so such a coordinate exists.
+__global__ __launch_bounds__(kBlock) void k_fs_wrap(const uint32_t *__restrict__ mask, int rows, int dim, int words,
+                                                    int32_t *__restrict__ wrap3) {
+    const int t = blockIdx.x * kBlock + threadIdx.x;
+    if (t >= 3 * rows) return;
+    const uint32_t *w = mask + (int64_t)t * words;
+    int occupied = 0;
+    for (int k = 0; k < words; k++) occupied += __popc(w[k]);
+    int32_t cut = -1;
+    if (occupied < dim) {
+        uint32_t carry = (w[(dim - 1) >> 5] >> ((dim - 1) & 31)) & 1u;  // the predecessor of coordinate 0 is dim - 1
+        for (int k = 0; k < words; k++) {
+            const uint32_t starts = w[k] & ~((w[k] << 1) | carry);
+            if (starts) { cut = 32 * k + __ffs(starts) - 1; break; }
+            carry = w[k] >> 31;
+        }
+    }
+    wrap3[t] = cut;
 }
 
 inline int nblocks(int64_t n) { return (int)((n + kBlock - 1) / kBlock); }
@@ -1909,11 +2014,20 @@ int bdmi_visible_vertices(bdmi_flock *f, const double *cam12, double tan_h, doub
 
 // ---- flock analysis (the kernels are above, next to the sweep whose grid they share) ---------------------------------
 namespace {
-int fs_radius_check(bdmi_flock *f, const char *what, const char *name, double v) {
+// walled_call = null: `what` is one of the walled calls, which refuse a periodic handle; else `what` is the periodic
+// counterpart of walled_call and refuses everything but a periodic handle
+int fs_radius_check(bdmi_flock *f, const char *what, const char *name, double v, const char *walled_call = nullptr) {
+    if (walled_call && !f) { nbmi::set_error("%s: null bdmi_flock handle", what); return -1; }
     if (int rc = whole_flock_check(f, what)) return rc;
-    if (f->periodic) {
-        nbmi::set_error("%s: refused on a periodic handle (bdmi_create_periodic): links through the faces of the box are "
-                        "not followed yet", what);
+    if (f->periodic && !walled_call) {
+        nbmi::set_error("%s: refused on a periodic handle (bdmi_create_periodic): this call does not follow links through the "
+                        "faces of the box; bdmi_periodic_flocks, bdmi_periodic_flock_catalogue and "
+                        "bdmi_periodic_neighbour_stats do", what);
+        return -1;
+    }
+    if (!f->periodic && walled_call) {
+        nbmi::set_error("%s: refused on a walled handle (bdmi_create): it works on the periodic box of bdmi_create_periodic; "
+                        "use %s", what, walled_call);
         return -1;
     }
     const double perception = f->params[5];
@@ -1954,12 +2068,16 @@ int fs_buffers(bdmi_flock *f) {
         return -2;
     return 0;
 }
+int fs_occ_words(const bdmi_flock *f) { return (f->grid.dim + 31) / 32; }
 int fs_row_buffers(bdmi_flock *f, int64_t rows, int64_t chunks) {
     FlockStats &s = f->fs;
     if (rows > s.rows_cap) {
         s.rows_cap = 0;
         if (dev_regrow(f, &s.chunk_off, (size_t)rows + 1) || dev_regrow(f, &s.rows16, (size_t)rows * 16) ||
             dev_regrow(f, &s.row_label, (size_t)rows) || dev_regrow(f, &s.row_members, (size_t)rows))
+            return -2;
+        if (f->periodic && (dev_regrow(f, &s.occ_mask, (size_t)rows * 3 * fs_occ_words(f)) ||
+                            dev_regrow(f, &s.wrap3, (size_t)rows * 3) || dev_regrow(f, &s.centre, (size_t)rows * 3)))
             return -2;
         s.rows_cap = rows;
     }
@@ -1980,16 +2098,20 @@ int fs_enqueue_flocks(bdmi_flock *f, double b2) {
     if (int rc = enqueue_grid(f, false)) return rc;
     NBMI_HIP_CHECK(hipMemsetAsync(s.counters, 0, 4 * sizeof(unsigned long long), st));
     k_fs_init<<<nblocks(n), kBlock, 0, st>>>(n, s.parent, s.minid, s.cnt, s.rank);
-    k_fs_link<<<nblocks(n), kBlock, 0, st>>>(f->B.p, f->occ, f->cell_start, n, f->grid, b2, s.parent, s.counters);
+    if (f->periodic)
+        k_fs_link<<<nblocks(n), kBlock, 0, st>>>(f->B.p, f->occ, f->cell_start, n, periodic_grid(f), b2, s.parent, s.counters);
+    else
+        k_fs_link<<<nblocks(n), kBlock, 0, st>>>(f->B.p, f->occ, f->cell_start, n, f->grid, b2, s.parent, s.counters);
     k_fs_flatten<<<nblocks(n), kBlock, 0, st>>>(n, s.parent, f->B.id, s.root, s.minid, s.cnt);
     k_fs_labels<<<nblocks(n), kBlock, 0, st>>>(n, s.root, s.minid, s.cnt, f->B.id, s.lab, s.lcnt, (int32_t *)f->stage,
                                                s.counters + 2);
     NBMI_HIP_CHECK(hipGetLastError());
     return 0;
 }
-// the two passes over `rows` rows whose members (host copy: members[]) are described by rkey / rhead on the device
+// the two passes over `rows` rows whose members (host copy: members[]) are described by rkey / rhead on the device;
+// torus = the rows of bdmi_periodic_flock_catalogue: occupancy and cuts first, then the FsTorus instances of the passes
 int fs_enqueue_rows(bdmi_flock *f, int64_t rows, const int64_t *members, const uint32_t *rank_s, const uint32_t *lab_s,
-                    const uint32_t *rkey, const uint32_t *rhead, bool with_labels) {
+                    const uint32_t *rkey, const uint32_t *rhead, bool with_labels, bool torus = false) {
     FlockStats &s = f->fs;
     hipStream_t st = f->stream;
     std::vector<int32_t> off((size_t)rows + 1);
@@ -2002,21 +2124,34 @@ int fs_enqueue_rows(bdmi_flock *f, int64_t rows, const int64_t *members, const u
     if (int rc = fs_row_buffers(f, rows, chunks)) return rc;
     NBMI_HIP_CHECK(hipMemcpyAsync(s.chunk_off, off.data(), off.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
     NBMI_HIP_CHECK(hipStreamSynchronize(st));  // `off` is pageable host memory that ends with this function
-    k_fs_chunks<1><<<(int)chunks, kBlock, 0, st>>>(f->B.p, f->B.v, rank_s, rkey, rhead, f->n, s.chunk_off, (int)rows, s.rows16,
-                                                  s.part);
-    k_fs_combine<1><<<nblocks(rows), kBlock, 0, st>>>(lab_s, rkey, rhead, f->n, s.chunk_off, (int)rows, s.part, s.rows16,
-                                                     with_labels ? s.row_label : nullptr, with_labels ? s.row_members : nullptr);
-    k_fs_chunks<2><<<(int)chunks, kBlock, 0, st>>>(f->B.p, f->B.v, rank_s, rkey, rhead, f->n, s.chunk_off, (int)rows, s.rows16,
-                                                  s.part);
-    k_fs_combine<2><<<nblocks(rows), kBlock, 0, st>>>(lab_s, rkey, rhead, f->n, s.chunk_off, (int)rows, s.part, s.rows16, nullptr,
-                                                     nullptr);
+    auto passes = [&](const auto &tor) {
+        k_fs_chunks<1><<<(int)chunks, kBlock, 0, st>>>(f->B.p, f->B.v, rank_s, rkey, rhead, f->n, s.chunk_off, (int)rows, s.rows16,
+                                                      s.part, tor);
+        k_fs_combine<1><<<nblocks(rows), kBlock, 0, st>>>(lab_s, rkey, rhead, f->n, s.chunk_off, (int)rows, s.part, s.rows16,
+                                                         with_labels ? s.row_label : nullptr,
+                                                         with_labels ? s.row_members : nullptr, tor);
+        k_fs_chunks<2><<<(int)chunks, kBlock, 0, st>>>(f->B.p, f->B.v, rank_s, rkey, rhead, f->n, s.chunk_off, (int)rows, s.rows16,
+                                                      s.part, tor);
+        k_fs_combine<2><<<nblocks(rows), kBlock, 0, st>>>(lab_s, rkey, rhead, f->n, s.chunk_off, (int)rows, s.part, s.rows16,
+                                                         nullptr, nullptr, tor);
+    };
+    if (torus) {
+        const GridPer g = periodic_grid(f);
+        const int words = fs_occ_words(f);
+        NBMI_HIP_CHECK(hipMemsetAsync(s.occ_mask, 0, (size_t)rows * 3 * words * sizeof(uint32_t), st));
+        k_fs_occupancy<<<(int)chunks, kBlock, 0, st>>>(f->B.p, rank_s, rkey, rhead, f->n, s.chunk_off, (int)rows, g, words,
+                                                      s.occ_mask);
+        k_fs_wrap<<<nblocks(3 * rows), kBlock, 0, st>>>(s.occ_mask, (int)rows, g.dim, words, s.wrap3);
+        passes(FsTorus{g, s.wrap3, s.centre});
+    } else {
+        passes(FsBox{});
+    }
     NBMI_HIP_CHECK(hipGetLastError());
     return 0;
 }
 }  // namespace
 
-int bdmi_flocks(bdmi_flock *f, double link, int32_t *labels, int64_t *n_flocks, int64_t *links, int64_t *evals) {
-    if (int rc = fs_radius_check(f, "bdmi_flocks", "link", link)) return rc;
+static int fs_flocks(bdmi_flock *f, double link, int32_t *labels, int64_t *n_flocks, int64_t *links, int64_t *evals) {
     const int64_t n = f->n;
     unsigned long long h[4] = {0, 0, 0, 0};
     if (n > 0) {
@@ -2031,17 +2166,25 @@ int bdmi_flocks(bdmi_flock *f, double link, int32_t *labels, int64_t *n_flocks, 
     if (n_flocks) *n_flocks = (int64_t)h[2];
     return 0;
 }
+int bdmi_flocks(bdmi_flock *f, double link, int32_t *labels, int64_t *n_flocks, int64_t *links, int64_t *evals) {
+    if (int rc = fs_radius_check(f, "bdmi_flocks", "link", link)) return rc;
+    return fs_flocks(f, link, labels, n_flocks, links, evals);
+}
+int bdmi_periodic_flocks(bdmi_flock *f, double link, int32_t *labels, int64_t *n_flocks, int64_t *links, int64_t *evals) {
+    if (int rc = fs_radius_check(f, "bdmi_periodic_flocks", "link", link, "bdmi_flocks")) return rc;
+    return fs_flocks(f, link, labels, n_flocks, links, evals);
+}
 
-int bdmi_flock_catalogue(bdmi_flock *f, double link, int64_t min_members, int64_t capacity, int32_t *label, int64_t *members,
-                         double *rows16, int64_t *count) {
-    if (int rc = fs_radius_check(f, "bdmi_flock_catalogue", "link", link)) return rc;
+// the catalogue of either kind of handle, behind fs_radius_check; wrap3 (may be null) only on a periodic one
+static int fs_catalogue(bdmi_flock *f, const char *what, double link, int64_t min_members, int64_t capacity, int32_t *label,
+                        int64_t *members, double *rows16, int32_t *wrap3, int64_t *count) {
     if (min_members < 1 || capacity < 0) {
-        nbmi::set_error("bdmi_flock_catalogue: min_members = %lld must be >= 1 and capacity = %lld >= 0", (long long)min_members,
+        nbmi::set_error("%s: min_members = %lld must be >= 1 and capacity = %lld >= 0", what, (long long)min_members,
                         (long long)capacity);
         return -1;
     }
     if (!count || (capacity > 0 && (!label || !members || !rows16))) {
-        nbmi::set_error("bdmi_flock_catalogue: null count, or null output with capacity > 0");
+        nbmi::set_error("%s: null count, or null output with capacity > 0", what);
         return -1;
     }
     const int64_t n = f->n;
@@ -2069,13 +2212,25 @@ int bdmi_flock_catalogue(bdmi_flock *f, double link, int64_t min_members, int64_
         NBMI_HIP_CHECK(hipMemcpyAsync(hkey.data(), s.qkey_s, (size_t)rows * 4, hipMemcpyDeviceToHost, st));
         if (int rc = sync_checked(f)) return rc;
         for (int64_t i = 0; i < rows; i++) members[i] = n - (int64_t)hkey[(size_t)i];
-        if (int rc = fs_enqueue_rows(f, rows, members, s.rank_s, s.lab_s, s.qkey_s, s.qval_s, true)) return rc;
+        if (int rc = fs_enqueue_rows(f, rows, members, s.rank_s, s.lab_s, s.qkey_s, s.qval_s, true, f->periodic)) return rc;
         NBMI_HIP_CHECK(hipMemcpyAsync(rows16, s.rows16, (size_t)rows * 16 * sizeof(double), hipMemcpyDeviceToHost, st));
         NBMI_HIP_CHECK(hipMemcpyAsync(label, s.row_label, (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        if (f->periodic && wrap3)
+            NBMI_HIP_CHECK(hipMemcpyAsync(wrap3, s.wrap3, (size_t)rows * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         if (int rc = sync_checked(f)) return rc;
     }
     *count = (int64_t)total;
     return 0;
+}
+int bdmi_flock_catalogue(bdmi_flock *f, double link, int64_t min_members, int64_t capacity, int32_t *label, int64_t *members,
+                         double *rows16, int64_t *count) {
+    if (int rc = fs_radius_check(f, "bdmi_flock_catalogue", "link", link)) return rc;
+    return fs_catalogue(f, "bdmi_flock_catalogue", link, min_members, capacity, label, members, rows16, nullptr, count);
+}
+int bdmi_periodic_flock_catalogue(bdmi_flock *f, double link, int64_t min_members, int64_t capacity, int32_t *label,
+                                  int64_t *members, double *rows16, int32_t *wrap3, int64_t *count) {
+    if (int rc = fs_radius_check(f, "bdmi_periodic_flock_catalogue", "link", link, "bdmi_flock_catalogue")) return rc;
+    return fs_catalogue(f, "bdmi_periodic_flock_catalogue", link, min_members, capacity, label, members, rows16, wrap3, count);
 }
 
 int bdmi_diagnostics(bdmi_flock *f, double *row16) {
@@ -2095,8 +2250,7 @@ int bdmi_diagnostics(bdmi_flock *f, double *row16) {
     return sync_checked(f);
 }
 
-int bdmi_neighbour_stats(bdmi_flock *f, double radius, int32_t *count, double *nn_d2, int64_t *evals) {
-    if (int rc = fs_radius_check(f, "bdmi_neighbour_stats", "radius", radius)) return rc;
+static int fs_neighbour_stats(bdmi_flock *f, double radius, int32_t *count, double *nn_d2, int64_t *evals) {
     const int64_t n = f->n;
     unsigned long long h = 0;
     if (n > 0) {
@@ -2106,8 +2260,12 @@ int bdmi_neighbour_stats(bdmi_flock *f, double radius, int32_t *count, double *n
         int32_t *d_count = (int32_t *)f->stage;
         double *d_nn = f->stage + n;  // behind the n int32 counts (n doubles hold them twice over)
         NBMI_HIP_CHECK(hipMemsetAsync(f->fs.counters + 3, 0, sizeof(unsigned long long), st));
-        k_fs_neighbours<<<nblocks(n), kBlock, 0, st>>>(f->B.p, f->B.id, f->occ, f->cell_start, n, f->grid, radius * radius, d_count,
-                                                       d_nn, f->fs.counters + 3);
+        if (f->periodic)
+            k_fs_neighbours<<<nblocks(n), kBlock, 0, st>>>(f->B.p, f->B.id, f->occ, f->cell_start, n, periodic_grid(f),
+                                                           radius * radius, d_count, d_nn, f->fs.counters + 3);
+        else
+            k_fs_neighbours<<<nblocks(n), kBlock, 0, st>>>(f->B.p, f->B.id, f->occ, f->cell_start, n, f->grid, radius * radius,
+                                                           d_count, d_nn, f->fs.counters + 3);
         NBMI_HIP_CHECK(hipGetLastError());
         if (count) NBMI_HIP_CHECK(hipMemcpyAsync(count, d_count, (size_t)n * 4, hipMemcpyDeviceToHost, st));
         if (nn_d2) NBMI_HIP_CHECK(hipMemcpyAsync(nn_d2, d_nn, (size_t)n * 8, hipMemcpyDeviceToHost, st));
@@ -2116,6 +2274,14 @@ int bdmi_neighbour_stats(bdmi_flock *f, double radius, int32_t *count, double *n
     }
     if (evals) *evals = (int64_t)h;
     return 0;
+}
+int bdmi_neighbour_stats(bdmi_flock *f, double radius, int32_t *count, double *nn_d2, int64_t *evals) {
+    if (int rc = fs_radius_check(f, "bdmi_neighbour_stats", "radius", radius)) return rc;
+    return fs_neighbour_stats(f, radius, count, nn_d2, evals);
+}
+int bdmi_periodic_neighbour_stats(bdmi_flock *f, double radius, int32_t *count, double *nn_d2, int64_t *evals) {
+    if (int rc = fs_radius_check(f, "bdmi_periodic_neighbour_stats", "radius", radius, "bdmi_neighbour_stats")) return rc;
+    return fs_neighbour_stats(f, radius, count, nn_d2, evals);
 }
 
 }  // extern "C"

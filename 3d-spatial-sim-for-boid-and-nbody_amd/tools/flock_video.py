@@ -9,6 +9,7 @@ machine without GL, display or window system.
     python -m tools.flock_video --boids 2m --frames 600 --diagnostics 10   # + flock.flock.jsonl: flocks, order parameters
     python -m tools.flock_video --boids 500k --neighbours topological --topological-k 7   # the k nearest within sight
     python -m tools.flock_video --boids 100k --periodic --noise 0.5 --noise-seed 3        # no walls, vectorial noise
+    python -m tools.flock_video --boids 100k --periodic --periodic-flocks --diagnostics 10 # + flocks through the faces
 
 Each frame: flock.update(dt, substeps), render_flock, sink.  Output formats and sinks are those of tools.export.
 With --diagnostics K every K-th frame also appends one JSON line (boids.analysis.jsonl_line) to <output stem>.flock.jsonl:
@@ -18,8 +19,10 @@ With --neighbours topological the flock interacts by the topological rule of inc
 neighbours within the perception radius); the clip's metadata and the analysis lines then name the mode.
 With --periodic the domain is the periodic box of include/bdmi.h (no walls, neighbours through the faces), with --noise ETA
 every update adds a unit vector of amplitude ETA * max_force, drawn from (--noise-seed, update, boid), to each boid's
-acceleration; both are set before the warm-up and named in the metadata and the analysis lines.  The flock finder does not
-follow links through the faces yet: with --periodic, --diagnostics writes the whole flock's row only.
+acceleration; both are set before the warm-up and named in the metadata and the analysis lines.  With --periodic alone
+--diagnostics writes the whole flock's row only; --periodic-flocks (which needs --periodic) makes them the full lines of a
+walled run, from the flock finder, catalogue and neighbour counts that follow links through the faces of the box
+(Flock.periodic_flocks and its siblings), each listed flock with "spans": per axis, whether it occupies every slab.
 """
 import argparse
 import json
@@ -77,6 +80,9 @@ def build_parser():
     ap.add_argument("--periodic", action="store_true",
                     help="periodic box instead of walls; --diagnostics then writes the whole-flock row only, without flocks "
                          "or neighbour counts")
+    ap.add_argument("--periodic-flocks", action="store_true",
+                    help="with --periodic: --diagnostics writes the full lines (flocks, sizes, neighbour counts), links "
+                         "followed through the faces, plus per flock whether it spans each axis")
     ap.add_argument("--noise", type=float, default=0.0, metavar="ETA",
                     help="vectorial noise: ETA * max_force times a random unit vector per boid and update (default: 0, off)")
     ap.add_argument("--noise-seed", type=int, default=0, metavar="S", help="seed of the noise (default: 0)")
@@ -134,19 +140,26 @@ def diagnostics_path(output: Path) -> Path:
     return output.with_name((output.stem if output.suffix else output.name) + ".flock.jsonl")
 
 
-def analysis_line(flock, frame, steps, link, min_members, neighbours=None, periodic=False, noise=None) -> str:
+def analysis_line(flock, frame, steps, link, min_members, neighbours=None, periodic=False, noise=None,
+                  periodic_flocks=False) -> str:
     """One line of the analysis file for the flock's current state (four device calls, no state copied out; on a
-    periodic flock one call: the whole flock's row)."""
+    periodic flock one call, the whole flock's row, unless periodic_flocks asks for the four through the faces)."""
     from boids.analysis import global_line, jsonl_line
-    if periodic:
+    if periodic and not periodic_flocks:
         return global_line(frame, steps, flock.diagnostics(), neighbours=neighbours, periodic=True, noise=noise)
-    fl = flock.flocks(link)
-    cat = flock.flock_catalogue(link, min_members=min_members, capacity=LARGEST_FLOCKS)
-    nb = flock.neighbour_stats(link)
+    if periodic:
+        fl = flock.periodic_flocks(link)
+        cat = flock.periodic_flock_catalogue(link, min_members=min_members, capacity=LARGEST_FLOCKS)
+        nb = flock.periodic_neighbour_stats(link)
+    else:
+        fl = flock.flocks(link)
+        cat = flock.flock_catalogue(link, min_members=min_members, capacity=LARGEST_FLOCKS)
+        nb = flock.neighbour_stats(link)
     count = np.asarray(nb["count"])
     return jsonl_line(frame, steps, flock.diagnostics(), fl["n_flocks"], fl["links"],
                       float(count.mean()) if count.size else 0.0, cat["rows"], flock_labels=cat["label"],
-                      link=link, min_members=min_members, qualifying=cat["count"], neighbours=neighbours, noise=noise)
+                      link=link, min_members=min_members, qualifying=cat["count"], neighbours=neighbours, noise=noise,
+                      flock_spans=cat["spans"] if periodic else None, periodic=periodic)
 
 
 def run(args, make_flock=None, make_renderer=None, say=print) -> dict:
@@ -164,6 +177,9 @@ def run(args, make_flock=None, make_renderer=None, say=print) -> dict:
         raise ValueError("--topological-k must be in 1..16")
     neighbours = {"mode": "topological", "k": topo_k} if topological else None
     periodic = bool(getattr(args, "periodic", False))
+    periodic_flocks = bool(getattr(args, "periodic_flocks", False))
+    if periodic_flocks and not periodic:
+        raise ValueError("--periodic-flocks needs --periodic (a walled run writes the full lines anyway)")
     eta = float(getattr(args, "noise", 0.0) or 0.0)
     if not (0.0 <= eta < float("inf")):
         raise ValueError("--noise must be finite and not negative")
@@ -216,7 +232,7 @@ def run(args, make_flock=None, make_renderer=None, say=print) -> dict:
                 ta = time.perf_counter()
                 steps = args.warmup + (i + 1) * args.substeps
                 diag_file.write(analysis_line(flock, i, steps, getattr(args, "link", None), min_members,
-                                              neighbours, periodic, noise) + "\n")
+                                              neighbours, periodic, noise, periodic_flocks) + "\n")
                 diag_lines += 1
                 t_analysis += time.perf_counter() - ta
         ok = True
@@ -241,6 +257,8 @@ def run(args, make_flock=None, make_renderer=None, say=print) -> dict:
             meta["flock"]["neighbours"] = neighbours
         if periodic:
             meta["flock"]["periodic"] = True
+        if periodic_flocks:
+            meta["flock"]["periodic_flocks"] = True
         if noise:
             meta["flock"]["noise"] = noise
         if every:

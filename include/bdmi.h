@@ -50,8 +50,8 @@ int bdmi_get_cell_indices(bdmi_flock *f, int32_t *cell_indices);
  * caller-side pre-fill of Flock.update (forces 0, avg_colors = colors; flock.py:633-636). */
 int bdmi_get_forces(bdmi_flock *f, double *sep, double *ali, double *coh, double *avg_colors);
 /* grid facts: dim, num_cells, non-empty cells of the last built grid.  The last built grid is that of the last
- * bdmi_step, or of the current positions after bdmi_get_forces, one of the four flock-analysis calls or
- * bdmi_topological_neighbours below. */
+ * bdmi_step, or of the current positions after bdmi_get_forces, one of the four flock-analysis calls (or their three
+ * periodic counterparts) or bdmi_topological_neighbours below. */
 int bdmi_grid_info(bdmi_flock *f, int32_t *grid_dim, int64_t *num_cells, int64_t *occupied);
 /* device ms accumulated per phase [cells+sort, reorder+table, sweep+physics], steps counted */
 int bdmi_enable_timers(bdmi_flock *f, int enable);
@@ -202,8 +202,9 @@ int bdmi_topological_neighbours(bdmi_flock *f, int k, int32_t *ids /* (N,k) */, 
  *     bdmi_diagnostics: polarisation, mean speed and vbar do not depend on positions; c, milling, lo and hi are computed
  *     from the coordinates in the box as they stand (a flock that straddles a face has its centre in between).
  *   Refused on periodic handles with NBMI_ERR_ARG ("<call>: ... periodic ..."), before anything is launched and with the
- *     outputs untouched: bdmi_flocks, bdmi_flock_catalogue, bdmi_neighbour_stats.  (A follow-up: linking through the
- *     faces is easy, a flock's centre on a torus is not.)  There is no periodic slab handle.
+ *     outputs untouched: bdmi_flocks, bdmi_flock_catalogue, bdmi_neighbour_stats.  Their counterparts through the faces
+ *     are bdmi_periodic_flocks, bdmi_periodic_flock_catalogue and bdmi_periodic_neighbour_stats ("Flock analysis on
+ *     periodic handles" below).  There is no periodic slab handle.
  *
  * NOISE, on walled and periodic handles, not on slab handles.
  *   bdmi_set_noise(f, eta, seed, step): eta must be finite and >= 0.  step >= 0 sets the handle's noise step, step == -1
@@ -230,6 +231,60 @@ int bdmi_get_box(bdmi_flock *f, int *periodic, double *length, double *cell_size
 int bdmi_set_noise(bdmi_flock *f, double eta, uint64_t seed, int64_t step);
 int bdmi_get_noise(bdmi_flock *f, double *eta, uint64_t *seed, int64_t *step); /* each may be NULL */
 int bdmi_noise_vectors(bdmi_flock *f, int64_t step, double *out_xyz /* (N,3) */);
+
+/* ---- flock analysis on periodic handles: flocks, catalogue and neighbour counts through the faces
+ * bdmi_flocks, bdmi_flock_catalogue and bdmi_neighbour_stats on the periodic box of bdmi_create_periodic, under names of
+ * their own: the walled calls keep refusing a periodic handle, and these three refuse a walled one.  This text is the
+ * specification; the kernels (csrc/bdmi.hip) and the tests' NumPy restatement (tests/torus_ref.py) both follow it.
+ * Arithmetic is float64 in the association written, without FMA; sqrt and divide are correctly rounded.  B, L, dim,
+ * cell_size and the cell coordinate are those of "Periodic handles" above.
+ *
+ * DISTANCE.  Per axis dx = x_j - x_i; if dx > B then dx = dx - L, else if dx < -B then dx = dx + L.  Equality does not
+ *   shift.  d2(i, j) = (dx dx + dy dy) + dz dz.  The rule acts on the DIFFERENCE, not on the neighbour's position as the
+ *   sweep's image does: x_i - x_j is exactly -(x_j - x_i) and both shifts are mirror images, so d2(i, j) and d2(j, i) are
+ *   the same bits and the link relation is symmetric whichever boid of a pair evaluates it.  The sweep's image-of-position
+ *   rule does not guarantee that: for a pair through a face this d2 may differ in the last bit from the d2 of
+ *   bdmi_topological_neighbours.
+ * LINKS.  As in the flock analysis above: b2 = link * link (one host product), boids i != j are linked iff d2(i, j) <= b2,
+ *   equality links, a coincident pair is linked.  `link` (and `radius`) must be finite, > 0 and <= perception_radius.  The
+ *   candidates of a boid are the 27 cells (cx+a, cy+b, cz+c) mod dim; with dim >= 3 and cell_size >= perception_radius
+ *   they are distinct and cover the link, so every pair is evaluated exactly once.
+ * bdmi_periodic_flocks: labels, *n_flocks, *links and *evals mean what they mean in bdmi_flocks.
+ * bdmi_periodic_neighbour_stats: as bdmi_neighbour_stats with this d2; the sum of count is 2 * links at link == radius.
+ * bdmi_periodic_flock_catalogue: selection, order, *count, capacity and the member order as in bdmi_flock_catalogue.  The
+ *   ROW of a flock on the torus:
+ *     cc_a(j) = the cell coordinate of member j on axis a (the decomposition of bdmi_get_cell_indices: index = cc_x +
+ *       cc_y dim + cc_z dim^2);  O_a = the set of cell coordinates the flock's members occupy on axis a.
+ *     The flock SPANS axis a if |O_a| == dim: wrap_a = -1 and the coordinates on that axis are taken as they stand,
+ *       y_ja = x_ja.  Spanning is necessary for a flock that winds around the box, not sufficient: a C-shaped flock that
+ *       has a member in every slab without closing also spans.
+ *     Otherwise wrap_a = s_a, the smallest c in O_a whose cyclic predecessor (c - 1 + dim) mod dim is not in O_a (one
+ *       exists), and y_ja = x_ja + L if cc_a(j) < s_a, else x_ja: one float64 add.  With link <= cell_size no link crosses
+ *       an empty slab, so the occupied slabs of a connected flock form one cyclic arc and this cut is the geometrically
+ *       right one; the rule is the definition whatever the geometry.
+ *     The 16 doubles have the layout and formulas of the row above with y in the place of p:  Sp = sum y_j, c~ = Sp / m;
+ *       the row's c_a = c~_a - L if c~_a > B, else c~_a;  lo / hi = the exact minimum / maximum of y (hi may exceed B;
+ *       hi - lo is the flock's extent);  the second pass uses r_j = y_j - c~, the unwrapped centre before it is brought
+ *       back;  vbar, polarisation and mean_speed do not see positions and are unchanged.
+ *     Member order, the chunks of 4096, the fold inside a chunk and the chunk order are exactly those of the row above, on
+ *       the periodic grid's cell order: two calls on an unchanged state give the same bits.
+ *   wrap3 (capacity, 3) int32, may be NULL: wrap_a of every row copied out.
+ * Unchanged from the walled calls: N == 0 (success, zeros, *count = 0) and N == 1 (one flock of one, whose wrap_a is its cell
+ *   coordinate); "changes nothing a later step reads"; the sort's sticky error; bdmi_grid_info
+ *   afterwards describes the grid of the current positions.
+ * Refused with NBMI_ERR_ARG (message "<call>: ..."), before anything is launched and with the outputs untouched: a walled
+ *   handle (the message names the walled call to use), a slab handle, a null handle, a link or radius that is not finite,
+ *   <= 0 or above the perception radius (the message names both numbers), min_members < 1, capacity < 0, a null count, or
+ *   a null label / members / rows16 with capacity > 0.
+ * Scratch on top of the flock analysis': per catalogue row copied out 12 * ceil(dim / 32) bytes of occupancy words, 24 bytes
+ *   of unwrapped centre and 12 bytes of wrap3. */
+int bdmi_periodic_flocks(bdmi_flock *f, double link, int32_t *labels /* (N,), may be NULL */, int64_t *n_flocks,
+                         int64_t *links, int64_t *evals); /* each may be NULL */
+int bdmi_periodic_flock_catalogue(bdmi_flock *f, double link, int64_t min_members, int64_t capacity, int32_t *label,
+                                  int64_t *members, double *rows16, int32_t *wrap3 /* (capacity,3), may be NULL */,
+                                  int64_t *count);
+int bdmi_periodic_neighbour_stats(bdmi_flock *f, double radius, int32_t *count /* (N,) */, double *nn_d2 /* (N,) */,
+                                  int64_t *evals); /* each output may be NULL */
 
 /* ---- multi-GPU: x-slabs with a one-cell halo -----------------------------------------
  * A rank owns the boids with x_lo <= x < x_hi (a whole number of cell planes, at least two cells wide); the

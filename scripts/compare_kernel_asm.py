@@ -6,8 +6,8 @@ sweep against the commit before the periodic box.)  Needs hipcc and c++filt, no 
 
 Each tree's bdmi.hip is compiled to device assembly for gfx950 with the Makefile's flags.  Kernels are matched by their
 demangled name up to the argument list, with the template arguments this tree added for the walled, noise-free instances
-(", GridP, FlockP" / ", GridP") dropped, so k_flock<true> of the old tree meets k_flock<true, GridP, FlockP> of the new
-one.  Compared: the instruction lines, with symbol names and block labels normalised, and the register, LDS and scratch
+(", GridP, FlockP" / ", GridP" / ", FsBox" / "<GridP>") dropped, so k_flock<true> of the old tree meets
+k_flock<true, GridP, FlockP> of the new one, k_fs_link meets k_fs_link<GridP> and k_fs_chunks<1> meets k_fs_chunks<1, FsBox>.  Compared: the instruction lines, with symbol names and block labels normalised, and the register, LDS and scratch
 figures of the kernel descriptor.  Exit status 1 if a kernel present in both trees differs.
 """
 import os
@@ -34,7 +34,10 @@ def kernels(tree, tmp, tag):
     res = {}
     for name, body in zip(names, found.values()):
         short = name.replace(ANON, "").split("(")[0]
-        res[short.replace(", GridP, FlockP>", ">").replace(", GridP>", ">")] = body
+        short = short[5:] if short.startswith("void ") else short  # a template instance carries its return type
+        for added in ((", GridP, FlockP>", ">"), (", GridP>", ">"), (", FsBox>", ">"), ("<GridP>", "")):
+            short = short.replace(*added)
+        res[short] = body
     return res
 
 
