@@ -2,7 +2,9 @@
 neighbour_stats): the named fields of a row of 16 doubles, the size histogram of a catalogue, and the builder of the
 JSON line that tools.flock_video writes with --diagnostics; and the order-against-noise experiment over
 Flock.set_noise / Flock.diagnostics (order_parameter_series, binder_cumulant, noise_sweep), with percolation_summary for
-the catalogue of a periodic flock (Flock.periodic_flock_catalogue).  Nothing here touches the
+the catalogue of a periodic flock (Flock.periodic_flock_catalogue); and the velocity correlation by distance from
+Flock.velocity_correlation (velocity_correlation_function, correlation_length, susceptibility, radial_distribution,
+correlation_line).  Nothing here touches the
 device itself: the helpers work on any object with the Flock methods they name.
 """
 import json
@@ -159,3 +161,80 @@ def noise_sweep(make_flock, etas, steps, discard, every, dt) -> list:
         out.append({"eta": float(eta), "samples": int(phi.size), "polarisation_mean": float(phi.mean()),
                     "polarisation_std": float(phi.std()), "binder": binder_cumulant(phi)})
     return out
+
+
+# ---- velocity correlation by distance (Cavagna et al. 2010; Attanasi et al. 2014), from Flock.velocity_correlation ------
+# `res` is that method's dict: edges (nb + 1), pairs and dot per slot (slot 0 = below the first edge, slot k = the bin
+# (edges[k-1], edges[k]]), qsq = the sum of |q_i|^2, n = the number of boids; q in units of res["quantum"] = 2^-24.
+def _vc_arrays(res):
+    edges = np.asarray(res["edges"], dtype=np.float64)
+    pairs = [int(x) for x in res["pairs"]]
+    dot = [int(x) for x in res["dot"]]
+    if len(edges) < 2 or len(pairs) != len(edges) or len(dot) != len(edges):
+        raise ValueError("a correlation result has nb + 1 edges, pairs and dot, nb >= 1")
+    centres = np.concatenate([[0.5 * edges[0]], 0.5 * (edges[:-1] + edges[1:])])
+    return edges, pairs, dot, centres
+
+
+def velocity_correlation_function(res):
+    """``(r, C)``: the slot centres (slot 0: half the first edge) and the connected correlation C_k = dot_k / (pairs_k
+    2^48), normalised by C0 = qsq / (n 2^48) so that a boid correlates with itself at 1.  NaN where a slot holds no pair,
+    and everywhere when C0 is 0."""
+    _, pairs, dot, centres = _vc_arrays(res)
+    n, qsq = int(res["n"]), int(res["qsq"])
+    c = np.full(len(pairs), np.nan)
+    for k, (p, d) in enumerate(zip(pairs, dot)):
+        if p > 0 and qsq > 0:
+            c[k] = (d * n) / (p * qsq)  # exact integers, one correctly rounded division
+    return centres, c
+
+
+def correlation_length(res):
+    """The first zero crossing of C(r): between the first two successive non-empty slots with C > 0 and then C <= 0,
+    interpolated linearly between their centres.  None without a crossing."""
+    r, c = velocity_correlation_function(res)
+    ok = np.flatnonzero(~np.isnan(c))
+    for a, b in zip(ok[:-1], ok[1:]):
+        if c[a] > 0 >= c[b]:
+            return float(r[a] + (r[b] - r[a]) * c[a] / (c[a] - c[b]))
+    return None
+
+
+def susceptibility(res):
+    """The finite-size susceptibility: ``chi`` = max over k of (2 / n) sum_{j <= k} dot_j / 2^48, the largest cumulated
+    correlation, and ``r`` = the edge edges[k] at which it is reached (the first such k).  n == 0: chi 0, r None."""
+    edges, _, dot, _ = _vc_arrays(res)
+    n = int(res["n"])
+    if n == 0:
+        return {"chi": 0.0, "r": None}
+    best, at, run = None, None, 0
+    for k, d in enumerate(dot):
+        run += d
+        if best is None or run > best:
+            best, at = run, k
+    return {"chi": (2 * best) / (n << 48), "r": float(edges[at])}
+
+
+def radial_distribution(res, box):
+    """``(r, g)`` of a periodic flock: pairs_k over what an ideal gas of n boids in the box would hold, n (n - 1) / 2
+    times the shell's volume over L^3.  ``box`` is Flock.box (or the box length).  Slot 0 is the ball below the first edge
+    (NaN where that edge is 0)."""
+    edges, pairs, _, centres = _vc_arrays(res)
+    length = float(box["length"] if isinstance(box, dict) else box)
+    n = int(res["n"])
+    vol = 4.0 / 3.0 * np.pi * np.diff(np.concatenate([[0.0], edges ** 3]))
+    ideal = 0.5 * n * (n - 1) * vol / length ** 3
+    with np.errstate(divide="ignore", invalid="ignore"):
+        g = np.where(ideal > 0, np.asarray(pairs, dtype=np.float64) / ideal, np.nan)
+    return centres, g
+
+
+def correlation_line(frame, steps, res) -> str:
+    """One line of tools.flock_video's correlation file: {frame, steps, edges, pairs, dot, mean, C, xi, chi}; NaN is
+    written as null, dot as decimal strings where it exceeds 2^53."""
+    _, c = velocity_correlation_function(res)
+    rec = {"frame": int(frame), "steps": int(steps), "edges": [float(e) for e in res["edges"]],
+           "pairs": [int(p) for p in res["pairs"]], "dot": [d if abs(d) < (1 << 53) else str(d) for d in map(int, res["dot"])],
+           "mean": [float(x) for x in res["mean"]], "C": [None if np.isnan(x) else float(x) for x in c],
+           "xi": correlation_length(res), "chi": susceptibility(res)["chi"]}
+    return json.dumps(rec)

@@ -290,6 +290,43 @@ class Flock:
                                                                C.addressof(evals)), "bdmi_periodic_neighbour_stats")
         return dict(count=count, nn_d2=nn, evals=int(evals.value))
 
+    # ---- velocity correlation beyond sight (include/bdmi.h: bdmi_velocity_correlation), walled or periodic ----
+    def heading_moments(self, mean=(0.0, 0.0, 0.0)):
+        """The exact integer moments of the quantised heading fluctuations q_i = rint((u_i - mean) 2^24): dict of
+        ``qsum`` (3 ints) and ``qsq`` (int, the sum of |q_i|^2).  No grid is built."""
+        mean = np.ascontiguousarray(mean, dtype=np.float64).reshape(3)
+        self5 = np.zeros(5, dtype=np.int64)
+        _nat.check_arg(self._lib.bdmi_velocity_correlation(self._h, 0, None, _nat.ptr(mean), None, None, _nat.ptr(self5),
+                                                           None), "bdmi_velocity_correlation")
+        return dict(qsum=[int(x) for x in self5[:3]], qsq=(int(self5[3]) << 32) + int(self5[4]))
+
+    def velocity_correlation(self, edges, mean=None):
+        """The connected correlation of the headings by distance: for the bins ``edges`` (increasing, at most 65 of them,
+        the last one at most 16 cells, and on a periodic flock below half the box) the exact number of pairs per bin and
+        the exact sum of q_i . q_j over them, q the heading fluctuation about ``mean`` in units of 2^-24 (default: the
+        mean heading).  Slot 0 is "below the first edge".  dict of ``edges``, ``pairs`` (int64 (nb+1,)), ``dot`` (Python
+        ints), ``mean``, ``quantum``, ``reach`` (cells), ``evals``, ``qsum``, ``qsq`` and ``n``; boids.analysis turns it into
+        C(r), the correlation length and the susceptibility."""
+        edges = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+        nb = len(edges) - 1
+        if nb < 1:
+            raise ValueError("velocity_correlation: at least two edges (one bin)")
+        n = self.num_boids
+        if mean is None:
+            s = self.heading_moments()["qsum"]
+            mean = [x / (n * 2.0 ** 24) if n else 0.0 for x in s]
+        mean = np.ascontiguousarray(mean, dtype=np.float64).reshape(3)
+        pairs = np.zeros(nb + 1, dtype=np.int64)
+        dot = np.zeros((nb + 1, 2), dtype=np.int64)
+        self5 = np.zeros(5, dtype=np.int64)
+        evals = C.c_int64(0)
+        _nat.check_arg(self._lib.bdmi_velocity_correlation(self._h, nb, _nat.ptr(edges), _nat.ptr(mean), _nat.ptr(pairs),
+                                                           _nat.ptr(dot), _nat.ptr(self5), C.addressof(evals)),
+                       "bdmi_velocity_correlation")
+        return dict(edges=edges, pairs=pairs, dot=[(int(h) << 32) + int(l) for h, l in dot], mean=mean.tolist(),
+                    quantum=2.0 ** -24, reach=int(math.ceil(float(edges[-1]) / self.box["cell_size"])), evals=int(evals.value),
+                    qsum=[int(x) for x in self5[:3]], qsq=(int(self5[3]) << 32) + int(self5[4]), n=n)
+
     # ---- topological interaction (include/bdmi.h: the k nearest neighbours within sight) ---------------------
     def set_neighbour_mode(self, mode, k=7):
         """``"metric"`` (the default: every boid within the perception radius counts, the reference's rule) or

@@ -833,6 +833,10 @@ struct FlockStats {
     int32_t *wrap3 = nullptr;
     double *centre = nullptr;
     int64_t rows_cap = 0, chunks_cap = 0;
+    // bdmi_velocity_correlation, allocated at its first call: the quantised fluctuations in rank order, the call's words
+    int4 *vc_q = nullptr;
+    unsigned long long *vc_acc = nullptr;
+    double vc_e2[65] = {};  // the squared edges of the call in flight (the source of their upload)
 };
 
 // d2(i, j) of the header: three products, two sums, symmetric in its arguments
@@ -945,6 +949,219 @@ __global__ __launch_bounds__(kBlock) void k_fs_neighbours(const double4 *__restr
         nn_d2[i] = least;
     }
     nbmi::wave_add(evals_out, evals, threadIdx.x & 63);
+}
+
+// ---- velocity correlation: bdmi_velocity_correlation (include/bdmi.h) ------------------------
+// The one boids query that looks further than sight: the cells within m of the boid's own, per axis.  for_each_run_wide is
+// for_each_run with that reach, for both grids: the (2m+1)^2 rows (cy+b, cz+c), clamped and skipped where out of a walled
+// grid, wrapped on a periodic one; a row's x cells [cx-m, cx+m] are one clamped segment (walled) or up to two wrapped ones
+// (periodic; 2m+1 <= dim keeps them apart).  A segment is up to 33 cells = up to three words of the occupancy table.  Same
+// shape as run_words / run_bounds: three rows go through each stage together - table words, then the cell_start bounds
+// of the first and last non-empty cell, then one run per segment.  m == 1 emits the runs of for_each_run.
+__device__ __forceinline__ double fs_heading(const double4 &v, double &ux, double &uy, double &uz);  // with the rows, below
+constexpr int kVcMaxBins = 64, kVcMaxReach = 16;
+struct WideWords {
+    uint32_t x0, x1, x2, y0, y1, y2;  // the words' bits and prefixes (scalars: selected by value, never through an index)
+    int lo_bit, hi_bit, nw;           // nw == 0: the segment does not exist
+};
+__device__ __forceinline__ WideWords wide_words(const uint2 *__restrict__ occ, int64_t c_lo, int64_t c_hi, bool ok) {
+    WideWords s;
+    s.lo_bit = (int)(c_lo & 31);
+    s.hi_bit = (int)(c_hi & 31);
+    s.nw = ok ? (int)((c_hi >> 5) - (c_lo >> 5)) + 1 : 0;
+    const int64_t w0 = c_lo >> 5;
+    const uint2 a = s.nw > 0 ? occ[w0] : make_uint2(0u, 0u);
+    const uint2 b = s.nw > 1 ? occ[w0 + 1] : make_uint2(0u, 0u);
+    const uint2 c = s.nw > 2 ? occ[w0 + 2] : make_uint2(0u, 0u);
+    s.x0 = a.x; s.y0 = a.y; s.x1 = b.x; s.y1 = b.y; s.x2 = c.x; s.y2 = c.y;
+    return s;
+}
+__device__ __forceinline__ void wide_bounds(const WideWords &s, const int32_t *__restrict__ cell_start, int32_t &qb, int32_t &qe) {
+    const uint32_t top = ~0u >> (31 - s.hi_bit);
+    const uint32_t b0 = s.x0 & (~0u << s.lo_bit) & (s.nw == 1 ? top : ~0u);
+    const uint32_t b1 = s.x1 & (s.nw == 2 ? top : ~0u);
+    const uint32_t b2 = s.x2 & top;  // (zero words where the segment has fewer than three)
+    qb = 0; qe = 0;
+    if (b0 | b1 | b2) {
+        // first and last non-empty cell of the segment; the words are picked with masks (a conditional between record
+        // members became a load through a computed address, and the records stayed in scratch memory)
+        const uint32_t f0 = b0 ? ~0u : 0u, f1 = ~f0 & (b1 ? ~0u : 0u), f2 = ~f0 & ~f1;
+        const uint32_t l2 = b2 ? ~0u : 0u, l1 = ~l2 & (b1 ? ~0u : 0u), l0 = ~l2 & ~l1;
+        const uint32_t fx = (s.x0 & f0) | (s.x1 & f1) | (s.x2 & f2), fy = (s.y0 & f0) | (s.y1 & f1) | (s.y2 & f2);
+        const uint32_t fb = (b0 & f0) | (b1 & f1) | (b2 & f2);
+        const uint32_t lx = (s.x0 & l0) | (s.x1 & l1) | (s.x2 & l2), ly = (s.y0 & l0) | (s.y1 & l1) | (s.y2 & l2);
+        const uint32_t lb = (b0 & l0) | (b1 & l1) | (b2 & l2);
+        const int first = __ffs(fb) - 1, last = 31 - __clz(lb);
+        qb = cell_start[fy + __popc(fx & ((1u << first) - 1u))];
+        qe = cell_start[ly + __popc(lx & ((1u << last) - 1u)) + 1u];
+    }
+}
+template <class G, class Emit>
+__device__ __forceinline__ void for_each_run_wide(const double4 &p, const G &g, int m, const uint2 *__restrict__ occ,
+                                                  const int32_t *__restrict__ cell_start, Emit emit) {
+    const int dim = g.dim;
+    const int cx = cell_coord(p.x, g), cy = cell_coord(p.y, g), cz = cell_coord(p.z, g);
+    // segment 0 = the cells around cx that are next to each other, segment 1 = those through the x face (periodic only)
+    int lo0 = cx - m, hi0 = cx + m, lo1 = 0, hi1 = 0;
+    bool second = false;
+    if constexpr (G::kPeriodic) {
+        if (lo0 < 0) { lo1 = lo0 + dim; hi1 = dim - 1; lo0 = 0; second = true; }
+        else if (hi0 > dim - 1) { lo1 = 0; hi1 = hi0 - dim; hi0 = dim - 1; second = true; }
+    } else {
+        lo0 = lo0 < 0 ? 0 : lo0;
+        hi0 = hi0 > dim - 1 ? dim - 1 : hi0;
+    }
+    for (int c = -m; c <= m; c++) {
+        int ncz = cz + c;
+        if constexpr (G::kPeriodic) ncz = ncz < 0 ? ncz + dim : (ncz >= dim ? ncz - dim : ncz);
+        else if (ncz < 0 || ncz >= dim) continue;
+        // the words of row cy + b: its segment 0, or its segment 1 where there is one
+        auto words = [&](int b, bool seg1) {
+            int ncy = cy + b;
+            bool rok = b <= m && (!seg1 || second);
+            if constexpr (G::kPeriodic) ncy = ncy < 0 ? ncy + dim : (ncy >= dim ? ncy - dim : ncy);
+            else rok = rok && ncy >= 0 && ncy < dim;
+            const int64_t row = rok ? (int64_t)ncy * dim + (int64_t)ncz * dim * dim : 0;
+            return wide_words(occ, row + (seg1 ? lo1 : lo0), row + (seg1 ? hi1 : hi0), rok);
+        };
+        for (int b0 = -m; b0 <= m; b0 += 3) {
+            // six named records, nothing indexed: what decides whether they stay in registers is wide_bounds' masks
+            const WideWords w0 = words(b0, false), w1 = words(b0, true), w2 = words(b0 + 1, false), w3 = words(b0 + 1, true),
+                            w4 = words(b0 + 2, false), w5 = words(b0 + 2, true);
+            int32_t qb0, qe0, qb1, qe1, qb2, qe2, qb3, qe3, qb4, qe4, qb5, qe5;
+            wide_bounds(w0, cell_start, qb0, qe0);
+            wide_bounds(w1, cell_start, qb1, qe1);
+            wide_bounds(w2, cell_start, qb2, qe2);
+            wide_bounds(w3, cell_start, qb3, qe3);
+            wide_bounds(w4, cell_start, qb4, qe4);
+            wide_bounds(w5, cell_start, qb5, qe5);
+            // one copy of emit's body: the run is picked by compares
+#pragma unroll 1
+            for (int j = 0; j < 6; j += G::kPeriodic ? 1 : 2) {
+                const int32_t rb = j == 0 ? qb0 : j == 1 ? qb1 : j == 2 ? qb2 : j == 3 ? qb3 : j == 4 ? qb4 : qb5;
+                const int32_t re = j == 0 ? qe0 : j == 1 ? qe1 : j == 2 ? qe2 : j == 3 ? qe3 : j == 4 ? qe4 : qe5;
+                if (re > rb) emit(rb, re);
+            }
+        }
+    }
+}
+
+// The device words of one call, zeroed on the stream ahead of the kernels: per slot k {pairs, the sum's low part, its high
+// part}, then {sum qx, sum qy, sum qz, Q low, Q high}, then evals; behind them the squared edges E[0 .. nb] as doubles.
+constexpr int kVcSlots = kVcMaxBins + 1;
+constexpr int kVcSelf = 3 * kVcSlots, kVcEvals = kVcSelf + 5, kVcZeroed = kVcEvals + 1, kVcEdges = 208;
+constexpr int kVcWords = kVcEdges + kVcSlots;
+static_assert(kVcEdges >= kVcZeroed, "the edges lie behind the zeroed words");
+
+// Ranks in a grid-stride loop (cell order when the grid was built: bv / bid are B's; else A's rows as they stand, bv == null):
+// q = rint((u - mean) 2^24) per component, 0 where the difference is not finite, as int4 with the caller id in w; and the
+// five sums of self5.  Q = qx^2 + qy^2 + qz^2 <= 3 * 2^50 per boid goes in as its low 32 bits and the rest, so that for
+// n < 2^31 neither 64-bit sum can wrap.  At most kVcQuantBlocks blocks and five atomics per block: the sums end in five
+// words, and one wave per 64 boids adding to them took 1.9 ms at 2 M boids, nearly all of it the atomics on those addresses.
+constexpr int kVcQuantBlocks = 512;
+__global__ __launch_bounds__(kBlock) void k_vc_quantise(const double4 *__restrict__ bv, const int32_t *__restrict__ bid, Boids a,
+                                                        int64_t n, double mx, double my, double mz, int4 *__restrict__ qv,
+                                                        unsigned long long *acc) {
+    long long sx = 0, sy = 0, sz = 0, q_lo = 0, q_hi = 0;
+    for (int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x; r < n; r += (int64_t)gridDim.x * kBlock) {
+        const double4 v = bv ? bv[r] : make_double4(a.vx[r], a.vy[r], a.vz[r], 0.0);
+        double ux, uy, uz;
+        (void)fs_heading(v, ux, uy, uz);
+        auto quant = [](double d) { return isfinite(d) ? (long long)rint(d * 16777216.0) : 0ll; };
+        const long long qx = quant(ux - mx), qy = quant(uy - my), qz = quant(uz - mz);
+        if (qv) qv[r] = make_int4((int)qx, (int)qy, (int)qz, bv ? bid[r] : a.id[r]);
+        const long long Q = qx * qx + qy * qy + qz * qz;
+        sx += qx; sy += qy; sz += qz;
+        q_lo += Q & 0xffffffffll;
+        q_hi += Q >> 32;
+    }
+    // wave sums by shuffles, the block's four through LDS, then five atomics per block
+    __shared__ long long red[5][kBlock / 64];
+    long long v[5] = {sx, sy, sz, q_lo, q_hi};
+#pragma unroll
+    for (int c = 0; c < 5; c++) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v[c] += __shfl_xor(v[c], o);
+        if ((threadIdx.x & 63) == 0) red[c][threadIdx.x >> 6] = v[c];
+    }
+    __syncthreads();
+    if (threadIdx.x < 5) {
+        long long t = 0;
+#pragma unroll
+        for (int w = 0; w < kBlock / 64; w++) t += red[threadIdx.x][w];
+        if (t != 0ll)
+            (void)__hip_atomic_fetch_add(acc + kVcSelf + threadIdx.x, (unsigned long long)t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// The pair kernel: one lane per rank r takes the candidates q < r of its runs (k_fs_link's rule: every candidate pair is
+// met once, by its higher rank), loads pos[q] and qv[q] together, takes fs_dist, finds the slot by a binary search over the
+// E[k] in LDS and adds 1 and g = q_r . q_q to the block's counters: three 64-bit LDS words per slot {pairs, sum of the low
+// 32 bits of g, sum of g >> 32}.  g = (g >> 32) 2^32 + (g & 0xffffffff) with an arithmetic shift, so the three are plain
+// integer sums.  A lane has fewer than 2^31 candidates: the high word stays below 2^8 * 2^31 * 3 * 2^18 < 2^59; the low word
+// could wrap, so its add returns the old value and a wrap carries 2^32 into the high word.  The flush is one agent-scope
+// integer atomic per non-empty word into acc[], with the same carry; evals goes through one LDS word and one atomic per
+// block.  Integers only: the result does not depend on any order.  No floating-point atomic, no flag, nothing waits on
+// another lane.
+template <class G>
+__global__ __launch_bounds__(kBlock) void k_vc_pairs(const double4 *__restrict__ pos, const int4 *__restrict__ qv,
+                                                     const uint2 *__restrict__ occ, const int32_t *__restrict__ cell_start,
+                                                     int64_t n, G g, int m, int nb, unsigned long long *acc, int xcd_contiguous) {
+    __shared__ double sE[kVcSlots];
+    __shared__ unsigned long long s_cnt[kVcSlots], s_lo[kVcSlots], s_hi[kVcSlots], s_evals;
+    if (threadIdx.x == 0) s_evals = 0ull;
+    if (threadIdx.x <= nb) {
+        sE[threadIdx.x] = reinterpret_cast<const double *>(acc + kVcEdges)[threadIdx.x];
+        s_cnt[threadIdx.x] = 0ull; s_lo[threadIdx.x] = 0ull; s_hi[threadIdx.x] = 0ull;
+    }
+    __syncthreads();
+    const int64_t r = logical_block((int)blockIdx.x, (int)gridDim.x, xcd_contiguous) * kBlock + threadIdx.x;
+    long long evals = 0;
+    if (r < n) {
+        const double4 pi = pos[r];
+        const int4 qi = qv[r];
+        const double e_max = sE[nb];
+        for_each_run_wide(pi, g, m, occ, cell_start, [&](int32_t qb, int32_t qe) {
+            const int32_t e = qe < (int32_t)r ? qe : (int32_t)r;
+            for (int32_t q = qb; q < e; q++) {
+                const double4 pj = pos[q];
+                const int4 qj = qv[q];
+                const double d2 = fs_dist(pi, pj, g);
+                evals++;
+                if (d2 <= e_max) {  // (a NaN d2 is in no slot)
+                    int lo = 0, hi = nb;
+                    while (lo < hi) {  // the first k with d2 <= E[k]
+                        const int mid = (lo + hi) >> 1;
+                        if (sE[mid] < d2) lo = mid + 1; else hi = mid;
+                    }
+                    const long long gg = (long long)qi.x * qj.x + (long long)qi.y * qj.y + (long long)qi.z * qj.z;
+                    const unsigned long long low = (unsigned long long)gg & 0xffffffffull;
+                    long long high = gg >> 32;
+                    atomicAdd(&s_cnt[lo], 1ull);
+                    const unsigned long long old = atomicAdd(&s_lo[lo], low);
+                    if (old + low < old) high += 1ll << 32;
+                    atomicAdd(&s_hi[lo], (unsigned long long)high);
+                }
+            }
+        });
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) evals += __shfl_xor(evals, o);
+    if ((threadIdx.x & 63) == 0 && evals) atomicAdd(&s_evals, (unsigned long long)evals);
+    __syncthreads();
+    if (threadIdx.x == kBlock - 1 && s_evals)
+        (void)__hip_atomic_fetch_add(acc + kVcEvals, s_evals, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (threadIdx.x <= nb) {
+        unsigned long long *out = acc + 3 * threadIdx.x;
+        const unsigned long long c = s_cnt[threadIdx.x], low = s_lo[threadIdx.x];
+        unsigned long long high = s_hi[threadIdx.x];
+        if (c) (void)__hip_atomic_fetch_add(out, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (low) {
+            const unsigned long long old = __hip_atomic_fetch_add(out + 1, low, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (old + low < old) high += 1ull << 32;
+        }
+        if (high) (void)__hip_atomic_fetch_add(out + 2, high, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
 }
 
 // the heads (first member) of the flocks with at least min_members members, in label order
@@ -2282,6 +2499,88 @@ int bdmi_neighbour_stats(bdmi_flock *f, double radius, int32_t *count, double *n
 int bdmi_periodic_neighbour_stats(bdmi_flock *f, double radius, int32_t *count, double *nn_d2, int64_t *evals) {
     if (int rc = fs_radius_check(f, "bdmi_periodic_neighbour_stats", "radius", radius, "bdmi_neighbour_stats")) return rc;
     return fs_neighbour_stats(f, radius, count, nn_d2, evals);
+}
+
+// C(r) beyond sight (include/bdmi.h): checks first, then quantise (+ grid and pair kernel when there are bins), then the
+// three words per slot normalised into (hi, lo)
+int bdmi_velocity_correlation(bdmi_flock *f, int nb, const double *edges, const double *mean3, int64_t *pairs, int64_t *dot,
+                              int64_t *self5, int64_t *evals) {
+    const char *what = "bdmi_velocity_correlation";
+    if (!f) { nbmi::set_error("%s: null bdmi_flock handle", what); return -1; }
+    if (int rc = whole_flock_check(f, what)) return rc;
+    if (nb < 0 || nb > kVcMaxBins) { nbmi::set_error("%s: nb = %d must be in 0..%d", what, nb, kVcMaxBins); return -1; }
+    if (nb > 0 && !edges) { nbmi::set_error("%s: null edges with nb = %d", what, nb); return -1; }
+    if (!mean3) { nbmi::set_error("%s: null mean3", what); return -1; }
+    for (int c = 0; c < 3; c++)
+        if (!(fabs(mean3[c]) <= 1.0)) {  // NaN and +-inf fail too
+            nbmi::set_error("%s: mean3[%d] = %g must be finite and at most 1 in magnitude", what, c, mean3[c]);
+            return -1;
+        }
+    double e2[kVcSlots];
+    int m = 0;
+    if (nb > 0) {
+        for (int k = 0; k <= nb; k++) {
+            const double e = edges[k];
+            e2[k] = e * e;
+            const bool ok = e >= 0 && e2[k] < INFINITY && (k == 0 || (e > edges[k - 1] && e2[k] > e2[k - 1]));
+            if (!ok) {
+                nbmi::set_error("%s: edges[%d] = %g: the edges must be finite, >= 0 and strictly increasing, and so must their "
+                                "squares", what, k, e);
+                return -1;
+            }
+        }
+        const double cell = f->grid.cell_size;
+        const int dim = f->grid.dim;
+        const int m_max = f->periodic && (dim - 1) / 2 < kVcMaxReach ? (dim - 1) / 2 : kVcMaxReach;
+        const double mf = ceil(edges[nb] / cell);
+        if (!(mf >= 1) || mf > m_max) {
+            nbmi::set_error("%s: reach m = ceil(%g / %g) = %.0f cells must be in 1..%d%s (dim = %d); the largest admissible last "
+                            "edge is %g", what, edges[nb], cell, mf, m_max,
+                            f->periodic ? " (at most 16, and 2 m + 1 <= dim on a periodic handle)" : "", dim, m_max * cell);
+            return -1;
+        }
+        m = (int)mf;
+    }
+    const int64_t n = f->n;
+    unsigned long long h[kVcZeroed];
+    memset(h, 0, sizeof(h));
+    if (n > 0) {
+        FlockStats &s = f->fs;
+        if (!s.vc_acc && (dev_alloc(f, &s.vc_q, (size_t)n) || dev_alloc(f, &s.vc_acc, (size_t)kVcWords))) return -2;
+        hipStream_t st = f->stream;
+        if (nb > 0) {
+            if (int rc = enqueue_grid(f, false)) return rc;
+            memcpy(s.vc_e2, e2, (size_t)(nb + 1) * sizeof(double));
+            NBMI_HIP_CHECK(hipMemcpyAsync(s.vc_acc + kVcEdges, s.vc_e2, (size_t)(nb + 1) * sizeof(double), hipMemcpyHostToDevice, st));
+        }
+        NBMI_HIP_CHECK(hipMemsetAsync(s.vc_acc, 0, kVcZeroed * sizeof(unsigned long long), st));
+        k_vc_quantise<<<nblocks(n) < kVcQuantBlocks ? nblocks(n) : kVcQuantBlocks, kBlock, 0, st>>>(nb > 0 ? f->B.v : nullptr, f->B.id, f->A, n, mean3[0], mean3[1], mean3[2],
+                                                    nb > 0 ? s.vc_q : nullptr, s.vc_acc);
+        if (nb > 0 && f->periodic)
+            k_vc_pairs<<<nblocks(n), kBlock, 0, st>>>(f->B.p, s.vc_q, f->occ, f->cell_start, n, periodic_grid(f), m, nb, s.vc_acc,
+                                                      f->xcd_contiguous);
+        else if (nb > 0)
+            k_vc_pairs<<<nblocks(n), kBlock, 0, st>>>(f->B.p, s.vc_q, f->occ, f->cell_start, n, f->grid, m, nb, s.vc_acc,
+                                                      f->xcd_contiguous);
+        NBMI_HIP_CHECK(hipGetLastError());
+        NBMI_HIP_CHECK(hipMemcpyAsync(h, s.vc_acc, sizeof(h), hipMemcpyDeviceToHost, st));
+        if (int rc = sync_checked(f)) return rc;
+    }
+    // S = high 2^32 + low with low < 2^64: the unique (hi, lo) with 0 <= lo < 2^32
+    auto norm = [](unsigned long long high, unsigned long long low, int64_t *out) {
+        out[0] = (int64_t)high + (int64_t)(low >> 32);
+        out[1] = (int64_t)(low & 0xffffffffull);
+    };
+    for (int k = 0; k <= nb && nb > 0; k++) {
+        if (pairs) pairs[k] = (int64_t)h[3 * k];
+        if (dot) norm(h[3 * k + 2], h[3 * k + 1], dot + 2 * k);
+    }
+    if (self5) {
+        for (int c = 0; c < 3; c++) self5[c] = (int64_t)h[kVcSelf + c];
+        norm(h[kVcSelf + 4], h[kVcSelf + 3], self5 + 3);
+    }
+    if (evals) *evals = (int64_t)h[kVcEvals];
+    return 0;
 }
 
 }  // extern "C"

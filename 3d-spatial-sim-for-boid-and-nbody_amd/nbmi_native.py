@@ -136,6 +136,7 @@ PROTOTYPES = {
     "bdmi_periodic_flocks": (C.c_int, [_vp, _dbl, _vp, _vp, _vp, _vp]),
     "bdmi_periodic_flock_catalogue": (C.c_int, [_vp, _dbl, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "bdmi_periodic_neighbour_stats": (C.c_int, [_vp, _dbl, _vp, _vp, _vp]),
+    "bdmi_velocity_correlation": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bdmi_visible_vertices": (C.c_int, [_vp, _vp, _dbl, _dbl, _dbl, _dbl, _dbl, _vp, _vp, _i64, _vp]),
     "bdmi_render_triangles": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp]),
     "bdmi_render_flock": (C.c_int, [_vp, _vp, _vp, _dbl, _dbl, _dbl, _dbl, _dbl, _vp, _vp, _vp]),

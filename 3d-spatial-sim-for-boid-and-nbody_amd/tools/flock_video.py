@@ -10,6 +10,7 @@ machine without GL, display or window system.
     python -m tools.flock_video --boids 500k --neighbours topological --topological-k 7   # the k nearest within sight
     python -m tools.flock_video --boids 100k --periodic --noise 0.5 --noise-seed 3        # no walls, vectorial noise
     python -m tools.flock_video --boids 100k --periodic --periodic-flocks --diagnostics 10 # + flocks through the faces
+    python -m tools.flock_video --boids 100k --periodic --noise 2 --correlations 10        # + flock.correlation.jsonl: C(r)
 
 Each frame: flock.update(dt, substeps), render_flock, sink.  Output formats and sinks are those of tools.export.
 With --diagnostics K every K-th frame also appends one JSON line (boids.analysis.jsonl_line) to <output stem>.flock.jsonl:
@@ -23,6 +24,11 @@ acceleration; both are set before the warm-up and named in the metadata and the 
 --diagnostics writes the whole flock's row only; --periodic-flocks (which needs --periodic) makes them the full lines of a
 walled run, from the flock finder, catalogue and neighbour counts that follow links through the faces of the box
 (Flock.periodic_flocks and its siblings), each listed flock with "spans": per axis, whether it occupies every slab.
+With --correlations K every K-th frame appends one JSON line (boids.analysis.correlation_line) to
+<output stem>.correlation.jsonl, a file of its own: the exact pair counts and heading-fluctuation sums per distance bin of
+Flock.velocity_correlation, the correlation function C, its first zero crossing xi and the susceptibility chi.
+--correlation-edges lists the bin edges; auto is 17 linear edges from 0 to 4 cell sizes (a convention, not a measured
+optimum).  It works with --periodic, --noise and both neighbour modes; the metadata names the file beside "diagnostics".
 """
 import argparse
 import json
@@ -86,6 +92,12 @@ def build_parser():
     ap.add_argument("--noise", type=float, default=0.0, metavar="ETA",
                     help="vectorial noise: ETA * max_force times a random unit vector per boid and update (default: 0, off)")
     ap.add_argument("--noise-seed", type=int, default=0, metavar="S", help="seed of the noise (default: 0)")
+    ap.add_argument("--correlations", type=int, default=0, metavar="K",
+                    help="every K-th frame append the velocity correlation C(r) of the headings, its correlation length "
+                         "and susceptibility to <output stem>.correlation.jsonl (default: 0 = off)")
+    ap.add_argument("--correlation-edges", type=str, default="auto", metavar="auto|E0,E1,...",
+                    help="bin edges of --correlations: increasing distances, or auto = 17 linear edges from 0 to 4 cell "
+                         "sizes (default: auto)")
     return ap
 
 
@@ -140,6 +152,26 @@ def diagnostics_path(output: Path) -> Path:
     return output.with_name((output.stem if output.suffix else output.name) + ".flock.jsonl")
 
 
+def correlation_path(output: Path) -> Path:
+    """<output stem>.correlation.jsonl next to the output (a frame directory keeps its whole name)."""
+    return output.with_name((output.stem if output.suffix else output.name) + ".correlation.jsonl")
+
+
+def correlation_edges(text, cell_size=None) -> np.ndarray:
+    """The edges of --correlation-edges: "auto" = 17 linear edges from 0 to 4 cell sizes (a convention, not a measured
+    optimum; needs cell_size, None returns None), or 2 to 65 comma-separated distances, finite, not negative and strictly
+    increasing."""
+    if str(text).strip().lower() == "auto":
+        return None if cell_size is None else np.linspace(0.0, 4.0 * float(cell_size), 17)
+    try:
+        edges = np.array([float(x) for x in str(text).split(",")], dtype=np.float64)
+    except ValueError:
+        raise ValueError(f"--correlation-edges: {text!r} is neither auto nor a comma-separated list of numbers") from None
+    if not 2 <= len(edges) <= 65 or not np.all(np.isfinite(edges)) or edges[0] < 0 or not np.all(np.diff(edges) > 0):
+        raise ValueError("--correlation-edges: 2 to 65 finite distances, the first not negative, strictly increasing")
+    return edges
+
+
 def analysis_line(flock, frame, steps, link, min_members, neighbours=None, periodic=False, noise=None,
                   periodic_flocks=False) -> str:
     """One line of the analysis file for the flock's current state (four device calls, no state copied out; on a
@@ -184,6 +216,11 @@ def run(args, make_flock=None, make_renderer=None, say=print) -> dict:
     if not (0.0 <= eta < float("inf")):
         raise ValueError("--noise must be finite and not negative")
     noise = {"eta": eta, "seed": int(getattr(args, "noise_seed", 0))} if eta > 0 else None
+    corr_every = int(getattr(args, "correlations", 0) or 0)
+    if corr_every < 0:
+        raise ValueError("--correlations must not be negative")
+    corr_text = getattr(args, "correlation_edges", "auto") or "auto"
+    corr_edges = correlation_edges(corr_text) if corr_every else None  # a bad list is refused before anything is made
     if make_flock is None:
         from boids import Flock
         make_flock = lambda n, seed, device, **kw: Flock(n, seed=seed, device=device, **kw)  # noqa: E731
@@ -203,6 +240,10 @@ def run(args, make_flock=None, make_renderer=None, say=print) -> dict:
     diag_path = diagnostics_path(output) if every else None
     diag_file = None
     diag_lines = 0
+    corr_path = correlation_path(output) if corr_every else None
+    corr_file = None
+    corr_lines = 0
+    t_corr = 0.0
     ok = False
     t_step = t_render = t_write = t_analysis = 0.0
     t0 = time.perf_counter()
@@ -217,6 +258,11 @@ def run(args, make_flock=None, make_renderer=None, say=print) -> dict:
         if every:
             diag_path.parent.mkdir(parents=True, exist_ok=True)
             diag_file = open(diag_path, "w")
+        if corr_every:
+            if corr_edges is None:
+                corr_edges = correlation_edges(corr_text, flock.box["cell_size"])
+            corr_path.parent.mkdir(parents=True, exist_ok=True)
+            corr_file = open(corr_path, "w")
         for i in range(args.frames):
             ts = time.perf_counter()
             flock.update(dt, args.substeps)
@@ -235,10 +281,19 @@ def run(args, make_flock=None, make_renderer=None, say=print) -> dict:
                                               neighbours, periodic, noise, periodic_flocks) + "\n")
                 diag_lines += 1
                 t_analysis += time.perf_counter() - ta
+            if corr_every and i % corr_every == 0:
+                from boids.analysis import correlation_line
+                ta = time.perf_counter()
+                corr_file.write(correlation_line(i, args.warmup + (i + 1) * args.substeps,
+                                                 flock.velocity_correlation(corr_edges)) + "\n")
+                corr_lines += 1
+                t_corr += time.perf_counter() - ta
         ok = True
     finally:
         if diag_file is not None:
             diag_file.close()
+        if corr_file is not None:
+            corr_file.close()
         ok = sink.close(ok) and ok
         renderer.close()
         flock.close()
@@ -247,6 +302,8 @@ def run(args, make_flock=None, make_renderer=None, say=print) -> dict:
                "write_s": t_write, "fps": args.frames / wall if wall > 0 else 0.0, "output": str(output), "format": fmt}
     if every:
         timings.update({"diagnostics": str(diag_path), "diagnostics_lines": diag_lines, "analysis_s": t_analysis})
+    if corr_every:
+        timings.update({"correlations": str(corr_path), "correlation_lines": corr_lines, "correlation_s": t_corr})
     if ok and fmt == "raw":  # the sink's sidecar, plus what produced the frames
         meta = json.loads(sink.meta_path.read_text())
         meta["flock"] = {"boids": args.boids, "seed": args.seed, "dt": dt, "substeps": args.substeps,
@@ -264,11 +321,16 @@ def run(args, make_flock=None, make_renderer=None, say=print) -> dict:
         if every:
             meta["diagnostics"] = {"file": diag_path.name, "every": every, "link": getattr(args, "link", None),
                                    "min_members": min_members, "lines": diag_lines}
+        if corr_every:
+            meta["correlations"] = {"file": corr_path.name, "every": corr_every, "edges": [float(e) for e in corr_edges],
+                                    "lines": corr_lines}
         sink.meta_path.write_text(json.dumps(meta, indent=2))
     say(f"[Flock] {'done' if ok else 'FAILED'}: {output} ({args.frames} frames in {format_time(wall)}, "
         f"{timings['fps']:.1f} fps; step {t_step:.2f}s, render {t_render:.2f}s, write {t_write:.2f}s)")
     if every:
         say(f"[Flock] flock analysis: {diag_lines} lines in {diag_path} ({t_analysis:.2f}s)")
+    if corr_every:
+        say(f"[Flock] velocity correlation: {corr_lines} lines in {corr_path} ({t_corr:.2f}s)")
     return timings
 
 

@@ -51,7 +51,7 @@ int bdmi_get_cell_indices(bdmi_flock *f, int32_t *cell_indices);
 int bdmi_get_forces(bdmi_flock *f, double *sep, double *ali, double *coh, double *avg_colors);
 /* grid facts: dim, num_cells, non-empty cells of the last built grid.  The last built grid is that of the last
  * bdmi_step, or of the current positions after bdmi_get_forces, one of the four flock-analysis calls (or their three
- * periodic counterparts) or bdmi_topological_neighbours below. */
+ * periodic counterparts), bdmi_topological_neighbours or bdmi_velocity_correlation (with nb > 0) below. */
 int bdmi_grid_info(bdmi_flock *f, int32_t *grid_dim, int64_t *num_cells, int64_t *occupied);
 /* device ms accumulated per phase [cells+sort, reorder+table, sweep+physics], steps counted */
 int bdmi_enable_timers(bdmi_flock *f, int enable);
@@ -285,6 +285,58 @@ int bdmi_periodic_flock_catalogue(bdmi_flock *f, double link, int64_t min_member
                                   int64_t *count);
 int bdmi_periodic_neighbour_stats(bdmi_flock *f, double radius, int32_t *count /* (N,) */, double *nn_d2 /* (N,) */,
                                   int64_t *evals); /* each output may be NULL */
+
+/* ---- velocity correlation C(r) beyond the sight radius ------------------------------------------
+ * The connected correlation of the heading fluctuations as a function of distance (Cavagna et al. 2010; the finite-size
+ * susceptibility of Attanasi et al. 2014 comes from the same sums), and with the same counts the radial distribution.  The
+ * boids counterpart of nbmi_pair_counts, and the one boids call that looks further than one cell.  It works on walled and
+ * periodic handles under one name.  This text is the specification; the kernels (csrc/bdmi.hip) and the tests' NumPy
+ * restatement (tests/vcorr_ref.py) both follow it.  Every result is a set of integers: unique, independent of the caller
+ * order, the cell order and the block order, equal to a brute force's.
+ *
+ * HEADINGS.  s_i and u_i are the row's above: s = sqrt((vx vx + vy vy) + vz vz), u_c = v_c / s, 0 when s == 0; float64
+ *   without FMA.
+ * FLUCTUATION AND QUANTISATION.  mean3 is required, finite, |mean_c| <= 1.  d_c = u_ic - mean_c (one float64 subtraction);
+ *   q_ic = rint(d_c 2^24), ties to even, as an integer (the product by a power of two is exact); q_ic = 0 where d_c is not
+ *   finite.  So |q_ic| <= 2^25, and a pair's g_ij = q_ix q_jx + q_iy q_jy + q_iz q_jz is an exact integer, |g_ij| <= 3 * 2^50.
+ *   The quantum 2^-24 is part of the specification: 6e-8 of a unit heading, far below any fluctuation of interest, and what
+ *   makes every sum below an integer.
+ * EDGES, as nbmi_pair_counts': nb + 1 float64 values, 1 <= nb <= 64, finite, edges[0] >= 0, strictly increasing;
+ *   E[k] = edges[k] * edges[k] (one host product each) must again be finite and strictly increasing.  Slot 0 of pairs and
+ *   dot is "below": the pairs with d2 <= E[0].  Slot k >= 1 holds those with E[k-1] < d2 <= E[k]: the upper edge belongs
+ *   to the bin.  A pair with d2 > E[nb] (or a d2 that is NaN) is in no slot.
+ * DISTANCE.  d2(i, j) is fs_d2 of the flock analysis on a walled handle and the difference-based minimum image of "Flock
+ *   analysis on periodic handles" on a periodic one: the same bits from either boid of a pair.
+ * REACH AND THE CANDIDATE RULE.  m = (int)ceil(edges[nb] / cell_size), one float64 divide, cell_size that of bdmi_get_box.
+ *   Required: 1 <= m <= 16, and on a periodic handle 2 m + 1 <= dim: then the (2m+1)^3 wrapped cells are distinct and
+ *   edges[nb] <= m cell_size < B, so the minimum image is the only one in range.
+ *   A pair {i, j}, i != j, is a CANDIDATE iff on every axis its cell coordinates (those of bdmi_get_cell_indices) differ by
+ *   at most m: the clamped coordinates on a walled handle, the cyclic difference min(|D|, dim - |D|) on a periodic one.
+ *   The candidate rule is the definition, as the catalogue's cut rule is.  Every candidate pair is evaluated exactly once;
+ *   *evals = their number.  A pair whose exact separation is below edges[nb] is always a candidate, except possibly within
+ *   a rounding of m cell_size (the cell coordinate is a rounded quotient).  Clamping is monotone, so boids outside a
+ *   walled grid stay exact.
+ * OUTPUTS.  pairs[k] = the number of candidate pairs in slot k.  dot[2k], dot[2k+1] = (hi, lo) of S_k = the sum of g_ij over
+ *   those pairs: S_k = hi 2^32 + lo with 0 <= lo < 2^32, which makes (hi, lo) unique; |S_k| can pass 2^63.  The device
+ *   carries three 64-bit integer words per slot with explicit carries, exact while |S_k| < 2^95, the range of (hi, lo)
+ *   itself: at the largest |g_ij| that is 2^43 pairs in one slot.
+ *   self5 = {sum q_ix, sum q_iy, sum q_iz, Q_hi, Q_lo} with Q = sum (q_ix^2 + q_iy^2 + q_iz^2) in the same form, over all
+ *   boids, without the grid (N 2^25 < 2^56: the three sums fit).  With a last edge that reaches every pair,
+ *   2 sum_k S_k == |sum q|^2 - Q.
+ *   nb == 0 is allowed (edges may then be NULL): only self5 is computed, no grid is built, *evals = 0, pairs and dot are
+ *   not written.  With mean3 = 0 this is the exact integer heading sum.
+ * It builds the grid for the current positions as bdmi_get_forces does (bdmi_grid_info then describes that grid), changes
+ *   nothing a later step reads, waits for its own work and reports the sort's sticky error.  N == 0 and N == 1 succeed
+ *   with zeros (self5 of the one boid).
+ * Refused with NBMI_ERR_ARG (message "bdmi_velocity_correlation: ..."), before anything is launched and with the outputs
+ *   untouched: a null handle, a slab handle, nb outside 0..64, null edges with nb > 0, null mean3, a bad edge (the message
+ *   names its index and value), m outside its range (the message names m, dim and the largest admissible last edge), a
+ *   mean3 that is not finite or above 1 in magnitude.
+ * Scratch, allocated at the first call and freed by bdmi_destroy: 16 bytes per boid (q as int4, the caller id in the
+ *   fourth word) and 2 184 bytes of counters and edges. */
+int bdmi_velocity_correlation(bdmi_flock *f, int nb, const double *edges /* nb+1 */, const double *mean3,
+                              int64_t *pairs /* nb+1 */, int64_t *dot /* (nb+1, 2): hi, lo */, int64_t *self5,
+                              int64_t *evals); /* each output may be NULL */
 
 /* ---- multi-GPU: x-slabs with a one-cell halo -----------------------------------------
  * A rank owns the boids with x_lo <= x < x_hi (a whole number of cell planes, at least two cells wide); the
