@@ -4677,6 +4677,281 @@ __global__ __launch_bounds__(kBlock) void k_deposit_out(unsigned long long *__re
     }
 }
 
+// ---------------------------------------------------------------------------------------
+// K26: radial profiles and mass radii about a centre (nbmi_radial_profile, nbmi_mass_radii; include/nbmi.h, DESIGN.md
+// section 4.26).  The profile is K20's scheme on a tiny dense table: k_profile_max finds max |q| per plane over the
+// bodies with a finite r2, the host turns it into e, k_profile adds the fixed-point integers per workgroup in LDS and
+// sends one global atomic per non-zero (slot, plane); the host converts the at most 8 x 257 sums.
+// ---------------------------------------------------------------------------------------
+constexpr int kProfPlanes = 8;       // NUMBER, MASS, RADIAL_MOMENTUM, RADIAL_KINETIC, KINETIC, ANGULAR_MOMENTUM x 3
+constexpr int kProfMaxBins = 256;
+constexpr int kProfRows = 8;         // state rows per thread of k_profile: a workgroup covers 2 048 consecutive rows
+constexpr int kProfEdgePad = 512;    // E in LDS, padded with +inf so that the 9-step search needs no bound test
+constexpr int kProfNeedM = 1, kProfNeedVr = 2, kProfNeedW2 = 4, kProfNeedL = 8;  // the mass; vr (sqrt, divide); w2; r x w
+struct ProfileArgs {
+    double c[3], b[3];
+    int bulk;                 // w = v - b (0: w = v, no subtraction)
+    int need;                 // kProfNeed*: what the selected planes read beyond the positions
+    int nb;
+    int planes;
+    int slot[kProfPlanes];    // plane -> quantity 0 .. 7 in the order above
+    int e[kProfPlanes];
+    int live[kProfPlanes];
+    double E[kProfMaxBins + 1];
+};
+
+// r = x - c and r2 = (rx rx + ry ry) + rz rz, as the header writes them
+struct ProfR { double rx, ry, rz, r2; };
+__device__ __forceinline__ ProfR prof_r(const Bodies &cur, int64_t i, const double *c) {
+    ProfR r;
+    r.rx = __dsub_rn(cur.x[i], c[0]);
+    r.ry = __dsub_rn(cur.y[i], c[1]);
+    r.rz = __dsub_rn(cur.z[i], c[2]);
+    r.r2 = __dadd_rn(__dadd_rn(__dmul_rn(r.rx, r.rx), __dmul_rn(r.ry, r.ry)), __dmul_rn(r.rz, r.rz));
+    return r;
+}
+// the eight quantities of a body with a finite r2
+struct ProfQ { double q[kProfPlanes]; };
+__device__ __forceinline__ ProfQ prof_quantities(const Bodies &cur, int64_t i, const ProfR &r, const ProfileArgs &a) {
+    ProfQ q = {};
+    q.q[0] = 1.0;
+    if (a.need == 0) return q;  // NUMBER alone.  (`need` is uniform: what no selected plane asks for is not loaded or computed)
+    const double m = cur.m[i];
+    q.q[1] = m;
+    if (!(a.need & (kProfNeedVr | kProfNeedW2 | kProfNeedL))) return q;
+    double wx = cur.vx[i], wy = cur.vy[i], wz = cur.vz[i];
+    if (a.bulk) {
+        wx = __dsub_rn(wx, a.b[0]); wy = __dsub_rn(wy, a.b[1]); wz = __dsub_rn(wz, a.b[2]);
+    }
+    if (a.need & kProfNeedVr) {
+        const double rho = sqrt(r.r2);
+        const double dot = __dadd_rn(__dadd_rn(__dmul_rn(r.rx, wx), __dmul_rn(r.ry, wy)), __dmul_rn(r.rz, wz));
+        const double vr = rho == 0.0 ? 0.0 : dot / rho;
+        const double mvr = __dmul_rn(m, vr);
+        q.q[2] = mvr;
+        q.q[3] = __dmul_rn(mvr, vr);
+    }
+    if (a.need & kProfNeedW2)
+        q.q[4] = __dmul_rn(m, __dadd_rn(__dadd_rn(__dmul_rn(wx, wx), __dmul_rn(wy, wy)), __dmul_rn(wz, wz)));
+    if (a.need & kProfNeedL) {
+        q.q[5] = __dmul_rn(m, __dsub_rn(__dmul_rn(r.ry, wz), __dmul_rn(r.rz, wy)));
+        q.q[6] = __dmul_rn(m, __dsub_rn(__dmul_rn(r.rz, wx), __dmul_rn(r.rx, wz)));
+        q.q[7] = __dmul_rn(m, __dsub_rn(__dmul_rn(r.rx, wy), __dmul_rn(r.ry, wx)));
+    }
+    return q;
+}
+__device__ __forceinline__ double prof_select(const ProfQ &q, int slot) {
+    double v = q.q[0];
+#pragma unroll
+    for (int t = 1; t < kProfPlanes; t++) v = slot == t ? q.q[t] : v;
+    return v;
+}
+
+__global__ __launch_bounds__(kBlock) void k_profile_max(Bodies cur, int64_t n, ProfileArgs a,
+                                                        unsigned long long *__restrict__ out /* [kProfPlanes] */) {
+    __shared__ unsigned long long sh[kBlock];
+    unsigned long long mx[kProfPlanes];
+#pragma unroll
+    for (int p = 0; p < kProfPlanes; p++) mx[p] = 0ull;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+        const ProfR r = prof_r(cur, i, a.c);
+        if (!isfinite(r.r2)) continue;
+        const ProfQ q = prof_quantities(cur, i, r, a);
+#pragma unroll
+        for (int p = 0; p < kProfPlanes; p++) {
+            if (p < a.planes) {
+                const unsigned long long b = (unsigned long long)__double_as_longlong(fabs(prof_select(q, a.slot[p])));
+                mx[p] = b > mx[p] ? b : mx[p];
+            }
+        }
+    }
+#pragma unroll
+    for (int p = 0; p < kProfPlanes; p++) {
+        if (p >= a.planes) break;
+        sh[threadIdx.x] = mx[p];
+        __syncthreads();
+        for (int w = kBlock / 2; w > 0; w >>= 1) {
+            if ((int)threadIdx.x < w) sh[threadIdx.x] = sh[threadIdx.x] > sh[threadIdx.x + w] ? sh[threadIdx.x] : sh[threadIdx.x + w];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0 && sh[0] != 0ull) atomicMax(&out[p], sh[0]);
+        __syncthreads();
+    }
+}
+
+// One pass over the state rows.  Dynamic LDS: kProfEdgePad doubles (E, then +inf), then planes x (nb + 1) sums, plane
+// major.  The slot is the number of E[k] < r2, found by nine unconditional halvings.  One LDS atomic per (body, plane) -
+// also where every body of the workgroup hits one shell: summing a wave's equal slots first measured 1 - 9 % slower
+// everywhere (scripts/experiments/profile_wave_sum.patch) - and at the end one global atomic per non-zero (slot, plane).
+// stats = {bodies in a slot, bodies beyond, bodies skipped}.
+__global__ __launch_bounds__(kBlock) void k_profile(Bodies cur, int64_t n, ProfileArgs a, unsigned long long *__restrict__ K,
+                                                    unsigned long long *__restrict__ stats) {
+    extern __shared__ unsigned long long prof_lds[];
+    __shared__ unsigned int sh_stats[3];
+    double *E = (double *)prof_lds;
+    unsigned long long *vals = prof_lds + kProfEdgePad;
+    const int nslots = a.nb + 1;
+    if (threadIdx.x < 3) sh_stats[threadIdx.x] = 0u;
+    for (int t = threadIdx.x; t < kProfEdgePad; t += kBlock) E[t] = t <= a.nb ? a.E[t] : __longlong_as_double(0x7ff0000000000000ll);
+    for (int t = threadIdx.x; t < a.planes * nslots; t += kBlock) vals[t] = 0ull;
+    __syncthreads();
+    unsigned int inside = 0u, beyond = 0u, skipped = 0u;
+    const int64_t base = (int64_t)blockIdx.x * (kBlock * kProfRows);
+    for (int r = 0; r < kProfRows; r++) {
+        const int64_t i = base + (int64_t)r * kBlock + threadIdx.x;
+        int slot = -1;  // -1: nothing to add
+        ProfQ q = {};
+        if (i < n) {
+            const ProfR rr = prof_r(cur, i, a.c);
+            if (!isfinite(rr.r2)) {
+                skipped++;
+            } else {
+                int pos = 0;
+#pragma unroll
+                for (int step = kProfEdgePad / 2; step > 0; step >>= 1) pos += E[pos + step - 1] < rr.r2 ? step : 0;
+                if (pos > a.nb) {
+                    beyond++;
+                } else {
+                    inside++;
+                    slot = pos;
+                    q = prof_quantities(cur, i, rr, a);
+                }
+            }
+        }
+        if (slot < 0) continue;
+#pragma unroll
+        for (int p = 0; p < kProfPlanes; p++) {
+            if (p >= a.planes || !a.live[p]) continue;  // (uniform)
+            const long long k = (long long)rint(ldexp(prof_select(q, a.slot[p]), -a.e[p]));
+            if (k != 0ll) atomicAdd(&vals[p * nslots + slot], (unsigned long long)k);
+        }
+    }
+    if (inside) atomicAdd(&sh_stats[0], inside);
+    if (beyond) atomicAdd(&sh_stats[1], beyond);
+    if (skipped) atomicAdd(&sh_stats[2], skipped);
+    __syncthreads();
+    if (threadIdx.x < 3 && sh_stats[threadIdx.x]) atomicAdd(&stats[threadIdx.x], (unsigned long long)sh_stats[threadIdx.x]);
+    for (int t = threadIdx.x; t < a.planes * nslots; t += kBlock) {
+        const unsigned long long v = vals[t];
+        if (v) atomicAdd(&K[t], v);
+    }
+}
+
+// ---- mass radii: sort by the bits of r2, prefix sums of the masses' integers, one crossing test per tie run ----
+constexpr uint64_t kMrSkipKey = 0x7fffffffffffffffull;  // above every finite r2's bits: the skipped bodies sort last
+constexpr int kMrMaxFractions = 64;
+struct MrArgs {
+    int nf;
+    int e;
+    long long T[kMrMaxFractions];
+    long long tmin, tmax;
+};
+// res[0] = the largest mass's bits (of |m|), res[1] = 1 if a mass is negative
+__global__ __launch_bounds__(kBlock) void k_mr_mass_max(Bodies cur, int64_t n, unsigned long long *__restrict__ res) {
+    __shared__ unsigned long long sh[kBlock];
+    __shared__ unsigned int neg;
+    if (threadIdx.x == 0) neg = 0u;
+    unsigned long long mx = 0ull;
+    bool negative = false;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+        const double m = cur.m[i];
+        negative = negative || m < 0.0;
+        const unsigned long long b = (unsigned long long)__double_as_longlong(fabs(m));
+        mx = b > mx ? b : mx;
+    }
+    sh[threadIdx.x] = mx;
+    __syncthreads();
+    if (negative) neg = 1u;
+    for (int w = kBlock / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) sh[threadIdx.x] = sh[threadIdx.x] > sh[threadIdx.x + w] ? sh[threadIdx.x] : sh[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        if (sh[0] != 0ull) atomicMax(&res[0], sh[0]);
+        if (neg) atomicMax(&res[1], 1ull);
+    }
+}
+// key = the bits of r2 (a non-negative finite double orders as its bits), kMrSkipKey for a body that is skipped
+__global__ __launch_bounds__(kBlock) void k_mr_keys(Bodies cur, int64_t n, double cx, double cy, double cz,
+                                                    uint64_t *__restrict__ key, uint32_t *__restrict__ idx,
+                                                    unsigned long long *__restrict__ skipped) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    long long skip = 0;
+    if (i < n) {
+        const double c[3] = {cx, cy, cz};
+        const ProfR r = prof_r(cur, i, c);
+        const bool ok = isfinite(r.r2);
+        key[i] = ok ? (uint64_t)__double_as_longlong(r.r2) : kMrSkipKey;
+        idx[i] = (uint32_t)i;
+        skip = ok ? 0 : 1;
+    }
+    nbmi::wave_add(skipped, skip, threadIdx.x & 63);
+}
+// Scan element over the sorted bodies: sum = the integers so far, run = those of the tie run that the last entry belongs
+// to (as far as it lies inside the scanned range), head = a run starts inside the range.
+struct MrSeg {
+    long long sum, run;
+    int head;
+};
+__device__ __forceinline__ MrSeg lane_up(const MrSeg &s, int d) { return MrSeg{__shfl_up(s.sum, d), __shfl_up(s.run, d), __shfl_up(s.head, d)}; }
+struct MrSegOp {
+    __device__ MrSeg operator()(const MrSeg &a, const MrSeg &b) const {
+        return MrSeg{a.sum + b.sum, b.head ? b.run : a.run + b.run, a.head | b.head};
+    }
+};
+// the entry of sorted position j: k = rint(ldexp(m, -e)) of its body (0 for a skipped body), head = it starts a tie run
+__device__ __forceinline__ MrSeg mr_entry(const uint64_t *__restrict__ key_s, const long long *__restrict__ kk, int64_t j) {
+    const long long k = kk[j];
+    return MrSeg{k, k, (j == 0 || key_s[j] != key_s[j - 1]) ? 1 : 0};
+}
+// phase 1: the integers in sorted order (kept in kk) and the fold of every tile of scan::kTile entries
+__global__ __launch_bounds__(scan::kBlock) void k_mr_tiles(Bodies cur, int64_t n, const uint64_t *__restrict__ key_s,
+                                                           const uint32_t *__restrict__ idx_s, int e, long long *__restrict__ kk,
+                                                           MrSeg *__restrict__ tiles) {
+    const int64_t first = ((int64_t)blockIdx.x * scan::kBlock + threadIdx.x) * scan::kItems;
+    MrSeg acc{0ll, 0ll, 0};
+#pragma unroll
+    for (int t = 0; t < scan::kItems; t++) {
+        const int64_t j = first + t;
+        if (j >= n) break;
+        const uint64_t key = key_s[j];
+        const long long k = key == kMrSkipKey ? 0ll : (long long)rint(ldexp(cur.m[idx_s[j]], -e));
+        kk[j] = k;
+        acc = MrSegOp()(acc, MrSeg{k, k, (j == 0 || key != key_s[j - 1]) ? 1 : 0});
+    }
+    const MrSeg total = scan::block_scan<scan::kBlock>(acc, MrSeg{0ll, 0ll, 0}, MrSegOp()).total;
+    if (threadIdx.x == 0) tiles[blockIdx.x] = total;
+}
+// phase 3: with the scanned tiles in front, every entry that ends a tie run of bodies taking part tests
+// C_prev_run < T <= C_run per fraction and writes out[3 f] = {bits of r2, bodies inside, the integer sum}
+__global__ __launch_bounds__(scan::kBlock) void k_mr_select(int64_t n, const uint64_t *__restrict__ key_s,
+                                                            const long long *__restrict__ kk, const MrSeg *__restrict__ tiles,
+                                                            MrArgs a, unsigned long long *__restrict__ out) {
+    const int64_t first = ((int64_t)blockIdx.x * scan::kBlock + threadIdx.x) * scan::kItems;
+    MrSeg acc{0ll, 0ll, 0};
+#pragma unroll
+    for (int t = 0; t < scan::kItems; t++)
+        if (first + t < n) acc = MrSegOp()(acc, mr_entry(key_s, kk, first + t));
+    MrSeg run = scan::block_scan<scan::kBlock>(acc, tiles[blockIdx.x], MrSegOp()).excl;
+#pragma unroll
+    for (int t = 0; t < scan::kItems; t++) {
+        const int64_t j = first + t;
+        if (j >= n) break;
+        run = MrSegOp()(run, mr_entry(key_s, kk, j));
+        const uint64_t key = key_s[j];
+        if (key == kMrSkipKey || (j + 1 < n && key_s[j + 1] == key)) continue;
+        const long long c_run = run.sum, c_prev = run.sum - run.run;
+        if (c_run < a.tmin || c_prev >= a.tmax) continue;
+        for (int f = 0; f < a.nf; f++) {
+            if (c_prev < a.T[f] && a.T[f] <= c_run) {
+                out[3 * f] = key;
+                out[3 * f + 1] = (unsigned long long)(j + 1);
+                out[3 * f + 2] = (unsigned long long)c_run;
+            }
+        }
+    }
+}
+
 }  // namespace
 
 // =========================================================================================
@@ -4870,6 +5145,23 @@ struct nbmi_sim {
         int64_t words = 0;
         unsigned long long *K = nullptr, *res = nullptr;
     } dep;
+    // Scratch of nbmi_radial_profile (section 4.26): 8 maxima, 3 stats and 8 x 257 sums.  No step touches it.
+    struct {
+        unsigned long long *res = nullptr;
+    } prof;
+    // Scratch of nbmi_mass_radii (section 4.26) for `rows` bodies - 32 bytes each: keys and rows in and out of the sort,
+    // the masses' integers in sorted order - the sort's temp buffer for that many pairs, 24 bytes per 2 048 bodies of
+    // tile folds and 195 words of results: the largest mass, "a mass is negative", bodies skipped, 3 per fraction.
+    struct {
+        int64_t rows = 0;
+        uint64_t *key = nullptr, *key_s = nullptr;
+        uint32_t *idx = nullptr, *idx_s = nullptr;
+        long long *kk = nullptr;
+        MrSeg *tiles = nullptr;
+        char *sort_tmp = nullptr;
+        size_t sort_bytes = 0;
+        unsigned long long *res = nullptr;
+    } mr;
     bool deposit_agg = true;  // the workgroup combines contributions per cell in LDS first (NBMI_DEPOSIT_AGG=0: one global
                               // atomic per contribution; same bits, 3.1 - 134 x the time: DESIGN.md section 4.20)
     // Scratch of nbmi_field_at (section 4.18): `rows` points of a chunk - 108 bytes each: the points as they came, acc,
@@ -6754,6 +7046,269 @@ int nbmi_deposit(nbmi_sim *s, const double *lo, const double *hi, const int32_t 
     }
     for (int p = 0; exponents && p < a.planes; p++) exponents[p] = a.e[p];
     for (int k = 0; stats3 && k < 3; k++) stats3[k] = (int64_t)h[kDepPlanes + k];
+    return 0;
+}
+
+namespace {
+// what both calls of section 4.26 refuse as nbmi_deposit does, and the centre
+int profile_refuse(nbmi_sim *s, const char *who, const double *center) {
+    if (s->owner) {
+        nbmi::set_error("%s: owner-mode handles are not supported (the other ranks hold the rest of the bodies)", who);
+        return NBMI_ERR_ARG;
+    }
+    if (s->shard_begin != 0 || s->shard_end != s->n) {
+        nbmi::set_error("%s: sharded handles are not supported", who);
+        return NBMI_ERR_ARG;
+    }
+    if (!center) {
+        nbmi::set_error("%s: null center", who);
+        return NBMI_ERR_ARG;
+    }
+    for (int k = 0; k < 3; k++) {
+        if (!isfinite(center[k])) {
+            nbmi::set_error("%s: center[%d] = %g is not finite", who, k, center[k]);
+            return NBMI_ERR_ARG;
+        }
+    }
+    return 0;
+}
+}  // namespace
+
+int nbmi_radial_profile(nbmi_sim *s, const double *center, const double *bulk_velocity, int nb, const double *edges,
+                        int quantities, double *out, int64_t *stats3, int32_t *exponents) {
+    static const char *const kWho = "nbmi_radial_profile";
+    static const char *const kPlaneName[kProfPlanes] = {"NUMBER", "MASS", "RADIAL_MOMENTUM", "RADIAL_KINETIC", "KINETIC",
+                                                        "ANGULAR_MOMENTUM x", "ANGULAR_MOMENTUM y", "ANGULAR_MOMENTUM z"};
+    if (int rc = check_handle(s)) return rc;
+    if (int rc = profile_refuse(s, kWho, center)) return rc;
+    if (!edges || !out) {
+        nbmi::set_error("%s: null %s", kWho, !edges ? "edges" : "out");
+        return NBMI_ERR_ARG;
+    }
+    for (int k = 0; bulk_velocity && k < 3; k++) {
+        if (!isfinite(bulk_velocity[k])) {
+            nbmi::set_error("%s: bulk_velocity[%d] = %g is not finite", kWho, k, bulk_velocity[k]);
+            return NBMI_ERR_ARG;
+        }
+    }
+    if (nb < 1 || nb > kProfMaxBins) {
+        nbmi::set_error("%s: nb = %d is outside 1 .. %d", kWho, nb, kProfMaxBins);
+        return NBMI_ERR_ARG;
+    }
+    if (quantities == 0 || (quantities & ~63) != 0) {
+        nbmi::set_error("%s: quantities = %d selects nothing or has unknown bits", kWho, quantities);
+        return NBMI_ERR_ARG;
+    }
+    ProfileArgs a{};
+    for (int k = 0; k <= nb; k++) {
+        if (!isfinite(edges[k]) || edges[k] < 0.0 || (k > 0 && !(edges[k] > edges[k - 1]))) {
+            nbmi::set_error("%s: edges[%d] = %g: the edges must be finite, >= 0 and strictly increasing", kWho, k, edges[k]);
+            return NBMI_ERR_ARG;
+        }
+        a.E[k] = edges[k] * edges[k];
+        if (!isfinite(a.E[k]) || (k > 0 && !(a.E[k] > a.E[k - 1]))) {
+            nbmi::set_error("%s: the square of edges[%d] = %g is not finite or not above the one before it", kWho, k, edges[k]);
+            return NBMI_ERR_ARG;
+        }
+    }
+    for (int k = 0; k < 3; k++) {
+        a.c[k] = center[k];
+        a.b[k] = bulk_velocity ? bulk_velocity[k] : 0.0;
+    }
+    a.bulk = bulk_velocity ? 1 : 0;
+    a.nb = nb;
+    for (int b = 0; b < 5; b++)
+        if (quantities & (1 << b)) a.slot[a.planes++] = b;
+    if (quantities & NBMI_PROFILE_ANGULAR_MOMENTUM)
+        for (int c = 0; c < 3; c++) a.slot[a.planes++] = 5 + c;
+    a.need = (quantities & ~NBMI_PROFILE_NUMBER ? kProfNeedM : 0) |
+             (quantities & (NBMI_PROFILE_RADIAL_MOMENTUM | NBMI_PROFILE_RADIAL_KINETIC) ? kProfNeedVr : 0) |
+             (quantities & NBMI_PROFILE_KINETIC ? kProfNeedW2 : 0) | (quantities & NBMI_PROFILE_ANGULAR_MOMENTUM ? kProfNeedL : 0);
+    const int64_t n = s->n;
+    const int nslots = nb + 1, words = a.planes * nslots;
+    hipStream_t st = s->stream;
+    NBMI_HIP_CHECK(hipStreamSynchronize(st));
+    if (int rc = check_device_error(s)) return rc;
+    constexpr int kRes = kProfPlanes + 3;
+    unsigned long long h[kRes] = {};
+    std::vector<unsigned long long> K((size_t)words, 0ull);
+    if (n > 0) {
+        if (!s->prof.res && dev_alloc(s, &s->prof.res, kRes + kProfPlanes * (kProfMaxBins + 1))) return NBMI_ERR_HIP;
+        const Bodies cur = s->buf[s->curbuf];
+        float ms = 0.0f, ms2 = 0.0f;
+        NBMI_HIP_CHECK(hipMemsetAsync(s->prof.res, 0, (size_t)(kRes + words) * sizeof(h[0]), st));
+        if (s->timers) NBMI_HIP_CHECK(hipEventRecord(s->ev[0], st));
+        const int64_t want = nblocks(n);
+        k_profile_max<<<(int)(want < 1024 ? want : 1024), kBlock, 0, st>>>(cur, n, a, s->prof.res);
+        NBMI_HIP_CHECK(hipGetLastError());
+        if (s->timers) NBMI_HIP_CHECK(hipEventRecord(s->ev[1], st));
+        NBMI_HIP_CHECK(hipMemcpyAsync(h, s->prof.res, kProfPlanes * sizeof(h[0]), hipMemcpyDeviceToHost, st));
+        NBMI_HIP_CHECK(hipStreamSynchronize(st));
+        const int L = 64 - __builtin_clzll((unsigned long long)n);  // the bit length of N
+        for (int p = 0; p < a.planes; p++) {
+            double mx;
+            memcpy(&mx, &h[p], sizeof(mx));
+            if (!isfinite(mx)) {
+                nbmi::set_error("%s: the largest |q| of plane %d (%s) is not finite", kWho, p, kPlaneName[a.slot[p]]);
+                return NBMI_ERR_ARG;
+            }
+            int E = 0;
+            if (mx != 0.0) (void)frexp(mx, &E);
+            a.live[p] = mx != 0.0;
+            a.e[p] = mx != 0.0 ? E + L - 62 : 0;
+        }
+        if (s->timers) NBMI_HIP_CHECK(hipEventRecord(s->ev[2], st));
+        const int blocks = (int)((n + kBlock * kProfRows - 1) / (kBlock * kProfRows));
+        const size_t lds = (size_t)(kProfEdgePad + words) * sizeof(unsigned long long);
+        k_profile<<<blocks, kBlock, lds, st>>>(cur, n, a, s->prof.res + kRes, s->prof.res + kProfPlanes);
+        NBMI_HIP_CHECK(hipGetLastError());
+        if (s->timers) NBMI_HIP_CHECK(hipEventRecord(s->ev[3], st));
+        NBMI_HIP_CHECK(hipMemcpyAsync(h + kProfPlanes, s->prof.res + kProfPlanes, 3 * sizeof(h[0]), hipMemcpyDeviceToHost, st));
+        NBMI_HIP_CHECK(hipMemcpyAsync(K.data(), s->prof.res + kRes, (size_t)words * sizeof(h[0]), hipMemcpyDeviceToHost, st));
+        NBMI_HIP_CHECK(hipStreamSynchronize(st));
+        if (s->timers) {  // the device time of the two passes, without the copies: "other"
+            NBMI_HIP_CHECK(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
+            NBMI_HIP_CHECK(hipEventElapsedTime(&ms2, s->ev[2], s->ev[3]));
+            s->ms[4] += (double)ms + (double)ms2;
+        }
+    }
+    for (int p = 0; p < a.planes; p++)
+        for (int k = 0; k < nslots; k++) out[p * nslots + k] = ldexp((double)(long long)K[(size_t)p * nslots + k], a.e[p]);
+    for (int p = 0; exponents && p < a.planes; p++) exponents[p] = a.e[p];
+    for (int k = 0; stats3 && k < 3; k++) stats3[k] = (int64_t)h[kProfPlanes + k];
+    return 0;
+}
+
+int nbmi_mass_radii(nbmi_sim *s, const double *center, int nf, const double *fractions, double *radius2, int64_t *inside,
+                    double *mass_inside, double *total_mass, int64_t *stats2, int32_t *exponent) {
+    static const char *const kWho = "nbmi_mass_radii";
+    if (int rc = check_handle(s)) return rc;
+    if (int rc = profile_refuse(s, kWho, center)) return rc;
+    if (!fractions || !radius2) {
+        nbmi::set_error("%s: null %s", kWho, !fractions ? "fractions" : "radius2");
+        return NBMI_ERR_ARG;
+    }
+    if (nf < 1 || nf > kMrMaxFractions) {
+        nbmi::set_error("%s: nf = %d is outside 1 .. %d", kWho, nf, kMrMaxFractions);
+        return NBMI_ERR_ARG;
+    }
+    for (int f = 0; f < nf; f++) {
+        if (!isfinite(fractions[f]) || !(fractions[f] > 0.0) || fractions[f] > 1.0) {
+            nbmi::set_error("%s: fractions[%d] = %g is not in (0, 1]", kWho, f, fractions[f]);
+            return NBMI_ERR_ARG;
+        }
+    }
+    const int64_t n = s->n;
+    hipStream_t st = s->stream;
+    NBMI_HIP_CHECK(hipStreamSynchronize(st));
+    if (int rc = check_device_error(s)) return rc;
+    constexpr int kRes = 3;  // the largest mass, a mass is negative, bodies skipped; then 3 words per fraction
+    unsigned long long h[kRes + 3 * kMrMaxFractions] = {};
+    long long k_total = 0;
+    int e = 0;
+    auto &g = s->mr;
+    if (n > 0) {
+        if (n > g.rows) {  // (nothing enqueued uses the old arrays: every call waits for its copies)
+            dev_free(s, &g.key); dev_free(s, &g.key_s); dev_free(s, &g.idx); dev_free(s, &g.idx_s); dev_free(s, &g.kk);
+            dev_free(s, &g.tiles); dev_free(s, &g.sort_tmp);
+            g.rows = 0;
+            g.sort_bytes = nbmi::radix_temp_bytes_u64((size_t)n, 63);
+            if ((!g.res && dev_alloc(s, &g.res, kRes + 3 * kMrMaxFractions)) || dev_alloc(s, &g.key, (size_t)n) ||
+                dev_alloc(s, &g.key_s, (size_t)n) || dev_alloc(s, &g.idx, (size_t)n) || dev_alloc(s, &g.idx_s, (size_t)n) ||
+                dev_alloc(s, &g.kk, (size_t)n) || dev_alloc(s, &g.tiles, (size_t)scan::tiles_for(n) + 1) ||
+                dev_alloc(s, &g.sort_tmp, g.sort_bytes + 256))
+                return NBMI_ERR_HIP;
+            NBMI_HIP_CHECK(nbmi::radix_init_temp(g.sort_tmp, st));
+            g.rows = n;
+        }
+        const Bodies cur = s->buf[s->curbuf];
+        float ms = 0.0f;
+        double total_ms = 0.0;
+        NBMI_HIP_CHECK(hipMemsetAsync(g.res, 0, sizeof(h), st));
+        if (s->timers) NBMI_HIP_CHECK(hipEventRecord(s->ev[0], st));
+        const int64_t want = nblocks(n);
+        k_mr_mass_max<<<(int)(want < 1024 ? want : 1024), kBlock, 0, st>>>(cur, n, g.res);
+        k_mr_keys<<<nblocks(n), kBlock, 0, st>>>(cur, n, center[0], center[1], center[2], g.key, g.idx, g.res + 2);
+        NBMI_HIP_CHECK(hipGetLastError());
+        if (s->timers) NBMI_HIP_CHECK(hipEventRecord(s->ev[1], st));
+        NBMI_HIP_CHECK(hipMemcpyAsync(h, g.res, kRes * sizeof(h[0]), hipMemcpyDeviceToHost, st));
+        NBMI_HIP_CHECK(hipStreamSynchronize(st));
+        if (s->timers) {
+            NBMI_HIP_CHECK(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
+            total_ms += (double)ms;
+        }
+        double mx;
+        memcpy(&mx, &h[0], sizeof(mx));
+        if (!isfinite(mx) || h[1]) {
+            nbmi::set_error("%s: a mass is %s", kWho, !isfinite(mx) ? "not finite" : "negative");
+            return NBMI_ERR_ARG;
+        }
+        if (mx != 0.0) {
+            int E = 0;
+            (void)frexp(mx, &E);
+            e = E + (64 - __builtin_clzll((unsigned long long)n)) - 53;
+            const int64_t ntiles = scan::tiles_for(n);
+            MrSeg total{};
+            if (s->timers) NBMI_HIP_CHECK(hipEventRecord(s->ev[2], st));
+            NBMI_HIP_CHECK(nbmi::radix_sort_pairs_u64(g.sort_tmp, g.sort_bytes, g.key, g.key_s, g.idx, g.idx_s, (size_t)n, 0, 63, st));
+            k_mr_tiles<<<(int)ntiles, scan::kBlock, 0, st>>>(cur, n, g.key_s, g.idx_s, e, g.kk, g.tiles);
+            scan::k_scan_values<<<1, scan::kScanThreads, 0, st>>>(g.tiles, g.tiles, ntiles, (int64_t)0, MrSeg{0ll, 0ll, 0}, MrSegOp());
+            NBMI_HIP_CHECK(hipGetLastError());
+            if (s->timers) NBMI_HIP_CHECK(hipEventRecord(s->ev[3], st));
+            NBMI_HIP_CHECK(hipMemcpyAsync(&total, g.tiles + ntiles, sizeof(total), hipMemcpyDeviceToHost, st));
+            NBMI_HIP_CHECK(hipStreamSynchronize(st));
+            if (s->timers) {
+                NBMI_HIP_CHECK(hipEventElapsedTime(&ms, s->ev[2], s->ev[3]));
+                total_ms += (double)ms;
+            }
+            k_total = total.sum;
+            if (k_total > 0) {
+                MrArgs a{};
+                a.nf = nf;
+                a.e = e;
+                for (int f = 0; f < nf; f++) {
+                    const long long t = (long long)ceil(fractions[f] * (double)k_total);
+                    a.T[f] = t < 1 ? 1 : t;
+                    a.tmin = f == 0 || a.T[f] < a.tmin ? a.T[f] : a.tmin;
+                    a.tmax = f == 0 || a.T[f] > a.tmax ? a.T[f] : a.tmax;
+                }
+                if (s->timers) NBMI_HIP_CHECK(hipEventRecord(s->ev[4], st));
+                k_mr_select<<<(int)ntiles, scan::kBlock, 0, st>>>(n, g.key_s, g.kk, g.tiles, a, g.res + kRes);
+                NBMI_HIP_CHECK(hipGetLastError());
+                if (s->timers) NBMI_HIP_CHECK(hipEventRecord(s->ev[5], st));
+                NBMI_HIP_CHECK(hipMemcpyAsync(h + kRes, g.res + kRes, (size_t)3 * nf * sizeof(h[0]), hipMemcpyDeviceToHost, st));
+            }
+            unsigned sort_err = 0u;
+            NBMI_HIP_CHECK(nbmi::radix_error_word(g.sort_tmp, &sort_err, st));
+            NBMI_HIP_CHECK(hipStreamSynchronize(st));
+            if (sort_err) {
+                NBMI_HIP_CHECK(nbmi::radix_init_temp(g.sort_tmp, st));
+                NBMI_HIP_CHECK(hipStreamSynchronize(st));
+                nbmi::set_error("%s: the sort of the squared radii failed", kWho);
+                return NBMI_ERR_HIP;
+            }
+            if (s->timers && k_total > 0) {
+                NBMI_HIP_CHECK(hipEventElapsedTime(&ms, s->ev[4], s->ev[5]));
+                total_ms += (double)ms;
+            }
+        }
+        if (s->timers) s->ms[4] += total_ms;  // the device time of the call's kernels, without its copies: "other"
+    }
+    for (int f = 0; f < nf; f++) {
+        if (k_total > 0) {
+            memcpy(&radius2[f], &h[kRes + 3 * f], sizeof(double));
+        } else {
+            radius2[f] = NAN;
+        }
+        if (inside) inside[f] = k_total > 0 ? (int64_t)h[kRes + 3 * f + 1] : 0;
+        if (mass_inside) mass_inside[f] = k_total > 0 ? ldexp((double)(long long)h[kRes + 3 * f + 2], e) : 0.0;
+    }
+    if (total_mass) *total_mass = ldexp((double)k_total, e);
+    if (stats2) {
+        stats2[0] = n - (int64_t)h[2];
+        stats2[1] = (int64_t)h[2];
+    }
+    if (exponent) *exponent = e;
     return 0;
 }
 

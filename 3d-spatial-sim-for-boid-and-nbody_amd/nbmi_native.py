@@ -60,6 +60,8 @@ PROTOTYPES = {
     "nbmi_pair_counts": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "nbmi_field_at": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp]),
     "nbmi_deposit": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "nbmi_radial_profile": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp]),
+    "nbmi_mass_radii": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "nbmi_set_tracers": (C.c_int, [_vp, _i64, _vp, _vp]),
     "nbmi_tracer_count": (_i64, [_vp]),
     "nbmi_get_tracers_f64": (C.c_int, [_vp, _vp, _vp]),

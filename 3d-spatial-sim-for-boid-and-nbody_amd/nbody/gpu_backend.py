@@ -35,6 +35,9 @@ MULTIPOLES = {"monopole": 0, "quadrupole": 1}
 COLOR_MODES = {"speed": 0, "density": 1}
 DEPOSIT_SCHEMES = {"ngp": 0, "cic": 1}  # NBMI_DEPOSIT_*
 DEPOSIT_QUANTITIES = {"number": 1, "mass": 2, "momentum": 4, "kinetic": 8}  # in the order of the planes
+# planes of nbmi_radial_profile (NBMI_PROFILE_*), in the order of the planes; "angular_momentum" has three
+PROFILE_QUANTITIES = {"number": 1, "mass": 2, "radial_momentum": 4, "radial_kinetic": 8, "kinetic": 16,
+                      "angular_momentum": 32}
 KNN_MAX_K = 64
 
 
@@ -413,6 +416,94 @@ class _HIPSimulation:
         if stats:
             res["stats"] = tuple(int(x) for x in st)
         return res
+
+    # ---- radial profiles and mass radii (include/nbmi.h nbmi_radial_profile; nbody/profile.py) ----
+    def _profile_center(self, what, center, bulk_velocity):
+        """(centre, bulk velocity) as float64 3-vectors: "com" = the centre of mass and P / M of diagnostics(), None or
+        "origin" = zeros, a 3-sequence as given."""
+        d = None
+        out = []
+        for name, val in (("center", center), ("bulk_velocity", bulk_velocity)):
+            if val is None or (isinstance(val, str) and val == "origin"):
+                out.append(np.zeros(3, dtype=np.float64))
+            elif isinstance(val, str) and val == "com":
+                if d is None:  # diagnostics(potential=False), a handle it refuses (a shard) being a ValueError here
+                    d = np.empty(12, dtype=np.float64)
+                    terms = C.c_int64(0)
+                    _nat.check_arg(self._lib.nbmi_diagnostics(self._h, 0, _nat.ptr(d), C.addressof(terms)), what,
+                                   "nbmi_diagnostics")
+                if name == "center":
+                    out.append(np.array([float(x) for x in d[1:4]], dtype=np.float64))
+                else:
+                    out.append(np.array([float(x) for x in d[4:7]], dtype=np.float64) / np.float64(float(d[0])))
+            else:
+                a = None if isinstance(val, str) else np.ascontiguousarray(val, dtype=np.float64).reshape(-1)
+                if a is None or len(a) != 3:
+                    raise ValueError(f'{what}: {name} must be "com", "origin", None or three numbers, not {val!r}')
+                out.append(a)
+        return out
+
+    def radial_profile(self, edges, center="com", bulk_velocity="com", quantities=("number", "mass"), stats=False):
+        """Sums of per-body quantities over the shells between the nb + 1 radii ``edges`` about ``center``, velocities
+        taken relative to ``bulk_velocity`` ("com": the centre of mass and its velocity from ``diagnostics``; None or
+        "origin": zeros; or three numbers).  ``quantities``: any of "number", "mass", "radial_momentum" (m v_r),
+        "radial_kinetic" (m v_r^2), "kinetic" (m w^2), "angular_momentum" (m r x w).  Returns a dict with one float64
+        array of nb + 1 values per quantity - entry 0 the ball inside edges[0], entry s the shell (edges[s-1], edges[s]];
+        "angular_momentum": (3, nb + 1) -, "center", "bulk_velocity", "exponents" (int32 per plane in the library's order)
+        and, with ``stats``, "stats" = (bodies in a slot, bodies beyond the last edge, bodies skipped as not finite).
+        Exact integer sums of fixed-point contributions: independent of the order of the bodies, the same bits on every
+        call.  Barnes-Hut and direct handles; ValueError for bad arguments, a quantity whose maximum is not finite, and
+        owner-mode and sharded handles.  The call does not change what the next step computes."""
+        what = "radial_profile"
+        self._query_refuse(what, tree=False)
+        if isinstance(quantities, str):
+            quantities = (quantities,)
+        unknown = [q for q in quantities if q not in PROFILE_QUANTITIES]
+        if unknown or not quantities:
+            raise ValueError(f"{what}: quantities must be some of {list(PROFILE_QUANTITIES)}, not {list(quantities)}")
+        e = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+        if len(e) < 2 or len(e) > 257:
+            raise ValueError(f"{what}: expected 2 .. 257 edges, got {len(e)}")
+        c, b = self._profile_center(what, center, bulk_velocity)
+        names = [q for q in PROFILE_QUANTITIES if q in quantities]  # the library's plane order
+        bits = sum(PROFILE_QUANTITIES[q] for q in names)
+        planes = sum(3 if q == "angular_momentum" else 1 for q in names)
+        out = np.zeros((planes, len(e)), dtype=np.float64)
+        st = np.zeros(3, dtype=np.int64)
+        ex = np.zeros(planes, dtype=np.int32)
+        self._query_call(what, self._lib.nbmi_radial_profile(self._h, _nat.ptr(c), _nat.ptr(b), len(e) - 1, _nat.ptr(e), bits,
+                                                           _nat.ptr(out), _nat.ptr(st), _nat.ptr(ex)))
+        res, p = {}, 0
+        for q in names:
+            res[q] = out[p:p + 3] if q == "angular_momentum" else out[p]
+            p += 3 if q == "angular_momentum" else 1
+        res["center"], res["bulk_velocity"], res["exponents"] = c, b, ex
+        if stats:
+            res["stats"] = tuple(int(x) for x in st)
+        return res
+
+    def mass_radii(self, fractions, center="com"):
+        """The squared radii about ``center`` (as in ``radial_profile``) that hold the given ``fractions`` (each in
+        (0, 1], any order) of the mass of the bodies with finite coordinates: a dict with "radius2" (the smallest r^2 of
+        a body within which at least that fraction lies, NaN if there is no mass), "inside" (bodies within it, int64),
+        "mass_inside", "total_mass", "center", "stats" = (bodies taking part, bodies skipped) and "exponent" (the masses
+        are counted in units of 2 ** exponent).  Exact and unique: a rank selection over integer masses in which bodies
+        of equal r^2 enter together.  Barnes-Hut and direct handles; ValueError as for ``radial_profile``."""
+        what = "mass_radii"
+        self._query_refuse(what, tree=False)
+        f = np.ascontiguousarray(fractions, dtype=np.float64).reshape(-1)
+        if len(f) < 1 or len(f) > 64:
+            raise ValueError(f"{what}: expected 1 .. 64 fractions, got {len(f)}")
+        c, = self._profile_center(what, center, None)[:1]
+        r2 = np.zeros(len(f), dtype=np.float64)
+        inside = np.zeros(len(f), dtype=np.int64)
+        mass = np.zeros(len(f), dtype=np.float64)
+        total, ex = C.c_double(0.0), C.c_int32(0)
+        st = np.zeros(2, dtype=np.int64)
+        self._query_call(what, self._lib.nbmi_mass_radii(self._h, _nat.ptr(c), len(f), _nat.ptr(f), _nat.ptr(r2), _nat.ptr(inside),
+                                                       _nat.ptr(mass), C.addressof(total), _nat.ptr(st), C.addressof(ex)))
+        return {"radius2": r2, "inside": inside, "mass_inside": mass, "total_mass": float(total.value), "center": c,
+                "stats": tuple(int(x) for x in st), "exponent": int(ex.value)}
 
     def knn(self, k: int, evals=False):
         """(r2_k, mass_k), (N,) float64 each in the caller's body order: the squared distance to the k-th nearest other

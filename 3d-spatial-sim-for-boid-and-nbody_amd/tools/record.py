@@ -536,6 +536,65 @@ def rotation_line(sim, frame: int, radii) -> str:
                        "phi": [float(x) for x in c["phi"]]}) + "\n"
 
 
+# ---- radial profile and Lagrangian radii (extra config key "profile") -----------------------
+PROFILE_FILE = "profile.jsonl"
+PROFILE_FRACTIONS = (0.1, 0.25, 0.5, 0.75, 0.9)
+
+
+def check_profile_edges(edges):
+    """The edges as a list of floats if nbmi_radial_profile can take them (ValueError otherwise): 2 .. 257 finite values,
+    the first >= 0, strictly increasing."""
+    e = np.asarray(edges, dtype=np.float64).reshape(-1)
+    if not 2 <= len(e) <= 257:
+        raise ValueError(f"need 2 .. 257 edges, got {len(e)}")
+    if not np.all(np.isfinite(e)) or e[0] < 0.0 or np.any(np.diff(e) <= 0.0):
+        raise ValueError("the edges must be finite, >= 0 and strictly increasing")
+    return [float(x) for x in e]
+
+
+def profile_config(config: dict):
+    """The "profile" key of a config, {"every": K, "edges": [e0, e1, ...], "fractions": [f0, ...]}, as (every, edges,
+    fractions); None without the key; ValueError for a malformed one."""
+    g = config.get("profile")
+    if not g:
+        return None
+    every = int(g.get("every", 0))
+    if every <= 0:
+        raise ValueError(f"--profile: K must be positive, not {every}")
+    try:
+        edges = check_profile_edges(g.get("edges"))
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"--profile-edges: {e}") from None
+    try:
+        fr = [float(x) for x in np.asarray(g.get("fractions", PROFILE_FRACTIONS), dtype=np.float64).reshape(-1)]
+    except (TypeError, ValueError):
+        fr = []
+    if not 1 <= len(fr) <= 64 or not all(np.isfinite(f) and 0.0 < f <= 1.0 for f in fr):
+        raise ValueError(f"--profile-fractions: need 1 .. 64 numbers in (0, 1], not {g.get('fractions')!r}")
+    return every, edges, fr
+
+
+def profile_line(sim, frame: int, edges, fractions) -> str:
+    """One JSON line (with its newline) for the radial structure of the state `sim` holds after `frame`, about its centre
+    of mass and relative to its velocity: per slot (the ball inside edges[0], then the shells) the bodies, the mass, the
+    density, the mean radial velocity, both dispersions and the anisotropy (null for an empty slot), and the Lagrangian
+    radii of `fractions` (nbody/profile.py)."""
+    from nbody import profile as prof
+    got = sim.radial_profile(edges, quantities=("number", "mass", "radial_momentum", "radial_kinetic", "kinetic"))
+    center = [float(x) for x in got["center"]]
+    rho, _ = prof.density_profile(got, edges)
+    vel = prof.velocity_profile(got)
+    radii = np.sqrt(sim.mass_radii(fractions, center=center)["radius2"])
+
+    def clean(a):
+        return [float(x) if np.isfinite(x) else None for x in a]
+    return json.dumps({"frame": frame, "center": center, "bulk_velocity": [float(x) for x in got["bulk_velocity"]],
+                       "edges": [float(e) for e in edges], "count": [int(c) for c in got["number"]],
+                       "mass": [float(x) for x in got["mass"]], "density": clean(rho), "mean_vr": clean(vel["mean_vr"]),
+                       "sigma_r": clean(vel["sigma_r"]), "sigma_t": clean(vel["sigma_t"]), "beta": clean(vel["beta"]),
+                       "fractions": [float(f) for f in fractions], "lagrangian_radii": clean(radii)}) + "\n"
+
+
 # ---- periodic side files: one description each, one mechanism for all (DESIGN.md section 4.17) -----------------------
 @dataclass(frozen=True)
 class LineStream:
@@ -571,8 +630,9 @@ GROUPS = LineStream(GROUPS_FILE, groups_config, groups_line, key="groups",
 PAIRS = LineStream(PAIRS_FILE, pairs_config, pairs_line, key="pairs",
                    auto=lambda sim, s: {"every": s[0], "edges": auto_pair_edges(sim.knn(1)[0])})
 ROTATION = LineStream(ROTATION_FILE, rotation_config, rotation_line)  # ("auto" radii need no state: build_config)
+PROFILE = LineStream(PROFILE_FILE, profile_config, profile_line)  # ("auto" edges need no state either)
 apply_groups, apply_pairs = GROUPS.apply, PAIRS.apply  # (gpu_sim, config, rec_dir=None) -> the config, "auto" resolved
-LINE_STREAMS = (DIAGNOSTICS, GROUPS, PAIRS, ROTATION)  # in the order of their lines after a frame; a new side file is one more entry
+LINE_STREAMS = (DIAGNOSTICS, GROUPS, PROFILE, PAIRS, ROTATION)  # in the order of their lines after a frame; a new side file is one more entry
 
 
 def line_due(frame: int, every: int) -> bool:
@@ -879,7 +939,7 @@ def record(config: dict, resume: bool = False, root: Path = None, quiet: bool = 
     say(f"[Record] GPU acceleration: {backend.value} - {info}")
     # extra config key "color": {"mode": "density", "k": K, "log10_range": [lo, hi]} = frames coloured by the k-NN
     # density through the unchanged colour and frame calls of both loops
-    # extra config keys "diagnostics_every", "groups", "pairs", "rotation_curve": every K-th frame a line in a side file (LINE_STREAMS)
+    # extra config keys "diagnostics_every", "groups", "profile", "pairs", "rotation_curve": every K-th frame a line in a side file (LINE_STREAMS)
     try:
         config = apply_color_mode(gpu_sim, config, rec_dir)
         for stream in LINE_STREAMS:
@@ -1046,6 +1106,21 @@ def show_status(session_name: str, root: Path = None) -> bool:
             last = rrows[-1]
             k = int(np.argmax(last["v_circ"]))
             print(f"    frame {last['frame']}: peak v_circ = {last['v_circ'][k]:.6g} at R = {last['radii'][k]:.6g}")
+    pf = meta.get("profile")
+    if pf:
+        edges = pf.get("edges") or [0.0]
+        print(f"  Profile: every {pf.get('every')} frames, {len(edges) - 1} shells from {edges[0]:.6g} to {edges[-1]:.6g}, "
+              f"{len(pf.get('fractions', PROFILE_FRACTIONS))} Lagrangian radii")
+        frows = read_diagnostics(rec_dir / PROFILE_FILE)
+        if frows:
+            last = frows[-1]
+            fr = [abs(f - 0.5) for f in last["fractions"]]
+            k = fr.index(min(fr))
+            central = next((x for x in last["density"] if x is not None), None)
+            half = last["lagrangian_radii"][k]
+            print(f"    frame {last['frame']}: r({last['fractions'][k]:.3g} M) = "
+                  + (f"{half:.6g}" if half is not None else "n/a") + ", central density = "
+                  + (f"{central:.6g}" if central is not None else "n/a"))
     tc = meta.get("tracers")
     if tc:
         try:
@@ -1101,7 +1176,7 @@ def build_parser():
                "--preset-id); --preset-id indexes this build's preset list (python -m tools.record --presets shows "
                "it); --dt sets dt_per_frame (the reference writes an unused 'dt' key); --presets, --seed, "
                "--device-ic, --diagnostics, --integrator, --multipole, --pipeline, --color, --density-k, --density-range, "
-               "--groups, --linking-length, --min-members, --pairs, --pair-edges, --rotation-curve, --curve-radii, --tracers, --tracers-every, "
+               "--groups, --linking-length, --min-members, --pairs, --pair-edges, --rotation-curve, --curve-radii, --profile, --profile-edges, --profile-fractions, --tracers, --tracers-every, "
                "--density-map, --map-pixels, --map-half-width, --map-axis and --root are "
                "additions.")
     ap.add_argument("session", nargs="?", help="session name (for --resume, --status or --extend)")
@@ -1160,6 +1235,15 @@ def build_parser():
                          "(stored in metadata.json as rotation_curve)")
     ap.add_argument("--curve-radii", type=str, default=None, metavar="auto|r0,r1,...",
                     help="1 .. 256 increasing radii (default auto: 16 radii, spawn_radius k / 16 for k = 1 .. 16)")
+    ap.add_argument("--profile", type=int, default=None, metavar="K",
+                    help="every K frames append the radial profile about the centre of mass (bodies, mass, density, mean "
+                         "radial velocity, dispersions and anisotropy per shell) and the Lagrangian radii to profile.jsonl "
+                         "(stored in metadata.json as profile)")
+    ap.add_argument("--profile-edges", type=str, default=None, metavar="auto|e0,e1,...",
+                    help="2 .. 257 increasing radii (default auto: 48 log-spaced shells from spawn_radius / 256 to "
+                         "4 spawn_radius)")
+    ap.add_argument("--profile-fractions", type=str, default=None, metavar="f0,f1,...",
+                    help="1 .. 64 mass fractions in (0, 1] for the Lagrangian radii (default 0.1,0.25,0.5,0.75,0.9)")
     ap.add_argument("--tracers", type=Path, default=None, metavar="FILE.npy",
                     help="massless tracers carried by the integrator: an array (m, 3) or (m, 6), rows x y z [vx vy vz] "
                          "(stored in metadata.json as tracers; state checkpoints carry them)")
@@ -1270,6 +1354,26 @@ def build_config(args) -> dict:
                 raise ValueError(f"--curve-radii: need auto or comma-separated numbers, not {cr!r}") from None
         config["rotation_curve"] = {"every": int(ck), "radii": radii}
         rotation_config(config)  # (a bad K or bad radii raise here)
+    fk, fe, ff = (getattr(args, a, None) for a in ("profile", "profile_edges", "profile_fractions"))
+    if fk is None and (fe is not None or ff is not None):
+        raise ValueError("--profile-edges and --profile-fractions need --profile K")
+    if fk is not None:  # the default writes no key
+        if fe is None or fe.strip().lower() == "auto":
+            from nbody.profile import auto_edges
+            edges = [float(x) for x in auto_edges(config["spawn_radius"])]
+        else:
+            try:
+                edges = [float(x) for x in fe.split(",")]
+            except ValueError:
+                raise ValueError(f"--profile-edges: need auto or comma-separated numbers, not {fe!r}") from None
+        fractions = list(PROFILE_FRACTIONS)
+        if ff is not None:
+            try:
+                fractions = [float(x) for x in ff.split(",")]
+            except ValueError:
+                raise ValueError(f"--profile-fractions: need comma-separated numbers, not {ff!r}") from None
+        config["profile"] = {"every": int(fk), "edges": edges, "fractions": fractions}
+        profile_config(config)  # (a bad K, bad edges or bad fractions raise here)
     tf, tk = (getattr(args, a, None) for a in ("tracers", "tracers_every"))
     if tf is None and tk is not None:
         raise ValueError("--tracers-every needs --tracers FILE.npy")

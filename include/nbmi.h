@@ -506,6 +506,85 @@ int nbmi_deposit(nbmi_sim *sim, const double lo[3], const double hi[3], const in
                  int quantities, double *out /* (P, dims[2], dims[1], dims[0]) C order */,
                  int64_t *stats3 /* may be NULL */, int32_t *exponents /* (P,), may be NULL */);
 
+/* ---- radial profiles and mass radii about a centre --------------------------------------------
+ * nbmi_deposit's spherical counterpart: sums of per-body quantities over the shells between nb + 1 radii about `center`,
+ * and the squared radii that hold given fractions of the mass (Lagrangian radii).  Masses are m, not G m; velocities are
+ * read as stored (see nbmi_deposit).  Both calls accept Barnes-Hut and direct handles, build no tree, refuse owner-mode
+ * handles and handles with a proper shard, wait for the work enqueued so far and report deferred errors as the getters
+ * do, and change nothing that a later step or query reads (the state and its order, the tree header, the precision flags,
+ * the step count, the stored leapfrog acceleration, the tracers).  With nbmi_enable_timers the device time of their
+ * kernels (without the copies) is added to "other".
+ *
+ * This text is the specification; the kernels and the tests' NumPy restatement (tests/profile_ref.py) both follow it.
+ * All arithmetic is float64 in the association written, without FMA contraction; sqrt and divide are correctly rounded.
+ *
+ * nbmi_radial_profile.  `quantities` selects the planes, in the order of the bits: P is their number (at most 8).
+ *   Edges.  1 <= nb <= 256; edges[0 .. nb] finite, edges[0] >= 0, strictly increasing; E[k] = edges[k] * edges[k], one
+ *     host product each, must again be finite and strictly increasing.
+ *   Per body.  r_a = x_a - center_a and w_a = v_a - bulk_velocity_a, one subtraction each (bulk_velocity == NULL: w = v
+ *     and no subtraction is made).  r2 = (rx rx + ry ry) + rz rz.  A body whose r2 is not finite is skipped: it is counted
+ *     in stats3[2] and takes no part in anything below, the maxima included.
+ *   Slot.  s = the number of k in 0 .. nb with E[k] < r2.  s == 0 is the inner ball r2 <= E[0] (with edges[0] == 0: the
+ *     bodies exactly at the centre); 1 <= s <= nb is the shell E[s-1] < r2 <= E[s], the upper edge belongs to the shell;
+ *     s == nb + 1 is beyond: the body contributes nothing and is counted in stats3[1].
+ *   Quantities.  rho = sqrt(r2);  vr = ((rx wx + ry wy) + rz wz) / rho, and vr = 0 when rho == 0;
+ *     w2 = (wx wx + wy wy) + wz wz.  The q of the planes are listed at the NBMI_PROFILE_ constants below; in
+ *     ANGULAR_MOMENTUM each product is rounded, then the difference, then the product by m.
+ *   Quantum of a plane (nbmi_deposit's rule).  mx = the maximum of |q_j| over all bodies that are not skipped, in a slot
+ *     or beyond.  mx == 0 (or N == 0): the plane is zeros and its exponent reads 0.  Otherwise, with frexp(mx) = (f, Ex)
+ *     and L = the bit length of N, e = Ex + L - 62.  exponents[p] = e.
+ *   Contribution and output.  k = (int64) rint(ldexp(q, -e)), ties to even; K[plane][slot] = the exact integer sum over
+ *     the bodies of the slot; out[plane][slot] = ldexp((double) K, e) for the slots 0 .. nb.  stats3 = {bodies in a slot,
+ *     bodies beyond, bodies skipped}; their sum is N.
+ *   Consequences (tested): the result does not depend on the order of the state rows, on the handle type or on how the
+ *   kernel aggregates; two calls give the same bits; the NUMBER plane holds exact counts and its sum equals stats3[0];
+ *   |out - exact sum of q| <= 0.5 * 2^e * (bodies of the slot) plus one rounding of the final conversion.
+ *   NBMI_ERR_ARG, message "nbmi_radial_profile: ...", before anything is launched and with `out` untouched: null center,
+ *   edges or out; a centre or bulk velocity that is not finite; nb outside 1 .. 256; a bad edge (the message names its
+ *   index and value); quantities equal to 0 or with unknown bits; the handles above.  After the pass over the maxima,
+ *   `out` still untouched: a selected plane whose maximum is not finite (the message names the plane).  N == 0 gives zeros.
+ *   Scratch: 16.5 KB on the device (8 maxima, 3 stats, 8 x 257 sums), allocated by the first call.
+ *   A workgroup adds its 2 048 bodies' integers into a table in LDS, one LDS atomic per body and plane, and the table
+ *   leaves as one global atomic per non-zero (slot, plane).  There is no environment knob: the alternative that was
+ *   measured, a wave summing its lanes of equal slot first, is scripts/experiments/profile_wave_sum.patch (DESIGN.md
+ *   section 4.26 has the A/B).
+ *
+ * nbmi_mass_radii.  r2 and the skip rule are as above; stats2 = {bodies taking part, bodies skipped}.
+ *   Mass quantum.  mx = the largest mass over all N bodies; with frexp(mx) = (f, Ex) and L = the bit length of N,
+ *     e = Ex + L - 53 (mx == 0 or N == 0: e = 0) and k_j = (int64) rint(ldexp(m_j, -e)), so that K_total = the sum of k_j
+ *     over the bodies taking part is < 2^53: it and every partial sum convert to float64 exactly.  *exponent = e.  This
+ *     quantum is deliberately NOT the profile's MASS plane's (e = Ex + L - 62): there the sums only have to fit int64,
+ *     here the threshold below is a float64 product with K_total, which must be exact in float64.
+ *   Selection.  1 <= nf <= 64 fractions, each finite with 0 < f <= 1, in any order, repeats allowed.  Per fraction
+ *     T = max(1, (int64) ceil(f * (double) K_total)), one product and one ceil.  radius2[f] = the smallest value R among
+ *     the r2 of the bodies taking part for which the sum of k_j over the bodies with r2_j <= R is >= T;  inside[f] = the
+ *     number of bodies taking part with r2_j <= R;  mass_inside[f] = ldexp((double) that sum, e);
+ *     *total_mass = ldexp((double) K_total, e).  Bodies of equal r2 enter together, so the result is unique whatever
+ *     order ties are met in.  K_total == 0 (N == 0, all masses below the quantum, nobody taking part): success with
+ *     radius2 = NaN, inside = 0, mass_inside = 0 and total_mass = 0.
+ *   NBMI_ERR_ARG, message "nbmi_mass_radii: ...", before anything is launched and with the outputs untouched: null center,
+ *   fractions or radius2; a centre that is not finite; nf outside 1 .. 64; a fraction outside (0, 1] or not finite; the
+ *   handles above.  After the pass over the masses, the outputs still untouched: a mass that is negative or not finite.
+ *   Device path: (bits of r2, row) pairs - a non-negative finite double orders as its bits, a skipped body gets a key
+ *   above all of them - through the library's radix sort, a segmented prefix sum of k in sorted order, and one test
+ *   "last of its tie run and C_prev_run < T <= C_run" per run and fraction.  Nothing of O(N) crosses to the host.
+ *   Scratch: 32 bytes per body (keys and rows in and out of the sort, k in sorted order), the sort's temp buffer for N
+ *   pairs (12 bytes per body and its status rows), 24 bytes per 2 048 bodies and 1.6 KB of results; allocated by the
+ *   first call (N is fixed), freed by nbmi_destroy. */
+#define NBMI_PROFILE_NUMBER 1            /* 1 plane:  q = 1                                           */
+#define NBMI_PROFILE_MASS 2              /* 1 plane:  q = m                                           */
+#define NBMI_PROFILE_RADIAL_MOMENTUM 4   /* 1 plane:  q = m * vr                                      */
+#define NBMI_PROFILE_RADIAL_KINETIC 8    /* 1 plane:  q = (m * vr) * vr                               */
+#define NBMI_PROFILE_KINETIC 16          /* 1 plane:  q = m * w2                                      */
+#define NBMI_PROFILE_ANGULAR_MOMENTUM 32 /* 3 planes: q = m * (ry wz - rz wy), m * (rz wx - rx wz), m * (rx wy - ry wx) */
+int nbmi_radial_profile(nbmi_sim *sim, const double center[3], const double bulk_velocity[3] /* NULL = 0 */, int nb,
+                        const double *edges /* nb+1 */, int quantities, double *out /* (P, nb+1) C order */,
+                        int64_t *stats3 /* may be NULL */, int32_t *exponents /* (P,), may be NULL */);
+int nbmi_mass_radii(nbmi_sim *sim, const double center[3], int nf, const double *fractions /* nf */,
+                    double *radius2 /* (nf,) */, int64_t *inside /* (nf,), may be NULL */,
+                    double *mass_inside /* (nf,), may be NULL */, double *total_mass /* may be NULL */,
+                    int64_t *stats2 /* may be NULL */, int32_t *exponent /* may be NULL */);
+
 /* Multi-GPU (one process per GPU).  A handle created with nbmi_create holds ALL bodies; with a
  * shard set, step() integrates only the key-sorted ranks [begin,end) (direct method: the body
  * indices [begin,end), its state is never re-ordered) and leaves the others untouched until
