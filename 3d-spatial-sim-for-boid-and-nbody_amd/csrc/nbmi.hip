@@ -4488,7 +4488,7 @@ __global__ __launch_bounds__(kBlock) void k_tracer_kick_drift(const TreeInfo *in
 // K20: grid deposit (nbmi_deposit; include/nbmi.h).  A scatter of fixed-point integers: every
 // (body, cell) contribution is rounded to a multiple of the plane's quantum 2^e and added with 64-bit integer atomics,
 // so the sum of a cell is one unique integer whatever the order and however the kernel combines contributions first.
-// k_deposit_max finds max |q| per plane (exact in any order; the bit pattern of a non-negative double orders as an
+// k_plane_max finds max |q| per plane (exact in any order; the bit pattern of a non-negative double orders as an
 // integer, and a NaN lies above +inf), the host turns it into e, k_deposit scatters, k_deposit_out converts in place.
 // ---------------------------------------------------------------------------------------
 constexpr int kDepPlanes = 6;      // NUMBER, MASS, MOMENTUM x 3, KINETIC
@@ -4507,41 +4507,44 @@ struct DepositArgs {
     long long cells;
 };
 
-// the six quantities of a body, as the header writes them (float64, no FMA), then the one a plane asks for
-struct DepQ { double q0, q1, q2, q3, q4, q5; };
-__device__ __forceinline__ DepQ dep_quantities(double m, double vx, double vy, double vz) {
-    DepQ q;
-    q.q0 = 1.0;
-    q.q1 = m;
-    q.q2 = __dmul_rn(m, vx);
-    q.q3 = __dmul_rn(m, vy);
-    q.q4 = __dmul_rn(m, vz);
-    q.q5 = __dmul_rn(m, __dadd_rn(__dadd_rn(__dmul_rn(vx, vx), __dmul_rn(vy, vy)), __dmul_rn(vz, vz)));
-    return q;
-}
-__device__ __forceinline__ double dep_select(const DepQ &q, int slot) {
-    return slot == 0 ? q.q0 : slot == 1 ? q.q1 : slot == 2 ? q.q2 : slot == 3 ? q.q3 : slot == 4 ? q.q4 : q.q5;
-}
+// ---- what every fixed-point sum over the state rows is made of (K20 and K26) ----
+// q -> its multiple of the plane's quantum 2^e, and a sum of those back
+__host__ __device__ __forceinline__ long long fx_quantise(double q, int e) { return (long long)rint(ldexp(q, -e)); }
+__host__ __device__ __forceinline__ double fx_value(unsigned long long K, int e) { return ldexp((double)(long long)K, e); }
 
-__global__ __launch_bounds__(kBlock) void k_deposit_max(Bodies cur, int64_t n, DepositArgs a,
-                                                        unsigned long long *__restrict__ out /* [kDepPlanes] */) {
+// The K quantities of a body, then the one a plane asks for.  A chain of uniform selects: nothing is indexed dynamically.
+template <int K>
+struct PlaneQ {
+    double q[K];
+    template <int T = 0>
+    __device__ __forceinline__ double select(int slot) const {
+        if constexpr (T == K - 1) return q[T];
+        else return slot == T ? q[T] : select<T + 1>(slot);
+    }
+};
+
+// Pass 1 of a sum: out[p] = the largest bit pattern of |q| of plane p.  `src` carries `planes` and `slot[]` and says
+// per body whether it takes part and what its quantities are: bool take(cur, i, q, out).
+template <int P, class Source>
+__global__ __launch_bounds__(kBlock) void k_plane_max(Bodies cur, int64_t n, Source src, unsigned long long *__restrict__ out /* [P] */) {
     __shared__ unsigned long long sh[kBlock];
-    unsigned long long mx[kDepPlanes];
+    unsigned long long mx[P];
 #pragma unroll
-    for (int p = 0; p < kDepPlanes; p++) mx[p] = 0ull;
+    for (int p = 0; p < P; p++) mx[p] = 0ull;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
-        const DepQ q = dep_quantities(cur.m[i], cur.vx[i], cur.vy[i], cur.vz[i]);
+        PlaneQ<P> q;
+        if (!src.take(cur, i, q, out)) continue;
 #pragma unroll
-        for (int p = 0; p < kDepPlanes; p++) {
-            if (p < a.planes) {
-                const unsigned long long b = (unsigned long long)__double_as_longlong(fabs(dep_select(q, a.slot[p])));
+        for (int p = 0; p < P; p++) {
+            if (p < src.planes) {
+                const unsigned long long b = (unsigned long long)__double_as_longlong(fabs(q.select(src.slot[p])));
                 mx[p] = b > mx[p] ? b : mx[p];
             }
         }
     }
 #pragma unroll
-    for (int p = 0; p < kDepPlanes; p++) {
-        if (p >= a.planes) break;
+    for (int p = 0; p < P; p++) {
+        if (p >= src.planes) break;
         sh[threadIdx.x] = mx[p];
         __syncthreads();
         for (int w = kBlock / 2; w > 0; w >>= 1) {
@@ -4552,6 +4555,34 @@ __global__ __launch_bounds__(kBlock) void k_deposit_max(Bodies cur, int64_t n, D
         __syncthreads();
     }
 }
+
+// The three counters of a main pass: per thread, then the workgroup's three LDS words (cleared before a barrier), then
+// one global atomic per non-zero word.  The barrier inside also ends the pass's LDS adds for the flush that follows.
+__device__ __forceinline__ void stats3_clear(unsigned int *sh) {
+    if (threadIdx.x < 3) sh[threadIdx.x] = 0u;
+}
+__device__ __forceinline__ void stats3_add(unsigned int *sh, unsigned long long *__restrict__ stats, unsigned int c0,
+                                           unsigned int c1, unsigned int c2) {
+    if (c0) atomicAdd(&sh[0], c0);
+    if (c1) atomicAdd(&sh[1], c1);
+    if (c2) atomicAdd(&sh[2], c2);
+    __syncthreads();
+    if (threadIdx.x < 3 && sh[threadIdx.x]) atomicAdd(&stats[threadIdx.x], (unsigned long long)sh[threadIdx.x]);
+}
+
+// the six quantities of a body, as the header writes them (float64, no FMA)
+using DepQ = PlaneQ<kDepPlanes>;
+__device__ __forceinline__ DepQ dep_quantities(double m, double vx, double vy, double vz) {
+    return DepQ{{1.0, m, __dmul_rn(m, vx), __dmul_rn(m, vy), __dmul_rn(m, vz),
+                 __dmul_rn(m, __dadd_rn(__dadd_rn(__dmul_rn(vx, vx), __dmul_rn(vy, vy)), __dmul_rn(vz, vz)))}};
+}
+// pass 1 of nbmi_deposit: every body takes part
+struct DepSource : DepositArgs {
+    __device__ __forceinline__ bool take(const Bodies &cur, int64_t i, DepQ &q, unsigned long long *) const {
+        q = dep_quantities(cur.m[i], cur.vx[i], cur.vy[i], cur.vz[i]);
+        return true;
+    }
+};
 
 // A body's cells and weights on one axis.  The range test is made on the floored double; an index is converted only
 // when it passed.
@@ -4595,7 +4626,7 @@ __global__ __launch_bounds__(kBlock) void k_deposit(Bodies cur, int64_t n, Depos
     __shared__ unsigned int sh_stats[3];
     unsigned long long *vals = dep_lds;
     int *keys = (int *)(dep_lds + (size_t)a.planes * kDepSlots);
-    if (threadIdx.x < 3) sh_stats[threadIdx.x] = 0u;
+    stats3_clear(sh_stats);
     if (AGG) {
         for (int t = threadIdx.x; t < kDepSlots; t += kBlock) keys[t] = -1;
         for (int t = threadIdx.x; t < a.planes * kDepSlots; t += kBlock) vals[t] = 0ull;
@@ -4619,7 +4650,7 @@ __global__ __launch_bounds__(kBlock) void k_deposit(Bodies cur, int64_t n, Depos
         const DepQ q = dep_quantities(cur.m[i], cur.vx[i], cur.vy[i], cur.vz[i]);
         double qp[kDepPlanes];
 #pragma unroll
-        for (int p = 0; p < kDepPlanes; p++) qp[p] = p < a.planes ? dep_select(q, a.slot[p]) : 0.0;
+        for (int p = 0; p < kDepPlanes; p++) qp[p] = p < a.planes ? q.select(a.slot[p]) : 0.0;
 #pragma unroll
         for (int c = 0; c < 8; c++) {
             const bool ok = ((c & 1) ? ax.ok1 : ax.ok0) && ((c & 2) ? ay.ok1 : ay.ok0) && ((c & 4) ? az.ok1 : az.ok0);
@@ -4643,18 +4674,14 @@ __global__ __launch_bounds__(kBlock) void k_deposit(Bodies cur, int64_t n, Depos
 #pragma unroll
             for (int p = 0; p < kDepPlanes; p++) {
                 if (p >= a.planes || !a.live[p]) continue;
-                const long long k = (long long)rint(ldexp(__dmul_rn(qp[p], w), -a.e[p]));
+                const long long k = fx_quantise(__dmul_rn(qp[p], w), a.e[p]);
                 if (k == 0) continue;
                 if (AGG && slot >= 0) atomicAdd(&vals[p * kDepSlots + slot], (unsigned long long)k);
                 else atomicAdd(&K[(long long)p * a.cells + cell], (unsigned long long)k);
             }
         }
     }
-    if (hit) atomicAdd(&sh_stats[0], hit);
-    if (contributions) atomicAdd(&sh_stats[1], contributions);
-    if (skipped) atomicAdd(&sh_stats[2], skipped);
-    __syncthreads();
-    if (threadIdx.x < 3 && sh_stats[threadIdx.x]) atomicAdd(&stats[threadIdx.x], (unsigned long long)sh_stats[threadIdx.x]);
+    stats3_add(sh_stats, stats, hit, contributions, skipped);
     if (AGG) {
         for (int t = threadIdx.x; t < kDepSlots; t += kBlock) {
             const int cell = keys[t];
@@ -4673,13 +4700,13 @@ __global__ __launch_bounds__(kBlock) void k_deposit_out(unsigned long long *__re
     if (i >= a.cells) return;
     for (int p = 0; p < a.planes; p++) {
         const long long j = (long long)p * a.cells + i;
-        K[j] = (unsigned long long)__double_as_longlong(ldexp((double)(long long)K[j], a.e[p]));
+        K[j] = (unsigned long long)__double_as_longlong(fx_value(K[j], a.e[p]));
     }
 }
 
 // ---------------------------------------------------------------------------------------
 // K26: radial profiles and mass radii about a centre (nbmi_radial_profile, nbmi_mass_radii; include/nbmi.h, DESIGN.md
-// section 4.26).  The profile is K20's scheme on a tiny dense table: k_profile_max finds max |q| per plane over the
+// section 4.26).  The profile is K20's scheme on a tiny dense table: k_plane_max finds max |q| per plane over the
 // bodies with a finite r2, the host turns it into e, k_profile adds the fixed-point integers per workgroup in LDS and
 // sends one global atomic per non-zero (slot, plane); the host converts the at most 8 x 257 sums.
 // ---------------------------------------------------------------------------------------
@@ -4711,7 +4738,7 @@ __device__ __forceinline__ ProfR prof_r(const Bodies &cur, int64_t i, const doub
     return r;
 }
 // the eight quantities of a body with a finite r2
-struct ProfQ { double q[kProfPlanes]; };
+using ProfQ = PlaneQ<kProfPlanes>;
 __device__ __forceinline__ ProfQ prof_quantities(const Bodies &cur, int64_t i, const ProfR &r, const ProfileArgs &a) {
     ProfQ q = {};
     q.q[0] = 1.0;
@@ -4740,44 +4767,15 @@ __device__ __forceinline__ ProfQ prof_quantities(const Bodies &cur, int64_t i, c
     }
     return q;
 }
-__device__ __forceinline__ double prof_select(const ProfQ &q, int slot) {
-    double v = q.q[0];
-#pragma unroll
-    for (int t = 1; t < kProfPlanes; t++) v = slot == t ? q.q[t] : v;
-    return v;
-}
-
-__global__ __launch_bounds__(kBlock) void k_profile_max(Bodies cur, int64_t n, ProfileArgs a,
-                                                        unsigned long long *__restrict__ out /* [kProfPlanes] */) {
-    __shared__ unsigned long long sh[kBlock];
-    unsigned long long mx[kProfPlanes];
-#pragma unroll
-    for (int p = 0; p < kProfPlanes; p++) mx[p] = 0ull;
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
-        const ProfR r = prof_r(cur, i, a.c);
-        if (!isfinite(r.r2)) continue;
-        const ProfQ q = prof_quantities(cur, i, r, a);
-#pragma unroll
-        for (int p = 0; p < kProfPlanes; p++) {
-            if (p < a.planes) {
-                const unsigned long long b = (unsigned long long)__double_as_longlong(fabs(prof_select(q, a.slot[p])));
-                mx[p] = b > mx[p] ? b : mx[p];
-            }
-        }
+// pass 1 of nbmi_radial_profile: the bodies with a finite r2 take part
+struct ProfSource : ProfileArgs {
+    __device__ __forceinline__ bool take(const Bodies &cur, int64_t i, ProfQ &q, unsigned long long *) const {
+        const ProfR r = prof_r(cur, i, c);
+        if (!isfinite(r.r2)) return false;
+        q = prof_quantities(cur, i, r, *this);
+        return true;
     }
-#pragma unroll
-    for (int p = 0; p < kProfPlanes; p++) {
-        if (p >= a.planes) break;
-        sh[threadIdx.x] = mx[p];
-        __syncthreads();
-        for (int w = kBlock / 2; w > 0; w >>= 1) {
-            if ((int)threadIdx.x < w) sh[threadIdx.x] = sh[threadIdx.x] > sh[threadIdx.x + w] ? sh[threadIdx.x] : sh[threadIdx.x + w];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0 && sh[0] != 0ull) atomicMax(&out[p], sh[0]);
-        __syncthreads();
-    }
-}
+};
 
 // One pass over the state rows.  Dynamic LDS: kProfEdgePad doubles (E, then +inf), then planes x (nb + 1) sums, plane
 // major.  The slot is the number of E[k] < r2, found by nine unconditional halvings.  One LDS atomic per (body, plane) -
@@ -4791,7 +4789,7 @@ __global__ __launch_bounds__(kBlock) void k_profile(Bodies cur, int64_t n, Profi
     double *E = (double *)prof_lds;
     unsigned long long *vals = prof_lds + kProfEdgePad;
     const int nslots = a.nb + 1;
-    if (threadIdx.x < 3) sh_stats[threadIdx.x] = 0u;
+    stats3_clear(sh_stats);
     for (int t = threadIdx.x; t < kProfEdgePad; t += kBlock) E[t] = t <= a.nb ? a.E[t] : __longlong_as_double(0x7ff0000000000000ll);
     for (int t = threadIdx.x; t < a.planes * nslots; t += kBlock) vals[t] = 0ull;
     __syncthreads();
@@ -4822,15 +4820,11 @@ __global__ __launch_bounds__(kBlock) void k_profile(Bodies cur, int64_t n, Profi
 #pragma unroll
         for (int p = 0; p < kProfPlanes; p++) {
             if (p >= a.planes || !a.live[p]) continue;  // (uniform)
-            const long long k = (long long)rint(ldexp(prof_select(q, a.slot[p]), -a.e[p]));
+            const long long k = fx_quantise(q.select(a.slot[p]), a.e[p]);
             if (k != 0ll) atomicAdd(&vals[p * nslots + slot], (unsigned long long)k);
         }
     }
-    if (inside) atomicAdd(&sh_stats[0], inside);
-    if (beyond) atomicAdd(&sh_stats[1], beyond);
-    if (skipped) atomicAdd(&sh_stats[2], skipped);
-    __syncthreads();
-    if (threadIdx.x < 3 && sh_stats[threadIdx.x]) atomicAdd(&stats[threadIdx.x], (unsigned long long)sh_stats[threadIdx.x]);
+    stats3_add(sh_stats, stats, inside, beyond, skipped);
     for (int t = threadIdx.x; t < a.planes * nslots; t += kBlock) {
         const unsigned long long v = vals[t];
         if (v) atomicAdd(&K[t], v);
@@ -4846,31 +4840,16 @@ struct MrArgs {
     long long T[kMrMaxFractions];
     long long tmin, tmax;
 };
-// res[0] = the largest mass's bits (of |m|), res[1] = 1 if a mass is negative
-__global__ __launch_bounds__(kBlock) void k_mr_mass_max(Bodies cur, int64_t n, unsigned long long *__restrict__ res) {
-    __shared__ unsigned long long sh[kBlock];
-    __shared__ unsigned int neg;
-    if (threadIdx.x == 0) neg = 0u;
-    unsigned long long mx = 0ull;
-    bool negative = false;
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
-        const double m = cur.m[i];
-        negative = negative || m < 0.0;
-        const unsigned long long b = (unsigned long long)__double_as_longlong(fabs(m));
-        mx = b > mx ? b : mx;
+// pass 1 of nbmi_mass_radii: every body, one plane, |m|.  res[0] = the largest mass's bits, res[1] = 1 if a mass is negative
+struct MrSource {
+    static constexpr int planes = 1;
+    static constexpr int slot[1] = {0};
+    __device__ __forceinline__ bool take(const Bodies &cur, int64_t i, PlaneQ<1> &q, unsigned long long *res) const {
+        q.q[0] = cur.m[i];
+        if (q.q[0] < 0.0) atomicMax(&res[1], 1ull);
+        return true;
     }
-    sh[threadIdx.x] = mx;
-    __syncthreads();
-    if (negative) neg = 1u;
-    for (int w = kBlock / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) sh[threadIdx.x] = sh[threadIdx.x] > sh[threadIdx.x + w] ? sh[threadIdx.x] : sh[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        if (sh[0] != 0ull) atomicMax(&res[0], sh[0]);
-        if (neg) atomicMax(&res[1], 1ull);
-    }
-}
+};
 // key = the bits of r2 (a non-negative finite double orders as its bits), kMrSkipKey for a body that is skipped
 __global__ __launch_bounds__(kBlock) void k_mr_keys(Bodies cur, int64_t n, double cx, double cy, double cz,
                                                     uint64_t *__restrict__ key, uint32_t *__restrict__ idx,
@@ -4899,7 +4878,7 @@ struct MrSegOp {
         return MrSeg{a.sum + b.sum, b.head ? b.run : a.run + b.run, a.head | b.head};
     }
 };
-// the entry of sorted position j: k = rint(ldexp(m, -e)) of its body (0 for a skipped body), head = it starts a tie run
+// the entry of sorted position j: k = fx_quantise(m, e) of its body (0 for a skipped body), head = it starts a tie run
 __device__ __forceinline__ MrSeg mr_entry(const uint64_t *__restrict__ key_s, const long long *__restrict__ kk, int64_t j) {
     const long long k = kk[j];
     return MrSeg{k, k, (j == 0 || key_s[j] != key_s[j - 1]) ? 1 : 0};
@@ -4915,7 +4894,7 @@ __global__ __launch_bounds__(scan::kBlock) void k_mr_tiles(Bodies cur, int64_t n
         const int64_t j = first + t;
         if (j >= n) break;
         const uint64_t key = key_s[j];
-        const long long k = key == kMrSkipKey ? 0ll : (long long)rint(ldexp(cur.m[idx_s[j]], -e));
+        const long long k = key == kMrSkipKey ? 0ll : fx_quantise(cur.m[idx_s[j]], e);
         kk[j] = k;
         acc = MrSegOp()(acc, MrSeg{k, k, (j == 0 || key != key_s[j - 1]) ? 1 : 0});
     }
@@ -6016,6 +5995,60 @@ int query_refuse(const nbmi_sim *s, const char *what) {
     return NBMI_ERR_ARG;
 }
 
+// ---- the host side of the fixed-point sums over the state rows (nbmi_deposit, nbmi_radial_profile, nbmi_mass_radii) ----
+// Which handles hold every body: every other is refused as `who`.
+int sums_refuse(nbmi_sim *s, const char *who) {
+    if (int rc = check_handle(s)) return rc;
+    const char *why = s->owner ? "owner-mode handles are not supported (the other ranks hold the rest of the bodies)"
+                      : s->shard_begin != 0 || s->shard_end != s->n ? "sharded handles are not supported"
+                                                                    : nullptr;
+    if (!why) return 0;
+    nbmi::set_error("%s: %s", who, why);
+    return NBMI_ERR_ARG;
+}
+// The exponent rule ("The quantum and its bound").  With max |q| in [2^(E-1), 2^E) and L the bit
+// length of N, the quantum 2^(E + L - headroom) keeps every |k| below 2^(headroom - L) and so any sum of N of them
+// below 2^headroom: 62 where a sum only has to fit a signed 64-bit word, 53 where (nbmi_mass_radii) every prefix sum
+// also has to be an exact double.  mx_bits = what k_plane_max wrote; a plane that is all zero gets e = 0 and live = 0.
+constexpr int kSumHeadroom = 62, kExactSumHeadroom = 53;
+int plane_exponents(const char *who, const unsigned long long *mx_bits, int64_t n, int headroom, int planes, const int *slot,
+                    const char *const *plane_name, int *e, int *live) {
+    const int L = 64 - __builtin_clzll((unsigned long long)n);  // the bit length of N
+    for (int p = 0; p < planes; p++) {
+        double mx;
+        memcpy(&mx, &mx_bits[p], sizeof(mx));
+        if (!isfinite(mx)) {
+            nbmi::set_error("%s: the largest |q| of plane %d (%s) is not finite", who, p, plane_name[slot[p]]);
+            return NBMI_ERR_ARG;
+        }
+        int E = 0;
+        if (mx != 0.0) (void)frexp(mx, &E);
+        live[p] = mx != 0.0;
+        e[p] = mx != 0.0 ? E + L - headroom : 0;
+    }
+    return 0;
+}
+// grid of k_plane_max
+int plane_max_blocks(int64_t n) { return (int)(nblocks(n) < 1024 ? nblocks(n) : 1024); }
+// The device time of a call's kernel groups, without its copies: begin() and end() bracket a group on the stream while
+// the timers are on (at most three per call), and add(), once the stream has been waited for, sums them into "other".
+struct TimedSpans {
+    nbmi_sim *s;
+    int spans = 0;
+    hipError_t begin() { return s->timers ? hipEventRecord(s->ev[2 * spans], s->stream) : hipSuccess; }
+    hipError_t end() { return s->timers ? hipEventRecord(s->ev[2 * spans++ + 1], s->stream) : hipSuccess; }
+    hipError_t add() {
+        double total = 0.0;
+        for (int k = 0; s->timers && k < spans; k++) {
+            float ms = 0.0f;
+            if (hipError_t err = hipEventElapsedTime(&ms, s->ev[2 * k], s->ev[2 * k + 1])) return err;
+            total += (double)ms;
+        }
+        s->ms[4] += total;
+        return hipSuccess;
+    }
+};
+
 }  // namespace
 
 // =========================================================================================
@@ -6931,15 +6964,7 @@ int nbmi_deposit(nbmi_sim *s, const double *lo, const double *hi, const int32_t 
                  double *out, int64_t *stats3, int32_t *exponents) {
     static const char *const kPlaneName[kDepPlanes] = {"NUMBER", "MASS", "MOMENTUM x", "MOMENTUM y", "MOMENTUM z", "KINETIC"};
     constexpr int64_t kDepMaxWords = (int64_t)1 << 28;
-    if (int rc = check_handle(s)) return rc;
-    if (s->owner) {
-        nbmi::set_error("nbmi_deposit: owner-mode handles are not supported (the other ranks hold the rest of the bodies)");
-        return NBMI_ERR_ARG;
-    }
-    if (s->shard_begin != 0 || s->shard_end != s->n) {
-        nbmi::set_error("nbmi_deposit: sharded handles are not supported");
-        return NBMI_ERR_ARG;
-    }
+    if (int rc = sums_refuse(s, "nbmi_deposit")) return rc;
     if (!lo || !hi || !dims || !out) {
         nbmi::set_error("nbmi_deposit: null %s", !lo ? "lo" : !hi ? "hi" : !dims ? "dims" : "out");
         return NBMI_ERR_ARG;
@@ -6952,7 +6977,7 @@ int nbmi_deposit(nbmi_sim *s, const double *lo, const double *hi, const int32_t 
         nbmi::set_error("nbmi_deposit: quantities = %d selects nothing or has unknown bits", quantities);
         return NBMI_ERR_ARG;
     }
-    DepositArgs a{};
+    DepSource a{};
     a.cells = 1;
     for (int k = 0; k < 3; k++) {
         if (!isfinite(lo[k]) || !isfinite(hi[k]) || !(hi[k] > lo[k])) {
@@ -6999,30 +7024,17 @@ int nbmi_deposit(nbmi_sim *s, const double *lo, const double *hi, const int32_t 
             s->dep.words = words;
         }
         const Bodies cur = s->buf[s->curbuf];
-        float ms = 0.0f, ms2 = 0.0f;
+        TimedSpans timed{s};
         NBMI_HIP_CHECK(hipMemsetAsync(s->dep.res, 0, sizeof(h), st));
-        if (s->timers) NBMI_HIP_CHECK(hipEventRecord(s->ev[0], st));
-        const int64_t want = nblocks(n);
-        k_deposit_max<<<(int)(want < 1024 ? want : 1024), kBlock, 0, st>>>(cur, n, a, s->dep.res);
+        NBMI_HIP_CHECK(timed.begin());
+        k_plane_max<kDepPlanes><<<plane_max_blocks(n), kBlock, 0, st>>>(cur, n, a, s->dep.res);
         NBMI_HIP_CHECK(hipGetLastError());
-        if (s->timers) NBMI_HIP_CHECK(hipEventRecord(s->ev[1], st));
+        NBMI_HIP_CHECK(timed.end());
         NBMI_HIP_CHECK(hipMemcpyAsync(h, s->dep.res, kDepPlanes * sizeof(h[0]), hipMemcpyDeviceToHost, st));
         NBMI_HIP_CHECK(hipStreamSynchronize(st));
-        const int L = 64 - __builtin_clzll((unsigned long long)n);  // the bit length of N
-        for (int p = 0; p < a.planes; p++) {
-            double mx;
-            memcpy(&mx, &h[p], sizeof(mx));
-            if (!isfinite(mx)) {
-                nbmi::set_error("nbmi_deposit: the largest |q| of plane %d (%s) is not finite", p, kPlaneName[a.slot[p]]);
-                return NBMI_ERR_ARG;
-            }
-            int E = 0;
-            if (mx != 0.0) (void)frexp(mx, &E);
-            a.live[p] = mx != 0.0;
-            a.e[p] = mx != 0.0 ? E + L - 62 : 0;
-        }
+        if (int rc = plane_exponents("nbmi_deposit", h, n, kSumHeadroom, a.planes, a.slot, kPlaneName, a.e, a.live)) return rc;
         NBMI_HIP_CHECK(hipMemsetAsync(s->dep.K, 0, (size_t)words * sizeof(unsigned long long), st));
-        if (s->timers) NBMI_HIP_CHECK(hipEventRecord(s->ev[2], st));
+        NBMI_HIP_CHECK(timed.begin());
         const int blocks = (int)((n + kBlock * kDepRows - 1) / (kBlock * kDepRows));
         if (s->deposit_agg) {
             const size_t lds = (size_t)kDepSlots * (a.planes * sizeof(unsigned long long) + sizeof(int));
@@ -7032,15 +7044,11 @@ int nbmi_deposit(nbmi_sim *s, const double *lo, const double *hi, const int32_t 
         }
         k_deposit_out<<<nblocks(a.cells), kBlock, 0, st>>>(s->dep.K, a);
         NBMI_HIP_CHECK(hipGetLastError());
-        if (s->timers) NBMI_HIP_CHECK(hipEventRecord(s->ev[3], st));
+        NBMI_HIP_CHECK(timed.end());
         NBMI_HIP_CHECK(hipMemcpyAsync(h + kDepPlanes, s->dep.res + kDepPlanes, 3 * sizeof(h[0]), hipMemcpyDeviceToHost, st));
         NBMI_HIP_CHECK(hipMemcpyAsync(out, s->dep.K, (size_t)words * sizeof(double), hipMemcpyDeviceToHost, st));
         NBMI_HIP_CHECK(hipStreamSynchronize(st));
-        if (s->timers) {  // the device time of the two passes, without the copies: "other"
-            NBMI_HIP_CHECK(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
-            NBMI_HIP_CHECK(hipEventElapsedTime(&ms2, s->ev[2], s->ev[3]));
-            s->ms[4] += (double)ms + (double)ms2;
-        }
+        NBMI_HIP_CHECK(timed.add());  // the two passes
     } else {
         for (int64_t i = 0; i < words; i++) out[i] = 0.0;
     }
@@ -7050,16 +7058,9 @@ int nbmi_deposit(nbmi_sim *s, const double *lo, const double *hi, const int32_t 
 }
 
 namespace {
-// what both calls of section 4.26 refuse as nbmi_deposit does, and the centre
+// what both calls of section 4.26 refuse: the handles that nbmi_deposit refuses, and a centre that is none
 int profile_refuse(nbmi_sim *s, const char *who, const double *center) {
-    if (s->owner) {
-        nbmi::set_error("%s: owner-mode handles are not supported (the other ranks hold the rest of the bodies)", who);
-        return NBMI_ERR_ARG;
-    }
-    if (s->shard_begin != 0 || s->shard_end != s->n) {
-        nbmi::set_error("%s: sharded handles are not supported", who);
-        return NBMI_ERR_ARG;
-    }
+    if (int rc = sums_refuse(s, who)) return rc;
     if (!center) {
         nbmi::set_error("%s: null center", who);
         return NBMI_ERR_ARG;
@@ -7079,7 +7080,6 @@ int nbmi_radial_profile(nbmi_sim *s, const double *center, const double *bulk_ve
     static const char *const kWho = "nbmi_radial_profile";
     static const char *const kPlaneName[kProfPlanes] = {"NUMBER", "MASS", "RADIAL_MOMENTUM", "RADIAL_KINETIC", "KINETIC",
                                                         "ANGULAR_MOMENTUM x", "ANGULAR_MOMENTUM y", "ANGULAR_MOMENTUM z"};
-    if (int rc = check_handle(s)) return rc;
     if (int rc = profile_refuse(s, kWho, center)) return rc;
     if (!edges || !out) {
         nbmi::set_error("%s: null %s", kWho, !edges ? "edges" : "out");
@@ -7099,7 +7099,7 @@ int nbmi_radial_profile(nbmi_sim *s, const double *center, const double *bulk_ve
         nbmi::set_error("%s: quantities = %d selects nothing or has unknown bits", kWho, quantities);
         return NBMI_ERR_ARG;
     }
-    ProfileArgs a{};
+    ProfSource a{};
     for (int k = 0; k <= nb; k++) {
         if (!isfinite(edges[k]) || edges[k] < 0.0 || (k > 0 && !(edges[k] > edges[k - 1]))) {
             nbmi::set_error("%s: edges[%d] = %g: the edges must be finite, >= 0 and strictly increasing", kWho, k, edges[k]);
@@ -7135,45 +7135,28 @@ int nbmi_radial_profile(nbmi_sim *s, const double *center, const double *bulk_ve
     if (n > 0) {
         if (!s->prof.res && dev_alloc(s, &s->prof.res, kRes + kProfPlanes * (kProfMaxBins + 1))) return NBMI_ERR_HIP;
         const Bodies cur = s->buf[s->curbuf];
-        float ms = 0.0f, ms2 = 0.0f;
+        TimedSpans timed{s};
         NBMI_HIP_CHECK(hipMemsetAsync(s->prof.res, 0, (size_t)(kRes + words) * sizeof(h[0]), st));
-        if (s->timers) NBMI_HIP_CHECK(hipEventRecord(s->ev[0], st));
-        const int64_t want = nblocks(n);
-        k_profile_max<<<(int)(want < 1024 ? want : 1024), kBlock, 0, st>>>(cur, n, a, s->prof.res);
+        NBMI_HIP_CHECK(timed.begin());
+        k_plane_max<kProfPlanes><<<plane_max_blocks(n), kBlock, 0, st>>>(cur, n, a, s->prof.res);
         NBMI_HIP_CHECK(hipGetLastError());
-        if (s->timers) NBMI_HIP_CHECK(hipEventRecord(s->ev[1], st));
+        NBMI_HIP_CHECK(timed.end());
         NBMI_HIP_CHECK(hipMemcpyAsync(h, s->prof.res, kProfPlanes * sizeof(h[0]), hipMemcpyDeviceToHost, st));
         NBMI_HIP_CHECK(hipStreamSynchronize(st));
-        const int L = 64 - __builtin_clzll((unsigned long long)n);  // the bit length of N
-        for (int p = 0; p < a.planes; p++) {
-            double mx;
-            memcpy(&mx, &h[p], sizeof(mx));
-            if (!isfinite(mx)) {
-                nbmi::set_error("%s: the largest |q| of plane %d (%s) is not finite", kWho, p, kPlaneName[a.slot[p]]);
-                return NBMI_ERR_ARG;
-            }
-            int E = 0;
-            if (mx != 0.0) (void)frexp(mx, &E);
-            a.live[p] = mx != 0.0;
-            a.e[p] = mx != 0.0 ? E + L - 62 : 0;
-        }
-        if (s->timers) NBMI_HIP_CHECK(hipEventRecord(s->ev[2], st));
+        if (int rc = plane_exponents(kWho, h, n, kSumHeadroom, a.planes, a.slot, kPlaneName, a.e, a.live)) return rc;
+        NBMI_HIP_CHECK(timed.begin());
         const int blocks = (int)((n + kBlock * kProfRows - 1) / (kBlock * kProfRows));
         const size_t lds = (size_t)(kProfEdgePad + words) * sizeof(unsigned long long);
         k_profile<<<blocks, kBlock, lds, st>>>(cur, n, a, s->prof.res + kRes, s->prof.res + kProfPlanes);
         NBMI_HIP_CHECK(hipGetLastError());
-        if (s->timers) NBMI_HIP_CHECK(hipEventRecord(s->ev[3], st));
+        NBMI_HIP_CHECK(timed.end());
         NBMI_HIP_CHECK(hipMemcpyAsync(h + kProfPlanes, s->prof.res + kProfPlanes, 3 * sizeof(h[0]), hipMemcpyDeviceToHost, st));
         NBMI_HIP_CHECK(hipMemcpyAsync(K.data(), s->prof.res + kRes, (size_t)words * sizeof(h[0]), hipMemcpyDeviceToHost, st));
         NBMI_HIP_CHECK(hipStreamSynchronize(st));
-        if (s->timers) {  // the device time of the two passes, without the copies: "other"
-            NBMI_HIP_CHECK(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
-            NBMI_HIP_CHECK(hipEventElapsedTime(&ms2, s->ev[2], s->ev[3]));
-            s->ms[4] += (double)ms + (double)ms2;
-        }
+        NBMI_HIP_CHECK(timed.add());  // the two passes
     }
     for (int p = 0; p < a.planes; p++)
-        for (int k = 0; k < nslots; k++) out[p * nslots + k] = ldexp((double)(long long)K[(size_t)p * nslots + k], a.e[p]);
+        for (int k = 0; k < nslots; k++) out[p * nslots + k] = fx_value(K[(size_t)p * nslots + k], a.e[p]);
     for (int p = 0; exponents && p < a.planes; p++) exponents[p] = a.e[p];
     for (int k = 0; stats3 && k < 3; k++) stats3[k] = (int64_t)h[kProfPlanes + k];
     return 0;
@@ -7182,7 +7165,6 @@ int nbmi_radial_profile(nbmi_sim *s, const double *center, const double *bulk_ve
 int nbmi_mass_radii(nbmi_sim *s, const double *center, int nf, const double *fractions, double *radius2, int64_t *inside,
                     double *mass_inside, double *total_mass, int64_t *stats2, int32_t *exponent) {
     static const char *const kWho = "nbmi_mass_radii";
-    if (int rc = check_handle(s)) return rc;
     if (int rc = profile_refuse(s, kWho, center)) return rc;
     if (!fractions || !radius2) {
         nbmi::set_error("%s: null %s", kWho, !fractions ? "fractions" : "radius2");
@@ -7222,45 +7204,33 @@ int nbmi_mass_radii(nbmi_sim *s, const double *center, int nf, const double *fra
             g.rows = n;
         }
         const Bodies cur = s->buf[s->curbuf];
-        float ms = 0.0f;
-        double total_ms = 0.0;
+        TimedSpans timed{s};
         NBMI_HIP_CHECK(hipMemsetAsync(g.res, 0, sizeof(h), st));
-        if (s->timers) NBMI_HIP_CHECK(hipEventRecord(s->ev[0], st));
-        const int64_t want = nblocks(n);
-        k_mr_mass_max<<<(int)(want < 1024 ? want : 1024), kBlock, 0, st>>>(cur, n, g.res);
+        NBMI_HIP_CHECK(timed.begin());
+        k_plane_max<1><<<plane_max_blocks(n), kBlock, 0, st>>>(cur, n, MrSource{}, g.res);
         k_mr_keys<<<nblocks(n), kBlock, 0, st>>>(cur, n, center[0], center[1], center[2], g.key, g.idx, g.res + 2);
         NBMI_HIP_CHECK(hipGetLastError());
-        if (s->timers) NBMI_HIP_CHECK(hipEventRecord(s->ev[1], st));
+        NBMI_HIP_CHECK(timed.end());
         NBMI_HIP_CHECK(hipMemcpyAsync(h, g.res, kRes * sizeof(h[0]), hipMemcpyDeviceToHost, st));
         NBMI_HIP_CHECK(hipStreamSynchronize(st));
-        if (s->timers) {
-            NBMI_HIP_CHECK(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
-            total_ms += (double)ms;
-        }
-        double mx;
-        memcpy(&mx, &h[0], sizeof(mx));
-        if (!isfinite(mx) || h[1]) {
-            nbmi::set_error("%s: a mass is %s", kWho, !isfinite(mx) ? "not finite" : "negative");
+        static const char *const kPlaneName[1] = {"MASS"};
+        int live = 0;
+        const int not_finite = plane_exponents(kWho, h, n, kExactSumHeadroom, 1, MrSource::slot, kPlaneName, &e, &live);
+        if (not_finite || h[1]) {
+            nbmi::set_error("%s: a mass is %s", kWho, not_finite ? "not finite" : "negative");
             return NBMI_ERR_ARG;
         }
-        if (mx != 0.0) {
-            int E = 0;
-            (void)frexp(mx, &E);
-            e = E + (64 - __builtin_clzll((unsigned long long)n)) - 53;
+        if (live) {
             const int64_t ntiles = scan::tiles_for(n);
             MrSeg total{};
-            if (s->timers) NBMI_HIP_CHECK(hipEventRecord(s->ev[2], st));
+            NBMI_HIP_CHECK(timed.begin());
             NBMI_HIP_CHECK(nbmi::radix_sort_pairs_u64(g.sort_tmp, g.sort_bytes, g.key, g.key_s, g.idx, g.idx_s, (size_t)n, 0, 63, st));
             k_mr_tiles<<<(int)ntiles, scan::kBlock, 0, st>>>(cur, n, g.key_s, g.idx_s, e, g.kk, g.tiles);
             scan::k_scan_values<<<1, scan::kScanThreads, 0, st>>>(g.tiles, g.tiles, ntiles, (int64_t)0, MrSeg{0ll, 0ll, 0}, MrSegOp());
             NBMI_HIP_CHECK(hipGetLastError());
-            if (s->timers) NBMI_HIP_CHECK(hipEventRecord(s->ev[3], st));
+            NBMI_HIP_CHECK(timed.end());
             NBMI_HIP_CHECK(hipMemcpyAsync(&total, g.tiles + ntiles, sizeof(total), hipMemcpyDeviceToHost, st));
             NBMI_HIP_CHECK(hipStreamSynchronize(st));
-            if (s->timers) {
-                NBMI_HIP_CHECK(hipEventElapsedTime(&ms, s->ev[2], s->ev[3]));
-                total_ms += (double)ms;
-            }
             k_total = total.sum;
             if (k_total > 0) {
                 MrArgs a{};
@@ -7272,10 +7242,10 @@ int nbmi_mass_radii(nbmi_sim *s, const double *center, int nf, const double *fra
                     a.tmin = f == 0 || a.T[f] < a.tmin ? a.T[f] : a.tmin;
                     a.tmax = f == 0 || a.T[f] > a.tmax ? a.T[f] : a.tmax;
                 }
-                if (s->timers) NBMI_HIP_CHECK(hipEventRecord(s->ev[4], st));
+                NBMI_HIP_CHECK(timed.begin());
                 k_mr_select<<<(int)ntiles, scan::kBlock, 0, st>>>(n, g.key_s, g.kk, g.tiles, a, g.res + kRes);
                 NBMI_HIP_CHECK(hipGetLastError());
-                if (s->timers) NBMI_HIP_CHECK(hipEventRecord(s->ev[5], st));
+                NBMI_HIP_CHECK(timed.end());
                 NBMI_HIP_CHECK(hipMemcpyAsync(h + kRes, g.res + kRes, (size_t)3 * nf * sizeof(h[0]), hipMemcpyDeviceToHost, st));
             }
             unsigned sort_err = 0u;
@@ -7287,12 +7257,8 @@ int nbmi_mass_radii(nbmi_sim *s, const double *center, int nf, const double *fra
                 nbmi::set_error("%s: the sort of the squared radii failed", kWho);
                 return NBMI_ERR_HIP;
             }
-            if (s->timers && k_total > 0) {
-                NBMI_HIP_CHECK(hipEventElapsedTime(&ms, s->ev[4], s->ev[5]));
-                total_ms += (double)ms;
-            }
         }
-        if (s->timers) s->ms[4] += total_ms;  // the device time of the call's kernels, without its copies: "other"
+        NBMI_HIP_CHECK(timed.add());  // the call's kernels
     }
     for (int f = 0; f < nf; f++) {
         if (k_total > 0) {
@@ -7301,9 +7267,9 @@ int nbmi_mass_radii(nbmi_sim *s, const double *center, int nf, const double *fra
             radius2[f] = NAN;
         }
         if (inside) inside[f] = k_total > 0 ? (int64_t)h[kRes + 3 * f + 1] : 0;
-        if (mass_inside) mass_inside[f] = k_total > 0 ? ldexp((double)(long long)h[kRes + 3 * f + 2], e) : 0.0;
+        if (mass_inside) mass_inside[f] = k_total > 0 ? fx_value(h[kRes + 3 * f + 2], e) : 0.0;
     }
-    if (total_mass) *total_mass = ldexp((double)k_total, e);
+    if (total_mass) *total_mass = fx_value((unsigned long long)k_total, e);
     if (stats2) {
         stats2[0] = n - (int64_t)h[2];
         stats2[1] = (int64_t)h[2];

@@ -110,6 +110,36 @@ def _as_f64(a, shape_tail):
     return a
 
 
+# What deposit() and radial_profile() share: the named quantities of a fixed-point sum over the state
+def _sum_names(what, quantities, table):
+    """The chosen names of ``table`` (name -> bit) in the library's plane order; ValueError for none or an unknown one."""
+    if isinstance(quantities, str):
+        quantities = (quantities,)
+    unknown = [q for q in quantities if q not in table]
+    if unknown or not quantities:
+        raise ValueError(f"{what}: quantities must be some of {list(table)}, not {list(quantities)}")
+    return [q for q in table if q in quantities]
+
+
+def _sum_planes(names, table, vector, shape, stats, extra, call):
+    """Allocates one float64 plane of ``shape`` per name (three for ``vector``), runs ``call(bits, out, st, ex)`` on their
+    pointers and returns the result dict: a plane per name, ``extra``, "exponents" and, with ``stats``, "stats"."""
+    width = {q: 3 if q == vector else 1 for q in names}
+    planes = sum(width.values())
+    out = np.zeros((planes,) + tuple(shape), dtype=np.float64)
+    st = np.zeros(3, dtype=np.int64)
+    ex = np.zeros(planes, dtype=np.int32)
+    call(sum(table[q] for q in names), _nat.ptr(out), _nat.ptr(st), _nat.ptr(ex))
+    res, p = {}, 0
+    for q in names:
+        res[q] = out[p:p + 3] if q == vector else out[p]
+        p += width[q]
+    res.update(extra, exponents=ex)
+    if stats:
+        res["stats"] = tuple(int(x) for x in st)
+    return res
+
+
 @dataclass(frozen=True)
 class Diagnostics:
     """Conserved quantities of a handle's current float64 state (include/nbmi.h, nbmi_diagnostics).
@@ -386,11 +416,7 @@ class _HIPSimulation:
         what the next step computes."""
         what = "deposit"
         self._query_refuse(what, tree=False)
-        if isinstance(quantities, str):
-            quantities = (quantities,)
-        unknown = [q for q in quantities if q not in DEPOSIT_QUANTITIES]
-        if unknown or not quantities:
-            raise ValueError(f"{what}: quantities must be some of {list(DEPOSIT_QUANTITIES)}, not {list(quantities)}")
+        names = _sum_names(what, quantities, DEPOSIT_QUANTITIES)
         if scheme not in DEPOSIT_SCHEMES:
             raise ValueError(f"{what}: scheme must be one of {list(DEPOSIT_SCHEMES)}, not {scheme!r}")
         lo_, hi_ = (np.ascontiguousarray(a, dtype=np.float64).reshape(-1) for a in (lo, hi))
@@ -399,23 +425,10 @@ class _HIPSimulation:
             raise ValueError(f"{what}: lo, hi and dims must have three entries each")
         if (d < 1).any() or int(d.max()) > 1 << 28 or int(d[0]) * int(d[1]) * int(d[2]) > 1 << 28:
             raise ValueError(f"{what}: dims {d.tolist()} must be >= 1 with at most 2^28 values in all planes")
-        names = [q for q in DEPOSIT_QUANTITIES if q in quantities]  # the library's plane order
-        bits = sum(DEPOSIT_QUANTITIES[q] for q in names)
-        planes = sum(3 if q == "momentum" else 1 for q in names)
         d32 = d.astype(np.int32)
-        out = np.zeros((planes, int(d[2]), int(d[1]), int(d[0])), dtype=np.float64)
-        st = np.zeros(3, dtype=np.int64)
-        ex = np.zeros(planes, dtype=np.int32)
-        self._query_call(what, self._lib.nbmi_deposit(self._h, _nat.ptr(lo_), _nat.ptr(hi_), _nat.ptr(d32),
-                                                    DEPOSIT_SCHEMES[scheme], bits, _nat.ptr(out), _nat.ptr(st), _nat.ptr(ex)))
-        res, p = {}, 0
-        for q in names:
-            res[q] = out[p:p + 3] if q == "momentum" else out[p]
-            p += 3 if q == "momentum" else 1
-        res["exponents"] = ex
-        if stats:
-            res["stats"] = tuple(int(x) for x in st)
-        return res
+        return _sum_planes(names, DEPOSIT_QUANTITIES, "momentum", (int(d[2]), int(d[1]), int(d[0])), stats, {},
+                           lambda bits, out, st, ex: self._query_call(what, self._lib.nbmi_deposit(
+                               self._h, _nat.ptr(lo_), _nat.ptr(hi_), _nat.ptr(d32), DEPOSIT_SCHEMES[scheme], bits, out, st, ex)))
 
     # ---- radial profiles and mass radii (include/nbmi.h nbmi_radial_profile; nbody/profile.py) ----
     def _profile_center(self, what, center, bulk_velocity):
@@ -456,31 +469,14 @@ class _HIPSimulation:
         owner-mode and sharded handles.  The call does not change what the next step computes."""
         what = "radial_profile"
         self._query_refuse(what, tree=False)
-        if isinstance(quantities, str):
-            quantities = (quantities,)
-        unknown = [q for q in quantities if q not in PROFILE_QUANTITIES]
-        if unknown or not quantities:
-            raise ValueError(f"{what}: quantities must be some of {list(PROFILE_QUANTITIES)}, not {list(quantities)}")
+        names = _sum_names(what, quantities, PROFILE_QUANTITIES)
         e = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
         if len(e) < 2 or len(e) > 257:
             raise ValueError(f"{what}: expected 2 .. 257 edges, got {len(e)}")
         c, b = self._profile_center(what, center, bulk_velocity)
-        names = [q for q in PROFILE_QUANTITIES if q in quantities]  # the library's plane order
-        bits = sum(PROFILE_QUANTITIES[q] for q in names)
-        planes = sum(3 if q == "angular_momentum" else 1 for q in names)
-        out = np.zeros((planes, len(e)), dtype=np.float64)
-        st = np.zeros(3, dtype=np.int64)
-        ex = np.zeros(planes, dtype=np.int32)
-        self._query_call(what, self._lib.nbmi_radial_profile(self._h, _nat.ptr(c), _nat.ptr(b), len(e) - 1, _nat.ptr(e), bits,
-                                                           _nat.ptr(out), _nat.ptr(st), _nat.ptr(ex)))
-        res, p = {}, 0
-        for q in names:
-            res[q] = out[p:p + 3] if q == "angular_momentum" else out[p]
-            p += 3 if q == "angular_momentum" else 1
-        res["center"], res["bulk_velocity"], res["exponents"] = c, b, ex
-        if stats:
-            res["stats"] = tuple(int(x) for x in st)
-        return res
+        return _sum_planes(names, PROFILE_QUANTITIES, "angular_momentum", (len(e),), stats, {"center": c, "bulk_velocity": b},
+                           lambda bits, out, st, ex: self._query_call(what, self._lib.nbmi_radial_profile(
+                               self._h, _nat.ptr(c), _nat.ptr(b), len(e) - 1, _nat.ptr(e), bits, out, st, ex)))
 
     def mass_radii(self, fractions, center="com"):
         """The squared radii about ``center`` (as in ``radial_profile``) that hold the given ``fractions`` (each in

@@ -1,15 +1,19 @@
-"""Are the kernels of csrc/bdmi.hip the same instructions in two source trees?  (the walled, noise-free
-sweep against the commit before the periodic box.)  Needs hipcc and c++filt, no GPU.
+"""Are the kernels of one file of csrc/ the same instructions in two source trees?  (the walled, noise-free
+sweep against the commit before the periodic box; 4.20: the state sums against the commit before their shared pieces.)
+Needs hipcc and c++filt, no GPU.
 
     git worktree add /tmp/parent <commit>
-    python scripts/compare_kernel_asm.py /tmp/parent . [kernel name fragments ...]
+    python scripts/compare_kernel_asm.py [--file nbmi.hip] [--pair OLD=NEW ...] /tmp/parent . [kernel name fragments ...]
 
-Each tree's bdmi.hip is compiled to device assembly for gfx950 with the Makefile's flags.  Kernels are matched by their
+Each tree's file (bdmi.hip unless --file names another) is compiled to device assembly for gfx950 with the Makefile's
+flags.  --pair compares kernel OLD of the first tree with kernel NEW of the second, both written as this script prints
+names (--pair 'k_deposit_max=k_plane_max<6, DepSource>').  Otherwise kernels are matched by their
 demangled name up to the argument list, with the template arguments this tree added for the walled, noise-free instances
 (", GridP, FlockP" / ", GridP" / ", FsBox" / "<GridP>") dropped, so k_flock<true> of the old tree meets
 k_flock<true, GridP, FlockP> of the new one, k_fs_link meets k_fs_link<GridP> and k_fs_chunks<1> meets k_fs_chunks<1, FsBox>.  Compared: the instruction lines, with symbol names and block labels normalised, and the register, LDS and scratch
 figures of the kernel descriptor.  Exit status 1 if a kernel present in both trees differs.
 """
+import argparse
 import os
 import re
 import subprocess
@@ -22,10 +26,10 @@ FACTS = ("next_free_vgpr", "next_free_sgpr", "group_segment_fixed_size", "privat
 ANON = "(anonymous namespace)::"
 
 
-def kernels(tree, tmp, tag):
+def kernels(tree, tmp, tag, file):
     out = os.path.join(tmp, tag + ".s")
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    subprocess.run([hipcc, *FLAGS, "-o", out, os.path.join(tree, PKG, "csrc", "bdmi.hip")], check=True,
+    subprocess.run([hipcc, *FLAGS, "-o", out, os.path.join(tree, PKG, "csrc", file)], check=True,
                    stderr=subprocess.DEVNULL)
     text = open(out).read()
     found = {m.group(1): m.group(2)
@@ -55,10 +59,19 @@ def facts(body):
 
 
 def main(argv):
-    if len(argv) < 2:
-        raise SystemExit(__doc__)
+    ap = argparse.ArgumentParser(usage=__doc__)
+    ap.add_argument("--file", default="bdmi.hip")
+    ap.add_argument("--pair", action="append", default=[], metavar="OLD=NEW")
+    ap.add_argument("trees", nargs=2)
+    ap.add_argument("fragments", nargs="*")
+    opt = ap.parse_args(argv)
+    argv = opt.trees + opt.fragments
     with tempfile.TemporaryDirectory() as tmp:
-        a, b = kernels(argv[0], tmp, "a"), kernels(argv[1], tmp, "b")
+        a, b = kernels(argv[0], tmp, "a", opt.file), kernels(argv[1], tmp, "b", opt.file)
+    for old, new in (p.split("=", 1) for p in opt.pair):
+        if old not in a or new not in b:
+            raise SystemExit(f"--pair {old}={new}: no kernel {old} in {argv[0]} or no {new} in {argv[1]}")
+        a[new] = a.pop(old)
     differ = 0
     for name in sorted(set(a) & set(b)):
         if argv[2:] and not any(f in name for f in argv[2:]):
