@@ -3208,12 +3208,27 @@ __global__ void k_copy_ids(const int32_t *__restrict__ ids, int32_t *__restrict_
 // second-order terms, with u = dist_sq and the cell's float64 second moments P = quad[9 idx + 3 .. 9 idx + 8]
 // (k_quad_level), in a scope of their own:
 //   phi += 1/2 [tr P u^-3/2 - 3 (d^T P d) u^-5/2],   a += [7.5 (d^T P d) u^-7/2 - 1.5 tr P u^-5/2] d - 3 u^-5/2 P d.
+// kTidal (nbmi_tidal_at / nbmi_get_tidal_f64, K27): the lane carries the six sums of the tidal
+// tensor T = da/dx and the term count, and neither the acceleration nor phi (kAcc is false); the result is a TidalSum.
+// With w = G M / (dist u), w5 = (3 w) / u an applied node adds  T_aa += (d_a d_a) w5 - w,  T_ab += (d_a d_b) w5;  an
+// applied internal cell in quadrupole mode, with g = P d, q = d^T P d, i7 = i5 / u, i9 = i7 / u,
+//   A = 1.5 tr i5 - 7.5 q i7,  B = 52.5 q i9 - 7.5 tr i7,  C = 3 i5,  D = 15 i7:
+//   T_ab += ((A delta_ab + B (d_a d_b)) + C P_ab) - D (g_a d_b + d_a g_b).
+// Without kTidal none of it is instantiated: the other walks are the code they were.
 struct FieldSum {
     double ax, ay, az, phi;
     int32_t terms;
 };
-template <bool kQuad, bool kAcc, bool kWiden>
-__device__ __forceinline__ FieldSum field_walk(const Node *__restrict__ nodes, const double4 *__restrict__ pot, const TreeInfo *info,
+struct TidalSum {
+    double xx, yy, zz, xy, xz, yz;
+    int32_t terms;
+};
+template <bool kTidal>
+struct WalkSum { using type = FieldSum; };
+template <>
+struct WalkSum<true> { using type = TidalSum; };
+template <bool kQuad, bool kAcc, bool kWiden, bool kTidal = false>
+__device__ __forceinline__ typename WalkSum<kTidal>::type field_walk(const Node *__restrict__ nodes, const double4 *__restrict__ pot, const TreeInfo *info,
                                                const Body64 &b64, double qx, double qy, double qz, float px, float py, float pz,
                                                bool valid, float eps2f, double eps, double pmax,
                                                const double *__restrict__ quad) {
@@ -3236,7 +3251,9 @@ __device__ __forceinline__ FieldSum field_walk(const Node *__restrict__ nodes, c
         near2 = eps2f + (float)(r * r);
     }
     unsigned resume = valid ? 0u : 0xffffffffu;
+    static_assert(!(kTidal && kAcc), "the tidal walk carries no acceleration");
     double ax = 0.0, ay = 0.0, az = 0.0, phi = 0.0;
+    double txx = 0.0, tyy = 0.0, tzz = 0.0, txy = 0.0, txz = 0.0, tyz = 0.0;  // (kTidal only)
     int32_t terms = 0;
     unsigned off = 0u;
     while (off < nn) {
@@ -3258,11 +3275,16 @@ __device__ __forceinline__ FieldSum field_walk(const Node *__restrict__ nodes, c
             const double d2 = ex * ex + ey * ey + ez * ez + eps2;  // (-ffp-contract=off: the reference's roundings)
             if (q.w > 0.0 && d2 > eps2) {
                 const double dist = sqrt(d2);
-                phi -= q.w / dist;
+                if (!kTidal) phi -= q.w / dist;
                 terms++;
                 if (kAcc) {
                     const double w = q.w / (dist * d2);
                     ax += ex * w; ay += ey * w; az += ez * w;
+                }
+                if (kTidal) {
+                    const double w = q.w / (dist * d2), w5 = (3.0 * w) / d2;
+                    txx += (ex * ex) * w5 - w; tyy += (ey * ey) * w5 - w; tzz += (ez * ez) * w5 - w;
+                    txy += (ex * ey) * w5; txz += (ex * ez) * w5; tyz += (ey * ez) * w5;
                 }
                 if (kQuad && nd.next_off != off + kNodeBytes) {  // an internal cell
                     const double *pq = quad + 9 * (size_t)idx + 3;
@@ -3270,7 +3292,20 @@ __device__ __forceinline__ FieldSum field_walk(const Node *__restrict__ nodes, c
                     const double dpd = ex * (pxx * ex + 2.0 * (pxy * ey + pxz * ez)) + ey * (pyy * ey + 2.0 * (pyz * ez)) + ez * (pzz * ez);
                     const double tr = pxx + pyy + pzz;
                     const double i1 = 1.0 / dist, i3 = i1 / d2, i5 = i3 / d2;
-                    phi += 0.5 * (tr * i3 - 3.0 * dpd * i5);
+                    if (!kTidal) phi += 0.5 * (tr * i3 - 3.0 * dpd * i5);
+                    if (kTidal) {
+                        const double gx = pxx * ex + pxy * ey + pxz * ez, gy = pxy * ex + pyy * ey + pyz * ez;
+                        const double gz = pxz * ex + pyz * ey + pzz * ez;
+                        const double i7 = i5 / d2, i9 = i7 / d2;
+                        const double A = 1.5 * tr * i5 - 7.5 * dpd * i7, B = 52.5 * dpd * i9 - 7.5 * tr * i7;
+                        const double Cc = 3.0 * i5, D = 15.0 * i7;
+                        txx += ((A + B * (ex * ex)) + Cc * pxx) - D * (gx * ex + ex * gx);
+                        tyy += ((A + B * (ey * ey)) + Cc * pyy) - D * (gy * ey + ey * gy);
+                        tzz += ((A + B * (ez * ez)) + Cc * pzz) - D * (gz * ez + ez * gz);
+                        txy += (B * (ex * ey) + Cc * pxy) - D * (gx * ey + ex * gy);
+                        txz += (B * (ex * ez) + Cc * pxz) - D * (gx * ez + ex * gz);
+                        tyz += (B * (ey * ez) + Cc * pyz) - D * (gy * ez + ey * gz);
+                    }
                     if (kAcc) {
                         const double sc = 7.5 * dpd * (i5 / d2) - 1.5 * tr * i5, t3 = 3.0 * i5;
                         ax += sc * ex - t3 * (pxx * ex + pxy * ey + pxz * ez);
@@ -3282,7 +3317,8 @@ __device__ __forceinline__ FieldSum field_walk(const Node *__restrict__ nodes, c
         }
         off = next;
     }
-    return FieldSum{ax, ay, az, phi, terms};
+    if constexpr (kTidal) return TidalSum{txx, tyy, tzz, txy, txz, tyz, terms};
+    else return FieldSum{ax, ay, az, phi, terms};
 }
 
 // Tree potential: the probe walk with a body in the lane - the build's band, phi and the term count only.  Both land at
@@ -4370,6 +4406,107 @@ __global__ __launch_bounds__(kBlock) void k_field_direct(Bodies cur, int64_t n, 
 }
 
 // ---------------------------------------------------------------------------------------
+// K27: the tidal tensor T_ab = da_a/dx_b at points and at the bodies (nbmi_tidal_at / nbmi_get_tidal_f64; include/nbmi.h,
+// DESIGN.md section 4.27).  The probe walk's tidal instantiation (field_walk<.., kTidal>) under K19's and K14's two lane
+// setups; rows are {Txx, Tyy, Tzz, Txy, Txz, Tyz}.
+// ---------------------------------------------------------------------------------------
+__device__ __forceinline__ void tidal_store(double *__restrict__ out, int64_t o, const TidalSum &f) {
+    double *r = out + 6 * o;
+    r[0] = f.xx; r[1] = f.yy; r[2] = f.zz; r[3] = f.xy; r[4] = f.xz; r[5] = f.yz;
+}
+// The Frobenius norm of a row, in the header's association.
+__device__ __forceinline__ double tidal_norm(const TidalSum &f) {
+    return sqrt(((f.xx * f.xx + f.yy * f.yy) + f.zz * f.zz) + 2.0 * ((f.xy * f.xy + f.xz * f.xz) + f.yz * f.yz));
+}
+
+// k_field_tree's twin: one chunk of probes, results at the probe's row of the chunk.
+template <bool kQuad>
+__global__ __launch_bounds__(kBlock) void k_tidal_tree(const Node *__restrict__ nodes, const double4 *__restrict__ pot,
+                                                       const WalkTable *tab, const TreeInfo *info,
+                                                       const double *__restrict__ sx, const double *__restrict__ sy,
+                                                       const double *__restrict__ sz, const uint32_t *__restrict__ order, int64_t m,
+                                                       float eps2f, double eps, double pmax, const double *__restrict__ quad,
+                                                       double *__restrict__ t6_out, int32_t *__restrict__ cnt_out) {
+    if (info->error != 0 || info->sticky_error != 0) return;  // the tree did not fit: the caller reports it
+    const int64_t rank = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const bool valid = rank < m;
+    double qx = 0.0, qy = 0.0, qz = 0.0;
+    if (valid) { qx = sx[rank]; qy = sy[rank]; qz = sz[rank]; }
+    const TidalSum f = field_walk<kQuad, false, true, true>(nodes, pot, info, Body64{tab, 0, (uint32_t)(valid ? rank : 0)}, qx, qy, qz,
+                                                            (float)qx, (float)qy, (float)qz, valid, eps2f, eps, pmax, quad);
+    if (valid) {
+        const int64_t o = order ? (int64_t)order[rank] : rank;
+        if (t6_out) tidal_store(t6_out, o, f);
+        if (cnt_out) cnt_out[o] = f.terms;
+    }
+}
+
+// k_potential_tree's twin: a body in the lane, the build's band.  Rows land in the caller's order, id[j] (either output
+// may be null).
+template <bool kQuad>
+__global__ __launch_bounds__(kBlock) void k_tidal_bodies(const Node *__restrict__ nodes, const double4 *__restrict__ pot,
+                                                         const WalkTable *tab, const TreeInfo *info,
+                                                         const float4 *__restrict__ posm_s, const uint32_t *__restrict__ perm,
+                                                         int curbuf, float eps2f, int64_t n, const int32_t *__restrict__ id,
+                                                         double *__restrict__ t6_out, double *__restrict__ norm_out,
+                                                         const double *__restrict__ quad) {
+    if (info->error != 0 || info->sticky_error != 0) return;  // the tree did not fit: the caller reports it
+    const int64_t rank = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const WalkCtx C = lane_prologue(nodes, posm_s, perm, rank, n, info, tab, curbuf);
+    const Lane64 L = lane_f64(C);
+    const TidalSum f = field_walk<kQuad, false, false, true>(nodes, pot, info, C.b64, L.qx, L.qy, L.qz, C.px, C.py, C.pz, C.valid, eps2f,
+                                                             0.0, 0.0, quad);
+    if (C.valid) {
+        const int64_t o = id[C.j];
+        if (t6_out) tidal_store(t6_out, o, f);
+        if (norm_out) norm_out[o] = tidal_norm(f);
+    }
+}
+
+// Direct handle: the sum over all bodies in body order with the one guard dist_sq > eps^2, field_direct_sum's tile loop.
+// pts != null: point i of (m, 3) rows, results at row i.  pts == null: state row i of the m = n bodies (its own term
+// has d = 0 and is dropped by the guard), results at the caller's row id[i].
+__global__ __launch_bounds__(kBlock) void k_tidal_direct(Bodies cur, int64_t n, double G, double eps2, const double *__restrict__ pts,
+                                                         int64_t m, double *__restrict__ t6_out, double *__restrict__ norm_out,
+                                                         int32_t *__restrict__ cnt_out) {
+    __shared__ double4 tile[kBlock];
+    const int t = threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * kBlock + t;
+    const bool valid = i < m;
+    double x = 0.0, y = 0.0, z = 0.0;
+    if (valid) {
+        if (pts) { x = pts[3 * i]; y = pts[3 * i + 1]; z = pts[3 * i + 2]; }
+        else { x = cur.x[i]; y = cur.y[i]; z = cur.z[i]; }
+    }
+    TidalSum f{0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0};
+    for (int64_t base = 0; base < n; base += kBlock) {
+        const int64_t jj = base + t;
+        tile[t] = jj < n ? make_double4(cur.x[jj], cur.y[jj], cur.z[jj], G * cur.m[jj]) : make_double4(0.0, 0.0, 0.0, 0.0);
+        __syncthreads();
+        const int lim = n - base < kBlock ? (int)(n - base) : kBlock;
+        for (int k = 0; k < lim; k++) {
+            const double4 q = tile[k];
+            const double ex = q.x - x, ey = q.y - y, ez = q.z - z;
+            const double d2 = ex * ex + ey * ey + ez * ez + eps2;
+            if (d2 > eps2) {
+                const double dist = sqrt(d2);
+                const double w = q.w / (dist * d2), w5 = (3.0 * w) / d2;
+                f.xx += (ex * ex) * w5 - w; f.yy += (ey * ey) * w5 - w; f.zz += (ez * ez) * w5 - w;
+                f.xy += (ex * ey) * w5; f.xz += (ex * ez) * w5; f.yz += (ey * ez) * w5;
+                f.terms++;
+            }
+        }
+        __syncthreads();
+    }
+    if (valid) {
+        const int64_t o = pts ? i : (int64_t)cur.id[i];
+        if (t6_out) tidal_store(t6_out, o, f);
+        if (norm_out) norm_out[o] = tidal_norm(f);
+        if (cnt_out) cnt_out[o] = f.terms;
+    }
+}
+
+// ---------------------------------------------------------------------------------------
 // K20: massless tracers carried by the integrator (nbmi_set_tracers; include/nbmi.h).
 // The probe walks of K19 with the handle's integrator as their epilogue, on the tree the step has just built.  State:
 // p, v (and the leapfrog's a), (m, 3) float64 rows in the caller's order.  kLeap: 0 = kick-drift, kLeapClose = the
@@ -5149,6 +5286,7 @@ struct nbmi_sim {
     struct : ProbeScratch {
         double *pts = nullptr, *acc = nullptr, *phi = nullptr;
         int32_t *cnt = nullptr;
+        double *t6 = nullptr;  // nbmi_tidal_at's rows, 48 bytes more per point: null until its first call (section 4.27)
     } field;
     bool field_sort = true;  // probes walk in key order (NBMI_FIELD_SORT=0: in the caller's order; measurement)
     // Massless tracers (nbmi_set_tracers, section 4.19); all null / 0 on a handle without them.  State: p and v, (m, 3)
@@ -7302,7 +7440,7 @@ int field_alloc(nbmi_sim *s, int64_t need) {
     while (rows < need) rows *= 2;
     if (rows > kFieldChunk) rows = kFieldChunk;
     probe_free(s, f);
-    dev_free(s, &f.pts); dev_free(s, &f.acc); dev_free(s, &f.phi); dev_free(s, &f.cnt);
+    dev_free(s, &f.pts); dev_free(s, &f.acc); dev_free(s, &f.phi); dev_free(s, &f.cnt); dev_free(s, &f.t6);
     const size_t r = (size_t)rows;
     if (dev_alloc(s, &f.pts, 3 * r) || dev_alloc(s, &f.acc, 3 * r) || dev_alloc(s, &f.phi, r) || dev_alloc(s, &f.cnt, r))
         return NBMI_ERR_HIP;
@@ -7311,9 +7449,10 @@ int field_alloc(nbmi_sim *s, int64_t need) {
     return 0;
 }
 
-// The chunks of one call, enqueued and copied out one after the other; the tree (Barnes-Hut) stands.  pmax: the call's
-// largest |coordinate|.
-int field_chunks(nbmi_sim *s, int64_t m, const double *pts, double pmax, double *acc, double *phi, int32_t *terms) {
+// The chunks of one call of `who` (nbmi_field_at, or nbmi_tidal_at: `tidal`, whose outputs are t6 and terms), enqueued and
+// copied out one after the other; the tree (Barnes-Hut) stands.  pmax: the call's largest |coordinate|.
+int field_chunks(nbmi_sim *s, const char *who, bool tidal, int64_t m, const double *pts, double pmax, double *acc, double *phi,
+                 double *t6, int32_t *terms) {
     auto &f = s->field;
     hipStream_t st = s->stream;
     const bool tree = s->method == NBMI_METHOD_BARNES_HUT;
@@ -7322,48 +7461,71 @@ int field_chunks(nbmi_sim *s, int64_t m, const double *pts, double pmax, double 
         const int64_t mc = m - b < f.rows ? m - b : f.rows;
         NBMI_HIP_CHECK(hipMemcpyAsync(f.pts, pts + 3 * b, (size_t)mc * 3 * sizeof(double), hipMemcpyHostToDevice, st));
         if (!tree) {
-            k_field_direct<<<nblocks(mc), kBlock, 0, st>>>(s->buf[s->curbuf], s->n, s->G, eps2, f.pts, mc, acc ? f.acc : nullptr,
-                                                           phi ? f.phi : nullptr, terms ? f.cnt : nullptr);
+            if (tidal)
+                k_tidal_direct<<<nblocks(mc), kBlock, 0, st>>>(s->buf[s->curbuf], s->n, s->G, eps2, f.pts, mc, t6 ? f.t6 : nullptr,
+                                                               nullptr, terms ? f.cnt : nullptr);
+            else
+                k_field_direct<<<nblocks(mc), kBlock, 0, st>>>(s->buf[s->curbuf], s->n, s->G, eps2, f.pts, mc, acc ? f.acc : nullptr,
+                                                               phi ? f.phi : nullptr, terms ? f.cnt : nullptr);
         } else {
             const uint32_t *order;
             if (int rc = probe_order_chunk(s, f, f.pts, mc, &order)) return rc;
             with_bool(s->multipole == NBMI_MULTIPOLE_QUADRUPOLE, [&](auto q) {
-                k_field_tree<decltype(q)::value><<<nblocks(mc), kBlock, 0, st>>>(
-                    s->nodes, s->diag_pot, f.wtab, s->info, f.sx, f.sy, f.sz, order, mc, (float)eps2, s->softening, pmax,
-                    decltype(q)::value ? s->quad_work : nullptr, acc ? f.acc : nullptr, phi ? f.phi : nullptr,
-                    terms ? f.cnt : nullptr);
+                const double *quad = decltype(q)::value ? s->quad_work : nullptr;
+                if (tidal)
+                    k_tidal_tree<decltype(q)::value><<<nblocks(mc), kBlock, 0, st>>>(
+                        s->nodes, s->diag_pot, f.wtab, s->info, f.sx, f.sy, f.sz, order, mc, (float)eps2, s->softening, pmax, quad,
+                        t6 ? f.t6 : nullptr, terms ? f.cnt : nullptr);
+                else
+                    k_field_tree<decltype(q)::value><<<nblocks(mc), kBlock, 0, st>>>(
+                        s->nodes, s->diag_pot, f.wtab, s->info, f.sx, f.sy, f.sz, order, mc, (float)eps2, s->softening, pmax, quad,
+                        acc ? f.acc : nullptr, phi ? f.phi : nullptr, terms ? f.cnt : nullptr);
             });
         }
         if (hipGetLastError() != hipSuccess) {
-            nbmi::set_error("nbmi_field_at: a kernel launch failed");
+            nbmi::set_error("%s: a kernel launch failed", who);
             return NBMI_ERR_HIP;
         }
         if (acc) NBMI_HIP_CHECK(hipMemcpyAsync(acc + 3 * b, f.acc, (size_t)mc * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
         if (phi) NBMI_HIP_CHECK(hipMemcpyAsync(phi + b, f.phi, (size_t)mc * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (t6) NBMI_HIP_CHECK(hipMemcpyAsync(t6 + 6 * b, f.t6, (size_t)mc * 6 * sizeof(double), hipMemcpyDeviceToHost, st));
         if (terms) NBMI_HIP_CHECK(hipMemcpyAsync(terms + b, f.cnt, (size_t)mc * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         NBMI_HIP_CHECK(hipStreamSynchronize(st));  // the next chunk overwrites the scratch
     }
-    return tree ? probe_sort_error(s, f, "nbmi_field_at: the sort of the points failed") : 0;
+    char what[64];
+    snprintf(what, sizeof(what), "%s: the sort of the points failed", who);
+    return tree ? probe_sort_error(s, f, what) : 0;
+}
+
+// What nbmi_field_at and nbmi_tidal_at (`who`) check before anything is enqueued: the handle's kind, m and the points.
+// *pmax: the largest |coordinate|.
+int field_points_check(nbmi_sim *s, const char *who, int64_t m, const double *points_xyz, double *pmax) {
+    if (int rc = diag_refuse(s, who)) return rc;
+    if (m < 0) {
+        nbmi::set_error("%s: m = %lld is negative", who, (long long)m);
+        return NBMI_ERR_ARG;
+    }
+    if (m == 0) return 0;
+    if (!points_xyz) {
+        nbmi::set_error("%s: null points_xyz", who);
+        return NBMI_ERR_ARG;
+    }
+    const int64_t bad = first_bad_row(points_xyz, m, 1e18, pmax);
+    if (bad >= 0) {
+        const double *r = points_xyz + 3 * bad;
+        nbmi::set_error("%s: points_xyz row %lld holds %g: coordinates must be finite and at most 1e18 in magnitude", who,
+                        (long long)bad, !(fabs(r[0]) <= 1e18) ? r[0] : !(fabs(r[1]) <= 1e18) ? r[1] : r[2]);
+        return NBMI_ERR_ARG;
+    }
+    return 0;
 }
 }  // namespace
 
 int nbmi_field_at(nbmi_sim *s, int64_t m, const double *points_xyz, double *acc_xyz, double *phi, int32_t *terms) {
     if (int rc = check_handle(s)) return rc;
-    if (int rc = diag_refuse(s, "nbmi_field_at")) return rc;
-    if (m < 0) {
-        nbmi::set_error("nbmi_field_at: m = %lld is negative", (long long)m);
-        return NBMI_ERR_ARG;
-    }
-    if (m == 0) return 0;
-    if (int rc = require_out(points_xyz, "nbmi_field_at: null points_xyz")) return rc;
     double pmax = 0.0;
-    const int64_t bad = first_bad_row(points_xyz, m, 1e18, &pmax);
-    if (bad >= 0) {
-        const double *r = points_xyz + 3 * bad;
-        nbmi::set_error("nbmi_field_at: points_xyz row %lld holds %g: coordinates must be finite and at most 1e18 in magnitude",
-                        (long long)bad, !(fabs(r[0]) <= 1e18) ? r[0] : !(fabs(r[1]) <= 1e18) ? r[1] : r[2]);
-        return NBMI_ERR_ARG;
-    }
+    if (int rc = field_points_check(s, "nbmi_field_at", m, points_xyz, &pmax)) return rc;
+    if (m == 0) return 0;
     const int64_t n = s->n;
     if (n == 0) {
         for (int64_t i = 0; i < m; i++) {
@@ -7375,8 +7537,64 @@ int nbmi_field_at(nbmi_sim *s, int64_t m, const double *points_xyz, double *acc_
     }
     if (!acc_xyz && !phi && !terms) return 0;
     if (int rc = field_alloc(s, m)) return rc;
-    auto chunks = [&] { return field_chunks(s, m, points_xyz, pmax, acc_xyz, phi, terms); };
+    auto chunks = [&] { return field_chunks(s, "nbmi_field_at", false, m, points_xyz, pmax, acc_xyz, phi, nullptr, terms); };
     return s->method != NBMI_METHOD_BARNES_HUT ? chunks() : side_tree(s, true, true, false, false, chunks);
+}
+
+int nbmi_tidal_at(nbmi_sim *s, int64_t m, const double *points_xyz, double *tidal6, int32_t *terms) {
+    if (int rc = check_handle(s)) return rc;
+    double pmax = 0.0;
+    if (int rc = field_points_check(s, "nbmi_tidal_at", m, points_xyz, &pmax)) return rc;
+    if (m == 0) return 0;
+    if (s->n == 0) {
+        for (int64_t i = 0; i < m; i++) {
+            for (int k = 0; tidal6 && k < 6; k++) tidal6[6 * i + k] = 0.0;
+            if (terms) terms[i] = 0;
+        }
+        return 0;
+    }
+    if (!tidal6 && !terms) return 0;
+    if (int rc = field_alloc(s, m)) return rc;
+    auto &f = s->field;
+    if (!f.t6 && dev_alloc(s, &f.t6, 6 * (size_t)f.rows)) return NBMI_ERR_HIP;  // 48 bytes per scratch row, from the first call on
+    auto chunks = [&] { return field_chunks(s, "nbmi_tidal_at", true, m, points_xyz, pmax, nullptr, nullptr, tidal6, terms); };
+    return s->method != NBMI_METHOD_BARNES_HUT ? chunks() : side_tree(s, true, true, false, false, chunks);
+}
+
+// The tidal tensor at every body's own position: nbmi_get_potentials_f64's build and lane setup, the rows written in the
+// caller's order straight into the getter staging (6 N doubles, then the N norms: it holds 7 N), so nothing is allocated.
+int nbmi_get_tidal_f64(nbmi_sim *s, double *tidal6, double *norm) {
+    if (int rc = check_handle(s)) return rc;
+    if (int rc = diag_refuse(s, "nbmi_get_tidal_f64")) return rc;
+    const int64_t n = s->n;
+    if (n == 0 || (!tidal6 && !norm)) return 0;
+    hipStream_t st = s->stream;
+    double *d_t6 = (double *)s->stage, *d_norm = d_t6 + 6 * n;
+    const double eps2 = s->softening * s->softening;
+    if (s->method != NBMI_METHOD_BARNES_HUT) {
+        k_tidal_direct<<<nblocks(n), kBlock, 0, st>>>(s->buf[s->curbuf], n, s->G, eps2, nullptr, n, tidal6 ? d_t6 : nullptr,
+                                                       norm ? d_norm : nullptr, nullptr);
+        if (hipGetLastError() != hipSuccess) {
+            nbmi::set_error("nbmi_get_tidal_f64: a kernel launch failed");
+            return NBMI_ERR_HIP;
+        }
+    } else {
+        const int rc = side_tree(s, true, false, true, false, [&] {
+            with_bool(s->multipole == NBMI_MULTIPOLE_QUADRUPOLE, [&](auto q) {
+                k_tidal_bodies<decltype(q)::value><<<nblocks(n), kBlock, 0, st>>>(
+                    s->nodes, s->diag_pot, s->wtab, s->info, s->posm_s, s->perm, s->curbuf, (float)eps2, n, s->buf[s->curbuf].id,
+                    tidal6 ? d_t6 : nullptr, norm ? d_norm : nullptr, decltype(q)::value ? s->quad_work : nullptr);
+            });
+            if (hipGetLastError() == hipSuccess) return 0;
+            nbmi::set_error("nbmi_get_tidal_f64: a kernel launch failed");
+            return (int)NBMI_ERR_HIP;
+        });
+        if (rc) return rc;
+    }
+    if (tidal6) NBMI_HIP_CHECK(hipMemcpyAsync(tidal6, d_t6, (size_t)n * 6 * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (norm) NBMI_HIP_CHECK(hipMemcpyAsync(norm, d_norm, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+    NBMI_HIP_CHECK(hipStreamSynchronize(st));
+    return 0;
 }
 
 namespace {

@@ -59,6 +59,8 @@ PROTOTYPES = {
     "nbmi_compute_group_colors": (C.c_int, [_vp, _dbl, _i64]),
     "nbmi_pair_counts": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "nbmi_field_at": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp]),
+    "nbmi_tidal_at": (C.c_int, [_vp, _i64, _vp, _vp, _vp]),
+    "nbmi_get_tidal_f64": (C.c_int, [_vp, _vp, _vp]),
     "nbmi_deposit": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "nbmi_radial_profile": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp]),
     "nbmi_mass_radii": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -1,6 +1,7 @@
 """Host side of the field evaluation (include/nbmi.h nbmi_field_at): what is derived from the
 field at chosen points.  Pure NumPy over any object with ``field_at(points, potential=True)`` -> (acc (m, 3), phi (m,))
-(and, for the tracers of section 4.19, ``get_tracers()`` -> (positions, velocities)); no device."""
+(and, for the tracers of section 4.19, ``get_tracers()`` -> (positions, velocities)); no device.  At the end, what is
+derived from the tidal tensor's rows (``tidal_at`` / ``tidal``, section 4.27): plain functions of arrays."""
 import numpy as np
 
 
@@ -107,3 +108,55 @@ def tracer_energies(sim):
 def escape_speed(phi):
     """sqrt(max(-2 phi, 0)): the speed at which a test particle at potential phi is unbound (phi -> 0 at infinity)."""
     return np.sqrt(np.maximum(-2.0 * np.asarray(phi, dtype=np.float64), 0.0))
+
+
+# ---- the tidal tensor (include/nbmi.h nbmi_tidal_at; DESIGN.md section 4.27): what is derived from rows
+# {Txx, Tyy, Tzz, Txy, Txz, Tyz} of ``tidal_at`` / ``tidal`` ----
+def _t6(t6):
+    t = np.asarray(t6, dtype=np.float64)
+    if t.ndim != 2 or t.shape[1] != 6:
+        raise ValueError(f"expected tidal rows of shape (m, 6), got {t.shape}")
+    return t
+
+
+def tidal_matrix(t6):
+    """(m, 3, 3) float64: the symmetric matrices T_ab = da_a/dx_b of the (m, 6) rows."""
+    t = _t6(t6)
+    return t[:, [0, 3, 4, 3, 1, 5, 4, 5, 2]].reshape(-1, 3, 3)
+
+
+def tidal_eigenvalues(t6):
+    """(m, 3) float64: the eigenvalues of T per row, descending (``numpy.linalg.eigvalsh``).  Positive: stretching along
+    that axis; negative: compression.  A point mass G M at distance r gives (2, -1, -1) G M / r^3."""
+    return np.linalg.eigvalsh(tidal_matrix(t6))[:, ::-1]
+
+
+def tidal_norm(t6):
+    """(m,) float64: the Frobenius norm of T per row, in the association of the device's ``norm``."""
+    t = _t6(t6)
+    return np.sqrt(((t[:, 0] * t[:, 0] + t[:, 1] * t[:, 1]) + t[:, 2] * t[:, 2])
+                   + 2.0 * ((t[:, 3] * t[:, 3] + t[:, 4] * t[:, 4]) + t[:, 5] * t[:, 5]))
+
+
+def phase_per_step(norm, dt):
+    """dt sqrt(norm / sqrt(6)): the orbital phase a step of ``dt`` advances where the tidal tensor has Frobenius norm
+    ``norm``.  On a Kepler orbit T has eigenvalues (2, -1, -1) G M / r^3, norm sqrt(6) G M / r^3, so this is Omega dt;
+    the kick-drift and leapfrog steps are unstable on a harmonic mode once it reaches 2."""
+    return float(dt) * np.sqrt(np.asarray(norm, dtype=np.float64) / np.sqrt(6.0))
+
+
+def web_type(t6, threshold=0.0):
+    """(m,) int: the number of eigenvalues of -T (the Hessian of phi) above ``threshold``, the T-web class of the point:
+    0 void, 1 sheet, 2 filament, 3 knot."""
+    return (-tidal_eigenvalues(t6) > float(threshold)).sum(axis=1)
+
+
+def tidal_radius(gm, t6):
+    """(m,) float64: cbrt(gm / lambda_max), the distance from a satellite of mass parameter ``gm`` = G m at which the
+    largest stretching eigenvalue lambda_max of the host's T balances the satellite's own pull; inf where lambda_max <= 0
+    (nothing stretches).  This is the static tidal limit: it carries no centrifugal term, so for a satellite on a
+    circular orbit the Jacobi radius is smaller (cbrt(gm / (lambda_max + Omega^2)))."""
+    lam = tidal_eigenvalues(t6)[:, 0]
+    gm = np.broadcast_to(np.asarray(gm, dtype=np.float64), lam.shape)
+    pos = lam > 0.0
+    return np.where(pos, np.cbrt(gm / np.where(pos, lam, 1.0)), np.inf)

@@ -355,6 +355,42 @@ class _HIPSimulation:
             return acc, phi, cnt
         return (acc, phi) if potential else acc
 
+    # ---- the tidal tensor at points and at the bodies (include/nbmi.h nbmi_tidal_at) ----
+    def tidal_at(self, points, terms=False):
+        """The tidal tensor T_ab = da_a/dx_b of the current float64 state at the (m, 3) ``points``: (m, 6) float64 rows
+        {Txx, Tyy, Tzz, Txy, Txz, Tyz}, or (rows, terms) with ``terms`` - (m,) int32, the number ``field_at`` gives for
+        the same point.  nbody/field.py turns the rows into matrices, eigenvalues, norms and time-step measures.
+        Refusals as ``field_at``'s; the call does not change what the next step computes."""
+        what = "tidal_at"
+        if self._field_refusal:
+            raise ValueError(f"{what}: {self._field_refusal}")
+        p = np.ascontiguousarray(points, dtype=np.float64)
+        if p.ndim != 2 or p.shape[1] != 3:
+            raise ValueError(f"{what}: expected points of shape (m, 3), got {p.shape}")
+        m = len(p)
+        t6 = np.zeros((m, 6), dtype=np.float64)
+        cnt = np.zeros(m, dtype=np.int32) if terms else None
+        _nat.check_arg(self._lib.nbmi_tidal_at(self._h, m, _nat.ptr(p), _nat.ptr(t6), _nat.ptr(cnt)), what, "nbmi_tidal_at")
+        return (t6, cnt) if terms else t6
+
+    def _tidal_bodies(self, what, rows, norm):
+        if self._field_refusal:
+            raise ValueError(f"{what}: {self._field_refusal}")
+        t6 = np.zeros((self.n, 6), dtype=np.float64) if rows else None
+        nrm = np.zeros(self.n, dtype=np.float64) if norm else None
+        _nat.check_arg(self._lib.nbmi_get_tidal_f64(self._h, _nat.ptr(t6), _nat.ptr(nrm)), what, "nbmi_get_tidal_f64")
+        return t6, nrm
+
+    def tidal(self, norm=False):
+        """The tidal tensor at every body's own position, (N, 6) float64 in the caller's body order - ``tidal_at`` of
+        ``get_positions_f64()`` bit for bit, without the upload - or (rows, norm) with ``norm``: (N,) Frobenius norms."""
+        t6, nrm = self._tidal_bodies("tidal", True, norm)
+        return (t6, nrm) if norm else t6
+
+    def tidal_norm(self) -> np.ndarray:
+        """(N,) float64: the Frobenius norm of every body's tidal tensor (``tidal(norm=True)[1]``, the rows not copied)."""
+        return self._tidal_bodies("tidal_norm", False, True)[1]
+
     # ---- massless tracers carried by the integrator (include/nbmi.h nbmi_set_tracers; DESIGN.md section 4.19) ----
     def set_tracers(self, positions, velocities=None):
         """Replace the handle's tracers by the (m, 3) ``positions`` with ``velocities`` (None: at rest): test particles

@@ -536,6 +536,55 @@ def rotation_line(sim, frame: int, radii) -> str:
                        "phi": [float(x) for x in c["phi"]]}) + "\n"
 
 
+# ---- time-step check (extra config key "timestep_check") ------------------------------------
+TIMESTEP_FILE = "timestep.jsonl"
+# chi = Omega dt per step.  Display values, not tolerances: 2 is the stability limit of a harmonic mode for both
+# integrators; 0.1 and 0.5 are 63 and 13 steps per orbit.
+CHI_LEVELS = (0.1, 0.5, 2.0)
+CHI_MAX_LEVELS = 16
+CHI_QUANTILES = (0.5, 0.9, 0.99, 1.0)
+CHI_UNSTABLE = 2.0
+
+
+def check_chi_levels(levels):
+    """The levels as a list of floats if the time-step check can take them (ValueError otherwise): 1 .. 16 finite,
+    positive, strictly increasing values."""
+    v = np.asarray(levels, dtype=np.float64).reshape(-1)
+    if not 1 <= len(v) <= CHI_MAX_LEVELS:
+        raise ValueError(f"need 1 .. {CHI_MAX_LEVELS} levels, got {len(v)}")
+    if not np.all(np.isfinite(v)) or np.any(v <= 0.0) or np.any(np.diff(v) <= 0.0):
+        raise ValueError("the levels must be finite, positive and strictly increasing")
+    return [float(x) for x in v]
+
+
+def timestep_config(config: dict):
+    """The "timestep_check" key of a config, {"every": K, "levels": [c0, c1, ...]}, as (every, dt of a step, levels);
+    None without the key; ValueError for a malformed one."""
+    g = config.get("timestep_check")
+    if not g:
+        return None
+    every = int(g.get("every", 0))
+    if every <= 0:
+        raise ValueError(f"--timestep-check: K must be positive, not {every}")
+    try:
+        levels = check_chi_levels(g.get("levels", CHI_LEVELS))
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"--chi-levels: {e}") from None
+    return every, config["dt_per_frame"] / config["substeps"], levels
+
+
+def timestep_line(sim, frame: int, dt: float, levels) -> str:
+    """One JSON line (with its newline) for the state `sim` holds after `frame`: chi = phase_per_step(tidal_norm, dt), the
+    orbital phase a step of `dt` advances at every body (nbody/field.py) - its quantiles over the bodies and, per level,
+    the number of bodies above it."""
+    from nbody.field import phase_per_step
+    chi = phase_per_step(sim.tidal_norm(), dt)
+    q = np.quantile(chi, CHI_QUANTILES) if len(chi) else np.zeros(len(CHI_QUANTILES))
+    return json.dumps({"frame": frame, "dt": float(dt), "chi_quantiles": {str(k): float(v) for k, v in zip(CHI_QUANTILES, q)},
+                       "levels": [float(c) for c in levels], "above": [int((chi > c).sum()) for c in levels],
+                       "bodies": int(len(chi))}) + "\n"
+
+
 # ---- radial profile and Lagrangian radii (extra config key "profile"; DESIGN.md section 4.26) -----------------------
 PROFILE_FILE = "profile.jsonl"
 PROFILE_FRACTIONS = (0.1, 0.25, 0.5, 0.75, 0.9)
@@ -632,7 +681,8 @@ PAIRS = LineStream(PAIRS_FILE, pairs_config, pairs_line, key="pairs",
 ROTATION = LineStream(ROTATION_FILE, rotation_config, rotation_line)  # ("auto" radii need no state: build_config)
 PROFILE = LineStream(PROFILE_FILE, profile_config, profile_line)  # ("auto" edges need no state either)
 apply_groups, apply_pairs = GROUPS.apply, PAIRS.apply  # (gpu_sim, config, rec_dir=None) -> the config, "auto" resolved
-LINE_STREAMS = (DIAGNOSTICS, GROUPS, PROFILE, PAIRS, ROTATION)  # in the order of their lines after a frame; a new side file is one more entry
+TIMESTEP = LineStream(TIMESTEP_FILE, timestep_config, timestep_line)
+LINE_STREAMS = (DIAGNOSTICS, TIMESTEP, GROUPS, PROFILE, PAIRS, ROTATION)  # in the order of their lines after a frame; a new side file is one more entry
 
 
 def line_due(frame: int, every: int) -> bool:
@@ -939,7 +989,7 @@ def record(config: dict, resume: bool = False, root: Path = None, quiet: bool = 
     say(f"[Record] GPU acceleration: {backend.value} - {info}")
     # extra config key "color": {"mode": "density", "k": K, "log10_range": [lo, hi]} = frames coloured by the k-NN
     # density through the unchanged colour and frame calls of both loops
-    # extra config keys "diagnostics_every", "groups", "profile", "pairs", "rotation_curve": every K-th frame a line in a side file (LINE_STREAMS)
+    # extra config keys "diagnostics_every", "timestep_check", "groups", "profile", "pairs", "rotation_curve": every K-th frame a line in a side file (LINE_STREAMS)
     try:
         config = apply_color_mode(gpu_sim, config, rec_dir)
         for stream in LINE_STREAMS:
@@ -1106,6 +1156,20 @@ def show_status(session_name: str, root: Path = None) -> bool:
             last = rrows[-1]
             k = int(np.argmax(last["v_circ"]))
             print(f"    frame {last['frame']}: peak v_circ = {last['v_circ'][k]:.6g} at R = {last['radii'][k]:.6g}")
+    tk = meta.get("timestep_check")
+    if tk:
+        print(f"  Time-step check: every {tk.get('every')} frames, levels "
+              + ", ".join(f"{c:.6g}" for c in tk.get("levels", CHI_LEVELS)))
+        trows = read_diagnostics(rec_dir / TIMESTEP_FILE)
+        if trows:
+            last = trows[-1]
+            q = last["chi_quantiles"]
+            print(f"    frame {last['frame']}: dt = {last['dt']:.6g}, phase per step median {q['0.5']:.3g}, "
+                  f"99 % {q['0.99']:.3g}, max {q['1.0']:.3g}")
+            for c, k in zip(last["levels"], last["above"]):
+                if c >= CHI_UNSTABLE and k > 0:
+                    print(f"    WARNING: {k:,} of {last['bodies']:,} bodies advance more than {c:.6g} rad per step: "
+                          f"their orbits are beyond the integrator's stability limit ({CHI_UNSTABLE:g}); reduce dt or raise substeps")
     pf = meta.get("profile")
     if pf:
         edges = pf.get("edges") or [0.0]
@@ -1176,7 +1240,7 @@ def build_parser():
                "--preset-id); --preset-id indexes this build's preset list (python -m tools.record --presets shows "
                "it); --dt sets dt_per_frame (the reference writes an unused 'dt' key); --presets, --seed, "
                "--device-ic, --diagnostics, --integrator, --multipole, --pipeline, --color, --density-k, --density-range, "
-               "--groups, --linking-length, --min-members, --pairs, --pair-edges, --rotation-curve, --curve-radii, --profile, --profile-edges, --profile-fractions, --tracers, --tracers-every, "
+               "--groups, --linking-length, --min-members, --pairs, --pair-edges, --rotation-curve, --curve-radii, --timestep-check, --chi-levels, --profile, --profile-edges, --profile-fractions, --tracers, --tracers-every, "
                "--density-map, --map-pixels, --map-half-width, --map-axis and --root are "
                "additions.")
     ap.add_argument("session", nargs="?", help="session name (for --resume, --status or --extend)")
@@ -1235,6 +1299,12 @@ def build_parser():
                          "(stored in metadata.json as rotation_curve)")
     ap.add_argument("--curve-radii", type=str, default=None, metavar="auto|r0,r1,...",
                     help="1 .. 256 increasing radii (default auto: 16 radii, spawn_radius k / 16 for k = 1 .. 16)")
+    ap.add_argument("--timestep-check", type=int, default=None, metavar="K",
+                    help="every K frames append the orbital phase per step at the bodies (dt sqrt(|T| / sqrt 6) from the "
+                         "tidal tensor T: quantiles, and the bodies above each level) to timestep.jsonl (stored in "
+                         "metadata.json as timestep_check); --status warns when bodies exceed the stability limit 2")
+    ap.add_argument("--chi-levels", type=str, default=None, metavar="c0,c1,...",
+                    help="1 .. 16 increasing phase-per-step levels to count bodies above (default 0.1,0.5,2)")
     ap.add_argument("--profile", type=int, default=None, metavar="K",
                     help="every K frames append the radial profile about the centre of mass (bodies, mass, density, mean "
                          "radial velocity, dispersions and anisotropy per shell) and the Lagrangian radii to profile.jsonl "
@@ -1354,6 +1424,18 @@ def build_config(args) -> dict:
                 raise ValueError(f"--curve-radii: need auto or comma-separated numbers, not {cr!r}") from None
         config["rotation_curve"] = {"every": int(ck), "radii": radii}
         rotation_config(config)  # (a bad K or bad radii raise here)
+    tk, tl = (getattr(args, a, None) for a in ("timestep_check", "chi_levels"))
+    if tk is None and tl is not None:
+        raise ValueError("--chi-levels needs --timestep-check K")
+    if tk is not None:  # the default writes no key
+        levels = list(CHI_LEVELS)
+        if tl is not None:
+            try:
+                levels = [float(x) for x in tl.split(",")]
+            except ValueError:
+                raise ValueError(f"--chi-levels: need comma-separated numbers, not {tl!r}") from None
+        config["timestep_check"] = {"every": int(tk), "levels": levels}
+        timestep_config(config)  # (a bad K or bad levels raise here)
     fk, fe, ff = (getattr(args, a, None) for a in ("profile", "profile_edges", "profile_fractions"))
     if fk is None and (fe is not None or ff is not None):
         raise ValueError("--profile-edges and --profile-fractions need --profile K")

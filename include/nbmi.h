@@ -400,6 +400,66 @@ int nbmi_field_at(nbmi_sim *sim, int64_t m, const double *points_xyz /* (m,3) */
                   double *acc_xyz /* (m,3), may be NULL */, double *phi /* (m,), may be NULL */,
                   int32_t *terms /* (m,), may be NULL */);
 
+/* The tidal tensor T_ab = d a_a / d x_b = -d^2 phi / dx_a dx_b of the handle's current float64 state, at m arbitrary
+ * points (nbmi_tidal_at) and at every body's own position (nbmi_get_tidal_f64); DESIGN.md section 4.27.  |T|^-1/2 is the
+ * local dynamical time and the eigenvalues of -T are the squared frequencies an integrator has to follow.  The kernels
+ * and the tests' NumPy restatement (tests/tidal_ref.py) both follow this text.  All arithmetic is float64 in the
+ * association written, without FMA contraction, sqrt and divide correctly rounded.
+ * tidal6 rows are {Txx, Tyy, Tzz, Txy, Txz, Tyz}: the order of nbmi_get_cell_moments.
+ *
+ * Accepted set.  Exactly the same accepted set as nbmi_field_at for the same point: the same octree of the current
+ * positions, the same opening test ((2 half) / dist < theta, with its fp32 band and its float64 re-decision), no own-leaf
+ * rule, and an accepted node is applied only when G M > 0 and dist_sq > eps^2.  terms[i] is therefore the number
+ * nbmi_field_at returns for the point, in both multipole modes.
+ * Monopole term.  With d = c - p, u = dist_sq = ((dx dx + dy dy) + dz dz) + eps^2 and dist = sqrt(u) as in nbmi_field_at,
+ * an applied node adds
+ *   w  = G M / (dist * u)                (nbmi_field_at's w)
+ *   w5 = (3.0 * w) / u
+ *   T_aa += (d_a * d_a) * w5 - w
+ *   T_ab += (d_a * d_b) * w5             (a != b)
+ * which is G M [3 d d^T u^-5/2 - I u^-3/2].  Its trace is -3 G M eps^2 u^-5/2: zero for eps == 0, and -4 pi G times the
+ * Plummer density otherwise.
+ * Quadrupole mode.  An applied internal cell (leaves add nothing) also adds the second-order term, from the cell's
+ * float64 second moments P about its centre of mass (G folded in; the rows nbmi_field_at reads).  With
+ *   g_x = (Pxx dx + Pxy dy) + Pxz dz,  g_y = (Pxy dx + Pyy dy) + Pyz dz,  g_z = (Pxz dx + Pyz dy) + Pzz dz      (g = P d)
+ *   q   = (dx (Pxx dx + 2.0 (Pxy dy + Pxz dz)) + dy (Pyy dy + 2.0 (Pyz dz))) + dz (Pzz dz)                      (d^T P d)
+ *   tr  = (Pxx + Pyy) + Pzz
+ *   i5  = ((1.0 / dist) / u) / u,   i7 = i5 / u,   i9 = i7 / u
+ *   A = (1.5 * tr) * i5 - (7.5 * q) * i7     B = (52.5 * q) * i9 - (7.5 * tr) * i7     C = 3.0 * i5     D = 15.0 * i7
+ * it adds, as one number per component,
+ *   T_aa += ((A + B * (d_a * d_a)) + C * P_aa) - D * (g_a * d_a + d_a * g_a)
+ *   T_ab += (B * (d_a * d_b) + C * P_ab) - D * (g_a * d_b + d_a * g_b)                                          (a != b)
+ * after the node's monopole term.  Both parts are minus the Hessian of what nbmi_field_at adds to phi.
+ * Direct handle.  The exact sum over all N bodies in body order with the monopole term (G M = G m_j, c = x_j) and the one
+ * guard dist_sq > eps^2; terms[i] = the number of bodies applied.
+ *
+ * Fixed summation order.  Each point sums its terms in pre-order of the node array (direct: in body order).  A row does
+ * not depend on the other points of the call, on their order or on how the call is split: two calls give the same bits,
+ * duplicated points give identical rows, a permutation of the points permutes the rows.
+ *
+ * nbmi_get_tidal_f64: the same tensor at every body's own position, without an upload, rows in the caller's body order:
+ * nbmi_get_potentials_f64's walk (a body in the lane, the build's band; the body's own leaf has d = 0 and is dropped by
+ * the guard).  tidal6 equals nbmi_tidal_at at nbmi_get_positions_f64 bit for bit, monopole and quadrupole, and the
+ * per-body term count equals the potential's.  Direct handles are accepted: a body's own term is skipped by the guard.
+ *   norm[i] = sqrt(((Txx^2 + Tyy^2) + Tzz^2) + 2.0 * ((Txy^2 + Txz^2) + Tyz^2)),  the Frobenius norm of row i.
+ *
+ * tidal6, terms and norm may each be NULL.  m == 0: success, nothing is touched.  N == 0: zeros (nbmi_get_tidal_f64:
+ * nothing to write).  NBMI_ERR_ARG, message "nbmi_tidal_at: ..." or "nbmi_get_tidal_f64: ...": m < 0, null points_xyz with
+ * m > 0, a coordinate that is not finite or exceeds 1e18 in magnitude (the message names the first bad row), owner-mode
+ * handles and handles with a proper shard.
+ * A call changes nothing that a later step or query reads (state and its order, the tree header - saved and restored -,
+ * the "auto" precision flags and force_all64, the step count, the stored leapfrog acceleration, the tracers): a leapfrog
+ * handle returns a plain handle's bits.  NBMI_ERR_CAPACITY of the call's own tree build is reported with a step's message.
+ * nbmi_tidal_at processes the points as nbmi_field_at does - chunks of at most 1 048 576, walked in key order within a
+ * chunk of more than 64, NBMI_FIELD_SORT=0 honoured: same bits, other time - through nbmi_field_at's scratch.
+ * Memory: the tensor rows cost 48 bytes per row of that scratch on top of its 108 (at most 50 MB), allocated by the
+ * first nbmi_tidal_at and freed with the scratch.  nbmi_get_tidal_f64 allocates nothing: its 56 bytes per body (6 + 1
+ * doubles) are the getters' staging buffer, which every handle has. */
+int nbmi_tidal_at(nbmi_sim *sim, int64_t m, const double *points_xyz /* (m,3) */,
+                  double *tidal6 /* (m,6), may be NULL */, int32_t *terms /* (m,), may be NULL */);
+int nbmi_get_tidal_f64(nbmi_sim *sim, double *tidal6 /* (N,6), caller's body order, may be NULL */,
+                       double *norm /* (N,), may be NULL */);
+
 /* Massless tracer particles carried by the handle's integrator: m test particles that feel the
  * bodies and pull on nothing.  They appear in no tree, no body getter, no diagnostic, no frame and no colour pass; the
  * bodies' trajectories, nbmi_force_precision_share, the walk counters and every query are bit for bit what they are on
