@@ -25,6 +25,7 @@
 //     wave-uniform cursor (scalar loads); every lane applies the reference's own per-body
 //     opening test; the wave descends if ANY lane opens, lanes that accepted an ancestor sit
 //     out until the cursor leaves that subtree.  Each lane's accepted set == the reference's.
+#include <limits.h>
 #include <math.h>
 #include <stdarg.h>
 #include <stddef.h>
@@ -1743,6 +1744,15 @@ __device__ __forceinline__ void publish_maxabs(const WalkTable *tab, double lane
 // holds about an eighth of last step's total wave time (bodies move little between steps), at most `jmax` blocks
 // (the launch has 8 jmax workgroups) and at least one.  One workgroup: per-thread chunk sums, scan, the seven
 // thread(s) whose chunk holds a cut find it.  All-zero times (first step) give equal ranges.
+// What the walk relies on is the covering property: b[0] = 0, b[8] = nb and 1 <= b[k + 1] - b[k] <= jmax, so that the
+// workgroups (xcd, jb < jmax) with b[xcd] + jb < b[xcd + 1] walk every logical block exactly once.
+// PRECONDITION: nb >= kXcdMinBlocks (with fewer blocks than XCDs no range can hold "at least one": the need_after clamp
+// pushes the cuts below 0 - nb = 5 gives 0 -2 -1 0 1 2 3 4 5 - and an XCD would start at a negative block) and
+// 8 jmax >= nb (xcd_jmax(nb) gives that).  The callers check both: enqueue_walk's gate and the two debug hooks.
+constexpr int kXcdMinBlocks = 8;
+// workgroups per XCD of a balanced launch over nb logical blocks: half as many again as an equal eighth, so that a cheap
+// range can hold that much more than its share (64 bits: the hooks test a caller's nb before anything is narrowed)
+inline int64_t xcd_jmax(int64_t nb) { return ((nb + 7) / 8) * 3 / 2 + 1; }
 __global__ __launch_bounds__(1024) void k_xcd_bounds(const unsigned *__restrict__ wave_cycles, int nb, int jmax, int *__restrict__ bounds) {
     __shared__ int cut[9];
     const int t = threadIdx.x;
@@ -5191,6 +5201,7 @@ struct nbmi_sim {
     hipStream_t side = nullptr;
     hipEvent_t ev_walked = nullptr, ev_cut = nullptr;
     bool cut_pending = false;         // a k_xcd_bounds on `side` that the next balanced walk has to wait for
+    int64_t balanced_walks = 0;       // walks of this handle launched in balance mode (nbmi_debug_wave_times reports it)
     int walk_block = kBlock;  // threads per walk block (64, 128 or 256; measurement knob NBMI_WALK_BLOCK)
     bool keys_lean = true;    // the stepping build (a BuildRequest with step_dt > 0 and no aux, plain handle) computes and
                               // stores the upper key word only (key_low_word); NBMI_KEYS_LEAN=0: full keys.  Dropped for good
@@ -5710,9 +5721,9 @@ int enqueue_walk(nbmi_sim *s, bool integrate, double dt, double *acc_out, int le
     // (measured: 10 M collision walk 15.9 -> 14.8 ms, fp32 10.4 -> 9.8; 4 M galaxy 6.96 -> 6.90; at 1 M bodies the eighths are
     // within 1 % of each other already and the half-empty launch costs 2 %: from 8 192 blocks = 2 M bodies on)
     const bool balance = integrate && !guard && s->xcd_balance && s->xcd_chunk == 0 && wb == kBlock && !s->owner &&
-                         (gb >= 8192 || s->xcd_balance > 1) &&
+                         (gb >= 8192 || s->xcd_balance > 1) && gb >= kXcdMinBlocks &&  // (k_xcd_bounds' precondition)
                          P.rank_begin == 0 && P.rank_end == n && getenv("NBMI_XCD_CHUNK") == nullptr;
-    const int jmax = ((gb + 7) / 8) * 3 / 2 + 1;  // balance mode: the launch has 8 jmax workgroups
+    const int jmax = (int)xcd_jmax(gb);  // balance mode: the launch has 8 jmax workgroups
     if (balance) {
         if (s->cut_pending) {  // the cuts made from the last walk's times (on the side stream)
             NBMI_HIP_CHECK(hipStreamWaitEvent(st, s->ev_cut, 0));
@@ -5740,6 +5751,7 @@ int enqueue_walk(nbmi_sim *s, bool integrate, double dt, double *acc_out, int le
     });
     NBMI_HIP_CHECK(hipGetLastError());
     if (balance) {
+        s->balanced_walks++;
         // cuts for the next step: beside whatever the main stream does next (the next step's keys, sort and build)
         NBMI_HIP_CHECK(hipEventRecord(s->ev_walked, st));
         NBMI_HIP_CHECK(hipStreamWaitEvent(s->side, s->ev_walked, 0));
@@ -7870,6 +7882,85 @@ int nbmi_walk_counters(nbmi_sim *s, int64_t *out8 /* 17 entries */) {
     out8[7] = (int64_t)h.jumps;
     for (int x = 0; x < 8; x++) out8[8 + x] = (int64_t)h.xcd_visits[x];
     out8[16] = (int64_t)h.band_visits;
+    return 0;
+}
+
+// Test hook: the product's k_xcd_bounds with the product's jmax on a caller's table of wave times; no handle, the
+// current device.  Refused before anything is allocated or launched, outputs untouched: what the kernel's precondition
+// excludes, a launch of 8 jmax workgroups that no int holds, null pointers.
+int nbmi_debug_xcd_bounds(int nb, const uint32_t *wave_cycles, int32_t *bounds9, int32_t *jmax_out) {
+    if (nb < kXcdMinBlocks || 8 * xcd_jmax(nb) > (int64_t)INT_MAX || !wave_cycles || !bounds9 || !jmax_out) {
+        nbmi::set_error("nbmi_debug_xcd_bounds: bad arguments (nb = %d: from %d blocks on, 8 jmax within an int; no null pointer)", nb,
+                        kXcdMinBlocks);
+        return NBMI_ERR_ARG;
+    }
+    const int jmax = (int)xcd_jmax(nb);
+    unsigned *d_times = nullptr;
+    int *d_bounds = nullptr;
+    hipStream_t st = nullptr;
+    int32_t got[9];
+    const int rc = [&]() -> int {
+        NBMI_HIP_CHECK(hipMalloc(&d_times, (size_t)nb * 16));
+        NBMI_HIP_CHECK(hipMalloc(&d_bounds, 16 * sizeof(int)));
+        NBMI_HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        NBMI_HIP_CHECK(hipMemcpyAsync(d_times, wave_cycles, (size_t)nb * 16, hipMemcpyHostToDevice, st));
+        k_xcd_bounds<<<1, 1024, 0, st>>>(d_times, nb, jmax, d_bounds);
+        NBMI_HIP_CHECK(hipGetLastError());
+        NBMI_HIP_CHECK(hipMemcpyAsync(got, d_bounds, sizeof(got), hipMemcpyDeviceToHost, st));
+        NBMI_HIP_CHECK(hipStreamSynchronize(st));
+        return 0;
+    }();
+    if (st) (void)hipStreamDestroy(st);
+    if (d_times) (void)hipFree(d_times);
+    if (d_bounds) (void)hipFree(d_bounds);
+    if (rc) return rc;
+    memcpy(bounds9, got, sizeof(got));
+    *jmax_out = jmax;
+    return 0;
+}
+
+// Test hook: what the next balanced walk of this handle will find, and - with a table - the times it is cut from.
+int nbmi_debug_wave_times(nbmi_sim *s, const uint32_t *wave_cycles, int64_t count, int32_t *bounds9, int32_t *nb_out,
+                          int32_t *jmax_out, int64_t *balanced_walks) {
+    if (int rc = check_handle(s)) return rc;
+    const char *why = nullptr;
+    const int64_t gb64 = (s->n + s->walk_block - 1) / s->walk_block;  // enqueue_walk's gb of a full walk
+    if (!bounds9 || !nb_out || !jmax_out || !balanced_walks) why = "null output";
+    else if (s->method != NBMI_METHOD_BARNES_HUT) why = "direct N^2 handles have no tree walk";
+    else if (s->owner) why = "owner-mode handles are not supported (their walks never run balanced)";
+    else if (s->shard_begin != 0 || s->shard_end != s->n) why = "sharded handles are not supported (their walks never run balanced)";
+    else if (wave_cycles && s->walk_block != kBlock) why = "the handle's walk block is not 256 threads (its walks never run balanced)";
+    else if (wave_cycles && gb64 < kXcdMinBlocks) why = "fewer than 8 walk blocks (balance mode is not used below that)";
+    else if (wave_cycles && count != 4 * gb64) why = "count is not 4 times the handle's walk blocks";
+    if (why) {
+        nbmi::set_error("nbmi_debug_wave_times: %s", why);
+        return NBMI_ERR_ARG;
+    }
+    const int gb = (int)gb64, jmax = (int)xcd_jmax(gb64);
+    hipStream_t st = s->stream;
+    if (wave_cycles) {
+        // as enqueue_walk's first use, with the caller's times for the zeros: behind a cut that is still on the side
+        // stream, and the next balanced walk finds nothing pending and bounds made for its gb
+        if (s->cut_pending) {
+            NBMI_HIP_CHECK(hipStreamWaitEvent(st, s->ev_cut, 0));
+            s->cut_pending = false;
+        }
+        NBMI_HIP_CHECK(hipMemcpyAsync(s->wave_cycles, wave_cycles, (size_t)gb * 16, hipMemcpyHostToDevice, st));
+        k_xcd_bounds<<<1, 1024, 0, st>>>(s->wave_cycles, gb, jmax, s->xcd_bounds);
+        NBMI_HIP_CHECK(hipGetLastError());
+        s->balance_blocks = gb;
+    } else if (s->cut_pending) {
+        NBMI_HIP_CHECK(hipEventSynchronize(s->ev_cut));  // (stays pending: the next walk's wait finds it complete)
+    }
+    int32_t got[9];
+    for (int k = 0; k < 9; k++) got[k] = -1;  // no cut for this grid yet: the first balanced walk makes one from zeroed times
+    if (s->balance_blocks == gb && gb > 0)
+        NBMI_HIP_CHECK(hipMemcpyAsync(got, s->xcd_bounds, sizeof(got), hipMemcpyDeviceToHost, st));
+    NBMI_HIP_CHECK(hipStreamSynchronize(st));
+    memcpy(bounds9, got, sizeof(got));
+    *nb_out = gb;
+    *jmax_out = jmax;
+    *balanced_walks = s->balanced_walks;
     return 0;
 }
 

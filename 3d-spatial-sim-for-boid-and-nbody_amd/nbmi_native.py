@@ -102,7 +102,9 @@ PROTOTYPES = {
     "nbmi_debug_sort_pairs": (C.c_int, [C.c_int, _i64, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "nbmi_debug_sort_keys": (C.c_int, [C.c_int, _i64, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "nbmi_debug_sort_config": (C.c_int, [C.c_int, _i64, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
-    "nbmi_render_create": (_vp, [C.c_int, C.c_int, C.c_int]),
+    "nbmi_debug_xcd_bounds": (C.c_int, [C.c_int, _vp, _vp, _vp]),
+    "nbmi_debug_wave_times": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "nbmi_render_create":(_vp, [C.c_int, C.c_int, C.c_int]),
     "nbmi_render_destroy": (None, [_vp]),
     "nbmi_render_points": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp]),
     "nbmi_render_sim": (C.c_int, [_vp, _vp, _vp, _vp]),

@@ -881,6 +881,27 @@ int nbmi_debug_sort_config(int key_bytes, int64_t n, const void *keys, const uin
                            uint32_t *values_out, int begin_bit, int end_bit, int digit_bits, int threads, int repeats,
                            double *ms_per_sort);
 
+/* Test hooks for the balance mode of the tree walk: from 2 M bodies on (NBMI_XCD_BALANCE=2: from
+ * 8 walk blocks on) XCD x walks the logical blocks [bounds[x], bounds[x + 1]) of 256 bodies, and k_xcd_bounds cuts those
+ * nine bounds from the times (4 per block, shader clocks) that the previous walk's waves left.  A walk is right exactly
+ * when bounds[0] = 0, bounds[8] = nb and every range holds 1 .. jmax blocks (the launch has 8 jmax workgroups).
+ *
+ * nbmi_debug_xcd_bounds: the product's cut kernel with the product's jmax on 4 nb HOST words, no handle (the current
+ * device).  Writes the 9 bounds and jmax.  NBMI_ERR_ARG before anything is launched, outputs untouched: nb < 8 (the cut
+ * rule needs at least one block per XCD), an nb whose launch of 8 jmax workgroups no int holds, a null pointer. */
+int nbmi_debug_xcd_bounds(int nb, const uint32_t *wave_cycles, int32_t *bounds9, int32_t *jmax_out);
+/* nbmi_debug_wave_times: waits for everything this handle has enqueued (a cut on its side stream included) and writes
+ * the 9 bounds its next balanced walk will read (all -1: none made yet, that walk cuts equal eighths from zeroed
+ * times), *nb_out = its walk blocks, *jmax_out, and *balanced_walks = how many walks of the handle were launched in
+ * balance mode so far.  wave_cycles != NULL (HOST, count == 4 * walk blocks): first replaces the handle's table of wave
+ * times by these and cuts the bounds from them, as the first balanced walk does from zeros; the next balanced walk
+ * runs on exactly these bounds.  The walks themselves and a handle that never calls this are unchanged.
+ * NBMI_ERR_ARG, message "nbmi_debug_wave_times: ...": a null output, direct N^2, owner-mode and sharded handles; with a
+ * table also a handle with fewer than 8 walk blocks or a walk block other than 256 (no walk of theirs runs balanced) and
+ * a count other than 4 * walk blocks. */
+int nbmi_debug_wave_times(nbmi_sim *sim, const uint32_t *wave_cycles, int64_t count, int32_t *bounds9, int32_t *nb_out,
+                          int32_t *jmax_out, int64_t *balanced_walks);
+
 /* ---- headless point renderer (csrc/render.hip; tools/export.py) ------------------------------------------------
  * The image fixed-function GL draws for the exporter's frame: GL_POINTS with GL_POINT_SMOOTH, glBlendFunc(GL_SRC_ALPHA,
  * GL_ONE), GL_DEPTH_TEST (GL_LESS, depth writes on), GL_EXP2 fog, gluLookAt + gluPerspective.  Where GL leaves the
