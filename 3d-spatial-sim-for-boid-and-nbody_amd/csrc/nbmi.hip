@@ -3713,6 +3713,9 @@ __device__ __forceinline__ double query_d2(double bx, double by, double bz, doub
 // G - (2^-49 - 4 u) t < G.  A body's computed |dx| is >= G (1 - u), its computed d2 >= (sum G^2)(1 - u)^5; the bound
 // below is <= (sum g^2)(1 + u)^3 (1 - 2^-48).  2^-48 = 32 u leaves a factor four.  Below 2^-960 the products may be
 // subnormal and the relative bounds no longer hold: such a bound counts as 0 (never prunes).
+// Nothing above uses that q is a body or lies in the root cube: every step is a relative rounding bound on t = fl|q - a|,
+// and with |q| <= 1e18 (nbmi_pair_counts_at's points) and the bodies inside the cube no difference, square or sum
+// overflows, so the bound holds for such a point unrestricted.
 __device__ __forceinline__ double query_lower(double4 a, double qx, double qy, double qz) {
     const double tx = fabs(__dsub_rn(a.x, qx)), ty = fabs(__dsub_rn(a.y, qy)), tz = fabs(__dsub_rn(a.z, qz));
     double gx = __dsub_rn(__dsub_rn(tx, a.w), __dmul_rn(tx, 0x1p-49));
@@ -4229,6 +4232,9 @@ __global__ __launch_bounds__(kBlock) void k_pair_cells(const Node *__restrict__ 
 //     side) is below 2^-113 of it: inside the margin.  A value of at most 2^-960 means every h <= 2^-480 (1 + u), every
 //     computed |dx| <= h, the computed d2 < 3 x 2^-960 (1 + 4 u) + 3 x 2^-1075 < 2^-958: that is returned instead.
 //   An overflow to +inf is harmless: +inf is <= no edge, the cell is never accepted.
+//   q may be any finite point, outside the root cube too (nbmi_pair_counts_at: |q| <= 1e18): the statements about w concern
+//     the cell alone, those about t, s and h are relative rounding bounds whatever the size of t, and far from the cube t
+//     merely dominates w.  Nothing had to be restricted.
 __device__ __forceinline__ double query_upper(double4 a, double qx, double qy, double qz) {
     const double sx = __dadd_rn(fabs(__dsub_rn(a.x, qx)), a.w), sy = __dadd_rn(fabs(__dsub_rn(a.y, qy)), a.w),
                  sz = __dadd_rn(fabs(__dsub_rn(a.z, qz)), a.w);
@@ -4302,6 +4308,70 @@ __global__ __launch_bounds__(kQueryBlock) void k_pair_counts(const Node *__restr
             return false;
         },
         [&](double d2, const double4 &, int64_t) { count(d2); });
+    for (int k = 0; k <= nb; k++) nbmi::wave_add(out + 2 + k, (long long)c[64 * k], C.lane);
+    nbmi::wave_add(out, evals, C.lane);
+    nbmi::wave_add(out + 1, whole, C.lane);
+}
+
+// ---------------------------------------------------------------------------------------
+// K28: exact counts of the bodies per distance bin about arbitrary points (nbmi_pair_counts_at; include/nbmi.h, DESIGN.md
+// section 4.28).  K18's counting with K19's lane setup: one wave per 64 probes of a chunk, lane `rank` has row `rank` of
+// the probe columns (probe_order_chunk), and walks the WHOLE tree from the root - a point is no body, so there is no
+// half search, no own leaves to skip (ex_lo = ex_hi = 0) and no own-wave condition on a whole cell.  At an internal cell
+// an active lane, with p = pair_bin(query_lower): prunes if p > nb; accepts whole if `accept` and query_upper <= E[p],
+// cnt bodies into counter p; else keeps the cell open.  A leaf's d2 is binned.
+// LDS as k_pair_counts: E[nb + 1], then uint32 [nb + 1][64]; a lane counts at most n < 2^31 bodies.  At the end a valid
+// lane stores its nb + 1 counters as int32 to row order[rank] of per_point (null: not asked for; the stores of a wave are
+// nb + 1 words apart), then every counter is summed over the wave in 64 bits and added to out[2 + counter], which
+// accumulates over the chunks of a call; out[0] += distances evaluated, out[1] += bodies counted through whole cells.
+__global__ __launch_bounds__(kQueryBlock) void k_pair_counts_at(const Node *__restrict__ nodes, const double4 *__restrict__ rows,
+                                                               const int32_t *__restrict__ node_ref,
+                                                               const int32_t *__restrict__ cnt, const TreeInfo *__restrict__ info,
+                                                               const double *__restrict__ sx, const double *__restrict__ sy,
+                                                               const double *__restrict__ sz, const uint32_t *__restrict__ order,
+                                                               int64_t mc, int nb, PairEdges edges, int accept,
+                                                               int32_t *__restrict__ per_point,
+                                                               unsigned long long *__restrict__ out) {
+    extern __shared__ double pair_at_lds[];  // E[nb + 1], then uint32 [nb + 1][64]
+    QueryCtx C;
+    C.frozen = info->error != 0 || info->sticky_error != 0;  // as query_prologue
+    if (C.frozen) return;
+    C.lane = threadIdx.x;
+    C.w0 = (int64_t)blockIdx.x * kQueryBlock;
+    C.rank = C.w0 + C.lane;
+    C.valid = C.rank < mc;
+    C.nn = __builtin_amdgcn_readfirstlane((unsigned)info->num_nodes * kNodeBytes);
+    C.own = QueryGroup{0.0, 0.0, 0.0, 0.0, C.w0};  // (no bodies of its own)
+    C.qx = C.qy = C.qz = 0.0;
+    if (C.valid) { C.qx = sx[C.rank]; C.qy = sy[C.rank]; C.qz = sz[C.rank]; }
+    double *E = pair_at_lds;
+    uint32_t *c = reinterpret_cast<uint32_t *>(pair_at_lds + nb + 1) + C.lane;
+    for (int k = 0; k <= nb; k++) {
+        E[k] = edges.e2[k];  // (every lane stores the same value)
+        c[64 * k] = 0u;
+    }
+    __syncthreads();
+    long long evals = 0, whole = 0;
+    query_walk_cells(
+        nodes, rows, node_ref, 0u, C, (int64_t)0, (int64_t)0, evals,
+        [&](unsigned idx, const double4 &row, unsigned) {
+            const int p = pair_bin(E, nb, query_lower(row, C.qx, C.qy, C.qz));
+            if (p > nb) return false;  // pruned
+            if (!accept) return true;
+            if (!(query_upper(row, C.qx, C.qy, C.qz) <= E[p])) return true;
+            const uint32_t m = (uint32_t)cnt[idx];
+            c[64 * p] += m;
+            whole += (long long)m;
+            return false;
+        },
+        [&](double d2, const double4 &, int64_t) {
+            const int b = pair_bin(E, nb, d2);
+            if (b <= nb) c[64 * b]++;
+        });
+    if (per_point && C.valid) {
+        int32_t *row = per_point + (order ? (int64_t)order[C.rank] : C.rank) * (nb + 1);
+        for (int k = 0; k <= nb; k++) row[k] = (int32_t)c[64 * k];
+    }
     for (int k = 0; k <= nb; k++) nbmi::wave_add(out + 2 + k, (long long)c[64 * k], C.lane);
     nbmi::wave_add(out, evals, C.lane);
     nbmi::wave_add(out + 1, whole, C.lane);
@@ -5298,6 +5368,10 @@ struct nbmi_sim {
         double *pts = nullptr, *acc = nullptr, *phi = nullptr;
         int32_t *cnt = nullptr;
         double *t6 = nullptr;  // nbmi_tidal_at's rows, 48 bytes more per point: null until its first call (section 4.27)
+        // nbmi_pair_counts_at's per-point rows (section 4.28), pp_words int32: null until a call asks for per_point, grown
+        // by the call that needs more than `rows` x (nb + 1) words hold
+        int32_t *pp = nullptr;
+        int64_t pp_words = 0;
     } field;
     bool field_sort = true;  // probes walk in key order (NBMI_FIELD_SORT=0: in the caller's order; measurement)
     // Massless tracers (nbmi_set_tracers, section 4.19); all null / 0 on a handle without them.  State: p and v, (m, 3)
@@ -6022,6 +6096,34 @@ int probe_sort_error(nbmi_sim *s, ProbeScratch &g, const char *what) {
     return NBMI_ERR_HIP;
 }
 
+// The chunks of one call of `who` through nbmi_field_at's scratch, one after the other: a chunk's points are uploaded
+// and - `tree`: a tree stands - put in walk order (probe_order_chunk; `order` stays null otherwise), walk(b, mc, order)
+// enqueues the kernel of the chunk of mc points that starts at point b, `copy_out(b, mc)` the copies of its results, and
+// the stream is waited for, since the next chunk overwrites the scratch.  At the end the sort's error word.
+template <class Walk, class CopyOut>
+int probe_chunks(nbmi_sim *s, const char *who, bool tree, int64_t m, const double *pts, Walk walk, CopyOut copy_out) {
+    auto &f = s->field;
+    hipStream_t st = s->stream;
+    for (int64_t b = 0; b < m; b += f.rows) {
+        const int64_t mc = m - b < f.rows ? m - b : f.rows;
+        NBMI_HIP_CHECK(hipMemcpyAsync(f.pts, pts + 3 * b, (size_t)mc * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+        const uint32_t *order = nullptr;
+        if (tree) {
+            if (int rc = probe_order_chunk(s, f, f.pts, mc, &order)) return rc;
+        }
+        walk(b, mc, order);
+        if (hipGetLastError() != hipSuccess) {
+            nbmi::set_error("%s: a kernel launch failed", who);
+            return NBMI_ERR_HIP;
+        }
+        if (int rc = copy_out(b, mc)) return rc;
+        NBMI_HIP_CHECK(hipStreamSynchronize(st));
+    }
+    char what[64];
+    snprintf(what, sizeof(what), "%s: the sort of the points failed", who);
+    return tree ? probe_sort_error(s, f, what) : 0;
+}
+
 // ---- tracers (section 4.19): what a step enqueues for them; nothing here waits for the device ----
 // Whether the tracers' field comes from k_field_direct's sum: a direct handle, or no bodies at all (a = 0).
 bool tracers_direct(const nbmi_sim *s) { return s->method != NBMI_METHOD_BARNES_HUT || s->n == 0; }
@@ -6107,8 +6209,9 @@ int query_buffers(nbmi_sim *s) {
         return dev_alloc(s, &g.rows, s->node_capacity + 2) || dev_alloc(s, &g.wleaf, (s->n + 63) / 64) || dev_alloc(s, &g.evals, 1);
     });
 }
-template <class Launch>
-int query_enqueue(nbmi_sim *s, const char *what, Launch launch) {
+// The scope itself: `work` (its result is the call's) runs with the tree and the rows enqueued, and may wait.
+template <class Work>
+int query_tree(nbmi_sim *s, Work work) {
     SideBuild side(s);
     if (side.rc) return side.rc;
     int rc = enqueue_tree(s);
@@ -6116,13 +6219,18 @@ int query_enqueue(nbmi_sim *s, const char *what, Launch launch) {
         k_query_rows<<<nblocks(s->own_node_rows), kBlock, 0, s->stream>>>(s->nodes, s->nodes64, s->node_ref, s->perm,
                                                                            s->buf[s->curbuf], s->info, s->own_node_rows,
                                                                            s->q.shared.rows, s->q.shared.wleaf);
-        launch();
-        if (hipGetLastError() != hipSuccess) {
-            nbmi::set_error("%s launch failed", what);
-            rc = NBMI_ERR_HIP;
-        }
+        rc = work();
     }
     return side.finish(rc, false);
+}
+template <class Launch>
+int query_enqueue(nbmi_sim *s, const char *what, Launch launch) {
+    return query_tree(s, [&]() -> int {
+        launch();
+        if (hipGetLastError() == hipSuccess) return 0;
+        nbmi::set_error("%s launch failed", what);
+        return NBMI_ERR_HIP;
+    });
 }
 // The synchronous form of a query: errors of earlier steps first, as a getter reports them, then the query (`enqueue`,
 // one of the *_enqueue forms, which never wait) and its own.
@@ -7068,32 +7176,37 @@ int pairs_enqueue(nbmi_sim *s, int nb, const PairEdges &e2) {
             s->pair_cells ? 1 : 0, s->q.shared.wleaf, g.out);
     });
 }
+// The header's rules for nb and edges, for nbmi_pair_counts and nbmi_pair_counts_at (`who`); *e2 = the E[k].
+int pair_edges_check(const char *who, int nb, const double *edges, PairEdges *e2) {
+    if (nb < 1 || nb > kPairMaxBins) {
+        nbmi::set_error("%s: nb = %d is outside 1 .. %d", who, nb, kPairMaxBins);
+        return NBMI_ERR_ARG;
+    }
+    if (!edges) {
+        nbmi::set_error("%s: null edges", who);
+        return NBMI_ERR_ARG;
+    }
+    for (int k = 0; k <= nb; k++) {
+        if (!isfinite(edges[k]) || edges[k] < 0.0 || (k > 0 && !(edges[k] > edges[k - 1]))) {
+            nbmi::set_error("%s: edges[%d] = %g: the edges must be finite, >= 0 and strictly increasing", who, k, edges[k]);
+            return NBMI_ERR_ARG;
+        }
+        e2->e2[k] = edges[k] * edges[k];
+        if (!isfinite(e2->e2[k]) || (k > 0 && !(e2->e2[k] > e2->e2[k - 1]))) {
+            nbmi::set_error("%s: the square of edges[%d] = %g is not finite or not above the one before it", who, k, edges[k]);
+            return NBMI_ERR_ARG;
+        }
+    }
+    return 0;
+}
 }  // namespace
 
 int nbmi_pair_counts(nbmi_sim *s, int nb, const double *edges, int64_t *counts, int64_t *below, int64_t *evals,
                      int64_t *cell_pairs) {
     if (int rc = check_handle(s)) return rc;
     if (int rc = query_refuse(s, "nbmi_pair_counts")) return rc;
-    if (nb < 1 || nb > kPairMaxBins) {
-        nbmi::set_error("nbmi_pair_counts: nb = %d is outside 1 .. %d", nb, kPairMaxBins);
-        return NBMI_ERR_ARG;
-    }
-    if (!edges) {
-        nbmi::set_error("nbmi_pair_counts: null edges");
-        return NBMI_ERR_ARG;
-    }
     PairEdges e2{};
-    for (int k = 0; k <= nb; k++) {
-        if (!isfinite(edges[k]) || edges[k] < 0.0 || (k > 0 && !(edges[k] > edges[k - 1]))) {
-            nbmi::set_error("nbmi_pair_counts: edges[%d] = %g: the edges must be finite, >= 0 and strictly increasing", k, edges[k]);
-            return NBMI_ERR_ARG;
-        }
-        e2.e2[k] = edges[k] * edges[k];
-        if (!isfinite(e2.e2[k]) || (k > 0 && !(e2.e2[k] > e2.e2[k - 1]))) {
-            nbmi::set_error("nbmi_pair_counts: the square of edges[%d] = %g is not finite or not above the one before it", k, edges[k]);
-            return NBMI_ERR_ARG;
-        }
-    }
+    if (int rc = pair_edges_check("nbmi_pair_counts", nb, edges, &e2)) return rc;
     for (int k = 0; counts && k < nb; k++) counts[k] = 0;
     if (below) *below = 0;
     if (evals) *evals = 0;
@@ -7453,6 +7566,8 @@ int field_alloc(nbmi_sim *s, int64_t need) {
     if (rows > kFieldChunk) rows = kFieldChunk;
     probe_free(s, f);
     dev_free(s, &f.pts); dev_free(s, &f.acc); dev_free(s, &f.phi); dev_free(s, &f.cnt); dev_free(s, &f.t6);
+    dev_free(s, &f.pp);
+    f.pp_words = 0;
     const size_t r = (size_t)rows;
     if (dev_alloc(s, &f.pts, 3 * r) || dev_alloc(s, &f.acc, 3 * r) || dev_alloc(s, &f.phi, r) || dev_alloc(s, &f.cnt, r))
         return NBMI_ERR_HIP;
@@ -7469,9 +7584,7 @@ int field_chunks(nbmi_sim *s, const char *who, bool tidal, int64_t m, const doub
     hipStream_t st = s->stream;
     const bool tree = s->method == NBMI_METHOD_BARNES_HUT;
     const double eps2 = s->softening * s->softening;
-    for (int64_t b = 0; b < m; b += f.rows) {
-        const int64_t mc = m - b < f.rows ? m - b : f.rows;
-        NBMI_HIP_CHECK(hipMemcpyAsync(f.pts, pts + 3 * b, (size_t)mc * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+    auto walk = [&](int64_t, int64_t mc, const uint32_t *order) {
         if (!tree) {
             if (tidal)
                 k_tidal_direct<<<nblocks(mc), kBlock, 0, st>>>(s->buf[s->curbuf], s->n, s->G, eps2, f.pts, mc, t6 ? f.t6 : nullptr,
@@ -7480,8 +7593,6 @@ int field_chunks(nbmi_sim *s, const char *who, bool tidal, int64_t m, const doub
                 k_field_direct<<<nblocks(mc), kBlock, 0, st>>>(s->buf[s->curbuf], s->n, s->G, eps2, f.pts, mc, acc ? f.acc : nullptr,
                                                                phi ? f.phi : nullptr, terms ? f.cnt : nullptr);
         } else {
-            const uint32_t *order;
-            if (int rc = probe_order_chunk(s, f, f.pts, mc, &order)) return rc;
             with_bool(s->multipole == NBMI_MULTIPOLE_QUADRUPOLE, [&](auto q) {
                 const double *quad = decltype(q)::value ? s->quad_work : nullptr;
                 if (tidal)
@@ -7494,19 +7605,15 @@ int field_chunks(nbmi_sim *s, const char *who, bool tidal, int64_t m, const doub
                         acc ? f.acc : nullptr, phi ? f.phi : nullptr, terms ? f.cnt : nullptr);
             });
         }
-        if (hipGetLastError() != hipSuccess) {
-            nbmi::set_error("%s: a kernel launch failed", who);
-            return NBMI_ERR_HIP;
-        }
+    };
+    auto copy_out = [&](int64_t b, int64_t mc) -> int {
         if (acc) NBMI_HIP_CHECK(hipMemcpyAsync(acc + 3 * b, f.acc, (size_t)mc * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
         if (phi) NBMI_HIP_CHECK(hipMemcpyAsync(phi + b, f.phi, (size_t)mc * sizeof(double), hipMemcpyDeviceToHost, st));
         if (t6) NBMI_HIP_CHECK(hipMemcpyAsync(t6 + 6 * b, f.t6, (size_t)mc * 6 * sizeof(double), hipMemcpyDeviceToHost, st));
         if (terms) NBMI_HIP_CHECK(hipMemcpyAsync(terms + b, f.cnt, (size_t)mc * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        NBMI_HIP_CHECK(hipStreamSynchronize(st));  // the next chunk overwrites the scratch
-    }
-    char what[64];
-    snprintf(what, sizeof(what), "%s: the sort of the points failed", who);
-    return tree ? probe_sort_error(s, f, what) : 0;
+        return 0;
+    };
+    return probe_chunks(s, who, tree, m, pts, walk, copy_out);
 }
 
 // What nbmi_field_at and nbmi_tidal_at (`who`) check before anything is enqueued: the handle's kind, m and the points.
@@ -7571,6 +7678,77 @@ int nbmi_tidal_at(nbmi_sim *s, int64_t m, const double *points_xyz, double *tida
     if (!f.t6 && dev_alloc(s, &f.t6, 6 * (size_t)f.rows)) return NBMI_ERR_HIP;  // 48 bytes per scratch row, from the first call on
     auto chunks = [&] { return field_chunks(s, "nbmi_tidal_at", true, m, points_xyz, pmax, nullptr, nullptr, tidal6, terms); };
     return s->method != NBMI_METHOD_BARNES_HUT ? chunks() : side_tree(s, true, true, false, false, chunks);
+}
+
+// The bodies per distance bin about m points (section 4.28): nbmi_pair_counts' tree, rows and cell counts, and on them
+// nbmi_field_at's chunks with k_pair_counts_at as their kernel.  Synchronous.
+int nbmi_pair_counts_at(nbmi_sim *s, int64_t m, const double *points_xyz, int nb, const double *edges, int64_t *counts,
+                        int64_t *below, int32_t *per_point, int64_t *evals, int64_t *cell_pairs) {
+    static const char *const who = "nbmi_pair_counts_at";
+    if (int rc = check_handle(s)) return rc;
+    if (int rc = query_refuse(s, who)) return rc;
+    if (int rc = field_points_check(s, who, m, points_xyz, nullptr)) return rc;
+    PairEdges e2{};
+    if (int rc = pair_edges_check(who, nb, edges, &e2)) return rc;
+    for (int k = 0; counts && k < nb; k++) counts[k] = 0;
+    if (below) *below = 0;
+    if (evals) *evals = 0;
+    if (cell_pairs) *cell_pairs = 0;
+    if (m == 0) return 0;
+    const int64_t n = s->n;
+    const int64_t cols = nb + 1;
+    if (n == 0) {
+        for (int64_t i = 0; per_point && i < m * cols; i++) per_point[i] = 0;
+        return 0;
+    }
+    if (int rc = field_alloc(s, m)) return rc;
+    auto &f = s->field;
+    auto &g = s->q.pairs;
+    if (per_point && f.pp_words < f.rows * cols) {  // (nothing enqueued uses the old rows: every call waits for its copies)
+        dev_free(s, &f.pp);
+        f.pp_words = 0;
+        if (dev_alloc(s, &f.pp, (size_t)(f.rows * cols))) return NBMI_ERR_HIP;
+        f.pp_words = f.rows * cols;
+    }
+    if (query_buffers(s) || query_alloc(g, [&] {
+            return dev_alloc(s, &g.cnt, s->node_capacity + 2) || dev_alloc(s, &g.out, kPairMaxBins + 3);
+        }))
+        return NBMI_ERR_HIP;
+    hipStream_t st = s->stream;
+    NBMI_HIP_CHECK(hipStreamSynchronize(st));
+    if (int rc = check_device_error(s)) return rc;  // of earlier steps, as a getter reports them
+    NBMI_HIP_CHECK(hipMemsetAsync(g.out, 0, (kPairMaxBins + 3) * sizeof(unsigned long long), st));
+    const size_t lds = (size_t)cols * (sizeof(double) + kQueryBlock * sizeof(uint32_t));
+    const int rc = query_tree(s, [&]() -> int {
+        k_pair_cells<<<nblocks(s->own_node_rows), kBlock, 0, st>>>(s->nodes, s->node_ref, s->info, n, s->own_node_rows, g.cnt);
+        if (hipGetLastError() != hipSuccess) {
+            nbmi::set_error("%s: a kernel launch failed", who);
+            return NBMI_ERR_HIP;
+        }
+        if (int r = check_device_error(s)) return r;  // the build's own capacity error, before anything walks
+        return probe_chunks(
+            s, who, true, m, points_xyz,
+            [&](int64_t, int64_t mc, const uint32_t *order) {
+                k_pair_counts_at<<<(int)((mc + kQueryBlock - 1) / kQueryBlock), kQueryBlock, lds, st>>>(
+                    s->nodes, s->q.shared.rows, s->node_ref, g.cnt, s->info, f.sx, f.sy, f.sz, order, mc, nb, e2,
+                    s->pair_cells ? 1 : 0, per_point ? f.pp : nullptr, g.out);
+            },
+            [&](int64_t b, int64_t mc) -> int {
+                if (per_point)
+                    NBMI_HIP_CHECK(hipMemcpyAsync(per_point + b * cols, f.pp, (size_t)(mc * cols) * sizeof(int32_t),
+                                                  hipMemcpyDeviceToHost, st));
+                return 0;
+            });
+    });
+    if (rc) return rc;
+    unsigned long long h[kPairMaxBins + 3];
+    NBMI_HIP_CHECK(hipMemcpyAsync(h, g.out, (size_t)(nb + 3) * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    NBMI_HIP_CHECK(hipStreamSynchronize(st));
+    if (evals) *evals = (int64_t)h[0];
+    if (cell_pairs) *cell_pairs = (int64_t)h[1];
+    if (below) *below = (int64_t)h[2];
+    for (int k = 0; counts && k < nb; k++) counts[k] = (int64_t)h[3 + k];
+    return 0;
 }
 
 // The tidal tensor at every body's own position: nbmi_get_potentials_f64's build and lane setup, the rows written in the

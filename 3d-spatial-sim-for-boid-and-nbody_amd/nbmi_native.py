@@ -58,6 +58,7 @@ PROTOTYPES = {
     "nbmi_fof_catalogue": (C.c_int, [_vp, _dbl, _i64, _i64, _vp, _vp, _vp, _vp]),
     "nbmi_compute_group_colors": (C.c_int, [_vp, _dbl, _i64]),
     "nbmi_pair_counts": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "nbmi_pair_counts_at": (C.c_int, [_vp, _i64, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "nbmi_field_at": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp]),
     "nbmi_tidal_at": (C.c_int, [_vp, _i64, _vp, _vp, _vp]),
     "nbmi_get_tidal_f64": (C.c_int, [_vp, _vp, _vp]),

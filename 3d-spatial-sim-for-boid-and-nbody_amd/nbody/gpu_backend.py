@@ -649,18 +649,69 @@ class _HIPSimulation:
                                                         C.addressof(cells) if evals else None))
         return (counts, int(below.value), int(ev.value), int(cells.value)) if evals else (counts, int(below.value))
 
-    def correlation_function(self, edges, randoms):
-        """xi (nb,) float64: the natural estimator DD / RR x M (M - 1) / (N (N - 1)) - 1 of the two-point correlation
-        function, DD = this handle's pair_counts(edges), RR = those of the (M, 3) random catalogue ``randoms`` (a temporary
-        Barnes-Hut handle with unit masses at rest); nan where RR == 0."""
-        from nbody.pairs import xi_natural
+    # ---- counts about arbitrary points (include/nbmi.h nbmi_pair_counts_at) ----
+    def pair_counts_at(self, points, edges, per_point=False, evals=False):
+        """(counts int64 (nb,), below int) of the bodies about the (m, 3) ``points`` for the nb + 1 ``edges`` (as
+        pair_counts'): counts[k] = the number of (point, body) pairs with edges[k]^2 < d2 <= edges[k + 1]^2, below = those
+        with d2 <= edges[0]^2 - DR, exact, equal to a brute force; nothing is excluded, a point on a body counts that
+        body in ``below``.  ``per_point=True`` appends the (m, nb + 1) int32 rows whose column sums these are (column 0:
+        below; nbody/pairs.py has counts_within and sphere_density for them), ``evals=True`` appends evals, cell_pairs:
+        the distances the call evaluated and the pairs it counted through whole cells.  ValueError for a wrong shape or
+        bad edges (before the library is called), for a coordinate that is not finite or beyond 1e18, and where knn() is
+        refused; the call does not change what the next step computes."""
+        from nbody.pairs import check_edges
+        what = "pair_counts_at"
+        self._query_refuse(what)
+        p = np.ascontiguousarray(points, dtype=np.float64)
+        if p.ndim != 2 or p.shape[1] != 3:
+            raise ValueError(f"{what}: expected points of shape (m, 3), got {p.shape}")
+        e = np.ascontiguousarray(check_edges(edges))
+        m, nb = len(p), len(e) - 1
+        counts = np.zeros(nb, dtype=np.int64)
+        rows = np.zeros((m, nb + 1), dtype=np.int32) if per_point else None
+        below, ev, cells = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._query_call(what, self._lib.nbmi_pair_counts_at(self._h, m, _nat.ptr(p), nb, _nat.ptr(e), _nat.ptr(counts),
+                                                           C.addressof(below), _nat.ptr(rows),
+                                                           C.addressof(ev) if evals else None,
+                                                           C.addressof(cells) if evals else None))
+        out = (counts, int(below.value))
+        if per_point:
+            out += (rows,)
+        return out + (int(ev.value), int(cells.value)) if evals else out
+
+    def neighbour_counts(self, edges):
+        """(N, nb + 1) int32, in the caller's body order: pair_counts_at's per-point rows at the bodies' own positions
+        with 1 subtracted from column 0, the body itself.  Column 0 is then the number of OTHER bodies within edges[0] of
+        body i - its coincident twins among them -, column k + 1 the number in (edges[k], edges[k + 1]]."""
+        self._query_refuse("neighbour_counts")
+        rows = self.pair_counts_at(self.get_positions_f64(), edges, per_point=True)[2]
+        rows[:, 0] -= 1
+        return rows
+
+    def correlation_function(self, edges, randoms, estimator="natural"):
+        """xi (nb,) float64, the two-point correlation function from DD = this handle's pair_counts(edges) and RR = those
+        of the (M, 3) random catalogue ``randoms`` (a temporary Barnes-Hut handle with unit masses at rest).
+        ``estimator``: "natural", DD / RR x M (M - 1) / (N (N - 1)) - 1, nan where RR == 0; "landy-szalay" and
+        "davis-peebles" (nbody/pairs.py xi_landy_szalay, xi_davis_peebles) also take DR = pair_counts_at(randoms, edges),
+        the bodies counted about the random points.  ValueError for any other name."""
+        from nbody.pairs import xi_davis_peebles, xi_landy_szalay, xi_natural
+        what = "correlation_function"
+        if estimator not in ("natural", "landy-szalay", "davis-peebles"):
+            raise ValueError(f'{what}: estimator = {estimator!r} is none of "natural", "landy-szalay", "davis-peebles"')
+        self._query_refuse(what)
         r = _as_f64(randoms, (3,))
         dd = self.pair_counts(edges)[0]
+        if estimator != "natural":
+            dr = self.pair_counts_at(r, edges)[0]
+            if estimator == "davis-peebles":
+                return xi_davis_peebles(dd, dr, self.n, len(r))
         tmp = HIPBarnesHutSimulation(r, np.zeros_like(r), np.ones(len(r)), 1.0, 0.1, 1.0)
         try:
             rr = tmp.pair_counts(edges)[0]
         finally:
             tmp.close()
+        if estimator == "landy-szalay":
+            return xi_landy_szalay(dd, dr, rr, self.n, len(r))
         return xi_natural(dd, rr, self.n, len(r))
 
     def visible_points(self, cam_pos, cam_forward, cam_right, cam_up, tan_h, tan_v, far_dist):

@@ -69,3 +69,51 @@ def xi_natural(dd, rr, n, n_random):
     norm = float(n_random) * (float(n_random) - 1.0) / (float(n) * (float(n) - 1.0))
     out[ok] = dd[ok] / rr[ok] * norm - 1.0
     return out
+
+
+def _per_pair(count, total_pairs):
+    return np.asarray(count, dtype=np.float64) / total_pairs
+
+
+def xi_landy_szalay(dd, dr, rr, n, m):
+    """The Landy-Szalay estimator per bin, (DD' - 2 DR' + RR') / RR' with every count divided by its number of pairs:
+    DD' = dd / (n (n - 1) / 2), DR' = dr / (n m), RR' = rr / (m (m - 1) / 2) - dd and rr the unordered pair counts of the
+    n bodies and of the m random points, dr the cross counts of the bodies about the random points (pair_counts_at's
+    totals, every (point, body) pair once); nan where rr == 0."""
+    n, m = float(n), float(m)
+    dd_n = _per_pair(dd, n * (n - 1.0) / 2.0)
+    dr_n = _per_pair(dr, n * m)
+    rr_n = _per_pair(rr, m * (m - 1.0) / 2.0)
+    out = np.full(dd_n.shape, np.nan)
+    ok = np.asarray(rr) != 0
+    out[ok] = (dd_n[ok] - 2.0 * dr_n[ok] + rr_n[ok]) / rr_n[ok]
+    return out
+
+
+def xi_davis_peebles(dd, dr, n, m):
+    """The Davis-Peebles estimator per bin, (2 m / (n - 1)) dd / dr - 1: the unordered pair counts of the n bodies over
+    their cross counts about m random points; nan where dr == 0."""
+    dd = np.asarray(dd, dtype=np.float64)
+    dr = np.asarray(dr, dtype=np.float64)
+    out = np.full(dd.shape, np.nan)
+    ok = dr != 0.0
+    out[ok] = 2.0 * float(m) / (float(n) - 1.0) * dd[ok] / dr[ok] - 1.0
+    return out
+
+
+def counts_within(per_point):
+    """(m, nb + 1) int64 from pair_counts_at's per-point rows: column k = the number of bodies within edges[k] of the
+    point (the cumulative sum along the columns)."""
+    return np.cumsum(np.asarray(per_point, dtype=np.int64), axis=-1, dtype=np.int64)
+
+
+def sphere_density(per_point, edges, mass=1.0):
+    """(m, nb + 1) float64: ``mass`` x counts_within over the volume 4/3 pi edges[k]^3 of each sphere - the mean density
+    of bodies of that mass inside edges[k] of each point.  A zero radius gives +inf where the sphere holds a body, as
+    nbmi_get_densities_f64 does for r2_k == 0, and nan where it holds none."""
+    e = np.asarray(edges, dtype=np.float64).reshape(-1)
+    within = counts_within(per_point)
+    if within.shape[-1] != len(e):
+        raise ValueError(f"sphere_density: {len(e)} edges need rows of {len(e)} columns, not {within.shape[-1]}")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return float(mass) * within / (4.1887902047863905 * (e * e * e))

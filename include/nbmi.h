@@ -351,6 +351,49 @@ int nbmi_compute_group_colors(nbmi_sim *sim, double link, int64_t min_members);
 int nbmi_pair_counts(nbmi_sim *sim, int nb, const double *edges, int64_t *counts /* (nb,), may be NULL */,
                      int64_t *below /* may be NULL */, int64_t *evals /* may be NULL */, int64_t *cell_pairs /* may be NULL */);
 
+/* ---- exact counts about arbitrary points: DR(r), counts in spheres ---------------------------
+ * For each of m arbitrary points, the number of bodies per distance bin.  Of the handle's current float64 state, exactly
+ * (the kernel and the tests' NumPy restatement, tests/pairs_at_ref.py, both follow this text):
+ *   d2(i, j)          = (dx dx + dy dy) + dz dz with dx = x_j - p_i per component, body j minus point i, float64 in this
+ *                     association, no FMA.
+ *   edges, E[k]       exactly nbmi_pair_counts': 1 <= nb <= 64, nb + 1 finite float64, edges[0] >= 0, strictly increasing;
+ *                     E[k] = edges[k] * edges[k], one float64 product each on the host, finite and strictly increasing.
+ *   per_point[i][0]   = the number of bodies j with d2(i, j) <= E[0].
+ *   per_point[i][k+1] = the number of bodies j with E[k] < d2(i, j) <= E[k + 1].  The upper edge belongs to the bin.
+ *   below, counts[k]  = the sums of column 0 and of column k + 1 over the m points: DR, every (point, body) pair once.
+ * Nothing is excluded: a point is not a body, and a point that coincides with a body counts that body in column 0.  With
+ * points = nbmi_get_positions_f64, column 0 of row i holds body i itself, its coincident twins and the bodies within
+ * edges[0] of it; then counts[k] = 2 nbmi_pair_counts' counts[k] and below = 2 nbmi_pair_counts' below + N.
+ * The counts are integers, the totals summed by integer atomics: every value is unique and independent of any order of
+ * evaluation, and equals a brute force's exactly.  A point's row does not depend on the other points of the call, on
+ * their order or on how the call is split: two calls give the same numbers, duplicated points give identical rows, a
+ * permutation of the points permutes the rows.  A quadrupole or leapfrog handle returns a plain handle's numbers.
+ * counts ((nb,) int64), below, per_point ((m, nb + 1) int32, row-major), evals and cell_pairs may each be NULL.
+ *   *evals      = the number of d2 the call evaluated;
+ *   *cell_pairs = the number of (point, body) pairs it counted through whole cells, without a d2.
+ * Both are measurement hooks as in nbmi_pair_counts.
+ * m == 0: success, counts, below, evals and cell_pairs are zeroed and nothing else is touched.  N == 0: zeros.  N == 1 is
+ * served by the tree like every other N (its root is a leaf); nothing is answered on the host.
+ * Refused with NBMI_ERR_ARG, message "nbmi_pair_counts_at: ...", before anything is launched and with every output
+ * untouched: m < 0, null points_xyz with m > 0, a coordinate that is not finite or exceeds 1e18 in magnitude (the message
+ * names the first bad row), nb or edges that nbmi_pair_counts refuses, and the handles nbmi_knn refuses (direct N^2, owner
+ * mode, a proper shard).  Points may lie anywhere, outside the root cube too.
+ * The call is synchronous.  It changes nothing that a later step or query reads (state and its order, the tree header -
+ * saved and restored -, the "auto" precision flags and force_all64 - the build runs without a dt -, the step count, the
+ * stored leapfrog acceleration, the tracers and their scratch).  NBMI_ERR_CAPACITY of the call's own tree build is
+ * reported with a step's message.
+ * The points are processed as nbmi_field_at's - chunks of at most 1 048 576, walked in key order within a chunk of more
+ * than 64, NBMI_FIELD_SORT=0 honoured - through nbmi_field_at's scratch (allocated by whichever call comes first), and the
+ * tree side is nbmi_pair_counts' (4 bytes per node row, 536 bytes of results, and the shared 32 bytes per node row and 4
+ * bytes per 64 bodies).  per_point costs 4 (nb + 1) bytes per row of that scratch more - at most 272 MB, at nb = 64 and
+ * a full chunk; the chunk is not made smaller for it - allocated by the first call that asks for per_point, regrown by a
+ * call that needs more and freed with the scratch.
+ * NBMI_PAIRS_CELLS=0 is honoured as in nbmi_pair_counts: same numbers, cell_pairs == 0. */
+int nbmi_pair_counts_at(nbmi_sim *sim, int64_t m, const double *points_xyz /* (m,3) */, int nb,
+                        const double *edges /* nb+1 */, int64_t *counts /* (nb,), may be NULL */,
+                        int64_t *below /* may be NULL */, int32_t *per_point /* (m, nb+1), may be NULL */,
+                        int64_t *evals /* may be NULL */, int64_t *cell_pairs /* may be NULL */);
+
 /* The gravitational field of the handle's current float64 state at m arbitrary points: what a
  * test particle at points_xyz[i] would feel.  The kernels and the tests' NumPy restatement (tests/field_ref.py) both
  * follow this text.  All arithmetic is float64 in the association written, without FMA contraction.
