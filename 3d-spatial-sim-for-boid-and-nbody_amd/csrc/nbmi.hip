@@ -152,6 +152,11 @@ struct TreeInfo {
 // ---------------------------------------------------------------------------------------
 // small device helpers
 // ---------------------------------------------------------------------------------------
+// The build did not fit (this build, or an earlier one that nobody has reported yet): a kernel that reads the tree does
+// nothing, the host reports it.
+__device__ __forceinline__ bool tree_frozen(const TreeInfo *info) {
+    return info->error != 0 || info->sticky_error != 0;
+}
 __device__ __forceinline__ double wave_max(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
@@ -1560,7 +1565,7 @@ __device__ __forceinline__ WalkCtx lane_prologue(const Node *nodes, const float4
     WalkCtx C;
     C.nodes = nodes;
     C.valid = rank < rank_end;
-    C.frozen = info_in->error != 0 || info_in->sticky_error != 0;
+    C.frozen = tree_frozen(info_in);
     C.rows = walk_rows(info_in, C.frozen);
     C.band2 = __builtin_amdgcn_readfirstlane(info_in->band2);
     C.px = C.py = C.pz = 0.f;
@@ -3339,7 +3344,7 @@ __global__ __launch_bounds__(kBlock) void k_potential_tree(const Node *__restric
                                                            const float4 *__restrict__ posm_s, const uint32_t *__restrict__ perm,
                                                            int curbuf, float eps2f, int64_t n, double *__restrict__ phi,
                                                            int32_t *__restrict__ cnt, const double *__restrict__ quad) {
-    if (info->error != 0 || info->sticky_error != 0) return;  // the tree did not fit: the caller reports it
+    if (tree_frozen(info)) return;  // the tree did not fit: the caller reports it
     const int64_t rank = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     const WalkCtx C = lane_prologue(nodes, posm_s, perm, rank, n, info, tab, curbuf);
     const Lane64 L = lane_f64(C);
@@ -3546,36 +3551,47 @@ __global__ __launch_bounds__(kBlock) void k_walk_quad(const Node *__restrict__ n
     }
 }
 
-// Direct potential: phi_i = -sum_{j != i} G m_j / sqrt(|x_j - x_i|^2 + eps^2), float64 bodies staged through LDS
-// tiles of kBlock, every thread one body, j in index order.  eps == 0: pairs at zero distance are skipped (k_direct's
-// guard).  (Not field_direct_sum: this guard counts a coincident distinct body when eps > 0, the probe sum's skips it.)
-__global__ __launch_bounds__(kBlock) void k_potential_direct(Bodies cur, int64_t n, double G, double eps2,
-                                                             double *__restrict__ phi, int32_t *__restrict__ cnt) {
-    __shared__ double4 tile[kBlock];
+// The tile loop of every direct sum over the bodies (potential, field, tidal tensor): the float64 bodies staged through
+// `tile` (kBlock rows of shared memory) as {x, y, z, G m}, kBlock at a time, and term(row, j) for every body j in index
+// order.  Every thread of the block calls it; guard and arithmetic are the caller's.
+template <class Term>
+__device__ __forceinline__ void direct_tiles(const Bodies &cur, int64_t n, double G, double4 *tile, Term term) {
     const int t = threadIdx.x;
-    const int64_t i = (int64_t)blockIdx.x * kBlock + t;
-    const bool valid = i < n;
-    double x = 0.0, y = 0.0, z = 0.0;
-    if (valid) { x = cur.x[i]; y = cur.y[i]; z = cur.z[i]; }
-    double acc = 0.0;
-    int32_t terms = 0;
     for (int64_t base = 0; base < n; base += kBlock) {
         const int64_t jj = base + t;
         tile[t] = jj < n ? make_double4(cur.x[jj], cur.y[jj], cur.z[jj], G * cur.m[jj]) : make_double4(0.0, 0.0, 0.0, 0.0);
         __syncthreads();
         const int lim = n - base < kBlock ? (int)(n - base) : kBlock;
-        const int self = (int)(i - base);  // this body's slot in the tile (outside [0, lim) when it is not in it)
         for (int k = 0; k < lim; k++) {
             const double4 q = tile[k];
-            const double ex = q.x - x, ey = q.y - y, ez = q.z - z;
-            const double d2 = ex * ex + ey * ey + ez * ez + eps2;
-            if (k != self && d2 > 0.0) {
-                acc -= q.w / sqrt(d2);
-                terms++;
-            }
+            term(q, base + k);
         }
         __syncthreads();
     }
+}
+
+// Direct potential: phi_i = -sum_{j != i} G m_j / sqrt(|x_j - x_i|^2 + eps^2), every thread one body, j in index order
+// (direct_tiles).  eps == 0: pairs at zero distance are skipped (k_direct's guard).  (Not field_direct_sum: this guard
+// counts a coincident distinct body when eps > 0, the probe sum's skips it.)
+__global__ __launch_bounds__(kBlock) void k_potential_direct(Bodies cur, int64_t n, double G, double eps2,
+                                                             double *__restrict__ phi, int32_t *__restrict__ cnt) {
+    __shared__ double4 tile[kBlock];
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const bool valid = i < n;
+    double x = 0.0, y = 0.0, z = 0.0;
+    if (valid) { x = cur.x[i]; y = cur.y[i]; z = cur.z[i]; }
+    double acc = 0.0;
+    int32_t terms = 0;
+    direct_tiles(cur, n, G, tile, [&](const double4 &q, int64_t j) {
+        const double ex = q.x - x, ey = q.y - y, ez = q.z - z;
+        const double d2 = ex * ex + ey * ey + ez * ez + eps2;
+        // j != i, on the low words: rows stay below kMaxBodies + kBlock < 2^32.  (The 64-bit comparison keeps both halves
+        // of i and of the tile's base in registers through the loop: 36 VGPRs / 38 SGPRs for 34 / 36.)
+        if ((uint32_t)j != (uint32_t)i && d2 > 0.0) {
+            acc -= q.w / sqrt(d2);
+            terms++;
+        }
+    });
     if (valid) {
         phi[i] = acc;
         cnt[i] = terms;
@@ -3679,7 +3695,7 @@ __global__ __launch_bounds__(kBlock) void k_query_rows(const Node *__restrict__ 
                                                        const int32_t *__restrict__ node_ref, const uint32_t *__restrict__ perm,
                                                        Bodies cur, const TreeInfo *__restrict__ info, int64_t capacity,
                                                        double4 *__restrict__ rows, uint32_t *__restrict__ wleaf) {
-    if (info->error != 0 || info->sticky_error != 0) return;  // the tree did not fit: the caller reports it
+    if (tree_frozen(info)) return;  // the tree did not fit: the caller reports it
     const int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (idx >= info->num_nodes || idx >= capacity) return;
     const int32_t r = node_ref[idx];
@@ -3750,22 +3766,29 @@ __device__ __forceinline__ QueryGroup query_group(const Bodies &cur, const uint3
 struct QueryCtx {
     bool frozen, valid;
     int lane;
-    int64_t w0, rank;
+    int64_t count, w0, rank;  // count: the bodies or points of the grid, 0 where frozen (such a wave has no valid lane)
     unsigned nn;
     QueryGroup own;
     double qx, qy, qz;
 };
-__device__ __forceinline__ QueryCtx query_prologue(const TreeInfo *__restrict__ info, const Bodies &cur,
-                                                   const uint32_t *__restrict__ perm, int64_t n) {
+// What does not depend on whose point the lane has - frozen, count, lane, w0, rank, valid, nn - for a grid over `count`
+// bodies or points.  `own` and the query point are the caller's to fill.
+__device__ __forceinline__ QueryCtx query_wave(const TreeInfo *__restrict__ info, int64_t count) {
     QueryCtx C;
-    C.frozen = info->error != 0 || info->sticky_error != 0;
-    const int64_t bodies = C.frozen ? 0 : n;  // (a frozen wave has no valid lane and loads nothing)
+    C.frozen = tree_frozen(info);
+    C.count = C.frozen ? 0 : count;
     C.lane = threadIdx.x;
     C.w0 = (int64_t)blockIdx.x * kQueryBlock;
     C.rank = C.w0 + C.lane;
-    C.valid = C.rank < bodies;
+    C.valid = C.rank < C.count;
     C.nn = __builtin_amdgcn_readfirstlane((unsigned)info->num_nodes * kNodeBytes);
-    C.own = query_group(cur, perm, C.w0, bodies);
+    return C;
+}
+// a body in the lane: the query point is the wave's own body of that lane
+__device__ __forceinline__ QueryCtx query_prologue(const TreeInfo *__restrict__ info, const Bodies &cur,
+                                                   const uint32_t *__restrict__ perm, int64_t n) {
+    QueryCtx C = query_wave(info, n);
+    C.own = query_group(cur, perm, C.w0, C.count);  // (a frozen wave loads nothing)
     C.qx = C.own.x; C.qy = C.own.y; C.qz = C.own.z;
     return C;
 }
@@ -3979,7 +4002,7 @@ __global__ __launch_bounds__(kBlock) void k_fof_flatten(const TreeInfo *__restri
                                                         const int32_t *__restrict__ parent, const uint32_t *__restrict__ perm,
                                                         const int32_t *__restrict__ id, int32_t *__restrict__ root,
                                                         int32_t *__restrict__ minid, int32_t *__restrict__ cnt) {
-    if (info->error != 0 || info->sticky_error != 0) return;
+    if (tree_frozen(info)) return;
     const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     fof_flatten(r, n, parent, root, minid, cnt, [&](int64_t q) { return id[perm[q]]; });
 }
@@ -3988,7 +4011,7 @@ __global__ __launch_bounds__(kBlock) void k_fof_labels(const TreeInfo *__restric
                                                        const int32_t *__restrict__ root, const int32_t *__restrict__ minid,
                                                        const uint32_t *__restrict__ perm, const int32_t *__restrict__ id,
                                                        int32_t *__restrict__ labels, unsigned long long *__restrict__ n_roots) {
-    if (info->error != 0 || info->sticky_error != 0) return;
+    if (tree_frozen(info)) return;
     const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     const bool is_root = r < n && root[r] == (int32_t)r;
     if (r < n && labels) labels[id[perm[r]]] = minid[root[r]];
@@ -4002,7 +4025,7 @@ __global__ __launch_bounds__(kBlock) void k_fof_colors(const TreeInfo *__restric
                                                        const int32_t *__restrict__ cnt, const uint32_t *__restrict__ perm,
                                                        const int32_t *__restrict__ id, int64_t min_members,
                                                        float *__restrict__ colors) {
-    if (info->error != 0 || info->sticky_error != 0) return;
+    if (tree_frozen(info)) return;
     const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (r >= n) return;
     const int32_t f = root[r];
@@ -4203,7 +4226,7 @@ struct PairEdges {
 __global__ __launch_bounds__(kBlock) void k_pair_cells(const Node *__restrict__ nodes, const int32_t *__restrict__ node_ref,
                                                        const TreeInfo *__restrict__ info, int64_t n, int64_t capacity,
                                                        int32_t *__restrict__ cnt) {
-    if (info->error != 0 || info->sticky_error != 0) return;
+    if (tree_frozen(info)) return;
     const int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     const int64_t num_nodes = info->num_nodes;
     if (idx >= num_nodes || idx >= capacity) return;
@@ -4255,6 +4278,58 @@ __device__ __forceinline__ int pair_bin(const double *__restrict__ E, int nb, do
     }
     return pos;
 }
+// The counters of a wave of K18 / K28 and what is done with them.  Dynamic LDS (pair_lds_bytes): E[nb + 1], then nb + 1
+// uint32 per lane, [counter][lane] - consecutive lanes, consecutive words, no bank conflicts; a lane counts at most n < 2^31
+// bodies.  The E[k] sit in LDS in front of the counters because the search's indices diverge by lane.
+struct PairCounters {
+    double *E;
+    uint32_t *c;  // the lane's column: counter k at c[64 k]
+    int nb;
+    long long whole;  // bodies this lane counted through whole cells
+    __device__ __forceinline__ void init(const PairEdges &edges, int bins, int lane) {
+        extern __shared__ double pair_lds[];
+        nb = bins;
+        whole = 0;
+        E = pair_lds;
+        c = reinterpret_cast<uint32_t *>(pair_lds + nb + 1) + lane;
+        for (int k = 0; k <= nb; k++) {
+            E[k] = edges.e2[k];  // (every lane stores the same value)
+            c[64 * k] = 0u;
+        }
+        __syncthreads();
+    }
+    __device__ __forceinline__ void count(double d2) {
+        const int b = pair_bin(E, nb, d2);
+        if (b <= nb) c[64 * b]++;
+    }
+    // An internal cell for an active lane (query_walk_cells' `cell`: true = it stays open), with p = pair_bin(query_lower):
+    // pruned if p > nb; counted whole, cnt[idx] bodies into counter p, if accept() and query_upper <= E[p]; else open.
+    // accept() is the caller's say on whole cells, asked only about a cell that was not pruned.
+    template <class Accept>
+    __device__ __forceinline__ bool cell(unsigned idx, const double4 &row, const QueryCtx &C, const int32_t *__restrict__ cnt,
+                                         Accept accept) {
+        const int p = pair_bin(E, nb, query_lower(row, C.qx, C.qy, C.qz));
+        if (p > nb) return false;  // pruned
+        if (!accept()) return true;
+        if (!(query_upper(row, C.qx, C.qy, C.qz) <= E[p])) return true;
+        const uint32_t m = (uint32_t)cnt[idx];
+        c[64 * p] += m;
+        whole += (long long)m;
+        return false;
+    }
+    // the lane's nb + 1 counters as int32 (K28's row of a point)
+    __device__ __forceinline__ void store_row(int32_t *__restrict__ row) const {
+        for (int k = 0; k <= nb; k++) row[k] = (int32_t)c[64 * k];
+    }
+    // every counter summed over the wave in 64 bits and added to out[2 + counter] (nbmi::wave_add); out[0] += distances
+    // evaluated, out[1] += bodies counted through whole cells
+    __device__ __forceinline__ void flush(unsigned long long *__restrict__ out, long long evals, int lane) const {
+        for (int k = 0; k <= nb; k++) nbmi::wave_add(out + 2 + k, (long long)c[64 * k], lane);
+        nbmi::wave_add(out, evals, lane);
+        nbmi::wave_add(out + 1, whole, lane);
+    }
+};
+constexpr size_t pair_lds_bytes(int nb) { return (size_t)(nb + 1) * (sizeof(double) + kQueryBlock * sizeof(uint32_t)); }
 // One wave per 64 key-adjacent bodies, as k_fof_link: pairs inside the wave directly (query_half_search), every other
 // pair by the walk that starts at the wave's own first leaf and skips the leaves of the ranks below w0 + 64 - the wave
 // sees exactly the bodies of a higher rank, every pair of two waves once.  At an internal cell an active lane, in this order:
@@ -4266,64 +4341,47 @@ __device__ __forceinline__ int pair_bin(const double *__restrict__ E, int nb, do
 // A cell whose ranks reach below w0 + 64 is NEVER accepted whole (it may be pruned): it holds bodies of the wave itself,
 // already counted directly, the lane's own among them.  The walk begins behind the leaf of rank w0, so every cell it
 // meets starts above w0 and the condition is node_ref < w0 + 64, wave-uniform.  accept = 0 (NBMI_PAIRS_CELLS=0) accepts
-// nothing.
-// Counters: nb + 1 uint32 per lane in LDS, [counter][lane] - consecutive lanes, consecutive words, no bank conflicts; a
-// lane counts at most n - 1 < 2^31 pairs.  The E[k] sit in LDS in front of them (the search's indices diverge by lane).
-// At the end every counter is summed over the wave in 64 bits and added to out[2 + counter] (nbmi::wave_add).  out[0] +=
-// distances evaluated, out[1] += pairs counted through whole cells.
+// nothing.  Counters and sums: PairCounters.
 __global__ __launch_bounds__(kQueryBlock) void k_pair_counts(const Node *__restrict__ nodes, const double4 *__restrict__ rows,
                                                             const int32_t *__restrict__ node_ref,
                                                             const int32_t *__restrict__ cnt, const TreeInfo *__restrict__ info,
                                                             const uint32_t *__restrict__ perm, Bodies cur, int64_t n, int nb,
                                                             PairEdges edges, int accept, const uint32_t *__restrict__ wleaf,
                                                             unsigned long long *__restrict__ out) {
-    extern __shared__ double pair_lds[];  // E[nb + 1], then uint32 [nb + 1][64]
     const QueryCtx C = query_prologue(info, cur, perm, n);
     if (C.frozen) return;
-    double *E = pair_lds;
-    uint32_t *c = reinterpret_cast<uint32_t *>(pair_lds + nb + 1) + C.lane;
-    for (int k = 0; k <= nb; k++) {
-        E[k] = edges.e2[k];  // (every lane stores the same value)
-        c[64 * k] = 0u;
-    }
-    __syncthreads();
-    long long evals = 0, whole = 0;
-    const auto count = [&](double d2) {
-        const int b = pair_bin(E, nb, d2);
-        if (b <= nb) c[64 * b]++;
-    };
-    query_half_search(C, n, evals, [&](double d2, int64_t) { count(d2); });
+    PairCounters K;
+    K.init(edges, nb, C.lane);
+    long long evals = 0;
+    query_half_search(C, n, evals, [&](double d2, int64_t) { K.count(d2); });
     const unsigned start = __builtin_amdgcn_readfirstlane(wleaf[blockIdx.x]) * kNodeBytes;
     const int64_t own_end = C.w0 + kQueryBlock;
     query_walk_cells(
         nodes, rows, node_ref, start, C, (int64_t)0, own_end, evals,
         [&](unsigned idx, const double4 &row, unsigned) {
-            const int p = pair_bin(E, nb, query_lower(row, C.qx, C.qy, C.qz));
-            if (p > nb) return false;  // pruned
-            if (!accept || (int64_t)node_ref[idx] < own_end) return true;
-            if (!(query_upper(row, C.qx, C.qy, C.qz) <= E[p])) return true;
-            const uint32_t m = (uint32_t)cnt[idx];
-            c[64 * p] += m;
-            whole += (long long)m;
-            return false;
+            return K.cell(idx, row, C, cnt, [&] { return accept && (int64_t)node_ref[idx] >= own_end; });  // (a cell of the wave's own stays open)
         },
-        [&](double d2, const double4 &, int64_t) { count(d2); });
-    for (int k = 0; k <= nb; k++) nbmi::wave_add(out + 2 + k, (long long)c[64 * k], C.lane);
-    nbmi::wave_add(out, evals, C.lane);
-    nbmi::wave_add(out + 1, whole, C.lane);
+        [&](double d2, const double4 &, int64_t) { K.count(d2); });
+    K.flush(out, evals, C.lane);
 }
 
 // ---------------------------------------------------------------------------------------
 // K28: exact counts of the bodies per distance bin about arbitrary points (nbmi_pair_counts_at; include/nbmi.h, DESIGN.md
-// section 4.28).  K18's counting with K19's lane setup: one wave per 64 probes of a chunk, lane `rank` has row `rank` of
-// the probe columns (probe_order_chunk), and walks the WHOLE tree from the root - a point is no body, so there is no
-// half search, no own leaves to skip (ex_lo = ex_hi = 0) and no own-wave condition on a whole cell.  At an internal cell
-// an active lane, with p = pair_bin(query_lower): prunes if p > nb; accepts whole if `accept` and query_upper <= E[p],
-// cnt bodies into counter p; else keeps the cell open.  A leaf's d2 is binned.
-// LDS as k_pair_counts: E[nb + 1], then uint32 [nb + 1][64]; a lane counts at most n < 2^31 bodies.  At the end a valid
-// lane stores its nb + 1 counters as int32 to row order[rank] of per_point (null: not asked for; the stores of a wave are
-// nb + 1 words apart), then every counter is summed over the wave in 64 bits and added to out[2 + counter], which
-// accumulates over the chunks of a call; out[0] += distances evaluated, out[1] += bodies counted through whole cells.
+// section 4.28).  K18's counting (PairCounters) with K19's lanes: one wave per 64 probes of a chunk, lane `rank` has row
+// `rank` of the probe columns (probe_order_chunk), each walking the WHOLE tree from the root - a point is no body, so
+// there is no half search, there are no own leaves to skip (ex_lo = ex_hi = 0) and no own-wave condition on a whole
+// cell.  At the end a valid lane also stores its nb + 1 counters to row order[rank] of per_point (null: not asked for;
+// the stores of a wave are nb + 1 words apart); out accumulates over the chunks of a call.
+// ---------------------------------------------------------------------------------------
+// a probe in the lane: the query point is row `rank` of the columns, the wave has no bodies of its own
+__device__ __forceinline__ QueryCtx query_prologue(const TreeInfo *__restrict__ info, const double *__restrict__ sx,
+                                                   const double *__restrict__ sy, const double *__restrict__ sz, int64_t mc) {
+    QueryCtx C = query_wave(info, mc);
+    C.own = QueryGroup{0.0, 0.0, 0.0, 0.0, C.w0};
+    C.qx = C.qy = C.qz = 0.0;
+    if (C.valid) { C.qx = sx[C.rank]; C.qy = sy[C.rank]; C.qz = sz[C.rank]; }
+    return C;
+}
 __global__ __launch_bounds__(kQueryBlock) void k_pair_counts_at(const Node *__restrict__ nodes, const double4 *__restrict__ rows,
                                                                const int32_t *__restrict__ node_ref,
                                                                const int32_t *__restrict__ cnt, const TreeInfo *__restrict__ info,
@@ -4332,49 +4390,17 @@ __global__ __launch_bounds__(kQueryBlock) void k_pair_counts_at(const Node *__re
                                                                int64_t mc, int nb, PairEdges edges, int accept,
                                                                int32_t *__restrict__ per_point,
                                                                unsigned long long *__restrict__ out) {
-    extern __shared__ double pair_at_lds[];  // E[nb + 1], then uint32 [nb + 1][64]
-    QueryCtx C;
-    C.frozen = info->error != 0 || info->sticky_error != 0;  // as query_prologue
-    if (C.frozen) return;
-    C.lane = threadIdx.x;
-    C.w0 = (int64_t)blockIdx.x * kQueryBlock;
-    C.rank = C.w0 + C.lane;
-    C.valid = C.rank < mc;
-    C.nn = __builtin_amdgcn_readfirstlane((unsigned)info->num_nodes * kNodeBytes);
-    C.own = QueryGroup{0.0, 0.0, 0.0, 0.0, C.w0};  // (no bodies of its own)
-    C.qx = C.qy = C.qz = 0.0;
-    if (C.valid) { C.qx = sx[C.rank]; C.qy = sy[C.rank]; C.qz = sz[C.rank]; }
-    double *E = pair_at_lds;
-    uint32_t *c = reinterpret_cast<uint32_t *>(pair_at_lds + nb + 1) + C.lane;
-    for (int k = 0; k <= nb; k++) {
-        E[k] = edges.e2[k];  // (every lane stores the same value)
-        c[64 * k] = 0u;
-    }
-    __syncthreads();
-    long long evals = 0, whole = 0;
+    if (tree_frozen(info)) return;  // (before the lane loads its point)
+    const QueryCtx C = query_prologue(info, sx, sy, sz, mc);
+    PairCounters K;
+    K.init(edges, nb, C.lane);
+    long long evals = 0;
     query_walk_cells(
         nodes, rows, node_ref, 0u, C, (int64_t)0, (int64_t)0, evals,
-        [&](unsigned idx, const double4 &row, unsigned) {
-            const int p = pair_bin(E, nb, query_lower(row, C.qx, C.qy, C.qz));
-            if (p > nb) return false;  // pruned
-            if (!accept) return true;
-            if (!(query_upper(row, C.qx, C.qy, C.qz) <= E[p])) return true;
-            const uint32_t m = (uint32_t)cnt[idx];
-            c[64 * p] += m;
-            whole += (long long)m;
-            return false;
-        },
-        [&](double d2, const double4 &, int64_t) {
-            const int b = pair_bin(E, nb, d2);
-            if (b <= nb) c[64 * b]++;
-        });
-    if (per_point && C.valid) {
-        int32_t *row = per_point + (order ? (int64_t)order[C.rank] : C.rank) * (nb + 1);
-        for (int k = 0; k <= nb; k++) row[k] = (int32_t)c[64 * k];
-    }
-    for (int k = 0; k <= nb; k++) nbmi::wave_add(out + 2 + k, (long long)c[64 * k], C.lane);
-    nbmi::wave_add(out, evals, C.lane);
-    nbmi::wave_add(out + 1, whole, C.lane);
+        [&](unsigned idx, const double4 &row, unsigned) { return K.cell(idx, row, C, cnt, [&] { return accept != 0; }); },
+        [&](double d2, const double4 &, int64_t) { K.count(d2); });
+    if (per_point && C.valid) K.store_row(per_point + (order ? (int64_t)order[C.rank] : C.rank) * (nb + 1));
+    K.flush(out, evals, C.lane);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -4423,7 +4449,7 @@ __global__ __launch_bounds__(kBlock) void k_field_tree(const Node *__restrict__ 
                                                        float eps2f, double eps, double pmax, const double *__restrict__ quad,
                                                        double *__restrict__ acc_out, double *__restrict__ phi_out,
                                                        int32_t *__restrict__ cnt_out) {
-    if (info->error != 0 || info->sticky_error != 0) return;  // the tree did not fit: the caller reports it
+    if (tree_frozen(info)) return;  // the tree did not fit: the caller reports it
     const int64_t rank = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     const bool valid = rank < m;
     double qx = 0.0, qy = 0.0, qz = 0.0;
@@ -4438,34 +4464,25 @@ __global__ __launch_bounds__(kBlock) void k_field_tree(const Node *__restrict__ 
     }
 }
 
-// Direct handle: the sum over all bodies in body order, k_potential_direct's twin with a point in the thread.  The only
-// guard is the definition's dist_sq > eps^2.
+// Direct handle: the sum over all bodies in body order (direct_tiles) with a point in the thread.  The only guard is the
+// definition's dist_sq > eps^2.
 // The sum itself, shared by k_field_direct and k_tracer_direct; every thread of the block calls it (`tile`: kBlock rows of
 // shared memory).
 __device__ __forceinline__ FieldSum field_direct_sum(const Bodies &cur, int64_t n, double G, double eps2, double x, double y, double z,
                                                      double4 *tile) {
-    const int t = threadIdx.x;
     double ax = 0.0, ay = 0.0, az = 0.0, phi = 0.0;
     int32_t terms = 0;
-    for (int64_t base = 0; base < n; base += kBlock) {
-        const int64_t jj = base + t;
-        tile[t] = jj < n ? make_double4(cur.x[jj], cur.y[jj], cur.z[jj], G * cur.m[jj]) : make_double4(0.0, 0.0, 0.0, 0.0);
-        __syncthreads();
-        const int lim = n - base < kBlock ? (int)(n - base) : kBlock;
-        for (int k = 0; k < lim; k++) {
-            const double4 q = tile[k];
-            const double ex = q.x - x, ey = q.y - y, ez = q.z - z;
-            const double d2 = ex * ex + ey * ey + ez * ez + eps2;
-            if (d2 > eps2) {
-                const double dist = sqrt(d2);
-                const double w = q.w / (dist * d2);
-                phi -= q.w / dist;
-                ax += ex * w; ay += ey * w; az += ez * w;
-                terms++;
-            }
+    direct_tiles(cur, n, G, tile, [&](const double4 &q, int64_t) {
+        const double ex = q.x - x, ey = q.y - y, ez = q.z - z;
+        const double d2 = ex * ex + ey * ey + ez * ez + eps2;
+        if (d2 > eps2) {
+            const double dist = sqrt(d2);
+            const double w = q.w / (dist * d2);
+            phi -= q.w / dist;
+            ax += ex * w; ay += ey * w; az += ez * w;
+            terms++;
         }
-        __syncthreads();
-    }
+    });
     return FieldSum{ax, ay, az, phi, terms};
 }
 
@@ -4499,7 +4516,7 @@ __device__ __forceinline__ double tidal_norm(const TidalSum &f) {
     return sqrt(((f.xx * f.xx + f.yy * f.yy) + f.zz * f.zz) + 2.0 * ((f.xy * f.xy + f.xz * f.xz) + f.yz * f.yz));
 }
 
-// k_field_tree's twin: one chunk of probes, results at the probe's row of the chunk.
+// One chunk of probes, the lane as k_field_tree's; results at the probe's row of the chunk.
 template <bool kQuad>
 __global__ __launch_bounds__(kBlock) void k_tidal_tree(const Node *__restrict__ nodes, const double4 *__restrict__ pot,
                                                        const WalkTable *tab, const TreeInfo *info,
@@ -4507,7 +4524,7 @@ __global__ __launch_bounds__(kBlock) void k_tidal_tree(const Node *__restrict__ 
                                                        const double *__restrict__ sz, const uint32_t *__restrict__ order, int64_t m,
                                                        float eps2f, double eps, double pmax, const double *__restrict__ quad,
                                                        double *__restrict__ t6_out, int32_t *__restrict__ cnt_out) {
-    if (info->error != 0 || info->sticky_error != 0) return;  // the tree did not fit: the caller reports it
+    if (tree_frozen(info)) return;  // the tree did not fit: the caller reports it
     const int64_t rank = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     const bool valid = rank < m;
     double qx = 0.0, qy = 0.0, qz = 0.0;
@@ -4521,7 +4538,7 @@ __global__ __launch_bounds__(kBlock) void k_tidal_tree(const Node *__restrict__ 
     }
 }
 
-// k_potential_tree's twin: a body in the lane, the build's band.  Rows land in the caller's order, id[j] (either output
+// A body in the lane (lane_prologue, as k_potential_tree), the build's band.  Rows land in the caller's order, id[j] (either output
 // may be null).
 template <bool kQuad>
 __global__ __launch_bounds__(kBlock) void k_tidal_bodies(const Node *__restrict__ nodes, const double4 *__restrict__ pot,
@@ -4530,7 +4547,7 @@ __global__ __launch_bounds__(kBlock) void k_tidal_bodies(const Node *__restrict_
                                                          int curbuf, float eps2f, int64_t n, const int32_t *__restrict__ id,
                                                          double *__restrict__ t6_out, double *__restrict__ norm_out,
                                                          const double *__restrict__ quad) {
-    if (info->error != 0 || info->sticky_error != 0) return;  // the tree did not fit: the caller reports it
+    if (tree_frozen(info)) return;  // the tree did not fit: the caller reports it
     const int64_t rank = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     const WalkCtx C = lane_prologue(nodes, posm_s, perm, rank, n, info, tab, curbuf);
     const Lane64 L = lane_f64(C);
@@ -4543,15 +4560,14 @@ __global__ __launch_bounds__(kBlock) void k_tidal_bodies(const Node *__restrict_
     }
 }
 
-// Direct handle: the sum over all bodies in body order with the one guard dist_sq > eps^2, field_direct_sum's tile loop.
+// Direct handle: the sum over all bodies in body order (direct_tiles) with the one guard dist_sq > eps^2.
 // pts != null: point i of (m, 3) rows, results at row i.  pts == null: state row i of the m = n bodies (its own term
 // has d = 0 and is dropped by the guard), results at the caller's row id[i].
 __global__ __launch_bounds__(kBlock) void k_tidal_direct(Bodies cur, int64_t n, double G, double eps2, const double *__restrict__ pts,
                                                          int64_t m, double *__restrict__ t6_out, double *__restrict__ norm_out,
                                                          int32_t *__restrict__ cnt_out) {
     __shared__ double4 tile[kBlock];
-    const int t = threadIdx.x;
-    const int64_t i = (int64_t)blockIdx.x * kBlock + t;
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     const bool valid = i < m;
     double x = 0.0, y = 0.0, z = 0.0;
     if (valid) {
@@ -4559,25 +4575,17 @@ __global__ __launch_bounds__(kBlock) void k_tidal_direct(Bodies cur, int64_t n, 
         else { x = cur.x[i]; y = cur.y[i]; z = cur.z[i]; }
     }
     TidalSum f{0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0};
-    for (int64_t base = 0; base < n; base += kBlock) {
-        const int64_t jj = base + t;
-        tile[t] = jj < n ? make_double4(cur.x[jj], cur.y[jj], cur.z[jj], G * cur.m[jj]) : make_double4(0.0, 0.0, 0.0, 0.0);
-        __syncthreads();
-        const int lim = n - base < kBlock ? (int)(n - base) : kBlock;
-        for (int k = 0; k < lim; k++) {
-            const double4 q = tile[k];
-            const double ex = q.x - x, ey = q.y - y, ez = q.z - z;
-            const double d2 = ex * ex + ey * ey + ez * ez + eps2;
-            if (d2 > eps2) {
-                const double dist = sqrt(d2);
-                const double w = q.w / (dist * d2), w5 = (3.0 * w) / d2;
-                f.xx += (ex * ex) * w5 - w; f.yy += (ey * ey) * w5 - w; f.zz += (ez * ez) * w5 - w;
-                f.xy += (ex * ey) * w5; f.xz += (ex * ez) * w5; f.yz += (ey * ez) * w5;
-                f.terms++;
-            }
+    direct_tiles(cur, n, G, tile, [&](const double4 &q, int64_t) {
+        const double ex = q.x - x, ey = q.y - y, ez = q.z - z;
+        const double d2 = ex * ex + ey * ey + ez * ez + eps2;
+        if (d2 > eps2) {
+            const double dist = sqrt(d2);
+            const double w = q.w / (dist * d2), w5 = (3.0 * w) / d2;
+            f.xx += (ex * ex) * w5 - w; f.yy += (ey * ey) * w5 - w; f.zz += (ez * ez) * w5 - w;
+            f.xy += (ex * ey) * w5; f.xz += (ex * ez) * w5; f.yz += (ey * ez) * w5;
+            f.terms++;
         }
-        __syncthreads();
-    }
+    });
     if (valid) {
         const int64_t o = pts ? i : (int64_t)cur.id[i];
         if (t6_out) tidal_store(t6_out, o, f);
@@ -4639,7 +4647,7 @@ __global__ __launch_bounds__(kBlock) void k_tracer_tree(const Node *__restrict__
                                                         float eps2f, double eps, unsigned long long *pmax_word,
                                                         const double *__restrict__ quad, double *__restrict__ p,
                                                         double *__restrict__ v, double *__restrict__ a, double dt, double damping) {
-    if (info->error != 0 || info->sticky_error != 0) return;  // the tree did not fit: neither bodies nor tracers advance
+    if (tree_frozen(info)) return;  // the tree did not fit: neither bodies nor tracers advance
     const int64_t rank = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     const bool inside = rank < m;
     double qx = 0.0, qy = 0.0, qz = 0.0, vx = 0.0, vy = 0.0, vz = 0.0;
@@ -4681,7 +4689,7 @@ __global__ __launch_bounds__(kBlock) void k_tracer_direct(Bodies cur, int64_t n,
 __global__ __launch_bounds__(kBlock) void k_tracer_kick_drift(const TreeInfo *info, int64_t m, double *__restrict__ p,
                                                               double *__restrict__ v, const double *__restrict__ a, double dt,
                                                               unsigned long long *pmax) {
-    if (info && (info->error != 0 || info->sticky_error != 0)) return;
+    if (info && tree_frozen(info)) return;
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     const double h = 0.5 * dt;
     bool moved = false;
@@ -5436,6 +5444,14 @@ void dev_free(nbmi_sim *s, T **p) {
     *p = nullptr;
 }
 
+// After a launch whose failure gets a message of its own: 0, or - it failed - NBMI_ERR_HIP with the message `fmt`
+// (printf-style, at most one %s: `who`).
+int launch_failed(const char *fmt, const char *who = "") {
+    if (hipGetLastError() == hipSuccess) return 0;
+    nbmi::set_error(fmt, who);
+    return NBMI_ERR_HIP;
+}
+
 int alloc_bodies(nbmi_sim *s, Bodies *b, int64_t n) {
     if (dev_alloc(s, &b->x, n) || dev_alloc(s, &b->y, n) || dev_alloc(s, &b->z, n) || dev_alloc(s, &b->vx, n) ||
         dev_alloc(s, &b->vy, n) || dev_alloc(s, &b->vz, n) || dev_alloc(s, &b->m, n) || dev_alloc(s, &b->id, n))
@@ -6112,10 +6128,7 @@ int probe_chunks(nbmi_sim *s, const char *who, bool tree, int64_t m, const doubl
             if (int rc = probe_order_chunk(s, f, f.pts, mc, &order)) return rc;
         }
         walk(b, mc, order);
-        if (hipGetLastError() != hipSuccess) {
-            nbmi::set_error("%s: a kernel launch failed", who);
-            return NBMI_ERR_HIP;
-        }
+        if (int rc = launch_failed("%s: a kernel launch failed", who)) return rc;
         if (int rc = copy_out(b, mc)) return rc;
         NBMI_HIP_CHECK(hipStreamSynchronize(st));
     }
@@ -6227,9 +6240,7 @@ template <class Launch>
 int query_enqueue(nbmi_sim *s, const char *what, Launch launch) {
     return query_tree(s, [&]() -> int {
         launch();
-        if (hipGetLastError() == hipSuccess) return 0;
-        nbmi::set_error("%s launch failed", what);
-        return NBMI_ERR_HIP;
+        return launch_failed("%s launch failed", what);
     });
 }
 // The synchronous form of a query: errors of earlier steps first, as a getter reports them, then the query (`enqueue`,
@@ -6850,9 +6861,7 @@ int diag_potential(nbmi_sim *s) {
                 s->nodes, s->diag_pot, s->wtab, s->info, s->posm_s, s->perm, s->curbuf, (float)(s->softening * s->softening), n,
                 s->diag_phi, s->diag_cnt, decltype(q)::value ? s->quad_work : nullptr);
         });
-        if (hipGetLastError() == hipSuccess) return 0;
-        nbmi::set_error("k_potential_tree launch failed");
-        return (int)NBMI_ERR_HIP;
+        return launch_failed("k_potential_tree launch failed");
     });
 }
 
@@ -7157,21 +7166,48 @@ int nbmi_compute_group_colors(nbmi_sim *s, double link, int64_t min_members) {
 }
 
 namespace {
-// Enqueues build, cell counts and the pair search and never waits.  Afterwards q.pairs.out = {distances evaluated, pairs
-// counted through whole cells, below, counts[0 .. nb)}.
-int pairs_enqueue(nbmi_sim *s, int nb, const PairEdges &e2) {
-    const int64_t n = s->n;
+// The scratch of a pair call, with the sums cleared: q.pairs.cnt, the cells' body counts, and q.pairs.out = {distances
+// evaluated, counted through whole cells, below, counts[0 .. nb)}, to which the kernels add.
+int pairs_prepare(nbmi_sim *s) {
     auto &g = s->q.pairs;
     if (query_buffers(s) || query_alloc(g, [&] {
             return dev_alloc(s, &g.cnt, s->node_capacity + 2) || dev_alloc(s, &g.out, kPairMaxBins + 3);
         }))
         return NBMI_ERR_HIP;
+    NBMI_HIP_CHECK(hipMemsetAsync(g.out, 0, (kPairMaxBins + 3) * sizeof(unsigned long long), s->stream));
+    return 0;
+}
+// The caller's side of q.pairs.out: where nbmi_pair_counts and nbmi_pair_counts_at put the sums (any may be null).
+struct PairSums {
+    int nb;
+    int64_t *counts, *below, *evals, *cell_pairs;
+    void set(const unsigned long long *h) const {
+        if (evals) *evals = (int64_t)h[0];
+        if (cell_pairs) *cell_pairs = (int64_t)h[1];
+        if (below) *below = (int64_t)h[2];
+        for (int k = 0; counts && k < nb; k++) counts[k] = (int64_t)h[3 + k];
+    }
+    void zero() const {
+        const unsigned long long h[kPairMaxBins + 3] = {};
+        set(h);
+    }
+    int read(nbmi_sim *s) const {  // waits for the stream
+        unsigned long long h[kPairMaxBins + 3];
+        NBMI_HIP_CHECK(hipMemcpyAsync(h, s->q.pairs.out, (size_t)(nb + 3) * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->stream));
+        NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
+        set(h);
+        return 0;
+    }
+};
+// Enqueues build, cell counts and the pair search and never waits.
+int pairs_enqueue(nbmi_sim *s, int nb, const PairEdges &e2) {
+    const int64_t n = s->n;
+    auto &g = s->q.pairs;
+    if (int rc = pairs_prepare(s)) return rc;
     hipStream_t st = s->stream;
-    NBMI_HIP_CHECK(hipMemsetAsync(g.out, 0, (kPairMaxBins + 3) * sizeof(unsigned long long), st));
     return query_enqueue(s, "k_pair_counts", [&] {
         k_pair_cells<<<nblocks(s->own_node_rows), kBlock, 0, st>>>(s->nodes, s->node_ref, s->info, n, s->own_node_rows, g.cnt);
-        const size_t lds = (size_t)(nb + 1) * (sizeof(double) + kQueryBlock * sizeof(uint32_t));
-        k_pair_counts<<<(int)((n + kQueryBlock - 1) / kQueryBlock), kQueryBlock, lds, st>>>(
+        k_pair_counts<<<(int)((n + kQueryBlock - 1) / kQueryBlock), kQueryBlock, pair_lds_bytes(nb), st>>>(
             s->nodes, s->q.shared.rows, s->node_ref, g.cnt, s->info, s->perm, s->buf[s->curbuf], n, nb, e2,
             s->pair_cells ? 1 : 0, s->q.shared.wleaf, g.out);
     });
@@ -7207,20 +7243,11 @@ int nbmi_pair_counts(nbmi_sim *s, int nb, const double *edges, int64_t *counts, 
     if (int rc = query_refuse(s, "nbmi_pair_counts")) return rc;
     PairEdges e2{};
     if (int rc = pair_edges_check("nbmi_pair_counts", nb, edges, &e2)) return rc;
-    for (int k = 0; counts && k < nb; k++) counts[k] = 0;
-    if (below) *below = 0;
-    if (evals) *evals = 0;
-    if (cell_pairs) *cell_pairs = 0;
+    const PairSums sums{nb, counts, below, evals, cell_pairs};
+    sums.zero();
     if (s->n < 2) return 0;
     if (int rc = query_sync(s, [&] { return pairs_enqueue(s, nb, e2); })) return rc;
-    unsigned long long h[kPairMaxBins + 3];
-    NBMI_HIP_CHECK(hipMemcpyAsync(h, s->q.pairs.out, (size_t)(nb + 3) * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->stream));
-    NBMI_HIP_CHECK(hipStreamSynchronize(s->stream));
-    if (evals) *evals = (int64_t)h[0];
-    if (cell_pairs) *cell_pairs = (int64_t)h[1];
-    if (below) *below = (int64_t)h[2];
-    for (int k = 0; counts && k < nb; k++) counts[k] = (int64_t)h[3 + k];
-    return 0;
+    return sums.read(s);
 }
 
 int nbmi_deposit(nbmi_sim *s, const double *lo, const double *hi, const int32_t *dims, int scheme, int quantities,
@@ -7576,41 +7603,56 @@ int field_alloc(nbmi_sim *s, int64_t need) {
     return 0;
 }
 
-// The chunks of one call of `who` (nbmi_field_at, or nbmi_tidal_at: `tidal`, whose outputs are t6 and terms), enqueued and
-// copied out one after the other; the tree (Barnes-Hut) stands.  pmax: the call's largest |coordinate|.
-int field_chunks(nbmi_sim *s, const char *who, bool tidal, int64_t m, const double *pts, double pmax, double *acc, double *phi,
-                 double *t6, int32_t *terms) {
+// What a point call writes, per point and each only if asked for (not null): nbmi_field_at's acc and phi, or - `tidal` -
+// nbmi_tidal_at's t6; terms for either.
+struct FieldOut {
+    bool tidal;
+    double *acc, *phi, *t6;
+    int32_t *terms;
+    bool any() const { return acc || phi || t6 || terms; }
+    void zero(int64_t m) const {  // no bodies: no field
+        for (int64_t i = 0; i < m; i++) {
+            if (acc) acc[3 * i] = acc[3 * i + 1] = acc[3 * i + 2] = 0.0;
+            if (phi) phi[i] = 0.0;
+            for (int k = 0; t6 && k < 6; k++) t6[6 * i + k] = 0.0;
+            if (terms) terms[i] = 0;
+        }
+    }
+};
+// The chunks of one call of `who`, enqueued and copied out one after the other; the tree (Barnes-Hut) stands.  pmax: the
+// call's largest |coordinate|.
+int field_chunks(nbmi_sim *s, const char *who, int64_t m, const double *pts, double pmax, const FieldOut &o) {
     auto &f = s->field;
     hipStream_t st = s->stream;
     const bool tree = s->method == NBMI_METHOD_BARNES_HUT;
     const double eps2 = s->softening * s->softening;
     auto walk = [&](int64_t, int64_t mc, const uint32_t *order) {
         if (!tree) {
-            if (tidal)
-                k_tidal_direct<<<nblocks(mc), kBlock, 0, st>>>(s->buf[s->curbuf], s->n, s->G, eps2, f.pts, mc, t6 ? f.t6 : nullptr,
-                                                               nullptr, terms ? f.cnt : nullptr);
+            if (o.tidal)
+                k_tidal_direct<<<nblocks(mc), kBlock, 0, st>>>(s->buf[s->curbuf], s->n, s->G, eps2, f.pts, mc, o.t6 ? f.t6 : nullptr,
+                                                               nullptr, o.terms ? f.cnt : nullptr);
             else
-                k_field_direct<<<nblocks(mc), kBlock, 0, st>>>(s->buf[s->curbuf], s->n, s->G, eps2, f.pts, mc, acc ? f.acc : nullptr,
-                                                               phi ? f.phi : nullptr, terms ? f.cnt : nullptr);
+                k_field_direct<<<nblocks(mc), kBlock, 0, st>>>(s->buf[s->curbuf], s->n, s->G, eps2, f.pts, mc, o.acc ? f.acc : nullptr,
+                                                               o.phi ? f.phi : nullptr, o.terms ? f.cnt : nullptr);
         } else {
             with_bool(s->multipole == NBMI_MULTIPOLE_QUADRUPOLE, [&](auto q) {
                 const double *quad = decltype(q)::value ? s->quad_work : nullptr;
-                if (tidal)
+                if (o.tidal)
                     k_tidal_tree<decltype(q)::value><<<nblocks(mc), kBlock, 0, st>>>(
                         s->nodes, s->diag_pot, f.wtab, s->info, f.sx, f.sy, f.sz, order, mc, (float)eps2, s->softening, pmax, quad,
-                        t6 ? f.t6 : nullptr, terms ? f.cnt : nullptr);
+                        o.t6 ? f.t6 : nullptr, o.terms ? f.cnt : nullptr);
                 else
                     k_field_tree<decltype(q)::value><<<nblocks(mc), kBlock, 0, st>>>(
                         s->nodes, s->diag_pot, f.wtab, s->info, f.sx, f.sy, f.sz, order, mc, (float)eps2, s->softening, pmax, quad,
-                        acc ? f.acc : nullptr, phi ? f.phi : nullptr, terms ? f.cnt : nullptr);
+                        o.acc ? f.acc : nullptr, o.phi ? f.phi : nullptr, o.terms ? f.cnt : nullptr);
             });
         }
     };
     auto copy_out = [&](int64_t b, int64_t mc) -> int {
-        if (acc) NBMI_HIP_CHECK(hipMemcpyAsync(acc + 3 * b, f.acc, (size_t)mc * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
-        if (phi) NBMI_HIP_CHECK(hipMemcpyAsync(phi + b, f.phi, (size_t)mc * sizeof(double), hipMemcpyDeviceToHost, st));
-        if (t6) NBMI_HIP_CHECK(hipMemcpyAsync(t6 + 6 * b, f.t6, (size_t)mc * 6 * sizeof(double), hipMemcpyDeviceToHost, st));
-        if (terms) NBMI_HIP_CHECK(hipMemcpyAsync(terms + b, f.cnt, (size_t)mc * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        if (o.acc) NBMI_HIP_CHECK(hipMemcpyAsync(o.acc + 3 * b, f.acc, (size_t)mc * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (o.phi) NBMI_HIP_CHECK(hipMemcpyAsync(o.phi + b, f.phi, (size_t)mc * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (o.t6) NBMI_HIP_CHECK(hipMemcpyAsync(o.t6 + 6 * b, f.t6, (size_t)mc * 6 * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (o.terms) NBMI_HIP_CHECK(hipMemcpyAsync(o.terms + b, f.cnt, (size_t)mc * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         return 0;
     };
     return probe_chunks(s, who, tree, m, pts, walk, copy_out);
@@ -7638,46 +7680,32 @@ int field_points_check(nbmi_sim *s, const char *who, int64_t m, const double *po
     }
     return 0;
 }
+// A point call (`who`) from its checks to its chunks: the points, m == 0, zeros where there are no bodies, nothing asked
+// for, the scratch, then the chunks - Barnes-Hut: on a side tree of the current positions with the float64 rows.
+int field_call(nbmi_sim *s, const char *who, int64_t m, const double *points_xyz, const FieldOut &o) {
+    if (int rc = check_handle(s)) return rc;
+    double pmax = 0.0;
+    if (int rc = field_points_check(s, who, m, points_xyz, &pmax)) return rc;
+    if (m == 0) return 0;
+    if (s->n == 0) {
+        o.zero(m);
+        return 0;
+    }
+    if (!o.any()) return 0;
+    if (int rc = field_alloc(s, m)) return rc;
+    auto &f = s->field;
+    if (o.tidal && !f.t6 && dev_alloc(s, &f.t6, 6 * (size_t)f.rows)) return NBMI_ERR_HIP;  // 48 bytes per scratch row, from the first tidal call on
+    auto chunks = [&] { return field_chunks(s, who, m, points_xyz, pmax, o); };
+    return s->method != NBMI_METHOD_BARNES_HUT ? chunks() : side_tree(s, true, true, false, false, chunks);
+}
 }  // namespace
 
 int nbmi_field_at(nbmi_sim *s, int64_t m, const double *points_xyz, double *acc_xyz, double *phi, int32_t *terms) {
-    if (int rc = check_handle(s)) return rc;
-    double pmax = 0.0;
-    if (int rc = field_points_check(s, "nbmi_field_at", m, points_xyz, &pmax)) return rc;
-    if (m == 0) return 0;
-    const int64_t n = s->n;
-    if (n == 0) {
-        for (int64_t i = 0; i < m; i++) {
-            if (acc_xyz) acc_xyz[3 * i] = acc_xyz[3 * i + 1] = acc_xyz[3 * i + 2] = 0.0;
-            if (phi) phi[i] = 0.0;
-            if (terms) terms[i] = 0;
-        }
-        return 0;
-    }
-    if (!acc_xyz && !phi && !terms) return 0;
-    if (int rc = field_alloc(s, m)) return rc;
-    auto chunks = [&] { return field_chunks(s, "nbmi_field_at", false, m, points_xyz, pmax, acc_xyz, phi, nullptr, terms); };
-    return s->method != NBMI_METHOD_BARNES_HUT ? chunks() : side_tree(s, true, true, false, false, chunks);
+    return field_call(s, "nbmi_field_at", m, points_xyz, FieldOut{false, acc_xyz, phi, nullptr, terms});
 }
 
 int nbmi_tidal_at(nbmi_sim *s, int64_t m, const double *points_xyz, double *tidal6, int32_t *terms) {
-    if (int rc = check_handle(s)) return rc;
-    double pmax = 0.0;
-    if (int rc = field_points_check(s, "nbmi_tidal_at", m, points_xyz, &pmax)) return rc;
-    if (m == 0) return 0;
-    if (s->n == 0) {
-        for (int64_t i = 0; i < m; i++) {
-            for (int k = 0; tidal6 && k < 6; k++) tidal6[6 * i + k] = 0.0;
-            if (terms) terms[i] = 0;
-        }
-        return 0;
-    }
-    if (!tidal6 && !terms) return 0;
-    if (int rc = field_alloc(s, m)) return rc;
-    auto &f = s->field;
-    if (!f.t6 && dev_alloc(s, &f.t6, 6 * (size_t)f.rows)) return NBMI_ERR_HIP;  // 48 bytes per scratch row, from the first call on
-    auto chunks = [&] { return field_chunks(s, "nbmi_tidal_at", true, m, points_xyz, pmax, nullptr, nullptr, tidal6, terms); };
-    return s->method != NBMI_METHOD_BARNES_HUT ? chunks() : side_tree(s, true, true, false, false, chunks);
+    return field_call(s, "nbmi_tidal_at", m, points_xyz, FieldOut{true, nullptr, nullptr, tidal6, terms});
 }
 
 // The bodies per distance bin about m points (section 4.28): nbmi_pair_counts' tree, rows and cell counts, and on them
@@ -7690,10 +7718,8 @@ int nbmi_pair_counts_at(nbmi_sim *s, int64_t m, const double *points_xyz, int nb
     if (int rc = field_points_check(s, who, m, points_xyz, nullptr)) return rc;
     PairEdges e2{};
     if (int rc = pair_edges_check(who, nb, edges, &e2)) return rc;
-    for (int k = 0; counts && k < nb; k++) counts[k] = 0;
-    if (below) *below = 0;
-    if (evals) *evals = 0;
-    if (cell_pairs) *cell_pairs = 0;
+    const PairSums sums{nb, counts, below, evals, cell_pairs};
+    sums.zero();
     if (m == 0) return 0;
     const int64_t n = s->n;
     const int64_t cols = nb + 1;
@@ -7710,26 +7736,18 @@ int nbmi_pair_counts_at(nbmi_sim *s, int64_t m, const double *points_xyz, int nb
         if (dev_alloc(s, &f.pp, (size_t)(f.rows * cols))) return NBMI_ERR_HIP;
         f.pp_words = f.rows * cols;
     }
-    if (query_buffers(s) || query_alloc(g, [&] {
-            return dev_alloc(s, &g.cnt, s->node_capacity + 2) || dev_alloc(s, &g.out, kPairMaxBins + 3);
-        }))
-        return NBMI_ERR_HIP;
     hipStream_t st = s->stream;
     NBMI_HIP_CHECK(hipStreamSynchronize(st));
     if (int rc = check_device_error(s)) return rc;  // of earlier steps, as a getter reports them
-    NBMI_HIP_CHECK(hipMemsetAsync(g.out, 0, (kPairMaxBins + 3) * sizeof(unsigned long long), st));
-    const size_t lds = (size_t)cols * (sizeof(double) + kQueryBlock * sizeof(uint32_t));
+    if (int rc = pairs_prepare(s)) return rc;
     const int rc = query_tree(s, [&]() -> int {
         k_pair_cells<<<nblocks(s->own_node_rows), kBlock, 0, st>>>(s->nodes, s->node_ref, s->info, n, s->own_node_rows, g.cnt);
-        if (hipGetLastError() != hipSuccess) {
-            nbmi::set_error("%s: a kernel launch failed", who);
-            return NBMI_ERR_HIP;
-        }
+        if (int r = launch_failed("%s: a kernel launch failed", who)) return r;
         if (int r = check_device_error(s)) return r;  // the build's own capacity error, before anything walks
         return probe_chunks(
             s, who, true, m, points_xyz,
             [&](int64_t, int64_t mc, const uint32_t *order) {
-                k_pair_counts_at<<<(int)((mc + kQueryBlock - 1) / kQueryBlock), kQueryBlock, lds, st>>>(
+                k_pair_counts_at<<<(int)((mc + kQueryBlock - 1) / kQueryBlock), kQueryBlock, pair_lds_bytes(nb), st>>>(
                     s->nodes, s->q.shared.rows, s->node_ref, g.cnt, s->info, f.sx, f.sy, f.sz, order, mc, nb, e2,
                     s->pair_cells ? 1 : 0, per_point ? f.pp : nullptr, g.out);
             },
@@ -7740,15 +7758,7 @@ int nbmi_pair_counts_at(nbmi_sim *s, int64_t m, const double *points_xyz, int nb
                 return 0;
             });
     });
-    if (rc) return rc;
-    unsigned long long h[kPairMaxBins + 3];
-    NBMI_HIP_CHECK(hipMemcpyAsync(h, g.out, (size_t)(nb + 3) * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    NBMI_HIP_CHECK(hipStreamSynchronize(st));
-    if (evals) *evals = (int64_t)h[0];
-    if (cell_pairs) *cell_pairs = (int64_t)h[1];
-    if (below) *below = (int64_t)h[2];
-    for (int k = 0; counts && k < nb; k++) counts[k] = (int64_t)h[3 + k];
-    return 0;
+    return rc ? rc : sums.read(s);
 }
 
 // The tidal tensor at every body's own position: nbmi_get_potentials_f64's build and lane setup, the rows written in the
@@ -7764,10 +7774,7 @@ int nbmi_get_tidal_f64(nbmi_sim *s, double *tidal6, double *norm) {
     if (s->method != NBMI_METHOD_BARNES_HUT) {
         k_tidal_direct<<<nblocks(n), kBlock, 0, st>>>(s->buf[s->curbuf], n, s->G, eps2, nullptr, n, tidal6 ? d_t6 : nullptr,
                                                        norm ? d_norm : nullptr, nullptr);
-        if (hipGetLastError() != hipSuccess) {
-            nbmi::set_error("nbmi_get_tidal_f64: a kernel launch failed");
-            return NBMI_ERR_HIP;
-        }
+        if (int rc = launch_failed("nbmi_get_tidal_f64: a kernel launch failed")) return rc;
     } else {
         const int rc = side_tree(s, true, false, true, false, [&] {
             with_bool(s->multipole == NBMI_MULTIPOLE_QUADRUPOLE, [&](auto q) {
@@ -7775,9 +7782,7 @@ int nbmi_get_tidal_f64(nbmi_sim *s, double *tidal6, double *norm) {
                     s->nodes, s->diag_pot, s->wtab, s->info, s->posm_s, s->perm, s->curbuf, (float)eps2, n, s->buf[s->curbuf].id,
                     tidal6 ? d_t6 : nullptr, norm ? d_norm : nullptr, decltype(q)::value ? s->quad_work : nullptr);
             });
-            if (hipGetLastError() == hipSuccess) return 0;
-            nbmi::set_error("nbmi_get_tidal_f64: a kernel launch failed");
-            return (int)NBMI_ERR_HIP;
+            return launch_failed("nbmi_get_tidal_f64: a kernel launch failed");
         });
         if (rc) return rc;
     }

@@ -1,5 +1,6 @@
-"""Writes tests/golden/probe_bits.json: what the float64 probe family computes - potentials, nbmi_field_at, tracers - at
-ONE commit, as SHA-256 hashes of the float64 arrays and the int32 term counts as they are.
+"""Writes tests/golden/probe_bits.json: what the float64 probe family computes - potentials, nbmi_field_at, the tidal
+tensor at points and bodies, tracers, on a tree and by the direct sums - at ONE commit, as SHA-256 hashes of the float64
+arrays and the int32 term counts as they are.
 
     python scripts/gen_probe_bits_golden.py --commit <full id of the commit the library was built from>
 

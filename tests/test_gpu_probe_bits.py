@@ -1,8 +1,9 @@
-"""The float64 probe family - potentials, nbmi_field_at, tracers - gives the bits recorded in
-tests/golden/probe_bits.json.
+"""The float64 probe family - potentials, nbmi_field_at, nbmi_tidal_at, nbmi_get_tidal_f64, tracers, on a tree and by
+the direct sums - gives the bits recorded in tests/golden/probe_bits.json.
 
-The three share one walk (field_walk), one probe scratch and one side-tree helper (DESIGN.md sections 4.9, 4.18, 4.19),
-so a test that compares the field with the potential compares a function with itself.  The fixture pins the family to
+The tree calls share one walk (field_walk), one probe scratch and one side-tree helper, the direct
+calls one tile loop (DESIGN.md sections 4.9, 4.18, 4.19, 4.27), so a test that compares the field with the potential, or
+tidal() with tidal_at(), compares a function with itself.  The fixture pins the family to
 the commit named in the file instead: for every case below a SHA-256 over the bytes of each float64 array and the int32
 term counts as they are.  It was written by scripts/gen_probe_bits_golden.py with the library built at that commit; a
 differing value is a defect of the library under test, never a reason to write the fixture again.  A lane's result
@@ -37,7 +38,12 @@ def _cases():
             for curve, env in (("hilbert", {}), ("morton", MORTON)):
                 for tag, eps in (("eps", EPS), ("eps0", 0.0)):
                     c[f"field_{dist}_{mp}_{curve}_{tag}"] = dict(kind="field", dist=dist, multipole=mp, env=env, eps=eps)
+                    c[f"tidal_{dist}_{mp}_{curve}_{tag}"] = dict(kind="tidal", dist=dist, multipole=mp, env=env, eps=eps)
     c["field_unsorted"] = dict(kind="field", dist="galaxy", multipole="monopole", env=UNSORTED, eps=EPS)
+    c["tidal_unsorted"] = dict(kind="tidal", dist="galaxy", multipole="monopole", env=UNSORTED, eps=EPS)
+    for dist in DISTS:  # the direct sums: the potential's tile loop, the probes' and the tidal tensor's
+        for tag, eps in (("eps", EPS), ("eps0", 0.0)):
+            c[f"direct_{dist}_{tag}"] = dict(kind="direct", dist=dist, multipole="monopole", env={}, eps=eps, direct=True)
     for mp in ("monopole", "quadrupole"):
         for integ in ("kick_drift", "leapfrog"):
             for m in TRACER_M:
@@ -58,7 +64,8 @@ def _cases():
 
 CASES = _cases()
 # the order of the walk decides speed, never a bit
-SORT_TWINS = {"field_unsorted": "field_galaxy_monopole_hilbert_eps", "tracers_unsorted": "tracers_monopole_kick_drift_1000"}
+SORT_TWINS = {"field_unsorted": "field_galaxy_monopole_hilbert_eps", "tidal_unsorted": "tidal_galaxy_monopole_hilbert_eps",
+              "tracers_unsorted": "tracers_monopole_kick_drift_1000"}
 
 
 def make_input(dist):
@@ -102,12 +109,19 @@ def run_case(case, inputs):
     sim = None
     try:
         if case.get("direct"):
-            sim = HIPDirectSimulation(pos, vel, mass, G, case["eps"], 1.0, integrator=case["integrator"])
+            sim = HIPDirectSimulation(pos, vel, mass, G, case["eps"], 1.0, integrator=case.get("integrator", "kick_drift"))
         else:
             sim = HIPBarnesHutSimulation(pos, vel, mass, G, case["eps"], 1.0, THETA, multipole=case["multipole"],
                                          integrator=case.get("integrator", "kick_drift"))
         out = {}
-        if case["kind"] == "field":
+        if case["kind"] in ("tidal", "direct"):
+            t6, norm = sim.tidal(norm=True)
+            out["t6_bodies"], out["norm_bodies"] = _sha(t6), _sha(norm)
+            for m in FIELD_M:
+                t6, terms = sim.tidal_at(pts[:m], terms=True)
+                assert terms.dtype == np.int32
+                out[f"tidal_m{m}"] = {"t6": _sha(t6), "terms": [int(t) for t in terms]}
+        if case["kind"] in ("field", "direct"):
             out["phi_bodies"] = _sha(sim.potentials())
             d = sim.diagnostics()
             out["terms_bodies"] = d.terms
@@ -116,7 +130,7 @@ def run_case(case, inputs):
                 acc, phi, terms = sim.field_at(pts[:m], terms=True)
                 assert terms.dtype == np.int32
                 out[f"m{m}"] = {"acc": _sha(acc), "phi": _sha(phi), "terms": [int(t) for t in terms]}
-        else:
+        if case["kind"] == "tracers":
             m = case["m"]
             sim.set_tracers(pts[:m], tv[:m])
             for _ in range(STEPS):
@@ -155,9 +169,14 @@ def test_fixture_covers_every_case(recorded):
         assert recorded["cases"][name] == recorded["cases"][twin], (name, twin)
     for name, case in CASES.items():
         got = recorded["cases"][name]
-        if case["kind"] == "field":
+        if case["kind"] in ("field", "direct"):
             assert all(len(got[f"m{m}"]["terms"]) == m and min(got[f"m{m}"]["terms"]) > 0 for m in FIELD_M), name
-        else:
+        if case["kind"] == "tidal":  # the tensor's walk accepts what the field's accepts
+            field = recorded["cases"]["field" + name[len("tidal"):]]
+            assert all(got[f"tidal_m{m}"]["terms"] == field[f"m{m}"]["terms"] for m in FIELD_M), name
+        if case["kind"] == "direct":
+            assert all(got[f"tidal_m{m}"]["terms"] == got[f"m{m}"]["terms"] for m in FIELD_M), name
+        if case["kind"] == "tracers":
             assert got["moved"] == case["m"], name  # every tracer was carried
 
 
