@@ -33,6 +33,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <chrono>
 #include <type_traits>
 #include <utility>
 #include <vector>
@@ -4404,6 +4405,273 @@ __global__ __launch_bounds__(kQueryBlock) void k_pair_counts_at(const Node *__re
 }
 
 // ---------------------------------------------------------------------------------------
+// K29: the exact Euclidean minimum spanning tree (nbmi_mst; include/nbmi.h).  Boruvka rounds on
+// top of the shared query part: per round every body finds its least foreign pair under the key (d2, min id, max id) -
+// the search, k_mst_search - every component the least of its bodies' pairs (two passes of 64-bit atomic minima), and
+// the winning pairs are appended to the edge list and united (unionfind.h).  Components live in key-rank space: comp[r]
+// is the root rank of r's set, flattened behind every round.  Everything one kernel reads of what other waves write -
+// comp, the cells' tags, the components' minima - was written before a kernel boundary; the only words touched across
+// waves INSIDE a kernel are the atomic minima (nobody reads them there) and parent[] in k_mst_emit, through fof_unite's
+// relaxed agent-scope atomics as unionfind.h (d) requires.  So no wave sees another's progress and evals is a function of
+// the state.
+// ---------------------------------------------------------------------------------------
+constexpr unsigned long long kMstNone = 0x7fffffffffffffffull;  // above the bits of every finite d2 >= 0 and every packed pair
+// the unordered pair of caller indices a, b as one word that orders as (min, max)
+__device__ __forceinline__ unsigned long long mst_pack(uint32_t a, uint32_t b) {
+    return a < b ? ((unsigned long long)a << 32) | b : ((unsigned long long)b << 32) | a;
+}
+// dst[c] = min(dst[c], v) for the lanes with `on`.  Key-adjacent bodies mostly share their component: the lanes that share
+// the first such lane's go in as one atomic, the others on their own (fof_flatten's pattern, one round of it).
+__device__ __forceinline__ void mst_wave_min(unsigned long long *dst, int c, unsigned long long v, bool on) {
+    const unsigned long long todo = __builtin_amdgcn_ballot_w64(on);
+    if (todo == 0ull) return;
+    const int lane = threadIdx.x & 63;
+    const int leader = __builtin_amdgcn_readfirstlane(__ffsll((long long)todo) - 1);
+    const int c0 = __builtin_amdgcn_readlane(c, leader);
+    const bool with = on && c == c0;
+    long long least = with ? (long long)v : (long long)kMstNone;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const long long other = __shfl_xor(least, o);
+        least = other < least ? other : least;
+    }
+    if (lane == leader) (void)__hip_atomic_fetch_min(dst + c0, (unsigned long long)least, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (on && !with) (void)__hip_atomic_fetch_min(dst + c, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// every rank a component of its own; rid[r] = the caller index of rank r
+__global__ __launch_bounds__(kBlock) void k_mst_init(const TreeInfo *__restrict__ info, int64_t n, const uint32_t *__restrict__ perm,
+                                                     const int32_t *__restrict__ id, int32_t *__restrict__ parent,
+                                                     int32_t *__restrict__ comp, int32_t *__restrict__ rid,
+                                                     double *__restrict__ bd2, int32_t *__restrict__ bpart,
+                                                     unsigned long long *__restrict__ cmin, unsigned long long *__restrict__ cpair) {
+    if (tree_frozen(info)) return;
+    const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (r >= n) return;
+    parent[r] = (int32_t)r;
+    comp[r] = (int32_t)r;
+    rid[r] = id[perm[r]];
+    bd2[r] = INFINITY;
+    bpart[r] = -1;
+    cmin[r] = kMstNone;
+    cpair[r] = kMstNone;
+}
+// diff[r] = rank r + 1 exists and lies in another component; its exclusive scan S tells every run of ranks whether it is
+// uniform: [a, a + c) holds one component iff S[a + c - 1] == S[a]
+__global__ __launch_bounds__(kBlock) void k_mst_diff(const TreeInfo *__restrict__ info, int64_t n, const int32_t *__restrict__ comp,
+                                                     int32_t *__restrict__ diff) {
+    if (tree_frozen(info)) return;
+    const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (r >= n) return;
+    diff[r] = r + 1 < n && comp[r] != comp[r + 1] ? 1 : 0;
+}
+// ctag[idx] = the component of node idx if all the bodies below it (k_pair_cells' cnt) share one, else -1; a leaf's tag is
+// its body's component.  All nodes at once: no pass per level.
+__global__ __launch_bounds__(kBlock) void k_mst_tags(const int32_t *__restrict__ node_ref, const int32_t *__restrict__ cnt,
+                                                     const TreeInfo *__restrict__ info, int64_t n, int64_t capacity,
+                                                     const int32_t *__restrict__ comp, const int32_t *__restrict__ dscan,
+                                                     int32_t *__restrict__ ctag) {
+    if (tree_frozen(info)) return;
+    const int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (idx >= info->num_nodes || idx >= capacity) return;
+    const int64_t a = node_ref[idx], c = cnt[idx];
+    const bool ok = a >= 0 && c >= 1 && a + c <= n;
+    ctag[idx] = ok && dscan[a + c - 1] == dscan[a] ? comp[a] : -1;
+}
+// The search: one wave per 64 key-adjacent bodies, one body per lane, k_knn's shape.  A lane keeps its least foreign pair
+// (best, bpack, bp = the partner's rank) under the full key and `bound`, an upper bound on the d2 of that pair.
+//   seed   the wave's own bodies and the 64 ranks on either side, by readlane (knn_seed's pattern), foreign ones only
+//   walk   from the root.  A cell is closed for a lane if it is uniform in the lane's own component (nothing foreign in
+//          it) or if query_lower EXCEEDS bound - strictly, so a pair that ties the best in d2 is always reached and then
+//          decided by the indices.  A cell that stays open is not uniform in the lane's component, so it holds a foreign
+//          body, and query_upper of it bounds the least foreign d2 from above before any leaf is seen: bound may drop to
+//          it.  That only ever lowers a true upper bound, so the strict pruning stays exact.  A leaf of the own component
+//          is skipped, every other compared under the full key.
+//   carry  (kCarry: every round but the first) components only grow, so a body's least foreign pair of the last round is
+//          still its least if that partner is still foreign: such a lane does not search again, and a wave without a lane
+//          left to search goes straight to the minimum.  The lanes that do search first take a bound from their own
+//          ancestors (below).
+// Then the component minimum's first pass: the bits of best d2 (a finite double >= 0 orders as its bits, as k_mr_keys
+// relies on) into cmin[component].
+template <bool kCarry>
+__global__ __launch_bounds__(kQueryBlock) void k_mst_search(const Node *__restrict__ nodes, const double4 *__restrict__ rows,
+                                                            const int32_t *__restrict__ node_ref, const TreeInfo *__restrict__ info,
+                                                            const uint32_t *__restrict__ perm, Bodies cur, int64_t n,
+                                                            const int32_t *__restrict__ comp, const int32_t *__restrict__ rid,
+                                                            const int32_t *__restrict__ ctag, const int32_t *__restrict__ cnt,
+                                                            double *__restrict__ bd2, int32_t *__restrict__ bpart,
+                                                            unsigned long long *cmin,
+                                                            unsigned long long *__restrict__ evals_out) {
+    QueryCtx C = query_prologue(info, cur, perm, n);
+    if (C.frozen) return;
+    const int64_t w0 = C.w0;
+    const bool has = C.valid;
+    const int mine = has ? comp[C.rank] : -1;
+    const uint32_t myid = has ? (uint32_t)rid[C.rank] : 0u;
+    double best = INFINITY;
+    unsigned long long bpack = kMstNone;
+    int bp = -1;
+    bool search = has;
+    if (kCarry && has) {
+        const int last = bpart[C.rank];
+        if (last >= 0 && comp[last] != mine) {
+            search = false;
+            bp = last;
+            best = bd2[C.rank];
+        }
+    }
+    long long evals = 0;
+    if (__builtin_amdgcn_ballot_w64(search) != 0ull) {
+        C.valid = search;  // the lanes that carry their pair over sit the search out
+        double bound = INFINITY;
+        auto consider = [&](double d2, uint32_t oid, int64_t r) {
+            const unsigned long long pack = mst_pack(myid, oid);
+            if (d2 < best || (d2 == best && pack < bpack)) {
+                best = d2;
+                bpack = pack;
+                bp = (int)r;
+                bound = d2 < bound ? d2 : bound;
+            }
+        };
+        const QueryGroup grp[3] = {C.own, query_group(cur, perm, w0 - 64, n), query_group(cur, perm, w0 + 64, n)};
+        const int64_t ex_lo = w0 - 64 > 0 ? w0 - 64 : 0, ex_hi = w0 + 128 < n ? w0 + 128 : n;
+#pragma unroll
+        for (int g = 0; g < 3; g++) {
+            const int64_t gr = grp[g].base + C.lane;
+            const bool in = gr >= 0 && gr < n;
+            const int gc = in ? comp[gr] : -1, gi = in ? rid[gr] : 0;
+            for (int i = 0; i < 64; i++) {
+                const int64_t r = grp[g].base + i;
+                if (r < 0 || r >= n) continue;
+                const double d2 = query_d2(query_bcast(grp[g].x, i), query_bcast(grp[g].y, i), query_bcast(grp[g].z, i), C.qx, C.qy, C.qz);
+                const int oc = __builtin_amdgcn_readlane(gc, i), oi = __builtin_amdgcn_readlane(gi, i);
+                if (search && oc != mine) {
+                    evals++;
+                    consider(d2, (uint32_t)oi, r);
+                }
+            }
+        }
+        if (kCarry) {
+            // Behind the first round the seeds are mostly of the lane's own component and leave no bound, and the walk
+            // below meets the cells in key order, not nearest first.  So first down the lane's own ancestors only - the
+            // cells whose ranks hold the lane's - as far as they are not uniform: the smallest of them that holds a
+            // foreign body bounds the lane's pair by query_upper.  No leaf is looked at (all ranks excluded).
+            query_walk_cells(
+                nodes, rows, node_ref, 0u, C, (int64_t)0, n, evals,
+                [&](unsigned idx, const double4 &row, unsigned) {
+                    const int64_t a = node_ref[idx];
+                    if (C.rank < a || C.rank >= a + cnt[idx] || ctag[idx] == mine) return false;
+                    const double up = query_upper(row, C.qx, C.qy, C.qz);
+                    bound = up < bound ? up : bound;
+                    return true;
+                },
+                [&](double, const double4 &, int64_t) {});
+        }
+        query_walk_cells(
+            nodes, rows, node_ref, 0u, C, ex_lo, ex_hi, evals,
+            [&](unsigned idx, const double4 &row, unsigned) {
+                if (ctag[idx] == mine) return false;
+                if (query_lower(row, C.qx, C.qy, C.qz) > bound) return false;
+                const double up = query_upper(row, C.qx, C.qy, C.qz);
+                bound = up < bound ? up : bound;
+                return true;
+            },
+            [&](double d2, const double4 &, int64_t r) {
+                if (comp[r] != mine) consider(d2, (uint32_t)rid[r], r);
+            });
+        if (search) {
+            bd2[C.rank] = best;
+            bpart[C.rank] = bp;
+        }
+    }
+    mst_wave_min(cmin, mine, (unsigned long long)__double_as_longlong(best), has && bp >= 0);
+    if (evals_out) nbmi::wave_add(evals_out, evals, threadIdx.x);
+}
+// The component minimum's second pass, behind the kernel boundary that made cmin final: among the bodies that hold their
+// component's least d2, the least packed pair into cpair[component].
+__global__ __launch_bounds__(kBlock) void k_mst_pick(const TreeInfo *__restrict__ info, int64_t n, const int32_t *__restrict__ comp,
+                                                     const int32_t *__restrict__ rid, const double *__restrict__ bd2,
+                                                     const int32_t *__restrict__ bpart, const unsigned long long *__restrict__ cmin,
+                                                     unsigned long long *cpair) {
+    if (tree_frozen(info)) return;
+    const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    int c = -1;
+    unsigned long long pack = kMstNone;
+    bool on = false;
+    if (r < n) {
+        c = comp[r];
+        const int bp = bpart[r];
+        if (bp >= 0 && (unsigned long long)__double_as_longlong(bd2[r]) == cmin[c]) {
+            on = true;
+            pack = mst_pack((uint32_t)rid[r], (uint32_t)rid[bp]);
+        }
+    }
+    mst_wave_min(cpair, c, pack, on);
+}
+// Emit and unite, behind the boundary that made cpair final.  A component's winning pair {i, j} has exactly one body in
+// the component - the other is foreign - so exactly one lane of the grid holds (cmin, cpair) of its component: that
+// lane, not the root's, appends the edge and unites the two sets.  Two components that chose each other chose the same
+// pair (the order is total and both minimise over a set that holds it), and then both winning lanes are the two ends of
+// that pair: only the end with the smaller caller index appends it.  A pair that is the minimum of one component only is
+// appended by that component's lane; so every chosen pair is appended once, none twice.  The slot comes from an integer
+// counter; the order of the list is settled by the sort behind the rounds.  parent[] is touched through fof_unite alone.
+__global__ __launch_bounds__(kBlock) void k_mst_emit(const TreeInfo *__restrict__ info, int64_t n, const int32_t *__restrict__ comp,
+                                                     const int32_t *__restrict__ rid, const double *__restrict__ bd2,
+                                                     const int32_t *__restrict__ bpart, const unsigned long long *__restrict__ cmin,
+                                                     const unsigned long long *__restrict__ cpair, int32_t *parent,
+                                                     unsigned long long *__restrict__ e_pack, unsigned long long *__restrict__ e_d2,
+                                                     unsigned long long *count) {
+    if (tree_frozen(info)) return;
+    const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (r >= n) return;
+    const int bp = bpart[r];
+    if (bp < 0) return;
+    const int c = comp[r];
+    const unsigned long long bits = (unsigned long long)__double_as_longlong(bd2[r]);
+    if (bits != cmin[c]) return;
+    const unsigned long long pack = mst_pack((uint32_t)rid[r], (uint32_t)rid[bp]);
+    if (pack != cpair[c]) return;
+    const int c2 = comp[bp];
+    const bool mutual = cmin[c2] == bits && cpair[c2] == pack;
+    if (!mutual || rid[r] < rid[bp]) {
+        const unsigned long long slot = atomicAdd(count, 1ull);
+        if (slot < (unsigned long long)(n - 1)) {  // (a tree has no more edges: nothing is ever written behind the list)
+            e_pack[slot] = pack;
+            e_d2[slot] = bits;
+        }
+    }
+    (void)fof_unite(parent, (int)r, bp);
+}
+// Behind the boundary parent[] is final and read plainly: the next round's components, and its minima cleared.
+__global__ __launch_bounds__(kBlock) void k_mst_flatten(const TreeInfo *__restrict__ info, int64_t n,
+                                                        const int32_t *__restrict__ parent, int32_t *__restrict__ comp,
+                                                        unsigned long long *__restrict__ cmin, unsigned long long *__restrict__ cpair) {
+    if (tree_frozen(info)) return;
+    const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (r >= n) return;
+    int f = (int)r;
+    for (int p = parent[f]; p != f; p = parent[f]) f = p;
+    comp[r] = f;
+    cmin[r] = kMstNone;
+    cpair[r] = kMstNone;
+}
+// the final order's helpers: 0 .. m - 1;  key[k] = d2 of the edge at `order[k]`;  the sorted list in the caller's arrays
+__global__ __launch_bounds__(kBlock) void k_mst_gather(int64_t m, const uint32_t *__restrict__ order,
+                                                       const unsigned long long *__restrict__ e_d2, uint64_t *__restrict__ key) {
+    const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (k < m) key[k] = e_d2[order[k]];
+}
+__global__ __launch_bounds__(kBlock) void k_mst_out(int64_t m, const uint32_t *__restrict__ order, const uint64_t *__restrict__ key,
+                                                    const unsigned long long *__restrict__ e_pack, int32_t *__restrict__ edge_i,
+                                                    int32_t *__restrict__ edge_j, double *__restrict__ edge_d2) {
+    const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (k >= m) return;
+    const unsigned long long pack = e_pack[order[k]];
+    edge_i[k] = (int32_t)(pack >> 32);
+    edge_j[k] = (int32_t)(pack & 0xffffffffull);
+    edge_d2[k] = __longlong_as_double((long long)key[k]);
+}
+
+// ---------------------------------------------------------------------------------------
 // K19: the field at arbitrary points (nbmi_field_at; include/nbmi.h).
 // The probe walk of K14 (field_walk) with a probe in the lane instead of a body, the acceleration summed as well.  Which
 // probes share a wave - the sort below, the chunks of the call, the other points - decides the speed of a call and never
@@ -5342,6 +5610,26 @@ struct nbmi_sim {
             int32_t *cnt = nullptr;
             unsigned long long *out = nullptr;  // [0] distances evaluated, [1] pairs counted through whole cells, [2 + c] counter c
         } pairs;
+        // nbmi_mst (section 4.29): 64 bytes per body - caller index, last partner and its d2, the components' two minima
+        // (after the rounds: the sort's two key arrays), the scan's input and output, the edge list, the sort's two index
+        // arrays - 4 bytes per node row (the cells' tags), 4 bytes per 2 048 bodies of scan tiles, the sort's temp buffer
+        // and two counters.  It also uses fof's parent / root and pairs' cnt.
+        struct {
+            bool ready = false;
+            int32_t *rid = nullptr, *bpart = nullptr, *diff = nullptr, *dscan = nullptr, *tiles = nullptr, *ctag = nullptr;
+            double *bd2 = nullptr;
+            unsigned long long *cmin = nullptr, *cpair = nullptr, *e_pack = nullptr, *e_d2 = nullptr;
+            uint32_t *va = nullptr, *vb = nullptr;
+            char *sort_tmp = nullptr;
+            size_t sort_bytes = 0;
+            unsigned long long *counters = nullptr;  // [0] distances evaluated, [1] edges appended
+            // of the last call, per round (nbmi_mst_rounds; host side): distances evaluated, edges appended, host wall ms
+            struct Round {
+                int64_t evals, edges;
+                double ms;
+            };
+            std::vector<Round> rounds;
+        } mst;
     } q;
     bool pair_cells = true;  // cells inside one bin are counted whole (NBMI_PAIRS_CELLS=0: never; measurement)
     // Scratch of nbmi_deposit (section 4.20): `words` 64-bit sums (planes x cells of the largest call so far, regrown by
@@ -7009,17 +7297,22 @@ int fof_check(nbmi_sim *s, double link, int64_t min_members, int64_t capacity, c
     }
     return 0;
 }
+// the union-find's arrays by key rank (nbmi_mst borrows parent and root)
+int fof_buffers(nbmi_sim *s) {
+    const int64_t n = s->n;
+    auto &g = s->q.fof;
+    return query_alloc(g, [&] {
+        return dev_alloc(s, &g.parent, n) || dev_alloc(s, &g.root, n) || dev_alloc(s, &g.minid, n) || dev_alloc(s, &g.cnt, n) ||
+               dev_alloc(s, &g.counters, 2);
+    });
+}
 // Enqueues build, pair search and flattening and never waits.  Afterwards, by key rank: q.fof.root, minid[root] (the
 // label), cnt[root]; counters = {distances evaluated (if `count`), roots}; `labels` (device, may be null) in the caller's
 // order.
 int fof_enqueue(nbmi_sim *s, double b2, bool count, int32_t *labels) {
     const int64_t n = s->n;
     auto &g = s->q.fof;
-    if (query_buffers(s) || query_alloc(g, [&] {
-            return dev_alloc(s, &g.parent, n) || dev_alloc(s, &g.root, n) || dev_alloc(s, &g.minid, n) ||
-                   dev_alloc(s, &g.cnt, n) || dev_alloc(s, &g.counters, 2);
-        }))
-        return NBMI_ERR_HIP;
+    if (query_buffers(s) || fof_buffers(s)) return NBMI_ERR_HIP;
     hipStream_t st = s->stream;
     NBMI_HIP_CHECK(hipMemsetAsync(g.counters, 0, 2 * sizeof(unsigned long long), st));
     return query_enqueue(s, "k_fof_link", [&] {
@@ -7248,6 +7541,135 @@ int nbmi_pair_counts(nbmi_sim *s, int nb, const double *edges, int64_t *counts, 
     if (s->n < 2) return 0;
     if (int rc = query_sync(s, [&] { return pairs_enqueue(s, nb, e2); })) return rc;
     return sums.read(s);
+}
+
+namespace {
+int mst_buffers(nbmi_sim *s) {
+    auto &g = s->q.mst;
+    const int64_t n = s->n;
+    return query_alloc(g, [&]() -> int {
+        g.sort_bytes = nbmi::radix_temp_bytes_u64((size_t)n, 64);
+        if (dev_alloc(s, &g.rid, n) || dev_alloc(s, &g.bpart, n) || dev_alloc(s, &g.diff, n) || dev_alloc(s, &g.dscan, n + 1) ||
+            dev_alloc(s, &g.tiles, (n + 1 + kScanTile - 1) / kScanTile + 1) || dev_alloc(s, &g.ctag, s->node_capacity + 2) ||
+            dev_alloc(s, &g.bd2, n) || dev_alloc(s, &g.cmin, n) || dev_alloc(s, &g.cpair, n) || dev_alloc(s, &g.e_pack, n) ||
+            dev_alloc(s, &g.e_d2, n) || dev_alloc(s, &g.va, n) || dev_alloc(s, &g.vb, n) ||
+            dev_alloc(s, &g.sort_tmp, g.sort_bytes + 256) || dev_alloc(s, &g.counters, 2))
+            return NBMI_ERR_HIP;
+        NBMI_HIP_CHECK(nbmi::radix_init_temp(g.sort_tmp, s->stream));
+        return 0;
+    });
+}
+}  // namespace
+
+int nbmi_mst(nbmi_sim *s, int32_t *edge_i, int32_t *edge_j, double *edge_d2, int64_t *rounds, int64_t *evals) {
+    static const char *const who = "nbmi_mst";
+    if (int rc = check_handle(s)) return rc;
+    if (int rc = query_refuse(s, who)) return rc;
+    if (rounds) *rounds = 0;
+    if (evals) *evals = 0;
+    const int64_t n = s->n;
+    if (n < 2) return 0;
+    hipStream_t st = s->stream;
+    NBMI_HIP_CHECK(hipStreamSynchronize(st));
+    if (int rc = check_device_error(s)) return rc;  // of earlier steps, as a getter reports them
+    if (query_buffers(s) || fof_buffers(s)) return NBMI_ERR_HIP;
+    if (int rc = pairs_prepare(s)) return rc;
+    if (int rc = mst_buffers(s)) return rc;
+    auto &g = s->q.mst;
+    int32_t *parent = s->q.fof.parent, *comp = s->q.fof.root;
+    const int64_t m = n - 1;  // the edges of the tree
+    int max_rounds = 0;       // ceil(log2 n): every round at least halves the number of components
+    while (((int64_t)1 << max_rounds) < n) max_rounds++;
+    int64_t done = 0;
+    unsigned long long c[2] = {0, 0};
+    unsigned sort_err = 0u;
+    // the staging holds 7 N doubles: the edges' two index arrays, then their d2
+    int32_t *o_i = (int32_t *)s->stage, *o_j = o_i + n;
+    double *o_d2 = (double *)s->stage + n;
+    TimedSpans timed{s};
+    g.rounds.clear();
+    NBMI_HIP_CHECK(hipMemsetAsync(g.counters, 0, 2 * sizeof(unsigned long long), st));
+    NBMI_HIP_CHECK(timed.begin());
+    int rc = query_tree(s, [&]() -> int {
+        const Bodies cur = s->buf[s->curbuf];
+        const int grid = nblocks(n), waves = (int)((n + kQueryBlock - 1) / kQueryBlock), node_grid = nblocks(s->own_node_rows);
+        const int64_t ntiles = (n + 1 + kScanTile - 1) / kScanTile;
+        k_pair_cells<<<node_grid, kBlock, 0, st>>>(s->nodes, s->node_ref, s->info, n, s->own_node_rows, s->q.pairs.cnt);
+        k_mst_init<<<grid, kBlock, 0, st>>>(s->info, n, s->perm, cur.id, parent, comp, g.rid, g.bd2, g.bpart, g.cmin, g.cpair);
+        if (int r = launch_failed("%s: a kernel launch failed", who)) return r;
+        // The loop ends when the tree is complete, after ceil(log2 n) rounds whatever the device says, and when a round
+        // appended nothing: the build did not fit (every kernel returned at once), which the caller's check reports.
+        while (c[1] < (unsigned long long)m && done < max_rounds) {
+            const unsigned long long before = c[1], evals_before = c[0];
+            const auto t0 = std::chrono::steady_clock::now();
+            k_mst_diff<<<grid, kBlock, 0, st>>>(s->info, n, comp, g.diff);
+            k_iscan_reduce<<<(unsigned)ntiles, kBlock, 0, st>>>(g.diff, n, 0, g.tiles, 0);
+            scan::k_scan_values<<<1, scan::kScanThreads, 0, st>>>(g.tiles, g.tiles, ntiles, (int64_t)0, 0, scan::Sum());
+            k_iscan_apply<<<(unsigned)ntiles, kBlock, 0, st>>>(g.diff, n, 0, g.tiles, 0, g.dscan);
+            k_mst_tags<<<node_grid, kBlock, 0, st>>>(s->node_ref, s->q.pairs.cnt, s->info, n, s->own_node_rows, comp, g.dscan, g.ctag);
+            with_bool(done > 0, [&](auto carry) {
+                k_mst_search<decltype(carry)::value><<<waves, kQueryBlock, 0, st>>>(
+                    s->nodes, s->q.shared.rows, s->node_ref, s->info, s->perm, cur, n, comp, g.rid, g.ctag, s->q.pairs.cnt, g.bd2, g.bpart,
+                    g.cmin, evals ? g.counters : nullptr);
+            });
+            k_mst_pick<<<grid, kBlock, 0, st>>>(s->info, n, comp, g.rid, g.bd2, g.bpart, g.cmin, g.cpair);
+            k_mst_emit<<<grid, kBlock, 0, st>>>(s->info, n, comp, g.rid, g.bd2, g.bpart, g.cmin, g.cpair, parent, g.e_pack, g.e_d2,
+                                                g.counters + 1);
+            k_mst_flatten<<<grid, kBlock, 0, st>>>(s->info, n, parent, comp, g.cmin, g.cpair);
+            if (int r = launch_failed("%s: a kernel launch failed", who)) return r;
+            NBMI_HIP_CHECK(hipMemcpyAsync(c, g.counters, sizeof(c), hipMemcpyDeviceToHost, st));
+            NBMI_HIP_CHECK(hipStreamSynchronize(st));
+            if (c[1] == before) break;
+            done++;
+            g.rounds.push_back({(int64_t)(c[0] - evals_before), (int64_t)(c[1] - before),
+                                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count()});
+        }
+        if (c[1] != (unsigned long long)m) return 0;
+        // the final order: two stable passes, by the packed indices, then by the bits of d2 (cmin / cpair are free now)
+        uint64_t *ka = (uint64_t *)g.cmin, *kb = (uint64_t *)g.cpair;
+        int idbits = 1;
+        while (idbits < 31 && ((int64_t)1 << idbits) < n) idbits++;
+        k_fof_iota<<<nblocks(m), kBlock, 0, st>>>(m, g.va);
+        NBMI_HIP_CHECK(nbmi::radix_sort_pairs_u64(g.sort_tmp, g.sort_bytes, (const uint64_t *)g.e_pack, ka, g.va, g.vb, (size_t)m, 0,
+                                                  32 + idbits, st));
+        k_mst_gather<<<nblocks(m), kBlock, 0, st>>>(m, g.vb, g.e_d2, kb);
+        NBMI_HIP_CHECK(nbmi::radix_sort_pairs_u64(g.sort_tmp, g.sort_bytes, kb, ka, g.vb, g.va, (size_t)m, 0, 63, st));
+        k_mst_out<<<nblocks(m), kBlock, 0, st>>>(m, g.va, ka, g.e_pack, o_i, o_j, o_d2);
+        if (int r = launch_failed("%s: a kernel launch failed", who)) return r;
+        return nbmi::radix_error_word(g.sort_tmp, &sort_err, st) == hipSuccess ? 0 : NBMI_ERR_HIP;
+    });
+    if (rc) return rc;
+    NBMI_HIP_CHECK(timed.end());
+    NBMI_HIP_CHECK(hipStreamSynchronize(st));
+    NBMI_HIP_CHECK(timed.add());
+    if (int r = check_device_error(s)) return r;  // the build's own capacity error, with a step's message
+    if (sort_err) {
+        NBMI_HIP_CHECK(nbmi::radix_init_temp(g.sort_tmp, st));
+        nbmi::set_error("%s: device radix sort: a look-back spin timed out", who);
+        return NBMI_ERR_HIP;
+    }
+    if (c[1] != (unsigned long long)m) {
+        nbmi::set_error("%s: %lld rounds left %llu of %lld edges", who, (long long)done, c[1], (long long)m);
+        return NBMI_ERR_HIP;
+    }
+    if (edge_i) NBMI_HIP_CHECK(hipMemcpyAsync(edge_i, o_i, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (edge_j) NBMI_HIP_CHECK(hipMemcpyAsync(edge_j, o_j, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (edge_d2) NBMI_HIP_CHECK(hipMemcpyAsync(edge_d2, o_d2, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, st));
+    NBMI_HIP_CHECK(hipStreamSynchronize(st));
+    if (rounds) *rounds = done;
+    if (evals) *evals = (int64_t)c[0];
+    return 0;
+}
+
+int nbmi_mst_rounds(nbmi_sim *s, int capacity, int64_t *evals, int64_t *edges, double *ms) {
+    if (int rc = check_handle(s)) return rc;
+    const auto &r = s->q.mst.rounds;
+    for (int k = 0; k < capacity && k < (int)r.size(); k++) {
+        if (evals) evals[k] = r[k].evals;
+        if (edges) edges[k] = r[k].edges;
+        if (ms) ms[k] = r[k].ms;
+    }
+    return (int)r.size();
 }
 
 int nbmi_deposit(nbmi_sim *s, const double *lo, const double *hi, const int32_t *dims, int scheme, int quantities,

@@ -57,6 +57,8 @@ PROTOTYPES = {
     "nbmi_fof": (C.c_int, [_vp, _dbl, _vp, _vp, _vp]),
     "nbmi_fof_catalogue": (C.c_int, [_vp, _dbl, _i64, _i64, _vp, _vp, _vp, _vp]),
     "nbmi_compute_group_colors": (C.c_int, [_vp, _dbl, _i64]),
+    "nbmi_mst": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "nbmi_mst_rounds": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "nbmi_pair_counts": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "nbmi_pair_counts_at": (C.c_int, [_vp, _i64, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "nbmi_field_at": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp]),

@@ -631,6 +631,33 @@ class _HIPSimulation:
         self._query_refuse(what)
         self._query_call(what, self._lib.nbmi_compute_group_colors(self._h, float(link), int(min_members)))
 
+    # ---- the minimum spanning tree (include/nbmi.h nbmi_mst; consumers in nbody/mst.py) ----
+    def minimum_spanning_tree(self, evals=False):
+        """(edges int32 (N - 1, 2), d2 float64 (N - 1,)): the Euclidean minimum spanning tree of the bodies under the
+        strict order (d2, i, j) on pairs - unique, exact, equal to a brute force - sorted ascending by that key, with
+        edges[k, 0] < edges[k, 1] in the caller's body order.  Cutting it at any link gives find_groups(link)
+        (``nbody.mst.cut``); ``evals=True`` returns (edges, d2, rounds, evals): also the Boruvka rounds run and the distances
+        the call evaluated.  Refused with ValueError where knn() is; the call does not change what the next step computes."""
+        what = "minimum_spanning_tree"
+        self._query_refuse(what)
+        m = max(self.n - 1, 0)
+        ei, ej = np.empty(m, dtype=np.int32), np.empty(m, dtype=np.int32)
+        d2 = np.empty(m, dtype=np.float64)
+        rounds, ev = C.c_int64(0), C.c_int64(0)
+        self._query_call(what, self._lib.nbmi_mst(self._h, _nat.ptr(ei), _nat.ptr(ej), _nat.ptr(d2), C.addressof(rounds),
+                                                C.addressof(ev) if evals else None))
+        edges = np.stack([ei, ej], axis=1)
+        return (edges, d2, int(rounds.value), int(ev.value)) if evals else (edges, d2)
+
+    def mst_rounds(self):
+        """The rounds of the last minimum_spanning_tree(), a measurement hook: a list of {"evals", "edges", "ms"} - the
+        distances the round evaluated (0 unless that call had ``evals=True``), the edges it appended and the host's wall
+        time for it."""
+        ev, ed, ms = np.zeros(64, dtype=np.int64), np.zeros(64, dtype=np.int64), np.zeros(64, dtype=np.float64)
+        k = self._lib.nbmi_mst_rounds(self._h, 64, _nat.ptr(ev), _nat.ptr(ed), _nat.ptr(ms))
+        _nat.check(min(k, 0), "nbmi_mst_rounds")
+        return [{"evals": int(ev[i]), "edges": int(ed[i]), "ms": float(ms[i])} for i in range(min(k, 64))]
+
     # ---- binned pair counts (include/nbmi.h nbmi_pair_counts; DESIGN.md section 4.16) ----
     def pair_counts(self, edges, evals=False):
         """(counts int64 (nb,), below int) for the nb + 1 ``edges`` (1 <= nb <= 64, finite, >= 0, strictly increasing):

@@ -318,6 +318,52 @@ int nbmi_fof_catalogue(nbmi_sim *sim, double link, int64_t min_members, int64_t 
                        int64_t *members, double *out13, int64_t *count);
 int nbmi_compute_group_colors(nbmi_sim *sim, double link, int64_t min_members);
 
+/* ---- the Euclidean minimum spanning tree of the bodies ---------------------------------------
+ * Every friends-of-friends partition at once: the groups at link b are the components left when the tree's edges longer
+ * than b are cut, and the N - 1 edge lengths are the merge heights of the single-linkage dendrogram (nbody/mst.py has the
+ * host-side consumers).  Of the handle's current float64 state, exactly:
+ *   d2(i, j)  as in nbmi_fof: (dx dx + dy dy) + dz dz with dx = x_j - x_i, float64 in this association, no FMA.  It is
+ *             symmetric in i and j bit for bit - a negated difference squares to the same value - and the search
+ *             evaluates it from either end.
+ *   order     the unordered pair {i, j} of caller indices, written with i < j, has the key (d2(i, j), i, j), compared
+ *             lexicographically: a strict total order on the N (N - 1) / 2 pairs, ties in d2 included.  A coincident pair
+ *             has d2 = 0 and is ordered by its indices.
+ *   the tree  the minimum spanning tree of the complete graph under that order.  It is unique: the edge set Kruskal's
+ *             algorithm accepts when it takes the pairs in that order, and equally what Prim's or Boruvka's gives when
+ *             every comparison uses that order.
+ *   output    the N - 1 edges sorted ascending by their key: edge_i[k] < edge_j[k] (int32, caller indices) and
+ *             edge_d2[k] = d2 of that pair.  Every value is independent of the key order of the state, of the order of
+ *             evaluation and of the handle's history; two calls return the same arrays.
+ * Consequences: the number of edges with edge_d2 <= link * link is N - n_groups of nbmi_fof(link), and the components of
+ * those edges are exactly nbmi_fof's groups, so the labels obtained from them (the smallest index of a component) equal
+ * nbmi_fof's array.
+ * edge_i, edge_j, edge_d2, rounds and evals may each be NULL.
+ *   *rounds   the number of Boruvka rounds run, at most ceil(log2 N): every round unites every component with at least
+ *             one other.
+ *   *evals    the number of d2 the call evaluated (a measurement hook like nbmi_fof's).  No wave reads what another
+ *             writes during a search, so it is a function of the state: two calls return the same number.
+ * N == 0 or 1: success, no edge is written, rounds = 0.
+ * Refused with NBMI_ERR_ARG, message "nbmi_mst: ...": the handles nbmi_knn refuses (direct N^2, owner mode, a proper
+ * shard).  NBMI_ERR_CAPACITY of the call's own tree build is reported with a step's message (seventy bodies at one
+ * position still do not fit).  Coordinates that are not finite leave bodies without a nearest foreign body: NBMI_ERR_HIP,
+ * "nbmi_mst: ... rounds left ...".
+ * Synchronous, like nbmi_pair_counts_at: errors of earlier steps are reported first, and the call returns with the arrays
+ * filled.  It changes nothing that a later step or query reads - state and order, the tree header, the "auto" precision
+ * flags, the step count, the stored leapfrog acceleration, the tracers.  Quadrupole and leapfrog handles return a plain
+ * handle's arrays.  With nbmi_enable_timers the time from the build's first kernel to the last write - the host's
+ * one 16-byte read per round included - goes to "other".
+ * The first call allocates 64 bytes per body, 4 bytes per node row, 4 bytes per 2 048 bodies and a radix sort buffer
+ * (about 12 bytes per body), and uses - allocating them if no earlier call has - nbmi_fof's 16 bytes per body,
+ * nbmi_pair_counts' 4 bytes per node row and (shared with nbmi_knn) 32 bytes per node row and 4 bytes per 64 bodies.  All
+ * of it is freed by nbmi_destroy. */
+int nbmi_mst(nbmi_sim *sim, int32_t *edge_i /* (N-1,), may be NULL */, int32_t *edge_j /* (N-1,), may be NULL */,
+             double *edge_d2 /* (N-1,), may be NULL */, int64_t *rounds /* may be NULL */, int64_t *evals /* may be NULL */);
+/* Measurement hook: the rounds of the handle's last nbmi_mst, oldest first, at most `capacity` of them into each array
+ * that is not NULL - the d2 evaluated in the round (0 if that call's evals was NULL), the edges it appended, and the
+ * host's wall time for it in ms (its kernels and the one read that ends it).  Returns the number of rounds (>= 0; 0
+ * before the first call), or a negative error for a bad handle. */
+int nbmi_mst_rounds(nbmi_sim *sim, int capacity, int64_t *evals, int64_t *edges, double *ms);
+
 /* ---- exact binned pair counts ---------------------------------------------------------------
  * Of the handle's current float64 state, exactly:
  *   d2(i, j)   as above: (dx dx + dy dy) + dz dz with dx = x_j - x_i, float64 in this association, no FMA.
